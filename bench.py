@@ -1,8 +1,12 @@
 #!/usr/bin/env python3
 """Headline benchmark: correlation-loss steps/sec at B=32, C=384, 28x28 (BASELINE.json `metric`).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 (for N > 1 launched by the driver through torch.distributed.run, one rank per GPU, RCCL).
+
+A plain run sets up, warms up, times exactly K steps, writes the last step's outputs with --dump-outputs and prints one JSON
+line.  --full adds the measurements that take runs of their own behind the timed steps: the fused kernel's roofline leg, the
+CPU baseline and, for N > 1, the exchange-stall and sync-all-reduce figures.
 
 A "step" = one forward + backward of the DepthG correlation loss, starting from the fp32 feature /
 code maps as the featurizer hands them over, resident in HBM:
@@ -96,6 +100,21 @@ def synth_inputs(B, seed, device, H=HEADLINE):
     d = torch.randint(0, 256, (B, 1, H["depth_hw"], H["depth_hw"]), generator=g).float()
     dp = torch.randint(0, 256, (B, 1, H["depth_hw"], H["depth_hw"]), generator=g).float()
     return [t.to(device) for t in (f, fp, c, cp, d, dp)]
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, outs):
+    """--dump-outputs: every tensor of `outs` as DIR/<name>.npy in float32, whole (C5, the largest, writes 56 MB)."""
+    import numpy as np
+    arrays = {k: v.detach().float().cpu().numpy() for k, v in outs.items()}
+    size = sum(a.nbytes for a in arrays.values())
+    if size > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"[bench] --dump-outputs: the step's outputs are {size} bytes, more than {DUMP_LIMIT_BYTES}")
+    os.makedirs(dirname, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(dirname, k + ".npy"), a)
 
 
 def algorithmic_gflop(B, P, C, D, n_neg):
@@ -370,7 +389,16 @@ def main():
     ap.add_argument("--ablate", choices=["", "noexchange", "onegraph", "streamwait", "twocalls", "torchmasks", "writefeats"], default="", help=argparse.SUPPRESS)
     ap.add_argument("--force-dist", action="store_true",
                     help="initialise torch.distributed (RCCL) and run the collective path even with one rank (self-test)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need, each after the timed steps: the roofline leg of the "
+                         "fused kernel (`roofline`), the CPU restatement (`cpu_baseline`, unless --no-cpu-baseline) and, for N > 1, "
+                         "the exchange stall and the sync-all-reduce step time (`dist`)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed (rank 0) as DIR/<name>.npy in float32: the fused loss vector "
+                         "(four loss means, four cd means, weighted total) and the gradients of the backward")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` without a launcher: THIS process never touches the GPU, it starts the N ranks itself
@@ -400,11 +428,6 @@ def main():
 
     conf = CONFIGS[args.config]
     H = conf["H"]
-    # the fused correlation kernel's workgroups stamp their entry / exit times (dg_prof_main_span) - also inside the replayed hipGraph,
-    # so the roofline leg below reads the kernel's execution span INSIDE steps, what a kernel trace shows, not a re-launch beside them
-    # (the timed steps run WITHOUT the stamps: the timer is armed only for a second recording of the step, made behind the timed
-    #  region, that the roofline leg replays - the pointer in force at capture time is baked into a hipGraph)
-    ktimer = ops.MainKernelTimer(dev)
     # ONE schedule for every N: the compute part of the step is replayed from a hipGraph (the eager step's Python side, 0.2 ms,
     # plus the collective's, 0.05-0.14 ms, would make the host the limit of a 0.3-ms step); N > 1 adds the collective on a side
     # stream and nothing else.  --eager / --sync-allreduce opt out (the JSON line says which schedule ran).
@@ -433,6 +456,16 @@ def main():
     seed_grad = torch.ones((), device=dev)   # d(total)/d(total): the upstream of the step, resident like the other inputs
     counter = [0]
 
+    def outputs(total):
+        """What a caller of the step receives: the weighted total, the fused loss vector (DG_OUT_* order) and the gradients of the
+        backward - when the step is captured, the graph's own tensors, which every replay rewrites."""
+        out = {"loss_total": total, "loss_scalars": loss_fn.last_scalars}
+        if head is None:
+            out["grad_code"], out["grad_code_pos"] = c.grad, cp.grad
+        else:
+            out.update(("grad_" + n.replace(".", "_"), prm.grad) for n, prm in head.named_parameters())
+        return out
+
     def compute_with_head(bucket=None):
         for prm in head_params:
             prm.grad = None
@@ -452,7 +485,7 @@ def main():
         total.backward(gradient=seed_grad)
         if bucket is not None:
             bucket.pack()                  # the real head gradients
-        return total
+        return outputs(total)
 
     def compute(bucket=None):
         if head is not None:
@@ -464,7 +497,7 @@ def main():
         total.backward(gradient=seed_grad)
         if bucket is not None:
             bucket.fill_from(c.grad)
-        return total
+        return outputs(total)
 
     def capture(fn):
         if os.environ.get("DG_BENCH_FAIL_CAPTURE"):      # (test hook: tests/test_gpu_configs.py drives the fall-back below)
@@ -504,20 +537,20 @@ def main():
     if not use_dist:
         captured = capture_or_die(compute) if graph_mode else None
         if captured is not None:
-            graph, total_static = captured
+            graph, out_static = captured
 
             def step():
                 graph.replay()
-                return total_static
+                return out_static
         else:
             step = compute
     elif args.sync_allreduce:
         exchange_mode = "every step, on the compute stream (which waits for it)"
 
         def step():
-            total = compute(buckets[0])
+            out = compute(buckets[0])
             buckets[0].allreduce_mean_(even_if_alone=args.force_dist)
-            return total
+            return out
     else:
         # The N > 1 schedule proper (depthg_amd.parallel.DoubleBufferedExchange; tests/test_dp_gloo.py drives the same class over
         # gloo with a stub compute): wait for the collective that read bucket k two steps ago -> the step's kernels, which end by
@@ -573,15 +606,24 @@ def main():
         clock_warmup_steps += 10
         torch.cuda.synchronize()
     sync()
+    # the step's random draws (the negatives' batch maps, the head's Dropout2d masks) start over behind the time-based clock warm-up,
+    # so that the last timed step draws the same in every run with the same arguments (--dump-outputs compares runs output for output)
+    if graph_mode:                                  # {seed, draws so far, ticket}: a fixed seed (torch's own is drawn per process)
+        loss_fn._graph_state(dev).copy_(torch.tensor([1234 + rank, 0, 0], dtype=torch.int64))
+    else:
+        torch.manual_seed(1234 + rank)              # the eager step draws from torch's generators
     for _ in range(args.warmup):
         step()
     sync()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        total = step()
+        out = step()
     host_elapsed = time.perf_counter() - t0     # the Python loop alone (enqueue side); equals `elapsed` when the host is the limit
     sync()
     elapsed = time.perf_counter() - t0
+    total = out["loss_total"]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out)
     dist_diag = None
     if use_dist:
         # what a first real N > 1 run needs to be read: every rank's own time (a slow rank, a straggling collective), how long the
@@ -595,7 +637,7 @@ def main():
                      "ms_per_step_min_rank": round(min(per_rank), 4), "ms_per_step_max_rank": round(max(per_rank), 4),
                      "ms_per_step_by_rank": [round(v, 4) for v in per_rank],
                      "host_ms_per_step_max_rank": round(max(float(t[1]) for t in every) / args.steps * 1e3, 4)}
-        if not args.sync_allreduce:
+        if args.full and not args.sync_allreduce:
             # device-side stall of the compute stream on `wait_exchange` (the collective of two steps ago), measured on extra,
             # untimed steps: events around the wait itself (every rank runs the same count: the collectives stay paired)
             nprobe, stall = 20, 0.0
@@ -632,126 +674,133 @@ def main():
     ms_per_step = elapsed / args.steps * 1e3
     value = world * args.steps / elapsed   # every rank completes `steps` steps of its own B=32 shard
 
-    # ---- roofline of the dominant kernel (the fused correlation launch), measured live with HIP events on the launch stream
-    desc, perms_t, ws = loss_fn.last_call
-    # The kernel's launch duration UNDER THE STEP'S CONDITIONS: [step + one extra launch of the fused kernel] minus [step], both
-    # timed with HIP events over `reps` iterations on the launch stream, five interleaved rounds, median.  (A bare loop of
-    # back-to-back re-launches keeps the matrix cores saturated, the chip lowers its clock, and the same kernel measures 5-6 %
-    # slower than rocprofv3's kernel trace shows it inside the step: 160 against 151 us, profiles/r03_SUMMARY.md.  `kernel_ms_loop`
-    # keeps that figure.)
-    reps = 20
-    ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+    roofline = None
+    if args.full:
+        # the fused correlation kernel's workgroups stamp their entry / exit times (dg_prof_main_span) - also inside the replayed hipGraph,
+        # so the roofline leg below reads the kernel's execution span INSIDE steps, what a kernel trace shows, not a re-launch beside them
+        # (the timed steps ran WITHOUT the stamps: the timer is armed only for a second recording of the step, made here, that the
+        #  roofline leg replays - the pointer in force at capture time is baked into a hipGraph)
+        ktimer = ops.MainKernelTimer(dev)
+        # ---- roofline of the dominant kernel (the fused correlation launch), measured live with HIP events on the launch stream
+        desc, perms_t, ws = loss_fn.last_call
+        # The kernel's launch duration UNDER THE STEP'S CONDITIONS: [step + one extra launch of the fused kernel] minus [step], both
+        # timed with HIP events over `reps` iterations on the launch stream, five interleaved rounds, median.  (A bare loop of
+        # back-to-back re-launches keeps the matrix cores saturated, the chip lowers its clock, and the same kernel measures 5-6 %
+        # slower than rocprofv3's kernel trace shows it inside the step: 160 against 151 us, profiles/r03_SUMMARY.md.  `kernel_ms_loop`
+        # keeps that figure.)
+        reps = 20
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
 
-    def timed(fn):
-        torch.cuda.synchronize()
-        ev[0].record()
-        for _ in range(reps):
-            fn()
-        ev[1].record()
-        torch.cuda.synchronize()
-        return ev[0].elapsed_time(ev[1]) / reps
+        def timed(fn):
+            torch.cuda.synchronize()
+            ev[0].record()
+            for _ in range(reps):
+                fn()
+            ev[1].record()
+            torch.cuda.synchronize()
+            return ev[0].elapsed_time(ev[1]) / reps
 
-    def step_plus_kernel():
-        warm()
-        ops.corr_relaunch_main(desc, perms_t, ws)
+        def step_plus_kernel():
+            warm()
+            ops.corr_relaunch_main(desc, perms_t, ws)
 
-    for _ in range(3):
-        ops.corr_relaunch_main(desc, perms_t, ws)
-    diffs = []
-    for _ in range(5):
-        t_step = timed(warm)
-        t_both = timed(step_plus_kernel)
-        diffs.append(t_both - t_step)
-    kern_ms_diff = sorted(diffs)[len(diffs) // 2]
-    kern_ms_loop = timed(lambda: ops.corr_relaunch_main(desc, perms_t, ws))
-    # the kernel inside the step: `reps` back-to-back steps, the span stamps reset in front of the LAST one and read behind it; 16 such
-    # samples, mean and spread.  This is the figure the committed rocprofv3 kernel trace of the same command reports as the kernel's
-    # average (minus the dispatch ramp) - `frac` is quoted on it.
-    ktimer.arm(True)
-    probe_graph = capture_or_die(compute) if graph_mode else None       # (kept alive to the end of main(): it writes to ktimer.span)
-    probe = (lambda: probe_graph[0].replay()) if probe_graph is not None else compute
-    in_step, held = [], []
-    for _ in range(16):
-        for _ in range(reps - 1):
+        for _ in range(3):
+            ops.corr_relaunch_main(desc, perms_t, ws)
+        diffs = []
+        for _ in range(5):
+            t_step = timed(warm)
+            t_both = timed(step_plus_kernel)
+            diffs.append(t_both - t_step)
+        kern_ms_diff = sorted(diffs)[len(diffs) // 2]
+        kern_ms_loop = timed(lambda: ops.corr_relaunch_main(desc, perms_t, ws))
+        # the kernel inside the step: `reps` back-to-back steps, the span stamps reset in front of the LAST one and read behind it; 16 such
+        # samples, mean and spread.  This is the figure the committed rocprofv3 kernel trace of the same command reports as the kernel's
+        # average (minus the dispatch ramp) - `frac` is quoted on it.
+        ktimer.arm(True)
+        probe_graph = capture_or_die(compute) if graph_mode else None       # (kept alive to the end of main(): it writes to ktimer.span)
+        probe = (lambda: probe_graph[0].replay()) if probe_graph is not None else compute
+        in_step, held = [], []
+        for _ in range(16):
+            for _ in range(reps - 1):
+                probe()
+            ktimer.reset()
             probe()
-        ktimer.reset()
-        probe()
-        ms, ghz = ktimer.last()
-        in_step.append(ms)
-        held.append(ghz)
-    # the same 20 steps with and without the stamps (what the instrumentation costs the step; the timed region above ran without)
-    t_probe = timed(probe)
-    ktimer.arm(False)
-    t_plain = timed(warm)
-    held = [v for v in held if v == v and v > 0.0]
-    held_ghz = sum(held) / len(held) if held else None
-    in_step = [v for v in in_step if v == v and v > 0.0]
-    kern_ms = sum(in_step) / len(in_step) if in_step else kern_ms_diff
-    kern_method = ("span of the kernel's workgroups (entry / exit stamps of the GPU's 100-MHz clock, atomic min / max) inside the "
-                   + ("replayed" if graph_mode else "host-launched") + " step, last of 20 back-to-back steps, mean of 16 samples"
-                   if in_step else "HIP events: [step + 1 extra launch] - [step], 5 x 20 iterations, median (no span stamps were read)")
-    step_gf, main_gf, gs_gf = algorithmic_gflop(H["B"], H["S"] ** 2, H["C"], H["D"], H["n_neg"])
-    # k_corr2's FOLD: the fused launch also forms the intra pair-set's streamed-side gradient (one correlation with K = D of the
-    # reference's work, by symmetry and one extra MFMA per chain) - that share moves from the k_gs launch to this one
-    intra_folded = ops.corr_intra_folded(desc)
-    if intra_folded:
-        share = 2.0 * H["B"] * (H["S"] ** 2) ** 2 * H["D"] / 1e9
-        main_gf += share
-        gs_gf -= share
-    # which kernel that launch is: the library's own predicate (dg_corr_main_kernel_name), not a copy of it
-    kname = ops.corr_main_kernel_name(desc)
-    # exact clamp masks on the dense grid: k_corr2's exact-mask form has NO cd chain (round 6) - the mask words come from k_cd_mask3,
-    # which forms every cd in split fp16 (three times the MFMAs of the chain) - so the (2 + n) code correlations of the forward are
-    # not the fused launch's work any more: they leave its algorithmic flops (nothing is credited for k_cd_mask3's recomputation)
-    cd_outside = bool(args.exact_masks) and kname == "k_corr2" and H["S"] ** 2 > 160
-    if cd_outside:
-        main_gf -= (2 + H["n_neg"]) * 2.0 * H["B"] * (H["S"] ** 2) ** 2 * H["D"] / 1e9
-    achieved = main_gf / 1e3 / (kern_ms / 1e3)   # TFLOP/s of the fused kernel alone
-    # HBM bytes per launch of that kernel: counters cannot be read from inside a run, so this is the figure of the committed PMC
-    # passes of THIS round (scripts/profile_round.sh: FETCH_SIZE x2 on gfx950 + WRITE_SIZE) - null when there is none
-    traffic, traffic_source = None, None
-    if args.config == "headline":
-        src = next((c for c in (os.path.join("profiles", f"r0{r}_pmc_per_launch.json") for r in (6, 5, 4))
-                    if os.path.exists(os.path.join(ROOT, c))), os.path.join("profiles", "r04_pmc_per_launch.json"))
-        try:
-            pmc = json.load(open(os.path.join(ROOT, src)))
-            for name, vals in pmc.items():
-                if kname in name and "hbm_traffic_bytes_per_launch" in vals:
-                    traffic, traffic_source = float(vals["hbm_traffic_bytes_per_launch"]), src
-        except (OSError, ValueError):
-            pass
-    roofline = {"bound": "mfma", "achieved": round(achieved, 2), "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s",
-                "frac": round(achieved / PEAK_BF16_TFLOPS, 4), "traffic": traffic, "traffic_source": traffic_source,
-                "kernel": kname, "kernel_ms": round(kern_ms, 4),
-                "kernel_ms_min": round(min(in_step), 4) if in_step else None, "kernel_ms_max": round(max(in_step), 4) if in_step else None,
-                "kernel_ms_diff": round(kern_ms_diff, 4), "kernel_ms_loop": round(kern_ms_loop, 4),
-                "kernel_ms_method": kern_method + "; kernel_ms_diff: [step + 1 extra launch] - [step], 5 x 20 iterations, median; "
-                                    "kernel_ms_loop: 20 back-to-back re-launches",
-                "algorithmic_gflop_per_launch": round(main_gf, 2), "algorithmic_gflop_per_step": round(step_gf, 2),
-                "intra_folded": bool(intra_folded), "cd_in_mask_kernel": cd_outside,
-                # the shader clock the kernel's CUs held while they ran it (sum of the workgroups' s_memtime cycles / sum of their
-                # 100-MHz wall ticks, same 16 in-step samples as kernel_ms) and the fraction of the peak AT THAT CLOCK: the
-                # 2.5-PFLOP/s peak is 1024 SIMDs x 1024 flop/cycle at 2.4 GHz.  Box-to-box differences of `frac` with equal
-                # cycles per launch are differences of this clock (power management), not of the kernel
-                "held_clock_ghz": round(held_ghz, 4) if held_ghz else None,
-                "frac_at_held_clock": round(achieved / PEAK_BF16_TFLOPS * PEAK_CLOCK_GHZ / held_ghz, 4) if held_ghz else None,
-                "kernel_mcycles": round(kern_ms * 1e-3 * held_ghz * 1e9 / 1e6, 3) if held_ghz else None,
-                "stamps_cost_ms_per_step": round(t_probe - t_plain, 5)}
+            ms, ghz = ktimer.last()
+            in_step.append(ms)
+            held.append(ghz)
+        # the same 20 steps with and without the stamps (what the instrumentation costs the step; the timed region above ran without)
+        t_probe = timed(probe)
+        ktimer.arm(False)
+        t_plain = timed(warm)
+        held = [v for v in held if v == v and v > 0.0]
+        held_ghz = sum(held) / len(held) if held else None
+        in_step = [v for v in in_step if v == v and v > 0.0]
+        kern_ms = sum(in_step) / len(in_step) if in_step else kern_ms_diff
+        kern_method = ("span of the kernel's workgroups (entry / exit stamps of the GPU's 100-MHz clock, atomic min / max) inside the "
+                       + ("replayed" if graph_mode else "host-launched") + " step, last of 20 back-to-back steps, mean of 16 samples"
+                       if in_step else "HIP events: [step + 1 extra launch] - [step], 5 x 20 iterations, median (no span stamps were read)")
+        step_gf, main_gf, gs_gf = algorithmic_gflop(H["B"], H["S"] ** 2, H["C"], H["D"], H["n_neg"])
+        # k_corr2's FOLD: the fused launch also forms the intra pair-set's streamed-side gradient (one correlation with K = D of the
+        # reference's work, by symmetry and one extra MFMA per chain) - that share moves from the k_gs launch to this one
+        intra_folded = ops.corr_intra_folded(desc)
+        if intra_folded:
+            share = 2.0 * H["B"] * (H["S"] ** 2) ** 2 * H["D"] / 1e9
+            main_gf += share
+            gs_gf -= share
+        # which kernel that launch is: the library's own predicate (dg_corr_main_kernel_name), not a copy of it
+        kname = ops.corr_main_kernel_name(desc)
+        # exact clamp masks on the dense grid: k_corr2's exact-mask form has NO cd chain (round 6) - the mask words come from k_cd_mask3,
+        # which forms every cd in split fp16 (three times the MFMAs of the chain) - so the (2 + n) code correlations of the forward are
+        # not the fused launch's work any more: they leave its algorithmic flops (nothing is credited for k_cd_mask3's recomputation)
+        cd_outside = bool(args.exact_masks) and kname == "k_corr2" and H["S"] ** 2 > 160
+        if cd_outside:
+            main_gf -= (2 + H["n_neg"]) * 2.0 * H["B"] * (H["S"] ** 2) ** 2 * H["D"] / 1e9
+        achieved = main_gf / 1e3 / (kern_ms / 1e3)   # TFLOP/s of the fused kernel alone
+        # HBM bytes per launch of that kernel: counters cannot be read from inside a run, so this is the figure of the committed PMC
+        # passes of THIS round (scripts/profile_round.sh: FETCH_SIZE x2 on gfx950 + WRITE_SIZE) - null when there is none
+        traffic, traffic_source = None, None
+        if args.config == "headline":
+            src = next((c for c in (os.path.join("profiles", f"r0{r}_pmc_per_launch.json") for r in (6, 5, 4))
+                        if os.path.exists(os.path.join(ROOT, c))), os.path.join("profiles", "r04_pmc_per_launch.json"))
+            try:
+                pmc = json.load(open(os.path.join(ROOT, src)))
+                for name, vals in pmc.items():
+                    if kname in name and "hbm_traffic_bytes_per_launch" in vals:
+                        traffic, traffic_source = float(vals["hbm_traffic_bytes_per_launch"]), src
+            except (OSError, ValueError):
+                pass
+        roofline = {"bound": "mfma", "achieved": round(achieved, 2), "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s",
+                    "frac": round(achieved / PEAK_BF16_TFLOPS, 4), "traffic": traffic, "traffic_source": traffic_source,
+                    "kernel": kname, "kernel_ms": round(kern_ms, 4),
+                    "kernel_ms_min": round(min(in_step), 4) if in_step else None, "kernel_ms_max": round(max(in_step), 4) if in_step else None,
+                    "kernel_ms_diff": round(kern_ms_diff, 4), "kernel_ms_loop": round(kern_ms_loop, 4),
+                    "kernel_ms_method": kern_method + "; kernel_ms_diff: [step + 1 extra launch] - [step], 5 x 20 iterations, median; "
+                                        "kernel_ms_loop: 20 back-to-back re-launches",
+                    "algorithmic_gflop_per_launch": round(main_gf, 2), "algorithmic_gflop_per_step": round(step_gf, 2),
+                    "intra_folded": bool(intra_folded), "cd_in_mask_kernel": cd_outside,
+                    # the shader clock the kernel's CUs held while they ran it (sum of the workgroups' s_memtime cycles / sum of their
+                    # 100-MHz wall ticks, same 16 in-step samples as kernel_ms) and the fraction of the peak AT THAT CLOCK: the
+                    # 2.5-PFLOP/s peak is 1024 SIMDs x 1024 flop/cycle at 2.4 GHz.  Differences of `frac` between GPUs with equal
+                    # cycles per launch are differences of this clock (power management), not of the kernel
+                    "held_clock_ghz": round(held_ghz, 4) if held_ghz else None,
+                    "frac_at_held_clock": round(achieved / PEAK_BF16_TFLOPS * PEAK_CLOCK_GHZ / held_ghz, 4) if held_ghz else None,
+                    "kernel_mcycles": round(kern_ms * 1e-3 * held_ghz * 1e9 / 1e6, 3) if held_ghz else None,
+                    "stamps_cost_ms_per_step": round(t_probe - t_plain, 5)}
 
-    if H["S"] ** 2 <= 160:
-        # Sample grids of <= 160 positions (configs 2-4: every recipe the reference ships): the step is a few MB of MFMA work behind
-        # samplers that read the whole maps - bytes and launch latencies, not flops.  The yardstick is HBM: the bytes that MUST move
-        # (the four maps and the depth maps read once, the two code gradients written once) over the step time, against 8 TB/s.  The
-        # fused kernel's MFMA figures stay on the line as `mfma_*` (they say how little of the step the contraction is).
-        nmaps = H["B"] * H["h"] * H["w"] * 4.0
-        depth_b = H["B"] * float(H["depth_hw"]) ** 2 * 4.0
-        compulsory = 2 * nmaps * H["C"] + 2 * nmaps * H["D"] + 2 * nmaps * H["D"] + (2 if conf["sampling"] == "fps" else 1) * depth_b
-        hbm = compulsory / (ms_per_step * 1e-3) / 1e9
-        roofline = {"bound": "hbm", "achieved": round(hbm, 1), "peak": PEAK_HBM_GBPS, "unit": "GB/s", "frac": round(hbm / PEAK_HBM_GBPS, 4),
-                    "traffic": None, "compulsory_bytes_per_step": int(compulsory),
-                    "what": "compulsory bytes of one step (feats + code maps and the depth maps read once, d/d code and d/d code_pos written "
-                            "once) / ms_per_step; the step's kernels also write and re-read the sampled rows (a design choice, not counted)",
-                    "mfma": roofline}
+        if H["S"] ** 2 <= 160:
+            # Sample grids of <= 160 positions (configs 2-4: every recipe the reference ships): the step is a few MB of MFMA work behind
+            # samplers that read the whole maps - bytes and launch latencies, not flops.  The yardstick is HBM: the bytes that MUST move
+            # (the four maps and the depth maps read once, the two code gradients written once) over the step time, against 8 TB/s.  The
+            # fused kernel's MFMA figures stay on the line as `mfma_*` (they say how little of the step the contraction is).
+            nmaps = H["B"] * H["h"] * H["w"] * 4.0
+            depth_b = H["B"] * float(H["depth_hw"]) ** 2 * 4.0
+            compulsory = 2 * nmaps * H["C"] + 2 * nmaps * H["D"] + 2 * nmaps * H["D"] + (2 if conf["sampling"] == "fps" else 1) * depth_b
+            hbm = compulsory / (ms_per_step * 1e-3) / 1e9
+            roofline = {"bound": "hbm", "achieved": round(hbm, 1), "peak": PEAK_HBM_GBPS, "unit": "GB/s", "frac": round(hbm / PEAK_HBM_GBPS, 4),
+                        "traffic": None, "compulsory_bytes_per_step": int(compulsory),
+                        "what": "compulsory bytes of one step (feats + code maps and the depth maps read once, d/d code and d/d code_pos written "
+                                "once) / ms_per_step; the step's kernels also write and re-read the sampled rows (a design choice, not counted)",
+                        "mfma": roofline}
     if rank == 0:
         line = {
             "metric": "correlation-loss steps/sec at B=32,C=384,28x28 (fwd+bwd, per-GPU batch 32)" if args.config == "headline"
@@ -770,11 +819,12 @@ def main():
                        "allreduce_elems": HEAD_GRAD_ELEMS if use_dist else 0,
                        "allreduce": exchange_mode},
             "loss_total": float(total.detach()),
-            "roofline": roofline,
         }
+        if roofline is not None:
+            line["roofline"] = roofline
         if dist_diag:
             line["dist"] = dist_diag
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(conf)
     if use_dist:
         dist.destroy_process_group()

@@ -2,8 +2,8 @@
 # configs 2-4 with the fused small-grid kernel and with the multi-launch path of round 4 (DG_SMALL_PATH=0), + per-kernel times
 out=gpurun_out/$1; mkdir -p $out
 for c in C2 C3 C4shard; do
-  python bench.py --config $c --steps 200 --warmup 20 --no-cpu-baseline > $out/bench_$c.json 2> $out/bench_$c.err
-  DG_SMALL_PATH=0 python bench.py --config $c --steps 200 --warmup 20 --no-cpu-baseline > $out/bench_${c}_old.json 2> $out/bench_${c}_old.err
+  python bench.py --config $c --steps 200 --warmup 20 --full --no-cpu-baseline > $out/bench_$c.json 2> $out/bench_$c.err
+  DG_SMALL_PATH=0 python bench.py --config $c --steps 200 --warmup 20 --full --no-cpu-baseline > $out/bench_${c}_old.json 2> $out/bench_${c}_old.err
   python - <<PY
 import json
 for tag in ("", "_old"):

@@ -6,7 +6,7 @@ export TMPDIR=/tmp
 out=/root/repo/gpurun_out/$tag
 mkdir -p $out
 [ -n "$2" ] && export DEPTHG_LIB=$2
-python3 /root/repo/bench.py --config headline+head --no-cpu-baseline 2>/dev/null | tail -1 | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print('step ms', d['ms_per_step'], 'held GHz', d['roofline'].get('held_clock_ghz'))" > $out/step.txt
+python3 "$(dirname "$0")/../../bench.py" --config headline+head --full --no-cpu-baseline 2>/dev/null | tail -1 | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print('step ms', d['ms_per_step'], 'held GHz', d['roofline'].get('held_clock_ghz'))" > $out/step.txt
 ( cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -- python3 /root/repo/bench.py --config headline+head --steps 50 --warmup 5 --clock-warmup-s 0.25 --no-cpu-baseline > /dev/null 2>&1 )
 python3 - <<PY
 import csv, glob

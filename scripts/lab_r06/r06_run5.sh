@@ -4,8 +4,8 @@ out=gpurun_out/r06_run5; mkdir -p $out
 python -m pytest tests -x -q -m gpu > $out/gputests.txt 2>&1; echo "pytest rc $?" >> $out/gputests.txt
 tail -3 $out/gputests.txt
 for i in 1 2; do for c in C2 C4shard C3; do
-python bench.py --steps 100 --warmup 5 --no-cpu-baseline --config $c > $out/bench_${c}_overlap_$i.json 2> $out/bench_${c}_overlap_$i.err
-DG_BENCH_NO_FPS_OVERLAP=1 python bench.py --steps 100 --warmup 5 --no-cpu-baseline --config $c > $out/bench_${c}_plain_$i.json 2> $out/bench_${c}_plain_$i.err
+python bench.py --steps 100 --warmup 5 --full --no-cpu-baseline --config $c > $out/bench_${c}_overlap_$i.json 2> $out/bench_${c}_overlap_$i.err
+DG_BENCH_NO_FPS_OVERLAP=1 python bench.py --steps 100 --warmup 5 --full --no-cpu-baseline --config $c > $out/bench_${c}_plain_$i.json 2> $out/bench_${c}_plain_$i.err
 done; done
 for f in $out/bench_*.json; do python - <<PY
 import json

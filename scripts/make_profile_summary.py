@@ -18,12 +18,12 @@ br = json.loads(open(os.path.join(dst, f"{tag}_bench_under_rocprofv3.json")).rea
 kname = b["roofline"]["kernel"]
 rows = [r for r in st if r["Name"].startswith(("k_", "void k_"))]
 o = [f"# Round profile summary {tag} (MI355X, gfx950)\n",
-     "Command: `python bench.py --steps 50 --warmup 5 --no-cpu-baseline` (hipGraph replay, 1 s of untimed clock warm-up) under `rocprofv3 --kernel-trace --stats` "
+     "Command: `python bench.py --steps 50 --warmup 5 --full --no-cpu-baseline` (hipGraph replay, 1 s of untimed clock warm-up) under `rocprofv3 --kernel-trace --stats` "
      f"(`scripts/profile_round.sh {tag}`); PMC passes (`--pmc FETCH_SIZE`, `--pmc WRITE_SIZE`, an SQ set) are separate runs of the "
      f"same command with `--steps 3`. Files: `{tag}_kernel_stats.csv`, `{tag}_pmc_per_launch.json`, `{tag}_bench_under_rocprofv3.json` "
-     f"(the bench line printed inside the profiled run), `{tag}_bench.json` (the plain `python bench.py` line, taken BEFORE the counter "
+     f"(the bench line printed inside the profiled run), `{tag}_bench.json` (the `python bench.py --full` line, taken BEFORE the counter "
      "passes: counter collection leaves the GPU in the profiling power state, a plain run right behind the PMC passes measures low), "
-     f"`{tag}_bench_<config>.json` (`python bench.py --config <config>` for BASELINE.json's other configurations).\n",
+     f"`{tag}_bench_<config>.json` (`python bench.py --full --config <config>` for BASELINE.json's other configurations).\n",
      "## Kernels of one headline step\n", "| kernel | calls | avg µs | min µs | max µs |\n|---|---|---|---|---|"]
 tail = 0.0
 for r in rows:

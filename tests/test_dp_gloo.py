@@ -83,8 +83,14 @@ def test_two_rank_allreduce_matches_mean_of_shard_gradients():
     mgr = mp.Manager()
     ret = mgr.dict()
     mp.spawn(_worker, args=(world, _free_port(), ret), nprocs=world, join=True)
-    want_w = sum(_shard_grads(r, world)[0] for r in range(world)) / world
-    want_b = sum(_shard_grads(r, world)[1] for r in range(world)) / world
+    # the shard gradients at the ranks' thread count (_worker): the host's CPU kernels sum in another order at another count
+    nthreads = torch.get_num_threads()
+    torch.set_num_threads(1)
+    try:
+        want_w = sum(_shard_grads(r, world)[0] for r in range(world)) / world
+        want_b = sum(_shard_grads(r, world)[1] for r in range(world)) / world
+    finally:
+        torch.set_num_threads(nthreads)
     assert ret["same"]
     assert ret["numel"] == D * C + D
     assert torch.allclose(ret["w"], want_w, rtol=1e-6, atol=1e-9)

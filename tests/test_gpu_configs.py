@@ -452,8 +452,8 @@ def test_bench_line_of_the_multi_gpu_schedule():
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", MASTER_ADDR="127.0.0.1", MASTER_PORT="29691")
     lines = {}
     for mode in ("--force-dist", "--graph", "--eager"):
-        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), mode, "--steps", "4", "--warmup", "2", "--no-cpu-baseline",
-                            "--clock-warmup-s", "0.05"],
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), mode, "--steps", "4", "--warmup", "2", "--full",
+                            "--no-cpu-baseline", "--clock-warmup-s", "0.05"],
                            capture_output=True, text=True, timeout=600, env=env)
         assert r.returncode == 0, r.stderr[-3000:]
         last = r.stdout.strip().splitlines()[-1]
@@ -480,7 +480,8 @@ def test_bench_reports_a_failed_graph_capture_and_times_the_eager_step():
     under the N > 1 schedule; --strict-graph turns it into exit code 3."""
     import json
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", MASTER_ADDR="127.0.0.1", MASTER_PORT="29693", DG_BENCH_FAIL_CAPTURE="1")
-    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--clock-warmup-s", "0.02"]
+    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline", "--clock-warmup-s",
+            "0.02"]
     for extra in ([], ["--force-dist"]):
         r = subprocess.run(base + extra, capture_output=True, text=True, timeout=600, env=env)
         assert r.returncode == 0, r.stderr[-3000:]
@@ -489,6 +490,34 @@ def test_bench_reports_a_failed_graph_capture_and_times_the_eager_step():
         assert "hipGraph capture failed on rank 0" in r.stderr and d["ms_per_step"] > 0 and d["roofline"]["kernel"] == "k_corr2"
     r = subprocess.run(base + ["--strict-graph"], capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode == 3 and not r.stdout.strip().startswith("{")
+
+
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """A plain run (no --full) times exactly --steps steps and measures nothing else: no roofline leg, no CPU baseline.
+    --dump-outputs writes the last timed step's loss vector and gradients in float32; two runs with the same arguments but
+    different clock warm-ups (a different number of untimed steps ahead of the draws) write the same arrays."""
+    import json
+    dumps, lines = [], []
+    for i, clock in enumerate(("0.05", "0.3")):
+        out = tmp_path / f"run{i}"
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2",
+                            "--clock-warmup-s", clock, "--dump-outputs", str(out)], capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        d = json.loads(r.stdout.strip().splitlines()[-1])
+        lines.append(d)
+        assert d["steps"] == 5 and d["warmup"] == 2 and d["ms_per_step"] > 0 and d["unit"] == "steps/s"
+        assert abs(d["value"] - 1e3 / d["ms_per_step"]) < 1e-2 * d["value"]
+        assert "roofline" not in d and "cpu_baseline" not in d
+        dumps.append({f.stem: np.load(f) for f in out.glob("*.npy")})
+    a, b = dumps
+    assert sorted(a) == ["grad_code", "grad_code_pos", "loss_scalars", "loss_total"]
+    assert a["grad_code"].shape == (32, 70, 28, 28) and a["loss_scalars"].shape == (9,)
+    assert all(v.dtype == np.float32 for v in a.values()) and sum(v.nbytes for v in a.values()) <= 64 << 20
+    assert lines[0]["config"]["clock_warmup_steps"] != lines[1]["config"]["clock_warmup_steps"]
+    assert abs(float(a["loss_total"]) - lines[0]["loss_total"]) <= 1e-6 * abs(lines[0]["loss_total"])
+    assert float(a["loss_scalars"][8]) == float(a["loss_total"])
+    for k in a:
+        assert np.isfinite(a[k]).all() and np.allclose(a[k], b[k], rtol=1e-5, atol=1e-6 * float(np.abs(a[k]).max())), k
 
 
 _WALK_CHILD = r"""
