@@ -59,12 +59,7 @@ struct Plan {
     size_t total;
 };
 
-// developer A/B: DG_SMALL_PATH=0 keeps the multi-launch small-grid path of rounds 2-4 (needs C <= 768)
 #define FOLD_STASH_OFF (5 * 1024)        // k_corr2<24, 6, 5>: code k-step 5 of the C part (channels 80 .. 95: padding for D <= 80)
-static bool small_path_enabled() {
-    static const bool on = [] { const char* e = getenv("DG_SMALL_PATH"); return !(e && e[0] == '0'); }();
-    return on;
-}
 
 static void clamp_bounds(const dg_corr_desc* d, float& lo, float& hi);
 static int make_plan(const dg_corr_desc* d, Plan& p) {
@@ -89,7 +84,7 @@ static int make_plan(const dg_corr_desc* d, Plan& p) {
     // Sample grids of at most 160 positions (every recipe the reference ships: feature_samples = 11 / 12) take the fused small-grid
     // kernel, which streams the feature channels in chunks and so has no width limit (FeaturePyramidNet: 2048).  The blob kernels
     // (larger grids, the identity grid) hold whole channel vectors in registers / LDS: C <= 768 there.
-    p.small = !(d->flags & DG_IDENTITY_GRID) && dg_small_supported(p.Ppad, p.KD) && small_path_enabled();
+    p.small = !(d->flags & DG_IDENTITY_GRID) && dg_small_supported(p.Ppad, p.KD);
     p.nsplit = p.Ppad == 160 ? 2 : 1;
     if (d->C > 768 && !p.small)
         return fail(DG_ERR_UNSUPPORTED, "C=%d > 768 feature channels are supported on sample grids of at most 160 positions "
@@ -148,9 +143,6 @@ static int make_plan(const dg_corr_desc* d, Plan& p) {
     // exact clamp masks: gradient passes of the zero_clamp recipe on small sample grids (fp32 sampled rows exist, <= 8 tiles, the
     // one-wave-per-SIMD form of k_corr_main)
     p.xmask = p.rows && !p.small && p.grad && (d->flags & DG_ZERO_CLAMP) && !(d->flags & DG_STABALIZE) && p.Ppad <= 256 && p.rf == 4;
-#ifdef DG_NO_XMASK      // developer A/B: the fp16 masks everywhere
-    p.xmask = false;
-#endif
     // DG_EXACT_MASKS: the dense identity grid at the widths of the one-wave-per-SIMD kernel (dg_corr2.hip) takes the same mask words,
     // computed from channel-last fp32 copies of the two code maps (the workspace's nhwc_c regions, otherwise unused on this grid)
     p.xmask_dense = (d->flags & DG_EXACT_MASKS) && p.ident && p.grad && (d->flags & DG_ZERO_CLAMP) && !(d->flags & DG_STABALIZE) &&
@@ -160,7 +152,7 @@ static int make_plan(const dg_corr_desc* d, Plan& p) {
                                         "identity grid with C <= 384 (padded to 384), D <= 80, P >= 160, B <= 64, zero_clamp without stabalize");
     for (int t = 0; t < p.T; ++t) p.maskbits[t] = take((p.xmask || p.xmask_dense) ? B * (size_t)(p.Ppad / 32) * p.Ppad * 4 : 0);
     // FOLD: gradient passes of the pointwise recipe that k_corr2 runs (dg_corr2_shape_supported: the launcher's own predicate; the
-    // job-level conditions - stationary = operand 1, G tiles wanted, no batch map on R - hold for every gradient pass); DG_FOLD_INTRA=0 keeps the k_gs job (developer A/B)
+    // job-level conditions - stationary = operand 1, G tiles wanted, no batch map on R - hold for every gradient pass); DG_FOLD_INTRA=0 keeps the k_gs job (test seam, dg_common.h)
     {
         static const bool fold_on = [] { const char* e = getenv("DG_FOLD_INTRA"); return !(e && e[0] == '0'); }();
         float lo, hi;
@@ -171,12 +163,11 @@ static int make_plan(const dg_corr_desc* d, Plan& p) {
     // fp16 gradient tiles (round 6): the identity grid's backward is ONE launch (k_combine_out) that reads the raw tiles of k_corr2 and the
     // streamed-side tiles of k_gs once - 93 of the headline step's 1342 MB go with fp32 -> fp16 (both producers bounded: the raw tiles by
     // construction, k_gs's by leaving the division by ||c|| to the consumer).  Where k_corr2 runs and k_combine_out will (its routed list
-    // holds n_neg x B entries at most 512); DG_HALF_TILES=0 keeps fp32 tiles (developer A/B)
+    // holds n_neg x B entries at most 512)
     {
-        static const bool half_on = [] { const char* e = getenv("DG_HALF_TILES"); return !(e && e[0] == '0'); }();
         float lo, hi;
         clamp_bounds(d, lo, hi);
-        p.half = half_on && p.ident && p.grad && !p.small && dg_corr2_shape_supported(p.KF, p.KD, p.D, lo, hi, p.Ppad, p.B) &&
+        p.half = p.ident && p.grad && !p.small && dg_corr2_shape_supported(p.KF, p.KD, p.D, lo, hi, p.Ppad, p.B) &&
                  p.N * p.B <= 512 && p.S == p.h && p.S == p.w;
     }
     for (int i = 0; i < 2; ++i) p.clo[i] = take((p.xmask_dense && p.pointwise) ? B * (size_t)(p.Ppad / 32) * p.KD * 64 : 0);
@@ -274,9 +265,6 @@ static SideStream* side_stream_for(hipStream_t caller) {
     static std::map<int, SideStream> table;
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess) return nullptr;
-#ifdef DG_DEVTOOLS
-    if (const char* e = getenv("DG_SIDE_STREAM")) if (e[0] == '0') return nullptr;       // (developer A/B: every call launches in sequence)
-#endif
     std::lock_guard<std::mutex> lk(mu);
     auto it = table.find(dev);
     if (it != table.end()) return &it->second;
@@ -405,7 +393,6 @@ static int build_corr_jobs(const Plan& p, const dg_corr_desc* desc, char* ws, co
     // key.  Worth it when the ragged row block is short (at most 4 of the 8 row tiles) and several pair-sets share an array
     // (shared coordinates: intra + the negatives stream operand 0 through batch maps).
     a.gr_list = nullptr;
-#ifndef DG_NO_GROUP          // (developer A/B: scripts/build_variant.sh with SRC=dg_api)
     {
         const int nt = p.Ppad / 32, L = nt % 8;
         if (p.grad && p.KF == 384 && p.KD == 96 && p.D <= 80 && p.nrb > 1 && L >= 1 && L <= 4 && p.B % 8 == 0 && p.B <= 64 && njA >= 2) {
@@ -433,7 +420,6 @@ static int build_corr_jobs(const Plan& p, const dg_corr_desc* desc, char* ws, co
             }
         }
     }
-#endif
     return njA;
 }
 
@@ -451,7 +437,7 @@ static hipError_t launch_main(const Plan& p, const DgCorrArgs& a, int njA, int d
 
 struct DrawArgs { int64_t* out; uint64_t seed; unsigned long long* state; };
 
-// (DG_SPLIT_MASKS=0: the exact-mask chain of the dense grid in sequence on the caller's stream, developer A/B)
+// (DG_SPLIT_MASKS=0: the exact-mask chain of the dense grid in sequence on the caller's stream; test seam, dg_common.h)
 static bool split_masks_enabled() {
     static const bool on = [] { const char* e = getenv("DG_SPLIT_MASKS"); return !(e && e[0] == '0'); }();
     return on;
@@ -1323,9 +1309,6 @@ static HeadPlan head_plan(int32_t B, int32_t C, int32_t D, int32_t P) {
     auto take = [&](size_t bytes) { size_t o = off; off += up(bytes, 256); return o; };
     // cluster2: d W2a and d W1 share the feature operand and one launch (same splits); cluster1 alone (linear head): d W1 by itself
     h.s2a = head_splits(B, C, C, P, D); h.s1 = head_splits(B, D, C, P); h.s2b = h.s1;
-#ifdef DG_DEVTOOLS
-    if (const char* e = getenv("DG_HEAD_S2B")) { const int v = atoi(e) & ~7; if (v >= 8 && v <= h.s2b) h.s2b = v; }
-#endif
     // k_head_dh2 (the headline widths) forms d W2b beside d hidden: one partial sum per block of its launch
     h.dh_blocks = dg_head_dh_fused_blocks(B, C, D, P);
     if (h.dh_blocks > 0) h.s2b = h.dh_blocks;

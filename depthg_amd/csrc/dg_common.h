@@ -12,14 +12,19 @@ typedef __attribute__((ext_vector_type(2))) float f32x2;
 typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
 typedef __attribute__((ext_vector_type(4))) _Float16 f16x4;
 
-// Developer ablation switches (the `debug` bits of the argument blocks, the DG_DEBUG / DG_PREP_DEBUG / DG_STAMPS /
-// DG_BLOCKLOG / DG_SCATTER_CG environment hooks) exist only in a `make EXTRA=-DDG_DEVTOOLS` build; in the production
-// library the bits fold to zero at compile time and the hooks are not compiled.
-#ifdef DG_DEVTOOLS
-#define DG_DBG(x) (x)
-#else
-#define DG_DBG(x) 0
-#endif
+// Switches of the library - the complete list (tests/test_host_cpu.py fails on a getenv or a tested macro not named here).
+// Test seams, read in every build; each selects a second route that must give the same bits (tests/test_gpu_configs.py):
+//   DG_FOLD_INTRA=0   the intra pair-set's streamed-side gradient by k_gs instead of k_corr2's fold (dg_api.hip make_plan)
+//   DG_SPLIT_MASKS=0  the dense grid's exact-mask chain in sequence on the caller's stream, no side stream (dg_api.hip)
+//   DG_C2_WALK=dynamic|static   the walk of k_corr2's persistent workgroups (dg_corr2.hip)
+// Measurement instruments, compiled only into a `make EXTRA=-DDG_DEVTOOLS` build (results unchanged, timing perturbed):
+//   DG_STAMPS=<file>, DG_BLOCKLOG=<file>   phase stamps / per-block timeline of the fused kernel (with -DDG_STAMP_BUILD for
+//                                           k_corr_main, -DC2_STAMPS [-DC2_STAMP_N=n -DC2_BLOCKSTAMPS_ONLY] or -DC2_BLOCKLOG for k_corr2)
+//   DG_HEAD_STAMPS=<file>, DG_DH_STAMPS=<file>   phase stamps of k_head_fwd / k_head_dh, k_head_dh2
+//   DG_SMALL_DEBUG=1  block 0 of k_corr_small prints its phase stamps
+// Python side: DG_POISON=1 (depthg_amd/ops.py: poisoned buffers, tests/test_gpu_poison.py), DEPTHG_LIB=<path> (another build).
+// Tuning constants (#ifndef X / #define X value, no other code behind them): C2_PF, PF, GS_CW, GS_NB, DG_STAGGER, DG_PRIO,
+// DG_F_IG, DENSE_TPB, COMB_HB, COMB_HB_HM, HEAD_FWD_PD, HEAD_SPLIT_TARGET.
 
 #define DG_EPS_NORM 1e-10f  // F.normalize eps, reference src/modules.py:790
 
@@ -253,7 +258,6 @@ struct DgCorrArgs {
     const char* dummy;    // any valid device address (source of DMA lanes that carry nothing)
     int32_t pos_w;        // > 0: positions are pixel indices y*w + x of a w x w identity grid (DG_IDENTITY_GRID); the un-reduced outputs
                           //      (materialise) are written at the reference's position x*w + y
-    int32_t debug;        // developer ablation bits (0 in production)
     uint32_t* wctr;       // k_corr2's persistent workgroups: [0..7] items handed out so far per XCD (beyond each workgroup's first), [8]
                           // workgroups that have left; all zero at launch (k_colmean) and again when the last workgroup leaves; null: static walk
     unsigned long long* span;   // measurement aid (dg_prof_main_span): [0] min of the workgroups' entry times, [1] max of their exit times, [2] / [3] sums of their lifetimes in shader cycles / wall ticks; or null
@@ -506,7 +510,6 @@ struct DgDenseArgs {        // identity-grid operand preparation (k_prep_dense)
     float* nz;               // [B][Ppad] depth indicators
     float* nzsum;            // [B] their per-image sums
     int32_t B, K, D, KF, KD, h, w, P, Ppad, dH, dW;
-    int32_t debug;           // developer ablation bits (0 in production): 1 skip feats, 2 skip code, 4 skip depth
     // draw_count > 0: that many extra blocks draw the negatives' batch maps (dg_super_perm_row) into draw_out - the step's
     // k_super_perms launch rides here (dg_corr_forward_draw)
     int64_t* draw_out;
@@ -649,7 +652,6 @@ struct DgScatterArgs {
     int32_t blob_bytes, blob_off_c;
     float* out[2];         // grad_code, grad_code_pos  (B,D,h,w)
     int32_t B, D, DP, h, w, S, Sh, P, Ppad, DC;   // DC = channels per block (power of two <= 32)
-    int32_t debug;         // developer ablation bits (0 in production)
     int32_t dense;         // 1: identity grid (DG_IDENTITY_GRID): the adjoint of sample() is a transposed copy
     // (set by the launcher) the direct sources of k_grad_combine per destination, in source order: raw ones, then final ones
     int8_t craw[2][DG_MAX_SCATTER / 2], cfin[2][DG_MAX_SCATTER / 2];
@@ -695,7 +697,6 @@ struct DgGsArgs {
     DgGsJob jobs[DG_MAX_NEG + 2];
     int32_t njobs, B, P, Ppad, KF, KD;
     int32_t D;             // real code channels (<= KD)
-    int32_t debug;         // developer ablation bits (0 in production)
     DgFinishArgs fin;      // the first block also reduces k_corr_main's partial sums (fin.out == null: nothing to do)
     // The depth term (depth_feature_correlation) as extra blocks of this launch (dep_blocks > 0): the G-stream blocks are
     // HBM-bound and their second round leaves block slots empty, so the depth blocks' latency chain costs next to nothing here

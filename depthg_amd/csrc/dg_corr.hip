@@ -157,7 +157,6 @@ __device__ __forceinline__ void corr_body(const DgCorrArgs& args, const DgJob& j
 
     // kernarg fields used inside the tile loop are copied to locals: behind the asm memory clobbers hipcc would re-load
     // them (s_load + s_waitcnt lgkmcnt(0), which also drains the LDS read ring) in every iteration
-    const int dbg = DG_DBG(args.debug);
     uint16_t* const Gout = job.Gout;
     float* const out_cd = job.out_cd;
     float* const out_loss = job.out_loss;
@@ -187,7 +186,7 @@ __device__ __forceinline__ void corr_body(const DgCorrArgs& args, const DgJob& j
     (void)st_lds;
 #endif
     BLOG(0);
-    const int ntiles = (dbg & 128) ? 1 : ntiles_all;     // developer ablation: one tile only (fixed per-block cost)
+    const int ntiles = ntiles_all;
     const int nR = job.ridx ? (int)job.ridx[n] : n;
     const int nS = job.sidx ? (int)job.sidx[n] : n;
 
@@ -195,8 +194,7 @@ __device__ __forceinline__ void corr_body(const DgCorrArgs& args, const DgJob& j
     //      the S tiles (even / odd), the other waves fetch; four tile buffers (the unused code-row slots hold the fourth).
     //      Without this the block runs one wave for as long as a full block runs eight.
     const int nact = min(NWAVES, (ntiles_all - rb * NWAVES * RF + RF - 1) / RF);
-    const bool pair = DG_STAGGER && NWAVES == 8 && RF == 1 && NBUF == 3 && !MAT && !RCREG && nact == 1 && ntiles > 1 &&
-                      !(dbg & 67108864);
+    const bool pair = DG_STAGGER && NWAVES == 8 && RF == 1 && NBUF == 3 && !MAT && !RCREG && nact == 1 && ntiles > 1;
     const bool owner = !(pair && wid == 1);               // wave 1 hands its gradient accumulators to wave 0 at the end
     // ---- the RF 32-row tiles of R owned by this wave
     const int rtile0 = (rb * NWAVES + ((pair && wid == 1) ? 0 : wid)) * RF;
@@ -242,7 +240,7 @@ __device__ __forceinline__ void corr_body(const DgCorrArgs& args, const DgJob& j
         }
     }
     bf16x8 Rf[RF][NSF > 0 ? NSF : 1];
-    if (KIND != KIND_DEPTH && !(dbg & 2048)) {
+    if (KIND != KIND_DEPTH) {
 #pragma unroll
         for (int f = 0; f < RF; ++f)
 #pragma unroll
@@ -257,7 +255,7 @@ __device__ __forceinline__ void corr_body(const DgCorrArgs& args, const DgJob& j
 #pragma unroll
             for (int t8 = 0; t8 < 8; ++t8) asm volatile("" : "+v"(mw[t8]));
         }
-        if (KIND != KIND_DEPTH && !(dbg & 1024)) {
+        if (KIND != KIND_DEPTH) {
 #pragma unroll
             for (int f = 0; f < RF; ++f)
 #pragma unroll
@@ -293,7 +291,7 @@ __device__ __forceinline__ void corr_body(const DgCorrArgs& args, const DgJob& j
     // which 1-KiB chunks of a tile this wave fetches: normally chunk c belongs to wave NWAVES-1 - c % NWAVES; in a ragged
     // last row block (fewer than half of the waves own rows) the idle waves share all chunks
     const int ncomp = pair ? 2 : nact;                      // waves that compute in this block
-    const bool idle_fetch = RF == 1 && nact > 0 && nact < NWAVES / 2 && !(dbg & 33554432);
+    const bool idle_fetch = RF == 1 && nact > 0 && nact < NWAVES / 2;
     const int dma_stride = idle_fetch ? NWAVES - ncomp : NWAVES;
     const int dma_first = idle_fetch ? (wid >= ncomp ? wid - ncomp : -1) : 0;
     auto issue = [&](int t, int b) {
@@ -337,7 +335,7 @@ __device__ __forceinline__ void corr_body(const DgCorrArgs& args, const DgJob& j
     // ---- one Y chain = NSF feature k-steps then NKD code k-steps.  The A operands (S fragments) run through an
     //      explicit ring of PF registers that is refilled right after each MFMA, so that PF LDS reads are always in
     //      flight; scheduling fences pin that order (left alone hipcc serialises read -> wait -> MFMA here).
-    const int late_prio = (STAG && DG_PRIO == 1 && wid >= NWAVES / 2 && !(dbg & 32768)) ? 1 : 0;   // priority outside the chain
+    const int late_prio = (STAG && DG_PRIO == 1 && wid >= NWAVES / 2) ? 1 : 0;   // priority outside the chain
     auto chain = [&](const char* tile, const int f, auto&& between) {
         auto a_ptr = [&](int st) -> const v4i* {
             return st < NSF ? reinterpret_cast<const v4i*>(tile + fbase[st % FPER] + (st / FPER) * (FPER * 1024))
@@ -360,7 +358,7 @@ __device__ __forceinline__ void corr_body(const DgCorrArgs& args, const DgJob& j
         __builtin_amdgcn_sched_barrier(0);
         // the wave in its MFMA chain wins the issue port: an MFMA needs it 8 cycles in 32, the partner's epilogue VALU
         // stream would otherwise starve the matrix pipe (stamps: iteration 4410 -> 4070 cycles)
-        if (STAG && !(dbg & 131072)) __builtin_amdgcn_s_setprio(2);
+        if (STAG) __builtin_amdgcn_s_setprio(2);
 #pragma unroll
         for (int st = 0; st < NS; ++st) {
             const v4i cur = ra[st % PF];
@@ -376,7 +374,7 @@ __device__ __forceinline__ void corr_body(const DgCorrArgs& args, const DgJob& j
             between(st);
             __builtin_amdgcn_sched_barrier(0);
         }
-        if (STAG && !(dbg & 131072)) { if (late_prio) __builtin_amdgcn_s_setprio(1); else __builtin_amdgcn_s_setprio(0); }
+        if (STAG) { if (late_prio) __builtin_amdgcn_s_setprio(1); else __builtin_amdgcn_s_setprio(0); }
     };
 
     // ---- everything after the Y chains of tile t: epilogue (VALU) and the gradient MFMAs.  For RF == 2 the epilogue of
@@ -427,9 +425,6 @@ __device__ __forceinline__ void corr_body(const DgCorrArgs& args, const DgJob& j
             });
 #pragma unroll
             for (int i = 0; i < 16; ++i) epi(RF - 1, i);
-        } else if (dbg & 16) {   // developer ablation: no epilogue VALU (results invalid)
-#pragma unroll
-            for (int f = 0; f < RF; ++f) { ga[f][0] = __builtin_bit_cast(f16x8, Yf[f][0] > 1e30f ? v4i{1, 1, 1, 1} : v4i{0, 0, 0, 0}); ga[f][1] = ga[f][0]; lsum += Yc[f][0]; }
         } else {
 #pragma unroll
             for (int i = 0; i < 16; ++i) epi(0, i);
@@ -437,7 +432,7 @@ __device__ __forceinline__ void corr_body(const DgCorrArgs& args, const DgJob& j
                 ga[RF - 1][0] = f16x8{}; ga[RF - 1][1] = f16x8{};
             }
         }
-        if (GRAD && GOUT && !(dbg & 8)) {
+        if (GRAD && GOUT) {
             // G tile (fp16, accumulator order) -> HBM, 2 KiB per wave and tile, fully coalesced: input of k_gs, which
             // forms the gradient of the STREAMED operand's code without recomputing fd / cd
 #pragma unroll
@@ -451,7 +446,7 @@ __device__ __forceinline__ void corr_body(const DgCorrArgs& args, const DgJob& j
                     __builtin_nontemporal_store(__builtin_bit_cast(v4i, ga[f][1]), g + 64);
                 }
         }
-        if (GRAD && !(dbg & 4)) {
+        if (GRAD) {
             // dR[f][r][:] += sum_s G[f][s][r] * ScP[s][:]   (accumulator tile as the A operand; B shared by the fragments)
             // k-step outer, channel group inner: consecutive MFMAs go to different accumulators
 #pragma unroll
@@ -472,11 +467,8 @@ __device__ __forceinline__ void corr_body(const DgCorrArgs& args, const DgJob& j
         // epilogue runs under the other's MFMA chain instead of both alternating in lockstep behind the tile barrier.
         // Tile t-1 must stay in LDS during iteration t, so tiles are fetched one (not two) ahead.
         const bool late = wid >= NWAVES / 2;
-        {   // static priority (experiment bits: 32768 = none, 65536 = waves 0-3 instead)
-            const int prio_mode = (dbg & 32768) ? 0 : ((dbg & 65536) ? 2 : DG_PRIO);
-            if (prio_mode == 1 && late) __builtin_amdgcn_s_setprio(1);
-            if (prio_mode == 2 && !late) __builtin_amdgcn_s_setprio(1);
-        }
+        if (DG_PRIO == 1 && late) __builtin_amdgcn_s_setprio(1);      // static priority
+        if (DG_PRIO == 2 && !late) __builtin_amdgcn_s_setprio(1);
         // pair mode (ragged last row block): every wave takes the "early" schedule; waves 0 and 1 compute the even / odd tiles
         // of a pair per barrier, waves 2-7 fetch the next pair into the other two of four buffers
         const bool late2 = late && !pair;
@@ -491,18 +483,16 @@ __device__ __forceinline__ void corr_body(const DgCorrArgs& args, const DgJob& j
             STAMP(t, 0);
             // tile t landed; only the G stores of the previous tile may still be in flight (fetch-only waves: nothing may)
             wait_vmcnt((pair && dma_first >= 0) ? 0 : nst);
-            if (!(dbg & 256)) __builtin_amdgcn_s_barrier();
+            __builtin_amdgcn_s_barrier();
             STAMP(t, 1);
             if (t == 0) BLOG(1);
             if (pair) {
-                if (!(dbg & 1)) {
-                    if (t + 2 < ntiles) issue(t + 2, (t + 2) & 3);
-                    if (t + 3 < ntiles) issue(t + 3, (t + 3) & 3);
-                }
+                if (t + 2 < ntiles) issue(t + 2, (t + 2) & 3);
+                if (t + 3 < ntiles) issue(t + 3, (t + 3) & 3);
             } else {
                 // waves 4-7 fetch the next tile here; waves 0-3 do it after their chain (the issue of 4-5 LDS-DMA pieces costs
-                // 400-600 cycles in front of the chain, but hides beside the partner's chain) - bit 524288 switches that off
-                if (t + 1 < ntiles && !(dbg & 1) && (late2 || (dbg & 524288))) issue(t + 1, (t + 1) % 3);
+                // 400-600 cycles in front of the chain, but hides beside the partner's chain)
+                if (t + 1 < ntiles && late2) issue(t + 1, (t + 1) % 3);
             }
             STAMP(t, 2);
         };
@@ -514,7 +504,7 @@ __device__ __forceinline__ void corr_body(const DgCorrArgs& args, const DgJob& j
                 const char* tile = tilep(t);
                 const bool work = wave_active && t < ntiles;
                 if (work) { chain(tile, 0, [](int) {}); STAMP(t0, 3); }
-                if (!pair && t0 + 1 < ntiles && !(dbg & 1) && !(dbg & 524288)) issue(t0 + 1, (t0 + 1) % 3);
+                if (!pair && t0 + 1 < ntiles) issue(t0 + 1, (t0 + 1) % 3);
                 if (work) post(tile, t, false);
             }
         } else {
@@ -539,7 +529,7 @@ __device__ __forceinline__ void corr_body(const DgCorrArgs& args, const DgJob& j
             // tile t has landed (this wave's pieces: vmcnt; everybody's: barrier); the buffer of tile t-1 is free again
             wait_vmcnt((NBUF == 3 && t + 1 < ntiles) ? my_dma + nst : nst);
             __builtin_amdgcn_s_barrier();
-            if (t + NBUF - 1 < ntiles && !(dbg & 1)) issue(t + NBUF - 1, bcur >= 1 ? bcur - 1 : NBUF - 1);
+            if (t + NBUF - 1 < ntiles) issue(t + NBUF - 1, bcur >= 1 ? bcur - 1 : NBUF - 1);
             const char* tile = smem + bcur * BUF;
             bcur = bcur == NBUF - 1 ? 0 : bcur + 1;
             if (!wave_active) continue;
@@ -571,7 +561,7 @@ __device__ __forceinline__ void corr_body(const DgCorrArgs& args, const DgJob& j
                 for (int i = 0; i < 16; ++i) dR[0][d][i] += xch[(d * 16 + i) * 64 + lane];
         }
     }
-    if (GRAD && job.dR && owner && !(dbg & 512)) {
+    if (GRAD && job.dR && owner) {
 #pragma unroll
         for (int f = 0; f < RF; ++f) {
             if (!act[f]) continue;
@@ -658,7 +648,7 @@ __global__ __launch_bounds__(NWAVES * 64) void k_corr_main(const DgCorrArgs args
     const int per_img = args.njobs * args.nrb;
     int n, jid, rb;
     const int nd = args.jobs[args.njobs - 1].kind == DG_JOB_DEPTH ? 1 : 0, nh = args.njobs - nd;
-    if ((gridDim.x & 7) == 0 && (args.B & 7) == 0 && nh > 0 && !(DG_DBG(args.debug) & 8388608)) {
+    if ((gridDim.x & 7) == 0 && (args.B & 7) == 0 && nh > 0) {
         // every XCD owns B/8 whole images; inside that chunk the long blocks go first (longest-processing-time order):
         // pair-set jobs with a full row block, then their ragged last row block, then the cheap depth job
         const int imgs = args.B >> 3, per_chunk = imgs * per_img;
@@ -683,8 +673,6 @@ __global__ __launch_bounds__(NWAVES * 64) void k_corr_main(const DgCorrArgs args
         rb = bid - jid * args.nrb;
     }
     const DgJob& job = args.jobs[jid];
-    if ((DG_DBG(args.debug) & 16777216) && rb == args.nrb - 1 && args.nrb > 1) return;     // (ablation: skip the last row block)
-    if ((DG_DBG(args.debug) & 134217728) && job.kind == DG_JOB_DEPTH) return;               // (ablation: skip the depth job)
     __shared__ unsigned long long span_keep[2];
     if (!MAT && threadIdx.x == 0) dg_span_enter(args.span, span_keep);
     if (job.kind == DG_JOB_DEPTH) corr_body<NKF, NKD, NWAVES, RF, GRAD, MAT, SIMPLE, KIND_DEPTH, NKC>(args, job, n, rb, smem);
@@ -897,11 +885,9 @@ __device__ __forceinline__ void gs_body(const DgGsArgs& a, const uint32_t* dep_m
     // the depth term's blocks FIRST (they are long latency chains: started last they would be this launch's tail), then the
     // G-stream blocks
     if ((int)blockIdx.x < a.dep_blocks) {
-        if (DG_DBG(a.debug) & 8192) return;                 // (ablation: no depth-term blocks)
         gs_depth_block<NKF, NKD, XM>(a, dep_maskbits, (int)blockIdx.x, gs_smem);
         return;
     }
-    if (DG_DBG(a.debug) & 16384) return;                    // (ablation: the depth-term blocks alone)
     int bid;
     {
         const int nwg = (int)gridDim.x - a.dep_blocks, orig = (int)blockIdx.x - a.dep_blocks;
@@ -913,8 +899,7 @@ __device__ __forceinline__ void gs_body(const DgGsArgs& a, const uint32_t* dep_m
     const int n = a.B - 1 - bz;
     const DgGsJob& J = a.jobs[by];
     const int ntS = a.Ppad >> 5;
-    const int gdbg = DG_DBG(a.debug);
-    const int nt = (gdbg & 4096) ? 1 : ntS;              // (ablation: one R tile only)
+    const int nt = ntS;
     const int nR = J.ridx ? (int)J.ridx[n] : n;
     if (wid == GS_CW) {
         // ---- producer: P parts of R tiles 0..nt-1 through the ring
@@ -955,7 +940,7 @@ __device__ __forceinline__ void gs_body(const DgGsArgs& a, const uint32_t* dep_m
     const v4i* Gbase = reinterpret_cast<const v4i*>(J.G) + ((size_t)n * ntS + st) * ntS * 128 + lane;      // [image][S tile][R tile]: one sequential 2 KiB-per-step stream per wave
     const size_t gstride = 128;                             // v4i per R tile step
     auto load_g = [&](int rt, v4i (&g)[2]) {
-        const v4i* gp = Gbase + (size_t)((gdbg & 64) ? 0 : rt) * gstride;
+        const v4i* gp = Gbase + (size_t)rt * gstride;
         g[0] = __builtin_nontemporal_load(gp);
         g[1] = __builtin_nontemporal_load(gp + 64);
     };
@@ -980,34 +965,31 @@ __device__ __forceinline__ void gs_body(const DgGsArgs& a, const uint32_t* dep_m
                 if (rt + 3 < nt) load_g(rt + 3, gring[k]);
                 __builtin_amdgcn_s_barrier();               // P part of tile rt is in the ring
                 asm volatile("" ::: "memory");
-                if (!(gdbg & 32)) {
-                    const char* P = gs_smem + (rt % GS_NB) * PB;
+                const char* P = gs_smem + (rt % GS_NB) * PB;
 #pragma unroll
-                    for (int ks = 0; ks < 2; ++ks) {
-                        // A fragment of dS = G^T x: element e of lane (q, h) is G[q][p], p = 16 ks + 8 (e>>2) + 4 h + (e&3) (the
-                        // position order of the P part's granule 2 ks + h); two transposing reads of 4 image rows each
-                        f16x8 afrag;
+                for (int ks = 0; ks < 2; ++ks) {
+                    // A fragment of dS = G^T x: element e of lane (q, h) is G[q][p], p = 16 ks + 8 (e>>2) + 4 h + (e&3) (the
+                    // position order of the P part's granule 2 ks + h); two transposing reads of 4 image rows each
+                    f16x8 afrag;
 #pragma unroll
-                        for (int u = 0; u < 2; ++u) {
-                            const int prow = 16 * ks + 8 * u + 4 * h + tr_a;
-                            typedef __attribute__((address_space(3))) s16x4* lds_s16x4_p;
-                            const s16x4 t = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-                                (lds_s16x4_p)(T + prow * 64 + ((tr_c ^ (prow & 7)) * 8)));
-                            const f16x4 tf = __builtin_bit_cast(f16x4, t);
+                    for (int u = 0; u < 2; ++u) {
+                        const int prow = 16 * ks + 8 * u + 4 * h + tr_a;
+                        typedef __attribute__((address_space(3))) s16x4* lds_s16x4_p;
+                        const s16x4 t = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
+                            (lds_s16x4_p)(T + prow * 64 + ((tr_c ^ (prow & 7)) * 8)));
+                        const f16x4 tf = __builtin_bit_cast(f16x4, t);
 #pragma unroll
-                            for (int e = 0; e < 4; ++e) afrag[4 * u + e] = tf[e];
-                        }
+                        for (int e = 0; e < 4; ++e) afrag[4 * u + e] = tf[e];
+                    }
 #pragma unroll
-                        for (int f = 0; f < NDF; ++f) {
-                            const f16x8 bfrag = *reinterpret_cast<const f16x8*>(P + ((2 * ks + h) * KD + 32 * f + r) * 16);
-                            acc[f] = __builtin_amdgcn_mfma_f32_32x32x16_f16(afrag, bfrag, acc[f], 0, 0, 0);
-                        }
+                    for (int f = 0; f < NDF; ++f) {
+                        const f16x8 bfrag = *reinterpret_cast<const f16x8*>(P + ((2 * ks + h) * KD + 32 * f + r) * 16);
+                        acc[f] = __builtin_amdgcn_mfma_f32_32x32x16_f16(afrag, bfrag, acc[f], 0, 0, 0);
                     }
                 }
             }
         }
     }
-    if (gdbg & 2048) { if (acc[0][0] == 1.2345f) J.dS[0] = acc[1][0] + acc[2][0]; return; }   // (ablation: no epilogue)
     // normalisation backward: acc[f][i] is (q = (i&3)+8*(i>>2)+4*h, channel 32 f + r);  dc = (dx - x <x,dx>) / ||c||
     const char* Cp = J.Sop + ((size_t)nS * ntS + st) * BL::BYTES + BL::OFF_C;
     static_assert(32 * GS_TS >= DG_XROWS_LDS, "scratch too small for the code rows");
@@ -1077,18 +1059,14 @@ __global__ __launch_bounds__((GS_CW + 1) * 64, 2) void k_gs_xm(const DgGsArgs a,
 hipError_t dg_launch_gs(const DgGsArgs& a, const uint32_t* dep_maskbits, hipStream_t stream, bool depth_only, bool half_out) {
     dim3 grid((depth_only ? 0 : ((a.Ppad / 32 + GS_CW - 1) / GS_CW) * a.njobs * a.B) + a.dep_blocks), block((GS_CW + 1) * 64);
     if (grid.x == 0) return hipSuccess;
-    DgGsArgs a2 = a;
-#ifdef DG_DEVTOOLS
-    if (const char* dbg = getenv("DG_DEBUG")) a2.debug = atoi(dbg);   // developer ablation switches (timing only)
-#endif
     const int smem = GS_NB * 4 * a.KD * 16 + GS_CW * 32 * GS_TS;
     if (half_out) {          // fp16 output tiles: the widths of k_corr2 only (the identity grid's plan asks for them there)
         if (a.KF != 384 || a.KD != 96) return hipErrorInvalidValue;
         const void* kern = dep_maskbits ? reinterpret_cast<const void*>(k_gs_xm<24, 6, true>) : reinterpret_cast<const void*>(k_gs<24, 6, true>);
         hipError_t e = dg_set_max_smem(kern, smem);
         if (e != hipSuccess) return e;
-        if (dep_maskbits) hipLaunchKernelGGL((k_gs_xm<24, 6, true>), grid, block, smem, stream, a2, dep_maskbits);
-        else hipLaunchKernelGGL((k_gs<24, 6, true>), grid, block, smem, stream, a2);
+        if (dep_maskbits) hipLaunchKernelGGL((k_gs_xm<24, 6, true>), grid, block, smem, stream, a, dep_maskbits);
+        else hipLaunchKernelGGL((k_gs<24, 6, true>), grid, block, smem, stream, a);
         return hipGetLastError();
     }
 #define DG_GS(NKF_, NKD_)                                                                                               \
@@ -1097,8 +1075,8 @@ hipError_t dg_launch_gs(const DgGsArgs& a, const uint32_t* dep_maskbits, hipStre
                                         : reinterpret_cast<const void*>(k_gs<NKF_, NKD_>);                               \
         hipError_t e = dg_set_max_smem(kern, smem);                                                                      \
         if (e != hipSuccess) return e;                                                                                   \
-        if (dep_maskbits) hipLaunchKernelGGL((k_gs_xm<NKF_, NKD_>), grid, block, smem, stream, a2, dep_maskbits);        \
-        else hipLaunchKernelGGL((k_gs<NKF_, NKD_>), grid, block, smem, stream, a2);                                      \
+        if (dep_maskbits) hipLaunchKernelGGL((k_gs_xm<NKF_, NKD_>), grid, block, smem, stream, a, dep_maskbits);         \
+        else hipLaunchKernelGGL((k_gs<NKF_, NKD_>), grid, block, smem, stream, a);                                       \
         return hipGetLastError();                                                                                        \
     }
     DG_GS(8, 6) DG_GS(8, 8) DG_GS(24, 6) DG_GS(24, 8) DG_GS(48, 6) DG_GS(48, 8)
@@ -1119,7 +1097,6 @@ static hipError_t launch_corr_t(const DgCorrArgs& args, hipStream_t stream) {
     DgCorrArgs a2 = args;
     int smem2 = smem;
 #ifdef DG_DEVTOOLS
-    if (const char* dbg = getenv("DG_DEBUG")) a2.debug = atoi(dbg);   // developer ablation switches (timing only, results invalid)
     const char* stamp_file = getenv("DG_STAMPS");                     // developer aid: phase time stamps of one block
     static uint32_t* stamp_buf = nullptr;
     if (stamp_file && smem + NWAVES * 400 <= 160 * 1024) {

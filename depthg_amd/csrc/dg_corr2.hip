@@ -113,13 +113,8 @@ template <int OFF> __device__ __forceinline__ void lds_rd(v4i_t& d, uint32_t add
     asm volatile("ds_read_b128 %0, %1 offset:%c2" : "=v"(d) : "v"(addr), "n"(OFF));
 }
 template <int N> __device__ __forceinline__ void wait_lgkm(void) { asm volatile("s_waitcnt lgkmcnt(%c0)" :: "n"(N) : "memory"); }
-#ifdef C2_XNOP      // (round-4 experiment: what one more s_nop 0 per chain MFMA costs = what the ones hipcc inserts cost)
-#define C2_XN "s_nop 0\n\t"
-#else
-#define C2_XN
-#endif
 template <int I> __device__ __forceinline__ void mfma_fd8(acc_t& acc, const v4i_t& a) {
-    asm volatile(C2_XN "v_mfma_f32_32x32x16_bf16 %0, %1, a[%c2:%c3], %0" : "+v"(acc) : "v"(a), "n"(4 * I), "n"(4 * I + 3));
+    asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, a[%c2:%c3], %0" : "+v"(acc) : "v"(a), "n"(4 * I), "n"(4 * I + 3));
 }
 // first MFMA of an fd chain: the accumulator STARTS at c (sixteen copies of the lane's c0, kept in registers for the whole block) -
 // no per-tile re-initialisation of the accumulator by sixteen 64-bit moves (round 4: hipcc gathered them into bursts of eight in
@@ -128,7 +123,7 @@ template <int I> __device__ __forceinline__ void mfma_fd8_from(acc_t& acc, const
     asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, a[%c3:%c4], %2" : "=&v"(acc) : "v"(a), "v"(c), "n"(4 * I), "n"(4 * I + 3));
 }
 __device__ __forceinline__ void mfma_h8(acc_t& acc, const v4i_t& a, const v4i_t& b) {
-    asm volatile(C2_XN "v_mfma_f32_32x32x16_f16 %0, %1, %2, %0" : "+v"(acc) : "v"(a), "v"(b));
+    asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, %0" : "+v"(acc) : "v"(a), "v"(b));
 }
 __device__ __forceinline__ void mfma_h80(acc_t& acc, const v4i_t& a, const v4i_t& b) {
     asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, 0" : "=&v"(acc) : "v"(a), "v"(b));
@@ -239,11 +234,7 @@ __global__ __launch_bounds__(256) void k_corr2(const DgCorrArgs args_k) {
     // chain steps per fragment and tile: the NKF feature k-steps, the NKC code k-steps - NOT in the exact-mask form (round 6): its mask
     // comes from the words of k_cd_mask3 and G = m (fd'' - shift) needs no cd; the loss and cd sums come out of the gradient tiles and
     // the column sums as ever, so the fp16 cd chain was 10 dead MFMAs of 70 per tile - and FOLD's one extra step
-#ifdef C2_XM_KEEP_CD        // (developer A/B: the exact-mask form with its dead cd chain, as until round 5)
-    constexpr bool NOCD = false;
-#else
     constexpr bool NOCD = XM;
-#endif
     constexpr int BUF = BL::BYTES, NS = NKF + (NOCD ? 0 : NKC) + (FOLD ? 1 : 0), PF = C2_PF, NBUF = 4;     // tiles are fetched NBUF - 1 ahead
     static_assert(PF == 8 || PF == 12, "phase C issues the first PF reads of a tile over its six gaps");
     static_assert(!FOLD || NKC < NKD, "FOLD needs a spare code k-step in the blob");
@@ -253,11 +244,7 @@ __global__ __launch_bounds__(256) void k_corr2(const DgCorrArgs args_k) {
     static_assert(ADR + RF * 2 * 16 <= 256 && NDF == 3, "accumulator-file plan: Rf + four gradient accumulators");
     // phase-A gaps: 0, 1 mask words, 2..9 the epilogue halves of fragment 1, then the DMA pieces of tile t + 3 - each in two halves over
     // two neighbouring gaps where the chain is long enough (SPLIT_DMA), whole in one gap otherwise (the exact-mask form's short chain)
-#ifdef C2_FORCE_SINGLE_DMA  // (developer A/B)
-    constexpr bool SPLIT_DMA = false;
-#else
     constexpr bool SPLIT_DMA = 10 + 2 * PIECES <= NS;
-#endif
     static_assert(10 + PIECES <= NS - 3 && NS >= 22 && NS > PF, "phase-A gaps for the epilogue halves and the DMA pieces / phase-B gaps");
     extern __shared__ __attribute__((aligned(16))) char smem[];   // [NBUF][BUF] tiles, red[8][4]
     declare_agprs();
@@ -624,21 +611,13 @@ __global__ __launch_bounds__(256) void k_corr2(const DgCorrArgs args_k) {
     v4i_t* gbase[RF];
 #pragma unroll
     for (int f = 0; f < RF; ++f)
-#ifdef C2_ABL_GSTORE      // (developer ablation, WRONG results: every G store of the launch into the same 2 KiB - what do the 246 MB of G writes cost the loop?)
-        gbase[f] = reinterpret_cast<v4i_t*>(args.jobs[fj[f]].Gout) + lane;
-#else
         gbase[f] = reinterpret_cast<v4i_t*>(args.jobs[fj[f]].Gout) + (fo[f] ? (size_t)0 : ((size_t)fn[f] * ntiles * ntiles + (act[f] ? ft[f] : 0)) * 128) + lane;
-#endif
     const size_t gstep = (size_t)ntiles * 128;
     // (a folded fragment has no reader for its G tiles; its stores stay in the instruction stream - the counted vmcnt waits of the
     //  tile barrier count them - but all go to the first 2 KiB of the pair-set's buffer with the default cache policy: L2 traffic)
     size_t gstepb[RF];
 #pragma unroll
-#ifdef C2_ABL_GSTORE
-    for (int f = 0; f < RF; ++f) gstepb[f] = 0;
-#else
     for (int f = 0; f < RF; ++f) gstepb[f] = fo[f] ? (size_t)0 : gstep * sizeof(v4i_t);
-#endif
     // running store addresses: a scalar base per fragment (advanced by scalar adds; the tile index times the tile stride as 64-bit scalar
     // multiplies in front of every store cost three s_mul and two adds each) + ONE 32-bit lane offset for every store - half the address
     // bytes of the vaddr form and no 64-bit VALU add (round 6: -0.5 % of the kernel, -2 us of the step).  gsb[0] points at S tile t,
@@ -653,9 +632,6 @@ __global__ __launch_bounds__(256) void k_corr2(const DgCorrArgs args_k) {
         // (asm: the store must be ISSUED here - the counted vmcnt waits at the tile barrier rely on it; hipcc is free to sink
         //  an ordinary store past the barrier, after which the wait lets the youngest DMA pieces of the next tile slip)
         (void)t;
-#ifdef C2_ABL_NOGSTORE     // (developer ablation, WRONG results: no G store is issued)
-        return;
-#endif
         // (non-temporal: with the default cache policy on these stores / k_gs's loads the step is 1-6 % slower, profiles/r03_SUMMARY.md)
         if (sp == 0) {
             if (FOLD && __builtin_expect(fo[f], 0)) asm volatile("global_store_dwordx4 %0, %1, %2" :: "v"(goff), "v"(ga[f][sp]), "s"(gsb[f]) : "memory");
@@ -741,11 +717,7 @@ __global__ __launch_bounds__(256) void k_corr2(const DgCorrArgs args_k) {
                 if constexpr (idx + PF < TOT) rd_step(std::integral_constant<int, (idx + PF) % NS>{}, ra[idx % PF]);
             };
             // DMA source / destination of tile t+3 (scalar)
-#ifdef C2_ABL_DMA         // (developer ablation, WRONG results: every tile of the loop is tile 0 of the streamed image - what does the arrival of the tiles cost?)
-            const int t2 = 0;
-#else
             const int t2 = t + 3 < ntiles ? t + 3 : 0;            // past the end: dummy pieces keep the counted waits uniform
-#endif
             const char* const sb2 = Sop_img + (size_t)t2 * BL::BYTES;
             const uint32_t dst2 = smem_a + bprev * BUF + wid * 1024;
             STAMP(t, 0);
@@ -756,13 +728,11 @@ __global__ __launch_bounds__(256) void k_corr2(const DgCorrArgs args_k) {
                 if constexpr (XM && ACT0 && st == 0) mask_issue(0, t + 3);
                 if constexpr (XM && ACT1 && st == 1) { mask_issue(1, t + 2); mask_prep(wsh[1], mwB, msh); }
                 if constexpr (ACT1 && st >= 2 && st < 18) epi1_half(std::integral_constant<int, st - 2>{});
-#ifndef C2_ABL_NODMA       // (developer ablation, WRONG results: no tile is fetched inside the loop - what does ISSUING the nine pieces cost?)
                 if constexpr (SPLIT_DMA && st >= 10 && st < 10 + 2 * PIECES) {           // piece k: M0 + offset in gap 10 + 2k, the load in gap 11 + 2k
                     constexpr int k = (st - 10) / 2;
                     if constexpr (((st - 10) & 1) == 0) dma_setup<k * 4096>(dst2, dma_voff, dtmp); else dma_go(dtmp, sb2);
                 }
                 if constexpr (!SPLIT_DMA && st >= 10 && st < 10 + PIECES) dma_piece<(st - 10) * 4096>(dst2, dma_voff, sb2);
-#endif
                 if constexpr (FRUN && ACT0 && st == NS - 3) ga[0][0] = v4i_t{fo[0] ? fold_w : 0, 0, 0, 0};
                 if constexpr (ACT1 && st == NS - 1) { if (t > 0) g_store(1, 0, t - 1); }
                 __builtin_amdgcn_sched_barrier(0);
@@ -1051,12 +1021,9 @@ static int dg_corr2_launch_grid(const DgCorrArgs& args) {
         int dev = 0, n = 0;
         if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 8) n = 256;
         ncu = n / 8 * 8;
-#ifdef DG_DEVTOOLS
-        if (const char* g = getenv("DG_C2_GRID")) ncu = atoi(g);     // developer A/B: 0 = one workgroup per item (the round-3 launch)
-#endif
     }
     const int items = dg_corr2_grid(args);
-    return (ncu <= 0 || items < ncu) ? items : ncu;
+    return items < ncu ? items : ncu;
 }
 
 // which walk the persistent workgroups take: dynamic (per-XCD work counters) at six or more items per workgroup, the fixed round-robin
@@ -1078,9 +1045,6 @@ static bool dg_corr2_dynamic_walk(const DgCorrArgs& args, int grid) {
 // from it whether the intra pair-set may be folded: a second copy of these conditions there could drift from this one and turn a
 // fall-back to k_corr_main into a failed call)
 bool dg_corr2_shape_supported(int KF, int KD, int D, float lo, float hi, int Ppad, int B) {
-#ifdef C2_DISABLE          // (developer A/B: everything through k_corr_main)
-    return false;
-#endif
     return KF == 384 && KD == 96 && D <= 80 && lo == 0.f && hi > 1e30f && Ppad >= 160 && B <= 64;
 }
 bool dg_corr2_supported(const DgCorrArgs& args, int KF, int KD) {

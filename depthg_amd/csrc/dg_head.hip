@@ -429,9 +429,7 @@ hipError_t dg_launch_head_fwd(const DgHeadFwdArgs& a, hipStream_t s) {
     // C <= 384 on maps whose positions split into tiles of 112 (28 x 28, 56 x 56, ...): eight waves and 112 positions per block -
     // every block streams the 0.4 MB of bf16 weights once per 112 positions instead of once per 32 (the 32-position form re-reads
     // them 784 times at the headline: 316 MB through L2 for 10 GFLOP)
-#ifndef HEAD_NT32
     if (a.C <= 384 && a.P % 112 == 0) return launch_head_fwd<3, 112, 8>(a, s);
-#endif
     // 32 positions per block: 40 KB of LDS and < 256 registers -> two blocks per CU, one block's tile load under the other's MFMAs
     if (a.C <= 384) return launch_head_fwd<6, 32>(a, s);
     if (a.C <= 768) return launch_head_fwd<12, 32>(a, s);
@@ -838,9 +836,6 @@ __global__ __launch_bounds__(512) void k_head_dh2(const DgHeadDhArgs a) {
 }
 
 int dg_head_dh_fused_blocks(int B, int C, int D, int P) {
-#ifdef DG_DEVTOOLS
-    if (const char* e = getenv("DG_HEAD_DH2")) if (e[0] == '0') return 0;
-#endif
     if (!(C > 192 && C <= 384 && D <= 96 && (P & 7) == 0)) return 0;
     const int ntiles = B * ((P + 63) / 64);
     return ntiles < 256 ? ntiles : 256;
@@ -1178,12 +1173,6 @@ __global__ __launch_bounds__(512) void k_head_wgrad3(const DgHeadWgradArgs a) {
     const bool has_g = wid < g16;
     const int npw = 5 + (has_g ? 1 : 0);                               // DMA instructions of this wave per step
     auto issue = [&](int b, int p0, const int st) __attribute__((always_inline)) {
-#ifdef W3_ABL_NODMA
-        if (b >= 0) return;                              // (developer ablation, WRONG results: nothing is fetched)
-#endif
-#ifdef W3_ABL_SAMESTEP
-        b = s0 / steps_img; p0 = 32 * (st & 1);          // (developer ablation, WRONG results: the block re-reads two steps - every piece an L2 hit)
-#endif
         const int v = a.P - p0;                                        // valid positions from p0 on (>= 8)
         const uint32_t dst = lds0 + st * W3_STAGE + wid * 1024;
         const uint32_t pa = (pos_a + 8 <= v ? pos_a : 0) * 2, pf = (pos_f + 4 <= v ? pos_f : 0) * 4;
@@ -1258,10 +1247,6 @@ __global__ __launch_bounds__(512) void k_head_wgrad3(const DgHeadWgradArgs a) {
         // the previous step and then read this step's: behind the barrier one wave of a SIMD is on the LDS pipe while the other is on the
         // matrix core.  The MFMAs stay unconditional (a condition around them makes hipcc shuffle the accumulators): the late waves'
         // first product is on zeros
-#ifdef W3_ABL_NOMUL
-        if (v == -12345)                                 // (developer ablation, WRONG results: no fragment reads, no products)
-#endif
-        {
         if (!late) { load_b(base, 0, v, b0); load_b(base, 1, v, b1); load_a(base, 0, a0); load_a(base, 1, a1); }
 #pragma unroll
         for (int i = 0; i < 4; ++i)
@@ -1272,7 +1257,6 @@ __global__ __launch_bounds__(512) void k_head_wgrad3(const DgHeadWgradArgs a) {
 #pragma unroll
             for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1[i], b1[j], acc[i][j], 0, 0, 0);
         if (late) { load_b(base, 0, v, b0); load_b(base, 1, v, b1); load_a(base, 0, a0); load_a(base, 1, a1); }
-        }
         pm += 32; if (pm >= a.P) { pm = 0; ++bm; }
         st = st + 1 == NSTAGE ? 0 : st + 1;
         stn = stn + 1 == NSTAGE ? 0 : stn + 1;
@@ -1301,18 +1285,12 @@ __global__ __launch_bounds__(512) void k_head_wgrad3(const DgHeadWgradArgs a) {
 #pragma unroll
             for (int e = 0; e < 16; ++e) {
                 const int m = (wm == 3 ? 0 : wm * 128) + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * kg;
-#ifdef W3_ABL_NOSTORE
-                if (acc[i][j][e] == 1.2345f)             // (developer ablation, WRONG results: no partial sums written)
-#endif
                 if (m < Mo && n < a.N) out[(size_t)m * a.N + n] = acc[i][j][e];
             }
         }
 }
 // (what the plan asks before it sizes the partial sums: dg_api.hip head_splits)
 bool dg_head_wgrad_one_pass(int M, int N, int M2, int P) {
-#ifdef DG_DEVTOOLS
-    if (const char* e = getenv("DG_HEAD_WGRAD3")) if (e[0] == '0') return false;
-#endif
     return M > 256 && M <= 384 && M2 > 0 && M2 <= 128 && (P & 7) == 0;
 }
 

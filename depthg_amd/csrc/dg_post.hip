@@ -160,9 +160,8 @@ __global__ __launch_bounds__(64 * NDF) void k_combine_out(const DgScatterArgs a)
     DG_LOAD_GS(a, gs)
     // ---- routed list of (dest, n): every thread tests one (routed source, image) pair per round
     int nr = 0;
-    if (DG_DBG(a.debug) & 8) { if (dest == 1) return; }                   // (developer ablations, WRONG results: 8 no destination-1 blocks,
-    for (int s = 0; s < a.nsrc; ++s)                                       //  1 no routed sources, 2 no norm() backward, 4 no output)
-        if (a.src[s].dest == dest && a.src[s].route != nullptr && !(DG_DBG(a.debug) & 1)) { if (tid == 0) rsrc[nr] = s; ++nr; }
+    for (int s = 0; s < a.nsrc; ++s)
+        if (a.src[s].dest == dest && a.src[s].route != nullptr) { if (tid == 0) rsrc[nr] = s; ++nr; }
     if (tid == 0) rl_cnt = 0;
     __syncthreads();
     for (int i0 = 0; i0 < nr * a.B; i0 += 64 * NDF) {
@@ -278,7 +277,7 @@ __global__ __launch_bounds__(64 * NDF) void k_combine_out(const DgScatterArgs a)
     const int nraw = a.ncraw[dest] + a.ncrawh[dest];
     add_sources(a.craw[dest], a.ncraw[dest]);
     add_sources_half(a.crawh[dest], a.ncrawh[dest], true);
-    if (nraw > 0 && !(DG_DBG(a.debug) & 2)) {
+    if (nraw > 0) {
         const char* xb = a.xop + ((size_t)n * (a.Ppad >> 5) + rt) * a.blob_bytes + a.blob_off_c + d * 2048;
         _Float16 x[1][16];
         dg_load_code_rows<1>(xb, xs[d], lane, x);
@@ -333,7 +332,6 @@ __global__ __launch_bounds__(64 * NDF) void k_combine_out(const DgScatterArgs a)
                 for (int e = 0; e < 4; ++e) v[4 * g + e] = fmaf(sc[k], ok ? u4[k][g][e] : 0.f, v[4 * g + e]);
     }
     // ---- out[dest][(n, channel, pixel)]: the wave's [32 channels][32 positions] tile through LDS, rows of 128 contiguous bytes
-    if (DG_DBG(a.debug) & 4) { if (v[0] == 1.2345f) a.out[dest][0] = v[1]; return; }
     float* st = stage[d];
 #pragma unroll
     for (int i = 0; i < 16; ++i) st[r * 33 + (i & 3) + 8 * (i >> 2) + 4 * h] = v[i];
@@ -767,7 +765,6 @@ hipError_t dg_launch_scatter(const DgScatterArgs& a, hipStream_t s) {
             }
         }
         const dim3 cgrid(a.Ppad / 32, a.B, 2);
-#ifndef DG_TWO_STAGE_DENSE      // (developer A/B: the round-2 form, k_grad_combine + k_scatter_dense)
         {
             // identity grid: combine + routed negatives + (B,D,h,w) output in one launch
             int nrouted = 0;
@@ -777,9 +774,6 @@ hipError_t dg_launch_scatter(const DgScatterArgs& a, hipStream_t s) {
             for (int i = 0; i < a.nsrc; ++i) { any_half = any_half || a.src[i].half != 0; routed_h += (a.src[i].route != nullptr && a.src[i].half) ? 1 : 0; }
             if (routed_h != 0 && routed_h != nrouted) return hipErrorInvalidValue;      // (fp16 tiles for every routed source or for none)
             ac.routed_half = routed_h != 0 ? 1 : 0;
-#ifdef DG_DEVTOOLS
-            if (const char* e = getenv("DG_COMB_DEBUG")) ac.debug = atoi(e);
-#endif
             const bool one_launch = a.dense && a.S == a.h && a.S == a.w && nrouted * a.B <= COMB_MAXROUTE && (a.DP == 96 || a.DP == 128);
             if (any_half && !one_launch) return hipErrorInvalidValue;      // (fp16 tiles are k_combine_out's: the plan asks for them only where it runs)
             if (one_launch) {
@@ -790,7 +784,6 @@ hipError_t dg_launch_scatter(const DgScatterArgs& a, hipStream_t s) {
                 return hipGetLastError();
             }
         }
-#endif
         const dim3 cgrid2(a.Ppad / 32, a.B, 2 + a.naxpy);
         if (a.DP == 96) hipLaunchKernelGGL(k_grad_combine<3>, cgrid2, dim3(192), 0, s, ac);
         else if (a.DP == 128) hipLaunchKernelGGL(k_grad_combine<4>, cgrid2, dim3(256), 0, s, ac);
@@ -801,13 +794,8 @@ hipError_t dg_launch_scatter(const DgScatterArgs& a, hipStream_t s) {
         // identity grid: transposed copy (needs the [32][HW+1] stage in LDS and a bounded routed list)
         int nrouted = 0;
         for (int i = 0; i < a.nsrc; ++i) nrouted += a.src[i].route != nullptr;
-        // 16 channels per block: 27 -> 21 us at the headline shape (8: 22 us); DG_SCATTER_CG overrides (developer A/B)
-#ifdef DG_DEVTOOLS
-        static const int cgsel = getenv("DG_SCATTER_CG") ? atoi(getenv("DG_SCATTER_CG")) : 16;
-#else
-        constexpr int cgsel = 16;
-#endif
-        int CGv = cgsel == 32 ? 32 : (cgsel == 8 ? 8 : 16);
+        // 16 channels per block: 27 -> 21 us at the headline shape (8: 22 us)
+        int CGv = 16;
         auto stage_bytes = [&](int cg) { return (size_t)cg * (HW + 2) * 4 + (size_t)DENSE_MAXROUTE * 12; };
         if (stage_bytes(CGv) > 150 * 1024 && CGv > 8) CGv = 8;      // 56 x 56 maps: 8 channels per block keep the [channel][pixel] stage in LDS
         const size_t dsm = stage_bytes(CGv);
@@ -842,10 +830,7 @@ hipError_t dg_launch_scatter(const DgScatterArgs& a, hipStream_t s) {
         // ... and 16-channel blocks fewer than half the CUs (config 4's shard of 8 images: 96 blocks): 8 channels per block.  Measured:
         // config 4 shard 0.2106 -> 0.2071 ms; config 2 (192 blocks of 16 channels) 0.1939 -> 0.1950 and config 3 (512) 0.220 -> 0.231
         // the other way - the tap records are loaded once per block, whatever its channel count
-        bool quarter = (a.DP / 16) * a.B * 2 < 128;
-#ifdef DG_DEVTOOLS
-        if (const char* sc = getenv("DG_SCAT_SMALL_CG")) quarter = atoi(sc) == 8;
-#endif
+        const bool quarter = (a.DP / 16) * a.B * 2 < 128;
         const int CGv = quarter ? 8 : (half ? 16 : 32);
         const size_t per_src = rec + (size_t)a.Ppad * (CGv + 1) * 4;
         int rb = (int)((size_t)(150 * 1024) / per_src);
@@ -1210,11 +1195,8 @@ __global__ __launch_bounds__(256) void k_rand_coords_state(unsigned long long* _
 }
 hipError_t dg_launch_rand_coords_state(unsigned long long* state, float* out, int n, hipStream_t s, float keep_p) {
     // (ten Philox rounds per value: one block was 15 us for the 74 k mask flags of a step; 256 blocks 8.2 us - every block ends with
-    //  a ticket on ONE address, and 256 of those in a row are most of it; DG_RAND_BLOCKS in developer builds)
-    int blocks = n >= 64 * 256 ? 64 : (n + 255) / 256;
-#ifdef DG_DEVTOOLS
-    if (const char* e = getenv("DG_RAND_BLOCKS")) blocks = atoi(e) > 0 ? atoi(e) : blocks;
-#endif
+    //  a ticket on ONE address, and 256 of those in a row are most of it)
+    const int blocks = n >= 64 * 256 ? 64 : (n + 255) / 256;
     hipLaunchKernelGGL(k_rand_coords_state, dim3(blocks), dim3(256), 0, s, state, out, n, keep_p);
     return hipGetLastError();
 }

@@ -612,15 +612,10 @@ hipError_t dg_launch_cd_mask3(const DgCdMask3Args& a_in, hipStream_t s) {
     if (a_in.KD != 96) return hipErrorInvalidValue;
     const int nt = a_in.Ppad / 32;
     // (W = 8 and one part measured fastest at the headline - 80.5 us against 90 with W = 5 and two parts, round 6: the staging of the
-    //  S tiles per R tile, not the idle waves of the last block, sets the pace; the other forms stay selectable in developer builds)
-    int w = 8;
+    //  S tiles per R tile, not the idle waves of the last block, sets the pace; the W = 5..7 forms stay compiled but are not launched)
+    constexpr int w = 8;
     DgCdMask3Args a = a_in;
     if (a.nsplit <= 0) a.nsplit = 1;
-#ifdef DG_DEVTOOLS
-    if (const char* e = getenv("DG_MASK3_SPLIT")) a.nsplit = atoi(e);
-    if (const char* e = getenv("DG_MASK3_W")) w = atoi(e);
-    if (w < 5 || w > 8) w = 8;
-#endif
     const dim3 grid(((nt + w - 1) / w) * a.nsplit, a.B, a.T);
     switch (w) {
         case 5: hipLaunchKernelGGL((k_cd_mask3<5, 5>), grid, dim3(320), 0, s, a); break;
@@ -721,7 +716,6 @@ __device__ __forceinline__ void prep_dense_feats(const DgDenseArgs& a, float* sl
             if (u < nu) *reinterpret_cast<__bf16*>(tb + xl * RS + (k0 + 8 * u) * 2) = (__bf16)(t[u] * inv);
     }
     __syncthreads();
-    if (DG_DBG(a.debug) & 32) return;                       // (ablation: loads + normalisation only)
     // blob rows: position p = y*w + x; the lanes of a row run along K
     const int pieces = KF / 8;                      // granules (16 bytes) per row
     for (int id = tid; id < wseg * pieces; id += 256) {
@@ -731,7 +725,6 @@ __device__ __forceinline__ void prep_dense_feats(const DgDenseArgs& a, float* sl
         char* blob = a.blob[o] + ((size_t)n * (a.Ppad / 32) + (p >> 5)) * L.bytes;
         *reinterpret_cast<uint4*>(blob + L.f(p & 31, g)) = v;
     }
-    if (DG_DBG(a.debug) & 64) return;                       // (ablation: no column sums)
     // per-source-row column sums of the normalised (bf16-rounded, i.e. exactly what the MFMA sees) rows
     for (int k = tid; k < KF; k += 256) {
         float cs = 0.f;
@@ -794,7 +787,6 @@ __device__ __forceinline__ void prep_dense_code(const DgDenseArgs& a, float* sl,
         red[kg * DENSE_CODE_PAIRS + ps + 64 * j] = ss;
     }
     __syncthreads();
-    if (DG_DBG(a.debug) & 8) return;                                  // (ablation: loads only)
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
         if (pos[j] < 0) continue;
@@ -808,7 +800,6 @@ __device__ __forceinline__ void prep_dense_code(const DgDenseArgs& a, float* sl,
     }
     __syncthreads();
     for (int pos2 = tid; pos2 < np; pos2 += 256) a.inv_norm[o][(size_t)n * a.Ppad + p0 + pos2] = inv[pos2];
-    if (DG_DBG(a.debug) & 16) return;                                 // (ablation: no output phases)
     char* blob0 = a.blob[o] + ((size_t)n * nt + t0) * L.bytes;
     const int GD = KD / 8;
     for (int id = tid; id < ntile * GD * 32; id += 256) {     // C part: granule g of position qq of tile tl
@@ -968,12 +959,12 @@ __global__ __launch_bounds__(256) void k_prep_dense(const DgDenseArgs a) {
     }
     if (!(roles & (z < 2 ? 1 : (z < 4 ? 2 : 4)))) return;         // (a role of the other launch of a split call)
     if (z < 2) {
-        if (!(DG_DBG(a.debug) & 1)) prep_dense_feats<MAXU, FK>(a, sl, x, n, z);
+        prep_dense_feats<MAXU, FK>(a, sl, x, n, z);
     } else if (z < 4) {
         if (a.code_split) {
             if (x * 256 < a.h * a.w) prep_dense_code_norms<UNC>(a, x, n, z - 2);
-        } else if (x * DENSE_TPB < a.Ppad / 32 && !(DG_DBG(a.debug) & 2)) prep_dense_code<UNC>(a, sl, x, n, z - 2);
-    } else if (x == 0 && !(DG_DBG(a.debug) & 4)) {
+        } else if (x * DENSE_TPB < a.Ppad / 32) prep_dense_code<UNC>(a, sl, x, n, z - 2);
+    } else if (x == 0) {
         depth_nz_image(a.depth, a.nz, a.nzsum, n, a.dH, a.dW, a.h, a.h, a.Ppad, true);
     }
 }
@@ -1064,15 +1055,11 @@ hipError_t dg_launch_prep_dense(const DgDenseArgs& a, hipStream_t s) {
     const int smem = max(max(32 * (a.KF * 2 + 16) + 8 * 32 * 4,
                              DENSE_TPB * 32 * (a.KD + 4) * 2 + 4 * DENSE_CODE_PAIRS * 4 + DENSE_TPB * 32 * 4), a.draw_count > 0 ? a.B * 4 : 0);
     if (a.h * ((DENSE_TPB * 32 + a.h - 1) / a.h + 1) > DENSE_CODE_PAIRS) return hipErrorInvalidValue;   // pairs per block
-    DgDenseArgs a2 = a;
-#ifdef DG_DEVTOOLS
-    if (const char* dbg = getenv("DG_PREP_DEBUG")) a2.debug = atoi(dbg);
-#endif
     const dim3 grid(gx * a.B * (a.depth ? 5 : 4) + (a.draw_count > 0 ? a.draw_count : 0));
     auto launch = [&](auto kern) -> hipError_t {
         hipError_t e = dg_set_max_smem(reinterpret_cast<const void*>(kern), smem);
         if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(kern, grid, dim3(256), smem, s, a2);
+        hipLaunchKernelGGL(kern, grid, dim3(256), smem, s, a);
         return hipGetLastError();
     };
     // registers per thread follow the widths

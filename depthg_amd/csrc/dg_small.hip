@@ -87,11 +87,6 @@ __global__ __launch_bounds__(SM_THREADS) __attribute__((amdgpu_waves_per_eu(1, 1
     const int opS = depth_job ? 0 : a.opS[t];
     const int nS = (!depth_job && a.sidx[t]) ? (int)a.sidx[t][n] : n;       // image whose rows the streamed operand is (shared coordinates: the batch map)
 #ifdef DG_DEVTOOLS
-    const int abl = a.debug >> 4;          // developer timing ablations (results invalid): 1 no phase 2b, 2 no gradient work in 2a, 4 one feature chunk
-#else
-    constexpr int abl = 0;
-#endif
-#ifdef DG_DEVTOOLS
     unsigned long long stp[12];
     int nstp = 0;
 #define SM_STAMP() do { if (a.debug == 1) { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); stp[nstp++] = wall_clock64(); } } while (0)
@@ -164,11 +159,6 @@ __global__ __launch_bounds__(SM_THREADS) __attribute__((amdgpu_waves_per_eu(1, 1
             const float inv = okc ? 1.f / fmaxf(sqrtf(s), DG_EPS_NORM) : 0.f;
             if (gran == 0) invC[pass_row(j)] = inv;
             const bool isR = j < NR;
-#ifdef DG_DEVTOOLS
-            if (a.debug == 2 && n == 0 && t == 1 && j == NR && row32 == 20)
-                printf("row 20 gran %d: s %.9g inv %.9g v %.9g %.9g %.9g %.9g | %.9g %.9g %.9g %.9g\n", gran, s, inv, vc[0][j][0][0], vc[0][j][0][1],
-                       vc[0][j][0][2], vc[0][j][0][3], vc[0][j][1][0], vc[0][j][1][1], vc[0][j][1][2], vc[0][j][1][3]);
-#endif
 #pragma unroll
             for (int c = 0; c < 2; ++c) {
                 float xn[8];
@@ -198,7 +188,7 @@ __global__ __launch_bounds__(SM_THREADS) __attribute__((amdgpu_waves_per_eu(1, 1
     };
     // (ONE call site per piece of straight-line code below - every copy of the loader or of the normalisation is a kilobyte of
     //  instructions, and the kernel has to stay inside the 64-KB instruction cache it shares with the neighbouring CU)
-    const int C4 = a.C4, nch = depth_job ? 0 : ((abl & 4) ? 1 : (C4 + KC - 1) / KC);
+    const int C4 = a.C4, nch = depth_job ? 0 : (C4 + KC - 1) / KC;
     const __bf16* srcp[NJ];
     bool ok[NJ];
 #pragma unroll
@@ -461,7 +451,7 @@ __global__ __launch_bounds__(SM_THREADS) __attribute__((amdgpu_waves_per_eu(1, 1
                     }
                 }
             }
-            if (grad && !(abl & 2)) {
+            if (grad) {
                 f16x8 ga[2], gm[2];
 #pragma unroll
                 for (int i = 0; i < 16; ++i) ga[i >> 3][i & 7] = __builtin_bit_cast(_Float16, gh[i]);
@@ -519,7 +509,7 @@ __global__ __launch_bounds__(SM_THREADS) __attribute__((amdgpu_waves_per_eu(1, 1
     }
 
     // ---- phase 2b: d/d(streamed code) = G x over this block's stationary tiles, normalisation backward, final tiles
-    if (grad && !depth_job && !(abl & 1)) {
+    if (grad && !depth_job) {
         for (int st = wid; st < NS; st += 4) {
             f32x16 dS1[NDF], dS2[PW ? NDF : 1];
 #pragma unroll

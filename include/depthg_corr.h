@@ -491,7 +491,7 @@ const char* dg_corr_main_kernel_name(const dg_corr_desc* desc);
 /* Measurement aid: 1 when the fused correlation launch of this descriptor also forms the intra pair-set's streamed-side code
  * gradient (k_corr2's FOLD: helper(feats, feats, code, code) of src/modules.py:1236-1254 is symmetric up to its row-mean centering;
  * DESIGN.md section 4.1) - that share of the algorithmic work then belongs to the fused launch, not to k_gs; 0 otherwise; -1 on a
- * bad desc.  (DG_FOLD_INTRA=0 in the environment switches the fold off.) */
+ * bad desc.  (DG_FOLD_INTRA=0 in the environment switches the fold off: a test seam, see the switch list in dg_common.h.) */
 int dg_corr_intra_folded(const dg_corr_desc* desc);
 
 /*

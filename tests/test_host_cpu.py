@@ -69,6 +69,65 @@ def test_product_does_not_import_oracle():
                 assert "oracle" not in src, f"{fn} mentions the oracle"
 
 
+# The library's switches (depthg_amd/csrc/dg_common.h lists them with what each one does): the environment variables it reads in
+# every build, and the macros its sources may test.  A new experiment is taken out before it merges or added here on purpose.
+LIB_TEST_SEAMS = {"DG_FOLD_INTRA", "DG_SPLIT_MASKS", "DG_C2_WALK"}
+LIB_MACROS = {"__HIPCC__", "DG_DEVTOOLS", "DG_STAMP_BUILD", "C2_STAMPS", "C2_BLOCKLOG", "C2_BLOCKSTAMPS_ONLY", "C2_STAMP_N",
+              "C2_PF", "PF", "GS_CW", "GS_NB", "DG_STAGGER", "DG_PRIO", "DG_F_IG", "DENSE_TPB", "COMB_HB", "COMB_HB_HM",
+              "HEAD_FWD_PD", "HEAD_SPLIT_TARGET"}
+
+
+def _switch_violations(text, name):
+    """getenv calls outside a DG_DEVTOOLS branch that read no test seam, and conditionals on macros off LIB_MACROS."""
+    text = re.sub(r"/\*.*?\*/", lambda m: "\n" * m.group().count("\n"), text, flags=re.S)
+    bad, stack = [], []          # stack: [this branch is DG_DEVTOOLS-only, the #else branch would be] per open conditional
+    for ln, line in enumerate(text.splitlines(), 1):
+        line = line.split("//")[0]
+        m = re.match(r"\s*#\s*(ifdef|ifndef|if|elif|else|endif)\b(.*)", line)
+        if m:
+            kw, expr = m.group(1), m.group(2).strip()
+            if kw in ("ifdef", "ifndef"):
+                names = expr.split()[:1]
+            elif kw in ("if", "elif"):
+                names = [n for n in re.findall(r"[A-Za-z_]\w*", expr) if n != "defined"]
+            else:
+                names = []
+            bad += [f"{name}:{ln}: #{kw} {n}" for n in names if n not in LIB_MACROS]
+            if kw == "ifdef":
+                stack.append([names == ["DG_DEVTOOLS"], False])
+            elif kw == "ifndef":
+                stack.append([False, names == ["DG_DEVTOOLS"]])
+            elif kw == "if":
+                stack.append([re.fullmatch(r"defined\s*\(\s*DG_DEVTOOLS\s*\)(\s*&&.*)?", expr) is not None, False])
+            elif not stack:
+                bad.append(f"{name}:{ln}: #{kw} without #if")
+            elif kw == "endif":
+                stack.pop()
+            else:
+                stack[-1] = [kw == "else" and stack[-1][1], False]
+            continue
+        if any(dev for dev, _ in stack):
+            continue
+        for arg in re.findall(r"getenv\s*\(([^)]*)\)", line):
+            if arg.strip() not in {f'"{s}"' for s in LIB_TEST_SEAMS}:
+                bad.append(f"{name}:{ln}: getenv({arg.strip()}) outside DG_DEVTOOLS")
+    if stack:
+        bad.append(f"{name}: {len(stack)} conditional(s) not closed")
+    return bad
+
+
+def test_library_switches_are_the_listed_ones():
+    csrc = os.path.join(ROOT, "depthg_amd", "csrc")
+    srcs = sorted(fn for fn in os.listdir(csrc) if fn.endswith((".hip", ".h")))
+    assert "dg_corr2.hip" in srcs and "dg_common.h" in srcs
+    bad = [v for fn in srcs for v in _switch_violations(open(os.path.join(csrc, fn)).read(), fn)]
+    assert not bad, "switches not in dg_common.h's list:\n" + "\n".join(bad)
+    # the scan sees an experiment switch of either kind, and leaves alone what DG_DEVTOOLS guards
+    assert len(_switch_violations('#ifdef FOO_ABL\n#endif\nconst char* e = getenv("DG_FOO");\n', "x")) == 2
+    assert not _switch_violations('#ifdef DG_DEVTOOLS\nconst char* e = getenv("DG_STAMPS");\n#endif\n', "x")
+    assert _switch_violations('#ifdef DG_DEVTOOLS\n#else\nconst char* e = getenv("DG_STAMPS");\n#endif\n', "x")
+
+
 def test_decay_schedules_match_reference():
     from depthg_amd import depth_decay as DD
     d = load_golden("decay.npz")
