@@ -21,7 +21,7 @@ EXPORTS = ["dg_version", "dg_last_error", "dg_corr_workspace_bytes", "dg_corr_fo
            "dg_head_backward_pair", "dg_cluster_lookup_forward",
            "dg_cluster_lookup_backward", "dg_probe_ce_forward", "dg_probe_ce_backward", "dg_knn_similarities",
            "dg_prof_main_span", "dg_corr_materialize_shared", "dg_normalize_split", "dg_sampled_sumsq",
-           "dg_corr_forward_extnorm"]
+           "dg_corr_forward_extnorm", "dg_segment_predict"]
 
 
 class CorrDesc(ctypes.Structure):
@@ -82,6 +82,9 @@ def load():
     lib.dg_probe_ce_forward.argtypes = [vp, vp] + [i32] * 6 + [vp] * 3
     lib.dg_probe_ce_backward.restype = ctypes.c_int
     lib.dg_probe_ce_backward.argtypes = [vp] * 4 + [i32] * 6 + [vp] * 2
+    lib.dg_segment_predict.restype = ctypes.c_int
+    lib.dg_segment_predict.argtypes = [vp, vp] + [i32] * 4 + [vp, vp, i32, vp, i32, vp, i32, i32, vp, vp, i32, vp, vp, vp,
+                                                            ctypes.c_size_t, vp]
     lib.dg_corr_main_kernel_name.restype = ctypes.c_char_p
     lib.dg_corr_main_kernel_name.argtypes = [cp]
     lib.dg_corr_intra_folded.restype = ctypes.c_int

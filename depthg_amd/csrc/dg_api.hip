@@ -1529,3 +1529,25 @@ extern "C" int dg_probe_ce_backward(const float* logits, const int64_t* label, c
     DG_HIP(dg_launch_probe_ce_bwd(a, static_cast<hipStream_t>(stream_)));
     return DG_OK;
 }
+
+extern "C" int dg_segment_predict(const float* code, const float* code_flip, int32_t B, int32_t D, int32_t h, int32_t w,
+                                  const float* lin_w, const float* lin_b, int32_t n, const float* clusters, int32_t m,
+                                  const int64_t* label, int32_t H, int32_t W, int64_t* stats_lin, int64_t* stats_clu, int32_t n_store,
+                                  int64_t* preds_lin, int64_t* preds_clu, void* scratch, size_t scratch_bytes, dg_stream_t stream_) {
+    if (B < 1 || D < 1 || h < 1 || w < 1 || n < 1 || m < 1 || H < 1 || W < 1 || n_store < 0)
+        return fail(DG_ERR_INVALID, "bad segment-predict dimensions");
+    if (D > DG_SEG_MAX_D) return fail(DG_ERR_UNSUPPORTED, "segment predict needs D <= %d (got %d)", DG_SEG_MAX_D, D);
+    if (n + m > DG_SEG_MAX_K) return fail(DG_ERR_UNSUPPORTED, "segment predict needs n + m <= %d (got %d)", DG_SEG_MAX_K, n + m);
+    if ((long long)w * dg_seg_kp(n, m) > DG_SEG_ROW_FLOATS)
+        return fail(DG_ERR_UNSUPPORTED, "segment predict needs w * (n + m, each rounded up to 4) <= %d (w=%d)", DG_SEG_ROW_FLOATS, w);
+    if ((long long)h * w > (1 << 24) || (long long)B * H * W > (1LL << 40)) return fail(DG_ERR_UNSUPPORTED, "maps too large");
+    if (!code || !lin_w || !clusters || !label || !scratch) return fail(DG_ERR_INVALID, "null pointer");
+    if (reinterpret_cast<uintptr_t>(scratch) % 16) return fail(DG_ERR_INVALID, "scratch must be 16-byte aligned");
+    const size_t need = (size_t)B * h * w * dg_seg_kp(n, m) * 4;
+    if (scratch_bytes < need) return fail(DG_ERR_WORKSPACE, "scratch of %zu bytes, %zu needed", scratch_bytes, need);
+    if (n_store > B) n_store = B;
+    DgSegArgs a{code, code_flip, lin_w, lin_b, clusters, label, static_cast<float*>(scratch), stats_lin, stats_clu, preds_lin, preds_clu,
+                B, D, h, w, n, m, H, W, n_store};
+    DG_HIP(dg_launch_segment_predict(a, static_cast<hipStream_t>(stream_)));
+    return DG_OK;
+}

@@ -911,3 +911,24 @@ hipError_t dg_launch_cluster_fwd(const DgClusterArgs& a, float* loss_out, hipStr
 hipError_t dg_launch_cluster_bwd(const DgClusterBwdArgs& a, hipStream_t s);
 hipError_t dg_launch_probe_ce_fwd(const DgProbeCeArgs& a, float* out3, hipStream_t s);
 hipError_t dg_launch_probe_ce_bwd(const DgProbeCeArgs& a, hipStream_t s);
+
+// ---- the probes' predictions and confusion counts (dg_eval.hip; src/train_segmentation.py:471-499, src/eval_segmentation.py:146-170)
+struct DgSegArgs {
+    const float* code;       // (B, D, h, w)
+    const float* code_flip;  // (B, D, h, w) second pass on the mirrored image, or null
+    const float* lin_w;      // (n, D)
+    const float* lin_b;      // (n) or null
+    const float* clusters;   // (m, D)
+    const int64_t* label;    // (B, H, W)
+    float* scores;           // scratch (B, h*w, Kp): Kp = n4 + m4 (each part rounded up to 4), linear rows at 0, cluster rows at n4
+    int64_t* stats_lin;      // (n, n) or null
+    int64_t* stats_clu;      // (m, n) or null (rows >= n are never touched)
+    int64_t* preds_lin;      // (n_store, H, W) or null
+    int64_t* preds_clu;      // (n_store, H, W) or null
+    int32_t B, D, h, w, n, m, H, W, n_store;
+};
+#define DG_SEG_MAX_D 1024
+#define DG_SEG_MAX_K 256                     // n + m
+#define DG_SEG_ROW_FLOATS 16384              // w * Kp: one vertically blended score row in LDS
+__host__ __device__ inline int dg_seg_kp(int n, int m) { return (n + 3) / 4 * 4 + (m + 3) / 4 * 4; }
+hipError_t dg_launch_segment_predict(const DgSegArgs& a, hipStream_t s);

@@ -6,6 +6,7 @@
 // The reference materialises (B*H*W, n_classes) logits at label resolution and three masks; here a label pixel's logits are blended
 // in registers and the adjoint of the resize is a gather per low-resolution row (fixed order: no floating-point atomics).
 #include "dg_common.h"
+#include "dg_taps.h"          // resize_taps
 
 #define DG_NORM_EPS 1e-12f       // F.normalize default eps (src/modules.py:668-669 call it without one)
 
@@ -206,16 +207,6 @@ hipError_t dg_launch_cluster_bwd(const DgClusterBwdArgs& a, hipStream_t s) {
 }
 
 // ------------------------------------------------------------------------------------------------ linear probe: resize + CE
-
-// source coordinate of F.interpolate(mode='bilinear', align_corners=False): max((dst + 0.5) * in / out - 0.5, 0)
-__device__ __forceinline__ void resize_taps(const int dst, const int in, const int out, int& i0, int& i1, float& l1) {
-    const float scale = (float)in / (float)out;
-    float src = ((float)dst + 0.5f) * scale - 0.5f;
-    src = src < 0.f ? 0.f : src;
-    i0 = (int)src; if (i0 > in - 1) i0 = in - 1;
-    i1 = i0 < in - 1 ? i0 + 1 : i0;
-    l1 = src - (float)i0;
-}
 
 // forward: block = one label row (b, Y); the two source rows of the logits sit in LDS
 __global__ __launch_bounds__(256) void k_probe_ce_fwd(const DgProbeCeArgs a) {

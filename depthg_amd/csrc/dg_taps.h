@@ -1,5 +1,6 @@
 // The bilinear tap map of sample() (src/modules.py:822-825: grid_sample, border, align_corners=True) and its inverse records - shared by
-// dg_post.hip (the sample() adjoint, k_build_taps / k_pre_general) and dg_prep.hip (the same records as extra blocks of the gather launch).
+// dg_post.hip (the sample() adjoint, k_build_taps / k_pre_general) and dg_prep.hip (the same records as extra blocks of the gather launch);
+// and resize_taps, the tap map of the align_corners=False resize (dg_probe.hip, dg_eval.hip).
 #pragma once
 #include "dg_common.h"
 
@@ -97,4 +98,16 @@ __device__ __forceinline__ void build_taps_block(const DgTapsArgs& t, const int 
     const int ne = off[HW];
     for (int i = tid; i < ne; i += NT) { g_w[i] = ewgt[i]; g_p[i] = eidx[i]; }
 }
+
+// The tap map of F.interpolate(size=(out...), mode='bilinear', align_corners=False) along one axis - dg_probe.hip (the linear probe's
+// loss) and dg_eval.hip (the probes' predictions).  Source coordinate max((dst + 0.5) * in / out - 0.5, 0).
+__device__ __forceinline__ void resize_taps(const int dst, const int in, const int out, int& i0, int& i1, float& l1) {
+    const float scale = (float)in / (float)out;
+    float src = ((float)dst + 0.5f) * scale - 0.5f;
+    src = src < 0.f ? 0.f : src;
+    i0 = (int)src; if (i0 > in - 1) i0 = in - 1;
+    i1 = i0 < in - 1 ? i0 + 1 : i0;
+    l1 = src - (float)i0;
+}
+
 #endif

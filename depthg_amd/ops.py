@@ -326,6 +326,60 @@ def confusion_update(stats, preds, target, n_classes, extra_clusters):
     return stats
 
 
+def segment_predict(code, label, lin_w, lin_b, clusters, code_flip=None, stats_lin=None, stats_clu=None, n_store=0):
+    """The probes' arg-max predictions at the label resolution and their confusion counts (dg_segment_predict; the chain of
+    src/train_segmentation.py:471-499 and, with `code_flip`, src/eval_segmentation.py:146-170 without the CRF).
+    code, code_flip (B,D,h,w); lin_w (n,D) or (n,D,1,1); lin_b (n) or None; clusters (m,D); label (B,H,W) (or any shape ending in
+    (H,W) with B*H*W elements).  stats_lin / stats_clu: int64 (rows, n) on the GPU, += the counts [pred][label] in place (rows >= n
+    are never touched), or None.  Returns (preds_lin, preds_clu), int64 (n_store,H,W), or (None, None) when n_store is 0."""
+    lib = _lib.load()
+    if code.dim() != 4:
+        raise ValueError(f"depthg_amd: code must be (B, D, h, w), got {tuple(code.shape)}")
+    B, D, h, w = code.shape
+    if code_flip is not None and tuple(code_flip.shape) != tuple(code.shape):
+        raise ValueError(f"depthg_amd: code_flip {tuple(code_flip.shape)} differs from code {tuple(code.shape)}")
+    if lin_w.dim() == 4 and tuple(lin_w.shape[2:]) == (1, 1):
+        lin_w = lin_w.reshape(lin_w.shape[0], lin_w.shape[1])
+    if lin_w.dim() != 2 or lin_w.shape[1] != D:
+        raise ValueError(f"depthg_amd: lin_w must be (n, {D}) (a 1x1 convolution's weight), got {tuple(lin_w.shape)}")
+    n = lin_w.shape[0]
+    if lin_b is not None and tuple(lin_b.shape) != (n,):
+        raise ValueError(f"depthg_amd: lin_b must be ({n},), got {tuple(lin_b.shape)}")
+    if clusters.dim() != 2 or clusters.shape[1] != D:
+        raise ValueError(f"depthg_amd: clusters must be (m, {D}), got {tuple(clusters.shape)}")
+    m = clusters.shape[0]
+    if label.dim() < 2 or label.numel() != B * label.shape[-2] * label.shape[-1]:
+        raise ValueError(f"depthg_amd: label must hold (B={B}, H, W) elements, got {tuple(label.shape)}")
+    H, W = label.shape[-2:]
+    for name, st, rows in (("stats_lin", stats_lin, n), ("stats_clu", stats_clu, min(n, m))):
+        if st is not None and (st.dtype != torch.int64 or not st.is_contiguous() or st.dim() != 2 or st.shape[1] != n
+                               or st.shape[0] < rows):
+            raise ValueError(f"depthg_amd: {name} must be a contiguous int64 (rows >= {rows}, {n}) tensor, got "
+                             f"{st.dtype} {tuple(st.shape)}")
+    n_store = int(n_store)
+    if n_store < 0:
+        raise ValueError(f"depthg_amd: n_store must be >= 0, got {n_store}")
+    n_store = min(n_store, B)
+    tensors = (("code", code), ("label", label), ("lin_w", lin_w), ("lin_b", lin_b), ("clusters", clusters),
+               ("code_flip", code_flip), ("stats_lin", stats_lin), ("stats_clu", stats_clu))
+    for name, t in tensors:
+        if t is not None and not t.is_cuda:
+            raise RuntimeError(f"depthg_amd: `{name}` must live on the GPU (got {t.device}); there is no CPU path")
+    dev = code.device
+    code, code_flip = _f32c(code, "code"), _f32c(code_flip, "code_flip")
+    lin_w, lin_b, clusters = _f32c(lin_w, "lin_w"), _f32c(lin_b, "lin_b"), _f32c(clusters, "clusters")
+    lab = label.detach().to(torch.int64).reshape(B, H, W).contiguous()
+    kp = (n + 3) // 4 * 4 + (m + 3) // 4 * 4
+    scratch = _empty((B * h * w * kp * 4,), torch.uint8, dev)
+    preds_lin = _empty((n_store, H, W), torch.int64, dev) if n_store else None
+    preds_clu = _empty((n_store, H, W), torch.int64, dev) if n_store else None
+    rc = lib.dg_segment_predict(_ptr(code), _ptr(code_flip), B, D, h, w, _ptr(lin_w), _ptr(lin_b), n, _ptr(clusters), m, _ptr(lab),
+                                H, W, _ptr(stats_lin), _ptr(stats_clu), n_store, _ptr(preds_lin), _ptr(preds_clu), _ptr(scratch),
+                                scratch.numel(), _stream(dev))
+    _lib.check(rc, "dg_segment_predict")
+    return preds_lin, preds_clu
+
+
 def topk_rows(vals, k, return_values=False):
     """Column indices of the k largest entries of every row of `vals` (rows, cols) fp32 on the GPU: value descending, ties by
     ascending column (src/precompute_knns.py:110 `torch.topk(pairwise_sims, 30)[1]`)."""

@@ -14,7 +14,9 @@ Mirrors, with the reference's names, parameter layout and arithmetic:
                             n_classes / use_depth, forward(x) = net(x)[1], configure_optimizers() -> three Adams,
                             training_step(batch, batch_idx) with manual optimisation: two featurizer passes, the HIP correlation
                             loss (and the second LHP call when cfg.lhp), the weighted total, the live legacy decay of the cfg
-                            scalars, linear-probe cross entropy and cluster-probe loss on the detached code, backward, three steps.
+                            scalars, linear-probe cross entropy and cluster-probe loss on the detached code, backward, three steps;
+                            validation_step / on_validation_epoch_end (:471-535) and evaluate_batch (src/eval_segmentation.py:146-170
+                            without the CRF) score the probes through evaluation.predict_and_score (one HIP launch pair).
 ProjectionHead / ClusterLookup (src/modules.py:647-675) / probe_cross_entropy live in depthg_amd/head.py and are re-exported
 here.  The head, the probes' losses and everything the correlation loss does run in the HIP library; what stays torch is the
 frozen backbone, the 27 x dim linear-probe convolution and the three Adams.  Under data parallelism `all_reduced_parameters()` is
@@ -27,9 +29,11 @@ import torch
 import torch.nn as nn
 
 from .depth_decay import legacy_decay_step
+from .evaluation import predict_and_score
 from .head import ClusterLookup, ProjectionHead, probe_cross_entropy, run_head, run_head_pair
 from .lhp import LocalHiddenPositiveProjection, OriginalLocalHiddenPositiveProjection
 from .loss import ContrastiveCorrelationLoss
+from .metrics import UnsupervisedMetrics
 from .training import correspondence_total
 
 
@@ -116,6 +120,10 @@ class UnsupervisedSegmenter(nn.Module):
         self.train_cluster_probe = ClusterLookup(dim, n_classes)                      # :110
         self.cluster_probe = ClusterLookup(dim, n_classes + cfg.extra_clusters)       # :112
         self.linear_probe = nn.Conv2d(dim, n_classes, (1, 1))                         # :113
+        self.cluster_metrics = UnsupervisedMetrics("test/cluster/", n_classes, cfg.extra_clusters, True)      # :117-125
+        self.linear_metrics = UnsupervisedMetrics("test/linear/", n_classes, 0, False)
+        self.test_cluster_metrics = UnsupervisedMetrics("final/cluster/", n_classes, cfg.extra_clusters, True)
+        self.test_linear_metrics = UnsupervisedMetrics("final/linear/", n_classes, 0, False)
         self.linear_probe_loss_fn = nn.CrossEntropyLoss()                             # :127 (kept for the surface; the step uses the fused HIP loss)
         self.contrastive_corr_loss_fn = ContrastiveCorrelationLoss(cfg)               # :131 (shares cfg: the decay below mutates it)
         for p in self.contrastive_corr_loss_fn.parameters():                          # :136
@@ -126,6 +134,11 @@ class UnsupervisedSegmenter(nn.Module):
         self.automatic_optimization = False                                           # :139
         self.global_step = 0
         self._optims = None
+        self.validation_step_outputs = []                                             # :149-157
+        self.max_cluster_accuracy = 0.0
+        self.max_cluster_miou = 0.0
+        self.max_linear_accuracy = 0.0
+        self.max_linear_miou = 0.0
 
     def forward(self, x):
         return self.net(x)[1]                                                          # :160-167
@@ -219,6 +232,66 @@ class UnsupervisedSegmenter(nn.Module):
         self.global_step += 1
         return loss.detach(), logs
 
+    def _eval_mode_codes(self, img, flip):
+        """code = net(img)[1] (and of the mirrored images when `flip`) with the net in eval mode; the net's mode is restored after
+        (what Lightning does around its validation loop: the next training_step needs the training-mode 3-tuple)."""
+        was_training = self.net.training
+        self.net.eval()
+        try:
+            with torch.no_grad():
+                code = self.net(img)[1]
+                code_flip = self.net(img.flip(dims=[3]))[1] if flip else None
+        finally:
+            self.net.train(was_training)
+        return code, code_flip
+
+    def validation_step(self, batch: Dict[str, torch.Tensor], batch_idx: int = 0):
+        """src/train_segmentation.py:471-499: the probes' arg-max predictions at the label resolution into linear_metrics /
+        cluster_metrics, one HIP launch pair (evaluation.predict_and_score) instead of the resize, 1x1 convolution, cosine
+        similarities and bincounts at label resolution.  Appends and returns the first cfg.n_images of img, linear_preds,
+        cluster_preds and label, on the CPU."""
+        img, label = batch["img"], batch["label"]
+        k = int(getattr(self.cfg, "n_images", 5))
+        code, _ = self._eval_mode_codes(img, False)
+        linear_preds, cluster_preds = predict_and_score(code, label, self.linear_probe, self.cluster_probe, self.linear_metrics,
+                                                        self.cluster_metrics, n_store=k)
+        none = torch.empty((0,) + tuple(label.shape[-2:]), dtype=torch.int64)          # (n_images = 0)
+        out = {"img": img[:k].detach().cpu(),
+               "linear_preds": linear_preds.cpu() if linear_preds is not None else none,
+               "cluster_preds": cluster_preds.cpu() if cluster_preds is not None else none.clone(),
+               "label": label[:k].detach().cpu()}
+        self.validation_step_outputs.append(out)
+        return out
+
+    def on_validation_epoch_end(self) -> Dict[str, float]:
+        """src/train_segmentation.py:501-535 without the logger: both metrics, the running maxima, reset; returns the metrics."""
+        tb_metrics = {**self.linear_metrics.compute(), **self.cluster_metrics.compute()}
+        if tb_metrics["test/cluster/Accuracy"] > self.max_cluster_accuracy:
+            self.max_cluster_accuracy = tb_metrics["test/cluster/Accuracy"]
+        if tb_metrics["test/cluster/mIoU"] > self.max_cluster_miou:
+            self.max_cluster_miou = tb_metrics["test/cluster/mIoU"]
+        if tb_metrics["test/linear/Accuracy"] > self.max_linear_accuracy:
+            self.max_linear_accuracy = tb_metrics["test/linear/Accuracy"]
+        if tb_metrics["test/linear/mIoU"] > self.max_linear_miou:
+            self.max_linear_miou = tb_metrics["test/linear/mIoU"]
+        tb_metrics["test/cluster/MaxAccuracy"] = self.max_cluster_accuracy
+        tb_metrics["test/cluster/MaxmIoU"] = self.max_cluster_miou
+        tb_metrics["test/linear/MaxAccuracy"] = self.max_linear_accuracy
+        tb_metrics["test/linear/MaxmIoU"] = self.max_linear_miou
+        self.linear_metrics.reset()
+        self.cluster_metrics.reset()
+        self.validation_step_outputs.clear()
+        return tb_metrics
+
+    def evaluate_batch(self, batch: Dict[str, torch.Tensor], flip: bool = True):
+        """src/eval_segmentation.py:146-170 without the CRF: code of the image and (flip) of its mirror, averaged as
+        (code1 + code2.flip(3)) / 2 inside the projection, the probes' arg-max predictions into test_linear_metrics /
+        test_cluster_metrics.  Returns (linear_preds, cluster_preds) (B,H,W) int64 on the GPU."""
+        img, label = batch["img"], batch["label"]
+        code, code_flip = self._eval_mode_codes(img, flip)
+        return predict_and_score(code, label, self.linear_probe, self.cluster_probe, self.test_linear_metrics,
+                                 self.test_cluster_metrics, code_flip=code_flip, n_store=img.shape[0])
+
 
 def default_segmenter_cfg(**over) -> SimpleNamespace:
     """The keys training_step and the featurizer read, with the values of src/configs/local_config.yml."""
@@ -236,7 +309,9 @@ def default_segmenter_cfg(**over) -> SimpleNamespace:
         depth_loss_decay=True, depth_loss_decay_factor=0.6, decay_every_steps=250, fix_depth_feat_shift=False,
         fps_until_step=0, post_fps_samples=11, fps_sample_decay=True, fps_sample_decay_every_steps=1000,
         fps_sample_decay_factor=0.9, fps_min_samples=0, lhp=False, lhp_weight=0.2, lhp_weight_balance=False,
-        lhp_depth_weight=0.5)
+        lhp_depth_weight=0.5,
+        # validation
+        n_images=5)
     for k, v in over.items():
         setattr(cfg, k, v)
     return cfg

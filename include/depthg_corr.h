@@ -484,6 +484,27 @@ int dg_probe_ce_forward(const float* logits, const int64_t* label, int32_t B, in
 int dg_probe_ce_backward(const float* logits, const int64_t* label, const float* out3, const float* grad_loss, int32_t B, int32_t n,
                          int32_t h, int32_t w, int32_t H, int32_t W, float* grad_logits, dg_stream_t stream);
 
+/*
+ * The probes' predictions at label resolution and their confusion counts: validation_step (src/train_segmentation.py:471-499:
+ * F.interpolate(code, label size, bilinear, align_corners=False) -> linear_probe -> argmax / cluster_probe(code, None) -> argmax ->
+ * linear_metrics / cluster_metrics.update) and eval_segmentation.py:146-170 without the CRF (code = (code + code_flip.flip(3)) / 2
+ * first).  Both arg-maxes commute with the resize (the tap weights sum to 1; the pixel norm of the cosine is one positive factor),
+ * so the code is projected at feature resolution and only the (n + m)-row score maps are resized, per label pixel; ties go to the
+ * lowest index (torch.argmax).
+ *  code : fp32 (B,D,h,w)    code_flip : fp32 (B,D,h,w), the pass on the horizontally mirrored image, or NULL
+ *  lin_w : fp32 (n,D), lin_b : fp32 (n) or NULL  (Conv2d(D, n, 1))    clusters : fp32 (m,D) (ClusterLookup.clusters, normalised here)
+ *  label : int64 (B,H,W)
+ *  stats_lin : int64 (n,n), stats_clu : int64 (m,n), each += the counts [pred][label] over the pixels with 0 <= label < n and
+ *      0 <= pred < n (UnsupervisedMetrics.update, src/utils.py:222-232: rows >= n of stats_clu are never touched), or NULL
+ *  preds_lin, preds_clu : int64 (n_store,H,W) out, the arg-maxes of the first n_store images, or NULL
+ *  scratch : B*h*w*(n4 + m4)*4 bytes, 16-byte aligned (n4, m4: n, m rounded up to a multiple of 4)
+ * Limits (DG_ERR_UNSUPPORTED beyond them): D <= 1024, n + m <= 256, w * (n4 + m4) <= 16384.  No allocation, two launches.
+ */
+int dg_segment_predict(const float* code, const float* code_flip, int32_t B, int32_t D, int32_t h, int32_t w,
+                       const float* lin_w, const float* lin_b, int32_t n, const float* clusters, int32_t m,
+                       const int64_t* label, int32_t H, int32_t W, int64_t* stats_lin, int64_t* stats_clu, int32_t n_store,
+                       int64_t* preds_lin, int64_t* preds_clu, void* scratch, size_t scratch_bytes, dg_stream_t stream);
+
 /* Measurement aid: name of the kernel the fused correlation launch of this descriptor runs ("k_corr2": the one-wave-per-SIMD
  * form of dg_corr2.hip, "k_corr_main": the general form), decided by the same predicate the launch uses; NULL on a bad desc. */
 const char* dg_corr_main_kernel_name(const dg_corr_desc* desc);
