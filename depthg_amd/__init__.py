@@ -7,7 +7,8 @@ Public surface (mirrors the reference's Python operator surface for this path):
                                  src/train_segmentation.py:240-350)
     metrics                      UnsupervisedMetrics (src/utils.py:202-319): confusion matrix on the GPU, summed over DP ranks
     evaluation                   predict_and_score: the probes' predictions at label resolution and their confusion counts
-                                 (src/train_segmentation.py:471-499, src/eval_segmentation.py:146-170 without the CRF)
+                                 (src/train_segmentation.py:471-499, src/eval_segmentation.py:146-170, run_crf for the CRF)
+    crf                          dense_crf / batched_crf (src/crf.py, src/eval_segmentation.py:55-60): mean-field dense CRF in HIP
     knn                          image-level nearest-neighbour table: search, file format, online pick (src/precompute_knns.py)
     lhp                          LocalHiddenPositiveProjection with depth propagation (src/modules.py:140-339)
     segmenter                    the producers and the caller: projection head, stand-in featurizer, cluster probe, one optimisation
@@ -20,8 +21,11 @@ from . import training  # noqa: F401
 from . import metrics  # noqa: F401
 from . import evaluation  # noqa: F401
 from .evaluation import predict_and_score  # noqa: F401
+from . import crf  # noqa: F401
+from .crf import batched_crf, dense_crf  # noqa: F401
 from . import knn  # noqa: F401
 from . import lhp  # noqa: F401
 from . import segmenter  # noqa: F401
 
-__all__ = ["ContrastiveCorrelationLoss", "depth_decay", "training", "metrics", "evaluation", "predict_and_score", "knn", "lhp", "segmenter"]
+__all__ = ["ContrastiveCorrelationLoss", "depth_decay", "training", "metrics", "evaluation", "predict_and_score", "crf", "dense_crf",
+           "batched_crf", "knn", "lhp", "segmenter"]

@@ -21,7 +21,8 @@ EXPORTS = ["dg_version", "dg_last_error", "dg_corr_workspace_bytes", "dg_corr_fo
            "dg_head_backward_pair", "dg_cluster_lookup_forward",
            "dg_cluster_lookup_backward", "dg_probe_ce_forward", "dg_probe_ce_backward", "dg_knn_similarities",
            "dg_prof_main_span", "dg_corr_materialize_shared", "dg_normalize_split", "dg_sampled_sumsq",
-           "dg_corr_forward_extnorm", "dg_segment_predict"]
+           "dg_corr_forward_extnorm", "dg_segment_predict", "dg_crf_workspace_bytes", "dg_crf_unary",
+           "dg_segment_unary", "dg_crf_filter", "dg_dense_crf"]
 
 
 class CorrDesc(ctypes.Structure):
@@ -85,6 +86,16 @@ def load():
     lib.dg_segment_predict.restype = ctypes.c_int
     lib.dg_segment_predict.argtypes = [vp, vp] + [i32] * 4 + [vp, vp, i32, vp, i32, vp, i32, i32, vp, vp, i32, vp, vp, vp,
                                                             ctypes.c_size_t, vp]
+    lib.dg_crf_workspace_bytes.restype = ctypes.c_size_t
+    lib.dg_crf_workspace_bytes.argtypes = [i32] * 5
+    lib.dg_crf_unary.restype = ctypes.c_int
+    lib.dg_crf_unary.argtypes = [vp] + [i32] * 6 + [vp, i32, vp, vp]
+    lib.dg_segment_unary.restype = ctypes.c_int
+    lib.dg_segment_unary.argtypes = [vp, vp] + [i32] * 4 + [vp, vp, i32, vp, i32, i32, i32, f32, vp, vp, ctypes.c_size_t, vp]
+    lib.dg_crf_filter.restype = ctypes.c_int
+    lib.dg_crf_filter.argtypes = [vp, vp] + [i32] * 5 + [f32, f32, vp, vp, ctypes.c_size_t, vp]
+    lib.dg_dense_crf.restype = ctypes.c_int
+    lib.dg_dense_crf.argtypes = [vp, vp] + [i32] * 3 + [vp, i32, i32] + [f32] * 5 + [vp, vp, vp, ctypes.c_size_t, vp]
     lib.dg_corr_main_kernel_name.restype = ctypes.c_char_p
     lib.dg_corr_main_kernel_name.argtypes = [cp]
     lib.dg_corr_intra_folded.restype = ctypes.c_int

@@ -172,8 +172,8 @@ __global__ __launch_bounds__(SS_THREADS) void k_seg_score(const DgSegArgs a, con
     }
 }
 
-// compute units of the current device, asked once per device
-static int seg_cu_count() {
+// compute units of the current device, asked once per device (also dg_crf.hip)
+int dg_cu_count() {
     static std::mutex mu;
     static std::map<int, int> cus;
     int dev = 0;
@@ -187,13 +187,21 @@ static int seg_cu_count() {
     return cu;
 }
 
-hipError_t dg_launch_segment_predict(const DgSegArgs& a, hipStream_t s) {
+// the score rows at feature resolution into a.scores (also the CRF's eval-route unary, dg_crf.hip)
+hipError_t dg_launch_seg_project(const DgSegArgs& a, hipStream_t s) {
     const int hw = a.h * a.w, Kp = dg_seg_kp(a.n, a.m);
     const int psmem = a.D * SP_KC * 4;
     const auto kp = a.code_flip ? k_seg_project<true> : k_seg_project<false>;
     hipError_t e = dg_set_max_smem(reinterpret_cast<const void*>(kp), psmem);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(kp, dim3((hw + SP_THREADS - 1) / SP_THREADS, (Kp + SP_KC - 1) / SP_KC, a.B), dim3(SP_THREADS), psmem, s, a);
+    return hipGetLastError();
+}
+
+hipError_t dg_launch_segment_predict(const DgSegArgs& a, hipStream_t s) {
+    const int Kp = dg_seg_kp(a.n, a.m);
+    hipError_t e = dg_launch_seg_project(a, s);
+    if (e != hipSuccess) return e;
     // chunk = R label rows: enough pixels for two passes of the block, as many blended rows as 64 KiB of LDS hold
     const int row_bytes = a.w * Kp * 4;
     int R = (2 * SS_THREADS + a.W - 1) / a.W;
@@ -202,7 +210,7 @@ hipError_t dg_launch_segment_predict(const DgSegArgs& a, hipStream_t s) {
     R = R < 1 ? 1 : R;
     const long long nrows = (long long)a.B * a.H;
     const long long nchunks = (nrows + R - 1) / R;
-    const int cu = seg_cu_count();
+    const int cu = dg_cu_count();
     const int blocks = (int)(nchunks < cu ? nchunks : cu);
     const bool ldshist = (size_t)2 * a.n * a.n * 4 <= SS_HIST_BYTES;
     const int smem = (ldshist ? ((2 * a.n * a.n * 4 + 15) / 16 * 16) : 0) + R * row_bytes;

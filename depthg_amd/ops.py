@@ -380,6 +380,131 @@ def segment_predict(code, label, lin_w, lin_b, clusters, code_flip=None, stats_l
     return preds_lin, preds_clu
 
 
+def _crf_groups(group_ends, C=None):
+    ends = [int(e) for e in group_ends]
+    if not ends or any(b <= a for a, b in zip([0] + ends, ends)) or (C is not None and ends[-1] != C):
+        raise ValueError(f"depthg_amd: group ends must rise strictly from above 0 to the channel count ({C}), got {ends}")
+    kp = sum((b - a + 3) // 4 * 4 for a, b in zip([0] + ends, ends))
+    return ends, (ctypes.c_int32 * len(ends))(*ends), kp
+
+
+CRF_WORKSPACE_BUDGET = 1 << 30        # bytes dense_crf / crf_filter allocate at most beyond one image's need (images go in chunks)
+
+
+def _crf_workspace(lib, B, H, W, kp, dev, budget, lattices):
+    """The workspace of the largest chunk of images that fits `budget` (at least one image); lattices: 1 Gaussian, 2 bilateral,
+    3 both."""
+    one = lib.dg_crf_workspace_bytes(1, H, W, kp, lattices)
+    if one == 0:
+        raise ValueError(f"depthg_amd: no CRF workspace plan for {H}x{W} pixels and {kp} padded channels")
+    c = max(1, min(B, int(budget) // one))
+    while c > 1 and not 0 < lib.dg_crf_workspace_bytes(c, H, W, kp, lattices) <= budget:     # 0: the chunk is refused
+        c -= 1
+    return _empty((lib.dg_crf_workspace_bytes(c, H, W, kp, lattices),), torch.uint8, dev)
+
+
+def _crf_image(img, B, H, W):
+    if img.dim() != 4 or tuple(img.shape) != (B, 3, H, W):
+        raise ValueError(f"depthg_amd: img must be ({B}, 3, {H}, {W}), got {tuple(img.shape)}")
+    return _f32c(img, "img")
+
+
+def crf_unary(logits, H, W, group_ends=None):
+    """U = -log(clip(softmax(interp(logits)), 1e-5, 1)) (dg_crf_unary; src/crf.py:27-35): logits (B,C,h,w) fp32 on the GPU resized
+    to (H,W) (bilinear, align_corners=False), one softmax per channel group (group_ends; None: one group).  Returns (B,C,H,W)."""
+    lib = _lib.load()
+    if logits.dim() != 4:
+        raise ValueError(f"depthg_amd: logits must be (B, C, h, w), got {tuple(logits.shape)}")
+    B, C, h, w = logits.shape
+    _, ends, _ = _crf_groups([C] if group_ends is None else group_ends, C)
+    logits = _f32c(logits, "logits")
+    U = _empty((B, C, int(H), int(W)), torch.float32, logits.device)
+    rc = lib.dg_crf_unary(_ptr(logits), B, C, h, w, int(H), int(W), ends, len(ends), _ptr(U), _stream(logits.device))
+    _lib.check(rc, "dg_crf_unary")
+    return U
+
+
+def segment_unary(code, lin_w, lin_b, clusters, H, W, code_flip=None, alpha=2.0):
+    """The evaluation's CRF unary (dg_segment_unary; src/eval_segmentation.py:150-167): code (B,D,h,w) (averaged with
+    code_flip.flip(3) when given) resized to (H,W), linear probe lin_w (n,D) / lin_b -> channels [0, n), cluster probe (clusters
+    (m,D), alpha) -> channels [n, n + m), U per probe.  Returns (B, n + m, H, W) fp32."""
+    lib = _lib.load()
+    if code.dim() != 4:
+        raise ValueError(f"depthg_amd: code must be (B, D, h, w), got {tuple(code.shape)}")
+    B, D, h, w = code.shape
+    if code_flip is not None and tuple(code_flip.shape) != tuple(code.shape):
+        raise ValueError(f"depthg_amd: code_flip {tuple(code_flip.shape)} differs from code {tuple(code.shape)}")
+    if lin_w.dim() == 4 and tuple(lin_w.shape[2:]) == (1, 1):
+        lin_w = lin_w.reshape(lin_w.shape[0], lin_w.shape[1])
+    if lin_w.dim() != 2 or lin_w.shape[1] != D:
+        raise ValueError(f"depthg_amd: lin_w must be (n, {D}), got {tuple(lin_w.shape)}")
+    n = lin_w.shape[0]
+    if lin_b is not None and tuple(lin_b.shape) != (n,):
+        raise ValueError(f"depthg_amd: lin_b must be ({n},), got {tuple(lin_b.shape)}")
+    if clusters.dim() != 2 or clusters.shape[1] != D:
+        raise ValueError(f"depthg_amd: clusters must be (m, {D}), got {tuple(clusters.shape)}")
+    m = clusters.shape[0]
+    dev = code.device
+    code, code_flip = _f32c(code, "code"), _f32c(code_flip, "code_flip")
+    lin_w, lin_b, clusters = _f32c(lin_w, "lin_w"), _f32c(lin_b, "lin_b"), _f32c(clusters, "clusters")
+    kp = (n + 3) // 4 * 4 + (m + 3) // 4 * 4
+    scratch = _empty((B * h * w * kp * 4,), torch.uint8, dev)
+    U = _empty((B, n + m, int(H), int(W)), torch.float32, dev)
+    rc = lib.dg_segment_unary(_ptr(code), _ptr(code_flip), B, D, h, w, _ptr(lin_w), _ptr(lin_b), n, _ptr(clusters), m, int(H), int(W),
+                              float(alpha), _ptr(U), _ptr(scratch), scratch.numel(), _stream(dev))
+    _lib.check(rc, "dg_segment_unary")
+    return U
+
+
+def crf_filter(values, img=None, bilateral=False, sxy=1.0, srgb=3.0, workspace_budget=CRF_WORKSPACE_BUDGET):
+    """One normalised dense-CRF message K~(values) = norm * K(norm * values) (dg_crf_filter; densecrf's DenseKernel with
+    NORMALIZE_SYMMETRIC): the Gaussian kernel over (x, y) / sxy, or (bilateral) over ((x, y) / sxy, (B, G, R) / srgb) of the
+    normalised image img (B,3,H,W).  values (B,C,H,W) fp32 on the GPU; returns (B,C,H,W)."""
+    lib = _lib.load()
+    if values.dim() != 4:
+        raise ValueError(f"depthg_amd: values must be (B, C, H, W), got {tuple(values.shape)}")
+    B, C, H, W = values.shape
+    values = _f32c(values, "values")
+    if bilateral:
+        if img is None:
+            raise ValueError("depthg_amd: the bilateral kernel needs the image")
+        img = _crf_image(img, B, H, W)
+    elif img is not None:
+        img = _crf_image(img, B, H, W)
+    dev = values.device
+    kp = (C + 3) // 4 * 4
+    ws = _crf_workspace(lib, B, H, W, kp, dev, workspace_budget, 2 if bilateral else 1)
+    out = _empty((B, C, H, W), torch.float32, dev)
+    rc = lib.dg_crf_filter(_ptr(img), _ptr(values), B, C, H, W, int(bool(bilateral)), float(sxy), float(srgb), _ptr(out), _ptr(ws),
+                           ws.numel(), _stream(dev))
+    _lib.check(rc, "dg_crf_filter")
+    return out
+
+
+def dense_crf(img, unary, group_ends=None, n_iter=10, pos_w=3.0, pos_xy_std=1.0, bi_w=4.0, bi_xy_std=67.0, bi_rgb_std=3.0,
+              return_q=True, return_preds=False, workspace_budget=CRF_WORKSPACE_BUDGET):
+    """Mean-field dense CRF (dg_dense_crf; src/crf.py dense_crf): img (B,3,H,W) normalised, unary U (B,C,H,W) fp32 on the GPU, one
+    softmax per channel group (group_ends; None: one group).  Returns (Q (B,C,H,W) fp32 or None, preds (G,B,H,W) int64 or None):
+    preds[g] is the arg-max of Q within group g, counted from the group's first channel."""
+    lib = _lib.load()
+    if unary.dim() != 4:
+        raise ValueError(f"depthg_amd: unary must be (B, C, H, W), got {tuple(unary.shape)}")
+    B, C, H, W = unary.shape
+    ends, cends, kp = _crf_groups([C] if group_ends is None else group_ends, C)
+    if not (return_q or return_preds):
+        raise ValueError("depthg_amd: dense_crf needs return_q or return_preds")
+    unary = _f32c(unary, "unary")
+    img = _crf_image(img, B, H, W)
+    dev = unary.device
+    ws = _crf_workspace(lib, B, H, W, kp, dev, workspace_budget, 3)
+    q = _empty((B, C, H, W), torch.float32, dev) if return_q else None
+    preds = _empty((len(ends), B, H, W), torch.int64, dev) if return_preds else None
+    rc = lib.dg_dense_crf(_ptr(img), _ptr(unary), B, H, W, cends, len(ends), int(n_iter), float(pos_w), float(pos_xy_std), float(bi_w),
+                          float(bi_xy_std), float(bi_rgb_std), _ptr(q), _ptr(preds), _ptr(ws), ws.numel(), _stream(dev))
+    _lib.check(rc, "dg_dense_crf")
+    return q, preds
+
+
 def topk_rows(vals, k, return_values=False):
     """Column indices of the k largest entries of every row of `vals` (rows, cols) fp32 on the GPU: value descending, ties by
     ascending column (src/precompute_knns.py:110 `torch.topk(pairwise_sims, 30)[1]`)."""

@@ -15,8 +15,8 @@ Mirrors, with the reference's names, parameter layout and arithmetic:
                             training_step(batch, batch_idx) with manual optimisation: two featurizer passes, the HIP correlation
                             loss (and the second LHP call when cfg.lhp), the weighted total, the live legacy decay of the cfg
                             scalars, linear-probe cross entropy and cluster-probe loss on the detached code, backward, three steps;
-                            validation_step / on_validation_epoch_end (:471-535) and evaluate_batch (src/eval_segmentation.py:146-170
-                            without the CRF) score the probes through evaluation.predict_and_score (one HIP launch pair).
+                            validation_step / on_validation_epoch_end (:471-535) and evaluate_batch (src/eval_segmentation.py:146-170,
+                            run_crf for the dense CRF) score the probes through evaluation.predict_and_score.
 ProjectionHead / ClusterLookup (src/modules.py:647-675) / probe_cross_entropy live in depthg_amd/head.py and are re-exported
 here.  The head, the probes' losses and everything the correlation loss does run in the HIP library; what stays torch is the
 frozen backbone, the 27 x dim linear-probe convolution and the three Adams.  Under data parallelism `all_reduced_parameters()` is
@@ -283,14 +283,16 @@ class UnsupervisedSegmenter(nn.Module):
         self.validation_step_outputs.clear()
         return tb_metrics
 
-    def evaluate_batch(self, batch: Dict[str, torch.Tensor], flip: bool = True):
-        """src/eval_segmentation.py:146-170 without the CRF: code of the image and (flip) of its mirror, averaged as
-        (code1 + code2.flip(3)) / 2 inside the projection, the probes' arg-max predictions into test_linear_metrics /
-        test_cluster_metrics.  Returns (linear_preds, cluster_preds) (B,H,W) int64 on the GPU."""
+    def evaluate_batch(self, batch: Dict[str, torch.Tensor], flip: bool = True, run_crf: bool = False):
+        """src/eval_segmentation.py:146-170: code of the image and (flip) of its mirror, averaged as (code1 + code2.flip(3)) / 2
+        inside the projection, the probes' arg-max predictions into test_linear_metrics / test_cluster_metrics; with run_crf
+        (eval_config.yml's run_crf) both probes' outputs are refined by the dense CRF on the batch's images first (:162-167).
+        Returns (linear_preds, cluster_preds) (B,H,W) int64 on the GPU."""
         img, label = batch["img"], batch["label"]
         code, code_flip = self._eval_mode_codes(img, flip)
         return predict_and_score(code, label, self.linear_probe, self.cluster_probe, self.test_linear_metrics,
-                                 self.test_cluster_metrics, code_flip=code_flip, n_store=img.shape[0])
+                                 self.test_cluster_metrics, code_flip=code_flip, n_store=img.shape[0], img=img if run_crf else None,
+                                 run_crf=run_crf)
 
 
 def default_segmenter_cfg(**over) -> SimpleNamespace:

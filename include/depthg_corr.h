@@ -505,6 +505,52 @@ int dg_segment_predict(const float* code, const float* code_flip, int32_t B, int
                        const int64_t* label, int32_t H, int32_t W, int64_t* stats_lin, int64_t* stats_clu, int32_t n_store,
                        int64_t* preds_lin, int64_t* preds_clu, void* scratch, size_t scratch_bytes, dg_stream_t stream);
 
+/*
+ * Dense-CRF refinement of the evaluation: src/crf.py dense_crf (pydensecrf's DenseCRF2D with addPairwiseGaussian(sxy=POS_XY_STD,
+ * compat=POS_W), addPairwiseBilateral(sxy=Bi_XY_STD, srgb=Bi_RGB_STD, rgbim=image, compat=Bi_W), inference(MAX_ITER)), run per image
+ * by batched_crf (src/eval_segmentation.py:55-60) on both probes' outputs (:162-167).  Mean field over permutohedral lattices built on
+ * the GPU; channels come in groups (one softmax each), so several probes share one lattice and one filter pass.  Deterministic: two
+ * identical calls give identical bits.
+ *  img : fp32 (B,3,H,W) normalised as the loader does (T.Normalize, src/utils.py:139); the colour image is UnNormalize
+ *      (src/utils.py:132-136: v * std + mean, two fp32 roundings) then mul(255).byte() (to_pil_image), BGR order; values outside
+ *      [0, 255] are clamped (undefined in the reference)
+ *  group_ends : HOST int32 (n_groups), strictly rising from above 0; group g = channels [ends[g-1], ends[g]); n_groups <= 8
+ *  Kp : the channels with each group rounded up to a multiple of 4; Kp <= 256
+ *  workspace : 256-byte aligned; the images are processed in chunks of the largest count c <= B with
+ *      dg_crf_workspace_bytes(c, H, W, Kp, lattices) <= workspace_bytes (at least one image must fit: DG_ERR_WORKSPACE)
+ *  The packed vertex keys must fit 63 bits (the range follows from H, W and the standard deviations; the bits above hold the image
+ *  of the chunk): DG_ERR_UNSUPPORTED otherwise.
+ */
+/* lattices: 1 the Gaussian one (dg_crf_filter with bilateral = 0), 2 the bilateral one (bilateral = 1), 3 both (dg_dense_crf).
+ * 0 on bad arguments, and where (d + 1) * chunk * H * W * Kp / 4 reaches 2^30 (d = 5 when the bilateral lattice is in). */
+size_t dg_crf_workspace_bytes(int32_t chunk, int32_t H, int32_t W, int32_t Kp, int32_t lattices);
+/* U = -log(clip(softmax(interp(logits)), 1e-5, 1)) per group (src/crf.py:27-35: F.interpolate(bilinear, align_corners=False) to
+ * (H,W), F.softmax over the channels, pydensecrf.utils.unary_from_softmax).  logits : fp32 (B,C,h,w); unary : fp32 (B,C,H,W) out */
+int dg_crf_unary(const float* logits, int32_t B, int32_t C, int32_t h, int32_t w, int32_t H, int32_t W, const int32_t* group_ends,
+                 int32_t n_groups, float* unary, dg_stream_t stream);
+/* The evaluation's unary straight from the code (src/eval_segmentation.py:150-167): code = (code + code_flip.flip(3)) / 2 when
+ * code_flip is given, F.interpolate to (H,W), linear probe -> channels [0, n), ClusterLookup(alpha) -> channels [n, n + m), and U of
+ * dg_crf_unary with the groups {n, n + m} (the softmax of the reference's log_softmax is the softmax).  The probes are projected at
+ * feature resolution (dg_segment_predict's projection) and resized per label pixel; the cluster rows are divided by the norm of the
+ * resized code at that pixel.  Arguments as dg_segment_predict; unary : fp32 (B, n + m, H, W) out;
+ * scratch : B*h*w*(n4 + m4)*4 bytes, 16-byte aligned. */
+int dg_segment_unary(const float* code, const float* code_flip, int32_t B, int32_t D, int32_t h, int32_t w, const float* lin_w,
+                     const float* lin_b, int32_t n, const float* clusters, int32_t m, int32_t H, int32_t W, float alpha, float* unary,
+                     void* scratch, size_t scratch_bytes, dg_stream_t stream);
+/* One normalised message K~(v) = norm . K(norm . v) of a DenseKernel with NORMALIZE_SYMMETRIC (densecrf's DenseKernel::apply): the
+ * Gaussian kernel over (x, y) / sxy (bilateral = 0, img may be NULL) or the bilateral one over ((x, y) / sxy, (B, G, R) / srgb).
+ * Without the Potts weight.  values, out : fp32 (B,C,H,W); Kp = C rounded up to 4 for the workspace. */
+int dg_crf_filter(const float* img, const float* values, int32_t B, int32_t C, int32_t H, int32_t W, int32_t bilateral, float sxy,
+                  float srgb, float* out, void* workspace, size_t workspace_bytes, dg_stream_t stream);
+/* Mean-field inference (densecrf's DenseCRF::inference): Q0 = softmax(-U), then n_iter times
+ * Q = softmax(-U + pos_w K~g(Q) + bi_w K~b(Q)) per group (the per-pixel maximum subtracted first).
+ *  unary : fp32 (B,C,H,W), C = group_ends[n_groups - 1]
+ *  q : fp32 (B,C,H,W) out, or NULL    preds : int64 (n_groups,B,H,W) out, the arg-max of Q within each group (lowest index on
+ *  ties; the index counts from the group's first channel), or NULL; not both NULL.  No host synchronisation, no allocation. */
+int dg_dense_crf(const float* img, const float* unary, int32_t B, int32_t H, int32_t W, const int32_t* group_ends, int32_t n_groups,
+                 int32_t n_iter, float pos_w, float pos_xy_std, float bi_w, float bi_xy_std, float bi_rgb_std, float* q, int64_t* preds,
+                 void* workspace, size_t workspace_bytes, dg_stream_t stream);
+
 /* Measurement aid: name of the kernel the fused correlation launch of this descriptor runs ("k_corr2": the one-wave-per-SIMD
  * form of dg_corr2.hip, "k_corr_main": the general form), decided by the same predicate the launch uses; NULL on a bad desc. */
 const char* dg_corr_main_kernel_name(const dg_corr_desc* desc);
