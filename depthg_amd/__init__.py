@@ -13,6 +13,8 @@ Public surface (mirrors the reference's Python operator surface for this path):
     lhp                          LocalHiddenPositiveProjection with depth propagation (src/modules.py:140-339)
     segmenter                    the producers and the caller: projection head, stand-in featurizer, cluster probe, one optimisation
                                  step of LitUnsupervisedSegmenter (src/modules.py:19-137,647-675; src/train_segmentation.py:71-462)
+    optim                        FusedAdam / FusedAdamSet: the step's three torch.optim.Adam (src/train_segmentation.py:447-455,537-547)
+                                 as one HIP launch, torch's state layout (cfg.dg_fused_adam in the segmenter)
     ops                          thin ctypes binding of the C ABI in include/depthg_corr.h
 """
 from .loss import ContrastiveCorrelationLoss  # noqa: F401
@@ -25,7 +27,9 @@ from . import crf  # noqa: F401
 from .crf import batched_crf, dense_crf  # noqa: F401
 from . import knn  # noqa: F401
 from . import lhp  # noqa: F401
+from . import optim  # noqa: F401
+from .optim import FusedAdam, FusedAdamSet  # noqa: F401
 from . import segmenter  # noqa: F401
 
 __all__ = ["ContrastiveCorrelationLoss", "depth_decay", "training", "metrics", "evaluation", "predict_and_score", "crf", "dense_crf",
-           "batched_crf", "knn", "lhp", "segmenter"]
+           "batched_crf", "knn", "lhp", "optim", "FusedAdam", "FusedAdamSet", "segmenter"]

@@ -22,7 +22,7 @@ EXPORTS = ["dg_version", "dg_last_error", "dg_corr_workspace_bytes", "dg_corr_fo
            "dg_cluster_lookup_backward", "dg_probe_ce_forward", "dg_probe_ce_backward", "dg_knn_similarities",
            "dg_prof_main_span", "dg_corr_materialize_shared", "dg_normalize_split", "dg_sampled_sumsq",
            "dg_corr_forward_extnorm", "dg_segment_predict", "dg_crf_workspace_bytes", "dg_crf_unary",
-           "dg_segment_unary", "dg_crf_filter", "dg_dense_crf"]
+           "dg_segment_unary", "dg_crf_filter", "dg_dense_crf", "dg_adam_step"]
 
 
 class CorrDesc(ctypes.Structure):
@@ -34,6 +34,18 @@ class CorrDesc(ctypes.Structure):
                 ("shift_depth", ctypes.c_float),
                 ("w_intra", ctypes.c_float), ("w_inter", ctypes.c_float), ("w_neg", ctypes.c_float),
                 ("w_depth", ctypes.c_float), ("code_h", ctypes.c_int32), ("code_w", ctypes.c_int32)]
+
+
+class AdamSeg(ctypes.Structure):
+    """struct dg_adam_seg"""
+    _fields_ = [("param", ctypes.c_void_p), ("grad", ctypes.c_void_p), ("exp_avg", ctypes.c_void_p), ("exp_avg_sq", ctypes.c_void_p),
+                ("step_dev", ctypes.c_void_p), ("numel", ctypes.c_int64), ("step_host", ctypes.c_double), ("group", ctypes.c_int32),
+                ("reserved", ctypes.c_int32)]
+
+
+class AdamGroup(ctypes.Structure):
+    """struct dg_adam_group"""
+    _fields_ = [("lr", ctypes.c_double), ("beta1", ctypes.c_double), ("beta2", ctypes.c_double), ("eps", ctypes.c_double)]
 
 
 _lib = None
@@ -150,6 +162,8 @@ def load():
     lib.dg_super_perms_seeded.argtypes = [ctypes.c_uint64, ctypes.c_int32, ctypes.c_int32, vp, vp]
     lib.dg_super_perms_state.restype = ctypes.c_int
     lib.dg_super_perms_state.argtypes = [vp, ctypes.c_int32, ctypes.c_int32, vp, vp]
+    lib.dg_adam_step.restype = ctypes.c_int
+    lib.dg_adam_step.argtypes = [ctypes.POINTER(AdamSeg), i32, ctypes.POINTER(AdamGroup), i32, i32, vp, vp]
     lib.dg_prof_main_span.restype = ctypes.c_int
     lib.dg_prof_main_span.argtypes = [vp]
     _lib = lib

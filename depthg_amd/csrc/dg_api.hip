@@ -1667,3 +1667,36 @@ extern "C" int dg_dense_crf(const float* img, const float* unary, int32_t B, int
     DG_HIP(dg_launch_dense_crf(a, static_cast<hipStream_t>(stream_)));
     return DG_OK;
 }
+
+// ---- the optimisation step's Adams (dg_optim.hip)
+extern "C" int dg_adam_step(const dg_adam_seg* segs, int32_t n_seg, const dg_adam_group* groups, int32_t n_groups, int32_t device_steps,
+                            void* tickets, dg_stream_t stream_) {
+    if (!segs || !groups) return fail(DG_ERR_INVALID, "dg_adam_step: null table");
+    if (n_seg < 1 || n_groups < 1) return fail(DG_ERR_INVALID, "dg_adam_step: n_seg=%d, n_groups=%d must be positive", n_seg, n_groups);
+    if (n_groups > DG_ADAM_MAX_GROUPS) return fail(DG_ERR_UNSUPPORTED, "dg_adam_step: %d groups (max %d per call)", n_groups, DG_ADAM_MAX_GROUPS);
+    for (int k = 0; k < n_groups; ++k) {
+        const dg_adam_group& g = groups[k];
+        if (!(g.lr >= 0.0) || !(g.beta1 >= 0.0 && g.beta1 < 1.0) || !(g.beta2 >= 0.0 && g.beta2 < 1.0) || !(g.eps >= 0.0))
+            return fail(DG_ERR_INVALID, "dg_adam_step: group %d: lr=%g betas=(%g, %g) eps=%g", k, g.lr, g.beta1, g.beta2, g.eps);
+    }
+    for (int k = 0; k < n_seg; ++k) {
+        const dg_adam_seg& s = segs[k];
+        if (!s.param || !s.exp_avg || !s.exp_avg_sq) return fail(DG_ERR_INVALID, "dg_adam_step: segment %d: null parameter / state pointer", k);
+        if (s.numel < 1 || s.numel > 0x7fffffffll) return fail(DG_ERR_INVALID, "dg_adam_step: segment %d: numel=%lld outside [1, 2^31)", k, (long long)s.numel);
+        if (s.group < 0 || s.group >= n_groups) return fail(DG_ERR_INVALID, "dg_adam_step: segment %d: group %d of %d", k, s.group, n_groups);
+        if (((uintptr_t)s.param | (uintptr_t)s.grad | (uintptr_t)s.exp_avg | (uintptr_t)s.exp_avg_sq) & 3)
+            return fail(DG_ERR_INVALID, "dg_adam_step: segment %d: a pointer is not 4-byte aligned", k);
+        if (device_steps) {
+            if (!s.step_dev || ((uintptr_t)s.step_dev & 3)) return fail(DG_ERR_INVALID, "dg_adam_step: segment %d: step_dev must be a device float", k);
+            if (s.numel > DG_ADAM_CHUNK && !tickets) return fail(DG_ERR_INVALID, "dg_adam_step: segment %d spans several blocks: tickets must be given", k);
+        } else if (!(s.step_host >= 1.0)) {
+            return fail(DG_ERR_INVALID, "dg_adam_step: segment %d: step_host=%g (the count after this step) must be >= 1", k, s.step_host);
+        }
+    }
+    for (int k0 = 0; k0 < n_seg; k0 += DG_ADAM_MAX_SEGS) {
+        const int c = n_seg - k0 < DG_ADAM_MAX_SEGS ? n_seg - k0 : DG_ADAM_MAX_SEGS;
+        DG_HIP(dg_launch_adam(segs + k0, c, groups, n_groups, device_steps != 0,
+                              tickets ? static_cast<unsigned int*>(tickets) + k0 : nullptr, static_cast<hipStream_t>(stream_)));
+    }
+    return DG_OK;
+}

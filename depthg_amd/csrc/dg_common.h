@@ -978,3 +978,12 @@ size_t dg_crf_sort_temp_bytes(int n);
 hipError_t dg_crf_sort_pairs(void* temp, size_t temp_bytes, const uint64_t* kin, uint64_t* kout, const uint32_t* vin, uint32_t* vout,
                              int n, int bits, hipStream_t s);
 hipError_t dg_crf_scan(void* temp, size_t temp_bytes, const int32_t* in, int32_t* out, int n, hipStream_t s);
+
+// ---- the optimisation step's Adams as one launch (dg_optim.hip; src/train_segmentation.py:447-455, 537-547)
+#define DG_ADAM_MAX_SEGS 16                  // segments (tensors) per launch: dg_adam_step splits longer tables
+#define DG_ADAM_MAX_GROUPS 16                // hyper-parameter groups per call
+#define DG_ADAM_THREADS 256
+#define DG_ADAM_CHUNK (4 * DG_ADAM_THREADS)  // elements per block: one 128-bit access per thread and tensor
+// at most DG_ADAM_MAX_SEGS segments; tickets: null, or the first segment's counter (segment k takes tickets[k])
+hipError_t dg_launch_adam(const dg_adam_seg* segs, int n_seg, const dg_adam_group* groups, int n_groups, bool device_steps,
+                          unsigned int* tickets, hipStream_t s);

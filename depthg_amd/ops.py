@@ -505,6 +505,51 @@ def dense_crf(img, unary, group_ends=None, n_iter=10, pos_w=3.0, pos_xy_std=1.0,
     return q, preds
 
 
+def adam_step(segs, groups, device_steps=False, tickets=None):
+    """torch.optim.Adam's default update of every listed tensor in ONE launch (dg_adam_step; src/train_segmentation.py:447-449).
+    segs   : sequence of (param, grad, exp_avg, exp_avg_sq, step, group) - fp32 contiguous tensors on the GPU; grad None = the
+             segment is skipped (state and step untouched); step = the count AFTER this step as a Python number (host mode), or
+             the float32 0-dim device tensor the kernel reads and advances (device_steps); group indexes `groups`
+    groups : sequence of (lr, beta1, beta2, eps)
+    tickets: device_steps only - int32 zeros (len(segs),) on the GPU, left zero by every call."""
+    lib = _lib.load()
+    n = len(segs)
+    table = (_lib.AdamSeg * max(n, 1))()
+    dev = None
+    for k, (p, g, m, v, step, gi) in enumerate(segs):
+        for name, t in (("param", p), ("grad", g), ("exp_avg", m), ("exp_avg_sq", v)):
+            if t is None and name == "grad":
+                continue
+            if not t.is_cuda:
+                raise RuntimeError(f"depthg_amd: `{name}` must live on the GPU (got {t.device}); there is no CPU path")
+            if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != p.numel() or t.device != p.device:
+                raise ValueError(f"depthg_amd: adam_step segment {k}: `{name}` must be a contiguous fp32 tensor of the parameter's size and device "
+                                 f"(got {t.dtype}, {tuple(t.shape)}, {t.device})")
+        if dev is None:
+            dev = p.device
+        elif p.device != dev:
+            raise RuntimeError(f"depthg_amd: adam_step: parameters on {dev} and {p.device} in one call")
+        e = table[k]
+        e.param, e.exp_avg, e.exp_avg_sq = p.data_ptr(), m.data_ptr(), v.data_ptr()
+        e.grad = g.data_ptr() if g is not None else None
+        e.numel, e.group = p.numel(), int(gi)
+        if device_steps:
+            if not (torch.is_tensor(step) and step.is_cuda and step.dtype == torch.float32 and step.numel() == 1):
+                raise ValueError(f"depthg_amd: adam_step segment {k}: the device step must be a float32 scalar on the GPU")
+            e.step_dev = step.data_ptr()
+        else:
+            e.step_host = float(step)
+    if n == 0:
+        return
+    gt = (_lib.AdamGroup * len(groups))()
+    for k, (lr, b1, b2, eps) in enumerate(groups):
+        gt[k].lr, gt[k].beta1, gt[k].beta2, gt[k].eps = float(lr), float(b1), float(b2), float(eps)
+    if tickets is not None and not (tickets.is_cuda and tickets.dtype == torch.int32 and tickets.numel() >= n and tickets.is_contiguous()):
+        raise ValueError("depthg_amd: adam_step: `tickets` must be int32 (len(segs),) on the GPU")
+    rc = lib.dg_adam_step(table, n, gt, len(groups), 1 if device_steps else 0, _ptr(tickets if device_steps else None), _stream(dev))
+    _lib.check(rc, "dg_adam_step")
+
+
 def topk_rows(vals, k, return_values=False):
     """Column indices of the k largest entries of every row of `vals` (rows, cols) fp32 on the GPU: value descending, ties by
     ascending column (src/precompute_knns.py:110 `torch.topk(pairwise_sims, 30)[1]`)."""

@@ -54,6 +54,16 @@ class GradBucket:
             else:
                 p.grad.copy_(v)
 
+    def grad_views(self) -> List[torch.Tensor]:
+        """The per-parameter views into the flat buffer, in the order of `parameters()`: after `pack()` and `allreduce_mean_()`
+        they ARE the averaged gradients - an optimiser that takes gradients as arguments (optim.FusedAdamSet.step(grads=...)) reads
+        them here, without the copies of `unpack()`."""
+        return list(self._views)
+
+    def parameters(self) -> List[torch.Tensor]:
+        """The registered parameters (those of `for_parameters` that require a gradient)."""
+        return list(getattr(self, "_params", []))
+
     def fill_from(self, t: torch.Tensor):
         """Benchmark stand-in: fill the bucket from the leading elements of a gradient tensor."""
         src = t.reshape(-1)

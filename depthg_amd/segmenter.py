@@ -19,8 +19,10 @@ Mirrors, with the reference's names, parameter layout and arithmetic:
                             run_crf for the dense CRF) score the probes through evaluation.predict_and_score.
 ProjectionHead / ClusterLookup (src/modules.py:647-675) / probe_cross_entropy live in depthg_amd/head.py and are re-exported
 here.  The head, the probes' losses and everything the correlation loss does run in the HIP library; what stays torch is the
-frozen backbone, the 27 x dim linear-probe convolution and the three Adams.  Under data parallelism `all_reduced_parameters()` is
-what `parallel.GradBucket` all-reduces.
+frozen backbone, the 27 x dim linear-probe convolution and - unless cfg.dg_fused_adam - the three Adams.  With cfg.dg_fused_adam
+(build-side key, off by default) configure_optimizers() returns three optim.FusedAdam and the step ends with ONE HIP launch over
+all nine tensors (optim.FusedAdamSet) instead of three torch.optim.Adam steps.  Under data parallelism `all_reduced_parameters()`
+is what `parallel.GradBucket` all-reduces.
 """
 from types import SimpleNamespace
 from typing import Dict, Optional
@@ -34,6 +36,8 @@ from .head import ClusterLookup, ProjectionHead, probe_cross_entropy, run_head, 
 from .lhp import LocalHiddenPositiveProjection, OriginalLocalHiddenPositiveProjection
 from .loss import ContrastiveCorrelationLoss
 from .metrics import UnsupervisedMetrics
+from .optim import FusedAdam, FusedAdamSet
+from .parallel import GradBucket
 from .training import correspondence_total
 
 
@@ -147,6 +151,10 @@ class UnsupervisedSegmenter(nn.Module):
         # as the reference: net_optim steps `self.net.parameters()` only (its decoder is out of scope here, rec_weight = 0) - the
         # LHP projection head is NOT among them, so it keeps its initial weights there and here
         main_params = list(self.net.parameters())
+        if getattr(self.cfg, "dg_fused_adam", False):          # the same three, stepped by one HIP launch (optim.FusedAdamSet)
+            return (FusedAdam([p for p in main_params if p.requires_grad], lr=self.cfg.lr),
+                    FusedAdam(list(self.linear_probe.parameters()), lr=5e-3),
+                    FusedAdam(list(self.cluster_probe.parameters()), lr=5e-3))
         net_optim = torch.optim.Adam([p for p in main_params if p.requires_grad], lr=self.cfg.lr)
         linear_probe_optim = torch.optim.Adam(list(self.linear_probe.parameters()), lr=5e-3)
         cluster_probe_optim = torch.optim.Adam(list(self.cluster_probe.parameters()), lr=5e-3)
@@ -156,6 +164,33 @@ class UnsupervisedSegmenter(nn.Module):
         if self._optims is None:
             self._optims = self.configure_optimizers()
         return self._optims
+
+    def _fused_set(self):
+        """cfg.dg_fused_adam: the three optimisers as one FusedAdamSet (rebuilt when `_optims` is replaced)."""
+        optims = self.optimizers()
+        cached = getattr(self, "_optim_set", None)
+        if cached is None or cached[0] is not optims:
+            self._optim_set = cached = (optims, FusedAdamSet(optims))
+        return cached[1]
+
+    def _handed_over_grads(self, handed, fused):
+        """What `grad_sync` returned -> the `grads` of FusedAdamSet.step, or None (read p.grad)."""
+        if not isinstance(handed, (GradBucket, list)):
+            return None
+        if not fused:
+            raise RuntimeError("training_step: `grad_sync` handed gradients over, which only the fused optimiser step reads "
+                               "(cfg.dg_fused_adam); without it unpack the bucket into p.grad and return None")
+        params = fused.parameters()
+        if isinstance(handed, GradBucket):
+            views = {id(p): v for p, v in zip(handed.parameters(), handed.grad_views())}
+            missing = [tuple(p.shape) for p in params if id(p) not in views]
+            if missing:
+                raise RuntimeError(f"training_step: the GradBucket lacks stepped parameters of shapes {missing} "
+                                   "(build it from all_reduced_parameters())")
+            return [views[id(p)] for p in params]
+        if len(handed) != len(params):
+            raise RuntimeError(f"training_step: `grad_sync` returned {len(handed)} gradients for {len(params)} stepped parameters")
+        return handed
 
     def head_parameters(self):
         """The parameters net_optim steps: cluster1 + cluster2."""
@@ -170,7 +205,12 @@ class UnsupervisedSegmenter(nn.Module):
 
     def training_step(self, batch: Dict[str, torch.Tensor], batch_idx: int = 0, grad_sync=None):
         """One optimisation step (src/train_segmentation.py:169-462).  `grad_sync`: callable run between backward and the
-        optimiser steps (data parallelism: GradBucket pack / all-reduce / unpack); returns (loss, logs)."""
+        optimiser steps (data parallelism: GradBucket pack / all-reduce / unpack); returns (loss, logs).
+        With cfg.dg_fused_adam `grad_sync` may hand the averaged gradients straight to the optimiser step instead of unpacking
+        them into p.grad: it returns the `GradBucket` (its `grad_views()` are read, matched to the parameters by identity), or a
+        `list` of tensors / None aligned with `all_reduced_parameters()`, e.g.
+            grad_sync = lambda: [bucket.pack(), bucket.allreduce_mean_(), bucket][-1]
+        Any other return value - None, or the tuple a `lambda: (a(), b())` chain yields - keeps today's meaning: p.grad is read."""
         cfg = self.cfg
         net_optim, linear_probe_optim, cluster_probe_optim = self.optimizers()
         net_optim.zero_grad(); linear_probe_optim.zero_grad(); cluster_probe_optim.zero_grad()        # :174-176
@@ -221,14 +261,19 @@ class UnsupervisedSegmenter(nn.Module):
         logs.update({"loss/linear": linear_loss.detach(), "loss/cluster": cluster_loss.detach(), "loss/total": loss.detach()})
 
         loss.backward()                                                                               # :446
-        if grad_sync is not None:
-            grad_sync()
-        net_optim.step(); cluster_probe_optim.step(); linear_probe_optim.step()                       # :447-449
+        fused = self._fused_set() if getattr(cfg, "dg_fused_adam", False) else None
+        handed = grad_sync() if grad_sync is not None else None
+        grads = self._handed_over_grads(handed, fused)
+        if fused is not None:
+            fused.step(grads=grads)                                                                   # :447-449 in one HIP launch
+        else:
+            net_optim.step(); cluster_probe_optim.step(); linear_probe_optim.step()                   # :447-449
         if cfg.reset_probe_steps is not None and self.global_step == cfg.reset_probe_steps:           # :451-455
             self.linear_probe.reset_parameters()
             self.cluster_probe.reset_parameters()
-            self._optims = (net_optim, torch.optim.Adam(list(self.linear_probe.parameters()), lr=5e-3),
-                            torch.optim.Adam(list(self.cluster_probe.parameters()), lr=5e-3))
+            adam = FusedAdam if fused is not None else torch.optim.Adam
+            self._optims = (net_optim, adam(list(self.linear_probe.parameters()), lr=5e-3),
+                            adam(list(self.cluster_probe.parameters()), lr=5e-3))
         self.global_step += 1
         return loss.detach(), logs
 
@@ -313,7 +358,9 @@ def default_segmenter_cfg(**over) -> SimpleNamespace:
         fps_sample_decay_factor=0.9, fps_min_samples=0, lhp=False, lhp_weight=0.2, lhp_weight_balance=False,
         lhp_depth_weight=0.5,
         # validation
-        n_images=5)
+        n_images=5,
+        # build-side: the step's three Adams as one HIP launch (optim.FusedAdam / FusedAdamSet)
+        dg_fused_adam=False)
     for k, v in over.items():
         setattr(cfg, k, v)
     return cfg

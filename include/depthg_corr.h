@@ -551,6 +551,41 @@ int dg_dense_crf(const float* img, const float* unary, int32_t B, int32_t H, int
                  int32_t n_iter, float pos_w, float pos_xy_std, float bi_w, float bi_xy_std, float bi_rgb_std, float* q, int64_t* preds,
                  void* workspace, size_t workspace_bytes, dg_stream_t stream);
 
+/*
+ * The optimisation step's Adams (src/train_segmentation.py:447-455: net_optim.step(), cluster_probe_optim.step(),
+ * linear_probe_optim.step(); :537-547: three torch.optim.Adam with default betas / eps, weight_decay = 0, amsgrad = False) as ONE
+ * launch over a table of segments (one per tensor); fp32 throughout:
+ *      exp_avg    = exp_avg + (1 - beta1) * (grad - exp_avg)
+ *      exp_avg_sq = beta2 * exp_avg_sq + (1 - beta2) * grad * grad
+ *      param      = param - (lr / (1 - beta1^t)) * exp_avg / (sqrt(exp_avg_sq) / sqrt(1 - beta2^t) + eps)
+ * The two tables are HOST memory, copied into the kernel's arguments (gradient pointers change every eager step; nothing is copied
+ * to the device).  Tables longer than 16 segments are stepped by further launches of 16; at most 16 groups per call.
+ *  device_steps = 0 : t = seg.step_host (the count AFTER this step, >= 1); both corrections are formed on the host in double.
+ *  device_steps = 1 : t = *seg.step_dev + 1 (a float32 in device memory, one per segment, not shared between segments); the kernel
+ *                     forms both corrections from it and stores t back, so a launch recorded into a hipGraph advances at every
+ *                     replay.  tickets : uint32 [n_seg] in device memory, zero before the first call and left zero by every call
+ *                     (segment k of more than 1024 elements counts its blocks in tickets[k]); may be NULL when no segment is
+ *                     that long.
+ * A segment with grad == NULL is skipped: parameter, moments and t untouched (torch skips parameters whose .grad is None - with
+ * correspondence_weight = 0 the head receives no gradient at all).  No workspace, no host synchronisation.
+ */
+typedef struct dg_adam_seg {
+    float* param;
+    const float* grad;       /* NULL: skip the segment */
+    float* exp_avg;
+    float* exp_avg_sq;
+    float* step_dev;         /* device_steps = 1 only */
+    int64_t numel;           /* 1 .. 2^31 - 1 */
+    double step_host;        /* device_steps = 0 only */
+    int32_t group;           /* index into groups */
+    int32_t reserved;
+} dg_adam_seg;
+typedef struct dg_adam_group {
+    double lr, beta1, beta2, eps;
+} dg_adam_group;
+int dg_adam_step(const dg_adam_seg* segs, int32_t n_seg, const dg_adam_group* groups, int32_t n_groups, int32_t device_steps,
+                 void* tickets, dg_stream_t stream);
+
 /* Measurement aid: name of the kernel the fused correlation launch of this descriptor runs ("k_corr2": the one-wave-per-SIMD
  * form of dg_corr2.hip, "k_corr_main": the general form), decided by the same predicate the launch uses; NULL on a bad desc. */
 const char* dg_corr_main_kernel_name(const dg_corr_desc* desc);
