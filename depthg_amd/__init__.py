@@ -15,6 +15,9 @@ Public surface (mirrors the reference's Python operator surface for this path):
                                  step of LitUnsupervisedSegmenter (src/modules.py:19-137,647-675; src/train_segmentation.py:71-462)
     optim                        FusedAdam / FusedAdamSet: the step's three torch.optim.Adam (src/train_segmentation.py:447-455,537-547)
                                  as one HIP launch, torch's state layout (cfg.dg_fused_adam in the segmenter)
+    vit                          the DINO vision transformer (src/dino/vision_transformer.py:68-280) on torch, checkpoint-compatible;
+                                 its attention optionally through the fused HIP kernel k_attn_fwd (cfg.dg_fused_attention)
+    featurizer / DinoFeaturizer  src/modules.py:19-137: frozen ViT + the fused projection head (cfg.dg_dino_backbone in the segmenter)
     ops                          thin ctypes binding of the C ABI in include/depthg_corr.h
 """
 from .loss import ContrastiveCorrelationLoss  # noqa: F401
@@ -29,7 +32,11 @@ from . import knn  # noqa: F401
 from . import lhp  # noqa: F401
 from . import optim  # noqa: F401
 from .optim import FusedAdam, FusedAdamSet  # noqa: F401
+from . import vit  # noqa: F401
+from . import featurizer  # noqa: F401
+from .featurizer import DinoFeaturizer  # noqa: F401
 from . import segmenter  # noqa: F401
 
 __all__ = ["ContrastiveCorrelationLoss", "depth_decay", "training", "metrics", "evaluation", "predict_and_score", "crf", "dense_crf",
-           "batched_crf", "knn", "lhp", "optim", "FusedAdam", "FusedAdamSet", "segmenter"]
+           "batched_crf", "knn", "lhp", "optim", "FusedAdam", "FusedAdamSet", "segmenter", "vit", "featurizer",
+           "DinoFeaturizer"]

@@ -22,7 +22,7 @@ EXPORTS = ["dg_version", "dg_last_error", "dg_corr_workspace_bytes", "dg_corr_fo
            "dg_cluster_lookup_backward", "dg_probe_ce_forward", "dg_probe_ce_backward", "dg_knn_similarities",
            "dg_prof_main_span", "dg_corr_materialize_shared", "dg_normalize_split", "dg_sampled_sumsq",
            "dg_corr_forward_extnorm", "dg_segment_predict", "dg_crf_workspace_bytes", "dg_crf_unary",
-           "dg_segment_unary", "dg_crf_filter", "dg_dense_crf", "dg_adam_step"]
+           "dg_segment_unary", "dg_crf_filter", "dg_dense_crf", "dg_adam_step", "dg_attention_workspace_bytes", "dg_attention_forward"]
 
 
 class CorrDesc(ctypes.Structure):
@@ -164,6 +164,10 @@ def load():
     lib.dg_super_perms_state.argtypes = [vp, ctypes.c_int32, ctypes.c_int32, vp, vp]
     lib.dg_adam_step.restype = ctypes.c_int
     lib.dg_adam_step.argtypes = [ctypes.POINTER(AdamSeg), i32, ctypes.POINTER(AdamGroup), i32, i32, vp, vp]
+    lib.dg_attention_workspace_bytes.restype = ctypes.c_size_t
+    lib.dg_attention_workspace_bytes.argtypes = [i32] * 3
+    lib.dg_attention_forward.restype = ctypes.c_int
+    lib.dg_attention_forward.argtypes = [vp] + [i32] * 4 + [f32, vp, vp, ctypes.c_size_t, vp]
     lib.dg_prof_main_span.restype = ctypes.c_int
     lib.dg_prof_main_span.argtypes = [vp]
     _lib = lib

@@ -1700,3 +1700,26 @@ extern "C" int dg_adam_step(const dg_adam_seg* segs, int32_t n_seg, const dg_ada
     }
     return DG_OK;
 }
+
+// ---- fused attention forward of the frozen ViT (dg_attn.hip)
+extern "C" size_t dg_attention_workspace_bytes(int32_t B, int32_t heads, int32_t N) {
+    if (B < 1 || heads < 1 || N < 1 || N > (1 << 24) || (long long)B * heads > 65535) return 0;
+    return up(dg_attn_workspace(B, heads, N), 256);
+}
+
+extern "C" int dg_attention_forward(const float* qkv, int32_t B, int32_t N, int32_t heads, int32_t head_dim, float scale, float* out,
+                                    void* workspace, size_t workspace_bytes, dg_stream_t stream_) {
+    if (head_dim != 64) return fail(DG_ERR_UNSUPPORTED, "dg_attention_forward: head_dim=%d (the kernel is built for 64)", head_dim);
+    if (B < 1 || heads < 1 || N < 1 || N > (1 << 24))
+        return fail(DG_ERR_INVALID, "dg_attention_forward: B=%d heads=%d N=%d", B, heads, N);
+    if ((long long)B * heads > 65535) return fail(DG_ERR_UNSUPPORTED, "dg_attention_forward: B * heads = %lld above 65535", (long long)B * heads);
+    if (!(scale == scale) || std::isinf(scale)) return fail(DG_ERR_INVALID, "dg_attention_forward: scale=%g", (double)scale);
+    if (!qkv || !out || !workspace) return fail(DG_ERR_INVALID, "dg_attention_forward: null pointer");
+    if (((uintptr_t)qkv | (uintptr_t)out | (uintptr_t)workspace) & 15)
+        return fail(DG_ERR_INVALID, "dg_attention_forward: qkv, out and workspace must be 16-byte aligned");
+    const size_t need = dg_attention_workspace_bytes(B, heads, N);
+    if (workspace_bytes < need)
+        return fail(DG_ERR_WORKSPACE, "workspace of %zu bytes, %zu needed (dg_attention_workspace_bytes)", workspace_bytes, need);
+    DG_HIP(dg_launch_attention(qkv, out, workspace, B, N, heads, scale, static_cast<hipStream_t>(stream_)));
+    return DG_OK;
+}

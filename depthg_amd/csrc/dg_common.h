@@ -987,3 +987,7 @@ hipError_t dg_crf_scan(void* temp, size_t temp_bytes, const int32_t* in, int32_t
 // at most DG_ADAM_MAX_SEGS segments; tickets: null, or the first segment's counter (segment k takes tickets[k])
 hipError_t dg_launch_adam(const dg_adam_seg* segs, int n_seg, const dg_adam_group* groups, int n_groups, bool device_steps,
                           unsigned int* tickets, hipStream_t s);
+
+// ---- fused attention forward of the frozen ViT (dg_attn.hip; src/dino/vision_transformer.py:80-92)
+size_t dg_attn_workspace(int B, int heads, int N);           // bytes of the packed bf16 K / V images
+hipError_t dg_launch_attention(const float* qkv, float* out, void* ws, int B, int N, int heads, float scale, hipStream_t s);

@@ -769,3 +769,44 @@ def corr_main_kernel_name(desc):
     if name is None:
         _lib.check(-1, "dg_corr_main_kernel_name")
     return name.decode()
+
+
+def attention_forward(qkv, heads, scale=None, out=None):
+    """softmax(q k^T * scale) v of one ViT block (dg_attention_forward; src/dino/vision_transformer.py:80-92) without the
+    (B, heads, N, N) matrix: qkv (B, N, 3 * heads * 64) fp32 contiguous on the GPU - the output of the block's qkv linear as it
+    stands - -> (B, N, heads * 64) fp32, the input of its proj linear.  scale: None = 64 ** -0.5.  out: optional result buffer.
+    Forward only (the backbone is frozen); bf16 MFMA operands, fp32 softmax.  Runs on the caller's current stream."""
+    heads = int(heads)
+    if qkv.dim() != 3 or heads < 1 or qkv.shape[2] % (3 * heads):
+        raise ValueError(f"depthg_amd: qkv must be (B, N, 3 * heads * 64) with heads={heads}, got {tuple(qkv.shape)}")
+    B, N, C3 = qkv.shape
+    hd = C3 // (3 * heads)
+    if hd != 64:
+        raise ValueError(f"depthg_amd: attention_forward is built for head dimension 64 (every DINO ViT), got {hd}")
+    if qkv.dtype != torch.float32:
+        raise ValueError(f"depthg_amd: qkv must be float32, got {qkv.dtype}")
+    if not qkv.is_contiguous():
+        raise ValueError(f"depthg_amd: qkv must be contiguous (strides {qkv.stride()})")
+    if not qkv.is_cuda:          # (shape, head dimension and dtype are refused first: those hold on any device)
+        raise RuntimeError(f"depthg_amd: `qkv` must live on the GPU (got {qkv.device}); there is no CPU path")
+    if B < 1 or N < 1:
+        raise ValueError(f"depthg_amd: qkv must hold at least one token, got {tuple(qkv.shape)}")
+    if qkv.requires_grad and torch.is_grad_enabled():
+        raise RuntimeError("depthg_amd: attention_forward has no backward (the ViT is frozen); call it under torch.no_grad()")
+    dev = qkv.device
+    if out is None:
+        out = _empty((B, N, heads * hd), torch.float32, dev)
+    elif not (isinstance(out, torch.Tensor) and out.device == dev and out.dtype == torch.float32 and out.is_contiguous()
+              and tuple(out.shape) == (B, N, heads * hd)):
+        raise ValueError(f"depthg_amd: `out` must be a contiguous float32 ({B}, {N}, {heads * hd}) tensor on {dev}")
+    if (qkv.data_ptr() | out.data_ptr()) & 15:       # (a slice of a larger buffer can start anywhere; the kernels use 128-bit accesses)
+        raise ValueError("depthg_amd: attention_forward needs qkv and out to start at 16-byte aligned addresses")
+    lib = _lib.load()
+    need = lib.dg_attention_workspace_bytes(B, heads, N)
+    if need == 0:
+        raise ValueError(f"depthg_amd: no attention plan for B={B}, heads={heads}, N={N} (B * heads <= 65535)")
+    ws = _empty((need,), torch.uint8, dev)
+    rc = lib.dg_attention_forward(_ptr(qkv.detach()), B, N, heads, hd, float(hd ** -0.5 if scale is None else scale), _ptr(out),
+                                  _ptr(ws), need, _stream(dev))
+    _lib.check(rc, "dg_attention_forward")
+    return out

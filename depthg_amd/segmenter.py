@@ -22,7 +22,9 @@ here.  The head, the probes' losses and everything the correlation loss does run
 frozen backbone, the 27 x dim linear-probe convolution and - unless cfg.dg_fused_adam - the three Adams.  With cfg.dg_fused_adam
 (build-side key, off by default) configure_optimizers() returns three optim.FusedAdam and the step ends with ONE HIP launch over
 all nine tensors (optim.FusedAdamSet) instead of three torch.optim.Adam steps.  Under data parallelism `all_reduced_parameters()`
-is what `parallel.GradBucket` all-reduces.
+is what `parallel.GradBucket` all-reduces.  With cfg.dg_dino_backbone (build-side key, off by default) the featurizer is
+featurizer.DinoFeaturizer - the real DINO ViT of depthg_amd/vit.py - instead of StandInFeaturizer; cfg.dg_fused_attention then routes
+its attention through the HIP kernel of dg_attn.hip.
 """
 from types import SimpleNamespace
 from typing import Dict, Optional
@@ -32,6 +34,7 @@ import torch.nn as nn
 
 from .depth_decay import legacy_decay_step
 from .evaluation import predict_and_score
+from .featurizer import DinoFeaturizer
 from .head import ClusterLookup, ProjectionHead, probe_cross_entropy, run_head, run_head_pair
 from .lhp import LocalHiddenPositiveProjection, OriginalLocalHiddenPositiveProjection
 from .loss import ContrastiveCorrelationLoss
@@ -120,7 +123,10 @@ class UnsupervisedSegmenter(nn.Module):
         self.cfg, self.n_classes = cfg, n_classes
         dim = n_classes if not cfg.continuous else cfg.dim                          # :78-81
         self.use_depth = bool(cfg.use_depth)
-        self.net = net if net is not None else StandInFeaturizer(dim, cfg)           # :99-108 (arch == "dino")
+        if net is None:                                                               # :99-108 (arch == "dino")
+            # cfg.dg_dino_backbone (build-side key, off by default): the real DINO ViT (featurizer.DinoFeaturizer) instead of the stand-in
+            net = DinoFeaturizer(dim, cfg) if getattr(cfg, "dg_dino_backbone", False) else StandInFeaturizer(dim, cfg)
+        self.net = net
         self.train_cluster_probe = ClusterLookup(dim, n_classes)                      # :110
         self.cluster_probe = ClusterLookup(dim, n_classes + cfg.extra_clusters)       # :112
         self.linear_probe = nn.Conv2d(dim, n_classes, (1, 1))                         # :113
@@ -360,7 +366,11 @@ def default_segmenter_cfg(**over) -> SimpleNamespace:
         # validation
         n_images=5,
         # build-side: the step's three Adams as one HIP launch (optim.FusedAdam / FusedAdamSet)
-        dg_fused_adam=False)
+        dg_fused_adam=False,
+        # build-side: the featurizer is featurizer.DinoFeaturizer (the ViT of vit.py) instead of StandInFeaturizer; its attention
+        # through the fused HIP kernel (ops.attention_forward)
+        # (dg_dino_vit_kwargs: test hook, constructor arguments of the ViT that override the architecture's)
+        dg_dino_backbone=False, dg_fused_attention=False, dg_dino_vit_kwargs=None)
     for k, v in over.items():
         setattr(cfg, k, v)
     return cfg

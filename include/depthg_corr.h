@@ -586,6 +586,23 @@ typedef struct dg_adam_group {
 int dg_adam_step(const dg_adam_seg* segs, int32_t n_seg, const dg_adam_group* groups, int32_t n_groups, int32_t device_steps,
                  void* tickets, dg_stream_t stream);
 
+/*
+ * Attention forward of the frozen DINO ViT (src/dino/vision_transformer.py:80-92: attn = softmax(q @ k^T * scale), x = attn @ v,
+ * transposed back to (B, N, C)) as one fused kernel: the (B, heads, N, N) matrix is never written.  Forward only (the backbone is
+ * frozen, src/modules.py:34-35).
+ *  qkv : fp32 (B, N, 3, heads, 64) contiguous - the output of the block's qkv linear as it stands (:82 before the permute)
+ *  out : fp32 (B, N, heads * 64), the input of the block's proj linear (:89-90)
+ *  head_dim : 64 only (every DINO ViT; :262-280) - DG_ERR_UNSUPPORTED otherwise, before any launch;  N >= 1, B * heads <= 65535
+ *  scale : the factor on the scores (:73, head_dim ** -0.5 unless qk_scale is given)
+ *  workspace : dg_attention_workspace_bytes(B, heads, N) bytes, 16-byte aligned: K and V as bf16 in MFMA fragment order
+ * Arithmetic: q, k, v rounded to bf16 (nearest even), products on v_mfma_f32_32x32x16_bf16 with fp32 accumulation, scores, running
+ * maximum, exponentials and row sums in fp32, the probabilities rounded to bf16 for the second product.  qkv and out must be
+ * 16-byte aligned too (DG_ERR_INVALID otherwise).  Nothing outside the two tensors is read or written.
+ */
+size_t dg_attention_workspace_bytes(int32_t B, int32_t heads, int32_t N);      /* 0 on bad arguments */
+int dg_attention_forward(const float* qkv, int32_t B, int32_t N, int32_t heads, int32_t head_dim, float scale, float* out,
+                         void* workspace, size_t workspace_bytes, dg_stream_t stream);
+
 /* Measurement aid: name of the kernel the fused correlation launch of this descriptor runs ("k_corr2": the one-wave-per-SIMD
  * form of dg_corr2.hip, "k_corr_main": the general form), decided by the same predicate the launch uses; NULL on a bad desc. */
 const char* dg_corr_main_kernel_name(const dg_corr_desc* desc);
