@@ -17,6 +17,8 @@ Public surface (mirrors the reference's Python operator surface for this path):
                                  as one HIP launch, torch's state layout (cfg.dg_fused_adam in the segmenter)
     vit                          the DINO vision transformer (src/dino/vision_transformer.py:68-280) on torch, checkpoint-compatible;
                                  its attention optionally through the fused HIP kernel k_attn_fwd (cfg.dg_fused_attention)
+                                 and its blocks' linear layers, LayerNorms, GELU and residual adds through the bf16 MFMA kernel
+                                 k_lin_fwd (cfg.dg_fused_linear)
     featurizer / DinoFeaturizer  src/modules.py:19-137: frozen ViT + the fused projection head (cfg.dg_dino_backbone in the segmenter)
     ops                          thin ctypes binding of the C ABI in include/depthg_corr.h
 """

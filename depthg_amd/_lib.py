@@ -11,6 +11,7 @@ DG_OUT_TOTAL = 8
 DG_VERSION = 118                     # must match include/depthg_corr.h: a stale library is refused
 DG_POINTWISE, DG_ZERO_CLAMP, DG_STABALIZE, DG_DEPTH_TERM, DG_NEED_GRAD, DG_SHARED_COORDS, DG_IDENTITY_GRID, DG_LINE_GRID, \
     DG_EXACT_MASKS, DG_FEATS_UNIT = (1 << i for i in range(10))
+DG_LIN_LAYERNORM, DG_LIN_GELU, DG_LIN_IN_BF16, DG_LIN_OUT_BF16 = 1, 2, 4, 8      # dg_vit_linear_forward flags
 
 EXPORTS = ["dg_version", "dg_last_error", "dg_corr_workspace_bytes", "dg_corr_forward", "dg_corr_backward",
            "dg_corr_materialize", "dg_corr_relaunch_main", "dg_fps_workspace_bytes", "dg_fps_coords", "dg_fps_coords_pair", "dg_rand_coords_state", "dg_rand_keep_state", "dg_super_perms",
@@ -22,7 +23,8 @@ EXPORTS = ["dg_version", "dg_last_error", "dg_corr_workspace_bytes", "dg_corr_fo
            "dg_cluster_lookup_backward", "dg_probe_ce_forward", "dg_probe_ce_backward", "dg_knn_similarities",
            "dg_prof_main_span", "dg_corr_materialize_shared", "dg_normalize_split", "dg_sampled_sumsq",
            "dg_corr_forward_extnorm", "dg_segment_predict", "dg_crf_workspace_bytes", "dg_crf_unary",
-           "dg_segment_unary", "dg_crf_filter", "dg_dense_crf", "dg_adam_step", "dg_attention_workspace_bytes", "dg_attention_forward"]
+           "dg_segment_unary", "dg_crf_filter", "dg_dense_crf", "dg_adam_step", "dg_attention_workspace_bytes", "dg_attention_forward",
+           "dg_vit_linear_packed_bytes", "dg_vit_linear_pack", "dg_vit_linear_forward"]
 
 
 class CorrDesc(ctypes.Structure):
@@ -168,6 +170,12 @@ def load():
     lib.dg_attention_workspace_bytes.argtypes = [i32] * 3
     lib.dg_attention_forward.restype = ctypes.c_int
     lib.dg_attention_forward.argtypes = [vp] + [i32] * 4 + [f32, vp, vp, ctypes.c_size_t, vp]
+    lib.dg_vit_linear_packed_bytes.restype = ctypes.c_size_t
+    lib.dg_vit_linear_packed_bytes.argtypes = [i32] * 2
+    lib.dg_vit_linear_pack.restype = ctypes.c_int
+    lib.dg_vit_linear_pack.argtypes = [vp, i32, i32, vp, vp]
+    lib.dg_vit_linear_forward.restype = ctypes.c_int
+    lib.dg_vit_linear_forward.argtypes = [vp, vp, vp, f32, vp, vp, vp, vp] + [i32] * 4 + [vp]
     lib.dg_prof_main_span.restype = ctypes.c_int
     lib.dg_prof_main_span.argtypes = [vp]
     _lib = lib

@@ -1723,3 +1723,40 @@ extern "C" int dg_attention_forward(const float* qkv, int32_t B, int32_t N, int3
     DG_HIP(dg_launch_attention(qkv, out, workspace, B, N, heads, scale, static_cast<hipStream_t>(stream_)));
     return DG_OK;
 }
+
+// ---- fused bf16 linear layers of the frozen ViT (dg_linear.hip)
+extern "C" size_t dg_vit_linear_packed_bytes(int32_t K, int32_t Nout) { return dg_linear_packed_bytes(K, Nout); }
+
+extern "C" int dg_vit_linear_pack(const float* weight, int32_t K, int32_t Nout, void* packed, dg_stream_t stream_) {
+    if (!dg_linear_supported(K, Nout))
+        return fail(DG_ERR_UNSUPPORTED, "dg_vit_linear_pack: K=%d Nout=%d (multiples of 64 up to 3072)", K, Nout);
+    if (!weight || !packed) return fail(DG_ERR_INVALID, "dg_vit_linear_pack: null pointer");
+    if (((uintptr_t)weight | (uintptr_t)packed) & 15) return fail(DG_ERR_INVALID, "dg_vit_linear_pack: weight and packed must be 16-byte aligned");
+    DG_HIP(dg_launch_linear_pack(weight, K, Nout, packed, static_cast<hipStream_t>(stream_)));
+    return DG_OK;
+}
+
+extern "C" int dg_vit_linear_forward(const void* x, const float* gamma, const float* beta, float eps, const void* packed, const float* bias,
+                                     const float* residual, void* out, int32_t M, int32_t K, int32_t Nout, int32_t flags,
+                                     dg_stream_t stream_) {
+    if (!dg_linear_supported(K, Nout))
+        return fail(DG_ERR_UNSUPPORTED, "dg_vit_linear_forward: K=%d Nout=%d (multiples of 64 up to 3072)", K, Nout);
+    if (flags & ~(DG_LIN_LAYERNORM | DG_LIN_GELU | DG_LIN_IN_BF16 | DG_LIN_OUT_BF16))
+        return fail(DG_ERR_INVALID, "dg_vit_linear_forward: unknown flags 0x%x", flags);
+    if (M < 1 || M > (1 << 24)) return fail(DG_ERR_INVALID, "dg_vit_linear_forward: M=%d", M);
+    if (!x || !packed || !out) return fail(DG_ERR_INVALID, "dg_vit_linear_forward: null pointer");
+    if (flags & DG_LIN_LAYERNORM) {
+        if (K > 768) return fail(DG_ERR_UNSUPPORTED, "dg_vit_linear_forward: LayerNorm prologue with K=%d (up to 768)", K);
+        if (flags & DG_LIN_IN_BF16) return fail(DG_ERR_INVALID, "dg_vit_linear_forward: the LayerNorm prologue reads fp32 rows");
+        if (!gamma || !beta) return fail(DG_ERR_INVALID, "dg_vit_linear_forward: the LayerNorm prologue needs gamma and beta");
+        if (!(eps >= 0.f) || std::isinf(eps)) return fail(DG_ERR_INVALID, "dg_vit_linear_forward: eps=%g", (double)eps);
+    } else {
+        gamma = beta = nullptr;
+    }
+    if (residual && (flags & DG_LIN_OUT_BF16)) return fail(DG_ERR_INVALID, "dg_vit_linear_forward: the residual stream is fp32, not a bf16 output");
+    if (x == out) return fail(DG_ERR_INVALID, "dg_vit_linear_forward: out may alias residual, not x");
+    if (((uintptr_t)x | (uintptr_t)gamma | (uintptr_t)beta | (uintptr_t)packed | (uintptr_t)bias | (uintptr_t)residual | (uintptr_t)out) & 15)
+        return fail(DG_ERR_INVALID, "dg_vit_linear_forward: every pointer must be 16-byte aligned");
+    DG_HIP(dg_launch_linear(x, gamma, beta, eps, packed, bias, residual, out, M, K, Nout, flags, static_cast<hipStream_t>(stream_)));
+    return DG_OK;
+}

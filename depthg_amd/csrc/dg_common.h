@@ -991,3 +991,10 @@ hipError_t dg_launch_adam(const dg_adam_seg* segs, int n_seg, const dg_adam_grou
 // ---- fused attention forward of the frozen ViT (dg_attn.hip; src/dino/vision_transformer.py:80-92)
 size_t dg_attn_workspace(int B, int heads, int N);           // bytes of the packed bf16 K / V images
 hipError_t dg_launch_attention(const float* qkv, float* out, void* ws, int B, int N, int heads, float scale, hipStream_t s);
+
+// ---- fused bf16 linear layers of the frozen ViT (dg_linear.hip; src/dino/vision_transformer.py:49-65, 68-92, 95-115)
+bool dg_linear_supported(int K, int Nout);                   // multiples of 64 up to 3072
+size_t dg_linear_packed_bytes(int K, int Nout);              // 0 when unsupported
+hipError_t dg_launch_linear_pack(const float* w, int K, int Nout, void* packed, hipStream_t s);
+hipError_t dg_launch_linear(const void* x, const float* gamma, const float* beta, float eps, const void* packed, const float* bias,
+                            const float* residual, void* out, int M, int K, int Nout, int flags, hipStream_t s);

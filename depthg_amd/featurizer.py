@@ -9,6 +9,8 @@ Differences from the reference, all on the build side:
                 (cfg.lhp with propagation_strategy == "attn", src/train_segmentation.py:202-203); otherwise the one-element
                 placeholder StandInFeaturizer returns.  cfg.dg_fused_attention (off by default) routes every block whose
                 probabilities nobody reads through the fused HIP kernel (ops.attention_forward).
+    linears     cfg.dg_fused_linear (off by default) runs the four linear layers of every block, with the LayerNorm, GELU and
+                residual add around them, through the bf16 MFMA kernel (ops.vit_linear_forward); the weights stay fp32 parameters.
     "KK"        the reference hard-codes 6 heads (:113); the head count of the model is used (the same for ViT-S).
     backbone    cfg.dg_dino_vit_kwargs (None, or a dict) overrides the architecture's constructor arguments: the test hook that builds
                 small backbones.
@@ -32,12 +34,13 @@ class DinoFeaturizer(nn.Module):
         self.feat_type = cfg.dino_feat_type
         arch = str(cfg.model_type)
         fused = bool(getattr(cfg, "dg_fused_attention", False))
+        fused_linear = bool(getattr(cfg, "dg_fused_linear", False))
         if arch not in vit.ARCHS:
             raise ValueError("Unknown arch and patch size")                     # :49-50
         kw = dict(getattr(cfg, "dg_dino_vit_kwargs", None) or {})
         if kw.pop("patch_size", self.patch_size) != self.patch_size:
             raise ValueError(f"depthg_amd: cfg.dg_dino_vit_kwargs names patch size other than cfg.dino_patch_size = {self.patch_size}")
-        model = vit.ARCHS[arch](patch_size=self.patch_size, fused_attention=fused, **kw)
+        model = vit.ARCHS[arch](patch_size=self.patch_size, fused_attention=fused, fused_linear=fused_linear, **kw)
         path = getattr(cfg, "pretrained_weights", None)
         if path is not None:
             msg = vit.load_checkpoint(model, path)                              # :52-64

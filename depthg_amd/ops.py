@@ -810,3 +810,113 @@ def attention_forward(qkv, heads, scale=None, out=None):
                                   _ptr(ws), need, _stream(dev))
     _lib.check(rc, "dg_attention_forward")
     return out
+
+
+VIT_LINEAR_MAX = 3072     # K and Nout of the fused linear kernel: multiples of 64 up to this
+
+
+def vit_linear_supported(K, Nout):
+    """Whether dg_vit_linear_forward has a plan for an nn.Linear(K, Nout): both multiples of 64 up to 3072.  (No library call: the
+    constructor of vit.VisionTransformer asks before anything is built.)"""
+    return all(64 <= int(v) <= VIT_LINEAR_MAX and int(v) % 64 == 0 for v in (K, Nout))
+
+
+def vit_linear_pack(weight):
+    """dg_vit_linear_pack: an nn.Linear weight (Nout, K) fp32 contiguous on the GPU -> uint8 (K * Nout * 2) tensor: the weight
+    rounded to bf16 in the MFMA fragment order k_lin_fwd reads.  Once per weight (the backbone is frozen)."""
+    if weight.dim() != 2:
+        raise ValueError(f"depthg_amd: weight must be (Nout, K), got {tuple(weight.shape)}")
+    Nout, K = weight.shape
+    if weight.dtype != torch.float32:
+        raise ValueError(f"depthg_amd: weight must be float32, got {weight.dtype}")
+    if not weight.is_contiguous():
+        raise ValueError(f"depthg_amd: weight must be contiguous (strides {weight.stride()})")
+    if not vit_linear_supported(K, Nout):
+        raise ValueError(f"depthg_amd: vit_linear_pack is built for K and Nout that are multiples of 64 up to {VIT_LINEAR_MAX}, "
+                         f"got K={K}, Nout={Nout}")
+    if not weight.is_cuda:
+        raise RuntimeError(f"depthg_amd: `weight` must live on the GPU (got {weight.device}); there is no CPU path")
+    if weight.data_ptr() & 15:
+        raise ValueError("depthg_amd: vit_linear_pack needs weight to start at a 16-byte aligned address")
+    lib = _lib.load()
+    packed = _empty((lib.dg_vit_linear_packed_bytes(K, Nout),), torch.uint8, weight.device)
+    _lib.check(lib.dg_vit_linear_pack(_ptr(weight.detach()), K, Nout, _ptr(packed), _stream(weight.device)), "dg_vit_linear_pack")
+    return packed
+
+
+def vit_linear_forward(x, packed, n_out, bias=None, *, ln_weight=None, ln_bias=None, eps=1e-6, gelu=False, residual=None,
+                       out=None, out_bf16=False):
+    """epilogue(prologue(x) W^T + bias) of one ViT linear layer as ONE launch (dg_vit_linear_forward;
+    src/dino/vision_transformer.py:49-65, 68-92, 95-115).
+        x          (..., K) contiguous on the GPU: float32, or bfloat16 (the fc1 -> fc2 hand-over)
+        packed     vit_linear_pack(weight) of the (n_out, K) weight;  bias: (n_out) float32 or None
+        ln_weight, ln_bias, eps   LayerNorm over the row first (float32 x, K <= 768)
+        gelu       exact GELU on accumulator + bias
+        residual   (..., n_out) float32: out = residual + (acc + bias); `out` may be `residual` itself
+        out        optional result buffer; out_bf16: a bfloat16 result (no residual then)
+    -> (..., n_out).  Forward only (the backbone is frozen); bf16 MFMA operands, fp32 accumulation and epilogue.  Runs on the caller's
+    current stream."""
+    n_out = int(n_out)
+    if x.dim() < 1:
+        raise ValueError(f"depthg_amd: x must be (..., K), got {tuple(x.shape)}")
+    K = x.shape[-1]
+    lead = tuple(x.shape[:-1])
+    M = 1
+    for d in lead:
+        M *= d
+    if not vit_linear_supported(K, n_out):
+        raise ValueError(f"depthg_amd: vit_linear_forward is built for K and Nout that are multiples of 64 up to {VIT_LINEAR_MAX}, "
+                         f"got K={K}, Nout={n_out}")
+    ln = ln_weight is not None or ln_bias is not None
+    if x.dtype not in (torch.float32, torch.bfloat16) or (ln and x.dtype != torch.float32):
+        raise ValueError(f"depthg_amd: x must be float32{'' if ln else ' or bfloat16'}, got {x.dtype}")
+    if not x.is_contiguous():
+        raise ValueError(f"depthg_amd: x must be contiguous (strides {x.stride()})")
+    if ln and (ln_weight is None or ln_bias is None):
+        raise ValueError("depthg_amd: the LayerNorm prologue needs both ln_weight and ln_bias")
+    if ln and K > 768:
+        raise ValueError(f"depthg_amd: the LayerNorm prologue is built for K <= 768, got {K}")
+    if residual is not None and out_bf16:
+        raise ValueError("depthg_amd: the residual stream is float32; a bfloat16 output takes no residual")
+    small = [("bias", bias, n_out), ("ln_weight", ln_weight, K), ("ln_bias", ln_bias, K)]
+    for name, t, n in small:
+        if t is not None and not (t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == (n,)):
+            raise ValueError(f"depthg_amd: `{name}` must be a contiguous float32 ({n},) tensor")
+    if residual is not None and not (residual.dtype == torch.float32 and residual.is_contiguous()
+                                     and tuple(residual.shape) == lead + (n_out,)):
+        raise ValueError(f"depthg_amd: `residual` must be a contiguous float32 {lead + (n_out,)} tensor")
+    tensors = [x, bias, ln_weight, ln_bias, residual]
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors):
+        raise RuntimeError("depthg_amd: vit_linear_forward has no backward (the ViT is frozen); call it under torch.no_grad()")
+    if not x.is_cuda:            # (shape, dtype and autograd are refused first: those hold on any device)
+        raise RuntimeError(f"depthg_amd: `x` must live on the GPU (got {x.device}); there is no CPU path")
+    if M < 1:
+        raise ValueError(f"depthg_amd: x must hold at least one row, got {tuple(x.shape)}")
+    dev = x.device
+    odt = torch.bfloat16 if out_bf16 else torch.float32
+    if out is None:
+        out = _empty(lead + (n_out,), odt, dev)
+    elif not (isinstance(out, torch.Tensor) and out.device == dev and out.dtype == odt and out.is_contiguous()
+              and tuple(out.shape) == lead + (n_out,)):
+        raise ValueError(f"depthg_amd: `out` must be a contiguous {odt} {lead + (n_out,)} tensor on {dev}")
+    lib = _lib.load()
+    if not (isinstance(packed, torch.Tensor) and packed.device == dev and packed.dtype == torch.uint8 and packed.is_contiguous()
+            and packed.numel() == lib.dg_vit_linear_packed_bytes(K, n_out)):
+        raise ValueError(f"depthg_amd: `packed` must be vit_linear_pack(weight) of a ({n_out}, {K}) weight on {dev}")
+    ptrs = 0
+    for t in tensors + [packed, out]:
+        if t is not None:
+            if t.device != dev:
+                raise RuntimeError(f"depthg_amd: every tensor must live on {dev} (got {t.device})")
+            ptrs |= t.data_ptr()
+    if ptrs & 15:                # (a slice of a larger buffer can start anywhere; the kernel uses 128-bit accesses)
+        raise ValueError("depthg_amd: vit_linear_forward needs every tensor to start at a 16-byte aligned address")
+    if out.data_ptr() == x.data_ptr():
+        raise ValueError("depthg_amd: `out` may alias `residual`, not `x`")
+    flags = (_lib.DG_LIN_LAYERNORM if ln else 0) | (_lib.DG_LIN_GELU if gelu else 0) \
+        | (_lib.DG_LIN_IN_BF16 if x.dtype == torch.bfloat16 else 0) | (_lib.DG_LIN_OUT_BF16 if out_bf16 else 0)
+    det = lambda t: _ptr(t.detach()) if t is not None else _ptr(None)
+    rc = lib.dg_vit_linear_forward(det(x), det(ln_weight), det(ln_bias), float(eps), _ptr(packed), det(bias), det(residual), _ptr(out),
+                                   M, K, n_out, flags, _stream(dev))
+    _lib.check(rc, "dg_vit_linear_forward")
+    return out

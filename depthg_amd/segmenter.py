@@ -24,7 +24,8 @@ frozen backbone, the 27 x dim linear-probe convolution and - unless cfg.dg_fused
 all nine tensors (optim.FusedAdamSet) instead of three torch.optim.Adam steps.  Under data parallelism `all_reduced_parameters()`
 is what `parallel.GradBucket` all-reduces.  With cfg.dg_dino_backbone (build-side key, off by default) the featurizer is
 featurizer.DinoFeaturizer - the real DINO ViT of depthg_amd/vit.py - instead of StandInFeaturizer; cfg.dg_fused_attention then routes
-its attention through the HIP kernel of dg_attn.hip.
+its attention through the HIP kernel of dg_attn.hip and cfg.dg_fused_linear its blocks' linear layers (with their LayerNorm, GELU and
+residual adds) through the bf16 MFMA kernel of dg_linear.hip.
 """
 from types import SimpleNamespace
 from typing import Dict, Optional
@@ -368,9 +369,9 @@ def default_segmenter_cfg(**over) -> SimpleNamespace:
         # build-side: the step's three Adams as one HIP launch (optim.FusedAdam / FusedAdamSet)
         dg_fused_adam=False,
         # build-side: the featurizer is featurizer.DinoFeaturizer (the ViT of vit.py) instead of StandInFeaturizer; its attention
-        # through the fused HIP kernel (ops.attention_forward)
+        # through the fused HIP kernel (ops.attention_forward), its blocks' linear layers through ops.vit_linear_forward
         # (dg_dino_vit_kwargs: test hook, constructor arguments of the ViT that override the architecture's)
-        dg_dino_backbone=False, dg_fused_attention=False, dg_dino_vit_kwargs=None)
+        dg_dino_backbone=False, dg_fused_attention=False, dg_fused_linear=False, dg_dino_vit_kwargs=None)
     for k, v in over.items():
         setattr(cfg, k, v)
     return cfg

@@ -15,6 +15,12 @@ linear.  fused = False is the reference's fp32 formulation in its order of opera
 materialised); fused = True (cfg.dg_fused_attention, off by default) is ops.attention_forward - the HIP kernel k_attn_fwd that
 keeps the matrix on the compute unit (bf16 operands, fp32 softmax) and so returns no probabilities.  The callers decide: a block
 asked for its attention probabilities is run with fused = False.
+
+`fused_linear` (cfg.dg_fused_linear, off by default) runs the four linear layers of every block through ops.vit_linear_forward - the
+HIP kernel k_lin_fwd (bf16 MFMA operands, fp32 accumulation) - as four launches: norm1 + qkv, proj + residual, norm2 + fc1 + GELU
+(handed over as bf16), fc2 + residual.  The parameters stay the fp32 nn.Linear / nn.LayerNorm ones; the bf16 fragment-order copies
+the kernel reads are a cache on the block (`Block._packs`), never part of state_dict(), rebuilt when a weight's storage or version
+counter changes (load_state_dict, .to(device), an in-place edit).
 """
 import math
 
@@ -78,9 +84,55 @@ class Block(nn.Module):
         self.norm2 = nn.LayerNorm(dim, eps=eps)
         self.mlp = Mlp(dim, int(dim * mlp_ratio))
 
-    def forward(self, x, return_attention=False, return_qkv=False, fused=False):
+    def packed_weight(self, name):
+        """The bf16 fragment-order copy of the weight of qkv / proj / fc1 / fc2 (ops.vit_linear_pack), packed at first use and again
+        whenever the parameter's storage or version counter is not the one it was packed from."""
+        w = self._linear(name).weight
+        key = (w.data_ptr(), w._version, w.device)
+        hit = self.__dict__.setdefault("_packs", {}).get(name)
+        if hit is None or hit[0] != key:
+            hit = (key, ops.vit_linear_pack(w.detach()))
+            self._packs[name] = hit
+        return hit[1]
+
+    def _apply(self, fn, *args, **kwargs):
+        """.to(device) / .cpu() / .float(): the parameters move, the packs of the old ones are dropped (the allocator may hand the
+        new storage the old address)."""
+        self.__dict__.pop("_packs", None)
+        return super()._apply(fn, *args, **kwargs)
+
+    def pack_is_stale(self, name):
+        """True when the next fused forward will pack the weight of `name` (again)."""
+        w, hit = self._linear(name).weight, self.__dict__.get("_packs", {}).get(name)
+        return hit is None or hit[0] != (w.data_ptr(), w._version, w.device)
+
+    def _linear(self, name):
+        return {"qkv": self.attn.qkv, "proj": self.attn.proj, "fc1": self.mlp.fc1, "fc2": self.mlp.fc2}[name]
+
+    def _fused_linear(self, name, x, norm=None, **kw):
+        lin = self._linear(name)
+        if norm is not None:
+            kw.update(ln_weight=norm.weight, ln_bias=norm.bias, eps=norm.eps)
+        return ops.vit_linear_forward(x, self.packed_weight(name), lin.out_features, lin.bias, **kw)
+
+    def _forward_fused_linear(self, x, return_attention, return_qkv, fused):
+        """The block as four launches of k_lin_fwd around the attention.  `x` is left as it is: proj writes a fresh residual
+        stream, fc2 adds into that one in place."""
+        x = x.contiguous()
+        qkv_packed = self._fused_linear("qkv", x, self.norm1)
+        y, attn, qkv = attention(qkv_packed, self.attn.num_heads, self.attn.scale, fused and not return_attention)
+        if return_attention:
+            return attn
+        x = self._fused_linear("proj", y.contiguous(), residual=x)
+        hidden = self._fused_linear("fc1", x, self.norm2, gelu=True, out_bf16=True)
+        x = self._fused_linear("fc2", hidden, residual=x, out=x)
+        return (x, attn, qkv) if return_qkv else x
+
+    def forward(self, x, return_attention=False, return_qkv=False, fused=False, fused_linear=False):
         """fused: this block's attention through the HIP kernel.  It yields no probabilities, so return_attention overrides it
-        and a fused return_qkv hands back (x, None, qkv)."""
+        and a fused return_qkv hands back (x, None, qkv).  fused_linear: the linear layers through the HIP kernel."""
+        if fused_linear:
+            return self._forward_fused_linear(x, return_attention, return_qkv, fused)
         y, attn, qkv = self.attn(self.norm1(x), fused=fused and not return_attention)
         if return_attention:
             return attn
@@ -103,16 +155,26 @@ class PatchEmbed(nn.Module):
 
 
 class VisionTransformer(nn.Module):
-    """:137-259.  `fused_attention`: the blocks' attention through ops.attention_forward (GPU only; head dimension 64)."""
+    """:137-259.  `fused_attention`: the blocks' attention through ops.attention_forward (GPU only; head dimension 64).
+    `fused_linear`: the blocks' linear layers through ops.vit_linear_forward (GPU only; widths that are multiples of 64)."""
 
     def __init__(self, img_size=(224,), patch_size=16, in_chans=3, embed_dim=768, depth=12, num_heads=12, mlp_ratio=4., qkv_bias=True,
-                 qk_scale=None, eps=1e-6, fused_attention=False):
+                 qk_scale=None, eps=1e-6, fused_attention=False, fused_linear=False):
         super().__init__()
         self.num_features = self.embed_dim = embed_dim
         self.num_heads = num_heads
         self.fused_attention = bool(fused_attention)
         if self.fused_attention and embed_dim // num_heads != 64:
             raise ValueError(f"depthg_amd: the fused attention kernel is built for head dimension 64, got {embed_dim // num_heads}")
+        self.fused_linear = bool(fused_linear)
+        if self.fused_linear:
+            hidden = int(embed_dim * mlp_ratio)
+            for what, k, n in (("embed_dim", embed_dim, 3 * embed_dim), ("mlp hidden width", hidden, embed_dim)):
+                if not ops.vit_linear_supported(k, n):
+                    raise ValueError(f"depthg_amd: the fused linear kernel is built for layer widths that are multiples of 64 up to "
+                                     f"{ops.VIT_LINEAR_MAX}, got {what} = {k} (a {k} -> {n} layer)")
+            if embed_dim > 768:
+                raise ValueError(f"depthg_amd: the fused linear kernel's LayerNorm prologue is built for embed_dim <= 768, got {embed_dim}")
         self.patch_embed = PatchEmbed(img_size[0], patch_size, in_chans, embed_dim)
         self.cls_token = nn.Parameter(torch.zeros(1, 1, embed_dim))
         self.pos_embed = nn.Parameter(torch.zeros(1, self.patch_embed.num_patches + 1, embed_dim))
@@ -149,7 +211,7 @@ class VisionTransformer(nn.Module):
         """All tokens after the final norm (:221-226)."""
         x = self.prepare_tokens(x)
         for blk in self.blocks:
-            x = blk(x, fused=self.fused_attention)
+            x = blk(x, fused=self.fused_attention, fused_linear=self.fused_linear)
         return self.norm(x)
 
     def forward(self, x):
@@ -163,25 +225,25 @@ class VisionTransformer(nn.Module):
         feat, attns, qkvs = [], [], []
         for i, blk in enumerate(self.blocks):
             if len(self.blocks) - i <= n:
-                x, attn, qkv = blk(x, return_qkv=True, fused=self.fused_attention and not want_attn)
+                x, attn, qkv = blk(x, return_qkv=True, fused=self.fused_attention and not want_attn, fused_linear=self.fused_linear)
                 feat.append(self.norm(x)); attns.append(attn); qkvs.append(qkv)
             else:
-                x = blk(x, fused=self.fused_attention)
+                x = blk(x, fused=self.fused_attention, fused_linear=self.fused_linear)
         return feat, attns, qkvs
 
     def get_last_selfattention(self, x):
         """:242-249."""
         x = self.prepare_tokens(x)
         for blk in self.blocks[:-1]:
-            x = blk(x, fused=self.fused_attention)
-        return self.blocks[-1](x, return_attention=True)
+            x = blk(x, fused=self.fused_attention, fused_linear=self.fused_linear)
+        return self.blocks[-1](x, return_attention=True, fused_linear=self.fused_linear)
 
     def get_intermediate_layers(self, x, n=1):
         """:251-259."""
         x = self.prepare_tokens(x)
         out = []
         for i, blk in enumerate(self.blocks):
-            x = blk(x, fused=self.fused_attention)
+            x = blk(x, fused=self.fused_attention, fused_linear=self.fused_linear)
             if len(self.blocks) - i <= n:
                 out.append(self.norm(x))
         return out

@@ -603,6 +603,34 @@ size_t dg_attention_workspace_bytes(int32_t B, int32_t heads, int32_t N);      /
 int dg_attention_forward(const float* qkv, int32_t B, int32_t N, int32_t heads, int32_t head_dim, float scale, float* out,
                          void* workspace, size_t workspace_bytes, dg_stream_t stream);
 
+/*
+ * Linear layers of the frozen DINO ViT with their surroundings fused (src/dino/vision_transformer.py:49-65 the MLP, 68-92 qkv and
+ * proj, 95-115 the block's norms and residual adds):   y = epilogue(prologue(x) W^T + b).  Forward only (the backbone is frozen).
+ *  dg_vit_linear_pack : weight fp32 (Nout, K) as nn.Linear stores it -> `packed`, dg_vit_linear_packed_bytes(K, Nout) bytes: the
+ *      weight rounded to bf16 (nearest even) in MFMA fragment order.  Once per weight; again only when the weight changes.
+ *  dg_vit_linear_forward :
+ *      x        (M, K) row-major contiguous: fp32, or bf16 with DG_LIN_IN_BF16 (the fc1 -> fc2 hand-over)
+ *      gamma, beta, eps : with DG_LIN_LAYERNORM the row is normalised first (norm1 -> qkv, norm2 -> fc1; :101-104): mean and biased
+ *                 variance in fp32 over the fp32 row (two passes), (x - mean) * rstd * gamma + beta in fp32.  K <= 768, fp32 x only
+ *      packed   the output of dg_vit_linear_pack for this (K, Nout)
+ *      bias     (Nout) fp32 or NULL
+ *      DG_LIN_GELU : exact (erf) GELU in fp32 on accumulator + bias (:56, nn.GELU's default)
+ *      residual (M, Nout) fp32 or NULL: out = residual + (acc + bias) in fp32 (:105-106); `out` may alias `residual`, not `x`
+ *      out      (M, Nout): fp32, or bf16 with DG_LIN_OUT_BF16 (no residual then)
+ *  Shapes: M >= 1 (the row tail is handled in the kernel; nothing outside the tensors is read or written); K and Nout multiples of
+ *  64 up to 3072 - DG_ERR_UNSUPPORTED otherwise, before any launch.  Every pointer 16-byte aligned (DG_ERR_INVALID otherwise).
+ *  Arithmetic: the A operand (LayerNorm output, or x) and W rounded to bf16, products on v_mfma_f32_32x32x16_bf16 with fp32
+ *  accumulation, bias / GELU / residual in fp32.  No host synchronisation, no workspace beyond `packed`, one launch on `stream`.
+ */
+#define DG_LIN_LAYERNORM 1
+#define DG_LIN_GELU      2
+#define DG_LIN_IN_BF16   4
+#define DG_LIN_OUT_BF16  8
+size_t dg_vit_linear_packed_bytes(int32_t K, int32_t Nout);                     /* 0 on bad arguments */
+int dg_vit_linear_pack(const float* weight, int32_t K, int32_t Nout, void* packed, dg_stream_t stream);
+int dg_vit_linear_forward(const void* x, const float* gamma, const float* beta, float eps, const void* packed, const float* bias,
+                          const float* residual, void* out, int32_t M, int32_t K, int32_t Nout, int32_t flags, dg_stream_t stream);
+
 /* Measurement aid: name of the kernel the fused correlation launch of this descriptor runs ("k_corr2": the one-wave-per-SIMD
  * form of dg_corr2.hip, "k_corr_main": the general form), decided by the same predicate the launch uses; NULL on a bad desc. */
 const char* dg_corr_main_kernel_name(const dg_corr_desc* desc);

@@ -4,6 +4,10 @@
 whole-model figures of vit_small(8) with seeded random weights.  Markdown on stdout or into the file named.  Needs the GPU.
 
     python scripts/vit_parity.py [profiles/vit_parity.md]
+    python scripts/vit_parity.py --linear [profiles/vit_linear_parity.md]
+
+--linear: the same for the fused linear kernel (k_lin_fwd, ops.vit_linear_forward) over the grid of tests/test_gpu_vit_linear.py
+against the yardstick of tests/linear_reference.py, then the whole model in the three fused flag combinations.
 """
 import os
 import sys
@@ -19,7 +23,70 @@ import attention_reference as AR  # noqa: E402
 from depthg_amd import ops, vit  # noqa: E402
 
 
+def linear_main(path):
+    import linear_reference as LR
+    if not torch.cuda.is_available():
+        sys.exit("vit_parity.py: needs the GPU (there is no CPU path)")
+    dev = torch.device("cuda:0")
+    out = ["# Fused linear parity (k_lin_fwd), measured on an MI355X", "",
+           "Relative L2 error against the float64 layer; yardstick = the float64 layer with the A operand (LayerNorm output, or x) and",
+           f"the weight rounded to bf16; the tests hold kernel <= {LR.FACTOR} x yardstick (tests/test_gpu_vit_linear.py).  Per (kind, K, Nout):",
+           "the largest ratio over M in {1, 63, 64, 129, 785, 4803} and sigma in {1, 3}, with the yardstick and kernel error of that case.", "",
+           "| kind | K | Nout | yardstick | k_lin_fwd | largest ratio | at M, sigma |", "|---|---|---|---|---|---|---|"]
+    worst = (0.0, None)
+    for kind, (ln, gelu, res, in_bf16, out_bf16) in LR.KINDS.items():
+        for K, Nout in [(128, 384), (384, 1152), (384, 384), (384, 1536), (1536, 384), (768, 2304), (3072, 768)]:
+            if not LR.kind_fits(kind, K):
+                continue
+            top = None
+            for M in (1, 63, 64, 129, 785, 3 * 1601):
+                for sigma in (1.0, 3.0):
+                    c = {k: (v.to(dev) if v is not None else None) for k, v in LR.make_case(kind, M, K, Nout, sigma, seed=100 * K + Nout + M).items()}
+                    got = ops.vit_linear_forward(c["x"], ops.vit_linear_pack(c["w"]), Nout, c["b"], ln_weight=c["gamma"], ln_bias=c["beta"],
+                                                 eps=LR.EPS, gelu=gelu, residual=c["residual"], out_bf16=out_bf16)
+                    err, yard = LR.ratios(got, kind, c)
+                    if top is None or err / yard > top[0]:
+                        top = (err / yard, yard, err, M, sigma)
+            out.append(f"| {kind} | {K} | {Nout} | {top[1]:.3e} | {top[2]:.3e} | {top[0]:.3f} | {top[3]}, {top[4]:g} |")
+            if top[0] > worst[0]:
+                worst = (top[0], f"{kind}, K = {K}, Nout = {Nout}, M = {top[3]}, sigma = {top[4]:g}")
+    out += ["", f"Largest ratio of the table: {worst[0]:.3f} ({worst[1]}).  The kind with a bf16 result carries the rounding of its output on top of",
+            "the operands' (the CPU emulation of the prescribed arithmetic gives 1.20-1.22 there, 1.00 elsewhere: tests/linear_reference.py).", "",
+            "## Whole model: vit_small(8), seeded random weights, B = 2, against the fp32 torch path", "",
+            "| input | flags | output | bf16-operand model (yardstick) | fused | ratio |", "|---|---|---|---|---|---|"]
+    model = AR.seed_module(vit.vit_small(8), 42).to(dev).eval()
+
+    def outputs(m, x):
+        feat, _, qkv = m.get_intermediate_feat(x, n=1, want_attn=False)
+        B, N = feat[0].shape[:2]
+        return {"forward_feats": m.forward_feats(x), "feat": feat[0], "KK": qkv[0][1].permute(0, 2, 1, 3).reshape(B, N, -1)}
+
+    for hw in ((224, 224), (224, 320)):
+        x = torch.randn(2, 3, *hw, generator=torch.Generator().manual_seed(7)).to(dev)
+        with torch.no_grad():
+            exact = outputs(model, x)
+            for fa, fl in ((False, True), (True, True), (True, False)):
+                yard = outputs(LR.bf16_operand_model(model, linear=fl, attention=fa), x)
+                model.fused_attention, model.fused_linear = fa, fl
+                fused = outputs(model, x)
+                model.fused_attention = model.fused_linear = False
+                for name in exact:
+                    ey, ef = AR.rel_l2(yard[name], exact[name].double()), AR.rel_l2(fused[name], exact[name].double())
+                    out.append(f"| {hw[0]} x {hw[1]} | attention={fa}, linear={fl} | {name} | {ey:.3e} | {ef:.3e} | {ef / ey:.3f} |")
+    out += ["", "The feature error of `cfg.dg_fused_attention` alone against the fp32 model is 7.4e-5 / 5.4e-5 at B = 32 (README); with",
+            "`cfg.dg_fused_linear` it is the `fused` column of the linear=True rows: the bf16 rounding of the operands of 48 linear layers.",
+            "No pretrained DINO checkpoint was available where this was measured: every figure is on seeded random weights, and the error",
+            "on real DINO weights is unmeasured."]
+    text = "\n".join(out) + "\n"
+    if path:
+        with open(path, "w") as fh:
+            fh.write(text)
+    print(text)
+
+
 def main():
+    if len(sys.argv) > 1 and sys.argv[1] == "--linear":
+        return linear_main(sys.argv[2] if len(sys.argv) > 2 else None)
     if not torch.cuda.is_available():
         sys.exit("vit_parity.py: needs the GPU (there is no CPU path)")
     dev = torch.device("cuda:0")

@@ -8,8 +8,12 @@ One JSON line per form and size, printed and appended to profiles/vit_time.jsonl
     sdpa_fp32        torch.nn.functional.scaled_dot_product_attention on fp32 q, k, v
     sdpa_bf16        the same on q, k, v cast to bf16 (result cast back to fp32)
     dg_fused         cfg.dg_fused_attention: ops.attention_forward (k_attn_pack + k_attn_fwd)
+    dg_fused_linear  cfg.dg_fused_attention + cfg.dg_fused_linear: the blocks' linear layers, LayerNorms, GELU and residual adds
+                     through ops.vit_linear_forward (k_lin_fwd) as well
+    torch_bf16       torch's own route, for honesty: the whole backbone .to(bfloat16) on a bf16 input with bf16 SDPA (the residual
+                     stream, LayerNorm and GELU in bf16 too: less precise than dg_fused_linear, whose stream stays fp32)
 
-All four in one process; host clock around `--steps` double passes ending in a device synchronise, after warm-up of every form and
+All six in one process; host clock around `--steps` double passes ending in a device synchronise, after warm-up of every form and
 size; the forms alternate and each is repeated `--repeats` times: median [min, max] in milliseconds.  The line of dg_fused also
 carries the algorithmic FLOPs of its attention (4 * B * heads * N^2 * 64 per block) for use with a kernel trace.  Needs the GPU.
 
@@ -17,6 +21,7 @@ carries the algorithmic FLOPs of its attention (4 * B * heads * N^2 * 64 per blo
     python scripts/vit_time.py --only dg_fused --sizes 224 --steps 2 --repeats 1      # the run to put under rocprofv3 --kernel-trace --stats
 """
 import argparse
+import copy
 import json
 import os
 import statistics
@@ -67,17 +72,33 @@ def main():
     torch.manual_seed(0)
     model = vit.vit_small(8).to(dev).eval()
     torch_attention = vit.attention
+    model_bf16 = copy.deepcopy(model).to(torch.bfloat16)
+
+    def sdpa_native(qkv_packed, heads, scale, fused=False):
+        B, N, C3 = qkv_packed.shape
+        qkv = qkv_packed.reshape(B, N, 3, heads, C3 // (3 * heads)).permute(2, 0, 3, 1, 4)
+        x = F.scaled_dot_product_attention(qkv[0], qkv[1], qkv[2], scale=scale)
+        return x.transpose(1, 2).reshape(B, N, C3 // 3), None, qkv
 
     def run(form, x, x_pos):
-        model.fused_attention = form == "dg_fused"
+        if form == "torch_bf16":
+            vit.attention = sdpa_native
+            try:
+                with torch.no_grad():
+                    return model_bf16.forward_feats(x.to(torch.bfloat16)).float(), model_bf16.forward_feats(x_pos.to(torch.bfloat16)).float()
+            finally:
+                vit.attention = torch_attention
+        model.fused_attention = form in ("dg_fused", "dg_fused_linear")
+        model.fused_linear = form == "dg_fused_linear"
         vit.attention = {"sdpa_fp32": sdpa_attention(torch.float32), "sdpa_bf16": sdpa_attention(torch.bfloat16)}.get(form, torch_attention)
         try:
             with torch.no_grad():
                 return model.forward_feats(x), model.forward_feats(x_pos)
         finally:
             vit.attention = torch_attention
+            model.fused_attention = model.fused_linear = False
 
-    names = ["materialised", "sdpa_fp32", "sdpa_bf16", "dg_fused"]
+    names = ["materialised", "sdpa_fp32", "sdpa_bf16", "dg_fused", "dg_fused_linear", "torch_bf16"]
     if args.only:
         names = [args.only]
     lines = []
@@ -103,6 +124,8 @@ def main():
             if exact is not None:
                 got = forms[k]()[0]
                 line["rel_l2_vs_materialised"] = float((got - exact).norm() / exact.norm())
+            if k == "dg_fused_linear":
+                line["linear_gflop_per_double_pass"] = round(2 * 12 * 2 * args.batch * N * 12 * 384 * 384 / 1e9, 1)
             if k == "dg_fused":
                 line["attention_gflop_per_double_pass"] = round(2 * 12 * 4 * args.batch * 6 * N * N * 64 / 1e9, 1)
             lines.append(line)
