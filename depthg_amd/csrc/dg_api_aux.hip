@@ -1,0 +1,314 @@
+// C ABI of the gfx950 DepthG library (include/depthg_corr.h), the units' shared state and the small subsystems: version and error
+// text, the library's side stream, batch maps / random draws / coordinate samplers, kNN, LHP, fused Adam, ViT attention and linear.
+// Host-side only: argument checks and kernel launches on the caller's stream.
+#include "dg_api.h"
+
+#include <cstdarg>
+
+// ---- error reporting (dg_api.h)
+thread_local char g_err[512] = "";
+int fail(int code, const char* fmt, ...) {
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(g_err, sizeof(g_err), fmt, ap);
+    va_end(ap);
+    return code;
+}
+
+extern "C" int dg_version(void) { return DG_VERSION; }
+extern "C" const char* dg_last_error(void) { return g_err; }
+
+// ---- the library's second stream (dg_api.h)
+SideStream* side_stream_for(hipStream_t caller) {
+    static std::mutex mu;
+    static std::map<int, SideStream> table;
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return nullptr;
+    std::lock_guard<std::mutex> lk(mu);
+    auto it = table.find(dev);
+    if (it != table.end()) return &it->second;
+    hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(caller, &st) != hipSuccess || st != hipStreamCaptureStatusNone) return nullptr;
+    hipStream_t s = nullptr;
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};       // fork, join, two hand-overs from the side stream in mid-region
+    if (hipStreamCreateWithFlags(&s, hipStreamNonBlocking) != hipSuccess) return nullptr;
+    bool ok = true;
+    for (int i = 0; i < 4 && ok; ++i) ok = hipEventCreateWithFlags(&ev[i], hipEventDisableTiming) == hipSuccess;
+    if (!ok) {
+        for (int i = 0; i < 4; ++i) if (ev[i]) (void)hipEventDestroy(ev[i]);      // nothing half-made stays behind: the call launches in sequence instead
+        (void)hipStreamDestroy(s);
+        return nullptr;
+    }
+    SideStream& ss = table[dev];        // (std::map nodes do not move: the pointer stays valid; std::mutex is not copyable)
+    ss.s = s; ss.fork = ev[0]; ss.join = ev[1]; ss.mid[0] = ev[2]; ss.mid[1] = ev[3];
+    return &ss;
+}
+
+extern "C" int dg_super_perms(const float* keys, int32_t count, int32_t B, int64_t* out, dg_stream_t stream_) {
+    if (count < 0 || B < 1 || B > 8192) return fail(DG_ERR_INVALID, "dg_super_perms: count=%d B=%d outside the supported range", count, B);
+    if (count == 0) return DG_OK;
+    if (!keys || !out) return fail(DG_ERR_INVALID, "null pointer");
+    DG_HIP(dg_launch_super_perms(keys, 0ull, nullptr, count, B, out, static_cast<hipStream_t>(stream_)));
+    return DG_OK;
+}
+
+extern "C" int dg_super_perms_seeded(uint64_t seed, int32_t count, int32_t B, int64_t* out, dg_stream_t stream_) {
+    if (count < 0 || B < 1 || B > 8192) return fail(DG_ERR_INVALID, "bad super_perm dimensions");
+    if (count == 0) return DG_OK;
+    if (!out) return fail(DG_ERR_INVALID, "null pointer");
+    DG_HIP(dg_launch_super_perms(nullptr, seed, nullptr, count, B, out, static_cast<hipStream_t>(stream_)));
+    return DG_OK;
+}
+
+extern "C" int dg_super_perms_state(uint64_t* state, int32_t count, int32_t B, int64_t* out, dg_stream_t stream_) {
+    if (count < 0 || B < 1 || B > 8192) return fail(DG_ERR_INVALID, "bad super_perm dimensions");
+    if (count == 0) return DG_OK;
+    if (!out || !state) return fail(DG_ERR_INVALID, "null pointer");
+    DG_HIP(dg_launch_super_perms(nullptr, 0ull, reinterpret_cast<unsigned long long*>(state), count, B, out, static_cast<hipStream_t>(stream_)));
+    return DG_OK;
+}
+
+extern "C" int dg_rand_coords_state(uint64_t* state, int64_t n, float* out, dg_stream_t stream_) {
+    if (!state || !out) return fail(DG_ERR_INVALID, "null pointer");
+    if (n < 1 || n > (1ll << 24)) return fail(DG_ERR_INVALID, "dg_rand_coords_state: n=%lld outside [1, 2^24]", (long long)n);
+    DG_HIP(dg_launch_rand_coords_state(reinterpret_cast<unsigned long long*>(state), out, (int)n, static_cast<hipStream_t>(stream_)));
+    return DG_OK;
+}
+
+extern "C" int dg_rand_keep_state(uint64_t* state, int64_t n, float p_keep, float* out, dg_stream_t stream_) {
+    if (!state || !out) return fail(DG_ERR_INVALID, "null pointer");
+    if (n < 1 || n > (1ll << 24) || !(p_keep >= 0.f && p_keep <= 1.f)) return fail(DG_ERR_INVALID, "dg_rand_keep_state: n=%lld, p_keep=%g", (long long)n, (double)p_keep);
+    DG_HIP(dg_launch_rand_coords_state(reinterpret_cast<unsigned long long*>(state), out, (int)n, static_cast<hipStream_t>(stream_), p_keep));
+    return DG_OK;
+}
+
+extern "C" int dg_salience_coords(const float* salience, int32_t B, int32_t H, int32_t W, int32_t n, const float* u_sel,
+                                  const float* u_fallback, float* out_coords, dg_stream_t stream_) {
+    if (!salience || !u_sel || !u_fallback || !out_coords) return fail(DG_ERR_INVALID, "null pointer");
+    if (B < 1 || H < 1 || W < 1 || n < 1) return fail(DG_ERR_INVALID, "bad salience sampler dimensions");
+    if ((size_t)H * W > (1u << 24)) return fail(DG_ERR_UNSUPPORTED, "salience map %dx%d too large", H, W);
+    DG_HIP(dg_launch_salience_coords(salience, B, H, W, n, u_sel, u_fallback, out_coords, static_cast<hipStream_t>(stream_)));
+    return DG_OK;
+}
+
+extern "C" int dg_simple_depth_coords(const float* depth, int32_t B, int32_t depth_h, int32_t depth_w, int32_t h, int32_t w,
+                                      int32_t n, const float* u_value, const float* u_pick, float* out_coords,
+                                      dg_stream_t stream_) {
+    if (!depth || !u_value || !u_pick || !out_coords) return fail(DG_ERR_INVALID, "null pointer");
+    if (B < 1 || h < 1 || w < 1 || n < 1 || depth_h < 1 || depth_w < 1) return fail(DG_ERR_INVALID, "bad sampler dimensions");
+    if ((size_t)h * w > 4096) return fail(DG_ERR_UNSUPPORTED, "feature map %dx%d too large for the sampler (max 4096 pixels)", h, w);
+    DG_HIP(dg_launch_simple_coords(depth, B, depth_h, depth_w, h, w, n, u_value, u_pick, out_coords,
+                                   static_cast<hipStream_t>(stream_)));
+    return DG_OK;
+}
+
+extern "C" int dg_knn_similarities(const float* queries, const float* feats, int64_t rows_q, int64_t n, int32_t F, int64_t q_stride,
+                                   int64_t f_stride, float* out, int64_t out_stride, dg_stream_t stream_) {
+    if (rows_q < 0 || n < 0 || F < 1 || q_stride < F || f_stride < F || out_stride < n) return fail(DG_ERR_INVALID, "bad similarity dimensions");
+    if (rows_q == 0 || n == 0) return DG_OK;
+    if (!queries || !feats || !out) return fail(DG_ERR_INVALID, "null pointer");
+    if (n > 65535ll * 128) return fail(DG_ERR_UNSUPPORTED, "more than 8,388,480 candidate rows per call");
+    DG_HIP(dg_launch_sims_nt(queries, feats, rows_q, n, F, q_stride, f_stride, out, out_stride, static_cast<hipStream_t>(stream_)));
+    return DG_OK;
+}
+
+extern "C" int dg_topk_rows(const float* vals, int64_t rows, int64_t cols, int64_t row_stride, int32_t k, int64_t* out_idx,
+                            float* out_val, dg_stream_t stream_) {
+    if (rows < 0 || cols < 1 || k < 1 || row_stride < cols) return fail(DG_ERR_INVALID, "bad top-k dimensions");
+    if (k > 64 || k > cols) return fail(DG_ERR_UNSUPPORTED, "top-k needs k <= 64 and k <= cols (k=%d, cols=%lld)", k, (long long)cols);
+    if (cols >= (1ll << 32) || rows >= (1ll << 31)) return fail(DG_ERR_UNSUPPORTED, "similarity matrix too large");
+    if (rows == 0) return DG_OK;
+    if (!vals || !out_idx) return fail(DG_ERR_INVALID, "null pointer");
+    DG_HIP(dg_launch_topk_rows(vals, rows, cols, row_stride, k, reinterpret_cast<long long*>(out_idx), out_val,
+                               static_cast<hipStream_t>(stream_)));
+    return DG_OK;
+}
+
+static int lhp_check(int32_t B, int32_t D, int32_t h, int32_t w) {
+    if (B < 1 || D < 1 || h < 1 || w < 1) return fail(DG_ERR_INVALID, "bad LHP dimensions");
+    if (D > 128) return fail(DG_ERR_UNSUPPORTED, "D=%d > 128 code channels not supported", D);
+    if ((size_t)h * w > 4096) return fail(DG_ERR_UNSUPPORTED, "feature map %dx%d too large for the LHP propagation (max 4096 positions)", h, w);
+    return DG_OK;
+}
+
+extern "C" int dg_lhp_forward(const float* code, const float* depth, int32_t B, int32_t D, int32_t h, int32_t w, int32_t depth_h,
+                              int32_t depth_w, float* out, float* points, float* stats, dg_stream_t stream_) {
+    if (int rc = lhp_check(B, D, h, w)) return rc;
+    if (depth_h < 1 || depth_w < 1) return fail(DG_ERR_INVALID, "bad depth size");
+    if (!code || !depth || !out || !points || !stats) return fail(DG_ERR_INVALID, "null pointer");
+    hipStream_t s = static_cast<hipStream_t>(stream_);
+    const uint32_t bits = 0x404f54cbu;            // 2*tan(90/2 rad), the reference's float32 factor (dg_fps_coords)
+    float factor;
+    memcpy(&factor, &bits, 4);
+    DG_HIP(dg_launch_lhp_points(depth, B, depth_h, depth_w, h, w, factor, points, s));
+    DG_HIP(dg_launch_lhp_propagate(false, code, points, stats, B, D, h * w, out, s));
+    return DG_OK;
+}
+
+extern "C" int dg_lhp_backward(const float* grad_out, const float* points, const float* stats, int32_t B, int32_t D, int32_t h,
+                               int32_t w, float* grad_code, dg_stream_t stream_) {
+    if (int rc = lhp_check(B, D, h, w)) return rc;
+    if (!grad_out || !points || !stats || !grad_code) return fail(DG_ERR_INVALID, "null pointer");
+    DG_HIP(dg_launch_lhp_propagate(true, grad_out, points, const_cast<float*>(stats), B, D, h * w, grad_code,
+                                   static_cast<hipStream_t>(stream_)));
+    return DG_OK;
+}
+
+extern "C" int dg_lhp_map_forward(int32_t mode, const float* code, const float* attn, const float* depth, const float* divide,
+                                  int32_t B, int32_t D, int32_t h, int32_t w, int32_t heads, int32_t depth_h, int32_t depth_w,
+                                  float* out, float* map, float* points, dg_stream_t stream_) {
+    if (int rc = lhp_check(B, D, h, w)) return rc;
+    if (mode < DG_LHP_ATTN || mode > DG_LHP_ORIG_ATTN) return fail(DG_ERR_INVALID, "unknown LHP map mode %d", mode);
+    if (!code || !out) return fail(DG_ERR_INVALID, "null pointer");
+    hipStream_t s = static_cast<hipStream_t>(stream_);
+    if (mode == DG_LHP_ORIG_DEPTH) {
+        if (!depth || !points || depth_h < 1 || depth_w < 1) return fail(DG_ERR_INVALID, "the depth map and the points scratch are required");
+        const uint32_t bits = 0x404f54cbu;        // 2*tan(90/2 rad), as in dg_lhp_forward
+        float factor;
+        memcpy(&factor, &bits, 4);
+        DG_HIP(dg_launch_lhp_points(depth, B, depth_h, depth_w, h, w, factor, points, s));
+    } else if (!attn || heads < 1) {
+        return fail(DG_ERR_INVALID, "the attention tensor (B,heads,h*w+1,h*w+1) is required");
+    }
+    if (!map) return fail(DG_ERR_INVALID, "the map buffer is required");
+    if (mode != DG_LHP_ATTN && !divide) return fail(DG_ERR_INVALID, "divide_num is required");
+    DG_HIP(dg_launch_lhp_map(mode, code, attn, points, divide, B, D, h, w, heads, out, map, s));
+    return DG_OK;
+}
+
+extern "C" int dg_lhp_map_backward(int32_t mode, const float* grad_out, const float* map, const float* divide, int32_t B, int32_t D,
+                                   int32_t h, int32_t w, float* grad_code, dg_stream_t stream_) {
+    if (int rc = lhp_check(B, D, h, w)) return rc;
+    if (mode < DG_LHP_ATTN || mode > DG_LHP_ORIG_ATTN) return fail(DG_ERR_INVALID, "unknown LHP map mode %d", mode);
+    if (!grad_out || !map || !grad_code || (mode != DG_LHP_ATTN && !divide)) return fail(DG_ERR_INVALID, "null pointer");
+    DG_HIP(dg_launch_lhp_map_bwd(mode, grad_out, map, divide, B, D, h, w, grad_code, static_cast<hipStream_t>(stream_)));
+    return DG_OK;
+}
+
+extern "C" size_t dg_fps_workspace_bytes(int32_t B, int32_t h, int32_t w) {
+    // the pooled depth maps of B images (adaptive_avg_pool2d to the feature map, written by a launch over the whole chip in front of
+    // the sampler); the sampler itself keeps its state in LDS
+    if (B < 1 || h < 1 || w < 1) return 256;
+    return (size_t)B * h * w * 4 + 256;
+}
+
+static int fps_entry(const float* depth, const float* depth_b, int32_t Ba, int32_t B, int32_t depth_h, int32_t depth_w, int32_t h,
+                     int32_t w, int32_t S, float* out_coords, int32_t* out_inds, void* workspace, size_t workspace_bytes, dg_stream_t stream_) {
+    if (!depth || !out_coords || (Ba < B && !depth_b)) return fail(DG_ERR_INVALID, "null pointer");
+    if (B < 1 || Ba < 1 || h < 1 || w < 1 || S < 1 || depth_h < h || depth_w < w) return fail(DG_ERR_INVALID, "bad FPS dimensions");
+    if (S * S > h * w) return fail(DG_ERR_INVALID, "cannot sample %d points from a %dx%d map", S * S, h, w);
+    if ((size_t)h * w > 4096) return fail(DG_ERR_UNSUPPORTED, "feature map %dx%d too large for the sampler (max 4096 pixels)", h, w);
+    // 2*tan(fov/2) with fov = 90 taken in radians (reference quirk, src/modules.py:989,1016), float32 bits
+    const uint32_t bits = 0x404f54cbu;
+    float factor;
+    memcpy(&factor, &bits, 4);
+    // (a workspace that is missing or too small is not an error: the sampler then pools inside its own blocks, one image per CU)
+    float* pooled = (workspace && workspace_bytes >= (size_t)B * h * w * 4) ? static_cast<float*>(workspace) : nullptr;
+    DG_HIP(dg_launch_fps(depth, depth_b, Ba, B, depth_h, depth_w, h, w, S, factor, out_coords, out_inds, pooled, static_cast<hipStream_t>(stream_)));
+    return DG_OK;
+}
+
+extern "C" int dg_fps_coords(const float* depth, int32_t B, int32_t depth_h, int32_t depth_w, int32_t h, int32_t w,
+                             int32_t S, float* out_coords, int32_t* out_inds, void* workspace, size_t workspace_bytes,
+                             dg_stream_t stream_) {
+    return fps_entry(depth, nullptr, B, B, depth_h, depth_w, h, w, S, out_coords, out_inds, workspace, workspace_bytes, stream_);
+}
+
+extern "C" int dg_fps_coords_pair(const float* depth, const float* depth_pos, int32_t B, int32_t depth_h, int32_t depth_w,
+                                  int32_t h, int32_t w, int32_t S, float* out_coords, int32_t* out_inds, void* workspace,
+                                  size_t workspace_bytes, dg_stream_t stream_) {
+    return fps_entry(depth, depth_pos, B, 2 * B, depth_h, depth_w, h, w, S, out_coords, out_inds, workspace, workspace_bytes, stream_);
+}
+
+// ---- the optimisation step's Adams (dg_optim.hip)
+extern "C" int dg_adam_step(const dg_adam_seg* segs, int32_t n_seg, const dg_adam_group* groups, int32_t n_groups, int32_t device_steps,
+                            void* tickets, dg_stream_t stream_) {
+    if (!segs || !groups) return fail(DG_ERR_INVALID, "dg_adam_step: null table");
+    if (n_seg < 1 || n_groups < 1) return fail(DG_ERR_INVALID, "dg_adam_step: n_seg=%d, n_groups=%d must be positive", n_seg, n_groups);
+    if (n_groups > DG_ADAM_MAX_GROUPS) return fail(DG_ERR_UNSUPPORTED, "dg_adam_step: %d groups (max %d per call)", n_groups, DG_ADAM_MAX_GROUPS);
+    for (int k = 0; k < n_groups; ++k) {
+        const dg_adam_group& g = groups[k];
+        if (!(g.lr >= 0.0) || !(g.beta1 >= 0.0 && g.beta1 < 1.0) || !(g.beta2 >= 0.0 && g.beta2 < 1.0) || !(g.eps >= 0.0))
+            return fail(DG_ERR_INVALID, "dg_adam_step: group %d: lr=%g betas=(%g, %g) eps=%g", k, g.lr, g.beta1, g.beta2, g.eps);
+    }
+    for (int k = 0; k < n_seg; ++k) {
+        const dg_adam_seg& s = segs[k];
+        if (!s.param || !s.exp_avg || !s.exp_avg_sq) return fail(DG_ERR_INVALID, "dg_adam_step: segment %d: null parameter / state pointer", k);
+        if (s.numel < 1 || s.numel > 0x7fffffffll) return fail(DG_ERR_INVALID, "dg_adam_step: segment %d: numel=%lld outside [1, 2^31)", k, (long long)s.numel);
+        if (s.group < 0 || s.group >= n_groups) return fail(DG_ERR_INVALID, "dg_adam_step: segment %d: group %d of %d", k, s.group, n_groups);
+        if (((uintptr_t)s.param | (uintptr_t)s.grad | (uintptr_t)s.exp_avg | (uintptr_t)s.exp_avg_sq) & 3)
+            return fail(DG_ERR_INVALID, "dg_adam_step: segment %d: a pointer is not 4-byte aligned", k);
+        if (device_steps) {
+            if (!s.step_dev || ((uintptr_t)s.step_dev & 3)) return fail(DG_ERR_INVALID, "dg_adam_step: segment %d: step_dev must be a device float", k);
+            if (s.numel > DG_ADAM_CHUNK && !tickets) return fail(DG_ERR_INVALID, "dg_adam_step: segment %d spans several blocks: tickets must be given", k);
+        } else if (!(s.step_host >= 1.0)) {
+            return fail(DG_ERR_INVALID, "dg_adam_step: segment %d: step_host=%g (the count after this step) must be >= 1", k, s.step_host);
+        }
+    }
+    for (int k0 = 0; k0 < n_seg; k0 += DG_ADAM_MAX_SEGS) {
+        const int c = n_seg - k0 < DG_ADAM_MAX_SEGS ? n_seg - k0 : DG_ADAM_MAX_SEGS;
+        DG_HIP(dg_launch_adam(segs + k0, c, groups, n_groups, device_steps != 0,
+                              tickets ? static_cast<unsigned int*>(tickets) + k0 : nullptr, static_cast<hipStream_t>(stream_)));
+    }
+    return DG_OK;
+}
+
+// ---- fused attention forward of the frozen ViT (dg_attn.hip)
+extern "C" size_t dg_attention_workspace_bytes(int32_t B, int32_t heads, int32_t N) {
+    if (B < 1 || heads < 1 || N < 1 || N > (1 << 24) || (long long)B * heads > 65535) return 0;
+    return up(dg_attn_workspace(B, heads, N), 256);
+}
+
+extern "C" int dg_attention_forward(const float* qkv, int32_t B, int32_t N, int32_t heads, int32_t head_dim, float scale, float* out,
+                                    void* workspace, size_t workspace_bytes, dg_stream_t stream_) {
+    if (head_dim != 64) return fail(DG_ERR_UNSUPPORTED, "dg_attention_forward: head_dim=%d (the kernel is built for 64)", head_dim);
+    if (B < 1 || heads < 1 || N < 1 || N > (1 << 24))
+        return fail(DG_ERR_INVALID, "dg_attention_forward: B=%d heads=%d N=%d", B, heads, N);
+    if ((long long)B * heads > 65535) return fail(DG_ERR_UNSUPPORTED, "dg_attention_forward: B * heads = %lld above 65535", (long long)B * heads);
+    if (!(scale == scale) || std::isinf(scale)) return fail(DG_ERR_INVALID, "dg_attention_forward: scale=%g", (double)scale);
+    if (!qkv || !out || !workspace) return fail(DG_ERR_INVALID, "dg_attention_forward: null pointer");
+    if (((uintptr_t)qkv | (uintptr_t)out | (uintptr_t)workspace) & 15)
+        return fail(DG_ERR_INVALID, "dg_attention_forward: qkv, out and workspace must be 16-byte aligned");
+    const size_t need = dg_attention_workspace_bytes(B, heads, N);
+    if (workspace_bytes < need)
+        return fail(DG_ERR_WORKSPACE, "workspace of %zu bytes, %zu needed (dg_attention_workspace_bytes)", workspace_bytes, need);
+    DG_HIP(dg_launch_attention(qkv, out, workspace, B, N, heads, scale, static_cast<hipStream_t>(stream_)));
+    return DG_OK;
+}
+
+// ---- fused bf16 linear layers of the frozen ViT (dg_linear.hip)
+extern "C" size_t dg_vit_linear_packed_bytes(int32_t K, int32_t Nout) { return dg_linear_packed_bytes(K, Nout); }
+
+extern "C" int dg_vit_linear_pack(const float* weight, int32_t K, int32_t Nout, void* packed, dg_stream_t stream_) {
+    if (!dg_linear_supported(K, Nout))
+        return fail(DG_ERR_UNSUPPORTED, "dg_vit_linear_pack: K=%d Nout=%d (multiples of 64 up to 3072)", K, Nout);
+    if (!weight || !packed) return fail(DG_ERR_INVALID, "dg_vit_linear_pack: null pointer");
+    if (((uintptr_t)weight | (uintptr_t)packed) & 15) return fail(DG_ERR_INVALID, "dg_vit_linear_pack: weight and packed must be 16-byte aligned");
+    DG_HIP(dg_launch_linear_pack(weight, K, Nout, packed, static_cast<hipStream_t>(stream_)));
+    return DG_OK;
+}
+
+extern "C" int dg_vit_linear_forward(const void* x, const float* gamma, const float* beta, float eps, const void* packed, const float* bias,
+                                     const float* residual, void* out, int32_t M, int32_t K, int32_t Nout, int32_t flags,
+                                     dg_stream_t stream_) {
+    if (!dg_linear_supported(K, Nout))
+        return fail(DG_ERR_UNSUPPORTED, "dg_vit_linear_forward: K=%d Nout=%d (multiples of 64 up to 3072)", K, Nout);
+    if (flags & ~(DG_LIN_LAYERNORM | DG_LIN_GELU | DG_LIN_IN_BF16 | DG_LIN_OUT_BF16))
+        return fail(DG_ERR_INVALID, "dg_vit_linear_forward: unknown flags 0x%x", flags);
+    if (M < 1 || M > (1 << 24)) return fail(DG_ERR_INVALID, "dg_vit_linear_forward: M=%d", M);
+    if (!x || !packed || !out) return fail(DG_ERR_INVALID, "dg_vit_linear_forward: null pointer");
+    if (flags & DG_LIN_LAYERNORM) {
+        if (K > 768) return fail(DG_ERR_UNSUPPORTED, "dg_vit_linear_forward: LayerNorm prologue with K=%d (up to 768)", K);
+        if (flags & DG_LIN_IN_BF16) return fail(DG_ERR_INVALID, "dg_vit_linear_forward: the LayerNorm prologue reads fp32 rows");
+        if (!gamma || !beta) return fail(DG_ERR_INVALID, "dg_vit_linear_forward: the LayerNorm prologue needs gamma and beta");
+        if (!(eps >= 0.f) || std::isinf(eps)) return fail(DG_ERR_INVALID, "dg_vit_linear_forward: eps=%g", (double)eps);
+    } else {
+        gamma = beta = nullptr;
+    }
+    if (residual && (flags & DG_LIN_OUT_BF16)) return fail(DG_ERR_INVALID, "dg_vit_linear_forward: the residual stream is fp32, not a bf16 output");
+    if (x == out) return fail(DG_ERR_INVALID, "dg_vit_linear_forward: out may alias residual, not x");
+    if (((uintptr_t)x | (uintptr_t)gamma | (uintptr_t)beta | (uintptr_t)packed | (uintptr_t)bias | (uintptr_t)residual | (uintptr_t)out) & 15)
+        return fail(DG_ERR_INVALID, "dg_vit_linear_forward: every pointer must be 16-byte aligned");
+    DG_HIP(dg_launch_linear(x, gamma, beta, eps, packed, bias, residual, out, M, K, Nout, flags, static_cast<hipStream_t>(stream_)));
+    return DG_OK;
+}

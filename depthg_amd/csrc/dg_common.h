@@ -14,8 +14,8 @@ typedef __attribute__((ext_vector_type(4))) _Float16 f16x4;
 
 // Switches of the library - the complete list (tests/test_host_cpu.py fails on a getenv or a tested macro not named here).
 // Test seams, read in every build; each selects a second route that must give the same bits (tests/test_gpu_configs.py):
-//   DG_FOLD_INTRA=0   the intra pair-set's streamed-side gradient by k_gs instead of k_corr2's fold (dg_api.hip make_plan)
-//   DG_SPLIT_MASKS=0  the dense grid's exact-mask chain in sequence on the caller's stream, no side stream (dg_api.hip)
+//   DG_FOLD_INTRA=0   the intra pair-set's streamed-side gradient by k_gs instead of k_corr2's fold (dg_api_corr.hip make_plan)
+//   DG_SPLIT_MASKS=0  the dense grid's exact-mask chain in sequence on the caller's stream, no side stream (dg_api_corr.hip)
 //   DG_C2_WALK=dynamic|static   the walk of k_corr2's persistent workgroups (dg_corr2.hip)
 // Measurement instruments, compiled only into a `make EXTRA=-DDG_DEVTOOLS` build (results unchanged, timing perturbed):
 //   DG_STAMPS=<file>, DG_BLOCKLOG=<file>   phase stamps / per-block timeline of the fused kernel (with -DDG_STAMP_BUILD for
@@ -524,7 +524,7 @@ struct DgDenseArgs {        // identity-grid operand preparation (k_prep_dense)
     float fscale;
     int32_t unit;            // DG_FEATS_UNIT: the feature rows are written as they are (unit vectors, or a channel chunk of them)
     int32_t roles;           // 0: every role; else a mask of the roles THIS launch runs - 1 feats, 2 code, 4 depth indicators, 8 the draw
-                             // (the launch split in two that run on two streams: dg_api.hip, exact clamp masks on the dense grid)
+                             // (the launch split in two that run on two streams: dg_api_corr.hip, exact clamp masks on the dense grid)
 };
 
 // Code operands of the identity grid from whole channel planes (extra blocks of the k_colmean launch, after the norms of
@@ -592,7 +592,7 @@ struct DgColmeanArgs {      // bbar[o][n][k] = (1/P) sum_groups colpart[o][n][gr
     DgGroupArgs gr;                    // gr.nkeys > 0: blockIdx.z == 2 writes the consumer lists of k_corr2's grouped ragged blocks
     DgDenseCodeArgs dc;                // dc.B > 0: blockIdx.z == 3 builds the dense code operands (and blockIdx.z == 1 is the k_rowmean launch's)
     int32_t zsel;                      // 0: every role; 1: only the dense code operands (blockIdx.z == 3); 2: every role but them - the launch
-                                       //    split in two that run on two streams (dg_api.hip, exact clamp masks on the dense grid)
+                                       //    split in two that run on two streams (dg_api_corr.hip, exact clamp masks on the dense grid)
 };
 
 struct DgRowmeanJob {
@@ -865,10 +865,25 @@ struct DgHeadWeightLayout {
         elems = w2bT + (size_t)C * ((D + 31) / 32 * 32);
     }
 };
-hipError_t dg_launch_head_dh(const DgHeadDhArgs& a, hipStream_t s);
-int dg_head_dh_fused_blocks(int B, int C, int D, int P);      // > 0: k_head_dh2 runs this shape with that many blocks and can form d W2b on the way
-hipError_t dg_launch_head_wgrad(const DgHeadWgradArgs& a, bool a_bf16, bool b_bf16, hipStream_t s);
-bool dg_head_wgrad_one_pass(int M, int N, int M2, int P);      // the two products over the features as k_head_wgrad3 (one block = all rows x 128 channels)
+// The backward's plan: the workspace carved for a shape AND the kernels that will run on it, decided once, next to the kernels
+// (dg_head.hip dg_head_plan).  The launchers below take the route from it; one they cannot run is hipErrorInvalidValue.
+enum DgHeadDhRoute { DG_HEAD_DH_TILES,           // k_head_dh, one block per 64-position tile; d W2b is a weight-gradient launch of its own
+                     DG_HEAD_DH_FUSED };         // k_head_dh2 on dh_blocks resident blocks; d W2b rides in it (DgHeadDhArgs.part_w2b)
+enum DgHeadWgradForm { DG_HEAD_WGRAD_DIRECT,     // k_head_wgrad, one product per launch
+                       DG_HEAD_WGRAD_GROUPED,    // k_head_wgrad2 (P and the splits multiples of 8)
+                       DG_HEAD_WGRAD_ONE_PASS }; // k_head_wgrad3: d W2a and d W1 in one pass over the features, d code as DgHeadWgradArgs.A2h
+struct DgHeadPlan {
+    size_t dh, p2a, p1, p2b, pbd, pb2a, gbf, total;      // workspace offsets (gbf: only with DG_HEAD_WGRAD_ONE_PASS), its size
+    int s2a, s1, s2b, tiles, dh_blocks;                  // splits of the d W2a + d W1 launch, of d W1 alone, of d W2b; tiles per image
+    DgHeadDhRoute dh_route;
+    DgHeadWgradForm wgrad_pair, wgrad_single;            // d W2a + d W1 in one call (s2a splits); a product alone (s1 splits: d W1 of the linear head, d W2b)
+    bool step_major;                                     // d hidden (and A2h) as DgHeadDhArgs.step_major: k_head_dh2 writes what k_head_wgrad3 reads
+};
+DgHeadPlan dg_head_plan(int B, int C, int D, int P);
+hipError_t dg_launch_head_dh(const DgHeadDhArgs& a, const DgHeadPlan& plan, hipStream_t s);
+// a_bf16 / b_bf16: element types of A and Bm - the three pairings the backward uses: fp32 x fp32, fp32 x bf16, and bf16 x fp32 with the
+// second product (a.M2 > 0)
+hipError_t dg_launch_head_wgrad(const DgHeadWgradArgs& a, DgHeadWgradForm form, bool a_bf16, bool b_bf16, hipStream_t s);
 struct DgHeadReduceJob { const float* part; float* out; float* out2; int32_t n, splits; float scale; };
 struct DgHeadReduceArgs { DgHeadReduceJob jobs[6]; int32_t njobs; };
 hipError_t dg_launch_head_reduce(const DgHeadReduceArgs& a, hipStream_t s);

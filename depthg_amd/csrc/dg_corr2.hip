@@ -226,7 +226,7 @@ __device__ __forceinline__ float wave_sum_dpp(float v) {
 // goes into the chain's start value; the streamed position's half rides in the chain as ONE more MFMA: the S tile's unused code
 // k-step NKC (channels 16 NKC .. of the zero padding, KD > 16 NKC) carries -r_q / 2 as an fp16 pair (hi, 2048 lo) in k = 0, 1
 // (k_rowmean writes it), the B fragment is the constant (1, 2^-11, 0 ...).  The loss sums come out of the gradient tiles
-// (sum <x_p, dR_p>) and stay right: sum m cd (r_q - r_p) = 0 by symmetry.  The host doubles the tile's weight (dg_api.hip).
+// (sum <x_p, dR_p>) and stay right: sum m cd (r_q - r_p) = 0 by symmetry.  The host doubles the tile's weight (dg_api_corr.hip).
 template <int NKF, int NKD, int NKC, bool XM = false, bool DYN = false, bool FOLD = false>      // DYN: the dynamic walk (many items per workgroup), below
 __global__ __launch_bounds__(256) void k_corr2(const DgCorrArgs args_k) {
     using BL = BlobT<NKF, NKD>;
@@ -1041,7 +1041,7 @@ static bool dg_corr2_dynamic_walk(const DgCorrArgs& args, int grid) {
 
 // Helper jobs (stationary = operand 1) of a gradient pass with clamp(cd) = cd * mask.  Returns hipErrorNotSupported for
 // shapes this form does not cover (the caller then uses k_corr_main).
-// The shapes and clamp recipe this form covers - ONE predicate for the launcher below and for the host's plan (dg_api.hip decides
+// The shapes and clamp recipe this form covers - ONE predicate for the launcher below and for the host's plan (dg_api_corr.hip decides
 // from it whether the intra pair-set may be folded: a second copy of these conditions there could drift from this one and turn a
 // fall-back to k_corr_main into a failed call)
 bool dg_corr2_shape_supported(int KF, int KD, int D, float lo, float hi, int Ppad, int B) {

@@ -835,17 +835,22 @@ __global__ __launch_bounds__(512) void k_head_dh2(const DgHeadDhArgs a) {
     }
 }
 
-int dg_head_dh_fused_blocks(int B, int C, int D, int P) {
+// > 0: k_head_dh2 runs this shape with that many blocks and forms d W2b on the way (dg_head_plan asks)
+static int dg_head_dh_fused_blocks(int B, int C, int D, int P) {
     if (!(C > 192 && C <= 384 && D <= 96 && (P & 7) == 0)) return 0;
     const int ntiles = B * ((P + 63) / 64);
     return ntiles < 256 ? ntiles : 256;
 }
-hipError_t dg_launch_head_dh(const DgHeadDhArgs& a, hipStream_t s) {
+hipError_t dg_launch_head_dh(const DgHeadDhArgs& a, const DgHeadPlan& plan, hipStream_t s) {
     dim3 grid((a.P + 63) / 64, a.B);
     DgHeadDhArgs a2 = a;
-    if (const int nblk = dg_head_dh_fused_blocks(a.B, a.C, a.D, a.P)) {
+    // (d W2b is formed by k_head_dh2 and always there; the step-major d hidden is its alone too)
+    if ((plan.dh_route == DG_HEAD_DH_FUSED) != (a.part_w2b != nullptr) || (a.step_major && plan.dh_route != DG_HEAD_DH_FUSED))
+        return hipErrorInvalidValue;
+    if (plan.dh_route == DG_HEAD_DH_FUSED) {
+        const int nblk = plan.dh_blocks;
         const int smem = 2 * DH2_HT + 2 * DH2_DT;
-        auto kern = !a.part_w2b ? k_head_dh2<0> : (a.D <= 80 ? k_head_dh2<5> : k_head_dh2<6>);
+        auto kern = a.D <= 80 ? k_head_dh2<5> : k_head_dh2<6>;
         hipError_t e = dg_set_max_smem(reinterpret_cast<const void*>(kern), smem);
         if (e != hipSuccess) return e;
 #ifdef DG_DEVTOOLS
@@ -865,7 +870,6 @@ hipError_t dg_launch_head_dh(const DgHeadDhArgs& a, hipStream_t s) {
         hipLaunchKernelGGL(kern, dim3(nblk), dim3(512), smem, s, a2);
         return hipGetLastError();
     }
-    if (a.part_w2b) return hipErrorInvalidValue;           // (only k_head_dh2 forms d W2b: the plan asks dg_head_dh_fused_blocks first)
 #ifdef DG_DEVTOOLS
     static unsigned long long* sbuf = nullptr;
     const char* sfile = getenv("DG_DH_STAMPS");
@@ -1289,29 +1293,67 @@ __global__ __launch_bounds__(512) void k_head_wgrad3(const DgHeadWgradArgs a) {
             }
         }
 }
-// (what the plan asks before it sizes the partial sums: dg_api.hip head_splits)
-bool dg_head_wgrad_one_pass(int M, int N, int M2, int P) {
+// the two products over the features as k_head_wgrad3 (one block = all rows x 128 channels): what the plan asks before it sizes the partial sums
+static bool dg_head_wgrad_one_pass(int M, int N, int M2, int P) {
     return M > 256 && M <= 384 && M2 > 0 && M2 <= 128 && (P & 7) == 0;
 }
 
-template <typename TA, typename TB, typename TA2 = TA>
-static hipError_t launch_wgrad(const DgHeadWgradArgs& a, hipStream_t s) {
-    if constexpr (std::is_same<TA, __bf16>::value && std::is_same<TB, float>::value && std::is_same<TA2, float>::value) {
-        if (a.A2h && dg_head_wgrad_one_pass(a.M, a.N, a.M2, a.P) && (a.splits & 7) == 0) {
-            const int smem = W3_NSTAGE * W3_STAGE;
-            hipError_t e = dg_set_max_smem(reinterpret_cast<const void*>(k_head_wgrad3), smem);
-            if (e != hipSuccess) return e;
-            hipLaunchKernelGGL(k_head_wgrad3, dim3(((a.N + 127) / 128) * a.splits), dim3(512), smem, s, a);
-            return hipGetLastError();
-        }
+// ---- the backward's plan (DgHeadPlan, dg_common.h): splits, workspace and the route of every launch, for the launchers and dg_api_head.hip
+static int head_splits(int32_t B, int32_t M, int32_t N, int32_t P, int32_t M2 = 0) {     // (M2: a second product in the same launch)
+    const int steps = B * ((P + 31) / 32);
+    if (dg_head_wgrad_one_pass(M, N, M2, P) && steps >= 8) {
+        // k_head_wgrad3: one block per CU and one round - the largest multiple of 8 splits whose blocks (channel tiles x splits) fit 256 CUs
+        const int s = (256 / ((N + 127) / 128)) & ~7;
+        return s > steps ? (steps & ~7) : s;              // (a multiple of 8 either way: what the one-pass form needs)
     }
-    const int tiles = ((a.N + 127) / 128) * ((a.M + 127) / 128 + (a.M2 + 127) / 128);
-    if ((a.P & 7) == 0 && (a.splits & 7) == 0) {
+    const int tiles = ((M + 127) / 128 + (M2 + 127) / 128) * ((N + 127) / 128);
+#ifndef HEAD_SPLIT_TARGET
+    // about two blocks per CU; three when both featurizer passes of a step share the launch (1600 position steps at the headline:
+    // 512 / 640 / 768 / 896 blocks gave 136 / 132 / 128 / 133 us for the two weight-gradient launches and their reduction)
+    const int HEAD_SPLIT_TARGET = steps >= 1200 ? 768 : 512;
+#endif
+    int s = (HEAD_SPLIT_TARGET + tiles - 1) / tiles;
+    s = (s + 7) & ~7;                                       // a multiple of 8: k_head_wgrad2 keeps the tiles of a split on one XCD
+    return s > steps ? steps : s;
+}
+DgHeadPlan dg_head_plan(int B, int C, int D, int P) {
+    DgHeadPlan h;
+    size_t off = 0;
+    auto take = [&](size_t bytes) { size_t o = off; off += (bytes + 255) / 256 * 256; return o; };
+    // (odd position counts, or fewer steps than eight splits: the direct form, one product per launch)
+    auto form = [&](int splits) { return ((P & 7) == 0 && (splits & 7) == 0) ? DG_HEAD_WGRAD_GROUPED : DG_HEAD_WGRAD_DIRECT; };
+    // cluster2: d W2a and d W1 share the feature operand and one launch (same splits); cluster1 alone (linear head): d W1 by itself
+    h.s2a = head_splits(B, C, C, P, D); h.s1 = head_splits(B, D, C, P); h.s2b = h.s1;
+    // k_head_dh2 (the headline widths) forms d W2b beside d hidden: one partial sum per block of its launch
+    h.dh_blocks = dg_head_dh_fused_blocks(B, C, D, P);
+    h.dh_route = h.dh_blocks > 0 ? DG_HEAD_DH_FUSED : DG_HEAD_DH_TILES;
+    if (h.dh_blocks > 0) h.s2b = h.dh_blocks;
+    h.tiles = (P + 63) / 64;
+    h.dh = take((size_t)B * C * ((P + 31) / 32 * 32) * 2);      // (+ the padding of the last step: the step-major form of k_head_dh2 / k_head_wgrad3)
+    h.p2a = take((size_t)h.s2a * C * C * 4);
+    h.p1 = take((size_t)(h.s1 > h.s2a ? h.s1 : h.s2a) * D * C * 4);
+    h.p2b = take((size_t)h.s2b * D * C * 4);
+    h.pbd = take((size_t)B * h.tiles * D * 4);
+    h.pb2a = take((size_t)B * h.tiles * C * 4);
+    // k_head_wgrad3 (d W2a and d W1 in one pass over the features) reads d code as the bf16 copy k_head_dh leaves
+    const bool one_pass = dg_head_wgrad_one_pass(C, C, D, P) && (h.s2a & 7) == 0;
+    h.wgrad_pair = one_pass ? DG_HEAD_WGRAD_ONE_PASS : form(h.s2a);
+    h.wgrad_single = form(h.s1);
+    h.step_major = one_pass && h.dh_route == DG_HEAD_DH_FUSED;      // (both ends: k_head_dh2 writes what k_head_wgrad3 reads)
+    h.gbf = one_pass ? take((size_t)B * D * ((P + 31) / 32 * 32) * 2) : 0;
+    h.total = off;
+    return h;
+}
+
+template <typename TA, typename TB, typename TA2 = TA>
+static hipError_t launch_wgrad(const DgHeadWgradArgs& a, DgHeadWgradForm form, hipStream_t s) {
+    if (form == DG_HEAD_WGRAD_GROUPED) {
+        const int tiles = ((a.N + 127) / 128) * ((a.M + 127) / 128 + (a.M2 + 127) / 128);
         const int smem = 4 * 128 * (32 * 2 + 16);
         hipLaunchKernelGGL((k_head_wgrad2<TA, TB, TA2>), dim3(tiles * a.splits), dim3(256), smem, s, a);
         return hipGetLastError();
     }
-    // (odd position counts, or fewer steps than eight splits: the direct form, one product per launch)
+    if (form != DG_HEAD_WGRAD_DIRECT) return hipErrorInvalidValue;
     dim3 grid((a.N + 127) / 128, (a.M + 127) / 128, a.splits);
     hipLaunchKernelGGL((k_head_wgrad<TA, TB>), grid, dim3(256), 0, s, a);
     if (a.M2 > 0) {
@@ -1321,16 +1363,23 @@ static hipError_t launch_wgrad(const DgHeadWgradArgs& a, hipStream_t s) {
     }
     return hipGetLastError();
 }
-// a_bf16 / b_bf16: element types of A and Bm; a second product (A2: fp32) rides in the same launch when a.M2 > 0
-hipError_t dg_launch_head_wgrad(const DgHeadWgradArgs& a, bool a_bf16, bool b_bf16, hipStream_t s) {
+// a_bf16 / b_bf16: element types of A and Bm; a second product (A2: fp32) rides in the same launch when a.M2 > 0 (A: bf16 then).
+// The form is the plan's (dg_head_plan); only k_head_wgrad3 reads the step-major operands.
+hipError_t dg_launch_head_wgrad(const DgHeadWgradArgs& a, DgHeadWgradForm form, bool a_bf16, bool b_bf16, hipStream_t s) {
+    if (a.a_step_major && form != DG_HEAD_WGRAD_ONE_PASS) return hipErrorInvalidValue;
     if (a.M2 > 0) {
-        if (a_bf16 && !b_bf16) return launch_wgrad<__bf16, float, float>(a, s);
-        return hipErrorInvalidValue;
+        if (!a_bf16 || b_bf16) return hipErrorInvalidValue;
+        if (form != DG_HEAD_WGRAD_ONE_PASS) return launch_wgrad<__bf16, float, float>(a, form, s);
+        if (!a.A2h) return hipErrorInvalidValue;
+        const int smem = W3_NSTAGE * W3_STAGE;
+        hipError_t e = dg_set_max_smem(reinterpret_cast<const void*>(k_head_wgrad3), smem);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(k_head_wgrad3, dim3(((a.N + 127) / 128) * a.splits), dim3(512), smem, s, a);
+        return hipGetLastError();
     }
-    if (a_bf16 && !b_bf16) return launch_wgrad<__bf16, float>(a, s);
-    if (!a_bf16 && !b_bf16) return launch_wgrad<float, float>(a, s);
-    if (!a_bf16 && b_bf16) return launch_wgrad<float, __bf16>(a, s);
-    return launch_wgrad<__bf16, __bf16>(a, s);
+    if (!a_bf16 && !b_bf16) return launch_wgrad<float, float>(a, form, s);
+    if (!a_bf16 && b_bf16) return launch_wgrad<float, __bf16>(a, form, s);
+    return hipErrorInvalidValue;        // (bf16 A without the second product, bf16 x bf16: nothing in the backward multiplies those)
 }
 
 // Up to six reductions in one launch: out[i] (and out2[i]) = scale * sum over splits of part[split][i], in a fixed order.

@@ -1149,7 +1149,7 @@ hipError_t dg_launch_fps(const float* depth, const float* depth_b, int Ba, int B
     };
     if (h * w <= 2 * FPS_THREADS) return launch(k_fps_coords<2>);
     if (h * w <= 4 * FPS_THREADS) return launch(k_fps_coords<4>);
-    if (h * w <= 8 * FPS_THREADS) return launch(k_fps_coords<8>);        // (4096 pixels: the sampler's limit, dg_api.hip fps_entry)
+    if (h * w <= 8 * FPS_THREADS) return launch(k_fps_coords<8>);        // (4096 pixels: the sampler's limit, dg_api_aux.hip fps_entry)
     return hipErrorInvalidValue;
 }
 
