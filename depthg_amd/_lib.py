@@ -13,20 +13,6 @@ DG_POINTWISE, DG_ZERO_CLAMP, DG_STABALIZE, DG_DEPTH_TERM, DG_NEED_GRAD, DG_SHARE
     DG_EXACT_MASKS, DG_FEATS_UNIT = (1 << i for i in range(10))
 DG_LIN_LAYERNORM, DG_LIN_GELU, DG_LIN_IN_BF16, DG_LIN_OUT_BF16 = 1, 2, 4, 8      # dg_vit_linear_forward flags
 
-EXPORTS = ["dg_version", "dg_last_error", "dg_corr_workspace_bytes", "dg_corr_forward", "dg_corr_backward",
-           "dg_corr_materialize", "dg_corr_relaunch_main", "dg_fps_workspace_bytes", "dg_fps_coords", "dg_fps_coords_pair", "dg_rand_coords_state", "dg_rand_keep_state", "dg_super_perms",
-           "dg_salience_coords", "dg_simple_depth_coords", "dg_confusion_update", "dg_topk_rows", "dg_lhp_forward", "dg_lhp_backward", "dg_super_perms_seeded", "dg_super_perms_state",
-           "dg_lhp_map_forward", "dg_lhp_map_backward", "dg_corr_forward_draw", "dg_corr_forward_masked",
-           "dg_corr_backward_total", "dg_corr_main_kernel_name", "dg_corr_intra_folded",
-           "dg_head_forward", "dg_head_workspace_bytes", "dg_head_weights_bytes", "dg_head_backward", "dg_head_forward_pair",
-           "dg_head_backward_pair", "dg_cluster_lookup_forward",
-           "dg_cluster_lookup_backward", "dg_probe_ce_forward", "dg_probe_ce_backward", "dg_knn_similarities",
-           "dg_prof_main_span", "dg_corr_materialize_shared", "dg_normalize_split", "dg_sampled_sumsq",
-           "dg_corr_forward_extnorm", "dg_segment_predict", "dg_crf_workspace_bytes", "dg_crf_unary",
-           "dg_segment_unary", "dg_crf_filter", "dg_dense_crf", "dg_adam_step", "dg_attention_workspace_bytes", "dg_attention_forward",
-           "dg_vit_linear_packed_bytes", "dg_vit_linear_pack", "dg_vit_linear_forward"]
-
-
 class CorrDesc(ctypes.Structure):
     """struct dg_corr_desc"""
     _fields_ = [("B", ctypes.c_int32), ("C", ctypes.c_int32), ("D", ctypes.c_int32), ("h", ctypes.c_int32),
@@ -50,6 +36,81 @@ class AdamGroup(ctypes.Structure):
     _fields_ = [("lr", ctypes.c_double), ("beta1", ctypes.c_double), ("beta2", ctypes.c_double), ("eps", ctypes.c_double)]
 
 
+_I, _SZ, _STR = ctypes.c_int, ctypes.c_size_t, ctypes.c_char_p
+vp, cp, i32, i64, u64, f32 = ctypes.c_void_p, ctypes.POINTER(CorrDesc), ctypes.c_int32, ctypes.c_int64, ctypes.c_uint64, ctypes.c_float
+
+# name -> (restype, argtypes): every prototype of include/depthg_corr.h, in the header's order (tests/test_host_cpu.py holds the two
+# against each other, parameter by parameter).  vp: any pointer and dg_stream_t; the last vp of most entries is the stream.
+SIGNATURES = {
+    "dg_version": (_I, []),
+    "dg_last_error": (_STR, []),
+    # correlation loss
+    "dg_corr_workspace_bytes": (_SZ, [cp]),
+    "dg_corr_forward": (_I, [cp] + [vp] * 9 + [vp, _SZ, vp]),
+    "dg_corr_forward_draw": (_I, [cp] + [vp] * 8 + [u64, vp, vp, vp, _SZ, vp]),
+    "dg_corr_forward_masked": (_I, [cp] + [vp] * 8 + [i32, u64, vp, vp, vp, f32, vp, vp, _SZ, vp]),
+    "dg_corr_backward": (_I, [cp] + [vp] * 6 + [vp, _SZ, vp]),
+    "dg_corr_backward_total": (_I, [cp] + [vp] * 6 + [vp, _SZ, vp]),
+    "dg_corr_materialize": (_I, [cp, i32, vp, vp, vp, _SZ, vp]),
+    "dg_corr_materialize_shared": (_I, [cp, i32, vp, vp, vp, vp, _SZ, vp]),
+    # samplers
+    "dg_fps_workspace_bytes": (_SZ, [i32] * 3),
+    "dg_fps_coords": (_I, [vp] + [i32] * 6 + [vp, vp, vp, _SZ, vp]),
+    "dg_fps_coords_pair": (_I, [vp, vp] + [i32] * 6 + [vp, vp, vp, _SZ, vp]),
+    "dg_salience_coords": (_I, [vp] + [i32] * 4 + [vp] * 4),
+    "dg_simple_depth_coords": (_I, [vp] + [i32] * 6 + [vp] * 4),
+    # metrics, LHP, nearest neighbours
+    "dg_confusion_update": (_I, [vp, vp, i64, i32, i32, vp, vp]),
+    "dg_lhp_forward": (_I, [vp, vp] + [i32] * 6 + [vp] * 4),
+    "dg_lhp_backward": (_I, [vp] * 3 + [i32] * 4 + [vp, vp]),
+    "dg_lhp_map_forward": (_I, [i32] + [vp] * 4 + [i32] * 7 + [vp] * 4),
+    "dg_lhp_map_backward": (_I, [i32] + [vp] * 3 + [i32] * 4 + [vp, vp]),
+    "dg_knn_similarities": (_I, [vp, vp, i64, i64, i32, i64, i64, vp, i64, vp]),
+    "dg_topk_rows": (_I, [vp, i64, i64, i64, i32, vp, vp, vp]),
+    # random draws
+    "dg_super_perms": (_I, [vp, i32, i32, vp, vp]),
+    "dg_super_perms_seeded": (_I, [u64, i32, i32, vp, vp]),
+    "dg_super_perms_state": (_I, [vp, i32, i32, vp, vp]),
+    "dg_rand_coords_state": (_I, [vp, i64, vp, vp]),
+    "dg_rand_keep_state": (_I, [vp, i64, f32, vp, vp]),
+    # wide feature maps
+    "dg_normalize_split": (_I, [i32] * 4 + [vp, i32, i32, ctypes.POINTER(vp), vp]),
+    "dg_sampled_sumsq": (_I, [i32] * 6 + [vp, vp, vp, i32, vp, vp]),
+    "dg_corr_forward_extnorm": (_I, [cp] + [vp] * 10 + [vp, _SZ, vp]),
+    # head and probes
+    "dg_head_weights_bytes": (_SZ, [i32] * 2),
+    "dg_head_forward": (_I, [i32] * 4 + [vp] * 10 + [f32] + [vp] * 5),
+    "dg_head_workspace_bytes": (_SZ, [i32] * 4),
+    "dg_head_backward": (_I, [i32] * 4 + [vp] * 3 + [f32] + [vp] * 10 + [_SZ, vp]),
+    "dg_head_forward_pair": (_I, [i32] * 4 + [vp] * 11 + [f32] + [vp] * 7),
+    "dg_head_backward_pair": (_I, [i32] * 4 + [vp] * 4 + [f32] + [vp] * 11 + [_SZ, vp]),
+    "dg_cluster_lookup_forward": (_I, [vp, vp, f32] + [i32] * 4 + [vp] * 6),
+    "dg_cluster_lookup_backward": (_I, [vp, vp, vp, f32, vp] + [i32] * 4 + [vp] * 4),
+    "dg_probe_ce_forward": (_I, [vp, vp] + [i32] * 6 + [vp] * 3),
+    "dg_probe_ce_backward": (_I, [vp] * 4 + [i32] * 6 + [vp] * 2),
+    # evaluation and dense CRF
+    "dg_segment_predict": (_I, [vp, vp] + [i32] * 4 + [vp, vp, i32, vp, i32, vp, i32, i32, vp, vp, i32, vp, vp, vp, _SZ, vp]),
+    "dg_crf_workspace_bytes": (_SZ, [i32] * 5),
+    "dg_crf_unary": (_I, [vp] + [i32] * 6 + [vp, i32, vp, vp]),
+    "dg_segment_unary": (_I, [vp, vp] + [i32] * 4 + [vp, vp, i32, vp, i32, i32, i32, f32, vp, vp, _SZ, vp]),
+    "dg_crf_filter": (_I, [vp, vp] + [i32] * 5 + [f32, f32, vp, vp, _SZ, vp]),
+    "dg_dense_crf": (_I, [vp, vp] + [i32] * 3 + [vp, i32, i32] + [f32] * 5 + [vp, vp, vp, _SZ, vp]),
+    # optimiser
+    "dg_adam_step": (_I, [ctypes.POINTER(AdamSeg), i32, ctypes.POINTER(AdamGroup), i32, i32, vp, vp]),
+    # frozen ViT
+    "dg_attention_workspace_bytes": (_SZ, [i32] * 3),
+    "dg_attention_forward": (_I, [vp] + [i32] * 4 + [f32, vp, vp, _SZ, vp]),
+    "dg_vit_linear_packed_bytes": (_SZ, [i32] * 2),
+    "dg_vit_linear_pack": (_I, [vp, i32, i32, vp, vp]),
+    "dg_vit_linear_forward": (_I, [vp, vp, vp, f32, vp, vp, vp, vp] + [i32] * 4 + [vp]),
+    # measurement aids
+    "dg_corr_main_kernel_name": (_STR, [cp]),
+    "dg_corr_intra_folded": (_I, [cp]),
+    "dg_prof_main_span": (_I, [vp]),
+    "dg_corr_relaunch_main": (_I, [cp, vp, vp, _SZ, vp]),
+}
+EXPORTS = list(SIGNATURES)
+
 _lib = None
 
 
@@ -62,122 +123,13 @@ def load():
             f"depthg_amd: {LIB_PATH} not found. Build it with `make -C depthg_amd/csrc` "
             "(or `python -c 'import __graft_entry__ as g; g.build()'`). There is no fallback path.")
     lib = ctypes.CDLL(LIB_PATH)
-    vp, cp = ctypes.c_void_p, ctypes.POINTER(CorrDesc)
-    i32, f32 = ctypes.c_int32, ctypes.c_float
-    lib.dg_version.restype = ctypes.c_int
+    lib.dg_version.restype = _I
     if lib.dg_version() != DG_VERSION:
         raise RuntimeError(f"depthg_amd: {LIB_PATH} is version {lib.dg_version()}, the Python layer expects {DG_VERSION}; "
                            "rebuild it with `make -C depthg_amd/csrc`")
-    lib.dg_last_error.restype = ctypes.c_char_p
-    lib.dg_corr_workspace_bytes.restype = ctypes.c_size_t
-    lib.dg_corr_workspace_bytes.argtypes = [cp]
-    lib.dg_corr_forward.restype = ctypes.c_int
-    lib.dg_corr_forward.argtypes = [cp] + [vp] * 10 + [ctypes.c_size_t, vp]
-    lib.dg_corr_forward_draw.restype = ctypes.c_int
-    lib.dg_corr_forward_draw.argtypes = [cp] + [vp] * 8 + [ctypes.c_uint64, vp, vp, vp, ctypes.c_size_t, vp]
-    lib.dg_corr_forward_masked.restype = ctypes.c_int
-    lib.dg_corr_forward_masked.argtypes = [cp] + [vp] * 8 + [i32, ctypes.c_uint64, vp, vp, vp, f32, vp, vp, ctypes.c_size_t, vp]
-    lib.dg_head_forward.restype = ctypes.c_int
-    lib.dg_head_forward.argtypes = [i32] * 4 + [vp] * 10 + [f32] + [vp] * 5
-    lib.dg_head_weights_bytes.restype = ctypes.c_size_t
-    lib.dg_head_weights_bytes.argtypes = [i32] * 2
-    lib.dg_head_workspace_bytes.restype = ctypes.c_size_t
-    lib.dg_head_workspace_bytes.argtypes = [i32] * 4
-    lib.dg_head_backward.restype = ctypes.c_int
-    lib.dg_head_backward.argtypes = [i32] * 4 + [vp] * 3 + [f32] + [vp] * 10 + [ctypes.c_size_t, vp]
-    lib.dg_head_forward_pair.restype = ctypes.c_int
-    lib.dg_head_forward_pair.argtypes = [i32] * 4 + [vp] * 11 + [f32] + [vp] * 7
-    lib.dg_head_backward_pair.restype = ctypes.c_int
-    lib.dg_head_backward_pair.argtypes = [i32] * 4 + [vp] * 4 + [f32] + [vp] * 11 + [ctypes.c_size_t, vp]
-    lib.dg_cluster_lookup_forward.restype = ctypes.c_int
-    lib.dg_cluster_lookup_forward.argtypes = [vp, vp, f32] + [i32] * 4 + [vp] * 6
-    lib.dg_cluster_lookup_backward.restype = ctypes.c_int
-    lib.dg_cluster_lookup_backward.argtypes = [vp, vp, vp, f32, vp] + [i32] * 4 + [vp] * 4
-    lib.dg_probe_ce_forward.restype = ctypes.c_int
-    lib.dg_probe_ce_forward.argtypes = [vp, vp] + [i32] * 6 + [vp] * 3
-    lib.dg_probe_ce_backward.restype = ctypes.c_int
-    lib.dg_probe_ce_backward.argtypes = [vp] * 4 + [i32] * 6 + [vp] * 2
-    lib.dg_segment_predict.restype = ctypes.c_int
-    lib.dg_segment_predict.argtypes = [vp, vp] + [i32] * 4 + [vp, vp, i32, vp, i32, vp, i32, i32, vp, vp, i32, vp, vp, vp,
-                                                            ctypes.c_size_t, vp]
-    lib.dg_crf_workspace_bytes.restype = ctypes.c_size_t
-    lib.dg_crf_workspace_bytes.argtypes = [i32] * 5
-    lib.dg_crf_unary.restype = ctypes.c_int
-    lib.dg_crf_unary.argtypes = [vp] + [i32] * 6 + [vp, i32, vp, vp]
-    lib.dg_segment_unary.restype = ctypes.c_int
-    lib.dg_segment_unary.argtypes = [vp, vp] + [i32] * 4 + [vp, vp, i32, vp, i32, i32, i32, f32, vp, vp, ctypes.c_size_t, vp]
-    lib.dg_crf_filter.restype = ctypes.c_int
-    lib.dg_crf_filter.argtypes = [vp, vp] + [i32] * 5 + [f32, f32, vp, vp, ctypes.c_size_t, vp]
-    lib.dg_dense_crf.restype = ctypes.c_int
-    lib.dg_dense_crf.argtypes = [vp, vp] + [i32] * 3 + [vp, i32, i32] + [f32] * 5 + [vp, vp, vp, ctypes.c_size_t, vp]
-    lib.dg_corr_main_kernel_name.restype = ctypes.c_char_p
-    lib.dg_corr_main_kernel_name.argtypes = [cp]
-    lib.dg_corr_intra_folded.restype = ctypes.c_int
-    lib.dg_corr_intra_folded.argtypes = [cp]
-    lib.dg_corr_backward.restype = ctypes.c_int
-    lib.dg_corr_backward.argtypes = [cp] + [vp] * 7 + [ctypes.c_size_t, vp]
-    lib.dg_corr_backward_total.restype = ctypes.c_int
-    lib.dg_corr_backward_total.argtypes = [cp] + [vp] * 7 + [ctypes.c_size_t, vp]
-    lib.dg_corr_materialize.restype = ctypes.c_int
-    lib.dg_corr_materialize.argtypes = [cp, ctypes.c_int32, vp, vp, vp, ctypes.c_size_t, vp]
-    lib.dg_corr_materialize_shared.restype = ctypes.c_int
-    lib.dg_corr_materialize_shared.argtypes = [cp, ctypes.c_int32, vp, vp, vp, vp, ctypes.c_size_t, vp]
-    lib.dg_corr_relaunch_main.restype = ctypes.c_int
-    lib.dg_corr_relaunch_main.argtypes = [cp, vp, vp, ctypes.c_size_t, vp]
-    lib.dg_fps_workspace_bytes.restype = ctypes.c_size_t
-    lib.dg_fps_workspace_bytes.argtypes = [ctypes.c_int32] * 3
-    lib.dg_fps_coords.restype = ctypes.c_int
-    lib.dg_fps_coords.argtypes = [vp] + [ctypes.c_int32] * 6 + [vp, vp, vp, ctypes.c_size_t, vp]
-    lib.dg_sampled_sumsq.restype = ctypes.c_int
-    lib.dg_sampled_sumsq.argtypes = [ctypes.c_int32] * 6 + [vp, vp, vp, ctypes.c_int32, vp, vp]
-    lib.dg_corr_forward_extnorm.restype = ctypes.c_int
-    lib.dg_corr_forward_extnorm.argtypes = [cp] + [vp] * 11 + [ctypes.c_size_t, vp]
-    lib.dg_normalize_split.restype = ctypes.c_int
-    lib.dg_normalize_split.argtypes = [ctypes.c_int32] * 4 + [vp, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_void_p), vp]
-    lib.dg_rand_coords_state.restype = ctypes.c_int
-    lib.dg_rand_coords_state.argtypes = [vp, ctypes.c_int64, vp, vp]
-    lib.dg_rand_keep_state.restype = ctypes.c_int
-    lib.dg_rand_keep_state.argtypes = [vp, ctypes.c_int64, ctypes.c_float, vp, vp]
-    lib.dg_fps_coords_pair.restype = ctypes.c_int
-    lib.dg_fps_coords_pair.argtypes = [vp, vp] + [ctypes.c_int32] * 6 + [vp, vp, vp, ctypes.c_size_t, vp]
-    lib.dg_super_perms.restype = ctypes.c_int
-    lib.dg_super_perms.argtypes = [vp, ctypes.c_int32, ctypes.c_int32, vp, vp]
-    lib.dg_salience_coords.restype = ctypes.c_int
-    lib.dg_salience_coords.argtypes = [vp] + [ctypes.c_int32] * 4 + [vp, vp, vp, vp]
-    lib.dg_simple_depth_coords.restype = ctypes.c_int
-    lib.dg_simple_depth_coords.argtypes = [vp] + [ctypes.c_int32] * 6 + [vp, vp, vp, vp]
-    lib.dg_confusion_update.restype = ctypes.c_int
-    lib.dg_confusion_update.argtypes = [vp, vp, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, vp, vp]
-    lib.dg_topk_rows.restype = ctypes.c_int
-    lib.dg_topk_rows.argtypes = [vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, vp, vp, vp]
-    lib.dg_knn_similarities.restype = ctypes.c_int
-    lib.dg_knn_similarities.argtypes = [vp, vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64, vp, ctypes.c_int64, vp]
-    lib.dg_lhp_forward.restype = ctypes.c_int
-    lib.dg_lhp_forward.argtypes = [vp, vp] + [ctypes.c_int32] * 6 + [vp, vp, vp, vp]
-    lib.dg_lhp_backward.restype = ctypes.c_int
-    lib.dg_lhp_backward.argtypes = [vp, vp, vp] + [ctypes.c_int32] * 4 + [vp, vp]
-    lib.dg_lhp_map_forward.restype = ctypes.c_int
-    lib.dg_lhp_map_forward.argtypes = [ctypes.c_int32, vp, vp, vp, vp] + [ctypes.c_int32] * 7 + [vp, vp, vp, vp]
-    lib.dg_lhp_map_backward.restype = ctypes.c_int
-    lib.dg_lhp_map_backward.argtypes = [ctypes.c_int32, vp, vp, vp] + [ctypes.c_int32] * 4 + [vp, vp]
-    lib.dg_super_perms_seeded.restype = ctypes.c_int
-    lib.dg_super_perms_seeded.argtypes = [ctypes.c_uint64, ctypes.c_int32, ctypes.c_int32, vp, vp]
-    lib.dg_super_perms_state.restype = ctypes.c_int
-    lib.dg_super_perms_state.argtypes = [vp, ctypes.c_int32, ctypes.c_int32, vp, vp]
-    lib.dg_adam_step.restype = ctypes.c_int
-    lib.dg_adam_step.argtypes = [ctypes.POINTER(AdamSeg), i32, ctypes.POINTER(AdamGroup), i32, i32, vp, vp]
-    lib.dg_attention_workspace_bytes.restype = ctypes.c_size_t
-    lib.dg_attention_workspace_bytes.argtypes = [i32] * 3
-    lib.dg_attention_forward.restype = ctypes.c_int
-    lib.dg_attention_forward.argtypes = [vp] + [i32] * 4 + [f32, vp, vp, ctypes.c_size_t, vp]
-    lib.dg_vit_linear_packed_bytes.restype = ctypes.c_size_t
-    lib.dg_vit_linear_packed_bytes.argtypes = [i32] * 2
-    lib.dg_vit_linear_pack.restype = ctypes.c_int
-    lib.dg_vit_linear_pack.argtypes = [vp, i32, i32, vp, vp]
-    lib.dg_vit_linear_forward.restype = ctypes.c_int
-    lib.dg_vit_linear_forward.argtypes = [vp, vp, vp, f32, vp, vp, vp, vp] + [i32] * 4 + [vp]
-    lib.dg_prof_main_span.restype = ctypes.c_int
-    lib.dg_prof_main_span.argtypes = [vp]
+    for name, (restype, argtypes) in SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, argtypes
     _lib = lib
     return lib
 

@@ -24,7 +24,55 @@ from . import vit
 from .head import ProjectionHead, run_head, run_head_pair
 
 
-class DinoFeaturizer(nn.Module):
+class FrozenBackboneFeaturizer(nn.Module):
+    """DinoFeaturizer's output contract (src/modules.py:90-137: train -> (feats, code, attn), eval -> (feats, code); feats get a
+    third Dropout2d mask when cfg.dropout) around any frozen backbone.  A subclass sets `cfg`, `patch_size`, `n_feats` and `model`,
+    calls `_register_head`, and supplies `_backbone(img, n, return_class_feat)` -> (image_feat (B, n_feats, H/p, W/p), attn), or
+    (the class feature (B, n_feats, 1, 1), None); it runs under no_grad with the backbone in eval mode."""
+
+    supports_deferred_dropout = True      # forward_pair(..., defer_feats_dropout=True) hands back ops.DeferredDropout feats
+
+    def _register_head(self, dim, cfg):
+        """Dropout2d, cluster1 and cluster2 under the reference's names (:75-88), behind `model`: its checkpoints load unchanged."""
+        self.dropout = nn.Dropout2d(p=.1)
+        head = ProjectionHead(self.n_feats, dim, getattr(cfg, "projection_type", "nonlinear"))   # (modules only: run_head does the work)
+        self.cluster1 = head.cluster1
+        if hasattr(head, "cluster2"):
+            self.cluster2 = head.cluster2
+        self.proj_type = head.proj_type
+
+    def _head_modules(self):
+        return self.cluster1, self.cluster2 if self.proj_type == "nonlinear" else None
+
+    def forward(self, img, n=1, return_class_feat=False):
+        self.model.eval()
+        with torch.no_grad():
+            image_feat, attn = self._backbone(img, n, return_class_feat)
+            if return_class_feat:
+                return image_feat
+        if self.proj_type is not None:
+            # one fused HIP launch: code = cluster1(drop(f)) [+ cluster2(drop(f))] and feats = drop(f) (:122-137; three draws)
+            code, feats = run_head(*self._head_modules(), image_feat, self.training, bool(self.cfg.dropout), float(self.dropout.p))
+        else:
+            code = image_feat
+            feats = self.dropout(image_feat) if self.cfg.dropout else image_feat    # :129-137 (identity in eval mode)
+        return (feats, code, attn) if self.training else (feats, code)
+
+    def forward_pair(self, img, img_pos, defer_feats_dropout=False):
+        """forward(img) and forward(img_pos) of one training step (src/train_segmentation.py:194-212) with the head's two passes in
+        one set of launches (run_head_pair): the frozen backbone has no random draws, so the six Dropout2d draws come in the
+        reference's order.  Training mode with a projection head only; returns ((feats, code, attn), (feats_pos, code_pos, attn_pos))."""
+        if not self.training or self.proj_type is None:
+            return self.forward(img), self.forward(img_pos)
+        self.model.eval()
+        with torch.no_grad():
+            (image_feat, attn), (image_feat_pos, attn_pos) = self._backbone(img), self._backbone(img_pos)
+        (code, feats), (code_pos, feats_pos) = run_head_pair(*self._head_modules(), image_feat, image_feat_pos, True,
+                                                             bool(self.cfg.dropout), float(self.dropout.p), None, defer_feats_dropout)
+        return (feats, code, attn), (feats_pos, code_pos, attn_pos)
+
+
+class DinoFeaturizer(FrozenBackboneFeaturizer):
     """DinoFeaturizer(dim, cfg) of src/modules.py:19-137."""
 
     def __init__(self, dim: int, cfg):
@@ -54,13 +102,8 @@ class DinoFeaturizer(nn.Module):
         for p in self.model.parameters():                                       # :34-35
             p.requires_grad = False
         self.model.eval()
-        self.dropout = nn.Dropout2d(p=.1)
         self.n_feats = int(model.embed_dim)                                     # :70-73 (384 / 768 for ViT-S / ViT-B)
-        head = ProjectionHead(self.n_feats, dim, getattr(cfg, "projection_type", "nonlinear"))   # (modules only: run_head does the work)
-        self.cluster1 = head.cluster1                                           # :75-78, the reference's names
-        if hasattr(head, "cluster2"):
-            self.cluster2 = head.cluster2
-        self.proj_type = head.proj_type
+        self._register_head(dim, cfg)
 
     def _attn_is_read(self):
         return self.training and bool(getattr(self.cfg, "lhp", False)) and getattr(self.cfg, "propagation_strategy", "depth") == "attn"
@@ -85,33 +128,3 @@ class DinoFeaturizer(nn.Module):
         if not want_attn:
             attn = torch.zeros(1, device=img.device)                            # placeholder: only `is None` is ever asked of it
         return image_feat, attn
-
-    def forward(self, img, n=1, return_class_feat=False):
-        self.model.eval()
-        with torch.no_grad():
-            image_feat, attn = self._backbone(img, n, return_class_feat)
-            if return_class_feat:
-                return image_feat
-        if self.proj_type is not None:
-            # one fused HIP launch: code = cluster1(drop(f)) [+ cluster2(drop(f))] and feats = drop(f) (:122-137; three draws)
-            code, feats = run_head(self.cluster1, self.cluster2 if self.proj_type == "nonlinear" else None, image_feat,
-                                   self.training, bool(self.cfg.dropout), float(self.dropout.p))
-        else:
-            code = image_feat
-            feats = self.dropout(image_feat) if self.cfg.dropout else image_feat
-        return (feats, code, attn) if self.training else (feats, code)
-
-    supports_deferred_dropout = True      # forward_pair(..., defer_feats_dropout=True) hands back ops.DeferredDropout feats
-
-    def forward_pair(self, img, img_pos, defer_feats_dropout=False):
-        """forward(img) and forward(img_pos) of one training step (src/train_segmentation.py:194-212) with the head's two passes in
-        one set of launches (run_head_pair), as StandInFeaturizer.forward_pair."""
-        if not self.training or self.proj_type is None:
-            return self.forward(img), self.forward(img_pos)
-        self.model.eval()
-        with torch.no_grad():
-            (image_feat, attn), (image_feat_pos, attn_pos) = self._backbone(img), self._backbone(img_pos)
-        (code, feats), (code_pos, feats_pos) = run_head_pair(self.cluster1, self.cluster2 if self.proj_type == "nonlinear" else None,
-                                                             image_feat, image_feat_pos, True, bool(self.cfg.dropout), float(self.dropout.p),
-                                                             None, defer_feats_dropout)
-        return (feats, code, attn), (feats_pos, code_pos, attn_pos)

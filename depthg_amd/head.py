@@ -10,20 +10,11 @@
                         resolution + cross entropy over the labelled pixels in one kernel (dg_probe_ce_forward / _backward)
 All arithmetic runs in the library; CPU tensors raise (there is no eager path).
 """
-import ctypes
-import math
-
 import torch
 import torch.nn as nn
 
 from . import _lib
-from .ops import _empty, _ptr, _stream
-
-
-def _gpu32(t, name):
-    if not t.is_cuda:
-        raise RuntimeError(f"depthg_amd: `{name}` must live on the GPU (got {t.device}); there is no CPU path")
-    return t.detach().to(torch.float32).contiguous()
+from .ops import DeferredDropout, _empty, _f32c, _on_gpu, _ptr, _stream
 
 
 def _check_keeps(keeps, rows, C, device, what):
@@ -53,129 +44,78 @@ def _check_keeps(keeps, rows, C, device, what):
 
 
 class _HeadFunction(torch.autograd.Function):
+    """The head on one featurizer pass (dg_head_forward / dg_head_backward) or on both passes of a step (img, img_pos) through ONE
+    set of launches (dg_head_forward_pair / dg_head_backward_pair): the same numbers as two single calls whose weight gradients
+    autograd adds up - without the six additions, with half the launches, and with no concatenated copy of the features.
+    `feats`: the one or two (B,C,h,w) maps; keeps: (rows, C) each, rows = B per pass, the first pass's first.
+    -> (code per pass ..., feats_out per pass ... (None unless want_feats))."""
+
     @staticmethod
-    def forward(ctx, feat, keeps, scale, want_feats, w1, b1, w2a, b2a, w2b, b2b):
+    def forward(ctx, keeps, scale, want_feats, w1, b1, w2a, b2a, w2b, b2b, *feats):
         lib = _lib.load()
-        f = _gpu32(feat, "image_feat")
-        B, C, h, w = f.shape
-        D, P, dev = w1.shape[0], h * w, f.device
-        nonlinear = w2a is not None
-        if ctx.needs_input_grad[0]:
+        n = len(feats)
+        pair = "_pair" if n == 2 else ""
+        fs = [_f32c(t, name) for t, name in zip(feats, ("image_feat", "image_feat_pos"))]
+        f = fs[0]
+        if n == 2 and (f.shape != fs[1].shape or f.device != fs[1].device):
+            raise ValueError(f"depthg_amd: the two passes' features must match: {tuple(f.shape)} on {f.device} and {tuple(fs[1].shape)} on {fs[1].device}")
+        if any(ctx.needs_input_grad[9:]):
             # (the backbone is frozen in the reference - DinoFeaturizer runs it under no_grad, src/modules.py:96 - and no
             #  d/d image_feat kernel exists: refuse rather than drop that gradient silently)
             raise RuntimeError("depthg_amd: ProjectionHead received features that require grad; the head has no gradient with "
                                "respect to its input (frozen backbone) - detach them")
-        # grad mode and requires_grad of the six parameters, as autograd sees them: under torch.no_grad() / eval inference the
-        # bf16 hidden tile (19 MB at the headline shape) is neither written nor kept
-        need_grad = any(ctx.needs_input_grad[4:])
-        code = _empty((B, D, h, w), torch.float32, dev)
-        feats_out = _empty((B, C, h, w), torch.float32, dev) if want_feats else None
-        hidden = _empty((B, C, P), torch.bfloat16, dev) if (nonlinear and need_grad) else None
-        k1, k2, k3 = _check_keeps(keeps, B, C, dev, "ProjectionHead.forward")
-        W = lambda t: _gpu32(t, "head parameter").reshape(t.shape[0], -1) if t is not None else None
-        w1c, w2ac, w2bc = W(w1), W(w2a), W(w2b)
-        wscratch = _empty((lib.dg_head_weights_bytes(C, D),), torch.uint8, dev)     # bf16 copies of the weights (first launch)
-        rc = lib.dg_head_forward(B, C, D, P, _ptr(f), _ptr(w1c), _ptr(_gpu32(b1, "bias")), _ptr(w2ac),
-                                 _ptr(_gpu32(b2a, "bias")) if nonlinear else None, _ptr(w2bc),
-                                 _ptr(_gpu32(b2b, "bias")) if nonlinear else None, _ptr(k1), _ptr(k2), _ptr(k3), float(scale),
-                                 _ptr(code), _ptr(feats_out), _ptr(hidden), _ptr(wscratch), _stream(dev))
-        _lib.check(rc, "dg_head_forward")
-        ctx.dims, ctx.scale, ctx.nonlinear = (B, C, D, P), float(scale), nonlinear
-        ctx.shapes = tuple(t.shape if t is not None else None for t in (w1, b1, w2a, b2a, w2b, b2b))
-        ctx.save_for_backward(f, k1, k2, hidden, wscratch)
-        if feats_out is not None:
-            ctx.mark_non_differentiable(feats_out)
-        return code, feats_out
-
-    @staticmethod
-    def backward(ctx, gcode, _gfeats):
-        lib = _lib.load()
-        f, k1, k2, hidden, wscratch = ctx.saved_tensors
-        B, C, D, P = ctx.dims
-        dev = f.device
-        if ctx.nonlinear and hidden is None:
-            raise RuntimeError("depthg_amd: head backward without the saved hidden activations")
-        g = _gpu32(gcode, "grad_code")
-        nb = lib.dg_head_workspace_bytes(B, C, D, P)
-        ws = _empty(nb, torch.uint8, dev)
-        gw1, gb1 = _empty((D, C), torch.float32, dev), _empty((D,), torch.float32, dev)
-        gw2a = gb2a = gw2b = gb2b = None
-        if ctx.nonlinear:
-            gw2a, gb2a = _empty((C, C), torch.float32, dev), _empty((C,), torch.float32, dev)
-            gw2b, gb2b = _empty((D, C), torch.float32, dev), _empty((D,), torch.float32, dev)
-        rc = lib.dg_head_backward(B, C, D, P, _ptr(f), _ptr(k1), _ptr(k2), ctx.scale, _ptr(hidden), _ptr(wscratch),
-                                  _ptr(g), _ptr(gw1), _ptr(gb1), _ptr(gw2a), _ptr(gb2a), _ptr(gw2b), _ptr(gb2b), _ptr(ws), nb,
-                                  _stream(dev))
-        _lib.check(rc, "dg_head_backward")
-        sh = ctx.shapes
-        R = lambda t, i: t.reshape(sh[i]) if t is not None else None
-        return (None, None, None, None, R(gw1, 0), R(gb1, 1), R(gw2a, 2), R(gb2a, 3), R(gw2b, 4), R(gb2b, 5))
-
-
-class _HeadPairFunction(torch.autograd.Function):
-    """Both featurizer passes of a step (img, img_pos) through ONE set of launches (dg_head_forward_pair / dg_head_backward_pair):
-    the same numbers as two _HeadFunction calls whose weight gradients autograd adds up - without the six additions, with half
-    the launches, and with no concatenated copy of the features."""
-
-    @staticmethod
-    def forward(ctx, feat, feat_pos, keeps, scale, want_feats, w1, b1, w2a, b2a, w2b, b2b):
-        lib = _lib.load()
-        f, fp = _gpu32(feat, "image_feat"), _gpu32(feat_pos, "image_feat_pos")
-        if f.shape != fp.shape or f.device != fp.device:
-            raise ValueError(f"depthg_amd: the two passes' features must match: {tuple(f.shape)} on {f.device} and {tuple(fp.shape)} on {fp.device}")
-        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
-            raise RuntimeError("depthg_amd: ProjectionHead received features that require grad; the head has no gradient with "
-                               "respect to its input (frozen backbone) - detach them")
         B, C, h, w = f.shape
         D, P, dev = w1.shape[0], h * w, f.device
         nonlinear = w2a is not None
-        need_grad = any(ctx.needs_input_grad[5:])
-        code, code_pos = _empty((B, D, h, w), torch.float32, dev), _empty((B, D, h, w), torch.float32, dev)
-        fo = _empty((B, C, h, w), torch.float32, dev) if want_feats else None
-        fo_pos = _empty((B, C, h, w), torch.float32, dev) if want_feats else None
-        hidden = _empty((2 * B, C, P), torch.bfloat16, dev) if (nonlinear and need_grad) else None
-        k1, k2, k3 = _check_keeps(keeps, 2 * B, C, dev, "ProjectionHead.forward_pair")   # (2B, C) each: the first pass's rows first
-        W = lambda t: _gpu32(t, "head parameter").reshape(t.shape[0], -1) if t is not None else None
-        w1c, w2ac, w2bc = W(w1), W(w2a), W(w2b)
-        wscratch = _empty((lib.dg_head_weights_bytes(C, D),), torch.uint8, dev)
-        rc = lib.dg_head_forward_pair(B, C, D, P, _ptr(f), _ptr(fp), _ptr(w1c), _ptr(_gpu32(b1, "bias")), _ptr(w2ac),
-                                      _ptr(_gpu32(b2a, "bias")) if nonlinear else None, _ptr(w2bc),
-                                      _ptr(_gpu32(b2b, "bias")) if nonlinear else None, _ptr(k1), _ptr(k2), _ptr(k3), float(scale),
-                                      _ptr(code), _ptr(code_pos), _ptr(fo), _ptr(fo_pos), _ptr(hidden), _ptr(wscratch), _stream(dev))
-        _lib.check(rc, "dg_head_forward_pair")
-        ctx.dims, ctx.scale, ctx.nonlinear = (B, C, D, P), float(scale), nonlinear
+        # grad mode and requires_grad of the six parameters, as autograd sees them: under torch.no_grad() / eval inference the
+        # bf16 hidden tile (19 MB at the headline shape) is neither written nor kept
+        need_grad = any(ctx.needs_input_grad[3:9])
+        codes = [_empty((B, D, h, w), torch.float32, dev) for _ in fs]
+        fouts = [_empty((B, C, h, w), torch.float32, dev) if want_feats else None for _ in fs]
+        hidden = _empty((n * B, C, P), torch.bfloat16, dev) if (nonlinear and need_grad) else None
+        k1, k2, k3 = _check_keeps(keeps, n * B, C, dev, "ProjectionHead.forward" + pair)
+        # (weights as (out, in) matrices; None stays None, which the library takes as NULL: projection_type "linear")
+        w1c, b1c, w2ac, b2ac, w2bc, b2bc = (_f32c(t, "head parameter") for t in (w1, b1, w2a, b2a, w2b, b2b))
+        w1c, w2ac, w2bc = (t.reshape(t.shape[0], -1) if t is not None else None for t in (w1c, w2ac, w2bc))
+        wscratch = _empty((lib.dg_head_weights_bytes(C, D),), torch.uint8, dev)     # bf16 copies of the weights (first launch)
+        entry = "dg_head_forward" + pair
+        rc = getattr(lib, entry)(B, C, D, P, *map(_ptr, fs), _ptr(w1c), _ptr(b1c), _ptr(w2ac), _ptr(b2ac), _ptr(w2bc), _ptr(b2bc),
+                                 _ptr(k1), _ptr(k2), _ptr(k3), float(scale), *map(_ptr, codes), *map(_ptr, fouts), _ptr(hidden),
+                                 _ptr(wscratch), _stream(dev))
+        _lib.check(rc, entry)
+        ctx.dims, ctx.scale, ctx.nonlinear, ctx.pair = (B, C, D, P), float(scale), nonlinear, pair
         ctx.shapes = tuple(t.shape if t is not None else None for t in (w1, b1, w2a, b2a, w2b, b2b))
-        ctx.save_for_backward(f, fp, k1, k2, hidden, wscratch)
+        ctx.save_for_backward(k1, k2, hidden, wscratch, *fs)
         ctx.set_materialize_grads(False)
-        if fo is not None:
-            ctx.mark_non_differentiable(fo, fo_pos)
-        return code, code_pos, fo, fo_pos
+        if want_feats:
+            ctx.mark_non_differentiable(*fouts)
+        return (*codes, *fouts)
 
     @staticmethod
-    def backward(ctx, gcode, gcode_pos, _gf, _gfp):
+    def backward(ctx, *grads):
         lib = _lib.load()
-        f, fp, k1, k2, hidden, wscratch = ctx.saved_tensors
+        k1, k2, hidden, wscratch, *fs = ctx.saved_tensors
         B, C, D, P = ctx.dims
-        dev = f.device
+        n, dev = len(fs), fs[0].device
         if ctx.nonlinear and hidden is None:
             raise RuntimeError("depthg_amd: head backward without the saved hidden activations")
         # (a pass whose code took no part in the loss contributes nothing: a zero upstream)
-        g = _gpu32(gcode, "grad_code") if gcode is not None else torch.zeros((B, D, P), dtype=torch.float32, device=dev)
-        gp = _gpu32(gcode_pos, "grad_code_pos") if gcode_pos is not None else torch.zeros((B, D, P), dtype=torch.float32, device=dev)
-        nb = lib.dg_head_workspace_bytes(2 * B, C, D, P)
+        gs = [_f32c(g, name) if g is not None else torch.zeros((B, D, P), dtype=torch.float32, device=dev)
+              for g, name in zip(grads[:n], ("grad_code", "grad_code_pos"))]
+        nb = lib.dg_head_workspace_bytes(n * B, C, D, P)
         ws = _empty(nb, torch.uint8, dev)
         gw1, gb1 = _empty((D, C), torch.float32, dev), _empty((D,), torch.float32, dev)
         gw2a = gb2a = gw2b = gb2b = None
         if ctx.nonlinear:
             gw2a, gb2a = _empty((C, C), torch.float32, dev), _empty((C,), torch.float32, dev)
             gw2b, gb2b = _empty((D, C), torch.float32, dev), _empty((D,), torch.float32, dev)
-        rc = lib.dg_head_backward_pair(B, C, D, P, _ptr(f), _ptr(fp), _ptr(k1), _ptr(k2), ctx.scale, _ptr(hidden), _ptr(wscratch),
-                                       _ptr(g), _ptr(gp), _ptr(gw1), _ptr(gb1), _ptr(gw2a), _ptr(gb2a), _ptr(gw2b), _ptr(gb2b),
-                                       _ptr(ws), nb, _stream(dev))
-        _lib.check(rc, "dg_head_backward_pair")
-        sh = ctx.shapes
-        R = lambda t, i: t.reshape(sh[i]) if t is not None else None
-        return (None, None, None, None, None, R(gw1, 0), R(gb1, 1), R(gw2a, 2), R(gb2a, 3), R(gw2b, 4), R(gb2b, 5))
+        entry = "dg_head_backward" + ctx.pair
+        rc = getattr(lib, entry)(B, C, D, P, *map(_ptr, fs), _ptr(k1), _ptr(k2), ctx.scale, _ptr(hidden), _ptr(wscratch),
+                                 *map(_ptr, gs), _ptr(gw1), _ptr(gb1), _ptr(gw2a), _ptr(gb2a), _ptr(gw2b), _ptr(gb2b), _ptr(ws), nb,
+                                 _stream(dev))
+        _lib.check(rc, entry)
+        gparams = (gw1, gb1, gw2a, gb2a, gw2b, gb2b)
+        return (None, None, None) + tuple(g.reshape(sh) if g is not None else None for g, sh in zip(gparams, ctx.shapes)) + (None,) * n
 
 
 def draw_keep_masks_pair(B, C, device, p=0.1, use=(True, True, True)):
@@ -198,26 +138,38 @@ def draw_keep_masks(B, C, device, p=0.1, use=(True, True, True)):
     return tuple(torch.empty(B, C, device=device, dtype=torch.float32).bernoulli_(1.0 - p) if u else None for u in use)
 
 
-def run_head(cluster1, cluster2, image_feat, training, feats_dropout, p=0.1, keeps=None):
-    """(code, feats) of one featurizer pass (src/modules.py:122-137) from the reference's modules: `cluster1` = Sequential(Conv2d),
-    `cluster2` = Sequential(Conv2d, ReLU, Conv2d) or None (projection_type "linear").  Training: three Dropout2d draws (`keeps`
-    or drawn here), feats = Dropout2d(image_feat) when `feats_dropout` (cfg.dropout); eval: no dropout, feats = image_feat."""
-    B, C = image_feat.shape[:2]
+def _run_head(cluster1, cluster2, feats, training, feats_dropout, p, keeps, draw, defer=False):
+    """What run_head and run_head_pair share: the keep masks that exist (given, or drawn with `draw`), the head's parameters, one
+    _HeadFunction call on the one or two maps of `feats`, and ((code, feats), ...) per pass."""
+    B, C = feats[0].shape[:2]
     nl = cluster2 is not None
+    scale = 1.0 / (1.0 - p)
     if training:
         if keeps is None:
-            keeps = draw_keep_masks(B, C, image_feat.device, p, use=(True, nl, bool(feats_dropout)))
+            keeps = draw(B, C, feats[0].device, p, use=(True, nl, bool(feats_dropout)))
         k1, k2, k3 = keeps
         keeps = (k1, k2 if nl else None, k3 if feats_dropout else None)
     else:
         keeps = None                                                                                  # eval: Dropout2d is the identity
-    c1 = cluster1[0]
-    c2a, c2b = (cluster2[0], cluster2[2]) if nl else (None, None)
     want_feats = bool(training and feats_dropout)
-    code, feats = _HeadFunction.apply(image_feat, keeps, 1.0 / (1.0 - p), want_feats, c1.weight, c1.bias,
-                                      c2a.weight if nl else None, c2a.bias if nl else None,
-                                      c2b.weight if nl else None, c2b.bias if nl else None)
-    return code, (feats if want_feats else image_feat)
+    deferred = None
+    if want_feats and defer:
+        deferred, want_feats = keeps[2], False
+        keeps = (keeps[0], keeps[1], None)
+    convs = (cluster1[0], cluster2[0], cluster2[2]) if nl else (cluster1[0],)
+    params = [t for conv in convs for t in (conv.weight, conv.bias)] + [None] * (6 - 2 * len(convs))
+    out = _HeadFunction.apply(keeps, scale, want_feats, *params, *feats)
+    codes, fouts = out[:len(feats)], out[len(feats):]
+    if deferred is not None:
+        return tuple((c, DeferredDropout(f, deferred[i * B:(i + 1) * B], scale)) for i, (c, f) in enumerate(zip(codes, feats)))
+    return tuple((c, fo if want_feats else f) for c, f, fo in zip(codes, feats, fouts))
+
+
+def run_head(cluster1, cluster2, image_feat, training, feats_dropout, p=0.1, keeps=None):
+    """(code, feats) of one featurizer pass (src/modules.py:122-137) from the reference's modules: `cluster1` = Sequential(Conv2d),
+    `cluster2` = Sequential(Conv2d, ReLU, Conv2d) or None (projection_type "linear").  Training: three Dropout2d draws (`keeps`
+    or drawn here), feats = Dropout2d(image_feat) when `feats_dropout` (cfg.dropout); eval: no dropout, feats = image_feat."""
+    return _run_head(cluster1, cluster2, (image_feat,), training, feats_dropout, p, keeps, draw_keep_masks)[0]
 
 
 def run_head_pair(cluster1, cluster2, image_feat, image_feat_pos, training, feats_dropout, p=0.1, keeps=None, defer_feats_dropout=False):
@@ -226,30 +178,8 @@ def run_head_pair(cluster1, cluster2, image_feat, image_feat_pos, training, feat
     Dropout2d of the returned feats is drawn as always but NOT applied - `feats` / `feats_pos` come back as ops.DeferredDropout
     (the input maps + their keep flags), which ContrastiveCorrelationLoss applies inside its operand preparation: the dropped
     tensors (38.5 MB each at the headline shape) are neither written here nor read there."""
-    B, C = image_feat.shape[:2]
-    nl = cluster2 is not None
-    if training:
-        if keeps is None:
-            keeps = draw_keep_masks_pair(B, C, image_feat.device, p, use=(True, nl, bool(feats_dropout)))
-        k1, k2, k3 = keeps
-        keeps = (k1, k2 if nl else None, k3 if feats_dropout else None)
-    else:
-        keeps = None
-    c1 = cluster1[0]
-    c2a, c2b = (cluster2[0], cluster2[2]) if nl else (None, None)
-    want_feats = bool(training and feats_dropout)
-    deferred = None
-    if want_feats and defer_feats_dropout:
-        deferred, want_feats = keeps[2], False
-        keeps = (keeps[0], keeps[1], None)
-    code, code_pos, feats, feats_pos = _HeadPairFunction.apply(
-        image_feat, image_feat_pos, keeps, 1.0 / (1.0 - p), want_feats, c1.weight, c1.bias,
-        c2a.weight if nl else None, c2a.bias if nl else None, c2b.weight if nl else None, c2b.bias if nl else None)
-    if deferred is not None:
-        from .ops import DeferredDropout
-        scale = 1.0 / (1.0 - p)
-        return ((code, DeferredDropout(image_feat, deferred[:B], scale)), (code_pos, DeferredDropout(image_feat_pos, deferred[B:], scale)))
-    return (code, feats if want_feats else image_feat), (code_pos, feats_pos if want_feats else image_feat_pos)
+    return _run_head(cluster1, cluster2, (image_feat, image_feat_pos), training, feats_dropout, p, keeps, draw_keep_masks_pair,
+                     defer_feats_dropout)
 
 
 class ProjectionHead(nn.Module):
@@ -297,7 +227,7 @@ class _ClusterFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, clusters, alpha, want_logp):
         lib = _lib.load()
-        xx, cc = _gpu32(x, "x"), _gpu32(clusters, "clusters")
+        xx, cc = _f32c(x, "x"), _f32c(clusters, "clusters")
         B, D, h, w = xx.shape
         n, P, dev = cc.shape[0], h * w, xx.device
         inner = _empty((B, n, h, w), torch.float32, dev)
@@ -324,7 +254,7 @@ class _ClusterFunction(torch.autograd.Function):
         xx, cc, inner = ctx.saved_tensors
         B, D, n, P = ctx.dims
         dev = xx.device
-        g = _gpu32(gloss, "grad_loss").reshape(1)
+        g = _f32c(gloss, "grad_loss").reshape(1)
         gc = _empty((n, D), torch.float32, dev)
         gx = _empty(tuple(xx.shape), torch.float32, dev) if ctx.x_grad else None
         scratch = _empty((B * n * P + B * ((P + 63) // 64) * n * D,), torch.float32, dev)
@@ -361,10 +291,8 @@ class _ProbeCeFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, logits, label):
         lib = _lib.load()
-        lg = _gpu32(logits, "linear_logits")
-        if not label.is_cuda:
-            raise RuntimeError("depthg_amd: `label` must live on the GPU; there is no CPU path")
-        lab = label.detach().to(torch.int64).contiguous()
+        lg = _f32c(logits, "linear_logits")
+        lab = _on_gpu(label, "label").detach().to(torch.int64).contiguous()
         B, n, h, w = lg.shape
         H, W = lab.shape[-2:]
         lab = lab.reshape(B, H, W)
@@ -382,7 +310,7 @@ class _ProbeCeFunction(torch.autograd.Function):
         lib = _lib.load()
         lg, lab, out3 = ctx.saved_tensors
         B, n, h, w, H, W = ctx.dims
-        g = _gpu32(gloss, "grad_loss").reshape(1)
+        g = _f32c(gloss, "grad_loss").reshape(1)
         gl = _empty((B, n, h, w), torch.float32, lg.device)
         rc = lib.dg_probe_ce_backward(_ptr(lg), _ptr(lab), _ptr(out3), _ptr(g), B, n, h, w, H, W, _ptr(gl), _stream(lg.device))
         _lib.check(rc, "dg_probe_ce_backward")

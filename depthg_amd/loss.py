@@ -18,6 +18,8 @@ After a call, `.scalars` is the fused fp32 output vector (DG_OUT_* order: the fo
 weighted total) with its grad_fn and `.total` its last element = the term `training_step` adds to its loss
 (src/train_segmentation.py:330-349, weights read from cfg), so `loss_fn.total.backward()` needs no further torch ops.
 """
+from types import SimpleNamespace
+
 import torch
 import torch.nn as nn
 
@@ -260,11 +262,46 @@ class ContrastiveCorrelationLoss(nn.Module):
     # -- everything after the RNG draws (explicit coords / perms: parity tests, DP shards) ----------
     def forward_with(self, orig_feats, orig_feats_pos, orig_code, orig_code_pos, depth, coords1, coords2, perms,
                      shared_coords=False, identity_grid=False, draw_state=None, _checked=False, feat_keep=None):
-        cfg = self.cfg
         if feat_keep is None:
             orig_feats, orig_feats_pos, feat_keep = self._unwrap_deferred(orig_feats, orig_feats_pos)
         if not _checked:
             self._check_maps(orig_feats, orig_feats_pos, orig_code, orig_code_pos, depth)
+        call = self._prepare(orig_feats, orig_feats_pos, orig_code, orig_code_pos, depth, coords1, coords2, perms,
+                             bool(shared_coords), bool(identity_grid), draw_state, feat_keep)
+        wide = call.C > ops.BLOB_MAX_C and (call.identity_grid or call.P_pos > SMALL_GRID_POSITIONS)
+        if call.feat_keep is not None and (wide or not call.identity_grid):
+            # only the identity grid's own operand preparation takes the keep flags (dg_corr_forward_masked): the samplers, and the
+            # normalisation in front of a wide map's chunks, read the dropped tensors - formed here, the same values
+            call.feats, call.feats_pos = self._apply_keep(call.feats, call.feats_pos, call.feat_keep)
+            call.feat_keep = None
+        if not wide:
+            out, total, chunks = self._run_chunks(call, [call.feats], [call.feats_pos], keep=call.feat_keep)
+        elif call.identity_grid:
+            # Feature maps wider than the operand kernels hold, on the dense identity grid: the loss is LINEAR in the feature
+            # correlation fd = sum over channels (src/modules.py:797-809; helper(), :1231-1254: the centering of fd, the shift and
+            # -clamp(cd) * (fd - shift)), and on this grid sample() is a transposition, so norm() can run in front of it.  The maps are
+            # normalised over all C channels once (dg_normalize_split) and evaluated chunk by chunk (DG_FEATS_UNIT): the first chunk
+            # with the recipe's shifts and depth term, the others with zero shifts and without it; the loss means and the code
+            # gradients add up, the cd means (and everything of the depth term) are the first chunk's.
+            chunk_c = self._chunk_channels(call.C)
+            out, total, chunks = self._run_chunks(call, ops.normalize_split(call.feats, chunk_c), ops.normalize_split(call.feats_pos, chunk_c),
+                                                  unit=True)
+        else:
+            fa, fb, feat_inv = self._wide_sampled_operands(call)
+            out, total, chunks = self._run_chunks(call, fa, fb, feat_inv=feat_inv)
+        desc, ws = chunks[0]
+        d = self.__dict__                      # plain attributes: nn.Module.__setattr__ costs microseconds per assignment
+        d["last_scalars"] = out.detach()
+        d["scalars"] = out                     # the fused output vector with its grad_fn (DG_OUT_* order)
+        d["total"] = total                     # weighted total of the loss means (src/train_segmentation.py:330-349)
+        d["last_call"] = (desc, call.perms, ws)   # measurement aid (bench.py re-launches the fused kernel alone)
+        return self._outputs(call, out, chunks)
+
+    def _prepare(self, orig_feats, orig_feats_pos, orig_code, orig_code_pos, depth, coords1, coords2, perms, shared_coords,
+                 identity_grid, draw_state, feat_keep):
+        """Everything forward_with checks and converts in front of the first launch, in the order the errors are promised in: the
+        call's operands as the library reads them and its dimensions, as one namespace."""
+        cfg = self.cfg
         if identity_grid and tuple(orig_code.shape[-2:]) != tuple(orig_feats.shape[-2:]):
             raise ValueError(f"depthg_amd: the identity grid needs code maps of the feature maps' size, got "
                              f"{orig_code.shape[-2]}x{orig_code.shape[-1]} against {orig_feats.shape[-2]}x{orig_feats.shape[-1]}")
@@ -276,21 +313,12 @@ class ContrastiveCorrelationLoss(nn.Module):
             # (cfg.dg_small_identity_blobs: the old route, kept for A/B runs and the C-ABI tests of DG_IDENTITY_GRID at small P.)
             identity_grid = False
         if feat_keep is not None:
-            ka, kb, kscale = feat_keep
-            for name, k in (("orig_feats", ka), ("orig_feats_pos", kb)):
+            for name, k in (("orig_feats", feat_keep[0]), ("orig_feats_pos", feat_keep[1])):
                 if k is not None and (tuple(k.shape) != tuple(orig_feats.shape[:2]) or k.device != orig_feats.device):
                     raise RuntimeError(f"depthg_amd: keep flags of `{name}` are {tuple(k.shape)} on {k.device}; the maps are "
                                        f"{tuple(orig_feats.shape)} on {orig_feats.device}")
-            if not identity_grid:
-                # sampled coordinates: the samplers read the maps themselves - the dropped tensors are formed here (same values)
-                if ka is not None:
-                    orig_feats = orig_feats * (ka * kscale)[:, :, None, None]
-                if kb is not None:
-                    orig_feats_pos = orig_feats_pos * (kb * kscale)[:, :, None, None]
-                feat_keep = None
         B, C, h, w = orig_feats.shape
         D, hc, wc = orig_code.shape[1:]
-        same_maps = (hc, wc) == (h, w)
         S, N = int(cfg.feature_samples), int(cfg.neg_samples)
         if tuple(coords1.shape) != tuple(coords2.shape) or tuple(coords1.shape) not in ((B, S, S, 2), (B, S, 1, 2)):
             raise ValueError(f"depthg_amd: coords must both be (B,S,S,2) or (B,S,1,2) with B={B}, S={S}; got "
@@ -306,7 +334,6 @@ class ContrastiveCorrelationLoss(nn.Module):
         coords2 = ops._f32c(coords2, "coords2")
         if coords1.device != dev or coords2.device != dev:
             raise RuntimeError(f"depthg_amd: coords live on {coords1.device} / {coords2.device}, the maps on {dev}")
-        line_grid = coords1.shape[2] == 1 and S != 1       # S x 1 grid of depth_sampling='simple'
         if perms is None:
             perms_t = None                 # drawn inside the forward (dg_corr_forward_draw)
         elif isinstance(perms, (list, tuple)):
@@ -317,133 +344,124 @@ class ContrastiveCorrelationLoss(nn.Module):
         if perms_t is not None:
             perms_t = perms_t.contiguous()
             assert perms_t.shape == (N, B), f"perms shape {tuple(perms_t.shape)} != {(N, B)}"
-        need_grad = torch.is_grad_enabled() and (orig_code.requires_grad or orig_code_pos.requires_grad)
-        code_in = orig_code if orig_code.dtype == torch.float32 else orig_code.float()
-        code_pos_in = orig_code_pos if orig_code_pos.dtype == torch.float32 else orig_code_pos.float()
-        code_in, code_pos_in = code_in.contiguous(), code_pos_in.contiguous()
-        all_shifts = (cfg.pos_intra_shift, cfg.pos_inter_shift, cfg.neg_inter_shift, cfg.depth_feat_shift if depth_term else 0.0)
+        code = orig_code if orig_code.dtype == torch.float32 else orig_code.float()
+        code_pos = orig_code_pos if orig_code_pos.dtype == torch.float32 else orig_code_pos.float()
+        return SimpleNamespace(
+            feats=feats, feats_pos=feats_pos, code=code.contiguous(), code_pos=code_pos.contiguous(), depth=depth_c, coords1=coords1,
+            coords2=coords2, perms=perms_t, feat_keep=feat_keep, draw_state=draw_state, dev=dev, B=B, C=C, h=h, w=w, D=D, S=S, N=N,
+            code_hw=None if (hc, wc) == (h, w) else (hc, wc), P_pos=int(coords1.shape[1]) * int(coords1.shape[2]),
+            line_grid=coords1.shape[2] == 1 and S != 1,       # S x 1 grid of depth_sampling='simple'
+            depth_term=depth_term, shared_coords=shared_coords, identity_grid=identity_grid,
+            need_grad=torch.is_grad_enabled() and (orig_code.requires_grad or orig_code_pos.requires_grad),
+            shifts=(cfg.pos_intra_shift, cfg.pos_inter_shift, cfg.neg_inter_shift, cfg.depth_feat_shift if depth_term else 0.0))
 
-        def run(f_a, f_b, perms_in, first=True, unit=False, keep=feat_keep, feat_inv=None):
-            """one launch set of the C ABI on feature maps of the width the operand kernels hold (`first`: the recipe's shifts and
-            depth term; else a further channel chunk of a wider map: zero shifts, no depth term - see below)"""
-            dt = depth_term and first
-            desc_ = ops.make_desc(B, f_a.shape[1], D, h, w, S, N, pointwise=bool(cfg.pointwise), zero_clamp=bool(cfg.zero_clamp),
-                                  stabalize=bool(cfg.stabalize), depth_term=dt, need_grad=need_grad,
-                                  shared_coords=bool(shared_coords),
-                                  shifts=all_shifts if first else (0.0, 0.0, 0.0, 0.0),
-                                  depth_hw=tuple(depth_c.shape[-2:]) if (depth_c is not None and dt) else (0, 0),
-                                  identity_grid=bool(identity_grid), weights=self._total_weights(dt),
-                                  line_grid=line_grid, code_hw=None if same_maps else (hc, wc),
-                                  exact_masks=bool(getattr(cfg, "dg_exact_masks", False)), feats_unit=unit)
-            holder_ = {"draw_state": draw_state, "feat_keep": keep, "feat_inv": feat_inv}
-            out_, total_ = _CorrLossFunction.apply(code_in, code_pos_in, f_a, f_b, depth_c if dt else None,
-                                                   coords1, coords2, perms_in, desc_, holder_)
-            return out_, total_, desc_, holder_["workspace"], (holder_["perms"] if perms_in is None else perms_in)
+    @staticmethod
+    def _apply_keep(feats, feats_pos, feat_keep):
+        """The deferred Dropout2d in torch: x * (keep * scale), the fp32 product the featurizer would have stored."""
+        ka, kb, kscale = feat_keep
+        if ka is not None:
+            feats = feats * (ka * kscale)[:, :, None, None]
+        if kb is not None:
+            feats_pos = feats_pos * (kb * kscale)[:, :, None, None]
+        return feats, feats_pos
 
-        wide = identity_grid and C > ops.BLOB_MAX_C
-        P_pos = int(coords1.shape[1]) * int(coords1.shape[2])
-        wide_sampled = (not identity_grid) and C > ops.BLOB_MAX_C and P_pos > SMALL_GRID_POSITIONS
-        if wide_sampled:
-            # ... and on SAMPLED coordinates above 160 positions: the reference normalises behind sample(), so the norm of every sampled
-            # vector is formed over all channel chunks first (dg_sampled_sumsq per operand: feats at coords1, feats_pos at coords2 and,
-            # with coordinates per image, feats through every negative's batch map at coords2), then each chunk runs with those norms
-            # (dg_corr_forward_extnorm) - shifts, depth term and the sums as on the dense grid below
-            if feat_keep is not None:
-                raise RuntimeError("depthg_amd: deferred feature dropout is the identity grid's")       # (forward_with formed the tensors above)
-            if perms_t is None:
-                perms_t = super_perms(N, B, dev) if N > 0 else torch.zeros(0, B, dtype=torch.long, device=dev)
-            nops = 2 if (shared_coords or N == 0) else 2 + N
-            nch = (C + ops.BLOB_MAX_C - 1) // ops.BLOB_MAX_C
-            chunk_c = ((C + nch - 1) // nch + 7) // 8 * 8
-            fa = [feats[:, k:k + chunk_c].contiguous() for k in range(0, C, chunk_c)]
-            fb = [feats_pos[:, k:k + chunk_c].contiguous() for k in range(0, C, chunk_c)]
-            sumsq = torch.empty(nops, B, P_pos, device=dev, dtype=torch.float32)
-            for k in range(len(fa)):
-                ops.sampled_sumsq(fa[k], coords1, None, sumsq[0], k > 0)
-                ops.sampled_sumsq(fb[k], coords2, None, sumsq[1], k > 0)
-                for j in range(2, nops):
-                    ops.sampled_sumsq(fa[k], coords2, perms_t[j - 2], sumsq[j], k > 0)     # (the negatives are orig_feats[perm] at coords2, src/modules.py:1341-1345)
-            feat_inv = (1.0 / sumsq.sqrt().clamp_min(1e-10)).contiguous()
-            chunks = []
-            for k in range(len(fa)):
-                o_k, t_k, desc_k, ws_k, perms_t = run(fa[k], fb[k], perms_t, first=(k == 0), keep=None, feat_inv=feat_inv)
-                chunks.append((o_k, t_k, desc_k, ws_k))
-            lossmask = torch.zeros(ops._lib.DG_OUT_COUNT, device=dev)
+    @staticmethod
+    def _chunk_channels(C):
+        """Channels per chunk of a map wider than the operand kernels hold: even chunks, a multiple of 8."""
+        nch = (C + ops.BLOB_MAX_C - 1) // ops.BLOB_MAX_C
+        return ((C + nch - 1) // nch + 7) // 8 * 8
+
+    def _run_chunk(self, call, f_a, f_b, first, unit, keep, feat_inv):
+        """One launch set of the C ABI on feature maps of the width the operand kernels hold (`first`: the recipe's shifts and depth
+        term; else a further channel chunk of a wider map: zero shifts, no depth term).  -> (out, total, desc, workspace)."""
+        cfg = self.cfg
+        dt = call.depth_term and first
+        desc = ops.make_desc(call.B, f_a.shape[1], call.D, call.h, call.w, call.S, call.N, pointwise=bool(cfg.pointwise),
+                             zero_clamp=bool(cfg.zero_clamp), stabalize=bool(cfg.stabalize), depth_term=dt, need_grad=call.need_grad,
+                             shared_coords=call.shared_coords, shifts=call.shifts if first else (0.0, 0.0, 0.0, 0.0),
+                             depth_hw=tuple(call.depth.shape[-2:]) if (call.depth is not None and dt) else (0, 0),
+                             identity_grid=call.identity_grid, weights=self._total_weights(dt), line_grid=call.line_grid,
+                             code_hw=call.code_hw, exact_masks=bool(getattr(cfg, "dg_exact_masks", False)), feats_unit=unit)
+        holder = {"draw_state": call.draw_state, "feat_keep": keep, "feat_inv": feat_inv}
+        out, total = _CorrLossFunction.apply(call.code, call.code_pos, f_a, f_b, call.depth if dt else None,
+                                             call.coords1, call.coords2, call.perms, desc, holder)
+        if call.perms is None:
+            call.perms = holder["perms"]       # (drawn by the forward: what backward, materialize and further chunks read)
+        return out, total, desc, holder["workspace"]
+
+    def _run_chunks(self, call, fa, fb, unit=False, keep=None, feat_inv=None):
+        """The channel chunks fa[k] / fb[k] of the two feature maps, one launch set each (a map the kernels hold whole: one chunk):
+        the loss means and the total add up over the chunks, the cd means (and everything of the depth term) are the first chunk's.
+        -> (out, total, [(desc, workspace) per chunk])."""
+        chunks = []
+        for k in range(len(fa)):
+            o_k, t_k, desc_k, ws_k = self._run_chunk(call, fa[k], fb[k], k == 0, unit, keep, feat_inv)
+            chunks.append((desc_k, ws_k, o_k, t_k))
+        out, total = chunks[0][2], chunks[0][3]
+        if len(chunks) > 1:
+            lossmask = torch.zeros(ops._lib.DG_OUT_COUNT, device=call.dev)
             lossmask[[0, 1, 2, ops._lib.DG_OUT_TOTAL]] = 1.0
-            out, total = chunks[0][0], chunks[0][1]
-            for o_k, t_k, _, _ in chunks[1:]:
+            for _, _, o_k, t_k in chunks[1:]:
                 out = out + o_k * lossmask
                 total = total + t_k
-            desc, ws = chunks[0][2], chunks[0][3]
-        elif not wide:
-            out, total, desc, ws, perms_t = run(feats, feats_pos, perms_t)
-            chunks = None
-        else:
-            # Feature maps wider than the operand kernels hold, on the dense identity grid: the loss is LINEAR in the feature
-            # correlation fd = sum over channels (src/modules.py:797-809; helper(), :1231-1254: the centering of fd, the shift and
-            # -clamp(cd) * (fd - shift)), and on this grid sample() is a transposition, so norm() can run in front of it.  The maps are
-            # normalised over all C channels once (dg_normalize_split) and evaluated chunk by chunk (DG_FEATS_UNIT): the first chunk
-            # with the recipe's shifts and depth term, the others with zero shifts and without it; the loss means and the code
-            # gradients add up, the cd means (and everything of the depth term) are the first chunk's.
-            if feat_keep is not None:          # (deferred Dropout2d: formed here, in front of the normalisation - same values)
-                ka, kb, kscale = feat_keep
-                if ka is not None:
-                    feats = feats * (ka * kscale)[:, :, None, None]
-                if kb is not None:
-                    feats_pos = feats_pos * (kb * kscale)[:, :, None, None]
-            nch = (C + ops.BLOB_MAX_C - 1) // ops.BLOB_MAX_C
-            chunk_c = ((C + nch - 1) // nch + 7) // 8 * 8
-            fa, fb = ops.normalize_split(feats, chunk_c), ops.normalize_split(feats_pos, chunk_c)
-            chunks = []
-            for k in range(len(fa)):
-                o_k, t_k, desc_k, ws_k, perms_t = run(fa[k], fb[k], perms_t, first=(k == 0), unit=True, keep=None)
-                chunks.append((o_k, t_k, desc_k, ws_k))
-            lossmask = torch.zeros(ops._lib.DG_OUT_COUNT, device=dev)
-            lossmask[[0, 1, 2, ops._lib.DG_OUT_TOTAL]] = 1.0
-            out, total = chunks[0][0], chunks[0][1]
-            for o_k, t_k, _, _ in chunks[1:]:
-                out = out + o_k * lossmask
-                total = total + t_k
-            desc, ws = chunks[0][2], chunks[0][3]
-        d = self.__dict__                      # plain attributes: nn.Module.__setattr__ costs microseconds per assignment
-        d["last_scalars"] = out.detach()
-        d["scalars"] = out                     # the fused output vector with its grad_fn (DG_OUT_* order)
-        d["total"] = total                     # weighted total of the loss means (src/train_segmentation.py:330-349)
-        d["last_call"] = (desc, perms_t, ws)   # measurement aid (bench.py re-launches the fused kernel alone)
+        return out, total, [c[:2] for c in chunks]
 
-        mode = getattr(cfg, "dg_outputs", "full")
+    def _wide_sampled_operands(self, call):
+        """Wide maps on SAMPLED coordinates above 160 positions: the reference normalises behind sample(), so the norm of every
+        sampled vector is formed over all channel chunks first (dg_sampled_sumsq per operand: feats at coords1, feats_pos at coords2
+        and, with coordinates per image, feats through every negative's batch map at coords2), then each chunk runs with those norms
+        (dg_corr_forward_extnorm) - shifts, depth term and the sums as on the dense grid.  -> (chunks of feats, of feats_pos, feat_inv)."""
+        B, C, N, dev = call.B, call.C, call.N, call.dev
+        if call.perms is None:
+            call.perms = super_perms(N, B, dev) if N > 0 else torch.zeros(0, B, dtype=torch.long, device=dev)
+        nops = 2 if (call.shared_coords or N == 0) else 2 + N
+        chunk_c = self._chunk_channels(C)
+        fa = [call.feats[:, k:k + chunk_c].contiguous() for k in range(0, C, chunk_c)]
+        fb = [call.feats_pos[:, k:k + chunk_c].contiguous() for k in range(0, C, chunk_c)]
+        sumsq = torch.empty(nops, B, call.P_pos, device=dev, dtype=torch.float32)
+        for k in range(len(fa)):
+            ops.sampled_sumsq(fa[k], call.coords1, None, sumsq[0], k > 0)
+            ops.sampled_sumsq(fb[k], call.coords2, None, sumsq[1], k > 0)
+            for j in range(2, nops):
+                ops.sampled_sumsq(fa[k], call.coords2, call.perms[j - 2], sumsq[j], k > 0)     # (the negatives are orig_feats[perm] at coords2, src/modules.py:1341-1345)
+        return fa, fb, (1.0 / sumsq.sqrt().clamp_min(1e-10)).contiguous()
+
+    def _outputs(self, call, out, chunks):
+        """The reference's 6- / 8-tuple (src/modules.py:1352-1367) from the fused scalars: cfg.dg_outputs "reduced" - the means
+        alone; "full" - the un-reduced tensors, materialised from the operands the forward left in the chunks' workspaces."""
+        mode = getattr(self.cfg, "dg_outputs", "full")
         if mode == "reduced":
             res = (out[0], out[4:5].detach(), out[1], out[5:6].detach(), out[2:3], out[6:7].detach())
-            if depth_term:
+            if call.depth_term:
                 res = res + (out[3], out[7:8].detach())
             return res
         if mode != "full":
             raise ValueError(f"cfg.dg_outputs must be 'full' or 'reduced', got {mode!r}")
-        # reference-shaped outputs (src/modules.py:1352-1367); cd tensors carry no gradient (the caller only logs them)
+        # cd tensors carry no gradient (the caller only logs them)
         # (on the shared dense grid the negatives' operands are the anchors' operand read through the batch maps: the maps go along;
         #  a 28 x 28 tensor is 78.7 MB per pair-set at B = 32 - the reference materialises them on every step, here only when asked)
+        (desc, ws), perms_t = chunks[0], call.perms
         intra_cd, _ = ops.corr_materialize(desc, 0, ws)
         inter_cd, _ = ops.corr_materialize(desc, 1, ws)
         neg_cd, neg_loss = [], []
-        for k in range(N):
+        for k in range(call.N):
             c, l = ops.corr_materialize(desc, 2 + k, ws, want_cd=True, want_loss=True, perms=perms_t)
-            if chunks is not None:             # (a wide map in channel chunks: the un-reduced loss is the sum of the chunks' too)
-                for _, _, desc_j, ws_j in chunks[1:]:
-                    l = l + ops.corr_materialize(desc_j, 2 + k, ws_j, want_cd=False, want_loss=True, perms=perms_t)[1]
+            for desc_j, ws_j in chunks[1:]:    # (a wide map in channel chunks: the un-reduced loss is the sum of the chunks' too)
+                l = l + ops.corr_materialize(desc_j, 2 + k, ws_j, want_cd=False, want_loss=True, perms=perms_t)[1]
             neg_cd.append(c)
             neg_loss.append(l)
-        if N > 0:
+        if call.N > 0:
             neg_cd_t = torch.cat(neg_cd, dim=0)
             # un-reduced negative loss: values from the kernel; gradient routed through its mean (exact for the
             # uniform upstreams that .mean()/.sum() produce, which is how the caller consumes it,
             # src/train_segmentation.py:303)
             neg_loss_t = torch.cat(neg_loss, dim=0) + (out[2] - out[2].detach())
         else:
-            sh = 1 if line_grid else S
-            neg_cd_t = torch.zeros(0, sh, S, sh, S, device=dev)
+            sh = 1 if call.line_grid else call.S
+            neg_cd_t = torch.zeros(0, sh, call.S, sh, call.S, device=call.dev)
             neg_loss_t = neg_cd_t.clone()
         res = (out[0], intra_cd, out[1], inter_cd, neg_loss_t, neg_cd_t)
-        if depth_term:
+        if call.depth_term:
             dd, _ = ops.corr_materialize(desc, -1, ws)
             res = res + (out[3], dd)
         return res

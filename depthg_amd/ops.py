@@ -39,12 +39,28 @@ def _stream(device):
     return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
-def _f32c(t, name):
-    if t is None:
-        return None
+def _on_gpu(t, name):
+    """The product path has no CPU route: a tensor anywhere else is refused by name."""
     if not t.is_cuda:
         raise RuntimeError(f"depthg_amd: `{name}` must live on the GPU (got {t.device}); there is no CPU path")
-    return t.detach().to(torch.float32).contiguous()
+    return t
+
+
+def _f32c(t, name):
+    """`t` as the library reads it - detached, fp32, contiguous, on the GPU (None stays None)."""
+    return None if t is None else _on_gpu(t, name).detach().to(torch.float32).contiguous()
+
+
+def _check_state(state, who, device=None):
+    """`state` must be new_perm_state's int64[3] generator words, on `device` when one is named, else on any GPU."""
+    placed = state.is_cuda if device is None else state.device == device
+    if state.dtype != torch.int64 or state.numel() != 3 or not placed:
+        raise ValueError(f"{who}: state must be the int64[3] tensor of new_perm_state on " + ("the same device" if device is not None else "the GPU"))
+
+
+def _cpu_seed():
+    """A 62-bit seed from torch's CPU generator: torch.manual_seed fixes every draw keyed by it, and no device RNG launch is needed."""
+    return int(torch.randint(0, 2 ** 62, (), dtype=torch.int64).item())
 
 
 def make_desc(B, C, D, h, w, S, n_neg, *, pointwise, zero_clamp, stabalize, depth_term, need_grad, shared_coords,
@@ -91,19 +107,6 @@ def sampled_sumsq(feats_chunk, coords, srcidx, out, accumulate):
                                             1 if accumulate else 0, _ptr(out), _stream(feats_chunk.device)), "dg_sampled_sumsq")
 
 
-def corr_forward_extnorm(desc, feats, feats_pos, code, code_pos, depth, coords1, coords2, perms, feat_inv, workspace):
-    """dg_corr_forward on ONE channel chunk of wider feature maps, normalised by `feat_inv` (nops, B, P): 1 / the norm of the whole
-    sampled vector (sampled coordinates above 160 positions; see include/depthg_corr.h)."""
-    lib = _lib.load()
-    dev = feats.device
-    out = _empty(_lib.DG_OUT_COUNT, torch.float32, dev)
-    rc = lib.dg_corr_forward_extnorm(ctypes.byref(desc), _ptr(feats), _ptr(feats_pos), _ptr(code), _ptr(code_pos), _ptr(depth),
-                                     _ptr(coords1), _ptr(coords2), _ptr(perms), _ptr(feat_inv), _ptr(out), _ptr(workspace),
-                                     workspace.numel(), _stream(dev))
-    _lib.check(rc, "dg_corr_forward_extnorm")
-    return out
-
-
 def workspace_bytes(desc):
     n = _lib.load().dg_corr_workspace_bytes(ctypes.byref(desc))
     if n == 0:
@@ -115,36 +118,45 @@ def alloc_workspace(desc, device):
     return _empty(workspace_bytes(desc), torch.uint8, device)
 
 
+def _corr_forward(entry, desc, maps, perms, mid, workspace):
+    """The one body of the four forward entry points, whose argument lists differ only between `perms` and `out_scalars`: `mid`."""
+    dev = maps[0].device
+    out = _empty(_lib.DG_OUT_COUNT, torch.float32, dev)
+    rc = getattr(_lib.load(), entry)(ctypes.byref(desc), *[_ptr(t) for t in maps], _ptr(perms), *mid, _ptr(out), _ptr(workspace),
+                                     workspace.numel(), _stream(dev))
+    _lib.check(rc, entry)
+    return out
+
+
+def _drawn_perms(desc, dev, state, who):
+    """(the (n_neg, B) buffer a drawing forward fills, its seed): `state` (new_perm_state) keys the draw on the device (seed 0), else
+    the seed comes from torch's CPU generator, as in super_perms()."""
+    perms = _empty((int(desc.n_neg), int(desc.B)), torch.long, dev)
+    if state is None:
+        return perms, _cpu_seed()
+    _check_state(state, who, dev)
+    return perms, 0
+
+
 def corr_forward(desc, feats, feats_pos, code, code_pos, depth, coords1, coords2, perms, workspace):
     """Returns fp32 [DG_OUT_COUNT] device tensor (order: DG_OUT_* of include/depthg_corr.h)."""
-    lib = _lib.load()
-    dev = feats.device
-    out = _empty(_lib.DG_OUT_COUNT, torch.float32, dev)
-    rc = lib.dg_corr_forward(ctypes.byref(desc), _ptr(feats), _ptr(feats_pos), _ptr(code), _ptr(code_pos), _ptr(depth),
-                             _ptr(coords1), _ptr(coords2), _ptr(perms), _ptr(out), _ptr(workspace),
-                             workspace.numel(), _stream(dev))
-    _lib.check(rc, "dg_corr_forward")
-    return out
+    return _corr_forward("dg_corr_forward", desc, (feats, feats_pos, code, code_pos, depth, coords1, coords2), perms, (), workspace)
+
+
+def corr_forward_extnorm(desc, feats, feats_pos, code, code_pos, depth, coords1, coords2, perms, feat_inv, workspace):
+    """dg_corr_forward on ONE channel chunk of wider feature maps, normalised by `feat_inv` (nops, B, P): 1 / the norm of the whole
+    sampled vector (sampled coordinates above 160 positions; see include/depthg_corr.h)."""
+    return _corr_forward("dg_corr_forward_extnorm", desc, (feats, feats_pos, code, code_pos, depth, coords1, coords2), perms,
+                         (_ptr(feat_inv),), workspace)
 
 
 def corr_forward_draw(desc, feats, feats_pos, code, code_pos, depth, coords1, coords2, workspace, state=None):
     """dg_corr_forward_draw: the forward draws the negatives' batch maps itself (on the identity grid inside its first launch).
     Returns (out, perms): perms (n_neg, B) int64 is what backward / materialize need.  `state` (new_perm_state) = device-resident
     generator (hipGraph-safe); without it the seed comes from torch's CPU generator, as in super_perms()."""
-    lib = _lib.load()
-    dev = feats.device
-    out = _empty(_lib.DG_OUT_COUNT, torch.float32, dev)
-    perms = _empty((int(desc.n_neg), int(desc.B)), torch.long, dev)
-    seed = 0
-    if state is None:
-        seed = int(torch.randint(0, 2 ** 62, (), dtype=torch.int64).item())
-    elif state.dtype != torch.int64 or state.numel() != 3 or state.device != dev:
-        raise ValueError("corr_forward_draw: state must be the int64[3] tensor of new_perm_state on the same device")
-    rc = lib.dg_corr_forward_draw(ctypes.byref(desc), _ptr(feats), _ptr(feats_pos), _ptr(code), _ptr(code_pos), _ptr(depth),
-                                  _ptr(coords1), _ptr(coords2), _ptr(perms), seed, _ptr(state), _ptr(out), _ptr(workspace),
-                                  workspace.numel(), _stream(dev))
-    _lib.check(rc, "dg_corr_forward_draw")
-    return out, perms
+    perms, seed = _drawn_perms(desc, feats.device, state, "corr_forward_draw")
+    return _corr_forward("dg_corr_forward_draw", desc, (feats, feats_pos, code, code_pos, depth, coords1, coords2), perms,
+                         (seed, _ptr(state)), workspace), perms
 
 
 class DeferredDropout:
@@ -177,49 +189,36 @@ def corr_forward_masked(desc, feats, feats_pos, code, code_pos, depth, coords1, 
                         scale):
     """dg_corr_forward_masked: the forward on UN-dropped feature maps + their Dropout2d keep flags (identity grid).  perms None:
     drawn inside (as corr_forward_draw).  Returns (out, perms)."""
-    lib = _lib.load()
     dev = feats.device
-    out = _empty(_lib.DG_OUT_COUNT, torch.float32, dev)
-    draw, seed = 0, 0
-    if perms is None:
-        draw = 1
-        perms = _empty((int(desc.n_neg), int(desc.B)), torch.long, dev)
-        if state is None:
-            seed = int(torch.randint(0, 2 ** 62, (), dtype=torch.int64).item())
-        elif state.dtype != torch.int64 or state.numel() != 3 or state.device != dev:
-            raise ValueError("corr_forward_masked: state must be the int64[3] tensor of new_perm_state on the same device")
+    draw, seed = int(perms is None), 0
+    if draw:
+        perms, seed = _drawn_perms(desc, dev, state, "corr_forward_masked")
     for k in (keep, keep_pos):
         if k is not None and (k.dtype != torch.float32 or not k.is_contiguous() or k.device != dev or tuple(k.shape) != (int(desc.B), int(desc.C))):
             raise ValueError(f"corr_forward_masked: keep flags must be contiguous fp32 (B,C) = ({desc.B},{desc.C}) on {dev}")
-    rc = lib.dg_corr_forward_masked(ctypes.byref(desc), _ptr(feats), _ptr(feats_pos), _ptr(code), _ptr(code_pos), _ptr(depth),
-                                    _ptr(coords1), _ptr(coords2), _ptr(perms), draw, seed, _ptr(state) if draw else None,
-                                    _ptr(keep), _ptr(keep_pos), float(scale), _ptr(out), _ptr(workspace), workspace.numel(),
-                                    _stream(dev))
-    _lib.check(rc, "dg_corr_forward_masked")
-    return out, perms
+    mid = (draw, seed, _ptr(state) if draw else None, _ptr(keep), _ptr(keep_pos), float(scale))
+    return _corr_forward("dg_corr_forward_masked", desc, (feats, feats_pos, code, code_pos, depth, coords1, coords2), perms, mid,
+                         workspace), perms
+
+
+def _corr_backward(entry, desc, grad, coords1, coords2, perms, workspace, shape_code):
+    dev = grad.device
+    g_code = _empty(shape_code, torch.float32, dev)
+    g_code_pos = _empty(shape_code, torch.float32, dev)
+    rc = getattr(_lib.load(), entry)(ctypes.byref(desc), _ptr(grad), _ptr(coords1), _ptr(coords2), _ptr(perms),
+                                     _ptr(g_code), _ptr(g_code_pos), _ptr(workspace), workspace.numel(), _stream(dev))
+    _lib.check(rc, entry)
+    return g_code, g_code_pos
 
 
 def corr_backward(desc, grad_scalars, coords1, coords2, perms, workspace, shape_code):
-    lib = _lib.load()
-    dev = grad_scalars.device
-    g_code = _empty(shape_code, torch.float32, dev)
-    g_code_pos = _empty(shape_code, torch.float32, dev)
-    rc = lib.dg_corr_backward(ctypes.byref(desc), _ptr(grad_scalars), _ptr(coords1), _ptr(coords2), _ptr(perms),
-                              _ptr(g_code), _ptr(g_code_pos), _ptr(workspace), workspace.numel(), _stream(dev))
-    _lib.check(rc, "dg_corr_backward")
-    return g_code, g_code_pos
+    """Backward for the upstream gradient of the whole out vector: grad_scalars fp32 [DG_OUT_COUNT] on the device."""
+    return _corr_backward("dg_corr_backward", desc, grad_scalars, coords1, coords2, perms, workspace, shape_code)
 
 
 def corr_backward_total(desc, grad_total, coords1, coords2, perms, workspace, shape_code):
     """Backward for an upstream gradient of out[DG_OUT_TOTAL] alone (`total.backward()`): grad_total is a device scalar."""
-    lib = _lib.load()
-    dev = grad_total.device
-    g_code = _empty(shape_code, torch.float32, dev)
-    g_code_pos = _empty(shape_code, torch.float32, dev)
-    rc = lib.dg_corr_backward_total(ctypes.byref(desc), _ptr(grad_total), _ptr(coords1), _ptr(coords2), _ptr(perms),
-                                    _ptr(g_code), _ptr(g_code_pos), _ptr(workspace), workspace.numel(), _stream(dev))
-    _lib.check(rc, "dg_corr_backward_total")
-    return g_code, g_code_pos
+    return _corr_backward("dg_corr_backward_total", desc, grad_total, coords1, coords2, perms, workspace, shape_code)
 
 
 def corr_materialize(desc, which, workspace, want_cd=True, want_loss=False, perms=None):
@@ -313,8 +312,7 @@ def confusion_update(stats, preds, target, n_classes, extra_clusters):
     """stats (n_classes + extra, n_classes) int64 on the GPU += confusion counts of (preds, target) (src/utils.py:222-232)."""
     lib = _lib.load()
     for name, t in (("stats", stats), ("preds", preds), ("target", target)):
-        if not t.is_cuda:
-            raise RuntimeError(f"depthg_amd: `{name}` must live on the GPU (got {t.device}); there is no CPU path")
+        _on_gpu(t, name)
     if stats.dtype != torch.int64 or not stats.is_contiguous() or tuple(stats.shape) != (n_classes + extra_clusters, n_classes):
         raise ValueError("depthg_amd: stats must be a contiguous int64 (n_classes + extra_clusters, n_classes) tensor")
     p = preds.detach().reshape(-1).to(torch.int64).contiguous()
@@ -326,16 +324,12 @@ def confusion_update(stats, preds, target, n_classes, extra_clusters):
     return stats
 
 
-def segment_predict(code, label, lin_w, lin_b, clusters, code_flip=None, stats_lin=None, stats_clu=None, n_store=0):
-    """The probes' arg-max predictions at the label resolution and their confusion counts (dg_segment_predict; the chain of
-    src/train_segmentation.py:471-499 and, with `code_flip`, src/eval_segmentation.py:146-170 without the CRF).
-    code, code_flip (B,D,h,w); lin_w (n,D) or (n,D,1,1); lin_b (n) or None; clusters (m,D); label (B,H,W) (or any shape ending in
-    (H,W) with B*H*W elements).  stats_lin / stats_clu: int64 (rows, n) on the GPU, += the counts [pred][label] in place (rows >= n
-    are never touched), or None.  Returns (preds_lin, preds_clu), int64 (n_store,H,W), or (None, None) when n_store is 0."""
-    lib = _lib.load()
+def _probe_args(code, code_flip, lin_w, lin_b, clusters):
+    """The probes' arguments of segment_predict / segment_unary, checked: code, code_flip (B,D,h,w); lin_w (n,D) or the 1x1
+    convolution's (n,D,1,1); lin_b (n) or None; clusters (m,D).  -> (lin_w as (n,D), (B, D, h, w), n, m)."""
     if code.dim() != 4:
         raise ValueError(f"depthg_amd: code must be (B, D, h, w), got {tuple(code.shape)}")
-    B, D, h, w = code.shape
+    D = code.shape[1]
     if code_flip is not None and tuple(code_flip.shape) != tuple(code.shape):
         raise ValueError(f"depthg_amd: code_flip {tuple(code_flip.shape)} differs from code {tuple(code.shape)}")
     if lin_w.dim() == 4 and tuple(lin_w.shape[2:]) == (1, 1):
@@ -347,7 +341,25 @@ def segment_predict(code, label, lin_w, lin_b, clusters, code_flip=None, stats_l
         raise ValueError(f"depthg_amd: lin_b must be ({n},), got {tuple(lin_b.shape)}")
     if clusters.dim() != 2 or clusters.shape[1] != D:
         raise ValueError(f"depthg_amd: clusters must be (m, {D}), got {tuple(clusters.shape)}")
-    m = clusters.shape[0]
+    return lin_w, tuple(code.shape), n, clusters.shape[0]
+
+
+def _probe_operands(code, code_flip, lin_w, lin_b, clusters, n, m):
+    """The five as the library reads them, and the scratch of the projection at feature resolution (n, m rounded up to 4)."""
+    B, _, h, w = code.shape
+    named = (("code", code), ("code_flip", code_flip), ("lin_w", lin_w), ("lin_b", lin_b), ("clusters", clusters))
+    scratch = _empty((B * h * w * ((n + 3) // 4 * 4 + (m + 3) // 4 * 4) * 4,), torch.uint8, code.device)
+    return tuple(_f32c(t, name) for name, t in named) + (scratch,)
+
+
+def segment_predict(code, label, lin_w, lin_b, clusters, code_flip=None, stats_lin=None, stats_clu=None, n_store=0):
+    """The probes' arg-max predictions at the label resolution and their confusion counts (dg_segment_predict; the chain of
+    src/train_segmentation.py:471-499 and, with `code_flip`, src/eval_segmentation.py:146-170 without the CRF).
+    code, code_flip (B,D,h,w); lin_w (n,D) or (n,D,1,1); lin_b (n) or None; clusters (m,D); label (B,H,W) (or any shape ending in
+    (H,W) with B*H*W elements).  stats_lin / stats_clu: int64 (rows, n) on the GPU, += the counts [pred][label] in place (rows >= n
+    are never touched), or None.  Returns (preds_lin, preds_clu), int64 (n_store,H,W), or (None, None) when n_store is 0."""
+    lib = _lib.load()
+    lin_w, (B, D, h, w), n, m = _probe_args(code, code_flip, lin_w, lin_b, clusters)
     if label.dim() < 2 or label.numel() != B * label.shape[-2] * label.shape[-1]:
         raise ValueError(f"depthg_amd: label must hold (B={B}, H, W) elements, got {tuple(label.shape)}")
     H, W = label.shape[-2:]
@@ -363,14 +375,11 @@ def segment_predict(code, label, lin_w, lin_b, clusters, code_flip=None, stats_l
     tensors = (("code", code), ("label", label), ("lin_w", lin_w), ("lin_b", lin_b), ("clusters", clusters),
                ("code_flip", code_flip), ("stats_lin", stats_lin), ("stats_clu", stats_clu))
     for name, t in tensors:
-        if t is not None and not t.is_cuda:
-            raise RuntimeError(f"depthg_amd: `{name}` must live on the GPU (got {t.device}); there is no CPU path")
+        if t is not None:
+            _on_gpu(t, name)
     dev = code.device
-    code, code_flip = _f32c(code, "code"), _f32c(code_flip, "code_flip")
-    lin_w, lin_b, clusters = _f32c(lin_w, "lin_w"), _f32c(lin_b, "lin_b"), _f32c(clusters, "clusters")
+    code, code_flip, lin_w, lin_b, clusters, scratch = _probe_operands(code, code_flip, lin_w, lin_b, clusters, n, m)
     lab = label.detach().to(torch.int64).reshape(B, H, W).contiguous()
-    kp = (n + 3) // 4 * 4 + (m + 3) // 4 * 4
-    scratch = _empty((B * h * w * kp * 4,), torch.uint8, dev)
     preds_lin = _empty((n_store, H, W), torch.int64, dev) if n_store else None
     preds_clu = _empty((n_store, H, W), torch.int64, dev) if n_store else None
     rc = lib.dg_segment_predict(_ptr(code), _ptr(code_flip), B, D, h, w, _ptr(lin_w), _ptr(lin_b), n, _ptr(clusters), m, _ptr(lab),
@@ -429,26 +438,9 @@ def segment_unary(code, lin_w, lin_b, clusters, H, W, code_flip=None, alpha=2.0)
     code_flip.flip(3) when given) resized to (H,W), linear probe lin_w (n,D) / lin_b -> channels [0, n), cluster probe (clusters
     (m,D), alpha) -> channels [n, n + m), U per probe.  Returns (B, n + m, H, W) fp32."""
     lib = _lib.load()
-    if code.dim() != 4:
-        raise ValueError(f"depthg_amd: code must be (B, D, h, w), got {tuple(code.shape)}")
-    B, D, h, w = code.shape
-    if code_flip is not None and tuple(code_flip.shape) != tuple(code.shape):
-        raise ValueError(f"depthg_amd: code_flip {tuple(code_flip.shape)} differs from code {tuple(code.shape)}")
-    if lin_w.dim() == 4 and tuple(lin_w.shape[2:]) == (1, 1):
-        lin_w = lin_w.reshape(lin_w.shape[0], lin_w.shape[1])
-    if lin_w.dim() != 2 or lin_w.shape[1] != D:
-        raise ValueError(f"depthg_amd: lin_w must be (n, {D}), got {tuple(lin_w.shape)}")
-    n = lin_w.shape[0]
-    if lin_b is not None and tuple(lin_b.shape) != (n,):
-        raise ValueError(f"depthg_amd: lin_b must be ({n},), got {tuple(lin_b.shape)}")
-    if clusters.dim() != 2 or clusters.shape[1] != D:
-        raise ValueError(f"depthg_amd: clusters must be (m, {D}), got {tuple(clusters.shape)}")
-    m = clusters.shape[0]
+    lin_w, (B, D, h, w), n, m = _probe_args(code, code_flip, lin_w, lin_b, clusters)
     dev = code.device
-    code, code_flip = _f32c(code, "code"), _f32c(code_flip, "code_flip")
-    lin_w, lin_b, clusters = _f32c(lin_w, "lin_w"), _f32c(lin_b, "lin_b"), _f32c(clusters, "clusters")
-    kp = (n + 3) // 4 * 4 + (m + 3) // 4 * 4
-    scratch = _empty((B * h * w * kp * 4,), torch.uint8, dev)
+    code, code_flip, lin_w, lin_b, clusters, scratch = _probe_operands(code, code_flip, lin_w, lin_b, clusters, n, m)
     U = _empty((B, n + m, int(H), int(W)), torch.float32, dev)
     rc = lib.dg_segment_unary(_ptr(code), _ptr(code_flip), B, D, h, w, _ptr(lin_w), _ptr(lin_b), n, _ptr(clusters), m, int(H), int(W),
                               float(alpha), _ptr(U), _ptr(scratch), scratch.numel(), _stream(dev))
@@ -520,8 +512,7 @@ def adam_step(segs, groups, device_steps=False, tickets=None):
         for name, t in (("param", p), ("grad", g), ("exp_avg", m), ("exp_avg_sq", v)):
             if t is None and name == "grad":
                 continue
-            if not t.is_cuda:
-                raise RuntimeError(f"depthg_amd: `{name}` must live on the GPU (got {t.device}); there is no CPU path")
+            _on_gpu(t, name)
             if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != p.numel() or t.device != p.device:
                 raise ValueError(f"depthg_amd: adam_step segment {k}: `{name}` must be a contiguous fp32 tensor of the parameter's size and device "
                                  f"(got {t.dtype}, {tuple(t.shape)}, {t.device})")
@@ -554,8 +545,7 @@ def topk_rows(vals, k, return_values=False):
     """Column indices of the k largest entries of every row of `vals` (rows, cols) fp32 on the GPU: value descending, ties by
     ascending column (src/precompute_knns.py:110 `torch.topk(pairwise_sims, 30)[1]`)."""
     lib = _lib.load()
-    if not vals.is_cuda:
-        raise RuntimeError(f"depthg_amd: `vals` must live on the GPU (got {vals.device}); there is no CPU path")
+    _on_gpu(vals, "vals")
     if vals.dim() != 2 or vals.dtype != torch.float32 or vals.stride(1) != 1:
         raise ValueError("depthg_amd: topk_rows wants a 2-D fp32 tensor with contiguous rows")
     rows, cols = vals.shape
@@ -571,8 +561,7 @@ def knn_similarities(queries, feats):
     src/precompute_knns.py:106-108 on the fp32 MFMA."""
     lib = _lib.load()
     for name, t in (("queries", queries), ("feats", feats)):
-        if not t.is_cuda:
-            raise RuntimeError(f"depthg_amd: `{name}` must live on the GPU (got {t.device}); there is no CPU path")
+        _on_gpu(t, name)
         if t.dim() != 2 or t.dtype != torch.float32 or t.stride(1) != 1:
             raise ValueError(f"depthg_amd: `{name}` must be a 2-D fp32 tensor with contiguous rows")
     if queries.shape[1] != feats.shape[1] or queries.device != feats.device:
@@ -658,16 +647,14 @@ def lhp_map_backward(mode, grad_out, wmap, divide=None):
 def new_perm_state(device):
     """Device-resident generator state for super_perms(state=...): int64 {seed, draws so far, 0}; the seed comes from torch's
     CPU generator, so torch.manual_seed before the first use fixes the whole sequence."""
-    seed = int(torch.randint(0, 2 ** 62, (), dtype=torch.int64).item())
-    return torch.tensor([seed, 0, 0], dtype=torch.int64, device=device)
+    return torch.tensor([_cpu_seed(), 0, 0], dtype=torch.int64, device=device)
 
 
 def rand_coords_state(state, shape):
     """Two coordinate tensors of `shape` (B, S, S2, 2), uniform in [-1, 1), from the device-resident generator `state`
     (new_perm_state) in ONE launch - for steps recorded in a hipGraph (dg_rand_coords_state); advances the state."""
     lib = _lib.load()
-    if state.dtype != torch.int64 or state.numel() != 3 or not state.is_cuda:
-        raise ValueError("rand_coords_state: state must be the int64[3] device tensor of new_perm_state")
+    _check_state(state, "rand_coords_state")
     both = _empty((2,) + tuple(int(v) for v in shape), torch.float32, state.device)
     rc = lib.dg_rand_coords_state(_ptr(state), both.numel(), _ptr(both), _stream(state.device))
     _lib.check(rc, "dg_rand_coords_state")
@@ -679,8 +666,7 @@ def keep_masks_state(state, rows, C, p=0.1, use=(True, True, True)):
     tensors of 1 / 0 (keep with probability 1 - p), None where `use` is False - what ProjectionHead.forward(_pair) takes as `keeps`
     (rows = B, or 2B for forward_pair).  Advances the state; not torch's random stream."""
     lib = _lib.load()
-    if state.dtype != torch.int64 or state.numel() != 3 or not state.is_cuda:
-        raise ValueError("keep_masks_state: state must be the int64[3] device tensor of new_perm_state")
+    _check_state(state, "keep_masks_state")
     k = sum(1 for u in use if u)
     if k == 0:
         return (None, None, None)
@@ -699,16 +685,13 @@ def super_perms(count, size, device, keys=None, state=None):
     if count == 0:
         return out
     if state is not None:
-        if state.dtype != torch.int64 or state.numel() != 3 or state.device != out.device:
-            raise ValueError("super_perms: state must be the int64[3] tensor of new_perm_state on the same device")
+        _check_state(state, "super_perms", out.device)
         rc = lib.dg_super_perms_state(_ptr(state), int(count), int(size), _ptr(out), _stream(out.device))
         _lib.check(rc, "dg_super_perms_state")
         return out
     if keys is None:
-        # one launch: the keys are drawn inside the kernel (Philox) from a 64-bit seed taken from torch's CPU generator, so
-        # torch.manual_seed still fixes the sequence and no device RNG launch is needed
-        seed = int(torch.randint(0, 2 ** 62, (), dtype=torch.int64).item())
-        rc = lib.dg_super_perms_seeded(seed, int(count), int(size), _ptr(out), _stream(out.device))
+        # one launch: the keys are drawn inside the kernel (Philox) from a seed of torch's CPU generator
+        rc = lib.dg_super_perms_seeded(_cpu_seed(), int(count), int(size), _ptr(out), _stream(out.device))
         _lib.check(rc, "dg_super_perms_seeded")
         return out
     rc = lib.dg_super_perms(_ptr(keys), int(count), int(size), _ptr(out), _stream(out.device))
@@ -787,8 +770,7 @@ def attention_forward(qkv, heads, scale=None, out=None):
         raise ValueError(f"depthg_amd: qkv must be float32, got {qkv.dtype}")
     if not qkv.is_contiguous():
         raise ValueError(f"depthg_amd: qkv must be contiguous (strides {qkv.stride()})")
-    if not qkv.is_cuda:          # (shape, head dimension and dtype are refused first: those hold on any device)
-        raise RuntimeError(f"depthg_amd: `qkv` must live on the GPU (got {qkv.device}); there is no CPU path")
+    _on_gpu(qkv, "qkv")          # (shape, head dimension and dtype are refused first: those hold on any device)
     if B < 1 or N < 1:
         raise ValueError(f"depthg_amd: qkv must hold at least one token, got {tuple(qkv.shape)}")
     if qkv.requires_grad and torch.is_grad_enabled():
@@ -834,8 +816,7 @@ def vit_linear_pack(weight):
     if not vit_linear_supported(K, Nout):
         raise ValueError(f"depthg_amd: vit_linear_pack is built for K and Nout that are multiples of 64 up to {VIT_LINEAR_MAX}, "
                          f"got K={K}, Nout={Nout}")
-    if not weight.is_cuda:
-        raise RuntimeError(f"depthg_amd: `weight` must live on the GPU (got {weight.device}); there is no CPU path")
+    _on_gpu(weight, "weight")
     if weight.data_ptr() & 15:
         raise ValueError("depthg_amd: vit_linear_pack needs weight to start at a 16-byte aligned address")
     lib = _lib.load()
@@ -888,8 +869,7 @@ def vit_linear_forward(x, packed, n_out, bias=None, *, ln_weight=None, ln_bias=N
     tensors = [x, bias, ln_weight, ln_bias, residual]
     if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors):
         raise RuntimeError("depthg_amd: vit_linear_forward has no backward (the ViT is frozen); call it under torch.no_grad()")
-    if not x.is_cuda:            # (shape, dtype and autograd are refused first: those hold on any device)
-        raise RuntimeError(f"depthg_amd: `x` must live on the GPU (got {x.device}); there is no CPU path")
+    _on_gpu(x, "x")              # (shape, dtype and autograd are refused first: those hold on any device)
     if M < 1:
         raise ValueError(f"depthg_amd: x must hold at least one row, got {tuple(x.shape)}")
     dev = x.device

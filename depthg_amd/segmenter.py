@@ -8,7 +8,8 @@ Mirrors, with the reference's names, parameter layout and arithmetic:
                             its weights cannot be fetched here, so the backbone is a frozen random patch embedding of the same
                             geometry (patch size, n_feats, no gradient) - any module returning (B, n_feats, H/p, W/p) can be
                             passed instead.  Its head (`cluster1` / `cluster2`, the three Dropout2d draws) is ONE fused HIP launch
-                            (depthg_amd/head.py run_head -> dg_head_forward / dg_head_backward).
+                            (depthg_amd/head.py run_head -> dg_head_forward / dg_head_backward); the head's registration, forward
+                            and forward_pair are featurizer.FrozenBackboneFeaturizer's, shared with DinoFeaturizer.
     UnsupervisedSegmenter   LitUnsupervisedSegmenter without Lightning (src/train_segmentation.py:71-158, 169-462): attributes
                             net / train_cluster_probe / cluster_probe / linear_probe / contrastive_corr_loss_fn / cfg /
                             n_classes / use_depth, forward(x) = net(x)[1], configure_optimizers() -> three Adams,
@@ -35,8 +36,8 @@ import torch.nn as nn
 
 from .depth_decay import legacy_decay_step
 from .evaluation import predict_and_score
-from .featurizer import DinoFeaturizer
-from .head import ClusterLookup, ProjectionHead, probe_cross_entropy, run_head, run_head_pair
+from .featurizer import DinoFeaturizer, FrozenBackboneFeaturizer
+from .head import ClusterLookup, ProjectionHead, probe_cross_entropy
 from .lhp import LocalHiddenPositiveProjection, OriginalLocalHiddenPositiveProjection
 from .loss import ContrastiveCorrelationLoss
 from .metrics import UnsupervisedMetrics
@@ -45,7 +46,7 @@ from .parallel import GradBucket
 from .training import correspondence_total
 
 
-class StandInFeaturizer(nn.Module):
+class StandInFeaturizer(FrozenBackboneFeaturizer):
     """DinoFeaturizer's contract with a frozen stand-in backbone (see the module docstring)."""
 
     def __init__(self, dim: int, cfg, backbone: Optional[nn.Module] = None):
@@ -59,12 +60,7 @@ class StandInFeaturizer(nn.Module):
         self.model = backbone
         for p in self.model.parameters():                       # frozen, as the DINO ViT (:34-35)
             p.requires_grad = False
-        self.dropout = nn.Dropout2d(p=.1)
-        head = ProjectionHead(self.n_feats, dim, getattr(cfg, "projection_type", "nonlinear"))   # (modules only: run_head does the work)
-        self.cluster1 = head.cluster1                           # registered under the reference's names
-        if hasattr(head, "cluster2"):
-            self.cluster2 = head.cluster2
-        self.proj_type = head.proj_type
+        self._register_head(dim, cfg)
 
     def _last_selfattention(self, img, image_feat):
         """The ViT's `get_last_selfattention` (B, heads, P+1, P+1) (src/modules.py:103-104).  A backbone that has the method is
@@ -80,40 +76,12 @@ class StandInFeaturizer(nn.Module):
         tok = torch.cat([tok.mean(1, keepdim=True), tok], dim=1).reshape(b, h * w + 1, heads, c // heads).transpose(1, 2)
         return torch.softmax(tok @ tok.transpose(-1, -2) / (c // heads) ** 0.5, dim=-1)
 
-    def forward(self, img, n=1, return_class_feat=False):
-        self.model.eval()
-        with torch.no_grad():
-            assert img.shape[2] % self.patch_size == 0 and img.shape[3] % self.patch_size == 0   # :93-94
-            image_feat = self.model(img)
-            if return_class_feat:
-                return image_feat.mean((2, 3), keepdim=True)
-            attn = self._last_selfattention(img, image_feat)
-        if self.proj_type is not None:
-            # one fused HIP launch: code = cluster1(drop(f)) [+ cluster2(drop(f))] and feats = drop(f) (:122-132; three draws)
-            code, feats = run_head(self.cluster1, self.cluster2 if self.proj_type == "nonlinear" else None, image_feat,
-                                   self.training, bool(self.cfg.dropout), float(self.dropout.p))
-        else:
-            code = image_feat
-            feats = self.dropout(image_feat) if self.cfg.dropout else image_feat    # :129-137 (identity in eval mode)
-        return (feats, code, attn) if self.training else (feats, code)
-
-    supports_deferred_dropout = True      # forward_pair(..., defer_feats_dropout=True) hands back ops.DeferredDropout feats
-
-    def forward_pair(self, img, img_pos, defer_feats_dropout=False):
-        """forward(img) and forward(img_pos) of one training step (src/train_segmentation.py:194-212) with the head's two passes in
-        one set of launches (run_head_pair): the frozen backbone has no random draws, so the six Dropout2d draws come in the
-        reference's order.  Training mode with a projection head only; returns ((feats, code, attn), (feats_pos, code_pos, attn_pos))."""
-        if not self.training or self.proj_type is None:
-            return self.forward(img), self.forward(img_pos)
-        self.model.eval()
-        with torch.no_grad():
-            assert img.shape[2] % self.patch_size == 0 and img.shape[3] % self.patch_size == 0
-            image_feat, image_feat_pos = self.model(img), self.model(img_pos)
-            attn, attn_pos = self._last_selfattention(img, image_feat), self._last_selfattention(img_pos, image_feat_pos)
-        (code, feats), (code_pos, feats_pos) = run_head_pair(self.cluster1, self.cluster2 if self.proj_type == "nonlinear" else None,
-                                                             image_feat, image_feat_pos, True, bool(self.cfg.dropout), float(self.dropout.p),
-                                                             None, defer_feats_dropout)
-        return (feats, code, attn), (feats_pos, code_pos, attn_pos)
+    def _backbone(self, img, n=1, return_class_feat=False):
+        assert img.shape[2] % self.patch_size == 0 and img.shape[3] % self.patch_size == 0   # :93-94
+        image_feat = self.model(img)
+        if return_class_feat:
+            return image_feat.mean((2, 3), keepdim=True), None
+        return image_feat, self._last_selfattention(img, image_feat)
 
 
 class UnsupervisedSegmenter(nn.Module):

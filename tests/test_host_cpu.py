@@ -21,6 +21,36 @@ def test_library_exports_every_declared_symbol():
         assert hasattr(lib, name), f"{name} declared in include/depthg_corr.h but not exported"
     assert declared == set(_lib.EXPORTS)
     assert lib.dg_version() == _lib.DG_VERSION == 118
+    # every prototype against the binding's signature table: the return type, the parameter count and each parameter's kind
+    # (a miscounted `[vp] * 10` would otherwise only show on a GPU, as a crash)
+    protos = _header_prototypes(header)
+    assert set(protos) == declared == set(_lib.SIGNATURES), "a prototype was not parsed"
+    assert list(protos) == _lib.EXPORTS, "the signature table follows the header's order"
+    returns = {"int": ctypes.c_int, "size_t": ctypes.c_size_t, "const char*": ctypes.c_char_p}
+    scalars = {"int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "uint64_t": ctypes.c_uint64, "float": ctypes.c_float,
+               "size_t": ctypes.c_size_t}
+    for name, (ret, params) in protos.items():
+        restype, argtypes = _lib.SIGNATURES[name]
+        assert restype is returns[ret], f"{name}: declared to return {ret}, bound as {restype.__name__}"
+        assert len(argtypes) == len(params), f"{name}: {len(params)} parameters declared, {len(argtypes)} argtypes bound"
+        fn = getattr(lib, name)
+        assert fn.restype is restype and list(fn.argtypes) == list(argtypes), f"{name}: load() did not apply the table"
+        for k, (param, bound) in enumerate(zip(params, argtypes)):
+            if "*" in param or param.startswith("dg_stream_t"):
+                assert bound is ctypes.c_void_p or issubclass(bound, ctypes._Pointer), f"{name}: parameter {k} `{param}` bound as {bound.__name__}"
+            else:
+                ctype = param.replace("const ", "").split()[0]
+                assert bound is scalars[ctype], f"{name}: parameter {k} `{param}` bound as {bound.__name__}"
+
+
+def _header_prototypes(header):
+    """{name: (return type, [parameter declarations])} of every function the header declares, in its order."""
+    code = re.sub(r"/\*.*?\*/", " ", header, flags=re.S)
+    protos = {}
+    for ret, name, params in re.findall(r"\b(int|size_t|const char\s*\*)\s+(dg_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", code):
+        params = [" ".join(p.split()) for p in params.split(",")]
+        protos[name] = (" ".join(ret.split()).replace(" *", "*"), [] if params == ["void"] else params)
+    return protos
 
 
 def test_descriptor_validation_and_workspace():
