@@ -7,6 +7,7 @@
 #include <cstdlib>
 #include <cstdio>
 #include <cstring>
+#include <mutex>
 #include <optional>
 
 // ---- error reporting: one thread-local message for the whole library (dg_last_error), defined in dg_api_aux.hip

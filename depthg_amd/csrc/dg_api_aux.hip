@@ -2,8 +2,11 @@
 // text, the library's side stream, batch maps / random draws / coordinate samplers, kNN, LHP, fused Adam, ViT attention and linear.
 // Host-side only: argument checks and kernel launches on the caller's stream.
 #include "dg_api.h"
+#include "dg_aux_args.h"
+#include "dg_corr_args.h"     // the samplers of dg_post.hip: super_perms, rand_coords_state, fps
 
 #include <cstdarg>
+#include <map>
 
 // ---- error reporting (dg_api.h)
 thread_local char g_err[512] = "";

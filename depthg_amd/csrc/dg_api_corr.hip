@@ -1,6 +1,8 @@
 // C ABI of the gfx950 DepthG library (include/depthg_corr.h): the correlation loss.  Host-side orchestration only: workspace
 // carving (Plan), job tables, kernel launches on the caller's stream and the library's side stream.
 #include "dg_api.h"
+#include "dg_corr_args.h"
+#include "dg_taps.h"          // dg_taps_record_bytes
 
 // ---- measurement aid: the fused correlation launch's execution span (include/depthg_corr.h dg_prof_main_span)
 static unsigned long long* g_prof_span = nullptr;

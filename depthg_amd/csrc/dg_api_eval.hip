@@ -1,6 +1,9 @@
 // C ABI of the gfx950 DepthG library (include/depthg_corr.h): the probes, evaluation and the dense CRF (dg_probe.hip, dg_eval.hip,
 // dg_crf.hip, dg_metrics.hip).  Host-side only: argument checks and kernel launches on the caller's stream.
 #include "dg_api.h"
+#include "dg_eval_args.h"
+#include "dg_head_args.h"     // the probes (dg_probe.hip)
+#include "dg_aux_args.h"      // dg_launch_confusion (dg_metrics.hip)
 
 extern "C" int dg_confusion_update(const int64_t* preds, const int64_t* target, int64_t count, int32_t n_classes,
                                    int32_t extra_clusters, int64_t* stats, dg_stream_t stream_) {

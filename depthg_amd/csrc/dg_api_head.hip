@@ -1,6 +1,7 @@
 // C ABI of the gfx950 DepthG library (include/depthg_corr.h): the segmentation head (dg_head.hip).  Host-side only: argument
 // checks, workspace carving by the kernels' own plan (dg_head_plan), kernel launches on the caller's stream.
 #include "dg_api.h"
+#include "dg_head_args.h"
 
 static int head_check(int32_t B, int32_t C, int32_t D, int32_t P) {
     if (B < 1 || C < 1 || D < 1 || P < 1) return fail(DG_ERR_INVALID, "bad head dimensions");

@@ -15,7 +15,8 @@
 //                     O^T += V^T P^T       4 x mfma (A = V^T fragment from LDS, B = P rounded to bf16 straight out of the registers)
 //                 The 8-KiB image of the next tile is fetched into registers before the products of this one and stored to the other
 //                 half of a 16-KiB LDS ring after them: one barrier per tile.
-#include "dg_common.h"
+#include "dg_device.h"
+#include "dg_aux_args.h"
 
 #define ATT_HD 64
 #define ATT_TILE 32                 // keys per tile
@@ -23,7 +24,6 @@
 #define ATT_QWG (32 * ATT_WAVES)    // queries per workgroup
 #define ATT_IMG 8192                // bytes of one packed tile image
 
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
 
 __global__ __launch_bounds__(256) void k_attn_pack(const float* __restrict__ qkv, uint8_t* __restrict__ kv, int N, int heads, int tiles) {
     const int tile = blockIdx.x, bh = blockIdx.y, b = bh / heads, head = bh % heads;

@@ -3,7 +3,7 @@
 // One workgroup = NWAVES waves (8 = two per SIMD for the ViT-S widths; more than 256 registers per wave makes
 // hipcc shuttle MFMA operands between the AGPR and VGPR halves, measured slower); each wave keeps RF x 32
 // positions of the stationary operand "R" (normalised feats, bf16) in registers and walks over the streamed
-// operand "S" in tiles of 32 positions.  A tile is one contiguous blob in HBM (dg_common.h) that is DMA'd
+// operand "S" in tiles of 32 positions.  A tile is one contiguous blob in HBM (dg_corr_args.h) that is DMA'd
 // into LDS (global_load_lds_dwordx4) two tiles ahead of the computation; one workgroup barrier per tile.
 // Per 32x32 tile and row fragment:
 //     Yc[s][r] = sum_d Sc[s][d] Rc[r][d]     (KD/16 x v_mfma_f32_32x32x16_f16, fp32 accumulate)
@@ -16,7 +16,8 @@
 //
 // Reference semantics reproduced here: helper() src/modules.py:1231-1254,
 // depth_feature_correlation() :1256-1278 (job kind DG_JOB_DEPTH), norm() :789-790 (backward part).
-#include "dg_common.h"
+#include "dg_device.h"
+#include "dg_corr_args.h"
 #include <cstdlib>
 #include <cstdio>
 
@@ -48,14 +49,7 @@ __device__ __forceinline__ void wait_vmcnt(int n) {   // n is wave-uniform
     }
 }
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 enum { KIND_LANE = 0, KIND_ROW = 1, KIND_DEPTH = 2 };   // centering vector on lanes (R = operand 1) / on tile rows / depth term
-typedef int v4i __attribute__((ext_vector_type(4)));
 #ifndef DG_STAGGER
 #define DG_STAGGER 1
 #endif
@@ -337,9 +331,9 @@ __device__ __forceinline__ void corr_body(const DgCorrArgs& args, const DgJob& j
     //      flight; scheduling fences pin that order (left alone hipcc serialises read -> wait -> MFMA here).
     const int late_prio = (STAG && DG_PRIO == 1 && wid >= NWAVES / 2) ? 1 : 0;   // priority outside the chain
     auto chain = [&](const char* tile, const int f, auto&& between) {
-        auto a_ptr = [&](int st) -> const v4i* {
-            return st < NSF ? reinterpret_cast<const v4i*>(tile + fbase[st % FPER] + (st / FPER) * (FPER * 1024))
-                            : reinterpret_cast<const v4i*>(tile + BL::OFF_C + crow + (st - NSF) * 1024);
+        auto a_ptr = [&](int st) -> const i32x4* {
+            return st < NSF ? reinterpret_cast<const i32x4*>(tile + fbase[st % FPER] + (st / FPER) * (FPER * 1024))
+                            : reinterpret_cast<const i32x4*>(tile + BL::OFF_C + crow + (st - NSF) * 1024);
         };
         Yc[f] = f32x16{};
         if (KIND == KIND_LANE) {          // start the feature accumulator at c0_lane: fd'' - shift comes out of the chain
@@ -348,12 +342,12 @@ __device__ __forceinline__ void corr_body(const DgCorrArgs& args, const DgJob& j
         } else {
             Yf[f] = f32x16{};
         }
-        v4i ra[PF], rb[2];
+        i32x4 ra[PF], rb[2];
 #pragma unroll
         for (int i = 0; i < PF; ++i) if (i < NS) ra[i] = *a_ptr(i);
         if (!RCREG) {
 #pragma unroll
-            for (int k = 0; k < 2; ++k) rb[k] = *reinterpret_cast<const v4i*>(rc_lds + f * RCB + crow + k * 1024);
+            for (int k = 0; k < 2; ++k) rb[k] = *reinterpret_cast<const i32x4*>(rc_lds + f * RCB + crow + k * 1024);
         }
         __builtin_amdgcn_sched_barrier(0);
         // the wave in its MFMA chain wins the issue port: an MFMA needs it 8 cycles in 32, the partner's epilogue VALU
@@ -361,14 +355,14 @@ __device__ __forceinline__ void corr_body(const DgCorrArgs& args, const DgJob& j
         if (STAG) __builtin_amdgcn_s_setprio(2);
 #pragma unroll
         for (int st = 0; st < NS; ++st) {
-            const v4i cur = ra[st % PF];
+            const i32x4 cur = ra[st % PF];
             if (st < NSF) {
                 Yf[f] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, cur), Rf[f][st < NSF ? st : 0], Yf[f], 0, 0, 0);
             } else {
                 const int k = st - NSF;
                 const f16x8 b = RCREG ? Rc[k] : __builtin_bit_cast(f16x8, rb[k & 1]);
                 Yc[f] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, cur), b, Yc[f], 0, 0, 0);
-                if (!RCREG && k + 2 < NKC) rb[k & 1] = *reinterpret_cast<const v4i*>(rc_lds + f * RCB + crow + (k + 2) * 1024);
+                if (!RCREG && k + 2 < NKC) rb[k & 1] = *reinterpret_cast<const i32x4*>(rc_lds + f * RCB + crow + (k + 2) * 1024);
             }
             if (st + PF < NS) ra[st % PF] = *a_ptr(st + PF);
             between(st);
@@ -441,9 +435,9 @@ __device__ __forceinline__ void corr_body(const DgCorrArgs& args, const DgJob& j
                     // non-temporal: the tiles are read by the NEXT kernel only; keeping them out of the way leaves the L2 to
                     // the operand blobs this kernel streams over and over
                     // tile = [2 k-steps][64 lanes][16 B]: every store instruction writes one contiguous KiB
-                    v4i* g = reinterpret_cast<v4i*>(Gout) + (((size_t)n * ntiles_all + t) * ntiles_all + rtile0 + f) * 128 + lane;     // [image][S tile][R tile]
-                    __builtin_nontemporal_store(__builtin_bit_cast(v4i, ga[f][0]), g);
-                    __builtin_nontemporal_store(__builtin_bit_cast(v4i, ga[f][1]), g + 64);
+                    i32x4* g = reinterpret_cast<i32x4*>(Gout) + (((size_t)n * ntiles_all + t) * ntiles_all + rtile0 + f) * 128 + lane;     // [image][S tile][R tile]
+                    __builtin_nontemporal_store(__builtin_bit_cast(i32x4, ga[f][0]), g);
+                    __builtin_nontemporal_store(__builtin_bit_cast(i32x4, ga[f][1]), g + 64);
                 }
         }
         if (GRAD) {
@@ -735,14 +729,14 @@ __device__ __forceinline__ void gs_depth_block(const DgGsArgs& a, const uint32_t
     const char* const img = a.dep_op + (size_t)n * ntiles * BL::BYTES;
     const float* const nz = a.dep_nz + (size_t)n * a.Ppad;
     // stationary fragment: code rows of this wave's tile as B operands, its indicators per lane
-    v4i Rc[NKD];
+    i32x4 Rc[NKD];
     const char* Rb = img + (size_t)(act ? rtile : 0) * BL::BYTES + BL::OFF_C;
 #pragma unroll
-    for (int k = 0; k < NKD; ++k) Rc[k] = *reinterpret_cast<const v4i*>(Rb + ((2 * k + h) * 32 + r) * 16);
+    for (int k = 0; k < NKD; ++k) Rc[k] = *reinterpret_cast<const i32x4*>(Rb + ((2 * k + h) * 32 + r) * 16);
     // (k-steps that are all channel padding: zero HERE - with k_corr2's FOLD the operand-1 blobs carry the intra row means in
     //  the first such k-step of the C part, dg_corr2.hip; a zero stationary fragment makes the product blind to it)
 #pragma unroll
-    for (int k = 0; k < NKD; ++k) if (16 * k >= a.D) Rc[k] = v4i{0, 0, 0, 0};
+    for (int k = 0; k < NKD; ++k) if (16 * k >= a.D) Rc[k] = i32x4{0, 0, 0, 0};
     const float nz_lane = act ? nz[rtile * 32 + r] : 0.f;
     const float c0 = -a.dep_shift;
     f32x16 acc[NDF];
@@ -750,7 +744,7 @@ __device__ __forceinline__ void gs_depth_block(const DgGsArgs& a, const uint32_t
     for (int d = 0; d < NDF; ++d) acc[d] = f32x16{};
     float lsum = 0.f;
     // tile staging: thread t owns pieces t and t + NTH of the C/P parts, threads 0..7 also four indicators each
-    v4i st0, st1 = v4i{0, 0, 0, 0};
+    i32x4 st0, st1 = i32x4{0, 0, 0, 0};
     f32x4 stz = f32x4{0.f, 0.f, 0.f, 0.f};
     // XM - exact clamp masks of the intra pair-set (zero_clamp, no upper bound; <= 8 tiles): the words of this lane's R position
     // against every S tile, loaded up front and waited for once.  The block without them sits at k_gs's 128 registers (9 spilled);
@@ -769,14 +763,14 @@ __device__ __forceinline__ void gs_depth_block(const DgGsArgs& a, const uint32_t
     }
     auto fetch = [&](int t) {
         const char* src = img + (size_t)t * BL::BYTES + BL::OFF_C;
-        st0 = *reinterpret_cast<const v4i*>(src + tid * 16);
-        if (tid + NTH < NPC) st1 = *reinterpret_cast<const v4i*>(src + (tid + NTH) * 16);
+        st0 = *reinterpret_cast<const i32x4*>(src + tid * 16);
+        if (tid + NTH < NPC) st1 = *reinterpret_cast<const i32x4*>(src + (tid + NTH) * 16);
         if (tid < 8) stz = *reinterpret_cast<const f32x4*>(nz + t * 32 + tid * 4);
     };
     auto stash = [&](int b) {
         char* tile = smem + b * TILE;
-        *reinterpret_cast<v4i*>(tile + 256 + tid * 16) = st0;
-        if (tid + NTH < NPC) *reinterpret_cast<v4i*>(tile + 256 + (tid + NTH) * 16) = st1;
+        *reinterpret_cast<i32x4*>(tile + 256 + tid * 16) = st0;
+        if (tid + NTH < NPC) *reinterpret_cast<i32x4*>(tile + 256 + (tid + NTH) * 16) = st1;
         if (tid < 8) *reinterpret_cast<f32x4*>(tile + tid * 16) = stz;
     };
     fetch(0);
@@ -937,14 +931,14 @@ __device__ __forceinline__ void gs_body(const DgGsArgs& a, const uint32_t* dep_m
     // ds_read_b64_tr_b16 addressing: lane l of a 16-lane group supplies row (l>>2)&3 and chunk 4*((l>>4)&1) + (l&3) of the block
     const int tr_a = (lane >> 2) & 3, tr_c = 4 * ((lane >> 4) & 1) + (lane & 3);
     typedef __attribute__((ext_vector_type(4))) short s16x4;
-    const v4i* Gbase = reinterpret_cast<const v4i*>(J.G) + ((size_t)n * ntS + st) * ntS * 128 + lane;      // [image][S tile][R tile]: one sequential 2 KiB-per-step stream per wave
-    const size_t gstride = 128;                             // v4i per R tile step
-    auto load_g = [&](int rt, v4i (&g)[2]) {
-        const v4i* gp = Gbase + (size_t)rt * gstride;
+    const i32x4* Gbase = reinterpret_cast<const i32x4*>(J.G) + ((size_t)n * ntS + st) * ntS * 128 + lane;      // [image][S tile][R tile]: one sequential 2 KiB-per-step stream per wave
+    const size_t gstride = 128;                             // i32x4 per R tile step
+    auto load_g = [&](int rt, i32x4 (&g)[2]) {
+        const i32x4* gp = Gbase + (size_t)rt * gstride;
         g[0] = __builtin_nontemporal_load(gp);
         g[1] = __builtin_nontemporal_load(gp + 64);
     };
-    v4i gring[3][2];
+    i32x4 gring[3][2];
 #pragma unroll
     for (int k = 0; k < 3; ++k)
         if (k < nt) load_g(k, gring[k]);
@@ -954,7 +948,7 @@ __device__ __forceinline__ void gs_body(const DgGsArgs& a, const uint32_t* dep_m
             const int rt = rt0 + k;
             if (rt < nt) {
                 // own scratch: no cross-wave hazard, so the transposition writes may start before the barrier
-                const v4i g0 = gring[k][0], g1 = gring[k][1];
+                const i32x4 g0 = gring[k][0], g1 = gring[k][1];
                 const uint32_t w[8] = {(uint32_t)g0[0], (uint32_t)g0[1], (uint32_t)g0[2], (uint32_t)g0[3],
                                        (uint32_t)g1[0], (uint32_t)g1[1], (uint32_t)g1[2], (uint32_t)g1[3]};
                 // [p][q] image, 64-byte rows of 8 chunks (4 q each), chunk index XOR-ed with p&7: the lane (p = r, h) owns

@@ -23,12 +23,12 @@
 // Round 4: the workgroups are PERSISTENT (one per CU, walking the work items).  BUILD THIS FILE WITH `-mllvm -disable-machine-licm`
 // (the Makefile's rule for dg_corr2.o, scripts/build_variant.sh, the audit in tests/test_host_cpu.py): without it hipcc hoists
 // constants of the item body out of the walk and spills scalar registers into VGPR lanes (correct, slower).
-#include "dg_common.h"
+#include "dg_device.h"
+#include "dg_corr_args.h"
 #include <utility>
 #include <cstdio>
 #include <cstdlib>
 
-typedef int v4i_t __attribute__((ext_vector_type(4)));
 #define C2_RED_BYTES 256   // behind the tile buffers: the block-end reduction's [8 fragment slots][4] dwords + [8] output pointers
 #ifndef C2_PF
 #define C2_PF 8            // LDS fragment reads in flight ahead of the MFMA that consumes them (8, or 12 in developer builds of the exact-mask form)
@@ -43,16 +43,16 @@ __device__ __forceinline__ void sfor(F&& f) { sfor_impl(f, std::make_integer_seq
 template <int I> __device__ __forceinline__ void agpr_load16(const void* p) {      // a[4I..4I+3] <- 16 bytes at p
     asm volatile("global_load_dwordx4 a[%c1:%c2], %0, off" :: "v"(p), "n"(4 * I), "n"(4 * I + 3) : "memory");
 }
-template <int I> __device__ __forceinline__ void mfma_fd(f32x16& acc, const v4i_t& a) {     // acc += A x Rf (bf16, B = a[4I..4I+3])
+template <int I> __device__ __forceinline__ void mfma_fd(f32x16& acc, const i32x4& a) {     // acc += A x Rf (bf16, B = a[4I..4I+3])
     asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, a[%c2:%c3], %0" : "+v"(acc) : "v"(a), "n"(4 * I), "n"(4 * I + 3));
 }
-__device__ __forceinline__ void mfma_h(f32x16& acc, const v4i_t& a, const v4i_t& b) {         // acc += A x B (f16)
+__device__ __forceinline__ void mfma_h(f32x16& acc, const i32x4& a, const i32x4& b) {         // acc += A x B (f16)
     asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, %0" : "+v"(acc) : "v"(a), "v"(b));
 }
-__device__ __forceinline__ void mfma_h0(f32x16& acc, const v4i_t& a, const v4i_t& b) {        // acc = A x B (f16)
+__device__ __forceinline__ void mfma_h0(f32x16& acc, const i32x4& a, const i32x4& b) {        // acc = A x B (f16)
     asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, 0" : "=&v"(acc) : "v"(a), "v"(b));
 }
-template <int X> __device__ __forceinline__ void mfma_h_acc(const v4i_t& a, const v4i_t& b) { // a[X..X+15] += A x B (f16); A must not be fresh from the VALU (2 wait states)
+template <int X> __device__ __forceinline__ void mfma_h_acc(const i32x4& a, const i32x4& b) { // a[X..X+15] += A x B (f16); A must not be fresh from the VALU (2 wait states)
     asm volatile("v_mfma_f32_32x32x16_f16 a[%c2:%c3], %0, %1, a[%c2:%c3]" :: "v"(a), "v"(b), "n"(X), "n"(X + 15));
 }
 template <int X> __device__ __forceinline__ float agpr_read(void) {
@@ -109,23 +109,23 @@ __device__ __forceinline__ void declare_agprs(void) {
 
 // ---- hand-placed loop instructions (nothing in the tile loop is left to hipcc's own wait insertion)
 typedef double acc_t __attribute__((ext_vector_type(8)));       // a 32x32 accumulator as eight 64-bit halves (v_mov_b64 initialisation)
-template <int OFF> __device__ __forceinline__ void lds_rd(v4i_t& d, uint32_t addr) {
+template <int OFF> __device__ __forceinline__ void lds_rd(i32x4& d, uint32_t addr) {
     asm volatile("ds_read_b128 %0, %1 offset:%c2" : "=v"(d) : "v"(addr), "n"(OFF));
 }
 template <int N> __device__ __forceinline__ void wait_lgkm(void) { asm volatile("s_waitcnt lgkmcnt(%c0)" :: "n"(N) : "memory"); }
-template <int I> __device__ __forceinline__ void mfma_fd8(acc_t& acc, const v4i_t& a) {
+template <int I> __device__ __forceinline__ void mfma_fd8(acc_t& acc, const i32x4& a) {
     asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, a[%c2:%c3], %0" : "+v"(acc) : "v"(a), "n"(4 * I), "n"(4 * I + 3));
 }
 // first MFMA of an fd chain: the accumulator STARTS at c (sixteen copies of the lane's c0, kept in registers for the whole block) -
 // no per-tile re-initialisation of the accumulator by sixteen 64-bit moves (round 4: hipcc gathered them into bursts of eight in
 // one MFMA gap)
-template <int I> __device__ __forceinline__ void mfma_fd8_from(acc_t& acc, const v4i_t& a, const acc_t& c) {
+template <int I> __device__ __forceinline__ void mfma_fd8_from(acc_t& acc, const i32x4& a, const acc_t& c) {
     asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, a[%c3:%c4], %2" : "=&v"(acc) : "v"(a), "v"(c), "n"(4 * I), "n"(4 * I + 3));
 }
-__device__ __forceinline__ void mfma_h8(acc_t& acc, const v4i_t& a, const v4i_t& b) {
+__device__ __forceinline__ void mfma_h8(acc_t& acc, const i32x4& a, const i32x4& b) {
     asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, %0" : "+v"(acc) : "v"(a), "v"(b));
 }
-__device__ __forceinline__ void mfma_h80(acc_t& acc, const v4i_t& a, const v4i_t& b) {
+__device__ __forceinline__ void mfma_h80(acc_t& acc, const i32x4& a, const i32x4& b) {
     asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, 0" : "=&v"(acc) : "v"(a), "v"(b));
 }
 // one 1-KiB LDS-DMA piece: M0 = LDS destination (written in this statement), the vector add is the wait state between the M0
@@ -207,15 +207,6 @@ __device__ __forceinline__ int epi2m_b(int o, int m0, int m1, const uint32_t lo1
                  "v_and_b32 %0, %0, %1"
                  : "+v"(o), "+v"(m0) : "v"(m1), "s"(lo16));
     return o;
-}
-
-// sum over the 64 lanes through DPP row operations (dg_common.h half_sum) instead of six LDS-crossbar shuffles
-__device__ __forceinline__ float wave_sum_dpp(float v) {
-#define DG_DPP_ADD2(ctrl, rmask) v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), ctrl, rmask, 0xf, false))
-    DG_DPP_ADD2(0x111, 0xf); DG_DPP_ADD2(0x112, 0xf); DG_DPP_ADD2(0x114, 0xf); DG_DPP_ADD2(0x118, 0xf);
-    DG_DPP_ADD2(0x142, 0xa);
-#undef DG_DPP_ADD2
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 31)) + __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
 }
 
 // NKF feature k-steps (C = 16 NKF), KD = 16 NKD padded code width, NKC code k-steps that are not all padding
@@ -461,7 +452,7 @@ __global__ __launch_bounds__(256) void k_corr2(const DgCorrArgs args_k) {
     // (NOCD - the exact-mask form, which has no cd chain: these fragments are needed at the block end only, and are loaded THERE by
     //  ordinary loads.  As asm loads up here with no reader inside the loop, hipcc - for which an asm statement's output exists the
     //  moment the statement ends - copied them to other registers before they had landed: NaN loss sums, round 6.)
-    v4i_t Rc[RF][NKC];                                    // B operands of the cd chain: granule 2k + h of row r
+    i32x4 Rc[RF][NKC];                                    // B operands of the cd chain: granule 2k + h of row r
     const char* rc_lane[RF];                              // (NOCD: this lane's address of granule h, kept in a vector register pair - as
                                                           //  scalar pointers across the tile loop they spilled into VGPR lanes)
 #pragma unroll
@@ -527,15 +518,15 @@ __global__ __launch_bounds__(256) void k_corr2(const DgCorrArgs args_k) {
     // per-lane LDS byte addresses of the fragments of the current tile
     const int crow = (h * 32 + r) * 16;
     uint32_t va0 = smem_a + fb0, va1 = smem_a + fb1, vc = smem_a + BL::OFF_C + crow, vp = smem_a + BL::OFF_P + (h * KD + r) * 16;
-    auto rd_step = [&](auto ST, v4i_t& d) {               // A fragment of chain step ST (feature k-steps, then code k-steps)
+    auto rd_step = [&](auto ST, i32x4& d) {               // A fragment of chain step ST (feature k-steps, then code k-steps)
         constexpr int st = ST.value;
         if constexpr (st < NKF) { if constexpr (st & 1) lds_rd<(st >> 1) * 2048>(d, va1); else lds_rd<(st >> 1) * 2048>(d, va0); }
         else lds_rd<(NOCD ? NKC : st - NKF) * 1024>(d, vc);          // (XM: the only step behind the feature steps is FOLD's, code k-step NKC)
     };
 
     acc_t Yf[RF], Yc[RF];
-    v4i_t ga[RF][2];                                     // -G as fp16 A fragments: k-step sp holds accumulator elements 8sp..8sp+7
-    v4i_t ra[PF], bP[2 * NDF];
+    i32x4 ga[RF][2];                                     // -G as fp16 A fragments: k-step sp holds accumulator elements 8sp..8sp+7
+    i32x4 ra[PF], bP[2 * NDF];
 
     BL_T(1);
     // tile 0 landed (everything older - the small inputs, the fragment loads of fragment 0, the code fragments - is complete as
@@ -608,16 +599,16 @@ __global__ __launch_bounds__(256) void k_corr2(const DgCorrArgs args_k) {
     (void)epi_pair;
     // per-fragment base of the G tiles [image][S tile t][R tile]: resolved HERE - a kernel-argument (scalar) load inside the
     // tile loop would have to be waited for with lgkmcnt(0), i.e. together with every LDS read in flight
-    v4i_t* gbase[RF];
+    i32x4* gbase[RF];
 #pragma unroll
     for (int f = 0; f < RF; ++f)
-        gbase[f] = reinterpret_cast<v4i_t*>(args.jobs[fj[f]].Gout) + (fo[f] ? (size_t)0 : ((size_t)fn[f] * ntiles * ntiles + (act[f] ? ft[f] : 0)) * 128) + lane;
+        gbase[f] = reinterpret_cast<i32x4*>(args.jobs[fj[f]].Gout) + (fo[f] ? (size_t)0 : ((size_t)fn[f] * ntiles * ntiles + (act[f] ? ft[f] : 0)) * 128) + lane;
     const size_t gstep = (size_t)ntiles * 128;
     // (a folded fragment has no reader for its G tiles; its stores stay in the instruction stream - the counted vmcnt waits of the
     //  tile barrier count them - but all go to the first 2 KiB of the pair-set's buffer with the default cache policy: L2 traffic)
     size_t gstepb[RF];
 #pragma unroll
-    for (int f = 0; f < RF; ++f) gstepb[f] = fo[f] ? (size_t)0 : gstep * sizeof(v4i_t);
+    for (int f = 0; f < RF; ++f) gstepb[f] = fo[f] ? (size_t)0 : gstep * sizeof(i32x4);
     // running store addresses: a scalar base per fragment (advanced by scalar adds; the tile index times the tile stride as 64-bit scalar
     // multiplies in front of every store cost three s_mul and two adds each) + ONE 32-bit lane offset for every store - half the address
     // bytes of the vaddr form and no 64-bit VALU add (round 6: -0.5 % of the kernel, -2 us of the step).  gsb[0] points at S tile t,
@@ -733,7 +724,7 @@ __global__ __launch_bounds__(256) void k_corr2(const DgCorrArgs args_k) {
                     if constexpr (((st - 10) & 1) == 0) dma_setup<k * 4096>(dst2, dma_voff, dtmp); else dma_go(dtmp, sb2);
                 }
                 if constexpr (!SPLIT_DMA && st >= 10 && st < 10 + PIECES) dma_piece<(st - 10) * 4096>(dst2, dma_voff, sb2);
-                if constexpr (FRUN && ACT0 && st == NS - 3) ga[0][0] = v4i_t{fo[0] ? fold_w : 0, 0, 0, 0};
+                if constexpr (FRUN && ACT0 && st == NS - 3) ga[0][0] = i32x4{fo[0] ? fold_w : 0, 0, 0, 0};
                 if constexpr (ACT1 && st == NS - 1) { if (t > 0) g_store(1, 0, t - 1); }
                 __builtin_amdgcn_sched_barrier(0);
             });
@@ -764,7 +755,7 @@ __global__ __launch_bounds__(256) void k_corr2(const DgCorrArgs args_k) {
                     if constexpr (st >= 2 && st < 18) epi_half(std::integral_constant<int, 0>{}, std::integral_constant<int, st - 2>{});
                     if constexpr (st == 11) g_store(0, 0, t);             // (pairs 0..3 are complete behind gap 9)
                     if constexpr (st == 19) g_store(0, 1, t);             // (pairs 4..7 behind gap 17)
-                    if constexpr (FRUN && ACT1 && st == 16) ga[1][0] = v4i_t{fo[1] ? fold_w : 0, 0, 0, 0};
+                    if constexpr (FRUN && ACT1 && st == 16) ga[1][0] = i32x4{fo[1] ? fold_w : 0, 0, 0, 0};
                     if constexpr (st >= NS - 9 && st < NS - 9 + 2 * NDF) {      // B fragments of the gradient products (shared by both fragments)
                         constexpr int q = st - (NS - 9), sp = q / NDF, d = q % NDF;
                         lds_rd<d * 512 + sp * (2 * KD * 16)>(bP[q], vp);
@@ -845,7 +836,7 @@ __global__ __launch_bounds__(256) void k_corr2(const DgCorrArgs args_k) {
         asm volatile("" : "+v"(Yc[1]));
     }
 #pragma unroll
-    for (int q = 0; q < 2 * NDF; ++q) bP[q] = v4i_t{0, 0, 0, 0};
+    for (int q = 0; q < 2 * NDF; ++q) bP[q] = i32x4{0, 0, 0, 0};
 #ifdef C2_BLOCKLOG
     // (e[13], e[14]: the shader clock - s_memtime - at the two ends of the tile loop, next to the 100-MHz wall clock in e[3], e[4]:
     //  cycles / wall time = the clock this CU HELD while it ran the loop, scripts/held_clock.py)
@@ -879,7 +870,7 @@ __global__ __launch_bounds__(256) void k_corr2(const DgCorrArgs args_k) {
                 // (a GLOBAL-address-space load: through the generic pointer hipcc emitted flat_load_dwordx4 here and the fragments came
                 //  back wrong - NaN loss sums with correct gradients, round 6 - as they did from asm loads at the top of the block that
                 //  nothing inside the tile loop named; scripts/lab_r06/lab_r06_nan.py, profiles/r06_xm_block_end_loads.txt)
-                Rc[f][k] = *reinterpret_cast<const v4i_t __attribute__((address_space(1)))*>(reinterpret_cast<uintptr_t>(rc_lane[f] + k * 1024));
+                Rc[f][k] = *reinterpret_cast<const i32x4 __attribute__((address_space(1)))*>(reinterpret_cast<uintptr_t>(rc_lane[f] + k * 1024));
     }
     float lsumf[RF] = {0.f, 0.f}, csumf[RF] = {0.f, 0.f};
     const bool half_tiles = args.half_tiles != 0;
@@ -890,13 +881,13 @@ __global__ __launch_bounds__(256) void k_corr2(const DgCorrArgs args_k) {
         float* const dRj = dRp[f];
         float* base = dRj ? dRj + ((size_t)fn[f] * ntiles + ft[f]) * (32 * DP) + lane * 4 : nullptr;
         // x in the layout of dR (rows in registers, channel on the lane) = X * I (selector fragments), as in k_corr_main
-        v4i_t sel[2];
+        i32x4 sel[2];
 #pragma unroll
         for (int sI = 0; sI < 2; ++sI) {
             f16x8 s8;
 #pragma unroll
             for (int j = 0; j < 8; ++j) s8[j] = (8 * h + j + 16 * sI == r) ? (_Float16)1.f : (_Float16)0.f;
-            sel[sI] = __builtin_bit_cast(v4i_t, s8);
+            sel[sI] = __builtin_bit_cast(i32x4, s8);
         }
         float lsum = 0.f, csum = 0.f;
         sfor<NDF>([&](auto DI) {
@@ -921,7 +912,7 @@ __global__ __launch_bounds__(256) void k_corr2(const DgCorrArgs args_k) {
                         for (int e = 0; e < 8; ++e) o[e] = (_Float16)v[8 * sp + e];
                         // (ordinary stores: non-temporal ones cost k_combine_out, which reads these tiles 80 us later, 3 us - 34.0 -> 31.1 - and
                         //  save this kernel 1.3)
-                        *reinterpret_cast<v4i_t*>(hb + sp * 512) = __builtin_bit_cast(v4i_t, o);
+                        *reinterpret_cast<i32x4*>(hb + sp * 512) = __builtin_bit_cast(i32x4, o);
                     }
                 } else {
 #pragma unroll

@@ -24,7 +24,8 @@
 //   slice            fused with the norms (folded into the splat and slice weights), alpha = 1 / (1 + 2^-d), the Potts weights,
 //                    -U and the per-group softmax: one kernel per iteration (k_crf_step), which writes the next Q
 // Every sum runs in an order fixed by the image's data alone, so two identical calls give identical bits, whatever the chunking.
-#include "dg_common.h"
+#include "dg_device.h"
+#include "dg_eval_args.h"
 #include "dg_taps.h"          // resize_taps
 
 #include <cmath>
@@ -40,7 +41,6 @@ __device__ __forceinline__ float crf_sub(const float a, const float b) { return 
 #define CRF_THREADS 256
 #define CRF_TILE 64           // splat: sorted contributors per partial sum
 #define CRF_CLIP_LO 1e-5f     // pydensecrf.utils.unary_from_softmax: -log(clip(p, 1e-5, 1))
-#define CRF_NORM_EPS 1e-12f   // F.normalize default eps (src/modules.py:664-665)
 
 // UnNormalize (src/utils.py:132-136) then to_pil_image's mul(255).byte(): two fp32 roundings, then one more, then truncation.
 // Values outside [0, 255] (undefined in the reference's byte()) are clamped.
@@ -688,7 +688,7 @@ __global__ __launch_bounds__(CRF_THREADS) void k_seg_unary(const DgSegArgs a, co
         const float v = crf_blend(v00, v01, v10, v11, lx, ly);
         ss = fmaf(v, v, ss);
     }
-    const float scl = alpha / fmaxf(sqrtf(ss), CRF_NORM_EPS);
+    const float scl = alpha / fmaxf(sqrtf(ss), DG_EPS_NORM_DEFAULT);
     const float* s00 = a.scores + ((size_t)b * hw + q00) * Kp, *s01 = a.scores + ((size_t)b * hw + q01) * Kp;
     const float* s10 = a.scores + ((size_t)b * hw + q10) * Kp, *s11 = a.scores + ((size_t)b * hw + q11) * Kp;
     float* ub = U + (size_t)b * C * HW + pix;

@@ -1,7 +1,8 @@
 // The two device-wide primitives of the dense-CRF lattice build (dg_crf.hip): a stable LSD radix sort of the packed vertex keys with
 // their entry numbers, and an inclusive integer scan of the new-key flags - rocPRIM's header-only implementations, in a unit of their
 // own.  Both results are unique (a stable sort, an integer sum), so they do not depend on how the work is scheduled.
-#include "dg_common.h"
+#include "dg_device.h"
+#include "dg_eval_args.h"
 
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>

@@ -10,13 +10,13 @@
 // persistent block (one block per CU); integer sums, so the matrices do not depend on the order.
 // Every blend is an explicit fmaf of an explicit product: left to fp-contract, hipcc fuses some lanes of a vector and not others,
 // and two identical score rows (duplicated centres or probe rows, a zero code map) would no longer tie exactly.
-#include "dg_common.h"
+#include "dg_device.h"
+#include "dg_eval_args.h"
 #include "dg_taps.h"          // resize_taps
 
 #include <map>
 #include <mutex>
 
-#define SEG_NORM_EPS 1e-12f   // F.normalize default eps (src/modules.py:664-665)
 #define SP_THREADS 256        // k_seg_project: positions per block
 #define SP_KC 16              // ... score rows per block (a multiple of 4: float4 stores)
 #define SS_THREADS 256        // k_seg_score
@@ -45,9 +45,8 @@ __global__ __launch_bounds__(SP_THREADS) void k_seg_project(const DgSegArgs a) {
         if (kp < n4 || kp - n4 >= m) continue;                       // (wave-uniform)
         float s = 0.f;
         for (int d = lane; d < D; d += 64) { const float v = wsm[d * SP_KC + r]; s = fmaf(v, v, s); }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-        const float nrm = fmaxf(sqrtf(s), SEG_NORM_EPS);
+        s = wave_sum(s);
+        const float nrm = fmaxf(sqrtf(s), DG_EPS_NORM_DEFAULT);
         for (int d = lane; d < D; d += 64) wsm[d * SP_KC + r] = wsm[d * SP_KC + r] / nrm;
     }
     __syncthreads();

@@ -9,7 +9,8 @@
 // Backward (the ViT is frozen: gradients for the six head tensors only): k_head_dh (d hidden from d code, ReLU mask), k_head_wgrad
 // (the three weight gradients: products over all positions of the batch, split over blocks, partial sums reduced in a fixed order),
 // k_head_rowsum (bias gradients).  No floating-point atomics: results are bit-reproducible.
-#include "dg_common.h"
+#include "dg_device.h"
+#include "dg_head_args.h"
 #include <type_traits>
 #include <cstdio>
 #include <cstdlib>
@@ -45,7 +46,6 @@ __device__ __forceinline__ bf16x8 tr_frag(const char* img, const int rowb, const
 // first k of element block u (0: elements 0..3, 1: elements 4..7) of a lane's fragment in the order tr_frag delivers
 __device__ __forceinline__ int frag_k_order(const int lane, const int u) { return 8 * (lane >> 4) + 4 * (u ^ ((lane >> 4) & 1)); }
 
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 // Raw A fragment from bf16 weights W[row][kbase + 8g .. + 7]: one 16-byte load from a clamped (always valid) address.  K is a
 // multiple of 8.  NO select on the loaded value: a VALU operation on it right behind the load makes hipcc wait for the load where it
 // is issued - the k-step-ahead prefetch of the GEMM loops then overlaps nothing (2.0 k cycles per k-step against 0.9 k of MFMAs).
@@ -64,7 +64,7 @@ __device__ __forceinline__ bf16x8 wfrag(u32x4 v, const u32x4 keep, const int lan
     return __builtin_bit_cast(bf16x8, v);
 }
 
-// fp32 parameters -> bf16 copies for the MFMA kernels (DgHeadWeightLayout, dg_common.h): w1 (D,C), w2a (C,C), w2b (D,C) fragment-major
+// fp32 parameters -> bf16 copies for the MFMA kernels (DgHeadWeightLayout, dg_head_args.h): w1 (D,C), w2a (C,C), w2b (D,C) fragment-major
 // for the forward, and w2b transposed (C, DP) row-major with DP = D rounded up to 32 (zero padded) for the backward's d hidden product
 __global__ __launch_bounds__(256) void k_head_prep(const float* __restrict__ w1, const float* __restrict__ w2a, const float* __restrict__ w2b,
                                                    __bf16* __restrict__ scratch, int C, int D, int DP) {
@@ -1298,7 +1298,7 @@ static bool dg_head_wgrad_one_pass(int M, int N, int M2, int P) {
     return M > 256 && M <= 384 && M2 > 0 && M2 <= 128 && (P & 7) == 0;
 }
 
-// ---- the backward's plan (DgHeadPlan, dg_common.h): splits, workspace and the route of every launch, for the launchers and dg_api_head.hip
+// ---- the backward's plan (DgHeadPlan, dg_head_args.h): splits, workspace and the route of every launch, for the launchers and dg_api_head.hip
 static int head_splits(int32_t B, int32_t M, int32_t N, int32_t P, int32_t M2 = 0) {     // (M2: a second product in the same launch)
     const int steps = B * ((P + 31) / 32);
     if (dg_head_wgrad_one_pass(M, N, M2, P) && steps >= 8) {

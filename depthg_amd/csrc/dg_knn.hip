@@ -6,12 +6,13 @@
 //   one ordered compaction collects those plus the first ties in index order, a bitonic sort orders the k winners.
 // Output order: value descending, ties by ascending index (torch.topk leaves the tie order unspecified).
 // One block per row, 256 threads.
-#include "dg_common.h"
+#include "dg_device.h"
+#include "dg_aux_args.h"
 
 #define TOPK_THREADS 256
 #define TOPK_MAXK 64
 
-__device__ __forceinline__ unsigned int topk_key(float x) {          // larger float <-> larger key
+__device__ __forceinline__ unsigned int topk_key(float x) {          // larger float <-> larger key: dg_device.h dg_float_key in other operations (other instructions)
     const unsigned int u = __float_as_uint(x);
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }

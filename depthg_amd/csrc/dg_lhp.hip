@@ -10,10 +10,11 @@
 // the forward stored - no neighbour lists, no atomics, fixed summation order.
 //   k_lhp_points      (B,1,H,W) -> points (B,3,P), same arithmetic as the FPS sampler (explicit float32 operations)
 //   k_lhp_propagate   forward (BWD = false) / backward (BWD = true); grid (ceil(P/4), B), block 256 = 4 waves
-#include "dg_common.h"
+#include "dg_device.h"
+#include "dg_aux_args.h"
 
 // every float operation below is the reference's (numpy / torch CPU) operation, one rounding each: products that feed an
-// addition go through dg_mul_rn (dg_common.h) - the __f*_rn intrinsics and the fp-contract pragma alone do not stop hipcc from
+// addition go through dg_mul_rn (dg_device.h) - the __f*_rn intrinsics and the fp-contract pragma alone do not stop hipcc from
 // fusing a*b+c
 
 #define LHP_THREADS 256
@@ -39,17 +40,6 @@ __global__ __launch_bounds__(LHP_THREADS) void k_lhp_points(const float* __restr
 
 // correctly rounded float32 square root (through double: exact for sqrt), whatever the float32 sqrt lowering is
 __device__ __forceinline__ float lhp_sqrt(float x) { return (float)sqrt((double)x); }
-
-__device__ __forceinline__ float lhp_wave_min(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o, 64));
-    return v;
-}
-__device__ __forceinline__ float lhp_wave_max(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-    return v;
-}
 
 // NJ = ceil(P / 64) rounded up to the template: every lane owns the partners lane + 64 j
 template <int NJ, bool BWD>
@@ -79,7 +69,7 @@ __global__ __launch_bounds__(LHP_THREADS) void k_lhp_propagate(const float* __re
                 mn = fminf(mn, dn[j]); mx = fmaxf(mx, dn[j]);
             }
         }
-        mn = lhp_wave_min(mn); mx = lhp_wave_max(mx);
+        mn = wave_min(mn); mx = wave_max(mx);
         const float range = __fsub_rn(mx, mn);
 #pragma unroll
         for (int j = 0; j < NJ; ++j) if (lane + 64 * j < P) dn[j] = __fdiv_rn(__fsub_rn(dn[j], mn), range);
@@ -94,7 +84,7 @@ __global__ __launch_bounds__(LHP_THREADS) void k_lhp_propagate(const float* __re
 #pragma unroll
             for (int j = 0; j < NJ; ++j)
                 if (!((gone >> j) & 1ull) && dn[j] < best) { best = dn[j]; bj = j; }
-            const float wmin = lhp_wave_min(best);
+            const float wmin = wave_min(best);
             const unsigned long long owners = __ballot(best == wmin && bj >= 0);
             if (owners == 0ull) break;                                    // (NaN rows: nothing comparable is left)
             if (lane == __ffsll((long long)owners) - 1) gone |= 1ull << bj;
@@ -156,18 +146,6 @@ __global__ __launch_bounds__(LHP_THREADS) void k_lhp_propagate(const float* __re
 // heads x larger); the Original variants keep their nine neighbour weights per row.
 enum { LHP_ATTN = 0, LHP_ORIG_DEPTH = 1, LHP_ORIG_ATTN = 2 };
 
-__device__ __forceinline__ float lhp_wave_sum(float v) {
-#define LHP_DPP_ADD(ctrl, rmask) v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), ctrl, rmask, 0xf, false))
-    LHP_DPP_ADD(0x111, 0xf); LHP_DPP_ADD(0x112, 0xf); LHP_DPP_ADD(0x114, 0xf); LHP_DPP_ADD(0x118, 0xf);
-    LHP_DPP_ADD(0x142, 0xa);
-#undef LHP_DPP_ADD
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 31)) + __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
-}
-__device__ __forceinline__ uint32_t lhp_key(float x) {
-    const uint32_t b = __float_as_uint(x);
-    return b ^ ((b >> 31) ? 0xffffffffu : 0x80000000u);
-}
-__device__ __forceinline__ float lhp_unkey(uint32_t k) { return __uint_as_float((k >> 31) ? (k ^ 0x80000000u) : ~k); }
 
 // torch.quantile(row, q) with linear interpolation: the values at floor / ceil of q (P - 1) in sorted order, torch.lerp between
 template <int NJ>
@@ -182,7 +160,7 @@ __device__ float lhp_quantile(const uint32_t (&key)[NJ], const int P, const floa
         for (int j = 0; j < NJ; ++j) cnt += __popcll(__ballot(key[j] < cand));
         if (cnt <= lo) res = cand;
     }
-    const float vlo = lhp_unkey(res);
+    const float vlo = dg_float_unkey(res);
     float vhi = vlo;
     if (hi != lo) {
         int le = 0;
@@ -195,7 +173,7 @@ __device__ float lhp_quantile(const uint32_t (&key)[NJ], const int P, const floa
         if (le < hi + 1) {                                // no duplicate of the lo-th value reaches rank hi: next larger key
 #pragma unroll
             for (int o = 32; o > 0; o >>= 1) { const uint32_t t = (uint32_t)__shfl_xor((int)nxt, o, 64); nxt = t < nxt ? t : nxt; }
-            vhi = lhp_unkey(nxt);
+            vhi = dg_float_unkey(nxt);
         }
     }
     const float w = __fsub_rn(rank, (float)lo);
@@ -275,14 +253,14 @@ __global__ __launch_bounds__(LHP_THREADS) void k_lhp_map(const LhpMapArgs a) {
     if (MODE == LHP_ORIG_ATTN) {
         uint32_t key[NJ];
 #pragma unroll
-        for (int j = 0; j < NJ; ++j) key[j] = lane + 64 * j < P ? lhp_key(v[j]) : 0xffffffffu;
+        for (int j = 0; j < NJ; ++j) key[j] = lane + 64 * j < P ? dg_float_key(v[j]) : 0xffffffffu;
         hi = lhp_quantile<NJ>(key, P, 0.9f);
         lo = lhp_quantile<NJ>(key, P, 0.1f);
     } else {
         lo = infty; hi = -infty;
 #pragma unroll
         for (int j = 0; j < NJ; ++j) if (lane + 64 * j < P) { lo = fminf(lo, v[j]); hi = fmaxf(hi, v[j]); }
-        lo = lhp_wave_min(lo); hi = lhp_wave_max(hi);
+        lo = wave_min(lo); hi = wave_max(hi);
     }
     const float range = __fsub_rn(hi, lo);
 #pragma unroll
@@ -291,7 +269,7 @@ __global__ __launch_bounds__(LHP_THREADS) void k_lhp_map(const LhpMapArgs a) {
     if (MODE == LHP_ATTN) {
         uint32_t key[NJ];
 #pragma unroll
-        for (int j = 0; j < NJ; ++j) key[j] = lane + 64 * j < P ? lhp_key(v[j]) : 0xffffffffu;
+        for (int j = 0; j < NJ; ++j) key[j] = lane + 64 * j < P ? dg_float_key(v[j]) : 0xffffffffu;
         const float thr = lhp_quantile<NJ>(key, P, 0.99f);
 #pragma unroll
         for (int j = 0; j < NJ; ++j) v[j] = (lane + 64 * j < P && !(v[j] > thr)) ? v[j] : 0.f;
@@ -299,7 +277,7 @@ __global__ __launch_bounds__(LHP_THREADS) void k_lhp_map(const LhpMapArgs a) {
         float sum = 0.f;
 #pragma unroll
         for (int j = 0; j < NJ; ++j) if (lane + 64 * j < P) sum += v[j];
-        const float mean = lhp_wave_sum(sum) / (float)P;
+        const float mean = wave_sum_dpp(sum) / (float)P;
 #pragma unroll
         for (int j = 0; j < NJ; ++j) {
             if (MODE == LHP_ORIG_DEPTH) v[j] = (lane + 64 * j < P && !(v[j] > mean)) ? __fsub_rn(1.0f, v[j]) : 0.f;

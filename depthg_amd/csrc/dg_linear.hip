@@ -14,9 +14,9 @@
 //                epilogue reads the residual and writes the result with 128-bit accesses (64-bit for bf16 output).
 //                No barrier after the staging one: W needs no LDS.  x is read from HBM once, LayerNorm computed once.
 //                BM = 128 for K <= 384, 64 for K <= 768, 32 for K <= 1536, 16 for K <= 3072: the stripe is at most 98.5 KiB.
-#include "dg_common.h"
+#include "dg_device.h"
+#include "dg_aux_args.h"
 
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4_t;
 
 #define LIN_WAVES 4
 #define LIN_THREADS (64 * LIN_WAVES)
@@ -112,17 +112,17 @@ __global__ __launch_bounds__(LIN_THREADS) void k_lin_fwd(LinArgs a) {
         const uint8_t* x = static_cast<const uint8_t*>(a.x);
         const int per = K / 8, total = BM * per;                    // 16-byte pieces
         for (int i0 = tid; i0 < total; i0 += 4 * LIN_THREADS) {
-            u32x4_t v[4];
+            u32x4 v[4];
             #pragma unroll
             for (int t = 0; t < 4; ++t) {
                 const int i = i0 + t * LIN_THREADS, rl = i / per, c = i - rl * per;
-                v[t] = u32x4_t{0u, 0u, 0u, 0u};
-                if (i < total && row0 + rl < M) v[t] = *reinterpret_cast<const u32x4_t*>(x + ((size_t)(row0 + rl) * K + 8 * c) * 2);
+                v[t] = u32x4{0u, 0u, 0u, 0u};
+                if (i < total && row0 + rl < M) v[t] = *reinterpret_cast<const u32x4*>(x + ((size_t)(row0 + rl) * K + 8 * c) * 2);
             }
             #pragma unroll
             for (int t = 0; t < 4; ++t) {
                 const int i = i0 + t * LIN_THREADS, rl = i / per, c = i - rl * per;
-                if (i < total) *reinterpret_cast<u32x4_t*>(lin_lds + (size_t)rl * pitch + 16 * c) = v[t];
+                if (i < total) *reinterpret_cast<u32x4*>(lin_lds + (size_t)rl * pitch + 16 * c) = v[t];
             }
         }
     } else {

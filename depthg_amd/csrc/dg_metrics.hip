@@ -4,7 +4,8 @@
 // predictions with n_classes too, so clusters n_classes..n_classes+extra-1 never reach the matrix (rows stay zero).
 // Integer counts: per-block histogram in LDS (32-bit), then one 64-bit atomic per non-empty bin - the result does not
 // depend on the order, bit-identical to torch.bincount.
-#include "dg_common.h"
+#include "dg_device.h"
+#include "dg_aux_args.h"
 
 #define CONF_THREADS 256
 

@@ -14,7 +14,8 @@
 // (beta^t by squaring: t is a whole number) and the segment's last block to take a ticket stores t + 1.  A block takes its ticket
 // after it has read t, so the store cannot overtake a reader; nothing else is handed from block to block, so there is no fence.
 // sqrtf and the division are the correctly rounded ones (hipcc's default: no fast-math flag on this file).
-#include "dg_common.h"
+#include "dg_device.h"
+#include "dg_aux_args.h"
 
 #include <cmath>
 #include <cstring>

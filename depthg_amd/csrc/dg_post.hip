@@ -5,7 +5,8 @@
 //                   over an inverse tap map built in LDS (no floating-point atomics), written as (B,D,h,w) fp32.
 //   k_fps_coords    farthest_point_sampling_depth (src/modules.py:999-1037) = adaptive_avg_pool2d
 //                   -> depth2points(fov=90 rad, :988-996) -> fps (:939-985) -> row-major coords*2-1.
-#include "dg_common.h"
+#include "dg_device.h"
+#include "dg_corr_args.h"
 #include "dg_taps.h"
 #include <cstdlib>
 
@@ -1156,7 +1157,7 @@ hipError_t dg_launch_fps(const float* depth, const float* depth_b, int Ba, int B
 // ------------------------------------------------------------------------------------------
 // super_perm (src/modules.py:1184-1188) for `count` rows at once: rank of every key inside its row (ties by index) =
 // position of that index in the argsort, then the fixed-point bump modulo B.  grid (count), block 256, LDS B floats.
-// (Philox and the row body: dg_common.h dg_super_perm_row - the dense forward draws inside its first launch)
+// (Philox: dg_device.h; the row body: dg_corr_args.h dg_super_perm_row - the dense forward draws inside its first launch)
 __global__ __launch_bounds__(256) void k_super_perms(const float* __restrict__ keys, uint64_t seed, unsigned long long* __restrict__ state,
                                                      int B, int64_t* __restrict__ out) {
     extern __shared__ float sk[];

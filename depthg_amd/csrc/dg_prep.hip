@@ -3,11 +3,12 @@
 //   k_gather_norm    sample() + norm() of the reference (src/modules.py:822-825, 789-790):
 //                    bilinear gather at coords (grid_sample, border, align_corners=True),
 //                    L2-normalise over channels, write the tile blobs (+ 1/norm, column sums)
-//   depth_nz_image   (dg_common.h; a role of k_prep_dense / k_pre_general) depth -> F.interpolate(size=(S,S), bilinear, align_corners=True) -> norm over
+//   depth_nz_image   (dg_corr_args.h; a role of k_prep_dense / k_pre_general) depth -> F.interpolate(size=(S,S), bilinear, align_corners=True) -> norm over
 //                    the single channel (src/modules.py:1261-1265): d / max(|d|, 1e-10)
 //   k_rowmean        r[n][p] = a[n][p] . mean_q b[n][q]   (row means of fd for `pointwise`,
 //                    src/modules.py:1236-1239 restated as a rank-1 term)
-#include "dg_common.h"
+#include "dg_device.h"
+#include "dg_corr_args.h"
 #include "dg_taps.h"
 #include <cstdlib>
 
@@ -100,7 +101,7 @@ __device__ __forceinline__ void cd_mask_tile(const DgCdMaskArgs& a, const int w,
 
 // block = 256 threads = 4 waves; block handles 32 consecutive positions (one operand tile),
 // wave w handles positions w, w+4, ...; lane l handles channels 4l + 256 m.  Output goes straight into
-// the tile blob (dg_common.h): feats -> F part (bf16, swizzled rows), code -> C part (fp16, granule-major)
+// the tile blob (dg_corr_args.h): feats -> F part (bf16, swizzled rows), code -> C part (fp16, granule-major)
 // and P part (fp16, P-major, dg_perm32 order; transposed through LDS).
 template <int MAXM, int NC = 0>      // NC > 0: the launch carries the exact clamp masks (cd_mask_tile<NC>) in extra z slices
 __global__ __launch_bounds__(256) void k_gather_norm(const DgGatherArgs a) {
@@ -321,7 +322,6 @@ hipError_t dg_launch_gather(const DgGatherArgs& a_in, int maxK4, hipStream_t s) 
 // leaves no launch whose time scales with B*h*w*C twice.
 // grid (sum over maps of ceil(K4 / 32), B), block 1024, dynamic LDS 32 * (h*w + 1) floats.
 #define PLANE_THREADS 1024
-typedef int v4i_pl __attribute__((ext_vector_type(4)));
 template <int CH>         // channels per block (32 or 16: smaller planes, more blocks per CU, their load and blend phases overlap)
 __global__ __launch_bounds__(PLANE_THREADS) void k_plane_sample(const DgPlaneArgs a) {
     extern __shared__ __attribute__((aligned(16))) float pl[];          // [CH][HW + 1], then the tap table [consumers][P][8]
@@ -468,7 +468,7 @@ __global__ __launch_bounds__(PLANE_THREADS) void k_plane_sample(const DgPlaneArg
 #pragma unroll 2
                     for (int p = ps; p < a.P; p += PSTEP, tt += PSTEP * 8, rows16 += rstep) {
                         const f32x4 w = *reinterpret_cast<const f32x4*>(tt);
-                        const v4i_pl ix = *reinterpret_cast<const v4i_pl*>(tt + 4);
+                        const i32x4 ix = *reinterpret_cast<const i32x4*>(tt + 4);
                         float acc = plane[ix[0]] * w[0];
                         acc = fmaf(plane[ix[1]], w[1], acc);
                         acc = fmaf(plane[ix[2]], w[2], acc);
@@ -479,7 +479,7 @@ __global__ __launch_bounds__(PLANE_THREADS) void k_plane_sample(const DgPlaneArg
 #pragma unroll 2
                     for (int p = ps; p < a.P; p += PSTEP, tt += PSTEP * 8, rows += rstep) {
                         const f32x4 w = *reinterpret_cast<const f32x4*>(tt);
-                        const v4i_pl ix = *reinterpret_cast<const v4i_pl*>(tt + 4);
+                        const i32x4 ix = *reinterpret_cast<const i32x4*>(tt + 4);
                         float acc = plane[ix[0]] * w[0];
                         acc = fmaf(plane[ix[1]], w[1], acc);
                         acc = fmaf(plane[ix[2]], w[2], acc);
@@ -510,13 +510,12 @@ __global__ __launch_bounds__(256) void k_cd_mask(const DgCdMaskArgs a) {
 // exact), with the rounding noise of an fp32 dot product (operands exact to 2^-22).  The 16 signs of a lane are shifted into a
 // word one v_alignbit each (first version: a compare, a select and an or per element - the launch was bound by its VALU count).
 // Output: the word format of k_cd_mask (bit i of word (S tile, R position) = S position 32 tile + i).
-typedef int v4i_m3 __attribute__((ext_vector_type(4)));
 // W = waves (R tiles) per block: a divisor of the tile count where there is one in 5..8 (25 tiles = 5 x 5, 98 = 14 x 7): with eight
 // waves and 25 tiles every fourth block ran ONE wave through the whole walk (round 5: 78 us for 33 us of MFMAs at the headline).
 template <int NKC, int W>
 __global__ __launch_bounds__(64 * W) void k_cd_mask3(const DgCdMask3Args a) {
     constexpr int NT = 64 * W;
-    using v4i = v4i_m3;
+    using i32x4 = i32x4;
     constexpr int HB = 2 * NKC * 512;                    // bytes of the hi (or lo) rows of one tile that the chain reads
     constexpr int NPC = 2 * HB / 16;                     // 16-byte pieces of one staged tile (hi then lo)
     __shared__ __attribute__((aligned(16))) char buf[2][2 * HB];
@@ -533,36 +532,36 @@ __global__ __launch_bounds__(64 * W) void k_cd_mask3(const DgCdMask3Args a) {
     const int nS = a.sidx[t] ? (int)a.sidx[t][n] : n;
     const size_t lo_tile = (size_t)a.KD * 64;            // bytes of one tile's lo part
     // stationary fragments: granule 2k + h of R position r, hi and lo
-    v4i Rh[NKC], Rl[NKC], Rs[NKC];                     // Rs = 2048 Rh
+    i32x4 Rh[NKC], Rl[NKC], Rs[NKC];                     // Rs = 2048 Rh
     {
         const char* rb = a.opR + ((size_t)n * nt + (act ? rt : 0)) * a.blob_bytes + a.off_c;
         const char* rl = a.loR + ((size_t)n * nt + (act ? rt : 0)) * lo_tile;
 #pragma unroll
         for (int k = 0; k < NKC; ++k) {
-            Rh[k] = *reinterpret_cast<const v4i*>(rb + ((2 * k + h) * 32 + r) * 16);
-            Rl[k] = *reinterpret_cast<const v4i*>(rl + ((2 * k + h) * 32 + r) * 16);
+            Rh[k] = *reinterpret_cast<const i32x4*>(rb + ((2 * k + h) * 32 + r) * 16);
+            Rl[k] = *reinterpret_cast<const i32x4*>(rl + ((2 * k + h) * 32 + r) * 16);
             f16x8 hs = __builtin_bit_cast(f16x8, Rh[k]);
 #pragma unroll
             for (int e = 0; e < 8; ++e) hs[e] = hs[e] * (_Float16)2048.f;
-            Rs[k] = __builtin_bit_cast(v4i, hs);
+            Rs[k] = __builtin_bit_cast(i32x4, hs);
         }
     }
     const char* const sh = a.opS[t] + (size_t)nS * nt * a.blob_bytes + a.off_c;
     const char* const sl = a.loS[t] + (size_t)nS * nt * lo_tile;
     // staging registers of two tiles: the loads of tile st + 2 are requested while tile st is worked on and tile st + 1 waits in
     // the other pair - one tile of look-ahead left the block waiting for memory (83 us for 33 us of MFMAs at the headline)
-    v4i sa0, sa1 = v4i{0, 0, 0, 0}, sb0, sb1 = v4i{0, 0, 0, 0};
+    i32x4 sa0, sa1 = i32x4{0, 0, 0, 0}, sb0, sb1 = i32x4{0, 0, 0, 0};
     auto piece_src = [&](int st, int pc) -> const char* {          // piece pc of tile st: hi rows first, then lo rows
         return pc < HB / 16 ? sh + (size_t)st * a.blob_bytes + pc * 16 : sl + (size_t)st * lo_tile + (pc - HB / 16) * 16;
     };
-    auto fetch = [&](int st, v4i& p0, v4i& p1) {
+    auto fetch = [&](int st, i32x4& p0, i32x4& p1) {
         const int sc = st < s1 ? st : s1 - 1;                      // (past the end: a harmless re-load)
-        p0 = *reinterpret_cast<const v4i*>(piece_src(sc, tid));
-        if (tid + NT < NPC) p1 = *reinterpret_cast<const v4i*>(piece_src(sc, tid + NT));
+        p0 = *reinterpret_cast<const i32x4*>(piece_src(sc, tid));
+        if (tid + NT < NPC) p1 = *reinterpret_cast<const i32x4*>(piece_src(sc, tid + NT));
     };
-    auto stash = [&](int b, const v4i& p0, const v4i& p1) {
-        *reinterpret_cast<v4i*>(buf[b] + tid * 16) = p0;
-        if (tid + NT < NPC) *reinterpret_cast<v4i*>(buf[b] + (tid + NT) * 16) = p1;
+    auto stash = [&](int b, const i32x4& p0, const i32x4& p1) {
+        *reinterpret_cast<i32x4*>(buf[b] + tid * 16) = p0;
+        if (tid + NT < NPC) *reinterpret_cast<i32x4*>(buf[b] + (tid + NT) * 16) = p1;
     };
     static_assert(NPC <= 2 * NT, "two pieces per thread");
     uint32_t* const out = a.bits[t] + (size_t)n * nt * a.Ppad + (act ? rt : 0) * 32 + r;

@@ -5,10 +5,10 @@
 //     the label resolution (align_corners=False), cross entropy over the labelled pixels (0 <= label < n_classes), mean.
 // The reference materialises (B*H*W, n_classes) logits at label resolution and three masks; here a label pixel's logits are blended
 // in registers and the adjoint of the resize is a gather per low-resolution row (fixed order: no floating-point atomics).
-#include "dg_common.h"
+#include "dg_device.h"
+#include "dg_head_args.h"
 #include "dg_taps.h"          // resize_taps
 
-#define DG_NORM_EPS 1e-12f       // F.normalize default eps (src/modules.py:668-669 call it without one)
 
 
 // one thread per position; the normalised centres sit in LDS ([n][D + 1])
@@ -20,7 +20,7 @@ __global__ __launch_bounds__(256) void k_cluster_fwd(const DgClusterArgs a) {
     for (int c = threadIdx.x; c < n; c += 256) {
         float s = 0.f;
         for (int d = 0; d < D; ++d) { const float v = a.clusters[(size_t)c * D + d]; s = fmaf(v, v, s); }
-        const float inv = 1.f / fmaxf(sqrtf(s), DG_NORM_EPS);
+        const float inv = 1.f / fmaxf(sqrtf(s), DG_EPS_NORM_DEFAULT);
         for (int d = 0; d < D; ++d) nc[c * ld + d] = a.clusters[(size_t)c * D + d] * inv;
     }
     __syncthreads();
@@ -30,7 +30,7 @@ __global__ __launch_bounds__(256) void k_cluster_fwd(const DgClusterArgs a) {
         const float* x = a.x + (size_t)b * D * P + p;
         float s = 0.f;
         for (int d = 0; d < D; ++d) { const float v = x[(size_t)d * P]; s = fmaf(v, v, s); }
-        const float inv = 1.f / fmaxf(sqrtf(s), DG_NORM_EPS);
+        const float inv = 1.f / fmaxf(sqrtf(s), DG_EPS_NORM_DEFAULT);
         const bool hard = a.alpha != a.alpha;
         float best = -INFINITY, mx = -INFINITY;
         int arg = 0;
@@ -93,7 +93,7 @@ __global__ __launch_bounds__(256) void k_cluster_bwd_pos(const DgClusterBwdArgs 
     for (int c = threadIdx.x; c < n; c += 256) {
         float s = 0.f;
         for (int d = 0; d < D; ++d) { const float v = a.clusters[(size_t)c * D + d]; s = fmaf(v, v, s); }
-        const float inv = 1.f / fmaxf(sqrtf(s), DG_NORM_EPS);
+        const float inv = 1.f / fmaxf(sqrtf(s), DG_EPS_NORM_DEFAULT);
         for (int d = 0; d < D; ++d) nc[c * ld + d] = a.clusters[(size_t)c * D + d] * inv;
     }
     __syncthreads();
@@ -122,7 +122,7 @@ __global__ __launch_bounds__(256) void k_cluster_bwd_pos(const DgClusterBwdArgs 
         const float* x = a.x + (size_t)b * D * P + p;
         float s = 0.f;
         for (int d = 0; d < D; ++d) { const float v = x[(size_t)d * P]; s = fmaf(v, v, s); }
-        const float nrm = fmaxf(sqrtf(s), DG_NORM_EPS), inv = 1.f / nrm;
+        const float nrm = fmaxf(sqrtf(s), DG_EPS_NORM_DEFAULT), inv = 1.f / nrm;
         // d nf[d] = sum_c dinner[c] nc[c][d];   d x = (d nf - nf <nf, d nf>) / ||x||   (||x|| above eps)
         float dot = 0.f;
         for (int d = 0; d < D; ++d) {
@@ -130,7 +130,7 @@ __global__ __launch_bounds__(256) void k_cluster_bwd_pos(const DgClusterBwdArgs 
             for (int c = 0; c < n; ++c) g = fmaf(di[(size_t)c * P], nc[c * ld + d], g);
             dot = fmaf(g, x[(size_t)d * P] * inv, dot);
         }
-        const bool clampd = sqrtf(s) < DG_NORM_EPS;
+        const bool clampd = sqrtf(s) < DG_EPS_NORM_DEFAULT;
         for (int d = 0; d < D; ++d) {
             float g = 0.f;
             for (int c = 0; c < n; ++c) g = fmaf(di[(size_t)c * P], nc[c * ld + d], g);
@@ -152,7 +152,7 @@ __global__ __launch_bounds__(256) void k_cluster_bwd_centres(const DgClusterBwdA
         const int p = p0 + threadIdx.x;
         float s = 0.f;
         if (p < P) for (int d = 0; d < D; ++d) { const float v = a.x[((size_t)b * D + d) * P + p]; s = fmaf(v, v, s); }
-        sinv[threadIdx.x] = 1.f / fmaxf(sqrtf(s), DG_NORM_EPS);
+        sinv[threadIdx.x] = 1.f / fmaxf(sqrtf(s), DG_EPS_NORM_DEFAULT);
     }
     __syncthreads();
     for (int i = threadIdx.x; i < n * 64; i += 256) {
@@ -185,12 +185,12 @@ __global__ __launch_bounds__(128) void k_cluster_bwd_finish(const DgClusterBwdAr
     sg[d] = v * v; sdot[d] = 0.f;
     __syncthreads();
     for (int o = 64; o > 0; o >>= 1) { if (d < o) sg[d] += sg[d + o]; __syncthreads(); }
-    const float raw = sqrtf(sg[0]), nrm = fmaxf(raw, DG_NORM_EPS);
+    const float raw = sqrtf(sg[0]), nrm = fmaxf(raw, DG_EPS_NORM_DEFAULT);
     __syncthreads();
     sdot[d] = g * (v / nrm);
     __syncthreads();
     for (int o = 64; o > 0; o >>= 1) { if (d < o) sdot[d] += sdot[d + o]; __syncthreads(); }
-    if (d < D) a.grad_clusters[(size_t)c * D + d] = raw < DG_NORM_EPS ? g / nrm : (g - (v / nrm) * sdot[0]) / nrm;
+    if (d < D) a.grad_clusters[(size_t)c * D + d] = raw < DG_EPS_NORM_DEFAULT ? g / nrm : (g - (v / nrm) * sdot[0]) / nrm;
 }
 
 hipError_t dg_launch_cluster_bwd(const DgClusterBwdArgs& a, hipStream_t s) {

@@ -5,7 +5,8 @@
 // the caller hands over iid uniforms u in [0,1) (torch.rand on the device) and a rank among `count` candidates is
 // min(int(u * count), count - 1) - the same distribution, and a deterministic function of (input, u) that the parity
 // tests check pixel for pixel.
-#include "dg_common.h"
+#include "dg_device.h"
+#include "dg_aux_args.h"
 
 #define SMP_THREADS 1024
 

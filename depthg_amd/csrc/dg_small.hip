@@ -23,10 +23,9 @@
 //
 // k_gather_rows: sample() (:822-825) of channel-last maps into the fp32 rows above, for calls whose maps k_plane_sample cannot take
 // (code maps of another size than the feature maps, maps beyond its LDS planes).
-#include "dg_common.h"
-#include <hip/hip_runtime.h>
+#include "dg_device.h"
+#include "dg_corr_args.h"
 
-typedef int v4i_s __attribute__((ext_vector_type(4)));
 
 #define SM_THREADS 256
 
@@ -37,7 +36,7 @@ __device__ __forceinline__ uint32_t sm_c(int row, int g) { return (uint32_t)row 
 
 // 1.0 where g != 0 (the clamp mask back out of the stored -G: the epilogue never stores an exact zero for an element that is on)
 __device__ __forceinline__ f16x8 sm_mask_of(const f16x8 g) {
-    const v4i_s b = __builtin_bit_cast(v4i_s, g) & v4i_s{0x7fff7fff, 0x7fff7fff, 0x7fff7fff, 0x7fff7fff};
+    const i32x4 b = __builtin_bit_cast(i32x4, g) & i32x4{0x7fff7fff, 0x7fff7fff, 0x7fff7fff, 0x7fff7fff};
     f16x8 t = __builtin_bit_cast(f16x8, b);
     const _Float16 big = (_Float16)32768.f;
     t = t * big;
@@ -173,7 +172,7 @@ __global__ __launch_bounds__(SM_THREADS) __attribute__((amdgpu_waves_per_eu(1, 1
                 // different instructions whose results differ at exact ties - hi from one rounding, lo from the other, 2.4e-4 off
                 // (found against the reference fixture at C = 2048: one code row in 242 carried such an element)
                 {
-                    v4i_s hb = __builtin_bit_cast(v4i_s, chi[c][j]);
+                    i32x4 hb = __builtin_bit_cast(i32x4, chi[c][j]);
                     asm volatile("" : "+v"(hb));
                     chi[c][j] = __builtin_bit_cast(f16x8, hb);
                 }
@@ -200,7 +199,7 @@ __global__ __launch_bounds__(SM_THREADS) __attribute__((amdgpu_waves_per_eu(1, 1
     }
     // The feature rows arrive as bf16 (the sampler's output): a chunk goes to LDS as it is, and the squared norms are taken from the
     // values that are multiplied.  Piece u of a thread = channels 64 u + 8 gran .. + 7 of its row.
-    v4i_s v[NJ][2];
+    i32x4 v[NJ][2];
     float ss[NJ];
 #pragma unroll
     for (int j = 0; j < NJ; ++j) ss[j] = 0.f;
@@ -212,7 +211,7 @@ __global__ __launch_bounds__(SM_THREADS) __attribute__((amdgpu_waves_per_eu(1, 1
                 // (no select at all: the rows are a whole number of chunks long - the sampler zero-fills the channels past C - and a
                 //  padded position reads position 0's finite values, which its zero inverse norm and the epilogue's validity mask
                 //  keep out of every result)
-                v[j][u] = *reinterpret_cast<const v4i_s*>(srcp[j] + ch * KC + 64 * u + gran * 8);
+                v[j][u] = *reinterpret_cast<const i32x4*>(srcp[j] + ch * KC + 64 * u + gran * 8);
             }
     };
     auto stash = [&](int buf) {
@@ -228,7 +227,7 @@ __global__ __launch_bounds__(SM_THREADS) __attribute__((amdgpu_waves_per_eu(1, 1
                     const int w = v[j][u][e];
                     asm("v_dot2c_f32_bf16 %0, %1, %1" : "+v"(ss[j]) : "v"(w));
                 }
-                *reinterpret_cast<v4i_s*>(sm + buf * FBUF + sm_c(pass_row(j), u * 8 + gran)) = v[j][u];
+                *reinterpret_cast<i32x4*>(sm + buf * FBUF + sm_c(pass_row(j), u * 8 + gran)) = v[j][u];
             }
         }
     };

@@ -4,7 +4,6 @@
 #pragma once
 #include "dg_common.h"
 
-#ifdef __HIPCC__
 __device__ __forceinline__ void dg_taps(const float* c, int h, int w, int& x0, int& y0, bool& inx, bool& iny,
                                         float& w00, float& w01, float& w10, float& w11) {
     float x = ((c[0] + 1.f) / 2.f) * (float)(w - 1);
@@ -22,6 +21,10 @@ __device__ __forceinline__ void dg_taps(const float* c, int h, int w, int& x0, i
 // (position, weight) that read it, as CSR in global memory (off[HW+1], then 4P weights, then 4P positions).
 // Lists are sorted by position, so the gather below sums in a fixed order (bit-reproducible gradients).
 // grid (B, 2), block SCAT_THREADS, dynamic LDS (2*HW + 1) ints + 4P floats + 4P ushorts.
+// bytes of one inverse-tap record: off[HW+1] ints, 4P weights, 4P positions (ushort), padded to 16
+__host__ __device__ inline size_t dg_taps_record_bytes(int HW, int P) {
+    return (((size_t)(HW + 1) * 4 + (size_t)4 * P * 6) + 15) / 16 * 16;
+}
 struct DgTapsArgs { const float* coords1; const float* coords2; char* taps; int B, h, w, S, Sh, P; };
 template <int NT>
 __device__ __forceinline__ void build_taps_block(const DgTapsArgs& t, const int nimg, const int cs, char* sg) {
@@ -109,5 +112,3 @@ __device__ __forceinline__ void resize_taps(const int dst, const int in, const i
     i1 = i0 < in - 1 ? i0 + 1 : i0;
     l1 = src - (float)i0;
 }
-
-#endif
