@@ -8,9 +8,64 @@
 static unsigned long long* g_prof_span = nullptr;
 extern "C" int dg_prof_main_span(void* span) { g_prof_span = static_cast<unsigned long long*>(span); return DG_OK; }
 
+// ---- the plan: everything that decides which kernels a call runs, on which operands and from which workspace regions, decided ONCE
+// per descriptor by make_plan.  Every job builder and every launch below reads it; none of them derives a route again.
+enum class Prep { Small, Dense, General };              // operand preparation: the fused small grid (dg_small.hip: sampled rows -> ONE launch) /
+                                                        // the dense identity grid straight from NCHW / general coordinates into blobs
+enum class Sampler { Plane, ChannelLast };              // sample(): k_plane_sample straight from NCHW / channel-last copies of the maps + a gather
+enum class MainKernel { Small, Corr2, CorrMain };       // the fused correlation launch: k_corr_small / k_corr2 (gradient passes of the
+                                                        // shapes dg_corr2_shape_supported names) / k_corr_main (everything else)
+enum class Depth { None, Job, GsBlocks, GsOwnLaunch };   // the depth term of the blob kernels: off (or inside k_corr_small) / a job of the fused launch
+                                                        // (forward-only calls) / blocks of the k_gs launch (gradient passes; dg_corr.hip gs_depth_block: in
+                                                        // the fused kernel's launch its latency-bound blocks were the tail) / those blocks, in the masked
+                                                        // form, as a launch of their own beside the G-stream blocks (fwd_finish)
+enum class Masks { None, Sampled, DenseRaw, DenseSplit };   // exact clamp masks: the sign of the fp16 cd / k_cd_mask blocks inside the gather launch
+                                                        // (small sample grids) / k_cd_mask on channel-last code maps / k_cd_mask3 on split fp16 operands
+
+struct PairSet {            // pair-set t: 0 intra, 1 inter, 2 + k negative k.  The stationary operand is operand 0
+    int op;                 // the streamed operand (pass A)
+    int neg;                // k, or -1
+    bool mapped;            // the streamed operand is read through negative k's batch map (DG_SHARED_COORDS: the negatives stream operand 0)
+    float shift;
+    int slot_loss, slot_cd; // DG_OUT_*
+    float fin_scale;        // 1 / numel of the tensor the pair-set's sums are means of
+    int gidx, csel, dest;   // the backward: upstream scalar, coordinate set and destination map of the streamed-side gradient ...
+    float factor;           // ... and the constant factor of both sides
+};
+struct Operand {            // operand o: 0 anchors, 1 positives, 2 + k the negatives' (not with DG_SHARED_COORDS)
+    int srcsel;             // 1: the *_pos maps (operand 1); 0: orig_feats / orig_code
+    int cset;               // 0: coords1, 1: coords2
+    int map;                // k: read through negative k's batch map; -1: none
+};
+
 struct Plan {
-    int B, C, D, h, w, hc, wc, S, Sh, P, Ppad, KF, KD, C4, D4, N, T, nops, rf, nrb, blob;     // (hc, wc): size of the code maps
-    bool shared, depth, grad, pointwise, ident, rows;
+    int B, C, D, h, w, hc, wc, S, Sh, P, Ppad, KF, KD, C4, D4, N, T, nops, rf, nrb;     // (hc, wc): size of the code maps
+    bool shared, depth, grad, pointwise;
+    // ---- routes
+    Prep prep;
+    Sampler sampler;                        // (Prep::Dense samples nothing: ChannelLast, the copies its DenseRaw masks read)
+    MainKernel main;
+    Masks masks;
+    bool fold;                              // MainKernel::Corr2 forms the intra pair-set's streamed-side gradient itself (dg_corr2.hip FOLD)
+    bool half;                              // MainKernel::Corr2 and k_gs write fp16 gradient tiles for k_combine_out (identity grid; DgScatterSrc.half)
+    Depth depth_run;
+    int nsplit;                             // Prep::Small: blocks per (image, pair-set), 2 when the image has 5 tiles
+    int dep_nrb;                            // row blocks of the depth term inside the k_gs launch: 8 row tiles each
+    float lo, hi;                           // clamp bounds of cd (zero_clamp / stabalize)
+    float shift_depth;
+    float inv_numel;                        // 1 / (B P P)
+    float grad_f, grad_fn;                  // the backward's factors: -1 / (B P P) (the kernels keep -G: the sign lives here), and / n_neg
+    int blob, blob_off_c;                   // the operand blobs at (KF, KD): bytes per tile, offset of the C part (DgBlob)
+    PairSet ps[DG_MAX_NEG + 2];
+    Operand ops[DG_MAX_NEG + 2];
+    // Ragged last row blocks grouped by streamed operand (dg_corr2.hip): pair-sets that stream the same operand form a key.  Worth it
+    // when the ragged row block is short (at most 4 of the 8 row tiles) and several pair-sets share an operand (shared coordinates:
+    // intra + the negatives stream operand 0 through batch maps).  gr_on: in use; key and first are filled whenever the shape is eligible
+    bool gr_on;
+    int gr_nkeys, gr_cpb, gr_blocks_per_image;
+    int8_t gr_key[DG_MAX_JOBS], gr_first[DG_MAX_JOBS];
+    int32_t gr_nblk[DG_MAX_JOBS];
+    // ---- workspace offsets
     size_t nhwc_f[2], nhwc_c[2];
     size_t rows_f[DG_MAX_NEG + 2], rows_c[DG_MAX_NEG + 2];     // sampled fp32 rows per operand (small sample grids)
     size_t op[DG_MAX_NEG + 2], inv[DG_MAX_NEG + 2], colpart[DG_MAX_NEG + 2], bbar[DG_MAX_NEG + 2];
@@ -21,22 +76,79 @@ struct Plan {
     size_t part[DG_MAX_NEG + 3];
     size_t comb[2], scratch_out, taps, gbuf[DG_MAX_NEG + 2];
     size_t ticket;                          // the depth blocks' ticket of the k_gs launch
-    size_t maskbits[DG_MAX_NEG + 2];        // exact clamp masks of the pair-sets (k_cd_mask), xmask: in use on a small sample grid,
-    bool half;                              // fp16 gradient tiles between k_corr2 / k_gs and k_combine_out (identity grid; DgScatterSrc.half)
-    bool xmask, xmask_dense;                // xmask_dense: on the dense identity grid (DG_EXACT_MASKS)
-    bool fold;                              // the intra pair-set's streamed-side gradient is formed in the fused kernel (dg_corr2.hip FOLD)
-    size_t clo[2];                          // ... with pointwise: the parts of the normalised code the fp16 C parts drop (k_cd_mask3)
-    size_t gr_list, gr_count, gr_rank;      // consumer lists of the grouped ragged row blocks (dg_corr2.hip)
-    // the fused small-grid path (dg_small.hip): sampled rows -> ONE launch
-    bool small;
-    int nsplit;                             // blocks per (image, pair-set): 2 when the image has 5 tiles
-    size_t dRA2[DG_MAX_NEG + 2], dRBs[DG_MAX_NEG + 2], dRB2[DG_MAX_NEG + 2][2], dRBm[DG_MAX_NEG + 2], part4, om;
+    size_t maskbits[DG_MAX_NEG + 2];        // exact clamp masks of the pair-sets
+    size_t clo[2];                          // Masks::DenseSplit: the parts of the normalised code the fp16 C parts drop (k_cd_mask3)
+    size_t gr_list, gr_count, gr_rank;      // consumer lists of the grouped ragged row blocks
+    size_t dRA2[DG_MAX_NEG + 2], dRBs[DG_MAX_NEG + 2], dRB2[DG_MAX_NEG + 2][2], dRBm[DG_MAX_NEG + 2], part4, om;      // Prep::Small
     size_t total;
+
+    bool small() const { return prep == Prep::Small; }
+    bool dense() const { return prep == Prep::Dense; }
+    bool plane() const { return sampler == Sampler::Plane; }
+    bool has_masks() const { return masks != Masks::None; }
+    bool depth_in_gs() const { return depth_run == Depth::GsBlocks || depth_run == Depth::GsOwnLaunch; }
+    bool dense_masks() const { return masks == Masks::DenseRaw || masks == Masks::DenseSplit; }
+    // Without `pointwise` the intra pair-set (t = 0) has NO k_gs job (round 4): it correlates the anchors with themselves at the same
+    // coordinates, so fd, cd and with them -G are symmetric and the gradient through the streamed side equals the one through the
+    // stationary side, which the fused kernel accumulates in registers anyway - the backward doubles that one (as it always did for the
+    // depth term) instead of reading 1/7 of the G tiles again.  With `pointwise` -G is NOT symmetric: the reference centres fd by its
+    // ROW means only (fd -= fd.mean([3, 4]), src/modules.py:1238-1239), -G[p][q] - -G[q][p] = mask (rowmean_q - rowmean_p) - invisible
+    // on i.i.d. features, 1e-2 of the gradient on the FPS recipes (the test with exact masks caught it).
+    // (fold: with `pointwise` k_corr2 forms G + G^T in its own accumulator, dg_corr2.hip FOLD - the same consequence for the launches)
+    bool intra_symmetric() const { return !pointwise || fold; }
+    // the batch map pair-set t / operand o reads its streamed images through (null: the image itself).  Formed as an integer: where no
+    // mapped pair-set is read (dg_corr_materialize of intra / inter on a shared grid) `perms` may be null and the address is never used
+    const int64_t* batch_map(int k, const int64_t* perms) const {
+        return k < 0 ? nullptr : reinterpret_cast<const int64_t*>(reinterpret_cast<uintptr_t>(perms) + (size_t)k * B * sizeof(int64_t));
+    }
+    const int64_t* map_of(int t, const int64_t* perms) const { return batch_map(ps[t].mapped ? ps[t].neg : -1, perms); }
 };
+
+static inline float* f32(char* ws, size_t off) { return reinterpret_cast<float*>(ws + off); }
 
 #define FOLD_STASH_OFF (5 * 1024)        // k_corr2<24, 6, 5>: code k-step 5 of the C part (channels 80 .. 95: padding for D <= 80)
 
-static void clamp_bounds(const dg_corr_desc* d, float& lo, float& hi);
+// the pair-set and operand tables, and from them the grouping of the ragged row blocks
+static void plan_tables(const dg_corr_desc* d, Plan& p) {
+    const double numel = (double)p.B * p.P * p.P;
+    p.inv_numel = (float)(1.0 / numel);
+    p.grad_f = (float)(-1.0 / numel);
+    p.grad_fn = p.N > 0 ? p.grad_f / (float)p.N : 0.f;
+    for (int t = 0; t < p.T; ++t) {
+        PairSet& s = p.ps[t];
+        const bool neg = t >= 2;
+        s.neg = neg ? t - 2 : -1;
+        s.mapped = neg && p.shared;
+        s.op = s.mapped ? 0 : t;
+        s.shift = t == 0 ? d->shift_intra : (t == 1 ? d->shift_inter : d->shift_neg);
+        s.slot_loss = neg ? DG_OUT_LOSS_NEG : t;
+        s.slot_cd = neg ? DG_OUT_CD_NEG : DG_OUT_CD_INTRA + t;
+        s.fin_scale = neg ? (float)(1.0 / (numel * p.N)) : p.inv_numel;
+        s.gidx = neg ? 2 : t; s.csel = t == 0 ? 0 : 1; s.dest = t == 1 ? 1 : 0;
+        s.factor = neg ? p.grad_fn : p.grad_f;
+    }
+    for (int o = 0; o < p.nops; ++o) p.ops[o] = Operand{o == 1 ? 1 : 0, o == 0 ? 0 : 1, o >= 2 ? o - 2 : -1};
+    const int L = (p.Ppad / 32) % 8;        // row tiles of the ragged last row block
+    if (!(p.grad && p.KF == 384 && p.KD == 96 && p.D <= 80 && p.nrb > 1 && L >= 1 && L <= 4 && p.B % 8 == 0 && p.B <= 64)) return;
+    int nkeys = 0, members[DG_MAX_JOBS] = {0};
+    for (int t = 0; t < p.T; ++t) {
+        int k = -1;
+        for (int q = 0; q < nkeys; ++q) if (p.ps[p.gr_first[q]].op == p.ps[t].op) k = q;
+        if (k < 0) { k = nkeys++; p.gr_first[k] = (int8_t)t; }
+        p.gr_key[t] = (int8_t)k; ++members[k];
+    }
+    for (int k = 0; k < nkeys; ++k) p.gr_on |= members[k] > 1;
+    if (!p.gr_on) return;
+    p.gr_nkeys = nkeys; p.gr_cpb = 8 / L;
+    for (int k = 0; k < nkeys; ++k) {
+        const bool single = members[k] == 1 && !p.ps[p.gr_first[k]].mapped;             // exactly one consumer per image
+        const int nb = single ? 1 : (5 * members[k] / 2 + p.gr_cpb - 1) / p.gr_cpb;     // 2.5 x the mean consumer count
+        const int cap = (DG_GR_CAP + p.gr_cpb - 1) / p.gr_cpb;
+        p.gr_nblk[k] = nb > cap ? cap : nb;
+        p.gr_blocks_per_image += p.gr_nblk[k];
+    }
+}
+
 static int make_plan(const dg_corr_desc* d, Plan& p) {
     if (!d) return fail(DG_ERR_INVALID, "null descriptor");
     if (d->B < 1 || d->C < 1 || d->D < 1 || d->h < 1 || d->w < 1 || d->S < 1)
@@ -59,14 +171,15 @@ static int make_plan(const dg_corr_desc* d, Plan& p) {
     // Sample grids of at most 160 positions (every recipe the reference ships: feature_samples = 11 / 12) take the fused small-grid
     // kernel, which streams the feature channels in chunks and so has no width limit (FeaturePyramidNet: 2048).  The blob kernels
     // (larger grids, the identity grid) hold whole channel vectors in registers / LDS: C <= 768 there.
-    p.small = !(d->flags & DG_IDENTITY_GRID) && dg_small_supported(p.Ppad, p.KD);
+    const bool ident = (d->flags & DG_IDENTITY_GRID) != 0;
+    p.prep = ident ? Prep::Dense : (dg_small_supported(p.Ppad, p.KD) ? Prep::Small : Prep::General);
     p.nsplit = p.Ppad == 160 ? 2 : 1;
-    if (d->C > 768 && !p.small)
+    if (d->C > 768 && !p.small())
         return fail(DG_ERR_UNSUPPORTED, "C=%d > 768 feature channels are supported on sample grids of at most 160 positions "
                                         "(feature_samples <= 12) only; this call has %d positions%s", d->C, p.P,
-                    (d->flags & DG_IDENTITY_GRID) ? " on the dense identity grid (wider maps go there in channel chunks: dg_normalize_split + DG_FEATS_UNIT)"
-                                                   : " (wider maps go there in channel chunks: dg_sampled_sumsq + dg_corr_forward_extnorm)");
-    if ((d->flags & DG_FEATS_UNIT) && !(d->flags & DG_IDENTITY_GRID))
+                    ident ? " on the dense identity grid (wider maps go there in channel chunks: dg_normalize_split + DG_FEATS_UNIT)"
+                          : " (wider maps go there in channel chunks: dg_sampled_sumsq + dg_corr_forward_extnorm)");
+    if ((d->flags & DG_FEATS_UNIT) && !ident)
         return fail(DG_ERR_INVALID, "DG_FEATS_UNIT needs DG_IDENTITY_GRID: on sampled coordinates the reference normalises BEHIND sample()");
     p.C4 = (int)up(d->C, 4); p.D4 = (int)up(d->D, 4);
     p.T = 2 + p.N;
@@ -74,15 +187,19 @@ static int make_plan(const dg_corr_desc* d, Plan& p) {
     p.depth = (d->flags & DG_DEPTH_TERM) != 0;
     p.grad = (d->flags & DG_NEED_GRAD) != 0;
     p.pointwise = (d->flags & DG_POINTWISE) != 0;
-    p.ident = (d->flags & DG_IDENTITY_GRID) != 0;
-    if (p.ident && (p.Sh != p.S || !p.shared || d->S != d->h || d->S != d->w || d->w > 64))
+    if (ident && (p.Sh != p.S || !p.shared || d->S != d->h || d->S != d->w || d->w > 64))
         return fail(DG_ERR_INVALID, "DG_IDENTITY_GRID needs DG_SHARED_COORDS and S == h == w <= 64");
-    if (p.ident && !same_maps)
+    if (ident && !same_maps)
         return fail(DG_ERR_INVALID, "DG_IDENTITY_GRID needs code maps of the feature maps' size (got %dx%d against %dx%d)", p.hc, p.wc, p.h, p.w);
     p.nops = p.shared ? 2 : p.T;
     p.rf = (p.KF == 384 && p.KD == 96 && p.Ppad > 128) ? 8 : 4;    // waves per block (32 stationary rows each)
     p.nrb = (p.Ppad + p.rf * 32 - 1) / (p.rf * 32);
-    p.blob = DgBlob(p.KF, p.KD).bytes;
+    p.dep_nrb = (p.Ppad / 32 + 7) / 8;
+    { const DgBlob bl(p.KF, p.KD); p.blob = bl.bytes; p.blob_off_c = bl.off_c; }
+    p.lo = (d->flags & DG_ZERO_CLAMP) ? 0.0f : -9999.0f;
+    p.hi = (d->flags & DG_STABALIZE) ? 0.8f : __builtin_inff();
+    p.shift_depth = d->shift_depth;
+    const bool plain_zero_clamp = (d->flags & DG_ZERO_CLAMP) && !(d->flags & DG_STABALIZE);
     size_t off = 0;
     auto take = [&](size_t bytes) { size_t o = off; off += up(bytes, 256); return o; };
     const size_t HW = (size_t)p.h * p.w, HWc = (size_t)p.hc * p.wc, B = p.B;
@@ -90,16 +207,17 @@ static int make_plan(const dg_corr_desc* d, Plan& p) {
     // fit the LDS; batch indices fit the 16-bit consumer lists): sample() straight from NCHW (k_plane_sample) instead of
     // channel-last copies of the whole maps
     // (code maps of another size than the feature maps - the FeaturePyramidNet contract - take the channel-last gather path)
-    p.rows = !p.ident && same_maps && (size_t)p.nops * p.P <= 2 * HW && HW <= 1024 && B <= 32767;
-    for (int i = 0; i < 2; ++i) { p.nhwc_f[i] = take(p.rows ? 0 : B * HW * p.C4 * 4); p.nhwc_c[i] = take(p.rows ? 0 : B * HWc * p.D4 * 4); }
-    const bool want_rows = p.rows || p.small;      // (the fused small-grid kernel reads sampled rows whichever sampler wrote them)
+    const bool rows = !ident && same_maps && (size_t)p.nops * p.P <= 2 * HW && HW <= 1024 && B <= 32767;
+    p.sampler = rows ? Sampler::Plane : Sampler::ChannelLast;
+    for (int i = 0; i < 2; ++i) { p.nhwc_f[i] = take(rows ? 0 : B * HW * p.C4 * 4); p.nhwc_c[i] = take(rows ? 0 : B * HWc * p.D4 * 4); }
+    const bool want_rows = rows || p.small();      // (the fused small-grid kernel reads sampled rows whichever sampler wrote them)
     // (the fused small-grid kernel takes bf16 feature rows of up(C, 128) channels - whole chunks; the multi-launch path fp32 rows of C4)
-    const size_t frow = p.small ? (size_t)up(p.C, 128) * 2 : (size_t)p.C4 * 4;
+    const size_t frow = p.small() ? (size_t)up(p.C, 128) * 2 : (size_t)p.C4 * 4;
     for (int i = 0; i < p.nops; ++i) { p.rows_f[i] = take(want_rows ? B * p.P * frow : 0); p.rows_c[i] = take(want_rows ? B * p.P * p.D4 * 4 : 0); }
     for (int i = 0; i < p.nops; ++i) {
         p.op[i] = take(B * (p.Ppad / 32) * (size_t)p.blob);
         p.inv[i] = take(B * p.Ppad * 4);
-        p.colpart[i] = take(B * (size_t)(p.ident ? p.h * ((p.w + 31) / 32) : p.Ppad / 32) * p.KF * 4);
+        p.colpart[i] = take(B * (size_t)(ident ? p.h * ((p.w + 31) / 32) : p.Ppad / 32) * p.KF * 4);
         p.bbar[i] = take(B * p.KF * 4);
         p.bsplit[i] = take(B * 2 * p.KF * 2);
         p.ccolpart[i] = take(B * (size_t)(p.Ppad / 32) * p.KD * 4);
@@ -113,229 +231,170 @@ static int make_plan(const dg_corr_desc* d, Plan& p) {
     for (int i = 0; i < 2; ++i) p.comb[i] = take(B * p.Ppad * p.KD * 4);
     p.scratch_out = take(DG_OUT_COUNT * 4);
     p.taps = take(2 * B * dg_taps_record_bytes(p.hc * p.wc, p.P));     // the adjoint of sample() scatters into the CODE maps
-    for (int t = 0; t < p.T; ++t) p.gbuf[t] = p.grad ? take(B * (size_t)(p.Ppad / 32) * (p.Ppad / 32) * 2048) : 0;     // (gbuf[0]: 4 KiB would do with p.fold, which is decided below)
+    for (int t = 0; t < p.T; ++t) p.gbuf[t] = p.grad ? take(B * (size_t)(p.Ppad / 32) * (p.Ppad / 32) * 2048) : 0;     // (gbuf[0]: 4 KiB would do with p.fold)
     p.ticket = take(256);
-    // exact clamp masks: gradient passes of the zero_clamp recipe on small sample grids (fp32 sampled rows exist, <= 8 tiles, the
-    // one-wave-per-SIMD form of k_corr_main)
-    p.xmask = p.rows && !p.small && p.grad && (d->flags & DG_ZERO_CLAMP) && !(d->flags & DG_STABALIZE) && p.Ppad <= 256 && p.rf == 4;
-    // DG_EXACT_MASKS: the dense identity grid at the widths of the one-wave-per-SIMD kernel (dg_corr2.hip) takes the same mask words,
-    // computed from channel-last fp32 copies of the two code maps (the workspace's nhwc_c regions, otherwise unused on this grid)
-    p.xmask_dense = (d->flags & DG_EXACT_MASKS) && p.ident && p.grad && (d->flags & DG_ZERO_CLAMP) && !(d->flags & DG_STABALIZE) &&
-                    p.KF == 384 && p.KD == 96 && p.D <= 80 && p.Ppad >= 160 && p.B <= 64;
-    if ((d->flags & DG_EXACT_MASKS) && p.grad && (d->flags & DG_ZERO_CLAMP) && !p.xmask && !p.xmask_dense && !p.small)
+    // The mask source.  Sampled: gradient passes of the zero_clamp recipe on small sample grids (fp32 sampled rows exist, <= 8 tiles, the
+    // one-wave-per-SIMD form of k_corr_main).  DG_EXACT_MASKS: the dense identity grid at the widths of the one-wave-per-SIMD kernel
+    // (dg_corr2.hip) takes the same mask words - without `pointwise` from channel-last fp32 copies of the two code maps (the workspace's
+    // nhwc_c regions, otherwise unused on this grid), with it from the split fp16 operands the k_colmean launch writes
+    const bool xmask = rows && !p.small() && p.grad && plain_zero_clamp && p.Ppad <= 256 && p.rf == 4;
+    const bool xmask_dense = (d->flags & DG_EXACT_MASKS) && ident && p.grad && plain_zero_clamp &&
+                             p.KF == 384 && p.KD == 96 && p.D <= 80 && p.Ppad >= 160 && p.B <= 64;
+    if ((d->flags & DG_EXACT_MASKS) && p.grad && (d->flags & DG_ZERO_CLAMP) && !xmask && !xmask_dense && !p.small())
         return fail(DG_ERR_UNSUPPORTED, "DG_EXACT_MASKS: exact clamp masks exist on small sample grids (always on there) and on the dense "
                                         "identity grid with C <= 384 (padded to 384), D <= 80, P >= 160, B <= 64, zero_clamp without stabalize");
-    for (int t = 0; t < p.T; ++t) p.maskbits[t] = take((p.xmask || p.xmask_dense) ? B * (size_t)(p.Ppad / 32) * p.Ppad * 4 : 0);
-    // FOLD: gradient passes of the pointwise recipe that k_corr2 runs (dg_corr2_shape_supported: the launcher's own predicate; the
-    // job-level conditions - stationary = operand 1, G tiles wanted, no batch map on R - hold for every gradient pass); DG_FOLD_INTRA=0 keeps the k_gs job (test seam, dg_common.h)
-    {
-        static const bool fold_on = [] { const char* e = getenv("DG_FOLD_INTRA"); return !(e && e[0] == '0'); }();
-        float lo, hi;
-        clamp_bounds(d, lo, hi);
-        p.fold = fold_on && p.grad && p.pointwise && !p.small && dg_corr2_shape_supported(p.KF, p.KD, p.D, lo, hi, p.Ppad, p.B) &&
-                 !p.xmask;          // (with the dense grid's exact mask words too, since round 6: k_corr2<.., XM, .., FOLD>)
-    }
+    p.masks = xmask ? Masks::Sampled : (!xmask_dense ? Masks::None : (p.pointwise ? Masks::DenseSplit : Masks::DenseRaw));
+    for (int t = 0; t < p.T; ++t) p.maskbits[t] = take(p.has_masks() ? B * (size_t)(p.Ppad / 32) * p.Ppad * 4 : 0);
+    // The main kernel.  On a gradient pass every job of the fused launch is a pair-set job with operand 0 stationary, G tiles wanted, no
+    // batch map on R and mask words for all pair-sets or none (build_corr_jobs), so the launcher's own predicate dg_corr2_supported
+    // comes down to its shape part: the plan knows the answer, and the launcher's check is the cross-check (launch_main).
+    p.main = p.small() ? MainKernel::Small
+                       : (p.grad && dg_corr2_shape_supported(p.KF, p.KD, p.D, p.lo, p.hi, p.Ppad, p.B) ? MainKernel::Corr2 : MainKernel::CorrMain);
+    // FOLD: gradient passes of the pointwise recipe that k_corr2 runs (with the dense grid's exact mask words too, since round 6:
+    // k_corr2<.., XM, .., FOLD>); DG_FOLD_INTRA=0 keeps the k_gs job (test seam, dg_common.h)
+    static const bool fold_on = [] { const char* e = getenv("DG_FOLD_INTRA"); return !(e && e[0] == '0'); }();
+    p.fold = fold_on && p.main == MainKernel::Corr2 && p.pointwise && !xmask;
     // fp16 gradient tiles (round 6): the identity grid's backward is ONE launch (k_combine_out) that reads the raw tiles of k_corr2 and the
     // streamed-side tiles of k_gs once - 93 of the headline step's 1342 MB go with fp32 -> fp16 (both producers bounded: the raw tiles by
     // construction, k_gs's by leaving the division by ||c|| to the consumer).  Where k_corr2 runs and k_combine_out will (its routed list
     // holds n_neg x B entries at most 512)
-    {
-        float lo, hi;
-        clamp_bounds(d, lo, hi);
-        p.half = p.ident && p.grad && !p.small && dg_corr2_shape_supported(p.KF, p.KD, p.D, lo, hi, p.Ppad, p.B) &&
-                 p.N * p.B <= 512 && p.S == p.h && p.S == p.w;
-    }
-    for (int i = 0; i < 2; ++i) p.clo[i] = take((p.xmask_dense && p.pointwise) ? B * (size_t)(p.Ppad / 32) * p.KD * 64 : 0);
+    p.half = p.main == MainKernel::Corr2 && ident && p.N * p.B <= 512 && p.S == p.h && p.S == p.w;
+    p.depth_run = (!p.depth || p.small()) ? Depth::None : (!p.grad ? Depth::Job : (p.dense_masks() ? Depth::GsOwnLaunch : Depth::GsBlocks));
+    for (int i = 0; i < 2; ++i) p.clo[i] = take(p.masks == Masks::DenseSplit ? B * (size_t)(p.Ppad / 32) * p.KD * 64 : 0);
     p.gr_list = take((size_t)DG_MAX_JOBS * B * DG_GR_CAP * 4);
     p.gr_count = take((size_t)DG_MAX_JOBS * B * 4);
     p.gr_rank = take((size_t)DG_MAX_JOBS * B * 2);
     {
-        const bool two = p.small && p.grad && p.pointwise;       // the old_mean terms of the gradient (dg_small.hip)
+        const bool sg = p.small() && p.grad, two = sg && p.pointwise;       // two: the old_mean terms of the gradient (dg_small.hip)
         const size_t gt = B * p.Ppad * p.KD * 4;
         for (int t = 0; t < p.T; ++t) {
             p.dRA2[t] = take(two ? gt : 0);
-            p.dRBs[t] = take(p.small && p.grad && p.nsplit == 2 ? gt : 0);
+            p.dRBs[t] = take(sg && p.nsplit == 2 ? gt : 0);
             for (int k = 0; k < 2; ++k) p.dRB2[t][k] = take(two && k < p.nsplit ? gt : 0);
-            p.dRBm[t] = take(p.small && p.grad && t >= 2 && (p.pointwise || p.nsplit == 2) ? gt : 0);
+            p.dRBm[t] = take(sg && t >= 2 && (p.pointwise || p.nsplit == 2) ? gt : 0);
         }
-        p.part4 = take(p.small ? (size_t)(p.T + 1) * B * p.nsplit * 16 : 0);
-        p.om = take(p.small ? (size_t)(p.T + 1) * 4 : 0);
+        p.part4 = take(p.small() ? (size_t)(p.T + 1) * B * p.nsplit * 16 : 0);
+        p.om = take(p.small() ? (size_t)(p.T + 1) * 4 : 0);
     }
     p.total = off;
+    plan_tables(d, p);
     return DG_OK;
 }
 
 extern "C" size_t dg_corr_workspace_bytes(const dg_corr_desc* desc) {
-    Plan p;
+    Plan p{};
     if (make_plan(desc, p) != DG_OK) return 0;
     return p.total;
 }
 
-// operand index used as the S operand (pass A) of pair-set t, and its batch map
-static inline int op_of(const Plan& p, int t) { return t < 2 ? t : (p.shared ? 0 : t); }
-static inline const int64_t* map_of(const Plan& p, int t, const int64_t* perms) {
-    return (t >= 2 && p.shared) ? perms + (size_t)(t - 2) * p.B : nullptr;
-}
-
-static void clamp_bounds(const dg_corr_desc* d, float& lo, float& hi) {
-    lo = (d->flags & DG_ZERO_CLAMP) ? 0.0f : -9999.0f;
-    hi = (d->flags & DG_STABALIZE) ? 0.8f : __builtin_inff();
-}
-
-static float shift_of(const dg_corr_desc* d, int t) { return t == 0 ? d->shift_intra : (t == 1 ? d->shift_inter : d->shift_neg); }
-
 // Fills one helper job.  passB: the stationary operand is operand 2 of pair-set t.
-static DgJob helper_job(const Plan& p, const dg_corr_desc* d, char* ws, int t, bool passB, const int64_t* perms) {
+static DgJob helper_job(const Plan& p, char* ws, int t, bool passB, const int64_t* perms) {
     DgJob j;
     memset(&j, 0, sizeof(j));
-    const int o2 = op_of(p, t);
-    const int64_t* m2 = map_of(p, t, perms);
-    auto F32 = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
+    const int o2 = p.ps[t].op;
+    const int64_t* m2 = p.map_of(t, perms);
     if (!passB) {
-        j.Rop = ws + p.op[0]; j.RcInv = F32(p.inv[0]); j.ridx = nullptr;
+        j.Rop = ws + p.op[0]; j.RcInv = f32(ws, p.inv[0]); j.ridx = nullptr;
         j.Sop = ws + p.op[o2]; j.sidx = m2;
-        j.Scsum = F32(p.csum[o2]);
+        j.Scsum = f32(ws, p.csum[o2]);
         j.center_on_lane = 1;
     } else {
-        j.Rop = ws + p.op[o2]; j.RcInv = F32(p.inv[o2]); j.ridx = m2;
+        j.Rop = ws + p.op[o2]; j.RcInv = f32(ws, p.inv[o2]); j.ridx = m2;
         j.Sop = ws + p.op[0]; j.sidx = nullptr;
         j.center_on_lane = 0;
     }
-    if (p.pointwise) { j.rvec = F32(p.rvec[t]); j.rimg = F32(p.rimg[t]); }
-    j.shift = shift_of(d, t);
+    if (p.pointwise) { j.rvec = f32(ws, p.rvec[t]); j.rimg = f32(ws, p.rimg[t]); }
+    j.shift = p.ps[t].shift;
     j.kind = DG_JOB_HELPER;
     return j;
 }
 
-static DgJob depth_job(const Plan& p, const dg_corr_desc* d, char* ws) {
+static DgJob depth_job(const Plan& p, char* ws) {
     DgJob j;
     memset(&j, 0, sizeof(j));
-    auto F32 = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
-    j.Rop = ws + p.op[0]; j.Sop = ws + p.op[0]; j.RcInv = F32(p.inv[0]);
-    j.nzR = F32(p.nz); j.nzS = F32(p.nz);
-    j.shift = d->shift_depth;
+    j.Rop = ws + p.op[0]; j.Sop = ws + p.op[0]; j.RcInv = f32(ws, p.inv[0]);
+    j.nzR = f32(ws, p.nz); j.nzS = f32(ws, p.nz);
+    j.shift = p.shift_depth;
     j.kind = DG_JOB_DEPTH;
     j.center_on_lane = 1;
     return j;
 }
 
-static void corr_args_base(const Plan& p, const dg_corr_desc* d, char* ws, DgCorrArgs& a) {
+static void corr_args_base(const Plan& p, char* ws, DgCorrArgs& a) {
     memset(&a, 0, sizeof(a));
     a.B = p.B; a.P = p.P; a.Ppad = p.Ppad; a.nrb = p.nrb; a.D = p.D;
-    clamp_bounds(d, a.lo, a.hi);
+    a.lo = p.lo; a.hi = p.hi;
     a.inv_BP = 1.0f / ((float)p.B * (float)p.P);
     a.dummy = ws + p.op[0];
     a.span = g_prof_span;
     a.half_tiles = p.half ? 1 : 0;
 }
 
-
 // k_gs jobs: one per pair-set; the producing job of the G tiles is helper_job(t) of the fused launch (R = operand 1,
-// S = operand 2 of pair-set t)
-// Without `pointwise` the intra pair-set (t = 0) has NO job here (round 4): it correlates the anchors with themselves at the same
-// coordinates, so fd, cd and with them -G are symmetric and the gradient through the streamed side equals the one through the
-// stationary side, which the fused kernel accumulates in registers anyway - the backward doubles that one (as it always did for the
-// depth term) instead of reading 1/7 of the G tiles again.  With `pointwise` -G is NOT symmetric: the reference centres fd by its
-// ROW means only (fd -= fd.mean([3, 4]), src/modules.py:1238-1239), -G[p][q] - -G[q][p] = mask (rowmean_q - rowmean_p) - invisible
-// on i.i.d. features, 1e-2 of the gradient on the FPS recipes (the test with exact masks caught it).
-// (p.fold: with `pointwise` k_corr2 forms G + G^T in its own accumulator, dg_corr2.hip FOLD - the same consequence for the launches)
-static bool intra_is_symmetric(const Plan& p) { return !p.pointwise || p.fold; }
+// S = operand 2 of pair-set t).  The intra pair-set has none where its -G is symmetric (Plan::intra_symmetric)
 static void build_gs_jobs(const Plan& p, char* ws, const int64_t* perms, DgGsArgs& g) {
     memset(&g, 0, sizeof(g));
-    const int t0 = intra_is_symmetric(p) ? 1 : 0;
+    const int t0 = p.intra_symmetric() ? 1 : 0;
     g.njobs = p.T - t0; g.B = p.B; g.P = p.P; g.Ppad = p.Ppad; g.KF = p.KF; g.KD = p.KD; g.D = p.D;
     for (int t = t0; t < p.T; ++t) {
-        const int o2 = op_of(p, t);
+        const int o2 = p.ps[t].op;
         DgGsJob& J = g.jobs[t - t0];
         J.G = reinterpret_cast<const uint16_t*>(ws + p.gbuf[t]);
         J.Rop = ws + p.op[0]; J.ridx = nullptr;
-        J.Sop = ws + p.op[o2]; J.sidx = map_of(p, t, perms);
-        J.ScInv = reinterpret_cast<const float*>(ws + p.inv[o2]);
-        J.dS = reinterpret_cast<float*>(ws + p.dRB[t]);
+        J.Sop = ws + p.op[o2]; J.sidx = p.map_of(t, perms);
+        J.ScInv = f32(ws, p.inv[o2]);
+        J.dS = f32(ws, p.dRB[t]);
     }
 }
 
 // Job table of the fused correlation launch: one job per pair-set (stationary = operand 1); on forward-only calls the cheap
-// depth job last.
-// Returns the number of pair-set jobs; *depth_index = position of the depth job or -1.  (Stationary = operand 2 is only
-// used by dg_corr_materialize, whose stores then run along the second position index.)
-static int build_corr_jobs(const Plan& p, const dg_corr_desc* desc, char* ws, const int64_t* perms, DgCorrArgs& a,
-                           int* depth_index) {
-    auto F32 = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
-    corr_args_base(p, desc, ws, a);
+// depth job last (Depth::Job).  (Stationary = operand 2 is only used by dg_corr_materialize, whose stores then run along the
+// second position index.)
+static void build_corr_jobs(const Plan& p, char* ws, const int64_t* perms, DgCorrArgs& a) {
+    corr_args_base(p, ws, a);
     a.wctr = p.grad ? reinterpret_cast<uint32_t*>(ws + p.ticket) + 16 : nullptr;      // (behind the depth blocks' ticket word)
-    const double numel = (double)p.B * p.P * p.P;
     int nj = 0;
     for (int t = 0; t < p.T; ++t) {
-        DgJob j = helper_job(p, desc, ws, t, false, perms);
-        j.part = F32(p.part[t]);
-        j.dR = p.grad ? F32(p.dRA[t]) : nullptr;
+        DgJob j = helper_job(p, ws, t, false, perms);
+        j.part = f32(ws, p.part[t]);
+        j.dR = p.grad ? f32(ws, p.dRA[t]) : nullptr;
+        // (the gradient of the streamed operand's code comes from k_gs, which consumes the G tiles these jobs store)
         j.Gout = p.grad ? reinterpret_cast<uint16_t*>(ws + p.gbuf[t]) : nullptr;
         j.fold = (p.fold && t == 0) ? 1 : 0;
-        j.maskbits = (p.xmask || p.xmask_dense) ? reinterpret_cast<const uint32_t*>(ws + p.maskbits[t]) : nullptr;
-        j.slot_loss = t < 2 ? t : DG_OUT_LOSS_NEG;
-        j.slot_cd = t < 2 ? DG_OUT_CD_INTRA + t : DG_OUT_CD_NEG;
-        j.fin_scale = (float)(1.0 / (t < 2 ? numel : numel * p.N));
+        j.maskbits = p.has_masks() ? reinterpret_cast<const uint32_t*>(ws + p.maskbits[t]) : nullptr;
+        j.slot_loss = p.ps[t].slot_loss; j.slot_cd = p.ps[t].slot_cd; j.fin_scale = p.ps[t].fin_scale;
         a.jobs[nj++] = j;
     }
-    const int njA = nj;
-    // (the gradient of the streamed operand's code comes from k_gs, which consumes the G tiles these jobs store)
-    *depth_index = -1;
-    // (on a gradient pass the depth term runs as blocks of the k_gs launch, dg_corr.hip gs_depth_block: in the fused kernel's
-    //  launch its latency-bound blocks were the tail)
-    if (p.depth && !p.grad) {
-        DgJob j = depth_job(p, desc, ws);
-        j.part = F32(p.part[p.T]);
+    if (p.depth_run == Depth::Job) {
+        DgJob j = depth_job(p, ws);
+        j.part = f32(ws, p.part[p.T]);
         j.dR = nullptr;
-        j.slot_loss = DG_OUT_LOSS_DEPTH; j.slot_cd = -1; j.fin_scale = (float)(1.0 / numel);
-        *depth_index = nj;
+        j.slot_loss = DG_OUT_LOSS_DEPTH; j.slot_cd = -1; j.fin_scale = p.inv_numel;
         a.jobs[nj++] = j;
     }
     a.njobs = nj;
-    // Ragged last row blocks grouped by streamed operand (dg_corr2.hip): pair-sets that stream the same operand array form a
-    // key.  Worth it when the ragged row block is short (at most 4 of the 8 row tiles) and several pair-sets share an array
-    // (shared coordinates: intra + the negatives stream operand 0 through batch maps).
-    a.gr_list = nullptr;
-    {
-        const int nt = p.Ppad / 32, L = nt % 8;
-        if (p.grad && p.KF == 384 && p.KD == 96 && p.D <= 80 && p.nrb > 1 && L >= 1 && L <= 4 && p.B % 8 == 0 && p.B <= 64 && njA >= 2) {
-            int nkeys = 0, members[DG_MAX_JOBS] = {0};
-            for (int j = 0; j < njA; ++j) {
-                int k = -1;
-                for (int q = 0; q < nkeys; ++q) if (a.jobs[(int)a.gr_first[q]].Sop == a.jobs[j].Sop) k = q;
-                if (k < 0) { k = nkeys++; a.gr_first[k] = (int8_t)j; }
-                a.gr_key[j] = (int8_t)k; ++members[k];
-            }
-            bool shared_any = false;
-            for (int k = 0; k < nkeys; ++k) shared_any |= members[k] > 1;
-            if (shared_any) {
-                a.gr_nkeys = nkeys; a.gr_cpb = 8 / L; a.gr_blocks_per_image = 0;
-                for (int k = 0; k < nkeys; ++k) {
-                    const bool single = members[k] == 1 && a.jobs[(int)a.gr_first[k]].sidx == nullptr;      // exactly one consumer per image
-                    int nb = single ? 1 : (5 * members[k] / 2 + a.gr_cpb - 1) / a.gr_cpb;           // 2.5 x the mean consumer count
-                    const int cap = (DG_GR_CAP + a.gr_cpb - 1) / a.gr_cpb;
-                    a.gr_nblk[k] = nb > cap ? cap : nb;
-                    a.gr_blocks_per_image += a.gr_nblk[k];
-                }
-                a.gr_list = reinterpret_cast<const int32_t*>(ws + p.gr_list);
-                a.gr_count = reinterpret_cast<const int32_t*>(ws + p.gr_count);
-                a.gr_rank = reinterpret_cast<const int16_t*>(ws + p.gr_rank);
-            }
-        }
+    // the grouped ragged row blocks (key and first ride along wherever the shape is eligible; the kernels read them with gr_list only)
+    memcpy(a.gr_key, p.gr_key, sizeof(a.gr_key)); memcpy(a.gr_first, p.gr_first, sizeof(a.gr_first));
+    if (p.gr_on) {
+        a.gr_nkeys = p.gr_nkeys; a.gr_cpb = p.gr_cpb; a.gr_blocks_per_image = p.gr_blocks_per_image;
+        memcpy(a.gr_nblk, p.gr_nblk, sizeof(a.gr_nblk));
+        a.gr_list = reinterpret_cast<const int32_t*>(ws + p.gr_list);
+        a.gr_count = reinterpret_cast<const int32_t*>(ws + p.gr_count);
+        a.gr_rank = reinterpret_cast<const int16_t*>(ws + p.gr_rank);
     }
-    return njA;
 }
 
-// Fused correlation launch.  Gradient passes of the ViT-S widths run the one-wave-per-SIMD kernel (dg_corr2.hip); everything else
-// (forward-only calls, stabalize / no zero_clamp, ViT-B widths, small P) k_corr_main.
-static hipError_t launch_main(const Plan& p, const DgCorrArgs& a, int njA, int depth_index, hipStream_t stream) {
-    (void)depth_index;
-    if (p.grad && njA > 0) {
+// Fused correlation launch: the kernel the plan names.  dg_launch_corr2 checks its own predicate once more (dg_corr2_supported):
+// a refusal there means the plan and the launcher disagree - an internal error, not a reason to run another kernel.
+static int launch_main(const Plan& p, const DgCorrArgs& a, hipStream_t stream) {
+    if (p.main == MainKernel::Corr2) {
         const hipError_t e = dg_launch_corr2(a, p.KF, p.KD, stream);      // the pair-set jobs, one launch
-        if (e != hipErrorNotSupported) return e;
-        if (p.fold || p.half) return hipErrorInvalidValue;          // (the plan folded the intra pair-set / asked for fp16 tiles of a kernel that does not run)
+        if (e == hipErrorNotSupported) return fail(DG_ERR_LAUNCH, "internal: the plan chose k_corr2 for a launch dg_corr2_supported refuses");
+        if (e != hipSuccess) return fail(DG_ERR_LAUNCH, "%s failed: %s", "dg_launch_corr2(a, p.KF, p.KD, stream)", hipGetErrorString(e));
+        return DG_OK;
     }
-    return dg_launch_corr(a, p.KF, p.KD, p.rf, p.grad ? 1 : 0, stream);
+    DG_HIP(dg_launch_corr(a, p.KF, p.KD, p.rf, p.grad ? 1 : 0, stream));
+    return DG_OK;
 }
 
 struct DrawArgs { int64_t* out; uint64_t seed; unsigned long long* state; };
@@ -349,24 +408,22 @@ static bool split_masks_enabled() {
 // the argument block of the fused small-grid kernel (dg_small.hip): forward, materialize and relaunch
 static void small_args(const Plan& p, const dg_corr_desc* d, char* ws, const int64_t* perms, DgSmallArgs& a) {
     memset(&a, 0, sizeof(a));
-    auto F32 = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
-    for (int o = 0; o < p.nops; ++o) { a.rowsF[o] = F32(p.rows_f[o]); a.rowsC[o] = F32(p.rows_c[o]); }
+    for (int o = 0; o < p.nops; ++o) { a.rowsF[o] = f32(ws, p.rows_f[o]); a.rowsC[o] = f32(ws, p.rows_c[o]); }
     a.T = p.T; a.B = p.B; a.P = p.P; a.Ppad = p.Ppad; a.C4 = (int)up(p.C, 128); a.D = p.D; a.D4 = p.D4; a.KD = p.KD;
     a.pointwise = p.pointwise ? 1 : 0; a.depth = p.depth ? 1 : 0; a.grad = p.grad ? 1 : 0;
-    clamp_bounds(d, a.lo, a.hi);
-    for (int t = 0; t < p.T; ++t) { a.shift[t] = shift_of(d, t); a.opS[t] = op_of(p, t); a.sidx[t] = map_of(p, t, perms); }
-    a.shift_depth = d->shift_depth;
-    a.nz = F32(p.nz); a.nzsum = F32(p.nzsum);
-    for (int t = 0; t <= p.T; ++t) a.dRA[t] = F32(p.dRA[t]);
+    a.lo = p.lo; a.hi = p.hi;
+    for (int t = 0; t < p.T; ++t) { a.shift[t] = p.ps[t].shift; a.opS[t] = p.ps[t].op; a.sidx[t] = p.map_of(t, perms); }
+    a.shift_depth = p.shift_depth;
+    a.nz = f32(ws, p.nz); a.nzsum = f32(ws, p.nzsum);
+    for (int t = 0; t <= p.T; ++t) a.dRA[t] = f32(ws, p.dRA[t]);
     for (int t = 0; t < p.T; ++t) {
-        a.dRA2[t] = F32(p.dRA2[t]);
-        a.dRB[t][0] = F32(p.dRB[t]); a.dRB[t][1] = F32(p.dRBs[t]);
-        a.dRB2[t][0] = F32(p.dRB2[t][0]); a.dRB2[t][1] = F32(p.dRB2[t][1]);
+        a.dRA2[t] = f32(ws, p.dRA2[t]);
+        a.dRB[t][0] = f32(ws, p.dRB[t]); a.dRB[t][1] = f32(ws, p.dRBs[t]);
+        a.dRB2[t][0] = f32(ws, p.dRB2[t][0]); a.dRB2[t][1] = f32(ws, p.dRB2[t][1]);
     }
-    a.part = F32(p.part4); a.om = F32(p.om);
+    a.part = f32(ws, p.part4); a.om = f32(ws, p.om);
     a.ticket = reinterpret_cast<unsigned int*>(ws + p.ticket) + 32;
-    const DgBlob bl(p.KF, p.KD);
-    a.xop = ws + p.op[0]; a.xinv = F32(p.inv[0]); a.blob_bytes = bl.bytes; a.blob_off_c = bl.off_c;
+    a.xop = ws + p.op[0]; a.xinv = f32(ws, p.inv[0]); a.blob_bytes = p.blob; a.blob_off_c = p.blob_off_c;
     a.wtot[0] = d->w_intra; a.wtot[1] = d->w_inter; a.wtot[2] = d->w_neg; a.wtot[3] = d->w_depth;
     a.nsplit = p.nsplit;
     a.span = g_prof_span;
@@ -379,7 +436,7 @@ struct FeatKeep { const float* keep[2]; float scale; };      // deferred Dropout
 
 // ---- the forward call: what its stages share
 struct Fwd {
-    Plan p;
+    Plan p{};
     const dg_corr_desc* desc;
     const float *feats, *feats_pos, *code, *code_pos, *depth, *coords1, *coords2;
     const int64_t* perms; const DrawArgs* draw; const FeatKeep* fk; const float* feat_inv;
@@ -389,17 +446,17 @@ struct Fwd {
     //  under `split`, and the k_gs launches, which re-use it)
     std::optional<SideRegion> side;
     bool split;
-    DgCorrArgs a;                       // the launch plan of step 4 (build_corr_jobs): steps 3 and 5 read it
-    int njA, depth_index;
-    float* f32(size_t off) const { return reinterpret_cast<float*>(ws + off); }
+    DgCorrArgs a;                       // the job table of step 4 (build_corr_jobs): steps 3 and 5 read it
+    const float* coords(int o) const { return p.ops[o].cset ? coords2 : coords1; }
+    const int64_t* op_map(int o) const { return p.batch_map(p.ops[o].map, perms); }
 };
 
 static int fwd_validate(Fwd& c, void* workspace, size_t workspace_bytes) {
     const Plan& p = c.p;
-    if (c.feat_inv && (p.ident || p.small))
+    if (c.feat_inv && p.prep != Prep::General)
         return fail(DG_ERR_INVALID, "dg_corr_forward_extnorm is the sampled-coordinate path above 160 positions: the identity grid takes "
                                     "DG_FEATS_UNIT, smaller grids any width as they are");
-    if (c.fk && (c.fk->keep[0] || c.fk->keep[1]) && !p.ident)
+    if (c.fk && (c.fk->keep[0] || c.fk->keep[1]) && !p.dense())
         return fail(DG_ERR_UNSUPPORTED, "deferred feature dropout (feat_keep) is built for the identity grid only: "
                                         "with sampled coordinates hand the dropped features in");
     if (!c.feats || !c.feats_pos || !c.code || !c.code_pos || !c.coords1 || !c.coords2 || !c.out || !workspace)
@@ -419,14 +476,14 @@ static int pre_args(const Fwd& c, DgPreArgs& q) {
     const Plan& p = c.p;
     memset(&q, 0, sizeof(q));
     if (c.draw && p.N > 0) { q.seed = c.draw->seed; q.state = c.draw->state; q.perms = c.draw->out; q.count = p.N; }
-    if (p.depth) { q.depth = c.depth; q.nz = c.f32(p.nz); q.nzsum = c.f32(p.nzsum); q.dH = c.desc->depth_h; q.dW = c.desc->depth_w; }
+    if (p.depth) { q.depth = c.depth; q.nz = f32(c.ws, p.nz); q.nzsum = f32(c.ws, p.nzsum); q.dH = c.desc->depth_h; q.dW = c.desc->depth_w; }
     if (p.grad && (size_t)p.hc * p.wc <= 4096 && p.P <= 65535) { q.coords1 = c.coords1; q.coords2 = c.coords2; q.taps = c.ws + p.taps; }
     q.B = p.B; q.h = p.hc; q.w = p.wc; q.S = p.S; q.Sh = p.Sh; q.P = p.P; q.Ppad = p.Ppad;      // (h, w): the maps the tap records index = the code maps
     if (p.B > 8192 && q.count > 0) return fail(DG_ERR_UNSUPPORTED, "B=%d too large for the in-call draw", p.B);
     return DG_OK;
 }
 
-// sample() straight from NCHW into rows per operand (p.rows); bf16_rows: feature rows as the fused small-grid kernel takes them
+// sample() straight from NCHW into rows per operand (Sampler::Plane); bf16_rows: feature rows as the fused small-grid kernel takes them
 static int plane_sample(const Fwd& c, bool bf16_rows) {
     const Plan& p = c.p;
     DgPlaneArgs t;
@@ -434,7 +491,7 @@ static int plane_sample(const Fwd& c, bool bf16_rows) {
     t.src[0] = c.feats; t.src[1] = c.feats_pos; t.src[2] = c.code; t.src[3] = c.code_pos;
     t.K[0] = t.K[1] = p.C; t.K4[0] = t.K4[1] = bf16_rows ? (int)up(p.C, 128) : p.C4; t.K[2] = t.K[3] = p.D; t.K4[2] = t.K4[3] = p.D4;
     t.feats_bf16 = bf16_rows ? 1 : 0;
-    for (int o = 0; o < p.nops; ++o) { t.rows[o][0] = c.f32(p.rows_f[o]); t.rows[o][1] = c.f32(p.rows_c[o]); }
+    for (int o = 0; o < p.nops; ++o) { t.rows[o][0] = f32(c.ws, p.rows_f[o]); t.rows[o][1] = f32(c.ws, p.rows_c[o]); }
     t.coords1 = c.coords1; t.coords2 = c.coords2; t.perms = c.perms;
     t.nops = p.nops; t.B = p.B; t.h = p.h; t.w = p.w; t.S = p.S; t.Sh = p.Sh; t.P = p.P;
     DG_HIP(dg_launch_plane_sample(t, c.stream));
@@ -447,10 +504,10 @@ static int transpose_maps(const Fwd& c) {
     DgTransposeArgs t;
     memset(&t, 0, sizeof(t));
     t.nmaps = 4;
-    t.src[0] = c.feats; t.dst[0] = c.f32(p.nhwc_f[0]); t.K[0] = p.C; t.K4[0] = p.C4; t.HW[0] = p.h * p.w;
-    t.src[1] = c.feats_pos; t.dst[1] = c.f32(p.nhwc_f[1]); t.K[1] = p.C; t.K4[1] = p.C4; t.HW[1] = p.h * p.w;
-    t.src[2] = c.code; t.dst[2] = c.f32(p.nhwc_c[0]); t.K[2] = p.D; t.K4[2] = p.D4; t.HW[2] = p.hc * p.wc;
-    t.src[3] = c.code_pos; t.dst[3] = c.f32(p.nhwc_c[1]); t.K[3] = p.D; t.K4[3] = p.D4; t.HW[3] = p.hc * p.wc;
+    t.src[0] = c.feats; t.dst[0] = f32(c.ws, p.nhwc_f[0]); t.K[0] = p.C; t.K4[0] = p.C4; t.HW[0] = p.h * p.w;
+    t.src[1] = c.feats_pos; t.dst[1] = f32(c.ws, p.nhwc_f[1]); t.K[1] = p.C; t.K4[1] = p.C4; t.HW[1] = p.h * p.w;
+    t.src[2] = c.code; t.dst[2] = f32(c.ws, p.nhwc_c[0]); t.K[2] = p.D; t.K4[2] = p.D4; t.HW[2] = p.hc * p.wc;
+    t.src[3] = c.code_pos; t.dst[3] = f32(c.ws, p.nhwc_c[1]); t.K[3] = p.D; t.K4[3] = p.D4; t.HW[3] = p.hc * p.wc;
     DG_HIP(dg_launch_transpose(t, p.B, c.stream));
     return DG_OK;
 }
@@ -459,9 +516,9 @@ static int transpose_maps(const Fwd& c) {
 static void cd_mask_args(const Fwd& c, const size_t* rows, DgCdMaskArgs& m) {
     const Plan& p = c.p;
     memset(&m, 0, sizeof(m));
-    m.rowsR = c.f32(rows[0]);
+    m.rowsR = f32(c.ws, rows[0]);
     for (int t = 0; t < p.T; ++t) {
-        m.rowsS[t] = c.f32(rows[op_of(p, t)]); m.sidx[t] = map_of(p, t, c.perms);
+        m.rowsS[t] = f32(c.ws, rows[p.ps[t].op]); m.sidx[t] = p.map_of(t, c.perms);
         m.bits[t] = reinterpret_cast<uint32_t*>(c.ws + p.maskbits[t]);
     }
     m.T = p.T; m.B = p.B; m.P = p.P; m.Ppad = p.Ppad; m.D = p.D; m.D4 = p.D4;
@@ -479,7 +536,7 @@ static int forward_small(const Fwd& c) {
     DgPreArgs q;
     if (int rc = pre_args(c, q)) return rc;
     DG_HIP(dg_launch_pre_general(q, c.stream));
-    if (p.rows) {
+    if (p.plane()) {
         if (int rc = plane_sample(c, true)) return rc;
     } else {
         // code maps of another size than the feature maps (the FeaturePyramidNet contract) or maps beyond the plane sampler's LDS:
@@ -489,12 +546,10 @@ static int forward_small(const Fwd& c) {
         memset(&g, 0, sizeof(g));
         int nj = 0;
         for (int o = 0; o < p.nops; ++o) {
-            const int srcsel = o == 1 ? 1 : 0;          // op 1 reads the *_pos maps, negatives read orig_feats / orig_code
-            const float* coords = o == 0 ? c.coords1 : c.coords2;
-            const int64_t* idx = o >= 2 ? c.perms + (size_t)(o - 2) * p.B : nullptr;
-            g.src[nj] = c.f32(p.nhwc_f[srcsel]); g.coords[nj] = coords; g.srcidx[nj] = idx; g.rows[nj] = c.f32(p.rows_f[o]);
+            const int srcsel = p.ops[o].srcsel;
+            g.src[nj] = f32(c.ws, p.nhwc_f[srcsel]); g.coords[nj] = c.coords(o); g.srcidx[nj] = c.op_map(o); g.rows[nj] = f32(c.ws, p.rows_f[o]);
             g.K4[nj] = p.C4; g.Kout[nj] = (int)up(p.C, 128); g.as_bf16[nj] = 1; g.h[nj] = p.h; g.w[nj] = p.w; ++nj;
-            g.src[nj] = c.f32(p.nhwc_c[srcsel]); g.coords[nj] = coords; g.srcidx[nj] = idx; g.rows[nj] = c.f32(p.rows_c[o]);
+            g.src[nj] = f32(c.ws, p.nhwc_c[srcsel]); g.coords[nj] = c.coords(o); g.srcidx[nj] = c.op_map(o); g.rows[nj] = f32(c.ws, p.rows_c[o]);
             g.K4[nj] = p.D4; g.Kout[nj] = p.D4; g.as_bf16[nj] = 0; g.h[nj] = p.hc; g.w[nj] = p.wc; ++nj;
         }
         g.njobs = nj; g.B = p.B; g.S = p.S; g.Sh = p.Sh; g.P = p.P;
@@ -512,8 +567,8 @@ static int fwd_operands_dense(Fwd& c) {
     DgDenseArgs g;
     memset(&g, 0, sizeof(g));
     g.src[0] = c.feats; g.src[1] = c.feats_pos; g.code[0] = c.code; g.code[1] = c.code_pos;
-    for (int o = 0; o < 2; ++o) { g.blob[o] = c.ws + p.op[o]; g.colpart[o] = c.f32(p.colpart[o]); g.inv_norm[o] = c.f32(p.inv[o]); g.ccolpart[o] = c.f32(p.ccolpart[o]); }
-    g.depth = p.depth ? c.depth : nullptr; g.nz = c.f32(p.nz); g.nzsum = c.f32(p.nzsum);
+    for (int o = 0; o < 2; ++o) { g.blob[o] = c.ws + p.op[o]; g.colpart[o] = f32(c.ws, p.colpart[o]); g.inv_norm[o] = f32(c.ws, p.inv[o]); g.ccolpart[o] = f32(c.ws, p.ccolpart[o]); }
+    g.depth = p.depth ? c.depth : nullptr; g.nz = f32(c.ws, p.nz); g.nzsum = f32(c.ws, p.nzsum);
     g.B = p.B; g.K = p.C; g.D = p.D; g.KF = p.KF; g.KD = p.KD; g.h = p.h; g.w = p.w; g.P = p.P; g.Ppad = p.Ppad;
     g.dH = c.desc->depth_h; g.dW = c.desc->depth_w;
     g.code_split = p.pointwise ? 1 : 0;        // (the code column sums then ride in the k_rowmean launch, which only pointwise has)
@@ -529,15 +584,15 @@ static int fwd_operands_dense(Fwd& c) {
         DG_HIP(dg_launch_prep_dense(gs, c.side->stream()));
     }
     DG_HIP(dg_launch_prep_dense(g, c.stream));
-    if (p.xmask_dense && !p.pointwise) {
+    if (p.masks == Masks::DenseRaw) {
         // exact clamp masks without `pointwise` (the code operands are then built by k_prep_dense itself, without the parts the
         // split-fp16 form of fwd_cd_mask3 needs): position-major fp32 rows of the two code maps (on this grid position p IS pixel p),
         // then the sign of every raw fp32 dot product (k_cd_mask) as one word per (S tile, R position) for all pair-sets
         DgTransposeArgs t;
         memset(&t, 0, sizeof(t));
         t.nmaps = 2;
-        t.src[0] = c.code; t.dst[0] = c.f32(p.nhwc_c[0]); t.K[0] = p.D; t.K4[0] = p.D4; t.HW[0] = p.h * p.w;
-        t.src[1] = c.code_pos; t.dst[1] = c.f32(p.nhwc_c[1]); t.K[1] = p.D; t.K4[1] = p.D4; t.HW[1] = p.h * p.w;
+        t.src[0] = c.code; t.dst[0] = f32(c.ws, p.nhwc_c[0]); t.K[0] = p.D; t.K4[0] = p.D4; t.HW[0] = p.h * p.w;
+        t.src[1] = c.code_pos; t.dst[1] = f32(c.ws, p.nhwc_c[1]); t.K[1] = p.D; t.K4[1] = p.D4; t.HW[1] = p.h * p.w;
         DG_HIP(dg_launch_transpose(t, p.B, c.stream));
         DgCdMaskArgs m;
         cd_mask_args(c, p.nhwc_c, m);
@@ -558,30 +613,29 @@ static int fwd_operands_general(Fwd& c) {
     pre_late.count = 0;
     q.depth = nullptr; q.taps = nullptr;
     DG_HIP(dg_launch_pre_general(q, c.stream));
-    if (int rc = p.rows ? plane_sample(c, false) : transpose_maps(c)) return rc;
+    if (int rc = p.plane() ? plane_sample(c, false) : transpose_maps(c)) return rc;
     DgGatherArgs g;
     memset(&g, 0, sizeof(g));
     g.B = p.B; g.S = p.S; g.Sh = p.Sh; g.P = p.P; g.Ppad = p.Ppad; g.KF = p.KF; g.KD = p.KD;
     int nj = 0;
     for (int o = 0; o < p.nops; ++o) {
-        const int srcsel = o == 1 ? 1 : 0;          // op 1 reads the *_pos maps, negatives read orig_feats/orig_code
-        const float* coords = o == 0 ? c.coords1 : c.coords2;
-        const int64_t* idx = o >= 2 ? c.perms + (size_t)(o - 2) * p.B : nullptr;
+        const int srcsel = p.ops[o].srcsel;
+        const int64_t* idx = p.plane() ? nullptr : c.op_map(o);       // (the plane sampler's rows are sampled through the batch maps already)
         DgGatherJob& f = g.jobs[nj++];
-        f.src = p.rows ? c.f32(p.rows_f[o]) : c.f32(p.nhwc_f[srcsel]); f.coords = coords; f.srcidx = p.rows ? nullptr : idx;
-        f.blob = c.ws + p.op[o]; f.inv_norm = nullptr; f.colpart = c.f32(p.colpart[o]);
+        f.src = p.plane() ? f32(c.ws, p.rows_f[o]) : f32(c.ws, p.nhwc_f[srcsel]); f.coords = c.coords(o); f.srcidx = idx;
+        f.blob = c.ws + p.op[o]; f.inv_norm = nullptr; f.colpart = f32(c.ws, p.colpart[o]);
         f.ext_inv = c.feat_inv ? c.feat_inv + (size_t)o * p.B * p.P : nullptr;
         f.K = p.C; f.K4 = p.C4; f.Kpad = p.KF; f.is_code = 0; f.h = p.h; f.w = p.w;
         DgGatherJob& k = g.jobs[nj++];
-        k.src = p.rows ? c.f32(p.rows_c[o]) : c.f32(p.nhwc_c[srcsel]); k.coords = coords; k.srcidx = p.rows ? nullptr : idx;
-        k.blob = c.ws + p.op[o]; k.inv_norm = c.f32(p.inv[o]); k.colpart = c.f32(p.ccolpart[o]);
+        k.src = p.plane() ? f32(c.ws, p.rows_c[o]) : f32(c.ws, p.nhwc_c[srcsel]); k.coords = c.coords(o); k.srcidx = idx;
+        k.blob = c.ws + p.op[o]; k.inv_norm = f32(c.ws, p.inv[o]); k.colpart = f32(c.ws, p.ccolpart[o]);
         k.K = p.D; k.K4 = p.D4; k.Kpad = p.KD; k.is_code = 1; k.h = p.hc; k.w = p.wc;
     }
     g.njobs = nj;
-    g.direct = p.rows ? 1 : 0;
+    g.direct = p.plane() ? 1 : 0;
     // exact clamp masks of the small sample grids: the sign of every fp32 code dot product from the sampled rows
     // (k_plane_sample's, like the gather's input) - extra blocks of the gather launch (its own launch until round 4)
-    if (p.xmask) cd_mask_args(c, p.rows_c, g.cd);
+    if (p.masks == Masks::Sampled) cd_mask_args(c, p.rows_c, g.cd);
     g.pre = pre_late;
     DG_HIP(dg_launch_gather(g, p.KF, c.stream));
     return DG_OK;
@@ -595,24 +649,24 @@ static int fwd_colmeans(Fwd& c) {
     memset(&m, 0, sizeof(m));
     m.nops = p.nops; m.B = p.B; m.P = p.P; m.Ppad = p.Ppad; m.KF = p.KF; m.KD = p.KD;
     for (int o = 0; o < p.nops; ++o) {
-        m.colpart[o] = p.pointwise ? c.f32(p.colpart[o]) : nullptr; m.bbar[o] = c.f32(p.bbar[o]);
+        m.colpart[o] = p.pointwise ? f32(c.ws, p.colpart[o]) : nullptr; m.bbar[o] = f32(c.ws, p.bbar[o]);
         m.bsplit[o] = reinterpret_cast<__bf16*>(c.ws + p.bsplit[o]);
         m.ngroups[o] = p.Ppad / 32;              // feats partial column sums: one group per tile on both paths
-        m.ccolpart[o] = c.f32(p.ccolpart[o]); m.csum[o] = c.f32(p.csum[o]);
+        m.ccolpart[o] = f32(c.ws, p.ccolpart[o]); m.csum[o] = f32(c.ws, p.csum[o]);
     }
-    m.zero_word = (p.grad && p.depth) ? reinterpret_cast<unsigned int*>(c.ws + p.ticket) : nullptr;
+    m.zero_word = p.depth_in_gs() ? reinterpret_cast<unsigned int*>(c.ws + p.ticket) : nullptr;
     m.zero_words9 = a.wctr;
-    if (a.gr_list) {           // the consumer lists of k_corr2's grouped ragged blocks ride along (extra blocks of this launch)
-        const int nd = a.jobs[a.njobs - 1].kind == DG_JOB_DEPTH ? 1 : 0;
-        m.gr.nh = a.njobs - nd; m.gr.nkeys = a.gr_nkeys; m.gr.B = p.B;
-        for (int j = 0; j < m.gr.nh; ++j) { m.gr.sidx[j] = a.jobs[j].sidx; m.gr.key[j] = a.gr_key[j]; }
-        m.gr.list = const_cast<int32_t*>(a.gr_list); m.gr.count = const_cast<int32_t*>(a.gr_count); m.gr.rank = const_cast<int16_t*>(a.gr_rank);
+    if (p.gr_on) {             // the consumer lists of k_corr2's grouped ragged blocks ride along (extra blocks of this launch)
+        m.gr.nh = p.T; m.gr.nkeys = p.gr_nkeys; m.gr.B = p.B;
+        for (int t = 0; t < p.T; ++t) { m.gr.sidx[t] = p.map_of(t, c.perms); m.gr.key[t] = p.gr_key[t]; }
+        m.gr.list = reinterpret_cast<int32_t*>(c.ws + p.gr_list); m.gr.count = reinterpret_cast<int32_t*>(c.ws + p.gr_count);
+        m.gr.rank = reinterpret_cast<int16_t*>(c.ws + p.gr_rank);
     }
-    if (p.ident && p.pointwise) {         // dense code operands from channel planes (norms: k_prep_dense; csum: k_rowmean launch)
+    if (p.dense() && p.pointwise) {       // dense code operands from channel planes (norms: k_prep_dense; csum: k_rowmean launch)
         m.dc.code[0] = c.code; m.dc.code[1] = c.code_pos;
-        for (int o = 0; o < 2; ++o) { m.dc.blob[o] = c.ws + p.op[o]; m.dc.inv_norm[o] = c.f32(p.inv[o]); m.dc.ccolpart[o] = c.f32(p.ccolpart[o]); }
+        for (int o = 0; o < 2; ++o) { m.dc.blob[o] = c.ws + p.op[o]; m.dc.inv_norm[o] = f32(c.ws, p.inv[o]); m.dc.ccolpart[o] = f32(c.ws, p.ccolpart[o]); }
         m.dc.B = p.B; m.dc.D = p.D; m.dc.KF = p.KF; m.dc.KD = p.KD; m.dc.h = p.h; m.dc.w = p.w; m.dc.P = p.P; m.dc.Ppad = p.Ppad;
-        if (p.xmask_dense) { m.dc.clo[0] = c.ws + p.clo[0]; m.dc.clo[1] = c.ws + p.clo[1]; }
+        if (p.masks == Masks::DenseSplit) { m.dc.clo[0] = c.ws + p.clo[0]; m.dc.clo[1] = c.ws + p.clo[1]; }
     }
     if (c.split) {
         DgColmeanArgs ms = m;
@@ -632,11 +686,10 @@ static int fwd_cd_mask3(Fwd& c) {
     memset(&m, 0, sizeof(m));
     m.opR = c.ws + p.op[0]; m.loR = c.ws + p.clo[0];
     for (int t = 0; t < p.T; ++t) {
-        m.opS[t] = c.ws + p.op[op_of(p, t)]; m.loS[t] = c.ws + p.clo[op_of(p, t)]; m.sidx[t] = map_of(p, t, c.perms);
+        m.opS[t] = c.ws + p.op[p.ps[t].op]; m.loS[t] = c.ws + p.clo[p.ps[t].op]; m.sidx[t] = p.map_of(t, c.perms);
         m.bits[t] = reinterpret_cast<uint32_t*>(c.ws + p.maskbits[t]);
     }
-    const DgBlob bl(p.KF, p.KD);
-    m.T = p.T; m.B = p.B; m.Ppad = p.Ppad; m.blob_bytes = bl.bytes; m.off_c = bl.off_c; m.KD = p.KD;
+    m.T = p.T; m.B = p.B; m.Ppad = p.Ppad; m.blob_bytes = p.blob; m.off_c = p.blob_off_c; m.KD = p.KD;
     if (c.split) {
         DG_HIP(c.side->hand_over(1));                        // the code operands: k_rowmean reduces their column sums and writes FOLD's
                                                              // stash into the padding they zeroed
@@ -653,16 +706,16 @@ static int fwd_rowmeans(Fwd& c) {
     const Plan& p = c.p;
     DgRowmeanArgs r;
     memset(&r, 0, sizeof(r));
-    r.B = p.B; r.P = p.P; r.Ppad = p.Ppad; r.KF = p.KF; r.KD = p.KD; r.njobs = p.T; r.abar = c.f32(p.bbar[0]);
+    r.B = p.B; r.P = p.P; r.Ppad = p.Ppad; r.KF = p.KF; r.KD = p.KD; r.njobs = p.T; r.abar = f32(c.ws, p.bbar[0]);
     for (int t = 0; t < p.T; ++t) {
         r.jobs[t].A = c.ws + p.op[0]; r.jobs[t].aidx = nullptr;
-        r.jobs[t].bbar = c.f32(p.bbar[op_of(p, t)]); r.jobs[t].bidx = map_of(p, t, c.perms);
-        r.jobs[t].bsplit = reinterpret_cast<const __bf16*>(c.ws + p.bsplit[op_of(p, t)]);
-        r.jobs[t].rvec = c.f32(p.rvec[t]); r.jobs[t].rimg = c.f32(p.rimg[t]);
+        r.jobs[t].bbar = f32(c.ws, p.bbar[p.ps[t].op]); r.jobs[t].bidx = p.map_of(t, c.perms);
+        r.jobs[t].bsplit = reinterpret_cast<const __bf16*>(c.ws + p.bsplit[p.ps[t].op]);
+        r.jobs[t].rvec = f32(c.ws, p.rvec[t]); r.jobs[t].rimg = f32(c.ws, p.rimg[t]);
     }
-    if (p.ident) {
+    if (p.dense()) {
         r.ncs = 2;
-        for (int o = 0; o < 2; ++o) { r.cs_part[o] = c.f32(p.ccolpart[o]); r.cs_out[o] = c.f32(p.csum[o]); }
+        for (int o = 0; o < 2; ++o) { r.cs_part[o] = f32(c.ws, p.ccolpart[o]); r.cs_out[o] = f32(c.ws, p.csum[o]); }
     }
     if (p.fold) { r.stash = c.ws + p.op[0]; r.stash_off = FOLD_STASH_OFF; }
     DG_HIP(dg_launch_rowmean(r, c.stream));
@@ -680,14 +733,13 @@ static int fwd_finish(Fwd& c) {
         f.scale[j] = a.jobs[j].fin_scale;
     }
     f.njobs = a.njobs; f.nblk = p.B * p.nrb; f.B = p.B; f.P = p.P;
-    const int dep_nrb = (p.Ppad / 32 + 7) / 8;               // row blocks of the depth term inside the k_gs launch: 8 row tiles each
-    if (p.grad && p.depth) {                                 // its partial sums: one more entry of the reduction
+    if (p.depth_in_gs()) {                                     // the depth blocks' partial sums: one more entry of the reduction
         const int j = f.njobs++;
-        f.part[j] = c.f32(p.part[p.T]); f.slot_loss[j] = DG_OUT_LOSS_DEPTH; f.slot_cd[j] = -1;
-        f.scale[j] = (float)(1.0 / ((double)p.B * p.P * p.P));
-        f.nblk_job[j] = p.B * dep_nrb;
+        f.part[j] = f32(c.ws, p.part[p.T]); f.slot_loss[j] = DG_OUT_LOSS_DEPTH; f.slot_cd[j] = -1;
+        f.scale[j] = p.inv_numel;
+        f.nblk_job[j] = p.B * p.dep_nrb;
     }
-    f.nzsum = p.depth ? c.f32(p.nzsum) : nullptr;
+    f.nzsum = p.depth ? f32(c.ws, p.nzsum) : nullptr;
     f.out = c.out;
     f.wtot[0] = c.desc->w_intra; f.wtot[1] = c.desc->w_inter; f.wtot[2] = c.desc->w_neg; f.wtot[3] = c.desc->w_depth;
     if (!p.grad) {
@@ -699,13 +751,13 @@ static int fwd_finish(Fwd& c) {
     build_gs_jobs(p, c.ws, c.perms, g);
     g.fin = f;
     if (p.depth) {
-        g.dep_op = c.ws + p.op[0]; g.dep_nz = c.f32(p.nz); g.dep_dR = c.f32(p.dRA[p.T]); g.dep_part = c.f32(p.part[p.T]);
+        g.dep_op = c.ws + p.op[0]; g.dep_nz = f32(c.ws, p.nz); g.dep_dR = f32(c.ws, p.dRA[p.T]); g.dep_part = f32(c.ws, p.part[p.T]);
         g.dep_ticket = reinterpret_cast<unsigned int*>(c.ws + p.ticket);
-        dep_maskbits = (p.xmask || p.xmask_dense) ? reinterpret_cast<const uint32_t*>(c.ws + p.maskbits[0]) : nullptr;   // cd of the depth term = intra's cd
-        g.dep_shift = c.desc->shift_depth; g.dep_nrb = dep_nrb; g.dep_blocks = p.B * dep_nrb;
-        clamp_bounds(c.desc, g.dep_lo, g.dep_hi);
+        dep_maskbits = p.has_masks() ? reinterpret_cast<const uint32_t*>(c.ws + p.maskbits[0]) : nullptr;   // cd of the depth term = intra's cd
+        g.dep_shift = p.shift_depth; g.dep_nrb = p.dep_nrb; g.dep_blocks = p.B * p.dep_nrb;
+        g.dep_lo = p.lo; g.dep_hi = p.hi;
     }
-    if (!(p.xmask_dense && p.depth)) {
+    if (p.depth_run != Depth::GsOwnLaunch) {
         DG_HIP(dg_launch_gs(g, dep_maskbits, c.stream, false, p.half));
         return DG_OK;
     }
@@ -748,25 +800,25 @@ static int corr_forward_impl(const dg_corr_desc* desc, const float* orig_feats, 
     // (code norms + draw -> code operands -> k_cd_mask3) runs on the library's side stream BESIDE the feature side of the preparation
     // (k_prep_dense's feats, k_colmean, k_rowmean) instead of in front of the fused kernel: the same launches split by role, joined
     // in front of the fused kernel.  Without a side stream (first call inside a capture) everything runs in sequence as before.
-    if (p.xmask_dense && p.ident && split_masks_enabled()) c.side.emplace(c.stream);
+    if (p.dense_masks() && split_masks_enabled()) c.side.emplace(c.stream);
     c.split = c.side && static_cast<bool>(*c.side) && p.pointwise;
 
     // 1.+2. operands
-    if (p.small) return forward_small(c);           // (sampled coordinates on a small grid: one fused kernel)
-    if (int rc = p.ident ? fwd_operands_dense(c) : fwd_operands_general(c)) return rc;
+    if (p.small()) return forward_small(c);         // (sampled coordinates on a small grid: one fused kernel)
+    if (int rc = p.dense() ? fwd_operands_dense(c) : fwd_operands_general(c)) return rc;
 
-    // (the launch plan of step 4 is needed here already: the consumer lists of k_corr2's grouped ragged blocks are written by
+    // (the job table of step 4 is needed here already: the consumer lists of k_corr2's grouped ragged blocks are written by
     //  extra blocks of the k_colmean launch)
-    c.njA = build_corr_jobs(p, desc, c.ws, perms, c.a, &c.depth_index);
+    build_corr_jobs(p, c.ws, perms, c.a);
 
     // 3. column sums of the operands, the exact masks that need them, then the row means of fd
     if (int rc = fwd_colmeans(c)) return rc;
-    if (p.xmask_dense && p.pointwise) { if (int rc = fwd_cd_mask3(c)) return rc; }
+    if (p.masks == Masks::DenseSplit) { if (int rc = fwd_cd_mask3(c)) return rc; }
     if (p.pointwise) { if (int rc = fwd_rowmeans(c)) return rc; }
 
     // 4. fused correlation passes
     if (c.split) DG_HIP(c.side->join());                        // the mask words
-    DG_HIP(launch_main(p, c.a, c.njA, c.depth_index, c.stream));
+    if (int rc = launch_main(p, c.a, c.stream)) return rc;
 
     // 5. scalar outputs
     return fwd_finish(c);
@@ -821,10 +873,64 @@ extern "C" int dg_corr_forward_masked(const dg_corr_desc* desc, const float* ori
                              draw_perms ? &draw : nullptr, out_scalars, workspace, workspace_bytes, stream_, &fk);
 }
 
+// ---- the backward: the source table of the one k_scatter launch, filled from the pair-set table
+struct ScatterFill {
+    DgScatterArgs& s;
+    char* ws;
+    void add(size_t buf, const int64_t* route, int gidx, int csel, float factor, int dest, int raw, int half = 0, const float* dfac = nullptr) {
+        DgScatterSrc& q = s.src[s.nsrc++];
+        q.buf = f32(ws, buf); q.route = route; q.gidx = gidx; q.coords_sel = csel;
+        q.factor = factor; q.dest = dest; q.raw = raw; q.half = half; q.dfac = dfac;
+    }
+};
+
+// the fused small-grid kernel (dg_small.hip): stationary-side tiles raw, streamed-side tiles final (one set per half of the
+// stationary tiles), and with `pointwise` the same again for the old_mean term, whose factor old_mean_t lives on the device
+static void scatter_sources_small(const Plan& p, const int64_t* perms, ScatterFill& f) {
+    DgScatterArgs& s = f.s;
+    char* ws = f.ws;
+    for (int t = 0; t < p.T; ++t) {
+        const PairSet& q = p.ps[t];
+        const int64_t* route = p.batch_map(q.neg, perms);
+        const float* om = p.pointwise ? f32(ws, p.om) + t : nullptr;
+        f.add(p.dRA[t], nullptr, q.gidx, 0, q.factor, 0, 1);
+        if (p.pointwise) f.add(p.dRA2[t], nullptr, q.gidx, 0, q.factor, 0, 1, 0, om);
+        // the streamed-side (final) tiles: one set per half of the stationary tiles, with `pointwise` the old_mean terms on top.
+        // ROUTED sources (the negatives) are merged into one buffer each by extra slices of the combine launch, in front of the
+        // adjoint launch that reads the result - routed sources are what that launch's time scales with.  Direct ones (intra,
+        // inter) are read by the combine launch itself: those keep their terms.
+        if (route && (p.pointwise || p.nsplit == 2)) {
+            const int j = s.naxpy++;
+            s.axo[j] = f32(ws, p.dRBm[t]); s.axd[j] = f32(ws, p.dRB[t]); s.axd2[j] = p.nsplit == 2 ? f32(ws, p.dRBs[t]) : nullptr;
+            s.axs[j] = p.pointwise ? f32(ws, p.dRB2[t][0]) : nullptr; s.axs2[j] = (p.pointwise && p.nsplit == 2) ? f32(ws, p.dRB2[t][1]) : nullptr;
+            s.axf[j] = om;
+            f.add(p.dRBm[t], route, q.gidx, q.csel, q.factor, q.dest, 0);
+        } else {
+            for (int k = 0; k < p.nsplit; ++k) {
+                f.add(k == 0 ? p.dRB[t] : p.dRBs[t], route, q.gidx, q.csel, q.factor, q.dest, 0);
+                if (p.pointwise) f.add(p.dRB2[t][k], route, q.gidx, q.csel, q.factor, q.dest, 0, 0, om);
+            }
+        }
+    }
+}
+
+// the blob kernels.  dRA[t]: the fused kernel's raw accumulator-order tiles (stationary operand = operand 1 for every pair-set);
+// dRB[t]: k_gs output, row-major, normalisation backward already applied.  Where the intra pair-set's -G is symmetric
+// (Plan::intra_symmetric: no k_gs job, build_gs_jobs) d/dc1 + d/dc2 = 2 d/dc1
+static void scatter_sources_blobs(const Plan& p, const int64_t* perms, ScatterFill& f) {
+    const int hf = p.half ? 1 : 0;              // (the pair-sets' tiles of k_corr2 and k_gs; the depth term's stay fp32)
+    for (int t = 0; t < p.T; ++t) {
+        const PairSet& q = p.ps[t];
+        const bool doubled = t == 0 && p.intra_symmetric();
+        f.add(p.dRA[t], nullptr, q.gidx, 0, doubled ? 2.0f * q.factor : q.factor, 0, 1, hf);
+        if (!doubled) f.add(p.dRB[t], p.batch_map(q.neg, perms), q.gidx, q.csel, q.factor, q.dest, 0, hf);
+    }
+}
+
 static int corr_backward_impl(const dg_corr_desc* desc, const float* grad_scalars, const float* grad_total, const float* coords1,
                               const float* coords2, const int64_t* perms, float* grad_code, float* grad_code_pos,
                               void* workspace, size_t workspace_bytes, dg_stream_t stream_) {
-    Plan p;
+    Plan p{};
     int rc = make_plan(desc, p);
     if (rc != DG_OK) return rc;
     if (!p.grad) return fail(DG_ERR_INVALID, "dg_corr_backward needs a descriptor with DG_NEED_GRAD (as used in forward)");
@@ -832,77 +938,26 @@ static int corr_backward_impl(const dg_corr_desc* desc, const float* grad_scalar
     if (p.N > 0 && !perms) return fail(DG_ERR_INVALID, "perms is null with n_neg=%d", p.N);
     if (workspace_bytes < p.total) return fail(DG_ERR_WORKSPACE, "workspace %zu < required %zu bytes", workspace_bytes, p.total);
     char* ws = static_cast<char*>(workspace);
-    auto F32 = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
     DgScatterArgs s;
     memset(&s, 0, sizeof(s));
-    // the kernels keep -G (mask * (fd'' - shift)) and its products: the sign lives here
-    const float f = (float)(-1.0 / ((double)p.B * p.P * p.P));
-    const float fn = p.N > 0 ? f / (float)p.N : 0.f;
-    int n = 0;
-    auto add = [&](size_t buf, const int64_t* route, int gidx, int csel, float factor, int dest, int raw, int half = 0) {
-        s.src[n].buf = F32(buf); s.src[n].route = route; s.src[n].gidx = gidx; s.src[n].coords_sel = csel;
-        s.src[n].factor = factor; s.src[n].dest = dest; s.src[n].raw = raw; s.src[n].half = half; ++n;
-    };
-    const int hf = p.half ? 1 : 0;              // (the pair-sets' tiles of k_corr2 and k_gs; the depth term's stay fp32)
-    // dRA[t]: the fused kernel's raw accumulator-order tiles (stationary operand = operand 1 for every pair-set);
-    // dRB[t]: k_gs output, row-major, normalisation backward already applied
-    if (p.small) {
-        // the fused small-grid kernel (dg_small.hip): stationary-side tiles raw, streamed-side tiles final (one set per half of the
-        // stationary tiles), and with `pointwise` the same again for the old_mean term, whose factor old_mean_t lives on the device
-        for (int t = 0; t < p.T; ++t) {
-            const int gi = t < 2 ? t : 2;
-            const float ft = t < 2 ? f : fn;
-            const int64_t* route = t >= 2 ? perms + (size_t)(t - 2) * p.B : nullptr;
-            const int csel = t == 0 ? 0 : 1, dest = t == 1 ? 1 : 0;
-            add(p.dRA[t], nullptr, gi, 0, ft, 0, 1);
-            const float* om = p.pointwise ? F32(p.om) + t : nullptr;
-            if (p.pointwise) { add(p.dRA2[t], nullptr, gi, 0, ft, 0, 1); s.src[n - 1].dfac = om; }
-            // the streamed-side (final) tiles: one set per half of the stationary tiles, with `pointwise` the old_mean terms on top.
-            // ROUTED sources (the negatives) are merged into one buffer each by extra slices of the combine launch, in front of the
-            // adjoint launch that reads the result - routed sources are what that launch's time scales with.  Direct ones (intra,
-            // inter) are read by the combine launch itself: those keep their terms.
-            if (route && (p.pointwise || p.nsplit == 2)) {
-                const int j = s.naxpy++;
-                s.axo[j] = F32(p.dRBm[t]); s.axd[j] = F32(p.dRB[t]); s.axd2[j] = p.nsplit == 2 ? F32(p.dRBs[t]) : nullptr;
-                s.axs[j] = p.pointwise ? F32(p.dRB2[t][0]) : nullptr; s.axs2[j] = (p.pointwise && p.nsplit == 2) ? F32(p.dRB2[t][1]) : nullptr;
-                s.axf[j] = om;
-                add(p.dRBm[t], route, gi, csel, ft, dest, 0);
-            } else {
-                for (int k = 0; k < p.nsplit; ++k) {
-                    add(k == 0 ? p.dRB[t] : p.dRBs[t], route, gi, csel, ft, dest, 0);
-                    if (p.pointwise) { add(p.dRB2[t][k], route, gi, csel, ft, dest, 0); s.src[n - 1].dfac = om; }
-                }
-            }
-        }
-    } else {
-    if (intra_is_symmetric(p)) add(p.dRA[0], nullptr, 0, 0, 2.0f * f, 0, 1, hf);      // -G symmetric: d/dc1 + d/dc2 = 2 d/dc1 (no k_gs job, build_gs_jobs)
-    else { add(p.dRA[0], nullptr, 0, 0, f, 0, 1, hf); add(p.dRB[0], nullptr, 0, 0, f, 0, 0, hf); }
-    add(p.dRA[1], nullptr, 1, 0, f, 0, 1, hf);
-    add(p.dRB[1], nullptr, 1, 1, f, 1, 0, hf);
-    for (int k = 0; k < p.N; ++k) {
-        add(p.dRA[2 + k], nullptr, 2, 0, fn, 0, 1, hf);
-        add(p.dRB[2 + k], perms + (size_t)k * p.B, 2, 1, fn, 0, 0, hf);
-    }
-    }
-    if (p.depth) add(p.dRA[p.T], nullptr, 3, 0, 2.0f * f, 0, 1);   // dd and cd symmetric: d/dc1 + d/dc2 = 2 d/dc1
-    s.nsrc = n;
+    ScatterFill fill{s, ws};
+    if (p.small()) scatter_sources_small(p, perms, fill);
+    else scatter_sources_blobs(p, perms, fill);
+    if (p.depth) fill.add(p.dRA[p.T], nullptr, 3, 0, 2.0f * p.grad_f, 0, 1);   // dd and cd symmetric: d/dc1 + d/dc2 = 2 d/dc1
     s.coords1 = coords1; s.coords2 = coords2; s.gscal = grad_scalars; s.gtot = grad_total;
     s.wtot[0] = desc->w_intra; s.wtot[1] = desc->w_inter; s.wtot[2] = desc->w_neg; s.wtot[3] = desc->w_depth;
-    s.comb[0] = F32(p.comb[0]); s.comb[1] = F32(p.comb[1]);
+    s.comb[0] = f32(ws, p.comb[0]); s.comb[1] = f32(ws, p.comb[1]);
     s.taps = ws + p.taps;
-    {
-        const DgBlob bl(p.KF, p.KD);
-        s.xop = ws + p.op[0]; s.xinv = F32(p.inv[0]); s.blob_bytes = bl.bytes; s.blob_off_c = bl.off_c;
-        // (half, final sources: destination 0 = the code map behind operand 0 - the negatives' streamed operand on the shared grid -,
-        //  destination 1 = operand 1's)
-        s.xinv_dest[0] = F32(p.inv[0]); s.xinv_dest[1] = p.nops > 1 ? F32(p.inv[1]) : nullptr;
-    }
+    s.xop = ws + p.op[0]; s.xinv = f32(ws, p.inv[0]); s.blob_bytes = p.blob; s.blob_off_c = p.blob_off_c;
+    // (half, final sources: destination 0 = the code map behind operand 0 - the negatives' streamed operand on the shared grid -,
+    //  destination 1 = operand 1's)
+    s.xinv_dest[0] = f32(ws, p.inv[0]); s.xinv_dest[1] = p.nops > 1 ? f32(ws, p.inv[1]) : nullptr;
     s.out[0] = grad_code; s.out[1] = grad_code_pos;
     s.B = p.B; s.D = p.D; s.DP = p.KD; s.h = p.hc; s.w = p.wc; s.S = p.S; s.Sh = p.Sh; s.P = p.P; s.Ppad = p.Ppad;     // (h, w): the code maps
     if ((size_t)p.hc * p.wc > 4096) return fail(DG_ERR_UNSUPPORTED, "code map %dx%d too large for the gradient gather (max 4096 pixels)", p.hc, p.wc);
     s.DC = 8;
-    s.dense = p.ident ? 1 : 0;
-    s.taps_ready = p.ident ? 0 : 1;            // (general coordinates: built by the forward's first launch, dg_launch_pre_general)
+    s.dense = p.dense() ? 1 : 0;
+    s.taps_ready = p.dense() ? 0 : 1;          // (general coordinates: built by the forward's first launch, dg_launch_pre_general)
     DG_HIP(dg_launch_scatter(s, static_cast<hipStream_t>(stream_)));
     return DG_OK;
 }
@@ -925,7 +980,7 @@ extern "C" int dg_corr_backward_total(const dg_corr_desc* desc, const float* gra
 
 static int materialize_impl(const dg_corr_desc* desc, int32_t which, const int64_t* perms, float* out_cd, float* out_loss,
                             void* workspace, size_t workspace_bytes, dg_stream_t stream_) {
-    Plan p;
+    Plan p{};
     int rc = make_plan(desc, p);
     if (rc != DG_OK) return rc;
     if (!workspace) return fail(DG_ERR_INVALID, "null workspace");
@@ -936,7 +991,7 @@ static int materialize_impl(const dg_corr_desc* desc, int32_t which, const int64
         return fail(DG_ERR_INVALID, "materialising a negative of a DG_SHARED_COORDS call needs its batch maps: dg_corr_materialize_shared");
     if (!out_cd && !out_loss) return DG_OK;
     char* ws = static_cast<char*>(workspace);
-    if (p.small) {          // the fused small-grid kernel again, on the rows (and old_mean_t) the forward left in the workspace
+    if (p.small()) {        // the fused small-grid kernel again, on the rows (and old_mean_t) the forward left in the workspace
         DgSmallArgs m;
         small_args(p, desc, ws, perms, m);
         m.mat = 1; m.mat_t = which; m.out_cd = out_cd; m.out_loss = out_loss; m.grad = 0; m.span = nullptr;
@@ -946,17 +1001,17 @@ static int materialize_impl(const dg_corr_desc* desc, int32_t which, const int64
     // (a gradient pass with k_corr2's FOLD left the intra row means in the padding of the operand-1 blobs' C part: k_corr_main's
     //  un-reduced forms multiply all of it.  Cleared for this launch and written back behind it, from the row means that are still in
     //  the workspace: the workspace stays what the forward prepared - dg_corr_relaunch_main remains valid.)
-    const int stash_off = (int)DgBlob(p.KF, p.KD).off_c + FOLD_STASH_OFF;
+    const int stash_off = p.blob_off_c + FOLD_STASH_OFF;
     if (p.fold)
         DG_HIP(dg_launch_set_stash(ws + p.op[0], p.B, p.Ppad / 32, (size_t)p.blob, stash_off, nullptr, p.P, p.Ppad, static_cast<hipStream_t>(stream_)));
     DgCorrArgs a;
-    corr_args_base(p, desc, ws, a);
+    corr_args_base(p, ws, a);
     // stationary = operand 2 (on MFMA lanes) -> the stores of one accumulator register are contiguous along q
-    DgJob j = which == -1 ? depth_job(p, desc, ws) : helper_job(p, desc, ws, which, true, perms);
+    DgJob j = which == -1 ? depth_job(p, ws) : helper_job(p, ws, which, true, perms);
     j.center_on_lane = 0;
     j.out_cd = out_cd; j.out_loss = out_loss; j.part = nullptr; j.dR = nullptr;
     a.jobs[0] = j; a.njobs = 1;
-    a.pos_w = p.ident ? p.w : 0;
+    a.pos_w = p.dense() ? p.w : 0;
     DG_HIP(dg_launch_corr(a, p.KF, p.KD, p.rf, 2, static_cast<hipStream_t>(stream_)));
     if (p.fold)
         DG_HIP(dg_launch_set_stash(ws + p.op[0], p.B, p.Ppad / 32, (size_t)p.blob, stash_off, reinterpret_cast<const float*>(ws + p.rvec[0]),
@@ -978,43 +1033,35 @@ extern "C" int dg_corr_materialize_shared(const dg_corr_desc* desc, int32_t whic
 // (same desc / perms / workspace) left in the workspace.  Idempotent (rewrites the same outputs).
 extern "C" int dg_corr_relaunch_main(const dg_corr_desc* desc, const int64_t* perms, void* workspace,
                                      size_t workspace_bytes, dg_stream_t stream_) {
-    Plan p;
+    Plan p{};
     int rc = make_plan(desc, p);
     if (rc != DG_OK) return rc;
     if (!workspace || workspace_bytes < p.total) return fail(DG_ERR_WORKSPACE, "workspace missing or too small");
     if (p.N > 0 && !perms) return fail(DG_ERR_INVALID, "perms is null");
-    if (p.small) {
+    char* ws = static_cast<char*>(workspace);
+    if (p.small()) {
         // (the scalars of the re-launch go to the workspace's scratch vector: the call's own outputs are not touched)
         DgSmallArgs m;
-        small_args(p, desc, static_cast<char*>(workspace), perms, m);
-        m.out = reinterpret_cast<float*>(static_cast<char*>(workspace) + p.scratch_out);
+        small_args(p, desc, ws, perms, m);
+        m.out = f32(ws, p.scratch_out);
         DG_HIP(dg_launch_corr_small(m, static_cast<hipStream_t>(stream_)));        // (the kernel alone: what the roofline leg times)
         return DG_OK;
     }
     DgCorrArgs a;
-    int depth_index;
-    const int njA = build_corr_jobs(p, desc, static_cast<char*>(workspace), perms, a, &depth_index);
-    DG_HIP(launch_main(p, a, njA, depth_index, static_cast<hipStream_t>(stream_)));
-    return DG_OK;
+    build_corr_jobs(p, ws, perms, a);
+    return launch_main(p, a, static_cast<hipStream_t>(stream_));
 }
 
 extern "C" int dg_corr_intra_folded(const dg_corr_desc* desc) {
-    Plan p;
+    Plan p{};
     if (make_plan(desc, p) != DG_OK) return -1;
     return p.fold ? 1 : 0;
 }
 
 extern "C" const char* dg_corr_main_kernel_name(const dg_corr_desc* desc) {
-    Plan p;
+    Plan p{};
     if (make_plan(desc, p) != DG_OK) return nullptr;
-    if (p.small) return "k_corr_small";
-    // the job table holds addresses only: a made-up workspace base and batch-map pointer decide nothing but null / non-null
-    char* const ws = reinterpret_cast<char*>(static_cast<uintptr_t>(1) << 21);
-    const int64_t* const perms = reinterpret_cast<const int64_t*>(static_cast<uintptr_t>(1) << 20);
-    DgCorrArgs a;
-    int depth_index;
-    const int njA = build_corr_jobs(p, desc, ws, perms, a, &depth_index);
-    return (p.grad && njA > 0 && dg_corr2_supported(a, p.KF, p.KD)) ? "k_corr2" : "k_corr_main";
+    return p.main == MainKernel::Small ? "k_corr_small" : (p.main == MainKernel::Corr2 ? "k_corr2" : "k_corr_main");
 }
 
 extern "C" int dg_normalize_split(int32_t B, int32_t C, int32_t h, int32_t w, const float* src, int32_t nchunks, int32_t chunk_c,
