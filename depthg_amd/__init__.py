@@ -1,7 +1,8 @@
 """depthg_amd - MI355X (gfx950) implementation of DepthG's feature-correlation loss hot path.
 
 Public surface (mirrors the reference's Python operator surface for this path):
-    ContrastiveCorrelationLoss   drop-in for src/modules.py:1221-1367
+    ContrastiveCorrelationLoss   drop-in for src/modules.py:1221-1367; .cd_histograms(): the cd histograms of its last call without
+                                 the un-reduced tensors (ops.corr_cd_hist; cfg.hist_freq / cfg.dg_hist_bins in the segmenter)
     depth_decay                  scalar decay schedules (src/depth_decay_modules.py) + the live legacy decay
     training                     the caller arithmetic around the loss (means, weighted total, log keys;
                                  src/train_segmentation.py:240-350)

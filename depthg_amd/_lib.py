@@ -53,6 +53,7 @@ SIGNATURES = {
     "dg_corr_backward_total": (_I, [cp] + [vp] * 6 + [vp, _SZ, vp]),
     "dg_corr_materialize": (_I, [cp, i32, vp, vp, vp, _SZ, vp]),
     "dg_corr_materialize_shared": (_I, [cp, i32, vp, vp, vp, vp, _SZ, vp]),
+    "dg_corr_cd_hist": (_I, [cp, i32, i32, vp, i32, f32, f32, vp, vp, _SZ, vp]),
     # samplers
     "dg_fps_workspace_bytes": (_SZ, [i32] * 3),
     "dg_fps_coords": (_I, [vp] + [i32] * 6 + [vp, vp, vp, _SZ, vp]),

@@ -19,6 +19,8 @@ enum class Depth { None, Job, GsBlocks, GsOwnLaunch };   // the depth term of th
                                                         // (forward-only calls) / blocks of the k_gs launch (gradient passes; dg_corr.hip gs_depth_block: in
                                                         // the fused kernel's launch its latency-bound blocks were the tail) / those blocks, in the masked
                                                         // form, as a launch of their own beside the G-stream blocks (fwd_finish)
+enum class Hist { Rows, Blobs };                          // dg_corr_cd_hist: the sampled fp32 code rows of the fused small grid (k_cd_hist_rows) / the
+                                                        // fp16 C parts of the operand blobs (k_cd_hist)
 enum class Masks { None, Sampled, DenseRaw, DenseSplit };   // exact clamp masks: the sign of the fp16 cd / k_cd_mask blocks inside the gather launch
                                                         // (small sample grids) / k_cd_mask on channel-last code maps / k_cd_mask3 on split fp16 operands
 
@@ -46,6 +48,7 @@ struct Plan {
     Sampler sampler;                        // (Prep::Dense samples nothing: ChannelLast, the copies its DenseRaw masks read)
     MainKernel main;
     Masks masks;
+    Hist hist;
     bool fold;                              // MainKernel::Corr2 forms the intra pair-set's streamed-side gradient itself (dg_corr2.hip FOLD)
     bool half;                              // MainKernel::Corr2 and k_gs write fp16 gradient tiles for k_combine_out (identity grid; DgScatterSrc.half)
     Depth depth_run;
@@ -174,6 +177,7 @@ static int make_plan(const dg_corr_desc* d, Plan& p) {
     const bool ident = (d->flags & DG_IDENTITY_GRID) != 0;
     p.prep = ident ? Prep::Dense : (dg_small_supported(p.Ppad, p.KD) ? Prep::Small : Prep::General);
     p.nsplit = p.Ppad == 160 ? 2 : 1;
+    p.hist = p.small() ? Hist::Rows : Hist::Blobs;    // (what the forward leaves behind: the fused small grid keeps rows, every other path code blobs)
     if (d->C > 768 && !p.small())
         return fail(DG_ERR_UNSUPPORTED, "C=%d > 768 feature channels are supported on sample grids of at most 160 positions "
                                         "(feature_samples <= 12) only; this call has %d positions%s", d->C, p.P,
@@ -1027,6 +1031,41 @@ extern "C" int dg_corr_materialize(const dg_corr_desc* desc, int32_t which, floa
 extern "C" int dg_corr_materialize_shared(const dg_corr_desc* desc, int32_t which, const int64_t* perms, float* out_cd, float* out_loss,
                                           void* workspace, size_t workspace_bytes, dg_stream_t stream_) {
     return materialize_impl(desc, which, perms, out_cd, out_loss, workspace, workspace_bytes, stream_);
+}
+
+// Histograms of the pair-sets' cd from the operands the forward left in the workspace (dg_hist.hip): one memset node and one launch,
+// the pair-set as a grid dimension.  Reads the workspace only - a later dg_corr_backward sees what the forward wrote.
+extern "C" int dg_corr_cd_hist(const dg_corr_desc* desc, int32_t first, int32_t count, const int64_t* perms, int32_t nbins, float lo,
+                               float hi, int64_t* out_counts, void* workspace, size_t workspace_bytes, dg_stream_t stream_) {
+    Plan p{};
+    int rc = make_plan(desc, p);
+    if (rc != DG_OK) return rc;
+    if (first < 0)
+        return fail(DG_ERR_INVALID, "dg_corr_cd_hist: first=%d: pair-sets start at 0 (the depth term's element is dd, which has no cd histogram)", first);
+    if (count < 1 || first > p.T - count) return fail(DG_ERR_INVALID, "dg_corr_cd_hist: pair-sets [%d,%d) outside [0,%d)", first, first + count, p.T);
+    if (nbins < 1 || nbins > DG_HIST_MAX_BINS) return fail(DG_ERR_INVALID, "dg_corr_cd_hist: nbins=%d outside [1,%d]", nbins, DG_HIST_MAX_BINS);
+    if (!__builtin_isfinite(lo) || !__builtin_isfinite(hi) || !(lo < hi))
+        return fail(DG_ERR_INVALID, "dg_corr_cd_hist: the range needs finite lo < hi, got [%g,%g]", (double)lo, (double)hi);
+    if (!out_counts || !workspace) return fail(DG_ERR_INVALID, "null pointer");
+    if (workspace_bytes < p.total) return fail(DG_ERR_WORKSPACE, "workspace %zu < required %zu bytes", workspace_bytes, p.total);
+    if (first + count > 2 && p.shared && !perms)
+        return fail(DG_ERR_INVALID, "dg_corr_cd_hist: a negative of a DG_SHARED_COORDS call needs its batch maps (perms)");
+    char* ws = static_cast<char*>(workspace);
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    DgCdHistArgs a;
+    memset(&a, 0, sizeof(a));
+    a.opR = ws + p.op[0]; a.rowsR = f32(ws, p.rows_c[0]);
+    for (int j = 0; j < count; ++j) {
+        const int t = first + j, o2 = p.ps[t].op;
+        a.opS[j] = ws + p.op[o2]; a.rowsS[j] = f32(ws, p.rows_c[o2]); a.sidx[j] = p.map_of(t, perms);
+    }
+    a.out = reinterpret_cast<unsigned long long*>(out_counts);
+    a.count = count; a.B = p.B; a.P = p.P; a.Ppad = p.Ppad; a.D = p.D; a.D4 = p.D4; a.KD = p.KD;
+    a.blob_bytes = p.blob; a.off_c = p.blob_off_c;
+    a.nbins = nbins; a.lo = lo; a.scale = (float)nbins / (hi - lo);
+    DG_HIP(hipMemsetAsync(out_counts, 0, (size_t)count * nbins * sizeof(int64_t), stream));
+    DG_HIP(dg_launch_cd_hist(a, p.hist == Hist::Rows, stream));
+    return DG_OK;
 }
 
 // Measurement aid: re-launch ONLY the fused correlation kernel on the operands a previous dg_corr_forward

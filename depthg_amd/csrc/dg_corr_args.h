@@ -595,6 +595,22 @@ struct DgCdMask3Args {
     int32_t nsplit;                          // parts the walk over the S tiles is split in (0: the launcher decides)
 };
 hipError_t dg_launch_cd_mask3(const DgCdMask3Args& a, hipStream_t s);
+// Histograms of cd (k_cd_hist / k_cd_hist_rows; dg_hist.hip): entry j of the tables is pair-set first + j of dg_corr_cd_hist.  The
+// stationary operand is operand 0 of image n, the streamed one the pair-set's operand of image sidx[j][n] - the tables helper_job
+// and small_args fill.  Blobs: opR / opS (the C parts are read); Rows: rowsR / rowsS (sampled fp32 code rows [B][P][D4]).
+#define DG_HIST_MAX_BINS 256
+struct DgCdHistArgs {
+    const char* opR;
+    const char* opS[DG_MAX_NEG + 2];
+    const float* rowsR;
+    const float* rowsS[DG_MAX_NEG + 2];
+    const int64_t* sidx[DG_MAX_NEG + 2];     // batch map of the streamed operand (null: identity)
+    unsigned long long* out;                 // [count][nbins], zero at launch
+    int32_t count, B, P, Ppad, D, D4, KD, blob_bytes, off_c;
+    int32_t nbins;
+    float lo, scale;                         // bin = floor((cd - lo) * scale), scale = nbins / (hi - lo); clamped into [0, nbins)
+};
+hipError_t dg_launch_cd_hist(const DgCdHistArgs& a, bool rows, hipStream_t s);
 hipError_t dg_launch_plane_sample(const DgPlaneArgs& a, hipStream_t s);
 hipError_t dg_launch_colmean(const DgColmeanArgs& a, hipStream_t s);
 hipError_t dg_launch_prep_dense(const DgDenseArgs& a, hipStream_t s);

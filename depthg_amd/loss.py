@@ -17,6 +17,8 @@ Extra, build-side cfg keys (all optional, read with getattr):
 After a call, `.scalars` is the fused fp32 output vector (DG_OUT_* order: the four loss means, the four cd means, the
 weighted total) with its grad_fn and `.total` its last element = the term `training_step` adds to its loss
 (src/train_segmentation.py:330-349, weights read from cfg), so `loss_fn.total.backward()` needs no further torch ops.
+`.cd_histograms()` gives the histograms of the three un-reduced cd tensors of that call (what the reference logs every cfg.hist_freq
+steps) in either dg_outputs mode, from the operands the forward left in its workspace.
 """
 from types import SimpleNamespace
 
@@ -295,7 +297,28 @@ class ContrastiveCorrelationLoss(nn.Module):
         d["scalars"] = out                     # the fused output vector with its grad_fn (DG_OUT_* order)
         d["total"] = total                     # weighted total of the loss means (src/train_segmentation.py:330-349)
         d["last_call"] = (desc, call.perms, ws)   # measurement aid (bench.py re-launches the fused kernel alone)
+        # cd_histograms(): handles only - descriptor, batch maps and workspace of the (first) chunk, and the stamp its forward left on it
+        d["_hist_call"] = (desc, call.perms, ws, getattr(ws, "_dg_forward", None))
         return self._outputs(call, out, chunks)
+
+    def cd_histograms(self, bins=64, range=(-1., 1.)):
+        """Histograms of the un-reduced code correlations of the most recent forward - what the reference's training_step logs every
+        cfg.hist_freq steps (src/train_segmentation.py:229-231, 298-301): {"intra_cd", "inter_cd", "neg_cd"} -> int64 (bins,) device
+        tensors over `range`, torch.histc's bins except that a value outside the range counts in the nearest end bin (every histogram
+        sums to its tensor's element count).  `neg_cd` is the sum over the negatives: the reference histograms their concatenation.
+        One small launch on the operands the forward left in its workspace (ops.corr_cd_hist), in both cfg.dg_outputs modes; a wide
+        map run in channel chunks uses the first chunk's, since cd does not depend on the feature chunk.  Reads only: a later
+        backward() is not affected."""
+        call = self.__dict__.get("_hist_call")
+        if call is None:
+            raise RuntimeError("depthg_amd: cd_histograms() covers the most recent forward of this loss, and none has run yet")
+        desc, perms, ws, stamp = call
+        if stamp is None or getattr(ws, "_dg_forward", None) != stamp:
+            raise RuntimeError("depthg_amd: cd_histograms(): the workspace of the last forward has been run on again since (its "
+                               "operands are gone); call cd_histograms() right after the forward it is to describe")
+        n_neg = int(desc.n_neg)
+        counts = ops.corr_cd_hist(desc, ws, 0, 2 + n_neg, perms=perms, bins=bins, range=range)
+        return {"intra_cd": counts[0], "inter_cd": counts[1], "neg_cd": counts[2:].sum(dim=0)}
 
     def _prepare(self, orig_feats, orig_feats_pos, orig_code, orig_code_pos, depth, coords1, coords2, perms, shared_coords,
                  identity_grid, draw_state, feat_keep):

@@ -118,9 +118,16 @@ def alloc_workspace(desc, device):
     return _empty(workspace_bytes(desc), torch.uint8, device)
 
 
+_forward_count = 0        # forwards run so far: every forward stamps its workspace tensor (`_dg_forward`), so that a reader of the
+                          # operands it left there (ContrastiveCorrelationLoss.cd_histograms) can tell a workspace that was run on again
+
+
 def _corr_forward(entry, desc, maps, perms, mid, workspace):
     """The one body of the four forward entry points, whose argument lists differ only between `perms` and `out_scalars`: `mid`."""
+    global _forward_count
     dev = maps[0].device
+    _forward_count += 1
+    workspace._dg_forward = _forward_count
     out = _empty(_lib.DG_OUT_COUNT, torch.float32, dev)
     rc = getattr(_lib.load(), entry)(ctypes.byref(desc), *[_ptr(t) for t in maps], _ptr(perms), *mid, _ptr(out), _ptr(workspace),
                                      workspace.numel(), _stream(dev))
@@ -234,6 +241,21 @@ def corr_materialize(desc, which, workspace, want_cd=True, want_loss=False, perm
                                         workspace.numel(), _stream(dev))
     _lib.check(rc, "dg_corr_materialize_shared")
     return cd, loss
+
+
+def corr_cd_hist(desc, workspace, first, count, perms=None, bins=64, range=(-1.0, 1.0)):
+    """int64 (count, bins) histograms of the un-reduced code correlations cd of pair-sets first .. first + count - 1 (0 intra, 1
+    inter, 2 + k negative k) over `range`, from the operands the forward left in `workspace` - nothing of size (B,P,P) is written
+    (dg_corr_cd_hist).  torch.histc's bins, except that values outside the range count in the end bins.  `perms`: the forward's
+    (n_neg, B) batch maps - needed for the negatives of a shared-coordinates (dense grid) call."""
+    dev = _on_gpu(workspace, "workspace").device
+    if perms is not None:
+        _on_gpu(perms, "perms")
+    out = _empty((max(int(count), 0), max(int(bins), 0)), torch.int64, dev)
+    rc = _lib.load().dg_corr_cd_hist(ctypes.byref(desc), int(first), int(count), _ptr(perms), int(bins), float(range[0]), float(range[1]),
+                                     _ptr(out), _ptr(workspace), workspace.numel(), _stream(dev))
+    _lib.check(rc, "dg_corr_cd_hist")
+    return out
 
 
 def fps_coords(depth, feat_hw, n_samples, return_inds=False):

@@ -26,7 +26,9 @@ all nine tensors (optim.FusedAdamSet) instead of three torch.optim.Adam steps.  
 is what `parallel.GradBucket` all-reduces.  With cfg.dg_dino_backbone (build-side key, off by default) the featurizer is
 featurizer.DinoFeaturizer - the real DINO ViT of depthg_amd/vit.py - instead of StandInFeaturizer; cfg.dg_fused_attention then routes
 its attention through the HIP kernel of dg_attn.hip and cfg.dg_fused_linear its blocks' linear layers (with their LayerNorm, GELU and
-residual adds) through the bf16 MFMA kernel of dg_linear.hip.
+residual adds) through the bf16 MFMA kernel of dg_linear.hip.  On the reference's histogram steps (cfg.hist_freq, src/train_segmentation.py:229-231,
+298-301) training_step puts the histograms of the three un-reduced cd tensors into its logs as `hist/intra_cd`, `hist/inter_cd`, `hist/neg_cd`
+(int64 counts on the device, cfg.dg_hist_bins bins, default 64) - from ContrastiveCorrelationLoss.cd_histograms(), without the tensors.
 """
 from types import SimpleNamespace
 from typing import Dict, Optional
@@ -218,10 +220,18 @@ class UnsupervisedSegmenter(nn.Module):
             use_depth_term = bool(cfg.depth_feat_correlation_loss)
             d_args = (depth, depth_pos) if use_depth_term else (None, None)                          # :242-292
             out = self.contrastive_corr_loss_fn(feats, feats_pos, salience, salience_pos, code, code_pos, *d_args)
+            # :229-231, :298-301: every cfg.hist_freq steps the reference histograms the three un-reduced cd tensors - here one small
+            # launch on the operands this call left in its workspace (in front of the LHP call, which runs the loss again)
+            hist_freq = getattr(cfg, "hist_freq", None)
+            hists = None
+            if hist_freq is not None and self.global_step % hist_freq == 0 and self.global_step > 0:
+                hists = self.contrastive_corr_loss_fn.cd_histograms(bins=int(getattr(cfg, "dg_hist_bins", 64)))
             lhp_out = None
             if getattr(cfg, "lhp", False) and use_depth_term:
                 lhp_out = self.contrastive_corr_loss_fn(feats, feats_pos, salience, salience_pos, lhp_code, lhp_code_pos, *d_args)
             total, logs = correspondence_total(cfg, out, lhp_out)                                    # :303-350
+            if hists is not None:
+                logs.update({"hist/" + k: v for k, v in hists.items()})
             loss = loss + total
         # the legacy decays sit at function-body level in the reference: they run every step, whatever correspondence_weight is
         legacy_decay_step(cfg, self.contrastive_corr_loss_fn.cfg, self.global_step)                  # :356-375 (mutates cfg)

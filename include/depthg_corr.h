@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define DG_VERSION 118   /* 118: dg_sampled_sumsq, dg_corr_forward_extnorm (feature maps wider than 768 channels on SAMPLED grids above 160 positions, in channel chunks); 117: DG_FEATS_UNIT, dg_normalize_split (feature maps wider than 768 channels on the dense identity grid, in chunks of the width the operand kernels hold: the loss is linear in the feature correlation); 116: dg_prof_main_span takes FOUR words (+ the workgroups' lifetimes in shader cycles and wall ticks: the clock the CUs held); 115: dg_corr_intra_folded; 114: dg_fps_coords_pair takes a workspace (dg_fps_workspace_bytes(2 B, h, w): the pooled depth maps, written by a launch over the whole chip in front of the sampler), dg_corr_materialize_shared, dg_prof_main_span (the fused correlation launch's execution span inside a replayed step), sample grids of <= 160 positions at any feature width (fused small-grid kernel); 113: dg_corr_forward_masked; 112: dg_rand_coords_state; 111: dg_head_forward_pair / dg_head_backward_pair; 110: dg_fps_coords_pair; 109: dg_knn_similarities; 108: dg_corr_desc.code_h / code_w (code maps of another resolution than the feature maps: the FeaturePyramidNet producer, src/modules.py:732-766), dg_corr_desc.flags DG_EXACT_MASKS; 107: dg_head_*, dg_cluster_lookup_*, dg_probe_ce_*; 106: dg_corr_main_kernel_name; 105: dg_corr_forward_draw; 104: dg_lhp_map_forward / dg_lhp_map_backward; 103: dg_super_perms_state; 102: DG_LINE_GRID, dg_salience_coords, dg_simple_depth_coords; 101: total weights, DG_OUT_TOTAL */
+#define DG_VERSION 118   /* 118: dg_corr_cd_hist (one more export under the same number: the layouts and meanings of every earlier entry point are unchanged, and a binding that declares the new symbol refuses a library without it when it loads), dg_sampled_sumsq, dg_corr_forward_extnorm (feature maps wider than 768 channels on SAMPLED grids above 160 positions, in channel chunks); 117: DG_FEATS_UNIT, dg_normalize_split (feature maps wider than 768 channels on the dense identity grid, in chunks of the width the operand kernels hold: the loss is linear in the feature correlation); 116: dg_prof_main_span takes FOUR words (+ the workgroups' lifetimes in shader cycles and wall ticks: the clock the CUs held); 115: dg_corr_intra_folded; 114: dg_fps_coords_pair takes a workspace (dg_fps_workspace_bytes(2 B, h, w): the pooled depth maps, written by a launch over the whole chip in front of the sampler), dg_corr_materialize_shared, dg_prof_main_span (the fused correlation launch's execution span inside a replayed step), sample grids of <= 160 positions at any feature width (fused small-grid kernel); 113: dg_corr_forward_masked; 112: dg_rand_coords_state; 111: dg_head_forward_pair / dg_head_backward_pair; 110: dg_fps_coords_pair; 109: dg_knn_similarities; 108: dg_corr_desc.code_h / code_w (code maps of another resolution than the feature maps: the FeaturePyramidNet producer, src/modules.py:732-766), dg_corr_desc.flags DG_EXACT_MASKS; 107: dg_head_*, dg_cluster_lookup_*, dg_probe_ce_*; 106: dg_corr_main_kernel_name; 105: dg_corr_forward_draw; 104: dg_lhp_map_forward / dg_lhp_map_backward; 103: dg_super_perms_state; 102: DG_LINE_GRID, dg_salience_coords, dg_simple_depth_coords; 101: total weights, DG_OUT_TOTAL */
 
 /* flags of dg_corr_desc.flags (names follow the cfg keys read at src/modules.py:1236-1352) */
 #define DG_POINTWISE      (1u << 0)  /* cfg.pointwise: spatial centering of fd (modules.py:1236-1239) */
@@ -221,6 +221,26 @@ int dg_corr_materialize(const dg_corr_desc* desc, int32_t which,
  */
 int dg_corr_materialize_shared(const dg_corr_desc* desc, int32_t which, const int64_t* perms, float* out_cd, float* out_loss,
                                void* workspace, size_t workspace_bytes, dg_stream_t stream);
+
+/*
+ * Histograms of the un-reduced code correlations cd of pair-sets first .. first + count - 1 (0 = pos_intra, 1 = pos_inter, 2+k =
+ * negative k) - what the reference's training_step logs every cfg.hist_freq steps (src/train_segmentation.py:229-231, 298-301) -
+ * WITHOUT the (B,S,S,S,S) tensors: every cd is formed again from the operands the forward left in the workspace, binned and
+ * dropped.  One memset node and one launch for all requested pair-sets, on the caller's stream; no allocation, no host
+ * synchronisation.  Works on every grid and in both forms of the forward's outputs.
+ *  nbins, lo, hi : 1 <= nbins <= 256 uniform bins over [lo, hi], lo < hi finite.  torch.histc's rule: bin = floor((v - lo) * nbins /
+ *                  (hi - lo)), v == hi in the last bin.  ONE difference: a value outside [lo, hi] is counted in the nearest end bin,
+ *                  not dropped (a cosine leaves [-1, 1] by a rounding error only), so every row sums to B * P * P.
+ *  out_counts    : int64 (count, nbins), overwritten.
+ *  perms         : the forward's (n_neg, B) batch maps; may be NULL unless a negative of a DG_SHARED_COORDS call is asked for.
+ * first < 0 is refused: the depth term's un-reduced tensor is dd, which the reference does not histogram.
+ * Valid after a forward on this workspace with the same desc and perms, before the next forward; the call only READS the
+ * workspace, so a later dg_corr_backward is still valid.  The values are those of the operands the forward's kernels multiply:
+ * fp16 code operands on grids above 160 positions and the identity grid (|error of a cd| <= 1e-3), fp32 rows below (2e-5).
+ */
+int dg_corr_cd_hist(const dg_corr_desc* desc, int32_t first, int32_t count, const int64_t* perms,
+                    int32_t nbins, float lo, float hi, int64_t* out_counts,
+                    void* workspace, size_t workspace_bytes, dg_stream_t stream);
 
 /*
  * Depth-guided sample locations (replaces farthest_point_sampling_depth, src/modules.py:999-1037,
