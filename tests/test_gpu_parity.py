@@ -10,7 +10,9 @@ Tolerances (stated here, measured in DESIGN.md):
   * gradients: relative L2 error <= 3e-2, cosine >= 0.9995.  The gradient is DISCONTINUOUS in cd (clamp mask
     1[lo <= cd <= hi]): a fraction phi of elements with |cd| below the cd rounding error flips its mask and the
     error of the (incoherent) sum scales like sqrt(phi); fp16 code operands give phi ~ 5e-4 -> ~2 %.  With
-    zero_clamp off (no mask) the same kernels agree to ~1e-3 (case `nozeroclamp`).
+    zero_clamp off (no mask) the same kernels agree to ~1e-3 (case `nozeroclamp`).  The arithmetic of the default backward, apart
+    from the mask flips, is pinned in tests/test_gpu_grad_margin.py: inputs whose cd stay >= 0.05 away from the clamp bounds, every
+    position row, channel and element against a float64 oracle within a factor of the operand formats' own error.
   * FPS coordinates and indices: bit exact.
 """
 import numpy as np
