@@ -74,6 +74,17 @@ extern "C" size_t dg_head_workspace_bytes(int32_t B, int32_t C, int32_t D, int32
     return dg_head_plan(B, C, D, P).total;
 }
 
+extern "C" int dg_head_plan_describe(int32_t B, int32_t C, int32_t D, int32_t P, int32_t* out) {
+    if (int rc = head_check(B, C, D, P)) return rc;
+    if (!out) return fail(DG_ERR_INVALID, "null pointer");
+    const DgHeadPlan h = dg_head_plan(B, C, D, P);
+    out[0] = h.dh_route; out[1] = h.dh_blocks; out[2] = h.tiles;
+    out[3] = h.wgrad_pair; out[4] = h.wgrad_single;
+    out[5] = h.s2a; out[6] = h.s1; out[7] = h.s2b;
+    out[8] = h.step_major ? 1 : 0;
+    return DG_OK;
+}
+
 static int head_backward_impl(int32_t B, int32_t Bs, int32_t C, int32_t D, int32_t P, const float* feat, const float* feat2, const float* keep1,
                               const float* keep2, float keep_scale, const void* hidden, const void* wscratch, const float* grad_code,
                               const float* grad_code2, float* grad_w1, float* grad_b1, float* grad_w2a, float* grad_b2a, float* grad_w2b,

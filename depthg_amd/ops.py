@@ -1,5 +1,6 @@
 """Tensor-level wrappers over the C ABI (raw device pointers + the current HIP stream).
 torch is used for device memory and streams only."""
+import collections
 import ctypes
 import os
 
@@ -774,6 +775,22 @@ def corr_main_kernel_name(desc):
     if name is None:
         _lib.check(-1, "dg_corr_main_kernel_name")
     return name.decode()
+
+
+HeadPlan = collections.namedtuple("HeadPlan", "dh_route dh_blocks tiles wgrad_pair wgrad_single s2a s1 s2b step_major")
+_HEAD_DH_ROUTES = ("TILES", "FUSED")
+_HEAD_WGRAD_FORMS = ("DIRECT", "GROUPED", "ONE_PASS")
+
+
+def head_plan(B, C, D, P):
+    """The routes dg_head_backward takes for B images (both passes of a pair call: 2 B) of C channels, D code channels and P
+    positions, from the library's own plan (dg_head_plan_describe): dh_route "TILES" (k_head_dh) / "FUSED" (k_head_dh2 on
+    dh_blocks persistent blocks, d W2b inside), tiles per image, wgrad_pair (the d W2a + d W1 launch, s2a splits) and wgrad_single
+    (a product alone, s1 splits) "DIRECT" / "GROUPED" / "ONE_PASS", s2b partial sums of d W2b, step_major.  Touches no GPU."""
+    out = (ctypes.c_int32 * 9)()
+    _lib.check(_lib.load().dg_head_plan_describe(int(B), int(C), int(D), int(P), out), "dg_head_plan_describe")
+    v = list(out)
+    return HeadPlan(_HEAD_DH_ROUTES[v[0]], v[1], v[2], _HEAD_WGRAD_FORMS[v[3]], _HEAD_WGRAD_FORMS[v[4]], v[5], v[6], v[7], bool(v[8]))
 
 
 def attention_forward(qkv, heads, scale=None, out=None):

@@ -479,6 +479,19 @@ int dg_head_backward_pair(int32_t B, int32_t C, int32_t D, int32_t P, const floa
                           float* grad_w2b, float* grad_b2b, void* workspace, size_t workspace_bytes, dg_stream_t stream);
 
 /*
+ * Measurement aid: the launch routes dg_head_backward takes for B images (dg_head_backward_pair: pass 2 B) of C channels, D code
+ * channels and P positions, from the plan the launches themselves follow.  Launches nothing and touches no GPU.  out[9] =
+ *   [0] d hidden route     0: k_head_dh, one block per 64-position tile      1: k_head_dh2, persistent blocks, d W2b inside
+ *   [1] blocks of k_head_dh2 (0 on route 0)          [2] 64-position tiles per image
+ *   [3] d W2a + d W1 launch, [4] a product alone (d W1 of the linear head, d W2b on route 0)
+ *                          0: k_head_wgrad           1: k_head_wgrad2 (grouped)            2: k_head_wgrad3 (one pass; [3] only)
+ *   [5] splits of [3]      [6] splits of [4]         [7] partial sums of d W2b ([1] on route 1, else [6])
+ *   [8] 1: d hidden and the bf16 d code are stored step-major ([image][step of 32 positions][row][32])
+ * Returns DG_OK, or the code dg_head_backward returns for a shape it refuses.
+ */
+int dg_head_plan_describe(int32_t B, int32_t C, int32_t D, int32_t P, int32_t* out);
+
+/*
  * ClusterLookup.forward (src/modules.py:664-675): inner = <normalize(x), normalize(clusters)>, probs = one-hot(arg-max) when
  * alpha is NaN (the reference's `alpha is None`) else softmax(alpha * inner), loss = -mean over (B,P) of sum_n probs * inner.
  *  x : fp32 (B,D,P)   clusters : fp32 (n,D), n * (D + 1) <= 16000   inner : fp32 (B,n,P) out (the backward reads it)

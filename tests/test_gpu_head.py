@@ -5,7 +5,12 @@ Tolerances: the head's 1x1 convolutions run as bf16 x bf16 MFMA products with fp
 mantissa, as the north_star prescribes for the correlation): code elements within 1.5e-2 of the largest |code| and 6e-3 relative
 L2 (measured ~2e-3); gradients of the head tensors 2e-2 relative L2 (bf16 operands again; 6e-2 behind the ReLU, whose mask flips
 where the bf16 pre-activation is within its rounding error of zero).  Dropout2d itself is exact (zeroed
-weight columns, fp32 scale), the returned feats are the fp32 product.  ClusterLookup and the probe loss are fp32 kernels: 1e-5."""
+weight columns, fp32 scale), the returned feats are the fp32 product.  ClusterLookup and the probe loss are fp32 kernels: 1e-5.
+
+These shapes keep B <= 4: every k_head_dh2 block processes one tile and every split of k_head_wgrad3 one or two steps.  The loops of
+the persistent kernels, the other route combinations of the backward's plan and bounds per row, column and element (on inputs whose
+ReLU masks cannot flip, so cluster2.0 is held to the same figures as the rest) live in tests/test_gpu_head_margin.py, with
+tests/head_margin_inputs.py and tests/test_head_margin_inputs_cpu.py."""
 import numpy as np
 import pytest
 import torch
