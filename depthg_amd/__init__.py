@@ -3,6 +3,8 @@
 Public surface (mirrors the reference's Python operator surface for this path):
     ContrastiveCorrelationLoss   drop-in for src/modules.py:1221-1367; .cd_histograms(): the cd histograms of its last call without
                                  the un-reduced tensors (ops.corr_cd_hist; cfg.hist_freq / cfg.dg_hist_bins in the segmenter)
+    ContrastiveCRFLoss           src/modules.py:1510-1542: forward() the reference's (B,n,n) tensor in plain torch, mean_loss() the training
+                                 step's `crf_loss_fn(resize(img, 56), norm(resize(code, 56))).mean()` as fused HIP kernels (cfg.crf_weight)
     depth_decay                  scalar decay schedules (src/depth_decay_modules.py) + the live legacy decay
     training                     the caller arithmetic around the loss (means, weighted total, log keys;
                                  src/train_segmentation.py:240-350)
@@ -24,6 +26,8 @@ Public surface (mirrors the reference's Python operator surface for this path):
     ops                          thin ctypes binding of the C ABI in include/depthg_corr.h
 """
 from .loss import ContrastiveCorrelationLoss  # noqa: F401
+from . import crf_loss  # noqa: F401
+from .crf_loss import ContrastiveCRFLoss  # noqa: F401
 from . import depth_decay  # noqa: F401
 from . import training  # noqa: F401
 from . import metrics  # noqa: F401
@@ -40,6 +44,6 @@ from . import featurizer  # noqa: F401
 from .featurizer import DinoFeaturizer  # noqa: F401
 from . import segmenter  # noqa: F401
 
-__all__ = ["ContrastiveCorrelationLoss", "depth_decay", "training", "metrics", "evaluation", "predict_and_score", "crf", "dense_crf",
+__all__ = ["ContrastiveCorrelationLoss", "ContrastiveCRFLoss", "crf_loss", "depth_decay", "training", "metrics", "evaluation", "predict_and_score", "crf", "dense_crf",
            "batched_crf", "knn", "lhp", "optim", "FusedAdam", "FusedAdamSet", "segmenter", "vit", "featurizer",
            "DinoFeaturizer"]

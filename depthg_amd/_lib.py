@@ -97,6 +97,10 @@ SIGNATURES = {
     "dg_segment_unary": (_I, [vp, vp] + [i32] * 4 + [vp, vp, i32, vp, i32, i32, i32, f32, vp, vp, _SZ, vp]),
     "dg_crf_filter": (_I, [vp, vp] + [i32] * 5 + [f32, f32, vp, vp, _SZ, vp]),
     "dg_dense_crf": (_I, [vp, vp] + [i32] * 3 + [vp, i32, i32] + [f32] * 5 + [vp, vp, vp, _SZ, vp]),
+    # contrastive CRF loss term
+    "dg_crfloss_workspace_bytes": (_SZ, [i32] * 3),
+    "dg_crfloss_forward": (_I, [vp, vp] + [i32] * 7 + [vp, i32] + [f32] * 6 + [vp, _SZ, vp, vp]),
+    "dg_crfloss_backward": (_I, [vp, _SZ, vp] + [i32] * 6 + [vp, vp, vp]),
     # optimiser
     "dg_adam_step": (_I, [ctypes.POINTER(AdamSeg), i32, ctypes.POINTER(AdamGroup), i32, i32, vp, vp]),
     # frozen ViT

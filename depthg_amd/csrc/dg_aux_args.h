@@ -1,4 +1,4 @@
-// The stand-alone operations (dg_sample, dg_metrics, dg_knn, dg_lhp, dg_optim, dg_attn, dg_linear .hip; dg_api_aux.hip): constants and launchers.
+// The stand-alone operations (dg_sample, dg_metrics, dg_knn, dg_lhp, dg_crf_loss, dg_optim, dg_attn, dg_linear .hip; dg_api_aux.hip): constants and launchers.
 #pragma once
 #include "dg_common.h"
 
@@ -28,6 +28,37 @@ hipError_t dg_launch_lhp_map_bwd(int mode, const float* g, const float* map, con
 // at most DG_ADAM_MAX_SEGS segments; tickets: null, or the first segment's counter (segment k takes tickets[k])
 hipError_t dg_launch_adam(const dg_adam_seg* segs, int n_seg, const dg_adam_group* groups, int n_groups, bool device_steps,
                           unsigned int* tickets, hipStream_t s);
+
+// ---- the contrastive CRF loss term (dg_crf_loss.hip; src/modules.py:1510-1542, src/train_segmentation.py:413-419)
+#define DG_CRFL_MAX_D 128
+#define DG_CRFL_MAX_N 4096                   // samples per image: k_crfl_backward lists a pixel's samples in LDS (8 bytes each)
+#define DG_CRFL_MAX_SIZE 256
+#define DG_CRFL_MAX_SIDE 16384               // h, w, H, W: pixel offsets inside one plane stay below 2^28
+// The workspace (include/depthg_corr.h describes it to callers): byte offsets of its sections, each a multiple of 256.
+struct DgCrflWs { size_t S, G, g4, nrm, q, part, total; };
+inline DgCrflWs dg_crfl_ws(int B, int D, int n) {
+    const size_t rows = (size_t)B * n, Dp = (size_t)(D + 3) / 4 * 4;
+    auto up256 = [](size_t x) { return (x + 255) / 256 * 256; };
+    DgCrflWs w;
+    w.S = 0;
+    w.G = w.S + up256(rows * Dp * 4);
+    w.g4 = w.G + up256(rows * Dp * 4);
+    w.nrm = w.g4 + up256(rows * 16);
+    w.q = w.nrm + up256(rows * 4);
+    w.part = w.q + up256(rows * 8);
+    w.total = w.part + up256((size_t)B * ((n + 63) / 64) * 8);      // one double per block of k_crfl_pair, at most
+    return w;
+}
+// One block for the four kernels; forward: everything but grad_*; backward: the workspace sections, coords, sizes and grad_*.
+struct DgCrflArgs {
+    const float* code; const float* img; const int* coords;
+    float* S; float* G; float* g4; float* nrm; double* q; double* part; float* loss;
+    const float* grad_out; float* grad_code;
+    int B, D, Dp, h, w, H, W, size, n;
+    float a2, b2, g2, w1, w2, shift;         // 2 alpha, 2 beta, 2 gamma: the divisors as the reference forms them
+};
+hipError_t dg_launch_crfl_forward(const DgCrflArgs& A, hipStream_t s);      // k_crfl_sample, k_crfl_pair, k_crfl_reduce
+hipError_t dg_launch_crfl_backward(const DgCrflArgs& A, hipStream_t s);     // k_crfl_backward
 
 // ---- fused attention forward of the frozen ViT (dg_attn.hip; src/dino/vision_transformer.py:80-92)
 size_t dg_attn_workspace(int B, int heads, int N);           // bytes of the packed bf16 K / V images

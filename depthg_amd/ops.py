@@ -259,6 +259,77 @@ def corr_cd_hist(desc, workspace, first, count, perms=None, bins=64, range=(-1.0
     return out
 
 
+def _crf_loss_coords(coords, n, dev):
+    if coords.dim() != 2 or coords.shape[0] != 2 or coords.shape[1] < 1:
+        raise ValueError(f"depthg_amd: coords must be (2, n) - the y row, then the x row - got {tuple(coords.shape)}")
+    if coords.dtype not in (torch.int32, torch.int64) or (n is not None and coords.shape[1] != n):
+        raise ValueError(f"depthg_amd: coords must be integer (2, {n if n is not None else 'n'}), got {coords.dtype} {tuple(coords.shape)}")
+    if _on_gpu(coords, "coords").device != dev:
+        raise RuntimeError(f"depthg_amd: coords live on {coords.device}, the maps on {dev}")
+    return coords.detach().to(torch.int32).contiguous()
+
+
+def crf_loss_workspace_sections(workspace, B, D, n):
+    """Views of what crf_loss_forward left in its workspace (the layout of include/depthg_corr.h: sections at multiples of 256
+    bytes): S (B,n,Dp) the normalised resized code vectors (Dp = D rounded up to 4, zero columns above D), G (B,n,Dp) = K S without
+    the rows' own terms, g (B,n,4) the resized image colours (a zero fourth column), norm (B,n), q (B,n) fp64 = S_a . G_a / |S_a|^2."""
+    Dp = (D + 3) // 4 * 4
+    up = lambda v: (v + 255) // 256 * 256
+    rows, off, out = B * n, 0, {}
+    for name, width, dtype in (("S", Dp, torch.float32), ("G", Dp, torch.float32), ("g", 4, torch.float32), ("norm", 1, torch.float32),
+                               ("q", 1, torch.float64)):
+        nbytes = rows * width * dtype.itemsize
+        out[name] = workspace[off:off + nbytes].view(dtype).view((B, n, width) if width > 1 else (B, n))
+        off += up(nbytes)
+    return out
+
+
+def crf_loss_forward(code, img, coords, size, alpha, beta, gamma, w1, w2, shift):
+    """mean(ContrastiveCRFLoss(resize(img, size), norm(resize(code, size)))) at the samples `coords` (dg_crfloss_forward;
+    src/modules.py:1510-1542, src/train_segmentation.py:413-419): code (B,D,h,w), img (B,3,H,W) on the GPU, coords integer (2,n)
+    (y row, x row) on the size x size grid.  Returns (loss, workspace): a 0-dim fp32 device tensor and what crf_loss_backward needs."""
+    lib = _lib.load()
+    if code.dim() != 4 or img.dim() != 4 or img.shape[0] != code.shape[0] or img.shape[1] != 3:
+        raise ValueError(f"depthg_amd: code must be (B, D, h, w) and img (B, 3, H, W), got {tuple(code.shape)} and {tuple(img.shape)}")
+    code, img = _f32c(code, "code"), _f32c(img, "img")
+    dev = code.device
+    if img.device != dev:
+        raise RuntimeError(f"depthg_amd: code lives on {dev}, img on {img.device}")
+    coords = _crf_loss_coords(coords, None, dev)
+    B, D, h, w = code.shape
+    n = coords.shape[1]
+    need = lib.dg_crfloss_workspace_bytes(B, D, n)
+    if need == 0:
+        raise ValueError(f"depthg_amd: no CRF-loss plan for B={B}, D={D}, n={n} (B <= 65535, D <= 128, n <= 4096)")
+    ws = _empty((need,), torch.uint8, dev)
+    loss = _empty((), torch.float32, dev)
+    rc = lib.dg_crfloss_forward(_ptr(code), _ptr(img), B, D, h, w, img.shape[2], img.shape[3], int(size), _ptr(coords), n, float(alpha),
+                                float(beta), float(gamma), float(w1), float(w2), float(shift), _ptr(ws), ws.numel(), _ptr(loss),
+                                _stream(dev))
+    _lib.check(rc, "dg_crfloss_forward")
+    return loss, ws
+
+
+def crf_loss_backward(workspace, coords, shape_code, size, grad_out, out=None):
+    """d loss / d code (B,D,h,w) of the crf_loss_forward whose workspace this is, times the 0-dim device tensor `grad_out`
+    (dg_crfloss_backward); every element is written.  out: optional result buffer."""
+    lib = _lib.load()
+    B, D, h, w = (int(v) for v in shape_code)
+    dev = _on_gpu(workspace, "workspace").device
+    coords = _crf_loss_coords(coords, None, dev)
+    grad_out = _f32c(grad_out, "grad_out")
+    if grad_out.numel() != 1 or grad_out.device != dev:
+        raise ValueError(f"depthg_amd: grad_out must be one element on {dev}, got {tuple(grad_out.shape)} on {grad_out.device}")
+    if out is None:
+        out = _empty((B, D, h, w), torch.float32, dev)
+    elif not (out.device == dev and out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (B, D, h, w)):
+        raise ValueError(f"depthg_amd: `out` must be a contiguous float32 {(B, D, h, w)} tensor on {dev}")
+    rc = lib.dg_crfloss_backward(_ptr(workspace), workspace.numel(), _ptr(coords), B, D, h, w, int(size), coords.shape[1], _ptr(grad_out),
+                                 _ptr(out), _stream(dev))
+    _lib.check(rc, "dg_crfloss_backward")
+    return out
+
+
 def fps_coords(depth, feat_hw, n_samples, return_inds=False):
     """depth (B,1,H,W) on GPU -> coords (B,S,S,2) in [-1,1) (already *2-1)."""
     lib = _lib.load()

@@ -29,6 +29,8 @@ its attention through the HIP kernel of dg_attn.hip and cfg.dg_fused_linear its 
 residual adds) through the bf16 MFMA kernel of dg_linear.hip.  On the reference's histogram steps (cfg.hist_freq, src/train_segmentation.py:229-231,
 298-301) training_step puts the histograms of the three un-reduced cd tensors into its logs as `hist/intra_cd`, `hist/inter_cd`, `hist/neg_cd`
 (int64 counts on the device, cfg.dg_hist_bins bins, default 64) - from ContrastiveCorrelationLoss.cd_histograms(), without the tensors.
+With cfg.crf_weight > 0 the step adds the contrastive CRF term (src/train_segmentation.py:413-419) through crf_loss.ContrastiveCRFLoss.mean_loss
+- the fused HIP kernels of dg_crf_loss.hip - and logs it as `loss/crf`.
 """
 from types import SimpleNamespace
 from typing import Dict, Optional
@@ -36,6 +38,7 @@ from typing import Dict, Optional
 import torch
 import torch.nn as nn
 
+from .crf_loss import ContrastiveCRFLoss
 from .depth_decay import legacy_decay_step
 from .evaluation import predict_and_score
 from .featurizer import DinoFeaturizer, FrozenBackboneFeaturizer
@@ -106,6 +109,10 @@ class UnsupervisedSegmenter(nn.Module):
         self.test_cluster_metrics = UnsupervisedMetrics("final/cluster/", n_classes, cfg.extra_clusters, True)
         self.test_linear_metrics = UnsupervisedMetrics("final/linear/", n_classes, 0, False)
         self.linear_probe_loss_fn = nn.CrossEntropyLoss()                             # :127 (kept for the surface; the step uses the fused HIP loss)
+        # :128-129; the reference's defaults (src/configs/train_config.yml) where a configuration lacks the keys
+        self.crf_loss_fn = ContrastiveCRFLoss(getattr(cfg, "crf_samples", 1000), getattr(cfg, "alpha", .5), getattr(cfg, "beta", .15),
+                                              getattr(cfg, "gamma", .05), getattr(cfg, "w1", 10.0), getattr(cfg, "w2", 3.0),
+                                              getattr(cfg, "shift", 0.0))
         self.contrastive_corr_loss_fn = ContrastiveCorrelationLoss(cfg)               # :131 (shares cfg: the decay below mutates it)
         for p in self.contrastive_corr_loss_fn.parameters():                          # :136
             p.requires_grad = False
@@ -236,6 +243,13 @@ class UnsupervisedSegmenter(nn.Module):
         # the legacy decays sit at function-body level in the reference: they run every step, whatever correspondence_weight is
         legacy_decay_step(cfg, self.contrastive_corr_loss_fn.cfg, self.global_step)                  # :356-375 (mutates cfg)
 
+        # :413-419: the contrastive CRF term, one fused HIP forward (the maps are resized at the crf_samples positions only, the
+        # similarity kernel is formed on the fly) and one HIP backward - ContrastiveCRFLoss.mean_loss.  Off: nothing is drawn or launched.
+        if getattr(cfg, "crf_weight", 0) > 0:
+            crf = self.crf_loss_fn.mean_loss(img, code)
+            logs["loss/crf"] = crf.detach()
+            loss = loss + cfg.crf_weight * crf
+
         # probes on the detached code (:421-444)
         detached_code = code.detach().clone()
         # resize to the label resolution + masked cross entropy in one HIP kernel (the reference materialises the logits at label
@@ -342,6 +356,8 @@ def default_segmenter_cfg(**over) -> SimpleNamespace:
         fps_until_step=0, post_fps_samples=11, fps_sample_decay=True, fps_sample_decay_every_steps=1000,
         fps_sample_decay_factor=0.9, fps_min_samples=0, lhp=False, lhp_weight=0.2, lhp_weight_balance=False,
         lhp_depth_weight=0.5,
+        # the contrastive CRF term (crf_weight > 0): ContrastiveCRFLoss(crf_samples, alpha, beta, gamma, w1, w2, shift)
+        crf_samples=1000, alpha=.5, beta=.15, gamma=.05, w1=10.0, w2=3.0, shift=0.0,
         # validation
         n_images=5,
         # build-side: the step's three Adams as one HIP launch (optim.FusedAdam / FusedAdamSet)

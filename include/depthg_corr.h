@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define DG_VERSION 118   /* 118: dg_corr_cd_hist (one more export under the same number: the layouts and meanings of every earlier entry point are unchanged, and a binding that declares the new symbol refuses a library without it when it loads), dg_sampled_sumsq, dg_corr_forward_extnorm (feature maps wider than 768 channels on SAMPLED grids above 160 positions, in channel chunks); 117: DG_FEATS_UNIT, dg_normalize_split (feature maps wider than 768 channels on the dense identity grid, in chunks of the width the operand kernels hold: the loss is linear in the feature correlation); 116: dg_prof_main_span takes FOUR words (+ the workgroups' lifetimes in shader cycles and wall ticks: the clock the CUs held); 115: dg_corr_intra_folded; 114: dg_fps_coords_pair takes a workspace (dg_fps_workspace_bytes(2 B, h, w): the pooled depth maps, written by a launch over the whole chip in front of the sampler), dg_corr_materialize_shared, dg_prof_main_span (the fused correlation launch's execution span inside a replayed step), sample grids of <= 160 positions at any feature width (fused small-grid kernel); 113: dg_corr_forward_masked; 112: dg_rand_coords_state; 111: dg_head_forward_pair / dg_head_backward_pair; 110: dg_fps_coords_pair; 109: dg_knn_similarities; 108: dg_corr_desc.code_h / code_w (code maps of another resolution than the feature maps: the FeaturePyramidNet producer, src/modules.py:732-766), dg_corr_desc.flags DG_EXACT_MASKS; 107: dg_head_*, dg_cluster_lookup_*, dg_probe_ce_*; 106: dg_corr_main_kernel_name; 105: dg_corr_forward_draw; 104: dg_lhp_map_forward / dg_lhp_map_backward; 103: dg_super_perms_state; 102: DG_LINE_GRID, dg_salience_coords, dg_simple_depth_coords; 101: total weights, DG_OUT_TOTAL */
+#define DG_VERSION 118   /* 118: dg_corr_cd_hist and the three dg_crfloss entry points (more exports under the same number: the layouts and meanings of every earlier entry point are unchanged, and a binding that declares a new symbol refuses a library without it when it loads), dg_sampled_sumsq, dg_corr_forward_extnorm (feature maps wider than 768 channels on SAMPLED grids above 160 positions, in channel chunks); 117: DG_FEATS_UNIT, dg_normalize_split (feature maps wider than 768 channels on the dense identity grid, in chunks of the width the operand kernels hold: the loss is linear in the feature correlation); 116: dg_prof_main_span takes FOUR words (+ the workgroups' lifetimes in shader cycles and wall ticks: the clock the CUs held); 115: dg_corr_intra_folded; 114: dg_fps_coords_pair takes a workspace (dg_fps_workspace_bytes(2 B, h, w): the pooled depth maps, written by a launch over the whole chip in front of the sampler), dg_corr_materialize_shared, dg_prof_main_span (the fused correlation launch's execution span inside a replayed step), sample grids of <= 160 positions at any feature width (fused small-grid kernel); 113: dg_corr_forward_masked; 112: dg_rand_coords_state; 111: dg_head_forward_pair / dg_head_backward_pair; 110: dg_fps_coords_pair; 109: dg_knn_similarities; 108: dg_corr_desc.code_h / code_w (code maps of another resolution than the feature maps: the FeaturePyramidNet producer, src/modules.py:732-766), dg_corr_desc.flags DG_EXACT_MASKS; 107: dg_head_*, dg_cluster_lookup_*, dg_probe_ce_*; 106: dg_corr_main_kernel_name; 105: dg_corr_forward_draw; 104: dg_lhp_map_forward / dg_lhp_map_backward; 103: dg_super_perms_state; 102: DG_LINE_GRID, dg_salience_coords, dg_simple_depth_coords; 101: total weights, DG_OUT_TOTAL */
 
 /* flags of dg_corr_desc.flags (names follow the cfg keys read at src/modules.py:1236-1352) */
 #define DG_POINTWISE      (1u << 0)  /* cfg.pointwise: spatial centering of fd (modules.py:1236-1239) */
@@ -583,6 +583,44 @@ int dg_crf_filter(const float* img, const float* values, int32_t B, int32_t C, i
 int dg_dense_crf(const float* img, const float* unary, int32_t B, int32_t H, int32_t W, const int32_t* group_ends, int32_t n_groups,
                  int32_t n_iter, float pos_w, float pos_xy_std, float bi_w, float bi_xy_std, float bi_rgb_std, float* q, int64_t* preds,
                  void* workspace, size_t workspace_bytes, dg_stream_t stream);
+
+/*
+ * The contrastive CRF loss term of the training step (cfg.crf_weight).  Replaces ContrastiveCRFLoss.forward (src/modules.py:1510-1542)
+ * TOGETHER WITH its caller's resize(img, size), norm(resize(code, size)) and .mean() (src/train_segmentation.py:413-419; resize:
+ * src/utils.py:60-61, bilinear, align_corners=False, no antialiasing; norm: src/modules.py:789-790, F.normalize(dim=1, eps=1e-10)):
+ *      loss = mean over (B, n, n) of -sims * K,     sims_ac = S_a . S_c,
+ *      K_ac = w1 exp(-|p_a - p_c|^2 / (2 alpha) - |g_a - g_c|^2 / (2 beta)) + w2 exp(-|p_a - p_c|^2 / (2 gamma)) - shift
+ * with S_a the normalised resized code vector and g_a the resized image colours at sample a, p_a = (y, x) its coordinates on the
+ * size x size grid.  The two maps are resized AT the n sampled positions only; neither a size x size map, nor the (B,3,n,n) guidance
+ * differences, nor any (B,n,n) tensor is written: K is symmetric, so with G_a = sum_c K_ac S_c the loss is -(1 / (B n^2)) sum S_a . G_a
+ * and d loss / d S_a = -(2 / (B n^2)) G_a.
+ *  code      : fp32 (B,D,h,w)              img : fp32 (B,3,H,W)        (the four sizes are free: up- and down-scaling)
+ *  coords    : int32 (2,n) - row 0 the y, row 1 the x of every sample on the size x size grid, shared by the batch, as the
+ *              reference's torch.cat([randint(0, h), randint(0, w)]) (:1529-1531).  Device data: values outside [0, size) are
+ *              clamped into it by the kernels.
+ *  workspace : dg_crfloss_workspace_bytes(B, D, n) bytes (0: bad arguments), 16-byte aligned.  Sections, each starting at the next
+ *              multiple of 256 bytes, Dp = D rounded up to 4:  S fp32 (B,n,Dp) | G fp32 (B,n,Dp) | g fp32 (B,n,4) | |x| fp32 (B,n)
+ *              (the norm in front of the eps clamp) | q fp64 (B,n) | the blocks' fp64 partial sums.  G_a is the sum over c != a
+ *              of K_ac S_c and q_a = S_a . G_a / |S_a|^2: the backward projects G_a off S_a, which removes the row's own term
+ *              K_aa S_a whatever its size, so that term (K_aa = w1 + w2 - shift, the largest by far where K is nearly diagonal)
+ *              enters the loss as the number it is and never the gradient.  On a row under the eps clamp (|x| < eps) G_a includes
+ *              it and q_a is 0.  The stored S_a is the fp64-normalised vector rounded to fp32; what its norm still differs from 1
+ *              by is taken out of the loss to first order.
+ *  out_loss  : one fp32 in device memory.
+ * dg_crfloss_backward: d loss / d code for the forward whose results are in `workspace` (same coords, B, D, h, w, size, n), times the
+ * upstream gradient *grad_out, read on the device (no host synchronisation): through norm (dx = (g - S (S . g)) / |x| where
+ * |x| >= eps, g / eps otherwise) and the resize's taps.  grad_code fp32 (B,D,h,w) is written completely, zeros included; no
+ * gradient goes to img.  Destination-major, no atomics: both calls give the same bits on the same inputs.
+ * Refused before any launch (DG_ERR_INVALID / DG_ERR_UNSUPPORTED): null or misaligned pointers (4 bytes; the workspace 16), D outside
+ * 1..128, n outside 1..4096, size outside 1..256, non-positive B, h, w, H, W (B <= 65535, sides <= 16384), alpha, beta or gamma <= 0,
+ * a workspace that is too small (DG_ERR_WORKSPACE).  fp32 arithmetic with expf and IEEE divisions; the loss sum in fp64.
+ */
+size_t dg_crfloss_workspace_bytes(int32_t B, int32_t D, int32_t n);
+int dg_crfloss_forward(const float* code, const float* img, int32_t B, int32_t D, int32_t h, int32_t w, int32_t H, int32_t W,
+                       int32_t size, const int32_t* coords, int32_t n, float alpha, float beta, float gamma, float w1, float w2,
+                       float shift, void* workspace, size_t workspace_bytes, float* out_loss, dg_stream_t stream);
+int dg_crfloss_backward(const void* workspace, size_t workspace_bytes, const int32_t* coords, int32_t B, int32_t D, int32_t h,
+                        int32_t w, int32_t size, int32_t n, const float* grad_out, float* grad_code, dg_stream_t stream);
 
 /*
  * The optimisation step's Adams (src/train_segmentation.py:447-455: net_optim.step(), cluster_probe_optim.step(),
