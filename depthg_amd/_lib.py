@@ -101,6 +101,10 @@ SIGNATURES = {
     "dg_crfloss_workspace_bytes": (_SZ, [i32] * 3),
     "dg_crfloss_forward": (_I, [vp, vp] + [i32] * 7 + [vp, i32] + [f32] * 6 + [vp, _SZ, vp, vp]),
     "dg_crfloss_backward": (_I, [vp, _SZ, vp] + [i32] * 6 + [vp, vp, vp]),
+    # augmentation-alignment loss term
+    "dg_augalign_workspace_bytes": (_SZ, [i32] * 5),
+    "dg_augalign_forward": (_I, [vp] * 3 + [i32] * 7 + [vp, _SZ, vp, vp]),
+    "dg_augalign_backward": (_I, [vp, vp, vp, _SZ] + [i32] * 5 + [vp] * 4),
     # optimiser
     "dg_adam_step": (_I, [ctypes.POINTER(AdamSeg), i32, ctypes.POINTER(AdamGroup), i32, i32, vp, vp]),
     # frozen ViT

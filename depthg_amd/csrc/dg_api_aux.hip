@@ -1,5 +1,5 @@
 // C ABI of the gfx950 DepthG library (include/depthg_corr.h), the units' shared state and the small subsystems: version and error
-// text, the library's side stream, batch maps / random draws / coordinate samplers, kNN, LHP, the contrastive CRF loss term, fused Adam, ViT attention and linear.
+// text, the library's side stream, batch maps / random draws / coordinate samplers, kNN, LHP, the contrastive CRF and augmentation-alignment loss terms, fused Adam, ViT attention and linear.
 // Host-side only: argument checks and kernel launches on the caller's stream.
 #include "dg_api.h"
 #include "dg_aux_args.h"
@@ -291,6 +291,79 @@ extern "C" int dg_crfloss_backward(const void* workspace, size_t workspace_bytes
     A.B = B; A.D = D; A.Dp = (D + 3) / 4 * 4; A.h = h; A.w = w; A.size = size; A.n = n;
     crfl_sections(A, const_cast<void*>(workspace), B, D, n);
     DG_HIP(dg_launch_crfl_backward(A, static_cast<hipStream_t>(stream_)));
+    return DG_OK;
+}
+
+// ---- the augmentation-alignment loss term (dg_aug.hip)
+static int aug_check(const char* who, int32_t B, int32_t D, int32_t h, int32_t w, int32_t n) {
+    if (B < 1 || D < 1 || h < 1 || w < 1 || n < 1)
+        return fail(DG_ERR_INVALID, "%s: B=%d, D=%d, code map %dx%d and n=%d must be positive", who, B, D, h, w, n);
+    if (B > 65535 || D > (1 << 20)) return fail(DG_ERR_UNSUPPORTED, "%s: B=%d above 65535 or D=%d above 2^20", who, B, D);
+    if (!dg_aug_fits(h, w, n))
+        return fail(DG_ERR_UNSUPPORTED, "%s: code map %dx%d under %dx%d positions: the inverse tap records index positions with 16 bits "
+                    "(n <= 255) and are built in LDS (8 h w + 24 n^2 + 4 = %zu bytes, %d at most)", who, h, w, n, n,
+                    h <= 16384 && w <= 16384 && n <= 16384 ? dg_aug_taps_lds(h * w, n * n) : (size_t)0, DG_AUG_MAX_LDS);
+    return DG_OK;
+}
+
+static void aug_sections(DgAugArgs& A, void* workspace, int32_t B, int32_t D, int32_t h, int32_t w, int32_t n) {
+    const DgAugWs ws = dg_aug_ws(B, D, h, w, n);
+    char* base = static_cast<char*>(workspace);
+    A.ds = reinterpret_cast<float*>(base + ws.ds);
+    A.nu = reinterpret_cast<float*>(base + ws.nu);
+    A.nv = reinterpret_cast<float*>(base + ws.nv);
+    A.s = reinterpret_cast<float*>(base + ws.s);
+    A.part = reinterpret_cast<double*>(base + ws.part);
+    A.du = reinterpret_cast<float*>(base + ws.du);
+    A.taps = base + ws.taps;
+    A.dsd = reinterpret_cast<double*>(base + ws.dsd);
+}
+
+extern "C" size_t dg_augalign_workspace_bytes(int32_t B, int32_t D, int32_t h, int32_t w, int32_t n) {
+    if (B < 1 || B > 65535 || D < 1 || D > (1 << 20) || !dg_aug_fits(h, w, n)) return 0;
+    return dg_aug_ws(B, D, h, w, n).total;
+}
+
+extern "C" int dg_augalign_forward(const float* code, const float* code_aug, const float* coord_aug, int32_t B, int32_t D, int32_t h,
+                                   int32_t w, int32_t n, int32_t H, int32_t W, void* workspace, size_t workspace_bytes, float* out_loss,
+                                   dg_stream_t stream_) {
+    if (int rc = aug_check("dg_augalign_forward", B, D, h, w, n)) return rc;
+    if (H < 1 || W < 1) return fail(DG_ERR_INVALID, "dg_augalign_forward: coordinate map %dx%d must be positive", H, W);
+    if (H > DG_AUG_MAX_SIDE || W > DG_AUG_MAX_SIDE)
+        return fail(DG_ERR_UNSUPPORTED, "dg_augalign_forward: coordinate map %dx%d above %d a side", H, W, DG_AUG_MAX_SIDE);
+    if (!code || !code_aug || !coord_aug || !workspace || !out_loss) return fail(DG_ERR_INVALID, "dg_augalign_forward: null pointer");
+    if ((((uintptr_t)code | (uintptr_t)code_aug | (uintptr_t)coord_aug | (uintptr_t)out_loss) & 3) || ((uintptr_t)workspace & 15))
+        return fail(DG_ERR_INVALID, "dg_augalign_forward: code, code_aug, coord_aug and out_loss must be 4-byte aligned, workspace 16-byte aligned");
+    const size_t need = dg_aug_ws(B, D, h, w, n).total;
+    if (workspace_bytes < need)
+        return fail(DG_ERR_WORKSPACE, "workspace of %zu bytes, %zu needed (dg_augalign_workspace_bytes)", workspace_bytes, need);
+    DgAugArgs A;
+    memset(&A, 0, sizeof(A));
+    A.code = code; A.code_aug = code_aug; A.coord_aug = coord_aug; A.loss = out_loss;
+    A.B = B; A.D = D; A.h = h; A.w = w; A.n = n; A.H = H; A.W = W;
+    aug_sections(A, workspace, B, D, h, w, n);
+    DG_HIP(dg_launch_aug_forward(A, static_cast<hipStream_t>(stream_)));
+    return DG_OK;
+}
+
+extern "C" int dg_augalign_backward(const float* code, const float* code_aug, void* workspace, size_t workspace_bytes, int32_t B,
+                                    int32_t D, int32_t h, int32_t w, int32_t n, const float* grad_out, float* grad_code,
+                                    float* grad_code_aug, dg_stream_t stream_) {
+    if (int rc = aug_check("dg_augalign_backward", B, D, h, w, n)) return rc;
+    if (!code || !code_aug || !workspace || !grad_out || !grad_code || !grad_code_aug)
+        return fail(DG_ERR_INVALID, "dg_augalign_backward: null pointer");
+    if ((((uintptr_t)code | (uintptr_t)code_aug | (uintptr_t)grad_out | (uintptr_t)grad_code | (uintptr_t)grad_code_aug) & 3) ||
+        ((uintptr_t)workspace & 15))
+        return fail(DG_ERR_INVALID, "dg_augalign_backward: the maps, grad_out and the gradients must be 4-byte aligned, workspace 16-byte aligned");
+    const size_t need = dg_aug_ws(B, D, h, w, n).total;
+    if (workspace_bytes < need)
+        return fail(DG_ERR_WORKSPACE, "workspace of %zu bytes, %zu needed (dg_augalign_workspace_bytes)", workspace_bytes, need);
+    DgAugArgs A;
+    memset(&A, 0, sizeof(A));
+    A.code = code; A.code_aug = code_aug; A.grad_out = grad_out; A.grad_code = grad_code; A.grad_code_aug = grad_code_aug;
+    A.B = B; A.D = D; A.h = h; A.w = w; A.n = n;
+    aug_sections(A, workspace, B, D, h, w, n);
+    DG_HIP(dg_launch_aug_backward(A, static_cast<hipStream_t>(stream_)));
     return DG_OK;
 }
 

@@ -1,6 +1,7 @@
-// The stand-alone operations (dg_sample, dg_metrics, dg_knn, dg_lhp, dg_crf_loss, dg_optim, dg_attn, dg_linear .hip; dg_api_aux.hip): constants and launchers.
+// The stand-alone operations (dg_sample, dg_metrics, dg_knn, dg_lhp, dg_crf_loss, dg_aug, dg_optim, dg_attn, dg_linear .hip; dg_api_aux.hip): constants and launchers.
 #pragma once
 #include "dg_common.h"
+#include "dg_taps.h"        // dg_taps_record_bytes: the augmentation-alignment workspace
 
 hipError_t dg_launch_salience_coords(const float* sal, int B, int H, int W, int n, const float* u_sel, const float* u_fb,
                                      float* out, hipStream_t s);
@@ -59,6 +60,43 @@ struct DgCrflArgs {
 };
 hipError_t dg_launch_crfl_forward(const DgCrflArgs& A, hipStream_t s);      // k_crfl_sample, k_crfl_pair, k_crfl_reduce
 hipError_t dg_launch_crfl_backward(const DgCrflArgs& A, hipStream_t s);     // k_crfl_backward
+
+// ---- the augmentation-alignment loss term (dg_aug.hip; src/train_segmentation.py:400-411)
+// The backward's inverse tap records (dg_taps.h) index the n^2 positions with a ushort and are built in one block's LDS: counters and
+// offsets over the h w code pixels, four (weight, position) slots per position.
+inline size_t dg_aug_taps_lds(int HW, int P) { return (((size_t)(2 * (size_t)HW + 1) * 4 + (size_t)P * 24) + 15) / 16 * 16; }
+#define DG_AUG_MAX_LDS (160 * 1024 - 64)     // the workgroup's LDS less build_taps_block's static words
+#define DG_AUG_MAX_SIDE 16384                // H, W: offsets inside one coordinate map stay below 2^29
+inline bool dg_aug_fits(int h, int w, int n) {
+    if (h < 1 || w < 1 || n < 1 || n > 255 || (long long)h * w > (1 << 20)) return false;      // n^2 <= 65025 < 2^16
+    return dg_aug_taps_lds(h * w, n * n) <= DG_AUG_MAX_LDS;
+}
+// The workspace (include/depthg_corr.h describes it to callers): byte offsets of its sections, each a multiple of 256.
+struct DgAugWs { size_t ds, nu, nv, s, part, du, taps, dsd, total; };
+inline DgAugWs dg_aug_ws(int B, int D, int h, int w, int n) {
+    const size_t rows = (size_t)B * n * n;
+    auto up256 = [](size_t x) { return (x + 255) / 256 * 256; };
+    DgAugWs ws;
+    ws.ds = 0;
+    ws.nu = ws.ds + up256(rows * 8);
+    ws.nv = ws.nu + up256(rows * 4);
+    ws.s = ws.nv + up256(rows * 4);
+    ws.part = ws.s + up256(rows * 4);
+    ws.du = ws.part + up256((size_t)B * (((size_t)n * n + 63) / 64) * 8);       // one double per block of k_aug_forward
+    ws.taps = ws.du + up256(rows * D * 4);
+    ws.dsd = ws.taps + up256((size_t)B * dg_taps_record_bytes(h * w, n * n));
+    ws.total = ws.dsd + up256(rows * 16);                                        // ds once more, fp64, by position
+    return ws;
+}
+// One block for the five kernels; forward: the maps, the forward sections, loss; backward: everything but coord_aug and loss.
+struct DgAugArgs {
+    const float* code; const float* code_aug; const float* coord_aug;
+    float* ds; double* dsd; float* nu; float* nv; float* s; double* part; float* du; char* taps; float* loss;
+    const float* grad_out; float* grad_code; float* grad_code_aug;
+    int B, D, h, w, n, H, W;
+};
+hipError_t dg_launch_aug_forward(const DgAugArgs& A, hipStream_t s);        // k_aug_forward, k_aug_reduce
+hipError_t dg_launch_aug_backward(const DgAugArgs& A, hipStream_t s);       // k_aug_bwd_pos, k_aug_taps, k_aug_gather
 
 // ---- fused attention forward of the frozen ViT (dg_attn.hip; src/dino/vision_transformer.py:80-92)
 size_t dg_attn_workspace(int B, int heads, int N);           // bytes of the packed bf16 K / V images

@@ -330,6 +330,87 @@ def crf_loss_backward(workspace, coords, shape_code, size, grad_out, out=None):
     return out
 
 
+def _aug_alignment_maps(code, code_aug):
+    if code.dim() != 4 or code_aug.dim() != 4:
+        raise ValueError(f"depthg_amd: code must be (B, D, h, w) and code_aug (B, D, n, n), got {tuple(code.shape)} and {tuple(code_aug.shape)}")
+    if code.shape[:2] != code_aug.shape[:2]:
+        raise ValueError(f"depthg_amd: code {tuple(code.shape)} and code_aug {tuple(code_aug.shape)} must share the batch size and D")
+    if code_aug.shape[2] != code_aug.shape[3]:
+        raise ValueError(f"depthg_amd: code_aug must be square (the reference resizes the coordinates to (n, n)), got {tuple(code_aug.shape)}")
+    code, code_aug = _f32c(code, "code"), _f32c(code_aug, "code_aug")
+    if code_aug.device != code.device:
+        raise RuntimeError(f"depthg_amd: code lives on {code.device}, code_aug on {code_aug.device}")
+    return code, code_aug
+
+
+def _aug_alignment_workspace_bytes(lib, B, D, h, w, n):
+    need = lib.dg_augalign_workspace_bytes(B, D, h, w, n)
+    if need == 0:
+        raise ValueError(f"depthg_amd: no augmentation-alignment plan for B={B}, D={D}, code map {h}x{w}, n={n} "
+                         "(B <= 65535, n <= 255, 8 h w + 24 n^2 + 4 <= 163776: the inverse tap records are built in LDS)")
+    return need
+
+
+def aug_alignment_workspace_sections(workspace, B, n):
+    """Views of what aug_alignment_forward left in its workspace (the layout of include/depthg_corr.h: sections at multiples of 256
+    bytes): ds (B,n,n,2) the resized coordinates, norm_u (B,n,n) and norm_v (B,n,n) the norms in front of the eps clamp, s (B,n,n)."""
+    up = lambda v: (v + 255) // 256 * 256
+    off, out = 0, {}
+    for name, shape in (("ds", (B, n, n, 2)), ("norm_u", (B, n, n)), ("norm_v", (B, n, n)), ("s", (B, n, n))):
+        nbytes = 4 * B * n * n * (2 if name == "ds" else 1)
+        out[name] = workspace[off:off + nbytes].view(torch.float32).view(shape)
+        off += up(nbytes)
+    return out
+
+
+def aug_alignment_forward(code, code_aug, coord_aug):
+    """-mean <norm(sample(code, resize(coord_aug, n))), norm(code_aug)> (dg_augalign_forward; src/train_segmentation.py:400-411):
+    code (B,D,h,w), code_aug (B,D,n,n), coord_aug (B,H,W,2) on the GPU.  Returns (loss, workspace): a 0-dim fp32 device tensor and
+    what aug_alignment_backward needs."""
+    lib = _lib.load()
+    code, code_aug = _aug_alignment_maps(code, code_aug)
+    if coord_aug.dim() != 4 or coord_aug.shape[3] != 2 or coord_aug.shape[0] != code.shape[0]:
+        raise ValueError(f"depthg_amd: coord_aug must be (B, H, W, 2) with code's batch size, got {tuple(coord_aug.shape)} beside {tuple(code.shape)}")
+    coord_aug = _f32c(coord_aug, "coord_aug")
+    dev = code.device
+    if coord_aug.device != dev:
+        raise RuntimeError(f"depthg_amd: code lives on {dev}, coord_aug on {coord_aug.device}")
+    B, D, h, w = code.shape
+    n = code_aug.shape[2]
+    ws = _empty((_aug_alignment_workspace_bytes(lib, B, D, h, w, n),), torch.uint8, dev)
+    loss = _empty((), torch.float32, dev)
+    rc = lib.dg_augalign_forward(_ptr(code), _ptr(code_aug), _ptr(coord_aug), B, D, h, w, n, coord_aug.shape[1], coord_aug.shape[2], _ptr(ws),
+                                 ws.numel(), _ptr(loss), _stream(dev))
+    _lib.check(rc, "dg_augalign_forward")
+    return loss, ws
+
+
+def aug_alignment_backward(workspace, code, code_aug, grad_out, out=None):
+    """(d loss / d code (B,D,h,w), d loss / d code_aug (B,D,n,n)) of the aug_alignment_forward whose workspace this is - same code and
+    code_aug - times the 0-dim device tensor `grad_out` (dg_augalign_backward); every element of both is written.  out: optional
+    pair of result buffers."""
+    lib = _lib.load()
+    code, code_aug = _aug_alignment_maps(code, code_aug)
+    dev = code.device
+    if _on_gpu(workspace, "workspace").device != dev or workspace.dtype != torch.uint8 or not workspace.is_contiguous():
+        raise ValueError(f"depthg_amd: workspace must be the contiguous uint8 tensor of aug_alignment_forward on {dev}")
+    grad_out = _f32c(grad_out, "grad_out")
+    if grad_out.numel() != 1 or grad_out.device != dev:
+        raise ValueError(f"depthg_amd: grad_out must be one element on {dev}, got {tuple(grad_out.shape)} on {grad_out.device}")
+    if out is None:
+        out = (_empty(tuple(code.shape), torch.float32, dev), _empty(tuple(code_aug.shape), torch.float32, dev))
+    for o, like, name in ((out[0], code, "code"), (out[1], code_aug, "code_aug")):
+        if not (o.device == dev and o.dtype == torch.float32 and o.is_contiguous() and o.shape == like.shape):
+            raise ValueError(f"depthg_amd: the `out` buffer of {name} must be a contiguous float32 {tuple(like.shape)} tensor on {dev}")
+    B, D, h, w = code.shape
+    n = code_aug.shape[2]
+    _aug_alignment_workspace_bytes(lib, B, D, h, w, n)
+    rc = lib.dg_augalign_backward(_ptr(code), _ptr(code_aug), _ptr(workspace), workspace.numel(), B, D, h, w, n, _ptr(grad_out), _ptr(out[0]),
+                                  _ptr(out[1]), _stream(dev))
+    _lib.check(rc, "dg_augalign_backward")
+    return out[0], out[1]
+
+
 def fps_coords(depth, feat_hw, n_samples, return_inds=False):
     """depth (B,1,H,W) on GPU -> coords (B,S,S,2) in [-1,1) (already *2-1)."""
     lib = _lib.load()

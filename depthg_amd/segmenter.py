@@ -30,7 +30,9 @@ residual adds) through the bf16 MFMA kernel of dg_linear.hip.  On the reference'
 298-301) training_step puts the histograms of the three un-reduced cd tensors into its logs as `hist/intra_cd`, `hist/inter_cd`, `hist/neg_cd`
 (int64 counts on the device, cfg.dg_hist_bins bins, default 64) - from ContrastiveCorrelationLoss.cd_histograms(), without the tensors.
 With cfg.crf_weight > 0 the step adds the contrastive CRF term (src/train_segmentation.py:413-419) through crf_loss.ContrastiveCRFLoss.mean_loss
-- the fused HIP kernels of dg_crf_loss.hip - and logs it as `loss/crf`.
+- the fused HIP kernels of dg_crf_loss.hip - and logs it as `loss/crf`.  With cfg.aug_alignment_weight > 0 it adds the
+augmentation-alignment term (src/train_segmentation.py:400-411) on batch["img_aug"] / batch["coord_aug"] through
+aug_loss.aug_alignment_loss - a third featurizer pass and the fused HIP kernels of dg_aug.hip - and logs it as `loss/aug_alignment`.
 """
 from types import SimpleNamespace
 from typing import Dict, Optional
@@ -38,6 +40,7 @@ from typing import Dict, Optional
 import torch
 import torch.nn as nn
 
+from .aug_loss import aug_alignment_loss
 from .crf_loss import ContrastiveCRFLoss
 from .depth_decay import legacy_decay_step
 from .evaluation import predict_and_score
@@ -132,7 +135,8 @@ class UnsupervisedSegmenter(nn.Module):
         return self.net(x)[1]                                                          # :160-167
 
     def configure_optimizers(self):                                                    # :537-547
-        # as the reference: net_optim steps `self.net.parameters()` only (its decoder is out of scope here, rec_weight = 0) - the
+        # as the reference: net_optim steps `self.net.parameters()` only (its decoder - the reconstruction term, rec_weight - is the
+        # one optional loss term not built here; the CRF and augmentation-alignment terms have no parameters of their own) - the
         # LHP projection head is NOT among them, so it keeps its initial weights there and here
         main_params = list(self.net.parameters())
         if getattr(self.cfg, "dg_fused_adam", False):          # the same three, stepped by one HIP launch (optim.FusedAdamSet)
@@ -201,6 +205,11 @@ class UnsupervisedSegmenter(nn.Module):
         img, img_pos, label = batch["img"], batch["img_pos"], batch["label"]
         depth = batch["depth"] if self.use_depth else None
         depth_pos = batch["depth_pos"] if self.use_depth else None
+        if getattr(cfg, "aug_alignment_weight", 0) > 0:         # (asked before anything is launched)
+            for key in ("img_aug", "coord_aug"):
+                if key not in batch:
+                    raise KeyError(f"training_step: cfg.aug_alignment_weight = {cfg.aug_alignment_weight} needs batch[{key!r}] "
+                                   "(the dataset's augmented view and its coordinate map, src/data.py:1132-1139)")
 
         # (both featurizer passes at once where nothing that draws random numbers stands between them in the reference - the LHP
         #  module does - and the featurizer offers it)
@@ -242,6 +251,16 @@ class UnsupervisedSegmenter(nn.Module):
             loss = loss + total
         # the legacy decays sit at function-body level in the reference: they run every step, whatever correspondence_weight is
         legacy_decay_step(cfg, self.contrastive_corr_loss_fn.cfg, self.global_step)                  # :356-375 (mutates cfg)
+
+        # :400-411: the augmentation-alignment term - a third featurizer pass (in training mode: its own Dropout2d draws, as the
+        # reference's would be) and aug_loss.aug_alignment_loss, one fused HIP forward and one HIP backward whose gradient reaches the
+        # head through both maps.  (:401 unpacks two values where the training-mode featurizer returns three: the intent is element 1.)
+        # Off: no pass, no draw, no launch, and the batch may lack the two keys.
+        if getattr(cfg, "aug_alignment_weight", 0) > 0:
+            code_aug = self.net(batch["img_aug"])[1]
+            aug_alignment = aug_alignment_loss(code, code_aug, batch["coord_aug"])
+            logs["loss/aug_alignment"] = aug_alignment.detach()
+            loss = loss + cfg.aug_alignment_weight * aug_alignment
 
         # :413-419: the contrastive CRF term, one fused HIP forward (the maps are resized at the crf_samples positions only, the
         # similarity kernel is formed on the fly) and one HIP backward - ContrastiveCRFLoss.mean_loss.  Off: nothing is drawn or launched.

@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define DG_VERSION 118   /* 118: dg_corr_cd_hist and the three dg_crfloss entry points (more exports under the same number: the layouts and meanings of every earlier entry point are unchanged, and a binding that declares a new symbol refuses a library without it when it loads), dg_sampled_sumsq, dg_corr_forward_extnorm (feature maps wider than 768 channels on SAMPLED grids above 160 positions, in channel chunks); 117: DG_FEATS_UNIT, dg_normalize_split (feature maps wider than 768 channels on the dense identity grid, in chunks of the width the operand kernels hold: the loss is linear in the feature correlation); 116: dg_prof_main_span takes FOUR words (+ the workgroups' lifetimes in shader cycles and wall ticks: the clock the CUs held); 115: dg_corr_intra_folded; 114: dg_fps_coords_pair takes a workspace (dg_fps_workspace_bytes(2 B, h, w): the pooled depth maps, written by a launch over the whole chip in front of the sampler), dg_corr_materialize_shared, dg_prof_main_span (the fused correlation launch's execution span inside a replayed step), sample grids of <= 160 positions at any feature width (fused small-grid kernel); 113: dg_corr_forward_masked; 112: dg_rand_coords_state; 111: dg_head_forward_pair / dg_head_backward_pair; 110: dg_fps_coords_pair; 109: dg_knn_similarities; 108: dg_corr_desc.code_h / code_w (code maps of another resolution than the feature maps: the FeaturePyramidNet producer, src/modules.py:732-766), dg_corr_desc.flags DG_EXACT_MASKS; 107: dg_head_*, dg_cluster_lookup_*, dg_probe_ce_*; 106: dg_corr_main_kernel_name; 105: dg_corr_forward_draw; 104: dg_lhp_map_forward / dg_lhp_map_backward; 103: dg_super_perms_state; 102: DG_LINE_GRID, dg_salience_coords, dg_simple_depth_coords; 101: total weights, DG_OUT_TOTAL */
+#define DG_VERSION 118   /* 118: dg_corr_cd_hist, the three dg_crfloss and the three dg_augalign entry points (more exports under the same number: the layouts and meanings of every earlier entry point are unchanged, and a binding that declares a new symbol refuses a library without it when it loads), dg_sampled_sumsq, dg_corr_forward_extnorm (feature maps wider than 768 channels on SAMPLED grids above 160 positions, in channel chunks); 117: DG_FEATS_UNIT, dg_normalize_split (feature maps wider than 768 channels on the dense identity grid, in chunks of the width the operand kernels hold: the loss is linear in the feature correlation); 116: dg_prof_main_span takes FOUR words (+ the workgroups' lifetimes in shader cycles and wall ticks: the clock the CUs held); 115: dg_corr_intra_folded; 114: dg_fps_coords_pair takes a workspace (dg_fps_workspace_bytes(2 B, h, w): the pooled depth maps, written by a launch over the whole chip in front of the sampler), dg_corr_materialize_shared, dg_prof_main_span (the fused correlation launch's execution span inside a replayed step), sample grids of <= 160 positions at any feature width (fused small-grid kernel); 113: dg_corr_forward_masked; 112: dg_rand_coords_state; 111: dg_head_forward_pair / dg_head_backward_pair; 110: dg_fps_coords_pair; 109: dg_knn_similarities; 108: dg_corr_desc.code_h / code_w (code maps of another resolution than the feature maps: the FeaturePyramidNet producer, src/modules.py:732-766), dg_corr_desc.flags DG_EXACT_MASKS; 107: dg_head_*, dg_cluster_lookup_*, dg_probe_ce_*; 106: dg_corr_main_kernel_name; 105: dg_corr_forward_draw; 104: dg_lhp_map_forward / dg_lhp_map_backward; 103: dg_super_perms_state; 102: DG_LINE_GRID, dg_salience_coords, dg_simple_depth_coords; 101: total weights, DG_OUT_TOTAL */
 
 /* flags of dg_corr_desc.flags (names follow the cfg keys read at src/modules.py:1236-1352) */
 #define DG_POINTWISE      (1u << 0)  /* cfg.pointwise: spatial centering of fd (modules.py:1236-1239) */
@@ -621,6 +621,44 @@ int dg_crfloss_forward(const float* code, const float* img, int32_t B, int32_t D
                        float shift, void* workspace, size_t workspace_bytes, float* out_loss, dg_stream_t stream);
 int dg_crfloss_backward(const void* workspace, size_t workspace_bytes, const int32_t* coords, int32_t B, int32_t D, int32_t h,
                         int32_t w, int32_t size, int32_t n, const float* grad_out, float* grad_code, dg_stream_t stream);
+
+/*
+ * The augmentation-alignment loss term of the training step (cfg.aug_alignment_weight).  Replaces the chain of
+ * src/train_segmentation.py:400-411 behind `orig_code_aug`: the resize of the coordinate map (src/utils.py:60-61, bilinear,
+ * align_corners=False), the two permutes, sample() (src/modules.py:822-825: grid_sample, border, align_corners=True), the two norm()
+ * (src/modules.py:789-790, F.normalize(dim=1, eps=1e-10)), the einsum and the mean:
+ *      ds   = resize(coord_aug.permute(0,3,1,2), n).permute(0,2,3,1)
+ *      u    = sample(code, ds)               u[b,:,i,j] reads code at x = ds[b,j,i,0], y = ds[b,j,i,1] (both transpositions as written)
+ *      loss = -mean over (b,i,j) of s,       s = <u / max(|u|, eps), v / max(|v|, eps)>,  v = code_aug[b,:,i,j]
+ *  code      : fp32 (B,D,h,w)     code_aug : fp32 (B,D,n,n)     coord_aug : fp32 (B,H,W,2) in [-1, 1] (device data: whatever lies
+ *              outside is clamped onto the border of the code map, as grid_sample's border mode does); all sizes are free.
+ *  workspace : dg_augalign_workspace_bytes(B, D, h, w, n) bytes (0: bad or unsupported arguments), 16-byte aligned.  Sections, each
+ *              starting at the next multiple of 256 bytes; the forward writes the first five and the last, the backward the other two:
+ *              ds fp32 (B,n,n,2) | |u| fp32 (B,n^2) | |v| fp32 (B,n^2) (the norms in front of the eps clamp) | s fp32 (B,n^2) |
+ *              the blocks' fp64 partial sums | d u fp32 (B,D,n^2) | B inverse tap records of ds on the code map | ds fp64 (B,n^2,2)
+ *              by position (the forward writes it too).  The coordinate resize, the pixel positions and the tap weights are formed
+ *              in fp64 from the fp32 inputs - the coordinates' rounding is otherwise the largest error of the term - and the weights
+ *              rounded to fp32; the fp32 ds only decides which pixels list a position in the records.
+ *  out_loss  : one fp32 in device memory (fp64 sum in a fixed order: the same bits on every call).
+ * dg_augalign_backward: both gradients for the forward whose results are in `workspace` (same code, code_aug and sizes), times the
+ * upstream gradient *grad_out, read on the device.  With c = -*grad_out / (B n^2):
+ *      d v = c (u^ - s v^) / |v|,    d u = c (v^ - s u^) / |u|     where the norm is >= eps;
+ *      d v = c u^ / eps,             d u = c v^ / eps              where it is below: F.normalize divides by clamp_min(|x|, eps),
+ *                                                                  which under autograd is the constant eps there (x^ = x / eps)
+ * and d code is the adjoint of sample() applied to d u, as a gather through position-sorted inverse tap records.  grad_code fp32
+ * (B,D,h,w) and grad_code_aug fp32 (B,D,n,n) are written completely, zeros included; nothing goes to coord_aug.  No floating-point
+ * atomics: two calls give the same bits.  No host synchronisation, no allocation: both calls can be captured into a graph.
+ * Refused before any launch (DG_ERR_INVALID / DG_ERR_UNSUPPORTED): null or misaligned pointers (4 bytes; the workspace 16),
+ * non-positive sizes, B above 65535, H or W above 16384, n above 255 (the records index the n^2 positions with 16 bits) or
+ * 8 h w + 24 n^2 + 4 above 163776 (the records are built in one workgroup's LDS; 56 x 56 positions on a 56 x 56 map take 100356), a
+ * workspace that is too small (DG_ERR_WORKSPACE).  fp32 arithmetic behind the tap weights, any D >= 1.
+ */
+size_t dg_augalign_workspace_bytes(int32_t B, int32_t D, int32_t h, int32_t w, int32_t n);
+int dg_augalign_forward(const float* code, const float* code_aug, const float* coord_aug, int32_t B, int32_t D, int32_t h, int32_t w,
+                        int32_t n, int32_t H, int32_t W, void* workspace, size_t workspace_bytes, float* out_loss, dg_stream_t stream);
+int dg_augalign_backward(const float* code, const float* code_aug, void* workspace, size_t workspace_bytes, int32_t B, int32_t D,
+                         int32_t h, int32_t w, int32_t n, const float* grad_out, float* grad_code, float* grad_code_aug,
+                         dg_stream_t stream);
 
 /*
  * The optimisation step's Adams (src/train_segmentation.py:447-455: net_optim.step(), cluster_probe_optim.step(),
