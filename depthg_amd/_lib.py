@@ -105,6 +105,10 @@ SIGNATURES = {
     "dg_augalign_workspace_bytes": (_SZ, [i32] * 5),
     "dg_augalign_forward": (_I, [vp] * 3 + [i32] * 7 + [vp, _SZ, vp, vp]),
     "dg_augalign_backward": (_I, [vp, vp, vp, _SZ] + [i32] * 5 + [vp] * 4),
+    # reconstruction loss term
+    "dg_recloss_workspace_bytes": (_SZ, [i32] * 5),
+    "dg_recloss_forward": (_I, [vp] * 5 + [f32] + [i32] * 5 + [vp, _SZ, vp, vp]),
+    "dg_recloss_backward": (_I, [vp] * 5 + [f32, vp, _SZ] + [i32] * 5 + [vp] * 5),
     # optimiser
     "dg_adam_step": (_I, [ctypes.POINTER(AdamSeg), i32, ctypes.POINTER(AdamGroup), i32, i32, vp, vp]),
     # frozen ViT

@@ -367,6 +367,77 @@ extern "C" int dg_augalign_backward(const float* code, const float* code_aug, vo
     return DG_OK;
 }
 
+// ---- the reconstruction loss term (dg_rec_loss.hip)
+static int rec_check(const char* who, int32_t B, int32_t D, int32_t C, int32_t h, int32_t w) {
+    if (B < 1 || D < 1 || C < 1 || h < 1 || w < 1)
+        return fail(DG_ERR_INVALID, "%s: B=%d, D=%d, C=%d and the map %dx%d must be positive", who, B, D, C, h, w);
+    if (D > DG_REC_MAX_D) return fail(DG_ERR_UNSUPPORTED, "%s: D=%d above %d (the head's limit)", who, D, DG_REC_MAX_D);
+    if (!dg_rec_fits(B, D, C, h, w))
+        return fail(DG_ERR_UNSUPPORTED, "%s: B=%d, D=%d, C=%d, map %dx%d: a tensor of 2^31 elements or more", who, B, D, C, h, w);
+    return DG_OK;
+}
+
+static void rec_args(DgRecArgs& A, const float* code, const float* feats, const float* weight, const float* bias, const float* keep,
+                     float scale, void* workspace, int32_t B, int32_t D, int32_t C, int32_t h, int32_t w) {
+    memset(&A, 0, sizeof(A));
+    const DgRecWs ws = dg_rec_ws(B, D, C, h, w);
+    char* base = static_cast<char*>(workspace);
+    A.code = code; A.feats = feats; A.weight = weight; A.bias = bias; A.keep = keep; A.scale = scale;
+    A.ny = reinterpret_cast<float*>(base + ws.ny);
+    A.nf = reinterpret_cast<float*>(base + ws.nf);
+    A.s = reinterpret_cast<float*>(base + ws.s);
+    A.part = reinterpret_cast<double*>(base + ws.part);
+    A.wpart = reinterpret_cast<float*>(base + ws.wpart);
+    A.bpart = reinterpret_cast<float*>(base + ws.bpart);
+    A.B = B; A.D = D; A.C = C; A.P = h * w; A.tiles_per_img = dg_rec_tiles_per_img(h, w); A.splits = dg_rec_splits(B, C, h, w);
+    A.inv_n = 1.0 / ((double)B * (double)h * (double)w);
+}
+
+extern "C" size_t dg_recloss_workspace_bytes(int32_t B, int32_t D, int32_t C, int32_t h, int32_t w) {
+    if (!dg_rec_fits(B, D, C, h, w)) return 0;
+    return dg_rec_ws(B, D, C, h, w).total;
+}
+
+extern "C" int dg_recloss_forward(const float* code, const float* feats, const float* weight, const float* bias, const float* keep,
+                                  float scale, int32_t B, int32_t D, int32_t C, int32_t h, int32_t w, void* workspace,
+                                  size_t workspace_bytes, float* out_loss, dg_stream_t stream_) {
+    if (int rc = rec_check("dg_recloss_forward", B, D, C, h, w)) return rc;
+    if (!code || !feats || !weight || !bias || !workspace || !out_loss) return fail(DG_ERR_INVALID, "dg_recloss_forward: null pointer");
+    if (keep && !(scale > 0.f && !std::isinf(scale))) return fail(DG_ERR_INVALID, "dg_recloss_forward: keep scale=%g must be positive and finite", (double)scale);
+    if ((((uintptr_t)code | (uintptr_t)feats | (uintptr_t)weight | (uintptr_t)bias | (uintptr_t)keep | (uintptr_t)out_loss) & 3) ||
+        ((uintptr_t)workspace & 15))
+        return fail(DG_ERR_INVALID, "dg_recloss_forward: the maps, the decoder, keep and out_loss must be 4-byte aligned, workspace 16-byte aligned");
+    const size_t need = dg_rec_ws(B, D, C, h, w).total;
+    if (workspace_bytes < need)
+        return fail(DG_ERR_WORKSPACE, "workspace of %zu bytes, %zu needed (dg_recloss_workspace_bytes)", workspace_bytes, need);
+    DgRecArgs A;
+    rec_args(A, code, feats, weight, bias, keep, scale, workspace, B, D, C, h, w);
+    A.loss = out_loss;
+    DG_HIP(dg_launch_rec_forward(A, static_cast<hipStream_t>(stream_)));
+    return DG_OK;
+}
+
+extern "C" int dg_recloss_backward(const float* code, const float* feats, const float* weight, const float* bias, const float* keep,
+                                   float scale, void* workspace, size_t workspace_bytes, int32_t B, int32_t D, int32_t C, int32_t h,
+                                   int32_t w, const float* grad_out, float* grad_code, float* grad_weight, float* grad_bias,
+                                   dg_stream_t stream_) {
+    if (int rc = rec_check("dg_recloss_backward", B, D, C, h, w)) return rc;
+    if (!code || !feats || !weight || !bias || !workspace || !grad_out || !grad_code || !grad_weight || !grad_bias)
+        return fail(DG_ERR_INVALID, "dg_recloss_backward: null pointer");
+    if (keep && !(scale > 0.f && !std::isinf(scale))) return fail(DG_ERR_INVALID, "dg_recloss_backward: keep scale=%g must be positive and finite", (double)scale);
+    if ((((uintptr_t)code | (uintptr_t)feats | (uintptr_t)weight | (uintptr_t)bias | (uintptr_t)keep | (uintptr_t)grad_out |
+          (uintptr_t)grad_code | (uintptr_t)grad_weight | (uintptr_t)grad_bias) & 3) || ((uintptr_t)workspace & 15))
+        return fail(DG_ERR_INVALID, "dg_recloss_backward: the maps, the decoder, keep, grad_out and the gradients must be 4-byte aligned, workspace 16-byte aligned");
+    const size_t need = dg_rec_ws(B, D, C, h, w).total;
+    if (workspace_bytes < need)
+        return fail(DG_ERR_WORKSPACE, "workspace of %zu bytes, %zu needed (dg_recloss_workspace_bytes)", workspace_bytes, need);
+    DgRecArgs A;
+    rec_args(A, code, feats, weight, bias, keep, scale, workspace, B, D, C, h, w);
+    A.grad_out = grad_out; A.grad_code = grad_code; A.grad_weight = grad_weight; A.grad_bias = grad_bias;
+    DG_HIP(dg_launch_rec_backward(A, static_cast<hipStream_t>(stream_)));
+    return DG_OK;
+}
+
 // ---- the optimisation step's Adams (dg_optim.hip)
 extern "C" int dg_adam_step(const dg_adam_seg* segs, int32_t n_seg, const dg_adam_group* groups, int32_t n_groups, int32_t device_steps,
                             void* tickets, dg_stream_t stream_) {

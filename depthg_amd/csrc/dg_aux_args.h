@@ -1,4 +1,4 @@
-// The stand-alone operations (dg_sample, dg_metrics, dg_knn, dg_lhp, dg_crf_loss, dg_aug, dg_optim, dg_attn, dg_linear .hip; dg_api_aux.hip): constants and launchers.
+// The stand-alone operations (dg_sample, dg_metrics, dg_knn, dg_lhp, dg_crf_loss, dg_aug, dg_rec_loss, dg_optim, dg_attn, dg_linear .hip; dg_api_aux.hip): constants and launchers.
 #pragma once
 #include "dg_common.h"
 #include "dg_taps.h"        // dg_taps_record_bytes: the augmentation-alignment workspace
@@ -97,6 +97,55 @@ struct DgAugArgs {
 };
 hipError_t dg_launch_aug_forward(const DgAugArgs& A, hipStream_t s);        // k_aug_forward, k_aug_reduce
 hipError_t dg_launch_aug_backward(const DgAugArgs& A, hipStream_t s);       // k_aug_bwd_pos, k_aug_taps, k_aug_gather
+
+// ---- the reconstruction loss term (dg_rec_loss.hip; src/train_segmentation.py:391-398)
+#define DG_REC_MAX_D 128                     // code channels: four 32-row accumulator tiles of d code per position half (the head's own limit)
+#define DG_REC_TP 64                         // positions per tile
+#define DG_REC_CHUNK 64                      // decoder rows staged in LDS at once
+#define DG_REC_BLOCK_TARGET 480              // blocks of the d W kernel: chunks x splits, about two per CU (what the LDS admits)
+inline int dg_rec_tiles_per_img(int h, int w) { return (int)(((long long)h * w + DG_REC_TP - 1) / DG_REC_TP); }
+// position splits of the d W kernel: each writes one (C, D) partial, summed in fp64 by k_rec_combine
+inline int dg_rec_splits(int B, int C, int h, int w) {
+    const long long tiles = (long long)B * dg_rec_tiles_per_img(h, w);
+    const int chunks = (C + DG_REC_CHUNK - 1) / DG_REC_CHUNK, want = (DG_REC_BLOCK_TARGET + chunks - 1) / chunks;
+    return (int)(tiles < want ? tiles : want);
+}
+// dy chunk [64][65], W chunk [64][D up to a multiple of 8, + 4], code tile [D up to a multiple of 32][65]
+inline size_t dg_rec_lds(int D) {
+    return ((size_t)DG_REC_CHUNK * 65 + (size_t)DG_REC_CHUNK * (((D + 7) & ~7) + 4) + (size_t)((D + 31) & ~31) * 65) * 4;
+}
+// sizes the kernels index with int32: positions, tiles, either map's element count and the decoder's
+inline bool dg_rec_fits(int B, int D, int C, int h, int w) {
+    if (B < 1 || D < 1 || C < 1 || h < 1 || w < 1 || D > DG_REC_MAX_D) return false;
+    const long long P = (long long)h * w, big = C > D ? C : D;
+    return P <= 0x7fffffffll / B && (long long)B * P <= 0x7fffffffll / big && (long long)C * D + C <= 0x7fffffffll;
+}
+// The workspace (include/depthg_corr.h describes it to callers): byte offsets of its sections, each a multiple of 256.
+struct DgRecWs { size_t ny, nf, s, part, wpart, bpart, total; };
+inline DgRecWs dg_rec_ws(int B, int D, int C, int h, int w) {
+    const size_t rows = (size_t)B * h * w, S = (size_t)dg_rec_splits(B, C, h, w);
+    auto up256 = [](size_t x) { return (x + 255) / 256 * 256; };
+    DgRecWs ws;
+    ws.ny = 0;
+    ws.nf = ws.ny + up256(rows * 4);
+    ws.s = ws.nf + up256(rows * 4);
+    ws.part = ws.s + up256(rows * 4);
+    ws.wpart = ws.part + up256((size_t)B * dg_rec_tiles_per_img(h, w) * 8);     // one double per tile of k_rec_forward
+    ws.bpart = ws.wpart + up256(S * C * D * 4);
+    ws.total = ws.bpart + up256(S * C * 4);
+    return ws;
+}
+// One block for the five kernels; forward: the maps, the decoder, ny / nf / s / part, loss; backward: everything but loss.
+struct DgRecArgs {
+    const float* code; const float* feats; const float* weight; const float* bias; const float* keep;
+    float* ny; float* nf; float* s; double* part; float* wpart; float* bpart; float* loss;
+    const float* grad_out; float* grad_code; float* grad_weight; float* grad_bias;
+    double inv_n;                            // 1 / (B h w), formed on the host
+    float scale;
+    int B, D, C, P, tiles_per_img, splits;
+};
+hipError_t dg_launch_rec_forward(const DgRecArgs& A, hipStream_t s);        // k_rec_forward, k_rec_reduce
+hipError_t dg_launch_rec_backward(const DgRecArgs& A, hipStream_t s);       // k_rec_bwd_code, k_rec_bwd_w, k_rec_combine
 
 // ---- fused attention forward of the frozen ViT (dg_attn.hip; src/dino/vision_transformer.py:80-92)
 size_t dg_attn_workspace(int B, int heads, int N);           // bytes of the packed bf16 K / V images

@@ -411,6 +411,104 @@ def aug_alignment_backward(workspace, code, code_aug, grad_out, out=None):
     return out[0], out[1]
 
 
+def rec_loss_shapes(code, feats, weight, bias):
+    """The reconstruction term's shape rules, on any device: code (B,D,h,w), feats (B,C,h,w) on the same grid, the decoder's weight
+    (C,D,1,1) or (C,D) and bias (C,).  Returns (weight as (C,D), (B, D, C, h, w))."""
+    if code.dim() != 4 or feats.dim() != 4:
+        raise ValueError(f"depthg_amd: code must be (B, D, h, w) and feats (B, C, h, w), got {tuple(code.shape)} and {tuple(feats.shape)}")
+    if code.shape[0] != feats.shape[0] or code.shape[2:] != feats.shape[2:]:
+        raise ValueError(f"depthg_amd: code {tuple(code.shape)} and feats {tuple(feats.shape)} must share the batch size and the grid")
+    B, D, h, w = code.shape
+    C = feats.shape[1]
+    if tuple(weight.shape) not in ((C, D, 1, 1), (C, D)) or tuple(bias.shape) != (C,):
+        raise ValueError(f"depthg_amd: the decoder maps code's {D} channels to feats' {C}: weight must be ({C}, {D}, 1, 1) or ({C}, {D}) and "
+                         f"bias ({C},), got {tuple(weight.shape)} and {tuple(bias.shape)}")
+    return (weight[:, :, 0, 0] if weight.dim() == 4 else weight), (B, D, C, h, w)
+
+
+def _rec_loss_operands(code, feats, weight, bias, keep, scale):
+    """The reconstruction term's tensors as the library reads them (contiguous fp32 on one GPU; nothing is copied that already is)
+    and its sizes; `feats` may be a DeferredDropout, whose flags and scale then stand for keep / scale."""
+    if isinstance(feats, DeferredDropout):
+        if keep is not None:
+            raise ValueError("depthg_amd: keep flags given twice (feats is a DeferredDropout)")
+        feats, keep, scale = feats.feats, feats.keep, feats.scale
+    weight, (B, D, C, h, w) = rec_loss_shapes(code, feats, weight, bias)
+    if D > 128:
+        raise ValueError(f"depthg_amd: the reconstruction term takes code of at most 128 channels on the GPU (the head's limit), got D={D}")
+    code, feats, weight, bias = _f32c(code, "code"), _f32c(feats, "feats"), _f32c(weight, "weight"), _f32c(bias, "bias")
+    dev = code.device
+    for t, name in ((feats, "feats"), (weight, "weight"), (bias, "bias")):
+        if t.device != dev:
+            raise RuntimeError(f"depthg_amd: code lives on {dev}, {name} on {t.device}")
+    if keep is not None:
+        if tuple(keep.shape) != (B, C) or not scale > 0:
+            raise ValueError(f"depthg_amd: keep flags must be (B, C) = ({B}, {C}) with a positive scale, got {tuple(keep.shape)} and scale {scale}")
+        keep = _f32c(keep, "keep")
+        if keep.device != dev:
+            raise RuntimeError(f"depthg_amd: code lives on {dev}, keep on {keep.device}")
+    return code, feats, weight, bias, keep, float(scale), (B, D, C, h, w)
+
+
+def _rec_loss_workspace_bytes(lib, B, D, C, h, w):
+    need = lib.dg_recloss_workspace_bytes(B, D, C, h, w)
+    if need == 0:
+        raise ValueError(f"depthg_amd: no reconstruction-loss plan for B={B}, D={D}, C={C}, map {h}x{w} (D <= 128, every tensor below 2^31 elements)")
+    return need
+
+
+def rec_loss_workspace_sections(workspace, B, h, w):
+    """Views of what rec_loss_forward left in its workspace (the layout of include/depthg_corr.h: sections at multiples of 256
+    bytes): norm_y (B,h,w) and norm_f (B,h,w) the norms in front of the eps clamp, s (B,h,w)."""
+    up = lambda v: (v + 255) // 256 * 256
+    off, out, nbytes = 0, {}, 4 * B * h * w
+    for name in ("norm_y", "norm_f", "s"):
+        out[name] = workspace[off:off + nbytes].view(torch.float32).view(B, h, w)
+        off += up(nbytes)
+    return out
+
+
+def rec_loss_forward(code, feats, weight, bias, keep=None, scale=1.0):
+    """-mean <norm(decoder(code)), norm(feats)> (dg_recloss_forward; src/train_segmentation.py:391-398): code (B,D,h,w), feats
+    (B,C,h,w) - a tensor or a DeferredDropout - the decoder's weight (C,D,1,1) or (C,D) and bias (C,), on the GPU; keep / scale:
+    Dropout2d flags (B,C) still to be applied to feats.  Returns (loss, workspace): a 0-dim fp32 device tensor and what
+    rec_loss_backward needs."""
+    lib = _lib.load()
+    code, feats, weight, bias, keep, scale, (B, D, C, h, w) = _rec_loss_operands(code, feats, weight, bias, keep, scale)
+    dev = code.device
+    ws = _empty((_rec_loss_workspace_bytes(lib, B, D, C, h, w),), torch.uint8, dev)
+    loss = _empty((), torch.float32, dev)
+    rc = lib.dg_recloss_forward(_ptr(code), _ptr(feats), _ptr(weight), _ptr(bias), _ptr(keep), scale, B, D, C, h, w, _ptr(ws), ws.numel(),
+                                _ptr(loss), _stream(dev))
+    _lib.check(rc, "dg_recloss_forward")
+    return loss, ws
+
+
+def rec_loss_backward(workspace, code, feats, weight, bias, grad_out, keep=None, scale=1.0, out=None):
+    """(d loss / d code (B,D,h,w), d loss / d weight (C,D), d loss / d bias (C,)) of the rec_loss_forward whose workspace this is -
+    same tensors - times the 0-dim device tensor `grad_out` (dg_recloss_backward); every element of the three is written.  out:
+    optional triple of result buffers."""
+    lib = _lib.load()
+    code, feats, weight, bias, keep, scale, (B, D, C, h, w) = _rec_loss_operands(code, feats, weight, bias, keep, scale)
+    dev = code.device
+    need = _rec_loss_workspace_bytes(lib, B, D, C, h, w)
+    if _on_gpu(workspace, "workspace").device != dev or workspace.dtype != torch.uint8 or not workspace.is_contiguous() or workspace.numel() < need:
+        raise ValueError(f"depthg_amd: workspace must be the contiguous uint8 tensor of rec_loss_forward on {dev}")
+    grad_out = _f32c(grad_out, "grad_out")
+    if grad_out.numel() != 1 or grad_out.device != dev:
+        raise ValueError(f"depthg_amd: grad_out must be one element on {dev}, got {tuple(grad_out.shape)} on {grad_out.device}")
+    shapes = ((B, D, h, w), (C, D), (C,))
+    if out is None:
+        out = tuple(_empty(sh, torch.float32, dev) for sh in shapes)
+    for o, sh, name in zip(out, shapes, ("code", "weight", "bias")):
+        if not (o.device == dev and o.dtype == torch.float32 and o.is_contiguous() and tuple(o.shape) == sh):
+            raise ValueError(f"depthg_amd: the `out` buffer of {name} must be a contiguous float32 {sh} tensor on {dev}")
+    rc = lib.dg_recloss_backward(_ptr(code), _ptr(feats), _ptr(weight), _ptr(bias), _ptr(keep), scale, _ptr(workspace), workspace.numel(),
+                                 B, D, C, h, w, _ptr(grad_out), _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _stream(dev))
+    _lib.check(rc, "dg_recloss_backward")
+    return out[0], out[1], out[2]
+
+
 def fps_coords(depth, feat_hw, n_samples, return_inds=False):
     """depth (B,1,H,W) on GPU -> coords (B,S,S,2) in [-1,1) (already *2-1)."""
     lib = _lib.load()

@@ -33,6 +33,8 @@ With cfg.crf_weight > 0 the step adds the contrastive CRF term (src/train_segmen
 - the fused HIP kernels of dg_crf_loss.hip - and logs it as `loss/crf`.  With cfg.aug_alignment_weight > 0 it adds the
 augmentation-alignment term (src/train_segmentation.py:400-411) on batch["img_aug"] / batch["coord_aug"] through
 aug_loss.aug_alignment_loss - a third featurizer pass and the fused HIP kernels of dg_aug.hip - and logs it as `loss/aug_alignment`.
+With cfg.rec_weight > 0 the segmenter has a `decoder` (src/train_segmentation.py:115), net_optim steps it (:540-541) and the step adds
+the reconstruction term (:391-398) through rec_loss.reconstruction_loss - the fused HIP kernels of dg_rec_loss.hip - logged as `loss/rec`.
 """
 from types import SimpleNamespace
 from typing import Dict, Optional
@@ -51,6 +53,7 @@ from .loss import ContrastiveCorrelationLoss
 from .metrics import UnsupervisedMetrics
 from .optim import FusedAdam, FusedAdamSet
 from .parallel import GradBucket
+from .rec_loss import reconstruction_loss
 from .training import correspondence_total
 
 
@@ -130,15 +133,20 @@ class UnsupervisedSegmenter(nn.Module):
         self.max_cluster_miou = 0.0
         self.max_linear_accuracy = 0.0
         self.max_linear_miou = 0.0
+        # :115 - the reconstruction term's decoder.  The reference always builds it and steps it only under rec_weight (:540-541);
+        # here it exists only then, and is built LAST: with rec_weight = 0 no module, no state_dict key and no random draw is
+        # added, and with it on every other module still takes the draws it takes without it - no existing initial value moves.
+        if getattr(cfg, "rec_weight", 0) > 0:
+            self.decoder = nn.Conv2d(dim, self.net.n_feats, (1, 1))
 
     def forward(self, x):
         return self.net(x)[1]                                                          # :160-167
 
     def configure_optimizers(self):                                                    # :537-547
-        # as the reference: net_optim steps `self.net.parameters()` only (its decoder - the reconstruction term, rec_weight - is the
-        # one optional loss term not built here; the CRF and augmentation-alignment terms have no parameters of their own) - the
-        # LHP projection head is NOT among them, so it keeps its initial weights there and here
-        main_params = list(self.net.parameters())
+        # as the reference: net_optim steps `self.net.parameters()` and, when the reconstruction term is on (rec_weight > 0,
+        # :540-541), its decoder's (the CRF and augmentation-alignment terms have no parameters of their own) - the LHP projection
+        # head is NOT among them, so it keeps its initial weights there and here
+        main_params = list(self.net.parameters()) + self._decoder_parameters()
         if getattr(self.cfg, "dg_fused_adam", False):          # the same three, stepped by one HIP launch (optim.FusedAdamSet)
             return (FusedAdam([p for p in main_params if p.requires_grad], lr=self.cfg.lr),
                     FusedAdam(list(self.linear_probe.parameters()), lr=5e-3),
@@ -180,16 +188,23 @@ class UnsupervisedSegmenter(nn.Module):
             raise RuntimeError(f"training_step: `grad_sync` returned {len(handed)} gradients for {len(params)} stepped parameters")
         return handed
 
+    def _decoder_parameters(self):
+        """The reconstruction term's decoder (weight, bias) when cfg.rec_weight > 0 built one, else nothing."""
+        decoder = getattr(self, "decoder", None)
+        return list(decoder.parameters()) if decoder is not None and getattr(self.cfg, "rec_weight", 0) > 0 else []
+
     def head_parameters(self):
         """The parameters net_optim steps: cluster1 + cluster2."""
         return [p for p in self.net.parameters() if p.requires_grad]
 
     def all_reduced_parameters(self):
-        """Every parameter one of the three optimisers steps - the head (net_optim), the linear probe and the cluster probe.
+        """Every parameter one of the three optimisers steps - the head and, under cfg.rec_weight, the decoder (net_optim), the
+        linear probe and the cluster probe, in the optimisers' order.
         Under data parallelism ALL of them must be averaged over the ranks before the optimiser steps (build the GradBucket
         from this list), or the replicas' probes drift apart.  (The LHP head is stepped by no optimiser, as in the reference,
         src/train_segmentation.py:537-547, so it needs no exchange.)"""
-        return self.head_parameters() + list(self.linear_probe.parameters()) + list(self.cluster_probe.parameters())
+        return self.head_parameters() + self._decoder_parameters() + list(self.linear_probe.parameters()) + \
+            list(self.cluster_probe.parameters())
 
     def training_step(self, batch: Dict[str, torch.Tensor], batch_idx: int = 0, grad_sync=None):
         """One optimisation step (src/train_segmentation.py:169-462).  `grad_sync`: callable run between backward and the
@@ -251,6 +266,17 @@ class UnsupervisedSegmenter(nn.Module):
             loss = loss + total
         # the legacy decays sit at function-body level in the reference: they run every step, whatever correspondence_weight is
         legacy_decay_step(cfg, self.contrastive_corr_loss_fn.cfg, self.global_step)                  # :356-375 (mutates cfg)
+
+        # :391-398: the reconstruction term - the decoder's 1 x 1 convolution of code against feats, both normalised - as one fused
+        # HIP forward and one HIP backward (rec_loss.reconstruction_loss): rec_feats is never written.  feats goes in as it is: in
+        # the paired pass it may be an ops.DeferredDropout, whose mask the kernels apply.  Off: nothing is launched or logged.
+        if getattr(cfg, "rec_weight", 0) > 0:
+            if getattr(self, "decoder", None) is None:
+                raise RuntimeError(f"training_step: cfg.rec_weight = {cfg.rec_weight} but this segmenter was built without a decoder "
+                                   "(rec_weight was 0 then); set cfg.rec_weight before constructing UnsupervisedSegmenter")
+            rec = reconstruction_loss(code, feats, self.decoder.weight, self.decoder.bias)
+            logs["loss/rec"] = rec.detach()
+            loss = loss + cfg.rec_weight * rec
 
         # :400-411: the augmentation-alignment term - a third featurizer pass (in training mode: its own Dropout2d draws, as the
         # reference's would be) and aug_loss.aug_alignment_loss, one fused HIP forward and one HIP backward whose gradient reaches the

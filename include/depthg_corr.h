@@ -661,6 +661,38 @@ int dg_augalign_backward(const float* code, const float* code_aug, void* workspa
                          dg_stream_t stream);
 
 /*
+ * The reconstruction loss term of the training step (src/train_segmentation.py:391-398 under cfg.rec_weight; its decoder is the
+ * nn.Conv2d(dim, n_feats, (1, 1)) of :115, stepped by net_optim when the term is on, :540-541):
+ *      rec_feats = decoder(code)                                                 (:392)
+ *      loss = -(norm(rec_feats) * norm(feats)).sum(1).mean()                     (:393; norm = F.normalize(dim=1, eps=1e-10), src/modules.py:789-790)
+ * fused: neither rec_feats, a normalised map, their product nor a gradient of that size is written.  Per position p, with
+ * y = W c_p + bias, f = feats at p, N = B h w and the upstream gradient G:
+ *      ny = max(|y|, eps), nf = max(|f|, eps), s = <y, f> / (ny nf), loss = -(1/N) sum s
+ *      dy = a f + b y, a = -(G/N) / (ny nf), b = (G/N) s / ny^2 where |y| > eps and 0 below (what F.normalize gives under autograd)
+ *      d code_p = W^T dy, d weight = sum_p dy c_p^T, d bias = sum_p dy;  feats receives no gradient (the frozen backbone's output)
+ *  code : fp32 (B, D, h, w);  feats : fp32 (B, C, h, w);  weight : fp32 (C, D);  bias : fp32 (C);  all contiguous, 4-byte aligned
+ *  keep, scale : NULL, or the Dropout2d keep flags fp32 (B, C), 1 / 0, of feats that have not been dropped yet: the kernels read
+ *                feats[b,c] * (keep[b,c] != 0 ? scale : 0) - the bits of the dropped tensor (src/modules.py:122-137); scale > 0
+ *  B, D, C, h, w >= 1;  D <= 128;  B C h w, B D h w and C D + C below 2^31 (DG_ERR_UNSUPPORTED otherwise, before any launch)
+ *  workspace : dg_recloss_workspace_bytes(B, D, C, h, w) bytes (0 on bad arguments), 16-byte aligned.  Sections at multiples of
+ *              256 bytes, in this order: |y| fp32 (B,h,w), |f| fp32 (B,h,w) - both in front of the eps clamp - s fp32 (B,h,w), one fp64
+ *              sum of -s per tile of 64 positions, then the backward's partial sums of d weight (S, C, D) and d bias (S, C) fp32
+ *  forward  : writes out_loss (one fp32) and the first four sections
+ *  backward : same tensors and workspace as the forward; grad_out one fp32 in device memory; writes EVERY element of grad_code
+ *             (B, D, h, w), grad_weight (C, D) and grad_bias (C)
+ * y, dy and the three products are fp32 (fp32 MFMA: fp32 operands, fp32 accumulation); the forward's sums of |y|^2, |f|^2 and <y, f>
+ * over the channels run in fp64, and s is formed from them in fp64; the loss and the partial sums of d weight / d bias (fp32 per
+ * split) are combined in fp64, in launches of their own and in one fixed order.  No atomics: two calls give the same bits.  No host synchronisation.
+ */
+size_t dg_recloss_workspace_bytes(int32_t B, int32_t D, int32_t C, int32_t h, int32_t w);
+int dg_recloss_forward(const float* code, const float* feats, const float* weight, const float* bias, const float* keep, float scale,
+                       int32_t B, int32_t D, int32_t C, int32_t h, int32_t w, void* workspace, size_t workspace_bytes, float* out_loss,
+                       dg_stream_t stream);
+int dg_recloss_backward(const float* code, const float* feats, const float* weight, const float* bias, const float* keep, float scale,
+                        void* workspace, size_t workspace_bytes, int32_t B, int32_t D, int32_t C, int32_t h, int32_t w,
+                        const float* grad_out, float* grad_code, float* grad_weight, float* grad_bias, dg_stream_t stream);
+
+/*
  * The optimisation step's Adams (src/train_segmentation.py:447-455: net_optim.step(), cluster_probe_optim.step(),
  * linear_probe_optim.step(); :537-547: three torch.optim.Adam with default betas / eps, weight_decay = 0, amsgrad = False) as ONE
  * launch over a table of segments (one per tensor); fp32 throughout:
