@@ -62,10 +62,8 @@ def aug_alignment_loss(code, code_aug, coord_aug):
         raise ValueError(f"depthg_amd: code_aug must be square - the reference resizes the coordinates to (n, n) and multiplies the "
                          f"maps element by element - got {tuple(code_aug.shape)}")
     if code.is_cuda or code_aug.is_cuda or coord_aug.is_cuda:
-        for t, name in ((code, "code"), (code_aug, "code_aug"), (coord_aug, "coord_aug")):
-            ops._on_gpu(t, name)
-            if t.dtype != torch.float32:     # (the kernels read and write fp32: a cast here would hand back gradients of another dtype)
-                raise ValueError(f"depthg_amd: aug_alignment_loss wants float32 tensors on the GPU, got {name} as {t.dtype}")
+        ops._gpu_float32(((code, "code"), (code_aug, "code_aug"), (coord_aug, "coord_aug")),
+                         "aug_alignment_loss wants float32 tensors on the GPU, got {name} as {dtype}")
         return _AugAlignment.apply(code, code_aug, coord_aug)
     n = code_aug.shape[2]
     ds = F.interpolate(coord_aug.to(code.dtype).permute(0, 3, 1, 2), (n, n), mode="bilinear", align_corners=False).permute(0, 2, 3, 1)

@@ -85,10 +85,8 @@ class ContrastiveCRFLoss(nn.Module):
         if img.requires_grad and torch.is_grad_enabled():
             raise RuntimeError("depthg_amd: ContrastiveCRFLoss.mean_loss has no gradient for `img` (the guidance is the input image); "
                                "detach it")
-        ops._on_gpu(code, "code")
-        ops._on_gpu(img, "img")
-        if code.dtype != torch.float32:            # (the kernels read and write fp32: a cast here would hand back a gradient of another dtype)
-            raise ValueError(f"depthg_amd: ContrastiveCRFLoss.mean_loss wants a float32 code map, got {code.dtype}")
+        # (img takes no gradient: ops.crf_loss_forward may cast it)
+        ops._gpu_float32(((code, "code"),), "ContrastiveCRFLoss.mean_loss wants a float32 code map, got {dtype}", also_gpu=((img, "img"),))
         size = int(size)
         if coords is None:
             coords = draw_coords(size, size, self.n_samples, code.device)

@@ -1,4 +1,4 @@
-// What the units of the C ABI share (dg_api_corr.hip, dg_api_head.hip, dg_api_eval.hip, dg_api_aux.hip): error reporting and the
+// What the units of the C ABI share (dg_api_corr.hip, dg_api_head.hip, dg_api_eval.hip, dg_api_loss.hip, dg_api_aux.hip): error reporting and the
 // library's second stream.  Internal: not installed beside include/depthg_corr.h.
 #pragma once
 #include "dg_common.h"

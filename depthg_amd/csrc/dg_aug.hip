@@ -7,7 +7,7 @@
 //   k_aug_forward   one thread per position (b,i,j), lanes over neighbouring j: the four resize taps of coord_aug (ds, kept in the
 //                   workspace), the four bilinear taps of code, the D-long loop for |u|^2, |v|^2, <u,v>,
 //                   then s; |u|, |v|, s to the workspace, the block's sum of -s as one double.  u is never written.
-//   k_aug_reduce    the blocks' sums -> the loss scalar (fp64, fixed order)
+//   k_loss_reduce   the blocks' sums -> the loss scalar (fp64, fixed order; dg_loss_reduce.hip)
 //   k_aug_bwd_pos   per position again: u re-formed through its taps, d code_aug written, d u (B,D,n^2) to the workspace
 //   k_aug_taps      the sorted inverse tap records of ds, one block per image (build_taps_block, dg_taps.h), their weights from
 //                   the fp64 coordinates
@@ -18,7 +18,7 @@
 // s = 0 and hands its partner's unit vector, over eps, to its own gradient: large and finite, as in the reference.
 // Coordinates and tap weights in fp64 (see aug_resize_taps), all other arithmetic fp32, the loss sum fp64.  No atomics on floating-point data; every result is a function of the inputs alone, bit
 // for bit.  Coordinates are device data the host cannot check: aug_pos and dg_taps clamp them into the map (NaN goes to pixel 0).
-#include "dg_aux_args.h"
+#include "dg_loss_args.h"
 #include "dg_device.h"
 #include "dg_taps.h"
 
@@ -113,23 +113,8 @@ __global__ __launch_bounds__(AUG_POS_THREADS) void k_aug_forward(const DgAugArgs
         A.nu[row] = nu; A.nv[row] = nv; A.s[row] = s;
         neg = -(double)s;
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) neg += __shfl_xor(neg, o, 64);
+    neg = wave_sum(neg);
     if (threadIdx.x == 0) A.part[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = neg;
-}
-
-// loss = scale * sum of the blocks' partial sums, in fp64 and in one fixed order.  grid 1, block 256.
-__global__ __launch_bounds__(256) void k_aug_reduce(const double* part, int np, double scale, float* loss) {
-    __shared__ double sh[256];
-    double s = 0.0;
-    for (int i = threadIdx.x; i < np; i += 256) s += part[i];
-    sh[threadIdx.x] = s;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) *loss = (float)(sh[0] * scale);
 }
 
 // d code_aug (B,D,n,n), every element written, and d u (B,D,n^2) for the gather.  With c = -(upstream gradient) / (B n^2):
@@ -206,8 +191,7 @@ hipError_t dg_launch_aug_forward(const DgAugArgs& A, hipStream_t s) {
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     const double scale = 1.0 / ((double)A.B * (double)A.n * (double)A.n);
-    hipLaunchKernelGGL(k_aug_reduce, dim3(1), dim3(256), 0, s, A.part, (int)(grid.x * grid.y), scale, A.loss);
-    return hipGetLastError();
+    return dg_launch_loss_reduce(A.part, (int)(grid.x * grid.y), scale, A.loss, s);
 }
 
 hipError_t dg_launch_aug_backward(const DgAugArgs& A, hipStream_t s) {

@@ -6,12 +6,12 @@
 // one pass that forms G gives the loss and everything the backward needs.  Nothing of size (B,n,n) or size x size is written.
 //   k_crfl_sample    the two bilinear resizes AT the n sampled positions only, the norm: S (B,n,Dp), |x| (B,n), g (B,n,4)
 //   k_crfl_pair      G = K S per image with K formed on the fly, q_a = S_a . G_a / |S_a|^2, one fp64 partial sum per block
-//   k_crfl_reduce    the partial sums -> the loss scalar (fp64, fixed order)
+//   k_loss_reduce    the partial sums -> the loss scalar (fp64, fixed order; dg_loss_reduce.hip)
 //   k_crfl_backward  d code, destination-major: one block per (image, code pixel) gathers the samples whose 2 x 2 taps touch it
 // All arithmetic fp32 (expf, IEEE divisions in the reference's order of operations), the loss sum in fp64.  No atomics: every result
 // is a function of the inputs alone, bit for bit.  Coordinates are device data the host cannot check: every kernel clamps them
 // into [0, size).
-#include "dg_aux_args.h"
+#include "dg_loss_args.h"
 #include "dg_device.h"
 #include "dg_taps.h"
 
@@ -221,23 +221,8 @@ __global__ __launch_bounds__(CRFL_PAIR_THREADS) void k_crfl_pair(const DgCrflArg
             qsum += unit ? q * (2.0 / sqrt(ss) - 1.0) + (double)kaa : q + (double)kaa * ss;
         }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) qsum += __shfl_xor(qsum, o, 64);
+    qsum = wave_sum(qsum);
     if (lane == 0) A.part[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = qsum;
-}
-
-// loss = scale * sum of the blocks' partial sums, in fp64 and in one fixed order.  grid 1, block 256.
-__global__ __launch_bounds__(256) void k_crfl_reduce(const double* part, int np, double scale, float* loss) {
-    __shared__ double sh[256];
-    double s = 0.0;
-    for (int i = threadIdx.x; i < np; i += 256) s += part[i];
-    sh[threadIdx.x] = s;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) *loss = (float)(sh[0] * scale);
 }
 
 // d code (B,D,h,w), every element written.  One block per (image, code pixel): wave 0 walks the n samples - the tap indices and
@@ -326,8 +311,7 @@ hipError_t dg_launch_crfl_forward(const DgCrflArgs& A, hipStream_t s) {
     else e = crfl_launch_pair<32, 1>(A, &blocks, s);
     if (e != hipSuccess) return e;
     const double scale = -1.0 / ((double)A.B * (double)A.n * (double)A.n);
-    hipLaunchKernelGGL(k_crfl_reduce, dim3(1), dim3(256), 0, s, A.part, blocks, scale, A.loss);
-    return hipGetLastError();
+    return dg_launch_loss_reduce(A.part, blocks, scale, A.loss, s);
 }
 
 hipError_t dg_launch_crfl_backward(const DgCrflArgs& A, hipStream_t s) {

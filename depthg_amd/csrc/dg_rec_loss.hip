@@ -17,7 +17,7 @@
 //                   pairwise; a lane then holds 16 channels of one position: |y|^2, |f|^2, <y,f> over the channels in fp64, the
 //                   two half waves and the two channel halves combined in one order; |y|, |f|, s to the workspace, the tile's sum
 //                   of -s as one double
-//   k_rec_reduce    the tiles' sums -> the loss (fp64, fixed order)
+//   k_loss_reduce   the tiles' sums -> the loss (fp64, fixed order; dg_loss_reduce.hip)
 //   k_rec_bwd_code  per tile again: y and dy of a chunk -> LDS, then W^T dy of the chunk is added to the wave's accumulator tiles
 //                   (32 rows of d code x 32 positions each) which live through all chunks; every element of d code written
 //   k_rec_bwd_w     grid (channel chunk, split): the chunk of W staged once, the block walks the tiles split, split + S, ...: dy of
@@ -27,7 +27,7 @@
 // y, dy and the three products are fp32; the forward's three sums over the channels run in fp64 (with fp32 sums a 1024-channel
 // decoder measured 8 x the float32 torch chain's loss error); no atomics; every result is a function of the inputs alone, bit for bit.
 // Dropout2d keep flags (ops.DeferredDropout): f = feats * (keep[b,c] ? scale : 0), the bits of the materialised tensor.
-#include "dg_aux_args.h"
+#include "dg_loss_args.h"
 #include "dg_device.h"
 
 #define RC_THREADS 256
@@ -183,23 +183,8 @@ __global__ __launch_bounds__(RC_THREADS) void k_rec_forward(const DgRecArgs A) {
         A.ny[row] = (float)ny; A.nf[row] = (float)nf; A.s[row] = (float)s;
         neg = -s;
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) neg += __shfl_xor(neg, o, 64);
+    neg = wave_sum(neg);
     if (lane == 0) A.part[blockIdx.x] = neg;
-}
-
-// loss = scale * sum of the tiles' sums, in fp64 and in one fixed order.  grid 1, block 256.
-__global__ __launch_bounds__(256) void k_rec_reduce(const double* part, int np, double scale, float* loss) {
-    __shared__ double sh[256];
-    double s = 0.0;
-    for (int i = threadIdx.x; i < np; i += 256) s += part[i];
-    sh[threadIdx.x] = s;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) *loss = (float)(sh[0] * scale);
 }
 
 // dy of the wave's 32 channels x 32 positions of the staged chunk -> dyl[row * RC_LS + position]; 0 for a channel past C
@@ -344,8 +329,7 @@ hipError_t dg_launch_rec_forward(const DgRecArgs& A, hipStream_t s) {
     hipLaunchKernelGGL(k_rec_forward, dim3(tiles), dim3(RC_THREADS), lds, s, A);
     e = hipGetLastError();
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_rec_reduce, dim3(1), dim3(256), 0, s, A.part, tiles, A.inv_n, A.loss);
-    return hipGetLastError();
+    return dg_launch_loss_reduce(A.part, tiles, A.inv_n, A.loss, s);
 }
 
 hipError_t dg_launch_rec_backward(const DgRecArgs& A, hipStream_t s) {

@@ -2,6 +2,7 @@
 torch is used for device memory and streams only."""
 import collections
 import ctypes
+import math
 import os
 
 import torch
@@ -259,6 +260,60 @@ def corr_cd_hist(desc, workspace, first, count, perms=None, bins=64, range=(-1.0
     return out
 
 
+# ---- what the three auxiliary loss terms share (dg_api_loss.hip)
+def _gpu_float32(tensors, text, also_gpu=()):
+    """The fused routes' gate: every (tensor, name) of both lists on the GPU, those of `tensors` float32 as well (the kernels read
+    and write fp32: a cast here would hand back gradients of another dtype).  text: the complaint, with {name} and {dtype}."""
+    for t, name in (*tensors, *also_gpu):
+        _on_gpu(t, name)
+    for t, name in tensors:
+        if t.dtype != torch.float32:
+            raise ValueError("depthg_amd: " + text.format(name=name, dtype=t.dtype))
+
+
+def _plan_bytes(need, term, dims, limits):
+    """A sizer's answer, or the refusal it stands for: 0 bytes means the library has no plan for these sizes."""
+    if need == 0:
+        raise ValueError(f"depthg_amd: no {term} plan for {dims} ({limits})")
+    return need
+
+
+def _workspace_views(workspace, specs):
+    """Views of a workspace's leading sections, specs = (name, shape, dtype) in the layout's order (include/depthg_corr.h: every
+    section starts at a multiple of 256 bytes)."""
+    off, out = 0, {}
+    for name, shape, dtype in specs:
+        nbytes = math.prod(shape) * dtype.itemsize
+        out[name] = workspace[off:off + nbytes].view(dtype).view(shape)
+        off += (nbytes + 255) // 256 * 256
+    return out
+
+
+def _forward_workspace(workspace, maker, dev, need):
+    """A backward's `workspace`: the contiguous uint8 tensor `maker` returned on `dev`, of at least `need` bytes."""
+    if _on_gpu(workspace, "workspace").device != dev or workspace.dtype != torch.uint8 or not workspace.is_contiguous() or workspace.numel() < need:
+        raise ValueError(f"depthg_amd: workspace must be the contiguous uint8 tensor of {maker} on {dev}")
+    return workspace
+
+
+def _grad_out_scalar(grad_out, dev):
+    """The upstream gradient of a scalar loss as the library reads it: one fp32 element on `dev`."""
+    grad_out = _f32c(grad_out, "grad_out")
+    if grad_out.numel() != 1 or grad_out.device != dev:
+        raise ValueError(f"depthg_amd: grad_out must be one element on {dev}, got {tuple(grad_out.shape)} on {grad_out.device}")
+    return grad_out
+
+
+def _out_buffers(out, shapes, names, dev):
+    """A backward's result buffers: fresh ones, or the caller's `out`, each a contiguous float32 tensor of its shape on `dev`."""
+    if out is None:
+        return tuple(_empty(sh, torch.float32, dev) for sh in shapes)
+    for o, sh, name in zip(out, shapes, names):
+        if not (o.device == dev and o.dtype == torch.float32 and o.is_contiguous() and tuple(o.shape) == tuple(sh)):
+            raise ValueError(f"depthg_amd: the `out` buffer of {name} must be a contiguous float32 {tuple(sh)} tensor on {dev}")
+    return tuple(out)
+
+
 def _crf_loss_coords(coords, n, dev):
     if coords.dim() != 2 or coords.shape[0] != 2 or coords.shape[1] < 1:
         raise ValueError(f"depthg_amd: coords must be (2, n) - the y row, then the x row - got {tuple(coords.shape)}")
@@ -274,14 +329,8 @@ def crf_loss_workspace_sections(workspace, B, D, n):
     bytes): S (B,n,Dp) the normalised resized code vectors (Dp = D rounded up to 4, zero columns above D), G (B,n,Dp) = K S without
     the rows' own terms, g (B,n,4) the resized image colours (a zero fourth column), norm (B,n), q (B,n) fp64 = S_a . G_a / |S_a|^2."""
     Dp = (D + 3) // 4 * 4
-    up = lambda v: (v + 255) // 256 * 256
-    rows, off, out = B * n, 0, {}
-    for name, width, dtype in (("S", Dp, torch.float32), ("G", Dp, torch.float32), ("g", 4, torch.float32), ("norm", 1, torch.float32),
-                               ("q", 1, torch.float64)):
-        nbytes = rows * width * dtype.itemsize
-        out[name] = workspace[off:off + nbytes].view(dtype).view((B, n, width) if width > 1 else (B, n))
-        off += up(nbytes)
-    return out
+    return _workspace_views(workspace, (("S", (B, n, Dp), torch.float32), ("G", (B, n, Dp), torch.float32), ("g", (B, n, 4), torch.float32),
+                                        ("norm", (B, n), torch.float32), ("q", (B, n), torch.float64)))
 
 
 def crf_loss_forward(code, img, coords, size, alpha, beta, gamma, w1, w2, shift):
@@ -298,9 +347,7 @@ def crf_loss_forward(code, img, coords, size, alpha, beta, gamma, w1, w2, shift)
     coords = _crf_loss_coords(coords, None, dev)
     B, D, h, w = code.shape
     n = coords.shape[1]
-    need = lib.dg_crfloss_workspace_bytes(B, D, n)
-    if need == 0:
-        raise ValueError(f"depthg_amd: no CRF-loss plan for B={B}, D={D}, n={n} (B <= 65535, D <= 128, n <= 4096)")
+    need = _plan_bytes(lib.dg_crfloss_workspace_bytes(B, D, n), "CRF-loss", f"B={B}, D={D}, n={n}", "B <= 65535, D <= 128, n <= 4096")
     ws = _empty((need,), torch.uint8, dev)
     loss = _empty((), torch.float32, dev)
     rc = lib.dg_crfloss_forward(_ptr(code), _ptr(img), B, D, h, w, img.shape[2], img.shape[3], int(size), _ptr(coords), n, float(alpha),
@@ -317,13 +364,10 @@ def crf_loss_backward(workspace, coords, shape_code, size, grad_out, out=None):
     B, D, h, w = (int(v) for v in shape_code)
     dev = _on_gpu(workspace, "workspace").device
     coords = _crf_loss_coords(coords, None, dev)
-    grad_out = _f32c(grad_out, "grad_out")
-    if grad_out.numel() != 1 or grad_out.device != dev:
-        raise ValueError(f"depthg_amd: grad_out must be one element on {dev}, got {tuple(grad_out.shape)} on {grad_out.device}")
-    if out is None:
-        out = _empty((B, D, h, w), torch.float32, dev)
-    elif not (out.device == dev and out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (B, D, h, w)):
-        raise ValueError(f"depthg_amd: `out` must be a contiguous float32 {(B, D, h, w)} tensor on {dev}")
+    # (sizes without a plan - 0 bytes - are the library's to refuse, by name)
+    _forward_workspace(workspace, "crf_loss_forward", dev, lib.dg_crfloss_workspace_bytes(B, D, coords.shape[1]))
+    grad_out = _grad_out_scalar(grad_out, dev)
+    out, = _out_buffers(None if out is None else (out,), ((B, D, h, w),), ("code",), dev)
     rc = lib.dg_crfloss_backward(_ptr(workspace), workspace.numel(), _ptr(coords), B, D, h, w, int(size), coords.shape[1], _ptr(grad_out),
                                  _ptr(out), _stream(dev))
     _lib.check(rc, "dg_crfloss_backward")
@@ -344,23 +388,14 @@ def _aug_alignment_maps(code, code_aug):
 
 
 def _aug_alignment_workspace_bytes(lib, B, D, h, w, n):
-    need = lib.dg_augalign_workspace_bytes(B, D, h, w, n)
-    if need == 0:
-        raise ValueError(f"depthg_amd: no augmentation-alignment plan for B={B}, D={D}, code map {h}x{w}, n={n} "
-                         "(B <= 65535, n <= 255, 8 h w + 24 n^2 + 4 <= 163776: the inverse tap records are built in LDS)")
-    return need
+    return _plan_bytes(lib.dg_augalign_workspace_bytes(B, D, h, w, n), "augmentation-alignment", f"B={B}, D={D}, code map {h}x{w}, n={n}",
+                       "B <= 65535, n <= 255, 8 h w + 24 n^2 + 4 <= 163776: the inverse tap records are built in LDS")
 
 
 def aug_alignment_workspace_sections(workspace, B, n):
     """Views of what aug_alignment_forward left in its workspace (the layout of include/depthg_corr.h: sections at multiples of 256
     bytes): ds (B,n,n,2) the resized coordinates, norm_u (B,n,n) and norm_v (B,n,n) the norms in front of the eps clamp, s (B,n,n)."""
-    up = lambda v: (v + 255) // 256 * 256
-    off, out = 0, {}
-    for name, shape in (("ds", (B, n, n, 2)), ("norm_u", (B, n, n)), ("norm_v", (B, n, n)), ("s", (B, n, n))):
-        nbytes = 4 * B * n * n * (2 if name == "ds" else 1)
-        out[name] = workspace[off:off + nbytes].view(torch.float32).view(shape)
-        off += up(nbytes)
-    return out
+    return _workspace_views(workspace, (("ds", (B, n, n, 2), torch.float32),) + tuple((name, (B, n, n), torch.float32) for name in ("norm_u", "norm_v", "s")))
 
 
 def aug_alignment_forward(code, code_aug, coord_aug):
@@ -392,19 +427,11 @@ def aug_alignment_backward(workspace, code, code_aug, grad_out, out=None):
     lib = _lib.load()
     code, code_aug = _aug_alignment_maps(code, code_aug)
     dev = code.device
-    if _on_gpu(workspace, "workspace").device != dev or workspace.dtype != torch.uint8 or not workspace.is_contiguous():
-        raise ValueError(f"depthg_amd: workspace must be the contiguous uint8 tensor of aug_alignment_forward on {dev}")
-    grad_out = _f32c(grad_out, "grad_out")
-    if grad_out.numel() != 1 or grad_out.device != dev:
-        raise ValueError(f"depthg_amd: grad_out must be one element on {dev}, got {tuple(grad_out.shape)} on {grad_out.device}")
-    if out is None:
-        out = (_empty(tuple(code.shape), torch.float32, dev), _empty(tuple(code_aug.shape), torch.float32, dev))
-    for o, like, name in ((out[0], code, "code"), (out[1], code_aug, "code_aug")):
-        if not (o.device == dev and o.dtype == torch.float32 and o.is_contiguous() and o.shape == like.shape):
-            raise ValueError(f"depthg_amd: the `out` buffer of {name} must be a contiguous float32 {tuple(like.shape)} tensor on {dev}")
     B, D, h, w = code.shape
     n = code_aug.shape[2]
-    _aug_alignment_workspace_bytes(lib, B, D, h, w, n)
+    _forward_workspace(workspace, "aug_alignment_forward", dev, _aug_alignment_workspace_bytes(lib, B, D, h, w, n))
+    grad_out = _grad_out_scalar(grad_out, dev)
+    out = _out_buffers(out, (code.shape, code_aug.shape), ("code", "code_aug"), dev)
     rc = lib.dg_augalign_backward(_ptr(code), _ptr(code_aug), _ptr(workspace), workspace.numel(), B, D, h, w, n, _ptr(grad_out), _ptr(out[0]),
                                   _ptr(out[1]), _stream(dev))
     _lib.check(rc, "dg_augalign_backward")
@@ -451,21 +478,14 @@ def _rec_loss_operands(code, feats, weight, bias, keep, scale):
 
 
 def _rec_loss_workspace_bytes(lib, B, D, C, h, w):
-    need = lib.dg_recloss_workspace_bytes(B, D, C, h, w)
-    if need == 0:
-        raise ValueError(f"depthg_amd: no reconstruction-loss plan for B={B}, D={D}, C={C}, map {h}x{w} (D <= 128, every tensor below 2^31 elements)")
-    return need
+    return _plan_bytes(lib.dg_recloss_workspace_bytes(B, D, C, h, w), "reconstruction-loss", f"B={B}, D={D}, C={C}, map {h}x{w}",
+                       "D <= 128, every tensor below 2^31 elements")
 
 
 def rec_loss_workspace_sections(workspace, B, h, w):
     """Views of what rec_loss_forward left in its workspace (the layout of include/depthg_corr.h: sections at multiples of 256
     bytes): norm_y (B,h,w) and norm_f (B,h,w) the norms in front of the eps clamp, s (B,h,w)."""
-    up = lambda v: (v + 255) // 256 * 256
-    off, out, nbytes = 0, {}, 4 * B * h * w
-    for name in ("norm_y", "norm_f", "s"):
-        out[name] = workspace[off:off + nbytes].view(torch.float32).view(B, h, w)
-        off += up(nbytes)
-    return out
+    return _workspace_views(workspace, tuple((name, (B, h, w), torch.float32) for name in ("norm_y", "norm_f", "s")))
 
 
 def rec_loss_forward(code, feats, weight, bias, keep=None, scale=1.0):
@@ -491,18 +511,9 @@ def rec_loss_backward(workspace, code, feats, weight, bias, grad_out, keep=None,
     lib = _lib.load()
     code, feats, weight, bias, keep, scale, (B, D, C, h, w) = _rec_loss_operands(code, feats, weight, bias, keep, scale)
     dev = code.device
-    need = _rec_loss_workspace_bytes(lib, B, D, C, h, w)
-    if _on_gpu(workspace, "workspace").device != dev or workspace.dtype != torch.uint8 or not workspace.is_contiguous() or workspace.numel() < need:
-        raise ValueError(f"depthg_amd: workspace must be the contiguous uint8 tensor of rec_loss_forward on {dev}")
-    grad_out = _f32c(grad_out, "grad_out")
-    if grad_out.numel() != 1 or grad_out.device != dev:
-        raise ValueError(f"depthg_amd: grad_out must be one element on {dev}, got {tuple(grad_out.shape)} on {grad_out.device}")
-    shapes = ((B, D, h, w), (C, D), (C,))
-    if out is None:
-        out = tuple(_empty(sh, torch.float32, dev) for sh in shapes)
-    for o, sh, name in zip(out, shapes, ("code", "weight", "bias")):
-        if not (o.device == dev and o.dtype == torch.float32 and o.is_contiguous() and tuple(o.shape) == sh):
-            raise ValueError(f"depthg_amd: the `out` buffer of {name} must be a contiguous float32 {sh} tensor on {dev}")
+    _forward_workspace(workspace, "rec_loss_forward", dev, _rec_loss_workspace_bytes(lib, B, D, C, h, w))
+    grad_out = _grad_out_scalar(grad_out, dev)
+    out = _out_buffers(out, ((B, D, h, w), (C, D), (C,)), ("code", "weight", "bias"), dev)
     rc = lib.dg_recloss_backward(_ptr(code), _ptr(feats), _ptr(weight), _ptr(bias), _ptr(keep), scale, _ptr(workspace), workspace.numel(),
                                  B, D, C, h, w, _ptr(grad_out), _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _stream(dev))
     _lib.check(rc, "dg_recloss_backward")

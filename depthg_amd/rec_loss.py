@@ -47,10 +47,7 @@ def reconstruction_loss(code, feats, weight, bias):
     weight2d, (_, D, C, _, _) = ops.rec_loss_shapes(code, maps, weight, bias)
     tensors = ((code, "code"), (maps, "feats"), (weight, "weight"), (bias, "bias"))
     if any(t.is_cuda for t, _ in tensors):
-        for t, name in tensors:
-            ops._on_gpu(t, name)
-            if t.dtype != torch.float32:     # (the kernels read and write fp32: a cast here would hand back gradients of another dtype)
-                raise ValueError(f"depthg_amd: reconstruction_loss wants float32 tensors on the GPU, got {name} as {t.dtype}")
+        ops._gpu_float32(tensors, "reconstruction_loss wants float32 tensors on the GPU, got {name} as {dtype}")
         keep, scale = (feats.keep, feats.scale) if deferred else (None, 1.0)
         return _Reconstruction.apply(code, weight, bias, maps, keep, scale)      # (D > 128 is refused there, before any launch)
     if deferred:

@@ -4,7 +4,7 @@ at the reference's shape - B = 32, D = 70, 28 x 28 code and code_aug, a 224 x 22
 per form into profiles/aug_alignment_time.jsonl:
 
     torch    resize, permutes, grid_sample, two F.normalize, einsum, mean, autograd (float32)
-    fused    aug_loss.aug_alignment_loss: k_aug_forward, k_aug_reduce forward; k_aug_bwd_pos, k_aug_taps, k_aug_gather backward
+    fused    aug_loss.aug_alignment_loss: k_aug_forward, k_loss_reduce forward; k_aug_bwd_pos, k_aug_taps, k_aug_gather backward
 
 Host clock around `--steps` calls ending in a device synchronise, after warm-up; the two forms alternate in one process and each is
 repeated `--repeats` times: median, minimum and maximum of the repeats are on the line (microseconds per call), and whether the two

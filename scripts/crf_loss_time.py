@@ -4,7 +4,7 @@ reference's shape - B = 32, D = 70, 224 x 224 images, 28 x 28 code, resized to 5
 line per form into profiles/crf_loss_time.jsonl:
 
     torch       resize, norm, ContrastiveCRFLoss.forward (the (B,n,n) tensor), .mean(), autograd
-    mean_loss   ContrastiveCRFLoss.mean_loss: k_crfl_sample, k_crfl_pair, k_crfl_reduce forward, k_crfl_backward
+    mean_loss   ContrastiveCRFLoss.mean_loss: k_crfl_sample, k_crfl_pair, k_loss_reduce forward, k_crfl_backward
 
 Host clock around `--steps` calls ending in a device synchronise, after warm-up; the two forms alternate in one process and each is
 repeated `--repeats` times: median, minimum and maximum of the repeats are on the line (microseconds per call), and whether the two

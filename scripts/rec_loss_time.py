@@ -3,7 +3,7 @@
 at the training shape - B = 32, D = 70, C = 384, 28 x 28 - one JSON line per form into profiles/rec_loss_time.jsonl:
 
     torch    conv2d, two F.normalize, product, sum, mean, autograd (float32): what a user had without the fused route
-    fused    rec_loss.reconstruction_loss: k_rec_forward, k_rec_reduce forward; k_rec_bwd_code, k_rec_bwd_w, k_rec_combine backward
+    fused    rec_loss.reconstruction_loss: k_rec_forward, k_loss_reduce forward; k_rec_bwd_code, k_rec_bwd_w, k_rec_combine backward
 
 Host clock around `--steps` calls ending in a device synchronise, after warm-up; the two forms alternate in one process and each is
 repeated `--repeats` times: median, minimum and maximum of the repeats are on the line (microseconds per call), and whether the two

@@ -23,6 +23,7 @@ SHAPES = {
     "wide": (1, 27, 1024, (4, 4)),        # many channel chunks; dim = n_classes
     "tall": (3, 128, 64, (9, 9)),         # the D limit
     "many": (2, 16, 32, (40, 40)),        # several position blocks per image, more than one partial in every reduction
+    "wraps": (5, 3, 5, (58, 58)),         # 5 x 53 = 265 tiles: more partials than k_loss_reduce has threads (sorts last: inputs() seeds by position)
 }
 KINDS = ("random", "scaled", "dropped", "aligned")
 CASES = [(shape, "random") for shape in SHAPES] + [("ragged", "scaled"), ("head", "scaled"), ("ragged", "dropped"), ("head", "dropped"),

@@ -56,7 +56,7 @@ def dev():
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("shape,kind", R.CASES)
+@pytest.mark.parametrize("shape,kind", R.CASES + [R.WRAPS_CASE])
 def test_loss_and_gradients_within_the_yardsticks_margin(shape, kind, dev):
     m = measure(shape, kind, dev)
     print(f"{shape}/{kind}: loss {m['loss']:.9e} | loss err kernel {m['loss_err_kernel']:.3e} yardstick {m['loss_err_yard']:.3e} | d code "

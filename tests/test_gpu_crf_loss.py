@@ -40,6 +40,13 @@ SHAPES = {
 }
 CASES = [(shape, sset) for shape in SHAPES for sset in SETS]
 B = 2
+# More partial sums than the 256 threads of k_loss_reduce, so that its strided loop runs twice.  k_crfl_pair leaves one partial per
+# image and 64 R samples, and R = 1 only above 72 channels (with D = 3 a block takes 128 samples and the same n leaves 135 partials;
+# D = 3 also lets interpolated code vectors fall below the 0.1 the cases keep): 5 images x ceil(3400 / 64) = 270.
+# (The name sorts behind the others: inputs() seeds by the sorted position.)
+SHAPES["wraps"] = (73, (8, 8), (16, 16), 64, 3400, "random")
+BATCH = {"wraps": 5}                                          # images, where not B
+CASES += [("wraps", "dense")]
 
 
 def make_coords(kind, size, n, gen):
@@ -58,8 +65,9 @@ def inputs(shape):
     """(img, code, coords) on the CPU: a normalised-RGB-like image, a code map whose interpolated vectors keep a norm >= 0.1."""
     D, (h, w), (H, W), size, n, kind = SHAPES[shape]
     gen = torch.Generator().manual_seed(sorted(SHAPES).index(shape) + 100)
-    img = (torch.randn(B, 3, H, W, generator=gen) * 1.1).clamp(-2.1, 2.6)
-    code = torch.randn(B, D, h, w, generator=gen) + 0.6
+    Bn = BATCH.get(shape, B)
+    img = (torch.randn(Bn, 3, H, W, generator=gen) * 1.1).clamp(-2.1, 2.6)
+    code = torch.randn(Bn, D, h, w, generator=gen) + 0.6
     return img, code, make_coords(kind, size, n, gen)
 
 
