@@ -26,7 +26,8 @@ Public surface (mirrors the reference's Python operator surface for this path):
                                  its attention optionally through the fused HIP kernel k_attn_fwd (cfg.dg_fused_attention)
                                  and its blocks' linear layers, LayerNorms, GELU and residual adds through the bf16 MFMA kernel
                                  k_lin_fwd (cfg.dg_fused_linear)
-    featurizer / DinoFeaturizer  src/modules.py:19-137: frozen ViT + the fused projection head (cfg.dg_dino_backbone in the segmenter)
+    featurizer / DinoFeaturizer  src/modules.py:19-137: frozen ViT + the fused projection head (cfg.dg_dino_backbone in the segmenter);
+                                 DinoFeaturizerWithDepth (:490-631, cfg.arch "dino_depth"): depth-guided features in front of the head
     ops                          thin ctypes binding of the C ABI in include/depthg_corr.h
 """
 from .loss import ContrastiveCorrelationLoss  # noqa: F401
@@ -49,9 +50,9 @@ from . import optim  # noqa: F401
 from .optim import FusedAdam, FusedAdamSet  # noqa: F401
 from . import vit  # noqa: F401
 from . import featurizer  # noqa: F401
-from .featurizer import DinoFeaturizer  # noqa: F401
+from .featurizer import DinoFeaturizer, DinoFeaturizerWithDepth  # noqa: F401
 from . import segmenter  # noqa: F401
 
 __all__ = ["ContrastiveCorrelationLoss", "ContrastiveCRFLoss", "crf_loss", "aug_loss", "aug_alignment_loss", "crop_flip_coords", "rec_loss", "reconstruction_loss", "depth_decay", "training", "metrics", "evaluation", "predict_and_score", "crf", "dense_crf",
            "batched_crf", "knn", "lhp", "optim", "FusedAdam", "FusedAdamSet", "segmenter", "vit", "featurizer",
-           "DinoFeaturizer"]
+           "DinoFeaturizer", "DinoFeaturizerWithDepth"]

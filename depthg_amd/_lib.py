@@ -85,6 +85,9 @@ SIGNATURES = {
     "dg_head_backward": (_I, [i32] * 4 + [vp] * 3 + [f32] + [vp] * 10 + [_SZ, vp]),
     "dg_head_forward_pair": (_I, [i32] * 4 + [vp] * 11 + [f32] + [vp] * 7),
     "dg_head_backward_pair": (_I, [i32] * 4 + [vp] * 4 + [f32] + [vp] * 11 + [_SZ, vp]),
+    "dg_head_input_workspace_bytes": (_SZ, [i32] * 2),
+    "dg_head_backward_input": (_I, [i32] * 4 + [vp] * 4 + [f32] + [vp] * 3 + [_SZ, vp, vp, _SZ, vp]),
+    "dg_head_backward_input_pair": (_I, [i32] * 4 + [vp] * 4 + [f32] + [vp] * 4 + [_SZ, vp, vp, vp, _SZ, vp]),
     "dg_head_plan_describe": (_I, [i32] * 4 + [vp]),
     "dg_cluster_lookup_forward": (_I, [vp, vp, f32] + [i32] * 4 + [vp] * 6),
     "dg_cluster_lookup_backward": (_I, [vp, vp, vp, f32, vp] + [i32] * 4 + [vp] * 4),

@@ -171,3 +171,57 @@ extern "C" int dg_head_backward_pair(int32_t B, int32_t C, int32_t D, int32_t P,
     return head_backward_impl(2 * B, B, C, D, P, feat, feat_pos, keep1, keep2, keep_scale, hidden, wscratch, grad_code, grad_code_pos, grad_w1,
                               grad_b1, grad_w2a, grad_b2a, grad_w2b, grad_b2b, workspace, workspace_bytes, stream_);
 }
+
+// ---- d image_feat (opt-in): behind dg_head_backward* on the same workspace and stream
+extern "C" size_t dg_head_input_workspace_bytes(int32_t C, int32_t D) {
+    if (head_check(1, C, D, 1) != DG_OK) return 0;
+    return DgHeadDxLayout(C, D, true).elems * 2;
+}
+
+static int head_backward_input_impl(int32_t B, int32_t Bs, int32_t C, int32_t D, int32_t P, const float* w1, const float* w2a, const float* keep1,
+                                    const float* keep2, float keep_scale, const void* hidden, const float* grad_code, const float* grad_code2,
+                                    const void* workspace, size_t workspace_bytes, float* grad_feat, float* grad_feat2,
+                                    void* input_workspace, size_t input_workspace_bytes, dg_stream_t stream_) {
+    if (int rc = head_check(B, C, D, P)) return rc;
+    if (!w1 || !grad_code || !input_workspace) return fail(DG_ERR_INVALID, "null pointer");
+    if (Bs < B ? (!grad_code2 || (!grad_feat && !grad_feat2)) : !grad_feat) return fail(DG_ERR_INVALID, "null pointer (grad_code of both passes, grad_feat of one at least)");
+    const bool nonlinear = w2a != nullptr;
+    if (nonlinear && (!hidden || !workspace)) return fail(DG_ERR_INVALID, "cluster2's half needs `hidden` and the workspace dg_head_backward left d hidden in");
+    const DgHeadPlan h = dg_head_plan(B, C, D, P);        // (the plan dg_head_backward followed: where d hidden is and how it is laid out)
+    if (nonlinear && workspace_bytes < h.total) return fail(DG_ERR_WORKSPACE, "workspace %zu < required %zu bytes", workspace_bytes, h.total);
+    const DgHeadDxLayout L(C, D, nonlinear);
+    if (input_workspace_bytes < L.elems * 2) return fail(DG_ERR_WORKSPACE, "input workspace %zu < required %zu bytes", input_workspace_bytes, L.elems * 2);
+    hipStream_t s = static_cast<hipStream_t>(stream_);
+    DG_HIP(dg_launch_head_dx_prep(w1, w2a, input_workspace, C, D, s));
+    DgHeadDxArgs a;
+    memset(&a, 0, sizeof(a));
+    a.gcode = grad_code;
+    a.dh = nonlinear ? reinterpret_cast<const __bf16*>(static_cast<const char*>(workspace) + h.dh) : nullptr;
+    a.wT = static_cast<const __bf16*>(input_workspace);
+    a.keep1 = keep1; a.keep2 = nonlinear ? keep2 : nullptr; a.scale = keep_scale;
+    a.dx = grad_feat; a.dx2 = grad_feat2;
+    a.B = B; a.C = C; a.D = D; a.P = P;
+    a.Bs = Bs; a.d_gcode = pair_delta(grad_code, grad_code2, Bs, (long long)D * P);
+    a.b0 = grad_feat ? 0 : Bs;                            // (a pass without grad_feat: its images are not walked)
+    a.nb = (Bs < B && grad_feat && grad_feat2) ? B : Bs;
+    a.step_major = (nonlinear && h.step_major) ? 1 : 0;
+    DG_HIP(dg_launch_head_dx(a, s));
+    return DG_OK;
+}
+
+extern "C" int dg_head_backward_input(int32_t B, int32_t C, int32_t D, int32_t P, const float* w1, const float* w2a, const float* keep1,
+                                      const float* keep2, float keep_scale, const void* hidden, const float* grad_code,
+                                      const void* workspace, size_t workspace_bytes, float* grad_feat,
+                                      void* input_workspace, size_t input_workspace_bytes, dg_stream_t stream_) {
+    return head_backward_input_impl(B, B, C, D, P, w1, w2a, keep1, keep2, keep_scale, hidden, grad_code, nullptr, workspace, workspace_bytes,
+                                    grad_feat, nullptr, input_workspace, input_workspace_bytes, stream_);
+}
+
+extern "C" int dg_head_backward_input_pair(int32_t B, int32_t C, int32_t D, int32_t P, const float* w1, const float* w2a, const float* keep1,
+                                           const float* keep2, float keep_scale, const void* hidden, const float* grad_code,
+                                           const float* grad_code_pos, const void* workspace, size_t workspace_bytes, float* grad_feat,
+                                           float* grad_feat_pos, void* input_workspace, size_t input_workspace_bytes, dg_stream_t stream_) {
+    if (B < 1 || B > (1 << 20)) return fail(DG_ERR_INVALID, "bad head dimensions");
+    return head_backward_input_impl(2 * B, B, C, D, P, w1, w2a, keep1, keep2, keep_scale, hidden, grad_code, grad_code_pos, workspace,
+                                    workspace_bytes, grad_feat, grad_feat_pos, input_workspace, input_workspace_bytes, stream_);
+}

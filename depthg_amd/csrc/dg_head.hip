@@ -1444,3 +1444,180 @@ hipError_t dg_launch_head_rowsum(const void* X, bool bf16, float* out, float* ou
     else hipLaunchKernelGGL(k_head_rowsum<float>, dim3(R), dim3(256), 0, s, static_cast<const float*>(X), out, out2, B, R, P, Bs, dX);
     return hipGetLastError();
 }
+
+// ---------------------------------------------------------------------------------------------------------------- d image_feat
+// dx[b][k][p] = s keep1[b][k] sum_d W1[d][k] g[b][d][p] + s keep2[b][k] sum_j W2a[j][k] dh[b][j][p]: per image ONE product
+// [W1^T | W2a^T] (C x (D + C)) x [g ; dh] ((D + C) x P), opt-in behind dg_head_backward, whose d hidden it reads from the workspace
+// in the layout the plan chose.  Block = (64-position tile, image): the tile's g rows (fp32, rounded to bf16 here) and dh rows become
+// one [row][position] bf16 image in LDS; the product is formed TRANSPOSED as k_head_dh's (rows = positions, read with the same
+// transposing fragment reads; columns = image_feat channels, the B fragments straight from the fragment-major weight copy): an
+// accumulator holds four consecutive positions of one channel - one 16-byte store, 64 contiguous bytes per channel and quarter wave.
+// Dropout2d as in the forward: a dropped channel is a zeroed weight COLUMN here (the lane's own channel: one mask word per lane), so
+// it comes out as exact 0; 1/(1-p) scales the accumulator.  Every element is written once, by one lane: no atomics.
+__global__ __launch_bounds__(256) void k_head_dx_prep(const float* __restrict__ w1, const float* __restrict__ w2a, __bf16* __restrict__ out,
+                                                      int C, int D, int KS1, int KS, size_t n) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    // [block rb][k-step ks][lane][e], lane = 16 g + c: channel k = 16 rb + c, row r = 32 ks + 8 g + e of [g ; dh]
+    const int e = (int)(i & 7), lane = (int)((i >> 3) & 63);
+    const size_t tile = i >> 9;
+    const int ks = (int)(tile % KS), rb = (int)(tile / KS);
+    const int k = 16 * rb + (lane & 15), r = 32 * ks + 8 * (lane >> 4) + e;
+    float v = 0.f;
+    if (k < C) {
+        if (ks < KS1) { if (r < D) v = w1[(size_t)r * C + k]; }
+        else { const int j = r - 32 * KS1; if (j < C) v = w2a[(size_t)j * C + k]; }
+    }
+    out[i] = (__bf16)v;
+}
+hipError_t dg_launch_head_dx_prep(const float* w1, const float* w2a, void* wT, int C, int D, hipStream_t s) {
+    const DgHeadDxLayout L(C, D, w2a != nullptr);
+    hipLaunchKernelGGL(k_head_dx_prep, dim3((unsigned)((L.elems + 255) / 256)), dim3(256), 0, s, w1, w2a, static_cast<__bf16*>(wT), C, D,
+                       L.KS1, L.KS1 + L.KS2, L.elems);
+    return hipGetLastError();
+}
+
+// MB: 16-channel blocks of image_feat per wave and pass (four waves; C > 384 takes two passes over the LDS image)
+template <int MB>
+__global__ __launch_bounds__(256, 2) void k_head_dx(const DgHeadDxArgs a) {
+    constexpr int NT = 64, FROW = NT * 2 + 32;
+    extern __shared__ __attribute__((aligned(16))) char dx_sm[];       // [32 (KS1 + KS2)][FROW]: g rows (D padded to 32 KS1), then dh rows
+    const int tid = threadIdx.x, lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6), g = lane >> 4, c16 = lane & 15;
+    const int b = a.b0 + blockIdx.y, p0 = blockIdx.x * NT;
+    const int C = a.C, D = a.D, P = a.P;
+    const bool nonlinear = a.dh != nullptr;
+    const int KS1 = (D + 31) / 32, KS2 = nonlinear ? (C + 31) / 32 : 0, KS = KS1 + KS2, DP = 32 * KS1;
+    const bool vec4 = (P & 3) == 0;
+    // ---- g tile: fp32 -> bf16 (the rounding k_head_dh gives the same values), rows beyond D and positions beyond P as zeros
+    {
+        const float* const gb = a.gcode + dg_img_off(b, (long long)D * P, a.Bs, a.d_gcode);
+        for (int idx = tid; idx < DP * (NT / 4); idx += 256) {
+            const int d = idx / (NT / 4), q4 = idx - d * (NT / 4), p = p0 + 4 * q4;
+            bf16x4 o;
+            if (vec4) {
+                const f32x4 v = *reinterpret_cast<const f32x4*>(gb + (size_t)(d < D ? d : D - 1) * P + (p < P ? p : P - 4));
+                const bool ok = d < D && p < P;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) o[e] = (__bf16)(ok ? v[e] : 0.f);
+            } else {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) o[e] = (__bf16)((d < D && p + e < P) ? gb[(size_t)d * P + p + e] : 0.f);
+            }
+            *reinterpret_cast<bf16x4*>(dx_sm + d * FROW + q4 * 8) = o;
+        }
+    }
+    // ---- dh tile: 16-byte pieces of 8 positions; step-major ([image][step of 32][row][32], zeros beyond the image) or row-major
+    if (nonlinear) {
+        const int steps_img = (P + 31) / 32;
+        const bool vec8 = (P & 7) == 0;
+        for (int idx = tid; idx < 32 * KS2 * (NT / 8); idx += 256) {
+            const int m = idx >> 3, pc = idx & 7, p = p0 + 8 * pc;
+            u32x4 val = {0u, 0u, 0u, 0u};
+            if (m < C) {
+                if (a.step_major) {
+                    const int stp = (p0 >> 5) + (pc >> 2);
+                    if (stp < steps_img) val = *reinterpret_cast<const u32x4*>(a.dh + (((size_t)b * steps_img + stp) * C + m) * 32 + 8 * (pc & 3));
+                } else if (vec8) {
+                    if (p < P) val = *reinterpret_cast<const u32x4*>(a.dh + ((size_t)b * C + m) * P + p);
+                } else {
+                    bf16x8 t;
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) t[e] = p + e < P ? a.dh[((size_t)b * C + m) * P + p + e] : (__bf16)0.f;
+                    val = __builtin_bit_cast(u32x4, t);
+                }
+            }
+            *reinterpret_cast<u32x4*>(dx_sm + (DP + m) * FROW + pc * 16) = val;
+        }
+    }
+    __syncthreads();
+
+    // one accumulator for both halves: the half of g is brought to the scale of the half of dh where they differ (one keep mask
+    // given and not the other; otherwise the factor is exactly 1), the common factor goes on in the epilogue
+    const float s1 = a.keep1 ? a.scale : 1.f, s2 = a.keep2 ? a.scale : 1.f;
+    const float sfin = nonlinear ? s2 : s1, smid = nonlinear ? s1 / s2 : 1.f;
+    const int KSW = KS;                                                 // k-steps per 16-row block of the weight copy
+    const int npass = (C + 64 * MB - 1) / (64 * MB);
+    float* const out = b < a.Bs ? a.dx + (size_t)b * C * P : a.dx2 + (size_t)(b - a.Bs) * C * P;
+    for (int ps = 0; ps < npass; ++ps) {
+        const int rb0 = (ps * 4 + wid) * MB;
+        unsigned m1[MB], m2[MB];
+#pragma unroll
+        for (int j = 0; j < MB; ++j) {
+            const int k = 16 * (rb0 + j) + c16, kc = k < C ? k : C - 1;
+            const float f1 = a.keep1 ? a.keep1[(size_t)b * C + kc] : 1.f, f2 = a.keep2 ? a.keep2[(size_t)b * C + kc] : 1.f;
+            m1[j] = (k < C && f1 != 0.f) ? 0xffffffffu : 0u;
+            m2[j] = (k < C && f2 != 0.f) ? 0xffffffffu : 0u;
+        }
+        f32x4 acc[4][MB];
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int j = 0; j < MB; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+        // the weight fragments of k-step ks + 1 are in flight while step ks runs
+        u32x4 wn[MB];
+#pragma unroll
+        for (int j = 0; j < MB; ++j) wn[j] = wtile(a.wT, KSW, rb0 + j, 0, lane);
+        for (int ks = 0; ks < KS; ++ks) {
+            u32x4 wc[MB];
+#pragma unroll
+            for (int j = 0; j < MB; ++j) wc[j] = wn[j];
+            if (ks + 1 < KS) {
+#pragma unroll
+                for (int j = 0; j < MB; ++j) wn[j] = wtile(a.wT, KSW, rb0 + j, ks + 1, lane);
+            }
+            if (ks == KS1 && smid != 1.f) {
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+#pragma unroll
+                    for (int j = 0; j < MB; ++j) acc[i][j] *= smid;
+            }
+            const bool first = ks < KS1;
+            bf16x8 af[4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) af[i] = tr_frag(dx_sm, FROW, 32 * ks, 16 * i, lane);      // A[position][row of g / dh]
+#pragma unroll
+            for (int j = 0; j < MB; ++j) {
+                const unsigned mk = first ? m1[j] : m2[j];
+                const bf16x8 bf = wfrag(wc[j], u32x4{mk, mk, mk, mk}, lane);                       // B[row][channel k]
+#pragma unroll
+                for (int i = 0; i < 4; ++i) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i], bf, acc[i][j], 0, 0, 0);
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < MB; ++j) {
+            const int k = 16 * (rb0 + j) + c16;
+            if (k < C) {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const int p = p0 + 16 * i + 4 * g;
+                    const f32x4 v = acc[i][j] * sfin;
+                    if (vec4) { if (p < P) *reinterpret_cast<f32x4*>(out + (size_t)k * P + p) = v; }
+                    else {
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) if (p + r < P) out[(size_t)k * P + p + r] = v[r];
+                    }
+                }
+            }
+        }
+    }
+}
+
+template <int MB>
+static hipError_t launch_head_dx(const DgHeadDxArgs& a, hipStream_t s) {
+    const DgHeadDxLayout L(a.C, a.D, a.dh != nullptr);
+    const int smem = 32 * (L.KS1 + L.KS2) * (64 * 2 + 32);
+    hipError_t e = dg_set_max_smem(reinterpret_cast<const void*>(k_head_dx<MB>), smem);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_head_dx<MB>, dim3((a.P + 63) / 64, a.nb), dim3(256), smem, s, a);
+    return hipGetLastError();
+}
+hipError_t dg_launch_head_dx(const DgHeadDxArgs& a, hipStream_t s) {
+    if (a.nb < 1 || a.b0 < 0 || a.b0 + a.nb > a.B || a.C > 768 || a.D > 128) return hipErrorInvalidValue;
+    switch (dg_head_dx_mb(a.C)) {
+        case 1: return launch_head_dx<1>(a, s);
+        case 2: return launch_head_dx<2>(a, s);
+        case 3: return launch_head_dx<3>(a, s);
+        case 4: return launch_head_dx<4>(a, s);
+        default: return launch_head_dx<6>(a, s);
+    }
+}

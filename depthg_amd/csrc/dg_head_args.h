@@ -89,6 +89,35 @@ hipError_t dg_launch_head_dh(const DgHeadDhArgs& a, const DgHeadPlan& plan, hipS
 // a_bf16 / b_bf16: element types of A and Bm - the three pairings the backward uses: fp32 x fp32, fp32 x bf16, and bf16 x fp32 with the
 // second product (a.M2 > 0)
 hipError_t dg_launch_head_wgrad(const DgHeadWgradArgs& a, DgHeadWgradForm form, bool a_bf16, bool b_bf16, hipStream_t s);
+// ---- d image_feat (k_head_dx; opt-in, behind dg_head_backward on the same workspace): per image one product [W1^T | W2a^T] x [g ; dh]
+// The transposed bf16 weight copies (k_head_dx_prep), fragment-major as the forward's: [16-row block of image_feat channels][k-step of
+// 32 rows of g, then of dh][lane][8 bf16].  Rows are padded to whole passes of the kernel's four waves x MB blocks, g's rows to KS1
+// steps and dh's to KS2 (0: linear head); the padding is zeros.
+__host__ __device__ inline int dg_head_dx_mb(int C) { return C <= 64 ? 1 : (C <= 128 ? 2 : (C <= 192 ? 3 : (C <= 256 ? 4 : 6))); }
+struct DgHeadDxLayout {
+    int MB, rows, KS1, KS2; size_t elems;
+    __host__ __device__ DgHeadDxLayout(int C, int D, bool nonlinear) {
+        MB = dg_head_dx_mb(C);
+        rows = (C + 64 * MB - 1) / (64 * MB) * (64 * MB);
+        KS1 = (D + 31) / 32; KS2 = nonlinear ? (C + 31) / 32 : 0;
+        elems = (size_t)(rows / 16) * (KS1 + KS2) * 512;
+    }
+};
+struct DgHeadDxArgs {
+    const float* gcode;              // (B,D,P) fp32, rounded to bf16 on load
+    const __bf16* dh;                // d hidden as dg_head_backward left it in its workspace (all B images), or null: linear head
+    const __bf16* wT;                // DgHeadDxLayout
+    const float* keep1; const float* keep2;   // (B,C) or null
+    float scale;
+    float* dx; float* dx2;           // (Bs,C,P) out: images 0 .. Bs - 1, and (B - Bs,C,P): images Bs ..; one of a pair may be null (b0 / nb skip it)
+    int32_t B, C, D, P;
+    int32_t Bs; long long d_gcode;   // (pair: images Bs.. of gcode in a second tensor, as DgHeadFwdArgs)
+    int32_t b0, nb;                  // the images this launch computes: b0 .. b0 + nb - 1
+    int32_t step_major;              // layout of dh (DgHeadDhArgs.step_major)
+};
+hipError_t dg_launch_head_dx_prep(const float* w1, const float* w2a, void* wT, int C, int D, hipStream_t s);
+hipError_t dg_launch_head_dx(const DgHeadDxArgs& a, hipStream_t s);
+
 struct DgHeadReduceJob { const float* part; float* out; float* out2; int32_t n, splits; float scale; };
 struct DgHeadReduceArgs { DgHeadReduceJob jobs[6]; int32_t njobs; };
 hipError_t dg_launch_head_reduce(const DgHeadReduceArgs& a, hipStream_t s);

@@ -14,6 +14,21 @@ Differences from the reference, all on the build side:
     "KK"        the reference hard-codes 6 heads (:113); the head count of the model is used (the same for ViT-S).
     backbone    cfg.dg_dino_vit_kwargs (None, or a dict) overrides the architecture's constructor arguments: the test hook that builds
                 small backbones.
+
+DinoFeaturizerWithDepth (src/modules.py:490-631, cfg.arch "dino_depth"): the same frozen backbone with a trainable depth encoder
+(`depth_downscaling`) whose feature-resolution map is mixed into the DINO features in front of the head - cfg.guidance "sum",
+"cross_attn" (`cross_attn`, `no_depth_embed`), "concat" or "none".  The head runs as ever (run_head) with input_grad=True: its
+d image_feat launch (dg_head_backward_input) carries the gradient into the depth modules, which are plain torch.  DepthGuidance is the
+guidance logic as a mixin over any FrozenBackboneFeaturizer (segmenter.StandInFeaturizerWithDepth is the stand-in variant).
+Differences from the reference:
+    concat      the reference's training branch is `pass` (:564-565) and leaves image_depth_feat unbound; here "concat" is "none".
+    unused work depth_downscaling is not run where its result is unused (:557 runs it always): "none", "concat", and eval mode, where
+                the reference feeds it zeros (:613) that "sum" / "none" then ignore.
+    frozen      parameters the chosen guidance never touches in training are built (the state dict is the reference's) but have
+                requires_grad = False: an optimiser never meets a parameter without a gradient - what torch's Adam does with
+                `grad is None` in the reference, skipping it.
+    image_feat  the third training-mode return value is the (B, C, h, w) map under every guidance (under "cross_attn" the reference
+                returns its sequence-first view, :568; nothing reads it).
 """
 import warnings
 
@@ -72,6 +87,116 @@ class FrozenBackboneFeaturizer(nn.Module):
         return (feats, code, attn), (feats_pos, code_pos, attn_pos)
 
 
+class LayerNorm2d(nn.Module):
+    """src/modules.py:619-631: normalisation over the channels of a (B, C, H, W) map, biased variance, eps inside the root."""
+
+    def __init__(self, num_channels: int, eps: float = 1e-6):
+        super().__init__()
+        self.weight = nn.Parameter(torch.ones(num_channels))
+        self.bias = nn.Parameter(torch.zeros(num_channels))
+        self.eps = eps
+
+    def forward(self, x):
+        u = x.mean(1, keepdim=True)
+        s = (x - u).pow(2).mean(1, keepdim=True)
+        x = (x - u) / torch.sqrt(s + self.eps)
+        return self.weight[:, None, None] * x + self.bias[:, None, None]
+
+
+GUIDANCES = ("cross_attn", "concat", "sum", "none")                             # src/modules.py:528
+
+
+def make_depth_downscaling(n_feats: int) -> nn.Sequential:
+    """src/modules.py:497-522: 2 x 2 stride-2 convolutions with LayerNorm2d + GELU between them - three stages (a factor 8, the
+    patch size) for n_feats == 384, five (a factor 32) otherwise."""
+    widths = (1, 64, 128, n_feats) if n_feats == 384 else (1, 64, 128, 256, 512, n_feats)
+    layers = []
+    for i, (cin, cout) in enumerate(zip(widths[:-1], widths[1:])):
+        layers.append(nn.Conv2d(cin, cout, kernel_size=2, stride=2))
+        if i < len(widths) - 2:
+            layers += [LayerNorm2d(cout), nn.GELU()]
+    return nn.Sequential(*layers)
+
+
+class DepthGuidance:
+    """DinoFeaturizerWithDepth's depth modules and forward (src/modules.py:495-614) over a FrozenBackboneFeaturizer: list it in
+    front of the featurizer class and call `_register_depth(cfg)` behind the featurizer's own __init__ (the head's initial values
+    then equal the plain featurizer's under the same seed).  Training input (img, depth) -> (feats, code, image_feat, attn); eval
+    input img -> (feats, code, attn).  forward_pair and deferred dropout are not offered."""
+
+    supports_deferred_dropout = False
+
+    def _register_depth(self, cfg):
+        self.guidance = getattr(cfg, "guidance", "none")                        # :526
+        if self.guidance not in GUIDANCES:                                      # :528
+            raise ValueError(f"depthg_amd: cfg.guidance must be one of {GUIDANCES}, got {self.guidance!r}")
+        self.depth_downscaling = make_depth_downscaling(self.n_feats)           # :497-522
+        self.cross_attn = nn.MultiheadAttention(embed_dim=self.n_feats, num_heads=8, dropout=0.1)    # :524 (sequence-first)
+        self.no_depth_embed = nn.Embedding(1, self.n_feats)                     # :530
+        frozen = {"none": (self.depth_downscaling, self.cross_attn, self.no_depth_embed),
+                  "concat": (self.depth_downscaling, self.cross_attn, self.no_depth_embed),
+                  "sum": (self.cross_attn, self.no_depth_embed),
+                  "cross_attn": (self.no_depth_embed,)}[self.guidance]
+        for m in frozen:
+            for p in m.parameters():
+                p.requires_grad = False
+
+    def depth_parameters(self):
+        """{name: parameter} of the depth modules (trainable or not)."""
+        return {n: p for n, p in self.named_parameters() if n.split(".")[0] in ("depth_downscaling", "cross_attn", "no_depth_embed")}
+
+    def _depth_feats(self, depth, image_feat):
+        if depth.dim() == 3:
+            depth = depth.unsqueeze(1)
+        depth_feats = self.depth_downscaling(depth.to(image_feat.dtype))        # :557
+        if depth_feats.shape != image_feat.shape:
+            raise ValueError(f"depthg_amd: depth_downscaling turns the depth map {tuple(depth.shape)} into {tuple(depth_feats.shape)}, "
+                             f"the backbone's features are {tuple(image_feat.shape)}: the depth must come at the image's resolution "
+                             f"and the stack must shrink it by the patch size ({self.patch_size})")
+        return depth_feats
+
+    def _cross_attend(self, query, image_feat):
+        """:568-575 / :577-585: cross_attn(query, image_feat, image_feat) on sequence-first tokens, back as a (B, C, h, w) map."""
+        B, C, fh, fw = image_feat.shape
+        kv = image_feat.reshape(B, C, -1).permute(2, 0, 1)
+        return self.cross_attn(query, kv, kv)[0].permute(1, 2, 0).reshape(B, C, fh, fw)
+
+    def forward(self, input, n=1, return_class_feat=False, keeps=None):
+        """`keeps`: the head's three Dropout2d keep masks (head.draw_keep_masks) instead of fresh draws - the test hook run_head has."""
+        if self.training:                                                       # :607-614
+            if not isinstance(input, (tuple, list)) or len(input) != 2:
+                raise ValueError("Input should be a tuple of (image, depth)")
+            img, depth = input
+        else:
+            img, depth = (input[0] if isinstance(input, (tuple, list)) else input), None
+        self.model.eval()
+        with torch.no_grad():
+            image_feat, attn = self._backbone(img, n, return_class_feat)
+            if return_class_feat:
+                return image_feat
+        B, C = image_feat.shape[:2]
+        if self.training and self.guidance == "sum":                            # :562-563
+            image_depth_feat = image_feat + self._depth_feats(depth, image_feat)
+        elif self.training and self.guidance == "cross_attn":                   # :566-575
+            image_depth_feat = self._cross_attend(self._depth_feats(depth, image_feat).reshape(B, C, -1).permute(2, 0, 1), image_feat)
+        elif self.guidance == "cross_attn":                                     # :576-585: no depth at evaluation, a learned query
+            P = image_feat.shape[2] * image_feat.shape[3]
+            image_depth_feat = self._cross_attend(self.no_depth_embed.weight.reshape(1, 1, -1).expand(P, B, -1), image_feat)
+        else:                                                                   # :586-587
+            image_depth_feat = image_feat
+        if self.proj_type is not None:
+            # :589-605 - the fused head; its three Dropout2d draws come behind whatever cross_attn's own dropout drew, as there
+            code, feats = run_head(*self._head_modules(), image_depth_feat, self.training, bool(self.cfg.dropout), float(self.dropout.p),
+                                   keeps, input_grad=True)
+        else:
+            code = image_depth_feat
+            feats = self.dropout(image_depth_feat) if self.cfg.dropout else image_depth_feat
+        return (feats, code, image_feat, attn) if self.training else (feats, code, attn)
+
+    def forward_pair(self, *args, **kwargs):
+        raise NotImplementedError("depthg_amd: the depth-guided featurizer has no paired pass (call it once per image set)")
+
+
 class DinoFeaturizer(FrozenBackboneFeaturizer):
     """DinoFeaturizer(dim, cfg) of src/modules.py:19-137."""
 
@@ -128,3 +253,11 @@ class DinoFeaturizer(FrozenBackboneFeaturizer):
         if not want_attn:
             attn = torch.zeros(1, device=img.device)                            # placeholder: only `is None` is ever asked of it
         return image_feat, attn
+
+
+class DinoFeaturizerWithDepth(DepthGuidance, DinoFeaturizer):
+    """DinoFeaturizerWithDepth(dim, cfg) of src/modules.py:490-631 over the ViT of depthg_amd/vit.py (see the module docstring)."""
+
+    def __init__(self, dim: int, cfg):
+        super().__init__(dim, cfg)
+        self._register_depth(cfg)

@@ -35,6 +35,10 @@ augmentation-alignment term (src/train_segmentation.py:400-411) on batch["img_au
 aug_loss.aug_alignment_loss - a third featurizer pass and the fused HIP kernels of dg_aug.hip - and logs it as `loss/aug_alignment`.
 With cfg.rec_weight > 0 the segmenter has a `decoder` (src/train_segmentation.py:115), net_optim steps it (:540-541) and the step adds
 the reconstruction term (:391-398) through rec_loss.reconstruction_loss - the fused HIP kernels of dg_rec_loss.hip - logged as `loss/rec`.
+With cfg.arch == "dino_depth" (:104-106) the featurizer is the depth-guided one - featurizer.DinoFeaturizerWithDepth over the ViT under
+cfg.dg_dino_backbone, StandInFeaturizerWithDepth otherwise - cfg.guidance chooses how the depth encoder's map meets the features, use_depth
+is forced on, the step feeds (img, depth) / (img_pos, depth_pos) one pass at a time and net_optim steps the depth modules the guidance
+trains with the head (the head's d image_feat launch, dg_head_backward_input, carries the gradient to them).
 """
 from types import SimpleNamespace
 from typing import Dict, Optional
@@ -46,7 +50,7 @@ from .aug_loss import aug_alignment_loss
 from .crf_loss import ContrastiveCRFLoss
 from .depth_decay import legacy_decay_step
 from .evaluation import predict_and_score
-from .featurizer import DinoFeaturizer, FrozenBackboneFeaturizer
+from .featurizer import DepthGuidance, DinoFeaturizer, DinoFeaturizerWithDepth, FrozenBackboneFeaturizer
 from .head import ClusterLookup, ProjectionHead, probe_cross_entropy
 from .lhp import LocalHiddenPositiveProjection, OriginalLocalHiddenPositiveProjection
 from .loss import ContrastiveCorrelationLoss
@@ -95,6 +99,14 @@ class StandInFeaturizer(FrozenBackboneFeaturizer):
         return image_feat, self._last_selfattention(img, image_feat)
 
 
+class StandInFeaturizerWithDepth(DepthGuidance, StandInFeaturizer):
+    """DinoFeaturizerWithDepth's contract (src/modules.py:490-631; featurizer.DepthGuidance) over the frozen stand-in backbone."""
+
+    def __init__(self, dim: int, cfg, backbone: Optional[nn.Module] = None):
+        super().__init__(dim, cfg, backbone)
+        self._register_depth(cfg)
+
+
 class UnsupervisedSegmenter(nn.Module):
     """LitUnsupervisedSegmenter(n_classes, cfg) without the Lightning plumbing (src/train_segmentation.py:71-158)."""
 
@@ -103,9 +115,18 @@ class UnsupervisedSegmenter(nn.Module):
         self.cfg, self.n_classes = cfg, n_classes
         dim = n_classes if not cfg.continuous else cfg.dim                          # :78-81
         self.use_depth = bool(cfg.use_depth)
-        if net is None:                                                               # :99-108 (arch == "dino")
+        self.depth_arch = getattr(cfg, "arch", "dino") == "dino_depth"
+        if self.depth_arch:
+            self._refuse_depth_arch_combinations(cfg)
+        if net is None:                                                               # :99-108
             # cfg.dg_dino_backbone (build-side key, off by default): the real DINO ViT (featurizer.DinoFeaturizer) instead of the stand-in
-            net = DinoFeaturizer(dim, cfg) if getattr(cfg, "dg_dino_backbone", False) else StandInFeaturizer(dim, cfg)
+            real = getattr(cfg, "dg_dino_backbone", False)
+            if self.depth_arch:                                                       # :104-106 (arch == "dino_depth")
+                net = DinoFeaturizerWithDepth(dim, cfg) if real else StandInFeaturizerWithDepth(dim, cfg)
+            else:                                                                     # (arch == "dino", any other value, or no key)
+                net = DinoFeaturizer(dim, cfg) if real else StandInFeaturizer(dim, cfg)
+        if self.depth_arch:
+            self.use_depth = True                                                     # :106
         self.net = net
         self.train_cluster_probe = ClusterLookup(dim, n_classes)                      # :110
         self.cluster_probe = ClusterLookup(dim, n_classes + cfg.extra_clusters)       # :112
@@ -139,11 +160,24 @@ class UnsupervisedSegmenter(nn.Module):
         if getattr(cfg, "rec_weight", 0) > 0:
             self.decoder = nn.Conv2d(dim, self.net.n_feats, (1, 1))
 
+    @staticmethod
+    def _refuse_depth_arch_combinations(cfg):
+        """cfg.arch == "dino_depth" with a term that cannot run on it (asked at construction and again in front of a step's first launch)."""
+        if getattr(cfg, "aug_alignment_weight", 0) > 0:
+            raise ValueError("depthg_amd: cfg.aug_alignment_weight > 0 cannot be combined with cfg.arch = 'dino_depth': the term's third "
+                             "featurizer pass has no depth map (the reference's `self.net(img_aug)` fails the depth featurizer's "
+                             "two-tuple assertion, src/modules.py:609)")
+        if getattr(cfg, "rec_weight", 0) > 0 and getattr(cfg, "guidance", "none") in ("sum", "cross_attn"):
+            raise ValueError(f"depthg_amd: cfg.rec_weight > 0 cannot be combined with cfg.arch = 'dino_depth' under guidance "
+                             f"{cfg.guidance!r}: there feats depend on trainable depth modules and the fused reconstruction kernels "
+                             "have no gradient with respect to feats")
+
     def forward(self, x):
         return self.net(x)[1]                                                          # :160-167
 
     def configure_optimizers(self):                                                    # :537-547
-        # as the reference: net_optim steps `self.net.parameters()` and, when the reconstruction term is on (rec_weight > 0,
+        # as the reference: net_optim steps `self.net.parameters()` (the head; with the depth-guided featurizer also the depth modules
+        # its guidance trains - the rest of the net has requires_grad = False) and, when the reconstruction term is on (rec_weight > 0,
         # :540-541), its decoder's (the CRF and augmentation-alignment terms have no parameters of their own) - the LHP projection
         # head is NOT among them, so it keeps its initial weights there and here
         main_params = list(self.net.parameters()) + self._decoder_parameters()
@@ -194,12 +228,13 @@ class UnsupervisedSegmenter(nn.Module):
         return list(decoder.parameters()) if decoder is not None and getattr(self.cfg, "rec_weight", 0) > 0 else []
 
     def head_parameters(self):
-        """The parameters net_optim steps: cluster1 + cluster2."""
+        """The parameters of the featurizer net_optim steps: cluster1 + cluster2 and, under cfg.arch
+        "dino_depth", the depth modules cfg.guidance trains (the others are built with requires_grad = False)."""
         return [p for p in self.net.parameters() if p.requires_grad]
 
     def all_reduced_parameters(self):
-        """Every parameter one of the three optimisers steps - the head and, under cfg.rec_weight, the decoder (net_optim), the
-        linear probe and the cluster probe, in the optimisers' order.
+        """Every parameter one of the three optimisers steps - the head, under cfg.arch "dino_depth" the trained depth modules and,
+        under cfg.rec_weight, the decoder (net_optim), the linear probe and the cluster probe, in the optimisers' order.
         Under data parallelism ALL of them must be averaged over the ranks before the optimiser steps (build the GradBucket
         from this list), or the replicas' probes drift apart.  (The LHP head is stepped by no optimiser, as in the reference,
         src/train_segmentation.py:537-547, so it needs no exchange.)"""
@@ -220,6 +255,8 @@ class UnsupervisedSegmenter(nn.Module):
         img, img_pos, label = batch["img"], batch["img_pos"], batch["label"]
         depth = batch["depth"] if self.use_depth else None
         depth_pos = batch["depth_pos"] if self.use_depth else None
+        if self.depth_arch:                                      # (cfg may have changed since construction)
+            self._refuse_depth_arch_combinations(cfg)
         if getattr(cfg, "aug_alignment_weight", 0) > 0:         # (asked before anything is launched)
             for key in ("img_aug", "coord_aug"):
                 if key not in batch:
@@ -228,7 +265,9 @@ class UnsupervisedSegmenter(nn.Module):
 
         # (both featurizer passes at once where nothing that draws random numbers stands between them in the reference - the LHP
         #  module does - and the featurizer offers it)
-        paired = cfg.correspondence_weight > 0 and not getattr(cfg, "lhp", False) and hasattr(self.net, "forward_pair") and self.net.training
+        #  (the depth-guided featurizer takes (img, depth) and returns four values, :191-200, one pass at a time)
+        paired = cfg.correspondence_weight > 0 and not getattr(cfg, "lhp", False) and hasattr(self.net, "forward_pair") and self.net.training \
+            and not self.depth_arch
         if paired:
             # (on the dense identity grid the Dropout2d of the returned feats is applied by the loss's operand preparation: the
             #  dropped feature tensors are never written - ops.DeferredDropout)
@@ -237,13 +276,20 @@ class UnsupervisedSegmenter(nn.Module):
                 self.contrastive_corr_loss_fn.takes_deferred_dropout((img.shape[2] // p, img.shape[3] // p))
             (feats, code, attn), (feats_pos, code_pos, _) = self.net.forward_pair(img, img_pos, defer) if defer else \
                 self.net.forward_pair(img, img_pos)                                                  # :194-200, :207-212
+        elif self.depth_arch:
+            # (feats carry a graph under guidance "sum" / "cross_attn"; the correlation loss reads them under no_grad, src/modules.py:1232-1234)
+            feats, code, _, attn = self.net((img, depth))                                            # :191-197
+            feats = feats.detach()
         else:
             feats, code, attn = self.net(img)                                                        # :194-200
         lhp_code = self.lhp_module(code, depth, img, attn) if getattr(cfg, "lhp", False) else None    # :202-203
         logs: Dict[str, torch.Tensor] = {}
         loss = 0
         if cfg.correspondence_weight > 0:
-            if not paired:
+            if self.depth_arch:
+                feats_pos, code_pos, _, _ = self.net((img_pos, depth_pos))                           # :205-210
+                feats_pos = feats_pos.detach()
+            elif not paired:
                 feats_pos, code_pos, _ = self.net(img_pos)                                           # :207-212
             lhp_code_pos = self.lhp_module(code_pos, None) if getattr(cfg, "lhp", False) else None   # :214-215
             salience = batch["mask"].to(torch.float32).squeeze(1) if cfg.use_salience else None      # :233-238
@@ -410,7 +456,10 @@ def default_segmenter_cfg(**over) -> SimpleNamespace:
         # build-side: the featurizer is featurizer.DinoFeaturizer (the ViT of vit.py) instead of StandInFeaturizer; its attention
         # through the fused HIP kernel (ops.attention_forward), its blocks' linear layers through ops.vit_linear_forward
         # (dg_dino_vit_kwargs: test hook, constructor arguments of the ViT that override the architecture's)
-        dg_dino_backbone=False, dg_fused_attention=False, dg_fused_linear=False, dg_dino_vit_kwargs=None)
+        dg_dino_backbone=False, dg_fused_attention=False, dg_fused_linear=False, dg_dino_vit_kwargs=None,
+        # arch "dino_depth" (above: "dino"): how DinoFeaturizerWithDepth mixes the depth encoder's map into the features -
+        # "sum", "cross_attn", "concat" or "none" (src/modules.py:526-528)
+        guidance="none")
     for k, v in over.items():
         setattr(cfg, k, v)
     return cfg

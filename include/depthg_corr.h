@@ -479,6 +479,31 @@ int dg_head_backward_pair(int32_t B, int32_t C, int32_t D, int32_t P, const floa
                           float* grad_w2b, float* grad_b2b, void* workspace, size_t workspace_bytes, dg_stream_t stream);
 
 /*
+ * d loss / d image_feat of the head (opt-in: the reference's DinoFeaturizer runs its backbone under no_grad, src/modules.py:96, but
+ * DinoFeaturizerWithDepth feeds the head `image_depth_feat`, which its trainable depth modules produced, src/modules.py:574-597, so
+ * autograd carries the gradient through cluster1 / cluster2 and their Dropout2d, :599-600, into it):
+ *     grad_feat[b,k,p] = keep_scale keep1[b,k] sum_d W1[d,k] grad_code[b,d,p] + keep_scale keep2[b,k] sum_j W2a[j,k] dh[b,j,p]
+ * with dh = d hidden as dg_head_backward formed it.  Call it AFTER dg_head_backward (_pair) with the same B, C, D, P, keep1, keep2,
+ * keep_scale, hidden, grad_code, workspace and stream: d hidden is read from that workspace, in the layout its plan chose.  bf16 MFMA
+ * operands (grad_code rounded on load), fp32 accumulation; every element of grad_feat is written once (no atomics: bit-reproducible),
+ * a dropped channel is exact 0.  The third Dropout2d draw (feats_out) takes no part: the loss reads feats under no_grad, :1232-1234.
+ *  w1, w2a              : the fp32 parameters (D,C), (C,C); w2a NULL for projection_type "linear" (hidden, workspace then unused)
+ *  grad_feat            : fp32 (B,C,P) out
+ *  input_workspace      : dg_head_input_workspace_bytes(C, D) bytes (the transposed bf16 weight copies, written by this call)
+ * The pair form walks the 2B images of dg_head_backward_pair; grad_feat or grad_feat_pos may be NULL (not both): that pass's images
+ * are then not computed.
+ */
+size_t dg_head_input_workspace_bytes(int32_t C, int32_t D);
+int dg_head_backward_input(int32_t B, int32_t C, int32_t D, int32_t P, const float* w1, const float* w2a, const float* keep1,
+                           const float* keep2, float keep_scale, const void* hidden, const float* grad_code,
+                           const void* workspace, size_t workspace_bytes, float* grad_feat,
+                           void* input_workspace, size_t input_workspace_bytes, dg_stream_t stream);
+int dg_head_backward_input_pair(int32_t B, int32_t C, int32_t D, int32_t P, const float* w1, const float* w2a, const float* keep1,
+                                const float* keep2, float keep_scale, const void* hidden, const float* grad_code,
+                                const float* grad_code_pos, const void* workspace, size_t workspace_bytes, float* grad_feat,
+                                float* grad_feat_pos, void* input_workspace, size_t input_workspace_bytes, dg_stream_t stream);
+
+/*
  * Measurement aid: the launch routes dg_head_backward takes for B images (dg_head_backward_pair: pass 2 B) of C channels, D code
  * channels and P positions, from the plan the launches themselves follow.  Launches nothing and touches no GPU.  out[9] =
  *   [0] d hidden route     0: k_head_dh, one block per 64-position tile      1: k_head_dh2, persistent blocks, d W2b inside
