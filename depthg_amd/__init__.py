@@ -37,6 +37,7 @@ from . import aug_loss  # noqa: F401
 from .aug_loss import aug_alignment_loss, crop_flip_coords  # noqa: F401
 from . import rec_loss  # noqa: F401
 from .rec_loss import reconstruction_loss  # noqa: F401
+from .depth_encoder import depth_encoder  # noqa: F401
 from . import depth_decay  # noqa: F401
 from . import training  # noqa: F401
 from . import metrics  # noqa: F401
@@ -53,6 +54,6 @@ from . import featurizer  # noqa: F401
 from .featurizer import DinoFeaturizer, DinoFeaturizerWithDepth  # noqa: F401
 from . import segmenter  # noqa: F401
 
-__all__ = ["ContrastiveCorrelationLoss", "ContrastiveCRFLoss", "crf_loss", "aug_loss", "aug_alignment_loss", "crop_flip_coords", "rec_loss", "reconstruction_loss", "depth_decay", "training", "metrics", "evaluation", "predict_and_score", "crf", "dense_crf",
+__all__ = ["ContrastiveCorrelationLoss", "ContrastiveCRFLoss", "crf_loss", "aug_loss", "aug_alignment_loss", "crop_flip_coords", "rec_loss", "reconstruction_loss", "depth_encoder", "depth_decay", "training", "metrics", "evaluation", "predict_and_score", "crf", "dense_crf",
            "batched_crf", "knn", "lhp", "optim", "FusedAdam", "FusedAdamSet", "segmenter", "vit", "featurizer",
            "DinoFeaturizer", "DinoFeaturizerWithDepth"]

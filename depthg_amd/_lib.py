@@ -120,6 +120,10 @@ SIGNATURES = {
     "dg_vit_linear_packed_bytes": (_SZ, [i32] * 2),
     "dg_vit_linear_pack": (_I, [vp, i32, i32, vp, vp]),
     "dg_vit_linear_forward": (_I, [vp, vp, vp, f32, vp, vp, vp, vp] + [i32] * 4 + [vp]),
+    # depth encoder
+    "dg_depthenc_workspace_bytes": (_SZ, [i32] * 5),
+    "dg_depthenc_forward": (_I, [vp] * 12 + [i32] * 8 + [vp, vp, _SZ, vp]),
+    "dg_depthenc_backward": (_I, [vp] * 12 + [i32] * 6 + [vp] * 11 + [_SZ, vp]),
     # measurement aids
     "dg_corr_main_kernel_name": (_STR, [cp]),
     "dg_corr_intra_folded": (_I, [cp]),

@@ -7,6 +7,7 @@
 #include <cstdlib>
 #include <cstdio>
 #include <cstring>
+#include <initializer_list>
 #include <mutex>
 #include <optional>
 
@@ -20,6 +21,21 @@ int fail(int code, const char* fmt, ...);
     } while (0)
 
 static inline size_t up(size_t x, size_t a) { return (x + a - 1) / a * a; }
+
+// ---- the argument checks the entry points with a workspace share (dg_api_loss.hip, the depth encoder of dg_api_aux.hip)
+// the pointers of `p4` on 4-byte boundaries (a null optional pointer passes), the workspace on a 16-byte one
+inline int check_aligned(const char* who, std::initializer_list<const void*> p4, const void* workspace) {
+    uintptr_t bits = 0;
+    for (const void* p : p4) bits |= (uintptr_t)p;
+    if ((bits & 3) || ((uintptr_t)workspace & 15))
+        return fail(DG_ERR_INVALID, "%s: the tensors must be 4-byte aligned, workspace 16-byte aligned", who);
+    return DG_OK;
+}
+
+inline int check_workspace(const char* who, size_t workspace_bytes, size_t need, const char* sizer) {
+    if (workspace_bytes < need) return fail(DG_ERR_WORKSPACE, "%s: workspace of %zu bytes, %zu needed (%s)", who, workspace_bytes, need, sizer);
+    return DG_OK;
+}
 
 // A second stream of the library's own (one per device, created on the first call that is not being captured into a graph) for the
 // launches that may run beside each other inside one call; null while none exists and the caller's stream is capturing (creating

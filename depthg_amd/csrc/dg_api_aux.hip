@@ -1,8 +1,9 @@
 // C ABI of the gfx950 DepthG library (include/depthg_corr.h), the units' shared state and the small subsystems: version and error
-// text, the library's side stream, batch maps / random draws / coordinate samplers, kNN, LHP, fused Adam, ViT attention and linear.  (The auxiliary loss terms: dg_api_loss.hip.)
+// text, the library's side stream, batch maps / random draws / coordinate samplers, kNN, LHP, fused Adam, ViT attention and linear, the fused depth encoder.  (The auxiliary loss terms: dg_api_loss.hip.)
 // Host-side only: argument checks and kernel launches on the caller's stream.
 #include "dg_api.h"
 #include "dg_aux_args.h"
+#include "dg_depth_args.h"
 #include "dg_corr_args.h"     // the samplers of dg_post.hip: super_perms, rand_coords_state, fps
 
 #include <cstdarg>
@@ -313,5 +314,80 @@ extern "C" int dg_vit_linear_forward(const void* x, const float* gamma, const fl
     if (((uintptr_t)x | (uintptr_t)gamma | (uintptr_t)beta | (uintptr_t)packed | (uintptr_t)bias | (uintptr_t)residual | (uintptr_t)out) & 15)
         return fail(DG_ERR_INVALID, "dg_vit_linear_forward: every pointer must be 16-byte aligned");
     DG_HIP(dg_launch_linear(x, gamma, beta, eps, packed, bias, residual, out, M, K, Nout, flags, static_cast<hipStream_t>(stream_)));
+    return DG_OK;
+}
+
+// ---- the fused depth encoder (dg_depth_enc.hip)
+static int depthenc_check(const char* who, int32_t B, int32_t C, int32_t h, int32_t w, int32_t depth_h, int32_t depth_w) {
+    if (B < 1 || h < 1 || w < 1) return fail(DG_ERR_INVALID, "%s: B=%d, feature grid %dx%d must be positive", who, B, h, w);
+    if (C < 64 || C > DG_DE_MAX_C || C % 64)
+        return fail(DG_ERR_UNSUPPORTED, "%s: C=%d: the last convolution's width must be a multiple of 64 up to %d", who, C, DG_DE_MAX_C);
+    if ((long long)B * h * w > DG_DE_MAX_POS) return fail(DG_ERR_UNSUPPORTED, "%s: B h w = %lld positions above %d", who, (long long)B * h * w, DG_DE_MAX_POS);
+    if (depth_h != 8 * h || depth_w != 8 * w)
+        return fail(DG_ERR_INVALID, "%s: the depth map is %dx%d, the three-stage stack shrinks by 8: a %dx%d grid needs %dx%d", who, depth_h,
+                    depth_w, h, w, 8 * h, 8 * w);
+    return DG_OK;
+}
+
+static DgDepthEncArgs depthenc_args(void* workspace, bool backward, const float* depth, const float* w1, const float* b1, const float* g1,
+                                    const float* be1, const float* w2, const float* b2, const float* g2, const float* be2, const float* w3,
+                                    const float* b3, int32_t B, int32_t C, int32_t h, int32_t w) {
+    DgDepthEncArgs A;
+    memset(&A, 0, sizeof(A));
+    const DgDepthWs ws = dg_depth_ws(B, C, h, w, backward);
+    char* base = static_cast<char*>(workspace);
+    A.depth = depth; A.w1 = w1; A.b1 = b1; A.g1 = g1; A.be1 = be1; A.w2 = w2; A.b2 = b2; A.g2 = g2; A.be2 = be2; A.w3 = w3; A.b3 = b3;
+    A.pack_w2 = base + ws.pack_w2; A.pack_w3 = base + ws.pack_w3; A.pack_w2t = base + ws.pack_w2t; A.pack_w3t = base + ws.pack_w3t;
+    A.x2t = base + ws.x2t; A.da2t = base + ws.da2t;
+    A.part_small = reinterpret_cast<float*>(base + ws.part_small); A.part_w2 = reinterpret_cast<float*>(base + ws.part_w2);
+    A.part_w3 = reinterpret_cast<float*>(base + ws.part_w3);
+    A.B = B; A.C = C; A.h = h; A.w = w; A.P = h * w; A.N = B * h * w;
+    A.tiles = ws.tiles; A.blocks_act = ws.blocks_act; A.splits_w2 = ws.splits_w2; A.splits_w3 = ws.splits_w3;
+    return A;
+}
+
+extern "C" size_t dg_depthenc_workspace_bytes(int32_t B, int32_t C, int32_t h, int32_t w, int32_t backward) {
+    if (!dg_depthenc_supported(B, C, h, w)) return 0;
+    return dg_depth_ws(B, C, h, w, backward != 0).total;
+}
+
+extern "C" int dg_depthenc_forward(const float* depth, const float* w1, const float* b1, const float* gamma1, const float* beta1,
+                                   const float* w2, const float* b2, const float* gamma2, const float* beta2, const float* w3,
+                                   const float* b3, const float* residual, int32_t residual_h, int32_t residual_w, int32_t B, int32_t C,
+                                   int32_t h, int32_t w, int32_t depth_h, int32_t depth_w, float* out, void* workspace,
+                                   size_t workspace_bytes, dg_stream_t stream_) {
+    if (int rc = depthenc_check(__func__, B, C, h, w, depth_h, depth_w)) return rc;
+    if (residual && (residual_h != h || residual_w != w))
+        return fail(DG_ERR_INVALID, "dg_depthenc_forward: the residual's grid is %dx%d, the encoder's result %dx%d: pass a (B, C, h, w) map", residual_h,
+                    residual_w, h, w);
+    if (!depth || !w1 || !b1 || !gamma1 || !beta1 || !w2 || !b2 || !gamma2 || !beta2 || !w3 || !b3 || !out || !workspace)
+        return fail(DG_ERR_INVALID, "dg_depthenc_forward: null pointer");
+    if (int rc = check_aligned(__func__, {depth, w1, b1, gamma1, beta1, w2, b2, gamma2, beta2, w3, b3, residual, out}, workspace)) return rc;
+    if (int rc = check_workspace(__func__, workspace_bytes, dg_depth_ws(B, C, h, w, false).total, "dg_depthenc_workspace_bytes")) return rc;
+    DgDepthEncArgs A = depthenc_args(workspace, false, depth, w1, b1, gamma1, beta1, w2, b2, gamma2, beta2, w3, b3, B, C, h, w);
+    A.residual = residual; A.out = out;
+    DG_HIP(dg_launch_depthenc_forward(A, static_cast<hipStream_t>(stream_)));
+    return DG_OK;
+}
+
+extern "C" int dg_depthenc_backward(const float* depth, const float* w1, const float* b1, const float* gamma1, const float* beta1,
+                                    const float* w2, const float* b2, const float* gamma2, const float* beta2, const float* w3,
+                                    const float* b3, const float* grad_out, int32_t B, int32_t C, int32_t h, int32_t w, int32_t depth_h,
+                                    int32_t depth_w, float* grad_w1, float* grad_b1, float* grad_gamma1, float* grad_beta1, float* grad_w2,
+                                    float* grad_b2, float* grad_gamma2, float* grad_beta2, float* grad_w3, float* grad_b3, void* workspace,
+                                    size_t workspace_bytes, dg_stream_t stream_) {
+    if (int rc = depthenc_check(__func__, B, C, h, w, depth_h, depth_w)) return rc;
+    if (!depth || !w1 || !b1 || !gamma1 || !beta1 || !w2 || !b2 || !gamma2 || !beta2 || !w3 || !b3 || !grad_out || !workspace)
+        return fail(DG_ERR_INVALID, "dg_depthenc_backward: null pointer");
+    if (!grad_w1 || !grad_b1 || !grad_gamma1 || !grad_beta1 || !grad_w2 || !grad_b2 || !grad_gamma2 || !grad_beta2 || !grad_w3 || !grad_b3)
+        return fail(DG_ERR_INVALID, "dg_depthenc_backward: null gradient pointer (all ten are written)");
+    if (int rc = check_aligned(__func__, {depth, w1, b1, gamma1, beta1, w2, b2, gamma2, beta2, w3, b3, grad_out, grad_w1, grad_b1, grad_gamma1,
+                                          grad_beta1, grad_w2, grad_b2, grad_gamma2, grad_beta2, grad_w3, grad_b3}, workspace)) return rc;
+    if (int rc = check_workspace(__func__, workspace_bytes, dg_depth_ws(B, C, h, w, true).total, "dg_depthenc_workspace_bytes")) return rc;
+    DgDepthEncArgs A = depthenc_args(workspace, true, depth, w1, b1, gamma1, beta1, w2, b2, gamma2, beta2, w3, b3, B, C, h, w);
+    A.grad_out = grad_out;
+    A.d_w1 = grad_w1; A.d_b1 = grad_b1; A.d_g1 = grad_gamma1; A.d_be1 = grad_beta1; A.d_w2 = grad_w2; A.d_b2 = grad_b2; A.d_g2 = grad_gamma2;
+    A.d_be2 = grad_beta2; A.d_w3 = grad_w3; A.d_b3 = grad_b3;
+    DG_HIP(dg_launch_depthenc_backward(A, static_cast<hipStream_t>(stream_)));
     return DG_OK;
 }

@@ -5,22 +5,6 @@
 #include "dg_api.h"
 #include "dg_loss_args.h"
 
-#include <initializer_list>
-
-// the pointers of `p4` on 4-byte boundaries (a null optional pointer passes), the workspace on a 16-byte one
-static int check_aligned(const char* who, std::initializer_list<const void*> p4, const void* workspace) {
-    uintptr_t bits = 0;
-    for (const void* p : p4) bits |= (uintptr_t)p;
-    if ((bits & 3) || ((uintptr_t)workspace & 15))
-        return fail(DG_ERR_INVALID, "%s: the tensors must be 4-byte aligned, workspace 16-byte aligned", who);
-    return DG_OK;
-}
-
-static int check_workspace(const char* who, size_t workspace_bytes, size_t need, const char* sizer) {
-    if (workspace_bytes < need) return fail(DG_ERR_WORKSPACE, "%s: workspace of %zu bytes, %zu needed (%s)", who, workspace_bytes, need, sizer);
-    return DG_OK;
-}
-
 // ---- the contrastive CRF loss term (dg_crf_loss.hip)
 static int crfl_check(const char* who, int32_t B, int32_t D, int32_t h, int32_t w, int32_t size, int32_t n) {
     if (B < 1 || h < 1 || w < 1) return fail(DG_ERR_INVALID, "%s: B=%d, code map %dx%d must be positive", who, B, h, w);

@@ -18,7 +18,9 @@ Differences from the reference, all on the build side:
 DinoFeaturizerWithDepth (src/modules.py:490-631, cfg.arch "dino_depth"): the same frozen backbone with a trainable depth encoder
 (`depth_downscaling`) whose feature-resolution map is mixed into the DINO features in front of the head - cfg.guidance "sum",
 "cross_attn" (`cross_attn`, `no_depth_embed`), "concat" or "none".  The head runs as ever (run_head) with input_grad=True: its
-d image_feat launch (dg_head_backward_input) carries the gradient into the depth modules, which are plain torch.  DepthGuidance is the
+d image_feat launch (dg_head_backward_input) carries the gradient into the depth modules, which are plain torch - except, with
+cfg.dg_fused_depth_encoder (off by default; n_feats == 384 only), the depth encoder: one fused HIP forward and backward
+(depth_encoder.py, dg_depth_enc.hip), the "sum" guidance's add in its epilogue.  DepthGuidance is the
 guidance logic as a mixin over any FrozenBackboneFeaturizer (segmenter.StandInFeaturizerWithDepth is the stand-in variant).
 Differences from the reference:
     concat      the reference's training branch is `pass` (:564-565) and leaves image_depth_feat unbound; here "concat" is "none".
@@ -36,6 +38,7 @@ import torch
 import torch.nn as nn
 
 from . import vit
+from .depth_encoder import depth_encoder
 from .head import ProjectionHead, run_head, run_head_pair
 
 
@@ -133,6 +136,10 @@ class DepthGuidance:
         self.depth_downscaling = make_depth_downscaling(self.n_feats)           # :497-522
         self.cross_attn = nn.MultiheadAttention(embed_dim=self.n_feats, num_heads=8, dropout=0.1)    # :524 (sequence-first)
         self.no_depth_embed = nn.Embedding(1, self.n_feats)                     # :530
+        self.fused_depth_encoder = bool(getattr(cfg, "dg_fused_depth_encoder", False))
+        if self.fused_depth_encoder and self.n_feats != 384:
+            raise ValueError(f"depthg_amd: cfg.dg_fused_depth_encoder fuses the three-stage depth encoder of n_feats == 384; this backbone "
+                             f"has n_feats = {self.n_feats}, whose five-stage stack stays on the torch route: leave the flag off")
         frozen = {"none": (self.depth_downscaling, self.cross_attn, self.no_depth_embed),
                   "concat": (self.depth_downscaling, self.cross_attn, self.no_depth_embed),
                   "sum": (self.cross_attn, self.no_depth_embed),
@@ -145,15 +152,21 @@ class DepthGuidance:
         """{name: parameter} of the depth modules (trainable or not)."""
         return {n: p for n, p in self.named_parameters() if n.split(".")[0] in ("depth_downscaling", "cross_attn", "no_depth_embed")}
 
-    def _depth_feats(self, depth, image_feat):
+    def _depth_feats(self, depth, image_feat, residual=None):
+        """depth_downscaling(depth) (+ residual); with cfg.dg_fused_depth_encoder one fused HIP forward (depth_encoder.py)."""
         if depth.dim() == 3:
             depth = depth.unsqueeze(1)
+        if self.fused_depth_encoder:
+            if tuple(depth.shape[2:]) != (8 * image_feat.shape[2], 8 * image_feat.shape[3]):
+                raise ValueError(f"depthg_amd: the depth map {tuple(depth.shape)} is not 8 x the backbone's feature grid {tuple(image_feat.shape)}: "
+                                 f"the depth must come at the image's resolution and the patch size ({self.patch_size}) must be 8")
+            return depth_encoder(depth.to(image_feat.dtype), self.depth_downscaling, residual)
         depth_feats = self.depth_downscaling(depth.to(image_feat.dtype))        # :557
         if depth_feats.shape != image_feat.shape:
             raise ValueError(f"depthg_amd: depth_downscaling turns the depth map {tuple(depth.shape)} into {tuple(depth_feats.shape)}, "
                              f"the backbone's features are {tuple(image_feat.shape)}: the depth must come at the image's resolution "
                              f"and the stack must shrink it by the patch size ({self.patch_size})")
-        return depth_feats
+        return depth_feats if residual is None else residual + depth_feats
 
     def _cross_attend(self, query, image_feat):
         """:568-575 / :577-585: cross_attn(query, image_feat, image_feat) on sequence-first tokens, back as a (B, C, h, w) map."""
@@ -176,7 +189,7 @@ class DepthGuidance:
                 return image_feat
         B, C = image_feat.shape[:2]
         if self.training and self.guidance == "sum":                            # :562-563
-            image_depth_feat = image_feat + self._depth_feats(depth, image_feat)
+            image_depth_feat = self._depth_feats(depth, image_feat, image_feat)    # (fused: the add runs in the kernel's epilogue)
         elif self.training and self.guidance == "cross_attn":                   # :566-575
             image_depth_feat = self._cross_attend(self._depth_feats(depth, image_feat).reshape(B, C, -1).permute(2, 0, 1), image_feat)
         elif self.guidance == "cross_attn":                                     # :576-585: no depth at evaluation, a learned query

@@ -520,6 +520,84 @@ def rec_loss_backward(workspace, code, feats, weight, bias, grad_out, keep=None,
     return out[0], out[1], out[2]
 
 
+def depth_encoder_shapes(depth, params, residual=None):
+    """The fused depth encoder's shape rules, on any device: depth (B, 1, 8h, 8w) or (B, 8h, 8w); params the ten tensors of the
+    three-stage stack in module order (w1, b1, gamma1, beta1, w2, b2, gamma2, beta2, w3, b3); residual None or (B, C, h, w).
+    Returns (B, C, h, w)."""
+    if depth.dim() == 4 and depth.shape[1] == 1:
+        depth = depth[:, 0]
+    if depth.dim() != 3:
+        raise ValueError(f"depthg_amd: the depth map must be (B, 1, H, W) or (B, H, W), got {tuple(depth.shape)}")
+    B, H, W = depth.shape
+    if B < 1 or H < 8 or W < 8 or H % 8 or W % 8:
+        raise ValueError(f"depthg_amd: the three-stage depth encoder shrinks by 8: the depth map's {H}x{W} must be positive multiples of 8")
+    if len(params) != 10:
+        raise ValueError(f"depthg_amd: the three-stage depth encoder has ten parameters, got {len(params)}")
+    C = params[8].shape[0]
+    want = ((64, 1, 2, 2), (64,), (64,), (64,), (128, 64, 2, 2), (128,), (128,), (128,), (C, 128, 2, 2), (C,))
+    names = ("w1", "b1", "gamma1", "beta1", "w2", "b2", "gamma2", "beta2", "w3", "b3")
+    for t, sh, name in zip(params, want, names):
+        if tuple(t.shape) != sh:
+            raise ValueError(f"depthg_amd: depth encoder parameter {name} must be {sh}, got {tuple(t.shape)}")
+    if C % 64 or not 64 <= C <= 768:
+        raise ValueError(f"depthg_amd: the fused depth encoder takes a last width that is a multiple of 64 up to 768, got C={C}")
+    h, w = H // 8, W // 8
+    if residual is not None and tuple(residual.shape) != (B, C, h, w):
+        raise ValueError(f"depthg_amd: residual must be (B, C, h, w) = {(B, C, h, w)}, the encoder's result, got {tuple(residual.shape)}")
+    return B, C, h, w
+
+
+def _depth_encoder_operands(depth, params, extra, extra_name):
+    """The encoder's tensors as the library reads them: fp32 (refused otherwise), on one GPU, contiguous (a strided depth map is
+    copied here, once); depth as (B, 8h, 8w).  extra: the residual (or None) / the upstream gradient, shaped (B, C, h, w)."""
+    B, C, h, w = depth_encoder_shapes(depth, params, extra)
+    names = ("w1", "b1", "gamma1", "beta1", "w2", "b2", "gamma2", "beta2", "w3", "b3")
+    tensors = [(depth, "depth"), *zip(params, names)] + ([(extra, extra_name)] if extra is not None else [])
+    _gpu_float32(tensors, "the fused depth encoder wants float32 tensors on the GPU, got {name} as {dtype}")
+    dev = depth.device
+    for t, name in tensors:
+        if t.device != dev:
+            raise RuntimeError(f"depthg_amd: depth lives on {dev}, {name} on {t.device}")
+    depth = depth.detach().reshape(B, 8 * h, 8 * w).contiguous()
+    params = [p.detach().contiguous() for p in params]
+    extra = extra.detach().contiguous() if extra is not None else None
+    return depth, params, extra, (B, C, h, w)
+
+
+def depth_encoder_workspace_bytes(B, C, h, w, backward):
+    return _plan_bytes(_lib.load().dg_depthenc_workspace_bytes(B, C, h, w, 1 if backward else 0), "depth-encoder", f"B={B}, C={C}, grid {h}x{w}",
+                       "C a multiple of 64 up to 768, B h w <= 2^24")
+
+
+def depth_encoder_forward(depth, params, residual=None):
+    """The three-stage depth encoder (dg_depthenc_forward; src/modules.py:497-506, :557): depth (B, 1, 8h, 8w) or (B, 8h, 8w), the
+    stack's ten parameters in module order, optionally `residual` (B, C, h, w) added in the epilogue (:562-563) -> (B, C, h, w)."""
+    lib = _lib.load()
+    depth, params, residual, (B, C, h, w) = _depth_encoder_operands(depth, params, residual, "residual")
+    dev = depth.device
+    ws = _empty((depth_encoder_workspace_bytes(B, C, h, w, False),), torch.uint8, dev)
+    out = _empty((B, C, h, w), torch.float32, dev)
+    rc = lib.dg_depthenc_forward(_ptr(depth), *[_ptr(p) for p in params], _ptr(residual), h, w, B, C, h, w, 8 * h, 8 * w, _ptr(out), _ptr(ws),
+                                 ws.numel(), _stream(dev))
+    _lib.check(rc, "dg_depthenc_forward")
+    return out
+
+
+def depth_encoder_backward(depth, params, grad_out, out=None):
+    """The gradients of depth_encoder_forward's ten parameters for the upstream gradient `grad_out` (B, C, h, w), in the parameters'
+    order and shapes (dg_depthenc_backward); every element written.  out: optional tuple of ten result buffers."""
+    lib = _lib.load()
+    depth, params, grad_out, (B, C, h, w) = _depth_encoder_operands(depth, params, grad_out, "grad_out")
+    dev = depth.device
+    names = ("w1", "b1", "gamma1", "beta1", "w2", "b2", "gamma2", "beta2", "w3", "b3")
+    out = _out_buffers(out, [tuple(p.shape) for p in params], names, dev)
+    ws = _empty((depth_encoder_workspace_bytes(B, C, h, w, True),), torch.uint8, dev)
+    rc = lib.dg_depthenc_backward(_ptr(depth), *[_ptr(p) for p in params], _ptr(grad_out), B, C, h, w, 8 * h, 8 * w, *[_ptr(o) for o in out],
+                                  _ptr(ws), ws.numel(), _stream(dev))
+    _lib.check(rc, "dg_depthenc_backward")
+    return out
+
+
 def fps_coords(depth, feat_hw, n_samples, return_inds=False):
     """depth (B,1,H,W) on GPU -> coords (B,S,S,2) in [-1,1) (already *2-1)."""
     lib = _lib.load()

@@ -459,7 +459,9 @@ def default_segmenter_cfg(**over) -> SimpleNamespace:
         dg_dino_backbone=False, dg_fused_attention=False, dg_fused_linear=False, dg_dino_vit_kwargs=None,
         # arch "dino_depth" (above: "dino"): how DinoFeaturizerWithDepth mixes the depth encoder's map into the features -
         # "sum", "cross_attn", "concat" or "none" (src/modules.py:526-528)
-        guidance="none")
+        guidance="none",
+        # build-side, arch "dino_depth" with n_feats == 384: the depth encoder as one fused HIP forward and backward (depth_encoder.py)
+        dg_fused_depth_encoder=False)
     for k, v in over.items():
         setattr(cfg, k, v)
     return cfg

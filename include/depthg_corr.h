@@ -797,6 +797,45 @@ int dg_vit_linear_pack(const float* weight, int32_t K, int32_t Nout, void* packe
 int dg_vit_linear_forward(const void* x, const float* gamma, const float* beta, float eps, const void* packed, const float* bias,
                           const float* residual, void* out, int32_t M, int32_t K, int32_t Nout, int32_t flags, dg_stream_t stream);
 
+/*
+ * The three-stage depth encoder of DinoFeaturizerWithDepth as fused kernels, forward and backward (src/modules.py:497-506: the
+ * `depth_downscaling` stack for n_feats == 384; :557 its call; :562-563 the "sum" guidance's add; :619-631 LayerNorm2d):
+ *      Conv2d(1,64,2,2), LayerNorm2d(64), GELU, Conv2d(64,128,2,2), LayerNorm2d(128), GELU, Conv2d(128,C,2,2)      [+ residual]
+ * Each output position depends on one 8 x 8 depth patch, so no activation map of stage 1 or 2 is written by the forward, and the
+ * backward re-forms them from the depth map.
+ *  depth : fp32 (B, depth_h, depth_w) contiguous with depth_h = 8 h, depth_w = 8 w (DG_ERR_INVALID otherwise)
+ *  w1 (64,1,2,2), b1 (64), gamma1, beta1 (64), w2 (128,64,2,2), b2 (128), gamma2, beta2 (128), w3 (C,128,2,2), b3 (C): the fp32
+ *          parameters as nn.Conv2d / LayerNorm2d store them, contiguous
+ *  residual : NULL, or fp32 (B, C, residual_h, residual_w) added in the forward's epilogue, out = residual + (acc + b3); its grid
+ *          must be h x w (DG_ERR_INVALID otherwise).  It receives no gradient here: d out passes to it unchanged.
+ *  C : a multiple of 64 up to 768 (DG_ERR_UNSUPPORTED otherwise);  B, h, w >= 1, B h w <= 2^24
+ *  workspace : dg_depthenc_workspace_bytes(B, C, h, w, backward) bytes (0 on bad arguments), 16-byte aligned; every tensor 4-byte
+ *          aligned.  Sections at multiples of 256 bytes: bf16 MFMA-fragment images of W2 and W3, made by every call (the weights
+ *          change every step) - that is all the forward uses (backward = 0); with backward = 1 also the images of W2^T and W3^T, the
+ *          stage-2 activation and its gradient as bf16, 2 x (tiles of 32 positions) x 512 x 32, and the fp32 partial sums of the
+ *          weight gradients: 832 per block of the activation kernel (at most 512), 128 x 256 per split of d W2 (at most 64),
+ *          C x 512 + 2 C per split of d W3 (at most 32).  Nothing of stage-1 size (B h w x 1024) is stored.
+ *  forward  : writes EVERY element of out (B, C, h, w)
+ *  backward : grad_out fp32 (B, C, h, w) contiguous; writes EVERY element of the ten gradients, shaped as their parameters.  There
+ *          is no gradient for the depth map.  Needs nothing of the forward's workspace.
+ * Arithmetic: stage 1 (K = 4) fp32 on the VALU; stages 2 and 3 and the backward's four products on v_mfma_f32_32x32x16_bf16 with
+ * fp32 accumulation - W2, W3, the stage-1 and stage-2 activations, grad_out and the stage-2 pre-norm gradient are rounded to bf16
+ * (nearest even) as MFMA operands.  LayerNorm statistics (biased variance, eps = 1e-6 inside the root), normalisation, exact (erf)
+ * GELU and the biases are fp32; d b3 sums the fp32 grad_out in fp64; all partials are combined in fp64 in one fixed order.  No
+ * atomics: two calls give the same bits.  No host synchronisation.
+ */
+size_t dg_depthenc_workspace_bytes(int32_t B, int32_t C, int32_t h, int32_t w, int32_t backward);
+int dg_depthenc_forward(const float* depth, const float* w1, const float* b1, const float* gamma1, const float* beta1,
+                        const float* w2, const float* b2, const float* gamma2, const float* beta2, const float* w3, const float* b3,
+                        const float* residual, int32_t residual_h, int32_t residual_w, int32_t B, int32_t C, int32_t h, int32_t w,
+                        int32_t depth_h, int32_t depth_w, float* out, void* workspace, size_t workspace_bytes, dg_stream_t stream);
+int dg_depthenc_backward(const float* depth, const float* w1, const float* b1, const float* gamma1, const float* beta1,
+                         const float* w2, const float* b2, const float* gamma2, const float* beta2, const float* w3, const float* b3,
+                         const float* grad_out, int32_t B, int32_t C, int32_t h, int32_t w, int32_t depth_h, int32_t depth_w,
+                         float* grad_w1, float* grad_b1, float* grad_gamma1, float* grad_beta1, float* grad_w2, float* grad_b2,
+                         float* grad_gamma2, float* grad_beta2, float* grad_w3, float* grad_b3, void* workspace,
+                         size_t workspace_bytes, dg_stream_t stream);
+
 /* Measurement aid: name of the kernel the fused correlation launch of this descriptor runs ("k_corr2": the one-wave-per-SIMD
  * form of dg_corr2.hip, "k_corr_main": the general form), decided by the same predicate the launch uses; NULL on a bad desc. */
 const char* dg_corr_main_kernel_name(const dg_corr_desc* desc);
