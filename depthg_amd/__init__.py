@@ -28,6 +28,8 @@ Public surface (mirrors the reference's Python operator surface for this path):
                                  k_lin_fwd (cfg.dg_fused_linear)
     featurizer / DinoFeaturizer  src/modules.py:19-137: frozen ViT + the fused projection head (cfg.dg_dino_backbone in the segmenter);
                                  DinoFeaturizerWithDepth (:490-631, cfg.arch "dino_depth"): depth-guided features in front of the head
+    cross_attn                   the depth guidance's nn.MultiheadAttention core (src/modules.py:524, :566-585) as a fused HIP forward
+                                 and backward with Philox dropout (cfg.dg_fused_cross_attn)
     ops                          thin ctypes binding of the C ABI in include/depthg_corr.h
 """
 from .loss import ContrastiveCorrelationLoss  # noqa: F401
@@ -38,6 +40,8 @@ from .aug_loss import aug_alignment_loss, crop_flip_coords  # noqa: F401
 from . import rec_loss  # noqa: F401
 from .rec_loss import reconstruction_loss  # noqa: F401
 from .depth_encoder import depth_encoder  # noqa: F401
+from . import cross_attn  # noqa: F401
+from .cross_attn import cross_attention, multihead_cross_attention  # noqa: F401
 from . import depth_decay  # noqa: F401
 from . import training  # noqa: F401
 from . import metrics  # noqa: F401
@@ -54,6 +58,6 @@ from . import featurizer  # noqa: F401
 from .featurizer import DinoFeaturizer, DinoFeaturizerWithDepth  # noqa: F401
 from . import segmenter  # noqa: F401
 
-__all__ = ["ContrastiveCorrelationLoss", "ContrastiveCRFLoss", "crf_loss", "aug_loss", "aug_alignment_loss", "crop_flip_coords", "rec_loss", "reconstruction_loss", "depth_encoder", "depth_decay", "training", "metrics", "evaluation", "predict_and_score", "crf", "dense_crf",
+__all__ = ["ContrastiveCorrelationLoss", "ContrastiveCRFLoss", "crf_loss", "aug_loss", "aug_alignment_loss", "crop_flip_coords", "rec_loss", "reconstruction_loss", "depth_encoder", "cross_attn", "cross_attention", "multihead_cross_attention", "depth_decay", "training", "metrics", "evaluation", "predict_and_score", "crf", "dense_crf",
            "batched_crf", "knn", "lhp", "optim", "FusedAdam", "FusedAdamSet", "segmenter", "vit", "featurizer",
            "DinoFeaturizer", "DinoFeaturizerWithDepth"]

@@ -124,6 +124,11 @@ SIGNATURES = {
     "dg_depthenc_workspace_bytes": (_SZ, [i32] * 5),
     "dg_depthenc_forward": (_I, [vp] * 12 + [i32] * 8 + [vp, vp, _SZ, vp]),
     "dg_depthenc_backward": (_I, [vp] * 12 + [i32] * 6 + [vp] * 11 + [_SZ, vp]),
+    # depth guidance: fused cross-attention
+    "dg_xattn_workspace_bytes": (_SZ, [i32] * 5),
+    "dg_xattn_forward": (_I, [vp] * 3 + [i32] * 5 + [f32, f32, u64, vp, vp, vp, _SZ, vp]),
+    "dg_xattn_backward": (_I, [vp] * 6 + [i32] * 5 + [f32, f32, u64, vp, vp, vp, vp, _SZ, vp]),
+    "dg_xattn_keep_mask": (_I, [u64] + [i32] * 4 + [f32, vp, vp]),
     # measurement aids
     "dg_corr_main_kernel_name": (_STR, [cp]),
     "dg_corr_intra_folded": (_I, [cp]),

@@ -1,5 +1,5 @@
 // C ABI of the gfx950 DepthG library (include/depthg_corr.h), the units' shared state and the small subsystems: version and error
-// text, the library's side stream, batch maps / random draws / coordinate samplers, kNN, LHP, fused Adam, ViT attention and linear, the fused depth encoder.  (The auxiliary loss terms: dg_api_loss.hip.)
+// text, the library's side stream, batch maps / random draws / coordinate samplers, kNN, LHP, fused Adam, ViT attention and linear, the fused depth encoder, the depth guidance's cross-attention.  (The auxiliary loss terms: dg_api_loss.hip.)
 // Host-side only: argument checks and kernel launches on the caller's stream.
 #include "dg_api.h"
 #include "dg_aux_args.h"
@@ -389,5 +389,79 @@ extern "C" int dg_depthenc_backward(const float* depth, const float* w1, const f
     A.d_w1 = grad_w1; A.d_b1 = grad_b1; A.d_g1 = grad_gamma1; A.d_be1 = grad_beta1; A.d_w2 = grad_w2; A.d_b2 = grad_b2; A.d_g2 = grad_gamma2;
     A.d_be2 = grad_beta2; A.d_w3 = grad_w3; A.d_b3 = grad_b3;
     DG_HIP(dg_launch_depthenc_backward(A, static_cast<hipStream_t>(stream_)));
+    return DG_OK;
+}
+
+// ---- fused cross-attention of the depth guidance (dg_xattn.hip)
+static bool xattn_supported(int32_t B, int32_t heads, int32_t Nq, int32_t Nk) {
+    return B >= 1 && heads >= 1 && Nq >= 1 && Nk >= 1 && Nq <= (1 << 24) && Nk <= (1 << 24) && (long long)B * heads <= 65535;
+}
+
+// what every entry refuses before it looks at a pointer
+static int xattn_check(const char* who, int32_t B, int32_t heads, int32_t Nq, int32_t Nk, int32_t head_dim, float scale, float p) {
+    if (head_dim != DG_XATTN_HD) return fail(DG_ERR_UNSUPPORTED, "%s: head_dim=%d (the kernels are built for %d)", who, head_dim, DG_XATTN_HD);
+    if (B < 1 || heads < 1 || Nq < 1 || Nk < 1 || Nq > (1 << 24) || Nk > (1 << 24))
+        return fail(DG_ERR_INVALID, "%s: B=%d heads=%d Nq=%d Nk=%d (all >= 1, Nq and Nk up to 2^24)", who, B, heads, Nq, Nk);
+    if ((long long)B * heads > 65535) return fail(DG_ERR_UNSUPPORTED, "%s: B * heads = %lld above 65535", who, (long long)B * heads);
+    if (!(p >= 0.f && p < 1.f)) return fail(DG_ERR_INVALID, "%s: dropout p=%g outside [0, 1)", who, (double)p);
+    if (!(scale == scale) || std::isinf(scale)) return fail(DG_ERR_INVALID, "%s: scale=%g", who, (double)scale);
+    return DG_OK;
+}
+
+static uint32_t xattn_threshold(float p) {            // keep iff word >= floor(p 2^32); 0 exactly when p == 0 for every p this library meets
+    const double t = std::floor((double)p * 4294967296.0);
+    return t >= 4294967295.0 ? 0xffffffffu : (uint32_t)t;
+}
+
+extern "C" size_t dg_xattn_workspace_bytes(int32_t B, int32_t heads, int32_t Nq, int32_t Nk, int32_t backward) {
+    if (!xattn_supported(B, heads, Nq, Nk)) return 0;
+    return dg_xattn_ws(B, heads, Nq, Nk, backward != 0).total;
+}
+
+extern "C" int dg_xattn_forward(const float* q, const float* k, const float* v, int32_t B, int32_t heads, int32_t Nq, int32_t Nk,
+                                int32_t head_dim, float scale, float p, uint64_t seed, float* out, float* lse, void* workspace,
+                                size_t workspace_bytes, dg_stream_t stream_) {
+    if (int rc = xattn_check(__func__, B, heads, Nq, Nk, head_dim, scale, p)) return rc;
+    if (!q || !k || !v || !out || !workspace) return fail(DG_ERR_INVALID, "dg_xattn_forward: null pointer");
+    if (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)out | (uintptr_t)workspace) & 15)
+        return fail(DG_ERR_INVALID, "dg_xattn_forward: q, k, v, out and workspace must be 16-byte aligned");
+    if ((uintptr_t)lse & 3) return fail(DG_ERR_INVALID, "dg_xattn_forward: lse must be 4-byte aligned");
+    if (int rc = check_workspace(__func__, workspace_bytes, dg_xattn_ws(B, heads, Nq, Nk, false).total, "dg_xattn_workspace_bytes")) return rc;
+    DgXattnArgs A;
+    memset(&A, 0, sizeof(A));
+    A.q = q; A.k = k; A.v = v; A.out_w = out; A.lse_w = lse; A.workspace = workspace;
+    A.B = B; A.heads = heads; A.Nq = Nq; A.Nk = Nk; A.scale = scale; A.seed = seed;
+    A.thr = xattn_threshold(p); A.inv_keep = 1.f / (1.f - p);
+    DG_HIP(dg_launch_xattn_forward(A, static_cast<hipStream_t>(stream_)));
+    return DG_OK;
+}
+
+extern "C" int dg_xattn_backward(const float* q, const float* k, const float* v, const float* out, const float* lse, const float* grad_out,
+                                 int32_t B, int32_t heads, int32_t Nq, int32_t Nk, int32_t head_dim, float scale, float p, uint64_t seed,
+                                 float* grad_q, float* grad_k, float* grad_v, void* workspace, size_t workspace_bytes, dg_stream_t stream_) {
+    if (int rc = xattn_check(__func__, B, heads, Nq, Nk, head_dim, scale, p)) return rc;
+    if (!q || !k || !v || !out || !lse || !grad_out || !workspace) return fail(DG_ERR_INVALID, "dg_xattn_backward: null pointer");
+    if (!grad_k != !grad_v) return fail(DG_ERR_INVALID, "dg_xattn_backward: grad_k and grad_v come from one kernel: give both or neither");
+    if (!grad_q && !grad_k) return fail(DG_ERR_INVALID, "dg_xattn_backward: no gradient asked for");
+    if (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)out | (uintptr_t)grad_out | (uintptr_t)grad_q | (uintptr_t)grad_k |
+         (uintptr_t)grad_v | (uintptr_t)workspace) & 15)
+        return fail(DG_ERR_INVALID, "dg_xattn_backward: the tensors, the gradients and workspace must be 16-byte aligned");
+    if ((uintptr_t)lse & 3) return fail(DG_ERR_INVALID, "dg_xattn_backward: lse must be 4-byte aligned");
+    if (int rc = check_workspace(__func__, workspace_bytes, dg_xattn_ws(B, heads, Nq, Nk, true).total, "dg_xattn_workspace_bytes")) return rc;
+    DgXattnArgs A;
+    memset(&A, 0, sizeof(A));
+    A.q = q; A.k = k; A.v = v; A.out = out; A.lse = lse; A.d_out = grad_out; A.d_q = grad_q; A.d_k = grad_k; A.d_v = grad_v;
+    A.workspace = workspace;
+    A.B = B; A.heads = heads; A.Nq = Nq; A.Nk = Nk; A.scale = scale; A.seed = seed;
+    A.thr = xattn_threshold(p); A.inv_keep = 1.f / (1.f - p);
+    DG_HIP(dg_launch_xattn_backward(A, static_cast<hipStream_t>(stream_)));
+    return DG_OK;
+}
+
+extern "C" int dg_xattn_keep_mask(uint64_t seed, int32_t B, int32_t heads, int32_t Nq, int32_t Nk, float p, uint8_t* out,
+                                  dg_stream_t stream_) {
+    if (int rc = xattn_check(__func__, B, heads, Nq, Nk, DG_XATTN_HD, 1.f, p)) return rc;
+    if (!out) return fail(DG_ERR_INVALID, "dg_xattn_keep_mask: null pointer");
+    DG_HIP(dg_launch_xattn_mask(out, B, heads, Nq, Nk, seed, xattn_threshold(p), static_cast<hipStream_t>(stream_)));
     return DG_OK;
 }

@@ -34,6 +34,29 @@ hipError_t dg_launch_adam(const dg_adam_seg* segs, int n_seg, const dg_adam_grou
 size_t dg_attn_workspace(int B, int heads, int N);           // bytes of the packed bf16 K / V images
 hipError_t dg_launch_attention(const float* qkv, float* out, void* ws, int B, int N, int heads, float scale, hipStream_t s);
 
+// ---- fused cross-attention of the depth guidance, forward and backward (dg_xattn.hip; src/modules.py:524, :566-585)
+#define DG_XATTN_HD 48                       // head dimension (384 / 8)
+#define DG_XATTN_IMG 7168                    // bytes of one packed tile of 32 rows: 3 row fragments + 4 transposed ones, 1 KiB each
+struct DgXattnWs {                           // byte offsets of the workspace's sections (multiples of 256)
+    size_t img_k, img_v, img_q, img_do, lse2, di, total;
+    int tiles_q, tiles_k;
+};
+DgXattnWs dg_xattn_ws(int B, int heads, int Nq, int Nk, bool backward);
+struct DgXattnArgs {
+    const float *q, *k, *v;                  // (B, Nq | Nk, heads * 48)
+    const float *out, *lse, *d_out;          // backward: the forward's results and d out
+    float *out_w, *lse_w;                    // forward: O, and the log-sum-exp (B, heads, Nq) or null
+    float *d_q, *d_k, *d_v;                  // backward: d_q may be null, d_k and d_v only together
+    void* workspace;
+    int B, heads, Nq, Nk;
+    float scale, inv_keep;
+    uint64_t seed;
+    uint32_t thr;                            // a key is kept iff its Philox word >= thr; 0: no dropout, no generator work
+};
+hipError_t dg_launch_xattn_forward(const DgXattnArgs& A, hipStream_t s);
+hipError_t dg_launch_xattn_backward(const DgXattnArgs& A, hipStream_t s);
+hipError_t dg_launch_xattn_mask(uint8_t* out, int B, int heads, int Nq, int Nk, uint64_t seed, uint32_t thr, hipStream_t s);
+
 // ---- fused bf16 linear layers of the frozen ViT (dg_linear.hip; src/dino/vision_transformer.py:49-65, 68-92, 95-115)
 bool dg_linear_supported(int K, int Nout);                   // multiples of 64 up to 3072
 size_t dg_linear_packed_bytes(int K, int Nout);              // 0 when unsupported

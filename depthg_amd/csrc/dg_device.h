@@ -140,6 +140,18 @@ __device__ __forceinline__ uint32_t dg_philox(uint64_t seed, uint32_t ctr) {
     }
     return c0;
 }
+// ... with a full 128-bit counter and all four output words (dg_philox(seed, c) == dg_philox4(seed, c, 0, 0, 0)[0])
+__device__ __forceinline__ u32x4 dg_philox4(uint64_t seed, uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3) {
+    uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
+        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
+        c1 = (uint32_t)p1; c3 = (uint32_t)p0; c0 = n0; c2 = n2;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+    return u32x4{c0, c1, c2, c3};
+}
 
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) is a host round trip of a few microseconds: do it once per kernel (and
 // again only if a larger size is ever needed).  Host threads of different devices may race benignly (same value).

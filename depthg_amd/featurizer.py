@@ -20,7 +20,13 @@ DinoFeaturizerWithDepth (src/modules.py:490-631, cfg.arch "dino_depth"): the sam
 "cross_attn" (`cross_attn`, `no_depth_embed`), "concat" or "none".  The head runs as ever (run_head) with input_grad=True: its
 d image_feat launch (dg_head_backward_input) carries the gradient into the depth modules, which are plain torch - except, with
 cfg.dg_fused_depth_encoder (off by default; n_feats == 384 only), the depth encoder: one fused HIP forward and backward
-(depth_encoder.py, dg_depth_enc.hip), the "sum" guidance's add in its epilogue.  DepthGuidance is the
+(depth_encoder.py, dg_depth_enc.hip), the "sum" guidance's add in its epilogue - and, with cfg.dg_fused_cross_attn (off by
+default; n_feats == 384 only), the core of the "cross_attn" guidance's attention (cross_attn.py, dg_xattn.hip): `cross_attn` stays
+the reference's nn.MultiheadAttention (same parameters, state dict and initial values), its projections run as F.linear, and the
+softmax(q k^T) v between them, with its dropout, is one fused HIP forward and backward.  With that flag on, the attention dropout's
+mask is a Philox function of a seed drawn from torch's CPU generator, not a draw from torch's GPU stream: the head's Dropout2d draws
+no longer sit behind it.  The seed is a kernel argument, so a captured graph replays the mask it was captured with; a
+device-resident generator state for it is out of scope.  DepthGuidance is the
 guidance logic as a mixin over any FrozenBackboneFeaturizer (segmenter.StandInFeaturizerWithDepth is the stand-in variant).
 Differences from the reference:
     concat      the reference's training branch is `pass` (:564-565) and leaves image_depth_feat unbound; here "concat" is "none".
@@ -38,6 +44,7 @@ import torch
 import torch.nn as nn
 
 from . import vit
+from .cross_attn import check_module, multihead_cross_attention
 from .depth_encoder import depth_encoder
 from .head import ProjectionHead, run_head, run_head_pair
 
@@ -140,6 +147,12 @@ class DepthGuidance:
         if self.fused_depth_encoder and self.n_feats != 384:
             raise ValueError(f"depthg_amd: cfg.dg_fused_depth_encoder fuses the three-stage depth encoder of n_feats == 384; this backbone "
                              f"has n_feats = {self.n_feats}, whose five-stage stack stays on the torch route: leave the flag off")
+        self.fused_cross_attn = bool(getattr(cfg, "dg_fused_cross_attn", False))
+        if self.fused_cross_attn:
+            if self.n_feats != 384:
+                raise ValueError(f"depthg_amd: cfg.dg_fused_cross_attn fuses the 8-heads-of-48 attention of n_feats == 384; this backbone has "
+                                 f"n_feats = {self.n_feats} (head dimension {self.n_feats / 8:g}), which stays on the torch route: leave the flag off")
+            check_module(self.cross_attn)
         frozen = {"none": (self.depth_downscaling, self.cross_attn, self.no_depth_embed),
                   "concat": (self.depth_downscaling, self.cross_attn, self.no_depth_embed),
                   "sum": (self.cross_attn, self.no_depth_embed),
@@ -190,6 +203,10 @@ class DepthGuidance:
         B, C = image_feat.shape[:2]
         if self.training and self.guidance == "sum":                            # :562-563
             image_depth_feat = self._depth_feats(depth, image_feat, image_feat)    # (fused: the add runs in the kernel's epilogue)
+        elif self.training and self.guidance == "cross_attn" and self.fused_cross_attn:
+            image_depth_feat = multihead_cross_attention(self.cross_attn, self._depth_feats(depth, image_feat), image_feat, True)
+        elif self.guidance == "cross_attn" and self.fused_cross_attn:
+            image_depth_feat = multihead_cross_attention(self.cross_attn, self.no_depth_embed.weight, image_feat, False)
         elif self.training and self.guidance == "cross_attn":                   # :566-575
             image_depth_feat = self._cross_attend(self._depth_feats(depth, image_feat).reshape(B, C, -1).permute(2, 0, 1), image_feat)
         elif self.guidance == "cross_attn":                                     # :576-585: no depth at evaluation, a learned query

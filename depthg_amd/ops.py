@@ -1278,3 +1278,106 @@ def vit_linear_forward(x, packed, n_out, bias=None, *, ln_weight=None, ln_bias=N
                                    M, K, n_out, flags, _stream(dev))
     _lib.check(rc, "dg_vit_linear_forward")
     return out
+
+
+XATTN_HEAD_DIM = 48       # head dimension of the fused cross-attention (384 / 8: the depth guidance's nn.MultiheadAttention)
+
+
+def _xattn_operands(who, q, k, v, heads, extra=()):
+    """Shapes, dtype and contiguity first (they hold on any device), then the device, then the alignment -> (B, Nq, Nk)."""
+    heads = int(heads)
+    if q.dim() != 3 or k.dim() != 3 or heads < 1 or q.shape[2] != heads * XATTN_HEAD_DIM:
+        raise ValueError(f"depthg_amd: {who}: q must be (B, Nq, heads * {XATTN_HEAD_DIM}) with heads={heads}, got {tuple(q.shape)}")
+    if k.shape[0] != q.shape[0] or k.shape[2] != q.shape[2] or v.shape != k.shape:
+        raise ValueError(f"depthg_amd: {who}: k and v must be (B, Nk, heads * {XATTN_HEAD_DIM}) like q {tuple(q.shape)}, got {tuple(k.shape)} "
+                         f"and {tuple(v.shape)}")
+    B, Nq, Nk = q.shape[0], q.shape[1], k.shape[1]
+    if B < 1 or Nq < 1 or Nk < 1:
+        raise ValueError(f"depthg_amd: {who}: needs at least one query and one key, got q {tuple(q.shape)}, k {tuple(k.shape)}")
+    named = [("q", q, q.shape), ("k", k, k.shape), ("v", v, k.shape)] + list(extra)
+    for name, t, shape in named:
+        if tuple(t.shape) != tuple(shape):
+            raise ValueError(f"depthg_amd: {who}: `{name}` must be {tuple(shape)}, got {tuple(t.shape)}")
+        if t.dtype != torch.float32:
+            raise ValueError(f"depthg_amd: {who}: `{name}` must be float32, got {t.dtype}")
+        if not t.is_contiguous():
+            raise ValueError(f"depthg_amd: {who}: `{name}` must be contiguous (strides {t.stride()})")
+    for name, t, _ in named:
+        _on_gpu(t, name)
+        if t.device != q.device:
+            raise RuntimeError(f"depthg_amd: {who}: `{name}` lives on {t.device}, q on {q.device}")
+    for name, t, _ in named:
+        if t.data_ptr() & (3 if name == "lse" else 15):       # (a slice of a larger buffer can start anywhere; the kernels use 128-bit accesses)
+            raise ValueError(f"depthg_amd: {who}: `{name}` must start at a 16-byte aligned address")
+    return B, Nq, Nk
+
+
+def _xattn_p(p):
+    p = float(p)
+    if not 0.0 <= p < 1.0:
+        raise ValueError(f"depthg_amd: the attention dropout probability must be in [0, 1), got {p}")
+    return p
+
+
+def _xattn_workspace(lib, B, heads, Nq, Nk, backward, dev):
+    need = lib.dg_xattn_workspace_bytes(B, heads, Nq, Nk, int(backward))
+    if need == 0:
+        raise ValueError(f"depthg_amd: no cross-attention plan for B={B}, heads={heads}, Nq={Nq}, Nk={Nk} (B * heads <= 65535, "
+                         "Nq and Nk up to 2^24)")
+    return _empty((need,), torch.uint8, dev), need
+
+
+def xattn_forward(q, k, v, heads, p=0.0, seed=0, scale=None, want_lse=False):
+    """dropout_p(softmax(q k^T * scale)) v per (batch, head) without the (B, heads, Nq, Nk) matrix (dg_xattn_forward): q (B, Nq,
+    heads * 48), k and v (B, Nk, heads * 48), fp32 contiguous on the GPU -> (out (B, Nq, heads * 48), lse (B, heads, Nq) or None).
+    scale: None = 48 ** -0.5.  p: dropout probability in [0, 1), the mask a Philox function of (seed, b, head, query, key) -
+    xattn_keep_mask shows it.  want_lse: also write the per-row log-sum-exp, all xattn_backward needs beside `out`.  bf16 MFMA
+    operands, fp32 softmax.  Runs on the caller's current stream."""
+    B, Nq, Nk = _xattn_operands("xattn_forward", q, k, v, heads)
+    heads, p, dev = int(heads), _xattn_p(p), q.device
+    out = _empty((B, Nq, heads * XATTN_HEAD_DIM), torch.float32, dev)
+    lse = _empty((B, heads, Nq), torch.float32, dev) if want_lse else None
+    lib = _lib.load()
+    ws, need = _xattn_workspace(lib, B, heads, Nq, Nk, False, dev)
+    rc = lib.dg_xattn_forward(_ptr(q.detach()), _ptr(k.detach()), _ptr(v.detach()), B, heads, Nq, Nk, XATTN_HEAD_DIM,
+                              float(XATTN_HEAD_DIM ** -0.5 if scale is None else scale), p, int(seed) & (2 ** 64 - 1), _ptr(out), _ptr(lse),
+                              _ptr(ws), need, _stream(dev))
+    _lib.check(rc, "dg_xattn_forward")
+    return out, lse
+
+
+def xattn_backward(q, k, v, out, lse, grad_out, heads, p=0.0, seed=0, scale=None, need=(True, True, True)):
+    """The gradients of xattn_forward (dg_xattn_backward) from its results `out` and `lse` and the same p, seed and scale ->
+    (grad_q, grad_k, grad_v); `need` says which are wanted (None for the rest: grad_q has a kernel of its own, grad_k and grad_v
+    share one).  No atomics: two calls give the same bits; every element of a returned gradient is written."""
+    heads = int(heads)
+    B, Nq, Nk = _xattn_operands("xattn_backward", q, k, v, heads,
+                                [("out", out, q.shape), ("grad_out", grad_out, q.shape), ("lse", lse, (q.shape[0], heads, q.shape[1]))])
+    p, dev = _xattn_p(p), q.device
+    need = tuple(bool(n) for n in need)
+    if not any(need):
+        return None, None, None
+    gq = _empty(tuple(q.shape), torch.float32, dev) if need[0] else None
+    gk = _empty(tuple(k.shape), torch.float32, dev) if need[1] or need[2] else None
+    gv = _empty(tuple(k.shape), torch.float32, dev) if need[1] or need[2] else None
+    lib = _lib.load()
+    ws, nbytes = _xattn_workspace(lib, B, heads, Nq, Nk, True, dev)
+    rc = lib.dg_xattn_backward(_ptr(q.detach()), _ptr(k.detach()), _ptr(v.detach()), _ptr(out.detach()), _ptr(lse), _ptr(grad_out.detach()),
+                               B, heads, Nq, Nk, XATTN_HEAD_DIM, float(XATTN_HEAD_DIM ** -0.5 if scale is None else scale), p,
+                               int(seed) & (2 ** 64 - 1), _ptr(gq), _ptr(gk), _ptr(gv), _ptr(ws), nbytes, _stream(dev))
+    _lib.check(rc, "dg_xattn_backward")
+    return gq, gk if need[1] else None, gv if need[2] else None
+
+
+def xattn_keep_mask(seed, B, heads, Nq, Nk, p, device):
+    """The keep decisions of xattn_forward / xattn_backward for (seed, p) as a uint8 (B, heads, Nq, Nk) tensor (1 = kept): element
+    (b, head, i, j) depends on the seed and its four indices only (include/depthg_corr.h), so a slice does not change with the
+    shape around it."""
+    B, heads, Nq, Nk, p = int(B), int(heads), int(Nq), int(Nk), _xattn_p(p)
+    if min(B, heads, Nq, Nk) < 1:
+        raise ValueError(f"depthg_amd: xattn_keep_mask: B={B}, heads={heads}, Nq={Nq}, Nk={Nk} must be positive")
+    dev = torch.device(device)
+    stream = _stream(dev)
+    out = _empty((B, heads, Nq, Nk), torch.uint8, dev)
+    _lib.check(_lib.load().dg_xattn_keep_mask(int(seed) & (2 ** 64 - 1), B, heads, Nq, Nk, p, _ptr(out), stream), "dg_xattn_keep_mask")
+    return out

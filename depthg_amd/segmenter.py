@@ -461,7 +461,10 @@ def default_segmenter_cfg(**over) -> SimpleNamespace:
         # "sum", "cross_attn", "concat" or "none" (src/modules.py:526-528)
         guidance="none",
         # build-side, arch "dino_depth" with n_feats == 384: the depth encoder as one fused HIP forward and backward (depth_encoder.py)
-        dg_fused_depth_encoder=False)
+        dg_fused_depth_encoder=False,
+        # build-side, the same arch under guidance "cross_attn": the attention core between cross_attn's projections as one fused HIP
+        # forward and backward (cross_attn.py)
+        dg_fused_cross_attn=False)
     for k, v in over.items():
         setattr(cfg, k, v)
     return cfg

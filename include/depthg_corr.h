@@ -836,6 +836,44 @@ int dg_depthenc_backward(const float* depth, const float* w1, const float* b1, c
                          float* grad_gamma2, float* grad_beta2, float* grad_w3, float* grad_b3, void* workspace,
                          size_t workspace_bytes, dg_stream_t stream);
 
+/*
+ * Cross-attention of the depth guidance (src/modules.py:524 `cross_attn = nn.MultiheadAttention(n_feats, 8, dropout=0.1)`, :566-585)
+ * between the three input projections and out_proj, forward and backward, as fused kernels: per (batch, head)
+ *      O = dropout_p(softmax(q k^T * scale)) v
+ * with online softmax; the (B, heads, Nq, Nk) matrix is never written, by the forward or by the backward.
+ *  q : fp32 (B, Nq, heads * 48);  k, v : fp32 (B, Nk, heads * 48);  out, grad_out, grad_q as q;  grad_k, grad_v as k - all contiguous,
+ *      batch-first, 16-byte aligned (DG_ERR_INVALID otherwise)
+ *  head_dim : 48 only - DG_ERR_UNSUPPORTED otherwise, before any launch;  heads, Nq, Nk >= 1 (up to 2^24), B * heads <= 65535
+ *  p : the dropout probability in [0, 1) (DG_ERR_INVALID otherwise); a kept probability is scaled by 1 / (1 - p).  p = 0 launches
+ *      kernels without generator code.  Element (b, head, query i, key j) is kept iff word (j & 3) of
+ *      Philox4x32-10(key = seed, counter = (i, j >> 2, head, b)) >= floor(p * 2^32): a pure function of the seed and the four indices,
+ *      one 32-bit counter word each - no shape, tile or grid enters it, the forward, the backward and dg_xattn_keep_mask form the same
+ *      mask, and no supported shape can wrap the counter (nothing is refused on its account).
+ *  lse : fp32 (B, heads, Nq), the per-row log-sum-exp of the scaled scores (natural logarithm), the only thing the forward saves for
+ *      the backward; NULL in the forward: not written
+ *  workspace : dg_xattn_workspace_bytes(B, heads, Nq, Nk, backward) bytes (0 on bad arguments), 16-byte aligned: k and v (backward:
+ *      and q and grad_out) as bf16 in MFMA fragment order, 7 KiB per (b, head, 32 rows), made by every call; backward: also
+ *      rowsum(grad_out * out) and the log-sum-exp in log2 units, padded to whole tiles.  The backward needs nothing of the forward's.
+ *  forward  : writes EVERY element of out (and of lse)
+ *  backward : `out` and `lse` are the forward's results for the same q, k, v, scale, p and seed.  grad_q may be NULL (its kernel is
+ *      not launched); grad_k and grad_v come from one kernel: both or neither.  Every element of a gradient that is given is written.
+ *      Di = rowsum(dO * O); P re-formed from q, k and lse; dV = Pd^T dO; dS = P * (keep / (1 - p) * (dO V^T) - Di); dQ = scale dS K;
+ *      dK = scale dS^T Q.
+ *  dg_xattn_keep_mask : the keep decisions of (seed, p) as bytes (1 = kept), out uint8 (B, heads, Nq, Nk); all ones for p = 0
+ * Arithmetic: q, k, v and grad_out rounded to bf16 (nearest even), products on v_mfma_f32_32x32x16_bf16 with fp32 accumulation; scores,
+ * running maximum, exponentials, row sums, Di and the dropout scale in fp32; P and dS rounded to bf16 for the products that follow.
+ * No atomics: every output element has one owner that sums in a fixed order, so two calls give the same bits.  No host
+ * synchronisation.  Nothing outside the tensors and the workspace is read or written.
+ */
+size_t dg_xattn_workspace_bytes(int32_t B, int32_t heads, int32_t Nq, int32_t Nk, int32_t backward);
+int dg_xattn_forward(const float* q, const float* k, const float* v, int32_t B, int32_t heads, int32_t Nq, int32_t Nk, int32_t head_dim,
+                     float scale, float p, uint64_t seed, float* out, float* lse, void* workspace, size_t workspace_bytes,
+                     dg_stream_t stream);
+int dg_xattn_backward(const float* q, const float* k, const float* v, const float* out, const float* lse, const float* grad_out,
+                      int32_t B, int32_t heads, int32_t Nq, int32_t Nk, int32_t head_dim, float scale, float p, uint64_t seed,
+                      float* grad_q, float* grad_k, float* grad_v, void* workspace, size_t workspace_bytes, dg_stream_t stream);
+int dg_xattn_keep_mask(uint64_t seed, int32_t B, int32_t heads, int32_t Nq, int32_t Nk, float p, uint8_t* out, dg_stream_t stream);
+
 /* Measurement aid: name of the kernel the fused correlation launch of this descriptor runs ("k_corr2": the one-wave-per-SIMD
  * form of dg_corr2.hip, "k_corr_main": the general form), decided by the same predicate the launch uses; NULL on a bad desc. */
 const char* dg_corr_main_kernel_name(const dg_corr_desc* desc);
