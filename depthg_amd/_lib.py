@@ -88,6 +88,8 @@ SIGNATURES = {
     "dg_head_input_workspace_bytes": (_SZ, [i32] * 2),
     "dg_head_backward_input": (_I, [i32] * 4 + [vp] * 4 + [f32] + [vp] * 3 + [_SZ, vp, vp, _SZ, vp]),
     "dg_head_backward_input_pair": (_I, [i32] * 4 + [vp] * 4 + [f32] + [vp] * 4 + [_SZ, vp, vp, vp, _SZ, vp]),
+    "dg_head_backward_input_add": (_I, [i32] * 4 + [vp] * 5 + [f32] + [vp] * 4 + [_SZ, vp, vp, _SZ, vp]),
+    "dg_head_backward_input_add_pair": (_I, [i32] * 4 + [vp] * 5 + [f32] + [vp] * 6 + [_SZ, vp, vp, vp, _SZ, vp]),
     "dg_head_plan_describe": (_I, [i32] * 4 + [vp]),
     "dg_cluster_lookup_forward": (_I, [vp, vp, f32] + [i32] * 4 + [vp] * 6),
     "dg_cluster_lookup_backward": (_I, [vp, vp, vp, f32, vp] + [i32] * 4 + [vp] * 4),
@@ -112,6 +114,7 @@ SIGNATURES = {
     "dg_recloss_workspace_bytes": (_SZ, [i32] * 5),
     "dg_recloss_forward": (_I, [vp] * 5 + [f32] + [i32] * 5 + [vp, _SZ, vp, vp]),
     "dg_recloss_backward": (_I, [vp] * 5 + [f32, vp, _SZ] + [i32] * 5 + [vp] * 5),
+    "dg_rec_feats_backward": (_I, [vp] * 5 + [f32, vp, _SZ] + [i32] * 5 + [vp] * 6),
     # optimiser
     "dg_adam_step": (_I, [ctypes.POINTER(AdamSeg), i32, ctypes.POINTER(AdamGroup), i32, i32, vp, vp]),
     # frozen ViT

@@ -181,8 +181,13 @@ extern "C" size_t dg_head_input_workspace_bytes(int32_t C, int32_t D) {
 static int head_backward_input_impl(int32_t B, int32_t Bs, int32_t C, int32_t D, int32_t P, const float* w1, const float* w2a, const float* keep1,
                                     const float* keep2, float keep_scale, const void* hidden, const float* grad_code, const float* grad_code2,
                                     const void* workspace, size_t workspace_bytes, float* grad_feat, float* grad_feat2,
-                                    void* input_workspace, size_t input_workspace_bytes, dg_stream_t stream_) {
+                                    void* input_workspace, size_t input_workspace_bytes, dg_stream_t stream_,
+                                    const float* keep3 = nullptr, const float* grad_feats_out = nullptr, const float* grad_feats_out2 = nullptr) {
     if (int rc = head_check(B, C, D, P)) return rc;
+    if ((((uintptr_t)grad_feats_out | (uintptr_t)grad_feats_out2) & 15) || ((uintptr_t)keep3 & 3))
+        return fail(DG_ERR_INVALID, "grad_feats_out must be 16-byte aligned, keep3 4-byte aligned");
+    if ((grad_feats_out && !grad_feat) || (grad_feats_out2 && !grad_feat2))
+        return fail(DG_ERR_INVALID, "grad_feats_out of a pass whose grad_feat is null");
     if (!w1 || !grad_code || !input_workspace) return fail(DG_ERR_INVALID, "null pointer");
     if (Bs < B ? (!grad_code2 || (!grad_feat && !grad_feat2)) : !grad_feat) return fail(DG_ERR_INVALID, "null pointer (grad_code of both passes, grad_feat of one at least)");
     const bool nonlinear = w2a != nullptr;
@@ -205,6 +210,7 @@ static int head_backward_input_impl(int32_t B, int32_t Bs, int32_t C, int32_t D,
     a.b0 = grad_feat ? 0 : Bs;                            // (a pass without grad_feat: its images are not walked)
     a.nb = (Bs < B && grad_feat && grad_feat2) ? B : Bs;
     a.step_major = (nonlinear && h.step_major) ? 1 : 0;
+    a.gfeats = grad_feats_out; a.gfeats2 = grad_feats_out2; a.keep3 = keep3;
     DG_HIP(dg_launch_head_dx(a, s));
     return DG_OK;
 }
@@ -224,4 +230,26 @@ extern "C" int dg_head_backward_input_pair(int32_t B, int32_t C, int32_t D, int3
     if (B < 1 || B > (1 << 20)) return fail(DG_ERR_INVALID, "bad head dimensions");
     return head_backward_input_impl(2 * B, B, C, D, P, w1, w2a, keep1, keep2, keep_scale, hidden, grad_code, grad_code_pos, workspace,
                                     workspace_bytes, grad_feat, grad_feat_pos, input_workspace, input_workspace_bytes, stream_);
+}
+
+// ---- d image_feat plus what reached the returned feats: grad_feat += keep_scale keep3 grad_feats_out, in the launch's epilogue
+extern "C" int dg_head_backward_input_add(int32_t B, int32_t C, int32_t D, int32_t P, const float* w1, const float* w2a, const float* keep1,
+                                          const float* keep2, const float* keep3, float keep_scale, const void* hidden,
+                                          const float* grad_code, const float* grad_feats_out, const void* workspace,
+                                          size_t workspace_bytes, float* grad_feat, void* input_workspace, size_t input_workspace_bytes,
+                                          dg_stream_t stream_) {
+    return head_backward_input_impl(B, B, C, D, P, w1, w2a, keep1, keep2, keep_scale, hidden, grad_code, nullptr, workspace, workspace_bytes,
+                                    grad_feat, nullptr, input_workspace, input_workspace_bytes, stream_, keep3, grad_feats_out, nullptr);
+}
+
+extern "C" int dg_head_backward_input_add_pair(int32_t B, int32_t C, int32_t D, int32_t P, const float* w1, const float* w2a,
+                                               const float* keep1, const float* keep2, const float* keep3, float keep_scale,
+                                               const void* hidden, const float* grad_code, const float* grad_code_pos,
+                                               const float* grad_feats_out, const float* grad_feats_out_pos, const void* workspace,
+                                               size_t workspace_bytes, float* grad_feat, float* grad_feat_pos, void* input_workspace,
+                                               size_t input_workspace_bytes, dg_stream_t stream_) {
+    if (B < 1 || B > (1 << 20)) return fail(DG_ERR_INVALID, "bad head dimensions");
+    return head_backward_input_impl(2 * B, B, C, D, P, w1, w2a, keep1, keep2, keep_scale, hidden, grad_code, grad_code_pos, workspace,
+                                    workspace_bytes, grad_feat, grad_feat_pos, input_workspace, input_workspace_bytes, stream_, keep3,
+                                    grad_feats_out, grad_feats_out_pos);
 }

@@ -183,3 +183,22 @@ extern "C" int dg_recloss_backward(const float* code, const float* feats, const 
     DG_HIP(dg_launch_rec_backward(A, static_cast<hipStream_t>(stream_)));
     return DG_OK;
 }
+
+// the backward with d feats: everything in one call; grad_code, grad_weight and grad_bias are given or null together
+extern "C" int dg_rec_feats_backward(const float* code, const float* feats, const float* weight, const float* bias, const float* keep,
+                                     float scale, void* workspace, size_t workspace_bytes, int32_t B, int32_t D, int32_t C, int32_t h,
+                                     int32_t w, const float* grad_out, float* grad_code, float* grad_weight, float* grad_bias,
+                                     float* grad_feats, dg_stream_t stream_) {
+    if (int rc = rec_check(__func__, B, D, C, h, w)) return rc;
+    if (!code || !feats || !weight || !bias || !workspace || !grad_out || !grad_feats)
+        return fail(DG_ERR_INVALID, "dg_rec_feats_backward: null pointer");
+    if ((grad_code != nullptr) != (grad_weight != nullptr) || (grad_code != nullptr) != (grad_bias != nullptr))
+        return fail(DG_ERR_INVALID, "dg_rec_feats_backward: grad_code, grad_weight and grad_bias are given together or null together");
+    if (keep && !(scale > 0.f && !std::isinf(scale))) return fail(DG_ERR_INVALID, "dg_rec_feats_backward: keep scale=%g must be positive and finite", (double)scale);
+    if (int rc = check_aligned(__func__, {code, feats, weight, bias, keep, grad_out, grad_code, grad_weight, grad_bias, grad_feats}, workspace)) return rc;
+    if (int rc = check_workspace(__func__, workspace_bytes, dg_rec_ws(B, D, C, h, w).total, "dg_recloss_workspace_bytes")) return rc;
+    DgRecArgs A = rec_args(code, feats, weight, bias, keep, scale, workspace, B, D, C, h, w);
+    A.grad_out = grad_out; A.grad_code = grad_code; A.grad_weight = grad_weight; A.grad_bias = grad_bias; A.grad_feats = grad_feats;
+    DG_HIP(dg_launch_rec_backward_feats(A, static_cast<hipStream_t>(stream_)));
+    return DG_OK;
+}

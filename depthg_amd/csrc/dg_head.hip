@@ -1454,6 +1454,8 @@ hipError_t dg_launch_head_rowsum(const void* X, bool bf16, float* out, float* ou
 // accumulator holds four consecutive positions of one channel - one 16-byte store, 64 contiguous bytes per channel and quarter wave.
 // Dropout2d as in the forward: a dropped channel is a zeroed weight COLUMN here (the lane's own channel: one mask word per lane), so
 // it comes out as exact 0; 1/(1-p) scales the accumulator.  Every element is written once, by one lane: no atomics.
+// ADD (dg_head_backward_input_add): the epilogue adds s keep3[b][k] gfeats[b][k][p] - the gradient that reached the head's returned
+// feats = Dropout2d(image_feat) - to the element it is about to store; a pass without gfeats adds nothing.
 __global__ __launch_bounds__(256) void k_head_dx_prep(const float* __restrict__ w1, const float* __restrict__ w2a, __bf16* __restrict__ out,
                                                       int C, int D, int KS1, int KS, size_t n) {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
@@ -1478,7 +1480,7 @@ hipError_t dg_launch_head_dx_prep(const float* w1, const float* w2a, void* wT, i
 }
 
 // MB: 16-channel blocks of image_feat per wave and pass (four waves; C > 384 takes two passes over the LDS image)
-template <int MB>
+template <int MB, bool ADD>
 __global__ __launch_bounds__(256, 2) void k_head_dx(const DgHeadDxArgs a) {
     constexpr int NT = 64, FROW = NT * 2 + 32;
     extern __shared__ __attribute__((aligned(16))) char dx_sm[];       // [32 (KS1 + KS2)][FROW]: g rows (D padded to 32 KS1), then dh rows
@@ -1538,6 +1540,11 @@ __global__ __launch_bounds__(256, 2) void k_head_dx(const DgHeadDxArgs a) {
     const int KSW = KS;                                                 // k-steps per 16-row block of the weight copy
     const int npass = (C + 64 * MB - 1) / (64 * MB);
     float* const out = b < a.Bs ? a.dx + (size_t)b * C * P : a.dx2 + (size_t)(b - a.Bs) * C * P;
+    const float* addp = nullptr;                                        // this image's gradient of feats_out, or null (block-uniform)
+    if constexpr (ADD) {
+        const float* const base = b < a.Bs ? a.gfeats : a.gfeats2;
+        if (base) addp = base + (size_t)(b < a.Bs ? b : b - a.Bs) * C * P;
+    }
     for (int ps = 0; ps < npass; ++ps) {
         const int rb0 = (ps * 4 + wid) * MB;
         unsigned m1[MB], m2[MB];
@@ -1587,10 +1594,23 @@ __global__ __launch_bounds__(256, 2) void k_head_dx(const DgHeadDxArgs a) {
         for (int j = 0; j < MB; ++j) {
             const int k = 16 * (rb0 + j) + c16;
             if (k < C) {
+                float m3 = 0.f;                                         // (keep3 ? scale : 0) of the lane's channel; no mask: 1
+                if constexpr (ADD) {
+                    if (addp) m3 = a.keep3 ? (a.keep3[(size_t)b * C + k] != 0.f ? a.scale : 0.f) : 1.f;
+                }
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
                     const int p = p0 + 16 * i + 4 * g;
-                    const f32x4 v = acc[i][j] * sfin;
+                    f32x4 v = acc[i][j] * sfin;
+                    if constexpr (ADD) {
+                        if (m3 != 0.f) {
+                            if (vec4) { if (p < P) v += *reinterpret_cast<const f32x4*>(addp + (size_t)k * P + p) * m3; }
+                            else {
+#pragma unroll
+                                for (int r = 0; r < 4; ++r) if (p + r < P) v[r] += addp[(size_t)k * P + p + r] * m3;
+                            }
+                        }
+                    }
                     if (vec4) { if (p < P) *reinterpret_cast<f32x4*>(out + (size_t)k * P + p) = v; }
                     else {
 #pragma unroll
@@ -1602,22 +1622,27 @@ __global__ __launch_bounds__(256, 2) void k_head_dx(const DgHeadDxArgs a) {
     }
 }
 
-template <int MB>
+template <int MB, bool ADD>
 static hipError_t launch_head_dx(const DgHeadDxArgs& a, hipStream_t s) {
     const DgHeadDxLayout L(a.C, a.D, a.dh != nullptr);
     const int smem = 32 * (L.KS1 + L.KS2) * (64 * 2 + 32);
-    hipError_t e = dg_set_max_smem(reinterpret_cast<const void*>(k_head_dx<MB>), smem);
+    hipError_t e = dg_set_max_smem(reinterpret_cast<const void*>(k_head_dx<MB, ADD>), smem);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_head_dx<MB>, dim3((a.P + 63) / 64, a.nb), dim3(256), smem, s, a);
+    hipLaunchKernelGGL((k_head_dx<MB, ADD>), dim3((a.P + 63) / 64, a.nb), dim3(256), smem, s, a);
     return hipGetLastError();
+}
+template <bool ADD>
+static hipError_t launch_head_dx_by_width(const DgHeadDxArgs& a, hipStream_t s) {
+    switch (dg_head_dx_mb(a.C)) {
+        case 1: return launch_head_dx<1, ADD>(a, s);
+        case 2: return launch_head_dx<2, ADD>(a, s);
+        case 3: return launch_head_dx<3, ADD>(a, s);
+        case 4: return launch_head_dx<4, ADD>(a, s);
+        default: return launch_head_dx<6, ADD>(a, s);
+    }
 }
 hipError_t dg_launch_head_dx(const DgHeadDxArgs& a, hipStream_t s) {
     if (a.nb < 1 || a.b0 < 0 || a.b0 + a.nb > a.B || a.C > 768 || a.D > 128) return hipErrorInvalidValue;
-    switch (dg_head_dx_mb(a.C)) {
-        case 1: return launch_head_dx<1>(a, s);
-        case 2: return launch_head_dx<2>(a, s);
-        case 3: return launch_head_dx<3>(a, s);
-        case 4: return launch_head_dx<4>(a, s);
-        default: return launch_head_dx<6>(a, s);
-    }
+    // (the epilogue addend is its own instantiation: without gfeats the kernel is the one it was)
+    return (a.gfeats || a.gfeats2) ? launch_head_dx_by_width<true>(a, s) : launch_head_dx_by_width<false>(a, s);
 }

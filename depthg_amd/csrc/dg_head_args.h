@@ -114,6 +114,9 @@ struct DgHeadDxArgs {
     int32_t Bs; long long d_gcode;   // (pair: images Bs.. of gcode in a second tensor, as DgHeadFwdArgs)
     int32_t b0, nb;                  // the images this launch computes: b0 .. b0 + nb - 1
     int32_t step_major;              // layout of dh (DgHeadDhArgs.step_major)
+    // the epilogue addend (k_head_dx<MB, true>; last: the other fields keep their offsets): d loss / d feats_out (Bs,C,P) per pass, either
+    // null, and the (B,C) keep flags of that Dropout2d (null: no mask); dx += scale keep3 gfeats
+    const float* gfeats; const float* gfeats2; const float* keep3;
 };
 hipError_t dg_launch_head_dx_prep(const float* w1, const float* w2a, void* wT, int C, int D, hipStream_t s);
 hipError_t dg_launch_head_dx(const DgHeadDxArgs& a, hipStream_t s);

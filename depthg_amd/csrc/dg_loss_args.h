@@ -123,7 +123,7 @@ inline DgRecWs dg_rec_ws(int B, int D, int C, int h, int w) {
     ws.total = c.off;
     return ws;
 }
-// One block for the five kernels; forward: the maps, the decoder, ny / nf / s / part, loss; backward: everything but loss.
+// One block for the five kernels; forward: the maps, the decoder, ny / nf / s / part, loss; backward: everything but loss (and grad_feats).
 struct DgRecArgs {
     const float* code; const float* feats; const float* weight; const float* bias; const float* keep;
     float* ny; float* nf; float* s; double* part; float* wpart; float* bpart; float* loss;
@@ -131,6 +131,10 @@ struct DgRecArgs {
     double inv_n;                            // 1 / (B h w), formed on the host
     float scale;
     int B, D, C, P, tiles_per_img, splits;
+    float* grad_feats;                       // d feats (B,C,h,w): dg_launch_rec_backward_feats alone (last: the other fields keep their offsets)
 };
 hipError_t dg_launch_rec_forward(const DgRecArgs& A, hipStream_t s);        // k_rec_forward, k_loss_reduce
-hipError_t dg_launch_rec_backward(const DgRecArgs& A, hipStream_t s);       // k_rec_bwd_code, k_rec_bwd_w, k_rec_combine
+hipError_t dg_launch_rec_backward(const DgRecArgs& A, hipStream_t s);       // k_rec_bwd_code<false>, k_rec_bwd_w, k_rec_combine
+// k_rec_bwd_code<true>: d feats too; with grad_code null (then grad_weight and grad_bias are as well) that launch alone, without its
+// W^T dy product
+hipError_t dg_launch_rec_backward_feats(const DgRecArgs& A, hipStream_t s);

@@ -5,6 +5,8 @@
 //     ny = max(|y|, eps), nf = max(|f|, eps), s = <y, f> / (ny nf), loss = -(1/N) sum s
 //     dy = a f + b y,  a = -(G/N) / (ny nf),  b = (G/N) s / ny^2 where |y| > eps, else 0 (clamp_min passes no gradient below its bound)
 //     d code_p = W^T dy,  d W = sum_p dy c_p^T,  d bias = sum_p dy
+//     d f = a y + b' f,  b' = (G/N) s / nf^2 where |f| > eps, else 0 - dy's mirror image, opt-in (dg_rec_feats_backward): feats is the
+//     frozen backbone's output except under the depth-guided featurizer, whose trained depth modules produced it
 // Neither y, the normalised maps nor dy exist in global memory: every kernel re-forms y for the channels it is at.  The three
 // products run on the fp32 MFMA (v_mfma_f32_32x32x2_f32: fp32 operands, fp32 accumulation, as dg_knn.hip) from LDS: a block holds
 // a tile of 64 positions of code ([d][p], rows of 65 words, zero rows up to the next multiple of 32), one chunk of RC_CHUNK = 64
@@ -19,14 +21,18 @@
 //                   of -s as one double
 //   k_loss_reduce   the tiles' sums -> the loss (fp64, fixed order; dg_loss_reduce.hip)
 //   k_rec_bwd_code  per tile again: y and dy of a chunk -> LDS, then W^T dy of the chunk is added to the wave's accumulator tiles
-//                   (32 rows of d code x 32 positions each) which live through all chunks; every element of d code written
+//                   (32 rows of d code x 32 positions each) which live through all chunks; every element of d code written.
+//                   <true>: the wave also stores d f of the 32 channels x 32 positions whose y, f and factors it holds, from
+//                   its registers in the accumulator layout (an accumulator row is 32 consecutive positions of one channel: 128
+//                   contiguous bytes per half wave), every element of d feats once; without grad_code the W^T dy product is skipped
 //   k_rec_bwd_w     grid (channel chunk, split): the chunk of W staged once, the block walks the tiles split, split + S, ...: dy of
 //                   its 64 channels into LDS, then dy c^T over the tile's 64 positions into accumulator tiles (32 channels x 32 rows
 //                   of d W) that live through all its tiles; one partial of d W / d bias per (split, chunk)
 //   k_rec_combine   the S partials -> d W, d bias (fp64, fixed order); every element written
 // y, dy and the three products are fp32; the forward's three sums over the channels run in fp64 (with fp32 sums a 1024-channel
 // decoder measured 8 x the float32 torch chain's loss error); no atomics; every result is a function of the inputs alone, bit for bit.
-// Dropout2d keep flags (ops.DeferredDropout): f = feats * (keep[b,c] ? scale : 0), the bits of the materialised tensor.
+// Dropout2d keep flags (ops.DeferredDropout): f = feats * (keep[b,c] ? scale : 0), the bits of the materialised tensor; d feats is
+// then the gradient of the un-dropped maps the pointer names: d f times (keep[b,c] ? scale : 0), a dropped channel an exact 0.
 #include "dg_loss_args.h"
 #include "dg_device.h"
 
@@ -134,6 +140,16 @@ __device__ __forceinline__ void rec_factors(const DgRecArgs& A, int b, int p, fl
     }
 }
 
+// b' of d f = a y + b' f at one position; 0 past the image's last position and where |f| <= eps (the rule b follows for |y|)
+__device__ __forceinline__ float rec_factor_f(const DgRecArgs& A, int b, int p) {
+    if (p >= A.P) return 0.f;
+    const size_t r = (size_t)b * A.P + p;
+    const float nf = A.nf[r], s = A.s[r];
+    const float gn = (float)((double)A.grad_out[0] * A.inv_n);
+    const float nfc = fmaxf(nf, DG_EPS_NORM);
+    return nf > DG_EPS_NORM ? gn * s / (nfc * nfc) : 0.f;
+}
+
 // grid B * tiles_per_img, block 256, dynamic LDS dg_rec_lds(D).
 __global__ __launch_bounds__(RC_THREADS) void k_rec_forward(const DgRecArgs A) {
     extern __shared__ float4 rec_smem[];
@@ -187,9 +203,12 @@ __global__ __launch_bounds__(RC_THREADS) void k_rec_forward(const DgRecArgs A) {
     if (lane == 0) A.part[blockIdx.x] = neg;
 }
 
-// dy of the wave's 32 channels x 32 positions of the staged chunk -> dyl[row * RC_LS + position]; 0 for a channel past C
+// dy of the wave's 32 channels x 32 positions of the staged chunk -> dyl[row * RC_LS + position]; 0 for a channel past C.
+// FEATS: d f = (a y + b' f) (keep ? scale : 0) of the same elements -> grad_feats (b: the image, p: the lane's position, fbf: b');
+// channels past C and positions past P are not stored.
+template <bool FEATS>
 __device__ __forceinline__ void rec_dy(const DgRecArgs& A, const RecLds& L, const float (&f)[16], int cb, int ch, int pb, int r, int h,
-                                       float fa, float fb) {
+                                       float fa, float fb, float fbf = 0.f, int b = 0, int p = 0) {
     const int c0 = cb + ch * 32;
     if (c0 < A.C) {
         const f32x16 y = rec_y(L, ch * 32, pb, r, h);
@@ -197,6 +216,13 @@ __device__ __forceinline__ void rec_dy(const DgRecArgs& A, const RecLds& L, cons
         for (int i = 0; i < 16; ++i) {
             const int c = c0 + rec_row(i, h);
             L.dyl[(ch * 32 + rec_row(i, h)) * RC_LS + pb * 32 + r] = c < A.C ? fmaf(fa, f[i], fb * (y[i] + A.bias[c])) : 0.f;
+            if constexpr (FEATS) {
+                if (c < A.C && p < A.P) {
+                    const float m = A.keep ? (A.keep[(size_t)b * A.C + c] != 0.f ? A.scale : 0.f) : 1.f;
+                    const float df = fmaf(fa, y[i] + A.bias[c], fbf * f[i]);
+                    A.grad_feats[((size_t)b * A.C + c) * A.P + p] = m != 0.f ? df * m : 0.f;
+                }
+            }
         }
     } else {
 #pragma unroll
@@ -205,6 +231,8 @@ __device__ __forceinline__ void rec_dy(const DgRecArgs& A, const RecLds& L, cons
 }
 
 // d code (B,D,h,w), every element written.  grid B * tiles_per_img, block 256, dynamic LDS dg_rec_lds(D).
+// FEATS: d feats (B,C,h,w) as well, every element written; grad_code may then be null (no W^T dy product, d code not stored).
+template <bool FEATS>
 __global__ __launch_bounds__(RC_THREADS) void k_rec_bwd_code(const DgRecArgs A) {
     extern __shared__ float4 rec_smem[];
     const RecLds L = rec_lds(reinterpret_cast<float*>(rec_smem), A.D);
@@ -215,6 +243,9 @@ __global__ __launch_bounds__(RC_THREADS) void k_rec_bwd_code(const DgRecArgs A) 
     rec_load_code(A.code, L, t.b, t.p0, A.D, A.P);
     float fa, fb;
     rec_factors(A, t.b, p, fa, fb);
+    float fbf = 0.f;
+    if constexpr (FEATS) fbf = rec_factor_f(A, t.b, p);
+    const bool want_code = !FEATS || A.grad_code != nullptr;   // (block-uniform; a constant without FEATS)
     // the wave's tiles of d code: rows 32 m .. + 31 for m = ch and ch + 2, its 32 positions
     f32x16 acc[2] = {{}, {}};
     for (int cb = 0; cb < A.C; cb += RC_CHUNK) {
@@ -223,8 +254,9 @@ __global__ __launch_bounds__(RC_THREADS) void k_rec_bwd_code(const DgRecArgs A) 
         __syncthreads();
         rec_load_w(A.weight, L, cb, A.C, A.D, wave, lane);
         __syncthreads();
-        rec_dy(A, L, f, cb, ch, pb, r, h, fa, fb);
+        rec_dy<FEATS>(A, L, f, cb, ch, pb, r, h, fa, fb, fbf, t.b, p);
         __syncthreads();
+        if (!want_code) continue;
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
             const int m = ch + 2 * u;
@@ -237,7 +269,7 @@ __global__ __launch_bounds__(RC_THREADS) void k_rec_bwd_code(const DgRecArgs A) 
                 acc[u] = __builtin_amdgcn_mfma_f32_32x32x2f32(wa[k * L.ws], db[k * RC_LS], acc[u], 0, 0, 0);
         }
     }
-    if (p < A.P) {
+    if (want_code && p < A.P) {
 #pragma unroll
         for (int u = 0; u < 2; ++u)
 #pragma unroll
@@ -272,7 +304,7 @@ __global__ __launch_bounds__(RC_THREADS) void k_rec_bwd_w(const DgRecArgs A) {
         __syncthreads();                                        // the last tile's readers are done with both tiles
         rec_load_code(A.code, L, t.b, t.p0, A.D, A.P);
         __syncthreads();
-        rec_dy(A, L, f, cb, ch, pb, r, h, fa, fb);
+        rec_dy<false>(A, L, f, cb, ch, pb, r, h, fa, fb);
         __syncthreads();
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
@@ -332,19 +364,28 @@ hipError_t dg_launch_rec_forward(const DgRecArgs& A, hipStream_t s) {
     return dg_launch_loss_reduce(A.part, tiles, A.inv_n, A.loss, s);
 }
 
-hipError_t dg_launch_rec_backward(const DgRecArgs& A, hipStream_t s) {
+// FEATS: k_rec_bwd_code<true> in place of <false>; params: the d W / d bias launches behind it
+template <bool FEATS>
+static hipError_t rec_backward(const DgRecArgs& A, bool params, hipStream_t s) {
     const int tiles = A.B * A.tiles_per_img, chunks = (A.C + RC_CHUNK - 1) / RC_CHUNK, lds = (int)dg_rec_lds(A.D);
-    hipError_t e = rec_smem_limit(reinterpret_cast<const void*>(k_rec_bwd_code), lds);
+    hipError_t e = rec_smem_limit(reinterpret_cast<const void*>(k_rec_bwd_code<FEATS>), lds);
     if (e != hipSuccess) return e;
     e = rec_smem_limit(reinterpret_cast<const void*>(k_rec_bwd_w), lds);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_rec_bwd_code, dim3(tiles), dim3(RC_THREADS), lds, s, A);
+    hipLaunchKernelGGL(k_rec_bwd_code<FEATS>, dim3(tiles), dim3(RC_THREADS), lds, s, A);
     e = hipGetLastError();
-    if (e != hipSuccess) return e;
+    if (e != hipSuccess || !params) return e;
     hipLaunchKernelGGL(k_rec_bwd_w, dim3(chunks, A.splits), dim3(RC_THREADS), lds, s, A);
     e = hipGetLastError();
     if (e != hipSuccess) return e;
     const size_t outs = (size_t)A.C * A.D + A.C;
     hipLaunchKernelGGL(k_rec_combine, dim3((unsigned)((outs + 255) / 256)), dim3(256), 0, s, A);
     return hipGetLastError();
+}
+
+hipError_t dg_launch_rec_backward(const DgRecArgs& A, hipStream_t s) { return rec_backward<false>(A, true, s); }
+
+hipError_t dg_launch_rec_backward_feats(const DgRecArgs& A, hipStream_t s) {
+    if (!A.grad_feats) return hipErrorInvalidValue;
+    return rec_backward<true>(A, A.grad_code != nullptr, s);
 }

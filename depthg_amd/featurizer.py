@@ -216,8 +216,9 @@ class DepthGuidance:
             image_depth_feat = image_feat
         if self.proj_type is not None:
             # :589-605 - the fused head; its three Dropout2d draws come behind whatever cross_attn's own dropout drew, as there
+            # (cfg.dg_rec_feats_grad: the returned feats stay attached, for the reconstruction term to train the depth modules through)
             code, feats = run_head(*self._head_modules(), image_depth_feat, self.training, bool(self.cfg.dropout), float(self.dropout.p),
-                                   keeps, input_grad=True)
+                                   keeps, input_grad=True, feats_grad=bool(getattr(self.cfg, "dg_rec_feats_grad", False)))
         else:
             code = image_depth_feat
             feats = self.dropout(image_depth_feat) if self.cfg.dropout else image_depth_feat

@@ -51,10 +51,13 @@ class _HeadFunction(torch.autograd.Function):
     `input_grad`: features that require grad are accepted, and backward returns d loss / d image_feat for each pass that asks
     (dg_head_backward_input / _pair, one more launch behind the parameter gradients, on their workspace); a pass that does not ask
     gets None and is not walked.  False: such features are refused, as ever.
+    `feats_grad` (with input_grad): the returned feats_out = Dropout2d(image_feat) of a pass whose features require grad stays
+    differentiable, and what reaches it is added - times keep3 scale - to that pass's d image_feat in the d image_feat launch's
+    epilogue (dg_head_backward_input_add / _pair).  False: feats_out is marked non-differentiable, as ever.
     -> (code per pass ..., feats_out per pass ... (None unless want_feats))."""
 
     @staticmethod
-    def forward(ctx, keeps, scale, want_feats, input_grad, w1, b1, w2a, b2a, w2b, b2b, *feats):
+    def forward(ctx, keeps, scale, want_feats, input_grad, feats_grad, w1, b1, w2a, b2a, w2b, b2b, *feats):
         lib = _lib.load()
         n = len(feats)
         pair = "_pair" if n == 2 else ""
@@ -62,7 +65,7 @@ class _HeadFunction(torch.autograd.Function):
         f = fs[0]
         if n == 2 and (f.shape != fs[1].shape or f.device != fs[1].device):
             raise ValueError(f"depthg_amd: the two passes' features must match: {tuple(f.shape)} on {f.device} and {tuple(fs[1].shape)} on {fs[1].device}")
-        if any(ctx.needs_input_grad[10:]) and not input_grad:
+        if any(ctx.needs_input_grad[11:]) and not input_grad:
             # (the backbone is frozen in the reference - DinoFeaturizer runs it under no_grad, src/modules.py:96 - and the
             #  d/d image_feat launch is opt-in: refuse rather than drop that gradient silently)
             raise RuntimeError("depthg_amd: ProjectionHead received features that require grad; the head has no gradient with "
@@ -72,7 +75,7 @@ class _HeadFunction(torch.autograd.Function):
         nonlinear = w2a is not None
         # grad mode and requires_grad of the six parameters, as autograd sees them: under torch.no_grad() / eval inference the
         # bf16 hidden tile (19 MB at the headline shape) is neither written nor kept
-        need_grad = any(ctx.needs_input_grad[4:])
+        need_grad = any(ctx.needs_input_grad[5:])
         codes = [_empty((B, D, h, w), torch.float32, dev) for _ in fs]
         fouts = [_empty((B, C, h, w), torch.float32, dev) if want_feats else None for _ in fs]
         hidden = _empty((n * B, C, P), torch.bfloat16, dev) if (nonlinear and need_grad) else None
@@ -90,17 +93,22 @@ class _HeadFunction(torch.autograd.Function):
         ctx.shapes = tuple(t.shape if t is not None else None for t in (w1, b1, w2a, b2a, w2b, b2b))
         ctx.hw = (h, w)
         # (the fp32 weight matrices: what the d image_feat launch makes its transposed copies from)
-        ctx.want_dx = bool(input_grad) and any(ctx.needs_input_grad[10:])
-        ctx.save_for_backward(k1, k2, hidden, wscratch, w1c if ctx.want_dx else None, w2ac if ctx.want_dx else None, *fs)
+        ctx.want_dx = bool(input_grad) and any(ctx.needs_input_grad[11:])
+        # the passes whose feats_out carries a gradient back: the third mask is then needed in backward
+        ctx.feats_diff = tuple(bool(want_feats and input_grad and feats_grad and need) for need in ctx.needs_input_grad[11:])
+        ctx.save_for_backward(k1, k2, hidden, wscratch, w1c if ctx.want_dx else None, w2ac if ctx.want_dx else None,
+                              k3 if any(ctx.feats_diff) else None, *fs)
         ctx.set_materialize_grads(False)
         if want_feats:
-            ctx.mark_non_differentiable(*fouts)
+            frozen = [fo for fo, diff in zip(fouts, ctx.feats_diff) if not diff]
+            if frozen:
+                ctx.mark_non_differentiable(*frozen)
         return (*codes, *fouts)
 
     @staticmethod
     def backward(ctx, *grads):
         lib = _lib.load()
-        k1, k2, hidden, wscratch, w1c, w2ac, *fs = ctx.saved_tensors
+        k1, k2, hidden, wscratch, w1c, w2ac, k3, *fs = ctx.saved_tensors
         B, C, D, P = ctx.dims
         n, dev = len(fs), fs[0].device
         if ctx.nonlinear and hidden is None:
@@ -124,14 +132,21 @@ class _HeadFunction(torch.autograd.Function):
         gfs = [None] * n
         if ctx.want_dx:
             # d image_feat of the passes that ask: one launch behind the parameter gradients, d hidden read from their workspace
-            gfs = [_empty((B, C) + ctx.hw, torch.float32, dev) if need else None for need in ctx.needs_input_grad[10:]]
+            gfs = [_empty((B, C) + ctx.hw, torch.float32, dev) if need else None for need in ctx.needs_input_grad[11:]]
             nbi = lib.dg_head_input_workspace_bytes(C, D)
             iws = _empty(nbi, torch.uint8, dev)
-            entry = "dg_head_backward_input" + ctx.pair
-            rc = getattr(lib, entry)(B, C, D, P, _ptr(w1c), _ptr(w2ac), _ptr(k1), _ptr(k2), ctx.scale, _ptr(hidden), *map(_ptr, gs),
-                                     _ptr(ws), nb, *map(_ptr, gfs), _ptr(iws), nbi, _stream(dev))
+            # what reached each pass's feats_out (None: nothing, or that output was not differentiable)
+            gfo = [_f32c(g, "grad_feats") if (g is not None and diff) else None for g, diff in zip(grads[n:2 * n], ctx.feats_diff)]
+            if any(g is not None for g in gfo):
+                entry = "dg_head_backward_input_add" + ctx.pair
+                rc = getattr(lib, entry)(B, C, D, P, _ptr(w1c), _ptr(w2ac), _ptr(k1), _ptr(k2), _ptr(k3), ctx.scale, _ptr(hidden),
+                                         *map(_ptr, gs), *map(_ptr, gfo), _ptr(ws), nb, *map(_ptr, gfs), _ptr(iws), nbi, _stream(dev))
+            else:
+                entry = "dg_head_backward_input" + ctx.pair
+                rc = getattr(lib, entry)(B, C, D, P, _ptr(w1c), _ptr(w2ac), _ptr(k1), _ptr(k2), ctx.scale, _ptr(hidden), *map(_ptr, gs),
+                                         _ptr(ws), nb, *map(_ptr, gfs), _ptr(iws), nbi, _stream(dev))
             _lib.check(rc, entry)
-        return (None, None, None, None) + tuple(g.reshape(sh) if g is not None else None for g, sh in zip(gparams, ctx.shapes)) + tuple(gfs)
+        return (None, None, None, None, None) + tuple(g.reshape(sh) if g is not None else None for g, sh in zip(gparams, ctx.shapes)) + tuple(gfs)
 
 
 def draw_keep_masks_pair(B, C, device, p=0.1, use=(True, True, True)):
@@ -154,9 +169,11 @@ def draw_keep_masks(B, C, device, p=0.1, use=(True, True, True)):
     return tuple(torch.empty(B, C, device=device, dtype=torch.float32).bernoulli_(1.0 - p) if u else None for u in use)
 
 
-def _run_head(cluster1, cluster2, feats, training, feats_dropout, p, keeps, draw, defer=False, input_grad=False):
+def _run_head(cluster1, cluster2, feats, training, feats_dropout, p, keeps, draw, defer=False, input_grad=False, feats_grad=False):
     """What run_head and run_head_pair share: the keep masks that exist (given, or drawn with `draw`), the head's parameters, one
     _HeadFunction call on the one or two maps of `feats`, and ((code, feats), ...) per pass."""
+    if feats_grad and not input_grad:
+        raise ValueError("depthg_amd: feats_grad=True carries the returned feats' gradient into the head's input: it needs input_grad=True")
     B, C = feats[0].shape[:2]
     nl = cluster2 is not None
     scale = 1.0 / (1.0 - p)
@@ -174,32 +191,36 @@ def _run_head(cluster1, cluster2, feats, training, feats_dropout, p, keeps, draw
         keeps = (keeps[0], keeps[1], None)
     convs = (cluster1[0], cluster2[0], cluster2[2]) if nl else (cluster1[0],)
     params = [t for conv in convs for t in (conv.weight, conv.bias)] + [None] * (6 - 2 * len(convs))
-    out = _HeadFunction.apply(keeps, scale, want_feats, bool(input_grad), *params, *feats)
+    out = _HeadFunction.apply(keeps, scale, want_feats, bool(input_grad), bool(feats_grad), *params, *feats)
     codes, fouts = out[:len(feats)], out[len(feats):]
     if deferred is not None:
         return tuple((c, DeferredDropout(f, deferred[i * B:(i + 1) * B], scale)) for i, (c, f) in enumerate(zip(codes, feats)))
     return tuple((c, fo if want_feats else f) for c, f, fo in zip(codes, feats, fouts))
 
 
-def run_head(cluster1, cluster2, image_feat, training, feats_dropout, p=0.1, keeps=None, input_grad=False):
+def run_head(cluster1, cluster2, image_feat, training, feats_dropout, p=0.1, keeps=None, input_grad=False, feats_grad=False):
     """(code, feats) of one featurizer pass (src/modules.py:122-137) from the reference's modules: `cluster1` = Sequential(Conv2d),
     `cluster2` = Sequential(Conv2d, ReLU, Conv2d) or None (projection_type "linear").  Training: three Dropout2d draws (`keeps`
     or drawn here), feats = Dropout2d(image_feat) when `feats_dropout` (cfg.dropout); eval: no dropout, feats = image_feat.
     `input_grad`: an image_feat that requires grad is accepted and receives its gradient through `code` (the returned feats stay
-    non-differentiable: the loss reads them under no_grad, src/modules.py:1232-1234); False refuses such features."""
-    return _run_head(cluster1, cluster2, (image_feat,), training, feats_dropout, p, keeps, draw_keep_masks, False, input_grad)[0]
+    non-differentiable: the loss reads them under no_grad, src/modules.py:1232-1234); False refuses such features.
+    `feats_grad` (only with input_grad): the returned feats stay attached - the reconstruction term reads them with a graph,
+    src/train_segmentation.py:391-398 - and their gradient, times the third mask, joins image_feat's inside the d image_feat launch.
+    (Without feats_dropout, or in eval mode, feats is image_feat itself and autograd needs no help.)"""
+    return _run_head(cluster1, cluster2, (image_feat,), training, feats_dropout, p, keeps, draw_keep_masks, False, input_grad, feats_grad)[0]
 
 
 def run_head_pair(cluster1, cluster2, image_feat, image_feat_pos, training, feats_dropout, p=0.1, keeps=None, defer_feats_dropout=False,
-                  input_grad=False):
+                  input_grad=False, feats_grad=False):
     """run_head for the two passes of a training step at once: ((code, feats), (code_pos, feats_pos)).  `keeps`: three (2B, C)
     tensors (draw_keep_masks_pair) or None (drawn here, in the order two run_head calls would draw).  `defer_feats_dropout`: the
     Dropout2d of the returned feats is drawn as always but NOT applied - `feats` / `feats_pos` come back as ops.DeferredDropout
     (the input maps + their keep flags), which ContrastiveCorrelationLoss applies inside its operand preparation: the dropped
     tensors (38.5 MB each at the headline shape) are neither written here nor read there.  `input_grad`: as run_head, per pass - a
-    pass whose features do not require grad gets no gradient and is not walked by the launch."""
+    pass whose features do not require grad gets no gradient and is not walked by the launch.  `feats_grad`: as run_head, per pass
+    (deferred feats are the input maps themselves: whoever applies the mask hands them their gradient)."""
     return _run_head(cluster1, cluster2, (image_feat, image_feat_pos), training, feats_dropout, p, keeps, draw_keep_masks_pair,
-                     defer_feats_dropout, input_grad)
+                     defer_feats_dropout, input_grad, feats_grad)
 
 
 class ProjectionHead(nn.Module):
@@ -214,7 +235,7 @@ class ProjectionHead(nn.Module):
         if projection_type == "nonlinear":                                                                # make_nonlinear_clusterer, :79-83
             self.cluster2 = nn.Sequential(nn.Conv2d(n_feats, n_feats, (1, 1)), nn.ReLU(), nn.Conv2d(n_feats, dim, (1, 1)))
 
-    def forward(self, image_feat, feats_dropout=True, keeps=None, input_grad=False):
+    def forward(self, image_feat, feats_dropout=True, keeps=None, input_grad=False, feats_grad=False):
         if self.proj_type is None:                                                                        # :125-126: code = image_feat
             feats = image_feat
             if self.training and feats_dropout:                                                           # :127-129: feats = Dropout2d(image_feat)
@@ -225,9 +246,10 @@ class ProjectionHead(nn.Module):
                 feats = image_feat * (k3 * (1.0 / (1.0 - self.p)))[:, :, None, None]
             return image_feat, feats
         return run_head(self.cluster1, getattr(self, "cluster2", None) if self.proj_type == "nonlinear" else None, image_feat,
-                        self.training, feats_dropout, self.p, keeps, input_grad)
+                        self.training, feats_dropout, self.p, keeps, input_grad, feats_grad)
 
-    def forward_pair(self, image_feat, image_feat_pos, feats_dropout=True, keeps=None, defer_feats_dropout=False, input_grad=False):
+    def forward_pair(self, image_feat, image_feat_pos, feats_dropout=True, keeps=None, defer_feats_dropout=False, input_grad=False,
+                     feats_grad=False):
         """forward(image_feat) and forward(image_feat_pos) of one training step (src/train_segmentation.py:303-306) as one set of
         launches: ((code, feats), (code_pos, feats_pos)), the same values and - after backward - the same parameter gradients.
         `defer_feats_dropout`: see run_head_pair (feats / feats_pos as ops.DeferredDropout for the loss to apply); `input_grad`:
@@ -241,7 +263,7 @@ class ProjectionHead(nn.Module):
                     ka, kb = (None, None, keeps[2][:B]), (None, None, keeps[2][B:])
             return self.forward(image_feat, feats_dropout, ka), self.forward(image_feat_pos, feats_dropout, kb)
         return run_head_pair(self.cluster1, getattr(self, "cluster2", None) if self.proj_type == "nonlinear" else None, image_feat,
-                             image_feat_pos, self.training, feats_dropout, self.p, keeps, defer_feats_dropout, input_grad)
+                             image_feat_pos, self.training, feats_dropout, self.p, keeps, defer_feats_dropout, input_grad, feats_grad)
 
 
 class _ClusterFunction(torch.autograd.Function):

@@ -504,20 +504,38 @@ def rec_loss_forward(code, feats, weight, bias, keep=None, scale=1.0):
     return loss, ws
 
 
-def rec_loss_backward(workspace, code, feats, weight, bias, grad_out, keep=None, scale=1.0, out=None):
+def rec_loss_backward(workspace, code, feats, weight, bias, grad_out, keep=None, scale=1.0, out=None, want_feats=False, want_params=True):
     """(d loss / d code (B,D,h,w), d loss / d weight (C,D), d loss / d bias (C,)) of the rec_loss_forward whose workspace this is -
     same tensors - times the 0-dim device tensor `grad_out` (dg_recloss_backward); every element of the three is written.  out:
-    optional triple of result buffers."""
+    optional triple of result buffers.
+    want_feats: a fourth value, d loss / d feats (B,C,h,w) - of the un-dropped maps when keep flags are given, dropped channels an
+    exact 0 - from the same launches (dg_rec_feats_backward; the first three keep their bits; `out` may then name four buffers);
+    with want_params=False on top the first three are None and one launch forms d feats alone."""
     lib = _lib.load()
     code, feats, weight, bias, keep, scale, (B, D, C, h, w) = _rec_loss_operands(code, feats, weight, bias, keep, scale)
     dev = code.device
     _forward_workspace(workspace, "rec_loss_forward", dev, _rec_loss_workspace_bytes(lib, B, D, C, h, w))
     grad_out = _grad_out_scalar(grad_out, dev)
-    out = _out_buffers(out, ((B, D, h, w), (C, D), (C,)), ("code", "weight", "bias"), dev)
-    rc = lib.dg_recloss_backward(_ptr(code), _ptr(feats), _ptr(weight), _ptr(bias), _ptr(keep), scale, _ptr(workspace), workspace.numel(),
-                                 B, D, C, h, w, _ptr(grad_out), _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _stream(dev))
-    _lib.check(rc, "dg_recloss_backward")
-    return out[0], out[1], out[2]
+    if not want_feats:
+        if not want_params:
+            raise ValueError("depthg_amd: rec_loss_backward(want_params=False) leaves nothing to compute without want_feats=True")
+        out = _out_buffers(out, ((B, D, h, w), (C, D), (C,)), ("code", "weight", "bias"), dev)
+        rc = lib.dg_recloss_backward(_ptr(code), _ptr(feats), _ptr(weight), _ptr(bias), _ptr(keep), scale, _ptr(workspace), workspace.numel(),
+                                     B, D, C, h, w, _ptr(grad_out), _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _stream(dev))
+        _lib.check(rc, "dg_recloss_backward")
+        return out[0], out[1], out[2]
+    if want_params:
+        if out is not None and len(out) != 4:
+            raise ValueError(f"depthg_amd: rec_loss_backward(want_feats=True) fills four `out` buffers, got {len(out)}")
+        out = _out_buffers(out, ((B, D, h, w), (C, D), (C,), (B, C, h, w)), ("code", "weight", "bias", "feats"), dev)
+    else:
+        if out is not None:
+            raise ValueError("depthg_amd: rec_loss_backward(want_params=False) allocates its one result itself")
+        out = (None, None, None, _empty((B, C, h, w), torch.float32, dev))
+    rc = lib.dg_rec_feats_backward(_ptr(code), _ptr(feats), _ptr(weight), _ptr(bias), _ptr(keep), scale, _ptr(workspace), workspace.numel(),
+                                   B, D, C, h, w, _ptr(grad_out), _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _ptr(out[3]), _stream(dev))
+    _lib.check(rc, "dg_rec_feats_backward")
+    return out[0], out[1], out[2], out[3]
 
 
 def depth_encoder_shapes(depth, params, residual=None):

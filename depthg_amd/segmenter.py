@@ -38,7 +38,9 @@ the reconstruction term (:391-398) through rec_loss.reconstruction_loss - the fu
 With cfg.arch == "dino_depth" (:104-106) the featurizer is the depth-guided one - featurizer.DinoFeaturizerWithDepth over the ViT under
 cfg.dg_dino_backbone, StandInFeaturizerWithDepth otherwise - cfg.guidance chooses how the depth encoder's map meets the features, use_depth
 is forced on, the step feeds (img, depth) / (img_pos, depth_pos) one pass at a time and net_optim steps the depth modules the guidance
-trains with the head (the head's d image_feat launch, dg_head_backward_input, carries the gradient to them).
+trains with the head (the head's d image_feat launch, dg_head_backward_input, carries the gradient to them).  There cfg.rec_weight > 0
+under guidance "sum" / "cross_attn" needs cfg.dg_rec_feats_grad: the reconstruction term then reads the first pass's attached feats, its
+backward writes d feats (dg_rec_feats_backward) and the head adds it into d image_feat (dg_head_backward_input_add).
 """
 from types import SimpleNamespace
 from typing import Dict, Optional
@@ -167,10 +169,11 @@ class UnsupervisedSegmenter(nn.Module):
             raise ValueError("depthg_amd: cfg.aug_alignment_weight > 0 cannot be combined with cfg.arch = 'dino_depth': the term's third "
                              "featurizer pass has no depth map (the reference's `self.net(img_aug)` fails the depth featurizer's "
                              "two-tuple assertion, src/modules.py:609)")
-        if getattr(cfg, "rec_weight", 0) > 0 and getattr(cfg, "guidance", "none") in ("sum", "cross_attn"):
+        if getattr(cfg, "rec_weight", 0) > 0 and getattr(cfg, "guidance", "none") in ("sum", "cross_attn") \
+                and not getattr(cfg, "dg_rec_feats_grad", False):
             raise ValueError(f"depthg_amd: cfg.rec_weight > 0 cannot be combined with cfg.arch = 'dino_depth' under guidance "
                              f"{cfg.guidance!r}: there feats depend on trainable depth modules and the fused reconstruction kernels "
-                             "have no gradient with respect to feats")
+                             "have no gradient with respect to feats, unless cfg.dg_rec_feats_grad = True asks them for it")
 
     def forward(self, x):
         return self.net(x)[1]                                                          # :160-167
@@ -268,6 +271,7 @@ class UnsupervisedSegmenter(nn.Module):
         #  (the depth-guided featurizer takes (img, depth) and returns four values, :191-200, one pass at a time)
         paired = cfg.correspondence_weight > 0 and not getattr(cfg, "lhp", False) and hasattr(self.net, "forward_pair") and self.net.training \
             and not self.depth_arch
+        rec_feats = None                                          # the first pass's ATTACHED feats, where the reconstruction term gets them
         if paired:
             # (on the dense identity grid the Dropout2d of the returned feats is applied by the loss's operand preparation: the
             #  dropped feature tensors are never written - ops.DeferredDropout)
@@ -279,6 +283,9 @@ class UnsupervisedSegmenter(nn.Module):
         elif self.depth_arch:
             # (feats carry a graph under guidance "sum" / "cross_attn"; the correlation loss reads them under no_grad, src/modules.py:1232-1234)
             feats, code, _, attn = self.net((img, depth))                                            # :191-197
+            # (cfg.dg_rec_feats_grad: the reconstruction term reads the attached tensor, :391-398, and trains the depth modules through it)
+            if getattr(cfg, "dg_rec_feats_grad", False) and getattr(cfg, "rec_weight", 0) > 0 and feats.requires_grad:
+                rec_feats = feats
             feats = feats.detach()
         else:
             feats, code, attn = self.net(img)                                                        # :194-200
@@ -320,7 +327,10 @@ class UnsupervisedSegmenter(nn.Module):
             if getattr(self, "decoder", None) is None:
                 raise RuntimeError(f"training_step: cfg.rec_weight = {cfg.rec_weight} but this segmenter was built without a decoder "
                                    "(rec_weight was 0 then); set cfg.rec_weight before constructing UnsupervisedSegmenter")
-            rec = reconstruction_loss(code, feats, self.decoder.weight, self.decoder.bias)
+            if rec_feats is not None:    # (arch "dino_depth" under "sum" / "cross_attn" with cfg.dg_rec_feats_grad: d feats is written too)
+                rec = reconstruction_loss(code, rec_feats, self.decoder.weight, self.decoder.bias, feats_grad=True)
+            else:
+                rec = reconstruction_loss(code, feats, self.decoder.weight, self.decoder.bias)
             logs["loss/rec"] = rec.detach()
             loss = loss + cfg.rec_weight * rec
 
@@ -464,7 +474,11 @@ def default_segmenter_cfg(**over) -> SimpleNamespace:
         dg_fused_depth_encoder=False,
         # build-side, the same arch under guidance "cross_attn": the attention core between cross_attn's projections as one fused HIP
         # forward and backward (cross_attn.py)
-        dg_fused_cross_attn=False)
+        dg_fused_cross_attn=False,
+        # the same arch under guidance "sum" / "cross_attn" with rec_weight > 0 (refused without this key): the reconstruction term
+        # reads the featurizer's ATTACHED feats and its backward writes d feats as well (rec_loss.reconstruction_loss(feats_grad=True)),
+        # so the term trains the depth modules as in the reference; under any other arch or guidance the key changes nothing
+        dg_rec_feats_grad=False)
     for k, v in over.items():
         setattr(cfg, k, v)
     return cfg

@@ -504,6 +504,27 @@ int dg_head_backward_input_pair(int32_t B, int32_t C, int32_t D, int32_t P, cons
                                 float* grad_feat_pos, void* input_workspace, size_t input_workspace_bytes, dg_stream_t stream);
 
 /*
+ * dg_head_backward_input (_pair) plus the gradient that reached the head's returned feats_out = Dropout2d(image_feat) (opt-in on top
+ * of the opt-in: under DinoFeaturizerWithDepth the reconstruction term reads the attached feats, src/modules.py:596-598 and
+ * src/train_segmentation.py:391-398), added in the launch's epilogue, to the element about to be stored:
+ *     grad_feat[b,k,p] = (the sum above) + keep_scale keep3[b,k] grad_feats_out[b,k,p]
+ * Same launches, same call order and same arguments as dg_head_backward_input (_pair), and:
+ *  keep3                : the third Dropout2d draw's flags fp32 (B,C) - (2B,C) in the pair form - or NULL (no mask: factor 1)
+ *  grad_feats_out       : fp32 (B,C,P), 16-byte aligned, or NULL: nothing is added for that pass (NULL for every pass: the bits
+ *                         of dg_head_backward_input).  A pass with grad_feats_out must have its grad_feat.
+ * fp32 addend on the fp32 accumulator; a channel keep3 dropped adds an exact 0; still one store per element, no atomics.
+ */
+int dg_head_backward_input_add(int32_t B, int32_t C, int32_t D, int32_t P, const float* w1, const float* w2a, const float* keep1,
+                               const float* keep2, const float* keep3, float keep_scale, const void* hidden, const float* grad_code,
+                               const float* grad_feats_out, const void* workspace, size_t workspace_bytes, float* grad_feat,
+                               void* input_workspace, size_t input_workspace_bytes, dg_stream_t stream);
+int dg_head_backward_input_add_pair(int32_t B, int32_t C, int32_t D, int32_t P, const float* w1, const float* w2a, const float* keep1,
+                                    const float* keep2, const float* keep3, float keep_scale, const void* hidden,
+                                    const float* grad_code, const float* grad_code_pos, const float* grad_feats_out,
+                                    const float* grad_feats_out_pos, const void* workspace, size_t workspace_bytes, float* grad_feat,
+                                    float* grad_feat_pos, void* input_workspace, size_t input_workspace_bytes, dg_stream_t stream);
+
+/*
  * Measurement aid: the launch routes dg_head_backward takes for B images (dg_head_backward_pair: pass 2 B) of C channels, D code
  * channels and P positions, from the plan the launches themselves follow.  Launches nothing and touches no GPU.  out[9] =
  *   [0] d hidden route     0: k_head_dh, one block per 64-position tile      1: k_head_dh2, persistent blocks, d W2b inside
@@ -695,6 +716,7 @@ int dg_augalign_backward(const float* code, const float* code_aug, void* workspa
  *      ny = max(|y|, eps), nf = max(|f|, eps), s = <y, f> / (ny nf), loss = -(1/N) sum s
  *      dy = a f + b y, a = -(G/N) / (ny nf), b = (G/N) s / ny^2 where |y| > eps and 0 below (what F.normalize gives under autograd)
  *      d code_p = W^T dy, d weight = sum_p dy c_p^T, d bias = sum_p dy;  feats receives no gradient (the frozen backbone's output)
+ *      except through dg_rec_feats_backward (below): d f = a y + b' f, b' = (G/N) s / nf^2 where |f| > eps and 0 below
  *  code : fp32 (B, D, h, w);  feats : fp32 (B, C, h, w);  weight : fp32 (C, D);  bias : fp32 (C);  all contiguous, 4-byte aligned
  *  keep, scale : NULL, or the Dropout2d keep flags fp32 (B, C), 1 / 0, of feats that have not been dropped yet: the kernels read
  *                feats[b,c] * (keep[b,c] != 0 ? scale : 0) - the bits of the dropped tensor (src/modules.py:122-137); scale > 0
@@ -716,6 +738,23 @@ int dg_recloss_forward(const float* code, const float* feats, const float* weigh
 int dg_recloss_backward(const float* code, const float* feats, const float* weight, const float* bias, const float* keep, float scale,
                         void* workspace, size_t workspace_bytes, int32_t B, int32_t D, int32_t C, int32_t h, int32_t w,
                         const float* grad_out, float* grad_code, float* grad_weight, float* grad_bias, dg_stream_t stream);
+
+/*
+ * The reconstruction term's backward WITH d loss / d feats (opt-in: under DinoFeaturizerWithDepth feats = dropout(image_depth_feat)
+ * is attached to the trained depth modules, src/modules.py:596-598, and the term trains them through it).  One entry that produces
+ * everything in one call - call it INSTEAD of dg_recloss_backward, with the same arguments, workspace and stream:
+ *  grad_feats : fp32 (B, C, h, w) out, every element written once: (a y + b' f) (keep[b,c] != 0 ? scale : 0) - the gradient of the
+ *               tensor the `feats` pointer names (the un-dropped maps when keep is given; a dropped channel is an exact 0)
+ *  grad_code, grad_weight, grad_bias : as dg_recloss_backward - the same bits - or all three NULL: d feats alone, from one launch
+ *               that skips the W^T dy product
+ * The kernel that forms d code holds y, f and the factors of every (channel, position) it visits and stores d f from those registers:
+ * no further product, no atomics, two calls give the same bits.  (Named dg_rec_feats_* so that the dg_recloss_* group stays the
+ * three entries it was.)
+ */
+int dg_rec_feats_backward(const float* code, const float* feats, const float* weight, const float* bias, const float* keep, float scale,
+                          void* workspace, size_t workspace_bytes, int32_t B, int32_t D, int32_t C, int32_t h, int32_t w,
+                          const float* grad_out, float* grad_code, float* grad_weight, float* grad_bias, float* grad_feats,
+                          dg_stream_t stream);
 
 /*
  * The optimisation step's Adams (src/train_segmentation.py:447-455: net_optim.step(), cluster_probe_optim.step(),
