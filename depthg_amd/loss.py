@@ -399,11 +399,16 @@ class ContrastiveCorrelationLoss(nn.Module):
         term; else a further channel chunk of a wider map: zero shifts, no depth term).  -> (out, total, desc, workspace)."""
         cfg = self.cfg
         dt = call.depth_term and first
+        # the total's weights are those of the CALL's depth term on every chunk: the caller's lhp balance scales all terms of the total
+        # (src/train_segmentation.py:326-335), not the first chunk's alone; a further chunk has no depth term, so no depth weight
+        weights = self._total_weights(call.depth_term)
+        if not dt:
+            weights = weights[:3] + (0.0,)
         desc = ops.make_desc(call.B, f_a.shape[1], call.D, call.h, call.w, call.S, call.N, pointwise=bool(cfg.pointwise),
                              zero_clamp=bool(cfg.zero_clamp), stabalize=bool(cfg.stabalize), depth_term=dt, need_grad=call.need_grad,
                              shared_coords=call.shared_coords, shifts=call.shifts if first else (0.0, 0.0, 0.0, 0.0),
                              depth_hw=tuple(call.depth.shape[-2:]) if (call.depth is not None and dt) else (0, 0),
-                             identity_grid=call.identity_grid, weights=self._total_weights(dt), line_grid=call.line_grid,
+                             identity_grid=call.identity_grid, weights=weights, line_grid=call.line_grid,
                              code_hw=call.code_hw, exact_masks=bool(getattr(cfg, "dg_exact_masks", False)), feats_unit=unit)
         holder = {"draw_state": call.draw_state, "feat_keep": keep, "feat_inv": feat_inv}
         out, total = _CorrLossFunction.apply(call.code, call.code_pos, f_a, f_b, call.depth if dt else None,

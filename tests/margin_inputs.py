@@ -14,9 +14,11 @@ few percent of its L2 norm only (header of tests/test_gpu_parity.py).  Here the 
                 kernel, no GPU involved.
     figures     grad_errors: relative L2 of the whole tensor, worst position row, worst channel plane, worst element.
     criterion   every figure of the kernel's gradient <= FACTOR[family][figure] x the yardstick's, and below the caps CAP_*.
+    total       the backward starts at the fused `loss.total`, which is held to the oracle's total: the weights, shifts,
+                correspondence_weight and lhp balance of a recipe (WEIGHTS) are part of both the truth and the yardstick.
 
 The constants FACTOR come from one run of the table on an MI355X (profiles/grad_margin.md holds the ratios): the worst ratio of a
-route family x 1.5, rounded up to one digit.
+route family x 1.5, rounded up to one digit.  A case added to a family later is held to the family's factor as it stands.
 """
 import contextlib
 import functools
@@ -36,6 +38,8 @@ FACTOR = {
     "taps": GradErrors(l2=3.0, row=3.0, channel=3.0, elem=3.0),              # 1.92 / 1.59 / 1.83 / 1.46
     "main": GradErrors(l2=3.0, row=3.0, channel=3.0, elem=4.0),              # 1.89 / 1.60 / 1.89 / 2.10
     "small": GradErrors(l2=2.0, row=2.0, channel=3.0, elem=3.0),             # 1.17 / 1.08 / 1.42 / 1.54
+    "wide-identity": GradErrors(l2=5.0, row=5.0, channel=6.0, elem=6.0),     # 2.98 / 3.15 / 3.76 / 3.65 (C > 768, dense grid in channel chunks)
+    "wide-taps": GradErrors(l2=4.0, row=4.0, channel=4.0, elem=4.0),         # 2.02 / 2.52 / 2.40 / 2.39 (C > 768, sampled grid in channel chunks)
 }
 # whatever the ratios: whole-tensor L2 at most what the exact-mask tests reach, worst row / channel at most 2e-2
 CAP_L2 = {"code": 2e-3, "code_pos": 3e-3}
@@ -45,13 +49,26 @@ CAP_ROW = CAP_CHANNEL = 2e-2
 # ---- the table of cases (shared by the CPU and the GPU test) --------------------------------------------------------------------
 # coords: "identity" = forward_with(..., shared_coords=True, identity_grid=True) on the S == h == w grid;
 #         "whole"    = coords1 != coords2 from whole_pixel_coords, not shared
+#         "shared"   = ONE whole_pixel_coords grid for both coordinate sets and every image: forward_with(..., shared_coords=True)
+#         "line"     = the (B, S, 1, 2) grid of depth_sampling='simple' on whole pixels, coords1 != coords2
+# depth_term: cfg.depth_feat_correlation_loss (off: the 6-tuple); code_hw: side of the code maps where it is not hw (then
+#         (code_hw - 1) % (hw - 1) == 0: a whole feature pixel is a whole code pixel); over: further cfg keys (weights, shifts, lhp,
+#         dg_exact_masks); chunks: launch sets the call runs (channel chunks of a map wider than 768)
 # seed:   fixed per case, chosen so that margin_report meets tests/test_margin_inputs_cpu.py (a condition on the inputs)
-Case = namedtuple("Case", "id family kernel B C D hw S N seed pointwise zero_clamp stabalize dup coords note")
+Case = namedtuple("Case", "id family kernel B C D hw S N seed pointwise zero_clamp stabalize dup coords note depth_term code_hw over chunks")
 
 
 def _case(id, family, kernel, B, C, D, hw, N, seed, note, S=None, pointwise=True, zero_clamp=True, stabalize=False, dup=False,
-          coords="identity"):
-    return Case(id, family, kernel, B, C, D, hw, hw if S is None else S, N, seed, pointwise, zero_clamp, stabalize, dup, coords, note)
+          coords="identity", depth_term=True, code_hw=None, over=None, chunks=1):
+    return Case(id, family, kernel, B, C, D, hw, hw if S is None else S, N, seed, pointwise, zero_clamp, stabalize, dup, coords, note,
+                depth_term, code_hw, dict(over or {}), chunks)
+
+
+# the weights case: lhp balance on, correspondence_weight != 1, four distinct weights and non-default shifts - a swapped, missing or
+# forgotten factor of the fused total (DG_OUT_TOTAL) changes `loss.total` and the gradient through it by percents
+WEIGHTS = dict(lhp=True, lhp_weight=0.3, lhp_weight_balance=True, correspondence_weight=1.3,
+               pos_intra_weight=0.9, pos_inter_weight=0.4, neg_inter_weight=0.7, depth_feat_weight=0.23,
+               pos_intra_shift=0.12, pos_inter_shift=0.05, neg_inter_shift=0.5, depth_feat_shift=0.06)
 
 
 CASES = [
@@ -74,6 +91,38 @@ CASES = [
     _case("main-C768-D100-noclamp", "main", "k_corr_main", 2, 768, 100, 14, 2, 8, "control: no mask at all", zero_clamp=False),
     # small grid (exact masks already): cross-check of the yardstick
     _case("small-S9", "small", "k_corr_small", 3, 64, 33, 12, 2, 11, "fused small-grid kernel", S=9, coords="whole"),
+    # C > 768 on the dense identity grid: channel chunks of unit vectors (dg_normalize_split + DG_FEATS_UNIT), loss means and
+    # gradients summed over the chunks
+    _case("wide-id-C1536", "wide-identity", "k_corr_main", 2, 1536, 24, 14, 1, 21, "two chunks of 768", chunks=2),
+    _case("wide-id-C1536-nopointwise", "wide-identity", "k_corr_main", 2, 1536, 24, 14, 1, 21, "the same without pointwise", pointwise=False, chunks=2),
+    _case("wide-id-C1536-weights", "wide-identity", "k_corr_main", 2, 1536, 24, 14, 1, 21, "the same with the weights case: lhp balance on every chunk",
+          over=WEIGHTS, chunks=2),
+    _case("wide-id-C800", "wide-identity", "k_corr_main", 3, 800, 70, 13, 2, 22, "chunks of 400: no multiple of 128", chunks=2),
+    _case("wide-id-C800-stabalize", "wide-identity", "k_corr_main", 3, 800, 70, 13, 2, 22, "the same with hi = 0.8", stabalize=True, chunks=2),
+    _case("wide-id-C2048-B1", "wide-identity", "k_corr_main", 1, 2048, 70, 13, 2, 25, "three chunks (688 + 688 + 672); the image is its own negative",
+          chunks=3),
+    # C > 768 on sampled coordinates above 160 positions: norms over all chunks first (dg_sampled_sumsq), then dg_corr_forward_extnorm
+    _case("wide-taps-C1024", "wide-taps", "k_corr_main", 2, 1024, 70, 14, 2, 23, "coordinates per image: the negatives are operands of their own",
+          S=14, coords="whole", chunks=2),
+    _case("wide-taps-C1024-shared", "wide-taps", "k_corr_main", 2, 1024, 70, 14, 2, 23, "one shared grid: the negatives go through the batch maps",
+          S=14, coords="shared", chunks=2),
+    _case("wide-taps-C1024-weights", "wide-taps", "k_corr_main", 2, 1024, 70, 14, 2, 23, "coordinates per image with the weights case",
+          S=14, coords="whole", over=WEIGHTS, chunks=2),
+    # C <= 768: the recipe switches and launch routes the table above does not reach
+    _case("corr2-13x13-nodepth", "identity", "k_corr2", 3, 384, 70, 13, 1, 1, "no depth term: the 6-tuple", depth_term=False),
+    _case("main-C768-D100-nodepth", "main", "k_corr_main", 2, 768, 100, 14, 2, 8, "no depth term", depth_term=False),
+    _case("small-S9-nodepth", "small", "k_corr_small", 3, 64, 33, 12, 2, 11, "no depth term", S=9, coords="whole", depth_term=False),
+    _case("ident-stabalize-C384", "main", "k_corr_main", 2, 384, 70, 13, 2, 24, "hi = 0.8 on the dense identity grid", stabalize=True),
+    _case("small-code13-feats7", "small", "k_corr_small", 3, 64, 33, 7, 2, 26, "code maps 13 x 13 on feature maps 7 x 7", S=6, coords="whole", code_hw=13),
+    _case("code27-feats14", "taps", "k_corr2", 2, 384, 70, 14, 2, 27, "code maps 27 x 27 on feature maps 14 x 14, 196 positions", S=14, coords="whole",
+          code_hw=27),
+    _case("small-line-S8", "small", "k_corr_small", 4, 48, 16, 10, 2, 28, "the S x 1 grid of depth_sampling='simple'", S=8, coords="line"),
+    _case("small-shared-dup", "small", "k_corr_small", 4, 64, 33, 12, 2, 29, "one shared non-identity grid, duplicate-heavy batch maps", S=9,
+          coords="shared", dup=True),
+    _case("corr2-13x13-exact", "identity", "k_corr2", 3, 384, 70, 13, 1, 1, "cfg.dg_exact_masks: the same bounds as the default kernels",
+          over=dict(dg_exact_masks=True)),
+    _case("corr2-14x14-weights", "identity", "k_corr2", 2, 384, 70, 14, 2, 30, "the weights case on a map the kernels hold whole", over=WEIGHTS),
+    _case("small-S9-weights", "small", "k_corr_small", 3, 64, 33, 12, 2, 11, "the weights case on the small grid", S=9, coords="whole", over=WEIGHTS),
 ]
 PROTOTYPES = 4          # K of margin_code_maps in every case
 FEATS_SIGMA = 0.5       # noise of the feature maps (case_inputs)
@@ -117,15 +166,15 @@ def _pixel_coordinate(idx, size):
     return cands[int(np.argmin(err))]
 
 
-def whole_pixel_coords(B, S, h, w, seed):
+def whole_pixel_coords(B, S, h, w, seed, Sh=None):
     """coords (B, S, S, 2) in [-1, 1] that land on pixel centres - a random selection of the h x w pixels per image, repeats
     allowed - so that the bilinear `sample` never mixes two prototypes (a neighbouring pixel enters with a weight below 1e-6,
-    where float32 has no coordinate for the centre itself)."""
+    where float32 has no coordinate for the centre itself).  Sh: the grid's second extent where it is not S (1: the line grid)."""
     g = torch.Generator().manual_seed(seed)
     xs = np.asarray([_pixel_coordinate(i, w) for i in range(w)], dtype=np.float32)
     ys = np.asarray([_pixel_coordinate(i, h) for i in range(h)], dtype=np.float32)
-    ix = torch.randint(0, w, (B, S, S), generator=g)
-    iy = torch.randint(0, h, (B, S, S), generator=g)
+    ix = torch.randint(0, w, (B, S, S if Sh is None else Sh), generator=g)
+    iy = torch.randint(0, h, (B, S, S if Sh is None else Sh), generator=g)
     return torch.stack([torch.from_numpy(xs)[ix], torch.from_numpy(ys)[iy]], dim=-1)
 
 
@@ -141,8 +190,9 @@ def iid_feats(case):
 
 
 def case_cfg(case, **over):
-    return O.default_cfg(feature_samples=case.S, neg_samples=case.N, dim=case.D, dg_outputs="reduced", pointwise=case.pointwise,
-                         zero_clamp=case.zero_clamp, stabalize=case.stabalize, **over)
+    return O.default_cfg(**{**dict(feature_samples=case.S, neg_samples=case.N, dim=case.D, dg_outputs="reduced", pointwise=case.pointwise,
+                                   zero_clamp=case.zero_clamp, stabalize=case.stabalize, depth_feat_correlation_loss=case.depth_term),
+                            **case.over, **over})
 
 
 def case_inputs(case):
@@ -159,11 +209,16 @@ def case_inputs(case):
         perms = [torch.randint(0, 3, (B,), generator=g) for _ in range(N)]
     else:
         perms = [O.super_perm(B, g) for _ in range(N)]
-    c, cp = margin_code_maps(B, D, hw, hw, PROTOTYPES, case.seed)
+    hc = hw if case.code_hw is None else case.code_hw
+    assert (hc - 1) % (hw - 1) == 0, "a whole feature pixel must be a whole code pixel"
+    c, cp = margin_code_maps(B, D, hc, hc, PROTOTYPES, case.seed)
     if case.coords == "identity":
         c1 = c2 = O.identity_coords(B, S)
+    elif case.coords == "shared":
+        c1 = c2 = whole_pixel_coords(1, S, hw, hw, 100 + case.seed).expand(B, S, S, 2).contiguous()
     else:
-        c1, c2 = whole_pixel_coords(B, S, hw, hw, 100 + case.seed), whole_pixel_coords(B, S, hw, hw, 200 + case.seed)
+        Sh = 1 if case.coords == "line" else None
+        c1, c2 = whole_pixel_coords(B, S, hw, hw, 100 + case.seed, Sh), whole_pixel_coords(B, S, hw, hw, 200 + case.seed, Sh)
     return f, fp, c, cp, d, c1, c2, perms
 
 

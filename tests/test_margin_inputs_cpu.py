@@ -41,6 +41,70 @@ def test_operand_yardstick_is_small_and_not_zero(case_id):
             assert 0.0 < v < 1e-2, (name, fig, v)
 
 
+def test_table_reaches_every_route_and_recipe_switch():
+    """The table itself: unique ids, and at least one case per launch route and recipe switch of the correlation loss."""
+    assert len(set(IDS)) == len(IDS)
+    has = lambda pred: any(pred(c) for c in M.CASES)
+    wide = lambda c: c.chunks > 1
+    assert has(lambda c: wide(c) and c.coords == "identity" and c.chunks == 3) and has(lambda c: wide(c) and c.coords == "whole")
+    assert has(lambda c: wide(c) and c.coords == "shared") and has(lambda c: wide(c) and not c.pointwise)
+    assert has(lambda c: wide(c) and c.stabalize) and has(lambda c: wide(c) and c.B == 1)
+    for coords in ("identity", "whole"):          # the weights case on both wide routes, on a narrow identity grid and on the small grid
+        assert has(lambda c: wide(c) and c.coords == coords and c.over.get("lhp_weight_balance"))
+    assert has(lambda c: c.kernel == "k_corr2" and not wide(c) and c.over.get("lhp_weight_balance"))
+    assert has(lambda c: c.kernel == "k_corr_small" and c.over.get("lhp_weight_balance"))
+    for kernel in ("k_corr2", "k_corr_main", "k_corr_small"):
+        assert has(lambda c: c.kernel == kernel and not c.depth_term)
+    assert has(lambda c: c.code_hw is not None and c.S ** 2 <= 160) and has(lambda c: c.code_hw is not None and c.S ** 2 > 160)
+    assert has(lambda c: c.coords == "line") and has(lambda c: c.coords == "shared" and c.S ** 2 <= 160 and c.dup)
+    assert has(lambda c: c.over.get("dg_exact_masks") and c.coords == "identity")
+    for c in M.CASES:
+        assert c.family in M.FACTOR, c.id
+        assert c.code_hw is None or (c.code_hw - 1) % (c.hw - 1) == 0, c.id
+        assert (c.chunks > 1) == (c.C > 768 and (c.coords == "identity" or c.S ** 2 > 160)), c.id
+
+
+def _weights_case():
+    return next(c for c in M.CASES if c.id == "wide-id-C1536-weights")
+
+
+def test_weights_case_scales_the_oracles_total_by_the_balance():
+    """The semantics the GPU weights cases are held to (src/train_segmentation.py:326-335): with the depth term, lhp and
+    lhp_weight_balance, EVERY term of the total is scaled by correspondence_weight - lhp_weight, so the total and both gradients are
+    (correspondence_weight - lhp_weight) / correspondence_weight times those of the same inputs without balance."""
+    case = _weights_case()
+    cfg, inp, ref = M.case_reference(case.id)
+    assert cfg.lhp and cfg.lhp_weight_balance and cfg.depth_feat_correlation_loss and cfg.correspondence_weight != 1.0
+    assert len({cfg.pos_intra_weight, cfg.pos_inter_weight, cfg.neg_inter_weight, cfg.depth_feat_weight}) == 4
+    plain = M.oracle_f64(M.case_cfg(case, lhp_weight_balance=False), *inp)
+    factor = (cfg.correspondence_weight - cfg.lhp_weight) / cfg.correspondence_weight
+    assert factor == pytest.approx(1.0 / 1.3, rel=1e-12)
+    assert float(ref[1]) == pytest.approx(factor * float(plain[1]), rel=1e-12)
+    for k in (2, 3):
+        assert float((ref[k] - factor * plain[k]).norm()) <= 1e-12 * float(plain[k].norm())
+    # the total by hand from the tuple: four distinct weights, one scale
+    o = ref[0]
+    by_hand = (cfg.pos_intra_weight * o[0] + cfg.pos_inter_weight * o[2] + cfg.neg_inter_weight * o[4].mean() +
+               cfg.depth_feat_weight * o[6]) * (cfg.correspondence_weight - cfg.lhp_weight)
+    assert float(ref[1]) == pytest.approx(float(by_hand), rel=1e-12)
+
+
+def test_no_balance_without_the_depth_term():
+    """With the depth term off the caller applies correspondence_weight alone (src/train_segmentation.py:337-349): the lhp keys change
+    nothing, and the tuple has six elements."""
+    case = _weights_case()
+    _, inp, _ = M.case_reference(case.id)
+    cfg_on = M.case_cfg(case, depth_feat_correlation_loss=False)
+    cfg_off = M.case_cfg(case, depth_feat_correlation_loss=False, lhp=False, lhp_weight_balance=False)
+    on, off = M.oracle_f64(cfg_on, *inp), M.oracle_f64(cfg_off, *inp)
+    assert len(on[0]) == len(off[0]) == 6
+    assert float(on[1]) == float(off[1]) and torch.equal(on[2], off[2]) and torch.equal(on[3], off[3])
+    o = on[0]
+    by_hand = (cfg_on.pos_intra_weight * o[0] + cfg_on.pos_inter_weight * o[2] + cfg_on.neg_inter_weight * o[4].mean()) * \
+        cfg_on.correspondence_weight
+    assert float(on[1]) == pytest.approx(float(by_hand), rel=1e-12)
+
+
 def test_margin_report_sees_a_cd_at_the_bound():
     """Random code maps (what the other parity tests use) do not pass: cds at the bound, masks that flip in fp16."""
     case = M.CASES[0]
