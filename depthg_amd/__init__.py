@@ -3,6 +3,8 @@
 Public surface (mirrors the reference's Python operator surface for this path):
     ContrastiveCorrelationLoss   drop-in for src/modules.py:1221-1367; .cd_histograms(): the cd histograms of its last call without
                                  the un-reduced tensors (ops.corr_cd_hist; cfg.hist_freq / cfg.dg_hist_bins in the segmenter)
+    DepthContrastiveCorrelationLoss  src/modules.py:1370-1463: the same loss with the intra pair-set's feature correlation taken from the
+                                 depth-augmented features (cfg.use_depth_only_intra in the segmenter); one launch set (dg_corr_forward_intra_feats)
     ContrastiveCRFLoss           src/modules.py:1510-1542: forward() the reference's (B,n,n) tensor in plain torch, mean_loss() the training
                                  step's `crf_loss_fn(resize(img, 56), norm(resize(code, 56))).mean()` as fused HIP kernels (cfg.crf_weight)
     aug_alignment_loss           src/train_segmentation.py:400-411: the augmentation-alignment term as fused HIP kernels (cfg.aug_alignment_weight);
@@ -32,7 +34,7 @@ Public surface (mirrors the reference's Python operator surface for this path):
                                  and backward with Philox dropout (cfg.dg_fused_cross_attn)
     ops                          thin ctypes binding of the C ABI in include/depthg_corr.h
 """
-from .loss import ContrastiveCorrelationLoss  # noqa: F401
+from .loss import ContrastiveCorrelationLoss, DepthContrastiveCorrelationLoss  # noqa: F401
 from . import crf_loss  # noqa: F401
 from .crf_loss import ContrastiveCRFLoss  # noqa: F401
 from . import aug_loss  # noqa: F401
@@ -58,6 +60,6 @@ from . import featurizer  # noqa: F401
 from .featurizer import DinoFeaturizer, DinoFeaturizerWithDepth  # noqa: F401
 from . import segmenter  # noqa: F401
 
-__all__ = ["ContrastiveCorrelationLoss", "ContrastiveCRFLoss", "crf_loss", "aug_loss", "aug_alignment_loss", "crop_flip_coords", "rec_loss", "reconstruction_loss", "depth_encoder", "cross_attn", "cross_attention", "multihead_cross_attention", "depth_decay", "training", "metrics", "evaluation", "predict_and_score", "crf", "dense_crf",
+__all__ = ["ContrastiveCorrelationLoss", "DepthContrastiveCorrelationLoss", "ContrastiveCRFLoss", "crf_loss", "aug_loss", "aug_alignment_loss", "crop_flip_coords", "rec_loss", "reconstruction_loss", "depth_encoder", "cross_attn", "cross_attention", "multihead_cross_attention", "depth_decay", "training", "metrics", "evaluation", "predict_and_score", "crf", "dense_crf",
            "batched_crf", "knn", "lhp", "optim", "FusedAdam", "FusedAdamSet", "segmenter", "vit", "featurizer",
            "DinoFeaturizer", "DinoFeaturizerWithDepth"]

@@ -49,6 +49,8 @@ SIGNATURES = {
     "dg_corr_forward": (_I, [cp] + [vp] * 9 + [vp, _SZ, vp]),
     "dg_corr_forward_draw": (_I, [cp] + [vp] * 8 + [u64, vp, vp, vp, _SZ, vp]),
     "dg_corr_forward_masked": (_I, [cp] + [vp] * 8 + [i32, u64, vp, vp, vp, f32, vp, vp, _SZ, vp]),
+    "dg_corr_workspace_bytes_intra_feats": (_SZ, [cp]),
+    "dg_corr_forward_intra_feats": (_I, [cp] + [vp] * 8 + [i32, u64, vp, vp, vp, vp, _SZ, vp]),
     "dg_corr_backward": (_I, [cp] + [vp] * 6 + [vp, _SZ, vp]),
     "dg_corr_backward_total": (_I, [cp] + [vp] * 6 + [vp, _SZ, vp]),
     "dg_corr_materialize": (_I, [cp, i32, vp, vp, vp, _SZ, vp]),

@@ -24,7 +24,9 @@ enum class Hist { Rows, Blobs };                          // dg_corr_cd_hist: th
 enum class Masks { None, Sampled, DenseRaw, DenseSplit };   // exact clamp masks: the sign of the fp16 cd / k_cd_mask blocks inside the gather launch
                                                         // (small sample grids) / k_cd_mask on channel-last code maps / k_cd_mask3 on split fp16 operands
 
-struct PairSet {            // pair-set t: 0 intra, 1 inter, 2 + k negative k.  The stationary operand is operand 0
+struct PairSet {            // pair-set t: 0 intra, 1 inter, 2 + k negative k
+    int rop;                // the stationary operand: operand 0 - but for the intra pair-set of dg_corr_forward_intra_feats, whose two sides
+                            // are both the intra feature operand (Plan::xop)
     int op;                 // the streamed operand (pass A)
     int neg;                // k, or -1
     bool mapped;            // the streamed operand is read through negative k's batch map (DG_SHARED_COORDS: the negatives stream operand 0)
@@ -43,6 +45,14 @@ struct Operand {            // operand o: 0 anchors, 1 positives, 2 + k the nega
 struct Plan {
     int B, C, D, h, w, hc, wc, S, Sh, P, Ppad, KF, KD, C4, D4, N, T, nops, rf, nrb;     // (hc, wc): size of the code maps
     bool shared, depth, grad, pointwise;
+    // dg_corr_forward_intra_feats: operand xop = T (-1: none) is one more prepared operand - intra_feats sampled at coords1 as its F
+    // part (rows), operand 0's code as its C part (the code rows ARE operand 0's: rows_c[xop] == rows_c[0]) - and both sides of
+    // pair-set 0.  Its regions lie behind everything the plain plan lays out, whose offsets are the same with and without it: the
+    // backward, dg_corr_cd_hist and dg_corr_materialize plan from the descriptor alone and find what they read (gradient tiles, code
+    // rows, C parts and inverse norms of operand 0, tap records) where the forward left it.
+    int xop;
+    size_t nhwc_x;
+    int nopx() const { return nops + (xop >= 0 ? 1 : 0); }       // prepared operands
     // ---- routes
     Prep prep;
     Sampler sampler;                        // (Prep::Dense samples nothing: ChannelLast, the copies its DenseRaw masks read)
@@ -123,6 +133,8 @@ static void plan_tables(const dg_corr_desc* d, Plan& p) {
         s.neg = neg ? t - 2 : -1;
         s.mapped = neg && p.shared;
         s.op = s.mapped ? 0 : t;
+        s.rop = 0;
+        if (t == 0 && p.xop >= 0) s.op = s.rop = p.xop;
         s.shift = t == 0 ? d->shift_intra : (t == 1 ? d->shift_inter : d->shift_neg);
         s.slot_loss = neg ? DG_OUT_LOSS_NEG : t;
         s.slot_cd = neg ? DG_OUT_CD_NEG : DG_OUT_CD_INTRA + t;
@@ -131,6 +143,7 @@ static void plan_tables(const dg_corr_desc* d, Plan& p) {
         s.factor = neg ? p.grad_fn : p.grad_f;
     }
     for (int o = 0; o < p.nops; ++o) p.ops[o] = Operand{o == 1 ? 1 : 0, o == 0 ? 0 : 1, o >= 2 ? o - 2 : -1};
+    if (p.xop >= 0) p.ops[p.xop] = Operand{0, 0, -1};       // (srcsel: of its CODE; its features are intra_feats)
     const int L = (p.Ppad / 32) % 8;        // row tiles of the ragged last row block
     if (!(p.grad && p.KF == 384 && p.KD == 96 && p.D <= 80 && p.nrb > 1 && L >= 1 && L <= 4 && p.B % 8 == 0 && p.B <= 64)) return;
     int nkeys = 0, members[DG_MAX_JOBS] = {0};
@@ -152,8 +165,23 @@ static void plan_tables(const dg_corr_desc* d, Plan& p) {
     }
 }
 
-static int make_plan(const dg_corr_desc* d, Plan& p) {
+static int make_plan(const dg_corr_desc* d, Plan& p, bool intra_feats = false) {
     if (!d) return fail(DG_ERR_INVALID, "null descriptor");
+    p.xop = -1;
+    if (intra_feats) {
+        // what dg_corr_forward_intra_feats serves: the coordinates DepthContrastiveCorrelationLoss draws (random or salience, per
+        // image, src/modules.py:1415-1425) and its six-tuple (no depth term, :1458-1463)
+        if (d->flags & DG_IDENTITY_GRID) return fail(DG_ERR_UNSUPPORTED, "dg_corr_forward_intra_feats: DG_IDENTITY_GRID is not served (general coordinates only)");
+        if (d->flags & DG_SHARED_COORDS) return fail(DG_ERR_UNSUPPORTED, "dg_corr_forward_intra_feats: DG_SHARED_COORDS is not served (coordinates per image only)");
+        if (d->flags & DG_LINE_GRID) return fail(DG_ERR_UNSUPPORTED, "dg_corr_forward_intra_feats: DG_LINE_GRID is not served (the class draws S x S grids)");
+        if (d->flags & DG_DEPTH_TERM) return fail(DG_ERR_UNSUPPORTED, "dg_corr_forward_intra_feats: DG_DEPTH_TERM is not served (the class has no depth term)");
+        if ((d->code_h || d->code_w) && (d->code_h != d->h || d->code_w != d->w))
+            return fail(DG_ERR_UNSUPPORTED, "dg_corr_forward_intra_feats: code maps of %dx%d against feature maps of %dx%d are not served (one size only)",
+                        d->code_h, d->code_w, d->h, d->w);
+        if (d->C > 768) return fail(DG_ERR_UNSUPPORTED, "dg_corr_forward_intra_feats: C=%d > 768 feature channels are not served", d->C);
+        if (d->n_neg > DG_MAX_NEG - 1)
+            return fail(DG_ERR_UNSUPPORTED, "dg_corr_forward_intra_feats: n_neg=%d > %d (one operand slot holds the intra features)", d->n_neg, DG_MAX_NEG - 1);
+    }
     if (d->B < 1 || d->C < 1 || d->D < 1 || d->h < 1 || d->w < 1 || d->S < 1)
         return fail(DG_ERR_INVALID, "non-positive dimension in descriptor");
     if (d->n_neg < 0 || d->n_neg > DG_MAX_NEG) return fail(DG_ERR_UNSUPPORTED, "n_neg=%d outside [0,%d]", d->n_neg, DG_MAX_NEG);
@@ -280,6 +308,19 @@ static int make_plan(const dg_corr_desc* d, Plan& p) {
         p.part4 = take(p.small() ? (size_t)(p.T + 1) * B * p.nsplit * 16 : 0);
         p.om = take(p.small() ? (size_t)(p.T + 1) * 4 : 0);
     }
+    if (intra_feats) {
+        // the intra feature operand, behind everything else (Plan::xop)
+        const int x = p.xop = p.T;
+        p.nhwc_x = take(rows ? 0 : B * HW * p.C4 * 4);
+        p.rows_f[x] = take(want_rows ? B * p.P * frow : 0); p.rows_c[x] = p.rows_c[0];
+        p.op[x] = take(B * (p.Ppad / 32) * (size_t)p.blob);
+        p.inv[x] = take(B * p.Ppad * 4);
+        p.colpart[x] = take(B * (size_t)(p.Ppad / 32) * p.KF * 4);
+        p.bbar[x] = take(B * p.KF * 4);
+        p.bsplit[x] = take(B * 2 * p.KF * 2);
+        p.ccolpart[x] = take(B * (size_t)(p.Ppad / 32) * p.KD * 4);
+        p.csum[x] = take(B * p.KD * 4);
+    }
     p.total = off;
     plan_tables(d, p);
     return DG_OK;
@@ -290,6 +331,11 @@ extern "C" size_t dg_corr_workspace_bytes(const dg_corr_desc* desc) {
     if (make_plan(desc, p) != DG_OK) return 0;
     return p.total;
 }
+extern "C" size_t dg_corr_workspace_bytes_intra_feats(const dg_corr_desc* desc) {
+    Plan p{};
+    if (make_plan(desc, p, true) != DG_OK) return 0;
+    return p.total;
+}
 
 // Fills one helper job.  passB: the stationary operand is operand 2 of pair-set t.
 static DgJob helper_job(const Plan& p, char* ws, int t, bool passB, const int64_t* perms) {
@@ -297,14 +343,15 @@ static DgJob helper_job(const Plan& p, char* ws, int t, bool passB, const int64_
     memset(&j, 0, sizeof(j));
     const int o2 = p.ps[t].op;
     const int64_t* m2 = p.map_of(t, perms);
+    const int o1 = p.ps[t].rop;
     if (!passB) {
-        j.Rop = ws + p.op[0]; j.RcInv = f32(ws, p.inv[0]); j.ridx = nullptr;
+        j.Rop = ws + p.op[o1]; j.RcInv = f32(ws, p.inv[o1]); j.ridx = nullptr;
         j.Sop = ws + p.op[o2]; j.sidx = m2;
         j.Scsum = f32(ws, p.csum[o2]);
         j.center_on_lane = 1;
     } else {
         j.Rop = ws + p.op[o2]; j.RcInv = f32(ws, p.inv[o2]); j.ridx = m2;
-        j.Sop = ws + p.op[0]; j.sidx = nullptr;
+        j.Sop = ws + p.op[o1]; j.sidx = nullptr;
         j.center_on_lane = 0;
     }
     if (p.pointwise) { j.rvec = f32(ws, p.rvec[t]); j.rimg = f32(ws, p.rimg[t]); }
@@ -344,7 +391,7 @@ static void build_gs_jobs(const Plan& p, char* ws, const int64_t* perms, DgGsArg
         const int o2 = p.ps[t].op;
         DgGsJob& J = g.jobs[t - t0];
         J.G = reinterpret_cast<const uint16_t*>(ws + p.gbuf[t]);
-        J.Rop = ws + p.op[0]; J.ridx = nullptr;
+        J.Rop = ws + p.op[p.ps[t].rop]; J.ridx = nullptr;
         J.Sop = ws + p.op[o2]; J.sidx = p.map_of(t, perms);
         J.ScInv = f32(ws, p.inv[o2]);
         J.dS = f32(ws, p.dRB[t]);
@@ -412,11 +459,11 @@ static bool split_masks_enabled() {
 // the argument block of the fused small-grid kernel (dg_small.hip): forward, materialize and relaunch
 static void small_args(const Plan& p, const dg_corr_desc* d, char* ws, const int64_t* perms, DgSmallArgs& a) {
     memset(&a, 0, sizeof(a));
-    for (int o = 0; o < p.nops; ++o) { a.rowsF[o] = f32(ws, p.rows_f[o]); a.rowsC[o] = f32(ws, p.rows_c[o]); }
+    for (int o = 0; o < p.nopx(); ++o) { a.rowsF[o] = f32(ws, p.rows_f[o]); a.rowsC[o] = f32(ws, p.rows_c[o]); }
     a.T = p.T; a.B = p.B; a.P = p.P; a.Ppad = p.Ppad; a.C4 = (int)up(p.C, 128); a.D = p.D; a.D4 = p.D4; a.KD = p.KD;
     a.pointwise = p.pointwise ? 1 : 0; a.depth = p.depth ? 1 : 0; a.grad = p.grad ? 1 : 0;
     a.lo = p.lo; a.hi = p.hi;
-    for (int t = 0; t < p.T; ++t) { a.shift[t] = p.ps[t].shift; a.opS[t] = p.ps[t].op; a.sidx[t] = p.map_of(t, perms); }
+    for (int t = 0; t < p.T; ++t) { a.shift[t] = p.ps[t].shift; a.opR[t] = p.ps[t].rop; a.opS[t] = p.ps[t].op; a.sidx[t] = p.map_of(t, perms); }
     a.shift_depth = p.shift_depth;
     a.nz = f32(ws, p.nz); a.nzsum = f32(ws, p.nzsum);
     for (int t = 0; t <= p.T; ++t) a.dRA[t] = f32(ws, p.dRA[t]);
@@ -444,6 +491,7 @@ struct Fwd {
     const dg_corr_desc* desc;
     const float *feats, *feats_pos, *code, *code_pos, *depth, *coords1, *coords2;
     const int64_t* perms; const DrawArgs* draw; const FeatKeep* fk; const float* feat_inv;
+    const float* intra;                 // dg_corr_forward_intra_feats: the map behind operand p.xop's features
     float* out;
     char* ws; hipStream_t stream;
     // (the region object - it holds the side stream's lock - exists only on calls that use it: the exact-mask chain of the dense grid
@@ -460,6 +508,7 @@ static int fwd_validate(Fwd& c, void* workspace, size_t workspace_bytes) {
     if (c.feat_inv && p.prep != Prep::General)
         return fail(DG_ERR_INVALID, "dg_corr_forward_extnorm is the sampled-coordinate path above 160 positions: the identity grid takes "
                                     "DG_FEATS_UNIT, smaller grids any width as they are");
+    if (p.xop >= 0 && !c.intra) return fail(DG_ERR_UNSUPPORTED, "dg_corr_forward_intra_feats: intra_feats is null");
     if (c.fk && (c.fk->keep[0] || c.fk->keep[1]) && !p.dense())
         return fail(DG_ERR_UNSUPPORTED, "deferred feature dropout (feat_keep) is built for the identity grid only: "
                                         "with sampled coordinates hand the dropped features in");
@@ -498,6 +547,7 @@ static int plane_sample(const Fwd& c, bool bf16_rows) {
     for (int o = 0; o < p.nops; ++o) { t.rows[o][0] = f32(c.ws, p.rows_f[o]); t.rows[o][1] = f32(c.ws, p.rows_c[o]); }
     t.coords1 = c.coords1; t.coords2 = c.coords2; t.perms = c.perms;
     t.nops = p.nops; t.B = p.B; t.h = p.h; t.w = p.w; t.S = p.S; t.Sh = p.Sh; t.P = p.P;
+    if (p.xop >= 0) { t.src_x = c.intra; t.rows_x = f32(c.ws, p.rows_f[p.xop]); }
     DG_HIP(dg_launch_plane_sample(t, c.stream));
     return DG_OK;
 }
@@ -512,6 +562,7 @@ static int transpose_maps(const Fwd& c) {
     t.src[1] = c.feats_pos; t.dst[1] = f32(c.ws, p.nhwc_f[1]); t.K[1] = p.C; t.K4[1] = p.C4; t.HW[1] = p.h * p.w;
     t.src[2] = c.code; t.dst[2] = f32(c.ws, p.nhwc_c[0]); t.K[2] = p.D; t.K4[2] = p.D4; t.HW[2] = p.hc * p.wc;
     t.src[3] = c.code_pos; t.dst[3] = f32(c.ws, p.nhwc_c[1]); t.K[3] = p.D; t.K4[3] = p.D4; t.HW[3] = p.hc * p.wc;
+    if (p.xop >= 0) { t.nmaps = 5; t.src[4] = c.intra; t.dst[4] = f32(c.ws, p.nhwc_x); t.K[4] = p.C; t.K4[4] = p.C4; t.HW[4] = p.h * p.w; }
     DG_HIP(dg_launch_transpose(t, p.B, c.stream));
     return DG_OK;
 }
@@ -555,6 +606,10 @@ static int forward_small(const Fwd& c) {
             g.K4[nj] = p.C4; g.Kout[nj] = (int)up(p.C, 128); g.as_bf16[nj] = 1; g.h[nj] = p.h; g.w[nj] = p.w; ++nj;
             g.src[nj] = f32(c.ws, p.nhwc_c[srcsel]); g.coords[nj] = c.coords(o); g.srcidx[nj] = c.op_map(o); g.rows[nj] = f32(c.ws, p.rows_c[o]);
             g.K4[nj] = p.D4; g.Kout[nj] = p.D4; g.as_bf16[nj] = 0; g.h[nj] = p.hc; g.w[nj] = p.wc; ++nj;
+        }
+        if (p.xop >= 0) {        // the intra feature rows: one more job of this launch (the code rows are operand 0's)
+            g.src[nj] = f32(c.ws, p.nhwc_x); g.coords[nj] = c.coords1; g.srcidx[nj] = nullptr; g.rows[nj] = f32(c.ws, p.rows_f[p.xop]);
+            g.K4[nj] = p.C4; g.Kout[nj] = (int)up(p.C, 128); g.as_bf16[nj] = 1; g.h[nj] = p.h; g.w[nj] = p.w; ++nj;
         }
         g.njobs = nj; g.B = p.B; g.S = p.S; g.Sh = p.Sh; g.P = p.P;
         DG_HIP(dg_launch_gather_rows(g, c.stream));
@@ -622,11 +677,12 @@ static int fwd_operands_general(Fwd& c) {
     memset(&g, 0, sizeof(g));
     g.B = p.B; g.S = p.S; g.Sh = p.Sh; g.P = p.P; g.Ppad = p.Ppad; g.KF = p.KF; g.KD = p.KD;
     int nj = 0;
-    for (int o = 0; o < p.nops; ++o) {
+    for (int o = 0; o < p.nopx(); ++o) {
+        // (the intra feature operand: its own feature rows / map, and operand 0's code once more as the C part of its blobs)
         const int srcsel = p.ops[o].srcsel;
         const int64_t* idx = p.plane() ? nullptr : c.op_map(o);       // (the plane sampler's rows are sampled through the batch maps already)
         DgGatherJob& f = g.jobs[nj++];
-        f.src = p.plane() ? f32(c.ws, p.rows_f[o]) : f32(c.ws, p.nhwc_f[srcsel]); f.coords = c.coords(o); f.srcidx = idx;
+        f.src = p.plane() ? f32(c.ws, p.rows_f[o]) : f32(c.ws, o == p.xop ? p.nhwc_x : p.nhwc_f[srcsel]); f.coords = c.coords(o); f.srcidx = idx;
         f.blob = c.ws + p.op[o]; f.inv_norm = nullptr; f.colpart = f32(c.ws, p.colpart[o]);
         f.ext_inv = c.feat_inv ? c.feat_inv + (size_t)o * p.B * p.P : nullptr;
         f.K = p.C; f.K4 = p.C4; f.Kpad = p.KF; f.is_code = 0; f.h = p.h; f.w = p.w;
@@ -651,8 +707,8 @@ static int fwd_colmeans(Fwd& c) {
     const DgCorrArgs& a = c.a;
     DgColmeanArgs m;
     memset(&m, 0, sizeof(m));
-    m.nops = p.nops; m.B = p.B; m.P = p.P; m.Ppad = p.Ppad; m.KF = p.KF; m.KD = p.KD;
-    for (int o = 0; o < p.nops; ++o) {
+    m.nops = p.nopx(); m.B = p.B; m.P = p.P; m.Ppad = p.Ppad; m.KF = p.KF; m.KD = p.KD;
+    for (int o = 0; o < p.nopx(); ++o) {
         m.colpart[o] = p.pointwise ? f32(c.ws, p.colpart[o]) : nullptr; m.bbar[o] = f32(c.ws, p.bbar[o]);
         m.bsplit[o] = reinterpret_cast<__bf16*>(c.ws + p.bsplit[o]);
         m.ngroups[o] = p.Ppad / 32;              // feats partial column sums: one group per tile on both paths
@@ -712,7 +768,7 @@ static int fwd_rowmeans(Fwd& c) {
     memset(&r, 0, sizeof(r));
     r.B = p.B; r.P = p.P; r.Ppad = p.Ppad; r.KF = p.KF; r.KD = p.KD; r.njobs = p.T; r.abar = f32(c.ws, p.bbar[0]);
     for (int t = 0; t < p.T; ++t) {
-        r.jobs[t].A = c.ws + p.op[0]; r.jobs[t].aidx = nullptr;
+        r.jobs[t].A = c.ws + p.op[p.ps[t].rop]; r.jobs[t].aidx = nullptr;
         r.jobs[t].bbar = f32(c.ws, p.bbar[p.ps[t].op]); r.jobs[t].bidx = p.map_of(t, c.perms);
         r.jobs[t].bsplit = reinterpret_cast<const __bf16*>(c.ws + p.bsplit[p.ps[t].op]);
         r.jobs[t].rvec = f32(c.ws, p.rvec[t]); r.jobs[t].rimg = f32(c.ws, p.rimg[t]);
@@ -721,7 +777,11 @@ static int fwd_rowmeans(Fwd& c) {
         r.ncs = 2;
         for (int o = 0; o < 2; ++o) { r.cs_part[o] = f32(c.ws, p.ccolpart[o]); r.cs_out[o] = f32(c.ws, p.csum[o]); }
     }
-    if (p.fold) { r.stash = c.ws + p.op[0]; r.stash_off = FOLD_STASH_OFF; }
+    if (p.xop >= 0) {         // job 0's stationary operand is its own: k_rowmean<true> (the kernel reads ONE set of blobs for all other jobs)
+        r.xA = c.ws + p.op[p.xop]; r.xabar = f32(c.ws, p.bbar[p.xop]);
+        r.jobs[0].A = c.ws + p.op[0];
+    }
+    if (p.fold) { r.stash = c.ws + p.op[p.ps[0].rop]; r.stash_off = FOLD_STASH_OFF; }
     DG_HIP(dg_launch_rowmean(r, c.stream));
     return DG_OK;
 }
@@ -791,9 +851,11 @@ static int corr_forward_impl(const dg_corr_desc* desc, const float* orig_feats, 
                              const float* orig_code, const float* orig_code_pos, const float* depth,
                              const float* coords1, const float* coords2, const int64_t* perms, const DrawArgs* draw,
                              float* out_scalars, void* workspace, size_t workspace_bytes, dg_stream_t stream_,
-                             const FeatKeep* fk = nullptr, const float* feat_inv = nullptr) {
+                             const FeatKeep* fk = nullptr, const float* feat_inv = nullptr, bool intra_entry = false,
+                             const float* intra_feats = nullptr) {
     Fwd c;
-    if (int rc = make_plan(desc, c.p)) return rc;
+    if (int rc = make_plan(desc, c.p, intra_entry)) return rc;
+    c.intra = intra_feats;
     const Plan& p = c.p;
     c.desc = desc; c.feats = orig_feats; c.feats_pos = orig_feats_pos; c.code = orig_code; c.code_pos = orig_code_pos; c.depth = depth;
     c.coords1 = coords1; c.coords2 = coords2; c.perms = perms; c.draw = draw; c.fk = fk; c.feat_inv = feat_inv; c.out = out_scalars;
@@ -861,6 +923,18 @@ extern "C" int dg_corr_forward_draw(const dg_corr_desc* desc, const float* orig_
     const DrawArgs draw{perms_out, seed, static_cast<unsigned long long*>(perm_state)};
     return corr_forward_impl(desc, orig_feats, orig_feats_pos, orig_code, orig_code_pos, depth, coords1, coords2, perms_out, &draw,
                              out_scalars, workspace, workspace_bytes, stream_);
+}
+
+extern "C" int dg_corr_forward_intra_feats(const dg_corr_desc* desc, const float* orig_feats, const float* orig_feats_pos,
+                                           const float* orig_code, const float* orig_code_pos, const float* depth,
+                                           const float* coords1, const float* coords2, int64_t* perms, int32_t draw_perms, uint64_t seed,
+                                           void* perm_state, const float* intra_feats,
+                                           float* out_scalars, void* workspace, size_t workspace_bytes, dg_stream_t stream_) {
+    if (!desc) return fail(DG_ERR_INVALID, "null descriptor");
+    if (desc->n_neg > 0 && !perms) return fail(DG_ERR_INVALID, "perms is null with n_neg=%d", desc->n_neg);
+    const DrawArgs draw{perms, seed, static_cast<unsigned long long*>(perm_state)};
+    return corr_forward_impl(desc, orig_feats, orig_feats_pos, orig_code, orig_code_pos, depth, coords1, coords2, perms,
+                             draw_perms ? &draw : nullptr, out_scalars, workspace, workspace_bytes, stream_, nullptr, nullptr, true, intra_feats);
 }
 
 extern "C" int dg_corr_forward_masked(const dg_corr_desc* desc, const float* orig_feats, const float* orig_feats_pos,

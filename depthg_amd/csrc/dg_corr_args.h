@@ -180,10 +180,11 @@ struct DgFinishArgs {
 
 // ---- argument blocks of the helper kernels (one definition shared by kernels and host API)
 
-struct DgTransposeArgs {    // NCHW (B,K,h,w) fp32 -> NHWC (B,h*w,K4) fp32 for up to four maps in one launch
-    const float* src[4];
-    float* dst[4];
-    int32_t K[4], K4[4], HW[4];      // per map: channels, padded channels, pixels (the code maps may differ in size from the feature maps)
+struct DgTransposeArgs {    // NCHW (B,K,h,w) fp32 -> NHWC (B,h*w,K4) fp32 for up to five maps in one launch (the fifth: intra_feats of
+                            // dg_corr_forward_intra_feats)
+    const float* src[5];
+    float* dst[5];
+    int32_t K[5], K4[5], HW[5];      // per map: channels, padded channels, pixels (the code maps may differ in size from the feature maps)
     int32_t nmaps;
 };
 
@@ -243,6 +244,10 @@ struct DgPlaneArgs {        // k_plane_sample: sample() of all operands straight
     int32_t nops, B, h, w, S, Sh, P;
     int32_t tap_consumers;   // (set by the launcher) consumers whose tap table is held in LDS together
     int32_t feats_bf16;      // 1: rows[.][0] are bf16 (B, P, K4) - the fused small-grid kernel's input (K4 then a multiple of 8)
+    // dg_corr_forward_intra_feats (k_plane_sample<CH, true> only): a FIFTH map of the feature maps' shape, sampled at coords1 by its
+    // image's own blocks into one more set of feature rows - the intra pair-set's feature operand (src/modules.py:1433, 1437-1438)
+    const float* src_x;      // intra_feats (B,K[0],h,w) fp32, or null
+    float* rows_x;           // (B, P, K4[0]) rows, fp32 or bf16 as rows[.][0]
 };
 
 // One row of super_perm (src/modules.py:1184-1188): rank of every key inside the row (ties by index) = position of that index in
@@ -326,6 +331,8 @@ struct DgSmallArgs {
     const void* rowsF[DG_MAX_NEG + 2];    // [operand][B][P][C4] sampled feature rows, bf16 (k_plane_sample / k_gather_rows), C4 a multiple of 128 (whole chunks), channels C..C4-1 zero
     const float* rowsC[DG_MAX_NEG + 2];   // [operand][B][P][D4] sampled code rows
     int32_t T, B, P, Ppad, C4, D, D4, KD; // T pair-sets; KD in {96, 128}: padded code width of the gradient tiles
+    int32_t opR[DG_MAX_NEG + 2];          // operand whose FEATURE rows are the stationary side of pair-set t: 0, or the intra feature operand of
+                                          // dg_corr_forward_intra_feats for t = 0 (the stationary CODE rows are always operand 0's)
     int32_t opS[DG_MAX_NEG + 2];          // streamed operand of pair-set t (t itself; with DG_SHARED_COORDS the negatives stream operand 0 ...
     const int64_t* sidx[DG_MAX_NEG + 2];  // ... of image sidx[t][n] - the batch map - instead of image n; null: image n)
     int32_t pointwise, depth, grad;
@@ -472,6 +479,8 @@ struct DgRowmeanArgs {
     DgRowmeanJob jobs[DG_MAX_NEG + 2];
     int32_t njobs, B, P, Ppad, KF, KD;
     const float* abar;           // [B][KF] mean normalised feats of operand 1
+    const char* xA;              // k_rowmean<true> (dg_corr_forward_intra_feats): job 0's stationary blobs and their mean feats, walked by the
+    const float* xabar;          //   blocks of blockIdx.z == 1; the blocks of z == 0 then serve the jobs 1 .. njobs - 1
     char* stash;                 // non-null: k_corr2 FOLD - job 0's row means r also go, as -r / 2 in an fp16 pair (hi, 2048 lo), into k = 0, 1
     int32_t stash_off;           //   of position p's granule of the operand-1 blobs' C part, k-step stash_off / 1024 (all channel padding)
     const float* cs_part[2];     // ncs > 0: block x == Ppad/32 + 1 of an image also reduces the code column sums of the dense

@@ -322,7 +322,10 @@ hipError_t dg_launch_gather(const DgGatherArgs& a_in, int maxK4, hipStream_t s) 
 // leaves no launch whose time scales with B*h*w*C twice.
 // grid (sum over maps of ceil(K4 / 32), B), block 1024, dynamic LDS 32 * (h*w + 1) floats.
 #define PLANE_THREADS 1024
-template <int CH>         // channels per block (32 or 16: smaller planes, more blocks per CU, their load and blend phases overlap)
+// XF (dg_corr_forward_intra_feats): behind the four maps' channel groups come those of a fifth map, intra_feats - blocks with ONE consumer,
+// their image's own positions at coords1, whose rows go to a.rows_x: the intra pair-set's feature operand, sampled by the launch that
+// samples orig_feats (no launch of its own).  The other callers launch <CH, false>, which names none of this.
+template <int CH, bool XF = false>         // channels per block (32 or 16: smaller planes, more blocks per CU, their load and blend phases overlap)
 __global__ __launch_bounds__(PLANE_THREADS) void k_plane_sample(const DgPlaneArgs a) {
     extern __shared__ __attribute__((aligned(16))) float pl[];          // [CH][HW + 1], then the tap table [consumers][P][8]
     __shared__ short l_o[(DG_MAX_NEG + 2) * 64 + 2], l_n[(DG_MAX_NEG + 2) * 64 + 2];
@@ -342,9 +345,11 @@ __global__ __launch_bounds__(PLANE_THREADS) void k_plane_sample(const DgPlaneArg
     }
     const int tid = threadIdx.x, HW = a.h * a.w, b = by;
     int m = 0, gy = bx;
-    while (m < 3 && gy >= (a.K4[m] + CH - 1) / CH) { gy -= (a.K4[m] + CH - 1) / CH; ++m; }
+    while (m < (XF ? 4 : 3) && gy >= (a.K4[m] + CH - 1) / CH) { gy -= (a.K4[m] + CH - 1) / CH; ++m; }
+    const bool xmap = XF && m == 4;              // the fifth map: the shape of map 0, consumed as operand 0's feature rows are
+    if (xmap) m = 0;
     const int K = a.K[m], K4 = a.K4[m], k0 = gy * CH, kind = m >> 1, pos_map = m & 1;
-    const float* __restrict__ src = a.src[m] + ((size_t)b * K + k0) * HW;
+    const float* __restrict__ src = (xmap ? a.src_x : a.src[m]) + ((size_t)b * K + k0) * HW;
     // planes -> LDS (rows of h*w contiguous floats; channels past K are zero)
     // (all loads of a thread are issued before the first LDS store: one memory latency per block, not one per element)
     if ((HW & 3) == 0 && (reinterpret_cast<uintptr_t>(src) & 15) == 0) {
@@ -397,11 +402,13 @@ __global__ __launch_bounds__(PLANE_THREADS) void k_plane_sample(const DgPlaneArg
     int pm0[DG_MAX_NEG];
 #pragma unroll
     for (int k = 0; k < DG_MAX_NEG; ++k)
-        pm0[k] = (!pos_map && k + 2 < a.nops && (tid & 63) < a.B) ? (int)a.perms[(size_t)k * a.B + (tid & 63)] : -1;
+        pm0[k] = (!pos_map && !xmap && k + 2 < a.nops && (tid & 63) < a.B) ? (int)a.perms[(size_t)k * a.B + (tid & 63)] : -1;
     for (int n0 = 0; n0 < a.B; n0 += 64) {
         const int nn = n0 + (tid & 63);
         int cnt = 0;
-        if (pos_map) {
+        if (xmap) {
+            if (n0 == 0) { if (tid == 0) { l_o[0] = 0; l_n[0] = (short)b; } cnt = 1; }     // (o = 0: coords1)
+        } else if (pos_map) {
             if (n0 == 0 && a.nops > 1) { if (tid == 0) { l_o[0] = 1; l_n[0] = (short)b; } cnt = 1; }
         } else {
             if (n0 == 0) { if (tid == 0) { l_o[0] = 0; l_n[0] = (short)b; } cnt = 1; }
@@ -458,13 +465,14 @@ __global__ __launch_bounds__(PLANE_THREADS) void k_plane_sample(const DgPlaneArg
             for (int e = 0; e < ne; ++e) {
                 const int o = l_o[e0 + e], n = l_n[e0 + e];
                 constexpr int PSTEP = PLANE_THREADS / CH;
-                float* rows = a.rows[o][kind] + ((size_t)n * a.P + ps) * K4 + k0 + c;
+                float* const rows_o = xmap ? a.rows_x : a.rows[o][kind];
+                float* rows = rows_o + ((size_t)n * a.P + ps) * K4 + k0 + c;
                 const float* tt = taps + ((size_t)e * a.P + ps) * 8;
                 const int rstep = PSTEP * K4;
                 if (chan && kind == 0 && a.feats_bf16) {
                     // feature rows for the fused small-grid kernel (dg_small.hip): bf16 - half the bytes written here and read there;
                     // that kernel multiplies bf16 rows anyway and takes its norms from the values it multiplies
-                    __bf16* rows16 = reinterpret_cast<__bf16*>(a.rows[o][0]) + ((size_t)n * a.P + ps) * K4 + k0 + c;
+                    __bf16* rows16 = reinterpret_cast<__bf16*>(rows_o) + ((size_t)n * a.P + ps) * K4 + k0 + c;
 #pragma unroll 2
                     for (int p = ps; p < a.P; p += PSTEP, tt += PSTEP * 8, rows16 += rstep) {
                         const f32x4 w = *reinterpret_cast<const f32x4*>(tt);
@@ -639,6 +647,7 @@ hipError_t dg_launch_plane_sample(const DgPlaneArgs& a, hipStream_t s) {
     constexpr int CH = 32;
     int gx = 0;
     for (int m = 0; m < 4; ++m) gx += (a.K4[m] + CH - 1) / CH;
+    if (a.src_x) gx += (a.K4[0] + CH - 1) / CH;
     // planes + the tap table of a batch of consumers (32 bytes per position), as many consumers as the LDS takes (<= 8)
     const int plane_bytes = ((CH * (a.h * a.w + 1) + 3) & ~3) * 4;
     DgPlaneArgs a2 = a;
@@ -646,6 +655,13 @@ hipError_t dg_launch_plane_sample(const DgPlaneArgs& a, hipStream_t s) {
     if (a2.tap_consumers < 1) return hipErrorInvalidValue;
     if (a2.tap_consumers > 8) a2.tap_consumers = 8;
     const int smem = plane_bytes + a2.tap_consumers * a.P * 32;
+    if (a.src_x) {
+        if (!a.rows_x) return hipErrorInvalidValue;
+        hipError_t e = dg_set_max_smem(reinterpret_cast<const void*>(k_plane_sample<CH, true>), smem);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL((k_plane_sample<CH, true>), dim3(gx, a.B), dim3(PLANE_THREADS), smem, s, a2);
+        return hipGetLastError();
+    }
     hipError_t e = dg_set_max_smem(reinterpret_cast<const void*>(k_plane_sample<CH>), smem);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_plane_sample<CH>, dim3(gx, a.B), dim3(PLANE_THREADS), smem, s, a2);
@@ -1150,13 +1166,19 @@ hipError_t dg_launch_colmean(const DgColmeanArgs& a, hipStream_t s) {
 // 32x32 MFMA chain over K with the tile's swizzled bf16 rows as A (read once for all pair-sets) and, as B, one column
 // per pair-set holding bbar split into two bf16 halves (columns t and 16 + t: hi + lo keeps ~16 mantissa bits, the
 // products with the bf16 rows are exact in the fp32 accumulator).  grid (Ppad/32, B), block 64.
+// XJ (dg_corr_forward_intra_feats): job 0 has a stationary operand of its own (a.xA, mean feats a.xabar): the grid is doubled along z,
+// the blocks of z == 1 walk those blobs for job 0 alone and the blocks of z == 0 serve the other jobs - every column of the MFMA is
+// one job's, so each job's bits are those of the plain kernel on the same operands.  The other callers launch <false>.
 #define ROWMEAN_WAVES 4
+template <bool XJ = false>
 __global__ __launch_bounds__(64 * ROWMEAN_WAVES) void k_rowmean(const DgRowmeanArgs a) {
     extern __shared__ __attribute__((aligned(16))) char rm_smem[];     // the tile's F part (32 bf16 rows, dg_f_off layout)
     const int tile = blockIdx.x, n = blockIdx.y, tid = threadIdx.x, lane = tid & 63, c = lane & 31, h = lane >> 5;
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int KF = a.KF, nt = a.Ppad / 32;
+    const bool xz = XJ && blockIdx.z == 1;
     if (tile == nt + 1) {                                 // code column sums of the dense operands (DgDenseArgs.code_split)
+        if (xz) return;
         for (int o = 0; o < a.ncs; ++o) colsum_reduce(a.cs_part[o], n, nt, a.KD, 1.f, a.cs_out[o]);
         return;
     }
@@ -1165,9 +1187,11 @@ __global__ __launch_bounds__(64 * ROWMEAN_WAVES) void k_rowmean(const DgRowmeanA
         // reference's fd.mean() before centering, src/modules.py:1237): sum_p a_p . bbar = P * abar . bbar, one K-long dot per
         // pair-set; the waves split the pair-sets (it used to trail the tile-0 wave as a serial chain of njobs dots)
         float av[12];                                   // KF <= 768: 12 values per lane
+        const float* const abar = xz ? a.xabar : a.abar;
 #pragma unroll
-        for (int j = 0; j < 12; ++j) av[j] = lane + 64 * j < KF ? a.abar[(size_t)n * KF + lane + 64 * j] : 0.f;
+        for (int j = 0; j < 12; ++j) av[j] = lane + 64 * j < KF ? abar[(size_t)n * KF + lane + 64 * j] : 0.f;
         for (int t = wid; t < a.njobs; t += ROWMEAN_WAVES) {
+            if (XJ && (t == 0) != xz) continue;
             const DgRowmeanJob& Jt = a.jobs[t];
             const float* bt = Jt.bbar + (size_t)(Jt.bidx ? (int)Jt.bidx[n] : n) * KF;
             float s = 0.f;
@@ -1181,7 +1205,7 @@ __global__ __launch_bounds__(64 * ROWMEAN_WAVES) void k_rowmean(const DgRowmeanA
     }
     const DgBlob L(a.KF, a.KD);
     const int jb = c & 15, lo = c >> 4;
-    const bool has = jb < a.njobs;
+    const bool has = jb < a.njobs && (!XJ || (jb == 0) == xz);
     const DgRowmeanJob& J = a.jobs[has ? jb : 0];
     const int nb = J.bidx ? (int)J.bidx[n] : n;
     // the four waves split K: wave w stages and multiplies the k-steps [w * nks, (w + 1) * nks) - a quarter of the F part
@@ -1189,7 +1213,7 @@ __global__ __launch_bounds__(64 * ROWMEAN_WAVES) void k_rowmean(const DgRowmeanA
     // 16-byte loads.  (One wave per tile left the kernel latency-bound: three waves per CU.)
     const int nks = KF / 16 / ROWMEAN_WAVES;                         // 2, 6 or 12 (KF in {128, 384, 768})
     const int pieces = L.off_c / 1024 / ROWMEAN_WAVES;               // = nks: 16 k-values x 32 rows x 2 B = 1 KiB per k-step
-    const char* fp = a.jobs[0].A + ((size_t)n * nt + tile) * L.bytes + lane * 16;
+    const char* fp = (xz ? a.xA : a.jobs[0].A) + ((size_t)n * nt + tile) * L.bytes + lane * 16;
     const uint32_t dst = lds_addr(rm_smem);
     for (int pc = wid * pieces; pc < (wid + 1) * pieces; ++pc) dma16(fp + pc * 1024, dst + pc * 1024);
     const __bf16* bb = J.bsplit + ((size_t)nb * 2 + lo) * KF + 8 * h;
@@ -1264,8 +1288,15 @@ hipError_t dg_launch_set_stash(char* blobs, int B, int ntiles, size_t blob_bytes
 hipError_t dg_launch_rowmean(const DgRowmeanArgs& a, hipStream_t s) {
     if (a.njobs > 16) return hipErrorInvalidValue;
     const int smem = max(32 * (a.KF / 8) * 16, (ROWMEAN_WAVES - 1) * 16 * 64 * 4);     // F part / partial accumulators
-    hipError_t e = dg_set_max_smem(reinterpret_cast<const void*>(k_rowmean), smem);
+    if (a.xA) {
+        if (!a.xabar || a.ncs > 0) return hipErrorInvalidValue;
+        hipError_t e = dg_set_max_smem(reinterpret_cast<const void*>(k_rowmean<true>), smem);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(k_rowmean<true>, dim3(a.Ppad / 32 + 1, a.B, 2), dim3(64 * ROWMEAN_WAVES), smem, s, a);
+        return hipGetLastError();
+    }
+    hipError_t e = dg_set_max_smem(reinterpret_cast<const void*>(k_rowmean<false>), smem);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_rowmean, dim3(a.Ppad / 32 + 1 + (a.ncs > 0 ? 1 : 0), a.B), dim3(64 * ROWMEAN_WAVES), smem, s, a);
+    hipLaunchKernelGGL(k_rowmean<false>, dim3(a.Ppad / 32 + 1 + (a.ncs > 0 ? 1 : 0), a.B), dim3(64 * ROWMEAN_WAVES), smem, s, a);
     return hipGetLastError();
 }

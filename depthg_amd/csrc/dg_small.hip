@@ -84,6 +84,7 @@ __global__ __launch_bounds__(SM_THREADS) __attribute__((amdgpu_waves_per_eu(1, 1
     const int NR = nsplit == 1 ? NS : (sp == 0 ? 3 : 2);
     const bool grad = a.grad != 0 && !a.mat;
     const int opS = depth_job ? 0 : a.opS[t];
+    const int opR = depth_job ? 0 : a.opR[t];       // (feature rows of the stationary side: operand 0 but for dg_corr_forward_intra_feats' intra pair-set)
     const int nS = (!depth_job && a.sidx[t]) ? (int)a.sidx[t][n] : n;       // image whose rows the streamed operand is (shared coordinates: the batch map)
 #ifdef DG_DEVTOOLS
     unsigned long long stp[12];
@@ -195,7 +196,7 @@ __global__ __launch_bounds__(SM_THREADS) __attribute__((amdgpu_waves_per_eu(1, 1
         const bool live = j < NR + NS;
         const int pos = live ? pass_pos(j) : 0;
         ok[j] = live && pos < P && !depth_job;
-        srcp[j] = static_cast<const __bf16*>(a.rowsF[j < NR ? 0 : opS]) + ((size_t)(j < NR ? n : nS) * P + (ok[j] ? pos : 0)) * C4;
+        srcp[j] = static_cast<const __bf16*>(a.rowsF[j < NR ? opR : opS]) +((size_t)(j < NR ? n : nS) * P + (ok[j] ? pos : 0)) * C4;
     }
     // The feature rows arrive as bf16 (the sampler's output): a chunk goes to LDS as it is, and the squared norms are taken from the
     // values that are multiplied.  Piece u of a thread = channels 64 u + 8 gran .. + 7 of its row.

@@ -62,9 +62,16 @@ class _CorrLossFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, orig_code, orig_code_pos, orig_feats, orig_feats_pos, depth, coords1, coords2, perms, desc, holder):
-        ws = ops.alloc_workspace(desc, orig_feats.device)
+        intra = holder.get("intra_feats")
+        ws = ops.alloc_workspace(desc, orig_feats.device) if intra is None else ops.alloc_workspace_intra_feats(desc, orig_feats.device)
         fk = holder.get("feat_keep")
-        if holder.get("feat_inv") is not None:     # one channel chunk of wider maps on sampled coordinates (forward_with: `wide`)
+        if intra is not None:              # the intra pair-set correlates a second feature map (DepthContrastiveCorrelationLoss)
+            drew = perms is None
+            out, perms = ops.corr_forward_intra_feats(desc, orig_feats, orig_feats_pos, orig_code, orig_code_pos, coords1, coords2,
+                                                      perms, intra, ws, holder.get("draw_state"))
+            if drew:
+                holder["perms"] = perms
+        elif holder.get("feat_inv") is not None:     # one channel chunk of wider maps on sampled coordinates (forward_with: `wide`)
             out = ops.corr_forward_extnorm(desc, orig_feats, orig_feats_pos, orig_code, orig_code_pos, depth, coords1, coords2,
                                            perms, holder["feat_inv"], ws)
         elif fk is not None:               # Dropout2d of the feature maps applied inside the operand preparation (identity grid)
@@ -410,7 +417,7 @@ class ContrastiveCorrelationLoss(nn.Module):
                              depth_hw=tuple(call.depth.shape[-2:]) if (call.depth is not None and dt) else (0, 0),
                              identity_grid=call.identity_grid, weights=weights, line_grid=call.line_grid,
                              code_hw=call.code_hw, exact_masks=bool(getattr(cfg, "dg_exact_masks", False)), feats_unit=unit)
-        holder = {"draw_state": call.draw_state, "feat_keep": keep, "feat_inv": feat_inv}
+        holder = {"draw_state": call.draw_state, "feat_keep": keep, "feat_inv": feat_inv, "intra_feats": getattr(call, "intra_feats", None)}
         out, total = _CorrLossFunction.apply(call.code, call.code_pos, f_a, f_b, call.depth if dt else None,
                                              call.coords1, call.coords2, call.perms, desc, holder)
         if call.perms is None:
@@ -493,3 +500,96 @@ class ContrastiveCorrelationLoss(nn.Module):
             dd, _ = ops.corr_materialize(desc, -1, ws)
             res = res + (out[3], dd)
         return res
+
+
+class DepthContrastiveCorrelationLoss(ContrastiveCorrelationLoss):
+    """Drop-in for the reference class of the same name (src/modules.py:1370-1463): ContrastiveCorrelationLoss with ONE difference -
+    the self-correlation (intra) pair-set takes its feature correlation from `depth_aug_feats` sampled at coords1 (:1433,
+    1437-1438); the inter pair-set and the negatives keep `orig_feats` / `orig_feats_pos`.  Same constructor, same call signature,
+    the 6-tuple with ContrastiveCorrelationLoss's conventions (detached cd tensors, `neg_inter_loss` routed through its mean; both
+    cfg.dg_outputs modes), `.scalars`, `.total` and `.cd_histograms()`.  One launch set (dg_corr_forward_intra_feats): the second map
+    costs one more gathered operand, not a second call.
+
+    Coordinates as the reference draws them (:1415-1425): the five draws of the salience branch, else two `torch.rand`;
+    `cfg.depth_sampling` is ignored (the class has no depth to sample by), and so is cfg.dg_dense_grid.  The negatives' batch maps
+    are drawn as ContrastiveCorrelationLoss draws them.
+
+    `depth_aug_feats_pos` is validated for shape, dtype and device and then NOT read: the reference samples it (:1434) and never
+    uses the result.
+
+    Refused, each with the way out: feature maps wider than 768 channels, ops.DeferredDropout inputs
+    (`takes_deferred_dropout` is False), cfg.depth_feat_correlation_loss (the reference's caller would unpack eight values from
+    this class's six) and cfg.dg_graph_safe."""
+
+    def takes_deferred_dropout(self, feat_hw, code_hw=None) -> bool:
+        return False
+
+    def _refuse_cfg(self):
+        cfg = self.cfg
+        if getattr(cfg, "depth_feat_correlation_loss", False):
+            raise ValueError("depthg_amd: DepthContrastiveCorrelationLoss has no depth term - the reference returns six values and its "
+                             "caller would unpack eight (src/train_segmentation.py:310-329); set cfg.depth_feat_correlation_loss = False "
+                             "or use ContrastiveCorrelationLoss")
+        if getattr(cfg, "dg_graph_safe", False):
+            raise ValueError("depthg_amd: DepthContrastiveCorrelationLoss does not run under cfg.dg_graph_safe (its draws are torch's); "
+                             "set cfg.dg_graph_safe = False or use ContrastiveCorrelationLoss")
+
+    @staticmethod
+    def _check_aug(orig_feats, depth_aug_feats, depth_aug_feats_pos):
+        for name, t in (("orig_feats", orig_feats), ("depth_aug_feats", depth_aug_feats), ("depth_aug_feats_pos", depth_aug_feats_pos)):
+            if isinstance(t, ops.DeferredDropout):
+                raise ValueError(f"depthg_amd: DepthContrastiveCorrelationLoss takes feature tensors, `{name}` is an ops.DeferredDropout: "
+                                 f"pass `{name}.materialize()` (or call the head without defer_feats_dropout)")
+        for name, t in (("depth_aug_feats", depth_aug_feats), ("depth_aug_feats_pos", depth_aug_feats_pos)):
+            if not isinstance(t, torch.Tensor) or not t.is_floating_point():
+                raise ValueError(f"depthg_amd: `{name}` must be a floating-point tensor, got "
+                                 f"{t.dtype if isinstance(t, torch.Tensor) else type(t).__name__}")
+            if isinstance(orig_feats, torch.Tensor) and tuple(t.shape) != tuple(orig_feats.shape):
+                raise RuntimeError(f"depthg_amd: `{name}` {tuple(t.shape)} must have the shape of orig_feats {tuple(orig_feats.shape)} "
+                                   f"(one featurizer produces both)")
+            if isinstance(orig_feats, torch.Tensor) and t.device != orig_feats.device:
+                raise RuntimeError(f"depthg_amd: `{name}` lives on {t.device}, `orig_feats` on {orig_feats.device}: all inputs of one "
+                                   f"call must share a device")
+        if isinstance(orig_feats, torch.Tensor) and orig_feats.dim() == 4 and orig_feats.shape[1] > ops.BLOB_MAX_C:
+            raise ValueError(f"depthg_amd: DepthContrastiveCorrelationLoss takes feature maps of at most {ops.BLOB_MAX_C} channels, got "
+                             f"{orig_feats.shape[1]}: reduce the maps' width, or form the loss from two ContrastiveCorrelationLoss calls "
+                             f"(it is linear in the feature correlation)")
+
+    def _draw_coords(self, orig_feats, orig_feats_pos, orig_salience, orig_salience_pos, depth=None, depth_pos=None, same_maps=True):
+        if getattr(self.cfg, "use_salience", False):          # (the parent's first branch: the same five draws, src/modules.py:1415-1422)
+            return super()._draw_coords(orig_feats, orig_feats_pos, orig_salience, orig_salience_pos, None, None, same_maps)
+        coord_shape = [orig_feats.shape[0], int(self.cfg.feature_samples), int(self.cfg.feature_samples), 2]
+        return _rand_coords(coord_shape, orig_feats.device), _rand_coords(coord_shape, orig_feats.device), False
+
+    def forward(self, orig_feats, orig_feats_pos, orig_salience, orig_salience_pos, orig_code, orig_code_pos,
+                depth_aug_feats, depth_aug_feats_pos):
+        self._refuse_cfg()
+        self._check_aug(orig_feats, depth_aug_feats, depth_aug_feats_pos)
+        self._check_maps(orig_feats, orig_feats_pos, orig_code, orig_code_pos, None)
+        coords1, coords2, _ = self._draw_coords(orig_feats, orig_feats_pos, orig_salience, orig_salience_pos)
+        return self.forward_with(orig_feats, orig_feats_pos, orig_code, orig_code_pos, depth_aug_feats, depth_aug_feats_pos,
+                                 coords1, coords2, None, _checked=True)
+
+    def forward_with(self, orig_feats, orig_feats_pos, orig_code, orig_code_pos, depth_aug_feats, depth_aug_feats_pos,
+                     coords1, coords2, perms, _checked=False):
+        """Everything after the RNG draws: explicit coords (B,S,S,2) and perms ((n_neg, B), or None: drawn by the forward)."""
+        if not _checked:
+            self._refuse_cfg()
+            self._check_aug(orig_feats, depth_aug_feats, depth_aug_feats_pos)
+            self._check_maps(orig_feats, orig_feats_pos, orig_code, orig_code_pos, None)
+        if tuple(orig_code.shape[-2:]) != tuple(orig_feats.shape[-2:]):
+            raise ValueError(f"depthg_amd: DepthContrastiveCorrelationLoss needs code maps of the feature maps' size, got "
+                             f"{orig_code.shape[-2]}x{orig_code.shape[-1]} against {orig_feats.shape[-2]}x{orig_feats.shape[-1]}")
+        if tuple(coords1.shape) != (orig_feats.shape[0], int(self.cfg.feature_samples), int(self.cfg.feature_samples), 2):
+            raise ValueError(f"depthg_amd: DepthContrastiveCorrelationLoss takes (B,S,S,2) coordinates, got {tuple(coords1.shape)}")
+        self.__dict__["_intra_feats"] = ops._f32c(depth_aug_feats, "depth_aug_feats")
+        try:
+            return super().forward_with(orig_feats, orig_feats_pos, orig_code, orig_code_pos, None, coords1, coords2, perms,
+                                        _checked=True)
+        finally:
+            self.__dict__["_intra_feats"] = None
+
+    def _prepare(self, *args):
+        call = super()._prepare(*args)
+        call.intra_feats = self.__dict__["_intra_feats"]
+        return call

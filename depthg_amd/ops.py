@@ -210,6 +210,32 @@ def corr_forward_masked(desc, feats, feats_pos, code, code_pos, depth, coords1, 
                          workspace), perms
 
 
+def alloc_workspace_intra_feats(desc, device):
+    """The workspace of corr_forward_intra_feats: dg_corr_workspace_bytes_intra_feats - the plain call's regions, then the intra
+    feature operand's (the backward, cd_hist and materialize take it as they take the plain one)."""
+    n = _lib.load().dg_corr_workspace_bytes_intra_feats(ctypes.byref(desc))
+    if n == 0:
+        _lib.check(-1, "dg_corr_workspace_bytes_intra_feats")
+    return _empty(n, torch.uint8, device)
+
+
+def corr_forward_intra_feats(desc, feats, feats_pos, code, code_pos, coords1, coords2, perms, intra_feats, workspace, state=None):
+    """dg_corr_forward_intra_feats: the forward whose intra pair-set correlates `intra_feats` (the shape of `feats`, sampled at
+    coords1) instead of `feats` (DepthContrastiveCorrelationLoss, src/modules.py:1427-1438).  perms None: drawn inside (as
+    corr_forward_draw).  `workspace`: alloc_workspace_intra_feats.  Returns (out, perms)."""
+    dev = feats.device
+    if intra_feats.dtype != torch.float32 or not intra_feats.is_contiguous() or intra_feats.device != dev or \
+            tuple(intra_feats.shape) != tuple(feats.shape):
+        raise ValueError(f"corr_forward_intra_feats: intra_feats must be contiguous fp32 {tuple(feats.shape)} on {dev}, got "
+                         f"{intra_feats.dtype} {tuple(intra_feats.shape)} on {intra_feats.device}")
+    draw, seed = int(perms is None), 0
+    if draw:
+        perms, seed = _drawn_perms(desc, dev, state, "corr_forward_intra_feats")
+    mid = (draw, seed, _ptr(state) if draw else None, _ptr(intra_feats))
+    return _corr_forward("dg_corr_forward_intra_feats", desc, (feats, feats_pos, code, code_pos, None, coords1, coords2), perms, mid,
+                         workspace), perms
+
+
 def _corr_backward(entry, desc, grad, coords1, coords2, perms, workspace, shape_code):
     dev = grad.device
     g_code = _empty(shape_code, torch.float32, dev)

@@ -55,7 +55,7 @@ from .evaluation import predict_and_score
 from .featurizer import DepthGuidance, DinoFeaturizer, DinoFeaturizerWithDepth, FrozenBackboneFeaturizer
 from .head import ClusterLookup, ProjectionHead, probe_cross_entropy
 from .lhp import LocalHiddenPositiveProjection, OriginalLocalHiddenPositiveProjection
-from .loss import ContrastiveCorrelationLoss
+from .loss import ContrastiveCorrelationLoss, DepthContrastiveCorrelationLoss
 from .metrics import UnsupervisedMetrics
 from .optim import FusedAdam, FusedAdamSet
 from .parallel import GradBucket
@@ -142,7 +142,14 @@ class UnsupervisedSegmenter(nn.Module):
         self.crf_loss_fn = ContrastiveCRFLoss(getattr(cfg, "crf_samples", 1000), getattr(cfg, "alpha", .5), getattr(cfg, "beta", .15),
                                               getattr(cfg, "gamma", .05), getattr(cfg, "w1", 10.0), getattr(cfg, "w2", 3.0),
                                               getattr(cfg, "shift", 0.0))
-        self.contrastive_corr_loss_fn = ContrastiveCorrelationLoss(cfg)               # :131 (shares cfg: the decay below mutates it)
+        # :79, :133-134: cfg.use_depth_only_intra swaps in DepthContrastiveCorrelationLoss, whose intra pair-set correlates the
+        # depth-augmented features; absent or False: the class, draws and launches are what they were
+        self.depth_only_intra = bool(getattr(cfg, "use_depth_only_intra", False))
+        if self.depth_only_intra:
+            self._refuse_depth_only_intra_combinations(cfg)
+            self.contrastive_corr_loss_fn = DepthContrastiveCorrelationLoss(cfg)
+        else:
+            self.contrastive_corr_loss_fn = ContrastiveCorrelationLoss(cfg)           # :131 (shares cfg: the decay below mutates it)
         for p in self.contrastive_corr_loss_fn.parameters():                          # :136
             p.requires_grad = False
         if getattr(cfg, "lhp", False):                                                 # :82-87
@@ -174,6 +181,21 @@ class UnsupervisedSegmenter(nn.Module):
             raise ValueError(f"depthg_amd: cfg.rec_weight > 0 cannot be combined with cfg.arch = 'dino_depth' under guidance "
                              f"{cfg.guidance!r}: there feats depend on trainable depth modules and the fused reconstruction kernels "
                              "have no gradient with respect to feats, unless cfg.dg_rec_feats_grad = True asks them for it")
+
+    @staticmethod
+    def _refuse_depth_only_intra_combinations(cfg):
+        """cfg.use_depth_only_intra with a configuration its loss cannot run on (asked at construction and in front of a step)."""
+        if getattr(cfg, "arch", "dino") != "dino_depth":
+            raise ValueError(f"depthg_amd: cfg.use_depth_only_intra needs cfg.arch = 'dino_depth': under arch "
+                             f"{getattr(cfg, 'arch', 'dino')!r} (\"dino\") the featurizer produces no depth-augmented features for the "
+                             "intra pair-set to correlate")
+        if getattr(cfg, "lhp", False):
+            raise ValueError("depthg_amd: cfg.use_depth_only_intra cannot be combined with cfg.lhp (the second loss call on the "
+                             "projected code is not built for DepthContrastiveCorrelationLoss); set cfg.lhp = False")
+        if getattr(cfg, "depth_feat_correlation_loss", False):
+            raise ValueError("depthg_amd: cfg.use_depth_only_intra cannot be combined with cfg.depth_feat_correlation_loss: "
+                             "DepthContrastiveCorrelationLoss returns six values and has no depth term; set "
+                             "cfg.depth_feat_correlation_loss = False")
 
     def forward(self, x):
         return self.net(x)[1]                                                          # :160-167
@@ -260,6 +282,8 @@ class UnsupervisedSegmenter(nn.Module):
         depth_pos = batch["depth_pos"] if self.use_depth else None
         if self.depth_arch:                                      # (cfg may have changed since construction)
             self._refuse_depth_arch_combinations(cfg)
+        if self.depth_only_intra:
+            self._refuse_depth_only_intra_combinations(cfg)
         if getattr(cfg, "aug_alignment_weight", 0) > 0:         # (asked before anything is launched)
             for key in ("img_aug", "coord_aug"):
                 if key not in batch:
@@ -282,7 +306,7 @@ class UnsupervisedSegmenter(nn.Module):
                 self.net.forward_pair(img, img_pos)                                                  # :194-200, :207-212
         elif self.depth_arch:
             # (feats carry a graph under guidance "sum" / "cross_attn"; the correlation loss reads them under no_grad, src/modules.py:1232-1234)
-            feats, code, _, attn = self.net((img, depth))                                            # :191-197
+            feats, code, image_feat, attn = self.net((img, depth))                                   # :191-197
             # (cfg.dg_rec_feats_grad: the reconstruction term reads the attached tensor, :391-398, and trains the depth modules through it)
             if getattr(cfg, "dg_rec_feats_grad", False) and getattr(cfg, "rec_weight", 0) > 0 and feats.requires_grad:
                 rec_feats = feats
@@ -294,7 +318,7 @@ class UnsupervisedSegmenter(nn.Module):
         loss = 0
         if cfg.correspondence_weight > 0:
             if self.depth_arch:
-                feats_pos, code_pos, _, _ = self.net((img_pos, depth_pos))                           # :205-210
+                feats_pos, code_pos, image_feat_pos, _ = self.net((img_pos, depth_pos))              # :205-210
                 feats_pos = feats_pos.detach()
             elif not paired:
                 feats_pos, code_pos, _ = self.net(img_pos)                                           # :207-212
@@ -303,7 +327,14 @@ class UnsupervisedSegmenter(nn.Module):
             salience_pos = batch["mask_pos"].to(torch.float32).squeeze(1) if cfg.use_salience else None
             use_depth_term = bool(cfg.depth_feat_correlation_loss)
             d_args = (depth, depth_pos) if use_depth_term else (None, None)                          # :242-292
-            out = self.contrastive_corr_loss_fn(feats, feats_pos, salience, salience_pos, code, code_pos, *d_args)
+            if self.depth_only_intra:
+                # :240-350 with the class of :133-134.  The reference's own call passes `depth=` / `depth_pos=` to parameters named
+                # depth_aug_feats / depth_aug_feats_pos and raises a TypeError; this is the call the names ask for: the frozen
+                # backbone's features (the featurizer's third output) as orig_feats, the depth-augmented ones (its first) as depth_aug_feats
+                out = self.contrastive_corr_loss_fn(image_feat.detach(), image_feat_pos.detach(), salience, salience_pos, code, code_pos,
+                                                    feats, feats_pos)
+            else:
+                out = self.contrastive_corr_loss_fn(feats, feats_pos, salience, salience_pos, code, code_pos, *d_args)
             # :229-231, :298-301: every cfg.hist_freq steps the reference histograms the three un-reduced cd tensors - here one small
             # launch on the operands this call left in its workspace (in front of the LHP call, which runs the loss again)
             hist_freq = getattr(cfg, "hist_freq", None)

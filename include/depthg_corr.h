@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define DG_VERSION 118   /* 118: dg_corr_cd_hist, the three dg_crfloss and the three dg_augalign entry points (more exports under the same number: the layouts and meanings of every earlier entry point are unchanged, and a binding that declares a new symbol refuses a library without it when it loads), dg_sampled_sumsq, dg_corr_forward_extnorm (feature maps wider than 768 channels on SAMPLED grids above 160 positions, in channel chunks); 117: DG_FEATS_UNIT, dg_normalize_split (feature maps wider than 768 channels on the dense identity grid, in chunks of the width the operand kernels hold: the loss is linear in the feature correlation); 116: dg_prof_main_span takes FOUR words (+ the workgroups' lifetimes in shader cycles and wall ticks: the clock the CUs held); 115: dg_corr_intra_folded; 114: dg_fps_coords_pair takes a workspace (dg_fps_workspace_bytes(2 B, h, w): the pooled depth maps, written by a launch over the whole chip in front of the sampler), dg_corr_materialize_shared, dg_prof_main_span (the fused correlation launch's execution span inside a replayed step), sample grids of <= 160 positions at any feature width (fused small-grid kernel); 113: dg_corr_forward_masked; 112: dg_rand_coords_state; 111: dg_head_forward_pair / dg_head_backward_pair; 110: dg_fps_coords_pair; 109: dg_knn_similarities; 108: dg_corr_desc.code_h / code_w (code maps of another resolution than the feature maps: the FeaturePyramidNet producer, src/modules.py:732-766), dg_corr_desc.flags DG_EXACT_MASKS; 107: dg_head_*, dg_cluster_lookup_*, dg_probe_ce_*; 106: dg_corr_main_kernel_name; 105: dg_corr_forward_draw; 104: dg_lhp_map_forward / dg_lhp_map_backward; 103: dg_super_perms_state; 102: DG_LINE_GRID, dg_salience_coords, dg_simple_depth_coords; 101: total weights, DG_OUT_TOTAL */
+#define DG_VERSION 118   /* 118: dg_corr_forward_intra_feats + dg_corr_workspace_bytes_intra_feats, dg_corr_cd_hist, the three dg_crfloss and the three dg_augalign entry points (more exports under the same number: the layouts and meanings of every earlier entry point are unchanged, and a binding that declares a new symbol refuses a library without it when it loads), dg_sampled_sumsq, dg_corr_forward_extnorm (feature maps wider than 768 channels on SAMPLED grids above 160 positions, in channel chunks); 117: DG_FEATS_UNIT, dg_normalize_split (feature maps wider than 768 channels on the dense identity grid, in chunks of the width the operand kernels hold: the loss is linear in the feature correlation); 116: dg_prof_main_span takes FOUR words (+ the workgroups' lifetimes in shader cycles and wall ticks: the clock the CUs held); 115: dg_corr_intra_folded; 114: dg_fps_coords_pair takes a workspace (dg_fps_workspace_bytes(2 B, h, w): the pooled depth maps, written by a launch over the whole chip in front of the sampler), dg_corr_materialize_shared, dg_prof_main_span (the fused correlation launch's execution span inside a replayed step), sample grids of <= 160 positions at any feature width (fused small-grid kernel); 113: dg_corr_forward_masked; 112: dg_rand_coords_state; 111: dg_head_forward_pair / dg_head_backward_pair; 110: dg_fps_coords_pair; 109: dg_knn_similarities; 108: dg_corr_desc.code_h / code_w (code maps of another resolution than the feature maps: the FeaturePyramidNet producer, src/modules.py:732-766), dg_corr_desc.flags DG_EXACT_MASKS; 107: dg_head_*, dg_cluster_lookup_*, dg_probe_ce_*; 106: dg_corr_main_kernel_name; 105: dg_corr_forward_draw; 104: dg_lhp_map_forward / dg_lhp_map_backward; 103: dg_super_perms_state; 102: DG_LINE_GRID, dg_salience_coords, dg_simple_depth_coords; 101: total weights, DG_OUT_TOTAL */
 
 /* flags of dg_corr_desc.flags (names follow the cfg keys read at src/modules.py:1236-1352) */
 #define DG_POINTWISE      (1u << 0)  /* cfg.pointwise: spatial centering of fd (modules.py:1236-1239) */
@@ -176,6 +176,41 @@ int dg_corr_forward_masked(const dg_corr_desc* desc,
                            void* perm_state, const float* feat_keep, const float* feat_pos_keep, float keep_scale,
                            float* out_scalars,
                            void* workspace, size_t workspace_bytes, dg_stream_t stream);
+
+/*
+ * The forward of DepthContrastiveCorrelationLoss (src/modules.py:1370-1463; the lines that differ: :1427-1438) - dg_corr_forward
+ * with ONE difference: the self-correlation (intra) pair-set takes its feature correlation fd from a second feature map,
+ *  intra_feats : fp32 (B,C,h,w), the shape of orig_feats - the reference's depth_aug_feats -
+ * which is sampled at coords1 and normalised exactly as orig_feats is (:1433) and is the feature operand of BOTH sides of pair-set 0
+ * (pos_intra, :1437-1438) and of nothing else.  The inter pair-set and the negatives keep orig_feats / orig_feats_pos; every code
+ * operand, the pointwise centering, shifts, clamp, out_scalars and DG_OUT_TOTAL are dg_corr_forward's.  (The reference also samples
+ * depth_aug_feats_pos, :1434, and never reads the result: this entry does not take it.)
+ * One entry for given and drawn batch maps, as dg_corr_forward_masked: draw_perms != 0: perms / seed / perm_state are perms_out / seed
+ * / perm_state of dg_corr_forward_draw; 0: perms is read, as by dg_corr_forward.
+ * Preparation: intra_feats is gathered by the launches that gather orig_feats (more blocks of the sampler's launch and of the
+ * operand-building launch: no launch of its own) into one more prepared operand, to which the plan points pair-set 0.  Both sides of
+ * the pair-set are the same operand, so its gradient is formed by symmetry as before; dg_corr_backward, dg_corr_backward_total,
+ * dg_corr_cd_hist and dg_corr_materialize (cd of every pair-set, loss of the inter pair-set and the negatives - NOT the un-reduced
+ * intra loss, which they would form from orig_feats) are called with the same descriptor and workspace and are unchanged: the backward
+ * reads no feature map and cd depends on none.
+ * Workspace: dg_corr_workspace_bytes_intra_feats(desc) bytes - the descriptor cannot tell the two entries apart, so the extra
+ * operand has a query of its own; it lies behind the regions of dg_corr_workspace_bytes(desc), whose result and layout are unchanged.
+ * Served: general coordinates per image on every route the plan picks for them (the fused small-grid kernel up to 160 positions,
+ * the blob kernels above), C <= 768, D <= 128, n_neg <= DG_MAX_NEG - 1 (the operand tables hold DG_MAX_NEG + 2 operands, one of them
+ * now the intra features), DG_NEED_GRAD on and off, every clamp / pointwise / stabalize combination.  DG_ERR_UNSUPPORTED, with the
+ * reason in dg_last_error(): DG_IDENTITY_GRID, DG_SHARED_COORDS, DG_LINE_GRID, DG_DEPTH_TERM (the reference class draws random or
+ * salience coordinates only and has no depth term; `depth` is not read), a code-map size other than (h, w), intra_feats == NULL.
+ * No atomics; two calls give the same bits; with intra_feats == orig_feats (a copy) every output has the bits of dg_corr_forward.
+ */
+size_t dg_corr_workspace_bytes_intra_feats(const dg_corr_desc* desc);
+int dg_corr_forward_intra_feats(const dg_corr_desc* desc,
+                                const float* orig_feats, const float* orig_feats_pos,
+                                const float* orig_code, const float* orig_code_pos,
+                                const float* depth,
+                                const float* coords1, const float* coords2, int64_t* perms, int32_t draw_perms, uint64_t seed,
+                                void* perm_state, const float* intra_feats,
+                                float* out_scalars,
+                                void* workspace, size_t workspace_bytes, dg_stream_t stream);
 
 /*
  * Backward (replaces autograd through helper()/sample(), SURVEY.md section 9 "Gradient"):
