@@ -16,7 +16,9 @@ Public surface (mirrors the reference's Python operator surface for this path):
                                  src/train_segmentation.py:240-350)
     metrics                      UnsupervisedMetrics (src/utils.py:202-319): confusion matrix on the GPU, summed over DP ranks
     evaluation                   predict_and_score: the probes' predictions at label resolution and their confusion counts
-                                 (src/train_segmentation.py:471-499, src/eval_segmentation.py:146-170, run_crf for the CRF)
+                                 (src/train_segmentation.py:471-499, src/eval_segmentation.py:146-170, run_crf for the CRF);
+                                 segment: label-free inference (src/demo_segmentation.py:59-78) - byte label maps and painted
+                                 images of every image from one fused HIP launch pair; `python -m depthg_amd.demo` is its command line
     crf                          dense_crf / batched_crf (src/crf.py, src/eval_segmentation.py:55-60): mean-field dense CRF in HIP
     knn                          image-level nearest-neighbour table: search, file format, online pick (src/precompute_knns.py)
     lhp                          LocalHiddenPositiveProjection with depth propagation (src/modules.py:140-339)
@@ -48,7 +50,7 @@ from . import depth_decay  # noqa: F401
 from . import training  # noqa: F401
 from . import metrics  # noqa: F401
 from . import evaluation  # noqa: F401
-from .evaluation import predict_and_score  # noqa: F401
+from .evaluation import predict_and_score, segment  # noqa: F401
 from . import crf  # noqa: F401
 from .crf import batched_crf, dense_crf  # noqa: F401
 from . import knn  # noqa: F401
@@ -60,6 +62,6 @@ from . import featurizer  # noqa: F401
 from .featurizer import DinoFeaturizer, DinoFeaturizerWithDepth  # noqa: F401
 from . import segmenter  # noqa: F401
 
-__all__ = ["ContrastiveCorrelationLoss", "DepthContrastiveCorrelationLoss", "ContrastiveCRFLoss", "crf_loss", "aug_loss", "aug_alignment_loss", "crop_flip_coords", "rec_loss", "reconstruction_loss", "depth_encoder", "cross_attn", "cross_attention", "multihead_cross_attention", "depth_decay", "training", "metrics", "evaluation", "predict_and_score", "crf", "dense_crf",
+__all__ = ["ContrastiveCorrelationLoss", "DepthContrastiveCorrelationLoss", "ContrastiveCRFLoss", "crf_loss", "aug_loss", "aug_alignment_loss", "crop_flip_coords", "rec_loss", "reconstruction_loss", "depth_encoder", "cross_attn", "cross_attention", "multihead_cross_attention", "depth_decay", "training", "metrics", "evaluation", "predict_and_score", "segment", "crf", "dense_crf",
            "batched_crf", "knn", "lhp", "optim", "FusedAdam", "FusedAdamSet", "segmenter", "vit", "featurizer",
            "DinoFeaturizer", "DinoFeaturizerWithDepth"]

@@ -99,6 +99,8 @@ SIGNATURES = {
     "dg_probe_ce_backward": (_I, [vp] * 4 + [i32] * 6 + [vp] * 2),
     # evaluation and dense CRF
     "dg_segment_predict": (_I, [vp, vp] + [i32] * 4 + [vp, vp, i32, vp, i32, vp, i32, i32, vp, vp, i32, vp, vp, vp, _SZ, vp]),
+    "dg_segment_labels": (_I, [vp, vp] + [i32] * 4 + [vp, vp, i32, vp] + [i32] * 3 + [vp] * 5 + [i32, i32] + [vp] * 4 + [vp, _SZ, vp]),
+    "dg_label_paint": (_I, [vp] + [i32] * 5 + [vp] * 5 + [i32, i32] + [vp] * 4 + [vp]),
     "dg_crf_workspace_bytes": (_SZ, [i32] * 5),
     "dg_crf_unary": (_I, [vp] + [i32] * 6 + [vp, i32, vp, vp]),
     "dg_segment_unary": (_I, [vp, vp] + [i32] * 4 + [vp, vp, i32, vp, i32, i32, i32, f32, vp, vp, _SZ, vp]),

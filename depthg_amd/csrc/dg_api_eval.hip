@@ -1,5 +1,5 @@
 // C ABI of the gfx950 DepthG library (include/depthg_corr.h): the probes, evaluation and the dense CRF (dg_probe.hip, dg_eval.hip,
-// dg_crf.hip, dg_metrics.hip).  Host-side only: argument checks and kernel launches on the caller's stream.
+// dg_seg_labels.hip, dg_crf.hip, dg_metrics.hip).  Host-side only: argument checks and kernel launches on the caller's stream.
 #include "dg_api.h"
 #include "dg_eval_args.h"
 #include "dg_head_args.h"     // the probes (dg_probe.hip)
@@ -79,6 +79,80 @@ extern "C" int dg_segment_predict(const float* code, const float* code_flip, int
     DgSegArgs a{code, code_flip, lin_w, lin_b, clusters, label, static_cast<float*>(scratch), stats_lin, stats_clu, preds_lin, preds_clu,
                 B, D, h, w, n, m, H, W, n_store};
     DG_HIP(dg_launch_segment_predict(a, static_cast<hipStream_t>(stream_)));
+    return DG_OK;
+}
+
+// ---- label-free inference (dg_seg_labels.hip)
+
+// the remap, paint and output arguments dg_segment_labels and dg_label_paint share, checked
+static int paint_check(const char* who, DgPaintArgs& p, int32_t B, int32_t H, int32_t W, int32_t m, const int32_t* remap, const float* img,
+                       const float* mean, const float* std, const uint8_t* cmap, int32_t cmap_rows, int32_t alpha256, uint8_t* lab_lin,
+                       uint8_t* lab_clu, uint8_t* rgb_lin, uint8_t* rgb_clu) {
+    if (m > DG_SEG_MAX_LABELS) return fail(DG_ERR_UNSUPPORTED, "%s needs m <= %d: a byte holds the cluster id, 255 is \"no class\" (got %d)", who, DG_SEG_MAX_LABELS, m);
+    if (!lab_lin && !lab_clu && !rgb_lin && !rgb_clu) return fail(DG_ERR_INVALID, "%s: nothing to write, the four outputs are null", who);
+    p = DgPaintArgs{};
+    p.remap = remap; p.lab_lin = lab_lin; p.lab_clu = lab_clu; p.rgb_lin = rgb_lin; p.rgb_clu = rgb_clu;
+    p.B = B; p.H = H; p.W = W; p.m = m; p.cmap_rows = 1; p.alpha256 = 256;
+    if (rgb_lin || rgb_clu) {
+        if (cmap_rows < 1 || cmap_rows > DG_SEG_MAX_CMAP)
+            return fail(DG_ERR_INVALID, "%s: a colour output needs 1 <= cmap_rows <= %d (got %d)", who, DG_SEG_MAX_CMAP, cmap_rows);
+        if (!cmap) return fail(DG_ERR_INVALID, "%s: a colour output needs cmap", who);
+        if (alpha256 < 0 || alpha256 > 256) return fail(DG_ERR_INVALID, "%s: alpha256 must lie in [0, 256] (got %d)", who, alpha256);
+        if (alpha256 < 256 && (!img || !mean || !std))
+            return fail(DG_ERR_INVALID, "%s: a colour output with alpha256 = %d < 256 blends with the image: img, mean and std are needed", who, alpha256);
+        p.cmap = cmap; p.cmap_rows = cmap_rows; p.alpha256 = alpha256;
+        if (alpha256 < 256) {
+            if (reinterpret_cast<uintptr_t>(img) % 4) return fail(DG_ERR_INVALID, "%s: img must be 4-byte aligned", who);
+            p.img = img;
+            for (int c = 0; c < 3; ++c) {
+                if (!std::isfinite(mean[c]) || !std::isfinite(std[c])) return fail(DG_ERR_INVALID, "%s: mean and std must be finite", who);
+                p.mean[c] = mean[c]; p.std[c] = std[c];
+            }
+        }
+    }
+    return DG_OK;
+}
+
+extern "C" int dg_segment_labels(const float* code, const float* code_flip, int32_t B, int32_t D, int32_t h, int32_t w, const float* lin_w,
+                                 const float* lin_b, int32_t n, const float* clusters, int32_t m, int32_t H, int32_t W, const int32_t* remap,
+                                 const float* img, const float* mean, const float* std, const uint8_t* cmap, int32_t cmap_rows,
+                                 int32_t alpha256, uint8_t* lab_lin, uint8_t* lab_clu, uint8_t* rgb_lin, uint8_t* rgb_clu, void* scratch,
+                                 size_t scratch_bytes, dg_stream_t stream_) {
+    if (B < 1 || D < 1 || h < 1 || w < 1 || n < 1 || m < 1 || H < 1 || W < 1) return fail(DG_ERR_INVALID, "bad segment-labels dimensions");
+    if (D > DG_SEG_MAX_D) return fail(DG_ERR_UNSUPPORTED, "segment labels needs D <= %d (got %d)", DG_SEG_MAX_D, D);
+    if (n > DG_SEG_MAX_LABELS)
+        return fail(DG_ERR_UNSUPPORTED, "segment labels needs n <= %d: a byte holds the class id, 255 is \"no class\" (got %d)", DG_SEG_MAX_LABELS, n);
+    DgPaintArgs p;
+    if (int rc = paint_check("segment labels", p, B, H, W, m, remap, img, mean, std, cmap, cmap_rows, alpha256, lab_lin, lab_clu, rgb_lin, rgb_clu))
+        return rc;
+    if (n + m > DG_SEG_MAX_K) return fail(DG_ERR_UNSUPPORTED, "segment labels needs n + m <= %d (got %d)", DG_SEG_MAX_K, n + m);
+    if ((long long)w * dg_seg_kp(n, m) > DG_SEG_ROW_FLOATS)
+        return fail(DG_ERR_UNSUPPORTED, "segment labels needs w * (n + m, each rounded up to 4) <= %d (w=%d)", DG_SEG_ROW_FLOATS, w);
+    if (W > (DG_SEG_STAGE_BYTES - 128) / 8) return fail(DG_ERR_UNSUPPORTED, "segment labels needs W <= %d (got %d)", (DG_SEG_STAGE_BYTES - 128) / 8, W);
+    if ((long long)h * w > (1 << 24) || (long long)B * H > (1LL << 30) || (long long)B * H * W > (1LL << 40))
+        return fail(DG_ERR_UNSUPPORTED, "maps too large");
+    if (!code || !lin_w || !clusters || !scratch) return fail(DG_ERR_INVALID, "null pointer");
+    if (reinterpret_cast<uintptr_t>(scratch) % 16) return fail(DG_ERR_INVALID, "scratch must be 16-byte aligned");
+    const size_t need = (size_t)B * h * w * dg_seg_kp(n, m) * 4;
+    if (scratch_bytes < need) return fail(DG_ERR_WORKSPACE, "scratch of %zu bytes, %zu needed", scratch_bytes, need);
+    DgSegArgs a{code, code_flip, lin_w, lin_b, clusters, nullptr, static_cast<float*>(scratch), nullptr, nullptr, nullptr, nullptr,
+                B, D, h, w, n, m, H, W, 0};
+    DG_HIP(dg_launch_segment_labels(a, p, static_cast<hipStream_t>(stream_)));
+    return DG_OK;
+}
+
+extern "C" int dg_label_paint(const int64_t* preds, int32_t n_groups, int32_t B, int32_t H, int32_t W, int32_t m, const int32_t* remap,
+                              const float* img, const float* mean, const float* std, const uint8_t* cmap, int32_t cmap_rows,
+                              int32_t alpha256, uint8_t* lab_lin, uint8_t* lab_clu, uint8_t* rgb_lin, uint8_t* rgb_clu, dg_stream_t stream_) {
+    if (B < 1 || H < 1 || W < 1 || m < 1 || n_groups < 1) return fail(DG_ERR_INVALID, "bad label-paint dimensions");
+    DgPaintArgs p;
+    if (int rc = paint_check("label paint", p, B, H, W, m, remap, img, mean, std, cmap, cmap_rows, alpha256, lab_lin, lab_clu, rgb_lin, rgb_clu))
+        return rc;
+    if (n_groups < 2 && (lab_clu || rgb_clu)) return fail(DG_ERR_INVALID, "label paint: the cluster outputs read preds[1], n_groups is %d", n_groups);
+    if ((long long)B * H * W > (1LL << 40)) return fail(DG_ERR_UNSUPPORTED, "maps too large");
+    if (!preds) return fail(DG_ERR_INVALID, "null pointer");
+    if (reinterpret_cast<uintptr_t>(preds) % 8) return fail(DG_ERR_INVALID, "preds must be 8-byte aligned");
+    DG_HIP(dg_launch_label_paint(preds, n_groups, p, static_cast<hipStream_t>(stream_)));
     return DG_OK;
 }
 

@@ -12,7 +12,7 @@
 // and two identical score rows (duplicated centres or probe rows, a zero code map) would no longer tie exactly.
 #include "dg_device.h"
 #include "dg_eval_args.h"
-#include "dg_taps.h"          // resize_taps
+#include "dg_seg_rows.h"      // seg_blend_rows, seg_argmax (shared with dg_seg_labels.hip), resize_taps
 
 #include <map>
 #include <mutex>
@@ -85,21 +85,6 @@ __global__ __launch_bounds__(SP_THREADS) void k_seg_project(const DgSegArgs a) {
     }
 }
 
-// arg-max of interp(scores) over rows [0, cnt) of a part, first maximum wins (torch.argmax)
-__device__ __forceinline__ int seg_argmax(const float* __restrict__ v0, const float* __restrict__ v1, const float lx, const int cnt) {
-    float best = -INFINITY;
-    int arg = 0;
-    for (int k4 = 0; k4 < cnt; k4 += 4) {
-        const f32x4 a = *reinterpret_cast<const f32x4*>(v0 + k4), c = *reinterpret_cast<const f32x4*>(v1 + k4);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const float v = fmaf(c[j], lx, a[j] * (1.f - lx));
-            if (k4 + j < cnt && v > best) { best = v; arg = k4 + j; }
-        }
-    }
-    return arg;
-}
-
 // Persistent blocks over chunks of R consecutive label rows of the flattened (b, Y) space.  Per chunk: the R vertically blended
 // score rows [R][w][Kp] go to LDS (coalesced reads of the two source rows), then every pixel of the chunk blends its two columns,
 // takes the two arg-maxes, counts and, for images < n_store, writes its predictions.
@@ -119,21 +104,7 @@ __global__ __launch_bounds__(SS_THREADS) void k_seg_score(const DgSegArgs a, con
         const long long r0 = (long long)c * R;
         const int nr = (int)(nrows - r0 < R ? nrows - r0 : R);
         __syncthreads();                                                       // the previous chunk's readers are done
-        for (int r = 0; r < nr; ++r) {
-            const int b = (int)((r0 + r) / H), Y = (int)(r0 + r - (long long)b * H);
-            int y0, y1; float ly;
-            resize_taps(Y, a.h, H, y0, y1, ly);
-            const float* s0 = a.scores + ((size_t)b * a.h + y0) * wK;
-            const float* s1 = a.scores + ((size_t)b * a.h + y1) * wK;
-            float* dst = rows + (size_t)r * wK;
-            for (int e = tid * 4; e < wK; e += SS_THREADS * 4) {
-                const f32x4 u = *reinterpret_cast<const f32x4*>(s0 + e), v = *reinterpret_cast<const f32x4*>(s1 + e);
-                f32x4 o;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) o[j] = fmaf(v[j], ly, u[j] * (1.f - ly));
-                *reinterpret_cast<f32x4*>(dst + e) = o;
-            }
-        }
+        seg_blend_rows<SS_THREADS>(a.scores, rows, r0, nr, a.h, H, wK, tid);
         __syncthreads();
         for (int i = tid; i < nr * W; i += SS_THREADS) {
             const int r = i / W, X = i - r * W;

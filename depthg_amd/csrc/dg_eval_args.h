@@ -25,6 +25,25 @@ hipError_t dg_launch_segment_predict(const DgSegArgs& a, hipStream_t s);
 hipError_t dg_launch_seg_project(const DgSegArgs& a, hipStream_t s);   // k_seg_project alone: a.scores (also dg_crf.hip)
 int dg_cu_count();                                                     // compute units of the current device (dg_eval.hip)
 
+// ---- label-free inference (dg_seg_labels.hip; src/demo_segmentation.py:59-78): byte label maps and painted images of both probes.
+// (Its kernels live beside dg_eval.hip, not in it: tests/test_eval_cpu.py pins that unit's kernels at the four of the scored route.)
+struct DgPaintArgs {
+    const int32_t* remap;    // (m) cluster id -> class id (-1 -> 255), or null: the raw cluster id
+    const float* img;        // (B, 3, H, W) normalised, or null (alpha256 == 256, or no colour output)
+    const uint8_t* cmap;     // (cmap_rows, 3), or null (no colour output)
+    uint8_t* lab_lin;        // (B, H, W) or null
+    uint8_t* lab_clu;        // (B, H, W) or null
+    uint8_t* rgb_lin;        // (B, H, W, 3) or null
+    uint8_t* rgb_clu;        // (B, H, W, 3) or null
+    float mean[3], std[3];   // pix = clamp(rint((img * std + mean) * 255), 0, 255)
+    int32_t B, H, W, m, cmap_rows, alpha256;
+};
+#define DG_SEG_MAX_LABELS 255                // n and m of the byte maps: 255 is the "no class" byte
+#define DG_SEG_MAX_CMAP 256
+#define DG_SEG_STAGE_BYTES (64 * 1024)       // LDS staging of a chunk's output bytes (8 per pixel and 16 of slack per output)
+hipError_t dg_launch_segment_labels(const DgSegArgs& a, const DgPaintArgs& p, hipStream_t s);   // a.scores: the projection scratch
+hipError_t dg_launch_label_paint(const int64_t* preds, int G, const DgPaintArgs& p, hipStream_t s);
+
 // ---- dense-CRF refinement (dg_crf.hip; src/crf.py dense_crf, src/eval_segmentation.py:55-60, :162-167)
 #define DG_CRF_MAX_GROUPS 8                  // channel groups (one softmax each: one per probe)
 #define DG_CRF_MAX_KP 256                    // channels, each group rounded up to a multiple of 4

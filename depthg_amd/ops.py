@@ -795,6 +795,123 @@ def segment_predict(code, label, lin_w, lin_b, clusters, code_flip=None, stats_l
     return preds_lin, preds_clu
 
 
+IMAGENET_MEAN = (0.485, 0.456, 0.406)          # the loader's T.Normalize (src/utils.py:139)
+IMAGENET_STD = (0.229, 0.224, 0.225)
+SEGMENT_OUTPUTS = ("lin", "clu", "lin_rgb", "clu_rgb")
+
+
+def pascal_colormap(rows=256):
+    """The PASCAL VOC colour map, uint8 (rows, 3), by its public rule: the bits of the class id go, three at a time from the lowest,
+    to red, green and blue, filling each channel from its highest bit down."""
+    cmap = torch.zeros(rows, 3, dtype=torch.uint8)
+    for i in range(rows):
+        c, rgb = i, [0, 0, 0]
+        for j in range(8):
+            for k in range(3):
+                rgb[k] |= ((c >> k) & 1) << (7 - j)
+            c >>= 3
+        cmap[i] = torch.tensor(rgb, dtype=torch.uint8)
+    return cmap
+
+
+_default_cmaps = {}
+
+
+def _paint_operands(dev, B, H, W, m, remap, img, cmap, alpha, want, mean, std, out):
+    """What dg_segment_labels and dg_label_paint share, checked and as the library reads it: (remap, img, mean, std, cmap, cmap_rows,
+    alpha256, outputs) - outputs a dict over SEGMENT_OUTPUTS of uint8 tensors or None (taken from `out` where it has the key)."""
+    want = tuple(want)
+    if not want or any(k not in SEGMENT_OUTPUTS for k in want):
+        raise ValueError(f"depthg_amd: want must name some of {SEGMENT_OUTPUTS}, got {want}")
+    if remap is not None:
+        remap = torch.as_tensor(remap)
+        if remap.dim() != 1 or remap.numel() != m or remap.dtype.is_floating_point:
+            raise ValueError(f"depthg_amd: remap must be an integer table of the m={m} cluster ids, got {remap.dtype} {tuple(remap.shape)}")
+        # (the table is device data to the library, which stores any entry it cannot put in a byte as 255: refuse it here, by name)
+        if remap.numel() and (int(remap.min()) < -1 or int(remap.max()) > 254):
+            raise ValueError(f"depthg_amd: remap entries must lie in [-1, 254] (-1: no class, stored as 255), got "
+                             f"[{int(remap.min())}, {int(remap.max())}]")
+        remap = remap.detach().to(device=dev, dtype=torch.int32).contiguous()
+    colour = any(k.endswith("rgb") for k in want)
+    alpha256 = int(round(float(alpha) * 256))
+    if not 0 <= alpha256 <= 256:
+        raise ValueError(f"depthg_amd: alpha must lie in [0, 1], got {alpha}")
+    cmean = cstd = None
+    if colour:
+        if alpha256 < 256 and img is None:
+            raise ValueError(f"depthg_amd: alpha = {alpha} < 1 blends the colours with the image: img is needed")
+        if cmap is None:
+            if dev not in _default_cmaps:
+                _default_cmaps[dev] = pascal_colormap().to(dev)
+            cmap = _default_cmaps[dev]
+        if cmap.dtype != torch.uint8 or cmap.dim() != 2 or cmap.shape[1] != 3 or not 1 <= cmap.shape[0] <= 256:
+            raise ValueError(f"depthg_amd: cmap must be uint8 (rows <= 256, 3), got {cmap.dtype} {tuple(cmap.shape)}")
+        cmap = _on_gpu(cmap, "cmap").contiguous()
+        if alpha256 < 256:
+            img = _crf_image(img, B, H, W)
+            if len(mean) != 3 or len(std) != 3:
+                raise ValueError("depthg_amd: mean and std must have three entries")
+            cmean, cstd = (ctypes.c_float * 3)(*[float(v) for v in mean]), (ctypes.c_float * 3)(*[float(v) for v in std])
+        else:
+            img = None
+    else:
+        cmap = img = None
+    shapes = {"lin": (B, H, W), "clu": (B, H, W), "lin_rgb": (B, H, W, 3), "clu_rgb": (B, H, W, 3)}
+    outs = {k: None for k in SEGMENT_OUTPUTS}
+    for k in want:
+        t = out.get(k) if out else None
+        if t is None:
+            t = _empty(shapes[k], torch.uint8, dev)
+        elif t.dtype != torch.uint8 or tuple(t.shape) != shapes[k] or not t.is_contiguous() or t.device != dev:
+            raise ValueError(f"depthg_amd: out[{k!r}] must be a contiguous uint8 {shapes[k]} tensor on {dev}, got {t.dtype} "
+                             f"{tuple(t.shape)} on {t.device}")
+        outs[k] = t
+    return remap, img, cmean, cstd, cmap, (cmap.shape[0] if cmap is not None else 0), alpha256, outs
+
+
+def segment_labels(code, lin_w, lin_b, clusters, H, W, code_flip=None, remap=None, img=None, cmap=None, alpha=1.0,
+                   want=("lin", "clu"), mean=IMAGENET_MEAN, std=IMAGENET_STD, out=None):
+    """Label-free inference (dg_segment_labels; src/demo_segmentation.py:59-78 without the CRF): both probes' arg-max label maps of
+    every image at (H, W) as bytes - ops.segment_predict's predictions bit for bit - and their painted images.
+    code, code_flip, lin_w, lin_b, clusters: as segment_predict (n, m <= 255).  remap: integer (m) table cluster id -> class id
+    (UnsupervisedMetrics.map_clusters; -1 is stored as 255) or None (the raw cluster id).  want: which of "lin", "clu" (uint8
+    (B,H,W)) and "lin_rgb", "clu_rgb" (uint8 (B,H,W,3)) to write.  A colour is (a cmap[label] + (256 - a) pix + 128) >> 8 with
+    a = round(256 alpha) and pix the de-normalised byte of img (B,3,H,W) (needed when alpha < 1); cmap: uint8 (rows <= 256, 3) on the
+    GPU, default the PASCAL map; a label past the map (255 among them) paints its last row.  out: a dict of tensors to write
+    into instead of new ones (keys of `want`; other keys are ignored and never touched).  Returns a dict over `want`."""
+    lib = _lib.load()
+    lin_w, (B, D, h, w), n, m = _probe_args(code, code_flip, lin_w, lin_b, clusters)
+    H, W = int(H), int(W)
+    dev = code.device
+    code, code_flip, lin_w, lin_b, clusters, scratch = _probe_operands(code, code_flip, lin_w, lin_b, clusters, n, m)
+    remap, img, cmean, cstd, cmap, rows, alpha256, outs = _paint_operands(dev, B, H, W, m, remap, img, cmap, alpha, want, mean, std, out)
+    rc = lib.dg_segment_labels(_ptr(code), _ptr(code_flip), B, D, h, w, _ptr(lin_w), _ptr(lin_b), n, _ptr(clusters), m, H, W, _ptr(remap),
+                               _ptr(img), cmean, cstd, _ptr(cmap), rows, alpha256, _ptr(outs["lin"]), _ptr(outs["clu"]),
+                               _ptr(outs["lin_rgb"]), _ptr(outs["clu_rgb"]), _ptr(scratch), scratch.numel(), _stream(dev))
+    _lib.check(rc, "dg_segment_labels")
+    return {k: v for k, v in outs.items() if v is not None}
+
+
+def label_paint(preds, m=None, remap=None, img=None, cmap=None, alpha=1.0, want=("lin", "clu"), mean=IMAGENET_MEAN, std=IMAGENET_STD,
+                out=None):
+    """The remap and paint of segment_labels on the dense CRF's predictions (dg_label_paint): preds int64 (G,B,H,W) on the GPU as
+    ops.dense_crf(..., return_preds=True) returns them, preds[0] the linear probe's map and preds[1] the cluster probe's.  m: the
+    number of clusters (default: remap's length, else 255).  A value no byte label holds (outside [0, 254]) is stored as 255."""
+    lib = _lib.load()
+    if preds.dim() != 4 or preds.dtype != torch.int64:
+        raise ValueError(f"depthg_amd: preds must be int64 (G, B, H, W), got {preds.dtype} {tuple(preds.shape)}")
+    preds = _on_gpu(preds, "preds").contiguous()
+    G, B, H, W = preds.shape
+    if m is None:
+        m = len(remap) if remap is not None else 255
+    dev = preds.device
+    remap, img, cmean, cstd, cmap, rows, alpha256, outs = _paint_operands(dev, B, H, W, int(m), remap, img, cmap, alpha, want, mean, std, out)
+    rc = lib.dg_label_paint(_ptr(preds), G, B, H, W, int(m), _ptr(remap), _ptr(img), cmean, cstd, _ptr(cmap), rows, alpha256,
+                            _ptr(outs["lin"]), _ptr(outs["clu"]), _ptr(outs["lin_rgb"]), _ptr(outs["clu_rgb"]), _stream(dev))
+    _lib.check(rc, "dg_label_paint")
+    return {k: v for k, v in outs.items() if v is not None}
+
+
 def _crf_groups(group_ends, C=None):
     ends = [int(e) for e in group_ends]
     if not ends or any(b <= a for a, b in zip([0] + ends, ends)) or (C is not None and ends[-1] != C):

@@ -17,7 +17,9 @@ Mirrors, with the reference's names, parameter layout and arithmetic:
                             loss (and the second LHP call when cfg.lhp), the weighted total, the live legacy decay of the cfg
                             scalars, linear-probe cross entropy and cluster-probe loss on the detached code, backward, three steps;
                             validation_step / on_validation_epoch_end (:471-535) and evaluate_batch (src/eval_segmentation.py:146-170,
-                            run_crf for the dense CRF) score the probes through evaluation.predict_and_score.
+                            run_crf for the dense CRF) score the probes through evaluation.predict_and_score; segment(img) is the
+                            label-free route of src/demo_segmentation.py:59-78 through evaluation.segment (byte label maps and
+                            painted images of every image; depthg_amd/demo.py is its command line).
 ProjectionHead / ClusterLookup (src/modules.py:647-675) / probe_cross_entropy live in depthg_amd/head.py and are re-exported
 here.  The head, the probes' losses and everything the correlation loss does run in the HIP library; what stays torch is the
 frozen backbone, the 27 x dim linear-probe convolution and - unless cfg.dg_fused_adam - the three Adams.  With cfg.dg_fused_adam
@@ -51,7 +53,7 @@ import torch.nn as nn
 from .aug_loss import aug_alignment_loss
 from .crf_loss import ContrastiveCRFLoss
 from .depth_decay import legacy_decay_step
-from .evaluation import predict_and_score
+from .evaluation import predict_and_score, segment
 from .featurizer import DepthGuidance, DinoFeaturizer, DinoFeaturizerWithDepth, FrozenBackboneFeaturizer
 from .head import ClusterLookup, ProjectionHead, probe_cross_entropy
 from .lhp import LocalHiddenPositiveProjection, OriginalLocalHiddenPositiveProjection
@@ -469,6 +471,21 @@ class UnsupervisedSegmenter(nn.Module):
         return predict_and_score(code, label, self.linear_probe, self.cluster_probe, self.test_linear_metrics,
                                  self.test_cluster_metrics, code_flip=code_flip, n_store=img.shape[0], img=img if run_crf else None,
                                  run_crf=run_crf)
+
+    def segment(self, img: torch.Tensor, flip: bool = True, run_crf: bool = False, overlay: Optional[float] = None, remap: bool = True):
+        """Label-free inference on normalised images (B,3,H,W) (src/demo_segmentation.py:59-78): the codes as evaluate_batch forms
+        them (eval mode, no_grad; `flip`: averaged with the mirrored pass), then evaluation.segment at the images' own size - byte
+        label maps of both probes and, with `overlay` (the colours' weight in [0, 1]), painted images; `run_crf` refines with the
+        dense CRF first.  `remap`: the cluster ids go through the Hungarian assignment of test_cluster_metrics if its compute() has
+        run, else of cluster_metrics, else (or with remap=False) they stay raw as in the reference demo.  Returns evaluation.Segmentation."""
+        if img.dim() != 4 or img.shape[1] != 3:
+            raise ValueError(f"depthg_amd: segment takes normalised images (B, 3, H, W), got {tuple(img.shape)}")
+        metrics = None
+        if remap:
+            metrics = next((mt for mt in (self.test_cluster_metrics, self.cluster_metrics) if getattr(mt, "assignments", None) is not None), None)
+        code, code_flip = self._eval_mode_codes(img, flip)
+        return segment(code, img.shape[-2:], self.linear_probe, self.cluster_probe, code_flip=code_flip, cluster_metrics=metrics,
+                       run_crf=run_crf, img=img if (run_crf or overlay is not None) else None, overlay=overlay)
 
 
 def default_segmenter_cfg(**over) -> SimpleNamespace:

@@ -620,6 +620,37 @@ int dg_segment_predict(const float* code, const float* code_flip, int32_t B, int
                        int64_t* preds_lin, int64_t* preds_clu, void* scratch, size_t scratch_bytes, dg_stream_t stream);
 
 /*
+ * Label-free inference.  Replaces the loop body of src/demo_segmentation.py:59-78 without its CRF - code = (code1 + code2.flip(3)) / 2,
+ * F.interpolate to the image size, linear_probe / cluster_probe, argmax, astype(uint8) - for the whole batch, and the colour lookups
+ * that turn a label map into a picture (src/eval_segmentation.py:170-240: label_cmap[preds], map_clusters).  The projection and the
+ * resize of the score rows are those of the scored route above, so the labels are its predictions bit for bit; there is no label
+ * tensor, no metric and no n_store: every image is written.  Each output may be NULL (skipped, never touched); every byte of a
+ * given output is written.
+ *  code .. m : as above; n <= 255 and m <= 255 (a byte holds the id, 255 is "no class")      H, W : the size of the outputs
+ *  remap : DEVICE int32 (m), cluster id -> class id, the Hungarian assignment as UnsupervisedMetrics.map_clusters forms it
+ *      (src/utils.py:234-246); -1 (and any entry outside [0, 254]) is stored as 255.  NULL: the raw cluster id, as the reference demo
+ *  lab_lin, lab_clu : uint8 (B,H,W) out          rgb_lin, rgb_clu : uint8 (B,H,W,3) out, interleaved
+ *      per channel (alpha256 * cmap[label] + (256 - alpha256) * pix + 128) >> 8 in integers, 0 <= alpha256 <= 256;
+ *      pix = clamp(rint((img * std + mean) * 255), 0, 255) (UnNormalize, src/utils.py:132-136, then the byte scale)
+ *  img : fp32 (B,3,H,W) normalised; mean, std : HOST float[3].  All three may be NULL when alpha256 == 256 or no colour is asked for
+ *  cmap : DEVICE uint8 (cmap_rows,3), 1 <= cmap_rows <= 256; a label >= cmap_rows - 255 among them - paints the last row
+ *  scratch : B*h*w*(n4 + m4)*4 bytes, 16-byte aligned
+ * Limits as above, and W <= 8176.  No allocation, no atomics, two launches; two identical calls give identical bytes.
+ */
+int dg_segment_labels(const float* code, const float* code_flip, int32_t B, int32_t D, int32_t h, int32_t w, const float* lin_w,
+                      const float* lin_b, int32_t n, const float* clusters, int32_t m, int32_t H, int32_t W, const int32_t* remap,
+                      const float* img, const float* mean, const float* std, const uint8_t* cmap, int32_t cmap_rows, int32_t alpha256,
+                      uint8_t* lab_lin, uint8_t* lab_clu, uint8_t* rgb_lin, uint8_t* rgb_clu, void* scratch, size_t scratch_bytes,
+                      dg_stream_t stream);
+/* The same remap and paint on the predictions of the dense CRF declared below (the CRF route of src/demo_segmentation.py:71-78 and the
+ * pictures of src/eval_segmentation.py:170-240).  preds : int64 (n_groups,B,H,W); preds[0] is the linear probe's map, preds[1] the
+ * cluster probe's (needed only for lab_clu / rgb_clu); a value outside [0, 254] is stored as 255.  m : the length of remap.
+ * The other arguments and the outputs as above.  One launch. */
+int dg_label_paint(const int64_t* preds, int32_t n_groups, int32_t B, int32_t H, int32_t W, int32_t m, const int32_t* remap,
+                   const float* img, const float* mean, const float* std, const uint8_t* cmap, int32_t cmap_rows, int32_t alpha256,
+                   uint8_t* lab_lin, uint8_t* lab_clu, uint8_t* rgb_lin, uint8_t* rgb_clu, dg_stream_t stream);
+
+/*
  * Dense-CRF refinement of the evaluation: src/crf.py dense_crf (pydensecrf's DenseCRF2D with addPairwiseGaussian(sxy=POS_XY_STD,
  * compat=POS_W), addPairwiseBilateral(sxy=Bi_XY_STD, srgb=Bi_RGB_STD, rgbim=image, compat=Bi_W), inference(MAX_ITER)), run per image
  * by batched_crf (src/eval_segmentation.py:55-60) on both probes' outputs (:162-167).  Mean field over permutohedral lattices built on
