@@ -9,6 +9,8 @@ Public surface (mirrors the reference's Python operator surface for this path):
                                  step's `crf_loss_fn(resize(img, 56), norm(resize(code, 56))).mean()` as fused HIP kernels (cfg.crf_weight)
     aug_alignment_loss           src/train_segmentation.py:400-411: the augmentation-alignment term as fused HIP kernels (cfg.aug_alignment_weight);
                                  aug_loss.crop_flip_coords makes a valid coord_aug (the crop-and-flip of the dataset's grid)
+    augment_batch                src/data.py:1082-1139: img_aug and coord_aug of a batch from two fused HIP kernels (augment.py,
+                                 draw_augment_params; cfg.dg_gpu_augment in the segmenter)
     reconstruction_loss          src/train_segmentation.py:391-398: the reconstruction term - the 1 x 1 decoder and both norms - as fused HIP
                                  kernels (cfg.rec_weight); no (B, n_feats, h, w) tensor is written in either direction
     depth_decay                  scalar decay schedules (src/depth_decay_modules.py) + the live legacy decay
@@ -41,6 +43,8 @@ from . import crf_loss  # noqa: F401
 from .crf_loss import ContrastiveCRFLoss  # noqa: F401
 from . import aug_loss  # noqa: F401
 from .aug_loss import aug_alignment_loss, crop_flip_coords  # noqa: F401
+from . import augment  # noqa: F401
+from .augment import AugmentParams, augment_batch, draw_augment_params  # noqa: F401
 from . import rec_loss  # noqa: F401
 from .rec_loss import reconstruction_loss  # noqa: F401
 from .depth_encoder import depth_encoder  # noqa: F401
@@ -62,6 +66,6 @@ from . import featurizer  # noqa: F401
 from .featurizer import DinoFeaturizer, DinoFeaturizerWithDepth  # noqa: F401
 from . import segmenter  # noqa: F401
 
-__all__ = ["ContrastiveCorrelationLoss", "DepthContrastiveCorrelationLoss", "ContrastiveCRFLoss", "crf_loss", "aug_loss", "aug_alignment_loss", "crop_flip_coords", "rec_loss", "reconstruction_loss", "depth_encoder", "cross_attn", "cross_attention", "multihead_cross_attention", "depth_decay", "training", "metrics", "evaluation", "predict_and_score", "segment", "crf", "dense_crf",
+__all__ = ["ContrastiveCorrelationLoss", "DepthContrastiveCorrelationLoss", "ContrastiveCRFLoss", "crf_loss", "aug_loss", "aug_alignment_loss", "crop_flip_coords", "augment", "AugmentParams", "augment_batch", "draw_augment_params", "rec_loss", "reconstruction_loss", "depth_encoder", "cross_attn", "cross_attention", "multihead_cross_attention", "depth_decay", "training", "metrics", "evaluation", "predict_and_score", "segment", "crf", "dense_crf",
            "batched_crf", "knn", "lhp", "optim", "FusedAdam", "FusedAdamSet", "segmenter", "vit", "featurizer",
            "DinoFeaturizer", "DinoFeaturizerWithDepth"]

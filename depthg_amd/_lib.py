@@ -136,6 +136,9 @@ SIGNATURES = {
     "dg_xattn_forward": (_I, [vp] * 3 + [i32] * 5 + [f32, f32, u64, vp, vp, vp, _SZ, vp]),
     "dg_xattn_backward": (_I, [vp] * 6 + [i32] * 5 + [f32, f32, u64, vp, vp, vp, vp, _SZ, vp]),
     "dg_xattn_keep_mask": (_I, [u64] + [i32] * 4 + [f32, vp, vp]),
+    # GPU batch augmentation
+    "dg_augment_workspace_bytes": (_SZ, [i32] * 3),
+    "dg_augment_forward": (_I, [vp] + [i64] * 4 + [vp] * 4 + [i32] * 6 + [vp, vp, vp, _SZ, vp]),
     # measurement aids
     "dg_corr_main_kernel_name": (_STR, [cp]),
     "dg_corr_intra_folded": (_I, [cp]),

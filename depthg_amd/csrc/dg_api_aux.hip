@@ -1,5 +1,5 @@
 // C ABI of the gfx950 DepthG library (include/depthg_corr.h), the units' shared state and the small subsystems: version and error
-// text, the library's side stream, batch maps / random draws / coordinate samplers, kNN, LHP, fused Adam, ViT attention and linear, the fused depth encoder, the depth guidance's cross-attention.  (The auxiliary loss terms: dg_api_loss.hip.)
+// text, the library's side stream, batch maps / random draws / coordinate samplers, kNN, LHP, fused Adam, ViT attention and linear, the fused depth encoder, the depth guidance's cross-attention, the GPU batch augmentation.  (The auxiliary loss terms: dg_api_loss.hip.)
 // Host-side only: argument checks and kernel launches on the caller's stream.
 #include "dg_api.h"
 #include "dg_aux_args.h"
@@ -463,5 +463,76 @@ extern "C" int dg_xattn_keep_mask(uint64_t seed, int32_t B, int32_t heads, int32
     if (int rc = xattn_check(__func__, B, heads, Nq, Nk, DG_XATTN_HD, 1.f, p)) return rc;
     if (!out) return fail(DG_ERR_INVALID, "dg_xattn_keep_mask: null pointer");
     DG_HIP(dg_launch_xattn_mask(out, B, heads, Nq, Nk, seed, xattn_threshold(p), static_cast<hipStream_t>(stream_)));
+    return DG_OK;
+}
+
+// ---- GPU batch augmentation (dg_augment.hip)
+static bool augment_sizes_ok(int32_t B, int32_t h, int32_t w) { return B >= 1 && B <= 65535 && h >= 3 && w >= 3 && h <= 16384 && w <= 16384; }
+
+static int augment_stat_blocks(int32_t h, int32_t w) {
+    const long long tiles = (long long)((h + DG_AUGM_TH - 1) / DG_AUGM_TH) * ((w + DG_AUGM_TW - 1) / DG_AUGM_TW);
+    return (int)(tiles < DG_AUGM_STAT_BLOCKS ? tiles : DG_AUGM_STAT_BLOCKS);
+}
+
+extern "C" size_t dg_augment_workspace_bytes(int32_t B, int32_t h, int32_t w) {
+    if (!augment_sizes_ok(B, h, w)) return 0;
+    return up((size_t)B * augment_stat_blocks(h, w) * sizeof(double), 256);
+}
+
+extern "C" int dg_augment_forward(const float* img, int64_t stride_b, int64_t stride_c, int64_t stride_h, int64_t stride_w,
+                                  const int32_t* records_host, const void* params, const float* mean, const float* stdv, int32_t B,
+                                  int32_t C, int32_t H, int32_t W, int32_t h, int32_t w, float* img_aug, float* coord_aug,
+                                  void* workspace, size_t workspace_bytes, dg_stream_t stream_) {
+    if (B < 1 || C < 1 || H < 1 || W < 1 || h < 1 || w < 1)
+        return fail(DG_ERR_INVALID, "dg_augment_forward: B=%d C=%d, image %dx%d, output %dx%d must be positive", B, C, H, W, h, w);
+    if (C != 3) return fail(DG_ERR_UNSUPPORTED, "dg_augment_forward: %d channels (the colour ops are RGB: 3)", C);
+    if (H < 3 || W < 3 || h < 3 || w < 3)
+        return fail(DG_ERR_UNSUPPORTED, "dg_augment_forward: image %dx%d, output %dx%d: reflect padding by 2 needs three pixels a side", H, W, h, w);
+    if (B > 65535 || H > 16384 || W > 16384 || h > 16384 || w > 16384)
+        return fail(DG_ERR_UNSUPPORTED, "dg_augment_forward: B=%d above 65535 or a side of %dx%d / %dx%d above 16384", B, H, W, h, w);
+    if (stride_w != 1 || stride_h != W || stride_c != (int64_t)H * W || stride_b != 3 * (int64_t)H * W)
+        return fail(DG_ERR_UNSUPPORTED, "dg_augment_forward: img is not contiguous (strides %lld, %lld, %lld, %lld): copy it once", (long long)stride_b,
+                    (long long)stride_c, (long long)stride_h, (long long)stride_w);
+    if (!img || !records_host || !params || !img_aug || !coord_aug || !workspace) return fail(DG_ERR_INVALID, "dg_augment_forward: null pointer");
+    if (!mean != !stdv) return fail(DG_ERR_INVALID, "dg_augment_forward: mean and std come together: give both or neither");
+    if (int rc = check_aligned(__func__, {img, params, img_aug, coord_aug}, workspace)) return rc;
+    if (int rc = check_workspace(__func__, workspace_bytes, dg_augment_workspace_bytes(B, h, w), "dg_augment_workspace_bytes")) return rc;
+    bool stats = false;
+    for (int b = 0; b < B; ++b) {
+        const int32_t* r = records_host + (size_t)b * DG_AUGM_REC_WORDS;
+        const long long top = r[1], left = r[2], bh = r[3], bw = r[4];
+        if (bh < 1 || bw < 1 || top < 0 || left < 0 || top + bh > H || left + bw > W)
+            return fail(DG_ERR_UNSUPPORTED, "dg_augment_forward: crop box (%lld, %lld, %lld, %lld) of image %d leaves the %dx%d image", top, left, bh,
+                        bw, b, H, W);
+        int contrasts = 0;
+        for (int k = 0; k < 4; ++k) {
+            if (r[5 + k] < -1 || r[5 + k] > DG_AUGM_HUE) return fail(DG_ERR_INVALID, "dg_augment_forward: image %d: op %d in slot %d (-1 .. 3)", b, r[5 + k], k);
+            contrasts += r[5 + k] == DG_AUGM_CONTRAST;
+        }
+        if (contrasts > 1) return fail(DG_ERR_UNSUPPORTED, "dg_augment_forward: image %d has %d contrast ops (one image mean per image: one at most)", b, contrasts);
+        float sigma;
+        memcpy(&sigma, &r[14], 4);
+        if (!(sigma >= 0.f) || std::isinf(sigma)) return fail(DG_ERR_INVALID, "dg_augment_forward: image %d: blur_sigma=%g", b, (double)sigma);
+        stats = stats || contrasts > 0;
+    }
+    DgAugmentArgs A;
+    memset(&A, 0, sizeof(A));
+    A.img = img;
+    A.recs = static_cast<const int32_t*>(params);
+    A.rows = reinterpret_cast<const float*>(A.recs + (size_t)B * DG_AUGM_REC_WORDS);
+    A.cols = A.rows + H;
+    A.img_aug = img_aug; A.coord_aug = coord_aug; A.partials = static_cast<double*>(workspace);
+    A.B = B; A.H = H; A.W = W; A.h = h; A.w = w;
+    A.tiles_x = (w + DG_AUGM_TW - 1) / DG_AUGM_TW; A.tiles_y = (h + DG_AUGM_TH - 1) / DG_AUGM_TH;
+    A.stat_blocks = augment_stat_blocks(h, w);
+    A.unit_space = mean ? 0 : 1;
+    A.vec_stores = (w % 4 == 0 && (((uintptr_t)img_aug | (uintptr_t)coord_aug) & 15) == 0) ? 1 : 0;
+    for (int c = 0; c < 3; ++c) {
+        A.mean[c] = mean ? mean[c] : 0.f;
+        A.stdv[c] = stdv ? stdv[c] : 1.f;
+        if (!(A.stdv[c] > 0.f) || std::isinf(A.stdv[c]) || !(A.mean[c] == A.mean[c]) || std::isinf(A.mean[c]))
+            return fail(DG_ERR_INVALID, "dg_augment_forward: channel %d: mean=%g std=%g", c, (double)A.mean[c], (double)A.stdv[c]);
+    }
+    DG_HIP(dg_launch_augment(A, stats, static_cast<hipStream_t>(stream_)));
     return DG_OK;
 }

@@ -1,4 +1,4 @@
-// The stand-alone operations (dg_sample, dg_metrics, dg_knn, dg_lhp, dg_optim, dg_attn, dg_linear .hip; dg_api_aux.hip): constants and launchers.
+// The stand-alone operations (dg_sample, dg_metrics, dg_knn, dg_lhp, dg_optim, dg_attn, dg_linear, dg_augment .hip; dg_api_aux.hip): constants and launchers.
 // (The auxiliary loss terms have a header of their own: dg_loss_args.h.)
 #pragma once
 #include "dg_common.h"
@@ -63,3 +63,28 @@ size_t dg_linear_packed_bytes(int K, int Nout);              // 0 when unsupport
 hipError_t dg_launch_linear_pack(const float* w, int K, int Nout, void* packed, hipStream_t s);
 hipError_t dg_launch_linear(const void* x, const float* gamma, const float* beta, float eps, const void* packed, const float* bias,
                             const float* residual, void* out, int M, int K, int Nout, int flags, hipStream_t s);
+
+// ---- GPU batch augmentation: img_aug and coord_aug of a batch in two launches (dg_augment.hip; src/data.py:1082-1139,
+// src/train_segmentation.py:602-610)
+#define DG_AUGM_TH 16                        // output tile: 16 rows x 64 columns, one thread per four neighbouring pixels
+#define DG_AUGM_TW 64
+#define DG_AUGM_THREADS 256
+#define DG_AUGM_STAT_BLOCKS 64               // k_augm_stats: at most this many blocks - and fp64 partials - per image
+#define DG_AUGM_REC_WORDS 16                 // 32-bit words of one image's record (include/depthg_corr.h lists them)
+#define DG_AUGM_BRIGHTNESS 0                 // op ids of a record's four slots; -1: none
+#define DG_AUGM_CONTRAST 1
+#define DG_AUGM_SATURATION 2
+#define DG_AUGM_HUE 3
+struct DgAugmentArgs {
+    const float* img;                        // (B, 3, H, W)
+    const int32_t* recs;                     // B records of DG_AUGM_REC_WORDS words
+    const float *rows, *cols;                // linspace(-1, 1, H), linspace(-1, 1, W)
+    float *img_aug, *coord_aug;              // (B, 3, h, w), (B, h, w, 2)
+    double* partials;                        // (B, stat_blocks): the gray sums in front of each image's contrast op
+    int B, H, W, h, w;
+    int tiles_x, tiles_y, stat_blocks;
+    int unit_space;                          // 1: the ops act on the tensor as given; 0: x * stdv + mean in front, (x - mean) / stdv behind
+    int vec_stores;                          // 1: w % 4 == 0 and both outputs 16-byte aligned
+    float mean[3], stdv[3];
+};
+hipError_t dg_launch_augment(const DgAugmentArgs& A, bool stats, hipStream_t s);

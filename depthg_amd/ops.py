@@ -464,6 +464,28 @@ def aug_alignment_backward(workspace, code, code_aug, grad_out, out=None):
     return out[0], out[1]
 
 
+def augment_forward(img, packed, out_size, mean=None, std=None):
+    """(img_aug (B,3,h,w), coord_aug (B,h,w,2)) of img (B,3,H,W) on the GPU under the records of `packed` - augment.pack_params's CPU
+    int32 tensor, uploaded here once - in two launches for the whole batch (dg_augment_forward, dg_augment.hip); every element of
+    both results is written.  mean / std: three floats each, or None (the ops act on the tensor as given)."""
+    lib = _lib.load()
+    img = _f32c(img, "img")                       # (a non-contiguous img is copied once, here)
+    dev = img.device
+    B, C, H, W = img.shape
+    h, w = int(out_size[0]), int(out_size[1])
+    if packed.dtype != torch.int32 or packed.is_cuda or packed.numel() != B * 16 + H + W or not packed.is_contiguous():
+        raise ValueError(f"depthg_amd: augment_forward wants augment.pack_params's CPU int32 tensor of {B} x 16 + {H} + {W} words")
+    ws = _empty((_plan_bytes(lib.dg_augment_workspace_bytes(B, h, w), "batch augmentation", f"B={B}, output {h}x{w}",
+                             "B <= 65535, sides from 3 to 16384"),), torch.uint8, dev)
+    img_aug, coord_aug = _empty((B, 3, h, w), torch.float32, dev), _empty((B, h, w, 2), torch.float32, dev)
+    params = packed.to(dev)
+    space = [None, None] if mean is None else [(ctypes.c_float * 3)(*mean), (ctypes.c_float * 3)(*std)]
+    rc = lib.dg_augment_forward(_ptr(img), *img.stride(), ctypes.c_void_p(packed.data_ptr()), _ptr(params), space[0], space[1], B, C, H, W,
+                                h, w, _ptr(img_aug), _ptr(coord_aug), _ptr(ws), ws.numel(), _stream(dev))
+    _lib.check(rc, "dg_augment_forward")
+    return img_aug, coord_aug
+
+
 def rec_loss_shapes(code, feats, weight, bias):
     """The reconstruction term's shape rules, on any device: code (B,D,h,w), feats (B,C,h,w) on the same grid, the decoder's weight
     (C,D,1,1) or (C,D) and bias (C,).  Returns (weight as (C,D), (B, D, C, h, w))."""

@@ -35,6 +35,9 @@ With cfg.crf_weight > 0 the step adds the contrastive CRF term (src/train_segmen
 - the fused HIP kernels of dg_crf_loss.hip - and logs it as `loss/crf`.  With cfg.aug_alignment_weight > 0 it adds the
 augmentation-alignment term (src/train_segmentation.py:400-411) on batch["img_aug"] / batch["coord_aug"] through
 aug_loss.aug_alignment_loss - a third featurizer pass and the fused HIP kernels of dg_aug.hip - and logs it as `loss/aug_alignment`.
+With cfg.dg_gpu_augment as well (build-side key, off by default) a batch that lacks `img_aug` gets both tensors from batch["img"] through
+augment.draw_augment_params / augment_batch - the fused HIP kernels of dg_augment.hip; "unit" runs the colour ops on de-normalised values.
+Capturing such a step into a graph is out of scope (the parameters are drawn on the host).
 With cfg.rec_weight > 0 the segmenter has a `decoder` (src/train_segmentation.py:115), net_optim steps it (:540-541) and the step adds
 the reconstruction term (:391-398) through rec_loss.reconstruction_loss - the fused HIP kernels of dg_rec_loss.hip - logged as `loss/rec`.
 With cfg.arch == "dino_depth" (:104-106) the featurizer is the depth-guided one - featurizer.DinoFeaturizerWithDepth over the ViT under
@@ -51,6 +54,7 @@ import torch
 import torch.nn as nn
 
 from .aug_loss import aug_alignment_loss
+from .augment import IMAGENET_MEAN, IMAGENET_STD, augment_batch, draw_augment_params
 from .crf_loss import ContrastiveCRFLoss
 from .depth_decay import legacy_decay_step
 from .evaluation import predict_and_score, segment
@@ -287,6 +291,17 @@ class UnsupervisedSegmenter(nn.Module):
         if self.depth_only_intra:
             self._refuse_depth_only_intra_combinations(cfg)
         if getattr(cfg, "aug_alignment_weight", 0) > 0:         # (asked before anything is launched)
+            # cfg.dg_gpu_augment (build-side key, absent or False by default): a batch without the augmented view gets it here -
+            # parameters drawn from torch's global CPU generator, both tensors from batch["img"] at its own size in two HIP launches
+            # (augment.augment_batch).  "unit": img is ImageNet-normalised and the colour ops work on [0, 1] values; any other true
+            # value: the ops act on the tensor as given, as the reference's do.  A batch that carries the keys wins, untouched.
+            # (The draw is host work: capturing such a step into a graph is out of scope.)
+            gpu_augment = getattr(cfg, "dg_gpu_augment", False)
+            if gpu_augment and "img_aug" not in batch:
+                unit = isinstance(gpu_augment, str) and gpu_augment == "unit"
+                params = draw_augment_params(img.shape[0], img.shape[2], img.shape[3])
+                img_aug, coord_aug = augment_batch(img, params, mean=IMAGENET_MEAN if unit else None, std=IMAGENET_STD if unit else None)
+                batch = {**batch, "img_aug": img_aug, "coord_aug": coord_aug}
             for key in ("img_aug", "coord_aug"):
                 if key not in batch:
                     raise KeyError(f"training_step: cfg.aug_alignment_weight = {cfg.aug_alignment_weight} needs batch[{key!r}] "

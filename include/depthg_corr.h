@@ -979,6 +979,42 @@ int dg_xattn_backward(const float* q, const float* k, const float* v, const floa
                       float* grad_q, float* grad_k, float* grad_v, void* workspace, size_t workspace_bytes, dg_stream_t stream);
 int dg_xattn_keep_mask(uint64_t seed, int32_t B, int32_t heads, int32_t Nq, int32_t Nk, float p, uint8_t* out, dg_stream_t stream);
 
+/*
+ * GPU batch augmentation: the dataset's augmented view `img_aug` and its coordinate map `coord_aug` (src/data.py:1082-1139;
+ * src/train_segmentation.py:602-610) of a whole batch, every image under its own parameters, in two launches (dg_augment.hip):
+ *      flip -> crop `box` -> bilinear resize to (h, w) (align_corners=False, taps held inside the crop; a box never exceeds the image,
+ *      so this is never a down-scale) -> the record's colour ops in slot order -> RandomGrayscale -> 5 x 5 Gaussian blur (reflect pad)
+ * with the arithmetic of torchvision's tensor transforms, and the same flip, crop and resize on meshgrid(linspace(-1,1,H),
+ * linspace(-1,1,W)): coord_aug channel 0 is the row coordinate (aug_loss.crop_flip_coords's rule, bit for bit).
+ *  img : fp32 (B, 3, H, W); its four element strides are passed and must be those of a contiguous tensor (DG_ERR_UNSUPPORTED otherwise)
+ *  records_host : HOST memory, B records of 16 32-bit words: 0 flip (0 / 1), 1-4 the crop (top, left, height, width) in whole pixels of
+ *      the flipped image, 5-8 the op of each slot (0 brightness, 1 contrast, 2 saturation, 3 hue, -1 none), 9-12 the four factors as
+ *      fp32 indexed by op id, 13 gray (0 / 1), 14 blur sigma as fp32 (0: no blur), 15 zero.  Read by this call, on the host, for its
+ *      checks and to decide whether the statistics kernel is launched; not kept.
+ *  params : DEVICE memory, 4-byte aligned: a copy of the same B records followed by the H floats of linspace(-1, 1, H) and the W
+ *      floats of linspace(-1, 1, W) - what the kernels read.  (The kernels hold every index inside the image whatever it says.)
+ *  mean, stdv : HOST memory, three floats each, or both NULL.  NULL: the ops act on the tensor as given (the reference feeds them the
+ *      ImageNet-normalised image; their clamps to [0, 1] act on those values).  Given: x * stdv + mean behind the resize and
+ *      (x - mean) / stdv at the very end, per channel.
+ *  img_aug : fp32 (B, 3, h, w);  coord_aug : fp32 (B, h, w, 2) - EVERY element of both is written
+ *  workspace : dg_augment_workspace_bytes(B, h, w) bytes (0: sizes outside the limits below), 16-byte aligned: the fp64 partial sums
+ *      of the contrast op's image mean, at most 64 per image, added in block order.  Nothing is kept between calls.
+ * Ops: brightness clamp(f x, 0, 1); contrast clamp(f x + (1 - f) m, 0, 1) with m the mean over the image of gray(x) as the image
+ * stands when the op's turn comes (one contrast op per image at most); saturation clamp(f x + (1 - f) gray(x), 0, 1); gray(x) =
+ * 0.2989 r + 0.587 g + 0.114 b; hue: torchvision's _rgb2hsv, h = (h + f) mod 1, _hsv2rgb (p, q, t clamped to [0, 1]).
+ * Refused before any launch: DG_ERR_UNSUPPORTED for C != 3, a side of the image or of the output below 3 (reflect padding by 2 needs
+ * three pixels) or above 16384, B > 65535, a box outside the image, two contrast ops in one record, a non-contiguous img;
+ * DG_ERR_INVALID for null or misaligned pointers, an op id outside -1 .. 3, a negative or non-finite sigma, std <= 0;
+ * DG_ERR_WORKSPACE for a workspace that is too small.  Arithmetic: source positions fp64, everything behind them fp32 with one
+ * rounding per operation (the blur's weights, products and sum are fp64, rounded once per pixel), the image mean fp64.  No atomics:
+ * two calls give the same bits.  No host synchronisation, no allocation.
+ */
+size_t dg_augment_workspace_bytes(int32_t B, int32_t h, int32_t w);
+int dg_augment_forward(const float* img, int64_t stride_b, int64_t stride_c, int64_t stride_h, int64_t stride_w,
+                       const int32_t* records_host, const void* params, const float* mean, const float* stdv, int32_t B, int32_t C,
+                       int32_t H, int32_t W, int32_t h, int32_t w, float* img_aug, float* coord_aug, void* workspace,
+                       size_t workspace_bytes, dg_stream_t stream);
+
 /* Measurement aid: name of the kernel the fused correlation launch of this descriptor runs ("k_corr2": the one-wave-per-SIMD
  * form of dg_corr2.hip, "k_corr_main": the general form), decided by the same predicate the launch uses; NULL on a bad desc. */
 const char* dg_corr_main_kernel_name(const dg_corr_desc* desc);
