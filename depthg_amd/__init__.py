@@ -36,7 +36,8 @@ Public surface (mirrors the reference's Python operator surface for this path):
                                  DinoFeaturizerWithDepth (:490-631, cfg.arch "dino_depth"): depth-guided features in front of the head
     cross_attn                   the depth guidance's nn.MultiheadAttention core (src/modules.py:524, :566-585) as a fused HIP forward
                                  and backward with Philox dropout (cfg.dg_fused_cross_attn)
-    ops                          thin ctypes binding of the C ABI in include/depthg_corr.h
+    ops                          thin ctypes binding of the C ABI in include/depthg_corr.h; ops.corr_forward is the one route to its five
+                                 forward entries (keep / feat_inv / intra_feats select one; perms=None draws the batch maps)
 """
 from .loss import ContrastiveCorrelationLoss, DepthContrastiveCorrelationLoss  # noqa: F401
 from . import crf_loss  # noqa: F401

@@ -485,13 +485,22 @@ static void small_args(const Plan& p, const dg_corr_desc* d, char* ws, const int
 
 struct FeatKeep { const float* keep[2]; float scale; };      // deferred Dropout2d of the two feature maps (dg_corr_forward_masked)
 
-// ---- the forward call: what its stages share
-struct Fwd {
+// ---- the forward call: what an entry point hands in (the seven maps, the batch maps, then one extra at most) ...
+struct FwdInputs {
+    const float *feats, *feats_pos, *code, *code_pos, *depth, *coords1, *coords2;
+    const int64_t* perms;
+    const DrawArgs* draw = nullptr;     // the call draws `perms` itself
+    const FeatKeep* fk = nullptr;       // dg_corr_forward_masked
+    const float* feat_inv = nullptr;    // dg_corr_forward_extnorm
+    const float* intra = nullptr;       // dg_corr_forward_intra_feats (intra_entry): the map behind operand p.xop's features
+    bool intra_entry = false;
+};
+
+// ... and what its stages share
+struct Fwd : FwdInputs {
+    explicit Fwd(const FwdInputs& in) : FwdInputs(in) {}
     Plan p{};
     const dg_corr_desc* desc;
-    const float *feats, *feats_pos, *code, *code_pos, *depth, *coords1, *coords2;
-    const int64_t* perms; const DrawArgs* draw; const FeatKeep* fk; const float* feat_inv;
-    const float* intra;                 // dg_corr_forward_intra_feats: the map behind operand p.xop's features
     float* out;
     char* ws; hipStream_t stream;
     // (the region object - it holds the side stream's lock - exists only on calls that use it: the exact-mask chain of the dense grid
@@ -847,19 +856,12 @@ static int fwd_finish(Fwd& c) {
     return DG_OK;
 }
 
-static int corr_forward_impl(const dg_corr_desc* desc, const float* orig_feats, const float* orig_feats_pos,
-                             const float* orig_code, const float* orig_code_pos, const float* depth,
-                             const float* coords1, const float* coords2, const int64_t* perms, const DrawArgs* draw,
-                             float* out_scalars, void* workspace, size_t workspace_bytes, dg_stream_t stream_,
-                             const FeatKeep* fk = nullptr, const float* feat_inv = nullptr, bool intra_entry = false,
-                             const float* intra_feats = nullptr) {
-    Fwd c;
-    if (int rc = make_plan(desc, c.p, intra_entry)) return rc;
-    c.intra = intra_feats;
+static int corr_forward_impl(const dg_corr_desc* desc, const FwdInputs& in, float* out_scalars, void* workspace, size_t workspace_bytes,
+                             dg_stream_t stream_) {
+    Fwd c(in);
+    if (int rc = make_plan(desc, c.p, in.intra_entry)) return rc;
     const Plan& p = c.p;
-    c.desc = desc; c.feats = orig_feats; c.feats_pos = orig_feats_pos; c.code = orig_code; c.code_pos = orig_code_pos; c.depth = depth;
-    c.coords1 = coords1; c.coords2 = coords2; c.perms = perms; c.draw = draw; c.fk = fk; c.feat_inv = feat_inv; c.out = out_scalars;
-    c.stream = static_cast<hipStream_t>(stream_);
+    c.desc = desc; c.out = out_scalars; c.stream = static_cast<hipStream_t>(stream_);
     if (int rc = fwd_validate(c, workspace, workspace_bytes)) return rc;
 
     // Exact clamp masks on the dense grid (round 6): the mask words depend on the code maps and the batch maps only, so their chain
@@ -875,7 +877,7 @@ static int corr_forward_impl(const dg_corr_desc* desc, const float* orig_feats, 
 
     // (the job table of step 4 is needed here already: the consumer lists of k_corr2's grouped ragged blocks are written by
     //  extra blocks of the k_colmean launch)
-    build_corr_jobs(p, c.ws, perms, c.a);
+    build_corr_jobs(p, c.ws, c.perms, c.a);
 
     // 3. column sums of the operands, the exact masks that need them, then the row means of fd
     if (int rc = fwd_colmeans(c)) return rc;
@@ -894,8 +896,8 @@ extern "C" int dg_corr_forward(const dg_corr_desc* desc, const float* orig_feats
                                const float* orig_code, const float* orig_code_pos, const float* depth,
                                const float* coords1, const float* coords2, const int64_t* perms,
                                float* out_scalars, void* workspace, size_t workspace_bytes, dg_stream_t stream_) {
-    return corr_forward_impl(desc, orig_feats, orig_feats_pos, orig_code, orig_code_pos, depth, coords1, coords2, perms, nullptr,
-                             out_scalars, workspace, workspace_bytes, stream_);
+    const FwdInputs in{orig_feats, orig_feats_pos, orig_code, orig_code_pos, depth, coords1, coords2, perms};
+    return corr_forward_impl(desc, in, out_scalars, workspace, workspace_bytes, stream_);
 }
 
 extern "C" int dg_corr_forward_extnorm(const dg_corr_desc* desc, const float* orig_feats, const float* orig_feats_pos,
@@ -903,8 +905,9 @@ extern "C" int dg_corr_forward_extnorm(const dg_corr_desc* desc, const float* or
                                        const float* coords1, const float* coords2, const int64_t* perms, const float* feat_inv,
                                        float* out_scalars, void* workspace, size_t workspace_bytes, dg_stream_t stream_) {
     if (!feat_inv) return fail(DG_ERR_INVALID, "dg_corr_forward_extnorm: feat_inv is null");
-    return corr_forward_impl(desc, orig_feats, orig_feats_pos, orig_code, orig_code_pos, depth, coords1, coords2, perms, nullptr,
-                             out_scalars, workspace, workspace_bytes, stream_, nullptr, feat_inv);
+    FwdInputs in{orig_feats, orig_feats_pos, orig_code, orig_code_pos, depth, coords1, coords2, perms};
+    in.feat_inv = feat_inv;
+    return corr_forward_impl(desc, in, out_scalars, workspace, workspace_bytes, stream_);
 }
 
 extern "C" int dg_sampled_sumsq(int32_t B, int32_t C, int32_t h, int32_t w, int32_t S, int32_t line_grid, const float* feats,
@@ -921,8 +924,9 @@ extern "C" int dg_corr_forward_draw(const dg_corr_desc* desc, const float* orig_
     if (!desc) return fail(DG_ERR_INVALID, "null descriptor");
     if (desc->n_neg > 0 && !perms_out) return fail(DG_ERR_INVALID, "perms_out is null with n_neg=%d", desc->n_neg);
     const DrawArgs draw{perms_out, seed, static_cast<unsigned long long*>(perm_state)};
-    return corr_forward_impl(desc, orig_feats, orig_feats_pos, orig_code, orig_code_pos, depth, coords1, coords2, perms_out, &draw,
-                             out_scalars, workspace, workspace_bytes, stream_);
+    FwdInputs in{orig_feats, orig_feats_pos, orig_code, orig_code_pos, depth, coords1, coords2, perms_out};
+    in.draw = &draw;
+    return corr_forward_impl(desc, in, out_scalars, workspace, workspace_bytes, stream_);
 }
 
 extern "C" int dg_corr_forward_intra_feats(const dg_corr_desc* desc, const float* orig_feats, const float* orig_feats_pos,
@@ -933,8 +937,9 @@ extern "C" int dg_corr_forward_intra_feats(const dg_corr_desc* desc, const float
     if (!desc) return fail(DG_ERR_INVALID, "null descriptor");
     if (desc->n_neg > 0 && !perms) return fail(DG_ERR_INVALID, "perms is null with n_neg=%d", desc->n_neg);
     const DrawArgs draw{perms, seed, static_cast<unsigned long long*>(perm_state)};
-    return corr_forward_impl(desc, orig_feats, orig_feats_pos, orig_code, orig_code_pos, depth, coords1, coords2, perms,
-                             draw_perms ? &draw : nullptr, out_scalars, workspace, workspace_bytes, stream_, nullptr, nullptr, true, intra_feats);
+    FwdInputs in{orig_feats, orig_feats_pos, orig_code, orig_code_pos, depth, coords1, coords2, perms};
+    in.draw = draw_perms ? &draw : nullptr; in.intra = intra_feats; in.intra_entry = true;
+    return corr_forward_impl(desc, in, out_scalars, workspace, workspace_bytes, stream_);
 }
 
 extern "C" int dg_corr_forward_masked(const dg_corr_desc* desc, const float* orig_feats, const float* orig_feats_pos,
@@ -947,8 +952,9 @@ extern "C" int dg_corr_forward_masked(const dg_corr_desc* desc, const float* ori
     if ((feat_keep || feat_pos_keep) && !(keep_scale > 0.f)) return fail(DG_ERR_INVALID, "keep_scale %g with keep flags", (double)keep_scale);
     const DrawArgs draw{perms, seed, static_cast<unsigned long long*>(perm_state)};
     const FeatKeep fk{{feat_keep, feat_pos_keep}, keep_scale};
-    return corr_forward_impl(desc, orig_feats, orig_feats_pos, orig_code, orig_code_pos, depth, coords1, coords2, perms,
-                             draw_perms ? &draw : nullptr, out_scalars, workspace, workspace_bytes, stream_, &fk);
+    FwdInputs in{orig_feats, orig_feats_pos, orig_code, orig_code_pos, depth, coords1, coords2, perms};
+    in.draw = draw_perms ? &draw : nullptr; in.fk = &fk;
+    return corr_forward_impl(desc, in, out_scalars, workspace, workspace_bytes, stream_);
 }
 
 // ---- the backward: the source table of the one k_scatter launch, filled from the pair-set table

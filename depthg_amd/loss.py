@@ -57,37 +57,23 @@ def identity_coords(b: int, s: int, device) -> torch.Tensor:
     return c
 
 
+class _Launched:
+    """What a forward hands back beside its autograd outputs: the batch maps it ran on (its own draw included) and its workspace."""
+    __slots__ = ("perms", "workspace")
+
+
 class _CorrLossFunction(torch.autograd.Function):
     """out[DG_OUT_COUNT] = fused loss scalars (+ weighted total); backward = dg_corr_backward with the upstream of that vector."""
 
     @staticmethod
-    def forward(ctx, orig_code, orig_code_pos, orig_feats, orig_feats_pos, depth, coords1, coords2, perms, desc, holder):
-        intra = holder.get("intra_feats")
-        ws = ops.alloc_workspace(desc, orig_feats.device) if intra is None else ops.alloc_workspace_intra_feats(desc, orig_feats.device)
-        fk = holder.get("feat_keep")
-        if intra is not None:              # the intra pair-set correlates a second feature map (DepthContrastiveCorrelationLoss)
-            drew = perms is None
-            out, perms = ops.corr_forward_intra_feats(desc, orig_feats, orig_feats_pos, orig_code, orig_code_pos, coords1, coords2,
-                                                      perms, intra, ws, holder.get("draw_state"))
-            if drew:
-                holder["perms"] = perms
-        elif holder.get("feat_inv") is not None:     # one channel chunk of wider maps on sampled coordinates (forward_with: `wide`)
-            out = ops.corr_forward_extnorm(desc, orig_feats, orig_feats_pos, orig_code, orig_code_pos, depth, coords1, coords2,
-                                           perms, holder["feat_inv"], ws)
-        elif fk is not None:               # Dropout2d of the feature maps applied inside the operand preparation (identity grid)
-            drew = perms is None
-            out, perms = ops.corr_forward_masked(desc, orig_feats, orig_feats_pos, orig_code, orig_code_pos, depth, coords1, coords2,
-                                                 perms, ws, holder.get("draw_state"), fk[0], fk[1], fk[2])
-            if drew:
-                holder["perms"] = perms
-        elif perms is None:                # the forward draws the negatives itself (holder["draw_state"]: device generator or None)
-            out, perms = ops.corr_forward_draw(desc, orig_feats, orig_feats_pos, orig_code, orig_code_pos, depth, coords1, coords2,
-                                               ws, state=holder.get("draw_state"))
-            holder["perms"] = perms
-        else:
-            out = ops.corr_forward(desc, orig_feats, orig_feats_pos, orig_code, orig_code_pos, depth, coords1, coords2,
-                                   perms, ws)
-        holder["workspace"] = ws
+    def forward(ctx, orig_code, orig_code_pos, orig_feats, orig_feats_pos, depth, coords1, coords2, perms, desc, draw_state, keep,
+                feat_inv, intra_feats, launched):
+        # perms None: the forward draws the negatives itself (draw_state: device generator or None); keep: Dropout2d of the feature maps
+        # applied inside the operand preparation (identity grid); feat_inv: one channel chunk of wider maps on sampled coordinates
+        # (forward_with: `wide`); intra_feats: the intra pair-set correlates a second feature map (DepthContrastiveCorrelationLoss)
+        out, perms, ws = ops.corr_forward(desc, orig_feats, orig_feats_pos, orig_code, orig_code_pos, depth, coords1, coords2, perms,
+                                          draw_state=draw_state, keep=keep, feat_inv=feat_inv, intra_feats=intra_feats)
+        launched.perms, launched.workspace = perms, ws
         ctx.desc, ctx.ws, ctx.shape = desc, ws, tuple(orig_code.shape)
         ctx.save_for_backward(coords1, coords2, perms)
         # second output: the weighted total as its own autograd output (a view of element DG_OUT_TOTAL), so that
@@ -97,7 +83,7 @@ class _CorrLossFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gout, gtotal):
-        nothing = (None,) * 10
+        nothing = (None,) * 14
         if gout is None and gtotal is None:
             return nothing
         coords1, coords2, perms = ctx.saved_tensors
@@ -270,13 +256,14 @@ class ContrastiveCorrelationLoss(nn.Module):
 
     # -- everything after the RNG draws (explicit coords / perms: parity tests, DP shards) ----------
     def forward_with(self, orig_feats, orig_feats_pos, orig_code, orig_code_pos, depth, coords1, coords2, perms,
-                     shared_coords=False, identity_grid=False, draw_state=None, _checked=False, feat_keep=None):
+                     shared_coords=False, identity_grid=False, draw_state=None, _checked=False, feat_keep=None, intra_feats=None):
+        """intra_feats: fp32 contiguous, the shape of orig_feats - the intra pair-set's feature map (DepthContrastiveCorrelationLoss)."""
         if feat_keep is None:
             orig_feats, orig_feats_pos, feat_keep = self._unwrap_deferred(orig_feats, orig_feats_pos)
         if not _checked:
             self._check_maps(orig_feats, orig_feats_pos, orig_code, orig_code_pos, depth)
         call = self._prepare(orig_feats, orig_feats_pos, orig_code, orig_code_pos, depth, coords1, coords2, perms,
-                             bool(shared_coords), bool(identity_grid), draw_state, feat_keep)
+                             bool(shared_coords), bool(identity_grid), draw_state, feat_keep, intra_feats=intra_feats)
         wide = call.C > ops.BLOB_MAX_C and (call.identity_grid or call.P_pos > SMALL_GRID_POSITIONS)
         if call.feat_keep is not None and (wide or not call.identity_grid):
             # only the identity grid's own operand preparation takes the keep flags (dg_corr_forward_masked): the samplers, and the
@@ -328,7 +315,7 @@ class ContrastiveCorrelationLoss(nn.Module):
         return {"intra_cd": counts[0], "inter_cd": counts[1], "neg_cd": counts[2:].sum(dim=0)}
 
     def _prepare(self, orig_feats, orig_feats_pos, orig_code, orig_code_pos, depth, coords1, coords2, perms, shared_coords,
-                 identity_grid, draw_state, feat_keep):
+                 identity_grid, draw_state, feat_keep, intra_feats=None):
         """Everything forward_with checks and converts in front of the first launch, in the order the errors are promised in: the
         call's operands as the library reads them and its dimensions, as one namespace."""
         cfg = self.cfg
@@ -378,9 +365,9 @@ class ContrastiveCorrelationLoss(nn.Module):
         code_pos = orig_code_pos if orig_code_pos.dtype == torch.float32 else orig_code_pos.float()
         return SimpleNamespace(
             feats=feats, feats_pos=feats_pos, code=code.contiguous(), code_pos=code_pos.contiguous(), depth=depth_c, coords1=coords1,
-            coords2=coords2, perms=perms_t, feat_keep=feat_keep, draw_state=draw_state, dev=dev, B=B, C=C, h=h, w=w, D=D, S=S, N=N,
-            code_hw=None if (hc, wc) == (h, w) else (hc, wc), P_pos=int(coords1.shape[1]) * int(coords1.shape[2]),
-            line_grid=coords1.shape[2] == 1 and S != 1,       # S x 1 grid of depth_sampling='simple'
+            coords2=coords2, perms=perms_t, feat_keep=feat_keep, intra_feats=intra_feats, draw_state=draw_state, dev=dev,
+            B=B, C=C, h=h, w=w, D=D, S=S, N=N, code_hw=None if (hc, wc) == (h, w) else (hc, wc),
+            P_pos=int(coords1.shape[1]) * int(coords1.shape[2]), line_grid=coords1.shape[2] == 1 and S != 1,       # S x 1 grid of depth_sampling='simple'
             depth_term=depth_term, shared_coords=shared_coords, identity_grid=identity_grid,
             need_grad=torch.is_grad_enabled() and (orig_code.requires_grad or orig_code_pos.requires_grad),
             shifts=(cfg.pos_intra_shift, cfg.pos_inter_shift, cfg.neg_inter_shift, cfg.depth_feat_shift if depth_term else 0.0))
@@ -417,12 +404,12 @@ class ContrastiveCorrelationLoss(nn.Module):
                              depth_hw=tuple(call.depth.shape[-2:]) if (call.depth is not None and dt) else (0, 0),
                              identity_grid=call.identity_grid, weights=weights, line_grid=call.line_grid,
                              code_hw=call.code_hw, exact_masks=bool(getattr(cfg, "dg_exact_masks", False)), feats_unit=unit)
-        holder = {"draw_state": call.draw_state, "feat_keep": keep, "feat_inv": feat_inv, "intra_feats": getattr(call, "intra_feats", None)}
-        out, total = _CorrLossFunction.apply(call.code, call.code_pos, f_a, f_b, call.depth if dt else None,
-                                             call.coords1, call.coords2, call.perms, desc, holder)
+        launched = _Launched()
+        out, total = _CorrLossFunction.apply(call.code, call.code_pos, f_a, f_b, call.depth if dt else None, call.coords1, call.coords2,
+                                             call.perms, desc, call.draw_state, keep, feat_inv, call.intra_feats, launched)
         if call.perms is None:
-            call.perms = holder["perms"]       # (drawn by the forward: what backward, materialize and further chunks read)
-        return out, total, desc, holder["workspace"]
+            call.perms = launched.perms        # (drawn by the forward: what backward, materialize and further chunks read)
+        return out, total, desc, launched.workspace
 
     def _run_chunks(self, call, fa, fb, unit=False, keep=None, feat_inv=None):
         """The channel chunks fa[k] / fb[k] of the two feature maps, one launch set each (a map the kernels hold whole: one chunk):
@@ -582,14 +569,5 @@ class DepthContrastiveCorrelationLoss(ContrastiveCorrelationLoss):
                              f"{orig_code.shape[-2]}x{orig_code.shape[-1]} against {orig_feats.shape[-2]}x{orig_feats.shape[-1]}")
         if tuple(coords1.shape) != (orig_feats.shape[0], int(self.cfg.feature_samples), int(self.cfg.feature_samples), 2):
             raise ValueError(f"depthg_amd: DepthContrastiveCorrelationLoss takes (B,S,S,2) coordinates, got {tuple(coords1.shape)}")
-        self.__dict__["_intra_feats"] = ops._f32c(depth_aug_feats, "depth_aug_feats")
-        try:
-            return super().forward_with(orig_feats, orig_feats_pos, orig_code, orig_code_pos, None, coords1, coords2, perms,
-                                        _checked=True)
-        finally:
-            self.__dict__["_intra_feats"] = None
-
-    def _prepare(self, *args):
-        call = super()._prepare(*args)
-        call.intra_feats = self.__dict__["_intra_feats"]
-        return call
+        return super().forward_with(orig_feats, orig_feats_pos, orig_code, orig_code_pos, None, coords1, coords2, perms,
+                                    _checked=True, intra_feats=ops._f32c(depth_aug_feats, "depth_aug_feats"))

@@ -109,63 +109,80 @@ def sampled_sumsq(feats_chunk, coords, srcidx, out, accumulate):
                                             1 if accumulate else 0, _ptr(out), _stream(feats_chunk.device)), "dg_sampled_sumsq")
 
 
-def workspace_bytes(desc):
-    n = _lib.load().dg_corr_workspace_bytes(ctypes.byref(desc))
+def workspace_bytes(desc, intra_feats=False):
+    """Bytes of workspace a forward on `desc` needs; intra_feats: the plain call's regions, then the intra feature operand's (the
+    backward, cd_hist and materialize take that workspace as they take the plain one)."""
+    entry = "dg_corr_workspace_bytes_intra_feats" if intra_feats else "dg_corr_workspace_bytes"
+    n = getattr(_lib.load(), entry)(ctypes.byref(desc))
     if n == 0:
-        _lib.check(-1, "dg_corr_workspace_bytes")
+        _lib.check(-1, entry)
     return n
 
 
-def alloc_workspace(desc, device):
-    return _empty(workspace_bytes(desc), torch.uint8, device)
+def alloc_workspace(desc, device, intra_feats=False):
+    return _empty(workspace_bytes(desc, intra_feats), torch.uint8, device)
 
 
 _forward_count = 0        # forwards run so far: every forward stamps its workspace tensor (`_dg_forward`), so that a reader of the
                           # operands it left there (ContrastiveCorrelationLoss.cd_histograms) can tell a workspace that was run on again
 
 
-def _corr_forward(entry, desc, maps, perms, mid, workspace):
-    """The one body of the four forward entry points, whose argument lists differ only between `perms` and `out_scalars`: `mid`."""
+def corr_forward(desc, feats, feats_pos, code, code_pos, depth, coords1, coords2, perms, workspace=None, *,
+                 draw_state=None, keep=None, feat_inv=None, intra_feats=None):
+    """The forward, through the one C entry its extras select.  -> (out, perms, workspace): out fp32 [DG_OUT_COUNT] on the device
+    (order: DG_OUT_* of include/depthg_corr.h); perms (n_neg, B) int64 and workspace are what backward / materialize need.
+      perms None    drawn by the forward itself (on the identity grid inside its first launch): dg_corr_forward_draw, or the masked /
+                    intra entry's own draw.  `draw_state` (new_perm_state) = device-resident generator (hipGraph-safe); without it the
+                    seed comes from torch's CPU generator, as in super_perms().
+      keep          (keep, keep_pos, scale): dg_corr_forward_masked - UN-dropped feature maps + their Dropout2d keep flags (B,C), either
+                    may be None (identity grid).
+      feat_inv      dg_corr_forward_extnorm - ONE channel chunk of wider feature maps, normalised by `feat_inv` (nops, B, P): 1 / the
+                    norm of the whole sampled vector (sampled coordinates above 160 positions; see include/depthg_corr.h).
+      intra_feats   dg_corr_forward_intra_feats - the intra pair-set correlates `intra_feats` (the shape of `feats`, sampled at coords1)
+                    instead of `feats` (DepthContrastiveCorrelationLoss, src/modules.py:1427-1438); `depth` is not read.
+      workspace     None: allocated here by the sizer of the entry; else alloc_workspace(desc, device, intra_feats=...)'s.
+    The C ABI has one entry per extra, so two extras at once are refused, and so is `feat_inv` without `perms` (that entry has no draw).
+    (Messages about an operand name its entry without the dg_ prefix, as they always have: entry[3:].)"""
     global _forward_count
-    dev = maps[0].device
+    if (keep is not None) + (feat_inv is not None) + (intra_feats is not None) > 1:
+        given = [f"`{n}`" for n, v in (("keep", keep), ("feat_inv", feat_inv), ("intra_feats", intra_feats)) if v is not None]
+        raise ValueError(f"corr_forward: {' and '.join(given)} cannot ride in one call (the C ABI has one entry for each)")
+    draw, seed, dev = perms is None, 0, feats.device
+    if draw and feat_inv is not None:
+        raise ValueError("corr_forward: `feat_inv` needs `perms`: perms=None asks for a draw, and dg_corr_forward_extnorm has none")
+    entry = ("dg_corr_forward_masked" if keep is not None else "dg_corr_forward_extnorm" if feat_inv is not None else
+             "dg_corr_forward_intra_feats" if intra_feats is not None else "dg_corr_forward_draw" if draw else "dg_corr_forward")
+    if workspace is None:
+        workspace = alloc_workspace(desc, dev, intra_feats is not None)
+    if intra_feats is not None and (intra_feats.dtype != torch.float32 or not intra_feats.is_contiguous() or intra_feats.device != dev
+                                    or tuple(intra_feats.shape) != tuple(feats.shape)):
+        raise ValueError(f"{entry[3:]}: intra_feats must be contiguous fp32 {tuple(feats.shape)} on {dev}, got "
+                         f"{intra_feats.dtype} {tuple(intra_feats.shape)} on {intra_feats.device}")
+    if draw:
+        perms = _empty((int(desc.n_neg), int(desc.B)), torch.long, dev)
+        if draw_state is None:
+            seed = _cpu_seed()
+        else:
+            _check_state(draw_state, entry[3:], dev)      # (keys the draw on the device: seed 0)
+    state = _ptr(draw_state) if draw else None
+    if keep is not None:
+        for k in keep[:2]:
+            if k is not None and (k.dtype != torch.float32 or not k.is_contiguous() or k.device != dev or tuple(k.shape) != (int(desc.B), int(desc.C))):
+                raise ValueError(f"{entry[3:]}: keep flags must be contiguous fp32 (B,C) = ({desc.B},{desc.C}) on {dev}")
+        mid = (int(draw), seed, state, _ptr(keep[0]), _ptr(keep[1]), float(keep[2]))
+    elif feat_inv is not None:
+        mid = (_ptr(feat_inv),)
+    elif intra_feats is not None:
+        mid, depth = (int(draw), seed, state, _ptr(intra_feats)), None
+    else:
+        mid = (seed, state) if draw else ()
     _forward_count += 1
     workspace._dg_forward = _forward_count
     out = _empty(_lib.DG_OUT_COUNT, torch.float32, dev)
-    rc = getattr(_lib.load(), entry)(ctypes.byref(desc), *[_ptr(t) for t in maps], _ptr(perms), *mid, _ptr(out), _ptr(workspace),
-                                     workspace.numel(), _stream(dev))
+    rc = getattr(_lib.load(), entry)(ctypes.byref(desc), _ptr(feats), _ptr(feats_pos), _ptr(code), _ptr(code_pos), _ptr(depth), _ptr(coords1),
+                                     _ptr(coords2), _ptr(perms), *mid, _ptr(out), _ptr(workspace), workspace.numel(), _stream(dev))
     _lib.check(rc, entry)
-    return out
-
-
-def _drawn_perms(desc, dev, state, who):
-    """(the (n_neg, B) buffer a drawing forward fills, its seed): `state` (new_perm_state) keys the draw on the device (seed 0), else
-    the seed comes from torch's CPU generator, as in super_perms()."""
-    perms = _empty((int(desc.n_neg), int(desc.B)), torch.long, dev)
-    if state is None:
-        return perms, _cpu_seed()
-    _check_state(state, who, dev)
-    return perms, 0
-
-
-def corr_forward(desc, feats, feats_pos, code, code_pos, depth, coords1, coords2, perms, workspace):
-    """Returns fp32 [DG_OUT_COUNT] device tensor (order: DG_OUT_* of include/depthg_corr.h)."""
-    return _corr_forward("dg_corr_forward", desc, (feats, feats_pos, code, code_pos, depth, coords1, coords2), perms, (), workspace)
-
-
-def corr_forward_extnorm(desc, feats, feats_pos, code, code_pos, depth, coords1, coords2, perms, feat_inv, workspace):
-    """dg_corr_forward on ONE channel chunk of wider feature maps, normalised by `feat_inv` (nops, B, P): 1 / the norm of the whole
-    sampled vector (sampled coordinates above 160 positions; see include/depthg_corr.h)."""
-    return _corr_forward("dg_corr_forward_extnorm", desc, (feats, feats_pos, code, code_pos, depth, coords1, coords2), perms,
-                         (_ptr(feat_inv),), workspace)
-
-
-def corr_forward_draw(desc, feats, feats_pos, code, code_pos, depth, coords1, coords2, workspace, state=None):
-    """dg_corr_forward_draw: the forward draws the negatives' batch maps itself (on the identity grid inside its first launch).
-    Returns (out, perms): perms (n_neg, B) int64 is what backward / materialize need.  `state` (new_perm_state) = device-resident
-    generator (hipGraph-safe); without it the seed comes from torch's CPU generator, as in super_perms()."""
-    perms, seed = _drawn_perms(desc, feats.device, state, "corr_forward_draw")
-    return _corr_forward("dg_corr_forward_draw", desc, (feats, feats_pos, code, code_pos, depth, coords1, coords2), perms,
-                         (seed, _ptr(state)), workspace), perms
+    return out, perms, workspace
 
 
 class DeferredDropout:
@@ -192,48 +209,6 @@ class DeferredDropout:
 
     def materialize(self):
         return self.feats * (self.keep.to(torch.float32) * self.scale)[:, :, None, None]
-
-
-def corr_forward_masked(desc, feats, feats_pos, code, code_pos, depth, coords1, coords2, perms, workspace, state, keep, keep_pos,
-                        scale):
-    """dg_corr_forward_masked: the forward on UN-dropped feature maps + their Dropout2d keep flags (identity grid).  perms None:
-    drawn inside (as corr_forward_draw).  Returns (out, perms)."""
-    dev = feats.device
-    draw, seed = int(perms is None), 0
-    if draw:
-        perms, seed = _drawn_perms(desc, dev, state, "corr_forward_masked")
-    for k in (keep, keep_pos):
-        if k is not None and (k.dtype != torch.float32 or not k.is_contiguous() or k.device != dev or tuple(k.shape) != (int(desc.B), int(desc.C))):
-            raise ValueError(f"corr_forward_masked: keep flags must be contiguous fp32 (B,C) = ({desc.B},{desc.C}) on {dev}")
-    mid = (draw, seed, _ptr(state) if draw else None, _ptr(keep), _ptr(keep_pos), float(scale))
-    return _corr_forward("dg_corr_forward_masked", desc, (feats, feats_pos, code, code_pos, depth, coords1, coords2), perms, mid,
-                         workspace), perms
-
-
-def alloc_workspace_intra_feats(desc, device):
-    """The workspace of corr_forward_intra_feats: dg_corr_workspace_bytes_intra_feats - the plain call's regions, then the intra
-    feature operand's (the backward, cd_hist and materialize take it as they take the plain one)."""
-    n = _lib.load().dg_corr_workspace_bytes_intra_feats(ctypes.byref(desc))
-    if n == 0:
-        _lib.check(-1, "dg_corr_workspace_bytes_intra_feats")
-    return _empty(n, torch.uint8, device)
-
-
-def corr_forward_intra_feats(desc, feats, feats_pos, code, code_pos, coords1, coords2, perms, intra_feats, workspace, state=None):
-    """dg_corr_forward_intra_feats: the forward whose intra pair-set correlates `intra_feats` (the shape of `feats`, sampled at
-    coords1) instead of `feats` (DepthContrastiveCorrelationLoss, src/modules.py:1427-1438).  perms None: drawn inside (as
-    corr_forward_draw).  `workspace`: alloc_workspace_intra_feats.  Returns (out, perms)."""
-    dev = feats.device
-    if intra_feats.dtype != torch.float32 or not intra_feats.is_contiguous() or intra_feats.device != dev or \
-            tuple(intra_feats.shape) != tuple(feats.shape):
-        raise ValueError(f"corr_forward_intra_feats: intra_feats must be contiguous fp32 {tuple(feats.shape)} on {dev}, got "
-                         f"{intra_feats.dtype} {tuple(intra_feats.shape)} on {intra_feats.device}")
-    draw, seed = int(perms is None), 0
-    if draw:
-        perms, seed = _drawn_perms(desc, dev, state, "corr_forward_intra_feats")
-    mid = (draw, seed, _ptr(state) if draw else None, _ptr(intra_feats))
-    return _corr_forward("dg_corr_forward_intra_feats", desc, (feats, feats_pos, code, code_pos, None, coords1, coords2), perms, mid,
-                         workspace), perms
 
 
 def _corr_backward(entry, desc, grad, coords1, coords2, perms, workspace, shape_code):

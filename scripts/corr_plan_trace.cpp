@@ -1,6 +1,6 @@
 // Recorded-launch trace of the correlation loss's host unit (depthg_amd/csrc/dg_api_corr.hip), without a GPU.
 // The unit is compiled for the host and linked against the recording stand-ins below for everything it calls outward: every
-// dg_launch_*, side_stream_for, hipEventRecord, hipStreamWaitEvent, fail and the error string; the dg_*_supported predicates are the
+// dg_launch_*, side_stream_for, hipEventRecord, hipStreamWaitEvent, hipMemsetAsync, fail and the error string; the dg_*_supported predicates are the
 // tree's own (predicates.inc: their text, lifted from dg_corr2.hip and dg_small.hip by the build script).  No call reaches the HIP runtime; the workspace and all tensors are fixed made-up
 // addresses, and the unit zeroes its argument blocks before it fills them, so two builds of the unit give records that compare byte
 // for byte.  main() walks a grid of descriptors and calls every entry point for each (refused calls included), prints one line per
@@ -137,7 +137,11 @@ hipError_t dg_launch_gs(const DgGsArgs& a, const uint32_t* dep_maskbits, hipStre
     return result("dg_launch_gs");
 }
 hipError_t dg_launch_finish(const DgFinishArgs& a, hipStream_t s) { record("dg_launch_finish", s, a); return result("dg_launch_finish"); }
-hipError_t dg_launch_transpose(const DgTransposeArgs& a, int B, hipStream_t s) { record("dg_launch_transpose", s, a, {B}); return result("dg_launch_transpose"); }
+hipError_t dg_launch_transpose(const DgTransposeArgs& a, int B, hipStream_t s) {
+    record("dg_launch_transpose", s, a, {B});
+    if (a.nmaps == 5) route("xop");          // (the plan's xop >= 0: the intra feature map is the fifth map, or src_x below)
+    return result("dg_launch_transpose");
+}
 hipError_t dg_launch_gather(const DgGatherArgs& a, int maxK, hipStream_t s) {
     record("dg_launch_gather", s, a, {maxK});
     route("general_blobs");
@@ -157,6 +161,7 @@ hipError_t dg_launch_cd_mask3(const DgCdMask3Args& a, hipStream_t s) {
 hipError_t dg_launch_plane_sample(const DgPlaneArgs& a, hipStream_t s) {
     record("dg_launch_plane_sample", s, a);
     if (a.feats_bf16) route("small_plane_sampler");
+    if (a.src_x) route("xop");
     return result("dg_launch_plane_sample");
 }
 hipError_t dg_launch_colmean(const DgColmeanArgs& a, hipStream_t s) { record("dg_launch_colmean", s, a); return result("dg_launch_colmean"); }
@@ -201,6 +206,11 @@ hipError_t dg_launch_sampled_sumsq(const float* feats, const float* coords, cons
     record_values("dg_launch_sampled_sumsq", s, {addr(feats), addr(coords), addr(srcidx), addr(out), B, C, h, w, S, Sh, accumulate});
     return result("dg_launch_sampled_sumsq");
 }
+extern "C" hipError_t hipMemsetAsync(void* dst, int value, size_t bytes, hipStream_t s) {
+    record_values("hipMemsetAsync", s, {addr(dst), value, (long long)bytes});
+    return result("hipMemsetAsync");
+}
+hipError_t dg_launch_cd_hist(const DgCdHistArgs& a, bool rows, hipStream_t s) { record("dg_launch_cd_hist", s, a, {rows ? 1 : 0}); return result("dg_launch_cd_hist"); }
 hipError_t dg_launch_normalize_split(const float* src, int B, int C, int P, int nchunks, int chunk_c, float* const* dst, hipStream_t s) {
     std::vector<long long> v = {addr(src), B, C, P, nchunks, chunk_c};
     for (int k = 0; k < nchunks; ++k) v.push_back(addr(dst[k]));
@@ -235,6 +245,8 @@ static float* const KEEP = fake<float>(0x2e0000000000ull);
 static float* const KEEP_POS = fake<float>(0x2f0000000000ull);
 static float* const FEAT_INV = fake<float>(0x300000000000ull);
 static void* const STATE = fake<void>(0x310000000000ull);
+static float* const INTRA = fake<float>(0x360000000000ull);
+static int64_t* const HIST = fake<int64_t>(0x370000000000ull);
 
 static long g_calls = 0, g_desc_calls = 0;
 static void begin(const dg_corr_desc* d, const char* entry) {
@@ -280,6 +292,13 @@ static void run_desc(const dg_corr_desc* d, bool refusals) {
         CALL(dg_corr_forward_masked, d, FEATS, FEATS_POS, CODE, CODE_POS, DEPTH, COORDS1, COORDS2, PERMS, 1, 7u, nullptr, nullptr, KEEP_POS, 2.f, OUT, WS, ws, st);
     }
     g_side_on = true;
+    // the intra-feature entry on its own, larger workspace: one accepted call (where the descriptor is served), one without the map
+    begin(d, "dg_corr_workspace_bytes_intra_feats");
+    const size_t wsx = dg_corr_workspace_bytes_intra_feats(d);
+    mix(&wsx, sizeof(wsx));
+    if (g_verbose) printf("    -> %zu bytes\n", wsx);
+    CALL(dg_corr_forward_intra_feats, d, FEATS, FEATS_POS, CODE, CODE_POS, nullptr, COORDS1, COORDS2, PERMS, 1, 5u, nullptr, INTRA, OUT, WS, wsx, st);
+    CALL(dg_corr_forward_intra_feats, d, FEATS, FEATS_POS, CODE, CODE_POS, nullptr, COORDS1, COORDS2, PERMS, 0, 0u, nullptr, nullptr, OUT, WS, wsx, st);
     CALL(dg_corr_backward, d, GRAD, COORDS1, COORDS2, PERMS, GCODE, GCODE_POS, WS, ws, st);
     CALL(dg_corr_backward_total, d, GRAD, COORDS1, COORDS2, PERMS, GCODE, GCODE_POS, WS, ws, st);
     for (int which = -1; which < T; ++which) {
@@ -288,6 +307,7 @@ static void run_desc(const dg_corr_desc* d, bool refusals) {
     }
     CALL(dg_corr_materialize_shared, d, 0, PERMS, nullptr, OUT_LOSS, WS, ws, st);
     CALL(dg_corr_materialize, d, 0, nullptr, nullptr, WS, ws, st);
+    CALL(dg_corr_cd_hist, d, 0, T, PERMS, 64, -1.f, 1.f, HIST, WS, ws, st);
     const int rc_relaunch = CALL(dg_corr_relaunch_main, d, PERMS, WS, ws, st);
     const std::string relaunched = g_last_main;
     begin(d, "dg_corr_intra_folded");
@@ -464,7 +484,7 @@ int main(int argc, char** argv) {
         static const char* const names[] = {"dg_launch_corr", "dg_launch_corr2", "dg_launch_gs", "dg_launch_finish", "dg_launch_transpose", "dg_launch_gather",
             "dg_launch_cd_mask", "dg_launch_cd_mask3", "dg_launch_plane_sample", "dg_launch_colmean", "dg_launch_prep_dense", "dg_launch_rowmean",
             "dg_launch_set_stash", "dg_launch_scatter", "dg_launch_pre_general", "dg_launch_corr_small", "dg_launch_small_finish", "dg_launch_gather_rows",
-            "hipEventRecord", "hipStreamWaitEvent"};
+            "dg_launch_cd_hist", "hipMemsetAsync", "hipEventRecord", "hipStreamWaitEvent"};
         for (const char* n : names)
             for (const dg_corr_desc& d : fd) { g_fail_name = n; visit(&d, false, n); }
         g_fail_name.clear();
@@ -485,10 +505,10 @@ int main(int argc, char** argv) {
         "grad_k_corr2", "grad_k_corr_main", "depth_as_job", "depth_as_gs_blocks", "masked_depth_side_stream", "masked_depth_caller_stream",
         "n_neg_0", "n_neg_1", "n_neg_max", "KF128", "KF384", "KF768", "KD96", "KD128", "stabalize", "no_zero_clamp",
         "feat_inv", "feat_keep", "draw_with_state", "draw_without_state", "refused", "launch_failed", "materialize_depth", "materialize_pairset",
-        "backward_small_merged", "backward_dense", "backward_general",
+        "backward_small_merged", "backward_dense", "backward_general", "xop",
         "entry_dg_corr_workspace_bytes", "entry_dg_corr_forward", "entry_dg_corr_forward_extnorm", "entry_dg_corr_forward_draw",
-        "entry_dg_corr_forward_masked", "entry_dg_corr_backward", "entry_dg_corr_backward_total", "entry_dg_corr_materialize",
-        "entry_dg_corr_materialize_shared", "entry_dg_corr_relaunch_main", "entry_dg_corr_intra_folded", "entry_dg_corr_main_kernel_name"};
+        "entry_dg_corr_forward_masked", "entry_dg_corr_workspace_bytes_intra_feats", "entry_dg_corr_forward_intra_feats", "entry_dg_corr_backward", "entry_dg_corr_backward_total", "entry_dg_corr_materialize",
+        "entry_dg_corr_materialize_shared", "entry_dg_corr_cd_hist", "entry_dg_corr_relaunch_main", "entry_dg_corr_intra_folded", "entry_dg_corr_main_kernel_name"};
     need.push_back(fold_off ? "pointwise_k_corr2_unfolded" : "fold");
     if (!fold_off) need.push_back("materialize_after_fold");
     need.push_back(split_off ? "mask3_caller_stream_with_side" : "mask3_side_stream");

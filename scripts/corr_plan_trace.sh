@@ -43,4 +43,5 @@ for r in default fold_off split_off; do
 done
 grep -h '^note:' "$work/parent-$rev/default.txt" | sed "s/^note:/parent $rev:/"
 grep -h '^note:' "$work/new/default.txt" | sed 's/^note:/working tree:/'
+grep -h '^route xop ' "$work/new/default.txt" | sed 's/^route xop \(.*\)/working tree: the intra-feature operand (xop) was reached by \1 launches/'
 exit $bad

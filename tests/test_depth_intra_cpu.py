@@ -2,6 +2,7 @@
 outputs and against the oracle's plain loss, the new export in header, library and binding, every refusal with its reason, and the
 segmenter's default."""
 import ctypes
+import inspect
 import os
 import re
 from types import SimpleNamespace
@@ -80,7 +81,7 @@ def test_export_is_in_header_library_and_binding():
         assert name in _lib.SIGNATURES and name in _lib.EXPORTS
         assert hasattr(_lib.load(), name)
     assert "src/modules.py:1370-1463" in header and ":1427-1438" in header
-    assert hasattr(ops, "corr_forward_intra_feats") and depthg_amd.DepthContrastiveCorrelationLoss is DepthContrastiveCorrelationLoss
+    assert "intra_feats" in inspect.signature(ops.corr_forward).parameters and depthg_amd.DepthContrastiveCorrelationLoss is DepthContrastiveCorrelationLoss
     assert issubclass(DepthContrastiveCorrelationLoss, ContrastiveCorrelationLoss)
 
 

@@ -547,7 +547,7 @@ def test_deferred_feature_dropout_gives_the_same_bits(B, C, D, hw, pointwise, de
                          shared_coords=False, shifts=(0.1, 0.1, 0.1, 0.0), depth_hw=(0, 0), identity_grid=False, weights=(1, 1, 1, 0))
     cz = torch.randn(B, D, hw, hw, device=dev)
     with pytest.raises(RuntimeError, match="identity grid"):
-        ops.corr_forward_masked(desc, f, fp, cz, cz, None, c1, c2, torch.stack(perms), ops.alloc_workspace(desc, dev), None, ka, kb, scale)
+        ops.corr_forward(desc, f, fp, cz, cz, None, c1, c2, torch.stack(perms), ops.alloc_workspace(desc, dev), keep=(ka, kb, scale))
 
 
 @pytest.mark.gpu

@@ -416,17 +416,17 @@ def test_forward_that_draws_its_negatives(dense, dev):
     # host seed
     torch.manual_seed(77)
     perms_a = ops.super_perms(N, B, dev)
-    out_a = ops.corr_forward(desc, f, fp, c, cp, d, c1, c2, perms_a, ops.alloc_workspace(desc, dev))
+    out_a = ops.corr_forward(desc, f, fp, c, cp, d, c1, c2, perms_a, ops.alloc_workspace(desc, dev))[0]
     torch.manual_seed(77)
-    out_b, perms_b = ops.corr_forward_draw(desc, f, fp, c, cp, d, c1, c2, ops.alloc_workspace(desc, dev))
+    out_b, perms_b, _ = ops.corr_forward(desc, f, fp, c, cp, d, c1, c2, None, ops.alloc_workspace(desc, dev))
     assert torch.equal(perms_a, perms_b) and torch.equal(out_a, out_b)
     # device generator
     st_a = ops.new_perm_state(dev)
     st_b = st_a.clone()
     for _ in range(2):
         perms_a = ops.super_perms(N, B, dev, state=st_a)
-        out_a = ops.corr_forward(desc, f, fp, c, cp, d, c1, c2, perms_a, ops.alloc_workspace(desc, dev))
-        out_b, perms_b = ops.corr_forward_draw(desc, f, fp, c, cp, d, c1, c2, ops.alloc_workspace(desc, dev), state=st_b)
+        out_a = ops.corr_forward(desc, f, fp, c, cp, d, c1, c2, perms_a, ops.alloc_workspace(desc, dev))[0]
+        out_b, perms_b, _ = ops.corr_forward(desc, f, fp, c, cp, d, c1, c2, None, ops.alloc_workspace(desc, dev), draw_state=st_b)
         assert torch.equal(perms_a, perms_b) and torch.equal(out_a, out_b) and torch.equal(st_a, st_b)
     assert int(st_b[1]) == 2 and int(st_b[2]) == 0
     # the module
