@@ -10,7 +10,8 @@
 //   DG_FOLD_INTRA=0   the intra pair-set's streamed-side gradient by k_gs instead of k_corr2's fold (dg_api_corr.hip make_plan)
 //   DG_SPLIT_MASKS=0  the dense grid's exact-mask chain in sequence on the caller's stream, no side stream (dg_api_corr.hip)
 //   DG_C2_WALK=dynamic|static   the walk of k_corr2's persistent workgroups (dg_corr2.hip)
-// Measurement instruments, compiled only into a `make EXTRA=-DDG_DEVTOOLS` build (results unchanged, timing perturbed):
+// Measurement instruments, compiled only into a `make EXTRA=-DDG_DEVTOOLS` build (results unchanged, timing perturbed; the capture
+// every launcher uses for them - variable, device buffer, file - and the kernels' stamp macro: dg_devtools.h):
 //   DG_STAMPS=<file>, DG_BLOCKLOG=<file>   phase stamps / per-block timeline of the fused kernel (with -DDG_STAMP_BUILD for
 //                                           k_corr_main, -DC2_STAMPS [-DC2_STAMP_N=n -DC2_BLOCKSTAMPS_ONLY] or -DC2_BLOCKLOG for k_corr2)
 //   DG_HEAD_STAMPS=<file>, DG_DH_STAMPS=<file>   phase stamps of k_head_fwd / k_head_dh, k_head_dh2

@@ -17,6 +17,7 @@
 // Reference semantics reproduced here: helper() src/modules.py:1231-1254,
 // depth_feature_correlation() :1256-1278 (job kind DG_JOB_DEPTH), norm() :789-790 (backward part).
 #include "dg_device.h"
+#include "dg_devtools.h"
 #include "dg_corr_args.h"
 #include <cstdlib>
 #include <cstdio>
@@ -1056,23 +1057,13 @@ hipError_t dg_launch_gs(const DgGsArgs& a, const uint32_t* dep_maskbits, hipStre
     const int smem = GS_NB * 4 * a.KD * 16 + GS_CW * 32 * GS_TS;
     if (half_out) {          // fp16 output tiles: the widths of k_corr2 only (the identity grid's plan asks for them there)
         if (a.KF != 384 || a.KD != 96) return hipErrorInvalidValue;
-        const void* kern = dep_maskbits ? reinterpret_cast<const void*>(k_gs_xm<24, 6, true>) : reinterpret_cast<const void*>(k_gs<24, 6, true>);
-        hipError_t e = dg_set_max_smem(kern, smem);
-        if (e != hipSuccess) return e;
-        if (dep_maskbits) hipLaunchKernelGGL((k_gs_xm<24, 6, true>), grid, block, smem, stream, a, dep_maskbits);
-        else hipLaunchKernelGGL((k_gs<24, 6, true>), grid, block, smem, stream, a);
-        return hipGetLastError();
+        return dep_maskbits ? dg_launch(k_gs_xm<24, 6, true>, grid, block, smem, stream, a, dep_maskbits)
+                            : dg_launch(k_gs<24, 6, true>, grid, block, smem, stream, a);
     }
 #define DG_GS(NKF_, NKD_)                                                                                               \
-    if (a.KF == NKF_ * 16 && a.KD == NKD_ * 16) {                                                                        \
-        const void* kern = dep_maskbits ? reinterpret_cast<const void*>(k_gs_xm<NKF_, NKD_>)                             \
-                                        : reinterpret_cast<const void*>(k_gs<NKF_, NKD_>);                               \
-        hipError_t e = dg_set_max_smem(kern, smem);                                                                      \
-        if (e != hipSuccess) return e;                                                                                   \
-        if (dep_maskbits) hipLaunchKernelGGL((k_gs_xm<NKF_, NKD_>), grid, block, smem, stream, a, dep_maskbits);         \
-        else hipLaunchKernelGGL((k_gs<NKF_, NKD_>), grid, block, smem, stream, a);                                       \
-        return hipGetLastError();                                                                                        \
-    }
+    if (a.KF == NKF_ * 16 && a.KD == NKD_ * 16)                                                                          \
+        return dep_maskbits ? dg_launch(k_gs_xm<NKF_, NKD_>, grid, block, smem, stream, a, dep_maskbits)                 \
+                            : dg_launch(k_gs<NKF_, NKD_>, grid, block, smem, stream, a);
     DG_GS(8, 6) DG_GS(8, 8) DG_GS(24, 6) DG_GS(24, 8) DG_GS(48, 6) DG_GS(48, 8)
 #undef DG_GS
     return hipErrorInvalidValue;
@@ -1084,45 +1075,18 @@ static hipError_t launch_corr_t(const DgCorrArgs& args, hipStream_t stream) {
     using BL = BlobT<NKF, NKD>;
     const bool big = BL::BYTES > 48 * 1024;
     const int smem = (big ? 2 : 3) * (BL::BYTES + 256) + (big ? 0 : NWAVES * RF * (BL::OFF_P - BL::OFF_C)) + NWAVES * 2 * 4;
-    auto kern = k_corr_main<NKF, NKD, NWAVES, RF, GRAD, MAT, SIMPLE, NKC>;
-    hipError_t e = dg_set_max_smem(reinterpret_cast<const void*>(kern), smem);
-    if (e != hipSuccess) return e;
     const int grid = args.njobs * args.B * args.nrb;
+    // developer aids (stamp build): phase stamps of one block, 100 words per wave kept in that much more LDS; per-block timeline
+    const DgCapture<uint32_t> stamps("DG_STAMPS", NWAVES * 100, smem + NWAVES * 400 <= 160 * 1024);
+    const DgCapture<unsigned long long> blog("DG_BLOCKLOG", 8192 * 8, grid <= 8192);
     DgCorrArgs a2 = args;
-    int smem2 = smem;
-#ifdef DG_DEVTOOLS
-    const char* stamp_file = getenv("DG_STAMPS");                     // developer aid: phase time stamps of one block
-    static uint32_t* stamp_buf = nullptr;
-    if (stamp_file && smem + NWAVES * 400 <= 160 * 1024) {
-        if (!stamp_buf && hipMalloc(&stamp_buf, NWAVES * 400) != hipSuccess) stamp_buf = nullptr;
-        if (stamp_buf) {
-            a2.stamps = stamp_buf; smem2 = smem + NWAVES * 400;
-            (void)dg_set_max_smem(reinterpret_cast<const void*>(kern), smem2);
-        }
-    }
-    const char* blog_file = getenv("DG_BLOCKLOG");                    // developer aid (stamp build): per-block timeline
-    static unsigned long long* blog_buf = nullptr;
-    if (blog_file) {
-        if (!blog_buf && hipMalloc(&blog_buf, 8192 * 64) != hipSuccess) blog_buf = nullptr;
-        if (blog_buf && grid <= 8192) a2.blocklog = blog_buf;
-    }
-#endif
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(NWAVES * 64), smem2, stream, a2);
-#ifdef DG_DEVTOOLS
-    if (a2.blocklog) {
-        static unsigned long long hostb[8192 * 8];
-        if (hipStreamSynchronize(stream) == hipSuccess && hipMemcpy(hostb, blog_buf, (size_t)grid * 64, hipMemcpyDeviceToHost) == hipSuccess) {
-            if (FILE* fp = fopen(blog_file, "wb")) { fwrite(hostb, 8, (size_t)grid * 8, fp); fclose(fp); }
-        }
-    }
-    if (a2.stamps) {
-        uint32_t host[8 * 100];
-        if (hipStreamSynchronize(stream) == hipSuccess && hipMemcpy(host, stamp_buf, NWAVES * 400, hipMemcpyDeviceToHost) == hipSuccess) {
-            if (FILE* fp = fopen(stamp_file, "wb")) { fwrite(host, 4, NWAVES * 100, fp); fclose(fp); }
-        }
-    }
-#endif
-    return hipGetLastError();
+    stamps.attach(a2.stamps);
+    blog.attach(a2.blocklog);
+    const hipError_t e = dg_launch(k_corr_main<NKF, NKD, NWAVES, RF, GRAD, MAT, SIMPLE, NKC>, dim3(grid), dim3(NWAVES * 64),
+                                   smem + (stamps ? NWAVES * 400 : 0), stream, a2);
+    blog.write_raw(stream, (size_t)grid * 8);
+    stamps.write_raw(stream, NWAVES * 100);
+    return e;
 }
 
 // KF in {128, 384, 768}, KD in {96, 128}; nwaves = waves per block (8: two per SIMD, 256 registers each; 4: one per

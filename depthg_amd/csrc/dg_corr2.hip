@@ -24,6 +24,7 @@
 // (the Makefile's rule for dg_corr2.o, scripts/build_variant.sh, the audit in tests/test_host_cpu.py): without it hipcc hoists
 // constants of the item body out of the walk and spills scalar registers into VGPR lanes (correct, slower).
 #include "dg_device.h"
+#include "dg_devtools.h"
 #include "dg_corr_args.h"
 #include <utility>
 #include <cstdio>
@@ -1048,79 +1049,43 @@ bool dg_corr2_supported(const DgCorrArgs& args, int KF, int KD) {
     return true;
 }
 
+// the developer captures this build's kernel fills (the variables: dg_common.h): -DC2_STAMPS the cycle stamps of one block (DG_STAMPS:
+// six per tile for 25 tiles and four block stamps per wave, kept in that much more LDS), -DC2_BLOCKLOG the items' timeline (DG_BLOCKLOG)
+#ifdef C2_STAMPS
+constexpr int C2_STAMP_WORDS = 4 * 25 * 6 + 16;
+#else
+constexpr int C2_STAMP_WORDS = 0;
+#endif
+#ifdef C2_BLOCKLOG
+constexpr int C2_BLOCKLOG_WORDS = 16;       // per item
+#else
+constexpr int C2_BLOCKLOG_WORDS = 0;
+#endif
+
 hipError_t dg_launch_corr2(const DgCorrArgs& args, int KF, int KD, hipStream_t stream) {
     if (!dg_corr2_supported(args, KF, KD)) return hipErrorNotSupported;
     using BL = BlobT<24, 6>;
-    if (args.njobs > 0 && args.jobs[0].maskbits) {
-        // exact clamp masks (DG_EXACT_MASKS on the dense grid): the mask words of k_cd_mask instead of the sign of the fp16 cd;
-        // 8 KiB more LDS for the four-slot word ring of the eight fragments
-        const int smem_x = 4 * BL::BYTES + C2_RED_BYTES + 4 * 2 * 4 * 256;
-        const int gx = dg_corr2_launch_grid(args);
-        const bool dynx = dg_corr2_dynamic_walk(args, gx);
-        bool foldx = false;
-        for (int j = 0; j < args.njobs; ++j) foldx = foldx || args.jobs[j].fold != 0;
-        auto kx = foldx ? (dynx ? k_corr2<24, 6, 5, true, true, true> : k_corr2<24, 6, 5, true, false, true>)
-                        : (dynx ? k_corr2<24, 6, 5, true, true> : k_corr2<24, 6, 5, true, false>);
-        hipError_t ex = dg_set_max_smem(reinterpret_cast<const void*>(kx), smem_x);
-        if (ex != hipSuccess) return ex;
-#if defined(DG_DEVTOOLS) && defined(C2_STAMPS)
-        if (const char* stamp_file = getenv("DG_STAMPS")) {
-            static uint32_t* stamp_buf = nullptr;
-            if (!stamp_buf && hipMalloc(&stamp_buf, (4 * 25 * 6 + 16) * 4) != hipSuccess) return hipErrorOutOfMemory;
-            DgCorrArgs a2 = args;
-            a2.stamps = stamp_buf;
-            (void)dg_set_max_smem(reinterpret_cast<const void*>(kx), smem_x + (4 * 25 * 6 + 16) * 4);
-            hipLaunchKernelGGL(kx, dim3(gx), dim3(256), smem_x + (4 * 25 * 6 + 16) * 4, stream, a2);
-            uint32_t host[4 * 25 * 6 + 16];
-            if (hipStreamSynchronize(stream) == hipSuccess && hipMemcpy(host, stamp_buf, sizeof(host), hipMemcpyDeviceToHost) == hipSuccess)
-                if (FILE* fp = fopen(stamp_file, "wb")) { fwrite(host, 4, 4 * 25 * 6 + 16, fp); fclose(fp); }
-            return hipGetLastError();
-        }
-#endif
-        hipLaunchKernelGGL(kx, dim3(gx), dim3(256), smem_x, stream, args);
-        return hipGetLastError();
-    }
-    const int smem = 4 * BL::BYTES + C2_RED_BYTES;
-    const int g0 = dg_corr2_launch_grid(args);
-    const bool dyn0 = dg_corr2_dynamic_walk(args, g0);
+    // exact clamp masks (DG_EXACT_MASKS on the dense grid): the mask words of k_cd_mask instead of the sign of the fp16 cd;
+    // 8 KiB more LDS for the four-slot word ring of the eight fragments
+    const bool exact = args.njobs > 0 && args.jobs[0].maskbits;
+    const int smem = 4 * BL::BYTES + C2_RED_BYTES + (exact ? 4 * 2 * 4 * 256 : 0);
+    const int grid = dg_corr2_launch_grid(args), items = dg_corr2_grid(args);
+    const bool dyn = dg_corr2_dynamic_walk(args, grid);
     bool fold = false;
     for (int j = 0; j < args.njobs; ++j) fold = fold || args.jobs[j].fold != 0;
-    auto kern = fold ? (dyn0 ? k_corr2<24, 6, 5, false, true, true> : k_corr2<24, 6, 5, false, false, true>)
-                     : (dyn0 ? k_corr2<24, 6, 5, false, true> : k_corr2<24, 6, 5, false, false>);
-    hipError_t e = dg_set_max_smem(reinterpret_cast<const void*>(kern), smem);
-    if (e != hipSuccess) return e;
-#if defined(DG_DEVTOOLS) && defined(C2_STAMPS)
-    if (const char* stamp_file = getenv("DG_STAMPS")) {
-        static uint32_t* stamp_buf = nullptr;
-        if (!stamp_buf && hipMalloc(&stamp_buf, (4 * 25 * 6 + 16) * 4) != hipSuccess) return hipErrorOutOfMemory;
-        DgCorrArgs a2 = args;
-        a2.stamps = stamp_buf;
-        (void)dg_set_max_smem(reinterpret_cast<const void*>(kern), smem + (4 * 25 * 6 + 16) * 4);
-        hipLaunchKernelGGL(kern, dim3(dg_corr2_launch_grid(args)), dim3(256), smem + (4 * 25 * 6 + 16) * 4, stream, a2);
-        uint32_t host[4 * 25 * 6 + 16];
-        if (hipStreamSynchronize(stream) == hipSuccess && hipMemcpy(host, stamp_buf, sizeof(host), hipMemcpyDeviceToHost) == hipSuccess)
-            if (FILE* fp = fopen(stamp_file, "wb")) { fwrite(host, 4, 4 * 25 * 6 + 16, fp); fclose(fp); }
-        return hipGetLastError();
-    }
-#endif
-#if defined(DG_DEVTOOLS) && defined(C2_BLOCKLOG)
-    if (const char* blog_file = getenv("DG_BLOCKLOG")) {
-        static unsigned long long* blog_buf = nullptr;
-        const int grid = dg_corr2_grid(args);
-        if (!blog_buf && hipMalloc(&blog_buf, 8192 * 128) != hipSuccess) return hipErrorOutOfMemory;
-        if (grid <= 8192) {
-            DgCorrArgs a2 = args;
-            a2.blocklog = blog_buf;
-            (void)hipMemsetAsync(blog_buf, 0, (size_t)grid * 128, stream);
-            hipLaunchKernelGGL(kern, dim3(dg_corr2_launch_grid(args)), dim3(256), smem, stream, a2);
-            static unsigned long long hostb[8192 * 16];
-            if (hipStreamSynchronize(stream) == hipSuccess && hipMemcpy(hostb, blog_buf, (size_t)grid * 128, hipMemcpyDeviceToHost) == hipSuccess)
-                if (FILE* fp = fopen(blog_file, "wb")) { fwrite(hostb, 8, (size_t)grid * 16, fp); fclose(fp); }
-            return hipGetLastError();
-        }
-    }
-#endif
-    hipLaunchKernelGGL(kern, dim3(dg_corr2_launch_grid(args)), dim3(256), smem, stream, args);
-    return hipGetLastError();
+    // XM, DYN, FOLD of the kernel: the three decisions above
+    const auto kern = exact ? (fold ? (dyn ? k_corr2<24, 6, 5, true, true, true> : k_corr2<24, 6, 5, true, false, true>)
+                                    : (dyn ? k_corr2<24, 6, 5, true, true> : k_corr2<24, 6, 5, true, false>))
+                            : (fold ? (dyn ? k_corr2<24, 6, 5, false, true, true> : k_corr2<24, 6, 5, false, false, true>)
+                                    : (dyn ? k_corr2<24, 6, 5, false, true> : k_corr2<24, 6, 5, false, false>));
+    const DgCapture<uint32_t> stamps("DG_STAMPS", C2_STAMP_WORDS, C2_STAMP_WORDS > 0 && smem + C2_STAMP_WORDS * 4 <= 160 * 1024);
+    const DgCapture<unsigned long long> blog("DG_BLOCKLOG", 8192 * C2_BLOCKLOG_WORDS, C2_BLOCKLOG_WORDS > 0 && items <= 8192);
+    DgCorrArgs a2 = args;
+    stamps.attach(a2.stamps);
+    blog.attach(a2.blocklog);
+    blog.zero(stream, (size_t)items * C2_BLOCKLOG_WORDS);
+    const hipError_t e = dg_launch(kern, dim3(grid), dim3(256), smem + (stamps ? C2_STAMP_WORDS * 4 : 0), stream, a2);
+    stamps.write_raw(stream, C2_STAMP_WORDS);
+    blog.write_raw(stream, (size_t)items * C2_BLOCKLOG_WORDS);
+    return e;
 }
-

@@ -289,14 +289,9 @@ static size_t crfl_pair_lds(int DV, int R) {
 template <int DV, int R>
 static hipError_t crfl_launch_pair(const DgCrflArgs& A, int* blocks, hipStream_t s) {
     const int lds = (int)crfl_pair_lds(DV, R);
-    if (lds > 64 * 1024) {
-        hipError_t e = dg_set_max_smem(reinterpret_cast<const void*>(k_crfl_pair<DV, R>), lds);
-        if (e != hipSuccess) return e;
-    }
     const dim3 grid((A.n + 64 * R - 1) / (64 * R), A.B);
     *blocks = (int)(grid.x * grid.y);
-    hipLaunchKernelGGL((k_crfl_pair<DV, R>), grid, dim3(CRFL_PAIR_THREADS), lds, s, A);
-    return hipGetLastError();
+    return dg_launch_if(lds > 64 * 1024, k_crfl_pair<DV, R>, grid, dim3(CRFL_PAIR_THREADS), lds, s, A);
 }
 
 hipError_t dg_launch_crfl_forward(const DgCrflArgs& A, hipStream_t s) {

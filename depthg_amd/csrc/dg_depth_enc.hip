@@ -528,10 +528,7 @@ static hipError_t de_pack(const DgDepthEncArgs& A, bool with_t, hipStream_t s) {
 hipError_t dg_launch_depthenc_forward(const DgDepthEncArgs& A, hipStream_t s) {
     hipError_t e = de_pack(A, false, s);
     if (e != hipSuccess) return e;
-    e = dg_set_max_smem(reinterpret_cast<const void*>(k_de_forward), de_fwd_lds());
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_de_forward, dim3(A.tiles), dim3(DE_THREADS), de_fwd_lds(), s, A);
-    return hipGetLastError();
+    return dg_launch(k_de_forward, dim3(A.tiles), dim3(DE_THREADS), de_fwd_lds(), s, A);
 }
 
 static hipError_t de_combine(const DeCombine& K, hipStream_t s) {
@@ -543,10 +540,7 @@ hipError_t dg_launch_depthenc_backward(const DgDepthEncArgs& A, hipStream_t s) {
     hipError_t e = de_pack(A, true, s);
     if (e != hipSuccess) return e;
     const int lds = de_act_lds(A.C);
-    e = dg_set_max_smem(reinterpret_cast<const void*>(k_de_bwd_act), lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_de_bwd_act, dim3(A.blocks_act), dim3(DE_THREADS), lds, s, A);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
+    if ((e = dg_launch(k_de_bwd_act, dim3(A.blocks_act), dim3(DE_THREADS), lds, s, A)) != hipSuccess) return e;
     hipLaunchKernelGGL(k_de_bwd_w2, dim3(4, A.splits_w2), dim3(DE_THREADS), 0, s, A);
     if ((e = hipGetLastError()) != hipSuccess) return e;
     hipLaunchKernelGGL(k_de_bwd_w3, dim3(A.C / 64, A.splits_w3), dim3(DE_THREADS), 0, s, A);

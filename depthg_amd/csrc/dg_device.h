@@ -1,5 +1,5 @@
 // Device primitives every kernel file may use: vector types, LDS-DMA, the wave reductions, Philox, the profiling span - and
-// dg_set_max_smem for their launchers.  Nothing here belongs to one subsystem.
+// dg_set_max_smem / dg_launch for their launchers.  Nothing here belongs to one subsystem.
 #pragma once
 #include "dg_common.h"
 #include <map>
@@ -167,4 +167,21 @@ inline hipError_t dg_set_max_smem(const void* kern, int bytes) {
     hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
     if (e == hipSuccess) done[key] = bytes;
     return e;
+}
+
+// One launch: grant the kernel its dynamic LDS (`grant` false: the site's own condition says the default limit serves), launch,
+// and hand back the launch's error.  A launcher that grants two kernels before it launches either, or asks for the error once
+// after two launches, is not this sequence and spells its own.
+template <class K, class... A>
+inline hipError_t dg_launch_if(bool grant, K kern, dim3 grid, dim3 block, int smem, hipStream_t s, const A&... a) {
+    if (grant) {
+        const hipError_t e = dg_set_max_smem(reinterpret_cast<const void*>(kern), smem);
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(kern, grid, block, smem, s, a...);
+    return hipGetLastError();
+}
+template <class K, class... A>
+inline hipError_t dg_launch(K kern, dim3 grid, dim3 block, int smem, hipStream_t s, const A&... a) {
+    return dg_launch_if(true, kern, grid, block, smem, s, a...);
 }

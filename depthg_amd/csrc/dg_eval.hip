@@ -162,10 +162,7 @@ hipError_t dg_launch_seg_project(const DgSegArgs& a, hipStream_t s) {
     const int hw = a.h * a.w, Kp = dg_seg_kp(a.n, a.m);
     const int psmem = a.D * SP_KC * 4;
     const auto kp = a.code_flip ? k_seg_project<true> : k_seg_project<false>;
-    hipError_t e = dg_set_max_smem(reinterpret_cast<const void*>(kp), psmem);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kp, dim3((hw + SP_THREADS - 1) / SP_THREADS, (Kp + SP_KC - 1) / SP_KC, a.B), dim3(SP_THREADS), psmem, s, a);
-    return hipGetLastError();
+    return dg_launch(kp, dim3((hw + SP_THREADS - 1) / SP_THREADS, (Kp + SP_KC - 1) / SP_KC, a.B), dim3(SP_THREADS), psmem, s, a);
 }
 
 hipError_t dg_launch_segment_predict(const DgSegArgs& a, hipStream_t s) {
@@ -185,8 +182,5 @@ hipError_t dg_launch_segment_predict(const DgSegArgs& a, hipStream_t s) {
     const bool ldshist = (size_t)2 * a.n * a.n * 4 <= SS_HIST_BYTES;
     const int smem = (ldshist ? ((2 * a.n * a.n * 4 + 15) / 16 * 16) : 0) + R * row_bytes;
     const auto ks = ldshist ? k_seg_score<true> : k_seg_score<false>;
-    e = dg_set_max_smem(reinterpret_cast<const void*>(ks), smem);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(ks, dim3(blocks), dim3(SS_THREADS), smem, s, a, R, (int)nchunks);
-    return hipGetLastError();
+    return dg_launch(ks, dim3(blocks), dim3(SS_THREADS), smem, s, a, R, (int)nchunks);
 }

@@ -10,6 +10,7 @@
 // (the three weight gradients: products over all positions of the batch, split over blocks, partial sums reduced in a fixed order),
 // k_head_rowsum (bias gradients).  No floating-point atomics: results are bit-reproducible.
 #include "dg_device.h"
+#include "dg_devtools.h"
 #include "dg_head_args.h"
 #include <type_traits>
 #include <cstdio>
@@ -122,11 +123,7 @@ __global__ __launch_bounds__(64 * NW) void k_head_fwd(const DgHeadFwdArgs a) {
     const int C = a.C, D = a.D, P = a.P;
     const bool nonlinear = a.w2a != nullptr;
     const float s1 = a.keep1 ? a.scale : 1.f, s2 = a.keep2 ? a.scale : 1.f, s3 = a.keep3 ? a.scale : 1.f;
-#ifdef DG_DEVTOOLS
-#define HSTAMP(k) if (a.stamps && blockIdx.x == 3 && blockIdx.y == 5 && tid == 0) a.stamps[k] = __builtin_amdgcn_s_memtime();
-#else
-#define HSTAMP(k)
-#endif
+#define HSTAMP(k) DG_PHASE_STAMP(blockIdx.x == 3 && blockIdx.y == 5 && tid == 0, k)
     HSTAMP(0)
 
     // ---- stage the feature tile: fp32 (C, NT) -> bf16 LDS image, drop3(f) written on the way.  Eight rows' loads in flight per
@@ -402,24 +399,14 @@ template <int MB, int NT, int NW = 4>
 static hipError_t launch_head_fwd(const DgHeadFwdArgs& a, hipStream_t s) {
     constexpr int CP = 16 * MB * NW;
     const int smem = CP * head_frow(NT) + 2 * CP * 2;
-    auto kern = k_head_fwd<MB, NT, NW>;
-    hipError_t e = dg_set_max_smem(reinterpret_cast<const void*>(kern), smem);
-    if (e != hipSuccess) return e;
-#ifdef DG_DEVTOOLS
-    if (const char* f = getenv("DG_HEAD_STAMPS")) {
-        static unsigned long long* buf = nullptr;
-        if (!buf && hipMalloc(&buf, 64) != hipSuccess) return hipErrorOutOfMemory;
-        DgHeadFwdArgs a2 = a;
-        a2.stamps = buf;
-        hipLaunchKernelGGL(kern, dim3((a.P + NT - 1) / NT, a.B), dim3(64 * NW), smem, s, a2);
-        unsigned long long h[8];
-        if (hipStreamSynchronize(s) == hipSuccess && hipMemcpy(h, buf, 64, hipMemcpyDeviceToHost) == hipSuccess)
-            if (FILE* fp = fopen(f, "w")) { for (int i = 1; i < 8; ++i) fprintf(fp, "phase %d: %llu cycles\n", i, h[i] - h[i - 1]); fclose(fp); }
-        return hipGetLastError();
-    }
-#endif
-    hipLaunchKernelGGL(kern, dim3((a.P + NT - 1) / NT, a.B), dim3(64 * NW), smem, s, a);
-    return hipGetLastError();
+    const DgCapture<unsigned long long> cap("DG_HEAD_STAMPS", 8);
+    DgHeadFwdArgs a2 = a;
+    cap.attach(a2.stamps);
+    const hipError_t e = dg_launch(k_head_fwd<MB, NT, NW>, dim3((a.P + NT - 1) / NT, a.B), dim3(64 * NW), smem, s, a2);
+    cap.write(s, 8, [](FILE* fp, const unsigned long long* h) {
+        for (int i = 1; i < 8; ++i) fprintf(fp, "phase %d: %llu cycles\n", i, h[i] - h[i - 1]);
+    });
+    return e;
 }
 
 hipError_t dg_launch_head_fwd(const DgHeadFwdArgs& a, hipStream_t s) {
@@ -456,12 +443,8 @@ __global__ __launch_bounds__(256) void k_head_dh(const DgHeadDhArgs a) {
     const int C = a.C, D = a.D, P = a.P, DP = (D + 31) / 32 * 32;
     const int blk = blockIdx.y * gridDim.x + blockIdx.x;
     const bool staged = a.staged != 0;                                 // (P a multiple of 8: every 16-byte piece of a row is whole)
-#ifdef DG_DEVTOOLS
     // two blocks' phase stamps: an early one and one of the second round (blocks 3 and 700 of the 13 x 64 grid)
-#define DSTAMP(k) if (a.stamps && tid == 0 && (blk == 3 || blk == 700)) a.stamps[(blk == 3 ? 0 : 8) + k] = __builtin_amdgcn_s_memtime();
-#else
-#define DSTAMP(k)
-#endif
+#define DSTAMP(k) DG_PHASE_STAMP(tid == 0 && (blk == 3 || blk == 700), (blk == 3 ? 0 : 8) + k)
     DSTAMP(0)
     // hidden rows of the tile: all of a thread's 16-byte pieces requested up front, next to the d code pieces below (one round trip)
     // Round 6: by LDS-DMA (no registers: 48 of them held the pieces until the d code tile was converted), rows of 128 bytes, the
@@ -699,10 +682,8 @@ __global__ __launch_bounds__(512) void k_head_dh2(const DgHeadDhArgs a) {
     int t = blockIdx.x, buf = 0;
 #ifdef DG_DEVTOOLS
     int tix = 0;
-#define D2STAMP(k) if (a.stamps && tid == 0 && blockIdx.x == 3 && tix < 2) a.stamps[8 * tix + k] = __builtin_amdgcn_s_memtime();
-#else
-#define D2STAMP(k)
 #endif
+#define D2STAMP(k) DG_PHASE_STAMP(tid == 0 && blockIdx.x == 3 && tix < 2, 8 * tix + k)
     if (t < ntiles) fetch(t, 0);
     for (; t < ntiles; t += gridDim.x, buf ^= 1) {
         const int b = t / tiles_img, p0 = (t - b * tiles_img) * NT;
@@ -841,63 +822,48 @@ static int dg_head_dh_fused_blocks(int B, int C, int D, int P) {
     const int ntiles = B * ((P + 63) / 64);
     return ntiles < 256 ? ntiles : 256;
 }
-hipError_t dg_launch_head_dh(const DgHeadDhArgs& a, const DgHeadPlan& plan, hipStream_t s) {
-    dim3 grid((a.P + 63) / 64, a.B);
+// the capture both d hidden kernels share: two rows of eight stamps, five phases each
+static void head_dh_stamp_lines(FILE* fp, const unsigned long long* hs, bool fused) {
+    for (int q = 0; q < 2; ++q)
+        for (int i = 1; i < 6; ++i) {
+            const unsigned long long cyc = hs[8 * q + i] - hs[8 * q + i - 1];
+            if (fused) fprintf(fp, "k_head_dh2 block 3 tile %d phase %d: %llu cycles\n", q, i, cyc);
+            else fprintf(fp, "block %d phase %d: %llu cycles (starts %llu after block 3)\n", q ? 700 : 3, i, cyc, hs[8 * q + i - 1] - hs[0]);
+        }
+    if (fused) fprintf(fp, "tile 0 start -> tile 1 start: %llu cycles\n", hs[8] - hs[0]);
+}
+
+template <int MB, int NKS>
+static hipError_t launch_head_dh(const DgHeadDhArgs& a, hipStream_t s) {
+    const DgCapture<unsigned long long> cap("DG_DH_STAMPS", 16);
     DgHeadDhArgs a2 = a;
+    cap.attach(a2.stamps);
+    a2.staged = ((a.P & 7) == 0 && a.C <= 384) ? 1 : 0;     // (ViT-B width: 130 KB of LDS would leave one block per CU)
+    const int smem = 128 * (64 * 2 + 32) + (a2.staged ? 16 * MB * 4 * (64 * 2) : 0);
+    const hipError_t e = dg_launch(k_head_dh<MB, NKS>, dim3((a.P + 63) / 64, a.B), dim3(256), smem, s, a2);
+    cap.write(s, 16, [](FILE* fp, const unsigned long long* hs) { head_dh_stamp_lines(fp, hs, false); });
+    return e;
+}
+
+hipError_t dg_launch_head_dh(const DgHeadDhArgs& a, const DgHeadPlan& plan, hipStream_t s) {
     // (d W2b is formed by k_head_dh2 and always there; the step-major d hidden is its alone too)
     if ((plan.dh_route == DG_HEAD_DH_FUSED) != (a.part_w2b != nullptr) || (a.step_major && plan.dh_route != DG_HEAD_DH_FUSED))
         return hipErrorInvalidValue;
     if (plan.dh_route == DG_HEAD_DH_FUSED) {
-        const int nblk = plan.dh_blocks;
-        const int smem = 2 * DH2_HT + 2 * DH2_DT;
+        const DgCapture<unsigned long long> cap("DG_DH_STAMPS", 16);
+        DgHeadDhArgs a2 = a;
+        cap.attach(a2.stamps);
         auto kern = a.D <= 80 ? k_head_dh2<5> : k_head_dh2<6>;
-        hipError_t e = dg_set_max_smem(reinterpret_cast<const void*>(kern), smem);
-        if (e != hipSuccess) return e;
-#ifdef DG_DEVTOOLS
-        if (const char* sf = getenv("DG_DH_STAMPS")) {
-            static unsigned long long* sb2 = nullptr;
-            if (!sb2 && hipMalloc(&sb2, 128) != hipSuccess) return hipErrorOutOfMemory;
-            a2.stamps = sb2;
-            hipLaunchKernelGGL(kern, dim3(nblk), dim3(512), smem, s, a2);
-            unsigned long long hs[16];
-            if (hipStreamSynchronize(s) == hipSuccess && hipMemcpy(hs, sb2, 128, hipMemcpyDeviceToHost) == hipSuccess)
-                if (FILE* fp = fopen(sf, "w")) { for (int q = 0; q < 2; ++q) for (int i = 1; i < 6; ++i)
-                    fprintf(fp, "k_head_dh2 block 3 tile %d phase %d: %llu cycles\n", q, i, hs[8 * q + i] - hs[8 * q + i - 1]);
-                    fprintf(fp, "tile 0 start -> tile 1 start: %llu cycles\n", hs[8] - hs[0]); fclose(fp); }
-            return hipGetLastError();
-        }
-#endif
-        hipLaunchKernelGGL(kern, dim3(nblk), dim3(512), smem, s, a2);
-        return hipGetLastError();
+        const hipError_t e = dg_launch(kern, dim3(plan.dh_blocks), dim3(512), 2 * DH2_HT + 2 * DH2_DT, s, a2);
+        cap.write(s, 16, [](FILE* fp, const unsigned long long* hs) { head_dh_stamp_lines(fp, hs, true); });
+        return e;
     }
-#ifdef DG_DEVTOOLS
-    static unsigned long long* sbuf = nullptr;
-    const char* sfile = getenv("DG_DH_STAMPS");
-    if (sfile) { if (!sbuf && hipMalloc(&sbuf, 128) != hipSuccess) return hipErrorOutOfMemory; a2.stamps = sbuf; }
-#endif
-    a2.staged = ((a.P & 7) == 0 && a.C <= 384) ? 1 : 0;     // (ViT-B width: 130 KB of LDS would leave one block per CU)
-#ifdef DG_DEVTOOLS
-#define DH_STAMP_DUMP if (sfile) { unsigned long long hs[16];                                                    \
-        if (hipStreamSynchronize(s) == hipSuccess && hipMemcpy(hs, sbuf, 128, hipMemcpyDeviceToHost) == hipSuccess)     \
-            if (FILE* fp = fopen(sfile, "w")) { for (int q = 0; q < 2; ++q) for (int i = 1; i < 6; ++i)          \
-                fprintf(fp, "block %d phase %d: %llu cycles (starts %llu after block 3)\n", q ? 700 : 3, i, hs[8 * q + i] - hs[8 * q + i - 1], hs[8 * q + i - 1] - hs[0]); fclose(fp); } }
-#else
-#define DH_STAMP_DUMP
-#endif
-#define DG_DH(MB_, NKS_) {                                                                                       \
-        const int smem = 128 * (64 * 2 + 32) + (a2.staged ? 16 * MB_ * 4 * (64 * 2) : 0);                        \
-        hipError_t e = dg_set_max_smem(reinterpret_cast<const void*>(k_head_dh<MB_, NKS_>), smem);               \
-        if (e != hipSuccess) return e;                                                                           \
-        hipLaunchKernelGGL((k_head_dh<MB_, NKS_>), grid, dim3(256), smem, s, a2);                                \
-        DH_STAMP_DUMP                                                                                            \
-        return hipGetLastError(); }
     const bool pre3 = a.D <= 96;        // (all weight fragments in registers: 72 of them at C = 384; a fourth k-step would leave one wave per SIMD)
-    if (a.C <= 64) { if (pre3) DG_DH(1, 3) else DG_DH(1, 4) }
-    if (a.C <= 128) { if (pre3) DG_DH(2, 3) else DG_DH(2, 4) }
-    if (a.C <= 192) { if (pre3) DG_DH(3, 3) else DG_DH(3, 4) }
-    if (a.C <= 384) { if (pre3) DG_DH(6, 3) else DG_DH(6, 0) }
-    if (a.C <= 768) DG_DH(12, 0)
-#undef DG_DH
+    if (a.C <= 64) return pre3 ? launch_head_dh<1, 3>(a, s) : launch_head_dh<1, 4>(a, s);
+    if (a.C <= 128) return pre3 ? launch_head_dh<2, 3>(a, s) : launch_head_dh<2, 4>(a, s);
+    if (a.C <= 192) return pre3 ? launch_head_dh<3, 3>(a, s) : launch_head_dh<3, 4>(a, s);
+    if (a.C <= 384) return pre3 ? launch_head_dh<6, 3>(a, s) : launch_head_dh<6, 0>(a, s);
+    if (a.C <= 768) return launch_head_dh<12, 0>(a, s);
     return hipErrorInvalidValue;
 }
 
@@ -1372,10 +1338,7 @@ hipError_t dg_launch_head_wgrad(const DgHeadWgradArgs& a, DgHeadWgradForm form, 
         if (form != DG_HEAD_WGRAD_ONE_PASS) return launch_wgrad<__bf16, float, float>(a, form, s);
         if (!a.A2h) return hipErrorInvalidValue;
         const int smem = W3_NSTAGE * W3_STAGE;
-        hipError_t e = dg_set_max_smem(reinterpret_cast<const void*>(k_head_wgrad3), smem);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(k_head_wgrad3, dim3(((a.N + 127) / 128) * a.splits), dim3(512), smem, s, a);
-        return hipGetLastError();
+        return dg_launch(k_head_wgrad3, dim3(((a.N + 127) / 128) * a.splits), dim3(512), smem, s, a);
     }
     if (!a_bf16 && !b_bf16) return launch_wgrad<float, float>(a, form, s);
     if (!a_bf16 && b_bf16) return launch_wgrad<float, __bf16>(a, form, s);
@@ -1626,10 +1589,7 @@ template <int MB, bool ADD>
 static hipError_t launch_head_dx(const DgHeadDxArgs& a, hipStream_t s) {
     const DgHeadDxLayout L(a.C, a.D, a.dh != nullptr);
     const int smem = 32 * (L.KS1 + L.KS2) * (64 * 2 + 32);
-    hipError_t e = dg_set_max_smem(reinterpret_cast<const void*>(k_head_dx<MB, ADD>), smem);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((k_head_dx<MB, ADD>), dim3((a.P + 63) / 64, a.nb), dim3(256), smem, s, a);
-    return hipGetLastError();
+    return dg_launch(k_head_dx<MB, ADD>, dim3((a.P + 63) / 64, a.nb), dim3(256), smem, s, a);
 }
 template <bool ADD>
 static hipError_t launch_head_dx_by_width(const DgHeadDxArgs& a, hipStream_t s) {

@@ -412,12 +412,7 @@ hipError_t dg_launch_lhp_map(int mode, const float* code, const float* attn, con
     LhpMapArgs a{code, attn, points, divide, out, map, D, P, heads, w};
     const dim3 grid((P + 3) / 4, B), block(LHP_THREADS);
     const size_t smem = mode == LHP_ATTN ? 0 : (size_t)(mode == LHP_ORIG_DEPTH ? 7 : 4) * P * sizeof(float);
-    auto launch = [&](auto kern) -> hipError_t {
-        hipError_t e = dg_set_max_smem(reinterpret_cast<const void*>(kern), (int)smem);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(kern, grid, block, smem, s, a);
-        return hipGetLastError();
-    };
+    auto launch = [&](auto kern) { return dg_launch(kern, grid, block, (int)smem, s, a); };
     if (mode == LHP_ATTN) {
         const hipError_t e = P <= 1024 ? launch(k_lhp_map<16, LHP_ATTN>) : P <= 4096 ? launch(k_lhp_map<64, LHP_ATTN>) : hipErrorInvalidValue;
         return e != hipSuccess ? e : lhp_attn_apply(true, code, map, B, D, P, out, s);
@@ -437,10 +432,7 @@ static hipError_t lhp_attn_apply(bool forward, const float* src, const float* ma
     auto launch = [&](auto kern, int nd) -> hipError_t {
         const int dp = 4 * nd, work = 64 * (dp + 4) + 64 * 65, fin = 4 * dp * 64;
         const size_t smem = (size_t)(work > fin ? work : fin) * sizeof(float);
-        hipError_t e = dg_set_max_smem(reinterpret_cast<const void*>(kern), (int)smem);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(kern, grid, block, smem, s, src, map, D, P, dst);
-        return hipGetLastError();
+        return dg_launch(kern, grid, block, (int)smem, s, src, map, D, P, dst);
     };
     if (forward) {
         if (D <= 32) return launch(k_lhp_attn_apply<8, true>, 8);
@@ -476,12 +468,7 @@ hipError_t dg_launch_lhp_propagate(bool backward, const float* src, const float*
                                    float* dst, hipStream_t s) {
     const dim3 grid((P + 3) / 4, B), block(LHP_THREADS);
     const size_t smem = (size_t)3 * P * sizeof(float);
-    auto launch = [&](auto kern) -> hipError_t {
-        hipError_t e = dg_set_max_smem(reinterpret_cast<const void*>(kern), (int)smem);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(kern, grid, block, smem, s, src, points, stats, D, P, dst);
-        return hipGetLastError();
-    };
+    auto launch = [&](auto kern) { return dg_launch(kern, grid, block, (int)smem, s, src, points, stats, D, P, dst); };
     if (P <= 1024) return backward ? launch(k_lhp_propagate<16, true>) : launch(k_lhp_propagate<16, false>);
     if (P <= 4096) return backward ? launch(k_lhp_propagate<64, true>) : launch(k_lhp_propagate<64, false>);
     return hipErrorInvalidValue;

@@ -236,10 +236,7 @@ hipError_t dg_launch_linear_pack(const float* w, int K, int Nout, void* packed, 
 template <int MT, int NT>
 static hipError_t lin_launch(const LinArgs& a, hipStream_t s) {
     const int lds = a.bm * (2 * a.K + 16);
-    hipError_t e = dg_set_max_smem(reinterpret_cast<const void*>(&k_lin_fwd<MT, NT>), lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((k_lin_fwd<MT, NT>), dim3((a.M + a.bm - 1) / a.bm), dim3(LIN_THREADS), lds, s, a);
-    return hipGetLastError();
+    return dg_launch(k_lin_fwd<MT, NT>, dim3((a.M + a.bm - 1) / a.bm), dim3(LIN_THREADS), lds, s, a);
 }
 
 hipError_t dg_launch_linear(const void* x, const float* gamma, const float* beta, float eps, const void* packed, const float* bias,

@@ -383,10 +383,7 @@ hipError_t dg_launch_pre_general(const DgPreArgs& a, hipStream_t s) {
         const size_t need = dg_taps_record_bytes(a.h * a.w, a.P) + (size_t)a.h * a.w * 4 + 16;
         smem = need > smem ? need : smem;
     }
-    hipError_t e = dg_set_max_smem(reinterpret_cast<const void*>(k_pre_general), (int)smem);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_pre_general, dim3(nblk), dim3(256), smem, s, a);
-    return hipGetLastError();
+    return dg_launch(k_pre_general, dim3(nblk), dim3(256), (int)smem, s, a);
 }
 
 // Stage 2: adjoint of sample() as a GATHER (no floating-point atomics).  One block = one destination image and
@@ -801,12 +798,7 @@ hipError_t dg_launch_scatter(const DgScatterArgs& a, hipStream_t s) {
         if (stage_bytes(CGv) > 150 * 1024 && CGv > 8) CGv = 8;      // 56 x 56 maps: 8 channels per block keep the [channel][pixel] stage in LDS
         const size_t dsm = stage_bytes(CGv);
         if (a.dense && a.S == a.h && a.S == a.w && dsm <= 150 * 1024 && (size_t)nrouted * a.B <= DENSE_MAXROUTE) {
-            auto launch = [&](auto kern, int threads) -> hipError_t {
-                hipError_t e = dg_set_max_smem(reinterpret_cast<const void*>(kern), (int)dsm);
-                if (e != hipSuccess) return e;
-                hipLaunchKernelGGL(kern, dim3(a.DP / CGv, a.B, 2), dim3(threads), dsm, s, a);
-                return hipGetLastError();
-            };
+            auto launch = [&](auto kern, int threads) { return dg_launch(kern, dim3(a.DP / CGv, a.B, 2), dim3(threads), (int)dsm, s, a); };
             if (CGv == 32) return launch(k_scatter_dense<32, 1024>, 1024);
             if (CGv == 16) return launch(k_scatter_dense<16, 512>, 512);
             return launch(k_scatter_dense<8, 512>, 512);
@@ -839,36 +831,18 @@ hipError_t dg_launch_scatter(const DgScatterArgs& a, hipStream_t s) {
         if (HW <= SCAT_THREADS && rb >= 2) {
             const int sm = (int)(rb * per_src);
             const dim3 sgrid(a.DP / CGv, a.B, 2);
-            if (quarter) {
-                e = dg_set_max_smem(reinterpret_cast<const void*>(k_scatter_small<8>), sm);
-                if (e != hipSuccess) return e;
-                hipLaunchKernelGGL(k_scatter_small<8>, sgrid, dim3(SCAT_THREADS), sm, s, a, rb);
-            } else if (half) {
-                e = dg_set_max_smem(reinterpret_cast<const void*>(k_scatter_small<16>), sm);
-                if (e != hipSuccess) return e;
-                hipLaunchKernelGGL(k_scatter_small<16>, sgrid, dim3(SCAT_THREADS), sm, s, a, rb);
-            } else {
-                e = dg_set_max_smem(reinterpret_cast<const void*>(k_scatter_small<32>), sm);
-                if (e != hipSuccess) return e;
-                hipLaunchKernelGGL(k_scatter_small<32>, sgrid, dim3(SCAT_THREADS), sm, s, a, rb);
-            }
-            return hipGetLastError();
+            if (quarter) return dg_launch(k_scatter_small<8>, sgrid, dim3(SCAT_THREADS), sm, s, a, rb);
+            if (half) return dg_launch(k_scatter_small<16>, sgrid, dim3(SCAT_THREADS), sm, s, a, rb);
+            return dg_launch(k_scatter_small<32>, sgrid, dim3(SCAT_THREADS), sm, s, a, rb);
         }
     }
     dim3 grid((a.D + SCAT_DC - 1) / SCAT_DC, a.B, 2);
     const int npass = (HW + SCAT_PX - 1) / SCAT_PX;
-#define DG_SCAT(NP)                                                                                                      \
-    {                                                                                                                    \
-        e = dg_set_max_smem(reinterpret_cast<const void*>(k_scatter_grad<NP>), smem); \
-        if (e != hipSuccess) return e;                                                                                   \
-        hipLaunchKernelGGL(k_scatter_grad<NP>, grid, dim3(SCAT_THREADS), smem, s, a, rmax);                                    \
-        return hipGetLastError();                                                                                        \
-    }
-    if (npass <= 2) DG_SCAT(2)
-    if (npass <= 4) DG_SCAT(4)
-    if (npass <= 8) DG_SCAT(8)
-    DG_SCAT(16)
-#undef DG_SCAT
+    auto launch = [&](auto kern) { return dg_launch(kern, grid, dim3(SCAT_THREADS), smem, s, a, rmax); };
+    if (npass <= 2) return launch(k_scatter_grad<2>);
+    if (npass <= 4) return launch(k_scatter_grad<4>);
+    if (npass <= 8) return launch(k_scatter_grad<8>);
+    return launch(k_scatter_grad<16>);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1141,12 +1115,9 @@ hipError_t dg_launch_fps(const float* depth, const float* depth_b, int Ba, int B
     if (stage_floats < h * w * 4) stage_floats = h * w * 4;          // (the point table takes the buffer over)
     if ((size_t)stage_floats * 4 + head > 158 * 1024) return hipErrorInvalidValue;
     const int smem = head + stage_floats * 4;
-    auto launch = [&](auto kern) -> hipError_t {
-        hipError_t e = dg_set_max_smem(reinterpret_cast<const void*>(kern), smem);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(kern, dim3(B), dim3(FPS_THREADS), smem, s, depth, depth_b, Ba, H, W, h, w, S, factor, stage_floats, out_coords, out_inds,
-                           (const float*)pooled_ws);
-        return hipGetLastError();
+    auto launch = [&](auto kern) {
+        return dg_launch(kern, dim3(B), dim3(FPS_THREADS), smem, s, depth, depth_b, Ba, H, W, h, w, S, factor, stage_floats, out_coords, out_inds,
+                         (const float*)pooled_ws);
     };
     if (h * w <= 2 * FPS_THREADS) return launch(k_fps_coords<2>);
     if (h * w <= 4 * FPS_THREADS) return launch(k_fps_coords<4>);

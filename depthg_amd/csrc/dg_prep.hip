@@ -295,14 +295,7 @@ hipError_t dg_launch_gather(const DgGatherArgs& a_in, int maxK4, hipStream_t s) 
         grid.z += (a.pre_blocks + per - 1) / per;
         if (a.pre.taps) smem = (int)(dg_taps_record_bytes(a.pre.h * a.pre.w, a.pre.P) + (size_t)a.pre.h * a.pre.w * 4 + 16);
     }
-    auto launch = [&](auto kern) -> hipError_t {
-        if (smem > 0) {
-            const hipError_t e = dg_set_max_smem(reinterpret_cast<const void*>(kern), smem);
-            if (e != hipSuccess) return e;
-        }
-        hipLaunchKernelGGL(kern, grid, block, smem, s, a);
-        return hipGetLastError();
-    };
+    auto launch = [&](auto kern) { return dg_launch_if(smem > 0, kern, grid, block, smem, s, a); };
 #define DG_GN4(M_) { if (nc == 0) return launch(k_gather_norm<M_, 0>); if (nc == 9) return launch(k_gather_norm<M_, 9>); \
                      if (nc == 13) return launch(k_gather_norm<M_, 13>); return launch(k_gather_norm<M_, 16>); }
     if (maxK4 <= 256) DG_GN4(1)
@@ -657,15 +650,9 @@ hipError_t dg_launch_plane_sample(const DgPlaneArgs& a, hipStream_t s) {
     const int smem = plane_bytes + a2.tap_consumers * a.P * 32;
     if (a.src_x) {
         if (!a.rows_x) return hipErrorInvalidValue;
-        hipError_t e = dg_set_max_smem(reinterpret_cast<const void*>(k_plane_sample<CH, true>), smem);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL((k_plane_sample<CH, true>), dim3(gx, a.B), dim3(PLANE_THREADS), smem, s, a2);
-        return hipGetLastError();
+        return dg_launch(k_plane_sample<CH, true>, dim3(gx, a.B), dim3(PLANE_THREADS), smem, s, a2);
     }
-    hipError_t e = dg_set_max_smem(reinterpret_cast<const void*>(k_plane_sample<CH>), smem);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_plane_sample<CH>, dim3(gx, a.B), dim3(PLANE_THREADS), smem, s, a2);
-    return hipGetLastError();
+    return dg_launch(k_plane_sample<CH>, dim3(gx, a.B), dim3(PLANE_THREADS), smem, s, a2);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1071,12 +1058,7 @@ hipError_t dg_launch_prep_dense(const DgDenseArgs& a, hipStream_t s) {
                              DENSE_TPB * 32 * (a.KD + 4) * 2 + 4 * DENSE_CODE_PAIRS * 4 + DENSE_TPB * 32 * 4), a.draw_count > 0 ? a.B * 4 : 0);
     if (a.h * ((DENSE_TPB * 32 + a.h - 1) / a.h + 1) > DENSE_CODE_PAIRS) return hipErrorInvalidValue;   // pairs per block
     const dim3 grid(gx * a.B * (a.depth ? 5 : 4) + (a.draw_count > 0 ? a.draw_count : 0));
-    auto launch = [&](auto kern) -> hipError_t {
-        hipError_t e = dg_set_max_smem(reinterpret_cast<const void*>(kern), smem);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(kern, grid, dim3(256), smem, s, a);
-        return hipGetLastError();
-    };
+    auto launch = [&](auto kern) { return dg_launch(kern, grid, dim3(256), smem, s, a); };
     // registers per thread follow the widths
     if (a.fkeep[0] || a.fkeep[1]) {      // (deferred Dropout2d of the feature maps: dg_corr_forward_masked)
         if (a.D <= 72) return a.KF <= 384 ? launch(k_prep_dense<48, 18, true>) : launch(k_prep_dense<96, 18, true>);
@@ -1155,11 +1137,8 @@ hipError_t dg_launch_colmean(const DgColmeanArgs& a, hipStream_t s) {
     if (a.dc.B > 0) {
         if (a.nops != 2) return hipErrorInvalidValue;       // (the dense path has two operands; their csum moves to the k_rowmean launch)
         ny = max(ny, 2 * (a.dc.KD / 8)); nz = 4; smem = a.dc.Ppad * 16 * ((a.dc.clo[0] || a.dc.clo[1]) ? 2 : 1);
-        hipError_t e = dg_set_max_smem(reinterpret_cast<const void*>(k_colmean), smem);
-        if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL(k_colmean, dim3(a.B, ny, nz), dim3(256), smem, s, a);
-    return hipGetLastError();
+    return dg_launch_if(a.dc.B > 0, k_colmean, dim3(a.B, ny, nz), dim3(256), smem, s, a);
 }
 
 // r[t][n][p] = a[n][p] . bbar_t[n] for all pair-sets t at once: one wave per operand-1 tile (32 positions) runs a
@@ -1290,13 +1269,7 @@ hipError_t dg_launch_rowmean(const DgRowmeanArgs& a, hipStream_t s) {
     const int smem = max(32 * (a.KF / 8) * 16, (ROWMEAN_WAVES - 1) * 16 * 64 * 4);     // F part / partial accumulators
     if (a.xA) {
         if (!a.xabar || a.ncs > 0) return hipErrorInvalidValue;
-        hipError_t e = dg_set_max_smem(reinterpret_cast<const void*>(k_rowmean<true>), smem);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(k_rowmean<true>, dim3(a.Ppad / 32 + 1, a.B, 2), dim3(64 * ROWMEAN_WAVES), smem, s, a);
-        return hipGetLastError();
+        return dg_launch(k_rowmean<true>, dim3(a.Ppad / 32 + 1, a.B, 2), dim3(64 * ROWMEAN_WAVES), smem, s, a);
     }
-    hipError_t e = dg_set_max_smem(reinterpret_cast<const void*>(k_rowmean<false>), smem);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_rowmean<false>, dim3(a.Ppad / 32 + 1 + (a.ncs > 0 ? 1 : 0), a.B), dim3(64 * ROWMEAN_WAVES), smem, s, a);
-    return hipGetLastError();
+    return dg_launch(k_rowmean<false>, dim3(a.Ppad / 32 + 1 + (a.ncs > 0 ? 1 : 0), a.B), dim3(64 * ROWMEAN_WAVES), smem, s, a);
 }

@@ -350,8 +350,5 @@ __global__ __launch_bounds__(256) void k_probe_ce_bwd(const DgProbeCeArgs a) {
 
 hipError_t dg_launch_probe_ce_bwd(const DgProbeCeArgs& a, hipStream_t s) {
     const int smem = (2 * a.n * a.w + a.n * a.W) * 4;
-    hipError_t e = dg_set_max_smem(reinterpret_cast<const void*>(k_probe_ce_bwd), smem);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_probe_ce_bwd, dim3(a.h, a.B), dim3(256), smem, s, a);
-    return hipGetLastError();
+    return dg_launch(k_probe_ce_bwd, dim3(a.h, a.B), dim3(256), smem, s, a);
 }

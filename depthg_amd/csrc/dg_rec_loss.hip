@@ -356,10 +356,7 @@ static hipError_t rec_smem_limit(const void* kern, int lds) {
 
 hipError_t dg_launch_rec_forward(const DgRecArgs& A, hipStream_t s) {
     const int tiles = A.B * A.tiles_per_img, lds = (int)dg_rec_lds(A.D);
-    hipError_t e = rec_smem_limit(reinterpret_cast<const void*>(k_rec_forward), lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_rec_forward, dim3(tiles), dim3(RC_THREADS), lds, s, A);
-    e = hipGetLastError();
+    const hipError_t e = dg_launch_if(lds > 64 * 1024, k_rec_forward, dim3(tiles), dim3(RC_THREADS), lds, s, A);
     if (e != hipSuccess) return e;
     return dg_launch_loss_reduce(A.part, tiles, A.inv_n, A.loss, s);
 }

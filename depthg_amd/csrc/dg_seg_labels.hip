@@ -191,10 +191,7 @@ hipError_t dg_launch_segment_labels(const DgSegArgs& a, const DgPaintArgs& p, hi
     const int cu = dg_cu_count();
     const int blocks = (int)(nchunks < cu ? nchunks : cu);
     const int smem = R * row_bytes + seg_stage_bytes(R * a.W);
-    e = dg_set_max_smem(reinterpret_cast<const void*>(k_seg_labels), smem);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_seg_labels, dim3(blocks), dim3(SL_THREADS), smem, s, a, p, R, (int)nchunks);
-    return hipGetLastError();
+    return dg_launch(k_seg_labels, dim3(blocks), dim3(SL_THREADS), smem, s, a, p, R, (int)nchunks);
 }
 
 hipError_t dg_launch_label_paint(const int64_t* preds, int G, const DgPaintArgs& p, hipStream_t s) {

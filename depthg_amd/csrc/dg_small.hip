@@ -666,12 +666,7 @@ hipError_t dg_launch_corr_small(const DgSmallArgs& a, hipStream_t s) {
     const int per = njob * a.nsplit;
     const int grid = ((a.B + 7) / 8) * 8 * per;
     const int smem = small_smem(NS);
-    auto go = [&](auto kern) -> hipError_t {
-        const hipError_t e = dg_set_max_smem(reinterpret_cast<const void*>(kern), smem);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(SM_THREADS), smem, s, a);
-        return hipGetLastError();
-    };
+    auto go = [&](auto kern) { return dg_launch(kern, dim3(grid), dim3(SM_THREADS), smem, s, a); };
 #define DG_SM_CASE(NS_)                                                                                  \
     if (NS == NS_) {                                                                                     \
         if (a.KD == 96) return a.pointwise ? go(k_corr_small<NS_, 6, true>) : go(k_corr_small<NS_, 6, false>); \

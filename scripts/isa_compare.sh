@@ -2,11 +2,13 @@
 # Device code of every unit of depthg_amd/csrc, a parent revision against the working tree: each .hip is compiled to gfx950
 # assembly with the Makefile's flags, the lines that carry the path-derived __hip_cuid name are dropped, and the two texts must be
 # equal (instruction streams, register counts, LDS and scratch sizes, kernel set).  Prints one markdown table row per unit and
-# fails if any differs.      usage: scripts/isa_compare.sh <parent-rev> [unit.hip ...]      (ISA_WORK: where the assembly is kept)
+# fails if any differs.      usage: scripts/isa_compare.sh <parent-rev> [unit.hip ...]      (ISA_WORK: where the assembly is kept;
+# EXTRA: further flags for both sides, e.g. EXTRA='-DDG_DEVTOOLS -DC2_STAMPS' - the assembly is then kept apart per flag set)
 set -euo pipefail
 root=$(git rev-parse --show-toplevel)
 rev=$(git -C "$root" rev-parse --short "$1"); shift
-work=${ISA_WORK:-${TMPDIR:-/tmp}/dg_isa}
+work=${ISA_WORK:-${TMPDIR:-/tmp}/dg_isa}$(echo "${EXTRA:-}" | tr -c 'A-Za-z0-9_=\n' _)
+export EXTRA=${EXTRA:-}
 mkdir -p "$work/parent-$rev" "$work/new"
 [ -d "$work/parent-$rev/depthg_amd" ] || git -C "$root" archive "$rev" depthg_amd/csrc include | tar -x -C "$work/parent-$rev"
 units=${*:-$(cd "$root/depthg_amd/csrc" && ls *.hip)}
@@ -15,7 +17,7 @@ asm() {     # asm <tree root> <unit> <output>: nothing to do when the output is 
     local src=$1/depthg_amd/csrc extra=
     [ "$2" = dg_corr2.hip ] && extra="-mllvm -disable-machine-licm"
     [ -s "$3" ] && [ -z "$(find "$src" "$1/include" -newer "$3" -type f \( -name '*.h' -o -name "$2" \))" ] && return 0
-    (cd "$src" && ${HIPCC:-hipcc} -O3 -std=c++17 --offload-arch=gfx950 --cuda-device-only -S $extra "$2" -o - | grep -v __hip_cuid > "$3.tmp") && mv "$3.tmp" "$3"
+    (cd "$src" && ${HIPCC:-hipcc} -O3 -std=c++17 --offload-arch=gfx950 --cuda-device-only -S $extra $EXTRA "$2" -o - | grep -v __hip_cuid > "$3.tmp") && mv "$3.tmp" "$3"
 }
 export -f asm
 for u in $units; do
