@@ -102,30 +102,32 @@ class Lattice:
         self._starts = np.flatnonzero(np.r_[True, np.diff(self.offsets.reshape(-1)[order]) != 0])
         self.alpha = F32(1.0) / (F32(1.0) + F32(2.0) ** F32(-d))
 
-    def filter(self, vals):
-        """K(vals) (N, C) fp32, without normalisation: splat, blur in directions 0..d, slice with alpha."""
-        vals = np.asarray(vals, F32)
+    def filter(self, vals, dtype=F32):
+        """K(vals) (N, C), without normalisation: splat, blur in directions 0..d, slice with alpha.  dtype: the type the three steps
+        accumulate in (fp32 as densecrf; np.float64: the same vertices and fp32 weights, summed in double)."""
+        vals = np.asarray(vals, dtype)
         d, M = self.d, self.M
-        contrib = self.bary.reshape(-1)[self._order, None] * vals[self._order // (d + 1)]
-        V = np.zeros((M + 1, vals.shape[1]), F32)
+        bary, half, alpha = self.bary.astype(dtype, copy=False), dtype(0.5), dtype(self.alpha)
+        contrib = bary.reshape(-1)[self._order, None] * vals[self._order // (d + 1)]
+        V = np.zeros((M + 1, vals.shape[1]), dtype)
         V[:M] = np.add.reduceat(contrib, self._starts, axis=0)
         for j in range(d + 1):
             W = np.zeros_like(V)
-            W[:M] = V[:M] + F32(0.5) * (V[self.nbrs[j, :, 0]] + V[self.nbrs[j, :, 1]])
+            W[:M] = V[:M] + half * (V[self.nbrs[j, :, 0]] + V[self.nbrs[j, :, 1]])
             V = W
         out = np.zeros_like(vals)
         for r in range(d + 1):
-            out += (self.bary[:, r, None] * V[self.offsets[:, r]]) * self.alpha
+            out += (bary[:, r, None] * V[self.offsets[:, r]]) * alpha
         return out
 
-    def norm(self):
-        k1 = self.filter(np.ones((self.N, 1), F32))[:, 0]
-        return (1.0 / np.sqrt(k1.astype(np.float64) + 1e-20)).astype(F32)
+    def norm(self, dtype=F32):
+        k1 = self.filter(np.ones((self.N, 1), dtype), dtype)[:, 0]
+        return (1.0 / np.sqrt(k1.astype(np.float64) + 1e-20)).astype(dtype)
 
-    def message(self, vals, norm=None):
-        """The normalised message K~(vals) = norm * K(norm * vals) (NORMALIZE_SYMMETRIC)."""
-        norm = self.norm() if norm is None else norm
-        return norm[:, None] * self.filter(norm[:, None] * np.asarray(vals, F32))
+    def message(self, vals, norm=None, dtype=F32):
+        """The normalised message K~(vals) = norm * K(norm * vals) (NORMALIZE_SYMMETRIC), accumulated in dtype (see filter)."""
+        norm = self.norm(dtype) if norm is None else norm
+        return norm[:, None] * self.filter(norm[:, None] * np.asarray(vals, dtype), dtype)
 
 
 def gaussian_lattice(H, W, sxy=POS_XY_STD):
@@ -164,17 +166,18 @@ def unary_from_logits(logits, H, W, group_ends=None):
 
 
 def dense_crf(img, U, group_ends=None, n_iter=MAX_ITER, pos_w=POS_W, pos_xy_std=POS_XY_STD, bi_w=BI_W, bi_xy_std=BI_XY_STD,
-              bi_rgb_std=BI_RGB_STD):
-    """Mean field for one image: img (3,H,W) normalised, U (C,H,W).  Returns Q (C,H,W) fp32."""
+              bi_rgb_std=BI_RGB_STD, dtype=F32):
+    """Mean field for one image: img (3,H,W) normalised, U (C,H,W).  Returns Q (C,H,W) in dtype (fp32 as densecrf; np.float64: the
+    same lattices, with the messages and the softmax in double)."""
     C, H, W = U.shape
     ends = [C] if group_ends is None else list(group_ends)
-    u = np.ascontiguousarray(np.asarray(U, F32).reshape(C, -1).T)
+    u = np.ascontiguousarray(np.asarray(U, F32).reshape(C, -1).T).astype(dtype, copy=False)
     Q = softmax_groups(-u, ends)
     if n_iter:
         lg, lb = gaussian_lattice(H, W, pos_xy_std), bilateral_lattice(img, bi_xy_std, bi_rgb_std)
-        ng, nb = lg.norm(), lb.norm()
+        ng, nb = lg.norm(dtype), lb.norm(dtype)
         for _ in range(n_iter):
-            E = -u + F32(pos_w) * lg.message(Q, ng)
-            E = E + F32(bi_w) * lb.message(Q, nb)
+            E = -u + dtype(pos_w) * lg.message(Q, ng, dtype)
+            E = E + dtype(bi_w) * lb.message(Q, nb, dtype)
             Q = softmax_groups(E, ends)
     return np.ascontiguousarray(Q.T.reshape(C, H, W))

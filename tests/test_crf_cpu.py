@@ -22,6 +22,40 @@ def normalised_images(rng, B, H, W):
     return (u8 - mean) / std
 
 
+def flat_region_images(rng, B, H, W, single_colour=False):
+    """T.Normalize of uint8 images made of flat regions, the input that puts thousands of pixels on one bilateral vertex: over a
+    horizontal ramp (green falling) a rectangle at exactly (255,255,255), one at exactly (0,0,0), one of a random colour and a
+    patch of noise.  The white rectangle reaches the bottom right corner in images 0 and 1 (the largest features, so the last
+    sorted run of the image is a long one); later images are mirrored (b % 3 == 2: left-right, b % 4 == 3: top-bottom), and
+    the random colour and the noise differ in every image.  single_colour: every image is one random colour."""
+    u8 = np.empty((B, 3, H, W), np.uint8)
+    for b in range(B):
+        if single_colour:
+            u8[b] = rng.integers(0, 256, 3).astype(np.uint8)[:, None, None]
+            continue
+        ramp = np.round(np.arange(W) * (255.0 / max(W - 1, 1))).astype(np.uint8)
+        im = np.broadcast_to(ramp, (3, H, W)).copy()
+        im[1] = 255 - im[1]
+        h2, w2, h3, w3 = H // 2, W // 2, H // 3, W // 3
+        im[:, h2:, w2:] = 255
+        im[:, :h3, :w2] = 0
+        im[:, h3:h2, w3:2 * w3] = rng.integers(1, 255, 3).astype(np.uint8)[:, None, None]
+        im[:, h2:h2 + h3 // 2 + 2, :w3] = rng.integers(0, 256, (3, h3 // 2 + 2, w3))
+        if b % 3 == 2:
+            im = im[:, :, ::-1]
+        if b % 4 == 3:
+            im = im[:, ::-1, :]
+        u8[b] = im
+    x = torch.from_numpy(u8.astype(np.float32) / 255)
+    mean, std = torch.tensor([0.485, 0.456, 0.406])[:, None, None], torch.tensor([0.229, 0.224, 0.225])[:, None, None]
+    return (x - mean) / std
+
+
+FLAT_SHAPES = [(37, 53), (96, 128), (40, 48)]     # the shapes of the GPU tests on flat images (test_gpu_crf_flat.py)
+FLAT_SEED = 40                            # those tests draw their images from this seed: the run lengths asserted here are theirs
+CRF_TILE = 64                            # dg_crf.hip: a splat run is cut at every multiple of CRF_TILE sorted positions of its image
+
+
 def test_crf_entry_points_are_declared_listed_and_exported():
     from depthg_amd import _lib
     import depthg_amd
@@ -221,3 +255,54 @@ def test_against_pydensecrf():
     d.addPairwiseBilateral(sxy=67, srgb=3, rgbim=R.colour_image(img), compat=4)
     want = np.array(d.inference(10)).reshape(C, H, W)
     assert np.abs(R.dense_crf(img, U) - want).max() <= 1e-4
+
+
+def _runs(img):
+    """The splat runs of one image's bilateral lattice, in sorted-key order: the restatement numbers its vertices by their packed
+    key, first coordinate most significant, as dg_crf.hip's sort does."""
+    return np.bincount(R.bilateral_lattice(img.numpy()).offsets.ravel())
+
+
+def test_flat_region_images_give_long_splat_runs_and_noise_does_not():
+    """Why flat_region_images exists: on noise no splat run is longer than 4 entries, so a run crosses one tile boundary at the
+    most: k_crf_splat_tail never sums a whole tile and k_crf_splat_head never adds two partial sums.  On flat regions every image
+    has runs that cross at least two boundaries wherever they start."""
+    src = open(os.path.join(ROOT, "depthg_amd", "csrc", "dg_crf.hip")).read()
+    assert re.search(rf"#define CRF_TILE {CRF_TILE}\b", src)
+    assert _runs(normalised_images(np.random.default_rng(10), 1, 37, 53)[0]).max() <= 4
+    assert any((6 * H * W) % CRF_TILE for H, W in FLAT_SHAPES)          # a last tile that is cut short by the end of its image
+    for H, W in FLAT_SHAPES:
+        img = flat_region_images(np.random.default_rng(FLAT_SEED), 4, H, W)
+        assert img.shape == (4, 3, H, W) and img.dtype == torch.float32
+        assert len({img[b].numpy().tobytes() for b in range(4)}) == 4
+        for b in range(4):
+            bgr = R.colour_image(img[b].numpy())
+            assert (bgr == 255).all(2).sum() >= H * W // 5 and (bgr == 0).all(2).sum() >= H * W // 8       # exactly white, exactly black
+            runs = _runs(img[b])
+            assert runs.max() >= 4 * CRF_TILE, (H, W, b, runs.max())
+            assert (runs > 2 * CRF_TILE).sum() >= 10, (H, W, b, (runs > 2 * CRF_TILE).sum())
+            if b < 2:                                                   # the image's last run continues into its last tiles
+                assert runs[-1] > 2 * CRF_TILE, (H, W, b, runs[-1])
+        one = flat_region_images(np.random.default_rng(FLAT_SEED), 2, H, W, single_colour=True)
+        assert not torch.equal(one[0], one[1])
+        for b in range(2):
+            assert len(np.unique(R.colour_image(one[b].numpy()).reshape(-1, 3), axis=0)) == 1
+            runs = _runs(one[b])
+            assert runs.max() >= 4 * CRF_TILE and (runs > 2 * CRF_TILE).sum() >= 10, (H, W, b, runs)
+
+
+@pytest.mark.parametrize("single_colour", [False, True])
+def test_restated_message_in_fp32_agrees_with_float64_accumulation_on_flat_images(single_colour):
+    """The restatement sums a run of thousands of entries in fp32, in sorted order.  Against the same lattice accumulated in
+    float64 (splat, blur, slice and norm) its message moves by 2e-7 .. 3e-7 of the largest value on these images (bound: 1e-6),
+    so the order of summation does not limit the 1e-5 bound of the GPU filter tests."""
+    for H, W in FLAT_SHAPES:
+        rng = np.random.default_rng(42)
+        img = flat_region_images(np.random.default_rng(FLAT_SEED), 1, H, W, single_colour=single_colour)[0].numpy()
+        lat = R.bilateral_lattice(img)
+        vals = rng.random((H * W, 6)).astype(np.float32)
+        m32, m64 = lat.message(vals), lat.message(vals, dtype=np.float64)
+        assert m32.dtype == np.float32 and m64.dtype == np.float64
+        rel = np.abs(m32 - m64).max() / np.abs(m64).max()
+        print(f"fp32 against float64 message, {H} x {W}, single_colour={single_colour}: {rel:.2e}")
+        assert rel <= 1e-6, (H, W, rel)

@@ -85,9 +85,9 @@ def test_crf_filter_symmetry_matches_the_restatement():
         assert abs(asym_ref) > 1e-5 and abs(asym - asym_ref) <= 2e-6, (asym, asym_ref)
 
 
-def _dense_case(rng, B, C_ends, H, W, h, w):
+def _dense_case(rng, B, C_ends, H, W, h, w, images=normalised_images):
     from depthg_amd import ops
-    img = normalised_images(rng, B, H, W)
+    img = images(rng, B, H, W)
     logits = torch.from_numpy(rng.standard_normal((B, C_ends[-1], h, w)).astype(np.float32) * 3)
     U = ops.crf_unary(logits.to(DEV), H, W, C_ends)
     U_ref = np.stack([R.unary_from_logits(logits[b].numpy(), H, W, C_ends) for b in range(B)])
@@ -163,22 +163,23 @@ def ref_log_probs(code, lin_w, lin_b, clusters, H, W, code_flip=None):
     return torch.log_softmax(lin, 1), torch.log_softmax(inner * 2, 1)
 
 
-def _eval_case(seed, B=2, D=16, h=8, w=10, H=40, W=48, n=5, m=6):
+def _eval_case(seed, B=2, D=16, h=8, w=10, H=40, W=48, n=5, m=6, images=normalised_images):
     rng = np.random.default_rng(seed)
     g = torch.Generator().manual_seed(seed)
     code, code_flip = torch.randn(B, D, h, w, generator=g), torch.randn(B, D, h, w, generator=g)
     lin_w, lin_b, clusters = torch.randn(n, D, generator=g), torch.randn(n, generator=g), torch.randn(m, D, generator=g)
     label = torch.randint(-1, n + 1, (B, H, W), generator=g)
-    img = normalised_images(rng, B, H, W)
+    img = images(rng, B, H, W)
     return code, code_flip, lin_w, lin_b, clusters, label, img
 
 
-@pytest.mark.parametrize("flip", [False, True])
-def test_predict_and_score_run_crf_matches_reference_chain(flip):
+def check_run_crf_chain(case, flip):
+    """predict_and_score(run_crf=True) on one _eval_case against the reference's chain: the unary, then the per-probe CRF's
+    predictions.  Returns the probes, the metrics it fed and the predictions."""
     from depthg_amd import ops, predict_and_score
     from depthg_amd.metrics import UnsupervisedMetrics
     from test_gpu_eval import make_probes
-    code, code_flip, lin_w, lin_b, clusters, label, img = _eval_case(21 + flip)
+    code, code_flip, lin_w, lin_b, clusters, label, img = case
     B, _, _, _ = code.shape
     n, m, H, W = lin_w.shape[0], clusters.shape[0], label.shape[-2], label.shape[-1]
     cf = code_flip if flip else None
@@ -198,6 +199,17 @@ def test_predict_and_score_run_crf_matches_reference_chain(flip):
         Q_lin = R.dense_crf(img[b].numpy(), U_ref[b][:n])
         Q_clu = R.dense_crf(img[b].numpy(), U_ref[b][n:])
         check_preds(torch.stack([pl[b], pc[b]]), np.concatenate([Q_lin, Q_clu]), [n, n + m])
+    return linear, cluster, lm, cm, pl, pc
+
+
+@pytest.mark.parametrize("flip", [False, True])
+def test_predict_and_score_run_crf_matches_reference_chain(flip):
+    from depthg_amd import predict_and_score
+    from depthg_amd.metrics import UnsupervisedMetrics
+    code, code_flip, lin_w, lin_b, clusters, label, img = case = _eval_case(21 + flip)
+    B, n, m = code.shape[0], lin_w.shape[0], clusters.shape[0]
+    cf = code_flip if flip else None
+    linear, cluster, lm, cm, pl, pc = check_run_crf_chain(case, flip)
     # the metrics' counts are the counts of the returned predictions
     lm2, cm2 = UnsupervisedMetrics("a/", n, 0, False), UnsupervisedMetrics("b/", n, m - n, True)
     lm2.update(pl, label.to(DEV))
