@@ -36,6 +36,11 @@ Public surface (mirrors the reference's Python operator surface for this path):
                                  DinoFeaturizerWithDepth (:490-631, cfg.arch "dino_depth"): depth-guided features in front of the head
     cross_attn                   the depth guidance's nn.MultiheadAttention core (src/modules.py:524, :566-585) as a fused HIP forward
                                  and backward with Philox dropout (cfg.dg_fused_cross_attn)
+    data                         the training data path (src/data.py:87-132, 815-912, 1073-1141; src/utils.py:164-182): CroppedFolder /
+                                 DirectoryFolder, loader_index_tables, ContrastiveBatches - the loader transform of a batch and its kNN
+                                 positives as ONE fused HIP launch (ops.batch_prep, k_batch_prep) - and precompute_knns
+    train                        fit(model, train_batches, val_batches, cfg, out_dir): the loop of src/train_segmentation.py:551-714 without
+                                 Lightning; `python -m depthg_amd.train` is its command line
     ops                          thin ctypes binding of the C ABI in include/depthg_corr.h; ops.corr_forward is the one route to its five
                                  forward entries (keep / feat_inv / intra_feats select one; perms=None draws the batch maps)
 """
@@ -66,7 +71,10 @@ from . import vit  # noqa: F401
 from . import featurizer  # noqa: F401
 from .featurizer import DinoFeaturizer, DinoFeaturizerWithDepth  # noqa: F401
 from . import segmenter  # noqa: F401
+from . import data  # noqa: F401
+from .data import ContrastiveBatches, CroppedFolder, DirectoryFolder, loader_index_tables, precompute_knns  # noqa: F401
 
 __all__ = ["ContrastiveCorrelationLoss", "DepthContrastiveCorrelationLoss", "ContrastiveCRFLoss", "crf_loss", "aug_loss", "aug_alignment_loss", "crop_flip_coords", "augment", "AugmentParams", "augment_batch", "draw_augment_params", "rec_loss", "reconstruction_loss", "depth_encoder", "cross_attn", "cross_attention", "multihead_cross_attention", "depth_decay", "training", "metrics", "evaluation", "predict_and_score", "segment", "crf", "dense_crf",
            "batched_crf", "knn", "lhp", "optim", "FusedAdam", "FusedAdamSet", "segmenter", "vit", "featurizer",
-           "DinoFeaturizer", "DinoFeaturizerWithDepth"]
+           "DinoFeaturizer", "DinoFeaturizerWithDepth", "data", "ContrastiveBatches", "CroppedFolder", "DirectoryFolder",
+           "loader_index_tables", "precompute_knns"]

@@ -139,6 +139,8 @@ SIGNATURES = {
     # GPU batch augmentation
     "dg_augment_workspace_bytes": (_SZ, [i32] * 3),
     "dg_augment_forward": (_I, [vp] + [i64] * 4 + [vp] * 4 + [i32] * 6 + [vp, vp, vp, _SZ, vp]),
+    # batch preparation
+    "dg_batch_prep": (_I, [vp, _SZ, vp, vp, vp] + [i32] * 4 + [vp] * 7),
     # measurement aids
     "dg_corr_main_kernel_name": (_STR, [cp]),
     "dg_corr_intra_folded": (_I, [cp]),

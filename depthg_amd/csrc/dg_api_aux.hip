@@ -1,5 +1,5 @@
 // C ABI of the gfx950 DepthG library (include/depthg_corr.h), the units' shared state and the small subsystems: version and error
-// text, the library's side stream, batch maps / random draws / coordinate samplers, kNN, LHP, fused Adam, ViT attention and linear, the fused depth encoder, the depth guidance's cross-attention, the GPU batch augmentation.  (The auxiliary loss terms: dg_api_loss.hip.)
+// text, the library's side stream, batch maps / random draws / coordinate samplers, kNN, LHP, fused Adam, ViT attention and linear, the fused depth encoder, the depth guidance's cross-attention, the GPU batch augmentation, the batch preparation.  (The auxiliary loss terms: dg_api_loss.hip.)
 // Host-side only: argument checks and kernel launches on the caller's stream.
 #include "dg_api.h"
 #include "dg_aux_args.h"
@@ -8,6 +8,7 @@
 
 #include <cstdarg>
 #include <map>
+#include <vector>
 
 // ---- error reporting (dg_api.h)
 thread_local char g_err[512] = "";
@@ -534,5 +535,77 @@ extern "C" int dg_augment_forward(const float* img, int64_t stride_b, int64_t st
             return fail(DG_ERR_INVALID, "dg_augment_forward: channel %d: mean=%g std=%g", c, (double)A.mean[c], (double)A.stdv[c]);
     }
     DG_HIP(dg_launch_augment(A, stats, static_cast<hipStream_t>(stream_)));
+    return DG_OK;
+}
+
+// ---- batch preparation (dg_batch.hip)
+extern "C" int dg_batch_prep(const uint8_t* packed, size_t packed_bytes, const int32_t* records_host, const int32_t* tables_host,
+                             const void* params, int32_t n_records, int32_t N, int32_t H, int32_t W, const float* mean, const float* stdv,
+                             float* img, int64_t* label, void* mask, float* depth, dg_stream_t stream_) {
+    if (n_records < 1 || N < 1 || H < 1 || W < 1)
+        return fail(DG_ERR_INVALID, "dg_batch_prep: n_records=%d N=%d, output %dx%d must be positive", n_records, N, H, W);
+    if (W % 4) return fail(DG_ERR_UNSUPPORTED, "dg_batch_prep: output width %d is not a multiple of 4 (a lane stores four columns as one vector)", W);
+    if (H > DG_BATCH_MAX_SIDE || W > DG_BATCH_MAX_SIDE || N > 65535 || n_records > 65535)
+        return fail(DG_ERR_UNSUPPORTED, "dg_batch_prep: output %dx%d above %d a side, or N=%d / n_records=%d above 65535", H, W, DG_BATCH_MAX_SIDE, N,
+                    n_records);
+    if (!records_host || !tables_host || !params || !mean || !stdv) return fail(DG_ERR_INVALID, "dg_batch_prep: null pointer");
+    if ((((uintptr_t)img | (uintptr_t)label | (uintptr_t)mask | (uintptr_t)depth) & 15) || ((uintptr_t)params & 3))
+        return fail(DG_ERR_INVALID, "dg_batch_prep: img, label, mask and depth must be 16-byte aligned (whole-vector stores), params 4-byte aligned");
+    DgBatchArgs A;
+    memset(&A, 0, sizeof(A));
+    for (int c = 0; c < 3; ++c) {
+        A.mean[c] = mean[c]; A.stdv[c] = stdv[c];
+        if (!(A.stdv[c] > 0.f) || std::isinf(A.stdv[c]) || !(A.mean[c] == A.mean[c]) || std::isinf(A.mean[c]))
+            return fail(DG_ERR_INVALID, "dg_batch_prep: channel %d: mean=%g std=%g", c, (double)A.mean[c], (double)A.stdv[c]);
+    }
+    // which sample each output has a record for: every element is written, and by one record
+    std::vector<uint8_t> seen((size_t)3 * N, 0);
+    int n_out[3] = {0, 0, 0}, rule = -1;
+    for (int i = 0; i < n_records; ++i) {
+        const int32_t* r = records_host + (size_t)i * DG_BATCH_REC_WORDS;
+        const int kind = r[0], n = r[1], sw = r[4], sh = r[5];
+        const unsigned long long off = (unsigned long long)(uint32_t)r[2] | ((unsigned long long)(uint32_t)r[3] << 32);
+        if (kind < DG_BATCH_IMAGE || kind > DG_BATCH_LABEL_FILL) return fail(DG_ERR_INVALID, "dg_batch_prep: record %d: unknown kind %d (0 .. 4)", i, kind);
+        if (n < 0 || n >= N) return fail(DG_ERR_INVALID, "dg_batch_prep: record %d: sample %d outside 0 .. %d", i, n, N - 1);
+        const bool labels = kind == DG_BATCH_LABEL || kind == DG_BATCH_LABEL_FILL;
+        const int out = kind == DG_BATCH_IMAGE ? 0 : labels ? 1 : 2;
+        if (out == 0 ? !img : out == 1 ? (!label || !mask) : !depth)
+            return fail(DG_ERR_INVALID, "dg_batch_prep: record %d (kind %d) writes an output that is null", i, kind);
+        if (seen[(size_t)out * N + n]++) return fail(DG_ERR_INVALID, "dg_batch_prep: record %d: sample %d of output %d is written twice", i, n, out);
+        ++n_out[out];
+        if (labels) {
+            if (r[7] != DG_BATCH_MASK_BOOL_IGNORED && r[7] != DG_BATCH_MASK_FLOAT_POSITIVE)
+                return fail(DG_ERR_INVALID, "dg_batch_prep: record %d: unknown mask rule %d (0, 1)", i, r[7]);
+            if (rule >= 0 && r[7] != rule) return fail(DG_ERR_INVALID, "dg_batch_prep: record %d: mask rule %d after %d (one mask tensor: one rule)", i, r[7], rule);
+            rule = r[7];
+        }
+        if (kind == DG_BATCH_DEPTH_PLANE || kind == DG_BATCH_LABEL_FILL) continue;      // no source
+        if (sw < 1 || sh < 1) return fail(DG_ERR_INVALID, "dg_batch_prep: record %d: zero-sized source plane %dx%d", i, sw, sh);
+        if (sw > DG_BATCH_MAX_SIDE || sh > DG_BATCH_MAX_SIDE)
+            return fail(DG_ERR_UNSUPPORTED, "dg_batch_prep: record %d: source plane %dx%d above %d a side", i, sw, sh, DG_BATCH_MAX_SIDE);
+        const unsigned long long bytes = (unsigned long long)sw * sh * (kind == DG_BATCH_IMAGE ? 3 : 1);
+        if (!packed || off > packed_bytes || bytes > packed_bytes - off)
+            return fail(DG_ERR_INVALID, "dg_batch_prep: record %d: plane of %llu bytes at offset %llu leaves the packed buffer of %zu bytes", i, bytes, off,
+                        packed_bytes);
+        const int32_t* xs = tables_host + (size_t)n * (W + H);
+        const int32_t* ys = xs + W;
+        for (int x = 0; x < W; ++x)
+            if (xs[x] < 0 || xs[x] >= sw)
+                return fail(DG_ERR_INVALID, "dg_batch_prep: record %d: column table entry %d = %d outside the source width %d (the plane is narrower than the tables address)", i, x, xs[x], sw);
+        for (int y = 0; y < H; ++y)
+            if (ys[y] < 0 || ys[y] >= sh)
+                return fail(DG_ERR_INVALID, "dg_batch_prep: record %d: row table entry %d = %d outside the source height %d (the plane is shorter than the tables address)", i, y, ys[y], sh);
+    }
+    const void* outs[3] = {img, label, depth};
+    for (int o = 0; o < 3; ++o)
+        if (outs[o] && n_out[o] != N)
+            return fail(DG_ERR_INVALID, "dg_batch_prep: output %d has records for %d of %d samples (every element must be written)", o, n_out[o], N);
+    A.packed = packed;
+    A.recs = static_cast<const int32_t*>(params);
+    A.tables = A.recs + (size_t)n_records * DG_BATCH_REC_WORDS;
+    A.img = img; A.label = reinterpret_cast<long long*>(label); A.mask = mask; A.depth = depth;
+    A.n_records = n_records; A.N = N; A.H = H; A.W = W;
+    A.tiles_x = (W + DG_BATCH_TW - 1) / DG_BATCH_TW; A.tiles_y = (H + DG_BATCH_TH - 1) / DG_BATCH_TH;
+    DG_HIP(dg_launch_batch_prep(A, static_cast<hipStream_t>(stream_)));
     return DG_OK;
 }

@@ -1,4 +1,4 @@
-// The stand-alone operations (dg_sample, dg_metrics, dg_knn, dg_lhp, dg_optim, dg_attn, dg_linear, dg_augment .hip; dg_api_aux.hip): constants and launchers.
+// The stand-alone operations (dg_sample, dg_metrics, dg_knn, dg_lhp, dg_optim, dg_attn, dg_linear, dg_augment, dg_batch .hip; dg_api_aux.hip): constants and launchers.
 // (The auxiliary loss terms have a header of their own: dg_loss_args.h.)
 #pragma once
 #include "dg_common.h"
@@ -88,3 +88,24 @@ struct DgAugmentArgs {
     float mean[3], stdv[3];
 };
 hipError_t dg_launch_augment(const DgAugmentArgs& A, bool stats, hipStream_t s);
+
+// ---- batch preparation: the loader transform of a batch and its positives in one launch (dg_batch.hip; src/utils.py:164-182,
+// src/data.py:87-132, 815-912, 1073-1141)
+#define DG_BATCH_TH 16                       // output tile: 16 rows x 64 columns, one thread per four neighbouring pixels
+#define DG_BATCH_TW 64
+#define DG_BATCH_THREADS 256
+#define DG_BATCH_REC_WORDS 8                 // 32-bit words of one record (include/depthg_corr.h lists them)
+#define DG_BATCH_MAX_SIDE 16384              // of a source plane and of the output
+struct DgBatchArgs {
+    const uint8_t* packed;                   // the decoded source planes of every sample
+    const int32_t* recs;                     // n_records records of DG_BATCH_REC_WORDS words
+    const int32_t* tables;                   // per sample xs[W] then ys[H]
+    float* img;                              // (N, 3, H, W)
+    long long* label;                        // (N, H, W)
+    void* mask;                              // (N, H, W): bool bytes or float32, by the label records' rule
+    float* depth;                            // (N, H, W)
+    int n_records, N, H, W;
+    int tiles_x, tiles_y;
+    float mean[3], stdv[3];
+};
+hipError_t dg_launch_batch_prep(const DgBatchArgs& A, hipStream_t s);

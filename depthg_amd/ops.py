@@ -461,6 +461,55 @@ def augment_forward(img, packed, out_size, mean=None, std=None):
     return img_aug, coord_aug
 
 
+BATCH_IMAGE, BATCH_LABEL, BATCH_DEPTH, BATCH_DEPTH_PLANE, BATCH_LABEL_FILL = range(5)      # dg_batch_prep's record kinds
+BATCH_MASK_BOOL_IGNORED, BATCH_MASK_FLOAT_POSITIVE = 0, 1                                   # and its mask rules
+BATCH_REC_WORDS = 8
+
+
+def batch_prep(packed, records, tables, out_size, device=None, mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225), params=None):
+    """The loader transform of a whole batch in one launch (dg_batch_prep, dg_batch.hip).  packed: uint8 tensor of the decoded source
+    planes - on the CPU (pinned memory makes the one upload asynchronous) or already on the GPU; records: CPU int32 (n_records, 8);
+    tables: CPU int32 (N, W + H), per sample xs[W] then ys[H] (data.pack_batch makes all three); out_size: (H, W).  `params`: the
+    device copy of [records, tables] when the caller has uploaded it already, else it is uploaded here, once.  Returns a dict of the
+    outputs the records write - img fp32 (N,3,H,W), label int64 (N,H,W), mask bool or fp32 (N,H,W), depth fp32 (N,H,W) - every
+    element written."""
+    lib = _lib.load()
+    H, W = int(out_size[0]), int(out_size[1])
+    for t, name, dt in ((records, "records", torch.int32), (tables, "tables", torch.int32)):
+        if t.dtype != dt or t.is_cuda or not t.is_contiguous():
+            raise ValueError(f"depthg_amd: batch_prep wants `{name}` as a contiguous CPU int32 tensor")
+    if records.dim() != 2 or records.shape[1] != BATCH_REC_WORDS or tables.dim() != 2 or tables.shape[1] != W + H:
+        raise ValueError(f"depthg_amd: batch_prep wants records (n, {BATCH_REC_WORDS}) and tables (N, {W} + {H}), got {tuple(records.shape)} and "
+                         f"{tuple(tables.shape)}")
+    if packed.dtype != torch.uint8 or packed.dim() != 1 or not packed.is_contiguous():
+        raise ValueError("depthg_amd: batch_prep wants `packed` as a flat contiguous uint8 tensor")
+    if device is None:
+        device = packed.device if packed.is_cuda else (params.device if params is not None else torch.device("cuda", torch.cuda.current_device()))
+    dev = torch.device(device)
+    stream = _stream(dev)
+    src = _on_gpu(packed.to(dev, non_blocking=True), "packed")
+    if params is None:
+        params = torch.cat([records.reshape(-1), tables.reshape(-1)]).to(dev, non_blocking=True)
+    elif not params.is_cuda or params.dtype != torch.int32 or params.numel() != records.numel() + tables.numel():
+        raise ValueError("depthg_amd: batch_prep wants `params` as the GPU int32 copy of [records, tables]")
+    n_records, N = records.shape[0], tables.shape[0]
+    kinds = set(records[:, 0].tolist())
+    rules = set(records[:, 7][(records[:, 0] == BATCH_LABEL) | (records[:, 0] == BATCH_LABEL_FILL)].tolist())
+    out = {}
+    if BATCH_IMAGE in kinds:
+        out["img"] = _empty((N, 3, H, W), torch.float32, dev)
+    if kinds & {BATCH_LABEL, BATCH_LABEL_FILL}:
+        out["label"] = _empty((N, H, W), torch.int64, dev)
+        out["mask"] = _empty((N, H, W), torch.float32 if rules == {BATCH_MASK_FLOAT_POSITIVE} else torch.bool, dev)
+    if kinds & {BATCH_DEPTH, BATCH_DEPTH_PLANE}:
+        out["depth"] = _empty((N, H, W), torch.float32, dev)
+    rc = lib.dg_batch_prep(_ptr(src), src.numel(), ctypes.c_void_p(records.data_ptr()), ctypes.c_void_p(tables.data_ptr()), _ptr(params),
+                           n_records, N, H, W, (ctypes.c_float * 3)(*mean), (ctypes.c_float * 3)(*std), _ptr(out.get("img")),
+                           _ptr(out.get("label")), _ptr(out.get("mask")), _ptr(out.get("depth")), stream)
+    _lib.check(rc, "dg_batch_prep")
+    return out
+
+
 def rec_loss_shapes(code, feats, weight, bias):
     """The reconstruction term's shape rules, on any device: code (B,D,h,w), feats (B,C,h,w) on the same grid, the decoder's weight
     (C,D,1,1) or (C,D) and bias (C,).  Returns (weight as (C,D), (B, D, C, h, w))."""

@@ -1,0 +1,204 @@
+"""Train a segmenter from a dataset folder: the loop of src/train_segmentation.py:551-714 without Lightning, Hydra, TensorBoard or wandb.
+
+    python -m depthg_amd.train --data-dir D --out O [--dataset directory] [--precompute-knns] [--device cuda:0] [key=value ...]
+
+builds the train pipeline (data.CroppedFolder, or data.DirectoryFolder with --dataset directory, under data.ContrastiveBatches: the
+loader transform of a batch and its kNN positives is one fused HIP launch) from the cfg keys dataset_name, crop_type, crop_ratio, res,
+loader_crop_type, num_neighbors, use_depth, depth_type, batch_size and max_steps, the val pipeline at eval_res 320 (224 for model_type
+"mae") with a centre crop (none for dataset_name "voc"), an UnsupervisedSegmenter, and runs `fit`.  Keys come from
+segmenter.default_segmenter_cfg and TRAIN_DEFAULTS, overridden by `key=value` arguments (values are read as Python literals where
+they parse, else as strings; `~` and `null` are None).  --precompute-knns writes a missing nearest-neighbour table first
+(data.precompute_knns).  The reference reads its val set from the uncropped dataset classes; here both splits come from the same
+folder layout (cfg.val_crop_type names the val folder's crop, default: cfg.crop_type).
+
+`fit(model, train_batches, val_batches, cfg, out_dir)`:
+    training_step per batch, epoch after epoch, until cfg.max_steps;
+    every cfg.val_freq batches of an epoch: validation_step over val_batches, then on_validation_epoch_end.  A val_freq above a quarter
+        of an epoch is dropped, as in the reference (:690-691): validation then runs at the end of every epoch.  The fit's last step is
+        always followed by a validation (unless one just ran), so the checkpoints it leaves carry metrics of their own weights;
+    <out_dir>/last.pt after every validation and at the end, <out_dir>/best.pt whenever `test/cluster/mIoU` (`test/cluster/Accuracy`
+        for dataset_name "potsdam") exceeds its best so far - both through demo.save_checkpoint;
+    <out_dir>/log.jsonl: one JSON line {"step": n, ...the step's logs} every cfg.scalar_log_freq steps and one {"step": n, "val": {...}}
+        per validation.
+"""
+import argparse
+import ast
+import json
+import os
+import sys
+
+import torch
+
+from .segmenter import UnsupervisedSegmenter, default_segmenter_cfg
+
+# the loop's and the pipelines' keys, with the values of src/configs/local_config.yml
+TRAIN_DEFAULTS = dict(dataset_name="cocostuff27", crop_type="five", crop_ratio=.5, res=224, loader_crop_type="center", num_neighbors=7,
+                      depth_type="zoedepth", batch_size=32, max_steps=7000, val_freq=100, scalar_log_freq=10, num_workers=8,
+                      dir_dataset_name=None, dir_dataset_n_classes=5, val_crop_type=None)
+
+
+def monitor_key(cfg):
+    return "test/cluster/Accuracy" if getattr(cfg, "dataset_name", None) == "potsdam" else "test/cluster/mIoU"      # :693-696
+
+
+def validation_interval(cfg, batches_per_epoch):
+    """cfg.val_freq in batches, or None (validate at the end of every epoch) when there is none or it exceeds a quarter of an epoch."""
+    val_freq = getattr(cfg, "val_freq", None)
+    if val_freq is None or int(val_freq) < 1 or int(val_freq) > batches_per_epoch // 4:                              # :690-691
+        return None
+    return int(val_freq)
+
+
+def _plain(v):
+    if isinstance(v, torch.Tensor):
+        return float(v) if v.numel() == 1 else v.detach().cpu().tolist()
+    return v.item() if hasattr(v, "item") else v
+
+
+def fit(model, train_batches, val_batches, cfg, out_dir, save_checkpoint=None):
+    """See the module docstring.  `save_checkpoint(model, path)`: demo.save_checkpoint unless given.  Returns {"steps", "validations",
+    "val_steps" (the step counts validations ran behind), "best", "best_step", "losses"}."""
+    if save_checkpoint is None:
+        from .demo import save_checkpoint
+    os.makedirs(out_dir, exist_ok=True)
+    max_steps = int(cfg.max_steps)
+    per_epoch = len(train_batches)
+    if per_epoch < 1:
+        raise ValueError("depthg_amd.train: the train pipeline has no batch")
+    interval = validation_interval(cfg, per_epoch)
+    log_freq = max(int(getattr(cfg, "scalar_log_freq", 10)), 1)
+    monitor = monitor_key(cfg)
+    log_path = os.path.join(out_dir, "log.jsonl")
+    state = {"steps": 0, "validations": 0, "val_steps": [], "best": None, "best_step": None, "losses": []}
+
+    def write(line):
+        with open(log_path, "a") as f:
+            f.write(json.dumps(line) + "\n")
+
+    def validate():
+        if val_batches is None:
+            return
+        for i, batch in enumerate(val_batches):
+            model.validation_step(batch, i)
+        metrics = {k: _plain(v) for k, v in model.on_validation_epoch_end().items()}
+        state["validations"] += 1
+        state["val_steps"].append(state["steps"])
+        write({"step": state["steps"], "val": metrics})
+        save_checkpoint(model, os.path.join(out_dir, "last.pt"))
+        score = metrics.get(monitor)
+        if score is not None and (state["best"] is None or score > state["best"]):
+            state["best"], state["best_step"] = score, state["steps"]
+            save_checkpoint(model, os.path.join(out_dir, "best.pt"))
+
+    while state["steps"] < max_steps:
+        for batch_idx, batch in enumerate(train_batches):
+            loss, logs = model.training_step(batch, batch_idx)
+            state["steps"] += 1
+            state["losses"].append(float(loss))
+            if state["steps"] % log_freq == 0:
+                write({"step": state["steps"], **{k: _plain(v) for k, v in logs.items()}})
+            last_of_epoch = batch_idx + 1 == per_epoch
+            if (interval is not None and (batch_idx + 1) % interval == 0) or (interval is None and last_of_epoch):
+                validate()
+            if state["steps"] >= max_steps:
+                break
+    if not state["val_steps"] or state["val_steps"][-1] != state["steps"]:
+        validate()
+    save_checkpoint(model, os.path.join(out_dir, "last.pt"))
+    return state
+
+
+# --------------------------------------------------------------------------------------------------------------- command line
+def parse_overrides(pairs):
+    out = {}
+    for pair in pairs:
+        key, sep, text = pair.partition("=")
+        if not sep or not key:
+            raise ValueError("Unexpected arg style {}".format(pair))                                                 # src/utils.py:160
+        if text in ("~", "null", "None"):
+            out[key] = None
+            continue
+        try:
+            out[key] = ast.literal_eval(text)
+        except (ValueError, SyntaxError):
+            out[key] = text
+    return out
+
+
+def build_cfg(overrides):
+    cfg = default_segmenter_cfg(**{**TRAIN_DEFAULTS, **overrides})
+    return cfg
+
+
+def build_dataset(cfg, data_dir, image_set, return_depth):
+    from . import data
+    if cfg.dataset_name == "directory":
+        return data.DirectoryFolder(data_dir, image_set, name=cfg.dir_dataset_name or "directory", n_classes=cfg.dir_dataset_n_classes,
+                                    crop_type=cfg.crop_type if image_set == "train" else None)
+    crop = cfg.crop_type if image_set == "train" or cfg.val_crop_type is None else cfg.val_crop_type
+    return data.CroppedFolder(data_dir, cfg.dataset_name, crop, cfg.crop_ratio, image_set, return_depth=return_depth, depth_type=cfg.depth_type)
+
+
+def build_pipelines(cfg, data_dir, device, precompute=False, net=None):
+    """(train_batches, val_batches, n_classes) of cfg (:614-658).  `precompute`: write the train table first when it is missing, with `net`."""
+    from . import data, knn
+    train_set = build_dataset(cfg, data_dir, "train", bool(cfg.use_depth))
+    if train_set.n_classes is None:
+        raise ValueError(f"Unknown dataset: {cfg.dataset_name}")                                                    # src/data.py:1039
+    path = knn.nns_path(data_dir, cfg.model_type, train_set.nns_name, "train", train_set.crop_type, cfg.res)
+    if precompute and not os.path.exists(path):
+        data.precompute_knns(net(train_set.n_classes), train_set, cfg, cfg.res, "train", train_set.crop_type, num_workers=cfg.num_workers,
+                             device=device, batch_size=min(128 if cfg.model_type == "vit_small" else 64, max(len(train_set), 1)))
+    gen = torch.Generator().manual_seed(0)                                                                           # seed_everything(0), :590
+    train_batches = data.ContrastiveBatches(train_set, cfg, "train", cfg.res, cfg.loader_crop_type, cfg.batch_size, shuffle=True, generator=gen,
+                                            num_workers=cfg.num_workers, pos=True, return_depth=bool(cfg.use_depth), device=device)
+    eval_res = 224 if cfg.model_type == "mae" else 320                                                               # :597-600
+    val_crop = None if cfg.dataset_name == "voc" else "center"                                                       # :632-635
+    val_set = build_dataset(cfg, data_dir, "val", False)
+    val_batches = data.ContrastiveBatches(val_set, cfg, "val", eval_res, val_crop, cfg.batch_size, shuffle=False, num_workers=cfg.num_workers,
+                                          pos=False, return_depth=False, device=device)
+    return train_batches, val_batches, train_set.n_classes
+
+
+def main(argv=None) -> int:
+    ap = argparse.ArgumentParser(prog="python -m depthg_amd.train", description=__doc__.split("\n\n")[0])
+    ap.add_argument("--data-dir", required=True)
+    ap.add_argument("--out", required=True)
+    ap.add_argument("--dataset", default=None, help="`directory`: imgs/{split} and labels/{split} under --data-dir (sets dataset_name)")
+    ap.add_argument("--precompute-knns", action="store_true", help="write the nearest-neighbour table first when it is missing")
+    ap.add_argument("--device", default="cuda:0")
+    ap.add_argument("overrides", nargs="*", help="cfg keys as key=value")
+    args = ap.parse_args(argv)
+    overrides = parse_overrides(args.overrides)
+    if args.dataset is not None:
+        overrides["dataset_name"] = args.dataset
+    cfg = build_cfg(overrides)
+    if not torch.cuda.is_available():
+        sys.exit("depthg_amd.train: no GPU (training_step has no CPU route)")
+    device = torch.device(args.device)
+    torch.manual_seed(0)                                                                                             # :590
+    holder = {}
+
+    def model_for(n_classes):
+        if "model" not in holder:
+            holder["model"] = UnsupervisedSegmenter(n_classes, cfg).to(device)
+        return holder["model"]
+
+    def knn_net(n_classes):
+        model = model_for(n_classes)
+        if model.depth_arch:
+            raise ValueError("depthg_amd.train: --precompute-knns pools the image featurizer's output; with cfg.arch = 'dino_depth' write the "
+                             "table under arch='dino' first")
+        return model.net
+
+    train_batches, val_batches, n_classes = build_pipelines(cfg, args.data_dir, device, args.precompute_knns, knn_net)
+    model = model_for(n_classes)
+    model.train()
+    state = fit(model, train_batches, val_batches, cfg, args.out)
+    print(f"depthg_amd.train: {state['steps']} step(s), {state['validations']} validation(s), best {monitor_key(cfg)} = {state['best']} "
+          f"at step {state['best_step']} -> {args.out}")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

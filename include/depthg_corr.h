@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define DG_VERSION 118   /* 118: dg_corr_forward_intra_feats + dg_corr_workspace_bytes_intra_feats, dg_corr_cd_hist, the three dg_crfloss and the three dg_augalign entry points (more exports under the same number: the layouts and meanings of every earlier entry point are unchanged, and a binding that declares a new symbol refuses a library without it when it loads), dg_sampled_sumsq, dg_corr_forward_extnorm (feature maps wider than 768 channels on SAMPLED grids above 160 positions, in channel chunks); 117: DG_FEATS_UNIT, dg_normalize_split (feature maps wider than 768 channels on the dense identity grid, in chunks of the width the operand kernels hold: the loss is linear in the feature correlation); 116: dg_prof_main_span takes FOUR words (+ the workgroups' lifetimes in shader cycles and wall ticks: the clock the CUs held); 115: dg_corr_intra_folded; 114: dg_fps_coords_pair takes a workspace (dg_fps_workspace_bytes(2 B, h, w): the pooled depth maps, written by a launch over the whole chip in front of the sampler), dg_corr_materialize_shared, dg_prof_main_span (the fused correlation launch's execution span inside a replayed step), sample grids of <= 160 positions at any feature width (fused small-grid kernel); 113: dg_corr_forward_masked; 112: dg_rand_coords_state; 111: dg_head_forward_pair / dg_head_backward_pair; 110: dg_fps_coords_pair; 109: dg_knn_similarities; 108: dg_corr_desc.code_h / code_w (code maps of another resolution than the feature maps: the FeaturePyramidNet producer, src/modules.py:732-766), dg_corr_desc.flags DG_EXACT_MASKS; 107: dg_head_*, dg_cluster_lookup_*, dg_probe_ce_*; 106: dg_corr_main_kernel_name; 105: dg_corr_forward_draw; 104: dg_lhp_map_forward / dg_lhp_map_backward; 103: dg_super_perms_state; 102: DG_LINE_GRID, dg_salience_coords, dg_simple_depth_coords; 101: total weights, DG_OUT_TOTAL */
+#define DG_VERSION 118   /* 118: dg_corr_forward_intra_feats + dg_corr_workspace_bytes_intra_feats, dg_corr_cd_hist, the three dg_crfloss the three dg_augalign entry points and dg_batch_prep (more exports under the same number: the layouts and meanings of every earlier entry point are unchanged, and a binding that declares a new symbol refuses a library without it when it loads), dg_sampled_sumsq, dg_corr_forward_extnorm (feature maps wider than 768 channels on SAMPLED grids above 160 positions, in channel chunks); 117: DG_FEATS_UNIT, dg_normalize_split (feature maps wider than 768 channels on the dense identity grid, in chunks of the width the operand kernels hold: the loss is linear in the feature correlation); 116: dg_prof_main_span takes FOUR words (+ the workgroups' lifetimes in shader cycles and wall ticks: the clock the CUs held); 115: dg_corr_intra_folded; 114: dg_fps_coords_pair takes a workspace (dg_fps_workspace_bytes(2 B, h, w): the pooled depth maps, written by a launch over the whole chip in front of the sampler), dg_corr_materialize_shared, dg_prof_main_span (the fused correlation launch's execution span inside a replayed step), sample grids of <= 160 positions at any feature width (fused small-grid kernel); 113: dg_corr_forward_masked; 112: dg_rand_coords_state; 111: dg_head_forward_pair / dg_head_backward_pair; 110: dg_fps_coords_pair; 109: dg_knn_similarities; 108: dg_corr_desc.code_h / code_w (code maps of another resolution than the feature maps: the FeaturePyramidNet producer, src/modules.py:732-766), dg_corr_desc.flags DG_EXACT_MASKS; 107: dg_head_*, dg_cluster_lookup_*, dg_probe_ce_*; 106: dg_corr_main_kernel_name; 105: dg_corr_forward_draw; 104: dg_lhp_map_forward / dg_lhp_map_backward; 103: dg_super_perms_state; 102: DG_LINE_GRID, dg_salience_coords, dg_simple_depth_coords; 101: total weights, DG_OUT_TOTAL */
 
 /* flags of dg_corr_desc.flags (names follow the cfg keys read at src/modules.py:1236-1352) */
 #define DG_POINTWISE      (1u << 0)  /* cfg.pointwise: spatial centering of fd (modules.py:1236-1239) */
@@ -1014,6 +1014,44 @@ int dg_augment_forward(const float* img, int64_t stride_b, int64_t stride_c, int
                        const int32_t* records_host, const void* params, const float* mean, const float* stdv, int32_t B, int32_t C,
                        int32_t H, int32_t W, int32_t h, int32_t w, float* img_aug, float* coord_aug, void* workspace,
                        size_t workspace_bytes, dg_stream_t stream);
+
+/*
+ * Batch preparation: the loader transform of the training data path (src/utils.py:164-182: Resize(res, NEAREST), the cropper, then
+ * ToTensor and Normalize on the image, ToTargetTensor on the label and the depth map) for a whole batch - the samples and their kNN
+ * positives, N = 2B - in ONE launch (dg_batch.hip), from the decoded uint8 planes of every sample at their own sizes.
+ *  packed : uint8 device buffer of packed_bytes bytes: images RGB HWC, labels and depth maps HW, at the byte offsets the records name
+ *  records_host : HOST memory, n_records records of 8 32-bit words, one per output plane group:
+ *      0 kind (below), 1 sample n in [0, N), 2-3 byte offset of the source plane in `packed` (low, high word), 4 source width,
+ *      5 source height, 6 label offset (added to the label byte; the value of DG_BATCH_LABEL_FILL), 7 mask rule (label kinds)
+ *  tables_host : HOST memory, per sample W + H int32: xs[W], the source column of every output column, then ys[H], the source row of
+ *      every output row - the resize and the crop composed by the caller (depthg_amd/data.py loader_index_tables).  Every record of
+ *      sample n reads sample n's tables, so its planes must have one size.
+ *  params : the DEVICE copy of both: the records, then the tables (one upload).  The host copies are read by this call for its checks.
+ *  mean, stdv : HOST memory, three floats each
+ *  img : fp32 (N,3,H,W) = (byte / 255 - mean[c]) / stdv[c], each operation rounded to float32 with IEEE division and no contraction,
+ *      in ToTensor's and Normalize's order: the bits of torch's CPU chain
+ *  label : int64 (N,H,W) = byte + label offset.  mask (N,H,W): by the records' rule (all label records of a call share one) bool bytes
+ *      label == -1 (DG_BATCH_MASK_BOOL_IGNORED, src/data.py:900-902) or fp32 label > 0 (DG_BATCH_MASK_FLOAT_POSITIVE, src/data.py:128)
+ *  depth : fp32 (N,H,W) = the byte value (DG_BATCH_DEPTH) or 255 (DG_BATCH_DEPTH_PLANE, src/data.py:897-898: no source is read)
+ * An output no record writes may be NULL.  For every other output the records must name each sample exactly once, so EVERY element
+ * is written, by one lane: no atomics, no intermediate image, two calls give the same bytes.  A lane owns four neighbouring columns
+ * of a row and stores whole 16-byte vectors (the bool mask: one 4-byte word).  No workspace, no allocation, no host synchronisation.
+ * Refused before any launch, with the reason in dg_last_error: DG_ERR_INVALID for null pointers, an unknown kind or mask rule, mixed
+ * mask rules, a sample outside [0, N), a zero-sized source plane, a plane that leaves `packed`, a table entry outside its plane
+ * (the plane is narrower than the tables address), an output that is not 16-byte aligned, a sample written twice or not at all,
+ * std <= 0; DG_ERR_UNSUPPORTED for W not a multiple of 4, a side of a source plane or of the output above 16384, N or n_records
+ * above 65535.
+ */
+#define DG_BATCH_IMAGE       0   /* RGB uint8 HWC -> img */
+#define DG_BATCH_LABEL       1   /* uint8 HW -> label and mask */
+#define DG_BATCH_DEPTH       2   /* uint8 HW -> depth */
+#define DG_BATCH_DEPTH_PLANE 3   /* no source: depth = 255 */
+#define DG_BATCH_LABEL_FILL  4   /* no source: label = label offset, and its mask (src/data.py:126: a folder without labels) */
+#define DG_BATCH_MASK_BOOL_IGNORED   0
+#define DG_BATCH_MASK_FLOAT_POSITIVE 1
+int dg_batch_prep(const uint8_t* packed, size_t packed_bytes, const int32_t* records_host, const int32_t* tables_host,
+                  const void* params, int32_t n_records, int32_t N, int32_t H, int32_t W, const float* mean, const float* stdv,
+                  float* img, int64_t* label, void* mask, float* depth, dg_stream_t stream);
 
 /* Measurement aid: name of the kernel the fused correlation launch of this descriptor runs ("k_corr2": the one-wave-per-SIMD
  * form of dg_corr2.hip, "k_corr_main": the general form), decided by the same predicate the launch uses; NULL on a bad desc. */
