@@ -8,7 +8,7 @@ LIB_PATH = os.environ.get("DEPTHG_LIB") or os.path.join(_HERE, "lib", "libdepthg
 
 DG_OUT_COUNT = 9
 DG_OUT_TOTAL = 8
-DG_VERSION = 118                     # must match include/depthg_corr.h: a stale library is refused
+DG_VERSION = 119                     # must match include/depthg_corr.h: a stale library is refused
 DG_POINTWISE, DG_ZERO_CLAMP, DG_STABALIZE, DG_DEPTH_TERM, DG_NEED_GRAD, DG_SHARED_COORDS, DG_IDENTITY_GRID, DG_LINE_GRID, \
     DG_EXACT_MASKS, DG_FEATS_UNIT = (1 << i for i in range(10))
 DG_LIN_LAYERNORM, DG_LIN_GELU, DG_LIN_IN_BF16, DG_LIN_OUT_BF16 = 1, 2, 4, 8      # dg_vit_linear_forward flags
@@ -58,8 +58,7 @@ SIGNATURES = {
     "dg_corr_cd_hist": (_I, [cp, i32, i32, vp, i32, f32, f32, vp, vp, _SZ, vp]),
     # samplers
     "dg_fps_workspace_bytes": (_SZ, [i32] * 3),
-    "dg_fps_coords": (_I, [vp] + [i32] * 6 + [vp, vp, vp, _SZ, vp]),
-    "dg_fps_coords_pair": (_I, [vp, vp] + [i32] * 6 + [vp, vp, vp, _SZ, vp]),
+    "dg_fps_coords": (_I, [vp, vp] + [i32] * 6 + [vp, vp, vp, _SZ, vp]),
     "dg_salience_coords": (_I, [vp] + [i32] * 4 + [vp] * 4),
     "dg_simple_depth_coords": (_I, [vp] + [i32] * 6 + [vp] * 4),
     # metrics, LHP, nearest neighbours
@@ -71,9 +70,7 @@ SIGNATURES = {
     "dg_knn_similarities": (_I, [vp, vp, i64, i64, i32, i64, i64, vp, i64, vp]),
     "dg_topk_rows": (_I, [vp, i64, i64, i64, i32, vp, vp, vp]),
     # random draws
-    "dg_super_perms": (_I, [vp, i32, i32, vp, vp]),
-    "dg_super_perms_seeded": (_I, [u64, i32, i32, vp, vp]),
-    "dg_super_perms_state": (_I, [vp, i32, i32, vp, vp]),
+    "dg_super_perms": (_I, [vp, u64, vp, i32, i32, vp, vp]),
     "dg_rand_coords_state": (_I, [vp, i64, vp, vp]),
     "dg_rand_keep_state": (_I, [vp, i64, f32, vp, vp]),
     # wide feature maps
@@ -82,16 +79,11 @@ SIGNATURES = {
     "dg_corr_forward_extnorm": (_I, [cp] + [vp] * 10 + [vp, _SZ, vp]),
     # head and probes
     "dg_head_weights_bytes": (_SZ, [i32] * 2),
-    "dg_head_forward": (_I, [i32] * 4 + [vp] * 10 + [f32] + [vp] * 5),
+    "dg_head_forward": (_I, [i32] * 4 + [vp] * 11 + [f32] + [vp] * 7),
     "dg_head_workspace_bytes": (_SZ, [i32] * 4),
-    "dg_head_backward": (_I, [i32] * 4 + [vp] * 3 + [f32] + [vp] * 10 + [_SZ, vp]),
-    "dg_head_forward_pair": (_I, [i32] * 4 + [vp] * 11 + [f32] + [vp] * 7),
-    "dg_head_backward_pair": (_I, [i32] * 4 + [vp] * 4 + [f32] + [vp] * 11 + [_SZ, vp]),
+    "dg_head_backward": (_I, [i32] * 4 + [vp] * 4 + [f32] + [vp] * 11 + [_SZ, vp]),
     "dg_head_input_workspace_bytes": (_SZ, [i32] * 2),
-    "dg_head_backward_input": (_I, [i32] * 4 + [vp] * 4 + [f32] + [vp] * 3 + [_SZ, vp, vp, _SZ, vp]),
-    "dg_head_backward_input_pair": (_I, [i32] * 4 + [vp] * 4 + [f32] + [vp] * 4 + [_SZ, vp, vp, vp, _SZ, vp]),
-    "dg_head_backward_input_add": (_I, [i32] * 4 + [vp] * 5 + [f32] + [vp] * 4 + [_SZ, vp, vp, _SZ, vp]),
-    "dg_head_backward_input_add_pair": (_I, [i32] * 4 + [vp] * 5 + [f32] + [vp] * 6 + [_SZ, vp, vp, vp, _SZ, vp]),
+    "dg_head_backward_input": (_I, [i32] * 4 + [vp] * 5 + [f32] + [vp] * 6 + [_SZ, vp, vp, vp, _SZ, vp]),
     "dg_head_plan_describe": (_I, [i32] * 4 + [vp]),
     "dg_cluster_lookup_forward": (_I, [vp, vp, f32] + [i32] * 4 + [vp] * 6),
     "dg_cluster_lookup_backward": (_I, [vp, vp, vp, f32, vp] + [i32] * 4 + [vp] * 4),

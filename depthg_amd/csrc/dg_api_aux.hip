@@ -49,27 +49,13 @@ SideStream* side_stream_for(hipStream_t caller) {
     return &ss;
 }
 
-extern "C" int dg_super_perms(const float* keys, int32_t count, int32_t B, int64_t* out, dg_stream_t stream_) {
+// the keys' source: `keys` (explicit), else `state` (the device-resident generator), else `seed`
+extern "C" int dg_super_perms(const float* keys, uint64_t seed, uint64_t* state, int32_t count, int32_t B, int64_t* out, dg_stream_t stream_) {
     if (count < 0 || B < 1 || B > 8192) return fail(DG_ERR_INVALID, "dg_super_perms: count=%d B=%d outside the supported range", count, B);
     if (count == 0) return DG_OK;
-    if (!keys || !out) return fail(DG_ERR_INVALID, "null pointer");
-    DG_HIP(dg_launch_super_perms(keys, 0ull, nullptr, count, B, out, static_cast<hipStream_t>(stream_)));
-    return DG_OK;
-}
-
-extern "C" int dg_super_perms_seeded(uint64_t seed, int32_t count, int32_t B, int64_t* out, dg_stream_t stream_) {
-    if (count < 0 || B < 1 || B > 8192) return fail(DG_ERR_INVALID, "bad super_perm dimensions");
-    if (count == 0) return DG_OK;
+    if (keys && state) return fail(DG_ERR_INVALID, "dg_super_perms: `keys` and `state` are two sources of the same keys: give one");
     if (!out) return fail(DG_ERR_INVALID, "null pointer");
-    DG_HIP(dg_launch_super_perms(nullptr, seed, nullptr, count, B, out, static_cast<hipStream_t>(stream_)));
-    return DG_OK;
-}
-
-extern "C" int dg_super_perms_state(uint64_t* state, int32_t count, int32_t B, int64_t* out, dg_stream_t stream_) {
-    if (count < 0 || B < 1 || B > 8192) return fail(DG_ERR_INVALID, "bad super_perm dimensions");
-    if (count == 0) return DG_OK;
-    if (!out || !state) return fail(DG_ERR_INVALID, "null pointer");
-    DG_HIP(dg_launch_super_perms(nullptr, 0ull, reinterpret_cast<unsigned long long*>(state), count, B, out, static_cast<hipStream_t>(stream_)));
+    DG_HIP(dg_launch_super_perms(keys, seed, reinterpret_cast<unsigned long long*>(state), count, B, out, static_cast<hipStream_t>(stream_)));
     return DG_OK;
 }
 
@@ -197,10 +183,12 @@ extern "C" size_t dg_fps_workspace_bytes(int32_t B, int32_t h, int32_t w) {
     return (size_t)B * h * w * 4 + 256;
 }
 
-static int fps_entry(const float* depth, const float* depth_b, int32_t Ba, int32_t B, int32_t depth_h, int32_t depth_w, int32_t h,
-                     int32_t w, int32_t S, float* out_coords, int32_t* out_inds, void* workspace, size_t workspace_bytes, dg_stream_t stream_) {
-    if (!depth || !out_coords || (Ba < B && !depth_b)) return fail(DG_ERR_INVALID, "null pointer");
-    if (B < 1 || Ba < 1 || h < 1 || w < 1 || S < 1 || depth_h < h || depth_w < w) return fail(DG_ERR_INVALID, "bad FPS dimensions");
+// depth_pos non-null: the B maps of a second tensor behind the first's (the anchors' depth, then the positives'), nB = 2 B maps in all
+extern "C" int dg_fps_coords(const float* depth, const float* depth_pos, int32_t B, int32_t depth_h, int32_t depth_w, int32_t h, int32_t w,
+                             int32_t S, float* out_coords, int32_t* out_inds, void* workspace, size_t workspace_bytes, dg_stream_t stream_) {
+    if (!depth || !out_coords) return fail(DG_ERR_INVALID, "null pointer");
+    const int32_t nB = depth_pos ? 2 * B : B;
+    if (nB < 1 || B < 1 || h < 1 || w < 1 || S < 1 || depth_h < h || depth_w < w) return fail(DG_ERR_INVALID, "bad FPS dimensions");
     if (S * S > h * w) return fail(DG_ERR_INVALID, "cannot sample %d points from a %dx%d map", S * S, h, w);
     if ((size_t)h * w > 4096) return fail(DG_ERR_UNSUPPORTED, "feature map %dx%d too large for the sampler (max 4096 pixels)", h, w);
     // 2*tan(fov/2) with fov = 90 taken in radians (reference quirk, src/modules.py:989,1016), float32 bits
@@ -208,21 +196,9 @@ static int fps_entry(const float* depth, const float* depth_b, int32_t Ba, int32
     float factor;
     memcpy(&factor, &bits, 4);
     // (a workspace that is missing or too small is not an error: the sampler then pools inside its own blocks, one image per CU)
-    float* pooled = (workspace && workspace_bytes >= (size_t)B * h * w * 4) ? static_cast<float*>(workspace) : nullptr;
-    DG_HIP(dg_launch_fps(depth, depth_b, Ba, B, depth_h, depth_w, h, w, S, factor, out_coords, out_inds, pooled, static_cast<hipStream_t>(stream_)));
+    float* pooled = (workspace && workspace_bytes >= (size_t)nB * h * w * 4) ? static_cast<float*>(workspace) : nullptr;
+    DG_HIP(dg_launch_fps(depth, depth_pos, B, nB, depth_h, depth_w, h, w, S, factor, out_coords, out_inds, pooled, static_cast<hipStream_t>(stream_)));
     return DG_OK;
-}
-
-extern "C" int dg_fps_coords(const float* depth, int32_t B, int32_t depth_h, int32_t depth_w, int32_t h, int32_t w,
-                             int32_t S, float* out_coords, int32_t* out_inds, void* workspace, size_t workspace_bytes,
-                             dg_stream_t stream_) {
-    return fps_entry(depth, nullptr, B, B, depth_h, depth_w, h, w, S, out_coords, out_inds, workspace, workspace_bytes, stream_);
-}
-
-extern "C" int dg_fps_coords_pair(const float* depth, const float* depth_pos, int32_t B, int32_t depth_h, int32_t depth_w,
-                                  int32_t h, int32_t w, int32_t S, float* out_coords, int32_t* out_inds, void* workspace,
-                                  size_t workspace_bytes, dg_stream_t stream_) {
-    return fps_entry(depth, depth_pos, B, 2 * B, depth_h, depth_w, h, w, S, out_coords, out_inds, workspace, workspace_bytes, stream_);
 }
 
 // ---- the optimisation step's Adams (dg_optim.hip)

@@ -1417,7 +1417,7 @@ hipError_t dg_launch_head_rowsum(const void* X, bool bf16, float* out, float* ou
 // accumulator holds four consecutive positions of one channel - one 16-byte store, 64 contiguous bytes per channel and quarter wave.
 // Dropout2d as in the forward: a dropped channel is a zeroed weight COLUMN here (the lane's own channel: one mask word per lane), so
 // it comes out as exact 0; 1/(1-p) scales the accumulator.  Every element is written once, by one lane: no atomics.
-// ADD (dg_head_backward_input_add): the epilogue adds s keep3[b][k] gfeats[b][k][p] - the gradient that reached the head's returned
+// ADD (dg_head_backward_input with a grad_feats_out): the epilogue adds s keep3[b][k] gfeats[b][k][p] - the gradient that reached the head's returned
 // feats = Dropout2d(image_feat) - to the element it is about to store; a pass without gfeats adds nothing.
 __global__ __launch_bounds__(256) void k_head_dx_prep(const float* __restrict__ w1, const float* __restrict__ w2a, __bf16* __restrict__ out,
                                                       int C, int D, int KS1, int KS, size_t n) {

@@ -16,7 +16,7 @@ struct DgHeadFwdArgs {
     __bf16* hidden;                        // (B,C,P) bf16: ReLU output saved for the backward, or null
     int32_t B, C, D, P;
     unsigned long long* stamps;            // developer timing stamps (null in production)
-    // two passes of the featurizer in one launch (dg_head_forward_pair: img, then img_pos): images Bs.. of feat / code / feats_out
+    // two passes of the featurizer in one launch (dg_head_forward with feat_pos: img, then img_pos): images Bs.. of feat / code / feats_out
     // live in a second tensor each; d_* = (its base - the first's base) in elements - Bs images, added to the offset of those images
     int32_t Bs;
     long long d_feat, d_code, d_fo;

@@ -913,7 +913,7 @@ __global__ __launch_bounds__(FPS_THREADS) void k_fps_coords(const float* __restr
     __shared__ long long skey[3];
     __shared__ int tie_low;
     const int n = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
-    // (images Ba.. of the launch come from a second tensor: depth and depth_pos of one step, dg_fps_coords_pair)
+    // (images Ba.. of the launch come from a second tensor: depth and depth_pos of one step, dg_fps_coords)
     const float* d = n < Ba ? depth + (size_t)n * H * W : depth_b + (size_t)(n - Ba) * H * W;
     float4* const pts = reinterpret_cast<float4*>(selbits + nwords + ((4 - ((nsel + nwords) & 3)) & 3));   // [HW] {x, y, z, 0}: takes over the staging buffer
 

@@ -43,24 +43,29 @@ def _check_keeps(keeps, rows, C, device, what):
     return tuple(keeps)
 
 
+def _ptr2(ts):
+    """The pointers of a per-pass tensor of the one or two passes in `ts`: the second slot of a single pass is NULL."""
+    return _ptr(ts[0]), _ptr(ts[1] if len(ts) == 2 else None)
+
+
 class _HeadFunction(torch.autograd.Function):
-    """The head on one featurizer pass (dg_head_forward / dg_head_backward) or on both passes of a step (img, img_pos) through ONE
-    set of launches (dg_head_forward_pair / dg_head_backward_pair): the same numbers as two single calls whose weight gradients
-    autograd adds up - without the six additions, with half the launches, and with no concatenated copy of the features.
+    """The head (dg_head_forward / dg_head_backward) on one featurizer pass or on both passes of a step (img, img_pos) through ONE
+    set of launches (the second pass's tensors in the entries' *_pos slots, NULL on a single pass): the same numbers as two single
+    calls whose weight gradients autograd adds up - without the six additions, with half the launches, and with no concatenated
+    copy of the features.
     `feats`: the one or two (B,C,h,w) maps; keeps: (rows, C) each, rows = B per pass, the first pass's first.
     `input_grad`: features that require grad are accepted, and backward returns d loss / d image_feat for each pass that asks
-    (dg_head_backward_input / _pair, one more launch behind the parameter gradients, on their workspace); a pass that does not ask
+    (dg_head_backward_input, one more launch behind the parameter gradients, on their workspace); a pass that does not ask
     gets None and is not walked.  False: such features are refused, as ever.
     `feats_grad` (with input_grad): the returned feats_out = Dropout2d(image_feat) of a pass whose features require grad stays
     differentiable, and what reaches it is added - times keep3 scale - to that pass's d image_feat in the d image_feat launch's
-    epilogue (dg_head_backward_input_add / _pair).  False: feats_out is marked non-differentiable, as ever.
+    epilogue (dg_head_backward_input's grad_feats_out slots).  False: feats_out is marked non-differentiable, as ever.
     -> (code per pass ..., feats_out per pass ... (None unless want_feats))."""
 
     @staticmethod
     def forward(ctx, keeps, scale, want_feats, input_grad, feats_grad, w1, b1, w2a, b2a, w2b, b2b, *feats):
         lib = _lib.load()
         n = len(feats)
-        pair = "_pair" if n == 2 else ""
         fs = [_f32c(t, name) for t, name in zip(feats, ("image_feat", "image_feat_pos"))]
         f = fs[0]
         if n == 2 and (f.shape != fs[1].shape or f.device != fs[1].device):
@@ -79,17 +84,16 @@ class _HeadFunction(torch.autograd.Function):
         codes = [_empty((B, D, h, w), torch.float32, dev) for _ in fs]
         fouts = [_empty((B, C, h, w), torch.float32, dev) if want_feats else None for _ in fs]
         hidden = _empty((n * B, C, P), torch.bfloat16, dev) if (nonlinear and need_grad) else None
-        k1, k2, k3 = _check_keeps(keeps, n * B, C, dev, "ProjectionHead.forward" + pair)
+        k1, k2, k3 = _check_keeps(keeps, n * B, C, dev, "ProjectionHead.forward" + ("_pair" if n == 2 else ""))
         # (weights as (out, in) matrices; None stays None, which the library takes as NULL: projection_type "linear")
         w1c, b1c, w2ac, b2ac, w2bc, b2bc = (_f32c(t, "head parameter") for t in (w1, b1, w2a, b2a, w2b, b2b))
         w1c, w2ac, w2bc = (t.reshape(t.shape[0], -1) if t is not None else None for t in (w1c, w2ac, w2bc))
         wscratch = _empty((lib.dg_head_weights_bytes(C, D),), torch.uint8, dev)     # bf16 copies of the weights (first launch)
-        entry = "dg_head_forward" + pair
-        rc = getattr(lib, entry)(B, C, D, P, *map(_ptr, fs), _ptr(w1c), _ptr(b1c), _ptr(w2ac), _ptr(b2ac), _ptr(w2bc), _ptr(b2bc),
-                                 _ptr(k1), _ptr(k2), _ptr(k3), float(scale), *map(_ptr, codes), *map(_ptr, fouts), _ptr(hidden),
+        rc = lib.dg_head_forward(B, C, D, P, *_ptr2(fs), _ptr(w1c), _ptr(b1c), _ptr(w2ac), _ptr(b2ac), _ptr(w2bc), _ptr(b2bc),
+                                 _ptr(k1), _ptr(k2), _ptr(k3), float(scale), *_ptr2(codes), *_ptr2(fouts), _ptr(hidden),
                                  _ptr(wscratch), _stream(dev))
-        _lib.check(rc, entry)
-        ctx.dims, ctx.scale, ctx.nonlinear, ctx.pair = (B, C, D, P), float(scale), nonlinear, pair
+        _lib.check(rc, "dg_head_forward")
+        ctx.dims, ctx.scale, ctx.nonlinear = (B, C, D, P), float(scale), nonlinear
         ctx.shapes = tuple(t.shape if t is not None else None for t in (w1, b1, w2a, b2a, w2b, b2b))
         ctx.hw = (h, w)
         # (the fp32 weight matrices: what the d image_feat launch makes its transposed copies from)
@@ -123,11 +127,10 @@ class _HeadFunction(torch.autograd.Function):
         if ctx.nonlinear:
             gw2a, gb2a = _empty((C, C), torch.float32, dev), _empty((C,), torch.float32, dev)
             gw2b, gb2b = _empty((D, C), torch.float32, dev), _empty((D,), torch.float32, dev)
-        entry = "dg_head_backward" + ctx.pair
-        rc = getattr(lib, entry)(B, C, D, P, *map(_ptr, fs), _ptr(k1), _ptr(k2), ctx.scale, _ptr(hidden), _ptr(wscratch),
-                                 *map(_ptr, gs), _ptr(gw1), _ptr(gb1), _ptr(gw2a), _ptr(gb2a), _ptr(gw2b), _ptr(gb2b), _ptr(ws), nb,
-                                 _stream(dev))
-        _lib.check(rc, entry)
+        rc = lib.dg_head_backward(B, C, D, P, *_ptr2(fs), _ptr(k1), _ptr(k2), ctx.scale, _ptr(hidden), _ptr(wscratch),
+                                  *_ptr2(gs), _ptr(gw1), _ptr(gb1), _ptr(gw2a), _ptr(gb2a), _ptr(gw2b), _ptr(gb2b), _ptr(ws), nb,
+                                  _stream(dev))
+        _lib.check(rc, "dg_head_backward")
         gparams = (gw1, gb1, gw2a, gb2a, gw2b, gb2b)
         gfs = [None] * n
         if ctx.want_dx:
@@ -137,15 +140,9 @@ class _HeadFunction(torch.autograd.Function):
             iws = _empty(nbi, torch.uint8, dev)
             # what reached each pass's feats_out (None: nothing, or that output was not differentiable)
             gfo = [_f32c(g, "grad_feats") if (g is not None and diff) else None for g, diff in zip(grads[n:2 * n], ctx.feats_diff)]
-            if any(g is not None for g in gfo):
-                entry = "dg_head_backward_input_add" + ctx.pair
-                rc = getattr(lib, entry)(B, C, D, P, _ptr(w1c), _ptr(w2ac), _ptr(k1), _ptr(k2), _ptr(k3), ctx.scale, _ptr(hidden),
-                                         *map(_ptr, gs), *map(_ptr, gfo), _ptr(ws), nb, *map(_ptr, gfs), _ptr(iws), nbi, _stream(dev))
-            else:
-                entry = "dg_head_backward_input" + ctx.pair
-                rc = getattr(lib, entry)(B, C, D, P, _ptr(w1c), _ptr(w2ac), _ptr(k1), _ptr(k2), ctx.scale, _ptr(hidden), *map(_ptr, gs),
-                                         _ptr(ws), nb, *map(_ptr, gfs), _ptr(iws), nbi, _stream(dev))
-            _lib.check(rc, entry)
+            rc = lib.dg_head_backward_input(B, C, D, P, _ptr(w1c), _ptr(w2ac), _ptr(k1), _ptr(k2), _ptr(k3), ctx.scale, _ptr(hidden),
+                                            *_ptr2(gs), *_ptr2(gfo), _ptr(ws), nb, *_ptr2(gfs), _ptr(iws), nbi, _stream(dev))
+            _lib.check(rc, "dg_head_backward_input")
         return (None, None, None, None, None) + tuple(g.reshape(sh) if g is not None else None for g, sh in zip(gparams, ctx.shapes)) + tuple(gfs)
 
 

@@ -688,38 +688,35 @@ def depth_encoder_backward(depth, params, grad_out, out=None):
     return out
 
 
-def fps_coords(depth, feat_hw, n_samples, return_inds=False):
-    """depth (B,1,H,W) on GPU -> coords (B,S,S,2) in [-1,1) (already *2-1)."""
+def _fps(depth, depth_pos, feat_hw, n_samples, return_inds):
+    """dg_fps_coords on the B maps of `depth` and - not None - on the B of `depth_pos` behind them."""
     lib = _lib.load()
-    depth = _f32c(depth, "depth")
     B, _, H, W = depth.shape
+    nB = B if depth_pos is None else 2 * B
     h, w = int(feat_hw[0]), int(feat_hw[1])
     S = int(n_samples)
-    coords = _empty((B, S, S, 2), torch.float32, depth.device)
-    inds = _empty((B, S * S), torch.int32, depth.device) if return_inds else None
-    ws = _empty((lib.dg_fps_workspace_bytes(B, h, w)), torch.uint8, depth.device)
-    rc = lib.dg_fps_coords(_ptr(depth), B, H, W, h, w, S, _ptr(coords), _ptr(inds), _ptr(ws), ws.numel(),
+    coords = _empty((nB, S, S, 2), torch.float32, depth.device)
+    inds = _empty((nB, S * S), torch.int32, depth.device) if return_inds else None
+    ws = _empty((lib.dg_fps_workspace_bytes(nB, h, w)), torch.uint8, depth.device)         # the pooled depth maps
+    rc = lib.dg_fps_coords(_ptr(depth), _ptr(depth_pos), B, H, W, h, w, S, _ptr(coords), _ptr(inds), _ptr(ws), ws.numel(),
                            _stream(depth.device))
     _lib.check(rc, "dg_fps_coords")
     return (coords, inds) if return_inds else coords
 
 
+def fps_coords(depth, feat_hw, n_samples, return_inds=False):
+    """depth (B,1,H,W) on GPU -> coords (B,S,S,2) in [-1,1) (already *2-1)."""
+    return _fps(_f32c(depth, "depth"), None, feat_hw, n_samples, return_inds)
+
+
 def fps_coords_pair(depth, depth_pos, feat_hw, n_samples):
-    """The two FPS calls of one step in one launch (dg_fps_coords_pair): depth, depth_pos (B,1,H,W) -> coords (2B,S,S,2), rows
-    [0,B) the anchors', [B,2B) the positives'."""
-    lib = _lib.load()
+    """The two FPS calls of one step in one launch (dg_fps_coords with depth_pos): depth, depth_pos (B,1,H,W) -> coords (2B,S,S,2),
+    rows [0,B) the anchors', [B,2B) the positives'."""
     depth, depth_pos = _f32c(depth, "depth"), _f32c(depth_pos, "depth_pos")
     if depth.shape != depth_pos.shape or depth.device != depth_pos.device:
         raise ValueError(f"depthg_amd: depth {tuple(depth.shape)} on {depth.device} and depth_pos {tuple(depth_pos.shape)} on "
                          f"{depth_pos.device} must match for the paired sampler")
-    B, _, H, W = depth.shape
-    h, w = int(feat_hw[0]), int(feat_hw[1])
-    S = int(n_samples)
-    coords = _empty((2 * B, S, S, 2), torch.float32, depth.device)
-    ws = _empty((lib.dg_fps_workspace_bytes(2 * B, h, w)), torch.uint8, depth.device)      # the pooled depth maps of both calls
-    rc = lib.dg_fps_coords_pair(_ptr(depth), _ptr(depth_pos), B, H, W, h, w, S, _ptr(coords), None, _ptr(ws), ws.numel(), _stream(depth.device))
-    _lib.check(rc, "dg_fps_coords_pair")
-    return coords
+    return _fps(depth, depth_pos, feat_hw, n_samples, False)
 
 
 def salience_coords(salience, n_side, u_sel=None, u_fallback=None):
@@ -1255,15 +1252,10 @@ def super_perms(count, size, device, keys=None, state=None):
         return out
     if state is not None:
         _check_state(state, "super_perms", out.device)
-        rc = lib.dg_super_perms_state(_ptr(state), int(count), int(size), _ptr(out), _stream(out.device))
-        _lib.check(rc, "dg_super_perms_state")
-        return out
-    if keys is None:
-        # one launch: the keys are drawn inside the kernel (Philox) from a seed of torch's CPU generator
-        rc = lib.dg_super_perms_seeded(_cpu_seed(), int(count), int(size), _ptr(out), _stream(out.device))
-        _lib.check(rc, "dg_super_perms_seeded")
-        return out
-    rc = lib.dg_super_perms(_ptr(keys), int(count), int(size), _ptr(out), _stream(out.device))
+        keys = None                              # (the state decides, as ever)
+    # neither: the keys are drawn inside the kernel (Philox) from a seed of torch's CPU generator, still one launch
+    seed = _cpu_seed() if state is None and keys is None else 0
+    rc = lib.dg_super_perms(_ptr(keys), seed, _ptr(state), int(count), int(size), _ptr(out), _stream(out.device))
     _lib.check(rc, "dg_super_perms")
     return out
 

@@ -45,7 +45,7 @@ cfg.dg_dino_backbone, StandInFeaturizerWithDepth otherwise - cfg.guidance choose
 is forced on, the step feeds (img, depth) / (img_pos, depth_pos) one pass at a time and net_optim steps the depth modules the guidance
 trains with the head (the head's d image_feat launch, dg_head_backward_input, carries the gradient to them).  There cfg.rec_weight > 0
 under guidance "sum" / "cross_attn" needs cfg.dg_rec_feats_grad: the reconstruction term then reads the first pass's attached feats, its
-backward writes d feats (dg_rec_feats_backward) and the head adds it into d image_feat (dg_head_backward_input_add).
+backward writes d feats (dg_rec_feats_backward) and the head adds it into d image_feat (dg_head_backward_input's grad_feats_out).
 """
 from types import SimpleNamespace
 from typing import Dict, Optional

@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define DG_VERSION 118   /* 118: dg_corr_forward_intra_feats + dg_corr_workspace_bytes_intra_feats, dg_corr_cd_hist, the three dg_crfloss the three dg_augalign entry points and dg_batch_prep (more exports under the same number: the layouts and meanings of every earlier entry point are unchanged, and a binding that declares a new symbol refuses a library without it when it loads), dg_sampled_sumsq, dg_corr_forward_extnorm (feature maps wider than 768 channels on SAMPLED grids above 160 positions, in channel chunks); 117: DG_FEATS_UNIT, dg_normalize_split (feature maps wider than 768 channels on the dense identity grid, in chunks of the width the operand kernels hold: the loss is linear in the feature correlation); 116: dg_prof_main_span takes FOUR words (+ the workgroups' lifetimes in shader cycles and wall ticks: the clock the CUs held); 115: dg_corr_intra_folded; 114: dg_fps_coords_pair takes a workspace (dg_fps_workspace_bytes(2 B, h, w): the pooled depth maps, written by a launch over the whole chip in front of the sampler), dg_corr_materialize_shared, dg_prof_main_span (the fused correlation launch's execution span inside a replayed step), sample grids of <= 160 positions at any feature width (fused small-grid kernel); 113: dg_corr_forward_masked; 112: dg_rand_coords_state; 111: dg_head_forward_pair / dg_head_backward_pair; 110: dg_fps_coords_pair; 109: dg_knn_similarities; 108: dg_corr_desc.code_h / code_w (code maps of another resolution than the feature maps: the FeaturePyramidNet producer, src/modules.py:732-766), dg_corr_desc.flags DG_EXACT_MASKS; 107: dg_head_*, dg_cluster_lookup_*, dg_probe_ce_*; 106: dg_corr_main_kernel_name; 105: dg_corr_forward_draw; 104: dg_lhp_map_forward / dg_lhp_map_backward; 103: dg_super_perms_state; 102: DG_LINE_GRID, dg_salience_coords, dg_simple_depth_coords; 101: total weights, DG_OUT_TOTAL */
+#define DG_VERSION 119   /* 119: one entry per operation where a NULL pointer already told the variants apart - dg_head_forward / dg_head_backward / dg_head_backward_input take the second pass's tensors (NULL: one pass) and the input gradient its optional feats_out addend, dg_fps_coords takes depth_pos, dg_super_perms takes keys, seed and state; the eight entries these replace are gone, nothing is computed differently; 118: dg_corr_forward_intra_feats + dg_corr_workspace_bytes_intra_feats, dg_corr_cd_hist, the three dg_crfloss the three dg_augalign entry points and dg_batch_prep (more exports under the same number: the layouts and meanings of every earlier entry point are unchanged, and a binding that declares a new symbol refuses a library without it when it loads), dg_sampled_sumsq, dg_corr_forward_extnorm (feature maps wider than 768 channels on SAMPLED grids above 160 positions, in channel chunks); 117: DG_FEATS_UNIT, dg_normalize_split (feature maps wider than 768 channels on the dense identity grid, in chunks of the width the operand kernels hold: the loss is linear in the feature correlation); 116: dg_prof_main_span takes FOUR words (+ the workgroups' lifetimes in shader cycles and wall ticks: the clock the CUs held); 115: dg_corr_intra_folded; 114: the two-tensor FPS call takes a workspace (dg_fps_workspace_bytes(2 B, h, w): the pooled depth maps, written by a launch over the whole chip in front of the sampler), dg_corr_materialize_shared, dg_prof_main_span (the fused correlation launch's execution span inside a replayed step), sample grids of <= 160 positions at any feature width (fused small-grid kernel); 113: dg_corr_forward_masked; 112: dg_rand_coords_state; 111: the head on both featurizer passes in one set of launches; 110: FPS on both depth tensors in one launch; 109: dg_knn_similarities; 108: dg_corr_desc.code_h / code_w (code maps of another resolution than the feature maps: the FeaturePyramidNet producer, src/modules.py:732-766), dg_corr_desc.flags DG_EXACT_MASKS; 107: dg_head_*, dg_cluster_lookup_*, dg_probe_ce_*; 106: dg_corr_main_kernel_name; 105: dg_corr_forward_draw; 104: dg_lhp_map_forward / dg_lhp_map_backward; 103: super_perms from a device-resident generator state; 102: DG_LINE_GRID, dg_salience_coords, dg_simple_depth_coords; 101: total weights, DG_OUT_TOTAL */
 
 /* flags of dg_corr_desc.flags (names follow the cfg keys read at src/modules.py:1236-1352) */
 #define DG_POINTWISE      (1u << 0)  /* cfg.pointwise: spatial centering of fd (modules.py:1236-1239) */
@@ -141,7 +141,7 @@ int dg_corr_forward(const dg_corr_desc* desc,
 /*
  * dg_corr_forward that also DRAWS the negatives' batch maps - the `super_perm` calls at the top of the reference's negative
  * loop (src/modules.py:1184-1188, 1340-1342) happen inside the forward there too.  perms_out (n_neg, B) is written (the same
- * values dg_super_perms_seeded(seed) / dg_super_perms_state(perm_state) would write: perm_state non-NULL selects the
+ * values dg_super_perms with that seed / that state would write: perm_state non-NULL selects the
  * device-resident generator and advances it, else `seed`) and must be handed to dg_corr_backward / dg_corr_materialize.  On
  * the identity grid the draw rides in the first launch of the forward (no launch of its own); with general coordinates, whose
  * first launch already reads the maps, it is launched first.
@@ -283,22 +283,19 @@ int dg_corr_cd_hist(const dg_corr_desc* desc, int32_t first, int32_t count, cons
  * back-projection with fov=90 (radians, quirk Q5), farthest point sampling of S*S points starting
  * at index 0, re-emitted in row-major order.
  *  depth      : fp32 (B,1,depth_h,depth_w)
- *  out_coords : fp32 (B,S,S,2), already mapped *2-1 as the caller does (modules.py:1305-1308)
- *  out_inds   : int32 (B,S*S) selection order (may be NULL)
- *  workspace  : >= dg_fps_workspace_bytes(B,h,w) bytes
+ *  depth_pos  : NULL, or a second tensor like depth: the two calls of one step (src/modules.py:1304-1308: the anchors' depth, then
+ *               the positives') as one launch over 2B maps - the sampler is sequential per image, so both run side by side on twice as
+ *               many CUs and the caller needs no concatenated copy
+ *  out_coords : fp32 (B,S,S,2), already mapped *2-1 as the caller does (modules.py:1305-1308); with depth_pos (2B,S,S,2): [0,B) from
+ *               depth, [B,2B) from depth_pos
+ *  out_inds   : int32 (B,S*S) - (2B,S*S) with depth_pos - selection order (may be NULL)
+ *  workspace  : >= dg_fps_workspace_bytes(B,h,w) bytes, of (2B,h,w) with depth_pos (the pooled depth maps, written by a launch over
+ *               the whole chip in front of the sampler)
  */
 size_t dg_fps_workspace_bytes(int32_t B, int32_t h, int32_t w);
-int dg_fps_coords(const float* depth, int32_t B, int32_t depth_h, int32_t depth_w,
-                  int32_t h, int32_t w, int32_t S,
-                  float* out_coords, int32_t* out_inds,
+int dg_fps_coords(const float* depth, const float* depth_pos, int32_t B, int32_t depth_h, int32_t depth_w,
+                  int32_t h, int32_t w, int32_t S, float* out_coords, int32_t* out_inds,
                   void* workspace, size_t workspace_bytes, dg_stream_t stream);
-/* The two calls of one step (src/modules.py:1304-1308: the anchors' depth, then the positives') as one launch: the sampler
- * is sequential per image, so both run side by side on twice as many CUs and the caller needs no concatenated copy.
- * depth, depth_pos : fp32 (B,1,depth_h,depth_w) each;  out_coords (2B,S,S,2): [0,B) from depth, [B,2B) from depth_pos;
- * out_inds int32 (2B,S*S) or NULL.  (version 110) */
-int dg_fps_coords_pair(const float* depth, const float* depth_pos, int32_t B, int32_t depth_h, int32_t depth_w,
-                       int32_t h, int32_t w, int32_t S, float* out_coords, int32_t* out_inds,
-                       void* workspace, size_t workspace_bytes, dg_stream_t stream);
 
 /*
  * Salience-guided sample locations (replaces sample_nonzero_locations, src/modules.py:1191-1204, the cfg.use_salience
@@ -407,21 +404,19 @@ int dg_topk_rows(const float* vals, int64_t rows, int64_t cols, int64_t row_stri
 /*
  * Negative-pair batch permutations (replaces super_perm, src/modules.py:1184-1188, called n_neg times per step at
  * :1336-1339): `count` independent uniform random permutations of 0..B-1 with fixed points bumped by one modulo B
- * (quirk Q6: B == 1 gives [0]).  The randomness comes from the caller: `keys` holds count*B iid uniforms (torch.rand);
- * row r of the result is the argsort of row r of the keys (ties by index), which is a uniform random permutation
- * like torch.randperm.
- *  keys : fp32 (count, B)      out : int64 (count, B)      B <= 8192
+ * (quirk Q6: B == 1 gives [0]).  Row r of the result is the argsort of row r of count*B iid uniform keys (ties by index), which is
+ * a uniform random permutation like torch.randperm.  The keys come from one of three sources:
+ *  keys  : fp32 (count, B) from the caller (torch.rand), or NULL
+ *  state : NULL, or the generator state ON THE DEVICE = {seed, draws so far, 0} (three 64-bit words owned by the caller, zero the
+ *          third): key(r, i) = Philox4x32-10({seed, draws}; counter r*B + i) >> 8 as a float in [0,1), drawn inside the launch, which
+ *          advances `draws` on the device.  Nothing about the draw is baked into the launch, so a call recorded in a hipGraph
+ *          (torch.cuda.graph around the training step) yields new permutations on every replay - the reference draws them with the
+ *          device generator at the same place, src/modules.py:1184-1188,1336-1339.  keys and state together are refused.
+ *  seed  : with neither: the same Philox draw keyed by this 64-bit value, fresh per call from the caller's own RNG - one launch per
+ *          step instead of rand + sort
+ *  out   : int64 (count, B)      B <= 8192; count == 0 returns DG_OK and looks at no pointer
  */
-int dg_super_perms(const float* keys, int32_t count, int32_t B, int64_t* out, dg_stream_t stream);
-/* Same, with the keys drawn inside the launch: key(r, i) = Philox4x32-10(seed; counter r*B + i) >> 8, as a float in [0,1).
- * The caller supplies a fresh 64-bit seed per call (from its own RNG): one launch per step instead of rand + sort. */
-int dg_super_perms_seeded(uint64_t seed, int32_t count, int32_t B, int64_t* out, dg_stream_t stream);
-/* The same draws with the generator state ON THE DEVICE: state = {seed, draws so far, 0} (three 64-bit words owned by the
- * caller, zero the third); every call uses {seed, draws} as the Philox key and advances `draws` on the device.  Nothing
- * about the draw is baked into the launch, so a call recorded in a hipGraph (torch.cuda.graph around the training step)
- * yields new permutations on every replay - the reference draws them with the device generator at the same place,
- * src/modules.py:1184-1188,1336-1339. */
-int dg_super_perms_state(uint64_t* state, int32_t count, int32_t B, int64_t* out, dg_stream_t stream);
+int dg_super_perms(const float* keys, uint64_t seed, uint64_t* state, int32_t count, int32_t B, int64_t* out, dg_stream_t stream);
 /* The random sample coordinates of a step (`torch.rand(B, S, S, 2) * 2 - 1` for coords1 and coords2, src/modules.py:1310-1321) from
  * the same device-resident generator: n floats in [-1, 1) into `out`, one launch for both coordinate sets; advances the state.  For
  * steps recorded in a hipGraph (cfg.dg_graph_safe), where torch's generator costs two launches per tensor and two fills per replay;
@@ -467,100 +462,79 @@ int dg_corr_forward_extnorm(const dg_corr_desc* desc, const float* orig_feats, c
  * fp32 accumulation, Dropout2d and ReLU fused (a dropped channel is a zeroed weight column, 1/(1-p) scales the accumulator),
  * the fp32 features read once.
  *  feat                 : fp32 (B,C,P), P = h*w, C <= 768 and a multiple of 8
+ *  feat_pos             : NULL, or the second featurizer pass of a training step (src/train_segmentation.py:303-306: `self.net(img)`,
+ *                         then `self.net(img_pos)`, with the same weights), fp32 (B,C,P): the call then covers both passes as if they
+ *                         were one batch of 2B images - one launch per kernel instead of two, no concatenated copy of the features.
+ *                         The second pass exists exactly when feat_pos is given: keep1/2/3 and hidden are then (2B, ...), the first
+ *                         pass's B rows first; B <= 2^20.  Without it code_pos and feats_out_pos must be NULL
  *  w1,b1                : cluster1[0].weight (D,C), .bias (D); D <= 128
  *  w2a,b2a,w2b,b2b      : cluster2[0] (C,C),(C) and cluster2[2] (D,C),(D); all NULL for projection_type "linear"
  *  keep1,keep2,keep3    : fp32 (B,C) 1 = keep / 0 = drop: the three Dropout2d draws in the reference's order (cluster1's
  *                         input, cluster2's input, the returned feats); NULL = no dropout for that use (eval mode)
  *  keep_scale           : 1/(1-p)
- *  code                 : fp32 (B,D,P) out
- *  feats_out            : fp32 (B,C,P) out = feat * keep3 * keep_scale, or NULL
+ *  code, code_pos       : fp32 (B,D,P) out, one tensor per pass
+ *  feats_out(_pos)      : fp32 (B,C,P) out = feat * keep3 * keep_scale per pass, or NULL (for both passes or neither)
  *  hidden               : bf16 (B,C,P) out: cluster2's ReLU output, needed by dg_head_backward; may be NULL without one
  *  wscratch             : dg_head_weights_bytes(C, D) bytes: the forward leaves the bf16 copies of the weight matrices there
  *                         (its first launch); dg_head_backward reads them - keep the buffer until then
  */
 size_t dg_head_weights_bytes(int32_t C, int32_t D);
-int dg_head_forward(int32_t B, int32_t C, int32_t D, int32_t P, const float* feat,
+int dg_head_forward(int32_t B, int32_t C, int32_t D, int32_t P, const float* feat, const float* feat_pos,
                     const float* w1, const float* b1, const float* w2a, const float* b2a, const float* w2b, const float* b2b,
                     const float* keep1, const float* keep2, const float* keep3, float keep_scale,
-                    float* code, float* feats_out, void* hidden, void* wscratch, dg_stream_t stream);
-/* Bytes of scratch dg_head_backward needs (d hidden + the split partial sums of the three weight gradients). */
+                    float* code, float* code_pos, float* feats_out, float* feats_out_pos, void* hidden, void* wscratch,
+                    dg_stream_t stream);
+/* Bytes of scratch dg_head_backward needs (d hidden + the split partial sums of the three weight gradients) for B images in all:
+ * pass 2 B for a call with a second pass. */
 size_t dg_head_workspace_bytes(int32_t B, int32_t C, int32_t D, int32_t P);
 /*
- * Gradients of the six head tensors from grad_code (B,D,P) (the backbone is frozen: nothing flows into feat).  Same feat /
+ * Gradients of the six head tensors from grad_code (B,D,P) (the backbone is frozen: nothing flows into feat).  Same feat / feat_pos /
  * keep1 / keep2 / keep_scale / hidden / wscratch as the forward.  grad_* : fp32, shapes of the parameters, overwritten; pass the
  * four cluster2 ones (and hidden) as NULL for projection_type "linear".  Bit-reproducible (no floating-point atomics).
+ * With feat_pos: grad_code_pos (B,D,P) is the second pass's upstream (NULL without feat_pos), the weight gradients come out summed
+ * over both passes (what autograd's accumulation of two calls yields), and the workspace is dg_head_workspace_bytes(2 B, C, D, P).
  */
-int dg_head_backward(int32_t B, int32_t C, int32_t D, int32_t P, const float* feat, const float* keep1, const float* keep2,
-                     float keep_scale, const void* hidden, const void* wscratch, const float* grad_code,
-                     float* grad_w1, float* grad_b1, float* grad_w2a, float* grad_b2a, float* grad_w2b, float* grad_b2b,
-                     void* workspace, size_t workspace_bytes, dg_stream_t stream);
-
-/*
- * Both featurizer passes of a training step in one set of launches (src/train_segmentation.py:303-306: `self.net(img)`, then
- * `self.net(img_pos)`, with the same weights): B images from feat, B from feat_pos, as if they were one batch of 2B - the weight
- * gradients come out summed over both passes (what autograd's accumulation of the two calls yields), one launch per kernel
- * instead of two, no concatenated copy of the features.  keep1/2/3, hidden: (2B, ...), the first pass's B rows first.
- * code / code_pos, feats_out / feats_out_pos, grad_code / grad_code_pos: separate (B, ...) tensors.  The backward's workspace:
- * dg_head_workspace_bytes(2 B, C, D, P).  (version 111)
- */
-int dg_head_forward_pair(int32_t B, int32_t C, int32_t D, int32_t P, const float* feat, const float* feat_pos,
-                         const float* w1, const float* b1, const float* w2a, const float* b2a, const float* w2b, const float* b2b,
-                         const float* keep1, const float* keep2, const float* keep3, float keep_scale,
-                         float* code, float* code_pos, float* feats_out, float* feats_out_pos, void* hidden, void* wscratch,
-                         dg_stream_t stream);
-int dg_head_backward_pair(int32_t B, int32_t C, int32_t D, int32_t P, const float* feat, const float* feat_pos, const float* keep1,
-                          const float* keep2, float keep_scale, const void* hidden, const void* wscratch, const float* grad_code,
-                          const float* grad_code_pos, float* grad_w1, float* grad_b1, float* grad_w2a, float* grad_b2a,
-                          float* grad_w2b, float* grad_b2b, void* workspace, size_t workspace_bytes, dg_stream_t stream);
+int dg_head_backward(int32_t B, int32_t C, int32_t D, int32_t P, const float* feat, const float* feat_pos, const float* keep1,
+                     const float* keep2, float keep_scale, const void* hidden, const void* wscratch, const float* grad_code,
+                     const float* grad_code_pos, float* grad_w1, float* grad_b1, float* grad_w2a, float* grad_b2a,
+                     float* grad_w2b, float* grad_b2b, void* workspace, size_t workspace_bytes, dg_stream_t stream);
 
 /*
  * d loss / d image_feat of the head (opt-in: the reference's DinoFeaturizer runs its backbone under no_grad, src/modules.py:96, but
  * DinoFeaturizerWithDepth feeds the head `image_depth_feat`, which its trainable depth modules produced, src/modules.py:574-597, so
  * autograd carries the gradient through cluster1 / cluster2 and their Dropout2d, :599-600, into it):
  *     grad_feat[b,k,p] = keep_scale keep1[b,k] sum_d W1[d,k] grad_code[b,d,p] + keep_scale keep2[b,k] sum_j W2a[j,k] dh[b,j,p]
- * with dh = d hidden as dg_head_backward formed it.  Call it AFTER dg_head_backward (_pair) with the same B, C, D, P, keep1, keep2,
- * keep_scale, hidden, grad_code, workspace and stream: d hidden is read from that workspace, in the layout its plan chose.  bf16 MFMA
- * operands (grad_code rounded on load), fp32 accumulation; every element of grad_feat is written once (no atomics: bit-reproducible),
- * a dropped channel is exact 0.  The third Dropout2d draw (feats_out) takes no part: the loss reads feats under no_grad, :1232-1234.
+ * with dh = d hidden as dg_head_backward formed it.  Call it AFTER dg_head_backward with the same B, C, D, P, keep1, keep2,
+ * keep_scale, hidden, grad_code (_pos), workspace and stream: d hidden is read from that workspace, in the layout its plan chose.  bf16
+ * MFMA operands (grad_code rounded on load), fp32 accumulation; every element of grad_feat is written once (no atomics:
+ * bit-reproducible), a dropped channel is exact 0.
  *  w1, w2a              : the fp32 parameters (D,C), (C,C); w2a NULL for projection_type "linear" (hidden, workspace then unused)
- *  grad_feat            : fp32 (B,C,P) out
+ *  grad_code_pos        : NULL, or the second pass's upstream: the second pass exists exactly when it is given, and the call walks the
+ *                         2B images of such a dg_head_backward (keep1/2/3 (2B,C); B <= 2^20).  Without it grad_feats_out_pos and
+ *                         grad_feat_pos must be NULL
+ *  grad_feat(_pos)      : fp32 (B,C,P) out per pass; with two passes one of them may be NULL (not both): that pass's images are then
+ *                         not computed
  *  input_workspace      : dg_head_input_workspace_bytes(C, D) bytes (the transposed bf16 weight copies, written by this call)
- * The pair form walks the 2B images of dg_head_backward_pair; grad_feat or grad_feat_pos may be NULL (not both): that pass's images
- * are then not computed.
+ * The third Dropout2d draw (feats_out) takes no part while the loss reads feats under no_grad, :1232-1234.  Where it reads the
+ * attached feats_out = Dropout2d(image_feat) (opt-in on top of the opt-in: under DinoFeaturizerWithDepth the reconstruction term does,
+ * src/modules.py:596-598 and src/train_segmentation.py:391-398), the gradient that reached them is added in the launch's epilogue, to
+ * the element about to be stored:
+ *     grad_feat[b,k,p] = (the sum above) + keep_scale keep3[b,k] grad_feats_out[b,k,p]
+ *  keep3                : the third Dropout2d draw's flags fp32 (B,C) - (2B,C) with two passes - or NULL (no mask: factor 1)
+ *  grad_feats_out(_pos) : fp32 (B,C,P) per pass, 16-byte aligned, or NULL: nothing is added for that pass (NULL for every pass, and
+ *                         keep3 NULL: the plain input gradient, the same launches and bits).  A pass with grad_feats_out must have
+ *                         its grad_feat.
+ * fp32 addend on the fp32 accumulator; a channel keep3 dropped adds an exact 0; still one store per element, no atomics.
  */
 size_t dg_head_input_workspace_bytes(int32_t C, int32_t D);
 int dg_head_backward_input(int32_t B, int32_t C, int32_t D, int32_t P, const float* w1, const float* w2a, const float* keep1,
-                           const float* keep2, float keep_scale, const void* hidden, const float* grad_code,
-                           const void* workspace, size_t workspace_bytes, float* grad_feat,
-                           void* input_workspace, size_t input_workspace_bytes, dg_stream_t stream);
-int dg_head_backward_input_pair(int32_t B, int32_t C, int32_t D, int32_t P, const float* w1, const float* w2a, const float* keep1,
-                                const float* keep2, float keep_scale, const void* hidden, const float* grad_code,
-                                const float* grad_code_pos, const void* workspace, size_t workspace_bytes, float* grad_feat,
-                                float* grad_feat_pos, void* input_workspace, size_t input_workspace_bytes, dg_stream_t stream);
+                           const float* keep2, const float* keep3, float keep_scale, const void* hidden,
+                           const float* grad_code, const float* grad_code_pos, const float* grad_feats_out,
+                           const float* grad_feats_out_pos, const void* workspace, size_t workspace_bytes, float* grad_feat,
+                           float* grad_feat_pos, void* input_workspace, size_t input_workspace_bytes, dg_stream_t stream);
 
 /*
- * dg_head_backward_input (_pair) plus the gradient that reached the head's returned feats_out = Dropout2d(image_feat) (opt-in on top
- * of the opt-in: under DinoFeaturizerWithDepth the reconstruction term reads the attached feats, src/modules.py:596-598 and
- * src/train_segmentation.py:391-398), added in the launch's epilogue, to the element about to be stored:
- *     grad_feat[b,k,p] = (the sum above) + keep_scale keep3[b,k] grad_feats_out[b,k,p]
- * Same launches, same call order and same arguments as dg_head_backward_input (_pair), and:
- *  keep3                : the third Dropout2d draw's flags fp32 (B,C) - (2B,C) in the pair form - or NULL (no mask: factor 1)
- *  grad_feats_out       : fp32 (B,C,P), 16-byte aligned, or NULL: nothing is added for that pass (NULL for every pass: the bits
- *                         of dg_head_backward_input).  A pass with grad_feats_out must have its grad_feat.
- * fp32 addend on the fp32 accumulator; a channel keep3 dropped adds an exact 0; still one store per element, no atomics.
- */
-int dg_head_backward_input_add(int32_t B, int32_t C, int32_t D, int32_t P, const float* w1, const float* w2a, const float* keep1,
-                               const float* keep2, const float* keep3, float keep_scale, const void* hidden, const float* grad_code,
-                               const float* grad_feats_out, const void* workspace, size_t workspace_bytes, float* grad_feat,
-                               void* input_workspace, size_t input_workspace_bytes, dg_stream_t stream);
-int dg_head_backward_input_add_pair(int32_t B, int32_t C, int32_t D, int32_t P, const float* w1, const float* w2a, const float* keep1,
-                                    const float* keep2, const float* keep3, float keep_scale, const void* hidden,
-                                    const float* grad_code, const float* grad_code_pos, const float* grad_feats_out,
-                                    const float* grad_feats_out_pos, const void* workspace, size_t workspace_bytes, float* grad_feat,
-                                    float* grad_feat_pos, void* input_workspace, size_t input_workspace_bytes, dg_stream_t stream);
-
-/*
- * Measurement aid: the launch routes dg_head_backward takes for B images (dg_head_backward_pair: pass 2 B) of C channels, D code
+ * Measurement aid: the launch routes dg_head_backward takes for B images in all (a call with a second pass: pass 2 B) of C channels, D code
  * channels and P positions, from the plan the launches themselves follow.  Launches nothing and touches no GPU.  out[9] =
  *   [0] d hidden route     0: k_head_dh, one block per 64-position tile      1: k_head_dh2, persistent blocks, d W2b inside
  *   [1] blocks of k_head_dh2 (0 on route 0)          [2] 64-position tiles per image

@@ -19,7 +19,7 @@ from depthg_amd.aug_loss import aug_alignment_loss, crop_flip_coords
 NAMES = ["dg_augalign_workspace_bytes", "dg_augalign_forward", "dg_augalign_backward"]
 
 
-def test_entry_points_are_declared_listed_and_exported_under_version_118():
+def test_entry_points_are_declared_listed_and_exported_under_the_current_version():
     from depthg_amd import _lib
     header = open(os.path.join(ROOT, "include", "depthg_corr.h")).read()
     lib = _lib.load()
@@ -27,8 +27,8 @@ def test_entry_points_are_declared_listed_and_exported_under_version_118():
         assert re.search(r"\b" + name + r"\s*\(", header), name
         assert name in _lib.EXPORTS and name in _lib.SIGNATURES and hasattr(lib, name), name
     assert [n for n in _lib.EXPORTS if "augalign" in n] == NAMES              # the header's order
-    assert lib.dg_version() == _lib.DG_VERSION == 118
-    assert re.search(r"#define\s+DG_VERSION\s+118\b", header)
+    assert lib.dg_version() == _lib.DG_VERSION == 119
+    assert re.search(r"#define\s+DG_VERSION\s+119\b", header)
 
 
 def test_workspace_bytes_and_the_record_bound():

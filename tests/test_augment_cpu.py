@@ -27,7 +27,7 @@ def _params(B, H, W, **over):
     return A.AugmentParams(**p)
 
 
-def test_entry_points_are_declared_listed_and_exported_under_version_118():
+def test_entry_points_are_declared_listed_and_exported_under_the_current_version():
     from depthg_amd import _lib
     header = open(os.path.join(ROOT, "include", "depthg_corr.h")).read()
     lib = _lib.load()
@@ -35,7 +35,7 @@ def test_entry_points_are_declared_listed_and_exported_under_version_118():
         assert re.search(r"\b" + name + r"\s*\(", header), name
         assert name in _lib.EXPORTS and name in _lib.SIGNATURES and hasattr(lib, name), name
     assert [n for n in _lib.EXPORTS if n.startswith("dg_augment_")] == NAMES              # the header's order
-    assert lib.dg_version() == _lib.DG_VERSION == 118
+    assert lib.dg_version() == _lib.DG_VERSION == 119
     assert _lib.SIGNATURES["dg_augment_workspace_bytes"] == (ctypes.c_size_t, [ctypes.c_int32] * 3)
     assert len(_lib.SIGNATURES["dg_augment_forward"][1]) == 20
     # one fp64 partial per statistics block, at most 64 per image

@@ -64,7 +64,7 @@ def test_crf_entry_points_are_declared_listed_and_exported():
     for name in NEW:
         assert re.search(rf"\b{name}\s*\(", header), name
         assert name in _lib.EXPORTS and hasattr(lib, name), name
-    assert lib.dg_version() == 118
+    assert lib.dg_version() == 119
     for name in ("dense_crf", "batched_crf", "crf"):
         assert name in depthg_amd.__all__ and hasattr(depthg_amd, name)
     from depthg_amd import crf

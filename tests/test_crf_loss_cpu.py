@@ -27,8 +27,8 @@ def test_crf_loss_entry_points_are_declared_listed_and_exported():
         assert name in _lib.EXPORTS and name in _lib.SIGNATURES and hasattr(lib, name), name
         assert re.fullmatch(r"[a-z_]+", name)
     assert [n for n in _lib.EXPORTS if "crfloss" in n] == NAMES              # the header's order
-    assert lib.dg_version() == _lib.DG_VERSION == 118
-    assert re.search(r"#define\s+DG_VERSION\s+118\b", header)
+    assert lib.dg_version() == _lib.DG_VERSION == 119
+    assert re.search(r"#define\s+DG_VERSION\s+119\b", header)
 
 
 def test_workspace_bytes_cover_the_documented_sections():

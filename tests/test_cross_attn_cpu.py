@@ -40,7 +40,7 @@ def test_exports_are_declared_and_the_version_stays():
     assert tuple(order) == NEW and [n for n in names if n in NEW][-4:] == list(NEW)
     for n in NEW:
         assert hasattr(lib(), n), n
-    assert _lib.DG_VERSION == 118 and lib().dg_version() == 118 and re.search(r"#define\s+DG_VERSION\s+118\b", header)
+    assert _lib.DG_VERSION == 119 and lib().dg_version() == 119 and re.search(r"#define\s+DG_VERSION\s+119\b", header)
 
 
 def test_workspace_bytes_is_zero_exactly_for_the_refused_shapes():

@@ -34,7 +34,7 @@ def test_exports_and_prototypes():
     doc = header[header.index("The three-stage depth encoder"):header.index("size_t dg_depthenc_workspace_bytes")]
     for cite in ("src/modules.py:497-506", ":557", ":562-563", ":619-631"):
         assert cite in doc, cite
-    assert lib.dg_version() == L.DG_VERSION == 118
+    assert lib.dg_version() == L.DG_VERSION == 119
 
 
 A16 = 4096        # a non-null, 16-byte aligned address that is never dereferenced: every refusal comes before any launch

@@ -14,7 +14,11 @@ import head_input_grad_reference as R
 import head_margin_inputs as H
 from conftest import ROOT
 
-NEW_EXPORTS = ("dg_head_input_workspace_bytes", "dg_head_backward_input", "dg_head_backward_input_pair")
+NEW_EXPORTS = ("dg_head_input_workspace_bytes", "dg_head_backward_input")
+# one entry per operation, the widest argument list each: the second pass's tensors and the feats_out addend are NULL where absent
+HEAD_ENTRIES = {"dg_head_forward": 23, "dg_head_backward": 22, "dg_head_backward_input": 22}
+FOLDED_VARIANTS = {"dg_head_forward": ("_pair",), "dg_head_backward": ("_pair",), "dg_head_backward_input": ("_pair", "_add", "_add_pair"),
+                   "dg_fps_coords": ("_pair",), "dg_super_perms": ("_seeded", "_state")}
 TINY_VIT = dict(embed_dim=384, depth=1)
 
 
@@ -37,6 +41,14 @@ def test_exports_are_declared_bound_and_built():
     for name in NEW_EXPORTS:
         assert re.search(r"\b" + name + r"\s*\(", header), name
         assert name in _lib.SIGNATURES and hasattr(lib, name), name
+    code = re.sub(r"/\*.*?\*/", " ", header, flags=re.S)
+    for name, count in HEAD_ENTRIES.items():
+        proto = re.search(r"\bint\s+" + name + r"\s*\(([^()]*)\)\s*;", code)
+        assert proto and len(proto.group(1).split(",")) == count, name
+        assert len(_lib.SIGNATURES[name][1]) == count and len(getattr(lib, name).argtypes) == count, name
+    for name, suffixes in FOLDED_VARIANTS.items():
+        for gone in (name + s for s in suffixes):
+            assert gone not in _lib.EXPORTS and gone not in header and not hasattr(lib, gone), gone
     assert lib.dg_head_input_workspace_bytes(384, 70) >= 2 * 384 * (70 + 384)
     assert lib.dg_head_input_workspace_bytes(384, 70) % 1024 == 0          # whole fragment tiles
     assert lib.dg_head_input_workspace_bytes(769, 70) == 0 and lib.dg_head_input_workspace_bytes(380, 70) == 0
@@ -54,10 +66,10 @@ def test_c_abi_refusals_return_before_any_launch():
     ws2 = lib.dg_head_workspace_bytes(2 * B, C, D, P)
 
     def single(C=C, D=D, P=P, w1=x, w2a=x, hidden=x, g=x, wsp=x, wsb=ws, dx=x, iw=x, iwb=iws):
-        return lib.dg_head_backward_input(B, C, D, P, w1, w2a, x, x, 1.0, hidden, g, wsp, wsb, dx, iw, iwb, null)
+        return lib.dg_head_backward_input(B, C, D, P, w1, w2a, x, x, null, 1.0, hidden, g, null, null, null, wsp, wsb, dx, null, iw, iwb, null)
 
     def pair(g2=x, dx=x, dx2=x, wsb=ws2, B=B):
-        return lib.dg_head_backward_input_pair(B, C, D, P, x, x, x, x, 1.0, x, x, g2, x, wsb, dx, dx2, x, iws, null)
+        return lib.dg_head_backward_input(B, C, D, P, x, x, x, x, null, 1.0, x, x, g2, null, null, x, wsb, dx, dx2, x, iws, null)
 
     assert single(C=776) == UNSUPPORTED and single(C=60) == UNSUPPORTED and single(D=129) == UNSUPPORTED
     assert single(P=0) == INVALID

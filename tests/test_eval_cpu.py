@@ -18,7 +18,7 @@ def test_segment_predict_is_exported_and_declared():
     assert re.search(r"\bdg_segment_predict\s*\(", header)
     assert "dg_segment_predict" in _lib.EXPORTS
     lib = _lib.load()
-    assert hasattr(lib, "dg_segment_predict") and lib.dg_version() == 118
+    assert hasattr(lib, "dg_segment_predict") and lib.dg_version() == 119
 
 
 def _call(B=2, D=8, h=4, w=4, n=3, m=4, H=8, W=8, n_store=0, ptr=16, scratch_bytes=1 << 30):

@@ -280,8 +280,8 @@ def test_fps_map_sizes_of_the_configs(hw, dhw, S, dev):
 
 @pytest.mark.parametrize("hw,dhw,S,B", [(28, 224, 11, 16), (28, 224, 12, 3), (14, 100, 6, 1)])
 def test_fps_pair_launch(hw, dhw, S, B, dev):
-    """dg_fps_coords_pair = the two calls of a step (src/modules.py:1304-1308) in one launch, without a concatenated copy of the
-    depth maps: the same coordinates, bit for bit, as one dg_fps_coords per tensor; tensors that do not match are refused."""
+    """dg_fps_coords with depth_pos = the two calls of a step (src/modules.py:1304-1308) in one launch, without a concatenated copy of
+    the depth maps: the same coordinates, bit for bit, as one dg_fps_coords per tensor; tensors that do not match are refused."""
     from depthg_amd import ops
     g = torch.Generator().manual_seed(3 * hw + S + B)
     d1 = (torch.rand(B, 1, dhw, dhw, generator=g) * 9 + 0.5).to(dev)
@@ -397,7 +397,7 @@ def test_depth_indicators_on_whole_pixel_source_coordinates(dev):
 @pytest.mark.parametrize("dense", [True, False])
 def test_forward_that_draws_its_negatives(dense, dev):
     """dg_corr_forward_draw (the reference draws super_perm inside forward too, src/modules.py:1340-1342): same batch maps and
-    the same outputs as dg_super_perms_seeded / dg_super_perms_state followed by dg_corr_forward - with a host seed and with the
+    the same outputs as dg_super_perms (from that seed / that state) followed by dg_corr_forward - with a host seed and with the
     device-resident generator, whose state advances by one draw either way; on the identity grid the draw has no launch of its
     own.  The module's forward() goes through it: two calls draw different negatives, torch.manual_seed repeats them."""
     from depthg_amd import ContrastiveCorrelationLoss, ops

@@ -1,4 +1,4 @@
-"""d loss / d image_feat of the projection head (ProjectionHead(..., input_grad=True) -> dg_head_backward_input / _pair, k_head_dx)
+"""d loss / d image_feat of the projection head (ProjectionHead(..., input_grad=True) -> dg_head_backward_input, k_head_dx)
 against float64 autograd of oracle.head_oracle.head_forward, on every case of tests/head_margin_inputs.py - dh_route FUSED and TILES,
 step-major and row-major d hidden, the linear head, the pair form, C = 256 / 352 / 384 / 768, D = 70 / 96 / 100, P = 225 - and two
 small cases of tests/head_input_grad_reference.py (an eval-mode head without keep masks; a pair in which only the second pass

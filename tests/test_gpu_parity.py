@@ -370,7 +370,7 @@ def test_super_perms_kernel(dev):
     for count, B in ((5, 32), (3, 1), (2, 257), (1, 2)):
         keys = torch.rand(count, B, device=dev)
         out = torch.empty(count, B, dtype=torch.long, device=dev)
-        rc = lib.dg_super_perms(ctypes.c_void_p(keys.data_ptr()), count, B, ctypes.c_void_p(out.data_ptr()),
+        rc = lib.dg_super_perms(ctypes.c_void_p(keys.data_ptr()), 0, None, count, B, ctypes.c_void_p(out.data_ptr()),
                                 ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
         assert rc == 0
         perm = torch.argsort(keys, dim=1, stable=True)

@@ -1,6 +1,6 @@
 """d loss / d feats of the reconstruction term on the GPU (k_rec_bwd_code<true> through dg_rec_feats_backward, ops.rec_loss_backward(
 want_feats=True), rec_loss.reconstruction_loss(feats_grad=True)), the head's epilogue addend (k_head_dx<MB, true> through
-dg_head_backward_input_add / _pair, ProjectionHead(input_grad=True, feats_grad=True)) and cfg.dg_rec_feats_grad in training_step.
+dg_head_backward_input's grad_feats_out, ProjectionHead(input_grad=True, feats_grad=True)) and cfg.dg_rec_feats_grad in training_step.
 
 Parity: d feats against the float64 restatement (tests/rec_feats_reference.py) with the float32 torch chain under autograd on the
 GPU as the yardstick, in the measure and under the MARGIN of tests/test_gpu_rec_loss.py: relative L2, at most 2 x the yardstick's.

@@ -20,7 +20,7 @@ def test_library_exports_every_declared_symbol():
     for name in sorted(declared):
         assert hasattr(lib, name), f"{name} declared in include/depthg_corr.h but not exported"
     assert declared == set(_lib.EXPORTS)
-    assert lib.dg_version() == _lib.DG_VERSION == 118
+    assert lib.dg_version() == _lib.DG_VERSION == 119
     # every prototype against the binding's signature table: the return type, the parameter count and each parameter's kind
     # (a miscounted `[vp] * 10` would otherwise only show on a GPU, as a crash)
     protos = _header_prototypes(header)

@@ -1,5 +1,5 @@
-"""CPU-side checks of the reconstruction term's gradient with respect to feats (dg_rec_feats_backward, dg_head_backward_input_add /
-_pair, rec_loss.reconstruction_loss(feats_grad=True), cfg.dg_rec_feats_grad): the exports, the C ABI's refusals (which return before
+"""CPU-side checks of the reconstruction term's gradient with respect to feats (dg_rec_feats_backward, dg_head_backward_input's
+grad_feats_out, rec_loss.reconstruction_loss(feats_grad=True), cfg.dg_rec_feats_grad): the exports, the C ABI's refusals (which return before
 any launch), the float64 restatement against autograd, the CPU route, and the segmenter's construction rule.  (The depth featurizer's
 head has no CPU route, so a training_step with the key runs on the GPU only: tests/test_gpu_rec_feats.py.)"""
 import ctypes
@@ -13,7 +13,7 @@ from conftest import ROOT
 import rec_feats_reference as F
 import rec_loss_reference as R
 
-NEW = {"dg_rec_feats_backward": 19, "dg_head_backward_input_add": 19, "dg_head_backward_input_add_pair": 22}
+NEW = {"dg_rec_feats_backward": 19, "dg_head_backward_input": 22}     # (the head's entry: keep3 and the two grad_feats_out among its 22)
 
 
 def test_exports_are_declared_bound_and_built():
@@ -29,8 +29,10 @@ def test_exports_are_declared_bound_and_built():
         assert len(_lib.SIGNATURES[name][1]) == count and len(getattr(lib, name).argtypes) == count, name
     order = list(_lib.SIGNATURES)
     assert order.index("dg_rec_feats_backward") == order.index("dg_recloss_backward") + 1
-    assert order.index("dg_head_backward_input_add") == order.index("dg_head_backward_input_pair") + 1
-    assert lib.dg_version() == _lib.DG_VERSION == 118                          # more exports under the same number
+    for suffix in ("_pair", "_add", "_add_pair"):                              # one input-gradient entry: its variants are folded into it
+        gone = "dg_head_backward_input" + suffix
+        assert gone not in _lib.EXPORTS and gone not in header and not hasattr(lib, gone), gone
+    assert lib.dg_version() == _lib.DG_VERSION == 119
 
 
 def _backward(B=2, D=8, C=12, h=4, w=4, ptr=16, scale=1.0, ws_bytes=1 << 30, **at):
@@ -80,10 +82,10 @@ def test_head_backward_input_add_refuses_bad_arguments_before_any_launch():
     ws2 = lib.dg_head_workspace_bytes(2 * B, C, D, P)
 
     def single(C=C, D=D, P=P, w1=x, k3=x, g=x, gf=x, wsb=ws, dx=x, iw=x, iwb=iws):
-        return lib.dg_head_backward_input_add(B, C, D, P, w1, x, x, x, k3, 1.0, x, g, gf, x, wsb, dx, iw, iwb, null)
+        return lib.dg_head_backward_input(B, C, D, P, w1, x, x, x, k3, 1.0, x, g, null, gf, null, x, wsb, dx, null, iw, iwb, null)
 
     def pair(g2=x, gf=x, gf2=x, dx=x, dx2=x, wsb=ws2, B=B):
-        return lib.dg_head_backward_input_add_pair(B, C, D, P, x, x, x, x, x, 1.0, x, x, g2, gf, gf2, x, wsb, dx, dx2, x, iws, null)
+        return lib.dg_head_backward_input(B, C, D, P, x, x, x, x, x, 1.0, x, x, g2, gf, gf2, x, wsb, dx, dx2, x, iws, null)
 
     assert single(C=776) == UNSUPPORTED and single(D=129) == UNSUPPORTED and single(P=0) == INVALID
     for kw in (dict(w1=null), dict(g=null), dict(dx=null), dict(iw=null)):

@@ -27,7 +27,7 @@ def test_exports_are_declared_bound_and_in_the_library():
     order = _lib.EXPORTS
     assert order.index("dg_segment_predict") < order.index(NAMES[0]) < order.index(NAMES[1]) < order.index("dg_crf_workspace_bytes")
     assert len(_lib.SIGNATURES[NAMES[0]][1]) == 27 and len(_lib.SIGNATURES[NAMES[1]][1]) == 18
-    assert lib.dg_version() == _lib.DG_VERSION == 118
+    assert lib.dg_version() == _lib.DG_VERSION == 119
 
 
 P = ctypes.c_void_p(256)                    # a dummy device address: every call below is refused before anything is dereferenced

@@ -23,7 +23,7 @@ def test_library_declares_the_linear_entry_points():
     lib = _lib.load()
     for name in NAMES:
         assert hasattr(lib, name)
-    assert lib.dg_version() == 118
+    assert lib.dg_version() == 119
 
 
 def test_pack_sizes():
