@@ -39,6 +39,10 @@ Public surface (mirrors the reference's Python operator surface for this path):
     data                         the training data path (src/data.py:87-132, 815-912, 1073-1141; src/utils.py:164-182): CroppedFolder /
                                  DirectoryFolder, loader_index_tables, ContrastiveBatches - the loader transform of a batch and its kNN
                                  positives as ONE fused HIP launch (ops.batch_prep, k_batch_prep) - and precompute_knns
+    feature_cache / FeatureCache the frozen backbone's image_feat of every train image (src/modules.py:90-137), stored once as float32,
+                                 float16 or bfloat16 and gathered per batch and positives in ONE HIP launch (k_fc_put / k_fc_gather);
+                                 data.build_feature_cache fills it, cfg.dg_feature_cache makes the step start from it
+                                 (src/train_segmentation.py:194-212 without the two backbone passes)
     train                        fit(model, train_batches, val_batches, cfg, out_dir): the loop of src/train_segmentation.py:551-714 without
                                  Lightning; `python -m depthg_amd.train` is its command line
     ops                          thin ctypes binding of the C ABI in include/depthg_corr.h; ops.corr_forward is the one route to its five
@@ -73,8 +77,11 @@ from .featurizer import DinoFeaturizer, DinoFeaturizerWithDepth  # noqa: F401
 from . import segmenter  # noqa: F401
 from . import data  # noqa: F401
 from .data import ContrastiveBatches, CroppedFolder, DirectoryFolder, loader_index_tables, precompute_knns  # noqa: F401
+from . import feature_cache  # noqa: F401
+from .feature_cache import FeatureCache  # noqa: F401
+from .data import build_feature_cache  # noqa: F401
 
 __all__ = ["ContrastiveCorrelationLoss", "DepthContrastiveCorrelationLoss", "ContrastiveCRFLoss", "crf_loss", "aug_loss", "aug_alignment_loss", "crop_flip_coords", "augment", "AugmentParams", "augment_batch", "draw_augment_params", "rec_loss", "reconstruction_loss", "depth_encoder", "cross_attn", "cross_attention", "multihead_cross_attention", "depth_decay", "training", "metrics", "evaluation", "predict_and_score", "segment", "crf", "dense_crf",
            "batched_crf", "knn", "lhp", "optim", "FusedAdam", "FusedAdamSet", "segmenter", "vit", "featurizer",
            "DinoFeaturizer", "DinoFeaturizerWithDepth", "data", "ContrastiveBatches", "CroppedFolder", "DirectoryFolder",
-           "loader_index_tables", "precompute_knns"]
+           "loader_index_tables", "precompute_knns", "feature_cache", "FeatureCache", "build_feature_cache"]

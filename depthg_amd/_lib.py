@@ -12,6 +12,7 @@ DG_VERSION = 119                     # must match include/depthg_corr.h: a stale
 DG_POINTWISE, DG_ZERO_CLAMP, DG_STABALIZE, DG_DEPTH_TERM, DG_NEED_GRAD, DG_SHARED_COORDS, DG_IDENTITY_GRID, DG_LINE_GRID, \
     DG_EXACT_MASKS, DG_FEATS_UNIT = (1 << i for i in range(10))
 DG_LIN_LAYERNORM, DG_LIN_GELU, DG_LIN_IN_BF16, DG_LIN_OUT_BF16 = 1, 2, 4, 8      # dg_vit_linear_forward flags
+DG_FC_F32, DG_FC_F16, DG_FC_BF16 = 0, 1, 2                                        # dg_featcache_put / _gather storage types
 
 class CorrDesc(ctypes.Structure):
     """struct dg_corr_desc"""
@@ -133,6 +134,9 @@ SIGNATURES = {
     "dg_augment_forward": (_I, [vp] + [i64] * 4 + [vp] * 4 + [i32] * 6 + [vp, vp, vp, _SZ, vp]),
     # batch preparation
     "dg_batch_prep": (_I, [vp, _SZ, vp, vp, vp] + [i32] * 4 + [vp] * 7),
+    # frozen-backbone feature cache
+    "dg_featcache_put": (_I, [vp, i32, i64, i64, vp, vp, i64, vp]),
+    "dg_featcache_gather": (_I, [vp, i32, i64, i64, vp, vp, i64, vp, vp]),
     # measurement aids
     "dg_corr_main_kernel_name": (_STR, [cp]),
     "dg_corr_intra_folded": (_I, [cp]),

@@ -1,5 +1,5 @@
 // C ABI of the gfx950 DepthG library (include/depthg_corr.h), the units' shared state and the small subsystems: version and error
-// text, the library's side stream, batch maps / random draws / coordinate samplers, kNN, LHP, fused Adam, ViT attention and linear, the fused depth encoder, the depth guidance's cross-attention, the GPU batch augmentation, the batch preparation.  (The auxiliary loss terms: dg_api_loss.hip.)
+// text, the library's side stream, batch maps / random draws / coordinate samplers, kNN, LHP, fused Adam, ViT attention and linear, the fused depth encoder, the depth guidance's cross-attention, the GPU batch augmentation, the batch preparation, the frozen-backbone feature cache.  (The auxiliary loss terms: dg_api_loss.hip.)
 // Host-side only: argument checks and kernel launches on the caller's stream.
 #include "dg_api.h"
 #include "dg_aux_args.h"
@@ -583,5 +583,40 @@ extern "C" int dg_batch_prep(const uint8_t* packed, size_t packed_bytes, const i
     A.n_records = n_records; A.N = N; A.H = H; A.W = W;
     A.tiles_x = (W + DG_BATCH_TW - 1) / DG_BATCH_TW; A.tiles_y = (H + DG_BATCH_TH - 1) / DG_BATCH_TH;
     DG_HIP(dg_launch_batch_prep(A, static_cast<hipStream_t>(stream_)));
+    return DG_OK;
+}
+
+// ---- frozen-backbone feature cache (dg_feat_cache.hip)
+// what both entries refuse before a launch; `lists`: index lists of n rows each (n * lists blocks along gridDim.y)
+static int featcache_check(const char* who, const void* cache, int32_t dtype, int64_t N, int64_t L, int64_t n, int lists) {
+    if (dtype < DG_FC_F32 || dtype > DG_FC_BF16) return fail(DG_ERR_INVALID, "%s: unknown dtype %d (0 float32, 1 float16, 2 bfloat16)", who, dtype);
+    if (N < 1 || L < 1 || n < 0) return fail(DG_ERR_INVALID, "%s: N=%lld L=%lld n=%lld (N and L positive, n not negative)", who, (long long)N, (long long)L, (long long)n);
+    if (n > DG_FC_MAX_ROWS / lists)
+        return fail(DG_ERR_UNSUPPORTED, "%s: %d list(s) of %lld rows in one call (at most %d rows)", who, lists, (long long)n, DG_FC_MAX_ROWS);
+    if (L > (1ll << 40) || N > (1ll << 62) / L) return fail(DG_ERR_UNSUPPORTED, "%s: a cache of %lld x %lld elements", who, (long long)N, (long long)L);
+    if (!cache) return fail(DG_ERR_INVALID, "%s: null pointer", who);
+    if ((uintptr_t)cache & (dtype == DG_FC_F32 ? 3 : 1)) return fail(DG_ERR_INVALID, "%s: the cache is not aligned to its element size", who);
+    return DG_OK;
+}
+
+extern "C" int dg_featcache_put(void* cache, int32_t dtype, int64_t N, int64_t L, const float* src, const int64_t* idx, int64_t n,
+                                dg_stream_t stream_) {
+    if (int rc = featcache_check(__func__, cache, dtype, N, L, n, 1)) return rc;
+    if (n == 0) return DG_OK;
+    if (!src || !idx) return fail(DG_ERR_INVALID, "dg_featcache_put: null pointer");
+    if (((uintptr_t)src & 3) || ((uintptr_t)idx & 7)) return fail(DG_ERR_INVALID, "dg_featcache_put: src must be 4-byte aligned, idx 8-byte aligned");
+    DG_HIP(dg_launch_featcache_put(cache, dtype, N, L, src, reinterpret_cast<const long long*>(idx), (int)n, static_cast<hipStream_t>(stream_)));
+    return DG_OK;
+}
+
+extern "C" int dg_featcache_gather(const void* cache, int32_t dtype, int64_t N, int64_t L, const int64_t* idx_a, const int64_t* idx_b,
+                                   int64_t n, float* out, dg_stream_t stream_) {
+    if (int rc = featcache_check(__func__, cache, dtype, N, L, n, idx_b ? 2 : 1)) return rc;
+    if (n == 0) return DG_OK;
+    if (!idx_a || !out) return fail(DG_ERR_INVALID, "dg_featcache_gather: null pointer");
+    if (((uintptr_t)out & 3) || (((uintptr_t)idx_a | (uintptr_t)idx_b) & 7))
+        return fail(DG_ERR_INVALID, "dg_featcache_gather: out must be 4-byte aligned, idx_a and idx_b 8-byte aligned");
+    DG_HIP(dg_launch_featcache_gather(cache, dtype, N, L, reinterpret_cast<const long long*>(idx_a), reinterpret_cast<const long long*>(idx_b),
+                                      (int)n, out, static_cast<hipStream_t>(stream_)));
     return DG_OK;
 }

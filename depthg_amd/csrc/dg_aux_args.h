@@ -1,4 +1,4 @@
-// The stand-alone operations (dg_sample, dg_metrics, dg_knn, dg_lhp, dg_optim, dg_attn, dg_linear, dg_augment, dg_batch .hip; dg_api_aux.hip): constants and launchers.
+// The stand-alone operations (dg_sample, dg_metrics, dg_knn, dg_lhp, dg_optim, dg_attn, dg_linear, dg_augment, dg_batch, dg_feat_cache .hip; dg_api_aux.hip): constants and launchers.
 // (The auxiliary loss terms have a header of their own: dg_loss_args.h.)
 #pragma once
 #include "dg_common.h"
@@ -109,3 +109,16 @@ struct DgBatchArgs {
     float mean[3], stdv[3];
 };
 hipError_t dg_launch_batch_prep(const DgBatchArgs& A, hipStream_t s);
+
+// ---- frozen-backbone feature cache: store image_feat rows once, gather a batch and its positives in one launch (dg_feat_cache.hip;
+// src/modules.py:90-137, src/train_segmentation.py:194-212)
+#define DG_FC_THREADS 256
+#define DG_FC_UNROLL 2                       // 16-byte cache vectors per lane
+#define DG_FC_SPAN (DG_FC_THREADS * DG_FC_UNROLL)      // ... and per block
+#define DG_FC_MAX_ROWS 65535                 // rows per call (gridDim.y)
+#define DG_FC_BF16_NAN 0xFFFFu               // every NaN as bfloat16: what torch's .to(torch.bfloat16) stores for a tensor
+hipError_t dg_launch_featcache_put(void* cache, int dtype, long long N, long long L, const float* src, const long long* idx, int n,
+                                   hipStream_t s);
+// idx_b null: n rows, else 2 n
+hipError_t dg_launch_featcache_gather(const void* cache, int dtype, long long N, long long L, const long long* idx_a, const long long* idx_b,
+                                      int n, float* out, hipStream_t s);

@@ -19,6 +19,9 @@ kNN positive).  All of it is a gather per output pixel and two float32 operation
                                       ind_pos, depth_pos, label_pos, mask_pos.  On a CPU device the same class runs the plain chain
                                       (PIL resize, crop, the torch operations): the restatement the GPU route is tested against.
     precompute_knns                   src/precompute_knns.py:15-21, 85-115 on centre-cropped batches through the same kernel
+    build_feature_cache               one pass of the frozen backbone over a split with a deterministic loader transform, kept as a
+                                      feature_cache.FeatureCache; ContrastiveBatches(feature_cache=...) then adds `image_feat` /
+                                      `image_feat_pos` to every batch (cfg.dg_feature_cache in the step)
 
 `img_aug` / `coord_aug` are not made here: cfg.dg_gpu_augment forms them inside the step (depthg_amd/augment.py).
 """
@@ -325,7 +328,7 @@ class ContrastiveBatches:
     last batch may be short (DataLoader's drop_last=False).  No img_aug / coord_aug: cfg.dg_gpu_augment makes them in the step."""
 
     def __init__(self, dataset, cfg, image_set, res, loader_crop_type, batch_size, shuffle=False, generator=None, num_workers=0,
-                 pos=True, return_depth=None, device=None):
+                 pos=True, return_depth=None, device=None, feature_cache=None):
         self.dataset, self.cfg, self.image_set, self.res, self.loader_crop_type = dataset, cfg, image_set, int(res), loader_crop_type
         self.batch_size, self.shuffle, self.generator, self.pos = int(batch_size), bool(shuffle), generator, bool(pos)
         if self.batch_size < 1:
@@ -342,6 +345,19 @@ class ContrastiveBatches:
             path = knn.nns_path(dataset.data_dir, cfg.model_type, dataset.nns_name, image_set, getattr(dataset, "crop_type", None),
                                 getattr(cfg, "res", self.res))
             self.nns = knn.load_nns(path, len(dataset))
+        # feature_cache.FeatureCache of this dataset's images (build_feature_cache): each batch then also carries the frozen backbone's
+        # `image_feat` of its samples and `image_feat_pos` of their positives, gathered in one launch from the indices while they are
+        # still on the host.  img / img_pos stay in the batch (the CRF and augmentation terms read them).
+        self.feature_cache = feature_cache
+        if feature_cache is not None:
+            if loader_crop_type == "random":
+                raise ValueError("depthg_amd.data: a feature cache holds the features of ONE view of every image; with loader_crop_type = "
+                                 "'random' the view changes with every draw")
+            if not self.pos:
+                raise ValueError("depthg_amd.data: a feature cache serves the training pipeline (pos=True): image_feat and image_feat_pos")
+            if feature_cache.n_images != len(dataset) or feature_cache.device != self.device:
+                raise ValueError(f"depthg_amd.data: the feature cache holds {feature_cache.n_images} images on {feature_cache.device}, the "
+                                 f"pipeline reads {len(dataset)} on {self.device}")
 
     def __len__(self):
         return (len(self.dataset) + self.batch_size - 1) // self.batch_size
@@ -373,6 +389,8 @@ class ContrastiveBatches:
             batch.update({"img_pos": img[B:], "ind_pos": torch.tensor(inds_pos, dtype=torch.int64), "label_pos": label[B:], "mask_pos": mask[B:]})
             if self.return_depth:
                 batch["depth_pos"] = depth[B:].unsqueeze(1)
+        if self.feature_cache is not None:
+            batch["image_feat"], batch["image_feat_pos"] = self.feature_cache.gather(inds, inds_pos)
         return batch
 
     def __iter__(self):
@@ -408,3 +426,62 @@ def precompute_knns(net, dataset, cfg, res, image_set, crop_type, batch_size=Non
     path = knn.nns_path(dataset.data_dir, cfg.model_type, dataset.nns_name, image_set, crop_type, res)
     knn.save_nns(path, table)
     return path
+
+
+# --------------------------------------------------------------------------------------------------------------- feature cache
+def feature_cache_meta(cfg, dataset, res, crop_type):
+    """What the cached features of `dataset` depend on (FeatureCache.meta): the backbone, the view, the images.  crop_type: the
+    LOADER's crop (the dataset's own crop is part of its name)."""
+    return {"model_type": str(getattr(cfg, "model_type", "vit_small")), "dino_patch_size": int(cfg.dino_patch_size),
+            "dino_feat_type": str(getattr(cfg, "dino_feat_type", "feat")), "res": int(res), "loader_crop_type": crop_type,
+            "dataset_name": "{}_{}".format(dataset.nns_name, getattr(dataset, "crop_type", None)), "n_images": len(dataset),
+            "pretrained_weights": getattr(cfg, "pretrained_weights", None)}
+
+
+def feature_cache_path(data_dir, meta, image_set, dtype):
+    """<data_dir>/feature_cache_<meta>.pt"""
+    from .feature_cache import as_dtype
+    name = "feature_cache_{model_type}_{dino_feat_type}{dino_patch_size}_{dataset_name}_{split}_{loader_crop_type}_{res}_{n_images}_{dtype}.pt".format(
+        split=image_set, dtype=str(as_dtype(dtype)).replace("torch.", ""), **meta)
+    return os.path.join(data_dir, name)
+
+
+def build_feature_cache(net, dataset, cfg, res, crop_type, dtype=torch.float32, device=None, batch_size=None, num_workers=0):
+    """A feature_cache.FeatureCache of `dataset`: one pass over the split in index order through `prepare_samples` with the loader
+    transform (res, crop_type - the pipeline's loader_crop_type), `net._backbone(img)` under no_grad with the backbone in eval mode
+    (what forward() runs, src/modules.py:93-120), one `put` per batch.  The pass --precompute-knns makes over the same images pools
+    and drops these maps; this one keeps them.  Refused: crop_type "random" (the features would depend on the draw) and cfg.arch
+    "dino_depth" (the depth-guided featurizer mixes the depth map in behind the backbone: out of scope for the cache)."""
+    from .feature_cache import FeatureCache
+    if crop_type == "random":
+        raise ValueError("depthg_amd.data: build_feature_cache with loader_crop_type = 'random': the features of an image would depend on "
+                         "the crop's draw; use 'center' or None")
+    if getattr(cfg, "arch", "dino") == "dino_depth" or not hasattr(net, "forward_pair_features") or not hasattr(net, "_backbone"):
+        raise ValueError("depthg_amd.data: build_feature_cache serves cfg.arch = 'dino' (a FrozenBackboneFeaturizer); the depth-guided "
+                         "featurizer of arch 'dino_depth' is out of scope for the feature cache")
+    resized_size(1, 1, res, crop_type)
+    if device is None:
+        device = "cuda:0" if torch.cuda.is_available() else "cpu"
+    device = torch.device(device)
+    if batch_size is None:
+        batch_size = 128 if cfg.model_type == "vit_small" else 64
+    threads = max(0, min(int(num_workers), MAX_DECODE_THREADS))
+    n = len(dataset)
+    cache = None
+    net.model.eval()
+    with torch.no_grad():
+        for i in range(0, n, int(batch_size)):
+            inds = list(range(i, min(i + int(batch_size), n)))
+            if threads == 0 or len(inds) < 2:
+                samples = [dataset.load(k) for k in inds]
+            else:
+                with ThreadPoolExecutor(max_workers=min(threads, len(inds))) as pool:
+                    samples = list(pool.map(dataset.load, inds))
+            img = prepare_samples(dataset, samples, res, crop_type, device, False)[0]
+            image_feat = net._backbone(img)[0]
+            if cache is None:
+                cache = FeatureCache(n, *image_feat.shape[1:], dtype=dtype, device=device, meta=feature_cache_meta(cfg, dataset, res, crop_type))
+            cache.put(inds, image_feat)
+    if cache is None:
+        raise ValueError("depthg_amd.data: build_feature_cache on an empty dataset")
+    return cache

@@ -75,6 +75,11 @@ class FrozenBackboneFeaturizer(nn.Module):
             image_feat, attn = self._backbone(img, n, return_class_feat)
             if return_class_feat:
                 return image_feat
+        return self.forward_features(image_feat, attn)
+
+    def forward_features(self, image_feat, attn=None):
+        """forward() behind the backbone (:122-137), from its `image_feat` (B, n_feats, h, w) - the backbone's own, or the rows a
+        feature_cache.FeatureCache kept of it (`attn` is then None: no attention map was stored)."""
         if self.proj_type is not None:
             # one fused HIP launch: code = cluster1(drop(f)) [+ cluster2(drop(f))] and feats = drop(f) (:122-137; three draws)
             code, feats = run_head(*self._head_modules(), image_feat, self.training, bool(self.cfg.dropout), float(self.dropout.p))
@@ -92,6 +97,13 @@ class FrozenBackboneFeaturizer(nn.Module):
         self.model.eval()
         with torch.no_grad():
             (image_feat, attn), (image_feat_pos, attn_pos) = self._backbone(img), self._backbone(img_pos)
+        return self.forward_pair_features(image_feat, image_feat_pos, defer_feats_dropout, attn, attn_pos)
+
+    def forward_pair_features(self, image_feat, image_feat_pos, defer_feats_dropout=False, attn=None, attn_pos=None):
+        """forward_pair() behind the backbone, from the two passes' `image_feat` - the backbone's own, or a FeatureCache's rows (the
+        attention maps are then None).  The Dropout2d draws come as forward_pair's do."""
+        if not self.training or self.proj_type is None:
+            return self.forward_features(image_feat, attn), self.forward_features(image_feat_pos, attn_pos)
         (code, feats), (code_pos, feats_pos) = run_head_pair(*self._head_modules(), image_feat, image_feat_pos, True,
                                                              bool(self.cfg.dropout), float(self.dropout.p), None, defer_feats_dropout)
         return (feats, code, attn), (feats_pos, code_pos, attn_pos)
@@ -226,6 +238,12 @@ class DepthGuidance:
 
     def forward_pair(self, *args, **kwargs):
         raise NotImplementedError("depthg_amd: the depth-guided featurizer has no paired pass (call it once per image set)")
+
+    def forward_features(self, *args, **kwargs):
+        raise NotImplementedError("depthg_amd: the depth-guided featurizer mixes the depth map in behind the backbone: it has no pass "
+                                  "from cached features (cfg.dg_feature_cache serves cfg.arch = 'dino')")
+
+    forward_pair_features = forward_features
 
 
 class DinoFeaturizer(FrozenBackboneFeaturizer):

@@ -510,6 +510,58 @@ def batch_prep(packed, records, tables, out_size, device=None, mean=(0.485, 0.45
     return out
 
 
+FEATURE_CACHE_DTYPES = {torch.float32: _lib.DG_FC_F32, torch.float16: _lib.DG_FC_F16, torch.bfloat16: _lib.DG_FC_BF16}
+FEATURE_CACHE_MAX_ROWS = 65535      # rows one dg_featcache_* call moves (gather: the two lists together)
+
+
+def _feature_cache_operands(who, cache, lists):
+    """The cache as the two entries take it - a contiguous (N, L) GPU tensor of a storage type - and each index list of `lists` as a
+    contiguous int64 tensor on the cache's device (the kernels read them there; the caller has checked the values on the host)."""
+    if cache.dim() != 2 or cache.dtype not in FEATURE_CACHE_DTYPES or not cache.is_contiguous():
+        raise ValueError(f"depthg_amd: {who} wants the cache as a contiguous (N, L) tensor of float32, float16 or bfloat16, got "
+                         f"{tuple(cache.shape)} {cache.dtype}")
+    _on_gpu(cache, "cache")
+    for name, idx in lists:
+        if idx.dtype != torch.int64 or idx.dim() != 1 or idx.device != cache.device or not idx.is_contiguous():
+            raise ValueError(f"depthg_amd: {who} wants `{name}` as a contiguous 1-d int64 tensor on {cache.device} (the kernel reads it there)")
+    return FEATURE_CACHE_DTYPES[cache.dtype]
+
+
+def feature_cache_put(cache, idx, src):
+    """Rows idx[0..n) of `cache` (N, L) = src (n, L) - or (n, C, h, w) with C h w = L - converted to the cache's dtype with torch's
+    rounding (dg_featcache_put, k_fc_put of dg_feat_cache.hip): one launch.  `idx`: int64 on the cache's device, each row once."""
+    lib = _lib.load()
+    dt = _feature_cache_operands("feature_cache_put", cache, (("idx", idx),))
+    N, L = cache.shape
+    n = idx.numel()
+    src = _f32c(src, "src")
+    if src.device != cache.device or src.numel() != n * L or src.shape[0] != n:
+        raise ValueError(f"depthg_amd: feature_cache_put: src {tuple(src.shape)} on {src.device} is not {n} rows of {L} elements on {cache.device}")
+    rc = lib.dg_featcache_put(_ptr(cache), dt, N, L, _ptr(src), _ptr(idx), n, _stream(cache.device))
+    _lib.check(rc, "dg_featcache_put")
+
+
+def feature_cache_gather(cache, idx_a, idx_b=None, out=None):
+    """(2n, L) fp32: the cache rows idx_a[0..n), then the rows idx_b[0..n) - or (n, L) without idx_b - from ONE launch into one
+    allocation (dg_featcache_gather, k_fc_gather of dg_feat_cache.hip): the layout the head's paired pass takes its two maps in.
+    Indices: int64 on the cache's device; they may repeat.  `out`: a buffer to write instead of a new one; every element is written."""
+    lib = _lib.load()
+    lists = (("idx_a", idx_a),) + ((("idx_b", idx_b),) if idx_b is not None else ())
+    dt = _feature_cache_operands("feature_cache_gather", cache, lists)
+    N, L = cache.shape
+    n = idx_a.numel()
+    if idx_b is not None and idx_b.numel() != n:
+        raise ValueError(f"depthg_amd: feature_cache_gather: {n} indices and {idx_b.numel()} positives")
+    rows = 2 * n if idx_b is not None else n
+    if out is None:
+        out = _empty((rows, L), torch.float32, cache.device)
+    elif out.dtype != torch.float32 or out.device != cache.device or tuple(out.shape) != (rows, L) or not out.is_contiguous():
+        raise ValueError(f"depthg_amd: feature_cache_gather: `out` must be a contiguous float32 ({rows}, {L}) tensor on {cache.device}")
+    rc = lib.dg_featcache_gather(_ptr(cache), dt, N, L, _ptr(idx_a), _ptr(idx_b), n, _ptr(out), _stream(cache.device))
+    _lib.check(rc, "dg_featcache_gather")
+    return out
+
+
 def rec_loss_shapes(code, feats, weight, bias):
     """The reconstruction term's shape rules, on any device: code (B,D,h,w), feats (B,C,h,w) on the same grid, the decoder's weight
     (C,D,1,1) or (C,D) and bias (C,).  Returns (weight as (C,D), (B, D, C, h, w))."""

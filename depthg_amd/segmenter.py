@@ -46,6 +46,10 @@ is forced on, the step feeds (img, depth) / (img_pos, depth_pos) one pass at a t
 trains with the head (the head's d image_feat launch, dg_head_backward_input, carries the gradient to them).  There cfg.rec_weight > 0
 under guidance "sum" / "cross_attn" needs cfg.dg_rec_feats_grad: the reconstruction term then reads the first pass's attached feats, its
 backward writes d feats (dg_rec_feats_backward) and the head adds it into d image_feat (dg_head_backward_input's grad_feats_out).
+With cfg.dg_feature_cache (build-side key, None by default; arch "dino") a batch that carries `image_feat` / `image_feat_pos` - the frozen
+backbone's outputs, kept by feature_cache.FeatureCache and gathered per batch by data.ContrastiveBatches - starts behind the backbone
+(FrozenBackboneFeaturizer.forward_pair_features / forward_features): the two backbone passes of :194-212 are not run, the head's draws and
+launches are unchanged.
 """
 from types import SimpleNamespace
 from typing import Dict, Optional
@@ -126,6 +130,9 @@ class UnsupervisedSegmenter(nn.Module):
         self.depth_arch = getattr(cfg, "arch", "dino") == "dino_depth"
         if self.depth_arch:
             self._refuse_depth_arch_combinations(cfg)
+        if getattr(cfg, "dg_feature_cache", None) and getattr(cfg, "lhp", False) and getattr(cfg, "propagation_strategy", "depth") == "attn":
+            raise ValueError("depthg_amd: cfg.dg_feature_cache cannot be combined with cfg.lhp under propagation_strategy = 'attn': the "
+                             "cache keeps image_feat, not the last block's attention map the LHP module would read")
         if net is None:                                                               # :99-108
             # cfg.dg_dino_backbone (build-side key, off by default): the real DINO ViT (featurizer.DinoFeaturizer) instead of the stand-in
             real = getattr(cfg, "dg_dino_backbone", False)
@@ -313,14 +320,23 @@ class UnsupervisedSegmenter(nn.Module):
         paired = cfg.correspondence_weight > 0 and not getattr(cfg, "lhp", False) and hasattr(self.net, "forward_pair") and self.net.training \
             and not self.depth_arch
         rec_feats = None                                          # the first pass's ATTACHED feats, where the reconstruction term gets them
+        # cfg.dg_feature_cache (build-side key, absent or None by default): a batch that carries `image_feat` / `image_feat_pos` - the
+        # frozen backbone's outputs, kept by feature_cache.FeatureCache and gathered by data.ContrastiveBatches - starts behind the
+        # backbone; the head's draws and launches are what they are without it.  (The third pass of the augmentation-alignment term
+        # still runs the backbone on img_aug.)
+        cached = bool(getattr(cfg, "dg_feature_cache", None)) and "image_feat" in batch and "image_feat_pos" in batch and \
+            not self.depth_arch and hasattr(self.net, "forward_pair_features")
         if paired:
             # (on the dense identity grid the Dropout2d of the returned feats is applied by the loss's operand preparation: the
             #  dropped feature tensors are never written - ops.DeferredDropout)
             p = getattr(self.net, "patch_size", None)
             defer = p is not None and getattr(self.net, "supports_deferred_dropout", False) and \
                 self.contrastive_corr_loss_fn.takes_deferred_dropout((img.shape[2] // p, img.shape[3] // p))
-            (feats, code, attn), (feats_pos, code_pos, _) = self.net.forward_pair(img, img_pos, defer) if defer else \
-                self.net.forward_pair(img, img_pos)                                                  # :194-200, :207-212
+            if cached:
+                (feats, code, attn), (feats_pos, code_pos, _) = self.net.forward_pair_features(batch["image_feat"], batch["image_feat_pos"], defer)
+            else:
+                (feats, code, attn), (feats_pos, code_pos, _) = self.net.forward_pair(img, img_pos, defer) if defer else \
+                    self.net.forward_pair(img, img_pos)                                              # :194-200, :207-212
         elif self.depth_arch:
             # (feats carry a graph under guidance "sum" / "cross_attn"; the correlation loss reads them under no_grad, src/modules.py:1232-1234)
             feats, code, image_feat, attn = self.net((img, depth))                                   # :191-197
@@ -328,8 +344,14 @@ class UnsupervisedSegmenter(nn.Module):
             if getattr(cfg, "dg_rec_feats_grad", False) and getattr(cfg, "rec_weight", 0) > 0 and feats.requires_grad:
                 rec_feats = feats
             feats = feats.detach()
+        elif cached:
+            feats, code, attn = self.net.forward_features(batch["image_feat"])
         else:
             feats, code, attn = self.net(img)                                                        # :194-200
+        if cached and attn is None and getattr(cfg, "lhp", False):
+            # (the LHP module projects without propagating when `attn is None`, :191-192; the featurizers hand it a placeholder where
+            #  nothing reads the map - so does the cached pass: the "attn" strategy, which would read it, is refused at construction)
+            attn = torch.zeros(1, device=code.device)
         lhp_code = self.lhp_module(code, depth, img, attn) if getattr(cfg, "lhp", False) else None    # :202-203
         logs: Dict[str, torch.Tensor] = {}
         loss = 0
@@ -338,7 +360,7 @@ class UnsupervisedSegmenter(nn.Module):
                 feats_pos, code_pos, image_feat_pos, _ = self.net((img_pos, depth_pos))              # :205-210
                 feats_pos = feats_pos.detach()
             elif not paired:
-                feats_pos, code_pos, _ = self.net(img_pos)                                           # :207-212
+                feats_pos, code_pos, _ = self.net.forward_features(batch["image_feat_pos"]) if cached else self.net(img_pos)   # :207-212
             lhp_code_pos = self.lhp_module(code_pos, None) if getattr(cfg, "lhp", False) else None   # :214-215
             salience = batch["mask"].to(torch.float32).squeeze(1) if cfg.use_salience else None      # :233-238
             salience_pos = batch["mask_pos"].to(torch.float32).squeeze(1) if cfg.use_salience else None
@@ -541,7 +563,10 @@ def default_segmenter_cfg(**over) -> SimpleNamespace:
         # the same arch under guidance "sum" / "cross_attn" with rec_weight > 0 (refused without this key): the reconstruction term
         # reads the featurizer's ATTACHED feats and its backward writes d feats as well (rec_loss.reconstruction_loss(feats_grad=True)),
         # so the term trains the depth modules as in the reference; under any other arch or guidance the key changes nothing
-        dg_rec_feats_grad=False)
+        dg_rec_feats_grad=False,
+        # build-side, arch "dino": None, or the storage type ("float32", "float16", "bfloat16") of a feature_cache.FeatureCache - a
+        # batch that carries `image_feat` / `image_feat_pos` (data.ContrastiveBatches(feature_cache=...)) then skips the frozen backbone
+        dg_feature_cache=None)
     for k, v in over.items():
         setattr(cfg, k, v)
     return cfg

@@ -1,6 +1,6 @@
 """Train a segmenter from a dataset folder: the loop of src/train_segmentation.py:551-714 without Lightning, Hydra, TensorBoard or wandb.
 
-    python -m depthg_amd.train --data-dir D --out O [--dataset directory] [--precompute-knns] [--device cuda:0] [key=value ...]
+    python -m depthg_amd.train --data-dir D --out O [--dataset directory] [--precompute-knns] [--feature-cache float32] [--device cuda:0] [key=value ...]
 
 builds the train pipeline (data.CroppedFolder, or data.DirectoryFolder with --dataset directory, under data.ContrastiveBatches: the
 loader transform of a batch and its kNN positives is one fused HIP launch) from the cfg keys dataset_name, crop_type, crop_ratio, res,
@@ -8,7 +8,10 @@ loader_crop_type, num_neighbors, use_depth, depth_type, batch_size and max_steps
 "mae") with a centre crop (none for dataset_name "voc"), an UnsupervisedSegmenter, and runs `fit`.  Keys come from
 segmenter.default_segmenter_cfg and TRAIN_DEFAULTS, overridden by `key=value` arguments (values are read as Python literals where
 they parse, else as strings; `~` and `null` are None).  --precompute-knns writes a missing nearest-neighbour table first
-(data.precompute_knns).  The reference reads its val set from the uncropped dataset classes; here both splits come from the same
+(data.precompute_knns).  --feature-cache {float32,float16,bfloat16} (cfg.dg_feature_cache) runs the frozen backbone over the train split
+once behind that, keeps its features in a feature_cache.FeatureCache - saved as <data-dir>/feature_cache_<meta>.pt and loaded from there when
+the file exists and matches - and trains from them: the step skips the backbone (loader_crop_type "center" or None, arch "dino"; validation
+is untouched).  The reference reads its val set from the uncropped dataset classes; here both splits come from the same
 folder layout (cfg.val_crop_type names the val folder's crop, default: cfg.crop_type).
 
 `fit(model, train_batches, val_batches, cfg, out_dir)`:
@@ -139,8 +142,32 @@ def build_dataset(cfg, data_dir, image_set, return_depth):
     return data.CroppedFolder(data_dir, cfg.dataset_name, crop, cfg.crop_ratio, image_set, return_depth=return_depth, depth_type=cfg.depth_type)
 
 
-def build_pipelines(cfg, data_dir, device, precompute=False, net=None):
-    """(train_batches, val_batches, n_classes) of cfg (:614-658).  `precompute`: write the train table first when it is missing, with `net`."""
+def train_feature_cache(cfg, data_dir, device, train_set, net, dtype):
+    """The train split's feature_cache.FeatureCache of storage type `dtype`: loaded from <data_dir>/feature_cache_<meta>.pt when that file
+    exists and its metadata match, else built with the featurizer `net` (data.build_feature_cache) and saved there."""
+    from . import data
+    from .feature_cache import FeatureCache
+    meta = data.feature_cache_meta(cfg, train_set, cfg.res, cfg.loader_crop_type)
+    path = data.feature_cache_path(data_dir, meta, "train", dtype)
+    if os.path.exists(path):
+        try:
+            cache = FeatureCache.load(path, device, expect_meta=meta)
+            if bool(cache.filled.all()):
+                print(f"depthg_amd.train: feature cache loaded from {path} ({cache.nbytes} bytes)")
+                return cache
+        except ValueError as e:
+            print(f"depthg_amd.train: {path} does not match ({e}); rebuilding")
+    cache = data.build_feature_cache(net, train_set, cfg, cfg.res, cfg.loader_crop_type, dtype=dtype, device=device,
+                                     batch_size=min(128 if cfg.model_type == "vit_small" else 64, max(len(train_set), 1)),
+                                     num_workers=cfg.num_workers)
+    cache.save(path)
+    print(f"depthg_amd.train: feature cache built and saved to {path} ({cache.nbytes} bytes)")
+    return cache
+
+
+def build_pipelines(cfg, data_dir, device, precompute=False, net=None, feature_cache=None):
+    """(train_batches, val_batches, n_classes) of cfg (:614-658).  `precompute`: write the train table first when it is missing, with `net`.
+    `feature_cache`: None, or the storage type of the train split's feature cache (train_feature_cache; `net` supplies the featurizer)."""
     from . import data, knn
     train_set = build_dataset(cfg, data_dir, "train", bool(cfg.use_depth))
     if train_set.n_classes is None:
@@ -149,9 +176,13 @@ def build_pipelines(cfg, data_dir, device, precompute=False, net=None):
     if precompute and not os.path.exists(path):
         data.precompute_knns(net(train_set.n_classes), train_set, cfg, cfg.res, "train", train_set.crop_type, num_workers=cfg.num_workers,
                              device=device, batch_size=min(128 if cfg.model_type == "vit_small" else 64, max(len(train_set), 1)))
+    cache = None
+    if feature_cache is not None:
+        cache = train_feature_cache(cfg, data_dir, device, train_set, net(train_set.n_classes), feature_cache)
     gen = torch.Generator().manual_seed(0)                                                                           # seed_everything(0), :590
     train_batches = data.ContrastiveBatches(train_set, cfg, "train", cfg.res, cfg.loader_crop_type, cfg.batch_size, shuffle=True, generator=gen,
-                                            num_workers=cfg.num_workers, pos=True, return_depth=bool(cfg.use_depth), device=device)
+                                            num_workers=cfg.num_workers, pos=True, return_depth=bool(cfg.use_depth), device=device,
+                                            feature_cache=cache)
     eval_res = 224 if cfg.model_type == "mae" else 320                                                               # :597-600
     val_crop = None if cfg.dataset_name == "voc" else "center"                                                       # :632-635
     val_set = build_dataset(cfg, data_dir, "val", False)
@@ -167,12 +198,20 @@ def main(argv=None) -> int:
     ap.add_argument("--dataset", default=None, help="`directory`: imgs/{split} and labels/{split} under --data-dir (sets dataset_name)")
     ap.add_argument("--precompute-knns", action="store_true", help="write the nearest-neighbour table first when it is missing")
     ap.add_argument("--device", default="cuda:0")
+    ap.add_argument("--feature-cache", choices=("float32", "float16", "bfloat16"), default=None,
+                    help="keep the frozen backbone's features of the train split in this type and train from them (sets dg_feature_cache); "
+                         "built once, saved as feature_cache_<meta>.pt under --data-dir and loaded from there afterwards")
     ap.add_argument("overrides", nargs="*", help="cfg keys as key=value")
     args = ap.parse_args(argv)
     overrides = parse_overrides(args.overrides)
     if args.dataset is not None:
         overrides["dataset_name"] = args.dataset
+    if args.feature_cache is not None:
+        overrides["dg_feature_cache"] = args.feature_cache
     cfg = build_cfg(overrides)
+    if getattr(cfg, "dg_feature_cache", None) and getattr(cfg, "arch", "dino") == "dino_depth":
+        raise ValueError("depthg_amd.train: --feature-cache serves cfg.arch = 'dino'; the depth-guided featurizer (arch 'dino_depth') is out of "
+                         "scope for the feature cache")
     if not torch.cuda.is_available():
         sys.exit("depthg_amd.train: no GPU (training_step has no CPU route)")
     device = torch.device(args.device)
@@ -191,7 +230,8 @@ def main(argv=None) -> int:
                              "table under arch='dino' first")
         return model.net
 
-    train_batches, val_batches, n_classes = build_pipelines(cfg, args.data_dir, device, args.precompute_knns, knn_net)
+    train_batches, val_batches, n_classes = build_pipelines(cfg, args.data_dir, device, args.precompute_knns, knn_net,
+                                                            getattr(cfg, "dg_feature_cache", None))
     model = model_for(n_classes)
     model.train()
     state = fit(model, train_batches, val_batches, cfg, args.out)

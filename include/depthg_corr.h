@@ -1027,6 +1027,37 @@ int dg_batch_prep(const uint8_t* packed, size_t packed_bytes, const int32_t* rec
                   const void* params, int32_t n_records, int32_t N, int32_t H, int32_t W, const float* mean, const float* stdv,
                   float* img, int64_t* label, void* mask, float* depth, dg_stream_t stream);
 
+/*
+ * Frozen-backbone feature cache (dg_feat_cache.hip).  The backbone is frozen, runs in eval mode and draws nothing (src/modules.py:90-137:
+ * `image_feat` under no_grad), and a deterministic loader transform feeds it, so the `image_feat` of train image i that the step's two
+ * featurizer passes recompute every epoch (src/train_segmentation.py:194-212) is one tensor: it is stored once and read back per batch.
+ *  cache : (N, L) rows, L = C h w, of `dtype` (below) on the device; row i = image_feat of image i, flattened
+ * dg_featcache_put (k_fc_put): rows idx[0..n) of the cache = src (n, L) fp32 converted to `dtype` - DG_FC_F32 a copy, DG_FC_F16 and
+ *  DG_FC_BF16 round to nearest even with the bits of torch's .to(dtype) on a tensor: infinities stay, overflow rounds to infinity,
+ *  fp16 subnormals are formed, a fp16 NaN keeps its sign and the top ten payload bits and is quiet, EVERY bf16 NaN is 0xFFFF
+ *  (what torch's vectorised CPU cast stores; c10::BFloat16's scalar constructor gives 0x7FC0 - both are quiet NaNs).
+ *  The caller gives each row once per call (two lanes would race for it otherwise); the entry cannot see that: the index lives on the device.
+ * dg_featcache_gather (k_fc_gather): out (2n, L) fp32, rows 0..n-1 = cache rows idx_a[0..n), rows n..2n-1 = cache rows idx_b[0..n),
+ *  widened exactly - ONE launch and one allocation for a batch and its positives, laid out as the head's paired pass takes its two
+ *  maps (dg_head_forward's feats / feats_pos = out and out + n L).  idx_b may be NULL: out is (n, L).  An index may repeat, within a
+ *  list and between the two.
+ * idx, idx_a, idx_b : int64 on the DEVICE, read by the kernels.  The caller checks them on the host beforehand; a row index outside
+ *  [0, N) is never dereferenced all the same: that row is skipped (in gather its output row stays unwritten).
+ * Both kernels stream: a lane moves 16 bytes of the cache per access (eight 16-bit elements = two 16-byte fp32 accesses, or four fp32)
+ * wherever the cache row and the fp32 row reach a 16-byte boundary at the same element, one element per lane in front of that boundary
+ * and behind the last whole vector - and over the whole row where they never do (L need not be a multiple of 8).  No LDS, no atomics,
+ * no workspace, no allocation, no host synchronisation; every element of the rows named is written exactly once, two calls give the
+ * same bytes.  Refused before any launch: DG_ERR_INVALID for an unknown dtype, N < 1, L < 1, n < 0, null or misaligned pointers (the
+ * cache on its element size, fp32 tensors on 4 bytes, indices on 8); DG_ERR_UNSUPPORTED for more than 65535 rows a call.  n == 0: nothing.
+ */
+#define DG_FC_F32  0
+#define DG_FC_F16  1
+#define DG_FC_BF16 2
+int dg_featcache_put(void* cache, int32_t dtype, int64_t N, int64_t L, const float* src, const int64_t* idx, int64_t n,
+                     dg_stream_t stream);
+int dg_featcache_gather(const void* cache, int32_t dtype, int64_t N, int64_t L, const int64_t* idx_a, const int64_t* idx_b, int64_t n,
+                        float* out, dg_stream_t stream);
+
 /* Measurement aid: name of the kernel the fused correlation launch of this descriptor runs ("k_corr2": the one-wave-per-SIMD
  * form of dg_corr2.hip, "k_corr_main": the general form), decided by the same predicate the launch uses; NULL on a bad desc. */
 const char* dg_corr_main_kernel_name(const dg_corr_desc* desc);
