@@ -43,6 +43,9 @@ Public surface (mirrors the reference's Python operator surface for this path):
                                  float16 or bfloat16 and gathered per batch and positives in ONE HIP launch (k_fc_put / k_fc_gather);
                                  data.build_feature_cache fills it, cfg.dg_feature_cache makes the step start from it
                                  (src/train_segmentation.py:194-212 without the two backbone passes)
+    sample_cache / SampleCache   the loader transform's output bytes of every image, label and depth map of a split on the device; a batch
+                                 and its positives come back as img / label / mask / depth from ONE launch (k_sc_gather), no decoding:
+                                 data.build_sample_cache fills it, ContrastiveBatches(sample_cache=...) reads it
     train                        fit(model, train_batches, val_batches, cfg, out_dir): the loop of src/train_segmentation.py:551-714 without
                                  Lightning; `python -m depthg_amd.train` is its command line
     ops                          thin ctypes binding of the C ABI in include/depthg_corr.h; ops.corr_forward is the one route to its five
@@ -80,8 +83,12 @@ from .data import ContrastiveBatches, CroppedFolder, DirectoryFolder, loader_ind
 from . import feature_cache  # noqa: F401
 from .feature_cache import FeatureCache  # noqa: F401
 from .data import build_feature_cache  # noqa: F401
+from . import sample_cache  # noqa: F401
+from .sample_cache import SampleCache  # noqa: F401
+from .data import build_sample_cache  # noqa: F401
 
 __all__ = ["ContrastiveCorrelationLoss", "DepthContrastiveCorrelationLoss", "ContrastiveCRFLoss", "crf_loss", "aug_loss", "aug_alignment_loss", "crop_flip_coords", "augment", "AugmentParams", "augment_batch", "draw_augment_params", "rec_loss", "reconstruction_loss", "depth_encoder", "cross_attn", "cross_attention", "multihead_cross_attention", "depth_decay", "training", "metrics", "evaluation", "predict_and_score", "segment", "crf", "dense_crf",
            "batched_crf", "knn", "lhp", "optim", "FusedAdam", "FusedAdamSet", "segmenter", "vit", "featurizer",
            "DinoFeaturizer", "DinoFeaturizerWithDepth", "data", "ContrastiveBatches", "CroppedFolder", "DirectoryFolder",
-           "loader_index_tables", "precompute_knns", "feature_cache", "FeatureCache", "build_feature_cache"]
+           "loader_index_tables", "precompute_knns", "feature_cache", "FeatureCache", "build_feature_cache",
+           "sample_cache", "SampleCache", "build_sample_cache"]

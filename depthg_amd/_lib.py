@@ -137,6 +137,9 @@ SIGNATURES = {
     # frozen-backbone feature cache
     "dg_featcache_put": (_I, [vp, i32, i64, i64, vp, vp, i64, vp]),
     "dg_featcache_gather": (_I, [vp, i32, i64, i64, vp, vp, i64, vp, vp]),
+    # device-resident sample cache
+    "dg_samplecache_put": (_I, [vp, i64] + [i32] * 4 + [vp, i32, vp, _SZ, vp, vp, vp, i32, vp]),
+    "dg_samplecache_gather": (_I, [vp, i64] + [i32] * 4 + [vp, vp, i32, vp, vp] + [i32] * 3 + [vp] * 5),
     # measurement aids
     "dg_corr_main_kernel_name": (_STR, [cp]),
     "dg_corr_intra_folded": (_I, [cp]),

@@ -1,5 +1,5 @@
 // C ABI of the gfx950 DepthG library (include/depthg_corr.h), the units' shared state and the small subsystems: version and error
-// text, the library's side stream, batch maps / random draws / coordinate samplers, kNN, LHP, fused Adam, ViT attention and linear, the fused depth encoder, the depth guidance's cross-attention, the GPU batch augmentation, the batch preparation, the frozen-backbone feature cache.  (The auxiliary loss terms: dg_api_loss.hip.)
+// text, the library's side stream, batch maps / random draws / coordinate samplers, kNN, LHP, fused Adam, ViT attention and linear, the fused depth encoder, the depth guidance's cross-attention, the GPU batch augmentation, the batch preparation, the frozen-backbone feature cache, the device-resident sample cache.  (The auxiliary loss terms: dg_api_loss.hip.)
 // Host-side only: argument checks and kernel launches on the caller's stream.
 #include "dg_api.h"
 #include "dg_aux_args.h"
@@ -515,6 +515,28 @@ extern "C" int dg_augment_forward(const float* img, int64_t stride_b, int64_t st
 }
 
 // ---- batch preparation (dg_batch.hip)
+// a record that reads a source plane: the plane lies inside `packed` and holds every pixel its sample's tables (xs[W], ys[H]) address
+static int batch_source_check(const char* who, int i, const int32_t* r, const int32_t* xs, int32_t H, int32_t W, const uint8_t* packed,
+                              size_t packed_bytes) {
+    const int kind = r[0], sw = r[4], sh = r[5];
+    const unsigned long long off = (unsigned long long)(uint32_t)r[2] | ((unsigned long long)(uint32_t)r[3] << 32);
+    if (sw < 1 || sh < 1) return fail(DG_ERR_INVALID, "%s: record %d: zero-sized source plane %dx%d", who, i, sw, sh);
+    if (sw > DG_BATCH_MAX_SIDE || sh > DG_BATCH_MAX_SIDE)
+        return fail(DG_ERR_UNSUPPORTED, "%s: record %d: source plane %dx%d above %d a side", who, i, sw, sh, DG_BATCH_MAX_SIDE);
+    const unsigned long long bytes = (unsigned long long)sw * sh * (kind == DG_BATCH_IMAGE ? 3 : 1);
+    if (!packed || off > packed_bytes || bytes > packed_bytes - off)
+        return fail(DG_ERR_INVALID, "%s: record %d: plane of %llu bytes at offset %llu leaves the packed buffer of %zu bytes", who, i, bytes, off,
+                    packed_bytes);
+    const int32_t* ys = xs + W;
+    for (int x = 0; x < W; ++x)
+        if (xs[x] < 0 || xs[x] >= sw)
+            return fail(DG_ERR_INVALID, "%s: record %d: column table entry %d = %d outside the source width %d (the plane is narrower than the tables address)", who, i, x, xs[x], sw);
+    for (int y = 0; y < H; ++y)
+        if (ys[y] < 0 || ys[y] >= sh)
+            return fail(DG_ERR_INVALID, "%s: record %d: row table entry %d = %d outside the source height %d (the plane is shorter than the tables address)", who, i, y, ys[y], sh);
+    return DG_OK;
+}
+
 extern "C" int dg_batch_prep(const uint8_t* packed, size_t packed_bytes, const int32_t* records_host, const int32_t* tables_host,
                              const void* params, int32_t n_records, int32_t N, int32_t H, int32_t W, const float* mean, const float* stdv,
                              float* img, int64_t* label, void* mask, float* depth, dg_stream_t stream_) {
@@ -539,8 +561,7 @@ extern "C" int dg_batch_prep(const uint8_t* packed, size_t packed_bytes, const i
     int n_out[3] = {0, 0, 0}, rule = -1;
     for (int i = 0; i < n_records; ++i) {
         const int32_t* r = records_host + (size_t)i * DG_BATCH_REC_WORDS;
-        const int kind = r[0], n = r[1], sw = r[4], sh = r[5];
-        const unsigned long long off = (unsigned long long)(uint32_t)r[2] | ((unsigned long long)(uint32_t)r[3] << 32);
+        const int kind = r[0], n = r[1];
         if (kind < DG_BATCH_IMAGE || kind > DG_BATCH_LABEL_FILL) return fail(DG_ERR_INVALID, "dg_batch_prep: record %d: unknown kind %d (0 .. 4)", i, kind);
         if (n < 0 || n >= N) return fail(DG_ERR_INVALID, "dg_batch_prep: record %d: sample %d outside 0 .. %d", i, n, N - 1);
         const bool labels = kind == DG_BATCH_LABEL || kind == DG_BATCH_LABEL_FILL;
@@ -556,21 +577,7 @@ extern "C" int dg_batch_prep(const uint8_t* packed, size_t packed_bytes, const i
             rule = r[7];
         }
         if (kind == DG_BATCH_DEPTH_PLANE || kind == DG_BATCH_LABEL_FILL) continue;      // no source
-        if (sw < 1 || sh < 1) return fail(DG_ERR_INVALID, "dg_batch_prep: record %d: zero-sized source plane %dx%d", i, sw, sh);
-        if (sw > DG_BATCH_MAX_SIDE || sh > DG_BATCH_MAX_SIDE)
-            return fail(DG_ERR_UNSUPPORTED, "dg_batch_prep: record %d: source plane %dx%d above %d a side", i, sw, sh, DG_BATCH_MAX_SIDE);
-        const unsigned long long bytes = (unsigned long long)sw * sh * (kind == DG_BATCH_IMAGE ? 3 : 1);
-        if (!packed || off > packed_bytes || bytes > packed_bytes - off)
-            return fail(DG_ERR_INVALID, "dg_batch_prep: record %d: plane of %llu bytes at offset %llu leaves the packed buffer of %zu bytes", i, bytes, off,
-                        packed_bytes);
-        const int32_t* xs = tables_host + (size_t)n * (W + H);
-        const int32_t* ys = xs + W;
-        for (int x = 0; x < W; ++x)
-            if (xs[x] < 0 || xs[x] >= sw)
-                return fail(DG_ERR_INVALID, "dg_batch_prep: record %d: column table entry %d = %d outside the source width %d (the plane is narrower than the tables address)", i, x, xs[x], sw);
-        for (int y = 0; y < H; ++y)
-            if (ys[y] < 0 || ys[y] >= sh)
-                return fail(DG_ERR_INVALID, "dg_batch_prep: record %d: row table entry %d = %d outside the source height %d (the plane is shorter than the tables address)", i, y, ys[y], sh);
+        if (int rc = batch_source_check("dg_batch_prep", i, r, tables_host + (size_t)n * (W + H), H, W, packed, packed_bytes)) return rc;
     }
     const void* outs[3] = {img, label, depth};
     for (int o = 0; o < 3; ++o)
@@ -618,5 +625,101 @@ extern "C" int dg_featcache_gather(const void* cache, int32_t dtype, int64_t N, 
         return fail(DG_ERR_INVALID, "dg_featcache_gather: out must be 4-byte aligned, idx_a and idx_b 8-byte aligned");
     DG_HIP(dg_launch_featcache_gather(cache, dtype, N, L, reinterpret_cast<const long long*>(idx_a), reinterpret_cast<const long long*>(idx_b),
                                       (int)n, out, static_cast<hipStream_t>(stream_)));
+    return DG_OK;
+}
+
+// ---- device-resident sample cache (dg_sample_cache.hip)
+// what both entries refuse before a launch; `lists`: index lists of n rows each
+static int samplecache_check(const char* who, const void* cache, int64_t n_images, int32_t has_labels, int32_t with_depth, int32_t H, int32_t W,
+                             int64_t n, int lists) {
+    if (n_images < 1 || H < 1 || W < 1 || n < 0)
+        return fail(DG_ERR_INVALID, "%s: n_images=%lld, rows of %dx%d, n=%lld (n_images, H and W positive, n not negative)", who, (long long)n_images, H,
+                    W, (long long)n);
+    if ((has_labels != 0 && has_labels != 1) || (with_depth != 0 && with_depth != 1))
+        return fail(DG_ERR_INVALID, "%s: has_labels=%d with_depth=%d (0 or 1 each)", who, has_labels, with_depth);
+    if (W % 4) return fail(DG_ERR_UNSUPPORTED, "%s: row width %d is not a multiple of 4 (a lane moves four columns as one word)", who, W);
+    if (H > DG_BATCH_MAX_SIDE || W > DG_BATCH_MAX_SIDE) return fail(DG_ERR_UNSUPPORTED, "%s: rows of %dx%d above %d a side", who, H, W, DG_BATCH_MAX_SIDE);
+    if (n > DG_SC_MAX_ROWS / lists)
+        return fail(DG_ERR_UNSUPPORTED, "%s: %d list(s) of %lld rows in one call (at most %d rows)", who, lists, (long long)n, DG_SC_MAX_ROWS);
+    if (n_images > (1ll << 62) / ((long long)5 * H * W)) return fail(DG_ERR_UNSUPPORTED, "%s: a cache of %lld rows of %dx%d", who, (long long)n_images, H, W);
+    if (!cache) return fail(DG_ERR_INVALID, "%s: null pointer", who);
+    if ((uintptr_t)cache & 3) return fail(DG_ERR_INVALID, "%s: the cache must be 4-byte aligned (a lane moves four bytes as one word)", who);
+    return DG_OK;
+}
+
+extern "C" int dg_samplecache_put(uint8_t* cache, int64_t n_images, int32_t has_labels, int32_t with_depth, int32_t H, int32_t W,
+                                  const int64_t* idx, int32_t n, const uint8_t* packed, size_t packed_bytes, const int32_t* records_host,
+                                  const int32_t* tables_host, const void* params, int32_t n_records, dg_stream_t stream_) {
+    if (int rc = samplecache_check(__func__, cache, n_images, has_labels, with_depth, H, W, n, 1)) return rc;
+    if (n == 0) return DG_OK;
+    if (n_records < 1 || n_records > 65535) return fail(DG_ERR_INVALID, "dg_samplecache_put: n_records=%d outside [1, 65535]", n_records);
+    if (!idx || !records_host || !tables_host || !params) return fail(DG_ERR_INVALID, "dg_samplecache_put: null pointer");
+    if (((uintptr_t)idx & 7) || ((uintptr_t)params & 3)) return fail(DG_ERR_INVALID, "dg_samplecache_put: idx must be 8-byte aligned, params 4-byte aligned");
+    // which plane group of each sample has a record: every byte of every row is written, and by one record
+    std::vector<uint8_t> seen((size_t)3 * n, 0);
+    int n_out[3] = {0, 0, 0};
+    for (int i = 0; i < n_records; ++i) {
+        const int32_t* r = records_host + (size_t)i * DG_BATCH_REC_WORDS;
+        const int kind = r[0], k = r[1];
+        if (kind < DG_BATCH_IMAGE || kind > DG_BATCH_LABEL_FILL) return fail(DG_ERR_INVALID, "dg_samplecache_put: record %d: unknown kind %d (0 .. 4)", i, kind);
+        if (k < 0 || k >= n) return fail(DG_ERR_INVALID, "dg_samplecache_put: record %d: sample %d outside 0 .. %d", i, k, n - 1);
+        const int out = kind == DG_BATCH_IMAGE ? 0 : (kind == DG_BATCH_LABEL || kind == DG_BATCH_LABEL_FILL) ? 1 : 2;
+        if (kind == DG_BATCH_LABEL && !has_labels)
+            return fail(DG_ERR_INVALID, "dg_samplecache_put: record %d: sample %d carries a label but the cache has no label plane", i, k);
+        if (kind == DG_BATCH_LABEL_FILL && has_labels)
+            return fail(DG_ERR_INVALID, "dg_samplecache_put: record %d: sample %d carries no label but the cache has a label plane", i, k);
+        if (out == 2 && !with_depth) return fail(DG_ERR_INVALID, "dg_samplecache_put: record %d: sample %d carries depth but the cache has no depth plane", i, k);
+        if (seen[(size_t)out * n + k]++) return fail(DG_ERR_INVALID, "dg_samplecache_put: record %d: plane group %d of sample %d is written twice", i, out, k);
+        ++n_out[out];
+        if (kind == DG_BATCH_DEPTH_PLANE || kind == DG_BATCH_LABEL_FILL) continue;      // no source
+        if (int rc = batch_source_check("dg_samplecache_put", i, r, tables_host + (size_t)k * (W + H), H, W, packed, packed_bytes)) return rc;
+    }
+    if (n_out[0] != n || (has_labels && n_out[1] != n) || n_out[2] != (with_depth ? n : 0))
+        return fail(DG_ERR_INVALID, "dg_samplecache_put: records for %d images, %d labels and %d depth maps of %d samples (every byte of a row must be written)",
+                    n_out[0], n_out[1], n_out[2], n);
+    DgSampleCachePutArgs A;
+    memset(&A, 0, sizeof(A));
+    A.cache = cache; A.idx = reinterpret_cast<const long long*>(idx); A.packed = packed;
+    A.recs = static_cast<const int32_t*>(params);
+    A.tables = A.recs + (size_t)n_records * DG_BATCH_REC_WORDS;
+    A.n_images = n_images; A.planes = 3 + has_labels + with_depth;
+    A.label_plane = has_labels ? 3 : -1; A.depth_plane = with_depth ? 3 + has_labels : -1;
+    A.n_records = n_records; A.n = n; A.H = H; A.W = W;
+    A.tiles_x = (W + DG_BATCH_TW - 1) / DG_BATCH_TW; A.tiles_y = (H + DG_BATCH_TH - 1) / DG_BATCH_TH;
+    DG_HIP(dg_launch_samplecache_put(A, static_cast<hipStream_t>(stream_)));
+    return DG_OK;
+}
+
+extern "C" int dg_samplecache_gather(const uint8_t* cache, int64_t n_images, int32_t has_labels, int32_t with_depth, int32_t H, int32_t W,
+                                     const int64_t* idx_a, const int64_t* idx_b, int32_t n, const float* mean, const float* stdv,
+                                     int32_t label_offset, int32_t fill, int32_t mask_rule, float* img, int64_t* label, void* mask, float* depth,
+                                     dg_stream_t stream_) {
+    if (int rc = samplecache_check(__func__, cache, n_images, has_labels, with_depth, H, W, n, idx_b ? 2 : 1)) return rc;
+    if (n == 0) return DG_OK;
+    if (!idx_a) return fail(DG_ERR_INVALID, "dg_samplecache_gather: null pointer");
+    if (((uintptr_t)idx_a | (uintptr_t)idx_b) & 7) return fail(DG_ERR_INVALID, "dg_samplecache_gather: idx_a and idx_b must be 8-byte aligned");
+    if (!img && !label && !mask && !depth) return fail(DG_ERR_INVALID, "dg_samplecache_gather: no output asked for");
+    if (((uintptr_t)img | (uintptr_t)label | (uintptr_t)mask | (uintptr_t)depth) & 15)
+        return fail(DG_ERR_INVALID, "dg_samplecache_gather: img, label, mask and depth must be 16-byte aligned (whole-vector stores)");
+    if (depth && !with_depth) return fail(DG_ERR_INVALID, "dg_samplecache_gather: depth asked of a cache without a depth plane");
+    if (mask && mask_rule != DG_BATCH_MASK_BOOL_IGNORED && mask_rule != DG_BATCH_MASK_FLOAT_POSITIVE)
+        return fail(DG_ERR_INVALID, "dg_samplecache_gather: unknown mask rule %d (0, 1)", mask_rule);
+    DgSampleCacheGatherArgs A;
+    memset(&A, 0, sizeof(A));
+    if (img) {
+        if (!mean || !stdv) return fail(DG_ERR_INVALID, "dg_samplecache_gather: img needs mean and stdv");
+        for (int c = 0; c < 3; ++c) {
+            A.mean[c] = mean[c]; A.stdv[c] = stdv[c];
+            if (!(A.stdv[c] > 0.f) || std::isinf(A.stdv[c]) || !(A.mean[c] == A.mean[c]) || std::isinf(A.mean[c]))
+                return fail(DG_ERR_INVALID, "dg_samplecache_gather: channel %d: mean=%g std=%g", c, (double)A.mean[c], (double)A.stdv[c]);
+        }
+    }
+    A.cache = cache; A.idx_a = reinterpret_cast<const long long*>(idx_a); A.idx_b = reinterpret_cast<const long long*>(idx_b);
+    A.img = img; A.label = reinterpret_cast<long long*>(label); A.mask = mask; A.depth = depth;
+    A.n_images = n_images; A.planes = 3 + has_labels + with_depth;
+    A.label_plane = has_labels ? 3 : -1; A.depth_plane = with_depth ? 3 + has_labels : -1;
+    A.n = n; A.H = H; A.W = W;
+    A.label_offset = label_offset; A.fill = fill; A.mask_rule = mask_rule;
+    DG_HIP(dg_launch_samplecache_gather(A, static_cast<hipStream_t>(stream_)));
     return DG_OK;
 }

@@ -1,4 +1,4 @@
-// The stand-alone operations (dg_sample, dg_metrics, dg_knn, dg_lhp, dg_optim, dg_attn, dg_linear, dg_augment, dg_batch, dg_feat_cache .hip; dg_api_aux.hip): constants and launchers.
+// The stand-alone operations (dg_sample, dg_metrics, dg_knn, dg_lhp, dg_optim, dg_attn, dg_linear, dg_augment, dg_batch, dg_feat_cache, dg_sample_cache .hip; dg_api_aux.hip): constants and launchers.
 // (The auxiliary loss terms have a header of their own: dg_loss_args.h.)
 #pragma once
 #include "dg_common.h"
@@ -109,6 +109,45 @@ struct DgBatchArgs {
     float mean[3], stdv[3];
 };
 hipError_t dg_launch_batch_prep(const DgBatchArgs& A, hipStream_t s);
+// a table entry held inside its plane of n pixels a side (the host entries have checked a host copy of the tables)
+__device__ __forceinline__ int dg_hold(int v, int n) { return v < 0 ? 0 : (v >= n ? n - 1 : v); }
+// ToTensor's division, then Normalize's sub and div, on one byte: float32 with IEEE division and no contraction - the bits of torch's
+// CPU chain.  k_batch_prep and k_sc_gather both form their image through this one function, so the two cannot drift apart.
+__device__ __forceinline__ float dg_normalized_byte(uint8_t b, float mean, float stdv) {
+#pragma clang fp contract(off)
+    return ((float)b / 255.0f - mean) / stdv;
+}
+
+// ---- device-resident sample cache: the loader's output bytes of every image, stored once; a batch and its positives come back in the
+// step's dtypes from one launch (dg_sample_cache.hip; src/utils.py:164-182, src/data.py:894-902, :126-128)
+#define DG_SC_THREADS 256                    // k_sc_gather: one lane per four neighbouring pixels of a row's planes
+#define DG_SC_MAX_ROWS 65535                 // rows per gather call, both lists together (gridDim.y)
+struct DgSampleCachePutArgs {
+    uint8_t* cache;                          // (n_images, planes, H, W)
+    const long long* idx;                    // n cache rows, one per sample
+    const uint8_t* packed;                   // the decoded source planes of every sample, as DgBatchArgs
+    const int32_t* recs;                     // n_records records of DG_BATCH_REC_WORDS words
+    const int32_t* tables;                   // per sample xs[W] then ys[H]
+    long long n_images;
+    int planes, label_plane, depth_plane;    // a plane the cache lacks: -1
+    int n_records, n, H, W;
+    int tiles_x, tiles_y;
+};
+struct DgSampleCacheGatherArgs {
+    const uint8_t* cache;
+    const long long *idx_a, *idx_b;          // n rows each; idx_b null: n output rows, else 2 n
+    float* img;                              // (rows, 3, H, W); any output may be null
+    long long* label;                        // (rows, H, W)
+    void* mask;                              // (rows, H, W): bool bytes or float32, by mask_rule
+    float* depth;                            // (rows, H, W)
+    long long n_images;
+    int planes, label_plane, depth_plane;
+    int n, H, W;
+    int label_offset, fill, mask_rule;       // label = byte + label_offset, or `fill` without a label plane
+    float mean[3], stdv[3];
+};
+hipError_t dg_launch_samplecache_put(const DgSampleCachePutArgs& A, hipStream_t s);
+hipError_t dg_launch_samplecache_gather(const DgSampleCacheGatherArgs& A, hipStream_t s);
 
 // ---- frozen-backbone feature cache: store image_feat rows once, gather a batch and its positives in one launch (dg_feat_cache.hip;
 // src/modules.py:90-137, src/train_segmentation.py:194-212)

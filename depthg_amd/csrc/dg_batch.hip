@@ -28,8 +28,6 @@ constexpr int TH = DG_BATCH_TH, TW = DG_BATCH_TW, NT = DG_BATCH_THREADS;
 static_assert(NT == TH * (TW / 4), "one thread per four neighbouring output pixels");
 static_assert(NT >= TW + TH, "the tables of a tile are read by the threads 0 .. TW + TH - 1");
 
-__device__ __forceinline__ int hold(int v, int n) { return v < 0 ? 0 : (v >= n ? n - 1 : v); }
-
 }  // namespace
 
 // grid (tiles_x * tiles_y, n_records), block 256, 320 bytes of LDS.
@@ -47,10 +45,10 @@ __global__ __launch_bounds__(DG_BATCH_THREADS) void k_batch_prep(DgBatchArgs A) 
         const int32_t* xs = A.tables + (size_t)n * (A.W + A.H);
         const int32_t* ys = xs + A.W;
         if (tid < TW) {
-            s_x[tid] = tx0 + tid < A.W ? hold(xs[tx0 + tid], sw) : 0;
+            s_x[tid] = tx0 + tid < A.W ? dg_hold(xs[tx0 + tid], sw) : 0;
         } else if (tid < TW + TH) {
             const int k = tid - TW;
-            s_y[k] = ty0 + k < A.H ? hold(ys[ty0 + k], sh) : 0;
+            s_y[k] = ty0 + k < A.H ? dg_hold(ys[ty0 + k], sh) : 0;
         }
         __syncthreads();
     }
@@ -68,7 +66,7 @@ __global__ __launch_bounds__(DG_BATCH_THREADS) void k_batch_prep(DgBatchArgs A) 
         for (int j = 0; j < 4; ++j) {
             const uint8_t* px = row + (size_t)s_x[lx + j] * 3;
 #pragma unroll
-            for (int c = 0; c < 3; ++c) v[c][j] = ((float)px[c] / 255.0f - A.mean[c]) / A.stdv[c];
+            for (int c = 0; c < 3; ++c) v[c][j] = dg_normalized_byte(px[c], A.mean[c], A.stdv[c]);
         }
         float* dst = A.img + (size_t)n * 3 * oplane + opix;
 #pragma unroll

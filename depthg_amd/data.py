@@ -22,6 +22,10 @@ kNN positive).  All of it is a gather per output pixel and two float32 operation
     build_feature_cache               one pass of the frozen backbone over a split with a deterministic loader transform, kept as a
                                       feature_cache.FeatureCache; ContrastiveBatches(feature_cache=...) then adds `image_feat` /
                                       `image_feat_pos` to every batch (cfg.dg_feature_cache in the step)
+    build_sample_cache                one decoding pass over a split with a deterministic loader transform, kept as the transform's
+                                      output BYTES in a sample_cache.SampleCache on the device; ContrastiveBatches(sample_cache=...)
+                                      then forms img / label / mask / depth of a batch and its positives with one launch from the
+                                      indices alone: a cached epoch opens no file
 
 `img_aug` / `coord_aug` are not made here: cfg.dg_gpu_augment forms them inside the step (depthg_amd/augment.py).
 """
@@ -318,6 +322,14 @@ def prepare_samples(dataset, samples, res, crop_type, device, want_depth, genera
     return out["img"], out["label"], out["mask"], out.get("depth")
 
 
+def _decode_samples(dataset, indices, threads):
+    """dataset.load of every index, in a pool of `threads` threads (0: in the caller's thread)."""
+    if threads == 0 or len(indices) < 2:
+        return [dataset.load(i) for i in indices]
+    with ThreadPoolExecutor(max_workers=min(threads, len(indices))) as pool:
+        return list(pool.map(dataset.load, indices))
+
+
 class ContrastiveBatches:
     """The batches `UnsupervisedSegmenter.training_step` / `validation_step` read, as the reference's DataLoader over
     ContrastiveSegDataset collates them (src/data.py:1073-1141): ind (B,), img (B,3,H,W), label, mask, depth (B,1,H,W) and, with
@@ -328,7 +340,7 @@ class ContrastiveBatches:
     last batch may be short (DataLoader's drop_last=False).  No img_aug / coord_aug: cfg.dg_gpu_augment makes them in the step."""
 
     def __init__(self, dataset, cfg, image_set, res, loader_crop_type, batch_size, shuffle=False, generator=None, num_workers=0,
-                 pos=True, return_depth=None, device=None, feature_cache=None):
+                 pos=True, return_depth=None, device=None, feature_cache=None, sample_cache=None):
         self.dataset, self.cfg, self.image_set, self.res, self.loader_crop_type = dataset, cfg, image_set, int(res), loader_crop_type
         self.batch_size, self.shuffle, self.generator, self.pos = int(batch_size), bool(shuffle), generator, bool(pos)
         if self.batch_size < 1:
@@ -359,14 +371,28 @@ class ContrastiveBatches:
                 raise ValueError(f"depthg_amd.data: the feature cache holds {feature_cache.n_images} images on {feature_cache.device}, the "
                                  f"pipeline reads {len(dataset)} on {self.device}")
 
+        # sample_cache.SampleCache of this dataset's images under this loader transform (build_sample_cache): img / label / mask / depth of
+        # a batch and its positives then come from one gather launch over the cached bytes - nothing is decoded, packed or uploaded.
+        self.sample_cache = sample_cache
+        if sample_cache is not None:
+            if loader_crop_type == "random":
+                raise ValueError("depthg_amd.data: a sample cache holds the bytes of ONE view of every image; with loader_crop_type = "
+                                 "'random' the view changes with every draw")
+            if sample_cache.n_images != len(dataset) or sample_cache.device != self.device:
+                raise ValueError(f"depthg_amd.data: the sample cache holds {sample_cache.n_images} images on {sample_cache.device}, the "
+                                 f"pipeline reads {len(dataset)} on {self.device}")
+            if (sample_cache.H, sample_cache.W) != (self.res, self.res) or sample_cache.has_labels != bool(dataset.has_labels) or \
+                    (self.return_depth and not sample_cache.with_depth) or sample_cache.mask_rule != dataset.mask_rule or \
+                    (dataset.has_labels and sample_cache.label_offset != dataset.label_offset):
+                raise ValueError(f"depthg_amd.data: the sample cache ({sample_cache.H} x {sample_cache.W}, has_labels={sample_cache.has_labels}, "
+                                 f"with_depth={sample_cache.with_depth}) was not built for this pipeline (res {self.res}, "
+                                 f"has_labels={bool(dataset.has_labels)}, return_depth={self.return_depth}): build_sample_cache makes one that fits")
+
     def __len__(self):
         return (len(self.dataset) + self.batch_size - 1) // self.batch_size
 
     def _decode(self, indices):
-        if self.threads == 0 or len(indices) < 2:
-            return [self.dataset.load(i) for i in indices]
-        with ThreadPoolExecutor(max_workers=min(self.threads, len(indices))) as pool:
-            return list(pool.map(self.dataset.load, indices))
+        return _decode_samples(self.dataset, indices, self.threads)
 
     def _shape(self, t, dims):
         return t.unsqueeze(1) if dims == 4 else t
@@ -376,9 +402,12 @@ class ContrastiveBatches:
         inds = [int(i) for i in inds]
         B = len(inds)
         inds_pos = [knn.pick_positive(self.nns, i, self.num_neighbors) for i in inds] if self.pos else []
-        samples = self._decode(inds + inds_pos)
-        img, label, mask, depth = prepare_samples(self.dataset, samples, self.res, self.loader_crop_type, self.device, self.return_depth,
-                                                  self.generator)
+        if self.sample_cache is not None:
+            img, label, mask, depth = self.sample_cache.gather(inds, inds_pos if self.pos else None)
+        else:
+            samples = self._decode(inds + inds_pos)
+            img, label, mask, depth = prepare_samples(self.dataset, samples, self.res, self.loader_crop_type, self.device, self.return_depth,
+                                                      self.generator)
         ld = self.dataset.label_dims
         label = self._shape(label, ld)
         mask = mask.unsqueeze(1) if (ld == 4 or self.dataset.mask_rule == ops.BATCH_MASK_BOOL_IGNORED) else mask
@@ -446,12 +475,15 @@ def feature_cache_path(data_dir, meta, image_set, dtype):
     return os.path.join(data_dir, name)
 
 
-def build_feature_cache(net, dataset, cfg, res, crop_type, dtype=torch.float32, device=None, batch_size=None, num_workers=0):
+def build_feature_cache(net, dataset, cfg, res, crop_type, dtype=torch.float32, device=None, batch_size=None, num_workers=0,
+                        sample_cache=None):
     """A feature_cache.FeatureCache of `dataset`: one pass over the split in index order through `prepare_samples` with the loader
     transform (res, crop_type - the pipeline's loader_crop_type), `net._backbone(img)` under no_grad with the backbone in eval mode
     (what forward() runs, src/modules.py:93-120), one `put` per batch.  The pass --precompute-knns makes over the same images pools
     and drops these maps; this one keeps them.  Refused: crop_type "random" (the features would depend on the draw) and cfg.arch
-    "dino_depth" (the depth-guided featurizer mixes the depth map in behind the backbone: out of scope for the cache)."""
+    "dino_depth" (the depth-guided featurizer mixes the depth map in behind the backbone: out of scope for the cache).
+    `sample_cache`: a sample_cache.SampleCache of the same split and transform to fill from the samples this pass decodes anyway, so
+    that a run that wants both caches decodes the split once."""
     from .feature_cache import FeatureCache
     if crop_type == "random":
         raise ValueError("depthg_amd.data: build_feature_cache with loader_crop_type = 'random': the features of an image would depend on "
@@ -472,11 +504,9 @@ def build_feature_cache(net, dataset, cfg, res, crop_type, dtype=torch.float32, 
     with torch.no_grad():
         for i in range(0, n, int(batch_size)):
             inds = list(range(i, min(i + int(batch_size), n)))
-            if threads == 0 or len(inds) < 2:
-                samples = [dataset.load(k) for k in inds]
-            else:
-                with ThreadPoolExecutor(max_workers=min(threads, len(inds))) as pool:
-                    samples = list(pool.map(dataset.load, inds))
+            samples = _decode_samples(dataset, inds, threads)
+            if sample_cache is not None:
+                sample_cache.put(inds, samples, res, crop_type)
             img = prepare_samples(dataset, samples, res, crop_type, device, False)[0]
             image_feat = net._backbone(img)[0]
             if cache is None:
@@ -485,3 +515,56 @@ def build_feature_cache(net, dataset, cfg, res, crop_type, dtype=torch.float32, 
     if cache is None:
         raise ValueError("depthg_amd.data: build_feature_cache on an empty dataset")
     return cache
+
+
+# --------------------------------------------------------------------------------------------------------------- sample cache
+def sample_cache_meta(dataset, image_set, res, crop_type, want_depth):
+    """What the cached bytes of `dataset` depend on (SampleCache.meta): the images, the split, the view, the planes.  crop_type: the
+    LOADER's crop (the dataset's own crop is part of its name)."""
+    return {"dataset_name": "{}_{}".format(dataset.nns_name, getattr(dataset, "crop_type", None)), "split": str(image_set), "res": int(res),
+            "loader_crop_type": crop_type, "n_images": len(dataset), "has_labels": bool(dataset.has_labels),
+            "depth_type": (("plane_" if getattr(dataset, "plane_depth", False) else "") + str(getattr(dataset, "depth_type", None)))
+            if want_depth else None}
+
+
+def sample_cache_path(data_dir, meta):
+    """<data_dir>/sample_cache_<meta>.pt"""
+    name = "sample_cache_{dataset_name}_{split}_{loader_crop_type}_{res}_{n_images}_{depth_type}_{labels}.pt".format(
+        labels="labels" if meta["has_labels"] else "nolabels", **meta)
+    return os.path.join(data_dir, name)
+
+
+def new_sample_cache(dataset, image_set, res, crop_type, want_depth, device):
+    """An empty sample_cache.SampleCache for `dataset` under the loader transform (res, crop_type): what build_sample_cache fills, and
+    what build_feature_cache(sample_cache=...) takes to fill on its own pass."""
+    from .sample_cache import SampleCache
+    if crop_type == "random":
+        raise ValueError("depthg_amd.data: a sample cache with loader_crop_type = 'random': the bytes of an image would depend on the crop's "
+                         "draw; use 'center' or None")
+    resized_size(1, 1, res, crop_type)
+    if len(dataset) < 1:
+        raise ValueError("depthg_amd.data: a sample cache of an empty dataset")
+    if device is None:
+        device = "cuda:0" if torch.cuda.is_available() else "cpu"
+    return SampleCache(len(dataset), int(res), int(res), dataset.has_labels, want_depth, dataset.label_offset if dataset.has_labels else 0, -1,
+                       dataset.mask_rule, device=device, meta=sample_cache_meta(dataset, image_set, res, crop_type, want_depth))
+
+
+def fill_sample_cache(cache, dataset, res, crop_type, num_workers=0, batch_size=64):
+    """Put every row of `cache` that has not been put yet, in index order: decoding in the thread pool (min(num_workers, 16) threads),
+    one `put` - one launch - per `batch_size` images."""
+    threads = max(0, min(int(num_workers), MAX_DECODE_THREADS))
+    missing = np.flatnonzero(~cache.filled).tolist()
+    for i in range(0, len(missing), int(batch_size)):
+        inds = missing[i:i + int(batch_size)]
+        cache.put(inds, _decode_samples(dataset, inds, threads), res, crop_type)
+    return cache
+
+
+def build_sample_cache(dataset, cfg, res, crop_type, want_depth=None, device=None, num_workers=0, image_set=None, batch_size=64):
+    """A sample_cache.SampleCache of `dataset` under the loader transform (res, crop_type): one decoding pass over the split in index
+    order (fill_sample_cache).  `want_depth`: None takes the dataset's return_depth.  Refused: crop_type "random" (the bytes would
+    depend on the draw).  (`cfg` is not read: the transform is all the bytes depend on.)"""
+    want_depth = bool(dataset.return_depth if want_depth is None else want_depth)
+    cache = new_sample_cache(dataset, image_set if image_set is not None else getattr(dataset, "split", None), res, crop_type, want_depth, device)
+    return fill_sample_cache(cache, dataset, res, crop_type, num_workers, batch_size)

@@ -562,6 +562,84 @@ def feature_cache_gather(cache, idx_a, idx_b=None, out=None):
     return out
 
 
+SAMPLE_CACHE_MAX_ROWS = 65535       # rows one dg_samplecache_gather call forms (the two lists together)
+
+
+def _sample_cache_operands(who, cache, has_labels, with_depth, lists):
+    """The cache as the two entries take it - a contiguous uint8 (n_images, planes, H, W) GPU tensor with planes = 3 + has_labels +
+    with_depth - and each index list of `lists` as a contiguous int64 tensor on the cache's device (the kernels read them there;
+    the caller has checked the values on the host)."""
+    planes = 3 + int(bool(has_labels)) + int(bool(with_depth))
+    if cache.dim() != 4 or cache.dtype != torch.uint8 or not cache.is_contiguous() or cache.shape[1] != planes:
+        raise ValueError(f"depthg_amd: {who} wants the cache as a contiguous uint8 (n_images, {planes}, H, W) tensor, got "
+                         f"{tuple(cache.shape)} {cache.dtype}")
+    _on_gpu(cache, "cache")
+    for name, idx in lists:
+        if idx.dtype != torch.int64 or idx.dim() != 1 or idx.device != cache.device or not idx.is_contiguous():
+            raise ValueError(f"depthg_amd: {who} wants `{name}` as a contiguous 1-d int64 tensor on {cache.device} (the kernel reads it there)")
+
+
+def sample_cache_put(cache, has_labels, with_depth, idx, packed, records, tables):
+    """Rows idx[0..n) of `cache` - uint8 (n_images, planes, H, W), planes R, G, B, label (has_labels), depth (with_depth) - = the bytes
+    the loader's nearest resize and crop select from the decoded planes of n samples (dg_samplecache_put, k_sc_put of
+    dg_sample_cache.hip): one launch.  packed / records / tables: what data.pack_batch makes and ops.batch_prep takes; `idx`: int64
+    on the cache's device, each row once."""
+    lib = _lib.load()
+    _sample_cache_operands("sample_cache_put", cache, has_labels, with_depth, (("idx", idx),))
+    N, _, H, W = cache.shape
+    for t, name in ((records, "records"), (tables, "tables")):
+        if t.dtype != torch.int32 or t.is_cuda or not t.is_contiguous():
+            raise ValueError(f"depthg_amd: sample_cache_put wants `{name}` as a contiguous CPU int32 tensor")
+    n = idx.numel()
+    if records.dim() != 2 or records.shape[1] != BATCH_REC_WORDS or tuple(tables.shape) != (n, W + H):
+        raise ValueError(f"depthg_amd: sample_cache_put wants records (k, {BATCH_REC_WORDS}) and tables ({n}, {W} + {H}), got {tuple(records.shape)} "
+                         f"and {tuple(tables.shape)}")
+    if packed.dtype != torch.uint8 or packed.dim() != 1 or not packed.is_contiguous():
+        raise ValueError("depthg_amd: sample_cache_put wants `packed` as a flat contiguous uint8 tensor")
+    dev = cache.device
+    stream = _stream(dev)
+    src = packed.to(dev, non_blocking=True)
+    params = torch.cat([records.reshape(-1), tables.reshape(-1)]).to(dev, non_blocking=True)
+    rc = lib.dg_samplecache_put(_ptr(cache), N, int(bool(has_labels)), int(bool(with_depth)), H, W, _ptr(idx), n, _ptr(src), src.numel(),
+                                ctypes.c_void_p(records.data_ptr()), ctypes.c_void_p(tables.data_ptr()), _ptr(params), records.shape[0], stream)
+    _lib.check(rc, "dg_samplecache_put")
+
+
+def sample_cache_gather(cache, has_labels, with_depth, idx_a, idx_b=None, label_offset=0, fill=-1, mask_rule=BATCH_MASK_BOOL_IGNORED,
+                        mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225), want=None):
+    """The rows idx_a[0..n), then the rows idx_b[0..n) (None: n rows), of a sample cache in the step's dtypes from ONE launch
+    (dg_samplecache_gather, k_sc_gather of dg_sample_cache.hip): a dict of img fp32 (rows,3,H,W) normalised with `mean` / `std`, label
+    int64 (rows,H,W) = byte + label_offset (or `fill` without a label plane), mask (rows,H,W) bool label == -1 or fp32 label > 0 by
+    `mask_rule`, depth fp32 (rows,H,W) - those of them `want` names (None: all the cache can form), every element written.  Indices:
+    int64 on the cache's device; they may repeat."""
+    lib = _lib.load()
+    lists = (("idx_a", idx_a),) + ((("idx_b", idx_b),) if idx_b is not None else ())
+    _sample_cache_operands("sample_cache_gather", cache, has_labels, with_depth, lists)
+    N, _, H, W = cache.shape
+    n = idx_a.numel()
+    if idx_b is not None and idx_b.numel() != n:
+        raise ValueError(f"depthg_amd: sample_cache_gather: {n} indices and {idx_b.numel()} positives")
+    can = ("img", "label", "mask") + (("depth",) if with_depth else ())
+    want = can if want is None else tuple(want)
+    if not want or set(want) - set(can):
+        raise ValueError(f"depthg_amd: sample_cache_gather: `want` = {want!r}, this cache forms {can!r}")
+    rows, dev = (2 * n if idx_b is not None else n), cache.device
+    out = {}
+    if "img" in want:
+        out["img"] = _empty((rows, 3, H, W), torch.float32, dev)
+    if "label" in want:
+        out["label"] = _empty((rows, H, W), torch.int64, dev)
+    if "mask" in want:
+        out["mask"] = _empty((rows, H, W), torch.float32 if mask_rule == BATCH_MASK_FLOAT_POSITIVE else torch.bool, dev)
+    if "depth" in want:
+        out["depth"] = _empty((rows, H, W), torch.float32, dev)
+    rc = lib.dg_samplecache_gather(_ptr(cache), N, int(bool(has_labels)), int(bool(with_depth)), H, W, _ptr(idx_a), _ptr(idx_b), n,
+                                   (ctypes.c_float * 3)(*mean), (ctypes.c_float * 3)(*std), int(label_offset), int(fill), int(mask_rule),
+                                   _ptr(out.get("img")), _ptr(out.get("label")), _ptr(out.get("mask")), _ptr(out.get("depth")), _stream(dev))
+    _lib.check(rc, "dg_samplecache_gather")
+    return out
+
+
 def rec_loss_shapes(code, feats, weight, bias):
     """The reconstruction term's shape rules, on any device: code (B,D,h,w), feats (B,C,h,w) on the same grid, the decoder's weight
     (C,D,1,1) or (C,D) and bias (C,).  Returns (weight as (C,D), (B, D, C, h, w))."""

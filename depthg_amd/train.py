@@ -1,6 +1,6 @@
 """Train a segmenter from a dataset folder: the loop of src/train_segmentation.py:551-714 without Lightning, Hydra, TensorBoard or wandb.
 
-    python -m depthg_amd.train --data-dir D --out O [--dataset directory] [--precompute-knns] [--feature-cache float32] [--device cuda:0] [key=value ...]
+    python -m depthg_amd.train --data-dir D --out O [--dataset directory] [--precompute-knns] [--feature-cache float32] [--sample-cache] [--device cuda:0] [key=value ...]
 
 builds the train pipeline (data.CroppedFolder, or data.DirectoryFolder with --dataset directory, under data.ContrastiveBatches: the
 loader transform of a batch and its kNN positives is one fused HIP launch) from the cfg keys dataset_name, crop_type, crop_ratio, res,
@@ -11,7 +11,9 @@ they parse, else as strings; `~` and `null` are None).  --precompute-knns writes
 (data.precompute_knns).  --feature-cache {float32,float16,bfloat16} (cfg.dg_feature_cache) runs the frozen backbone over the train split
 once behind that, keeps its features in a feature_cache.FeatureCache - saved as <data-dir>/feature_cache_<meta>.pt and loaded from there when
 the file exists and matches - and trains from them: the step skips the backbone (loader_crop_type "center" or None, arch "dino"; validation
-is untouched).  The reference reads its val set from the uncropped dataset classes; here both splits come from the same
+is untouched).  --sample-cache keeps the loader's output bytes of the train and the val split on the device (sample_cache.SampleCache,
+saved as <data-dir>/sample_cache_<meta>.pt and loaded from there when the file matches): every batch is then one gather launch over them
+and an epoch opens no image file; without the flag nothing changes.  The reference reads its val set from the uncropped dataset classes; here both splits come from the same
 folder layout (cfg.val_crop_type names the val folder's crop, default: cfg.crop_type).
 
 `fit(model, train_batches, val_batches, cfg, out_dir)`:
@@ -142,9 +144,10 @@ def build_dataset(cfg, data_dir, image_set, return_depth):
     return data.CroppedFolder(data_dir, cfg.dataset_name, crop, cfg.crop_ratio, image_set, return_depth=return_depth, depth_type=cfg.depth_type)
 
 
-def train_feature_cache(cfg, data_dir, device, train_set, net, dtype):
+def train_feature_cache(cfg, data_dir, device, train_set, net, dtype, sample_cache=None):
     """The train split's feature_cache.FeatureCache of storage type `dtype`: loaded from <data_dir>/feature_cache_<meta>.pt when that file
-    exists and its metadata match, else built with the featurizer `net` (data.build_feature_cache) and saved there."""
+    exists and its metadata match, else built with the featurizer `net` (data.build_feature_cache) and saved there.  `sample_cache`: an
+    empty sample cache of the split that the building pass fills from the samples it decodes (left empty when the file is loaded)."""
     from . import data
     from .feature_cache import FeatureCache
     meta = data.feature_cache_meta(cfg, train_set, cfg.res, cfg.loader_crop_type)
@@ -159,15 +162,46 @@ def train_feature_cache(cfg, data_dir, device, train_set, net, dtype):
             print(f"depthg_amd.train: {path} does not match ({e}); rebuilding")
     cache = data.build_feature_cache(net, train_set, cfg, cfg.res, cfg.loader_crop_type, dtype=dtype, device=device,
                                      batch_size=min(128 if cfg.model_type == "vit_small" else 64, max(len(train_set), 1)),
-                                     num_workers=cfg.num_workers)
+                                     num_workers=cfg.num_workers, sample_cache=sample_cache)
     cache.save(path)
     print(f"depthg_amd.train: feature cache built and saved to {path} ({cache.nbytes} bytes)")
     return cache
 
 
-def build_pipelines(cfg, data_dir, device, precompute=False, net=None, feature_cache=None):
+def load_sample_cache(data_dir, device, dataset, image_set, res, crop_type, want_depth):
+    """(cache, path): the split's sample_cache.SampleCache from <data_dir>/sample_cache_<meta>.pt when that file exists, its metadata
+    match and every row is there - else an EMPTY cache for the caller to fill (finish_sample_cache) and save there."""
+    from . import data
+    from .sample_cache import SampleCache
+    meta = data.sample_cache_meta(dataset, image_set, res, crop_type, want_depth)
+    path = data.sample_cache_path(data_dir, meta)
+    if os.path.exists(path):
+        try:
+            cache = SampleCache.load(path, device, expect_meta=meta)
+            if bool(cache.filled.all()):
+                print(f"depthg_amd.train: sample cache loaded from {path} ({cache.nbytes} bytes)")
+                return cache, path
+        except ValueError as e:
+            print(f"depthg_amd.train: {path} does not match ({e}); rebuilding")
+    return data.new_sample_cache(dataset, image_set, res, crop_type, want_depth, device), path
+
+
+def finish_sample_cache(cfg, cache, path, dataset, res, crop_type):
+    """Fill the rows of `cache` that no earlier pass has put (all of them, unless the feature cache's building pass did) and save it."""
+    from . import data
+    if bool(cache.filled.all()) and os.path.exists(path):
+        return cache
+    data.fill_sample_cache(cache, dataset, res, crop_type, num_workers=cfg.num_workers)
+    cache.save(path)
+    print(f"depthg_amd.train: sample cache built and saved to {path} ({cache.nbytes} bytes)")
+    return cache
+
+
+def build_pipelines(cfg, data_dir, device, precompute=False, net=None, feature_cache=None, sample_cache=False):
     """(train_batches, val_batches, n_classes) of cfg (:614-658).  `precompute`: write the train table first when it is missing, with `net`.
-    `feature_cache`: None, or the storage type of the train split's feature cache (train_feature_cache; `net` supplies the featurizer)."""
+    `feature_cache`: None, or the storage type of the train split's feature cache (train_feature_cache; `net` supplies the featurizer).
+    `sample_cache`: keep both splits' loader outputs on the device (--sample-cache); with a feature cache to build as well, the train
+    split is decoded once for both."""
     from . import data, knn
     train_set = build_dataset(cfg, data_dir, "train", bool(cfg.use_depth))
     if train_set.n_classes is None:
@@ -176,18 +210,26 @@ def build_pipelines(cfg, data_dir, device, precompute=False, net=None, feature_c
     if precompute and not os.path.exists(path):
         data.precompute_knns(net(train_set.n_classes), train_set, cfg, cfg.res, "train", train_set.crop_type, num_workers=cfg.num_workers,
                              device=device, batch_size=min(128 if cfg.model_type == "vit_small" else 64, max(len(train_set), 1)))
-    cache = None
+    cache = samples = val_samples = None
+    if sample_cache:
+        samples, samples_path = load_sample_cache(data_dir, device, train_set, "train", cfg.res, cfg.loader_crop_type, bool(cfg.use_depth))
     if feature_cache is not None:
-        cache = train_feature_cache(cfg, data_dir, device, train_set, net(train_set.n_classes), feature_cache)
+        cache = train_feature_cache(cfg, data_dir, device, train_set, net(train_set.n_classes), feature_cache,
+                                    sample_cache=samples if samples is not None and not samples.filled.any() else None)
+    if sample_cache:
+        finish_sample_cache(cfg, samples, samples_path, train_set, cfg.res, cfg.loader_crop_type)
     gen = torch.Generator().manual_seed(0)                                                                           # seed_everything(0), :590
     train_batches = data.ContrastiveBatches(train_set, cfg, "train", cfg.res, cfg.loader_crop_type, cfg.batch_size, shuffle=True, generator=gen,
                                             num_workers=cfg.num_workers, pos=True, return_depth=bool(cfg.use_depth), device=device,
-                                            feature_cache=cache)
+                                            feature_cache=cache, sample_cache=samples)
     eval_res = 224 if cfg.model_type == "mae" else 320                                                               # :597-600
     val_crop = None if cfg.dataset_name == "voc" else "center"                                                       # :632-635
     val_set = build_dataset(cfg, data_dir, "val", False)
+    if sample_cache:
+        val_samples, val_path = load_sample_cache(data_dir, device, val_set, "val", eval_res, val_crop, False)
+        finish_sample_cache(cfg, val_samples, val_path, val_set, eval_res, val_crop)
     val_batches = data.ContrastiveBatches(val_set, cfg, "val", eval_res, val_crop, cfg.batch_size, shuffle=False, num_workers=cfg.num_workers,
-                                          pos=False, return_depth=False, device=device)
+                                          pos=False, return_depth=False, device=device, sample_cache=val_samples)
     return train_batches, val_batches, train_set.n_classes
 
 
@@ -201,6 +243,10 @@ def main(argv=None) -> int:
     ap.add_argument("--feature-cache", choices=("float32", "float16", "bfloat16"), default=None,
                     help="keep the frozen backbone's features of the train split in this type and train from them (sets dg_feature_cache); "
                          "built once, saved as feature_cache_<meta>.pt under --data-dir and loaded from there afterwards")
+    ap.add_argument("--sample-cache", action="store_true",
+                    help="keep the loader's output bytes of the train and the val split on the device and form every batch from them in one "
+                         "launch; built once, saved as sample_cache_<meta>.pt under --data-dir and loaded from there afterwards "
+                         "(loader_crop_type 'center' or None)")
     ap.add_argument("overrides", nargs="*", help="cfg keys as key=value")
     args = ap.parse_args(argv)
     overrides = parse_overrides(args.overrides)
@@ -231,7 +277,7 @@ def main(argv=None) -> int:
         return model.net
 
     train_batches, val_batches, n_classes = build_pipelines(cfg, args.data_dir, device, args.precompute_knns, knn_net,
-                                                            getattr(cfg, "dg_feature_cache", None))
+                                                            getattr(cfg, "dg_feature_cache", None), args.sample_cache)
     model = model_for(n_classes)
     model.train()
     state = fit(model, train_batches, val_batches, cfg, args.out)

@@ -1058,6 +1058,41 @@ int dg_featcache_put(void* cache, int32_t dtype, int64_t N, int64_t L, const flo
 int dg_featcache_gather(const void* cache, int32_t dtype, int64_t N, int64_t L, const int64_t* idx_a, const int64_t* idx_b, int64_t n,
                         float* out, dg_stream_t stream);
 
+/*
+ * Device-resident sample cache (dg_sample_cache.hip).  With a deterministic loader crop the resized and cropped bytes of every image,
+ * label and depth map (src/utils.py:164-182) are the same in every epoch, and the reference's datasets form their tensors from those
+ * bytes alone (src/data.py:894-902, :126-128): they are stored once on the card and a batch comes back from them without a file, a
+ * decoder, a pinned buffer or an upload.
+ *  cache : uint8 (n_images, planes, H, W) on the device at the loader's OUTPUT size, W a multiple of 4, 4-byte aligned.  planes =
+ *      3 + has_labels + with_depth in the order R, G, B, label (has_labels), depth (with_depth).
+ * dg_samplecache_put, kernel k_sc_put: packed / packed_bytes / records_host / tables_host / params / n_records exactly as dg_batch_prep
+ *  takes them for n samples, and idx: int64 on the DEVICE, the cache row of each sample, each row once per call.  Writes the BYTES the
+ *  nearest resize and crop select - k_batch_prep's geometry without its arithmetic: image HWC becomes three planes, a
+ *  DG_BATCH_DEPTH_PLANE record stores the byte 255, a DG_BATCH_LABEL_FILL record writes nothing.  Every sample needs one image record,
+ *  one DG_BATCH_LABEL record iff has_labels and one depth record iff with_depth, so every byte of every named row is written once.
+ * dg_samplecache_gather, kernel k_sc_gather: ONE launch writes rows 0..n-1 from idx_a and rows n..2n-1 from idx_b (int64 on the DEVICE;
+ *  idx_b may be NULL: n rows; an index may repeat, within a list and between the two) of every output that is not NULL:
+ *      img   fp32 (rows,3,H,W) = (byte / 255 - mean[c]) / stdv[c] through the device function dg_batch_prep's kernel uses: its bits
+ *      label int64 (rows,H,W)  = byte + label_offset, or `fill` for a cache without a label plane
+ *      mask  (rows,H,W)        = fp32 label > 0 (DG_BATCH_MASK_FLOAT_POSITIVE) or bool bytes label == -1 (DG_BATCH_MASK_BOOL_IGNORED)
+ *      depth fp32 (rows,H,W)   = the byte value
+ *  mean, stdv : HOST memory, three floats each (needed with img).  A lane owns four neighbouring pixels of a row: one 32-bit load per
+ *  plane, 16-byte stores (the bool mask: one 4-byte word).
+ * No LDS in the gather, no atomics, no workspace, no allocation, no host synchronisation; two calls give the same bytes.  The callers
+ * check the indices on the host; a row index outside [0, n_images) is never dereferenced all the same: that row is skipped.
+ * Refused before any launch: DG_ERR_INVALID for null or misaligned pointers (the cache on 4 bytes, indices on 8, outputs on 16), sizes
+ * that are not positive, an unknown record kind or mask rule, a record that does not fit the cache's planes, a plane group written
+ * twice or not at all, a source plane that leaves `packed` or is smaller than its tables address, depth asked of a cache without a
+ * depth plane, no output asked for, std <= 0; DG_ERR_UNSUPPORTED for W not a multiple of 4, a side above 16384, more than 65535 rows or
+ * records a call.  n == 0: nothing.
+ */
+int dg_samplecache_put(uint8_t* cache, int64_t n_images, int32_t has_labels, int32_t with_depth, int32_t H, int32_t W, const int64_t* idx,
+                       int32_t n, const uint8_t* packed, size_t packed_bytes, const int32_t* records_host, const int32_t* tables_host,
+                       const void* params, int32_t n_records, dg_stream_t stream);
+int dg_samplecache_gather(const uint8_t* cache, int64_t n_images, int32_t has_labels, int32_t with_depth, int32_t H, int32_t W,
+                          const int64_t* idx_a, const int64_t* idx_b, int32_t n, const float* mean, const float* stdv, int32_t label_offset,
+                          int32_t fill, int32_t mask_rule, float* img, int64_t* label, void* mask, float* depth, dg_stream_t stream);
+
 /* Measurement aid: name of the kernel the fused correlation launch of this descriptor runs ("k_corr2": the one-wave-per-SIMD
  * form of dg_corr2.hip, "k_corr_main": the general form), decided by the same predicate the launch uses; NULL on a bad desc. */
 const char* dg_corr_main_kernel_name(const dg_corr_desc* desc);
