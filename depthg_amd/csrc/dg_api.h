@@ -1,4 +1,4 @@
-// What the units of the C ABI share (dg_api_corr.hip, dg_api_head.hip, dg_api_eval.hip, dg_api_loss.hip, dg_api_aux.hip): error reporting and the
+// What the units of the C ABI share (dg_api_corr.hip, dg_api_head.hip, dg_api_eval.hip, dg_api_loss.hip, dg_api_data.hip, dg_api_aux.hip): error reporting and the
 // library's second stream.  Internal: not installed beside include/depthg_corr.h.
 #pragma once
 #include "dg_common.h"
@@ -22,7 +22,7 @@ int fail(int code, const char* fmt, ...);
 
 static inline size_t up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
-// ---- the argument checks the entry points with a workspace share (dg_api_loss.hip, the depth encoder of dg_api_aux.hip)
+// ---- the argument checks the entry points with a workspace share (dg_api_loss.hip, the depth encoder of dg_api_aux.hip, the augmentation of dg_api_data.hip)
 // the pointers of `p4` on 4-byte boundaries (a null optional pointer passes), the workspace on a 16-byte one
 inline int check_aligned(const char* who, std::initializer_list<const void*> p4, const void* workspace) {
     uintptr_t bits = 0;

@@ -1,5 +1,5 @@
 // C ABI of the gfx950 DepthG library (include/depthg_corr.h), the units' shared state and the small subsystems: version and error
-// text, the library's side stream, batch maps / random draws / coordinate samplers, kNN, LHP, fused Adam, ViT attention and linear, the fused depth encoder, the depth guidance's cross-attention, the GPU batch augmentation, the batch preparation, the frozen-backbone feature cache, the device-resident sample cache.  (The auxiliary loss terms: dg_api_loss.hip.)
+// text, the library's side stream, batch maps / random draws / coordinate samplers, kNN, LHP, fused Adam, ViT attention and linear, the fused depth encoder, the depth guidance's cross-attention.  (The auxiliary loss terms: dg_api_loss.hip; the training data path: dg_api_data.hip.)
 // Host-side only: argument checks and kernel launches on the caller's stream.
 #include "dg_api.h"
 #include "dg_aux_args.h"
@@ -8,7 +8,6 @@
 
 #include <cstdarg>
 #include <map>
-#include <vector>
 
 // ---- error reporting (dg_api.h)
 thread_local char g_err[512] = "";
@@ -440,286 +439,5 @@ extern "C" int dg_xattn_keep_mask(uint64_t seed, int32_t B, int32_t heads, int32
     if (int rc = xattn_check(__func__, B, heads, Nq, Nk, DG_XATTN_HD, 1.f, p)) return rc;
     if (!out) return fail(DG_ERR_INVALID, "dg_xattn_keep_mask: null pointer");
     DG_HIP(dg_launch_xattn_mask(out, B, heads, Nq, Nk, seed, xattn_threshold(p), static_cast<hipStream_t>(stream_)));
-    return DG_OK;
-}
-
-// ---- GPU batch augmentation (dg_augment.hip)
-static bool augment_sizes_ok(int32_t B, int32_t h, int32_t w) { return B >= 1 && B <= 65535 && h >= 3 && w >= 3 && h <= 16384 && w <= 16384; }
-
-static int augment_stat_blocks(int32_t h, int32_t w) {
-    const long long tiles = (long long)((h + DG_AUGM_TH - 1) / DG_AUGM_TH) * ((w + DG_AUGM_TW - 1) / DG_AUGM_TW);
-    return (int)(tiles < DG_AUGM_STAT_BLOCKS ? tiles : DG_AUGM_STAT_BLOCKS);
-}
-
-extern "C" size_t dg_augment_workspace_bytes(int32_t B, int32_t h, int32_t w) {
-    if (!augment_sizes_ok(B, h, w)) return 0;
-    return up((size_t)B * augment_stat_blocks(h, w) * sizeof(double), 256);
-}
-
-extern "C" int dg_augment_forward(const float* img, int64_t stride_b, int64_t stride_c, int64_t stride_h, int64_t stride_w,
-                                  const int32_t* records_host, const void* params, const float* mean, const float* stdv, int32_t B,
-                                  int32_t C, int32_t H, int32_t W, int32_t h, int32_t w, float* img_aug, float* coord_aug,
-                                  void* workspace, size_t workspace_bytes, dg_stream_t stream_) {
-    if (B < 1 || C < 1 || H < 1 || W < 1 || h < 1 || w < 1)
-        return fail(DG_ERR_INVALID, "dg_augment_forward: B=%d C=%d, image %dx%d, output %dx%d must be positive", B, C, H, W, h, w);
-    if (C != 3) return fail(DG_ERR_UNSUPPORTED, "dg_augment_forward: %d channels (the colour ops are RGB: 3)", C);
-    if (H < 3 || W < 3 || h < 3 || w < 3)
-        return fail(DG_ERR_UNSUPPORTED, "dg_augment_forward: image %dx%d, output %dx%d: reflect padding by 2 needs three pixels a side", H, W, h, w);
-    if (B > 65535 || H > 16384 || W > 16384 || h > 16384 || w > 16384)
-        return fail(DG_ERR_UNSUPPORTED, "dg_augment_forward: B=%d above 65535 or a side of %dx%d / %dx%d above 16384", B, H, W, h, w);
-    if (stride_w != 1 || stride_h != W || stride_c != (int64_t)H * W || stride_b != 3 * (int64_t)H * W)
-        return fail(DG_ERR_UNSUPPORTED, "dg_augment_forward: img is not contiguous (strides %lld, %lld, %lld, %lld): copy it once", (long long)stride_b,
-                    (long long)stride_c, (long long)stride_h, (long long)stride_w);
-    if (!img || !records_host || !params || !img_aug || !coord_aug || !workspace) return fail(DG_ERR_INVALID, "dg_augment_forward: null pointer");
-    if (!mean != !stdv) return fail(DG_ERR_INVALID, "dg_augment_forward: mean and std come together: give both or neither");
-    if (int rc = check_aligned(__func__, {img, params, img_aug, coord_aug}, workspace)) return rc;
-    if (int rc = check_workspace(__func__, workspace_bytes, dg_augment_workspace_bytes(B, h, w), "dg_augment_workspace_bytes")) return rc;
-    bool stats = false;
-    for (int b = 0; b < B; ++b) {
-        const int32_t* r = records_host + (size_t)b * DG_AUGM_REC_WORDS;
-        const long long top = r[1], left = r[2], bh = r[3], bw = r[4];
-        if (bh < 1 || bw < 1 || top < 0 || left < 0 || top + bh > H || left + bw > W)
-            return fail(DG_ERR_UNSUPPORTED, "dg_augment_forward: crop box (%lld, %lld, %lld, %lld) of image %d leaves the %dx%d image", top, left, bh,
-                        bw, b, H, W);
-        int contrasts = 0;
-        for (int k = 0; k < 4; ++k) {
-            if (r[5 + k] < -1 || r[5 + k] > DG_AUGM_HUE) return fail(DG_ERR_INVALID, "dg_augment_forward: image %d: op %d in slot %d (-1 .. 3)", b, r[5 + k], k);
-            contrasts += r[5 + k] == DG_AUGM_CONTRAST;
-        }
-        if (contrasts > 1) return fail(DG_ERR_UNSUPPORTED, "dg_augment_forward: image %d has %d contrast ops (one image mean per image: one at most)", b, contrasts);
-        float sigma;
-        memcpy(&sigma, &r[14], 4);
-        if (!(sigma >= 0.f) || std::isinf(sigma)) return fail(DG_ERR_INVALID, "dg_augment_forward: image %d: blur_sigma=%g", b, (double)sigma);
-        stats = stats || contrasts > 0;
-    }
-    DgAugmentArgs A;
-    memset(&A, 0, sizeof(A));
-    A.img = img;
-    A.recs = static_cast<const int32_t*>(params);
-    A.rows = reinterpret_cast<const float*>(A.recs + (size_t)B * DG_AUGM_REC_WORDS);
-    A.cols = A.rows + H;
-    A.img_aug = img_aug; A.coord_aug = coord_aug; A.partials = static_cast<double*>(workspace);
-    A.B = B; A.H = H; A.W = W; A.h = h; A.w = w;
-    A.tiles_x = (w + DG_AUGM_TW - 1) / DG_AUGM_TW; A.tiles_y = (h + DG_AUGM_TH - 1) / DG_AUGM_TH;
-    A.stat_blocks = augment_stat_blocks(h, w);
-    A.unit_space = mean ? 0 : 1;
-    A.vec_stores = (w % 4 == 0 && (((uintptr_t)img_aug | (uintptr_t)coord_aug) & 15) == 0) ? 1 : 0;
-    for (int c = 0; c < 3; ++c) {
-        A.mean[c] = mean ? mean[c] : 0.f;
-        A.stdv[c] = stdv ? stdv[c] : 1.f;
-        if (!(A.stdv[c] > 0.f) || std::isinf(A.stdv[c]) || !(A.mean[c] == A.mean[c]) || std::isinf(A.mean[c]))
-            return fail(DG_ERR_INVALID, "dg_augment_forward: channel %d: mean=%g std=%g", c, (double)A.mean[c], (double)A.stdv[c]);
-    }
-    DG_HIP(dg_launch_augment(A, stats, static_cast<hipStream_t>(stream_)));
-    return DG_OK;
-}
-
-// ---- batch preparation (dg_batch.hip)
-// a record that reads a source plane: the plane lies inside `packed` and holds every pixel its sample's tables (xs[W], ys[H]) address
-static int batch_source_check(const char* who, int i, const int32_t* r, const int32_t* xs, int32_t H, int32_t W, const uint8_t* packed,
-                              size_t packed_bytes) {
-    const int kind = r[0], sw = r[4], sh = r[5];
-    const unsigned long long off = (unsigned long long)(uint32_t)r[2] | ((unsigned long long)(uint32_t)r[3] << 32);
-    if (sw < 1 || sh < 1) return fail(DG_ERR_INVALID, "%s: record %d: zero-sized source plane %dx%d", who, i, sw, sh);
-    if (sw > DG_BATCH_MAX_SIDE || sh > DG_BATCH_MAX_SIDE)
-        return fail(DG_ERR_UNSUPPORTED, "%s: record %d: source plane %dx%d above %d a side", who, i, sw, sh, DG_BATCH_MAX_SIDE);
-    const unsigned long long bytes = (unsigned long long)sw * sh * (kind == DG_BATCH_IMAGE ? 3 : 1);
-    if (!packed || off > packed_bytes || bytes > packed_bytes - off)
-        return fail(DG_ERR_INVALID, "%s: record %d: plane of %llu bytes at offset %llu leaves the packed buffer of %zu bytes", who, i, bytes, off,
-                    packed_bytes);
-    const int32_t* ys = xs + W;
-    for (int x = 0; x < W; ++x)
-        if (xs[x] < 0 || xs[x] >= sw)
-            return fail(DG_ERR_INVALID, "%s: record %d: column table entry %d = %d outside the source width %d (the plane is narrower than the tables address)", who, i, x, xs[x], sw);
-    for (int y = 0; y < H; ++y)
-        if (ys[y] < 0 || ys[y] >= sh)
-            return fail(DG_ERR_INVALID, "%s: record %d: row table entry %d = %d outside the source height %d (the plane is shorter than the tables address)", who, i, y, ys[y], sh);
-    return DG_OK;
-}
-
-extern "C" int dg_batch_prep(const uint8_t* packed, size_t packed_bytes, const int32_t* records_host, const int32_t* tables_host,
-                             const void* params, int32_t n_records, int32_t N, int32_t H, int32_t W, const float* mean, const float* stdv,
-                             float* img, int64_t* label, void* mask, float* depth, dg_stream_t stream_) {
-    if (n_records < 1 || N < 1 || H < 1 || W < 1)
-        return fail(DG_ERR_INVALID, "dg_batch_prep: n_records=%d N=%d, output %dx%d must be positive", n_records, N, H, W);
-    if (W % 4) return fail(DG_ERR_UNSUPPORTED, "dg_batch_prep: output width %d is not a multiple of 4 (a lane stores four columns as one vector)", W);
-    if (H > DG_BATCH_MAX_SIDE || W > DG_BATCH_MAX_SIDE || N > 65535 || n_records > 65535)
-        return fail(DG_ERR_UNSUPPORTED, "dg_batch_prep: output %dx%d above %d a side, or N=%d / n_records=%d above 65535", H, W, DG_BATCH_MAX_SIDE, N,
-                    n_records);
-    if (!records_host || !tables_host || !params || !mean || !stdv) return fail(DG_ERR_INVALID, "dg_batch_prep: null pointer");
-    if ((((uintptr_t)img | (uintptr_t)label | (uintptr_t)mask | (uintptr_t)depth) & 15) || ((uintptr_t)params & 3))
-        return fail(DG_ERR_INVALID, "dg_batch_prep: img, label, mask and depth must be 16-byte aligned (whole-vector stores), params 4-byte aligned");
-    DgBatchArgs A;
-    memset(&A, 0, sizeof(A));
-    for (int c = 0; c < 3; ++c) {
-        A.mean[c] = mean[c]; A.stdv[c] = stdv[c];
-        if (!(A.stdv[c] > 0.f) || std::isinf(A.stdv[c]) || !(A.mean[c] == A.mean[c]) || std::isinf(A.mean[c]))
-            return fail(DG_ERR_INVALID, "dg_batch_prep: channel %d: mean=%g std=%g", c, (double)A.mean[c], (double)A.stdv[c]);
-    }
-    // which sample each output has a record for: every element is written, and by one record
-    std::vector<uint8_t> seen((size_t)3 * N, 0);
-    int n_out[3] = {0, 0, 0}, rule = -1;
-    for (int i = 0; i < n_records; ++i) {
-        const int32_t* r = records_host + (size_t)i * DG_BATCH_REC_WORDS;
-        const int kind = r[0], n = r[1];
-        if (kind < DG_BATCH_IMAGE || kind > DG_BATCH_LABEL_FILL) return fail(DG_ERR_INVALID, "dg_batch_prep: record %d: unknown kind %d (0 .. 4)", i, kind);
-        if (n < 0 || n >= N) return fail(DG_ERR_INVALID, "dg_batch_prep: record %d: sample %d outside 0 .. %d", i, n, N - 1);
-        const bool labels = kind == DG_BATCH_LABEL || kind == DG_BATCH_LABEL_FILL;
-        const int out = kind == DG_BATCH_IMAGE ? 0 : labels ? 1 : 2;
-        if (out == 0 ? !img : out == 1 ? (!label || !mask) : !depth)
-            return fail(DG_ERR_INVALID, "dg_batch_prep: record %d (kind %d) writes an output that is null", i, kind);
-        if (seen[(size_t)out * N + n]++) return fail(DG_ERR_INVALID, "dg_batch_prep: record %d: sample %d of output %d is written twice", i, n, out);
-        ++n_out[out];
-        if (labels) {
-            if (r[7] != DG_BATCH_MASK_BOOL_IGNORED && r[7] != DG_BATCH_MASK_FLOAT_POSITIVE)
-                return fail(DG_ERR_INVALID, "dg_batch_prep: record %d: unknown mask rule %d (0, 1)", i, r[7]);
-            if (rule >= 0 && r[7] != rule) return fail(DG_ERR_INVALID, "dg_batch_prep: record %d: mask rule %d after %d (one mask tensor: one rule)", i, r[7], rule);
-            rule = r[7];
-        }
-        if (kind == DG_BATCH_DEPTH_PLANE || kind == DG_BATCH_LABEL_FILL) continue;      // no source
-        if (int rc = batch_source_check("dg_batch_prep", i, r, tables_host + (size_t)n * (W + H), H, W, packed, packed_bytes)) return rc;
-    }
-    const void* outs[3] = {img, label, depth};
-    for (int o = 0; o < 3; ++o)
-        if (outs[o] && n_out[o] != N)
-            return fail(DG_ERR_INVALID, "dg_batch_prep: output %d has records for %d of %d samples (every element must be written)", o, n_out[o], N);
-    A.packed = packed;
-    A.recs = static_cast<const int32_t*>(params);
-    A.tables = A.recs + (size_t)n_records * DG_BATCH_REC_WORDS;
-    A.img = img; A.label = reinterpret_cast<long long*>(label); A.mask = mask; A.depth = depth;
-    A.n_records = n_records; A.N = N; A.H = H; A.W = W;
-    A.tiles_x = (W + DG_BATCH_TW - 1) / DG_BATCH_TW; A.tiles_y = (H + DG_BATCH_TH - 1) / DG_BATCH_TH;
-    DG_HIP(dg_launch_batch_prep(A, static_cast<hipStream_t>(stream_)));
-    return DG_OK;
-}
-
-// ---- frozen-backbone feature cache (dg_feat_cache.hip)
-// what both entries refuse before a launch; `lists`: index lists of n rows each (n * lists blocks along gridDim.y)
-static int featcache_check(const char* who, const void* cache, int32_t dtype, int64_t N, int64_t L, int64_t n, int lists) {
-    if (dtype < DG_FC_F32 || dtype > DG_FC_BF16) return fail(DG_ERR_INVALID, "%s: unknown dtype %d (0 float32, 1 float16, 2 bfloat16)", who, dtype);
-    if (N < 1 || L < 1 || n < 0) return fail(DG_ERR_INVALID, "%s: N=%lld L=%lld n=%lld (N and L positive, n not negative)", who, (long long)N, (long long)L, (long long)n);
-    if (n > DG_FC_MAX_ROWS / lists)
-        return fail(DG_ERR_UNSUPPORTED, "%s: %d list(s) of %lld rows in one call (at most %d rows)", who, lists, (long long)n, DG_FC_MAX_ROWS);
-    if (L > (1ll << 40) || N > (1ll << 62) / L) return fail(DG_ERR_UNSUPPORTED, "%s: a cache of %lld x %lld elements", who, (long long)N, (long long)L);
-    if (!cache) return fail(DG_ERR_INVALID, "%s: null pointer", who);
-    if ((uintptr_t)cache & (dtype == DG_FC_F32 ? 3 : 1)) return fail(DG_ERR_INVALID, "%s: the cache is not aligned to its element size", who);
-    return DG_OK;
-}
-
-extern "C" int dg_featcache_put(void* cache, int32_t dtype, int64_t N, int64_t L, const float* src, const int64_t* idx, int64_t n,
-                                dg_stream_t stream_) {
-    if (int rc = featcache_check(__func__, cache, dtype, N, L, n, 1)) return rc;
-    if (n == 0) return DG_OK;
-    if (!src || !idx) return fail(DG_ERR_INVALID, "dg_featcache_put: null pointer");
-    if (((uintptr_t)src & 3) || ((uintptr_t)idx & 7)) return fail(DG_ERR_INVALID, "dg_featcache_put: src must be 4-byte aligned, idx 8-byte aligned");
-    DG_HIP(dg_launch_featcache_put(cache, dtype, N, L, src, reinterpret_cast<const long long*>(idx), (int)n, static_cast<hipStream_t>(stream_)));
-    return DG_OK;
-}
-
-extern "C" int dg_featcache_gather(const void* cache, int32_t dtype, int64_t N, int64_t L, const int64_t* idx_a, const int64_t* idx_b,
-                                   int64_t n, float* out, dg_stream_t stream_) {
-    if (int rc = featcache_check(__func__, cache, dtype, N, L, n, idx_b ? 2 : 1)) return rc;
-    if (n == 0) return DG_OK;
-    if (!idx_a || !out) return fail(DG_ERR_INVALID, "dg_featcache_gather: null pointer");
-    if (((uintptr_t)out & 3) || (((uintptr_t)idx_a | (uintptr_t)idx_b) & 7))
-        return fail(DG_ERR_INVALID, "dg_featcache_gather: out must be 4-byte aligned, idx_a and idx_b 8-byte aligned");
-    DG_HIP(dg_launch_featcache_gather(cache, dtype, N, L, reinterpret_cast<const long long*>(idx_a), reinterpret_cast<const long long*>(idx_b),
-                                      (int)n, out, static_cast<hipStream_t>(stream_)));
-    return DG_OK;
-}
-
-// ---- device-resident sample cache (dg_sample_cache.hip)
-// what both entries refuse before a launch; `lists`: index lists of n rows each
-static int samplecache_check(const char* who, const void* cache, int64_t n_images, int32_t has_labels, int32_t with_depth, int32_t H, int32_t W,
-                             int64_t n, int lists) {
-    if (n_images < 1 || H < 1 || W < 1 || n < 0)
-        return fail(DG_ERR_INVALID, "%s: n_images=%lld, rows of %dx%d, n=%lld (n_images, H and W positive, n not negative)", who, (long long)n_images, H,
-                    W, (long long)n);
-    if ((has_labels != 0 && has_labels != 1) || (with_depth != 0 && with_depth != 1))
-        return fail(DG_ERR_INVALID, "%s: has_labels=%d with_depth=%d (0 or 1 each)", who, has_labels, with_depth);
-    if (W % 4) return fail(DG_ERR_UNSUPPORTED, "%s: row width %d is not a multiple of 4 (a lane moves four columns as one word)", who, W);
-    if (H > DG_BATCH_MAX_SIDE || W > DG_BATCH_MAX_SIDE) return fail(DG_ERR_UNSUPPORTED, "%s: rows of %dx%d above %d a side", who, H, W, DG_BATCH_MAX_SIDE);
-    if (n > DG_SC_MAX_ROWS / lists)
-        return fail(DG_ERR_UNSUPPORTED, "%s: %d list(s) of %lld rows in one call (at most %d rows)", who, lists, (long long)n, DG_SC_MAX_ROWS);
-    if (n_images > (1ll << 62) / ((long long)5 * H * W)) return fail(DG_ERR_UNSUPPORTED, "%s: a cache of %lld rows of %dx%d", who, (long long)n_images, H, W);
-    if (!cache) return fail(DG_ERR_INVALID, "%s: null pointer", who);
-    if ((uintptr_t)cache & 3) return fail(DG_ERR_INVALID, "%s: the cache must be 4-byte aligned (a lane moves four bytes as one word)", who);
-    return DG_OK;
-}
-
-extern "C" int dg_samplecache_put(uint8_t* cache, int64_t n_images, int32_t has_labels, int32_t with_depth, int32_t H, int32_t W,
-                                  const int64_t* idx, int32_t n, const uint8_t* packed, size_t packed_bytes, const int32_t* records_host,
-                                  const int32_t* tables_host, const void* params, int32_t n_records, dg_stream_t stream_) {
-    if (int rc = samplecache_check(__func__, cache, n_images, has_labels, with_depth, H, W, n, 1)) return rc;
-    if (n == 0) return DG_OK;
-    if (n_records < 1 || n_records > 65535) return fail(DG_ERR_INVALID, "dg_samplecache_put: n_records=%d outside [1, 65535]", n_records);
-    if (!idx || !records_host || !tables_host || !params) return fail(DG_ERR_INVALID, "dg_samplecache_put: null pointer");
-    if (((uintptr_t)idx & 7) || ((uintptr_t)params & 3)) return fail(DG_ERR_INVALID, "dg_samplecache_put: idx must be 8-byte aligned, params 4-byte aligned");
-    // which plane group of each sample has a record: every byte of every row is written, and by one record
-    std::vector<uint8_t> seen((size_t)3 * n, 0);
-    int n_out[3] = {0, 0, 0};
-    for (int i = 0; i < n_records; ++i) {
-        const int32_t* r = records_host + (size_t)i * DG_BATCH_REC_WORDS;
-        const int kind = r[0], k = r[1];
-        if (kind < DG_BATCH_IMAGE || kind > DG_BATCH_LABEL_FILL) return fail(DG_ERR_INVALID, "dg_samplecache_put: record %d: unknown kind %d (0 .. 4)", i, kind);
-        if (k < 0 || k >= n) return fail(DG_ERR_INVALID, "dg_samplecache_put: record %d: sample %d outside 0 .. %d", i, k, n - 1);
-        const int out = kind == DG_BATCH_IMAGE ? 0 : (kind == DG_BATCH_LABEL || kind == DG_BATCH_LABEL_FILL) ? 1 : 2;
-        if (kind == DG_BATCH_LABEL && !has_labels)
-            return fail(DG_ERR_INVALID, "dg_samplecache_put: record %d: sample %d carries a label but the cache has no label plane", i, k);
-        if (kind == DG_BATCH_LABEL_FILL && has_labels)
-            return fail(DG_ERR_INVALID, "dg_samplecache_put: record %d: sample %d carries no label but the cache has a label plane", i, k);
-        if (out == 2 && !with_depth) return fail(DG_ERR_INVALID, "dg_samplecache_put: record %d: sample %d carries depth but the cache has no depth plane", i, k);
-        if (seen[(size_t)out * n + k]++) return fail(DG_ERR_INVALID, "dg_samplecache_put: record %d: plane group %d of sample %d is written twice", i, out, k);
-        ++n_out[out];
-        if (kind == DG_BATCH_DEPTH_PLANE || kind == DG_BATCH_LABEL_FILL) continue;      // no source
-        if (int rc = batch_source_check("dg_samplecache_put", i, r, tables_host + (size_t)k * (W + H), H, W, packed, packed_bytes)) return rc;
-    }
-    if (n_out[0] != n || (has_labels && n_out[1] != n) || n_out[2] != (with_depth ? n : 0))
-        return fail(DG_ERR_INVALID, "dg_samplecache_put: records for %d images, %d labels and %d depth maps of %d samples (every byte of a row must be written)",
-                    n_out[0], n_out[1], n_out[2], n);
-    DgSampleCachePutArgs A;
-    memset(&A, 0, sizeof(A));
-    A.cache = cache; A.idx = reinterpret_cast<const long long*>(idx); A.packed = packed;
-    A.recs = static_cast<const int32_t*>(params);
-    A.tables = A.recs + (size_t)n_records * DG_BATCH_REC_WORDS;
-    A.n_images = n_images; A.planes = 3 + has_labels + with_depth;
-    A.label_plane = has_labels ? 3 : -1; A.depth_plane = with_depth ? 3 + has_labels : -1;
-    A.n_records = n_records; A.n = n; A.H = H; A.W = W;
-    A.tiles_x = (W + DG_BATCH_TW - 1) / DG_BATCH_TW; A.tiles_y = (H + DG_BATCH_TH - 1) / DG_BATCH_TH;
-    DG_HIP(dg_launch_samplecache_put(A, static_cast<hipStream_t>(stream_)));
-    return DG_OK;
-}
-
-extern "C" int dg_samplecache_gather(const uint8_t* cache, int64_t n_images, int32_t has_labels, int32_t with_depth, int32_t H, int32_t W,
-                                     const int64_t* idx_a, const int64_t* idx_b, int32_t n, const float* mean, const float* stdv,
-                                     int32_t label_offset, int32_t fill, int32_t mask_rule, float* img, int64_t* label, void* mask, float* depth,
-                                     dg_stream_t stream_) {
-    if (int rc = samplecache_check(__func__, cache, n_images, has_labels, with_depth, H, W, n, idx_b ? 2 : 1)) return rc;
-    if (n == 0) return DG_OK;
-    if (!idx_a) return fail(DG_ERR_INVALID, "dg_samplecache_gather: null pointer");
-    if (((uintptr_t)idx_a | (uintptr_t)idx_b) & 7) return fail(DG_ERR_INVALID, "dg_samplecache_gather: idx_a and idx_b must be 8-byte aligned");
-    if (!img && !label && !mask && !depth) return fail(DG_ERR_INVALID, "dg_samplecache_gather: no output asked for");
-    if (((uintptr_t)img | (uintptr_t)label | (uintptr_t)mask | (uintptr_t)depth) & 15)
-        return fail(DG_ERR_INVALID, "dg_samplecache_gather: img, label, mask and depth must be 16-byte aligned (whole-vector stores)");
-    if (depth && !with_depth) return fail(DG_ERR_INVALID, "dg_samplecache_gather: depth asked of a cache without a depth plane");
-    if (mask && mask_rule != DG_BATCH_MASK_BOOL_IGNORED && mask_rule != DG_BATCH_MASK_FLOAT_POSITIVE)
-        return fail(DG_ERR_INVALID, "dg_samplecache_gather: unknown mask rule %d (0, 1)", mask_rule);
-    DgSampleCacheGatherArgs A;
-    memset(&A, 0, sizeof(A));
-    if (img) {
-        if (!mean || !stdv) return fail(DG_ERR_INVALID, "dg_samplecache_gather: img needs mean and stdv");
-        for (int c = 0; c < 3; ++c) {
-            A.mean[c] = mean[c]; A.stdv[c] = stdv[c];
-            if (!(A.stdv[c] > 0.f) || std::isinf(A.stdv[c]) || !(A.mean[c] == A.mean[c]) || std::isinf(A.mean[c]))
-                return fail(DG_ERR_INVALID, "dg_samplecache_gather: channel %d: mean=%g std=%g", c, (double)A.mean[c], (double)A.stdv[c]);
-        }
-    }
-    A.cache = cache; A.idx_a = reinterpret_cast<const long long*>(idx_a); A.idx_b = reinterpret_cast<const long long*>(idx_b);
-    A.img = img; A.label = reinterpret_cast<long long*>(label); A.mask = mask; A.depth = depth;
-    A.n_images = n_images; A.planes = 3 + has_labels + with_depth;
-    A.label_plane = has_labels ? 3 : -1; A.depth_plane = with_depth ? 3 + has_labels : -1;
-    A.n = n; A.H = H; A.W = W;
-    A.label_offset = label_offset; A.fill = fill; A.mask_rule = mask_rule;
-    DG_HIP(dg_launch_samplecache_gather(A, static_cast<hipStream_t>(stream_)));
     return DG_OK;
 }

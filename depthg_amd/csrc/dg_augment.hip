@@ -13,7 +13,7 @@
 // float32 in the order of torchvision's tensor transforms, one rounding per operation (contraction is off for this unit: the float32
 // torch chain the tests hold this against rounds every product); the blur's weights, products and sum are fp64, rounded once per
 // pixel; the contrast op's image mean is the fp64 sum of the float32 grays.
-#include "dg_aux_args.h"
+#include "dg_data_args.h"
 #include "dg_device.h"
 
 #pragma clang fp contract(off)

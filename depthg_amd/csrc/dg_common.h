@@ -1,5 +1,5 @@
 // What every unit of the library shares: the public header, the list of the library's switches, the two normalisation constants.
-// Device primitives: dg_device.h; a subsystem's argument blocks and launchers: dg_corr_args.h, dg_head_args.h, dg_eval_args.h, dg_loss_args.h, dg_aux_args.h.
+// Device primitives: dg_device.h; a subsystem's argument blocks and launchers: dg_corr_args.h, dg_head_args.h, dg_eval_args.h, dg_loss_args.h, dg_data_args.h, dg_aux_args.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -13,7 +13,7 @@
 // The row index is read from device memory (int64) by every block of the row; an index outside [0, N) ends the block before any
 // address is formed from it.
 #include "dg_device.h"
-#include "dg_aux_args.h"
+#include "dg_data_args.h"
 
 template <int DT> struct FcElem;
 template <> struct FcElem<DG_FC_F32> { typedef float T; static constexpr int V = 4; };

@@ -42,6 +42,21 @@ from . import knn, ops
 
 MAX_DECODE_THREADS = 16       # the decoding pool never grows past this, whatever num_workers says and however many CPUs the host shows
 
+
+def _decode_threads(num_workers):
+    return max(0, min(int(num_workers), MAX_DECODE_THREADS))
+
+
+def _default_device(device):
+    """`device`, or without one the first GPU if there is one, else the CPU."""
+    return ("cuda:0" if torch.cuda.is_available() else "cpu") if device is None else device
+
+
+def _refuse_random_crop(crop_type, subject, what):
+    """A cache keeps ONE view of every image: `subject` (the message's opening, its prefix included) refuses the random cropper."""
+    if crop_type == "random":
+        raise ValueError(f"{subject} with loader_crop_type = 'random': the {what} of an image would depend on the crop's draw; use 'center' or None")
+
 # decoded planes of one sample: image (h, w, 3) uint8; label (h, w) uint8 or None; depth (h, w) uint8, None, or PLANE
 Sample = namedtuple("Sample", "image label depth")
 PLANE = "plane"               # Sample.depth of the `_plane` depth types: a constant 255 map, no file is read (src/data.py:897-898)
@@ -347,10 +362,8 @@ class ContrastiveBatches:
             raise ValueError(f"depthg_amd.data: batch_size={batch_size}")
         resized_size(1, 1, self.res, loader_crop_type)                  # (refuses an unknown cropper before anything is read)
         self.return_depth = bool(dataset.return_depth if return_depth is None else return_depth)
-        self.threads = max(0, min(int(num_workers), MAX_DECODE_THREADS))
-        if device is None:
-            device = "cuda:0" if torch.cuda.is_available() else "cpu"
-        self.device = torch.device(device)
+        self.threads = _decode_threads(num_workers)
+        self.device = torch.device(_default_device(device))
         self.num_neighbors = int(getattr(cfg, "num_neighbors", 7))
         self.nns = None
         if self.pos:
@@ -485,19 +498,15 @@ def build_feature_cache(net, dataset, cfg, res, crop_type, dtype=torch.float32, 
     `sample_cache`: a sample_cache.SampleCache of the same split and transform to fill from the samples this pass decodes anyway, so
     that a run that wants both caches decodes the split once."""
     from .feature_cache import FeatureCache
-    if crop_type == "random":
-        raise ValueError("depthg_amd.data: build_feature_cache with loader_crop_type = 'random': the features of an image would depend on "
-                         "the crop's draw; use 'center' or None")
+    _refuse_random_crop(crop_type, "depthg_amd.data: build_feature_cache", "features")
     if getattr(cfg, "arch", "dino") == "dino_depth" or not hasattr(net, "forward_pair_features") or not hasattr(net, "_backbone"):
         raise ValueError("depthg_amd.data: build_feature_cache serves cfg.arch = 'dino' (a FrozenBackboneFeaturizer); the depth-guided "
                          "featurizer of arch 'dino_depth' is out of scope for the feature cache")
     resized_size(1, 1, res, crop_type)
-    if device is None:
-        device = "cuda:0" if torch.cuda.is_available() else "cpu"
-    device = torch.device(device)
+    device = torch.device(_default_device(device))
     if batch_size is None:
         batch_size = 128 if cfg.model_type == "vit_small" else 64
-    threads = max(0, min(int(num_workers), MAX_DECODE_THREADS))
+    threads = _decode_threads(num_workers)
     n = len(dataset)
     cache = None
     net.model.eval()
@@ -538,14 +547,10 @@ def new_sample_cache(dataset, image_set, res, crop_type, want_depth, device):
     """An empty sample_cache.SampleCache for `dataset` under the loader transform (res, crop_type): what build_sample_cache fills, and
     what build_feature_cache(sample_cache=...) takes to fill on its own pass."""
     from .sample_cache import SampleCache
-    if crop_type == "random":
-        raise ValueError("depthg_amd.data: a sample cache with loader_crop_type = 'random': the bytes of an image would depend on the crop's "
-                         "draw; use 'center' or None")
+    _refuse_random_crop(crop_type, "depthg_amd.data: a sample cache", "bytes")
     resized_size(1, 1, res, crop_type)
     if len(dataset) < 1:
         raise ValueError("depthg_amd.data: a sample cache of an empty dataset")
-    if device is None:
-        device = "cuda:0" if torch.cuda.is_available() else "cpu"
     return SampleCache(len(dataset), int(res), int(res), dataset.has_labels, want_depth, dataset.label_offset if dataset.has_labels else 0, -1,
                        dataset.mask_rule, device=device, meta=sample_cache_meta(dataset, image_set, res, crop_type, want_depth))
 
@@ -553,7 +558,7 @@ def new_sample_cache(dataset, image_set, res, crop_type, want_depth, device):
 def fill_sample_cache(cache, dataset, res, crop_type, num_workers=0, batch_size=64):
     """Put every row of `cache` that has not been put yet, in index order: decoding in the thread pool (min(num_workers, 16) threads),
     one `put` - one launch - per `batch_size` images."""
-    threads = max(0, min(int(num_workers), MAX_DECODE_THREADS))
+    threads = _decode_threads(num_workers)
     missing = np.flatnonzero(~cache.filled).tolist()
     for i in range(0, len(missing), int(batch_size)):
         inds = missing[i:i + int(batch_size)]

@@ -466,6 +466,54 @@ BATCH_MASK_BOOL_IGNORED, BATCH_MASK_FLOAT_POSITIVE = 0, 1                       
 BATCH_REC_WORDS = 8
 
 
+def _packed_source(who, packed, records, tables, H, W, device, rows=None, params=None):
+    """What data.pack_batch makes, as dg_batch_prep and dg_samplecache_put take it: records CPU int32 (k, 8), tables CPU int32 of W + H
+    columns - and `rows` rows, if given - and packed a flat uint8 tensor.  Returns (src, params, device, stream): packed on `device`
+    (None: where packed or `params` lives, else the current GPU) and the device copy of [records, tables] - `params`, or uploaded
+    here, once."""
+    for t, name in ((records, "records"), (tables, "tables")):
+        if t.dtype != torch.int32 or t.is_cuda or not t.is_contiguous():
+            raise ValueError(f"depthg_amd: {who} wants `{name}` as a contiguous CPU int32 tensor")
+    if (records.dim() != 2 or records.shape[1] != BATCH_REC_WORDS or tables.dim() != 2 or tables.shape[1] != W + H or
+            (rows is not None and tables.shape[0] != rows)):
+        k, N = ("n", "N") if rows is None else ("k", rows)
+        raise ValueError(f"depthg_amd: {who} wants records ({k}, {BATCH_REC_WORDS}) and tables ({N}, {W} + {H}), got {tuple(records.shape)} and "
+                         f"{tuple(tables.shape)}")
+    if packed.dtype != torch.uint8 or packed.dim() != 1 or not packed.is_contiguous():
+        raise ValueError(f"depthg_amd: {who} wants `packed` as a flat contiguous uint8 tensor")
+    if device is None:
+        device = packed.device if packed.is_cuda else (params.device if params is not None else torch.device("cuda", torch.cuda.current_device()))
+    dev = torch.device(device)
+    stream = _stream(dev)
+    src = _on_gpu(packed.to(dev, non_blocking=True), "packed")
+    if params is None:
+        params = torch.cat([records.reshape(-1), tables.reshape(-1)]).to(dev, non_blocking=True)
+    elif not params.is_cuda or params.dtype != torch.int32 or params.numel() != records.numel() + tables.numel():
+        raise ValueError(f"depthg_amd: {who} wants `params` as the GPU int32 copy of [records, tables]")
+    return src, params, dev, stream
+
+
+def _loader_outputs(rows, H, W, names, mask_rule, dev):
+    """The loader's outputs `names` of `rows` samples, unwritten: img fp32 (rows,3,H,W), label int64, mask fp32 or bool by `mask_rule`,
+    depth fp32 (rows,H,W) each."""
+    kinds = {"img": ((rows, 3, H, W), torch.float32), "label": ((rows, H, W), torch.int64),
+             "mask": ((rows, H, W), torch.float32 if mask_rule == BATCH_MASK_FLOAT_POSITIVE else torch.bool), "depth": ((rows, H, W), torch.float32)}
+    return {k: _empty(*kinds[k], dev) for k in kinds if k in names}
+
+
+def _index_lists(who, cache, idx_a, idx_b=None, names=("idx_a", "idx_b")):
+    """The index lists of a cache entry: each a contiguous int64 tensor on the cache's device (the kernels read them there; the caller
+    has checked the values on the host), both of one length.  Returns (n, the rows of both lists together)."""
+    _on_gpu(cache, "cache")
+    for name, idx in zip(names, (idx_a,) if idx_b is None else (idx_a, idx_b)):
+        if idx.dtype != torch.int64 or idx.dim() != 1 or idx.device != cache.device or not idx.is_contiguous():
+            raise ValueError(f"depthg_amd: {who} wants `{name}` as a contiguous 1-d int64 tensor on {cache.device} (the kernel reads it there)")
+    n = idx_a.numel()
+    if idx_b is not None and idx_b.numel() != n:
+        raise ValueError(f"depthg_amd: {who}: {n} indices and {idx_b.numel()} positives")
+    return n, (2 * n if idx_b is not None else n)
+
+
 def batch_prep(packed, records, tables, out_size, device=None, mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225), params=None):
     """The loader transform of a whole batch in one launch (dg_batch_prep, dg_batch.hip).  packed: uint8 tensor of the decoded source
     planes - on the CPU (pinned memory makes the one upload asynchronous) or already on the GPU; records: CPU int32 (n_records, 8);
@@ -475,34 +523,13 @@ def batch_prep(packed, records, tables, out_size, device=None, mean=(0.485, 0.45
     element written."""
     lib = _lib.load()
     H, W = int(out_size[0]), int(out_size[1])
-    for t, name, dt in ((records, "records", torch.int32), (tables, "tables", torch.int32)):
-        if t.dtype != dt or t.is_cuda or not t.is_contiguous():
-            raise ValueError(f"depthg_amd: batch_prep wants `{name}` as a contiguous CPU int32 tensor")
-    if records.dim() != 2 or records.shape[1] != BATCH_REC_WORDS or tables.dim() != 2 or tables.shape[1] != W + H:
-        raise ValueError(f"depthg_amd: batch_prep wants records (n, {BATCH_REC_WORDS}) and tables (N, {W} + {H}), got {tuple(records.shape)} and "
-                         f"{tuple(tables.shape)}")
-    if packed.dtype != torch.uint8 or packed.dim() != 1 or not packed.is_contiguous():
-        raise ValueError("depthg_amd: batch_prep wants `packed` as a flat contiguous uint8 tensor")
-    if device is None:
-        device = packed.device if packed.is_cuda else (params.device if params is not None else torch.device("cuda", torch.cuda.current_device()))
-    dev = torch.device(device)
-    stream = _stream(dev)
-    src = _on_gpu(packed.to(dev, non_blocking=True), "packed")
-    if params is None:
-        params = torch.cat([records.reshape(-1), tables.reshape(-1)]).to(dev, non_blocking=True)
-    elif not params.is_cuda or params.dtype != torch.int32 or params.numel() != records.numel() + tables.numel():
-        raise ValueError("depthg_amd: batch_prep wants `params` as the GPU int32 copy of [records, tables]")
+    src, params, dev, stream = _packed_source("batch_prep", packed, records, tables, H, W, device, params=params)
     n_records, N = records.shape[0], tables.shape[0]
     kinds = set(records[:, 0].tolist())
     rules = set(records[:, 7][(records[:, 0] == BATCH_LABEL) | (records[:, 0] == BATCH_LABEL_FILL)].tolist())
-    out = {}
-    if BATCH_IMAGE in kinds:
-        out["img"] = _empty((N, 3, H, W), torch.float32, dev)
-    if kinds & {BATCH_LABEL, BATCH_LABEL_FILL}:
-        out["label"] = _empty((N, H, W), torch.int64, dev)
-        out["mask"] = _empty((N, H, W), torch.float32 if rules == {BATCH_MASK_FLOAT_POSITIVE} else torch.bool, dev)
-    if kinds & {BATCH_DEPTH, BATCH_DEPTH_PLANE}:
-        out["depth"] = _empty((N, H, W), torch.float32, dev)
+    names = ((("img",) if BATCH_IMAGE in kinds else ()) + (("label", "mask") if kinds & {BATCH_LABEL, BATCH_LABEL_FILL} else ()) +
+             (("depth",) if kinds & {BATCH_DEPTH, BATCH_DEPTH_PLANE} else ()))
+    out = _loader_outputs(N, H, W, names, BATCH_MASK_FLOAT_POSITIVE if rules == {BATCH_MASK_FLOAT_POSITIVE} else BATCH_MASK_BOOL_IGNORED, dev)
     rc = lib.dg_batch_prep(_ptr(src), src.numel(), ctypes.c_void_p(records.data_ptr()), ctypes.c_void_p(tables.data_ptr()), _ptr(params),
                            n_records, N, H, W, (ctypes.c_float * 3)(*mean), (ctypes.c_float * 3)(*std), _ptr(out.get("img")),
                            _ptr(out.get("label")), _ptr(out.get("mask")), _ptr(out.get("depth")), stream)
@@ -514,26 +541,21 @@ FEATURE_CACHE_DTYPES = {torch.float32: _lib.DG_FC_F32, torch.float16: _lib.DG_FC
 FEATURE_CACHE_MAX_ROWS = 65535      # rows one dg_featcache_* call moves (gather: the two lists together)
 
 
-def _feature_cache_operands(who, cache, lists):
-    """The cache as the two entries take it - a contiguous (N, L) GPU tensor of a storage type - and each index list of `lists` as a
-    contiguous int64 tensor on the cache's device (the kernels read them there; the caller has checked the values on the host)."""
+def _feature_cache_operands(who, cache, idx_a, idx_b=None, names=("idx_a", "idx_b")):
+    """The cache as the two entries take it - a contiguous (N, L) GPU tensor of a storage type - and its index lists (_index_lists).
+    Returns (the storage type's id, n, rows)."""
     if cache.dim() != 2 or cache.dtype not in FEATURE_CACHE_DTYPES or not cache.is_contiguous():
         raise ValueError(f"depthg_amd: {who} wants the cache as a contiguous (N, L) tensor of float32, float16 or bfloat16, got "
                          f"{tuple(cache.shape)} {cache.dtype}")
-    _on_gpu(cache, "cache")
-    for name, idx in lists:
-        if idx.dtype != torch.int64 or idx.dim() != 1 or idx.device != cache.device or not idx.is_contiguous():
-            raise ValueError(f"depthg_amd: {who} wants `{name}` as a contiguous 1-d int64 tensor on {cache.device} (the kernel reads it there)")
-    return FEATURE_CACHE_DTYPES[cache.dtype]
+    return (FEATURE_CACHE_DTYPES[cache.dtype],) + _index_lists(who, cache, idx_a, idx_b, names)
 
 
 def feature_cache_put(cache, idx, src):
     """Rows idx[0..n) of `cache` (N, L) = src (n, L) - or (n, C, h, w) with C h w = L - converted to the cache's dtype with torch's
     rounding (dg_featcache_put, k_fc_put of dg_feat_cache.hip): one launch.  `idx`: int64 on the cache's device, each row once."""
     lib = _lib.load()
-    dt = _feature_cache_operands("feature_cache_put", cache, (("idx", idx),))
+    dt, n, _ = _feature_cache_operands("feature_cache_put", cache, idx, names=("idx",))
     N, L = cache.shape
-    n = idx.numel()
     src = _f32c(src, "src")
     if src.device != cache.device or src.numel() != n * L or src.shape[0] != n:
         raise ValueError(f"depthg_amd: feature_cache_put: src {tuple(src.shape)} on {src.device} is not {n} rows of {L} elements on {cache.device}")
@@ -546,13 +568,8 @@ def feature_cache_gather(cache, idx_a, idx_b=None, out=None):
     allocation (dg_featcache_gather, k_fc_gather of dg_feat_cache.hip): the layout the head's paired pass takes its two maps in.
     Indices: int64 on the cache's device; they may repeat.  `out`: a buffer to write instead of a new one; every element is written."""
     lib = _lib.load()
-    lists = (("idx_a", idx_a),) + ((("idx_b", idx_b),) if idx_b is not None else ())
-    dt = _feature_cache_operands("feature_cache_gather", cache, lists)
+    dt, n, rows = _feature_cache_operands("feature_cache_gather", cache, idx_a, idx_b)
     N, L = cache.shape
-    n = idx_a.numel()
-    if idx_b is not None and idx_b.numel() != n:
-        raise ValueError(f"depthg_amd: feature_cache_gather: {n} indices and {idx_b.numel()} positives")
-    rows = 2 * n if idx_b is not None else n
     if out is None:
         out = _empty((rows, L), torch.float32, cache.device)
     elif out.dtype != torch.float32 or out.device != cache.device or tuple(out.shape) != (rows, L) or not out.is_contiguous():
@@ -565,18 +582,14 @@ def feature_cache_gather(cache, idx_a, idx_b=None, out=None):
 SAMPLE_CACHE_MAX_ROWS = 65535       # rows one dg_samplecache_gather call forms (the two lists together)
 
 
-def _sample_cache_operands(who, cache, has_labels, with_depth, lists):
+def _sample_cache_operands(who, cache, has_labels, with_depth, idx_a, idx_b=None, names=("idx_a", "idx_b")):
     """The cache as the two entries take it - a contiguous uint8 (n_images, planes, H, W) GPU tensor with planes = 3 + has_labels +
-    with_depth - and each index list of `lists` as a contiguous int64 tensor on the cache's device (the kernels read them there;
-    the caller has checked the values on the host)."""
+    with_depth - and its index lists (_index_lists).  Returns (n, rows)."""
     planes = 3 + int(bool(has_labels)) + int(bool(with_depth))
     if cache.dim() != 4 or cache.dtype != torch.uint8 or not cache.is_contiguous() or cache.shape[1] != planes:
         raise ValueError(f"depthg_amd: {who} wants the cache as a contiguous uint8 (n_images, {planes}, H, W) tensor, got "
                          f"{tuple(cache.shape)} {cache.dtype}")
-    _on_gpu(cache, "cache")
-    for name, idx in lists:
-        if idx.dtype != torch.int64 or idx.dim() != 1 or idx.device != cache.device or not idx.is_contiguous():
-            raise ValueError(f"depthg_amd: {who} wants `{name}` as a contiguous 1-d int64 tensor on {cache.device} (the kernel reads it there)")
+    return _index_lists(who, cache, idx_a, idx_b, names)
 
 
 def sample_cache_put(cache, has_labels, with_depth, idx, packed, records, tables):
@@ -585,21 +598,9 @@ def sample_cache_put(cache, has_labels, with_depth, idx, packed, records, tables
     dg_sample_cache.hip): one launch.  packed / records / tables: what data.pack_batch makes and ops.batch_prep takes; `idx`: int64
     on the cache's device, each row once."""
     lib = _lib.load()
-    _sample_cache_operands("sample_cache_put", cache, has_labels, with_depth, (("idx", idx),))
+    n, _ = _sample_cache_operands("sample_cache_put", cache, has_labels, with_depth, idx, names=("idx",))
     N, _, H, W = cache.shape
-    for t, name in ((records, "records"), (tables, "tables")):
-        if t.dtype != torch.int32 or t.is_cuda or not t.is_contiguous():
-            raise ValueError(f"depthg_amd: sample_cache_put wants `{name}` as a contiguous CPU int32 tensor")
-    n = idx.numel()
-    if records.dim() != 2 or records.shape[1] != BATCH_REC_WORDS or tuple(tables.shape) != (n, W + H):
-        raise ValueError(f"depthg_amd: sample_cache_put wants records (k, {BATCH_REC_WORDS}) and tables ({n}, {W} + {H}), got {tuple(records.shape)} "
-                         f"and {tuple(tables.shape)}")
-    if packed.dtype != torch.uint8 or packed.dim() != 1 or not packed.is_contiguous():
-        raise ValueError("depthg_amd: sample_cache_put wants `packed` as a flat contiguous uint8 tensor")
-    dev = cache.device
-    stream = _stream(dev)
-    src = packed.to(dev, non_blocking=True)
-    params = torch.cat([records.reshape(-1), tables.reshape(-1)]).to(dev, non_blocking=True)
+    src, params, _, stream = _packed_source("sample_cache_put", packed, records, tables, H, W, cache.device, rows=n)
     rc = lib.dg_samplecache_put(_ptr(cache), N, int(bool(has_labels)), int(bool(with_depth)), H, W, _ptr(idx), n, _ptr(src), src.numel(),
                                 ctypes.c_void_p(records.data_ptr()), ctypes.c_void_p(tables.data_ptr()), _ptr(params), records.shape[0], stream)
     _lib.check(rc, "dg_samplecache_put")
@@ -613,26 +614,14 @@ def sample_cache_gather(cache, has_labels, with_depth, idx_a, idx_b=None, label_
     `mask_rule`, depth fp32 (rows,H,W) - those of them `want` names (None: all the cache can form), every element written.  Indices:
     int64 on the cache's device; they may repeat."""
     lib = _lib.load()
-    lists = (("idx_a", idx_a),) + ((("idx_b", idx_b),) if idx_b is not None else ())
-    _sample_cache_operands("sample_cache_gather", cache, has_labels, with_depth, lists)
+    n, rows = _sample_cache_operands("sample_cache_gather", cache, has_labels, with_depth, idx_a, idx_b)
     N, _, H, W = cache.shape
-    n = idx_a.numel()
-    if idx_b is not None and idx_b.numel() != n:
-        raise ValueError(f"depthg_amd: sample_cache_gather: {n} indices and {idx_b.numel()} positives")
     can = ("img", "label", "mask") + (("depth",) if with_depth else ())
     want = can if want is None else tuple(want)
     if not want or set(want) - set(can):
         raise ValueError(f"depthg_amd: sample_cache_gather: `want` = {want!r}, this cache forms {can!r}")
-    rows, dev = (2 * n if idx_b is not None else n), cache.device
-    out = {}
-    if "img" in want:
-        out["img"] = _empty((rows, 3, H, W), torch.float32, dev)
-    if "label" in want:
-        out["label"] = _empty((rows, H, W), torch.int64, dev)
-    if "mask" in want:
-        out["mask"] = _empty((rows, H, W), torch.float32 if mask_rule == BATCH_MASK_FLOAT_POSITIVE else torch.bool, dev)
-    if "depth" in want:
-        out["depth"] = _empty((rows, H, W), torch.float32, dev)
+    dev = cache.device
+    out = _loader_outputs(rows, H, W, want, mask_rule, dev)
     rc = lib.dg_samplecache_gather(_ptr(cache), N, int(bool(has_labels)), int(bool(with_depth)), H, W, _ptr(idx_a), _ptr(idx_b), n,
                                    (ctypes.c_float * 3)(*mean), (ctypes.c_float * 3)(*std), int(label_offset), int(fill), int(mask_rule),
                                    _ptr(out.get("img")), _ptr(out.get("label")), _ptr(out.get("mask")), _ptr(out.get("depth")), _stream(dev))

@@ -5,9 +5,9 @@ the same bytes of an image, its label and its depth map in every epoch, and ever
 Normalize, `label - 1`, the masks, the depth as float (src/data.py:894-902, :126-128) - is arithmetic on those bytes.  The cache
 stores them once as a uint8 tensor (n_images, planes, H, W) at the loader's OUTPUT size, planes R, G, B, then the label if the dataset
 has labels, then the depth if it is wanted: 251 KB per image at 224 x 224 with all five.  `put` writes rows from decoded samples with
-one launch (ops.sample_cache_put, k_sc_put of dg_sample_cache.hip: k_batch_prep's geometry without its arithmetic), `gather` hands a
-batch and its positives back as img / label / mask / depth in the step's dtypes from ONE launch (ops.sample_cache_gather,
-k_sc_gather) - no file, no decoder, no pinned buffer, no upload but the indices.  data.build_sample_cache fills one and
+one launch (ops.sample_cache_put, k_sc_put of dg_sample_cache.hip: k_batch_prep's tile prologue and gather, the bytes stored as they
+are), `gather` hands a batch and its positives back as img / label / mask / depth in the step's dtypes from ONE launch
+(ops.sample_cache_gather, k_sc_gather) - no file, no decoder, no pinned buffer, no upload but the indices.  data.build_sample_cache fills one and
 data.ContrastiveBatches(sample_cache=...) serves its batches from it.
 
 On a CPU `device` the class is plain torch - index_copy_ / index_select on the byte tensor, then the operations of data._cpu_chain in
@@ -18,9 +18,10 @@ import numpy as np
 import torch
 
 from . import ops
+from .row_cache import RowCache
 
 
-class SampleCache:
+class SampleCache(RowCache):
     """SampleCache(n_images, H, W, has_labels, with_depth, label_offset, fill, mask_rule, device, meta=None): row i = the planes of image i.
         has_labels, with_depth       whether a row carries a label plane / a depth plane
         label_offset, fill           label = byte + label_offset; without a label plane the label is the constant `fill`
@@ -36,10 +37,11 @@ class SampleCache:
     Indices are CPU int64 tensors or sequences of ints, checked on the host before anything is launched: an index outside
     [0, n_images) is an IndexError; a duplicate inside one `put`, a count that differs from the samples', and a `gather` of a row that
     was never put are ValueErrors.  `gather` may repeat an index, inside a list or between them."""
+    noun = "sample cache"
 
     def __init__(self, n_images, H, W, has_labels, with_depth, label_offset, fill, mask_rule, device=None, meta=None):
-        self.n_images, self.H, self.W = int(n_images), int(H), int(W)
-        if self.n_images < 1 or self.H < 1 or self.W < 1:
+        self.H, self.W = int(H), int(W)
+        if int(n_images) < 1 or self.H < 1 or self.W < 1:
             raise ValueError(f"depthg_amd: SampleCache of {n_images} images of {H} x {W}")
         if self.W % 4:
             raise ValueError(f"depthg_amd: SampleCache rows of width {W}: the kernels move four columns as one word, as dg_batch_prep does; "
@@ -51,45 +53,12 @@ class SampleCache:
         self.planes = 3 + int(self.has_labels) + int(self.with_depth)
         self.label_plane = 3 if self.has_labels else None
         self.depth_plane = 3 + int(self.has_labels) if self.with_depth else None
-        if device is None:
-            device = "cuda:0" if torch.cuda.is_available() else "cpu"
-        self.device = torch.device(device)
-        need = self.n_images * self.planes * self.H * self.W
-        try:
-            self.data = torch.empty((self.n_images, self.planes, self.H, self.W), dtype=torch.uint8, device=self.device)
-        except torch.OutOfMemoryError as e:
-            raise torch.OutOfMemoryError(f"depthg_amd: a sample cache of {self.n_images} images of {self.planes} planes of {self.H} x {self.W} "
-                                         f"needs {need} bytes on {self.device}: {e}") from e
-        self.filled = np.zeros(self.n_images, dtype=bool)
-        self.meta = {"n_images": self.n_images, **(meta or {})}
-
-    @property
-    def nbytes(self):
-        return self.data.numel()
-
-    def _indices(self, indices, name):
-        """`indices` as a numpy int64 array, every value inside [0, n_images)."""
-        if isinstance(indices, torch.Tensor):
-            if indices.is_cuda or indices.is_floating_point() or indices.dtype == torch.bool or indices.dim() != 1:
-                raise ValueError(f"depthg_amd: SampleCache wants `{name}` as a 1-d CPU integer tensor or a sequence of ints, got "
-                                 f"{tuple(indices.shape)} {indices.dtype} on {indices.device}")
-            arr = indices.to(torch.int64).numpy()
-        else:
-            arr = np.asarray(indices)
-            if arr.ndim != 1 or (arr.size and arr.dtype.kind not in "iu"):
-                raise ValueError(f"depthg_amd: SampleCache wants `{name}` as a 1-d CPU integer tensor or a sequence of ints, got an array "
-                                 f"of shape {arr.shape} and type {arr.dtype}")
-            arr = arr.astype(np.int64, copy=False)
-        if arr.size and (arr.min() < 0 or arr.max() >= self.n_images):
-            bad = arr[(arr < 0) | (arr >= self.n_images)]
-            raise IndexError(f"depthg_amd: SampleCache `{name}` holds {int(bad[0])}, outside [0, {self.n_images})")
-        return arr
+        super().__init__(n_images, (self.planes, self.H, self.W), torch.uint8, device, meta,
+                         f"a sample cache of {int(n_images)} images of {self.planes} planes of {self.H} x {self.W}")
 
     def put(self, indices, samples, res, crop_type):
         from . import data
-        if crop_type == "random":
-            raise ValueError("depthg_amd: SampleCache.put with loader_crop_type = 'random': the bytes of an image would depend on the crop's "
-                             "draw; use 'center' or None")
+        data._refuse_random_crop(crop_type, "depthg_amd: SampleCache.put", "bytes")
         tables = []
         for k, s in enumerate(samples):
             xs, ys, out_size = data.loader_index_tables(s.image.shape[1], s.image.shape[0], res, crop_type)
@@ -108,9 +77,7 @@ class SampleCache:
         n = idx.size
         if len(samples) != n or len(tables) != n:
             raise ValueError(f"depthg_amd: SampleCache.put of {n} indices got {len(samples)} samples")
-        values, counts = np.unique(idx, return_counts=True)
-        if values.size != n:
-            raise ValueError(f"depthg_amd: SampleCache.put names row {int(values[counts > 1][0])} more than once in one call")
+        self._check_unique(idx)
         for k, s, (xs, ys) in zip(idx, samples, tables):
             if (s.label is not None) != self.has_labels:
                 raise ValueError(f"depthg_amd: SampleCache.put: sample {int(k)} " +
@@ -141,22 +108,10 @@ class SampleCache:
         self.filled[idx] = True
 
     def gather(self, inds, inds_pos=None):
-        lists = [self._indices(inds, "inds")] + ([self._indices(inds_pos, "inds_pos")] if inds_pos is not None else [])
-        n = lists[0].size
-        if inds_pos is not None and lists[1].size != n:
-            raise ValueError(f"depthg_amd: SampleCache.gather: {n} indices and {lists[1].size} positives")
-        both = np.concatenate(lists) if inds_pos is not None else np.ascontiguousarray(lists[0])
-        if not self.filled[both].all():
-            for idx, name in zip(lists, ("inds", "inds_pos")):
-                empty = idx[~self.filled[idx]]
-                if empty.size:
-                    raise ValueError(f"depthg_amd: SampleCache.gather: row {int(empty[0])} of `{name}` was never put")
-        rows = torch.from_numpy(both)
+        rows, _, idx_a, idx_b = self._gather_rows(inds, inds_pos, ("inds", "inds_pos"))
         if self.device.type == "cuda":
-            on_dev = rows.to(self.device)                      # one upload for both lists
-            out = ops.sample_cache_gather(self.data, self.has_labels, self.with_depth, on_dev[:n], on_dev[n:] if inds_pos is not None else None,
-                                          label_offset=self.label_offset, fill=self.fill, mask_rule=self.mask_rule,
-                                          mean=ops.IMAGENET_MEAN, std=ops.IMAGENET_STD)
+            out = ops.sample_cache_gather(self.data, self.has_labels, self.with_depth, idx_a, idx_b, label_offset=self.label_offset,
+                                          fill=self.fill, mask_rule=self.mask_rule, mean=ops.IMAGENET_MEAN, std=ops.IMAGENET_STD)
             return out["img"], out["label"], out["mask"], out.get("depth")
         planes = self.data.index_select(0, rows)
         mean, std = (torch.tensor(v, dtype=torch.float32).reshape(1, 3, 1, 1) for v in (ops.IMAGENET_MEAN, ops.IMAGENET_STD))
@@ -164,34 +119,19 @@ class SampleCache:
         if self.has_labels:
             label = planes[:, self.label_plane].to(torch.int64) + self.label_offset                  # ToTargetTensor, src/data.py:901
         else:
-            label = torch.full((both.size, self.H, self.W), self.fill, dtype=torch.int64)            # :126
+            label = torch.full((rows.numel(), self.H, self.W), self.fill, dtype=torch.int64)         # :126
         mask = (label == -1) if self.mask_rule == ops.BATCH_MASK_BOOL_IGNORED else (label > 0).to(torch.float32)
         depth = planes[:, self.depth_plane].to(torch.int64).float() if self.with_depth else None     # :894-898
         return img, label, mask, depth
 
-    def check_meta(self, expect_meta):
-        """ValueError naming the keys of `expect_meta` this cache's metadata lacks or holds another value for."""
-        differ = [k for k, v in expect_meta.items() if k not in self.meta or self.meta[k] != v]
-        if differ:
-            raise ValueError("depthg_amd: the sample cache was built for other settings: " +
-                             ", ".join(f"{k} = {self.meta.get(k)!r} (expected {expect_meta[k]!r})" for k in differ))
-
-    def save(self, path):
-        torch.save({"meta": dict(self.meta), "H": self.H, "W": self.W, "has_labels": self.has_labels, "with_depth": self.with_depth,
-                    "label_offset": self.label_offset, "fill": self.fill, "mask_rule": self.mask_rule,
-                    "filled": torch.from_numpy(self.filled.copy()), "data": self.data.cpu()}, path)
+    def _header(self):
+        return {"H": self.H, "W": self.W, "has_labels": self.has_labels, "with_depth": self.with_depth, "label_offset": self.label_offset,
+                "fill": self.fill, "mask_rule": self.mask_rule}
 
     @classmethod
-    def load(cls, path, device=None, expect_meta=None):
-        """The cache `save` wrote, on `device`.  `expect_meta`: a dict every key of which must be in the file's metadata with that value."""
-        blob = torch.load(path, map_location="cpu", weights_only=True)
-        cache = cls(int(blob["meta"]["n_images"]), blob["H"], blob["W"], blob["has_labels"], blob["with_depth"], blob["label_offset"],
-                    blob["fill"], blob["mask_rule"], device=device, meta=blob["meta"])
-        if expect_meta is not None:
-            cache.check_meta(expect_meta)
-        if tuple(blob["data"].shape) != tuple(cache.data.shape) or blob["data"].dtype != torch.uint8:
-            raise ValueError(f"depthg_amd: {path}: the stored table {tuple(blob['data'].shape)} {blob['data'].dtype} is not the "
-                             f"{tuple(cache.data.shape)} uint8 its header describes")
-        cache.data.copy_(blob["data"])
-        cache.filled[:] = blob["filled"].numpy()
-        return cache
+    def _from_header(cls, blob, device):
+        return cls(int(blob["meta"]["n_images"]), blob["H"], blob["W"], blob["has_labels"], blob["with_depth"], blob["label_offset"],
+                   blob["fill"], blob["mask_rule"], device=device, meta=blob["meta"])
+
+    def _table_text(self):
+        return f"{tuple(self.data.shape)} uint8"
