@@ -46,6 +46,10 @@ Public surface (mirrors the reference's Python operator surface for this path):
     sample_cache / SampleCache   the loader transform's output bytes of every image, label and depth map of a split on the device; a batch
                                  and its positives come back as img / label / mask / depth from ONE launch (k_sc_gather), no decoding:
                                  data.build_sample_cache fills it, ContrastiveBatches(sample_cache=...) reads it
+    epoch / DeviceEpoch          the batches of a cached epoch chosen on the device (src/data.py:1073-1080): indices from the epoch's order,
+                                 kNN positives from Philox, ONE launch (ops.epoch_draw, k_epoch_draw), then the two caches' gathers
+    graph_step / GraphedTrainStep  cfg.dg_graph_step: DeviceEpoch.batch + training_step recorded once in a hipGraph and replayed; the
+                                 host bookkeeping (legacy decay, step count) behind every replay, a new recording when it changes a scalar
     train                        fit(model, train_batches, val_batches, cfg, out_dir): the loop of src/train_segmentation.py:551-714 without
                                  Lightning; `python -m depthg_amd.train` is its command line
     ops                          thin ctypes binding of the C ABI in include/depthg_corr.h; ops.corr_forward is the one route to its five
@@ -86,9 +90,13 @@ from .data import build_feature_cache  # noqa: F401
 from . import sample_cache  # noqa: F401
 from .sample_cache import SampleCache  # noqa: F401
 from .data import build_sample_cache  # noqa: F401
+from . import epoch  # noqa: F401
+from .epoch import DeviceEpoch  # noqa: F401
+from . import graph_step  # noqa: F401
+from .graph_step import GraphedTrainStep  # noqa: F401
 
 __all__ = ["ContrastiveCorrelationLoss", "DepthContrastiveCorrelationLoss", "ContrastiveCRFLoss", "crf_loss", "aug_loss", "aug_alignment_loss", "crop_flip_coords", "augment", "AugmentParams", "augment_batch", "draw_augment_params", "rec_loss", "reconstruction_loss", "depth_encoder", "cross_attn", "cross_attention", "multihead_cross_attention", "depth_decay", "training", "metrics", "evaluation", "predict_and_score", "segment", "crf", "dense_crf",
            "batched_crf", "knn", "lhp", "optim", "FusedAdam", "FusedAdamSet", "segmenter", "vit", "featurizer",
            "DinoFeaturizer", "DinoFeaturizerWithDepth", "data", "ContrastiveBatches", "CroppedFolder", "DirectoryFolder",
            "loader_index_tables", "precompute_knns", "feature_cache", "FeatureCache", "build_feature_cache",
-           "sample_cache", "SampleCache", "build_sample_cache"]
+           "sample_cache", "SampleCache", "build_sample_cache", "epoch", "DeviceEpoch", "graph_step", "GraphedTrainStep"]

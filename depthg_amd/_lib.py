@@ -140,6 +140,8 @@ SIGNATURES = {
     # device-resident sample cache
     "dg_samplecache_put": (_I, [vp, i64] + [i32] * 4 + [vp, i32, vp, _SZ, vp, vp, vp, i32, vp]),
     "dg_samplecache_gather": (_I, [vp, i64] + [i32] * 4 + [vp, vp, i32, vp, vp] + [i32] * 3 + [vp] * 5),
+    # the batch draw of a cached step
+    "dg_epoch_draw": (_I, [vp, vp, vp, i32, i32, i64, i32, vp, vp, vp]),
     # measurement aids
     "dg_corr_main_kernel_name": (_STR, [cp]),
     "dg_corr_intra_folded": (_I, [cp]),

@@ -1,5 +1,5 @@
 // C ABI of the gfx950 DepthG library (include/depthg_corr.h), the training data path: the GPU batch augmentation, the batch preparation,
-// the frozen-backbone feature cache, the device-resident sample cache.
+// the frozen-backbone feature cache, the device-resident sample cache, the batch draw of a cached step.
 // Host-side only: argument checks and kernel launches on the caller's stream.
 #include "dg_api.h"
 #include "dg_data_args.h"
@@ -305,5 +305,25 @@ extern "C" int dg_samplecache_gather(const uint8_t* cache, int64_t n_images, int
     A.n = n; A.H = H; A.W = W;
     A.label_offset = label_offset; A.fill = fill; A.mask_rule = mask_rule;
     DG_HIP(dg_launch_samplecache_gather(A, static_cast<hipStream_t>(stream_)));
+    return DG_OK;
+}
+
+// ---- the batch draw of a cached step (dg_epoch.hip)
+extern "C" int dg_epoch_draw(uint64_t* state, const int64_t* order, const int64_t* nns, int32_t B, int32_t num_neighbors, int64_t n_images,
+                             int32_t K, int64_t* ind, int64_t* ind_pos, dg_stream_t stream_) {
+    if (B < 1 || n_images < 1 || K < 1)
+        return fail(DG_ERR_INVALID, "dg_epoch_draw: B=%d n_images=%lld K=%d must be positive", B, (long long)n_images, K);
+    if (num_neighbors < 1 || num_neighbors >= K)
+        return fail(DG_ERR_INVALID, "dg_epoch_draw: num_neighbors=%d outside [1, K - 1] of a table with K=%d columns (column 0 is the image itself)",
+                    num_neighbors, K);
+    if (B > DG_EPOCH_MAX_B) return fail(DG_ERR_UNSUPPORTED, "dg_epoch_draw: B=%d above %d (one block draws the batch)", B, DG_EPOCH_MAX_B);
+    if (n_images > (1ll << 62) / K) return fail(DG_ERR_UNSUPPORTED, "dg_epoch_draw: a table of %lld x %d entries", (long long)n_images, K);
+    if (!state || !order || !nns || !ind || !ind_pos) return fail(DG_ERR_INVALID, "dg_epoch_draw: null pointer");
+    if (((uintptr_t)state | (uintptr_t)order | (uintptr_t)nns | (uintptr_t)ind | (uintptr_t)ind_pos) & 7)
+        return fail(DG_ERR_INVALID, "dg_epoch_draw: state, order, nns, ind and ind_pos must be 8-byte aligned");
+    // (cursor + B <= n_images cannot be asked here: the cursor lives on the device; the kernel holds its read inside `order`)
+    DG_HIP(dg_launch_epoch_draw(reinterpret_cast<unsigned long long*>(state), reinterpret_cast<const long long*>(order),
+                                reinterpret_cast<const long long*>(nns), B, num_neighbors, n_images, K, reinterpret_cast<long long*>(ind),
+                                reinterpret_cast<long long*>(ind_pos), static_cast<hipStream_t>(stream_)));
     return DG_OK;
 }

@@ -1,4 +1,4 @@
-// The training data path (dg_augment, dg_batch, dg_sample_cache, dg_feat_cache .hip; dg_api_data.hip): constants, argument blocks and
+// The training data path (dg_augment, dg_batch, dg_sample_cache, dg_feat_cache, dg_epoch .hip; dg_api_data.hip): constants, argument blocks and
 // launchers, and the device code the loader kernels share - the record decode, the tile prologue, the four-byte gather and the
 // four-pixel writers of k_batch_prep, k_sc_put and k_sc_gather.
 #pragma once
@@ -99,6 +99,12 @@ hipError_t dg_launch_featcache_put(void* cache, int dtype, long long N, long lon
 // idx_b null: n rows, else 2 n
 hipError_t dg_launch_featcache_gather(const void* cache, int dtype, long long N, long long L, const long long* idx_a, const long long* idx_b,
                                       int n, float* out, hipStream_t s);
+
+// ---- the batch draw of a cached step on the device: dataset indices from the epoch's order, kNN positives from Philox, both keyed by
+// device memory (dg_epoch.hip; src/data.py:1073-1080)
+#define DG_EPOCH_MAX_B 1024                  // one block: a batch of at most this many samples
+hipError_t dg_launch_epoch_draw(unsigned long long* state, const long long* order, const long long* nns, int B, int num_neighbors,
+                                long long n_images, int K, long long* ind, long long* ind_pos, hipStream_t s);
 
 // ---- the loader kernels' shared device code.  A lane owns four neighbouring pixels of a row and carries their bytes of a plane as one
 // 32-bit word, pixel k in bits 8 k .. 8 k + 7: what the cache stores, what the gather loads, what the writers take.

@@ -629,6 +629,77 @@ def sample_cache_gather(cache, has_labels, with_depth, idx_a, idx_b=None, label_
     return out
 
 
+EPOCH_DRAW_MAX_B = 1024             # one block of k_epoch_draw draws the batch
+
+
+def _philox_word0(seed, counters):
+    """Word 0 of Philox4x32-10 (dg_philox4 of csrc/dg_device.h) keyed by the 64-bit `seed` at the 128-bit counters (c, 0): numpy
+    uint64 in, numpy uint64 (32-bit values) out.  The host statement of what k_epoch_draw draws."""
+    import numpy as np
+    u, M = np.uint64, np.uint64(0xFFFFFFFF)
+    c = np.asarray(counters, dtype=np.uint64)
+    c0, c1, c2, c3 = c & M, c >> u(32), np.zeros_like(c), np.zeros_like(c)
+    k0, k1 = u(seed & 0xFFFFFFFF), u((seed >> 32) & 0xFFFFFFFF)
+    for _ in range(10):
+        p0, p1 = u(0xD2511F53) * c0, u(0xCD9E8D57) * c2
+        c0, c1, c2, c3 = (p1 >> u(32)) ^ c1 ^ k0, p1 & M, (p0 >> u(32)) ^ c3 ^ k1, p0 & M
+        k0, k1 = (k0 + u(0x9E3779B9)) & M, (k1 + u(0xBB67AE85)) & M
+    return c0
+
+
+def epoch_draw(state, order, nns, B, num_neighbors, ind=None, ind_pos=None):
+    """The next batch of a cached epoch and its kNN positives (src/data.py:1073-1080) from operands that all live on one device, ONE
+    launch (dg_epoch_draw, k_epoch_draw of dg_epoch.hip).  state: int64 {seed, draws, cursor} - the words of new_perm_state, the
+    third used as the cursor: a state of its own, not one super_perms or rand_coords_state also advance; order: int64 (n_images,);
+    nns: int64 (n_images, K), the table knn.load_nns returns.  Slot j: ind[j] = order[cursor + j], ind_pos[j] =
+    nns[ind[j]][1 + u % num_neighbors] with u = word 0 of Philox4x32-10 keyed by the seed at counter draws + j; then cursor and draws
+    advance by B.  Nothing about the draw is an argument of the launch: recorded in a hipGraph it draws anew at every replay.
+    The positives are uniform over columns 1 .. num_neighbors as the reference's are, but they are this generator's stream, NOT
+    torch.randint's.  `ind` / `ind_pos`: int64 (B,) buffers to write instead of new ones; every element is written.  The caller keeps
+    cursor + B <= n_images (the cursor is not read on the host); the position in `order` is held at n_images - 1 all the same.
+    On CPU tensors the same arithmetic runs in numpy: the statement the kernel is tested against."""
+    B, num_neighbors = int(B), int(num_neighbors)
+    dev = state.device
+    if state.dtype != torch.int64 or state.numel() != 3 or not state.is_contiguous():
+        raise ValueError("depthg_amd: epoch_draw: state must be the contiguous int64[3] tensor {seed, draws, cursor}")
+    if order.dtype != torch.int64 or order.dim() != 1 or nns.dtype != torch.int64 or nns.dim() != 2 or nns.shape[0] != order.shape[0] \
+            or not order.is_contiguous() or not nns.is_contiguous() or order.device != dev or nns.device != dev:
+        raise ValueError(f"depthg_amd: epoch_draw wants order as a contiguous int64 (n_images,) tensor and nns as a contiguous int64 "
+                         f"(n_images, K) tensor on {dev}, got {tuple(order.shape)} {order.dtype} on {order.device} and "
+                         f"{tuple(nns.shape)} {nns.dtype} on {nns.device}")
+    n_images, K = int(nns.shape[0]), int(nns.shape[1])
+    if B < 1 or B > EPOCH_DRAW_MAX_B or n_images < 1:
+        raise ValueError(f"depthg_amd: epoch_draw: B={B} outside [1, {EPOCH_DRAW_MAX_B}] (one block draws the batch), or an empty table")
+    if num_neighbors < 1 or num_neighbors >= K:
+        raise ValueError(f"depthg_amd: epoch_draw: num_neighbors={num_neighbors} outside [1, {K - 1}] of a table with {K} columns "
+                         "(column 0 is the image itself)")
+    outs = []
+    for name, t in (("ind", ind), ("ind_pos", ind_pos)):
+        if t is None:
+            t = _empty((B,), torch.int64, dev)
+        elif t.dtype != torch.int64 or tuple(t.shape) != (B,) or t.device != dev or not t.is_contiguous():
+            raise ValueError(f"depthg_amd: epoch_draw: `{name}` must be a contiguous int64 ({B},) tensor on {dev}")
+        outs.append(t)
+    ind, ind_pos = outs
+    if dev.type == "cuda":
+        rc = _lib.load().dg_epoch_draw(_ptr(state), _ptr(order), _ptr(nns), B, num_neighbors, n_images, K, _ptr(ind), _ptr(ind_pos), _stream(dev))
+        _lib.check(rc, "dg_epoch_draw")
+        return ind, ind_pos
+    import numpy as np
+    mask = (1 << 64) - 1
+    seed, draws, cursor = (int(v) & mask for v in state.tolist())
+    j = np.arange(B, dtype=np.uint64)
+    at = np.minimum((np.uint64(cursor) + j) & np.uint64(mask), np.uint64(n_images - 1)).astype(np.int64)
+    image = order.numpy()[at]
+    r = 1 + (_philox_word0(seed, np.uint64(draws) + j) % np.uint64(num_neighbors)).astype(np.int64)
+    ind.copy_(torch.from_numpy(image))
+    ind_pos.copy_(torch.from_numpy(nns.numpy()[np.clip(image, 0, n_images - 1), r]))
+    for k, v in ((1, draws + B), (2, cursor + B)):
+        v &= mask
+        state[k] = v - (1 << 64) if v >= (1 << 63) else v
+    return ind, ind_pos
+
+
 def rec_loss_shapes(code, feats, weight, bias):
     """The reconstruction term's shape rules, on any device: code (B,D,h,w), feats (B,C,h,w) on the same grid, the decoder's weight
     (C,D,1,1) or (C,D) and bias (C,).  Returns (weight as (C,D), (B, D, C, h, w))."""

@@ -566,7 +566,10 @@ def default_segmenter_cfg(**over) -> SimpleNamespace:
         dg_rec_feats_grad=False,
         # build-side, arch "dino": None, or the storage type ("float32", "float16", "bfloat16") of a feature_cache.FeatureCache - a
         # batch that carries `image_feat` / `image_feat_pos` (data.ContrastiveBatches(feature_cache=...)) then skips the frozen backbone
-        dg_feature_cache=None)
+        dg_feature_cache=None,
+        # build-side: the cached step recorded in a hipGraph and replayed, its batches drawn on the device (graph_step.GraphedTrainStep
+        # over epoch.DeviceEpoch; the train command's --graph-step).  training_step itself does not read the key
+        dg_graph_step=False)
     for k, v in over.items():
         setattr(cfg, k, v)
     return cfg

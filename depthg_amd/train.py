@@ -13,7 +13,9 @@ once behind that, keeps its features in a feature_cache.FeatureCache - saved as 
 the file exists and matches - and trains from them: the step skips the backbone (loader_crop_type "center" or None, arch "dino"; validation
 is untouched).  --sample-cache keeps the loader's output bytes of the train and the val split on the device (sample_cache.SampleCache,
 saved as <data-dir>/sample_cache_<meta>.pt and loaded from there when the file matches): every batch is then one gather launch over them
-and an epoch opens no image file; without the flag nothing changes.  The reference reads its val set from the uncropped dataset classes; here both splits come from the same
+and an epoch opens no image file; without the flag nothing changes.  --graph-step (cfg.dg_graph_step; with both caches) draws every batch
+and its positives on the device (epoch.DeviceEpoch) and replays the step from a hipGraph (graph_step.GraphedTrainStep): the short last
+batch of an epoch is dropped and the positives come from the epoch's own random stream.  The reference reads its val set from the uncropped dataset classes; here both splits come from the same
 folder layout (cfg.val_crop_type names the val folder's crop, default: cfg.crop_type).
 
 `fit(model, train_batches, val_batches, cfg, out_dir)`:
@@ -60,14 +62,17 @@ def _plain(v):
     return v.item() if hasattr(v, "item") else v
 
 
-def fit(model, train_batches, val_batches, cfg, out_dir, save_checkpoint=None):
+def fit(model, train_batches, val_batches, cfg, out_dir, save_checkpoint=None, graph_step=None):
     """See the module docstring.  `save_checkpoint(model, path)`: demo.save_checkpoint unless given.  Returns {"steps", "validations",
-    "val_steps" (the step counts validations ran behind), "best", "best_step", "losses"}."""
+    "val_steps" (the step counts validations ran behind), "best", "best_step", "losses"}.
+    `graph_step`: a graph_step.GraphedTrainStep (cfg.dg_graph_step) - the same loop over its step(), an epoch being the
+    steps_per_epoch batches of its DeviceEpoch behind a begin_epoch(); `train_batches` is then not read.  The losses stay on the device
+    until the loop ends (no synchronisation per step)."""
     if save_checkpoint is None:
         from .demo import save_checkpoint
     os.makedirs(out_dir, exist_ok=True)
     max_steps = int(cfg.max_steps)
-    per_epoch = len(train_batches)
+    per_epoch = len(train_batches) if graph_step is None else graph_step.epoch.steps_per_epoch
     if per_epoch < 1:
         raise ValueError("depthg_amd.train: the train pipeline has no batch")
     interval = validation_interval(cfg, per_epoch)
@@ -95,11 +100,21 @@ def fit(model, train_batches, val_batches, cfg, out_dir, save_checkpoint=None):
             state["best"], state["best_step"] = score, state["steps"]
             save_checkpoint(model, os.path.join(out_dir, "best.pt"))
 
+    def epoch_steps():
+        """(batch_idx, (loss, logs)) of one epoch, each step run when it is asked for."""
+        if graph_step is None:
+            for batch_idx, batch in enumerate(train_batches):
+                yield batch_idx, model.training_step(batch, batch_idx)
+        else:
+            graph_step.epoch.begin_epoch()
+            for batch_idx in range(per_epoch):
+                loss, logs = graph_step.step()
+                yield batch_idx, (loss.clone(), logs)            # (a replay's tensors are the recording's own: the next step overwrites them)
+
     while state["steps"] < max_steps:
-        for batch_idx, batch in enumerate(train_batches):
-            loss, logs = model.training_step(batch, batch_idx)
+        for batch_idx, (loss, logs) in epoch_steps():
             state["steps"] += 1
-            state["losses"].append(float(loss))
+            state["losses"].append(float(loss) if graph_step is None else loss)
             if state["steps"] % log_freq == 0:
                 write({"step": state["steps"], **{k: _plain(v) for k, v in logs.items()}})
             last_of_epoch = batch_idx + 1 == per_epoch
@@ -110,6 +125,8 @@ def fit(model, train_batches, val_batches, cfg, out_dir, save_checkpoint=None):
     if not state["val_steps"] or state["val_steps"][-1] != state["steps"]:
         validate()
     save_checkpoint(model, os.path.join(out_dir, "last.pt"))
+    if graph_step is not None and state["losses"]:
+        state["losses"] = torch.stack(state["losses"]).tolist()
     return state
 
 
@@ -247,6 +264,10 @@ def main(argv=None) -> int:
                     help="keep the loader's output bytes of the train and the val split on the device and form every batch from them in one "
                          "launch; built once, saved as sample_cache_<meta>.pt under --data-dir and loaded from there afterwards "
                          "(loader_crop_type 'center' or None)")
+    ap.add_argument("--graph-step", action="store_true",
+                    help="record the cached training step in a hipGraph and replay it, the batches drawn on the device (sets dg_graph_step, and "
+                         "dg_graph_safe and dg_fused_adam unless given); needs --feature-cache and --sample-cache; the short last batch of an "
+                         "epoch is dropped")
     ap.add_argument("overrides", nargs="*", help="cfg keys as key=value")
     args = ap.parse_args(argv)
     overrides = parse_overrides(args.overrides)
@@ -254,6 +275,12 @@ def main(argv=None) -> int:
         overrides["dataset_name"] = args.dataset
     if args.feature_cache is not None:
         overrides["dg_feature_cache"] = args.feature_cache
+    if args.graph_step:
+        if args.feature_cache is None or not args.sample_cache:
+            ap.error("--graph-step replays the CACHED step: give --feature-cache {float32,float16,bfloat16} and --sample-cache as well")
+        overrides["dg_graph_step"] = True
+        overrides.setdefault("dg_graph_safe", True)              # (given as False they are refused by GraphedTrainStep, with the way out)
+        overrides.setdefault("dg_fused_adam", True)
     cfg = build_cfg(overrides)
     if getattr(cfg, "dg_feature_cache", None) and getattr(cfg, "arch", "dino") == "dino_depth":
         raise ValueError("depthg_amd.train: --feature-cache serves cfg.arch = 'dino'; the depth-guided featurizer (arch 'dino_depth') is out of "
@@ -280,7 +307,16 @@ def main(argv=None) -> int:
                                                             getattr(cfg, "dg_feature_cache", None), args.sample_cache)
     model = model_for(n_classes)
     model.train()
-    state = fit(model, train_batches, val_batches, cfg, args.out)
+    graph_step = None
+    if getattr(cfg, "dg_graph_step", False):
+        from .epoch import DeviceEpoch
+        from .graph_step import GraphedTrainStep
+        epoch = DeviceEpoch(train_batches.nns, cfg.batch_size, train_batches.num_neighbors, device, shuffle=True, generator=train_batches.generator)
+        graph_step = GraphedTrainStep(model, epoch, train_batches.sample_cache, train_batches.feature_cache,
+                                      label_dims=train_batches.dataset.label_dims)
+    state = fit(model, train_batches, val_batches, cfg, args.out, graph_step=graph_step)
+    if graph_step is not None:
+        print(f"depthg_amd.train: {graph_step.captures} recording(s) of the step")
     print(f"depthg_amd.train: {state['steps']} step(s), {state['validations']} validation(s), best {monitor_key(cfg)} = {state['best']} "
           f"at step {state['best_step']} -> {args.out}")
     return 0

@@ -1093,6 +1093,33 @@ int dg_samplecache_gather(const uint8_t* cache, int64_t n_images, int32_t has_la
                           const int64_t* idx_a, const int64_t* idx_b, int32_t n, const float* mean, const float* stdv, int32_t label_offset,
                           int32_t fill, int32_t mask_rule, float* img, int64_t* label, void* mask, float* depth, dg_stream_t stream);
 
+/*
+ * The batch draw of a cached training step on the device (dg_epoch.hip, kernel k_epoch_draw).  It replaces, for a batch of B,
+ * src/data.py:1073-1080:
+ *      def __getitem__(self, ind):
+ *          pack = self.dataset[ind]
+ *          if self.pos_images or self.pos_labels:
+ *              ind_pos = self.nns[ind][torch.randint(low=1, high=self.num_neighbors + 1, size=[]).item()]
+ *              pack_pos = self.dataset[ind_pos]
+ * - B host draws with a synchronisation each, and the sampler's index list behind them - by ONE launch whose operands all live on the
+ * device, so that a step recorded in a hipGraph draws its next batch at every replay:
+ *  state   : {seed, draws, cursor}, three 64-bit words on the DEVICE, owned by the caller.  The words are laid out as the generator
+ *            state of dg_super_perms is, but the third is this entry's cursor, not a ticket: give this entry a state of its own.
+ *  order   : int64 (n_images,) on the device, the epoch's visiting order (a permutation of 0..n_images-1)
+ *  nns     : int64 (n_images, K) on the device, the nearest-neighbour table; column 0 is the image itself
+ *  ind, ind_pos : int64 (B,) on the device, every element written, with plain vector stores
+ * Slot j: ind[j] = order[cursor + j]; r = 1 + u % num_neighbors with u = word 0 of Philox4x32-10 (dg_device.h) keyed by `seed` at the
+ * 128-bit counter (draws + j, 0); ind_pos[j] = nns[ind[j]][r].  After every slot has read the state one thread stores cursor + B and
+ * draws + B.  The positives are a uniform draw from columns 1..num_neighbors as the reference's are, but NOT torch.randint's stream.
+ * One block: B <= 1024.  No LDS, no atomics, no workspace, no allocation, no host synchronisation.
+ * Refused before any launch: DG_ERR_INVALID for B, n_images or K < 1, num_neighbors < 1 or >= K, null or misaligned (8 bytes)
+ * pointers; DG_ERR_UNSUPPORTED for B > 1024.  cursor + B <= n_images is the CALLER's invariant (the cursor cannot be read here
+ * without a synchronisation): the kernel holds its position in `order` at n_images - 1 and the table row inside [0, n_images), so a
+ * broken invariant repeats an entry and never reads outside the two buffers.
+ */
+int dg_epoch_draw(uint64_t* state, const int64_t* order, const int64_t* nns, int32_t B, int32_t num_neighbors, int64_t n_images, int32_t K,
+                  int64_t* ind, int64_t* ind_pos, dg_stream_t stream);
+
 /* Measurement aid: name of the kernel the fused correlation launch of this descriptor runs ("k_corr2": the one-wave-per-SIMD
  * form of dg_corr2.hip, "k_corr_main": the general form), decided by the same predicate the launch uses; NULL on a bad desc. */
 const char* dg_corr_main_kernel_name(const dg_corr_desc* desc);
