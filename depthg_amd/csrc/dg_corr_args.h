@@ -75,14 +75,18 @@ __host__ __device__ inline size_t dg_gtile_off(int p, int d, int DP) {
 // read with coalesced 16-byte loads and turned around through a per-wave LDS scratch of DG_XROWS_LDS bytes (granule rows
 // padded by one granule against bank conflicts).
 #define DG_XROWS_LDS (4 * 33 * 16)
+// The two halves of it, for a caller that requests the rows long before it needs them (k_combine_out): the global loads ...
 template <int NDF>
-__device__ __forceinline__ void dg_load_code_rows(const char* Cp, char* T, int lane, _Float16 (&x)[NDF][16]) {
-        const int r = lane & 31, h = lane >> 5;
-    i32x4 raw[NDF][2];
+__device__ __forceinline__ void dg_request_code_rows(const char* Cp, int lane, i32x4 (&raw)[NDF][2]) {
 #pragma unroll
     for (int f = 0; f < NDF; ++f)
 #pragma unroll
         for (int k = 0; k < 2; ++k) raw[f][k] = *reinterpret_cast<const i32x4*>(Cp + f * 2048 + k * 1024 + lane * 16);
+}
+// ... and the turn through the wave's LDS scratch
+template <int NDF>
+__device__ __forceinline__ void dg_turn_code_rows(const i32x4 (&raw)[NDF][2], char* T, int lane, _Float16 (&x)[NDF][16]) {
+    const int r = lane & 31, h = lane >> 5;
 #pragma unroll
     for (int f = 0; f < NDF; ++f) {
 #pragma unroll
@@ -96,6 +100,12 @@ __device__ __forceinline__ void dg_load_code_rows(const char* Cp, char* T, int l
             x[f][i] = *reinterpret_cast<const _Float16*>(T + ((r >> 3) * 33 + q) * 16 + (r & 7) * 2);
         }
     }
+}
+template <int NDF>
+__device__ __forceinline__ void dg_load_code_rows(const char* Cp, char* T, int lane, _Float16 (&x)[NDF][16]) {
+    i32x4 raw[NDF][2];
+    dg_request_code_rows<NDF>(Cp, lane, raw);
+    dg_turn_code_rows<NDF>(raw, T, lane, x);
 }
 
 // job kinds of the fused correlation kernel

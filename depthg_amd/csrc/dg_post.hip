@@ -133,10 +133,19 @@ __global__ __launch_bounds__(64 * NDF) void k_grad_combine(const DgScatterArgs a
 
 // Identity grid (DG_IDENTITY_GRID; positions = pixel indices): stage 1 and the adjoint of sample() in ONE launch.  The block of
 // k_grad_combine - (tile, image, destination), one wave per 32-channel group - also adds the tiles of the images ROUTED here (the
-// negatives whose batch map points at this image: list built per block by ordered ballot compaction, (source, image) order:
-// bit-reproducible) and writes (B,D,h,w) directly: a tile's 32 positions are 32 consecutive pixels, so each channel row of the
-// tile is one 128-byte run (through a per-wave LDS stage, two channel rows per store instruction).  No combined-tile round trip,
-// no second launch.
+// negatives whose batch map points at this image) and writes (B,D,h,w) directly: a tile's 32 positions are 32 consecutive pixels,
+// so each channel row of the tile is one 128-byte run (through a per-wave LDS stage, two channel rows per store instruction).  No
+// combined-tile round trip, no second launch.
+// Order of a block (the sums are in the order raw fp32, raw fp16, norm() backward, final fp32, final fp16, routed - requests are not):
+//   1. the routed sources of `dest` from the kernel arguments (uniform; route pointer, tile base and weight of each to LDS);
+//   2. REQUESTS, none of which waits for another: the batch-map entries of all (routed source, image) pairs, 64 per wave
+//      instruction; 1 / ||c|| of the destination's and of operand 1's positions; the code rows of the norm() backward; the first
+//      batch of raw tiles;
+//   3. the routed list of (dest, n), by EVERY WAVE FOR ITSELF while those loads are in flight: one ballot per 64 pairs in (source,
+//      image) order, offsets from the popcount of the lower lanes - no block barrier, no counter in LDS, no serial thread.  The waves
+//      write identical entries to one array and each reads it behind its own wave barrier; the order is that of the pair index:
+//      bit-reproducible.  A destination without routed sources (d code at the headline) skips it;
+//   4. the sums, batch by batch.  The one block barrier left is that of <x, dx>, which the channel groups share.
 #ifndef COMB_HB_HM
 #define COMB_HB_HM 4          // ... in half mode (6, 8: 176 registers, three instead of four-plus waves per SIMD: 44 us against 27.5)
 #endif
@@ -144,9 +153,11 @@ __global__ __launch_bounds__(64 * NDF) void k_grad_combine(const DgScatterArgs a
 #define COMB_HB 4          // fp16 tiles per batch of k_combine_out (two 16-byte loads each; 8: 176 registers, two waves per SIMD, 48 us against 34)
 #endif
 #define COMB_MAXROUTE 512      // (routed source, image) pairs a destination image can collect at worst: routed sources x B
-// HM (half mode: the call's pair-set tiles are fp16, only the depth term's are fp32): eight fp16 tiles and ONE fp32 tile per batch instead
-// of four and four - the block is a chain of load phases (ablations, experiments/r06.md 18.8: each costs 3-5 us of the launch), and
-// with every raw tile of a destination in one batch and every routed one in another there are four of them instead of seven
+#define COMB_BALLOTS 4         // ballots of 64 pairs whose batch-map entries a wave requests at a time (one register each)
+// HM (half mode: the call's pair-set tiles are fp16, only the depth term's are fp32): four fp16 tiles or ONE fp32 tile per batch instead
+// of four or four - the block is a chain of load phases (ablations, experiments/r06.md 18.8: each costs 3-5 us of the launch), and what
+// helps is registers: four waves per SIMD instead of three.  The batch in flight has one set of registers whichever kind it is, the
+// routed fp32 loop included (half mode: 124 registers; a set per kind: 153 and three waves).
 template <int NDF, bool HM = false>
 __global__ __launch_bounds__(64 * NDF) void k_combine_out(const DgScatterArgs a) {
     const int rt = blockIdx.x, n = blockIdx.y, dest = blockIdx.z;
@@ -157,47 +168,42 @@ __global__ __launch_bounds__(64 * NDF) void k_combine_out(const DgScatterArgs a)
     __shared__ float stage[NDF][32 * 33];
     __shared__ const float* rl_p[COMB_MAXROUTE];
     __shared__ float rl_w[COMB_MAXROUTE];
-    __shared__ int rl_cnt, wcnt[NDF], rsrc[DG_MAX_SCATTER];
+    // the routed sources of `dest`: what a list entry is made of (every wave's lane 0 writes the same values)
+    __shared__ const int64_t* rs_route[DG_MAX_SCATTER];
+    __shared__ const float* rs_buf[DG_MAX_SCATTER];
+    __shared__ float rs_w[DG_MAX_SCATTER];
     DG_LOAD_GS(a, gs)
-    // ---- routed list of (dest, n): every thread tests one (routed source, image) pair per round
     int nr = 0;
-    for (int s = 0; s < a.nsrc; ++s)
-        if (a.src[s].dest == dest && a.src[s].route != nullptr) { if (tid == 0) rsrc[nr] = s; ++nr; }
-    if (tid == 0) rl_cnt = 0;
-    __syncthreads();
-    for (int i0 = 0; i0 < nr * a.B; i0 += 64 * NDF) {
-        const int i = i0 + tid;
-        bool hit = false;
-        int m = 0, s = 0;
-        if (i < nr * a.B) {
-            const int rs = i / a.B;
-            m = i - rs * a.B; s = rsrc[rs];
-            hit = (int)a.src[s].route[m] == n;
+    for (int s = 0; s < a.nsrc; ++s) {
+        const DgScatterSrc& q = a.src[s];
+        if (q.dest == dest && q.route != nullptr) {
+            if (lane == 0) { rs_route[nr] = q.route; rs_buf[nr] = q.buf; rs_w[nr] = dg_src_factor(q) * dg_pick(gs, q.gidx); }
+            ++nr;
         }
-        const unsigned long long bal = __ballot(hit);
-        if (lane == 0) wcnt[d] = __popcll(bal);
-        __syncthreads();
-        int base = rl_cnt;
-        for (int wv = 0; wv < d; ++wv) base += wcnt[wv];
-        if (hit) {
-            const int o = base + __popcll(bal & ((1ull << lane) - 1));
-            const DgScatterSrc& q = a.src[s];
-            if (o < COMB_MAXROUTE) {
-                // (half tiles: the same element index, two bytes per element - the pointer stays a float* and is re-typed at the load)
-                rl_p[o] = q.half ? reinterpret_cast<const float*>(reinterpret_cast<const _Float16*>(q.buf) + (size_t)m * a.Ppad * a.DP) : q.buf + (size_t)m * a.Ppad * a.DP;
-                rl_w[o] = dg_src_factor(q) * dg_pick(gs, q.gidx);
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    // ---- requests.  The batch-map entries: pair i = (routed source i / B, image i % B), lane l of ballot k holds pair i0 + 64 k + l
+    // (-1: no pair, equals no image).  COMB_BALLOTS ballots = 256 pairs at a time; the first set is requested here (the headline's
+    // 160 pairs are one set), a later one inside the list's loop (the launcher admits COMB_MAXROUTE pairs).
+    const int npairs = min(nr * a.B, COMB_MAXROUTE);
+    int rdst[COMB_BALLOTS];
+    auto request_routes = [&](const int i0) __attribute__((always_inline)) {
+#pragma unroll
+        for (int k = 0; k < COMB_BALLOTS; ++k) {
+            rdst[k] = -1;
+            if (i0 + 64 * k < npairs) {
+                const unsigned i = i0 + 64 * k + lane;
+                if (i < (unsigned)npairs) {
+                    const unsigned rs = i / (unsigned)a.B;
+                    // (pointer out of LDS: name its address space - else a FLAT load)
+                    rdst[k] = (int)((const int64_t __attribute__((address_space(1)))*)rs_route[rs])[i - rs * a.B];
+                }
             }
         }
-        __syncthreads();
-        if (tid == 0) {
-            int c = rl_cnt;
-            for (int wv = 0; wv < NDF; ++wv) c += wcnt[wv];
-            rl_cnt = min(c, COMB_MAXROUTE);
-        }
-        __syncthreads();
-    }
-    const int cnt = rl_cnt;
-    // ---- the direct sources, as k_grad_combine
+    };
+    request_routes(0);
     const bool ok = 32 * d + r < a.D;
     const size_t in_img = (size_t)rt * (32 * DP) + lane * 4 + (ok ? d * 1024 : 0);
     const size_t tile_off = (size_t)n * a.Ppad * DP + in_img;
@@ -205,83 +211,125 @@ __global__ __launch_bounds__(64 * NDF) void k_combine_out(const DgScatterArgs a)
 #pragma unroll
     for (int i = 0; i < 16; ++i) v[i] = 0.f;
     // fp16 tiles (DgScatterSrc.half): [2][64][8] per channel group - the lane's elements 8s .. 8s+7 in one 16-byte piece; final ones are
-    // projected but not yet divided by ||c||: 1 / ||c|| of the destination's own positions, loaded once
+    // projected but not yet divided by ||c||: 1 / ||c|| of the destination's own positions, loaded once (position rt * 32 + r on lane
+    // r: ONE register while the raw batches are summed; handed round to the accumulator order behind the norm() backward)
     const size_t in_img_h = (size_t)rt * (32 * DP) + lane * 8 + (ok ? d * 1024 : 0);
     constexpr int HB = HM ? COMB_HB_HM : COMB_HB, FB = HM ? 1 : 4;
+    const float invd_r = (a.xinv_dest[dest] && rt * 32 + r < a.P) ? a.xinv_dest[dest][(size_t)n * a.Ppad + rt * 32 + r] : 0.f;
     float invd[16];
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-        const int rr = rt * 32 + (i & 3) + 8 * (i >> 2) + 4 * h;
-        invd[i] = (a.xinv_dest[dest] && rr < a.P) ? a.xinv_dest[dest][(size_t)n * a.Ppad + rr] : 0.f;
-    }
     const _Float16 __attribute__((address_space(1)))* const hdummy = reinterpret_cast<const _Float16 __attribute__((address_space(1)))*>(reinterpret_cast<uintptr_t>(a.xinv));
-    // up to eight half tiles at a time (HB: sixteen 16-byte loads in flight, what four fp32 tiles are), every load of the batch in flight before the first is used (one at a time the launch was
-    // bound by the latency of its loads: the fp32 form's 28 us came back as 24 instead of 17)
-    auto add_half4 = [&](const _Float16 __attribute__((address_space(1)))* const (&hb)[HB], const float (&sc)[HB], const bool raw) __attribute__((always_inline)) {
-        f16x8 t0[HB], t1[HB];
+    // A batch is REQUESTED (every load of it in flight before the first is used: one tile at a time the launch was bound by the latency of
+    // its loads, the fp32 form's 28 us came back as 24 instead of 17) and SUMMED in two steps, so that a block's first batch can be under
+    // way while its routed list is built.  Up to HB half tiles (two 16-byte loads each) or FB fp32 tiles (four) at a time.
+    // One set of registers for the batch in flight, of either kind (16-byte pieces: two per half tile, four per fp32 tile).
+    constexpr int TB = 4 * FB > 2 * HB ? 4 * FB : 2 * HB;
+    i32x4 tb[TB];
+    float sch[HB];
+    auto request_half = [&](const _Float16 __attribute__((address_space(1)))* const (&hb)[HB]) __attribute__((always_inline)) {
 #pragma unroll
         for (int u = 0; u < HB; ++u) {
-            t0[u] = *reinterpret_cast<const f16x8 __attribute__((address_space(1)))*>(hb[u]);
-            t1[u] = *reinterpret_cast<const f16x8 __attribute__((address_space(1)))*>(hb[u] + ((ok && hb[u] != hdummy) ? 512 : 0));
+            tb[2 * u] = *reinterpret_cast<const i32x4 __attribute__((address_space(1)))*>(hb[u]);
+            tb[2 * u + 1] = *reinterpret_cast<const i32x4 __attribute__((address_space(1)))*>(hb[u] + ((ok && hb[u] != hdummy) ? 512 : 0));
         }
+    };
+    auto sum_half = [&](const bool raw) __attribute__((always_inline)) {
 #pragma unroll
         for (int u = 0; u < HB; ++u) {
-            const bool use = ok && sc[u] != 0.f;
+            const bool use = ok && sch[u] != 0.f;
+            const f16x8 t0 = __builtin_bit_cast(f16x8, tb[2 * u]), t1 = __builtin_bit_cast(f16x8, tb[2 * u + 1]);
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
-                v[e] = fmaf(raw ? sc[u] : sc[u] * invd[e], use ? (float)t0[u][e] : 0.f, v[e]);
-                v[8 + e] = fmaf(raw ? sc[u] : sc[u] * invd[8 + e], use ? (float)t1[u][e] : 0.f, v[8 + e]);
+                v[e] = fmaf(raw ? sch[u] : sch[u] * invd[e], use ? (float)t0[e] : 0.f, v[e]);
+                v[8 + e] = fmaf(raw ? sch[u] : sch[u] * invd[8 + e], use ? (float)t1[e] : 0.f, v[8 + e]);
             }
         }
     };
-    auto add_sources_half = [&](const int8_t* list, const int nsrc_, const bool raw) __attribute__((always_inline)) {
-        for (int k0 = 0; k0 < nsrc_; k0 += HB) {
-            const _Float16 __attribute__((address_space(1)))* hb[HB];
-            float sc[HB];
+    auto request_sources_half = [&](const int8_t* list, const int k0, const int nsrc_) __attribute__((always_inline)) {
+        const _Float16 __attribute__((address_space(1)))* hb[HB];
 #pragma unroll
-            for (int u = 0; u < HB; ++u) {
-                const bool live = k0 + u < nsrc_;
-                const DgScatterSrc& q = a.src[(int)list[live ? k0 + u : k0]];
-                sc[u] = live ? dg_src_factor(q) * dg_pick(gs, q.gidx) : 0.f;
-                // (the address does not wait for the weight - the upstream gradients are a load of their own: a tile whose weight turns
-                //  out zero is fetched and dropped by the select in add_half4, never multiplied: it may be unwritten)
-                hb[u] = live ? reinterpret_cast<const _Float16 __attribute__((address_space(1)))*>(reinterpret_cast<uintptr_t>(q.buf)) + (size_t)n * a.Ppad * DP + in_img_h
-                             : hdummy;
-            }
-            add_half4(hb, sc, raw);
+        for (int u = 0; u < HB; ++u) {
+            const bool live = k0 + u < nsrc_;
+            const DgScatterSrc& q = a.src[(int)list[live ? k0 + u : k0]];
+            sch[u] = live ? dg_src_factor(q) * dg_pick(gs, q.gidx) : 0.f;
+            // (the address does not wait for the weight - the upstream gradients are a load of their own: a tile whose weight turns
+            //  out zero is fetched and dropped by the select in sum_half, never multiplied: it may be unwritten)
+            hb[u] = live ? reinterpret_cast<const _Float16 __attribute__((address_space(1)))*>(reinterpret_cast<uintptr_t>(q.buf)) + (size_t)n * a.Ppad * DP + in_img_h
+                         : hdummy;
+        }
+        request_half(hb);
+    };
+    float scf[FB];
+    auto request_sources = [&](const int8_t* list, const int k0, const int nsrc_) __attribute__((always_inline)) {
+#pragma unroll
+        for (int u = 0; u < FB; ++u) {
+            const bool live = k0 + u < nsrc_;
+            const DgScatterSrc& q = a.src[(int)list[live ? k0 + u : k0]];
+            scf[u] = live ? dg_src_factor(q) * dg_pick(gs, q.gidx) : 0.f;
+            const float* base = q.buf + tile_off;
+#pragma unroll
+            for (int g = 0; g < 4; ++g) tb[4 * u + g] = *reinterpret_cast<const i32x4*>(base + (ok ? g * 256 : 0));
         }
     };
-    auto add_sources = [&](const int8_t* list, const int nsrc_) __attribute__((always_inline)) {
-
-        for (int k0 = 0; k0 < nsrc_; k0 += FB) {
-            f32x4 t[FB][4];
-            float sc[FB];
+    auto sum_sources = [&](const int k0, const int nsrc_) __attribute__((always_inline)) {
 #pragma unroll
-            for (int u = 0; u < FB; ++u) {
-                const bool live = k0 + u < nsrc_;
-                const DgScatterSrc& q = a.src[(int)list[live ? k0 + u : k0]];
-                sc[u] = live ? dg_src_factor(q) * dg_pick(gs, q.gidx) : 0.f;
-                const float* base = q.buf + tile_off;
+        for (int u = 0; u < FB; ++u) {
+            const bool use = ok && k0 + u < nsrc_;
 #pragma unroll
-                for (int g = 0; g < 4; ++g) t[u][g] = *reinterpret_cast<const f32x4*>(base + (ok ? g * 256 : 0));
-            }
+            for (int g = 0; g < 4; ++g) {
+                const f32x4 t = __builtin_bit_cast(f32x4, tb[4 * u + g]);
 #pragma unroll
-            for (int u = 0; u < FB; ++u) {
-                const bool use = ok && k0 + u < nsrc_;
-#pragma unroll
-                for (int g = 0; g < 4; ++g)
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) v[4 * g + e] = fmaf(sc[u], use ? t[u][g][e] : 0.f, v[4 * g + e]);
+                for (int e = 0; e < 4; ++e) v[4 * g + e] = fmaf(scf[u], use ? t[e] : 0.f, v[4 * g + e]);
             }
         }
     };
-    const int nraw = a.ncraw[dest] + a.ncrawh[dest];
-    add_sources(a.craw[dest], a.ncraw[dest]);
-    add_sources_half(a.crawh[dest], a.ncrawh[dest], true);
+    // ... the rest of the requests: 1 / ||c|| of operand 1 (position rt * 32 + r on lane r: one register until the norm() backward
+    // hands it round), the code rows, and the destination's first raw batch
+    const int nrawf = a.ncraw[dest], nrawh = a.ncrawh[dest], nraw = nrawf + nrawh;
+    float xinv_r = 0.f;
+    i32x4 xraw[1][2];
     if (nraw > 0) {
-        const char* xb = a.xop + ((size_t)n * (a.Ppad >> 5) + rt) * a.blob_bytes + a.blob_off_c + d * 2048;
+        if (rt * 32 + r < a.P) xinv_r = a.xinv[(size_t)n * a.Ppad + rt * 32 + r];
+        dg_request_code_rows<1>(a.xop + ((size_t)n * (a.Ppad >> 5) + rt) * a.blob_bytes + a.blob_off_c + d * 2048, lane, xraw);
+    }
+    if (nrawf > 0) request_sources(a.craw[dest], 0, nrawf);
+    else if (nrawh > 0) request_sources_half(a.crawh[dest], 0, nrawh);
+    // ---- routed list of (dest, n), this wave's own: entry order = pair order, (routed source, image)
+    int cnt = 0;
+    for (int i0 = 0; i0 < npairs; i0 += 64 * COMB_BALLOTS) {
+        if (i0 > 0) request_routes(i0);
+#pragma unroll
+        for (int k = 0; k < COMB_BALLOTS; ++k) {
+            if (i0 + 64 * k < npairs) {
+                const bool hit = rdst[k] == n;
+                const unsigned long long bal = __ballot(hit);
+                const int o = cnt + __popcll(bal & ((1ull << lane) - 1));
+                if (hit && o < COMB_MAXROUTE) {
+                    const unsigned i = i0 + 64 * k + lane, rs = i / (unsigned)a.B;
+                    const size_t img = (size_t)(i - rs * a.B) * a.Ppad * a.DP;
+                    // (half tiles: the same element index, two bytes per element - the pointer stays a float* and is re-typed at the load)
+                    rl_p[o] = a.routed_half ? reinterpret_cast<const float*>(reinterpret_cast<const _Float16*>(rs_buf[rs]) + img) : rs_buf[rs] + img;
+                    rl_w[o] = rs_w[rs];
+                }
+                cnt += __popcll(bal);
+            }
+        }
+    }
+    cnt = min(cnt, COMB_MAXROUTE);
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    // ---- the direct sources, as k_grad_combine
+    for (int k0 = 0; k0 < nrawf; k0 += FB) {
+        if (k0 > 0) request_sources(a.craw[dest], k0, nrawf);
+        sum_sources(k0, nrawf);
+    }
+    for (int k0 = 0; k0 < nrawh; k0 += HB) {
+        if (k0 > 0 || nrawf > 0) request_sources_half(a.crawh[dest], k0, nrawh);
+        sum_half(true);
+    }
+    if (nraw > 0) {
         _Float16 x[1][16];
-        dg_load_code_rows<1>(xb, xs[d], lane, x);
+        dg_turn_code_rows<1>(xraw, xs[d], lane, x);
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
             const float t = half_sum((float)x[0][i] * v[i]);
@@ -293,44 +341,57 @@ __global__ __launch_bounds__(64 * NDF) void k_combine_out(const DgScatterArgs a)
             float t = part[0][h * 16 + i];
 #pragma unroll
             for (int f = 1; f < NDF; ++f) t += part[f][h * 16 + i];
-            const int rr = rt * 32 + (i & 3) + 8 * (i >> 2) + 4 * h;
-            const float inv = rr < a.P ? a.xinv[(size_t)n * a.Ppad + rr] : 0.f;
+            const float inv = __shfl(xinv_r, (i & 3) + 8 * (i >> 2) + 4 * h);
             v[i] = (v[i] - (float)x[0][i] * t) * inv;
         }
     }
-    add_sources(a.cfin[dest], a.ncfin[dest]);
-    add_sources_half(a.cfinh[dest], a.ncfinh[dest], false);
+#pragma unroll
+    for (int i = 0; i < 16; ++i) invd[i] = __shfl(invd_r, (i & 3) + 8 * (i >> 2) + 4 * h);
+    for (int k0 = 0; k0 < a.ncfin[dest]; k0 += FB) {
+        request_sources(a.cfin[dest], k0, a.ncfin[dest]);
+        sum_sources(k0, a.ncfin[dest]);
+    }
+    for (int k0 = 0; k0 < a.ncfinh[dest]; k0 += HB) {
+        request_sources_half(a.cfinh[dest], k0, a.ncfinh[dest]);
+        sum_half(false);
+    }
     // ---- the routed images' tiles (k_gs output: final), four at a time
     if (a.routed_half) {
         for (int e0 = 0; e0 < cnt; e0 += HB) {
             const _Float16 __attribute__((address_space(1)))* hb[HB];
-            float sc[HB];
 #pragma unroll
             for (int k = 0; k < HB; ++k) {
                 const int e = min(e0 + k, cnt - 1);
-                sc[k] = e0 + k < cnt ? rl_w[e] : 0.f;
-                hb[k] = sc[k] != 0.f ? reinterpret_cast<const _Float16 __attribute__((address_space(1)))*>(reinterpret_cast<uintptr_t>(rl_p[e])) + in_img_h : hdummy;
+                sch[k] = e0 + k < cnt ? rl_w[e] : 0.f;
+                hb[k] = sch[k] != 0.f ? reinterpret_cast<const _Float16 __attribute__((address_space(1)))*>(reinterpret_cast<uintptr_t>(rl_p[e])) + in_img_h : hdummy;
             }
-            add_half4(hb, sc, false);
+            request_half(hb);
+            sum_half(false);
         }
-    } else
-    for (int e0 = 0; e0 < cnt; e0 += 4) {
-        f32x4 u4[4][4];
-        float sc[4];
+    } else {
+        // fp32 routed tiles, as many at a time as the batch registers hold (half mode: two - a batch of four here, 64 registers of its
+        // own, was what set the half-mode kernel's register count).  The list is walked in fours whatever the batch: the entries behind
+        // its end are sums with weight zero, and their number stays what it was.
+        constexpr int RB = TB / 4;
+        for (int e0 = 0; e0 < ((cnt + 3) & ~3); e0 += RB) {
+            float sc[RB];
 #pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const int e = min(e0 + k, cnt - 1);
-            sc[k] = e0 + k < cnt ? rl_w[e] : 0.f;
-            const gfloat_p sb = (gfloat_p)rl_p[e] + in_img;       // (pointer out of LDS: name its address space - else FLAT loads)
+            for (int k = 0; k < RB; ++k) {
+                const int e = min(e0 + k, cnt - 1);
+                sc[k] = e0 + k < cnt ? rl_w[e] : 0.f;
+                const gfloat_p sb = (gfloat_p)rl_p[e] + in_img;       // (pointer out of LDS: name its address space - else FLAT loads)
 #pragma unroll
-            for (int g = 0; g < 4; ++g) u4[k][g] = *(const f32x4 __attribute__((address_space(1)))*)(sb + (ok ? g * 256 : 0));
+                for (int g = 0; g < 4; ++g) tb[4 * k + g] = *(const i32x4 __attribute__((address_space(1)))*)(sb + (ok ? g * 256 : 0));
+            }
+#pragma unroll
+            for (int k = 0; k < RB; ++k)
+#pragma unroll
+                for (int g = 0; g < 4; ++g) {
+                    const f32x4 t = __builtin_bit_cast(f32x4, tb[4 * k + g]);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) v[4 * g + e] = fmaf(sc[k], ok ? t[e] : 0.f, v[4 * g + e]);
+                }
         }
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-#pragma unroll
-            for (int g = 0; g < 4; ++g)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[4 * g + e] = fmaf(sc[k], ok ? u4[k][g][e] : 0.f, v[4 * g + e]);
     }
     // ---- out[dest][(n, channel, pixel)]: the wave's [32 channels][32 positions] tile through LDS, rows of 128 contiguous bytes
     float* st = stage[d];
