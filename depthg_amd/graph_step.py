@@ -26,6 +26,7 @@ import torch
 
 from .depth_decay import legacy_decay_step
 from .optim import FusedAdam
+from .training import histogram_step, reset_probe_step
 
 # The cfg fields a recorded step holds as launch arguments, shapes or branches: a change of any of them drops the recording.
 CAPTURE_KEY = (
@@ -114,14 +115,10 @@ class GraphedTrainStep:
         return tuple(getattr(c, k, None) for c in self._cfgs() for k in CAPTURE_KEY) + (bool(self.model.training), bool(self.model.net.training))
 
     def _forced_eager(self, global_step):
-        cfg = self.model.cfg
-        hist_freq = getattr(cfg, "hist_freq", None)
-        hist = getattr(cfg, "correspondence_weight", 0) > 0 and hist_freq is not None and global_step % hist_freq == 0 and global_step > 0
-        return hist or self._reset_step(global_step)
+        return histogram_step(self.model.cfg, global_step) or self._reset_step(global_step)
 
     def _reset_step(self, global_step):
-        reset = getattr(self.model.cfg, "reset_probe_steps", None)
-        return reset is not None and global_step == reset
+        return reset_probe_step(self.model.cfg, global_step)
 
     # ---- the step itself, as both routes run it
     def _run(self):

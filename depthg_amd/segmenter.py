@@ -2,54 +2,26 @@
 (SURVEY.md section 8 rows A14, N1 and the step-level caller around A13).
 
 Mirrors, with the reference's names, parameter layout and arithmetic:
-    StandInFeaturizer       a featurizer with DinoFeaturizer's output contract (src/modules.py:90-137: train -> (feats, code,
-                            attn), eval -> (feats, code); feats get a third Dropout2d mask when cfg.dropout).  The frozen DINO
-                            ViT itself is out of scope (north_star: "the Python host calls PyTorch-ROCm for the ViT forward") and
-                            its weights cannot be fetched here, so the backbone is a frozen random patch embedding of the same
-                            geometry (patch size, n_feats, no gradient) - any module returning (B, n_feats, H/p, W/p) can be
-                            passed instead.  Its head (`cluster1` / `cluster2`, the three Dropout2d draws) is ONE fused HIP launch
-                            (depthg_amd/head.py run_head -> dg_head_forward / dg_head_backward); the head's registration, forward
-                            and forward_pair are featurizer.FrozenBackboneFeaturizer's, shared with DinoFeaturizer.
-    UnsupervisedSegmenter   LitUnsupervisedSegmenter without Lightning (src/train_segmentation.py:71-158, 169-462): attributes
-                            net / train_cluster_probe / cluster_probe / linear_probe / contrastive_corr_loss_fn / cfg /
-                            n_classes / use_depth, forward(x) = net(x)[1], configure_optimizers() -> three Adams,
-                            training_step(batch, batch_idx) with manual optimisation: two featurizer passes, the HIP correlation
-                            loss (and the second LHP call when cfg.lhp), the weighted total, the live legacy decay of the cfg
-                            scalars, linear-probe cross entropy and cluster-probe loss on the detached code, backward, three steps;
-                            validation_step / on_validation_epoch_end (:471-535) and evaluate_batch (src/eval_segmentation.py:146-170,
-                            run_crf for the dense CRF) score the probes through evaluation.predict_and_score; segment(img) is the
-                            label-free route of src/demo_segmentation.py:59-78 through evaluation.segment (byte label maps and
-                            painted images of every image; depthg_amd/demo.py is its command line).
-ProjectionHead / ClusterLookup (src/modules.py:647-675) / probe_cross_entropy live in depthg_amd/head.py and are re-exported
-here.  The head, the probes' losses and everything the correlation loss does run in the HIP library; what stays torch is the
-frozen backbone, the 27 x dim linear-probe convolution and - unless cfg.dg_fused_adam - the three Adams.  With cfg.dg_fused_adam
-(build-side key, off by default) configure_optimizers() returns three optim.FusedAdam and the step ends with ONE HIP launch over
-all nine tensors (optim.FusedAdamSet) instead of three torch.optim.Adam steps.  Under data parallelism `all_reduced_parameters()`
-is what `parallel.GradBucket` all-reduces.  With cfg.dg_dino_backbone (build-side key, off by default) the featurizer is
-featurizer.DinoFeaturizer - the real DINO ViT of depthg_amd/vit.py - instead of StandInFeaturizer; cfg.dg_fused_attention then routes
-its attention through the HIP kernel of dg_attn.hip and cfg.dg_fused_linear its blocks' linear layers (with their LayerNorm, GELU and
-residual adds) through the bf16 MFMA kernel of dg_linear.hip.  On the reference's histogram steps (cfg.hist_freq, src/train_segmentation.py:229-231,
-298-301) training_step puts the histograms of the three un-reduced cd tensors into its logs as `hist/intra_cd`, `hist/inter_cd`, `hist/neg_cd`
-(int64 counts on the device, cfg.dg_hist_bins bins, default 64) - from ContrastiveCorrelationLoss.cd_histograms(), without the tensors.
-With cfg.crf_weight > 0 the step adds the contrastive CRF term (src/train_segmentation.py:413-419) through crf_loss.ContrastiveCRFLoss.mean_loss
-- the fused HIP kernels of dg_crf_loss.hip - and logs it as `loss/crf`.  With cfg.aug_alignment_weight > 0 it adds the
-augmentation-alignment term (src/train_segmentation.py:400-411) on batch["img_aug"] / batch["coord_aug"] through
-aug_loss.aug_alignment_loss - a third featurizer pass and the fused HIP kernels of dg_aug.hip - and logs it as `loss/aug_alignment`.
-With cfg.dg_gpu_augment as well (build-side key, off by default) a batch that lacks `img_aug` gets both tensors from batch["img"] through
-augment.draw_augment_params / augment_batch - the fused HIP kernels of dg_augment.hip; "unit" runs the colour ops on de-normalised values.
-Capturing such a step into a graph is out of scope (the parameters are drawn on the host).
-With cfg.rec_weight > 0 the segmenter has a `decoder` (src/train_segmentation.py:115), net_optim steps it (:540-541) and the step adds
-the reconstruction term (:391-398) through rec_loss.reconstruction_loss - the fused HIP kernels of dg_rec_loss.hip - logged as `loss/rec`.
-With cfg.arch == "dino_depth" (:104-106) the featurizer is the depth-guided one - featurizer.DinoFeaturizerWithDepth over the ViT under
-cfg.dg_dino_backbone, StandInFeaturizerWithDepth otherwise - cfg.guidance chooses how the depth encoder's map meets the features, use_depth
-is forced on, the step feeds (img, depth) / (img_pos, depth_pos) one pass at a time and net_optim steps the depth modules the guidance
-trains with the head (the head's d image_feat launch, dg_head_backward_input, carries the gradient to them).  There cfg.rec_weight > 0
-under guidance "sum" / "cross_attn" needs cfg.dg_rec_feats_grad: the reconstruction term then reads the first pass's attached feats, its
-backward writes d feats (dg_rec_feats_backward) and the head adds it into d image_feat (dg_head_backward_input's grad_feats_out).
-With cfg.dg_feature_cache (build-side key, None by default; arch "dino") a batch that carries `image_feat` / `image_feat_pos` - the frozen
-backbone's outputs, kept by feature_cache.FeatureCache and gathered per batch by data.ContrastiveBatches - starts behind the backbone
-(FrozenBackboneFeaturizer.forward_pair_features / forward_features): the two backbone passes of :194-212 are not run, the head's draws and
-launches are unchanged.
+    StandInFeaturizer       DinoFeaturizer's output contract (src/modules.py:90-137: train -> (feats, code, attn), eval -> (feats,
+                            code); a third Dropout2d mask on feats when cfg.dropout) over a frozen random patch embedding of the
+                            ViT's geometry - the DINO weights cannot be fetched here; any module returning (B, n_feats, H/p, W/p)
+                            can be passed instead.  The head (`cluster1` / `cluster2`, the three Dropout2d draws) is ONE fused HIP
+                            launch (head.run_head); its registration, forward and forward_pair are
+                            featurizer.FrozenBackboneFeaturizer's, shared with DinoFeaturizer (cfg.dg_dino_backbone: the real ViT).
+    UnsupervisedSegmenter   LitUnsupervisedSegmenter without Lightning (src/train_segmentation.py:71-158, 169-462): the same attributes,
+                            forward(x) = net(x)[1], configure_optimizers() -> three Adams, training_step (below), validation_step /
+                            on_validation_epoch_end (:471-535), evaluate_batch (src/eval_segmentation.py:146-170) and segment(img),
+                            the label-free route of src/demo_segmentation.py:59-78 (depthg_amd/demo.py is its command line).
+                            cfg.arch == "dino_depth" (:104-106): the depth-guided featurizer, use_depth forced on.
+ProjectionHead / ClusterLookup (src/modules.py:647-675) / probe_cross_entropy live in depthg_amd/head.py and are re-exported here.
+
+training_step is a driver over stages whose switches are all decided once, in front of the step, by training.step_plan (the featurizer
+route - pair, depth or single -, whether it starts from cached features, the terms that run, this step number's histogram and
+probe-reset decisions).  The stages, in the reference's order, which is the order of every launch and every random draw: zero_grad;
+_refuse_or_fill;  _anchor_pass (both passes on the pair route);  LHP on the anchor code;  _positive_pass (depth and single routes);  LHP
+on the positive code;  _correspondence_term (`hist/*` logs on a cfg.hist_freq step);  depth_decay.legacy_decay_step;  _auxiliary_terms
+(`loss/rec`, `loss/aug_alignment`, `loss/crf`);  _probe_terms;  _backward_and_step.  The passes hand their tensors on in one record.
+graph_step.GraphedTrainStep asks training.histogram_step / reset_probe_step, as the plan does, which steps it must run eagerly.
 """
 from types import SimpleNamespace
 from typing import Dict, Optional
@@ -70,7 +42,7 @@ from .metrics import UnsupervisedMetrics
 from .optim import FusedAdam, FusedAdamSet
 from .parallel import GradBucket
 from .rec_loss import reconstruction_loss
-from .training import correspondence_total
+from .training import correspondence_total, step_plan
 
 
 class StandInFeaturizer(FrozenBackboneFeaturizer):
@@ -172,10 +144,7 @@ class UnsupervisedSegmenter(nn.Module):
         self.global_step = 0
         self._optims = None
         self.validation_step_outputs = []                                             # :149-157
-        self.max_cluster_accuracy = 0.0
-        self.max_cluster_miou = 0.0
-        self.max_linear_accuracy = 0.0
-        self.max_linear_miou = 0.0
+        self.max_cluster_accuracy = self.max_cluster_miou = self.max_linear_accuracy = self.max_linear_miou = 0.0
         # :115 - the reconstruction term's decoder.  The reference always builds it and steps it only under rec_weight (:540-541);
         # here it exists only then, and is built LAST: with rec_weight = 0 no module, no state_dict key and no random draw is
         # added, and with it on every other module still takes the draws it takes without it - no existing initial value moves.
@@ -219,14 +188,10 @@ class UnsupervisedSegmenter(nn.Module):
         # :540-541), its decoder's (the CRF and augmentation-alignment terms have no parameters of their own) - the LHP projection
         # head is NOT among them, so it keeps its initial weights there and here
         main_params = list(self.net.parameters()) + self._decoder_parameters()
-        if getattr(self.cfg, "dg_fused_adam", False):          # the same three, stepped by one HIP launch (optim.FusedAdamSet)
-            return (FusedAdam([p for p in main_params if p.requires_grad], lr=self.cfg.lr),
-                    FusedAdam(list(self.linear_probe.parameters()), lr=5e-3),
-                    FusedAdam(list(self.cluster_probe.parameters()), lr=5e-3))
-        net_optim = torch.optim.Adam([p for p in main_params if p.requires_grad], lr=self.cfg.lr)
-        linear_probe_optim = torch.optim.Adam(list(self.linear_probe.parameters()), lr=5e-3)
-        cluster_probe_optim = torch.optim.Adam(list(self.cluster_probe.parameters()), lr=5e-3)
-        return net_optim, linear_probe_optim, cluster_probe_optim
+        # (cfg.dg_fused_adam: the same three as optim.FusedAdam, stepped by one HIP launch - optim.FusedAdamSet)
+        adam = FusedAdam if getattr(self.cfg, "dg_fused_adam", False) else torch.optim.Adam
+        return (adam([p for p in main_params if p.requires_grad], lr=self.cfg.lr),                    # net, linear probe, cluster probe
+                adam(list(self.linear_probe.parameters()), lr=5e-3), adam(list(self.cluster_probe.parameters()), lr=5e-3))
 
     def optimizers(self):
         if self._optims is None:
@@ -280,148 +245,157 @@ class UnsupervisedSegmenter(nn.Module):
             list(self.cluster_probe.parameters())
 
     def training_step(self, batch: Dict[str, torch.Tensor], batch_idx: int = 0, grad_sync=None):
-        """One optimisation step (src/train_segmentation.py:169-462).  `grad_sync`: callable run between backward and the
-        optimiser steps (data parallelism: GradBucket pack / all-reduce / unpack); returns (loss, logs).
-        With cfg.dg_fused_adam `grad_sync` may hand the averaged gradients straight to the optimiser step instead of unpacking
-        them into p.grad: it returns the `GradBucket` (its `grad_views()` are read, matched to the parameters by identity), or a
-        `list` of tensors / None aligned with `all_reduced_parameters()`, e.g.
+        """One optimisation step (src/train_segmentation.py:169-462); returns (loss, logs).  `grad_sync`: callable run between backward and
+        the optimiser steps (data parallelism: GradBucket pack / all-reduce / unpack).  With cfg.dg_fused_adam it may hand the averaged
+        gradients straight to the optimiser step instead of unpacking them into p.grad: it returns the `GradBucket` (its `grad_views()` are
+        read, matched to the parameters by identity), or a `list` of tensors / None aligned with `all_reduced_parameters()`, e.g.
             grad_sync = lambda: [bucket.pack(), bucket.allreduce_mean_(), bucket][-1]
         Any other return value - None, or the tuple a `lambda: (a(), b())` chain yields - keeps today's meaning: p.grad is read."""
-        cfg = self.cfg
-        net_optim, linear_probe_optim, cluster_probe_optim = self.optimizers()
-        net_optim.zero_grad(); linear_probe_optim.zero_grad(); cluster_probe_optim.zero_grad()        # :174-176
-        img, img_pos, label = batch["img"], batch["img_pos"], batch["label"]
-        depth = batch["depth"] if self.use_depth else None
-        depth_pos = batch["depth_pos"] if self.use_depth else None
-        if self.depth_arch:                                      # (cfg may have changed since construction)
-            self._refuse_depth_arch_combinations(cfg)
-        if self.depth_only_intra:
-            self._refuse_depth_only_intra_combinations(cfg)
-        if getattr(cfg, "aug_alignment_weight", 0) > 0:         # (asked before anything is launched)
-            # cfg.dg_gpu_augment (build-side key, absent or False by default): a batch without the augmented view gets it here -
-            # parameters drawn from torch's global CPU generator, both tensors from batch["img"] at its own size in two HIP launches
-            # (augment.augment_batch).  "unit": img is ImageNet-normalised and the colour ops work on [0, 1] values; any other true
-            # value: the ops act on the tensor as given, as the reference's do.  A batch that carries the keys wins, untouched.
-            # (The draw is host work: capturing such a step into a graph is out of scope.)
-            gpu_augment = getattr(cfg, "dg_gpu_augment", False)
-            if gpu_augment and "img_aug" not in batch:
-                unit = isinstance(gpu_augment, str) and gpu_augment == "unit"
-                params = draw_augment_params(img.shape[0], img.shape[2], img.shape[3])
-                img_aug, coord_aug = augment_batch(img, params, mean=IMAGENET_MEAN if unit else None, std=IMAGENET_STD if unit else None)
-                batch = {**batch, "img_aug": img_aug, "coord_aug": coord_aug}
-            for key in ("img_aug", "coord_aug"):
-                if key not in batch:
-                    raise KeyError(f"training_step: cfg.aug_alignment_weight = {cfg.aug_alignment_weight} needs batch[{key!r}] "
-                                   "(the dataset's augmented view and its coordinate map, src/data.py:1132-1139)")
-
-        # (both featurizer passes at once where nothing that draws random numbers stands between them in the reference - the LHP
-        #  module does - and the featurizer offers it)
-        #  (the depth-guided featurizer takes (img, depth) and returns four values, :191-200, one pass at a time)
-        paired = cfg.correspondence_weight > 0 and not getattr(cfg, "lhp", False) and hasattr(self.net, "forward_pair") and self.net.training \
-            and not self.depth_arch
-        rec_feats = None                                          # the first pass's ATTACHED feats, where the reconstruction term gets them
-        # cfg.dg_feature_cache (build-side key, absent or None by default): a batch that carries `image_feat` / `image_feat_pos` - the
-        # frozen backbone's outputs, kept by feature_cache.FeatureCache and gathered by data.ContrastiveBatches - starts behind the
-        # backbone; the head's draws and launches are what they are without it.  (The third pass of the augmentation-alignment term
-        # still runs the backbone on img_aug.)
-        cached = bool(getattr(cfg, "dg_feature_cache", None)) and "image_feat" in batch and "image_feat_pos" in batch and \
-            not self.depth_arch and hasattr(self.net, "forward_pair_features")
-        if paired:
-            # (on the dense identity grid the Dropout2d of the returned feats is applied by the loss's operand preparation: the
-            #  dropped feature tensors are never written - ops.DeferredDropout)
-            p = getattr(self.net, "patch_size", None)
-            defer = p is not None and getattr(self.net, "supports_deferred_dropout", False) and \
-                self.contrastive_corr_loss_fn.takes_deferred_dropout((img.shape[2] // p, img.shape[3] // p))
-            if cached:
-                (feats, code, attn), (feats_pos, code_pos, _) = self.net.forward_pair_features(batch["image_feat"], batch["image_feat_pos"], defer)
-            else:
-                (feats, code, attn), (feats_pos, code_pos, _) = self.net.forward_pair(img, img_pos, defer) if defer else \
-                    self.net.forward_pair(img, img_pos)                                              # :194-200, :207-212
-        elif self.depth_arch:
-            # (feats carry a graph under guidance "sum" / "cross_attn"; the correlation loss reads them under no_grad, src/modules.py:1232-1234)
-            feats, code, image_feat, attn = self.net((img, depth))                                   # :191-197
-            # (cfg.dg_rec_feats_grad: the reconstruction term reads the attached tensor, :391-398, and trains the depth modules through it)
-            if getattr(cfg, "dg_rec_feats_grad", False) and getattr(cfg, "rec_weight", 0) > 0 and feats.requires_grad:
-                rec_feats = feats
-            feats = feats.detach()
-        elif cached:
-            feats, code, attn = self.net.forward_features(batch["image_feat"])
-        else:
-            feats, code, attn = self.net(img)                                                        # :194-200
-        if cached and attn is None and getattr(cfg, "lhp", False):
-            # (the LHP module projects without propagating when `attn is None`, :191-192; the featurizers hand it a placeholder where
-            #  nothing reads the map - so does the cached pass: the "attn" strategy, which would read it, is refused at construction)
-            attn = torch.zeros(1, device=code.device)
-        lhp_code = self.lhp_module(code, depth, img, attn) if getattr(cfg, "lhp", False) else None    # :202-203
-        logs: Dict[str, torch.Tensor] = {}
-        loss = 0
-        if cfg.correspondence_weight > 0:
-            if self.depth_arch:
-                feats_pos, code_pos, image_feat_pos, _ = self.net((img_pos, depth_pos))              # :205-210
-                feats_pos = feats_pos.detach()
-            elif not paired:
-                feats_pos, code_pos, _ = self.net.forward_features(batch["image_feat_pos"]) if cached else self.net(img_pos)   # :207-212
-            lhp_code_pos = self.lhp_module(code_pos, None) if getattr(cfg, "lhp", False) else None   # :214-215
-            salience = batch["mask"].to(torch.float32).squeeze(1) if cfg.use_salience else None      # :233-238
-            salience_pos = batch["mask_pos"].to(torch.float32).squeeze(1) if cfg.use_salience else None
-            use_depth_term = bool(cfg.depth_feat_correlation_loss)
-            d_args = (depth, depth_pos) if use_depth_term else (None, None)                          # :242-292
-            if self.depth_only_intra:
-                # :240-350 with the class of :133-134.  The reference's own call passes `depth=` / `depth_pos=` to parameters named
-                # depth_aug_feats / depth_aug_feats_pos and raises a TypeError; this is the call the names ask for: the frozen
-                # backbone's features (the featurizer's third output) as orig_feats, the depth-augmented ones (its first) as depth_aug_feats
-                out = self.contrastive_corr_loss_fn(image_feat.detach(), image_feat_pos.detach(), salience, salience_pos, code, code_pos,
-                                                    feats, feats_pos)
-            else:
-                out = self.contrastive_corr_loss_fn(feats, feats_pos, salience, salience_pos, code, code_pos, *d_args)
-            # :229-231, :298-301: every cfg.hist_freq steps the reference histograms the three un-reduced cd tensors - here one small
-            # launch on the operands this call left in its workspace (in front of the LHP call, which runs the loss again)
-            hist_freq = getattr(cfg, "hist_freq", None)
-            hists = None
-            if hist_freq is not None and self.global_step % hist_freq == 0 and self.global_step > 0:
-                hists = self.contrastive_corr_loss_fn.cd_histograms(bins=int(getattr(cfg, "dg_hist_bins", 64)))
-            lhp_out = None
-            if getattr(cfg, "lhp", False) and use_depth_term:
-                lhp_out = self.contrastive_corr_loss_fn(feats, feats_pos, salience, salience_pos, lhp_code, lhp_code_pos, *d_args)
-            total, logs = correspondence_total(cfg, out, lhp_out)                                    # :303-350
-            if hists is not None:
-                logs.update({"hist/" + k: v for k, v in hists.items()})
+        plan = step_plan(self.cfg, net=self.net, batch=batch, depth_arch=self.depth_arch, depth_only_intra=self.depth_only_intra,
+                         global_step=self.global_step)
+        for optim in self.optimizers():                                                               # :174-176
+            optim.zero_grad()
+        img, label = batch["img"], batch["label"]
+        depth, depth_pos = (batch["depth"], batch["depth_pos"]) if self.use_depth else (None, None)
+        batch = self._refuse_or_fill(plan, batch)
+        p = self._anchor_pass(plan, batch, depth)
+        lhp_code = self.lhp_module(p.code, depth, img, p.attn) if plan.lhp else None                  # :202-203
+        logs, loss = {}, 0
+        if plan.correspondence:
+            # (the positive pass stays behind the LHP call above: that module draws random numbers)
+            self._positive_pass(plan, batch, depth_pos, p)
+            lhp_code_pos = self.lhp_module(p.code_pos, None) if plan.lhp else None                    # :214-215
+            total, logs = self._correspondence_term(plan, batch, p, (depth, depth_pos), (lhp_code, lhp_code_pos))
             loss = loss + total
         # the legacy decays sit at function-body level in the reference: they run every step, whatever correspondence_weight is
-        legacy_decay_step(cfg, self.contrastive_corr_loss_fn.cfg, self.global_step)                  # :356-375 (mutates cfg)
+        legacy_decay_step(self.cfg, self.contrastive_corr_loss_fn.cfg, self.global_step)             # :356-375 (mutates cfg)
+        loss = self._auxiliary_terms(plan, batch, p, loss, logs)
+        loss = self._probe_terms(p.code, label, loss, logs)
+        self._backward_and_step(plan, loss, grad_sync)
+        return loss.detach(), logs
 
+    def _refuse_or_fill(self, plan, batch):
+        """What can refuse the step, asked before anything is launched (cfg may have changed since construction) -> the batch to read."""
+        if self.depth_arch:
+            self._refuse_depth_arch_combinations(self.cfg)
+        if self.depth_only_intra:
+            self._refuse_depth_only_intra_combinations(self.cfg)
+        if not plan.aug:
+            return batch
+        # cfg.dg_gpu_augment (build-side key, absent or False by default): a batch without the augmented view gets it here - parameters drawn
+        # from torch's global CPU generator (host work: such a step is not captured into a graph), both tensors from batch["img"] at its own
+        # size in two HIP launches (augment.augment_batch).  "unit": img is ImageNet-normalised and the colour ops work on [0, 1] values; any
+        # other true value: the ops act on the tensor as given, as the reference's do.  A batch that carries the keys wins, untouched.
+        if plan.gpu_augment and "img_aug" not in batch:
+            img, unit = batch["img"], plan.gpu_augment == "unit"
+            params = draw_augment_params(img.shape[0], img.shape[2], img.shape[3])
+            img_aug, coord_aug = augment_batch(img, params, mean=IMAGENET_MEAN if unit else None, std=IMAGENET_STD if unit else None)
+            batch = {**batch, "img_aug": img_aug, "coord_aug": coord_aug}
+        for key in ("img_aug", "coord_aug"):
+            if key not in batch:
+                raise KeyError(f"training_step: cfg.aug_alignment_weight = {self.cfg.aug_alignment_weight} needs batch[{key!r}] "
+                               "(the dataset's augmented view and its coordinate map, src/data.py:1132-1139)")
+        return batch
+
+    def _anchor_pass(self, plan, batch, depth):
+        """The featurizer pass on the anchor image - on the pair route both passes at once - as one record.  plan.cached
+        (cfg.dg_feature_cache, build-side key, absent or None by default): the batch carries `image_feat` / `image_feat_pos` - the frozen
+        backbone's outputs, kept by feature_cache.FeatureCache and gathered by data.ContrastiveBatches - and the pass starts behind the
+        backbone; the head's draws and launches are unchanged.  (The augmentation-alignment term's third pass still runs the backbone.)"""
+        # (the record the later stages read - image_feat: the depth route's third output; rec_feats: this pass's ATTACHED feats)
+        p = SimpleNamespace(feats=None, code=None, attn=None, image_feat=None, feats_pos=None, code_pos=None, image_feat_pos=None, rec_feats=None)
+        net, img = self.net, batch["img"]
+        if plan.route == "pair":
+            # (on the dense identity grid the Dropout2d of the returned feats is applied by the loss's operand preparation: the
+            #  dropped feature tensors are never written - ops.DeferredDropout)
+            ps = getattr(net, "patch_size", None)
+            defer = ps is not None and getattr(net, "supports_deferred_dropout", False) and \
+                self.contrastive_corr_loss_fn.takes_deferred_dropout((img.shape[2] // ps, img.shape[3] // ps))
+            (p.feats, p.code, p.attn), (p.feats_pos, p.code_pos, _) = \
+                net.forward_pair_features(batch["image_feat"], batch["image_feat_pos"], defer) if plan.cached else \
+                net.forward_pair(img, batch["img_pos"], defer) if defer else net.forward_pair(img, batch["img_pos"])   # :194-200, :207-212
+        elif plan.route == "depth":
+            # (feats carry a graph under guidance "sum" / "cross_attn"; the correlation loss reads them under no_grad, src/modules.py:1232-1234)
+            feats, p.code, p.image_feat, p.attn = net((img, depth))                                  # :191-197
+            # (cfg.dg_rec_feats_grad: the reconstruction term reads the attached tensor, :391-398, and trains the depth modules through it)
+            p.rec_feats = feats if plan.rec_feats_grad and plan.rec and feats.requires_grad else None
+            p.feats = feats.detach()
+        elif plan.cached:
+            p.feats, p.code, p.attn = net.forward_features(batch["image_feat"])
+        else:
+            p.feats, p.code, p.attn = net(img)                                                       # :194-200
+        if plan.cached and p.attn is None and plan.lhp:
+            # (the LHP module projects without propagating when `attn is None`, :191-192; the featurizers hand it a placeholder where
+            #  nothing reads the map - so does the cached pass: the "attn" strategy, which would read it, is refused at construction)
+            p.attn = torch.zeros(1, device=p.code.device)
+        return p
+
+    def _positive_pass(self, plan, batch, depth_pos, p):
+        """The featurizer pass on the positive image, where the anchor pass did not run it (the depth and single routes)."""
+        if plan.route == "depth":
+            feats_pos, p.code_pos, p.image_feat_pos, _ = self.net((batch["img_pos"], depth_pos))     # :205-210
+            p.feats_pos = feats_pos.detach()
+        elif plan.route == "single":
+            p.feats_pos, p.code_pos, _ = self.net.forward_features(batch["image_feat_pos"]) if plan.cached else \
+                self.net(batch["img_pos"])                                                           # :207-212
+
+    def _correspondence_term(self, plan, batch, p, depths, lhp_codes):
+        """The correlation loss, its histograms, its second call on the LHP codes and the weighted total (:229-350) -> (term, logs)."""
+        loss_fn = self.contrastive_corr_loss_fn
+        salience = batch["mask"].to(torch.float32).squeeze(1) if plan.use_salience else None         # :233-238
+        salience_pos = batch["mask_pos"].to(torch.float32).squeeze(1) if plan.use_salience else None
+        d_args = depths if plan.depth_term else (None, None)                                         # :242-292
+        if plan.depth_only_intra:
+            # :240-350 with the class of :133-134.  The reference's own call passes `depth=` / `depth_pos=` to parameters named
+            # depth_aug_feats / depth_aug_feats_pos and raises a TypeError; this is the call the names ask for: the frozen
+            # backbone's features (the featurizer's third output) as orig_feats, the depth-augmented ones (its first) as depth_aug_feats
+            out = loss_fn(p.image_feat.detach(), p.image_feat_pos.detach(), salience, salience_pos, p.code, p.code_pos, p.feats, p.feats_pos)
+        else:
+            out = loss_fn(p.feats, p.feats_pos, salience, salience_pos, p.code, p.code_pos, *d_args)
+        # :229-231, :298-301: every cfg.hist_freq steps the reference histograms the three un-reduced cd tensors - here one small
+        # launch on the operands this call left in its workspace (in front of the LHP call, which runs the loss again)
+        hists = loss_fn.cd_histograms(bins=plan.hist_bins) if plan.histograms else None
+        lhp_out = loss_fn(p.feats, p.feats_pos, salience, salience_pos, *lhp_codes, *d_args) if plan.lhp and plan.depth_term else None
+        total, logs = correspondence_total(self.cfg, out, lhp_out)                                   # :303-350
+        if hists is not None:
+            logs.update({"hist/" + k: v for k, v in hists.items()})
+        return total, logs
+
+    def _auxiliary_terms(self, plan, batch, p, loss, logs):
+        """The reconstruction, augmentation-alignment and CRF terms, in the reference's order; each logs itself.  Returns the loss."""
+        cfg = self.cfg
         # :391-398: the reconstruction term - the decoder's 1 x 1 convolution of code against feats, both normalised - as one fused
         # HIP forward and one HIP backward (rec_loss.reconstruction_loss): rec_feats is never written.  feats goes in as it is: in
         # the paired pass it may be an ops.DeferredDropout, whose mask the kernels apply.  Off: nothing is launched or logged.
-        if getattr(cfg, "rec_weight", 0) > 0:
+        if plan.rec:
             if getattr(self, "decoder", None) is None:
                 raise RuntimeError(f"training_step: cfg.rec_weight = {cfg.rec_weight} but this segmenter was built without a decoder "
                                    "(rec_weight was 0 then); set cfg.rec_weight before constructing UnsupervisedSegmenter")
-            if rec_feats is not None:    # (arch "dino_depth" under "sum" / "cross_attn" with cfg.dg_rec_feats_grad: d feats is written too)
-                rec = reconstruction_loss(code, rec_feats, self.decoder.weight, self.decoder.bias, feats_grad=True)
+            if p.rec_feats is not None:  # (arch "dino_depth" under "sum" / "cross_attn" with cfg.dg_rec_feats_grad: d feats is written too)
+                rec = reconstruction_loss(p.code, p.rec_feats, self.decoder.weight, self.decoder.bias, feats_grad=True)
             else:
-                rec = reconstruction_loss(code, feats, self.decoder.weight, self.decoder.bias)
+                rec = reconstruction_loss(p.code, p.feats, self.decoder.weight, self.decoder.bias)
             logs["loss/rec"] = rec.detach()
             loss = loss + cfg.rec_weight * rec
-
         # :400-411: the augmentation-alignment term - a third featurizer pass (in training mode: its own Dropout2d draws, as the
         # reference's would be) and aug_loss.aug_alignment_loss, one fused HIP forward and one HIP backward whose gradient reaches the
         # head through both maps.  (:401 unpacks two values where the training-mode featurizer returns three: the intent is element 1.)
         # Off: no pass, no draw, no launch, and the batch may lack the two keys.
-        if getattr(cfg, "aug_alignment_weight", 0) > 0:
+        if plan.aug:
             code_aug = self.net(batch["img_aug"])[1]
-            aug_alignment = aug_alignment_loss(code, code_aug, batch["coord_aug"])
+            aug_alignment = aug_alignment_loss(p.code, code_aug, batch["coord_aug"])
             logs["loss/aug_alignment"] = aug_alignment.detach()
             loss = loss + cfg.aug_alignment_weight * aug_alignment
-
         # :413-419: the contrastive CRF term, one fused HIP forward (the maps are resized at the crf_samples positions only, the
         # similarity kernel is formed on the fly) and one HIP backward - ContrastiveCRFLoss.mean_loss.  Off: nothing is drawn or launched.
-        if getattr(cfg, "crf_weight", 0) > 0:
-            crf = self.crf_loss_fn.mean_loss(img, code)
+        if plan.crf:
+            crf = self.crf_loss_fn.mean_loss(batch["img"], p.code)
             logs["loss/crf"] = crf.detach()
             loss = loss + cfg.crf_weight * crf
+        return loss
 
-        # probes on the detached code (:421-444)
+    def _probe_terms(self, code, label, loss, logs):
+        """The probes on the detached code (:421-444); logs both terms and the total.  Returns the loss."""
         detached_code = code.detach().clone()
         # resize to the label resolution + masked cross entropy in one HIP kernel (the reference materialises the logits at label
         # resolution and three masks, :427-434); the cluster probe's similarity / arg-max / loss likewise
@@ -429,23 +403,25 @@ class UnsupervisedSegmenter(nn.Module):
         cluster_loss, _ = self.cluster_probe(detached_code, None)
         loss = loss + linear_loss + cluster_loss
         logs.update({"loss/linear": linear_loss.detach(), "loss/cluster": cluster_loss.detach(), "loss/total": loss.detach()})
+        return loss
 
+    def _backward_and_step(self, plan, loss, grad_sync):
+        """Backward, `grad_sync`, the optimiser step or steps, the probe reset on its step, the step count (:446-455)."""
+        net_optim, linear_probe_optim, cluster_probe_optim = self.optimizers()
         loss.backward()                                                                               # :446
-        fused = self._fused_set() if getattr(cfg, "dg_fused_adam", False) else None
-        handed = grad_sync() if grad_sync is not None else None
-        grads = self._handed_over_grads(handed, fused)
+        fused = self._fused_set() if plan.fused_adam else None
+        grads = self._handed_over_grads(grad_sync() if grad_sync is not None else None, fused)
         if fused is not None:
             fused.step(grads=grads)                                                                   # :447-449 in one HIP launch
         else:
             net_optim.step(); cluster_probe_optim.step(); linear_probe_optim.step()                   # :447-449
-        if cfg.reset_probe_steps is not None and self.global_step == cfg.reset_probe_steps:           # :451-455
+        if plan.reset_probes:                                                                         # :451-455
             self.linear_probe.reset_parameters()
             self.cluster_probe.reset_parameters()
             adam = FusedAdam if fused is not None else torch.optim.Adam
             self._optims = (net_optim, adam(list(self.linear_probe.parameters()), lr=5e-3),
                             adam(list(self.cluster_probe.parameters()), lr=5e-3))
         self.global_step += 1
-        return loss.detach(), logs
 
     def _eval_mode_codes(self, img, flip):
         """code = net(img)[1] (and of the mirrored images when `flip`) with the net in eval mode; the net's mode is restored after
@@ -481,18 +457,10 @@ class UnsupervisedSegmenter(nn.Module):
     def on_validation_epoch_end(self) -> Dict[str, float]:
         """src/train_segmentation.py:501-535 without the logger: both metrics, the running maxima, reset; returns the metrics."""
         tb_metrics = {**self.linear_metrics.compute(), **self.cluster_metrics.compute()}
-        if tb_metrics["test/cluster/Accuracy"] > self.max_cluster_accuracy:
-            self.max_cluster_accuracy = tb_metrics["test/cluster/Accuracy"]
-        if tb_metrics["test/cluster/mIoU"] > self.max_cluster_miou:
-            self.max_cluster_miou = tb_metrics["test/cluster/mIoU"]
-        if tb_metrics["test/linear/Accuracy"] > self.max_linear_accuracy:
-            self.max_linear_accuracy = tb_metrics["test/linear/Accuracy"]
-        if tb_metrics["test/linear/mIoU"] > self.max_linear_miou:
-            self.max_linear_miou = tb_metrics["test/linear/mIoU"]
-        tb_metrics["test/cluster/MaxAccuracy"] = self.max_cluster_accuracy
-        tb_metrics["test/cluster/MaxmIoU"] = self.max_cluster_miou
-        tb_metrics["test/linear/MaxAccuracy"] = self.max_linear_accuracy
-        tb_metrics["test/linear/MaxmIoU"] = self.max_linear_miou
+        for prefix, metric, attr in (("test/cluster/", "Accuracy", "max_cluster_accuracy"), ("test/cluster/", "mIoU", "max_cluster_miou"),
+                                     ("test/linear/", "Accuracy", "max_linear_accuracy"), ("test/linear/", "mIoU", "max_linear_miou")):
+            setattr(self, attr, max(getattr(self, attr), tb_metrics[prefix + metric]))
+            tb_metrics[prefix + "Max" + metric] = getattr(self, attr)        # (new keys: appended behind the metrics, in this order)
         self.linear_metrics.reset()
         self.cluster_metrics.reset()
         self.validation_step_outputs.clear()

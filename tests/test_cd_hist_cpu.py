@@ -99,5 +99,9 @@ def test_segmenter_cfg_keys():
     cfg = segmenter.default_segmenter_cfg()
     assert cfg.hist_freq == 100                                       # the reference's shipped default
     assert not hasattr(cfg, "dg_hist_bins")                           # optional, build-side: read with getattr
-    src = inspect.getsource(segmenter.UnsupervisedSegmenter.training_step)
-    assert 'getattr(cfg, "dg_hist_bins", 64)' in src and "cd_histograms" in src
+    # (the step reads the key through its plan, training.step_plan, and takes the histograms in its correspondence stage)
+    from depthg_amd import training
+    assert 'getattr(cfg, "dg_hist_bins", 64)' in inspect.getsource(training.step_plan)
+    assert "step_plan(" in inspect.getsource(segmenter.UnsupervisedSegmenter.training_step)
+    src = inspect.getsource(segmenter.UnsupervisedSegmenter._correspondence_term)
+    assert "cd_histograms(bins=plan.hist_bins)" in src
