@@ -372,14 +372,14 @@ class ContrastiveBatches:
             self.nns = knn.load_nns(path, len(dataset))
         # feature_cache.FeatureCache of this dataset's images (build_feature_cache): each batch then also carries the frozen backbone's
         # `image_feat` of its samples and `image_feat_pos` of their positives, gathered in one launch from the indices while they are
-        # still on the host.  img / img_pos stay in the batch (the CRF and augmentation terms read them).
+        # still on the host.  img / img_pos stay in the batch (the CRF and augmentation terms read them).  Without positives
+        # (pos=False: a val split, whose cache train.val_feature_cache builds) the batch carries `image_feat` alone, from one launch
+        # over the one index list - the short last batch included.
         self.feature_cache = feature_cache
         if feature_cache is not None:
             if loader_crop_type == "random":
                 raise ValueError("depthg_amd.data: a feature cache holds the features of ONE view of every image; with loader_crop_type = "
-                                 "'random' the view changes with every draw")
-            if not self.pos:
-                raise ValueError("depthg_amd.data: a feature cache serves the training pipeline (pos=True): image_feat and image_feat_pos")
+                                 "'random' the view changes with every draw; use 'center' or None, or run without the cache")
             if feature_cache.n_images != len(dataset) or feature_cache.device != self.device:
                 raise ValueError(f"depthg_amd.data: the feature cache holds {feature_cache.n_images} images on {feature_cache.device}, the "
                                  f"pipeline reads {len(dataset)} on {self.device}")
@@ -431,8 +431,10 @@ class ContrastiveBatches:
             batch.update({"img_pos": img[B:], "ind_pos": torch.tensor(inds_pos, dtype=torch.int64), "label_pos": label[B:], "mask_pos": mask[B:]})
             if self.return_depth:
                 batch["depth_pos"] = depth[B:].unsqueeze(1)
-        if self.feature_cache is not None:
+        if self.feature_cache is not None and self.pos:
             batch["image_feat"], batch["image_feat_pos"] = self.feature_cache.gather(inds, inds_pos)
+        elif self.feature_cache is not None:
+            batch["image_feat"] = self.feature_cache.gather(inds)
         return batch
 
     def __iter__(self):
@@ -471,32 +473,42 @@ def precompute_knns(net, dataset, cfg, res, image_set, crop_type, batch_size=Non
 
 
 # --------------------------------------------------------------------------------------------------------------- feature cache
-def feature_cache_meta(cfg, dataset, res, crop_type):
+def feature_cache_meta(cfg, dataset, res, crop_type, image_set=None, mirrored=False):
     """What the cached features of `dataset` depend on (FeatureCache.meta): the backbone, the view, the images.  crop_type: the
-    LOADER's crop (the dataset's own crop is part of its name)."""
-    return {"model_type": str(getattr(cfg, "model_type", "vit_small")), "dino_patch_size": int(cfg.dino_patch_size),
+    LOADER's crop (the dataset's own crop is part of its name).  `image_set`: the split, named in the metadata of every cache but the
+    train split's (whose files carry no such key: a file without it never matches a request that names one).  `mirrored`: the features
+    of the horizontally mirrored images (evaluate_batch's flip pass)."""
+    meta = {"model_type": str(getattr(cfg, "model_type", "vit_small")), "dino_patch_size": int(cfg.dino_patch_size),
             "dino_feat_type": str(getattr(cfg, "dino_feat_type", "feat")), "res": int(res), "loader_crop_type": crop_type,
             "dataset_name": "{}_{}".format(dataset.nns_name, getattr(dataset, "crop_type", None)), "n_images": len(dataset),
             "pretrained_weights": getattr(cfg, "pretrained_weights", None)}
+    if image_set is not None:
+        meta["split"] = str(image_set)
+    if mirrored:
+        meta["mirrored"] = True
+    return meta
 
 
 def feature_cache_path(data_dir, meta, image_set, dtype):
     """<data_dir>/feature_cache_<meta>.pt"""
     from .feature_cache import as_dtype
-    name = "feature_cache_{model_type}_{dino_feat_type}{dino_patch_size}_{dataset_name}_{split}_{loader_crop_type}_{res}_{n_images}_{dtype}.pt".format(
-        split=image_set, dtype=str(as_dtype(dtype)).replace("torch.", ""), **meta)
+    name = "feature_cache_{model_type}_{dino_feat_type}{dino_patch_size}_{dataset_name}_{image_set}_{loader_crop_type}_{res}_{n_images}_{dtype}.pt".format(
+        image_set=image_set, dtype=("mirrored_" if meta.get("mirrored") else "") + str(as_dtype(dtype)).replace("torch.", ""), **meta)
     return os.path.join(data_dir, name)
 
 
 def build_feature_cache(net, dataset, cfg, res, crop_type, dtype=torch.float32, device=None, batch_size=None, num_workers=0,
-                        sample_cache=None):
+                        sample_cache=None, image_set=None, mirrored=False):
     """A feature_cache.FeatureCache of `dataset`: one pass over the split in index order through `prepare_samples` with the loader
     transform (res, crop_type - the pipeline's loader_crop_type), `net._backbone(img)` under no_grad with the backbone in eval mode
     (what forward() runs, src/modules.py:93-120), one `put` per batch.  The pass --precompute-knns makes over the same images pools
     and drops these maps; this one keeps them.  Refused: crop_type "random" (the features would depend on the draw) and cfg.arch
     "dino_depth" (the depth-guided featurizer mixes the depth map in behind the backbone: out of scope for the cache).
     `sample_cache`: a sample_cache.SampleCache of the same split and transform to fill from the samples this pass decodes anyway, so
-    that a run that wants both caches decodes the split once."""
+    that a run that wants both caches decodes the split once.  `image_set`: the split the metadata name (feature_cache_meta; None: the
+    train split's form).  `mirrored`: the backbone runs on img.flip(dims=[3]) - the features evaluate_batch(flip=True) reads as
+    `image_feat_flip` (a mirrored feature map is not the feature map of the mirrored image); the sample cache still gets the images
+    as they are."""
     from .feature_cache import FeatureCache
     _refuse_random_crop(crop_type, "depthg_amd.data: build_feature_cache", "features")
     if getattr(cfg, "arch", "dino") == "dino_depth" or not hasattr(net, "forward_pair_features") or not hasattr(net, "_backbone"):
@@ -517,9 +529,10 @@ def build_feature_cache(net, dataset, cfg, res, crop_type, dtype=torch.float32, 
             if sample_cache is not None:
                 sample_cache.put(inds, samples, res, crop_type)
             img = prepare_samples(dataset, samples, res, crop_type, device, False)[0]
-            image_feat = net._backbone(img)[0]
+            image_feat = net._backbone(img.flip(dims=[3]) if mirrored else img)[0]
             if cache is None:
-                cache = FeatureCache(n, *image_feat.shape[1:], dtype=dtype, device=device, meta=feature_cache_meta(cfg, dataset, res, crop_type))
+                cache = FeatureCache(n, *image_feat.shape[1:], dtype=dtype, device=device,
+                                     meta=feature_cache_meta(cfg, dataset, res, crop_type, image_set, mirrored))
             cache.put(inds, image_feat)
     if cache is None:
         raise ValueError("depthg_amd.data: build_feature_cache on an empty dataset")

@@ -8,7 +8,9 @@ The cache stores it as an (n_images, C h w) table of float32, float16 or bfloat1
 ops.feature_cache_gather over k_fc_put / k_fc_gather of dg_feat_cache.hip), laid out as the head's paired pass takes its two maps.
 data.build_feature_cache fills one, data.ContrastiveBatches(feature_cache=...) puts `image_feat` / `image_feat_pos` into its batches,
 and with cfg.dg_feature_cache set training_step starts from them (FrozenBackboneFeaturizer.forward_features / forward_pair_features)
-instead of running the backbone.
+instead of running the backbone.  A second cache can hold the val split (train.val_feature_cache, cfg.dg_val_feature_cache):
+data.ContrastiveBatches(pos=False, feature_cache=...) then puts `image_feat` alone into each val batch - `gather` with one index list,
+still one launch - and validation_step / evaluate_batch start behind the backbone.
 
 On a CPU `device` the class is plain torch - index_copy_, index_select and casts: the statement the kernels are tested against.
 A cache that does not fit on the card is out of scope: construction fails with torch's out-of-memory error, the needed bytes named.

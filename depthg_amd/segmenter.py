@@ -105,6 +105,8 @@ class UnsupervisedSegmenter(nn.Module):
         if getattr(cfg, "dg_feature_cache", None) and getattr(cfg, "lhp", False) and getattr(cfg, "propagation_strategy", "depth") == "attn":
             raise ValueError("depthg_amd: cfg.dg_feature_cache cannot be combined with cfg.lhp under propagation_strategy = 'attn': the "
                              "cache keeps image_feat, not the last block's attention map the LHP module would read")
+        if getattr(cfg, "dg_val_feature_cache", None):
+            self._refuse_val_feature_cache_combinations(cfg)
         if net is None:                                                               # :99-108
             # cfg.dg_dino_backbone (build-side key, off by default): the real DINO ViT (featurizer.DinoFeaturizer) instead of the stand-in
             real = getattr(cfg, "dg_dino_backbone", False)
@@ -423,15 +425,63 @@ class UnsupervisedSegmenter(nn.Module):
                             adam(list(self.cluster_probe.parameters()), lr=5e-3))
         self.global_step += 1
 
-    def _eval_mode_codes(self, img, flip):
+    @staticmethod
+    def _refuse_val_feature_cache_combinations(cfg):
+        """cfg.dg_val_feature_cache with a configuration whose evaluation cannot start behind the backbone (asked at construction)."""
+        from .feature_cache import as_dtype
+        as_dtype(cfg.dg_val_feature_cache)
+        if getattr(cfg, "arch", "dino") == "dino_depth":
+            raise ValueError("depthg_amd: cfg.dg_val_feature_cache serves cfg.arch = 'dino': the evaluation branch of the depth-guided "
+                             "featurizer (arch 'dino_depth') forms its features from the image and has no forward_features; leave "
+                             "cfg.dg_val_feature_cache unset (validation then runs the backbone) or use arch 'dino'")
+
+    def _cached_eval_features(self, batch, flip):
+        """(image_feat, image_feat_flip) for the evaluation routes to start from, or (None, None): the backbone runs.  Only with
+        cfg.dg_val_feature_cache (build-side key, absent or None by default) and a batch that carries `image_feat` - the frozen
+        backbone's output on batch["img"], kept by a feature_cache.FeatureCache of the split (train.val_feature_cache) and gathered
+        by data.ContrastiveBatches(pos=False, feature_cache=...); `image_feat_flip`: the same of the mirrored images, from a second
+        cache (data.build_feature_cache(mirrored=True))."""
+        if not getattr(self.cfg, "dg_val_feature_cache", None) or "image_feat" not in batch:
+            return None, None
+        img, feats = batch["img"], [batch["image_feat"]]
+        if flip:
+            if "image_feat_flip" not in batch:
+                raise ValueError("depthg_amd: evaluate_batch(flip=True) from cached features needs batch['image_feat_flip'] as well: "
+                                 "the backbone's features of the MIRRORED images (a mirrored feature map is not the feature map of "
+                                 "the mirrored image: the ViT's position embedding is not symmetric).  Build a second cache with "
+                                 "data.build_feature_cache(..., mirrored=True) and gather it into the batch, call "
+                                 "evaluate_batch(flip=False), or drop 'image_feat' from the batch to run the backbone")
+            feats.append(batch["image_feat_flip"])
+        if self.depth_arch or not all(hasattr(self.net, a) for a in ("forward_features", "patch_size", "n_feats")):
+            raise ValueError("depthg_amd: cfg.dg_val_feature_cache needs a featurizer with a pass from cached features "
+                             "(FrozenBackboneFeaturizer.forward_features, cfg.arch = 'dino'); leave the key unset to run the backbone")
+        ps = int(self.net.patch_size)
+        want = (img.shape[0], int(self.net.n_feats), img.shape[2] // ps, img.shape[3] // ps)
+        for name, f in zip(("image_feat", "image_feat_flip"), feats):
+            if f.dim() != 4 or tuple(f.shape) != want:
+                raise ValueError(f"depthg_amd: batch[{name!r}] is {tuple(f.shape)}, the featurizer's output on images of "
+                                 f"{tuple(img.shape)} is {want}: the cache was built for another backbone or resolution - rebuild it "
+                                 "(train.val_feature_cache at this eval_res) or leave cfg.dg_val_feature_cache unset")
+        return feats[0], (feats[1] if flip else None)
+
+    def _eval_mode_codes(self, img, flip, image_feat=None, image_feat_flip=None):
         """code = net(img)[1] (and of the mirrored images when `flip`) with the net in eval mode; the net's mode is restored after
-        (what Lightning does around its validation loop: the next training_step needs the training-mode 3-tuple)."""
+        (what Lightning does around its validation loop: the next training_step needs the training-mode 3-tuple).  With `image_feat`
+        (and, under `flip`, `image_feat_flip`: the backbone's features of the mirrored images) the pass starts behind the backbone:
+        code = net.forward_features(image_feat)[1], the eval-mode head - no dropout, no draw."""
+        if image_feat is not None and flip and image_feat_flip is None:
+            raise ValueError("depthg_amd: the flipped pass from cached features needs image_feat_flip (data.build_feature_cache(..., "
+                             "mirrored=True)): a mirrored feature map is not the feature map of the mirrored image")
         was_training = self.net.training
         self.net.eval()
         try:
             with torch.no_grad():
-                code = self.net(img)[1]
-                code_flip = self.net(img.flip(dims=[3]))[1] if flip else None
+                if image_feat is not None:
+                    code = self.net.forward_features(image_feat)[1]
+                    code_flip = self.net.forward_features(image_feat_flip)[1] if flip else None
+                else:
+                    code = self.net(img)[1]
+                    code_flip = self.net(img.flip(dims=[3]))[1] if flip else None
         finally:
             self.net.train(was_training)
         return code, code_flip
@@ -440,10 +490,12 @@ class UnsupervisedSegmenter(nn.Module):
         """src/train_segmentation.py:471-499: the probes' arg-max predictions at the label resolution into linear_metrics /
         cluster_metrics, one HIP launch pair (evaluation.predict_and_score) instead of the resize, 1x1 convolution, cosine
         similarities and bincounts at label resolution.  Appends and returns the first cfg.n_images of img, linear_preds,
-        cluster_preds and label, on the CPU."""
+        cluster_preds and label, on the CPU.  With cfg.dg_val_feature_cache set, a batch that carries `image_feat` skips the
+        backbone (the batch keeps `img`: it is returned); a batch without the key, or any batch without the cfg key, runs it."""
         img, label = batch["img"], batch["label"]
         k = int(getattr(self.cfg, "n_images", 5))
-        code, _ = self._eval_mode_codes(img, False)
+        # cfg.dg_val_feature_cache and a batch with `image_feat`: the pass starts behind the frozen backbone (_cached_eval_features)
+        code, _ = self._eval_mode_codes(img, False, *self._cached_eval_features(batch, False))
         linear_preds, cluster_preds = predict_and_score(code, label, self.linear_probe, self.cluster_probe, self.linear_metrics,
                                                         self.cluster_metrics, n_store=k)
         none = torch.empty((0,) + tuple(label.shape[-2:]), dtype=torch.int64)          # (n_images = 0)
@@ -470,9 +522,11 @@ class UnsupervisedSegmenter(nn.Module):
         """src/eval_segmentation.py:146-170: code of the image and (flip) of its mirror, averaged as (code1 + code2.flip(3)) / 2
         inside the projection, the probes' arg-max predictions into test_linear_metrics / test_cluster_metrics; with run_crf
         (eval_config.yml's run_crf) both probes' outputs are refined by the dense CRF on the batch's images first (:162-167).
-        Returns (linear_preds, cluster_preds) (B,H,W) int64 on the GPU."""
+        Returns (linear_preds, cluster_preds) (B,H,W) int64 on the GPU.  With cfg.dg_val_feature_cache set, a batch that carries
+        `image_feat` and (flip) `image_feat_flip` - the backbone's features of the mirrored images, from a cache built with
+        data.build_feature_cache(mirrored=True) - skips the backbone; `image_feat` alone under flip is refused."""
         img, label = batch["img"], batch["label"]
-        code, code_flip = self._eval_mode_codes(img, flip)
+        code, code_flip = self._eval_mode_codes(img, flip, *self._cached_eval_features(batch, flip))
         return predict_and_score(code, label, self.linear_probe, self.cluster_probe, self.test_linear_metrics,
                                  self.test_cluster_metrics, code_flip=code_flip, n_store=img.shape[0], img=img if run_crf else None,
                                  run_crf=run_crf)
@@ -535,6 +589,10 @@ def default_segmenter_cfg(**over) -> SimpleNamespace:
         # build-side, arch "dino": None, or the storage type ("float32", "float16", "bfloat16") of a feature_cache.FeatureCache - a
         # batch that carries `image_feat` / `image_feat_pos` (data.ContrastiveBatches(feature_cache=...)) then skips the frozen backbone
         dg_feature_cache=None,
+        # build-side, arch "dino": None, or the storage type of a FeatureCache of the VAL split (train.val_feature_cache) - a val batch
+        # that carries `image_feat` (data.ContrastiveBatches(pos=False, feature_cache=...)) then skips the frozen backbone in
+        # validation_step and evaluate_batch
+        dg_val_feature_cache=None,
         # build-side: the cached step recorded in a hipGraph and replayed, its batches drawn on the device (graph_step.GraphedTrainStep
         # over epoch.DeviceEpoch; the train command's --graph-step).  training_step itself does not read the key
         dg_graph_step=False)

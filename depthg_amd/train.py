@@ -1,6 +1,6 @@
 """Train a segmenter from a dataset folder: the loop of src/train_segmentation.py:551-714 without Lightning, Hydra, TensorBoard or wandb.
 
-    python -m depthg_amd.train --data-dir D --out O [--dataset directory] [--precompute-knns] [--feature-cache float32] [--sample-cache] [--device cuda:0] [key=value ...]
+    python -m depthg_amd.train --data-dir D --out O [--dataset directory] [--precompute-knns] [--feature-cache float32] [--val-feature-cache float32] [--sample-cache] [--device cuda:0] [key=value ...]
 
 builds the train pipeline (data.CroppedFolder, or data.DirectoryFolder with --dataset directory, under data.ContrastiveBatches: the
 loader transform of a batch and its kNN positives is one fused HIP launch) from the cfg keys dataset_name, crop_type, crop_ratio, res,
@@ -11,7 +11,11 @@ they parse, else as strings; `~` and `null` are None).  --precompute-knns writes
 (data.precompute_knns).  --feature-cache {float32,float16,bfloat16} (cfg.dg_feature_cache) runs the frozen backbone over the train split
 once behind that, keeps its features in a feature_cache.FeatureCache - saved as <data-dir>/feature_cache_<meta>.pt and loaded from there when
 the file exists and matches - and trains from them: the step skips the backbone (loader_crop_type "center" or None, arch "dino"; validation
-is untouched).  --sample-cache keeps the loader's output bytes of the train and the val split on the device (sample_cache.SampleCache,
+is untouched).  --val-feature-cache {float32,float16,bfloat16} (cfg.dg_val_feature_cache) does the same for the val split, behind the
+train cache: the backbone runs over the val images once, at eval_res and the val crop (val_feature_cache; the file's metadata name the
+split, so a train file is never taken for it), every val batch carries `image_feat` from one gather launch, and validation_step starts
+behind the backbone - the eval-mode head, then the fused probe-and-score launches, as ever; with a float32 cache its predictions and
+metrics are those of the uncached validation.  --feature-cache alone leaves validation as it was.  --sample-cache keeps the loader's output bytes of the train and the val split on the device (sample_cache.SampleCache,
 saved as <data-dir>/sample_cache_<meta>.pt and loaded from there when the file matches): every batch is then one gather launch over them
 and an epoch opens no image file; without the flag nothing changes.  --graph-step (cfg.dg_graph_step; with both caches) draws every batch
 and its positives on the device (epoch.DeviceEpoch) and replays the step from a hipGraph (graph_step.GraphedTrainStep): the short last
@@ -185,6 +189,39 @@ def train_feature_cache(cfg, data_dir, device, train_set, net, dtype, sample_cac
     return cache
 
 
+def val_view(cfg):
+    """(eval_res, val_crop): the val pipeline's loader transform - 320 (224 for model_type "mae"), a centre crop (none for "voc")."""
+    return (224 if cfg.model_type == "mae" else 320), (None if cfg.dataset_name == "voc" else "center")          # :597-600, :632-635
+
+
+def val_feature_cache(cfg, data_dir, device, val_set, net, dtype, sample_cache=None):
+    """The VAL split's feature_cache.FeatureCache of storage type `dtype`, at the val pipeline's view (val_view: eval_res and the val
+    crop): loaded from <data_dir>/feature_cache_<meta>.pt when that file exists and its metadata match - the split ("val"), the
+    resolution, the crop and the image count among them, so the train split's file is never taken for it - else built with the
+    featurizer `net` (data.build_feature_cache) and saved there.  `sample_cache`: an empty sample cache of the val split that the
+    building pass fills from the samples it decodes (left empty when the file is loaded).  The table takes n * C * h * w * itemsize
+    bytes on the device; one that does not fit fails with the bytes named (row_cache.RowCache)."""
+    from . import data
+    from .feature_cache import FeatureCache
+    eval_res, val_crop = val_view(cfg)
+    meta = data.feature_cache_meta(cfg, val_set, eval_res, val_crop, image_set="val")
+    path = data.feature_cache_path(data_dir, meta, "val", dtype)
+    if os.path.exists(path):
+        try:
+            cache = FeatureCache.load(path, device, expect_meta=meta)
+            if bool(cache.filled.all()):
+                print(f"depthg_amd.train: val feature cache loaded from {path} ({cache.nbytes} bytes)")
+                return cache
+        except ValueError as e:
+            print(f"depthg_amd.train: {path} does not match ({e}); rebuilding")
+    cache = data.build_feature_cache(net, val_set, cfg, eval_res, val_crop, dtype=dtype, device=device,
+                                     batch_size=min(int(cfg.batch_size), max(len(val_set), 1)), num_workers=cfg.num_workers,
+                                     sample_cache=sample_cache, image_set="val")
+    cache.save(path)
+    print(f"depthg_amd.train: val feature cache built and saved to {path} ({cache.nbytes} bytes)")
+    return cache
+
+
 def load_sample_cache(data_dir, device, dataset, image_set, res, crop_type, want_depth):
     """(cache, path): the split's sample_cache.SampleCache from <data_dir>/sample_cache_<meta>.pt when that file exists, its metadata
     match and every row is there - else an EMPTY cache for the caller to fill (finish_sample_cache) and save there."""
@@ -214,11 +251,12 @@ def finish_sample_cache(cfg, cache, path, dataset, res, crop_type):
     return cache
 
 
-def build_pipelines(cfg, data_dir, device, precompute=False, net=None, feature_cache=None, sample_cache=False):
+def build_pipelines(cfg, data_dir, device, precompute=False, net=None, feature_cache=None, sample_cache=False, val_cache=None):
     """(train_batches, val_batches, n_classes) of cfg (:614-658).  `precompute`: write the train table first when it is missing, with `net`.
     `feature_cache`: None, or the storage type of the train split's feature cache (train_feature_cache; `net` supplies the featurizer).
     `sample_cache`: keep both splits' loader outputs on the device (--sample-cache); with a feature cache to build as well, the train
-    split is decoded once for both."""
+    split is decoded once for both.  `val_cache`: None, or the storage type of the val split's feature cache (val_feature_cache, built
+    or loaded behind the train one): the val batches then carry `image_feat`."""
     from . import data, knn
     train_set = build_dataset(cfg, data_dir, "train", bool(cfg.use_depth))
     if train_set.n_classes is None:
@@ -239,14 +277,18 @@ def build_pipelines(cfg, data_dir, device, precompute=False, net=None, feature_c
     train_batches = data.ContrastiveBatches(train_set, cfg, "train", cfg.res, cfg.loader_crop_type, cfg.batch_size, shuffle=True, generator=gen,
                                             num_workers=cfg.num_workers, pos=True, return_depth=bool(cfg.use_depth), device=device,
                                             feature_cache=cache, sample_cache=samples)
-    eval_res = 224 if cfg.model_type == "mae" else 320                                                               # :597-600
-    val_crop = None if cfg.dataset_name == "voc" else "center"                                                       # :632-635
+    eval_res, val_crop = val_view(cfg)
     val_set = build_dataset(cfg, data_dir, "val", False)
+    val_feats = None
     if sample_cache:
         val_samples, val_path = load_sample_cache(data_dir, device, val_set, "val", eval_res, val_crop, False)
+    if val_cache is not None:
+        val_feats = val_feature_cache(cfg, data_dir, device, val_set, net(train_set.n_classes), val_cache,
+                                      sample_cache=val_samples if val_samples is not None and not val_samples.filled.any() else None)
+    if sample_cache:
         finish_sample_cache(cfg, val_samples, val_path, val_set, eval_res, val_crop)
     val_batches = data.ContrastiveBatches(val_set, cfg, "val", eval_res, val_crop, cfg.batch_size, shuffle=False, num_workers=cfg.num_workers,
-                                          pos=False, return_depth=False, device=device, sample_cache=val_samples)
+                                          pos=False, return_depth=False, device=device, feature_cache=val_feats, sample_cache=val_samples)
     return train_batches, val_batches, train_set.n_classes
 
 
@@ -260,6 +302,10 @@ def main(argv=None) -> int:
     ap.add_argument("--feature-cache", choices=("float32", "float16", "bfloat16"), default=None,
                     help="keep the frozen backbone's features of the train split in this type and train from them (sets dg_feature_cache); "
                          "built once, saved as feature_cache_<meta>.pt under --data-dir and loaded from there afterwards")
+    ap.add_argument("--val-feature-cache", choices=("float32", "float16", "bfloat16"), default=None,
+                    help="keep the frozen backbone's features of the VAL split (at eval_res, the val crop) in this type and validate from "
+                         "them (sets dg_val_feature_cache); built once behind the train cache, saved as feature_cache_<meta>.pt under "
+                         "--data-dir and loaded from there afterwards")
     ap.add_argument("--sample-cache", action="store_true",
                     help="keep the loader's output bytes of the train and the val split on the device and form every batch from them in one "
                          "launch; built once, saved as sample_cache_<meta>.pt under --data-dir and loaded from there afterwards "
@@ -275,6 +321,8 @@ def main(argv=None) -> int:
         overrides["dataset_name"] = args.dataset
     if args.feature_cache is not None:
         overrides["dg_feature_cache"] = args.feature_cache
+    if args.val_feature_cache is not None:
+        overrides["dg_val_feature_cache"] = args.val_feature_cache
     if args.graph_step:
         if args.feature_cache is None or not args.sample_cache:
             ap.error("--graph-step replays the CACHED step: give --feature-cache {float32,float16,bfloat16} and --sample-cache as well")
@@ -304,7 +352,8 @@ def main(argv=None) -> int:
         return model.net
 
     train_batches, val_batches, n_classes = build_pipelines(cfg, args.data_dir, device, args.precompute_knns, knn_net,
-                                                            getattr(cfg, "dg_feature_cache", None), args.sample_cache)
+                                                            getattr(cfg, "dg_feature_cache", None), args.sample_cache,
+                                                            getattr(cfg, "dg_val_feature_cache", None))
     model = model_for(n_classes)
     model.train()
     graph_step = None
