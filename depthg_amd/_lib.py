@@ -90,6 +90,9 @@ SIGNATURES = {
     "dg_cluster_lookup_backward": (_I, [vp, vp, vp, f32, vp] + [i32] * 4 + [vp] * 4),
     "dg_probe_ce_forward": (_I, [vp, vp] + [i32] * 6 + [vp] * 3),
     "dg_probe_ce_backward": (_I, [vp] * 4 + [i32] * 6 + [vp] * 2),
+    "dg_probe_step_workspace_bytes": (_SZ, [i32] * 8),
+    "dg_probe_step_forward": (_I, [vp] * 5 + [i32] * 8 + [vp, vp, _SZ, vp]),
+    "dg_probe_step_backward": (_I, [vp, _SZ, vp, vp] + [i32] * 8 + [vp] * 4),
     # evaluation and dense CRF
     "dg_segment_predict": (_I, [vp, vp] + [i32] * 4 + [vp, vp, i32, vp, i32, vp, i32, i32, vp, vp, i32, vp, vp, vp, _SZ, vp]),
     "dg_segment_labels": (_I, [vp, vp] + [i32] * 4 + [vp, vp, i32, vp] + [i32] * 3 + [vp] * 5 + [i32, i32] + [vp] * 4 + [vp, _SZ, vp]),

@@ -2,7 +2,7 @@
 // dg_seg_labels.hip, dg_crf.hip, dg_metrics.hip).  Host-side only: argument checks and kernel launches on the caller's stream.
 #include "dg_api.h"
 #include "dg_eval_args.h"
-#include "dg_head_args.h"     // the probes (dg_probe.hip)
+#include "dg_head_args.h"     // the probes (dg_probe.hip, dg_probe_step.hip)
 #include "dg_aux_args.h"      // dg_launch_confusion (dg_metrics.hip)
 
 extern "C" int dg_confusion_update(const int64_t* preds, const int64_t* target, int64_t count, int32_t n_classes,
@@ -57,6 +57,46 @@ extern "C" int dg_probe_ce_backward(const float* logits, const int64_t* label, c
     if (!logits || !label || !out3 || !grad_loss || !grad_logits) return fail(DG_ERR_INVALID, "null pointer");
     DgProbeCeArgs a{logits, label, nullptr, grad_loss, out3, grad_logits, B, n, h, w, H, W};
     DG_HIP(dg_launch_probe_ce_bwd(a, static_cast<hipStream_t>(stream_)));
+    return DG_OK;
+}
+
+// ---- the fused probe step (dg_probe_step.hip): the plan refuses in front of any launch
+static int probe_step_check(const char* who, int32_t B, int32_t D, int32_t n, int32_t m, int32_t h, int32_t w, int32_t H, int32_t W,
+                            DgProbeStepPlan& pl) {
+    if (B < 1 || D < 1 || n < 1 || m < 1 || h < 1 || w < 1 || H < 1 || W < 1) return fail(DG_ERR_INVALID, "%s: bad dimensions", who);
+    if (const char* why = dg_probe_step_plan(B, D, n, m, h, w, H, W, pl))
+        return fail(DG_ERR_UNSUPPORTED, "%s: %s (B=%d D=%d n_lin=%d n_clu=%d h=%d w=%d H=%d W=%d)", who, why, B, D, n, m, h, w, H, W);
+    return DG_OK;
+}
+extern "C" size_t dg_probe_step_workspace_bytes(int32_t B, int32_t D, int32_t n_lin, int32_t n_clu, int32_t h, int32_t w, int32_t H, int32_t W) {
+    DgProbeStepPlan pl;
+    if (probe_step_check("probe step", B, D, n_lin, n_clu, h, w, H, W, pl)) return 0;
+    return pl.floats * 4;
+}
+extern "C" int dg_probe_step_forward(const float* code, const int64_t* label, const float* lin_w, const float* lin_b, const float* clusters,
+                                     int32_t B, int32_t D, int32_t n_lin, int32_t n_clu, int32_t h, int32_t w, int32_t H, int32_t W,
+                                     float* out3, void* workspace, size_t workspace_bytes, dg_stream_t stream_) {
+    DgProbeStepPlan pl;
+    if (int rc = probe_step_check("probe step forward", B, D, n_lin, n_clu, h, w, H, W, pl)) return rc;
+    if (!code || !label || !lin_w || !clusters || !out3 || !workspace) return fail(DG_ERR_INVALID, "probe step forward: null pointer");
+    if (int rc = check_aligned("probe step forward", {code, lin_w, lin_b, clusters, out3}, workspace)) return rc;
+    if (reinterpret_cast<uintptr_t>(label) % 8) return fail(DG_ERR_INVALID, "probe step forward: label must be 8-byte aligned");
+    if (int rc = check_workspace("probe step forward", workspace_bytes, pl.floats * 4, "dg_probe_step_workspace_bytes")) return rc;
+    DgProbeStepArgs a{code, label, lin_w, lin_b, clusters, static_cast<float*>(workspace), out3, B, D, n_lin, n_clu, h, w, H, W};
+    DG_HIP(dg_launch_probe_step_fwd(a, pl, static_cast<hipStream_t>(stream_)));
+    return DG_OK;
+}
+extern "C" int dg_probe_step_backward(const void* workspace, size_t workspace_bytes, const float* grad_linear, const float* grad_cluster,
+                                      int32_t B, int32_t D, int32_t n_lin, int32_t n_clu, int32_t h, int32_t w, int32_t H, int32_t W,
+                                      float* grad_w, float* grad_b, float* grad_clusters, dg_stream_t stream_) {
+    DgProbeStepPlan pl;
+    if (int rc = probe_step_check("probe step backward", B, D, n_lin, n_clu, h, w, H, W, pl)) return rc;
+    if (!workspace || !grad_linear || !grad_cluster || !grad_w || !grad_b || !grad_clusters)
+        return fail(DG_ERR_INVALID, "probe step backward: null pointer");
+    if (int rc = check_aligned("probe step backward", {grad_linear, grad_cluster, grad_w, grad_b, grad_clusters}, workspace)) return rc;
+    if (int rc = check_workspace("probe step backward", workspace_bytes, pl.floats * 4, "dg_probe_step_workspace_bytes")) return rc;
+    DG_HIP(dg_launch_probe_step_bwd(static_cast<const float*>(workspace), pl, grad_linear, grad_cluster, D, n_lin, n_clu, grad_w, grad_b,
+                                    grad_clusters, static_cast<hipStream_t>(stream_)));
     return DG_OK;
 }
 

@@ -163,3 +163,40 @@ hipError_t dg_launch_cluster_fwd(const DgClusterArgs& a, float* loss_out, hipStr
 hipError_t dg_launch_cluster_bwd(const DgClusterBwdArgs& a, hipStream_t s);
 hipError_t dg_launch_probe_ce_fwd(const DgProbeCeArgs& a, float* out3, hipStream_t s);
 hipError_t dg_launch_probe_ce_bwd(const DgProbeCeArgs& a, hipStream_t s);
+
+// ---- the fused probe step (dg_probe_step.hip; both probes of src/train_segmentation.py:421-444 on the detached code, their
+// parameter gradients formed in the forward)
+struct DgProbeStepArgs {
+    const float* code;       // (B, D, h, w), detached
+    const int64_t* label;    // (B, H, W)
+    const float* lin_w;      // (n, D) the linear probe's 1 x 1 convolution
+    const float* lin_b;      // (n) or null
+    const float* clusters;   // (m, D) the cluster probe's centres
+    float* ws;               // the workspace (DgProbeStepPlan)
+    float* out3;             // [3] = {linear loss, cluster loss, labelled pixels}
+    int32_t B, D, n, m, h, w, H, W;
+};
+// The workspace's sections (offsets in floats, each a multiple of 4) and the launches' grids and LDS, for one shape.  P = h w, R = n + m.
+//   logits (B,n,P)  the linear probe at feature resolution            ptop, pbot (B,n,P)  the unscaled d logits a feature row receives
+//   inv, arg (B,P)  1 / |code| and the winning centre (int32)         from the label rows whose upper tap is that row / the row above
+//   part_pos [chunks]  the position pass's partial cluster losses     part_lab [B h][2]  per (image, feature row): loss sum, count (int32)
+//   part_red [splits][R][D + 1] doubles  the reduction pass's partial products
+//   grads [n D + n + m D] doubles  d W, d b, d clusters for upstream gradients of 1: what the backward scales
+struct DgProbeStepPlan {
+    size_t o_logits, o_ptop, o_pbot, o_inv, o_arg, o_part_pos, o_part_lab, o_part_red, o_grads, floats;
+    int32_t R4, DC4, cpi, chunks, splits, smem_pos, smem_label, smem_reduce;     // cpi: 64-position chunks per image
+    __host__ __device__ float* logits(float* ws) const { return ws + o_logits; }
+    __host__ __device__ float* ptop(float* ws) const { return ws + o_ptop; }
+    __host__ __device__ float* pbot(float* ws) const { return ws + o_pbot; }
+    __host__ __device__ float* inv(float* ws) const { return ws + o_inv; }
+    __host__ __device__ int32_t* arg(float* ws) const { return reinterpret_cast<int32_t*>(ws + o_arg); }
+    __host__ __device__ float* part_pos(float* ws) const { return ws + o_part_pos; }
+    __host__ __device__ float* part_lab(float* ws) const { return ws + o_part_lab; }
+    __host__ __device__ double* part_red(float* ws) const { return reinterpret_cast<double*>(ws + o_part_red); }
+    __host__ __device__ double* grads(float* ws) const { return reinterpret_cast<double*>(ws + o_grads); }
+};
+// null: the shape is served and `pl` is filled; else the reason it is refused (nothing is launched)
+const char* dg_probe_step_plan(int B, int D, int n, int m, int h, int w, int H, int W, DgProbeStepPlan& pl);
+hipError_t dg_launch_probe_step_fwd(const DgProbeStepArgs& a, const DgProbeStepPlan& pl, hipStream_t s);
+hipError_t dg_launch_probe_step_bwd(const float* ws, const DgProbeStepPlan& pl, const float* g_lin, const float* g_clu, int D, int n, int m,
+                                    float* gw, float* gb, float* gc, hipStream_t s);

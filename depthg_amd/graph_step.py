@@ -112,7 +112,9 @@ class GraphedTrainStep:
         return (cfg,) if loss_cfg is cfg else (cfg, loss_cfg)
 
     def capture_key(self):
-        return tuple(getattr(c, k, None) for c in self._cfgs() for k in CAPTURE_KEY) + (bool(self.model.training), bool(self.model.net.training))
+        # (cfg.dg_fused_probes decides launches too, but the segmenter reads it once, at construction: its attribute is the key)
+        return tuple(getattr(c, k, None) for c in self._cfgs() for k in CAPTURE_KEY) + \
+            (bool(self.model.training), bool(self.model.net.training), bool(getattr(self.model, "fused_probes", False)))
 
     def _forced_eager(self, global_step):
         return histogram_step(self.model.cfg, global_step) or self._reset_step(global_step)

@@ -8,10 +8,14 @@
     ClusterLookup       src/modules.py:647-675 (dg_cluster_lookup_forward / _backward)
     probe_cross_entropy the linear probe's loss, src/train_segmentation.py:427-434: resize of the probe's logits to the label
                         resolution + cross entropy over the labelled pixels in one kernel (dg_probe_ce_forward / _backward)
-All arithmetic runs in the library; CPU tensors raise (there is no eager path).
+    fused_probe_losses  both probes of the training step on the detached code as ONE operation (cfg.dg_fused_probes;
+                        src/train_segmentation.py:421-444): the two losses and, already in the forward, the gradients of the
+                        three probe parameters (dg_probe_step_forward / _backward).  On CPU tensors: the plain torch chain.
+All arithmetic runs in the library; CPU tensors raise (there is no eager path) - fused_probe_losses apart.
 """
 import torch
 import torch.nn as nn
+import torch.nn.functional as F
 
 from . import _lib
 from .ops import DeferredDropout, _empty, _f32c, _on_gpu, _ptr, _stream
@@ -361,3 +365,98 @@ def probe_cross_entropy(linear_logits, label):
     """`CrossEntropyLoss()(interpolate(linear_logits, label.shape[-2:], 'bilinear', align_corners=False)[mask], label[mask])`
     with mask = (label >= 0) & (label < n_classes)  (src/train_segmentation.py:421-434), without the label-resolution logits."""
     return _ProbeCeFunction.apply(linear_logits, label)
+
+
+PROBE_STEP_MAX_D, PROBE_STEP_MAX_N = 128, 64          # dg_probe_step_forward's limits (include/depthg_corr.h)
+
+
+def _probe_step_args(code, label, weight, bias, clusters):
+    """The arguments of fused_probe_losses, checked -> (label as (B,H,W), (B, D, n_lin, n_clu, h, w, H, W): the C entries' order)."""
+    if code.requires_grad:
+        raise RuntimeError("depthg_amd: fused_probe_losses received a code that requires grad: the fused probe step has no gradient "
+                           "with respect to the code (the probes train on code.detach(), src/train_segmentation.py:421) - detach it, "
+                           "or take the unfused route: probe_cross_entropy(linear_probe(code), label) and ClusterLookup(code, None)")
+    if code.dim() != 4:
+        raise ValueError(f"depthg_amd: fused_probe_losses: code must be (B, D, h, w), got {tuple(code.shape)}")
+    B, D, h, w = code.shape
+    if weight.dim() not in (2, 4) or weight.shape[1] != D or weight.numel() != weight.shape[0] * D:
+        raise ValueError(f"depthg_amd: fused_probe_losses: weight must be (n_lin, {D}) or (n_lin, {D}, 1, 1), got {tuple(weight.shape)}")
+    n = weight.shape[0]
+    if bias is None or tuple(bias.shape) != (n,):
+        raise ValueError(f"depthg_amd: fused_probe_losses: bias must be ({n},), got {None if bias is None else tuple(bias.shape)}")
+    if clusters.dim() != 2 or clusters.shape[1] != D:
+        raise ValueError(f"depthg_amd: fused_probe_losses: clusters must be (n_clu, {D}), got {tuple(clusters.shape)}")
+    m = clusters.shape[0]
+    if label.dim() == 4 and label.shape[1] == 1:
+        label = label[:, 0]
+    if label.dim() != 3:
+        raise ValueError(f"depthg_amd: fused_probe_losses: label must be (B, H, W) or (B, 1, H, W), got {tuple(label.shape)}")
+    if label.shape[0] != B:
+        raise ValueError(f"depthg_amd: fused_probe_losses: label holds {label.shape[0]} images, code {B}")
+    if D > PROBE_STEP_MAX_D:
+        raise RuntimeError(f"depthg_amd: fused_probe_losses serves D <= {PROBE_STEP_MAX_D} (got {D}); take the unfused route")
+    if n > PROBE_STEP_MAX_N or m > PROBE_STEP_MAX_N:
+        raise RuntimeError(f"depthg_amd: fused_probe_losses serves n_lin <= {PROBE_STEP_MAX_N} and n_clu <= {PROBE_STEP_MAX_N} "
+                           f"(got {n} and {m}); take the unfused route")
+    H, W = label.shape[-2:]
+    return label, (B, D, n, m, h, w, H, W)
+
+
+def _probe_losses_torch(code, label, weight, bias, clusters):
+    """The reference's chain (src/train_segmentation.py:421-444, src/modules.py:664-675 with alpha None) in plain torch."""
+    n, D = weight.shape[0], code.shape[1]
+    logits = F.interpolate(F.conv2d(code, weight.reshape(n, D, 1, 1), bias), label.shape[-2:], mode="bilinear", align_corners=False)
+    flat, lab = logits.permute(0, 2, 3, 1).reshape(-1, n), label.reshape(-1)
+    mask = (lab >= 0) & (lab < n)
+    linear_loss = F.cross_entropy(flat[mask], lab[mask])
+    inner = torch.einsum("bchw,nc->bnhw", F.normalize(code, dim=1), F.normalize(clusters, dim=1))
+    probs = F.one_hot(torch.argmax(inner, dim=1), clusters.shape[0]).permute(0, 3, 1, 2).to(torch.float32)
+    return linear_loss, -(probs * inner).sum(1).mean()
+
+
+class _ProbeStepFunction(torch.autograd.Function):
+    """dg_probe_step_forward / _backward: the code is detached, so the forward leaves the three parameter gradients - for upstream
+    gradients of 1 - in its workspace and the backward is one launch that scales them by the two scalars autograd hands it."""
+
+    @staticmethod
+    def forward(ctx, code, label, weight, bias, clusters):
+        lib = _lib.load()
+        label, dims = _probe_step_args(code, label, weight, bias, clusters)
+        B, D, n, m, h, w, H, W = dims
+        cc, ww, bb, cl = (_f32c(t, name) for t, name in ((code, "code"), (weight, "weight"), (bias, "bias"), (clusters, "clusters")))
+        lab = _on_gpu(label, "label").detach().to(torch.int64).contiguous()
+        dev = cc.device
+        nb = lib.dg_probe_step_workspace_bytes(*dims)
+        if nb == 0:
+            _lib.check(-2, "dg_probe_step_workspace_bytes")
+        ws = _empty(nb, torch.uint8, dev)
+        out3 = _empty((3,), torch.float32, dev)
+        rc = lib.dg_probe_step_forward(_ptr(cc), _ptr(lab), _ptr(ww), _ptr(bb), _ptr(cl), *dims, _ptr(out3), _ptr(ws), nb, _stream(dev))
+        _lib.check(rc, "dg_probe_step_forward")
+        ctx.dims, ctx.shapes = dims, (weight.shape, bias.shape, clusters.shape)
+        ctx.save_for_backward(ws)
+        return out3[0], out3[1]
+
+    @staticmethod
+    def backward(ctx, g_lin, g_clu):
+        lib = _lib.load()
+        ws, = ctx.saved_tensors
+        B, D, n, m, h, w, H, W = ctx.dims
+        dev = ws.device
+        gl, gc = _f32c(g_lin, "grad_linear_loss").reshape(1), _f32c(g_clu, "grad_cluster_loss").reshape(1)
+        gw, gb, gk = _empty((n, D), torch.float32, dev), _empty((n,), torch.float32, dev), _empty((m, D), torch.float32, dev)
+        rc = lib.dg_probe_step_backward(_ptr(ws), ws.numel(), _ptr(gl), _ptr(gc), *ctx.dims, _ptr(gw), _ptr(gb), _ptr(gk), _stream(dev))
+        _lib.check(rc, "dg_probe_step_backward")
+        return None, None, gw.reshape(ctx.shapes[0]), gb, gk
+
+
+def fused_probe_losses(code, label, weight, bias, clusters):
+    """(linear_loss, cluster_loss) of the two probes the training step trains on the detached code (src/train_segmentation.py:421-444):
+    `CrossEntropyLoss()(interpolate(conv2d(code, weight, bias), label.shape[-2:], 'bilinear', align_corners=False)[mask], label[mask])`
+    with mask = (label >= 0) & (label < n_lin), and ClusterLookup(code, None)'s loss for the centres `clusters` (n_clu, D) - one
+    operation whose backward hands `weight`, `bias` and `clusters` their gradients and the code none.  A code that requires grad is
+    refused.  GPU tensors: dg_probe_step_forward / _backward (D <= 128, n_lin and n_clu <= 64); CPU tensors: the torch chain."""
+    if not code.is_cuda:
+        label, _ = _probe_step_args(code, label, weight, bias, clusters)
+        return _probe_losses_torch(code.to(torch.float32), label.to(torch.int64), weight, bias, clusters)
+    return _ProbeStepFunction.apply(code, label, weight, bias, clusters)

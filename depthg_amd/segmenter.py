@@ -13,7 +13,7 @@ Mirrors, with the reference's names, parameter layout and arithmetic:
                             on_validation_epoch_end (:471-535), evaluate_batch (src/eval_segmentation.py:146-170) and segment(img),
                             the label-free route of src/demo_segmentation.py:59-78 (depthg_amd/demo.py is its command line).
                             cfg.arch == "dino_depth" (:104-106): the depth-guided featurizer, use_depth forced on.
-ProjectionHead / ClusterLookup (src/modules.py:647-675) / probe_cross_entropy live in depthg_amd/head.py and are re-exported here.
+ProjectionHead / ClusterLookup (src/modules.py:647-675) / probe_cross_entropy / fused_probe_losses live in depthg_amd/head.py and are re-exported here.
 
 training_step is a driver over stages whose switches are all decided once, in front of the step, by training.step_plan (the featurizer
 route - pair, depth or single -, whether it starts from cached features, the terms that run, this step number's histogram and
@@ -35,7 +35,7 @@ from .crf_loss import ContrastiveCRFLoss
 from .depth_decay import legacy_decay_step
 from .evaluation import predict_and_score, segment
 from .featurizer import DepthGuidance, DinoFeaturizer, DinoFeaturizerWithDepth, FrozenBackboneFeaturizer
-from .head import ClusterLookup, ProjectionHead, probe_cross_entropy
+from .head import ClusterLookup, ProjectionHead, fused_probe_losses, probe_cross_entropy
 from .lhp import LocalHiddenPositiveProjection, OriginalLocalHiddenPositiveProjection
 from .loss import ContrastiveCorrelationLoss, DepthContrastiveCorrelationLoss
 from .metrics import UnsupervisedMetrics
@@ -142,6 +142,9 @@ class UnsupervisedSegmenter(nn.Module):
         if getattr(cfg, "lhp", False):                                                 # :82-87
             original = "lhp_original" in str(getattr(cfg, "experiment_name", ""))
             self.lhp_module = OriginalLocalHiddenPositiveProjection(cfg) if original else LocalHiddenPositiveProjection(cfg)
+        # cfg.dg_fused_probes (build-side key, absent or False by default): _probe_terms makes ONE call, head.fused_probe_losses, on
+        # the detached code instead of the convolution and the two probe operations.  Read here, once: the step's plan does not carry it.
+        self.fused_probes = bool(getattr(cfg, "dg_fused_probes", False))
         self.automatic_optimization = False                                           # :139
         self.global_step = 0
         self._optims = None
@@ -398,6 +401,13 @@ class UnsupervisedSegmenter(nn.Module):
 
     def _probe_terms(self, code, label, loss, logs):
         """The probes on the detached code (:421-444); logs both terms and the total.  Returns the loss."""
+        if self.fused_probes:
+            # both probes, and already their parameter gradients, in one HIP forward (no clone: the operation only reads the code)
+            linear_loss, cluster_loss = fused_probe_losses(code.detach(), label, self.linear_probe.weight, self.linear_probe.bias,
+                                                           self.cluster_probe.clusters)
+            loss = loss + linear_loss + cluster_loss
+            logs.update({"loss/linear": linear_loss.detach(), "loss/cluster": cluster_loss.detach(), "loss/total": loss.detach()})
+            return loss
         detached_code = code.detach().clone()
         # resize to the label resolution + masked cross entropy in one HIP kernel (the reference materialises the logits at label
         # resolution and three masks, :427-434); the cluster probe's similarity / arg-max / loss likewise
@@ -595,7 +605,10 @@ def default_segmenter_cfg(**over) -> SimpleNamespace:
         dg_val_feature_cache=None,
         # build-side: the cached step recorded in a hipGraph and replayed, its batches drawn on the device (graph_step.GraphedTrainStep
         # over epoch.DeviceEpoch; the train command's --graph-step).  training_step itself does not read the key
-        dg_graph_step=False)
+        dg_graph_step=False,
+        # build-side: both probes of the step and their parameter gradients as one fused HIP operation on the detached code
+        # (head.fused_probe_losses; the train command's --fused-probes).  Read once, when the segmenter is constructed
+        dg_fused_probes=False)
     for k, v in over.items():
         setattr(cfg, k, v)
     return cfg

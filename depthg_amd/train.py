@@ -314,6 +314,8 @@ def main(argv=None) -> int:
                     help="record the cached training step in a hipGraph and replay it, the batches drawn on the device (sets dg_graph_step, and "
                          "dg_graph_safe and dg_fused_adam unless given); needs --feature-cache and --sample-cache; the short last batch of an "
                          "epoch is dropped")
+    ap.add_argument("--fused-probes", action="store_true",
+                    help="train the linear and the cluster probe through one fused HIP operation per step (sets dg_fused_probes)")
     ap.add_argument("overrides", nargs="*", help="cfg keys as key=value")
     args = ap.parse_args(argv)
     overrides = parse_overrides(args.overrides)
@@ -323,6 +325,8 @@ def main(argv=None) -> int:
         overrides["dg_feature_cache"] = args.feature_cache
     if args.val_feature_cache is not None:
         overrides["dg_val_feature_cache"] = args.val_feature_cache
+    if args.fused_probes:
+        overrides["dg_fused_probes"] = True
     if args.graph_step:
         if args.feature_cache is None or not args.sample_cache:
             ap.error("--graph-step replays the CACHED step: give --feature-cache {float32,float16,bfloat16} and --sample-cache as well")

@@ -573,6 +573,30 @@ int dg_probe_ce_backward(const float* logits, const int64_t* label, const float*
                          int32_t h, int32_t w, int32_t H, int32_t W, float* grad_logits, dg_stream_t stream);
 
 /*
+ * The fused probe step: both probes the training step trains on the DETACHED code (src/train_segmentation.py:421-444) in one call -
+ * linear_loss = cross entropy of interpolate(lin_w . code + lin_b, (H,W), bilinear, align_corners=False) over the pixels with
+ * 0 <= label < n_lin (:427-434), cluster_loss = -mean over (B,P) of max_j <normalize(clusters)_j, normalize(code)> (ClusterLookup with
+ * alpha None, src/modules.py:664-675) - with the gradients of lin_w, lin_b and clusters.  The code receives no gradient, so the three
+ * are linear in the upstream scalars: the forward forms them for upstream gradients of 1 and keeps them in the workspace, the backward
+ * multiplies by the two scalars, which it reads on the device.
+ *  code : fp32 (B,D,h,w)   label : int64 (B,H,W)   lin_w : fp32 (n_lin,D)   lin_b : fp32 (n_lin) or NULL   clusters : fp32 (n_clu,D)
+ *  out3 : fp32 [3] out = {linear_loss, cluster_loss, labelled pixels}; no labelled pixel: linear_loss = 0 / 0 as dg_probe_ce_forward
+ *  workspace : dg_probe_step_workspace_bytes, 16-byte aligned; the backward reads what the forward of the same shape left in it
+ * dg_probe_step_backward: grad_linear, grad_cluster fp32 [1] (device) -> grad_w (n_lin,D), grad_b (n_lin), grad_clusters (n_clu,D),
+ * every element written.
+ * Limits (DG_ERR_UNSUPPORTED with the reason, before any launch; the sizer then returns 0): D <= 128, n_lin <= 64, n_clu <= 64,
+ * n_lin * w <= 4096, B*h*w <= 2^24, H*W <= 2^30; any H, W >= 1 (non-integer ratios included).  Four launches forward, one backward, on
+ * the caller's stream; no floating-point atomics: two calls give the same bits.
+ */
+size_t dg_probe_step_workspace_bytes(int32_t B, int32_t D, int32_t n_lin, int32_t n_clu, int32_t h, int32_t w, int32_t H, int32_t W);
+int dg_probe_step_forward(const float* code, const int64_t* label, const float* lin_w, const float* lin_b, const float* clusters,
+                          int32_t B, int32_t D, int32_t n_lin, int32_t n_clu, int32_t h, int32_t w, int32_t H, int32_t W,
+                          float* out3, void* workspace, size_t workspace_bytes, dg_stream_t stream);
+int dg_probe_step_backward(const void* workspace, size_t workspace_bytes, const float* grad_linear, const float* grad_cluster,
+                           int32_t B, int32_t D, int32_t n_lin, int32_t n_clu, int32_t h, int32_t w, int32_t H, int32_t W,
+                           float* grad_w, float* grad_b, float* grad_clusters, dg_stream_t stream);
+
+/*
  * The probes' predictions at label resolution and their confusion counts: validation_step (src/train_segmentation.py:471-499:
  * F.interpolate(code, label size, bilinear, align_corners=False) -> linear_probe -> argmax / cluster_probe(code, None) -> argmax ->
  * linear_metrics / cluster_metrics.update) and eval_segmentation.py:146-170 without the CRF (code = (code + code_flip.flip(3)) / 2

@@ -1,14 +1,16 @@
 """Times an epoch of cached training through the host-chosen route against the recorded one.
 
-    python scripts/graph_step_time.py [--out profiles/graph_step_time.jsonl] [--repeats 5] [--epochs 4] [--images 256] [--only a|b]
+    python scripts/graph_step_time.py [--out profiles/graph_step_time.jsonl] [--repeats 5] [--epochs 4] [--images 256] [--only a|b|c|bc] [--append]
 
 vit_small(8) with seeded random weights, a float16 feature cache and a sample cache of `--images` stub images (the folder of
 scripts/sample_cache_time.py), B = 32, 224 x 224, label and depth.  Two forms in one process, alternated inside each of `--repeats`
 repeats, `--epochs` epochs per sample, host clock between two device synchronisations:
     a_contrastive_batches   the parent's route: data.ContrastiveBatches (both caches) + training_step, cfg.dg_fused_adam
     b_graphed_train_step    epoch.DeviceEpoch + graph_step.GraphedTrainStep (cfg.dg_graph_step): begin_epoch() and step() per batch
-One JSON line per form: batches per second, median [min, max] over the repeats, and for (b) the recordings made and the share of
-steps that were replays.  --only b runs that form alone (for a kernel trace).
+    c_graphed_fused_probes  (b) with cfg.dg_fused_probes: both probes as one fused operation (only with --only c or --only bc)
+One JSON line per form: batches per second, median [min, max] over the repeats, and for (b), (c) the recordings made and the share of
+steps that were replays.  --only b runs that form alone (for a kernel trace); --only bc alternates (b) and (c); --append adds the
+lines to --out instead of replacing it.
 """
 import argparse
 import json
@@ -41,7 +43,8 @@ def main():
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--epochs", type=int, default=4)
     ap.add_argument("--images", type=int, default=256)
-    ap.add_argument("--only", choices=("a", "b"), default=None)
+    ap.add_argument("--only", choices=("a", "b", "c", "bc"), default=None)
+    ap.add_argument("--append", action="store_true")
     args = ap.parse_args()
     from depthg_amd import data
     from depthg_amd.epoch import DeviceEpoch
@@ -72,6 +75,19 @@ def main():
         epoch = DeviceEpoch(batches.nns, B, batches.num_neighbors, dev, shuffle=True, generator=torch.Generator().manual_seed(1))
         graphed = GraphedTrainStep(seg_b, epoch, cache, feats, label_dims=ds.label_dims)
         replays = [0, 0]
+        graphed_c, replays_c = None, [0, 0]
+        if args.only and "c" in args.only:
+            epoch_c = DeviceEpoch(batches.nns, B, batches.num_neighbors, dev, shuffle=True, generator=torch.Generator().manual_seed(1))
+            graphed_c = GraphedTrainStep(segmenter(dg_graph_safe=True, dg_graph_step=True, dg_fused_probes=True), epoch_c, cache, feats,
+                                         label_dims=ds.label_dims)
+
+        def form_c():
+            for _ in range(args.epochs):
+                epoch_c.begin_epoch()
+                for _ in range(epoch_c.steps_per_epoch):
+                    graphed_c.step()
+                    replays_c[0] += int(graphed_c.graphed)
+                    replays_c[1] += 1
 
         def form_a():
             for _ in range(args.epochs):
@@ -87,11 +103,14 @@ def main():
                     replays[1] += 1
 
         forms = {"a_contrastive_batches": (form_a, len(batches)), "b_graphed_train_step": (form_b, epoch.steps_per_epoch)}
+        if graphed_c is not None:
+            forms["c_graphed_fused_probes"] = (form_c, epoch.steps_per_epoch)
         if args.only:
-            forms = {k: v for k, v in forms.items() if k.startswith(args.only + "_")}
+            forms = {k: v for k, v in forms.items() if k[0] in args.only}
         for fn, _ in forms.values():                # warm-up: allocator, kernel attributes, clocks, the first recording
             timed(fn)
         replays[:] = [0, 0]
+        replays_c[:] = [0, 0]
         samples = {name: [] for name in forms}
         for _ in range(args.repeats):
             for name, (fn, per_epoch) in forms.items():
@@ -103,9 +122,11 @@ def main():
                     "images": N, "batch_size": B, "ms_per_batch_at_median": round(1e3 / statistics.median(rate), 4)}
             if name.startswith("b_"):
                 line.update({"recordings": graphed.captures, "replayed_steps": replays[0], "timed_steps": replays[1]})
+            if name.startswith("c_"):
+                line.update({"recordings": graphed_c.captures, "replayed_steps": replays_c[0], "timed_steps": replays_c[1]})
             lines.append(line)
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as out:
+    with open(args.out, "a" if args.append else "w") as out:
         for line in lines:
             line["device"] = torch.cuda.get_device_name(0)
             print(json.dumps(line))
