@@ -200,6 +200,34 @@ extern "C" int dg_fps_coords(const float* depth, const float* depth_pos, int32_t
     return DG_OK;
 }
 
+extern "C" size_t dg_fps_feats_workspace_bytes(int32_t B, int32_t h, int32_t w) { return dg_fps_workspace_bytes(B, h, w); }      // the pooled depth maps
+
+// dg_fps_coords with the feature term of fps_depth_feats (src/modules.py:1124-1180); depth_pos and feats_pos come together or not at all
+extern "C" int dg_fps_feats_coords(const float* depth, const float* depth_pos, const float* feats, const float* feats_pos, int32_t B, int32_t C,
+                                   int32_t depth_h, int32_t depth_w, int32_t h, int32_t w, int32_t S, float* out_coords, int32_t* out_inds,
+                                   void* workspace, size_t workspace_bytes, dg_stream_t stream_) {
+    if (!depth || !feats || !out_coords || !workspace) return fail(DG_ERR_INVALID, "dg_fps_feats_coords: null pointer");
+    if ((depth_pos == nullptr) != (feats_pos == nullptr)) return fail(DG_ERR_INVALID, "dg_fps_feats_coords: depth_pos and feats_pos come together");
+    if (((uintptr_t)depth | (uintptr_t)depth_pos | (uintptr_t)feats | (uintptr_t)feats_pos | (uintptr_t)out_coords | (uintptr_t)out_inds |
+         (uintptr_t)workspace) & 3)
+        return fail(DG_ERR_INVALID, "dg_fps_feats_coords: pointers must be 4-byte aligned");
+    if (B < 1 || B > (1 << 20) || h < 1 || w < 1 || S < 1 || depth_h < h || depth_w < w) return fail(DG_ERR_INVALID, "bad FPS dimensions");
+    if (C < 1) return fail(DG_ERR_INVALID, "dg_fps_feats_coords: C=%d feature channels", C);
+    const int32_t nB = depth_pos ? 2 * B : B;
+    if ((size_t)h * w > 4096) return fail(DG_ERR_UNSUPPORTED, "feature map %dx%d too large for the sampler (max 4096 pixels)", h, w);
+    if ((int64_t)S * S > (int64_t)h * w) return fail(DG_ERR_INVALID, "cannot sample %lld points from a %dx%d map", (long long)S * S, h, w);
+    if (C > 16384) return fail(DG_ERR_UNSUPPORTED, "dg_fps_feats_coords: C=%d > 16384 feature channels (the last point's row lives in LDS)", C);
+    if (!dg_pool_depth_fits(depth_h, depth_w, h))
+        return fail(DG_ERR_UNSUPPORTED, "dg_fps_feats_coords: the %d-wide depth rows of one pooled row exceed 64 KB of LDS", depth_w);
+    if (workspace_bytes < (size_t)nB * h * w * 4) return fail(DG_ERR_WORKSPACE, "dg_fps_feats_coords: workspace too small (dg_fps_feats_workspace_bytes)");
+    const uint32_t bits = 0x404f54cbu;            // 2*tan(90/2 rad), the reference's float32 factor (dg_fps_coords)
+    float factor;
+    memcpy(&factor, &bits, 4);
+    DG_HIP(dg_launch_fps_feats(depth, depth_pos, feats, feats_pos, B, nB, C, depth_h, depth_w, h, w, S, factor, out_coords, out_inds,
+                               static_cast<float*>(workspace), static_cast<hipStream_t>(stream_)));
+    return DG_OK;
+}
+
 // ---- the optimisation step's Adams (dg_optim.hip)
 extern "C" int dg_adam_step(const dg_adam_seg* segs, int32_t n_seg, const dg_adam_group* groups, int32_t n_groups, int32_t device_steps,
                             void* tickets, dg_stream_t stream_) {

@@ -646,5 +646,10 @@ hipError_t dg_launch_rand_coords_state(unsigned long long* state, float* out, in
 // (B images in all; the first Ba from `depth`, the rest from `depth_b`)
 hipError_t dg_launch_fps(const float* depth, const float* depth_b, int Ba, int B, int H, int W, int h, int w, int S, float factor,
                          float* out_coords, int32_t* out_inds, float* pooled_ws, hipStream_t s);
+// ... with the feature term (k_fps_feats; `feats` / `feats_b` (., C, h, w) beside the depth maps).  The pooling pre-pass must fit:
+bool dg_pool_depth_fits(int H, int W, int h);
+hipError_t dg_launch_fps_feats(const float* depth, const float* depth_b, const float* feats, const float* feats_b, int Ba, int B, int C,
+                               int H, int W, int h, int w, int S, float factor, float* out_coords, int32_t* out_inds, float* pooled,
+                               hipStream_t s);
 hipError_t dg_launch_sampled_sumsq(const float* feats, const float* coords, const int64_t* srcidx, float* out, int B, int C, int h, int w, int S, int Sh, int accumulate, hipStream_t s);
 hipError_t dg_launch_normalize_split(const float* src, int B, int C, int P, int nchunks, int chunk_c, float* const* dst, hipStream_t s);

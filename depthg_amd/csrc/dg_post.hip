@@ -1153,13 +1153,19 @@ __global__ __launch_bounds__(256) void k_pool_depth(const float* __restrict__ de
     for (int j = tid; j < w; j += 256) pooled[((size_t)n * h + i) * w + j] = fps_pool_lds(st, ys, H, W, h, w, i, j);
 }
 
+// The pooling pre-pass of both samplers (k_fps_coords, k_fps_feats): the image rows of one pooled row must fit 64 KB of LDS.
+bool dg_pool_depth_fits(int H, int W, int h) { return (size_t)((H + h - 1) / h + 1) * W * 4 <= 64 * 1024; }
+static hipError_t launch_pool_depth(const float* depth, const float* depth_b, int Ba, int B, int H, int W, int h, int w, float* pooled, hipStream_t s) {
+    const int win_rows = (H + h - 1) / h + 1;
+    hipLaunchKernelGGL(k_pool_depth, dim3(h, B), dim3(256), win_rows * W * 4, s, depth, depth_b, Ba, H, W, h, w, pooled);
+    return hipGetLastError();
+}
+
 hipError_t dg_launch_fps(const float* depth, const float* depth_b, int Ba, int B, int H, int W, int h, int w, int S, float factor,
                          float* out_coords, int32_t* out_inds, float* pooled_ws, hipStream_t s) {
     if (pooled_ws) {
-        const int win_rows = (H + h - 1) / h + 1;
-        if ((size_t)win_rows * W * 4 <= 64 * 1024) {
-            hipLaunchKernelGGL(k_pool_depth, dim3(h, B), dim3(256), win_rows * W * 4, s, depth, depth_b, Ba, H, W, h, w, pooled_ws);
-            const hipError_t e = hipGetLastError();
+        if (dg_pool_depth_fits(H, W, h)) {
+            const hipError_t e = launch_pool_depth(depth, depth_b, Ba, B, H, W, h, w, pooled_ws, s);
             if (e != hipSuccess) return e;
         } else {
             pooled_ws = nullptr;
@@ -1184,6 +1190,181 @@ hipError_t dg_launch_fps(const float* depth, const float* depth_b, int Ba, int B
     if (h * w <= 4 * FPS_THREADS) return launch(k_fps_coords<4>);
     if (h * w <= 8 * FPS_THREADS) return launch(k_fps_coords<8>);        // (4096 pixels: the sampler's limit, dg_api_aux.hip fps_entry)
     return hipErrorInvalidValue;
+}
+
+// ------------------------------------------------------------------------------------------
+// Feature-aware FPS (cfg.dg_fps_feats): farthest_point_sampling_depth (src/modules.py:999-1037) with its fps call replaced by
+// fps_depth_feats (:1124-1180), the sampler the reference wrote for depth_sampling = 'fps_depth_feat' and never called.  One block
+// per image; the pooled depth comes from k_pool_depth (the pre-pass the depth-only sampler uses), the features stay (C, h*w) in
+// place.  Per round, with `last` the point selected before it and over the points not yet selected:
+//     pd_j = |p_last - p_j|^2 (numpy's float32 operations), fd_j = sum_c (f_last,c - f_j,c)^2 (direct fp32 form, channel order),
+//     d_j = pd_j / max pd + fd_j / max fd, dists_j = min(dists_j, d_j), next = first arg-max of dists.
+// A maximum of 0 (every point left coincides with the last one in space, or in feature space) makes the reference divide 0 / 0
+// and select on NaNs; here that term contributes 0.
+// A thread owns the points tid + FPSF_THREADS * k: a wave reads 256 contiguous bytes of a channel plane per load, the last point's
+// C values are read from LDS (one address per wave: a broadcast).  Points, running distances and the selected flags stay in
+// registers.  Three barriers per round: behind the last point's features, behind the waves' two maxima, behind the waves' arg-max
+// keys (distance bits : 0x7fffffff - index, so the larger key is the larger distance, then the lower index).  No atomics: every
+// wave writes its own slot and every thread folds the 16 slots.
+#define FPSF_THREADS 1024
+#define FPSF_WAVES (FPSF_THREADS / 64)
+
+__device__ __forceinline__ long long fpsf_wave_max_key(long long v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const long long t = __shfl_xor(v, o, 64);
+        v = t > v ? t : v;
+    }
+    return v;
+}
+
+template <int NPT>       // points per thread: h*w <= NPT * FPSF_THREADS
+__global__ __launch_bounds__(FPSF_THREADS) void k_fps_feats(const float* __restrict__ pooled, const float* __restrict__ feats,
+                                                            const float* __restrict__ feats_b, int Ba, int C, int h, int w, int S, float factor,
+                                                            float* __restrict__ out_coords, int32_t* __restrict__ out_inds) {
+    constexpr int UNR = NPT == 4 ? 4 : 8;                  // channels whose loads are requested before the first is used
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    __shared__ float smaxp[FPSF_WAVES], smaxf[FPSF_WAVES], lastp[4];
+    __shared__ long long skey[FPSF_WAVES];
+    const int HW = h * w, nsel = S * S, Cpad = (C + 3) & ~3;
+    float* fl = sm;                                                   // [Cpad] the last point's features
+    int* order = reinterpret_cast<int*>(fl + Cpad);                   // [nsel] selection order
+    uint32_t* selbits = reinterpret_cast<uint32_t*>(order + nsel);    // [NPT * FPSF_THREADS / 32] selected set as a bit mask
+    const int n = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    // (images Ba.. of the launch come from a second tensor: feats and feats_pos of one step, dg_fps_feats_coords)
+    const float* f = n < Ba ? feats + (size_t)n * C * HW : feats_b + (size_t)(n - Ba) * C * HW;
+    const float* pd = pooled + (size_t)n * HW;
+
+    // depth2points of the pooled depth, as k_fps_coords forms it; a slot past the map is never live (and reads point 0's features)
+    float px[NPT], py[NPT], pz[NPT], dist[NPT];
+    int fidx[NPT];
+    uint32_t valid = 0u, selmask = 0u;
+#pragma unroll
+    for (int k = 0; k < NPT; ++k) {
+        const int idx = tid + FPSF_THREADS * k;
+        const int i = idx / w, j = idx - i * w;
+        px[k] = py[k] = pz[k] = 0.f;
+        dist[k] = __builtin_inff();
+        fidx[k] = idx < HW ? idx : 0;
+        if (idx < HW) {
+            const float dv = pd[idx];
+            const float fd = __fmul_rn(factor, dv);
+            py[k] = __fdiv_rn(__fmul_rn(fd, __fsub_rn((float)i, (float)h / 2.0f)), (float)h);
+            px[k] = __fdiv_rn(__fmul_rn(fd, __fsub_rn((float)j, (float)w / 2.0f)), (float)w);
+            pz[k] = __fmul_rn(-dv, 5.0f);
+            valid |= 1u << k;
+        }
+    }
+    int last = 0;
+    if (tid == 0) order[0] = 0;
+    for (int it = 1; it < nsel; ++it) {
+        // the last selection leaves the remainder and hands out its coordinates and its C feature values
+#pragma unroll
+        for (int k = 0; k < NPT; ++k) {
+            if (tid + FPSF_THREADS * k == last) {
+                selmask |= 1u << k;
+                lastp[0] = px[k]; lastp[1] = py[k]; lastp[2] = pz[k];
+            }
+        }
+        for (int c = tid; c < C; c += FPSF_THREADS) fl[c] = f[c * HW + last];
+        __syncthreads();
+        const uint32_t live = valid & ~selmask;
+        const float lx = lastp[0], ly = lastp[1], lz = lastp[2];
+        float acc[NPT];
+#pragma unroll
+        for (int k = 0; k < NPT; ++k) acc[k] = 0.f;
+        int c0 = 0;
+        for (; c0 + UNR <= C; c0 += UNR) {
+            float v[UNR][NPT];
+#pragma unroll
+            for (int u = 0; u < UNR; ++u)
+#pragma unroll
+                for (int k = 0; k < NPT; ++k) v[u][k] = f[(c0 + u) * HW + fidx[k]];
+#pragma unroll
+            for (int u = 0; u < UNR; ++u) {
+                const float l = fl[c0 + u];
+#pragma unroll
+                for (int k = 0; k < NPT; ++k) { const float df = l - v[u][k]; acc[k] = fmaf(df, df, acc[k]); }
+            }
+        }
+        for (; c0 < C; ++c0) {
+            const float l = fl[c0];
+#pragma unroll
+            for (int k = 0; k < NPT; ++k) { const float df = l - f[c0 * HW + fidx[k]]; acc[k] = fmaf(df, df, acc[k]); }
+        }
+        float pdist[NPT], mp = -1.f, mf = -1.f;
+#pragma unroll
+        for (int k = 0; k < NPT; ++k) {
+            const float dx = __fsub_rn(lx, px[k]), dy = __fsub_rn(ly, py[k]), dz = __fsub_rn(lz, pz[k]);
+            pdist[k] = __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
+            if ((live >> k) & 1u) { mp = fmaxf(mp, pdist[k]); mf = fmaxf(mf, acc[k]); }
+        }
+        mp = wave_max(mp); mf = wave_max(mf);
+        if (lane == 0) { smaxp[wave] = mp; smaxf[wave] = mf; }
+        __syncthreads();
+#pragma unroll
+        for (int q = 0; q < FPSF_WAVES; ++q) { mp = fmaxf(mp, smaxp[q]); mf = fmaxf(mf, smaxf[q]); }
+        long long key = (long long)0x8000000000000000ull;
+#pragma unroll
+        for (int k = 0; k < NPT; ++k) {
+            if ((live >> k) & 1u) {
+                const float tp = mp > 0.f ? __fdiv_rn(pdist[k], mp) : 0.f, tf = mf > 0.f ? __fdiv_rn(acc[k], mf) : 0.f;
+                dist[k] = fminf(dist[k], __fadd_rn(tp, tf));
+                const long long kk = ((long long)__float_as_int(dist[k]) << 32) | (long long)(0x7fffffff - (tid + FPSF_THREADS * k));
+                key = kk > key ? kk : key;           // (ascending k = ascending index: an equal distance keeps the lower one)
+            }
+        }
+        key = fpsf_wave_max_key(key);
+        if (lane == 0) skey[wave] = key;
+        __syncthreads();
+#pragma unroll
+        for (int q = 0; q < FPSF_WAVES; ++q) { const long long t = skey[q]; key = t > key ? t : key; }
+        last = 0x7fffffff - (int)(key & 0xffffffffll);
+        if (tid == 0) order[it] = last;
+    }
+#pragma unroll
+    for (int k = 0; k < NPT; ++k) if (tid + FPSF_THREADS * k == last) selmask |= 1u << k;
+    // the selected set as a bit mask (a wave's 64 points of one k are two whole words), then as k_fps_coords emits it: row-major
+    // order -> coords (row/h, col/w)*2-1; rank of a pixel = selected pixels in front of it
+#pragma unroll
+    for (int k = 0; k < NPT; ++k) {
+        const unsigned long long b = __ballot((selmask >> k) & 1u);
+        if (lane == 0) {
+            const int wd = (wave * 64 + FPSF_THREADS * k) >> 5;
+            selbits[wd] = (uint32_t)b; selbits[wd + 1] = (uint32_t)(b >> 32);
+        }
+    }
+    __syncthreads();
+    if (out_inds) for (int k = tid; k < nsel; k += FPSF_THREADS) out_inds[(size_t)n * nsel + k] = order[k];
+#pragma unroll
+    for (int k = 0; k < NPT; ++k) {
+        const int idx = tid + FPSF_THREADS * k;
+        if (!((selmask >> k) & 1u)) continue;
+        int rank = __popc(selbits[idx >> 5] & ((1u << (idx & 31)) - 1u));
+        for (int q = 0; q < (idx >> 5); ++q) rank += __popc(selbits[q]);
+        const int i = idx / w, j = idx - i * w;
+        float* o = out_coords + ((size_t)n * nsel + rank) * 2;
+        o[0] = __fsub_rn(__fmul_rn(__fdiv_rn((float)i, (float)h), 2.0f), 1.0f);
+        o[1] = __fsub_rn(__fmul_rn(__fdiv_rn((float)j, (float)w), 2.0f), 1.0f);
+    }
+}
+
+// (B images in all; the first Ba from `depth` / `feats`, the rest from `depth_b` / `feats_b`; `pooled` (B, h, w) is written first)
+hipError_t dg_launch_fps_feats(const float* depth, const float* depth_b, const float* feats, const float* feats_b, int Ba, int B, int C,
+                               int H, int W, int h, int w, int S, float factor, float* out_coords, int32_t* out_inds, float* pooled,
+                               hipStream_t s) {
+    if (!dg_pool_depth_fits(H, W, h)) return hipErrorInvalidValue;
+    const hipError_t e = launch_pool_depth(depth, depth_b, Ba, B, H, W, h, w, pooled, s);
+    if (e != hipSuccess) return e;
+    const int npt = h * w <= FPSF_THREADS ? 1 : (h * w <= 2 * FPSF_THREADS ? 2 : 4);
+    const int smem = (((C + 3) & ~3) + S * S + npt * (FPSF_THREADS / 32)) * 4;
+    auto launch = [&](auto kern) {
+        return dg_launch(kern, dim3(B), dim3(FPSF_THREADS), smem, s, (const float*)pooled, feats, feats_b, Ba, C, h, w, S, factor, out_coords, out_inds);
+    };
+    if (h * w > 4 * FPSF_THREADS) return hipErrorInvalidValue;          // (4096 pixels: the samplers' limit, dg_api_aux.hip)
+    if (npt == 1) return launch(k_fps_feats<1>);
+    if (npt == 2) return launch(k_fps_feats<2>);
+    return launch(k_fps_feats<4>);
 }
 
 // ------------------------------------------------------------------------------------------

@@ -34,7 +34,7 @@ CAPTURE_KEY = (
     "correspondence_weight", "pos_intra_weight", "pos_inter_weight", "neg_inter_weight", "depth_feat_weight",
     "pos_intra_shift", "pos_inter_shift", "neg_inter_shift", "depth_feat_shift", "rec_weight",
     # the sample grid and how it is drawn (legacy_decay_step changes the first two)
-    "feature_samples", "depth_sampling", "neg_samples", "use_salience", "depth_feat_correlation_loss",
+    "feature_samples", "depth_sampling", "dg_fps_feats", "neg_samples", "use_salience", "depth_feat_correlation_loss",
     # the loss's form
     "pointwise", "zero_clamp", "stabalize", "dropout", "dg_dense_grid", "dg_outputs", "dg_exact_masks", "dg_small_identity_blobs",
     # what the constructor refuses (set later, they are refused in front of the next recording)

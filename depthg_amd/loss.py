@@ -154,10 +154,22 @@ class ContrastiveCorrelationLoss(nn.Module):
             c1 = ops.simple_depth_coords(depth, orig_feats.shape[-2:], S)
             c2 = ops.simple_depth_coords(depth_pos, orig_feats_pos.shape[-2:], S)
             return c1, c2, False
-        if mode in ("fps", "fps_depth_feat"):   # 'fps_depth_feat' == 'fps' in the reference (quirk Q13)
+        # 'fps_depth_feat' == 'fps' in the reference (quirk Q13: farthest_point_sampling_depth drops the feature rows it forms and
+        # calls the depth-only fps).  cfg.dg_fps_feats = True gives that mode the sampler its name promises - the reference's
+        # uncalled fps_depth_feats (src/modules.py:1124-1180) on the feature maps as handed in; 'fps' never reads the key.
+        if mode in ("fps", "fps_depth_feat"):
             if depth is None or depth_pos is None:
                 raise AttributeError("depth_sampling='fps' needs depth and depth_pos (the reference fails on None too, quirk Q8)")
-            if depth.shape == depth_pos.shape and orig_feats.shape[-2:] == orig_feats_pos.shape[-2:]:
+            if mode == "fps_depth_feat" and getattr(cfg, "dg_fps_feats", False):
+                as_read = lambda t: t.to(torch.float32).contiguous()         # (the sampler reads its maps in place)
+                d1, d2, f1, f2 = as_read(depth), as_read(depth_pos), as_read(orig_feats), as_read(orig_feats_pos)
+                if d1.shape == d2.shape and f1.shape == f2.shape:
+                    both = ops.fps_feats_coords_pair(d1, d2, f1, f2, f1.shape[-2:], S)
+                    c1, c2 = both[:B], both[B:]
+                else:
+                    c1 = ops.fps_feats_coords(d1, f1, f1.shape[-2:], S)
+                    c2 = ops.fps_feats_coords(d2, f2, f2.shape[-2:], S)
+            elif depth.shape == depth_pos.shape and orig_feats.shape[-2:] == orig_feats_pos.shape[-2:]:
                 # one launch for both maps: the sampler is a sequential per-image loop (one block per image), so the two
                 # calls of the reference (src/modules.py:1304-1308) simply run side by side on twice as many CUs
                 both = ops.fps_coords_pair(depth, depth_pos, orig_feats.shape[-2:], S)

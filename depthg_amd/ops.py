@@ -909,6 +909,53 @@ def fps_coords_pair(depth, depth_pos, feat_hw, n_samples):
     return _fps(depth, depth_pos, feat_hw, n_samples, False)
 
 
+def _fps_feats_operand(t, name):
+    """The feature-aware sampler reads its maps in place: a contiguous fp32 GPU tensor, or a refusal by name."""
+    _on_gpu(t, name)
+    if t.dtype != torch.float32 or t.dim() != 4 or not t.is_contiguous():
+        raise ValueError(f"depthg_amd: `{name}` must be a contiguous 4-D float32 tensor (the sampler reads it in place), got "
+                         f"{t.dtype} {tuple(t.shape)}{'' if t.is_contiguous() else ', not contiguous'}")
+    return t.detach()
+
+
+def _fps_feats(depth, depth_pos, feats, feats_pos, feat_hw, n_samples, return_inds):
+    """dg_fps_feats_coords on the B maps of `depth` / `feats` and - not None - on the B of `depth_pos` / `feats_pos` behind them."""
+    lib = _lib.load()
+    B, _, H, W = depth.shape
+    h, w = int(feat_hw[0]), int(feat_hw[1])
+    C = feats.shape[1]
+    for name, d, f in (("depth", depth, feats),) + ((("depth_pos", depth_pos, feats_pos),) if depth_pos is not None else ()):
+        if d.shape[1] != 1 or tuple(f.shape) != (d.shape[0], C, h, w) or f.device != d.device:
+            raise ValueError(f"depthg_amd: `{name}` {tuple(d.shape)} on {d.device} needs features ({d.shape[0]}, C, {h}, {w}) on the same device, "
+                             f"got {tuple(f.shape)} on {f.device}")
+    nB = B if depth_pos is None else 2 * B
+    S = int(n_samples)
+    coords = _empty((nB, S, S, 2), torch.float32, depth.device)
+    inds = _empty((nB, S * S), torch.int32, depth.device) if return_inds else None
+    ws = _empty((lib.dg_fps_feats_workspace_bytes(nB, h, w)), torch.uint8, depth.device)         # the pooled depth maps
+    rc = lib.dg_fps_feats_coords(_ptr(depth), _ptr(depth_pos), _ptr(feats), _ptr(feats_pos), B, C, H, W, h, w, S, _ptr(coords), _ptr(inds),
+                                 _ptr(ws), ws.numel(), _stream(depth.device))
+    _lib.check(rc, "dg_fps_feats_coords")
+    return (coords, inds) if return_inds else coords
+
+
+def fps_feats_coords(depth, feats, feat_hw, n_samples, return_inds=False):
+    """Farthest point sampling over depth AND features (dg_fps_feats_coords; the reference's fps_depth_feats, src/modules.py:1124-1180,
+    inside farthest_point_sampling_depth): depth (B,1,H,W), feats (B,C,h,w) with (h,w) = feat_hw, both contiguous float32 on the GPU
+    -> coords (B,S,S,2) in [-1,1) (already *2-1), and the selection order int32 (B,S*S) with return_inds."""
+    return _fps_feats(_fps_feats_operand(depth, "depth"), None, _fps_feats_operand(feats, "feats"), None, feat_hw, n_samples, return_inds)
+
+
+def fps_feats_coords_pair(depth, depth_pos, feats, feats_pos, feat_hw, n_samples):
+    """The two calls of one step in one launch over 2B blocks: -> coords (2B,S,S,2), rows [0,B) the anchors', [B,2B) the positives'."""
+    depth, depth_pos = _fps_feats_operand(depth, "depth"), _fps_feats_operand(depth_pos, "depth_pos")
+    feats, feats_pos = _fps_feats_operand(feats, "feats"), _fps_feats_operand(feats_pos, "feats_pos")
+    if depth.shape != depth_pos.shape or depth.device != depth_pos.device or feats.shape != feats_pos.shape:
+        raise ValueError(f"depthg_amd: depth {tuple(depth.shape)} on {depth.device} / feats {tuple(feats.shape)} and depth_pos "
+                         f"{tuple(depth_pos.shape)} on {depth_pos.device} / feats_pos {tuple(feats_pos.shape)} must match for the paired sampler")
+    return _fps_feats(depth, depth_pos, feats, feats_pos, feat_hw, n_samples, False)
+
+
 def salience_coords(salience, n_side, u_sel=None, u_fallback=None):
     """sample_nonzero_locations (src/modules.py:1191-1204) on the GPU: salience (B,H,W) -> (B,S,S,2), flipped and *2-1 like
     the reference.  u_sel (B,S*S) / u_fallback (B,S*S,2): iid uniforms in [0,1), drawn here unless given (tests)."""

@@ -608,7 +608,10 @@ def default_segmenter_cfg(**over) -> SimpleNamespace:
         dg_graph_step=False,
         # build-side: both probes of the step and their parameter gradients as one fused HIP operation on the detached code
         # (head.fused_probe_losses; the train command's --fused-probes).  Read once, when the segmenter is constructed
-        dg_fused_probes=False)
+        dg_fused_probes=False,
+        # depth_sampling "fps_depth_feat" only: True draws the sample grid with the feature-aware sampler (ops.fps_feats_coords_pair, the
+        # reference's uncalled fps_depth_feats); False keeps the reference's behaviour, where that mode is 'fps' (quirk Q13)
+        dg_fps_feats=False)
     for k, v in over.items():
         setattr(cfg, k, v)
     return cfg

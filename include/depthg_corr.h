@@ -298,6 +298,27 @@ int dg_fps_coords(const float* depth, const float* depth_pos, int32_t B, int32_t
                   void* workspace, size_t workspace_bytes, dg_stream_t stream);
 
 /*
+ * Depth-and-feature-guided sample locations (cfg.dg_fps_feats): farthest_point_sampling_depth (src/modules.py:999-1037) with its
+ * `fps(point_cloud, n*n)` call (:1020) replaced by `fps_depth_feats(point_cloud, feats, n*n)` (:1124-1180) on the feature rows the
+ * reference forms at :1017 and drops - the sampler depth_sampling = 'fps_depth_feat' names and the reference never calls (quirk
+ * Q13: without cfg.dg_fps_feats that mode stays dg_fps_coords).  Per round, over the points not yet selected: squared distance to
+ * the last selected point in space (3 coordinates) and in feature space (C channels, direct fp32 sum of squared differences),
+ * each divided by its maximum over those points, summed, folded into the running minimum; the first arg-max is selected next.
+ * One deviation: where a maximum is 0 (all points left coincide with the last one in space - a zero depth map - or in feature
+ * space) the reference divides 0 / 0 and selects on NaNs; here that term contributes 0.
+ *  depth, depth_pos      : as dg_fps_coords
+ *  feats                 : fp32 (B,C,h,w), unnormalised, as handed to the loss; feats_pos: NULL exactly when depth_pos is
+ *  out_coords, out_inds  : as dg_fps_coords
+ *  workspace             : >= dg_fps_feats_workspace_bytes(B,h,w) bytes, of (2B,h,w) with depth_pos; required
+ * Refused before any launch: a null or misaligned pointer, the grid limits of dg_fps_coords (h*w <= 4096, depth no smaller than the
+ * grid), S*S > h*w, C < 1 (and C > 16384, a pooled row's depth rows beyond 64 KB).  No atomics; two calls give equal bits.
+ */
+size_t dg_fps_feats_workspace_bytes(int32_t B, int32_t h, int32_t w);
+int dg_fps_feats_coords(const float* depth, const float* depth_pos, const float* feats, const float* feats_pos,
+                        int32_t B, int32_t C, int32_t depth_h, int32_t depth_w, int32_t h, int32_t w, int32_t S,
+                        float* out_coords, int32_t* out_inds, void* workspace, size_t workspace_bytes, dg_stream_t stream);
+
+/*
  * Salience-guided sample locations (replaces sample_nonzero_locations, src/modules.py:1191-1204, the cfg.use_salience
  * branch of the coordinate draw, :1290-1297): every position gets a uniformly drawn non-zero pixel of its image's
  * salience map (torch.nonzero = row-major order), returned as the reference does: both pixel coordinates divided by
