@@ -62,6 +62,9 @@ SIGNATURES = {
     "dg_fps_coords": (_I, [vp, vp] + [i32] * 6 + [vp, vp, vp, _SZ, vp]),
     "dg_fps_feats_workspace_bytes": (_SZ, [i32] * 3),
     "dg_fps_feats_coords": (_I, [vp] * 4 + [i32] * 7 + [vp, vp, vp, _SZ, vp]),
+    "dg_fps_large_workspace_bytes": (_SZ, [i32] * 3),
+    "dg_fps_coords_large": (_I, [vp, vp] + [i32] * 6 + [vp, vp, vp, _SZ, vp]),
+    "dg_label_onehot": (_I, [vp, vp] + [i32] * 4 + [vp, vp]),
     "dg_salience_coords": (_I, [vp] + [i32] * 4 + [vp] * 4),
     "dg_simple_depth_coords": (_I, [vp] + [i32] * 6 + [vp] * 4),
     # metrics, LHP, nearest neighbours

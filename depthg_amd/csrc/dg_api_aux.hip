@@ -228,6 +228,53 @@ extern "C" int dg_fps_feats_coords(const float* depth, const float* depth_pos, c
     return DG_OK;
 }
 
+// The pooled depth maps of the large sampler (written only where the depth maps are larger than the grid)
+extern "C" size_t dg_fps_large_workspace_bytes(int32_t B, int32_t h, int32_t w) {
+    if (B < 1 || h < 1 || w < 1 || (int64_t)h * w > DG_FPS_LARGE_MAX_POS) return 256;
+    return (size_t)B * h * w * 4 + 256;
+}
+
+// dg_fps_coords on pooled grids of up to 65536 positions (k_fps_large): the same selection, bit for bit, on every grid both serve
+extern "C" int dg_fps_coords_large(const float* depth, const float* depth_pos, int32_t B, int32_t depth_h, int32_t depth_w, int32_t h, int32_t w,
+                                   int32_t S, float* out_coords, int32_t* out_inds, void* workspace, size_t workspace_bytes, dg_stream_t stream_) {
+    if (!depth || !out_coords) return fail(DG_ERR_INVALID, "dg_fps_coords_large: null pointer");
+    if (((uintptr_t)depth | (uintptr_t)depth_pos | (uintptr_t)out_coords | (uintptr_t)out_inds | (uintptr_t)workspace) & 3)
+        return fail(DG_ERR_INVALID, "dg_fps_coords_large: pointers must be 4-byte aligned");
+    if (B < 1 || B > (1 << 20) || h < 1 || w < 1 || S < 1 || depth_h < h || depth_w < w) return fail(DG_ERR_INVALID, "dg_fps_coords_large: bad FPS dimensions");
+    const int32_t nB = depth_pos ? 2 * B : B;
+    if ((int64_t)h * w > DG_FPS_LARGE_MAX_POS)
+        return fail(DG_ERR_UNSUPPORTED, "dg_fps_coords_large: grid %dx%d too large for the sampler (max %d positions)", h, w, DG_FPS_LARGE_MAX_POS);
+    if ((int64_t)S * S > (int64_t)h * w) return fail(DG_ERR_INVALID, "dg_fps_coords_large: cannot sample %lld points from a %dx%d map", (long long)S * S, h, w);
+    if ((int64_t)S * S > DG_FPS_LARGE_MAX_SEL)
+        return fail(DG_ERR_UNSUPPORTED, "dg_fps_coords_large: %lld selections exceed the %d the block's selection table holds", (long long)S * S, DG_FPS_LARGE_MAX_SEL);
+    const bool pooling = depth_h != h || depth_w != w;
+    if (pooling && !dg_pool_depth_fits(depth_h, depth_w, h))
+        return fail(DG_ERR_UNSUPPORTED, "dg_fps_coords_large: the %d-wide depth rows of one pooled row exceed 64 KB of LDS", depth_w);
+    if (pooling && (!workspace || workspace_bytes < (size_t)nB * h * w * 4))
+        return fail(DG_ERR_WORKSPACE, "dg_fps_coords_large: workspace too small for the pooled depth maps (dg_fps_large_workspace_bytes)");
+    const uint32_t bits = 0x404f54cbu;            // 2*tan(90/2 rad), the reference's float32 factor (dg_fps_coords)
+    float factor;
+    memcpy(&factor, &bits, 4);
+    DG_HIP(dg_launch_fps_large(depth, depth_pos, B, nB, depth_h, depth_w, h, w, S, factor, out_coords, out_inds, static_cast<float*>(workspace),
+                               static_cast<hipStream_t>(stream_)));
+    return DG_OK;
+}
+
+// label_pos non-null: the B label maps of a second tensor behind the first's, 2 B images of ONE output in one launch
+extern "C" int dg_label_onehot(const int64_t* label, const int64_t* label_pos, int32_t B, int32_t n_classes, int32_t H, int32_t W, float* out,
+                               dg_stream_t stream_) {
+    if (!label || !out) return fail(DG_ERR_INVALID, "dg_label_onehot: null pointer");
+    if (((uintptr_t)label | (uintptr_t)label_pos) & 7) return fail(DG_ERR_INVALID, "dg_label_onehot: the label maps must be 8-byte aligned");
+    if ((uintptr_t)out & 3) return fail(DG_ERR_INVALID, "dg_label_onehot: `out` must be 4-byte aligned");
+    if (B < 1 || H < 1 || W < 1 || n_classes < 0) return fail(DG_ERR_INVALID, "dg_label_onehot: B=%d n_classes=%d map %dx%d", B, n_classes, H, W);
+    if (n_classes + 1 > 256) return fail(DG_ERR_UNSUPPORTED, "dg_label_onehot: n_classes + 1 = %d > 256 channels", n_classes + 1);
+    const int64_t nB = label_pos ? 2 * (int64_t)B : B;
+    if (nB > 65535) return fail(DG_ERR_UNSUPPORTED, "dg_label_onehot: %lld images in one launch (max 65535)", (long long)nB);
+    if ((int64_t)H * W > (1 << 24)) return fail(DG_ERR_UNSUPPORTED, "dg_label_onehot: map %dx%d too large (max 2^24 pixels)", H, W);
+    DG_HIP(dg_launch_label_onehot(label, label_pos, B, (int)nB, n_classes + 1, H, W, out, static_cast<hipStream_t>(stream_)));
+    return DG_OK;
+}
+
 // ---- the optimisation step's Adams (dg_optim.hip)
 extern "C" int dg_adam_step(const dg_adam_seg* segs, int32_t n_seg, const dg_adam_group* groups, int32_t n_groups, int32_t device_steps,
                             void* tickets, dg_stream_t stream_) {

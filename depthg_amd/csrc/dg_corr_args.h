@@ -646,6 +646,14 @@ hipError_t dg_launch_rand_coords_state(unsigned long long* state, float* out, in
 // (B images in all; the first Ba from `depth`, the rest from `depth_b`)
 hipError_t dg_launch_fps(const float* depth, const float* depth_b, int Ba, int B, int H, int W, int h, int w, int S, float factor,
                          float* out_coords, int32_t* out_inds, float* pooled_ws, hipStream_t s);
+// ... on pooled grids of up to DG_FPS_LARGE_MAX_POS positions and DG_FPS_LARGE_MAX_SEL selections (k_fps_large; the limits and the
+// pooling pre-pass are the caller's to check; `pooled` (B, h, w) is written unless the depth maps already have the grid's size)
+#define DG_FPS_LARGE_MAX_POS 65536
+#define DG_FPS_LARGE_MAX_SEL 8192
+hipError_t dg_launch_fps_large(const float* depth, const float* depth_b, int Ba, int B, int H, int W, int h, int w, int S, float factor,
+                               float* out_coords, int32_t* out_inds, float* pooled, hipStream_t s);
+// The one-hot label signal (dg_label_onehot.hip; B images in all, the first Ba from `label`, the rest from `label_b`; K = n_classes + 1)
+hipError_t dg_launch_label_onehot(const int64_t* label, const int64_t* label_b, int Ba, int B, int K, int H, int W, float* out, hipStream_t s);
 // ... with the feature term (k_fps_feats; `feats` / `feats_b` (., C, h, w) beside the depth maps).  The pooling pre-pass must fit:
 bool dg_pool_depth_fits(int H, int W, int h);
 hipError_t dg_launch_fps_feats(const float* depth, const float* depth_b, const float* feats, const float* feats_b, int Ba, int B, int C,

@@ -1193,6 +1193,163 @@ hipError_t dg_launch_fps(const float* depth, const float* depth_b, int Ba, int B
 }
 
 // ------------------------------------------------------------------------------------------
+// FPS on pooled grids above k_fps_coords' 4096 positions (cfg.use_true_labels: the loss's signal, and with it the grid, has the
+// labels' resolution), up to DG_FPS_LARGE_MAX_POS.  One block per image, the rounds of k_fps_coords: every wave reduces its values with
+// DPP, the lanes that hold the wave's maximum hand {value : 0x7fffffff - index} to an LDS atomic max, one barrier per round.  What
+// differs is where a point lives.  k_fps_coords keeps {x, y, z, running distance} of 8 points per thread in registers and a point table
+// in LDS; 65536 points of four values are 1 MB, a CU's register file holds 512 KB and its LDS 160 KB.  Here a thread keeps its points'
+// pooled DEPTH and running distance (two registers per point, DREG) and rebuilds {x, y, z} from the depth and the point's index in
+// every round, with depth2points' operations in k_fps_coords' order: the same bits, so the same distances, the same arg-max and the
+// same selection on any grid both kernels serve.  Above 100 points per thread the depths no longer fit beside the distances: they are
+// read from the pooled map again in every round (256 KB per image: L2; the loads do not depend on the round's chain).  The selected
+// point's depth comes from the pooled map too (one address for the whole block).
+// Row and column of a point: i = int((idx + 0.5) * (1 / w)) in fp32 - exact for h * w < 2^21 ((idx + 0.5) / w lies 0.5 / w from the
+// nearest integer, the product's error is below i * 2^-22) - where an integer division per point and round would cost as much as the
+// distance itself.
+__device__ __forceinline__ void fpsl_point(int idx, float dv, float factor, float five, float rw, int w, float fh, float fw, float hh, float wh,
+                                           float& x, float& y, float& z) {
+#pragma clang fp contract(off)
+    const int i = (int)__fmul_rn(__fadd_rn((float)idx, 0.5f), rw), j = idx - i * w;
+    const float fd = __fmul_rn(factor, dv);
+    y = __fdiv_rn(__fmul_rn(fd, __fsub_rn((float)i, hh)), fh);
+    x = __fdiv_rn(__fmul_rn(fd, __fsub_rn((float)j, wh)), fw);
+    z = __fmul_rn(-dv, five);
+}
+
+// |l - q|^2 with separately rounded products and sums in numpy's order, as k_fps_coords' packed instructions form it.  (hipcc fuses
+// __fmul_rn into a following __fadd_rn - they are plain operators to it - and a fused dx*dx + dy*dy is no longer symmetric in x and
+// y: on a flat depth map the exact ties between mirrored points then break the wrong way.)
+__device__ __forceinline__ float fpsl_dist(float lx, float ly, float lz, float x, float y, float z) {
+#pragma clang fp contract(off)
+    const float dx = lx - x, dy = ly - y, dz = lz - z;
+    const float xx = dx * dx, yy = dy * dy, zz = dz * dz;
+    return (xx + yy) + zz;
+}
+
+template <int NPT, bool DREG>       // points per thread: h*w <= NPT * FPS_THREADS; DREG: their depths stay in registers
+__global__ __launch_bounds__(FPS_THREADS) void k_fps_large(const float* __restrict__ pooled, const float* __restrict__ pooled_b, int Ba,
+                                                           int h, int w, int S, float factor, float* __restrict__ out_coords,
+                                                           int32_t* __restrict__ out_inds) {
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    const int HW = h * w, nsel = S * S, nwords = (HW + 31) >> 5;
+    int* order = reinterpret_cast<int*>(sm);               // [nsel] selection order
+    uint32_t* selbits = reinterpret_cast<uint32_t*>(order + nsel);   // [nwords] selected set as a bit mask
+    __shared__ long long skey[3];                          // the round's arg-max key, three in rotation (k_fps_coords)
+    __shared__ int tie_low;
+    const int n = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
+    // (images Ba.. of the launch come from a second tensor: the two depth maps of one step where no pooling is needed)
+    const float* pd = n < Ba ? pooled + (size_t)n * HW : pooled_b + (size_t)(n - Ba) * HW;
+    const float fh = (float)h, fw = (float)w, hh = (float)h / 2.0f, wh = (float)w / 2.0f, rw = __fdiv_rn(1.0f, (float)w);
+
+    float dvs[DREG ? NPT : 1], qd[NPT];
+#pragma unroll
+    for (int k = 0; k < NPT; ++k) {
+        const int idx = tid + FPS_THREADS * k;
+        if constexpr (DREG) dvs[k] = idx < HW ? pd[idx] : 0.f;
+        qd[k] = idx < HW ? __builtin_inff() : -1.f;        // a point past the map has distance -1 and never wins
+    }
+    for (int k = tid; k < nwords; k += FPS_THREADS) selbits[k] = 0u;
+    if (tid < 3) skey[tid] = (long long)0x8000000000000000ull;
+    if (lane == 0) order[0] = 0;
+    __syncthreads();
+    float lx, ly, lz;                                      // the last selected point; point 0 starts the selection
+    fpsl_point(0, pd[0], factor, 5.0f, rw, w, fh, fw, hh, wh, lx, ly, lz);
+    const uint32_t key_addr = lds_addr(&skey[0]);
+    int cur = 1, nxt = 2;                  // key of round it: it % 3
+    for (int it = 1; it < nsel; ++it) {
+        // A point does not change from round to round, so hipcc would form all of them once, in front of the loop, and keep them: the
+        // registers this kernel does not have.  Every input of the rebuild but the depth passes an empty asm statement per round.
+        int rtid = tid;
+        float rfactor = factor, five = 5.0f;
+        asm volatile("" : "+v"(rtid), "+v"(rfactor), "+v"(five));
+        int mb = (int)0x80000000;
+#pragma unroll
+        for (int k = 0; k < NPT; ++k) {
+            const int idx = rtid + FPS_THREADS * k;
+            float dv;
+            if constexpr (DREG) dv = dvs[k];
+            else dv = idx < HW ? pd[idx] : 0.f;
+            float x, y, z;
+            fpsl_point(idx, dv, rfactor, five, rw, w, fh, fw, hh, wh, x, y, z);
+            qd[k] = fps_min(fpsl_dist(lx, ly, lz, x, y, z), qd[k]);
+            // this thread's largest distance (values are >= 0 or -1: their bit patterns order like signed integers)
+            mb = max(mb, __float_as_int(qd[k]));
+        }
+        const int wmax = dpp_wave_max_i(mb);
+        if (mb == wmax) {
+            int bk = NPT - 1;                  // the FIRST of this thread's points that attains it (ascending k = ascending index)
+#pragma unroll
+            for (int k = NPT - 2; k >= 0; --k) bk = __float_as_int(qd[k]) == mb ? k : bk;
+            const long long key = ((long long)mb << 32) | (long long)(0x7fffffff - (tid + FPS_THREADS * bk));
+            asm volatile("ds_max_i64 %0, %1" :: "v"(key_addr + 8 * cur), "v"(key) : "memory");
+        }
+        if (lane == 0) skey[nxt] = (long long)0x8000000000000000ull;     // (its readers of two rounds ago are behind the previous barrier)
+        __syncthreads();
+        const long long kb = skey[cur];
+        int i0 = 0x7fffffff - (int)(kb & 0xffffffffll);
+        if (__builtin_expect((int)(kb >> 32) == 0, 0)) {
+            // largest distance 0: every point that is left coincides with a selected one - the lowest index still unselected (k_fps_coords)
+            if (tid == 0) tie_low = 0x7fffffff;
+            __syncthreads();
+#pragma unroll 1
+            for (int k = 0; k < NPT; ++k) {
+                const int idx = tid + FPS_THREADS * k;
+                bool used = idx >= HW;
+                for (int q = 0; q < it && !used; ++q) used = order[q] == idx;
+                if (!used) atomicMin(&tie_low, idx);
+            }
+            __syncthreads();
+            i0 = tie_low;
+            __syncthreads();
+        }
+        i0 = min(i0, HW - 1);                  // (never moves a winner: keeps the address below inside the map whatever the depths hold)
+        fpsl_point(i0, pd[i0], factor, 5.0f, rw, w, fh, fw, hh, wh, lx, ly, lz);
+        cur = nxt; nxt = nxt == 2 ? 0 : nxt + 1;
+        if (lane == 0) order[it] = i0;         // (one lane of EVERY wave, the same value: kept in LDS, as k_fps_coords keeps it)
+    }
+    __syncthreads();
+    for (int k = tid; k < nsel; k += FPS_THREADS) {
+        const int i0 = order[k];
+        atomicOr(&selbits[i0 >> 5], 1u << (i0 & 31));
+        if (out_inds) out_inds[(size_t)n * nsel + k] = i0;
+    }
+    __syncthreads();
+    // selected set in row-major order -> coords (row/h, col/w)*2-1; rank of a pixel = selected pixels in front of it
+    for (int idx = tid; idx < HW; idx += FPS_THREADS) {
+        const uint32_t wd = selbits[idx >> 5];
+        if (!((wd >> (idx & 31)) & 1u)) continue;
+        int rank = __popc(wd & ((1u << (idx & 31)) - 1u));
+        for (int k = 0; k < (idx >> 5); ++k) rank += __popc(selbits[k]);
+        const int i = idx / w, j = idx - i * w;
+        float* o = out_coords + ((size_t)n * nsel + rank) * 2;
+        o[0] = __fsub_rn(__fmul_rn(__fdiv_rn((float)i, (float)h), 2.0f), 1.0f);
+        o[1] = __fsub_rn(__fmul_rn(__fdiv_rn((float)j, (float)w), 2.0f), 1.0f);
+    }
+}
+
+// (the caller has checked the grid's limits and, where the maps are pooled, dg_pool_depth_fits)
+hipError_t dg_launch_fps_large(const float* depth, const float* depth_b, int Ba, int B, int H, int W, int h, int w, int S, float factor,
+                               float* out_coords, int32_t* out_inds, float* pooled, hipStream_t s) {
+    const int HW = h * w;
+    if (HW < 1 || HW > DG_FPS_LARGE_MAX_POS || S * S > DG_FPS_LARGE_MAX_SEL || S * S > HW) return hipErrorInvalidValue;
+    const float* pa = depth;
+    const float* pb = depth_b;
+    if (H != h || W != w) {             // (depth maps of the grid's own size: adaptive_avg_pool2d is the identity, nothing is copied)
+        if (!pooled || !dg_pool_depth_fits(H, W, h)) return hipErrorInvalidValue;
+        const hipError_t e = launch_pool_depth(depth, depth_b, Ba, B, H, W, h, w, pooled, s);
+        if (e != hipSuccess) return e;
+        pa = pooled; pb = pooled + (size_t)Ba * HW;
+    }
+    const int smem = (S * S + (HW + 31) / 32 + 3) / 4 * 16;
+    auto launch = [&](auto kern) { return dg_launch(kern, dim3(B), dim3(FPS_THREADS), smem, s, pa, pb, Ba, h, w, S, factor, out_coords, out_inds); };
+    if (HW <= 16 * FPS_THREADS) return launch(k_fps_large<16, true>);
+    if (HW <= 32 * FPS_THREADS) return launch(k_fps_large<32, true>);
+    if (HW <= 64 * FPS_THREADS) return launch(k_fps_large<64, true>);
+    if (HW <= 100 * FPS_THREADS) return launch(k_fps_large<100, true>);      // (224 x 224: 98 points per thread)
+    return launch(k_fps_large<128, false>);
+}
+
+// ------------------------------------------------------------------------------------------
 // Feature-aware FPS (cfg.dg_fps_feats): farthest_point_sampling_depth (src/modules.py:999-1037) with its fps call replaced by
 // fps_depth_feats (:1124-1180), the sampler the reference wrote for depth_sampling = 'fps_depth_feat' and never called.  One block
 // per image; the pooled depth comes from k_pool_depth (the pre-pass the depth-only sampler uses), the features stay (C, h*w) in

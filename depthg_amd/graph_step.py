@@ -66,6 +66,9 @@ def refuse(cfg, sample_cache, feature_cache, grad_sync=None):
     if getattr(cfg, "use_depth_only_intra", False):
         raise ValueError(f"{who} cannot record cfg.use_depth_only_intra (DepthContrastiveCorrelationLoss does not run under cfg.dg_graph_safe); set "
                          "cfg.use_depth_only_intra = False or train without dg_graph_step")
+    if getattr(cfg, "use_true_labels", False):
+        raise ValueError(f"{who} cannot record cfg.use_true_labels: the one-hot label signal is a diagnostic route the recorded step does not "
+                         "carry; set cfg.use_true_labels = False or train without dg_graph_step")
     if grad_sync is not None:
         raise ValueError(f"{who} records one GPU's step: a `grad_sync` (data parallelism) is out of scope; call training_step(batch, grad_sync=...) "
                          "eagerly instead")

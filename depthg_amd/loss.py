@@ -151,6 +151,7 @@ class ContrastiveCorrelationLoss(nn.Module):
         if mode == "simple":                             # src/modules.py:1299-1302: S x 1 grids, (B,S,1,2)
             if depth is None or depth_pos is None:
                 raise AttributeError("depth_sampling='simple' needs depth and depth_pos")
+            self._refuse_large_grid(orig_feats, "depth_sampling = 'simple'")
             c1 = ops.simple_depth_coords(depth, orig_feats.shape[-2:], S)
             c2 = ops.simple_depth_coords(depth_pos, orig_feats_pos.shape[-2:], S)
             return c1, c2, False
@@ -160,7 +161,12 @@ class ContrastiveCorrelationLoss(nn.Module):
         if mode in ("fps", "fps_depth_feat"):
             if depth is None or depth_pos is None:
                 raise AttributeError("depth_sampling='fps' needs depth and depth_pos (the reference fails on None too, quirk Q8)")
+            # a signal above 4096 positions (cfg.use_true_labels: the one-hot maps have the labels' resolution, and the reference pools
+            # the depth to the signal's, src/modules.py:1003): the large sampler, the same selection bit for bit where both serve
+            large = orig_feats.shape[-2] * orig_feats.shape[-1] > ops.FPS_MAX_POSITIONS
+            fps_one, fps_pair = (ops.fps_coords_large, ops.fps_coords_large_pair) if large else (ops.fps_coords, ops.fps_coords_pair)
             if mode == "fps_depth_feat" and getattr(cfg, "dg_fps_feats", False):
+                self._refuse_large_grid(orig_feats, "depth_sampling = 'fps_depth_feat' with cfg.dg_fps_feats")
                 as_read = lambda t: t.to(torch.float32).contiguous()         # (the sampler reads its maps in place)
                 d1, d2, f1, f2 = as_read(depth), as_read(depth_pos), as_read(orig_feats), as_read(orig_feats_pos)
                 if d1.shape == d2.shape and f1.shape == f2.shape:
@@ -172,11 +178,11 @@ class ContrastiveCorrelationLoss(nn.Module):
             elif depth.shape == depth_pos.shape and orig_feats.shape[-2:] == orig_feats_pos.shape[-2:]:
                 # one launch for both maps: the sampler is a sequential per-image loop (one block per image), so the two
                 # calls of the reference (src/modules.py:1304-1308) simply run side by side on twice as many CUs
-                both = ops.fps_coords_pair(depth, depth_pos, orig_feats.shape[-2:], S)
+                both = fps_pair(depth, depth_pos, orig_feats.shape[-2:], S)
                 c1, c2 = both[:B], both[B:]
             else:
-                c1 = ops.fps_coords(depth, orig_feats.shape[-2:], S)
-                c2 = ops.fps_coords(depth_pos, orig_feats_pos.shape[-2:], S)
+                c1 = fps_one(depth, orig_feats.shape[-2:], S)
+                c2 = fps_one(depth_pos, orig_feats_pos.shape[-2:], S)
             assert tuple(c1.shape) == tuple(c2.shape) == tuple(coord_shape), f"{c1.shape} != {c2.shape} != {coord_shape}"
             return c1, c2, False
         if getattr(cfg, "dg_dense_grid", False) and same_maps and S == orig_feats.shape[-2] == orig_feats.shape[-1]:
@@ -193,6 +199,15 @@ class ContrastiveCorrelationLoss(nn.Module):
         c1 = _rand_coords(coord_shape, dev)
         c2 = _rand_coords(coord_shape, dev)
         return c1, c2, False
+
+    @staticmethod
+    def _refuse_large_grid(orig_feats, what):
+        """The samplers that stay at 4096 positions, asked in front of their launch: the way out by name."""
+        h, w = orig_feats.shape[-2:]
+        if h * w > ops.FPS_MAX_POSITIONS:
+            raise ValueError(f"depthg_amd: {what} samples on the signal's own grid and serves at most {ops.FPS_MAX_POSITIONS} positions, "
+                             f"got {h}x{w}.  Under cfg.use_true_labels the signal has the labels' resolution: set cfg.depth_sampling = "
+                             f"'fps' (its sampler serves up to {ops.FPS_LARGE_MAX_POSITIONS} positions) or 'none'")
 
     def _graph_state(self, dev):
         """Generator state on the device (hipGraph-capturable step: nothing about a draw is baked into a launch)."""

@@ -909,6 +909,94 @@ def fps_coords_pair(depth, depth_pos, feat_hw, n_samples):
     return _fps(depth, depth_pos, feat_hw, n_samples, False)
 
 
+FPS_MAX_POSITIONS = 4096             # pooled grids up to here: dg_fps_coords (and the 'simple' / feature-aware samplers' limit)
+FPS_LARGE_MAX_POSITIONS = 65536      # ... up to here: dg_fps_coords_large
+
+
+def _fps_large(depth, depth_pos, feat_hw, n_samples, return_inds):
+    """dg_fps_coords_large on the B maps of `depth` and - not None - on the B of `depth_pos` behind them."""
+    lib = _lib.load()
+    B, _, H, W = depth.shape
+    nB = B if depth_pos is None else 2 * B
+    h, w = int(feat_hw[0]), int(feat_hw[1])
+    S = int(n_samples)
+    coords = _empty((nB, S, S, 2), torch.float32, depth.device)
+    inds = _empty((nB, S * S), torch.int32, depth.device) if return_inds else None
+    # (the pooled depth maps; depth maps of the grid's own size are read in place)
+    ws = _empty((lib.dg_fps_large_workspace_bytes(nB, h, w)), torch.uint8, depth.device) if (H, W) != (h, w) else None
+    rc = lib.dg_fps_coords_large(_ptr(depth), _ptr(depth_pos), B, H, W, h, w, S, _ptr(coords), _ptr(inds), _ptr(ws),
+                                 ws.numel() if ws is not None else 0, _stream(depth.device))
+    _lib.check(rc, "dg_fps_coords_large")
+    return (coords, inds) if return_inds else coords
+
+
+def fps_coords_large(depth, feat_hw, n_samples, return_inds=False):
+    """fps_coords on pooled grids of up to 65536 positions (dg_fps_coords_large; the grid of the loss under cfg.use_true_labels is
+    the labels'): depth (B,1,H,W) on GPU -> coords (B,S,S,2) in [-1,1).  Equal to fps_coords, bit for bit, on every grid both take."""
+    return _fps_large(_f32c(depth, "depth"), None, feat_hw, n_samples, return_inds)
+
+
+def fps_coords_large_pair(depth, depth_pos, feat_hw, n_samples):
+    """The two calls of one step in one launch: -> coords (2B,S,S,2), rows [0,B) the anchors', [B,2B) the positives'."""
+    depth, depth_pos = _f32c(depth, "depth"), _f32c(depth_pos, "depth_pos")
+    if depth.shape != depth_pos.shape or depth.device != depth_pos.device:
+        raise ValueError(f"depthg_amd: depth {tuple(depth.shape)} on {depth.device} and depth_pos {tuple(depth_pos.shape)} on "
+                         f"{depth_pos.device} must match for the paired sampler")
+    return _fps_large(depth, depth_pos, feat_hw, n_samples, False)
+
+
+LABEL_ONEHOT_MAX_CHANNELS = 256
+
+
+def _label_map(label, name, n_classes, check):
+    """One label tensor as dg_label_onehot reads it: int64 (B,H,W) - or (B,1,H,W) -, contiguous; check: its range, on the host."""
+    if not isinstance(label, torch.Tensor) or label.dtype != torch.int64 or label.dim() not in (3, 4) or (label.dim() == 4 and label.shape[1] != 1):
+        raise ValueError(f"depthg_amd: `{name}` must be an int64 (B,H,W) or (B,1,H,W) tensor, got "
+                         f"{(label.dtype, tuple(label.shape)) if isinstance(label, torch.Tensor) else type(label).__name__}")
+    label = label.detach()
+    label = (label.squeeze(1) if label.dim() == 4 else label).contiguous()
+    if check and label.numel():
+        lo, hi = (int(v) for v in torch.aminmax(label))          # (one host sync; check=False launches without it)
+        if lo < -1 or hi > n_classes - 1:
+            bad = lo if lo < -1 else hi
+            raise ValueError(f"depthg_amd: `{name}` holds the value {bad}, outside [-1, {n_classes - 1}] (n_classes = {n_classes}): "
+                             "the reference's F.one_hot(label + 1, n_classes + 1) raises on it")
+    return label
+
+
+def label_onehot(label, n_classes, label_pos=None, check=True):
+    """one_hot_feats(label + 1, n_classes + 1) of the reference (src/train_segmentation.py:219-225; src/utils.py:64-65) - the
+    correlation loss's signal under cfg.use_true_labels: int64 labels (B,H,W) or (B,1,H,W) with values in [-1, n_classes - 1] ->
+    fp32 (B, n_classes + 1, H, W), channel label + 1 of a pixel 1.0 and every other 0.0.  With `label_pos` (the same shape): the pair
+    (signal, signal_pos), two views of ONE (2B, ...) tensor written by ONE launch (dg_label_onehot: the labels are read in place, no
+    int64 one-hot tensor and no permuted copy exist).  On CPU tensors: the reference's torch chain.
+    check=True reads the labels' range on the host first (one sync) and raises ValueError naming the offending value, where the
+    reference's F.one_hot would raise.  check=False launches without that read (a step recorded in a graph): THE CALLER then vouches
+    for the range - the kernel writes an all-zero pixel for a label outside it, where the reference would have raised."""
+    n_classes = int(n_classes)
+    if n_classes < 0 or n_classes + 1 > LABEL_ONEHOT_MAX_CHANNELS:
+        raise ValueError(f"depthg_amd: label_onehot serves 1 <= n_classes + 1 <= {LABEL_ONEHOT_MAX_CHANNELS}, got n_classes = {n_classes}")
+    label = _label_map(label, "label", n_classes, check)
+    if label_pos is not None:
+        label_pos = _label_map(label_pos, "label_pos", n_classes, check)
+        if label_pos.shape != label.shape or label_pos.device != label.device:
+            raise ValueError(f"depthg_amd: label {tuple(label.shape)} on {label.device} and label_pos {tuple(label_pos.shape)} on "
+                             f"{label_pos.device} must match")
+    B, H, W = label.shape
+    if not label.is_cuda:
+        chain = lambda t: torch.nn.functional.one_hot(t + 1, n_classes + 1).permute(0, 3, 1, 2).to(torch.float32)
+        if not check:          # (F.one_hot raises on an out-of-range value; the kernel's contract is an all-zero pixel)
+            chain = lambda t: (t.unsqueeze(1) + 1 == torch.arange(n_classes + 1).view(1, -1, 1, 1)).to(torch.float32)
+        return chain(label) if label_pos is None else (chain(label), chain(label_pos))
+    if B < 1 or H < 1 or W < 1:
+        raise ValueError(f"depthg_amd: label_onehot needs a non-empty label map, got {tuple(label.shape)}")
+    nB = B if label_pos is None else 2 * B
+    out = _empty((nB, n_classes + 1, H, W), torch.float32, label.device)
+    rc = _lib.load().dg_label_onehot(_ptr(label), _ptr(label_pos), B, n_classes, H, W, _ptr(out), _stream(label.device))
+    _lib.check(rc, "dg_label_onehot")
+    return out if label_pos is None else (out[:B], out[B:])
+
+
 def _fps_feats_operand(t, name):
     """The feature-aware sampler reads its maps in place: a contiguous fp32 GPU tensor, or a refusal by name."""
     _on_gpu(t, name)

@@ -29,6 +29,7 @@ from typing import Dict, Optional
 import torch
 import torch.nn as nn
 
+from . import ops
 from .aug_loss import aug_alignment_loss
 from .augment import IMAGENET_MEAN, IMAGENET_STD, augment_batch, draw_augment_params
 from .crf_loss import ContrastiveCRFLoss
@@ -184,6 +185,18 @@ class UnsupervisedSegmenter(nn.Module):
                              "DepthContrastiveCorrelationLoss returns six values and has no depth term; set "
                              "cfg.depth_feat_correlation_loss = False")
 
+    @staticmethod
+    def _refuse_true_labels_combinations(cfg, batch):
+        """cfg.use_true_labels with a batch or a configuration its signal cannot be formed for (asked in front of a step's first launch)."""
+        if "label_pos" not in batch:
+            raise KeyError("training_step: cfg.use_true_labels needs batch['label_pos'] (the positive image's labels are its signal, "
+                           "src/train_segmentation.py:219-225); use a dataset that hands them out (data.ContrastiveBatches does) or set "
+                           "cfg.use_true_labels = False")
+        if getattr(cfg, "use_depth_only_intra", False):
+            raise ValueError("depthg_amd: cfg.use_true_labels cannot be combined with cfg.use_depth_only_intra: DepthContrastiveCorrelationLoss "
+                             "correlates the backbone's and the depth-augmented features, and the one-hot labels would replace only one of "
+                             "them; set one of the two keys to False")
+
     def forward(self, x):
         return self.net(x)[1]                                                          # :160-167
 
@@ -285,6 +298,8 @@ class UnsupervisedSegmenter(nn.Module):
             self._refuse_depth_arch_combinations(self.cfg)
         if self.depth_only_intra:
             self._refuse_depth_only_intra_combinations(self.cfg)
+        if getattr(self.cfg, "use_true_labels", False):
+            self._refuse_true_labels_combinations(self.cfg, batch)
         if not plan.aug:
             return batch
         # cfg.dg_gpu_augment (build-side key, absent or False by default): a batch without the augmented view gets it here - parameters drawn
@@ -350,17 +365,25 @@ class UnsupervisedSegmenter(nn.Module):
         salience = batch["mask"].to(torch.float32).squeeze(1) if plan.use_salience else None         # :233-238
         salience_pos = batch["mask_pos"].to(torch.float32).squeeze(1) if plan.use_salience else None
         d_args = depths if plan.depth_term else (None, None)                                         # :242-292
+        signal, signal_pos = p.feats, p.feats_pos
         if plan.depth_only_intra:
             # :240-350 with the class of :133-134.  The reference's own call passes `depth=` / `depth_pos=` to parameters named
             # depth_aug_feats / depth_aug_feats_pos and raises a TypeError; this is the call the names ask for: the frozen
             # backbone's features (the featurizer's third output) as orig_feats, the depth-augmented ones (its first) as depth_aug_feats
             out = loss_fn(p.image_feat.detach(), p.image_feat_pos.detach(), salience, salience_pos, p.code, p.code_pos, p.feats, p.feats_pos)
         else:
-            out = loss_fn(p.feats, p.feats_pos, salience, salience_pos, p.code, p.code_pos, *d_args)
+            if getattr(self.cfg, "use_true_labels", False):
+                # :219-225: the one-hot ground-truth labels replace the frozen backbone's features as the loss's signal - the method's
+                # supervised upper bound; everything else in the step is unchanged.  Both maps from one HIP launch, at the labels' own
+                # resolution (ops.label_onehot; under cfg.dg_graph_safe without the host's look at the labels' range).  Read here: the
+                # step's plan does not carry the key.  Absent or False: nothing of this runs.
+                signal, signal_pos = ops.label_onehot(batch["label"], self.n_classes, batch["label_pos"],
+                                                      check=not getattr(self.cfg, "dg_graph_safe", False))
+            out = loss_fn(signal, signal_pos, salience, salience_pos, p.code, p.code_pos, *d_args)
         # :229-231, :298-301: every cfg.hist_freq steps the reference histograms the three un-reduced cd tensors - here one small
         # launch on the operands this call left in its workspace (in front of the LHP call, which runs the loss again)
         hists = loss_fn.cd_histograms(bins=plan.hist_bins) if plan.histograms else None
-        lhp_out = loss_fn(p.feats, p.feats_pos, salience, salience_pos, *lhp_codes, *d_args) if plan.lhp and plan.depth_term else None
+        lhp_out = loss_fn(signal, signal_pos, salience, salience_pos, *lhp_codes, *d_args) if plan.lhp and plan.depth_term else None
         total, logs = correspondence_total(self.cfg, out, lhp_out)                                   # :303-350
         if hists is not None:
             logs.update({"hist/" + k: v for k, v in hists.items()})

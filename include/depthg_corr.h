@@ -319,6 +319,37 @@ int dg_fps_feats_coords(const float* depth, const float* depth_pos, const float*
                         float* out_coords, int32_t* out_inds, void* workspace, size_t workspace_bytes, dg_stream_t stream);
 
 /*
+ * dg_fps_coords on pooled grids above its 4096 positions: 1 <= h*w <= 65536, one block per image.  Needed under cfg.use_true_labels,
+ * where the loss's signal - and so the grid farthest_point_sampling_depth pools the depth to (src/modules.py:1003) - has the labels'
+ * resolution (src/train_segmentation.py:219-225).  A thread keeps its points' pooled depth and running distance and rebuilds the
+ * point from the depth in every round with depth2points' operations (src/modules.py:985-996) in dg_fps_coords' order; rounds, ties
+ * (first arg-max) and the row-major output are dg_fps_coords': on a grid both entries accept the results are equal bit for bit.
+ * dg_fps_coords itself is unchanged.
+ *  depth, depth_pos, out_coords, out_inds : as dg_fps_coords
+ *  workspace : >= dg_fps_large_workspace_bytes(B,h,w) bytes, of (2B,h,w) with depth_pos - the pooled depth maps; not read, and may
+ *              be NULL, where the depth maps have the grid's own size (the pooling is then the identity and nothing is copied)
+ * Refused before any launch: a null or misaligned pointer, h*w > 65536, depth smaller than the grid, S*S > h*w, S*S > 8192 (the
+ * selection order lives in LDS), a pooled row whose depth rows exceed 64 KB of LDS, a workspace too small for the pooling.
+ */
+size_t dg_fps_large_workspace_bytes(int32_t B, int32_t h, int32_t w);
+int dg_fps_coords_large(const float* depth, const float* depth_pos, int32_t B, int32_t depth_h, int32_t depth_w,
+                        int32_t h, int32_t w, int32_t S, float* out_coords, int32_t* out_inds,
+                        void* workspace, size_t workspace_bytes, dg_stream_t stream);
+
+/*
+ * The supervised signal of the correlation loss (cfg.use_true_labels): one_hot_feats(label + 1, n_classes + 1)
+ * (src/train_segmentation.py:219-225; src/utils.py:64-65) without the int64 (B,H,W,K) tensor and its permuted copy.
+ *  label     : int64 (B,H,W), values in [-1, n_classes - 1], read in place; label_pos: the same shape, or NULL
+ *  out       : fp32 (B, n_classes + 1, H, W) - (2B, ...) with label_pos, rows [0,B) from label, [B,2B) from label_pos; channel
+ *              label + 1 of a pixel is 1.0, every other 0.0; every element written exactly once (no atomics, no LDS)
+ * A label outside the range selects no channel (an all-zero pixel); the reference's F.one_hot raises there - the caller checks.
+ * Refused before the launch: a null pointer, labels not 8-byte or out not 4-byte aligned, n_classes + 1 > 256, 2B > 65535,
+ * H*W > 2^24.
+ */
+int dg_label_onehot(const int64_t* label, const int64_t* label_pos, int32_t B, int32_t n_classes, int32_t H, int32_t W, float* out,
+                    dg_stream_t stream);
+
+/*
  * Salience-guided sample locations (replaces sample_nonzero_locations, src/modules.py:1191-1204, the cfg.use_salience
  * branch of the coordinate draw, :1290-1297): every position gets a uniformly drawn non-zero pixel of its image's
  * salience map (torch.nonzero = row-major order), returned as the reference does: both pixel coordinates divided by
