@@ -65,6 +65,7 @@ SIGNATURES = {
     "dg_fps_large_workspace_bytes": (_SZ, [i32] * 3),
     "dg_fps_coords_large": (_I, [vp, vp] + [i32] * 6 + [vp, vp, vp, _SZ, vp]),
     "dg_label_onehot": (_I, [vp, vp] + [i32] * 4 + [vp, vp]),
+    "dg_sample_rows": (_I, [vp] * 3 + [i32] * 8 + [vp, vp]),
     "dg_salience_coords": (_I, [vp] + [i32] * 4 + [vp] * 4),
     "dg_simple_depth_coords": (_I, [vp] + [i32] * 6 + [vp] * 4),
     # metrics, LHP, nearest neighbours

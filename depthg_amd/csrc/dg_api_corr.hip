@@ -12,7 +12,8 @@ extern "C" int dg_prof_main_span(void* span) { g_prof_span = static_cast<unsigne
 // per descriptor by make_plan.  Every job builder and every launch below reads it; none of them derives a route again.
 enum class Prep { Small, Dense, General };              // operand preparation: the fused small grid (dg_small.hip: sampled rows -> ONE launch) /
                                                         // the dense identity grid straight from NCHW / general coordinates into blobs
-enum class Sampler { Plane, ChannelLast };              // sample(): k_plane_sample straight from NCHW / channel-last copies of the maps + a gather
+enum class Sampler { Plane, ChannelLast, Direct };      // sample(): k_plane_sample straight from NCHW / channel-last copies of the maps + a gather /
+                                                        // k_sample_direct: the four taps read in place (feature maps above 16384 positions)
 enum class MainKernel { Small, Corr2, CorrMain };       // the fused correlation launch: k_corr_small / k_corr2 (gradient passes of the
                                                         // shapes dg_corr2_shape_supported names) / k_corr_main (everything else)
 enum class Depth { None, Job, GsBlocks, GsOwnLaunch };   // the depth term of the blob kernels: off (or inside k_corr_small) / a job of the fused launch
@@ -98,6 +99,8 @@ struct Plan {
     bool small() const { return prep == Prep::Small; }
     bool dense() const { return prep == Prep::Dense; }
     bool plane() const { return sampler == Sampler::Plane; }
+    bool direct() const { return sampler == Sampler::Direct; }
+    bool sampled_rows() const { return sampler != Sampler::ChannelLast; }      // the sampler itself leaves rows per operand (batch maps applied)
     bool has_masks() const { return masks != Masks::None; }
     bool depth_in_gs() const { return depth_run == Depth::GsBlocks || depth_run == Depth::GsOwnLaunch; }
     bool dense_masks() const { return masks == Masks::DenseRaw || masks == Masks::DenseSplit; }
@@ -119,6 +122,7 @@ struct Plan {
 
 static inline float* f32(char* ws, size_t off) { return reinterpret_cast<float*>(ws + off); }
 
+#define DG_CHANNEL_LAST_MAX_POS 16384    // positions of a map the channel-last route copies (feature maps above it: Sampler::Direct; code maps: refused)
 #define FOLD_STASH_OFF (5 * 1024)        // k_corr2<24, 6, 5>: code k-step 5 of the C part (channels 80 .. 95: padding for D <= 80)
 
 // the pair-set and operand tables, and from them the grouping of the ragged row blocks
@@ -181,18 +185,21 @@ static int make_plan(const dg_corr_desc* d, Plan& p, bool intra_feats = false) {
         if (d->C > 768) return fail(DG_ERR_UNSUPPORTED, "dg_corr_forward_intra_feats: C=%d > 768 feature channels are not served", d->C);
         if (d->n_neg > DG_MAX_NEG - 1)
             return fail(DG_ERR_UNSUPPORTED, "dg_corr_forward_intra_feats: n_neg=%d > %d (one operand slot holds the intra features)", d->n_neg, DG_MAX_NEG - 1);
+        if (d->h > 0 && d->w > 0 && (size_t)d->h * d->w > DG_CHANNEL_LAST_MAX_POS)
+            return fail(DG_ERR_UNSUPPORTED, "dg_corr_forward_intra_feats: feature map %dx%d too large (max %d positions)", d->h, d->w, DG_CHANNEL_LAST_MAX_POS);
     }
     if (d->B < 1 || d->C < 1 || d->D < 1 || d->h < 1 || d->w < 1 || d->S < 1)
         return fail(DG_ERR_INVALID, "non-positive dimension in descriptor");
     if (d->n_neg < 0 || d->n_neg > DG_MAX_NEG) return fail(DG_ERR_UNSUPPORTED, "n_neg=%d outside [0,%d]", d->n_neg, DG_MAX_NEG);
     if (d->C > 8192) return fail(DG_ERR_UNSUPPORTED, "C=%d > 8192 feature channels not supported", d->C);
     if (d->D > 128) return fail(DG_ERR_UNSUPPORTED, "D=%d > 128 code channels not supported", d->D);
-    if ((size_t)d->h * d->w > 16384) return fail(DG_ERR_UNSUPPORTED, "feature map %dx%d too large", d->h, d->w);
+    if ((size_t)d->h * d->w > DG_SAMPLE_DIRECT_MAX_POS)
+        return fail(DG_ERR_UNSUPPORTED, "feature map %dx%d too large (max %d positions)", d->h, d->w, DG_SAMPLE_DIRECT_MAX_POS);
     if (d->code_h < 0 || d->code_w < 0 || (d->code_h == 0) != (d->code_w == 0))
         return fail(DG_ERR_INVALID, "code_h=%d, code_w=%d: both zero (code maps of the feature maps' size) or both positive", d->code_h, d->code_w);
     p.B = d->B; p.C = d->C; p.D = d->D; p.h = d->h; p.w = d->w; p.S = d->S; p.N = d->n_neg;
     p.hc = d->code_h ? d->code_h : d->h; p.wc = d->code_w ? d->code_w : d->w;
-    if ((size_t)p.hc * p.wc > 16384) return fail(DG_ERR_UNSUPPORTED, "code map %dx%d too large", p.hc, p.wc);
+    if ((size_t)p.hc * p.wc > DG_CHANNEL_LAST_MAX_POS) return fail(DG_ERR_UNSUPPORTED, "code map %dx%d too large", p.hc, p.wc);
     const bool same_maps = p.hc == p.h && p.wc == p.w;
     p.Sh = (d->flags & DG_LINE_GRID) ? 1 : d->S;      // sample grid: Sh rows x S columns
     p.P = p.Sh * d->S;
@@ -240,9 +247,14 @@ static int make_plan(const dg_corr_desc* d, Plan& p, bool intra_feats = false) {
     // channel-last copies of the whole maps
     // (code maps of another size than the feature maps - the FeaturePyramidNet contract - take the channel-last gather path)
     const bool rows = !ident && same_maps && (size_t)p.nops * p.P <= 2 * HW && HW <= 1024 && B <= 32767;
-    p.sampler = rows ? Sampler::Plane : Sampler::ChannelLast;
-    for (int i = 0; i < 2; ++i) { p.nhwc_f[i] = take(rows ? 0 : B * HW * p.C4 * 4); p.nhwc_c[i] = take(rows ? 0 : B * HWc * p.D4 * 4); }
-    const bool want_rows = rows || p.small();      // (the fused small-grid kernel reads sampled rows whichever sampler wrote them)
+    // feature maps above the channel-last route's limit (cfg.use_true_labels: the signal has the labels' resolution): the taps are read
+    // in place (k_sample_direct) - the sample grid touches a few percent of such a map, and a copy of it is hundreds of megabytes
+    const bool direct = !ident && HW > DG_CHANNEL_LAST_MAX_POS;
+    p.sampler = rows ? Sampler::Plane : (direct ? Sampler::Direct : Sampler::ChannelLast);
+    if (direct && B > 65535) return fail(DG_ERR_UNSUPPORTED, "B=%d > 65535 images on a feature map above %d positions", p.B, DG_CHANNEL_LAST_MAX_POS);
+    const bool copies = p.sampler == Sampler::ChannelLast;
+    for (int i = 0; i < 2; ++i) { p.nhwc_f[i] = take(copies ? B * HW * p.C4 * 4 : 0); p.nhwc_c[i] = take(copies ? B * HWc * p.D4 * 4 : 0); }
+    const bool want_rows = rows || direct || p.small();      // (the fused small-grid kernel reads sampled rows whichever sampler wrote them)
     // (the fused small-grid kernel takes bf16 feature rows of up(C, 128) channels - whole chunks; the multi-launch path fp32 rows of C4)
     const size_t frow = p.small() ? (size_t)up(p.C, 128) * 2 : (size_t)p.C4 * 4;
     for (int i = 0; i < p.nops; ++i) { p.rows_f[i] = take(want_rows ? B * p.P * frow : 0); p.rows_c[i] = take(want_rows ? B * p.P * p.D4 * 4 : 0); }
@@ -561,6 +573,25 @@ static int plane_sample(const Fwd& c, bool bf16_rows) {
     return DG_OK;
 }
 
+// sample() with the taps read in place (Sampler::Direct): rows per operand as plane_sample leaves them, the code maps - of their own
+// size - as further jobs of the one launch
+static int direct_sample(const Fwd& c, bool bf16_rows) {
+    const Plan& p = c.p;
+    DgSampleDirectArgs g;
+    memset(&g, 0, sizeof(g));
+    int nj = 0;
+    for (int o = 0; o < p.nops; ++o) {
+        const int srcsel = p.ops[o].srcsel;
+        g.src[nj] = srcsel ? c.feats_pos : c.feats; g.coords[nj] = c.coords(o); g.srcidx[nj] = c.op_map(o); g.rows[nj] = f32(c.ws, p.rows_f[o]);
+        g.K[nj] = p.C; g.Kout[nj] = bf16_rows ? (int)up(p.C, 128) : p.C4; g.as_bf16[nj] = bf16_rows ? 1 : 0; g.h[nj] = p.h; g.w[nj] = p.w; ++nj;
+        g.src[nj] = srcsel ? c.code_pos : c.code; g.coords[nj] = c.coords(o); g.srcidx[nj] = c.op_map(o); g.rows[nj] = f32(c.ws, p.rows_c[o]);
+        g.K[nj] = p.D; g.Kout[nj] = p.D4; g.as_bf16[nj] = 0; g.h[nj] = p.hc; g.w[nj] = p.wc; ++nj;
+    }
+    g.njobs = nj; g.B = p.B; g.S = p.S; g.Sh = p.Sh; g.P = p.P;
+    DG_HIP(dg_launch_sample_direct(g, c.stream));
+    return DG_OK;
+}
+
 // channel-last copies of the four maps (the gathers read whole channel vectors per tap)
 static int transpose_maps(const Fwd& c) {
     const Plan& p = c.p;
@@ -602,6 +633,8 @@ static int forward_small(const Fwd& c) {
     DG_HIP(dg_launch_pre_general(q, c.stream));
     if (p.plane()) {
         if (int rc = plane_sample(c, true)) return rc;
+    } else if (p.direct()) {
+        if (int rc = direct_sample(c, true)) return rc;
     } else {
         // code maps of another size than the feature maps (the FeaturePyramidNet contract) or maps beyond the plane sampler's LDS:
         // channel-last copies, then a bilinear gather into the same rows
@@ -681,7 +714,7 @@ static int fwd_operands_general(Fwd& c) {
     pre_late.count = 0;
     q.depth = nullptr; q.taps = nullptr;
     DG_HIP(dg_launch_pre_general(q, c.stream));
-    if (int rc = p.plane() ? plane_sample(c, false) : transpose_maps(c)) return rc;
+    if (int rc = p.plane() ? plane_sample(c, false) : (p.direct() ? direct_sample(c, false) : transpose_maps(c))) return rc;
     DgGatherArgs g;
     memset(&g, 0, sizeof(g));
     g.B = p.B; g.S = p.S; g.Sh = p.Sh; g.P = p.P; g.Ppad = p.Ppad; g.KF = p.KF; g.KD = p.KD;
@@ -689,19 +722,19 @@ static int fwd_operands_general(Fwd& c) {
     for (int o = 0; o < p.nopx(); ++o) {
         // (the intra feature operand: its own feature rows / map, and operand 0's code once more as the C part of its blobs)
         const int srcsel = p.ops[o].srcsel;
-        const int64_t* idx = p.plane() ? nullptr : c.op_map(o);       // (the plane sampler's rows are sampled through the batch maps already)
+        const int64_t* idx = p.sampled_rows() ? nullptr : c.op_map(o);       // (the samplers' rows are sampled through the batch maps already)
         DgGatherJob& f = g.jobs[nj++];
-        f.src = p.plane() ? f32(c.ws, p.rows_f[o]) : f32(c.ws, o == p.xop ? p.nhwc_x : p.nhwc_f[srcsel]); f.coords = c.coords(o); f.srcidx = idx;
+        f.src = p.sampled_rows() ? f32(c.ws, p.rows_f[o]) : f32(c.ws, o == p.xop ? p.nhwc_x : p.nhwc_f[srcsel]); f.coords = c.coords(o); f.srcidx = idx;
         f.blob = c.ws + p.op[o]; f.inv_norm = nullptr; f.colpart = f32(c.ws, p.colpart[o]);
         f.ext_inv = c.feat_inv ? c.feat_inv + (size_t)o * p.B * p.P : nullptr;
         f.K = p.C; f.K4 = p.C4; f.Kpad = p.KF; f.is_code = 0; f.h = p.h; f.w = p.w;
         DgGatherJob& k = g.jobs[nj++];
-        k.src = p.plane() ? f32(c.ws, p.rows_c[o]) : f32(c.ws, p.nhwc_c[srcsel]); k.coords = c.coords(o); k.srcidx = idx;
+        k.src = p.sampled_rows() ? f32(c.ws, p.rows_c[o]) : f32(c.ws, p.nhwc_c[srcsel]); k.coords = c.coords(o); k.srcidx = idx;
         k.blob = c.ws + p.op[o]; k.inv_norm = f32(c.ws, p.inv[o]); k.colpart = f32(c.ws, p.ccolpart[o]);
         k.K = p.D; k.K4 = p.D4; k.Kpad = p.KD; k.is_code = 1; k.h = p.hc; k.w = p.wc;
     }
     g.njobs = nj;
-    g.direct = p.plane() ? 1 : 0;
+    g.direct = p.sampled_rows() ? 1 : 0;
     // exact clamp masks of the small sample grids: the sign of every fp32 code dot product from the sampled rows
     // (k_plane_sample's, like the gather's input) - extra blocks of the gather launch (its own launch until round 4)
     if (p.masks == Masks::Sampled) cd_mask_args(c, p.rows_c, g.cd);
@@ -905,6 +938,8 @@ extern "C" int dg_corr_forward_extnorm(const dg_corr_desc* desc, const float* or
                                        const float* coords1, const float* coords2, const int64_t* perms, const float* feat_inv,
                                        float* out_scalars, void* workspace, size_t workspace_bytes, dg_stream_t stream_) {
     if (!feat_inv) return fail(DG_ERR_INVALID, "dg_corr_forward_extnorm: feat_inv is null");
+    if (desc && desc->h > 0 && desc->w > 0 && (size_t)desc->h * desc->w > DG_CHANNEL_LAST_MAX_POS)
+        return fail(DG_ERR_UNSUPPORTED, "dg_corr_forward_extnorm: feature map %dx%d too large (max %d positions)", desc->h, desc->w, DG_CHANNEL_LAST_MAX_POS);
     FwdInputs in{orig_feats, orig_feats_pos, orig_code, orig_code_pos, depth, coords1, coords2, perms};
     in.feat_inv = feat_inv;
     return corr_forward_impl(desc, in, out_scalars, workspace, workspace_bytes, stream_);
@@ -913,7 +948,29 @@ extern "C" int dg_corr_forward_extnorm(const dg_corr_desc* desc, const float* or
 extern "C" int dg_sampled_sumsq(int32_t B, int32_t C, int32_t h, int32_t w, int32_t S, int32_t line_grid, const float* feats,
                                 const float* coords, const int64_t* srcidx, int32_t accumulate, float* out, dg_stream_t stream_) {
     if (B < 1 || C < 1 || h < 1 || w < 1 || S < 1 || !feats || !coords || !out) return fail(DG_ERR_INVALID, "dg_sampled_sumsq: bad arguments");
+    if ((size_t)h * w > DG_CHANNEL_LAST_MAX_POS)
+        return fail(DG_ERR_UNSUPPORTED, "dg_sampled_sumsq: feature map %dx%d too large (max %d positions)", h, w, DG_CHANNEL_LAST_MAX_POS);
     DG_HIP(dg_launch_sampled_sumsq(feats, coords, srcidx, out, B, C, h, w, S, line_grid ? 1 : S, accumulate ? 1 : 0, static_cast<hipStream_t>(stream_)));
+    return DG_OK;
+}
+
+extern "C" int dg_sample_rows(const float* map, const float* coords, const int64_t* srcidx, int32_t B, int32_t K, int32_t h, int32_t w,
+                              int32_t S, int32_t Sh, int32_t Kout, int32_t as_bf16, void* out, dg_stream_t stream_) {
+    if (!map || !coords || !out) return fail(DG_ERR_INVALID, "dg_sample_rows: null pointer");
+    if (((uintptr_t)map | (uintptr_t)coords | (uintptr_t)out) & 3) return fail(DG_ERR_INVALID, "dg_sample_rows: map, coords and out must be 4-byte aligned");
+    if ((uintptr_t)srcidx & 7) return fail(DG_ERR_INVALID, "dg_sample_rows: srcidx must be 8-byte aligned");
+    if (B < 1 || K < 1 || h < 1 || w < 1 || S < 1 || Sh < 1)
+        return fail(DG_ERR_INVALID, "dg_sample_rows: non-positive dimension (B=%d K=%d map %dx%d grid %dx%d)", B, K, h, w, Sh, S);
+    if ((size_t)h * w > DG_SAMPLE_DIRECT_MAX_POS)
+        return fail(DG_ERR_UNSUPPORTED, "dg_sample_rows: map %dx%d too large (max %d positions)", h, w, DG_SAMPLE_DIRECT_MAX_POS);
+    if (Kout < K || Kout % 4 != 0) return fail(DG_ERR_INVALID, "dg_sample_rows: Kout=%d must be a multiple of 4 and at least K=%d", Kout, K);
+    if (B > 65535 || (int64_t)S * Sh > (1 << 24)) return fail(DG_ERR_UNSUPPORTED, "dg_sample_rows: B=%d (max 65535) or a grid of %dx%d (max 2^24 positions)", B, Sh, S);
+    DgSampleDirectArgs g;
+    memset(&g, 0, sizeof(g));
+    g.src[0] = map; g.coords[0] = coords; g.srcidx[0] = srcidx; g.rows[0] = out;
+    g.K[0] = K; g.Kout[0] = Kout; g.as_bf16[0] = as_bf16 ? 1 : 0; g.h[0] = h; g.w[0] = w;
+    g.njobs = 1; g.B = B; g.S = S; g.Sh = Sh; g.P = S * Sh;
+    DG_HIP(dg_launch_sample_direct(g, static_cast<hipStream_t>(stream_)));
     return DG_OK;
 }
 

@@ -382,6 +382,19 @@ struct DgGatherRowsArgs {   // k_gather_rows: sample() of channel-last maps into
     int32_t njobs, B, S, Sh, P;
 };
 
+// k_sample_direct (dg_sample_direct.hip): sample() of NCHW maps, four taps per (position, channel) read in place - no channel-last
+// copy, no LDS planes.  The sampler of feature maps above 16384 positions (Sampler::Direct) and the kernel behind dg_sample_rows.
+#define DG_SAMPLE_DIRECT_MAX_POS 65536
+struct DgSampleDirectArgs {
+    const float* src[2 * (DG_MAX_NEG + 2)];      // NCHW fp32 (B, K, h, w)
+    const float* coords[2 * (DG_MAX_NEG + 2)];   // [B][S][Sh][2]
+    const int64_t* srcidx[2 * (DG_MAX_NEG + 2)]; // batch map or null
+    void* rows[2 * (DG_MAX_NEG + 2)];            // [B][P][Kout]: fp32, or bf16 when as_bf16; channels K..Kout-1 zero
+    int32_t K[2 * (DG_MAX_NEG + 2)], h[2 * (DG_MAX_NEG + 2)], w[2 * (DG_MAX_NEG + 2)];
+    int32_t Kout[2 * (DG_MAX_NEG + 2)], as_bf16[2 * (DG_MAX_NEG + 2)];
+    int32_t njobs, B, S, Sh, P;
+};
+
 struct DgDenseArgs {        // identity-grid operand preparation (k_prep_dense)
     const float* src[2];     // feats NCHW fp32 (B,K,h,w): orig_feats, orig_feats_pos
     const float* code[2];    // code NCHW fp32 (B,D,h,w): orig_code, orig_code_pos
@@ -642,6 +655,7 @@ bool dg_small_supported(int Ppad, int KD);
 hipError_t dg_launch_corr_small(const struct DgSmallArgs& a, hipStream_t s);       // the fused kernel; the call's scalars need ...
 hipError_t dg_launch_small_finish(const struct DgSmallArgs& a, hipStream_t s);     // ... this one-wave launch behind it
 hipError_t dg_launch_gather_rows(const struct DgGatherRowsArgs& a, hipStream_t s);
+hipError_t dg_launch_sample_direct(const struct DgSampleDirectArgs& a, hipStream_t s);
 hipError_t dg_launch_rand_coords_state(unsigned long long* state, float* out, int n, hipStream_t s, float keep_p = -1.f);
 // (B images in all; the first Ba from `depth`, the rest from `depth_b`)
 hipError_t dg_launch_fps(const float* depth, const float* depth_b, int Ba, int B, int H, int W, int h, int w, int S, float factor,

@@ -997,6 +997,41 @@ def label_onehot(label, n_classes, label_pos=None, check=True):
     return out if label_pos is None else (out[:B], out[B:])
 
 
+def sample_rows(t, coords, srcidx=None, bf16=False):
+    """sample() of the reference (src/modules.py:822-825) as rows: t (B,K,h,w) fp32, coords (B,S,Sh,2) in [-1,1] -> (B, Sh*S, Kout),
+    row p = i*S + j of image n = t[srcidx[n]] (srcidx None: t[n]) sampled at coords[n, j, i], channels K..Kout-1 zero.  fp32 rows with
+    Kout = K rounded up to 4, or (bf16=True) bfloat16 rows with Kout = K rounded up to 128 - what the loss's kernels read.  On the GPU
+    dg_sample_rows: the four taps of every element read in place from the NCHW map (maps of up to 65536 positions; no copy of the map
+    is made).  On CPU tensors: F.grid_sample with the reference's arguments, permuted to rows."""
+    if not isinstance(t, torch.Tensor) or t.dim() != 4 or not isinstance(coords, torch.Tensor) or coords.dim() != 4 or coords.shape[-1] != 2 \
+            or coords.shape[0] != t.shape[0]:
+        raise ValueError(f"depthg_amd: sample_rows takes a (B,K,h,w) map and (B,S,Sh,2) coordinates, got "
+                         f"{tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__} and "
+                         f"{tuple(coords.shape) if isinstance(coords, torch.Tensor) else type(coords).__name__}")
+    B, K, h, w = t.shape
+    S, Sh = int(coords.shape[1]), int(coords.shape[2])
+    if min(B, K, h, w, S, Sh) < 1:
+        raise ValueError(f"depthg_amd: sample_rows needs non-empty operands, got a map {tuple(t.shape)} and coordinates {tuple(coords.shape)}")
+    if srcidx is not None and (srcidx.dtype != torch.int64 or tuple(srcidx.shape) != (B,) or srcidx.device != t.device):
+        raise ValueError(f"depthg_amd: `srcidx` must be an int64 ({B},) tensor on {t.device}, got {srcidx.dtype} {tuple(srcidx.shape)} on {srcidx.device}")
+    if coords.device != t.device:
+        raise ValueError(f"depthg_amd: `coords` lives on {coords.device}, the map on {t.device}")
+    Kout = (K + 127) // 128 * 128 if bf16 else (K + 3) // 4 * 4
+    if not t.is_cuda:
+        src = t.detach().to(torch.float32)
+        src = src if srcidx is None else src[srcidx]
+        rows = torch.nn.functional.grid_sample(src, coords.detach().to(torch.float32).permute(0, 2, 1, 3), padding_mode="border",
+                                               align_corners=True).permute(0, 2, 3, 1).reshape(B, Sh * S, K)
+        rows = torch.nn.functional.pad(rows, (0, Kout - K))
+        return rows.to(torch.bfloat16) if bf16 else rows
+    t, coords = _f32c(t, "t"), _f32c(coords, "coords")
+    srcidx = srcidx.contiguous() if srcidx is not None else None
+    out = _empty((B, Sh * S, Kout), torch.bfloat16 if bf16 else torch.float32, t.device)
+    rc = _lib.load().dg_sample_rows(_ptr(t), _ptr(coords), _ptr(srcidx), B, K, h, w, S, Sh, Kout, 1 if bf16 else 0, _ptr(out), _stream(t.device))
+    _lib.check(rc, "dg_sample_rows")
+    return out
+
+
 def _fps_feats_operand(t, name):
     """The feature-aware sampler reads its maps in place: a contiguous fp32 GPU tensor, or a refusal by name."""
     _on_gpu(t, name)

@@ -350,6 +350,24 @@ int dg_label_onehot(const int64_t* label, const int64_t* label_pos, int32_t B, i
                     dg_stream_t stream);
 
 /*
+ * The reference's sample() (src/modules.py:822-825: F.grid_sample(t, coords.permute(0, 2, 1, 3), padding_mode='border',
+ * align_corners=True), bilinear) as rows, the four taps of every (position, channel) read in place from the NCHW map: no
+ * channel-last copy, no LDS.  It is the sampler dg_corr_forward runs on feature maps above 16384 and up to 65536 positions (the
+ * label-size signal of cfg.use_true_labels), behind an entry of its own for maps of 1 to 65536 positions.
+ *  map      : fp32 (B,K,h,w)           coords : fp32 (B,S,Sh,2), (x, y) in [-1, 1]; values outside are clamped to the border
+ *  srcidx   : int64 (B) or NULL: image n is sampled from map[srcidx[n]] at coords[n] (the negatives' batch maps); an entry outside
+ *             [0, B) is the caller's error and is clamped into it
+ *  out      : (B, Sh*S, Kout) rows, position p = i*S + j sampled at coords[n][j][i]; fp32, or bf16 with as_bf16 != 0; channels
+ *             K..Kout-1 are zero.  Every element is written exactly once (no atomics): two calls give equal bits.
+ * Tap arithmetic: x = ((c + 1) / 2) * (w - 1), clamped to [0, w - 1], floor, the four weight products with the weights of taps
+ * beyond the border zeroed, then a0 * w00 followed by three fused multiply-adds - the operations of every sampler of this library.
+ * Refused before the launch: a null map, coords or out; map, coords or out not 4-byte, srcidx not 8-byte aligned; a non-positive
+ * dimension; h*w > 65536; Kout < K or Kout % 4 != 0; B > 65535.
+ */
+int dg_sample_rows(const float* map, const float* coords, const int64_t* srcidx, int32_t B, int32_t K, int32_t h, int32_t w,
+                   int32_t S, int32_t Sh, int32_t Kout, int32_t as_bf16, void* out, dg_stream_t stream);
+
+/*
  * Salience-guided sample locations (replaces sample_nonzero_locations, src/modules.py:1191-1204, the cfg.use_salience
  * branch of the coordinate draw, :1290-1297): every position gets a uniformly drawn non-zero pixel of its image's
  * salience map (torch.nonzero = row-major order), returned as the reference does: both pixel coordinates divided by
